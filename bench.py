@@ -213,6 +213,69 @@ def tree_digests(tree, min_level=0):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_MAX_SAMPLE = 1 << 20
+DUMP_SAMPLE_SEED = 20260417
+_ENC_DTYPE = {1: "u1", 2: "<u2", 3: "<f4", 4: "<f8"}  # PCV_ENC_UINT8 .. PCV_ENC_FLOAT64: one .xyz component
+
+
+def dump_outputs(tree, directory):
+    """--dump-outputs: what the caller of a build receives, as .npy files under `directory`, every value exact:
+      meta.npy         f64 [resolution, bbox_min xyz, bbox_max xyz]
+      nodes.npy        f64 one row per node in the library's (level, index) order: id_high and id_low as 32-bit halves
+                       (hi, lo, hi, lo), num_points, level, encoding, cube_min xyz, cube_edge, xyz_offset, point_offset
+      point_index.npy  f64 a fixed, seeded sample of the points (at most DUMP_MAX_SAMPLE): positions in the node-contiguous
+                       point order of the .rgb blob, ascending
+      xyz.npy          f64 [sample, 3] those points' stored .xyz values (u8 / u16 fixed point, f32 or f64, per the node's encoding)
+      rgb.npy          f32 [sample, 3] their stored .rgb bytes
+    The sample depends on the number of points alone, so two builds given the same cloud dump the same points."""
+    import ctypes as C
+    import numpy as np
+
+    def node_bytes(i, which):
+        ptr, ln = C.c_void_p(), C.c_uint64()
+        tree.ctx._check(tree.lib.pcv_octree_node_data(tree.handle, i, which, C.byref(ptr), C.byref(ln)))
+        return np.frombuffer((C.c_uint8 * ln.value).from_address(ptr.value), np.uint8) if ln.value else np.zeros(0, np.uint8)
+
+    meta = tree.meta()
+    m = tree.num_nodes
+    rows = np.zeros((m, 13), dtype=np.float64)
+    for i in range(m):
+        nd = tree.node(i)
+        rows[i] = (nd.id_high >> 32, nd.id_high & 0xFFFFFFFF, nd.id_low >> 32, nd.id_low & 0xFFFFFFFF, nd.num_points,
+                   nd.level, nd.encoding, *nd.cube_min, nd.cube_edge, nd.xyz_offset, nd.point_offset)
+    n = int(tree.num_points)
+    per_point = 8 + 3 * 8 + 3 * 4  # point_index + xyz + rgb
+    room = (DUMP_LIMIT_BYTES - rows.nbytes - 7 * 8 - 5 * 128) // per_point  # (128: .npy header)
+    if room < 1:
+        raise SystemExit(f"--dump-outputs: a node table of {m} nodes leaves no room for points under {DUMP_LIMIT_BYTES} bytes")
+    sample = min(n, DUMP_MAX_SAMPLE, room)
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=sample, replace=False)) if sample < n else np.arange(n)
+    xyz = np.zeros((sample, 3), dtype=np.float64)
+    rgb = np.zeros((sample, 3), dtype=np.float32)
+    counts, starts = rows[:, 4].astype(np.int64), rows[:, 12].astype(np.int64)
+    filled = np.nonzero(counts)[0]
+    filled = filled[np.argsort(starts[filled], kind="stable")]
+    owner = filled[np.searchsorted(starts[filled], idx, side="right") - 1]  # node holding each sampled point
+    for i in np.unique(owner):
+        sel = np.nonzero(owner == i)[0]
+        k = idx[sel] - starts[i]
+        assert np.all(k < counts[i]), i
+        enc = np.dtype(_ENC_DTYPE[int(rows[i, 6])])
+        b = node_bytes(int(i), 0)
+        assert b.size == counts[i] * 3 * enc.itemsize, (i, b.size)
+        xyz[sel] = b.view(enc).reshape(-1, 3)[k]
+        rgb[sel] = node_bytes(int(i), 1).reshape(-1, 3)[k]
+    out = {"meta": np.array([meta["resolution"], *meta["bbox_min"], *meta["bbox_max"]], dtype=np.float64), "nodes": rows,
+           "point_index": idx.astype(np.float64), "xyz": xyz, "rgb": rgb}
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(directory, name + ".npy"), arr)
+    total = sum(os.path.getsize(os.path.join(directory, name + ".npy")) for name in out)
+    assert total <= DUMP_LIMIT_BYTES, total
+    return {"dir": directory, "bytes": total, "nodes": m, "points": n, "sampled_points": sample, "sample_seed": DUMP_SAMPLE_SEED}
+
+
 def sharded_digests(result):
     """This rank's share of a sharded build in the same shape: its subtrees (level >= 2); the finished root / level-1
     nodes (every rank holds them after the top all-reduce) are added by rank 0 only."""
@@ -1159,7 +1222,15 @@ def main():
                          "bench_detail.json + a trimmed detail line + the <= 4 KB line of record")
     ap.add_argument("--fixed-bbox", action="store_true",
                     help="take the bounding box as an argument (K1 outside the step), as round 1 measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what the last timed build returned as DIR/<name>.npy (node table and a "
+                         "fixed, seeded sample of the points; <= 64 MB, see dump_outputs): single-GPU build path only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.config1 or args.query or args.only_intensity or args.virtual_ranks or args.gpus > 1 or
+                              args.force_sharded):
+        ap.error("--dump-outputs covers the single-GPU build path only")
     if args.no_kernel_events:
         args.kernel_events = "none"
 
@@ -1239,13 +1310,15 @@ def main():
             bmin, bmax = ctx.aabb_reduce(x, y, z)
             bbox = pcv.Aabb(bmin, bmax)
 
-        def step(details=True):
+        def step(details=True, keep=False):
             t = ctx.build(args.resolution, bbox, x, y, z, rgb,  # bbox None: K1 runs inside the step
                           single_chain=False if args.exact_pipeline else None)
             if details:  # (not inside the timed region: a dozen ctypes calls per step)
                 info["nodes"], info["stages"], info["build"] = t.num_nodes, t.stage_ms(), t.build_info()
                 info.setdefault("all_stages", []).append({k: round(v, 2) for k, v in info["stages"].items()})
             info.setdefault("gpu_ms", []).append(round(t.total_gpu_ms(), 3))
+            if keep:  # --dump-outputs: the caller reads the last timed build after the timed region
+                return t
             t.free()
     else:
         from point_cloud_viewer_amd import distributed as pdist
@@ -1280,14 +1353,22 @@ def main():
     barrier()
     t0 = time.perf_counter()
     step_marks = [t0]
-    for _ in range(args.steps):
-        step(False)
+    last = None
+    for s in range(args.steps):
+        if args.dump_outputs and s == args.steps - 1:
+            last = step(False, keep=True)
+        else:
+            step(False)
         step_marks.append(time.perf_counter())  # every step ends with a stream sync inside the library
     barrier()
     elapsed = time.perf_counter() - t0
     gc.enable()
     if rank == 0:
         box["right_after_timed_region"] = box_info()
+    if last is not None:
+        dumped = dump_outputs(last, args.dump_outputs)
+        last.free()
+        print(f"--dump-outputs: {json.dumps(dumped)}", file=sys.stderr, flush=True)
     per_step_ms = [round((b - a) * 1e3, 3) for a, b in zip(step_marks[:-1], step_marks[1:])]
     if dist is not None:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)

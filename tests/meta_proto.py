@@ -1,12 +1,17 @@
 """The reference's `Meta` schema (point_viewer_proto_rust/src/proto.proto:27-149) as a protobuf descriptor built at
 run time with the REAL protobuf runtime — an independent reader/writer for meta.pb (the library's own writer and
 reader are hand-rolled). Field numbers are restated here; `check_against_reference()` re-derives them from the
-reference's proto.proto when /root/reference is present (build container only)."""
+reference's proto.proto, and tests/golden/reference_proto_schema.json holds the digest of what that file declares
+(refresh: python tests/meta_proto.py <reference checkout>/point_viewer_proto_rust/src/proto.proto)."""
+import hashlib
+import json
 import os
 import re
+import sys
 
 from google.protobuf import descriptor_pb2, descriptor_pool, message_factory
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_proto_schema.json")
 _T = descriptor_pb2.FieldDescriptorProto
 _SCALAR = {"double": _T.TYPE_DOUBLE, "float": _T.TYPE_FLOAT, "int32": _T.TYPE_INT32, "int64": _T.TYPE_INT64,
            "uint64": _T.TYPE_UINT64, "string": _T.TYPE_STRING}
@@ -73,26 +78,56 @@ def classes():
     return _classes
 
 
-def check_against_reference(path="/root/reference/point_viewer_proto_rust/src/proto.proto"):
-    """Field numbers / types / labels of SCHEMA and ENUMS against the reference's own proto file. Returns the number of
-    fields compared, or None when the reference checkout is not there (GPU box)."""
-    if not os.path.exists(path):
-        return None
+def read_proto(path):
+    """The messages of SCHEMA and the enums of ENUMS as a .proto file declares them, in the shape of SCHEMA / ENUMS.
+    Of S2Meta only the fields SCHEMA names are kept (its attributes are not part of the octree path)."""
     text = re.sub(r"//[^\n]*", "", open(path).read())
-    compared = 0
+    schema, enums = {}, {}
     for mname, fields in SCHEMA.items():
         body = re.search(r"message\s+%s\s*\{(.*?)\n\}" % mname, text, re.S).group(1)
-        found = {}
-        for rep, typ, name, num in re.findall(r"(repeated\s+)?([\w.]+)\s+(\w+)\s*=\s*(\d+)\s*;", body):
-            found[name] = (int(num), typ, bool(rep))
-        for fname, num, typ, rep in fields:
-            assert found[fname] == (num, typ, rep), (mname, fname, found[fname], (num, typ, rep))
-            compared += 1
-        if mname != "S2Meta":  # (attributes of S2Meta are not part of the octree path)
-            assert set(found) == {f[0] for f in fields}, (mname, sorted(found))
-    for ename, values in ENUMS.items():
+        found = [(name, int(num), typ, bool(rep))
+                 for rep, typ, name, num in re.findall(r"(repeated\s+)?([\w.]+)\s+(\w+)\s*=\s*(\d+)\s*;", body)]
+        if mname == "S2Meta":
+            found = [f for f in found if f[0] in {g[0] for g in fields}]
+        schema[mname] = found
+    for ename in ENUMS:
         body = re.search(r"enum\s+%s\s*\{(.*?)\}" % ename, text, re.S).group(1)
-        assert [(n, int(v)) for n, v in re.findall(r"(\w+)\s*=\s*(\d+)\s*;", body)] == values
+        enums[ename] = [(n, int(v)) for n, v in re.findall(r"(\w+)\s*=\s*(\d+)\s*;", body)]
+    return schema, enums
+
+
+def schema_digest(schema, enums):
+    """SHA-256 of a (schema, enums) pair shaped like SCHEMA / ENUMS; the order fields are listed in does not count, the
+    order of enum values does."""
+    canon = ({m: sorted(list(f) for f in fields) for m, fields in schema.items()},
+             {e: [list(v) for v in values] for e, values in enums.items()})
+    return hashlib.sha256(json.dumps(canon, sort_keys=True).encode()).hexdigest()
+
+
+def check_against_reference(path):
+    """Field numbers / types / labels of SCHEMA and ENUMS against the reference's own proto file
+    (point_viewer_proto_rust/src/proto.proto). Returns the number of fields compared."""
+    schema, enums = read_proto(path)
+    compared = 0
+    for mname, fields in SCHEMA.items():
+        found = {f[0]: f[1:] for f in schema[mname]}
+        for fname, num, typ, rep in fields:
+            assert found.get(fname) == (num, typ, rep), (mname, fname, found.get(fname), (num, typ, rep))
+            compared += 1
+        assert set(found) == {f[0] for f in fields}, (mname, sorted(found))
+    for ename, values in ENUMS.items():
+        assert enums[ename] == values, (ename, enums[ename])
+    return compared
+
+
+def freeze_reference(path, out=GOLDEN):
+    """Check SCHEMA / ENUMS against the reference's proto file and store the digest of what the file declares, so that
+    the test can check the schema where the reference is not at hand."""
+    compared = check_against_reference(path)
+    with open(out, "w") as f:
+        json.dump({"source": "point_viewer_proto_rust/src/proto.proto of the reference", "fields": compared,
+                   "enum_values": sum(len(v) for v in ENUMS.values()), "sha256": schema_digest(*read_proto(path))}, f, indent=1)
+        f.write("\n")
     return compared
 
 
@@ -100,3 +135,7 @@ def node_id(level, index):
     """(high, low) of NodeId u128 = level << 120 | index (src/octree/node.rs:101-111)."""
     v = (level << 120) | index
     return v >> 64, v & ((1 << 64) - 1)
+
+
+if __name__ == "__main__":
+    print(freeze_reference(sys.argv[1]), "fields checked; digest written to", os.path.relpath(GOLDEN))

@@ -140,3 +140,74 @@ def test_final_line_is_small(tmp_path, monkeypatch, capsys):
     fat["cpu_baseline"]["sample"] *= 10
     fat["kernel_ms_per_step"] = {f"kernel_with_a_long_name_{i}": 1.0 for i in range(200)}
     assert len(json.dumps(bench.final_line(fat))) <= bench.FINAL_LINE_LIMIT
+
+
+class _FakeTree:
+    """The part of OctreeResult that bench.dump_outputs reads, over host bytes: nodes = [(id_high, id_low, level, encoding,
+    point_offset, xyz bytes, rgb bytes)]."""
+
+    def __init__(self, nodes):
+        import ctypes as C
+        import types
+        from point_cloud_viewer_amd import _lib as L
+        self.handle, self._C, self._L = 1, C, L
+        self.ctx = types.SimpleNamespace(_check=lambda rc: None)
+        self.lib = types.SimpleNamespace(pcv_octree_node_data=self._node_data)
+        self._nodes = nodes
+        self._bufs = [(C.create_string_buffer(xyz, max(1, len(xyz))), C.create_string_buffer(rgb, max(1, len(rgb))))
+                      for *_, xyz, rgb in nodes]
+
+    def _node_data(self, handle, i, which, pptr, pln):
+        pptr._obj.value = self._C.addressof(self._bufs[i][which])
+        pln._obj.value = len(self._nodes[i][5 + which])
+        return 0
+
+    @property
+    def num_nodes(self):
+        return len(self._nodes)
+
+    @property
+    def num_points(self):
+        return sum(len(nd[6]) // 3 for nd in self._nodes)
+
+    def meta(self):
+        return dict(resolution=0.001, bbox_min=np.array([-1.0, -2.0, -3.0]), bbox_max=np.array([4.0, 5.0, 6.0]), version=13)
+
+    def node(self, i):
+        hi, lo, level, enc, off, xyz, rgb = self._nodes[i]
+        return self._L.NodeInfo(id_high=hi, id_low=lo, num_points=len(rgb) // 3, level=level, encoding=enc,
+                                cube_min=(self._C.c_double * 3)(0.5, 1.5, 2.5), cube_edge=8.0, xyz_offset=0, point_offset=off)
+
+
+def test_dump_outputs_writes_what_the_build_returned(tmp_path, monkeypatch):
+    """bench --dump-outputs: node table + the stored .xyz / .rgb values of a seeded sample of points, exact, in float32 /
+    float64 .npy files, the same sample on every run. Nodes listed in another order than their points lie in the blobs, an
+    empty node, every position encoding."""
+    rng = np.random.default_rng(4)
+    nodes, want = [], {}
+    for level, enc, dt, count, off in ((0, 2, "<u2", 5, 7), (1, 1, "u1", 0, 12), (1, 4, "<f8", 3, 12), (2, 3, "<f4", 7, 0)):
+        vals = (rng.integers(0, 256 if enc == 1 else 65536, (count, 3)) if enc <= 2 else rng.random((count, 3))).astype(dt)
+        rgb = rng.integers(0, 256, (count, 3)).astype(np.uint8)
+        nodes.append(((level << 56) | 0xABCDEF01, (1 << 63) | count, level, enc, off, vals.tobytes(), rgb.tobytes()))
+        for k in range(count):
+            want[off + k] = (vals[k].astype(np.float64), rgb[k].astype(np.float32))
+    tree = _FakeTree(nodes)
+    n = tree.num_points
+    assert sorted(want) == list(range(n))
+    for sample in (n, 6):
+        monkeypatch.setattr(bench, "DUMP_MAX_SAMPLE", sample)
+        d = tmp_path / f"s{sample}"
+        rec = bench.dump_outputs(tree, str(d))
+        got = {p.stem: np.load(p) for p in d.glob("*.npy")}
+        assert set(got) == {"meta", "nodes", "point_index", "xyz", "rgb"} and rec["sampled_points"] == sample
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values()) and rec["bytes"] <= 64 << 20
+        assert got["meta"].tolist() == [0.001, -1.0, -2.0, -3.0, 4.0, 5.0, 6.0]
+        assert got["nodes"].shape == (4, 13) and got["nodes"][:, 4].tolist() == [5, 0, 3, 7]
+        assert got["nodes"][0, :4].tolist() == [0, 0xABCDEF01, 1 << 31, 5] and got["nodes"][3, 12] == 0
+        idx = got["point_index"].astype(np.int64)
+        assert idx.size == sample and np.all(np.diff(idx) > 0)
+        assert np.array_equal(got["xyz"], np.array([want[i][0] for i in idx]))
+        assert np.array_equal(got["rgb"], np.array([want[i][1] for i in idx]))
+        again = bench.dump_outputs(tree, str(tmp_path / "again"))
+        assert again == dict(rec, dir=str(tmp_path / "again"))
+        assert np.array_equal(np.load(tmp_path / "again" / "point_index.npy"), got["point_index"])

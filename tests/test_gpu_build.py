@@ -312,7 +312,7 @@ def test_device_ply_decode_equals_host_decode(ctx, tmp_path):
     """pcv_build_octree_from_ply (vertex records uploaded as they are, cast + `comment offset` on the device,
     ply.rs:488-493) against the host parser + pcv_build_octree on the same file: x / y / z of different scalar types at
     unaligned offsets inside a 23-byte record, properties that are skipped, a trailing element; and the reference's own
-    fixture files when the checkout is there."""
+    fixture files (tests/golden/)."""
     import os
     rng = np.random.default_rng(5)
     n = 60_000
@@ -328,9 +328,9 @@ def test_device_ply_decode_equals_host_decode(ctx, tmp_path):
                  "element face 0\nproperty list uchar int vertex_indices\nend_header\n").encode())
         f.write(rec.tobytes())
     files = [(tmp_path / "mixed.ply", True)]
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
     for name, has_int in (("xyz_f32_rgb_u8_le.ply", False), ("xyz_f32_rgba_u8_le.ply", False), ("xyz_f32_rgb_u8_intensity_f32.ply", True)):
-        if os.path.exists(os.path.join("/root/reference/src/test_data", name)):
-            files.append((os.path.join("/root/reference/src/test_data", name), has_int))
+        files.append((os.path.join(golden, name), has_int))
     for path, has_int in files:
         dev = ctx.build_from_ply(0.01, path, with_intensity=has_int, max_points_per_node=2000)
         pts = pcv.read_ply(path)

@@ -12,8 +12,14 @@ import meta_proto  # noqa: E402
 
 
 def test_schema_matches_the_reference_proto_file():
-    compared = meta_proto.check_against_reference()
-    assert compared is None or compared >= 25
+    """SCHEMA / ENUMS against what the reference's proto.proto declares, as frozen in tests/golden/ by
+    meta_proto.freeze_reference (which checked them field by field against the file itself)."""
+    import json
+    with open(meta_proto.GOLDEN) as f:
+        golden = json.load(f)
+    assert golden["fields"] == sum(len(v) for v in meta_proto.SCHEMA.values()) >= 25
+    assert golden["enum_values"] == sum(len(v) for v in meta_proto.ENUMS.values())
+    assert meta_proto.schema_digest(meta_proto.SCHEMA, meta_proto.ENUMS) == golden["sha256"]
 
 
 def test_meta_pb_parses_with_the_protobuf_runtime(tmp_path):

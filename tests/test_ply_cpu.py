@@ -1,6 +1,8 @@
 """Host-side PLY ingest (pcv_ply_read) against fixtures equivalent to the reference's src/test_data/*.ply
 (8 vertices: xyz = 1..24 as f32, rgb = 255..232, optional alpha / NaN intensity) and the behaviours pinned by
-src/read_write/ply.rs:753-836. The fixtures are generated here (the reference's files are not copied)."""
+src/read_write/ply.rs:753-836. The fixtures are generated here; the reference's own three files are read from
+tests/golden/ as well."""
+import os
 import struct
 
 import numpy as np
@@ -95,20 +97,16 @@ def test_rejects_what_the_reference_rejects(tmp_path):
         pcv.read_ply(tmp_path / "short.ply")
 
 
-REFERENCE_FIXTURES = "/root/reference/src/test_data"
+REFERENCE_FIXTURES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 @pytest.mark.parametrize("name,last_red,has_intensity", [("xyz_f32_rgb_u8_le.ply", 234, False), ("xyz_f32_rgba_u8_le.ply", 227, False),
                                                           ("xyz_f32_rgb_u8_intensity_f32.ply", 234, True)])
 def test_the_reference_own_fixture_files(name, last_red, has_intensity):
-    """The three byte fixtures the reference ships, read FROM the reference checkout when it is there (build container;
-    the GPU box has no /root/reference), against exactly what src/read_write/ply.rs:753-797 asserts: 4 batches of 2 = 8
-    points, first x == 1, last x == 22, first red == 255, last red == 234 / 227, NaN intensities present."""
-    import os
-    path = os.path.join(REFERENCE_FIXTURES, name)
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not present")
-    p = pcv.read_ply(path)
+    """The three byte fixtures the reference ships (src/test_data/, stored unchanged under tests/golden/), against exactly
+    what src/read_write/ply.rs:753-797 asserts: 4 batches of 2 = 8 points, first x == 1, last x == 22, first red == 255,
+    last red == 234 / 227, NaN intensities present."""
+    p = pcv.read_ply(os.path.join(REFERENCE_FIXTURES, name))
     assert p["x"].size == 8                       # NUM_BATCHES * BATCH_SIZE
     assert p["x"][0] == 1.0 and p["x"][-1] == 22.0
     assert p["color"][0, 0] == 255 and p["color"][-1, 0] == last_red
