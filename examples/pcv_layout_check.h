@@ -44,4 +44,9 @@ PCV_SA(sizeof(pcv_split_node) == 56 && offsetof(pcv_split_node, first) == 16 && 
        "pcv_split_node");
 PCV_SA(sizeof(pcv_promote_node) == 24 && offsetof(pcv_promote_node, child_offset) == 16, "pcv_promote_node");
 
+PCV_SA(sizeof(pcv_ooc_stats) == 120, "pcv_ooc_stats");
+PCV_SA(offsetof(pcv_ooc_stats, spill_bytes) == 32 && offsetof(pcv_ooc_stats, h2d_ms) == 56 && offsetof(pcv_ooc_stats, write_ms) == 104 &&
+           offsetof(pcv_ooc_stats, split_mask) == 112 && offsetof(pcv_ooc_stats, routed) == 116,
+       "pcv_ooc_stats fields");
+
 #endif

@@ -142,7 +142,9 @@ int pcv_build_octree(pcv_ctx* ctx, const pcv_build_params* params, const pcv_poi
  * most 2^32 - 2 points (PCV_E_INVALID above that); everything is device-resident, about 80 bytes of HBM per point at the
  * peak of a build (27-31 B of input + records, rank counts, the wide-code pool and the output blobs), so ONE 288 GB MI355X
  * ends at roughly 3 x 10^9 points. The reference streams any size through node files (generation.rs:58-126); larger clouds
- * go through the multi-GPU path (pcv_route_* + pcv_build_begin_routed), which shards by subtree. */
+ * go through the out-of-core build (pcv_ooc_*, below: one GPU, the points wait in host memory — about 17-21 B per point with a
+ * Float32-coded level 1, 28-32 B otherwise — and are built in passes of at most max_points_per_pass points, each under this
+ * limit; the total is counted in 64 bits) or the multi-GPU path (pcv_route_* + pcv_build_begin_routed), which shards by subtree. */
 #define PCV_MAX_POINTS_PER_BUILD 0xfffffffeull
 
 /* ---- streaming batch ingest: the reference's `impl Iterator<Item = PointsBatch>` (generation.rs:289-295) ------------
@@ -213,6 +215,62 @@ typedef struct pcv_routed_points {
 int pcv_build_begin_routed(pcv_ctx* ctx, const pcv_build_params* params, const pcv_routed_points* routed, pcv_octree** out);
 int pcv_build_top_streams(const pcv_octree* tree, pcv_top_streams* out);
 int pcv_build_finish(pcv_octree* tree, const pcv_top_layout* top /* nullable */);
+
+/* ---- out-of-core build: clouds larger than the device through ONE GPU (build_octree, generation.rs:289-403) -------------
+ * The reference streams any number of points through node files on disk. These calls take its batches one at a time, like
+ * pcv_ingest_*, and write its directory; the points wait in host memory between two phases:
+ *   pcv_ooc_begin   params: resolution, the GLOBAL bounding box (PCV_BUILD_COMPUTE_BBOX is rejected: the stream is read once),
+ *                   max_points_per_node. max_points_per_pass bounds the points resident on the device at once (0 = derived
+ *                   from the free device memory); each pass also stays under PCV_MAX_POINTS_PER_BUILD.
+ *   pcv_ooc_append  the batch goes up through the context's pinned ring; one HIP pass writes it as 64 stable level-2 bucket runs
+ *                   (the level-1 chain state, 16 B per point, where level 1 is Float32-coded, the raw 27 B otherwise; + 4 B of
+ *                   intensity) that come back into per-bucket host spills, each in global input order. Host memory on the
+ *                   input side is O(batch); the spill is O(cloud).
+ *   pcv_ooc_finish  the 64 global counts give the level-1 split mask and partitions of whole units (single buckets under split
+ *                   level-1 nodes, whole octants otherwise) of at most max_points_per_pass points — PCV_E_OOM naming the bucket
+ *                   when one unit alone is larger; every partition is built twice (topology, then pcv_build_finish with the
+ *                   global pcv_top_layout), its nodes of level >= 2 written as it finishes; the root / level-1 files and meta.pb
+ *                   come last (a failed build leaves no meta.pb). The same directory as pcv_build_octree + pcv_octree_write_dir
+ *                   of the whole cloud, byte for byte, whatever the partitioning. ALWAYS consumes the handle.
+ *   pcv_ooc_abort   drops the build; releases all device and host memory.
+ * Counts on the host are 64-bit: the total may exceed 2^32. Other calls on the context between appends are allowed. */
+typedef struct pcv_ooc pcv_ooc;
+typedef struct pcv_ooc_stats {
+  uint64_t points;          /* appended */
+  uint64_t nodes;           /* in meta.pb */
+  uint64_t partitions;
+  uint64_t largest_bucket;  /* points */
+  uint64_t spill_bytes;     /* host memory the points waited in between the phases */
+  uint64_t h2d_bytes;       /* over the host link: batches up, partitions up (twice) */
+  uint64_t d2h_bytes;       /* bucket runs down, the top nodes down */
+  double h2d_ms, d2h_ms;    /* time of those copies */
+  double stream_ms;         /* appends: copy into the ring + DMA + bucket runs + spill */
+  double topology_ms;       /* first pass over the partitions (upload + topology) */
+  double build_ms;          /* second pass (upload + build to the finished blobs) */
+  double merge_ms;          /* top nodes folded into the accumulator */
+  double write_ms;          /* node files and meta.pb */
+  uint32_t split_mask;      /* bit c: the level-1 node c is split */
+  uint32_t routed;          /* 1: the spill held the level-1 chain state; 0: raw planes */
+} pcv_ooc_stats;
+int pcv_ooc_begin(pcv_ctx* ctx, const pcv_build_params* params, int has_intensity, uint64_t max_points_per_pass, pcv_ooc** out);
+int pcv_ooc_append(pcv_ooc* ooc, const double* xyz /* n x 3 (host) */, const uint8_t* rgb /* n x 3 (host) */,
+                   const float* intensity /* n (host), NULL without the attribute */, uint64_t n);
+int pcv_ooc_finish(pcv_ooc* ooc, const char* directory, pcv_ooc_stats* stats /* nullable */);
+void pcv_ooc_abort(pcv_ooc* ooc);
+/* The plan of pcv_ooc_finish from the 64 global bucket counts (host only, pure): split_mask by plan_buckets' rule (level-1 node c
+ * is split iff level1_can_split and its octant holds more than max_points_per_node points); units in bucket order go next-fit into
+ * partitions of at most max_points_per_pass points (0 = PCV_MAX_POINTS_PER_BUILD); partition_of_bucket[b] = UINT32_MAX for an
+ * empty bucket. PCV_E_OOM (message in err) when one unit is larger than the budget. */
+int pcv_ooc_plan(const uint64_t counts[64], uint32_t max_points_per_node, int level1_can_split, uint64_t max_points_per_pass,
+                 uint32_t partition_of_bucket[64], uint32_t* num_partitions, uint32_t* split_mask, char* err, uint64_t errcap);
+/* The global top layout from the summed stream lengths (l1[c] ignored where split_mask has bit c); host only. */
+int pcv_ooc_top_layout(const uint64_t l1[8], const uint64_t l2[64], uint32_t split_mask, pcv_top_layout* out);
+/* The pass of pcv_ooc_append on n device-resident points (xyz n x 3 AoS, rgb n x 3, intensity nullable): planes[0..4] receive
+ * the 64 stable bucket runs (routed != 0: cx, cy, cz, oct_rgb as pcv_route_state, then intensity; routed == 0: x, y, z (f64),
+ * rgb (3 B), intensity), octant_digits[n] the level-2 digit of every point in its root octant's range, in input order;
+ * counts[64] (host) the run lengths. params->flags: PCV_ROUTE_OCTANTS_ONLY as for pcv_route_plan. */
+int pcv_ooc_bucket_runs(pcv_ctx* ctx, const pcv_build_params* params, const double* xyz, const uint8_t* rgb, const float* intensity,
+                        uint64_t n, int routed, void* const planes[5], uint8_t* octant_digits, uint64_t counts[64]);
 
 /* One finished node == one `proto::OctreeNode` (proto.proto:90-94) + where its bytes are. */
 typedef struct pcv_node_info {

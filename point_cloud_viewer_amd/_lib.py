@@ -103,6 +103,13 @@ class NodeInfo(C.Structure):
                 ("xyz_offset", C.c_uint64), ("point_offset", C.c_uint64)]
 
 
+class OocStats(C.Structure):
+    _fields_ = [("points", C.c_uint64), ("nodes", C.c_uint64), ("partitions", C.c_uint64), ("largest_bucket", C.c_uint64),
+                ("spill_bytes", C.c_uint64), ("h2d_bytes", C.c_uint64), ("d2h_bytes", C.c_uint64), ("h2d_ms", C.c_double),
+                ("d2h_ms", C.c_double), ("stream_ms", C.c_double), ("topology_ms", C.c_double), ("build_ms", C.c_double),
+                ("merge_ms", C.c_double), ("write_ms", C.c_double), ("split_mask", C.c_uint32), ("routed", C.c_uint32)]
+
+
 # every symbol include/pcv_hip.h declares: name -> (restype, argtypes)
 _vp = C.c_void_p
 _SIGNATURES = {
@@ -125,6 +132,15 @@ _SIGNATURES = {
     "pcv_ingest_bbox": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "pcv_ingest_finish": (C.c_int, [_vp, C.POINTER(BuildParams), C.POINTER(_vp)]),
     "pcv_ingest_abort": (None, [_vp]),
+    "pcv_ooc_begin": (C.c_int, [_vp, C.POINTER(BuildParams), C.c_int, C.c_uint64, C.POINTER(_vp)]),
+    "pcv_ooc_append": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64]),
+    "pcv_ooc_finish": (C.c_int, [_vp, C.c_char_p, C.POINTER(OocStats)]),
+    "pcv_ooc_abort": (None, [_vp]),
+    "pcv_ooc_plan": (C.c_int, [C.POINTER(C.c_uint64), C.c_uint32, C.c_int, C.c_uint64, C.POINTER(C.c_uint32),
+                               C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_char_p, C.c_uint64]),
+    "pcv_ooc_top_layout": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(TopLayout)]),
+    "pcv_ooc_bucket_runs": (C.c_int, [_vp, C.POINTER(BuildParams), _vp, _vp, _vp, C.c_uint64, C.c_int, C.POINTER(_vp), _vp,
+                                      C.POINTER(C.c_uint64)]),
     "pcv_octree_num_nodes": (C.c_uint64, [_vp]),
     "pcv_octree_num_points": (C.c_uint64, [_vp]),
     "pcv_octree_has_intensity": (C.c_int, [_vp]),

@@ -280,6 +280,9 @@ static int ingest_flush(pcv_ingest* g) {
        hipEventRecord(ctx->ring_ev[slot], cs) == hipSuccess;
   if (ok && cs != ctx->stream) ok = hipStreamWaitEvent(ctx->stream, ctx->ring_ev[slot], 0) == hipSuccess;
   if (!ok) {
+    // the DMA may have been queued before the event record failed: wait it out, so that no copy still reads the chunk once it is
+    // handed on (ring_busy stays false, ring_ev does not cover it)
+    (void)hipStreamSynchronize(cs);
     g->failed = true;
     return ctx->fail(PCV_E_HIP, "pcv_ingest_append: queuing the DMA of a chunk of batches failed");
   }

@@ -221,6 +221,39 @@ class Context:
         self._check(self.lib.pcv_ingest_begin(self.handle, int(num_points_hint), 1 if has_intensity else 0, C.byref(h)))
         return Ingest(self, h, has_intensity)
 
+    def out_of_core(self, resolution, bounding_box, has_intensity=False, max_points_per_pass=0, max_points_per_node=0):
+        """Out-of-core build (pcv_ooc_begin): batches of any total size stream through the device into host spills, and
+        finish(directory) writes the reference's directory partition by partition. bounding_box is required (the stream is
+        read once); max_points_per_pass bounds the points on the device at once (0 = derived from free device memory)."""
+        if bounding_box is None:
+            raise ValueError("the out-of-core build needs the bounding box up front: the stream is read once")
+        pr = self._params(resolution, bounding_box.min, bounding_box.max, max_points_per_node, 0)
+        h = C.c_void_p()
+        self._check(self.lib.pcv_ooc_begin(self.handle, C.byref(pr), 1 if has_intensity else 0, int(max_points_per_pass), C.byref(h)))
+        return OutOfCore(self, h, has_intensity)
+
+    def ooc_bucket_runs(self, resolution, bounding_box, xyz, color, intensity=None, routed=True, octants_only=False):
+        """The pass of the out-of-core append on device tensors (pcv_ooc_bucket_runs): xyz (n, 3) f64, color (n, 3) u8,
+        intensity (n,) f32 or None. Returns (planes, octant_digits, counts): planes = [cx, cy, cz, oct_rgb] int32 (routed) or
+        [x, y, z] f64 + rgb (n, 3) u8 (raw), then intensity; every plane holds the 64 bucket runs one after the other."""
+        import torch
+        n = int(xyz.shape[0])
+        dev = xyz.device
+        if routed:
+            planes = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(4)]
+        else:
+            planes = [torch.empty(n, dtype=torch.float64, device=dev) for _ in range(3)] + [torch.empty((n, 3), dtype=torch.uint8, device=dev)]
+        planes.append(torch.empty(n, dtype=torch.float32, device=dev) if intensity is not None else None)
+        digits = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        ptrs = (C.c_void_p * 5)(*[None if t is None else t.data_ptr() for t in planes])
+        counts = (C.c_uint64 * 64)()
+        pr = self._params(resolution, bounding_box.min, bounding_box.max, 0, L.ROUTE_OCTANTS_ONLY if octants_only else 0)
+        self.wait_torch()
+        self._check(self.lib.pcv_ooc_bucket_runs(self.handle, C.byref(pr), xyz.data_ptr(), color.data_ptr(),
+                                                 None if intensity is None else intensity.data_ptr(), n, 1 if routed else 0, ptrs,
+                                                 digits.data_ptr(), counts))
+        return planes, digits[:n], np.array(counts[:], dtype=np.int64)
+
     def build_from_ply(self, resolution, filename, with_intensity=False, max_points_per_node=0):
         """build_octree_from_file (generation.rs:272-287) with the decode on the device: the file's vertex records go up as
         they are, a HIP kernel casts x / y / z to f64 and adds the header offset (ply.rs:488-493), the bounding box is
@@ -553,6 +586,80 @@ class Ingest:
             self.abort()
         except Exception:  # noqa: BLE001 - interpreter shutdown
             pass
+
+
+class OutOfCore:
+    """One pcv_ooc: batches of `PointsBatch` shape (positions (n, 3) f64, colour (n, 3) u8, intensity (n,) f32) of a cloud of
+    any size; `finish(directory)` writes the reference's directory and returns the build's statistics (a dict) — the tree
+    never exists whole, so there is no OctreeResult."""
+
+    def __init__(self, ctx, handle, has_intensity):
+        self.ctx, self.lib, self.handle, self.has_intensity = ctx, ctx.lib, handle, bool(has_intensity)
+
+    def append(self, position, color, intensity=None):
+        pos = np.ascontiguousarray(position, dtype=np.float64)
+        if pos.ndim != 2 or pos.shape[1] != 3:
+            raise ValueError("position must be (n, 3): one Point3<f64> per row")
+        n = pos.shape[0]
+        col = np.ascontiguousarray(color, dtype=np.uint8)
+        if col.shape != (n, 3):
+            raise ValueError("color must be (n, 3) u8")
+        inten = None
+        if self.has_intensity:
+            if intensity is None:
+                raise ValueError("the build was begun with intensity: every batch must carry it")
+            inten = np.ascontiguousarray(intensity, dtype=np.float32)
+            if inten.shape != (n,):
+                raise ValueError("intensity must be (n,) f32")
+        if self.handle is None:
+            raise ValueError("the out-of-core build is finished")
+        self.ctx._check(self.lib.pcv_ooc_append(self.handle, pos.ctypes.data, col.ctypes.data,
+                                                None if inten is None else inten.ctypes.data, n))
+
+    def finish(self, directory):
+        """pcv_ooc_finish: plan, the two passes over the partitions, the directory; consumes the handle whatever it returns."""
+        if self.handle is None:
+            raise ValueError("the out-of-core build is finished")
+        st, mine = L.OocStats(), self.handle
+        self.handle = None
+        self.ctx._check(self.lib.pcv_ooc_finish(mine, str(directory).encode(), C.byref(st)))
+        return {name: getattr(st, name) for name, _ in L.OocStats._fields_}
+
+    def abort(self):
+        if self.handle is not None:
+            self.lib.pcv_ooc_abort(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.abort()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+def ooc_plan(counts, max_points_per_node, level1_can_split, max_points_per_pass):
+    """pcv_ooc_plan (host only, pure): (partition_of_bucket[64] with -1 for empty buckets, num_partitions, split_mask) from the
+    64 global bucket counts; raises PcvError(PCV_E_OOM) naming the bucket when one unit is larger than the budget."""
+    cnt = (C.c_uint64 * 64)(*[int(v) for v in counts])
+    part, nparts, mask = (C.c_uint32 * 64)(), C.c_uint32(), C.c_uint32()
+    err = C.create_string_buffer(256)
+    lib = L.load_library()
+    rc = lib.pcv_ooc_plan(cnt, int(max_points_per_node), 1 if level1_can_split else 0, int(max_points_per_pass), part,
+                          C.byref(nparts), C.byref(mask), err, 256)
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, err.value.decode())
+    return np.array([-1 if v == 0xFFFFFFFF else int(v) for v in part], dtype=np.int64), int(nparts.value), int(mask.value)
+
+
+def ooc_top_layout(l1, l2, split_mask):
+    """pcv_ooc_top_layout: distributed.top_layout in the library (host only)."""
+    a, b = (C.c_uint64 * 8)(*[int(v) for v in l1]), (C.c_uint64 * 64)(*[int(v) for v in l2])
+    tl = L.TopLayout()
+    rc = L.load_library().pcv_ooc_top_layout(a, b, int(split_mask), C.byref(tl))
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, "top streams exceed 32-bit offsets")
+    return dict(root_points=int(tl.root_points), l1_stream=[int(v) for v in tl.l1_stream], l1_offset=[int(v) for v in tl.l1_offset],
+                l2_offset=[int(v) for v in tl.l2_offset])
 
 
 class PendingBuild:
@@ -915,12 +1022,16 @@ def default_context():
 
 
 def build_octree(output_directory, resolution, bounding_box, points, attributes=("color",), ctx=None,
-                 max_points_per_node=0):
+                 max_points_per_node=0, max_points_per_pass=None):
     """Drop-in for reference `build_octree` (generation.rs:289-295): builds on the GPU and writes the
     reference's directory layout. `points` = dict(x=, y=, z=, color=, intensity=optional) — or, like the reference, an
     ITERATOR OF BATCHES, each dict(position=(n, 3) f64, color=(n, 3) u8[, intensity=(n,) f32]) (PointsBatch,
     src/lib.rs:102-107): the batches are streamed to the device one at a time (pcv_ingest_*), host memory stays O(batch).
-    An iterator with `num_points` (NumberOfPoints, src/lib.rs:56-58) sizes the device arrays up front."""
+    An iterator with `num_points` (NumberOfPoints, src/lib.rs:56-58) sizes the device arrays up front.
+    max_points_per_pass: None = the in-core build above. An integer (0 = derived from free device memory) takes the
+    out-of-core build (pcv_ooc_*) for clouds larger than the device: the batches wait in host memory, the tree is built
+    partition by partition straight into the directory, and the build's statistics (a dict) are returned instead of an
+    OctreeResult. The bounding box is required then."""
     attributes = tuple(attributes)
     if "color" not in attributes:
         raise ValueError("the octree format requires the 'color' attribute (on_disk.rs:20-22)")
@@ -928,6 +1039,22 @@ def build_octree(output_directory, resolution, bounding_box, points, attributes=
         if a not in ("color", "intensity"):
             raise ValueError(f"unsupported attribute {a!r} (octree/mod.rs:62-74 implies color and intensity)")
     ctx = ctx or default_context()
+    if max_points_per_pass is not None:
+        want_intensity = "intensity" in attributes
+        if isinstance(points, dict):
+            pos = np.stack([np.asarray(points["x"]), np.asarray(points["y"]), np.asarray(points["z"])], axis=1)
+            one = dict(position=pos, color=points["color"], intensity=points.get("intensity"))
+            points = [one]
+        ooc = ctx.out_of_core(resolution, bounding_box, want_intensity, max_points_per_pass, max_points_per_node)
+        try:
+            for batch in points:
+                if want_intensity and batch.get("intensity") is None:
+                    raise ValueError("attribute 'intensity' requested but not present in the input")
+                ooc.append(batch["position"], batch["color"], batch.get("intensity") if want_intensity else None)
+        except BaseException:
+            ooc.abort()
+            raise
+        return ooc.finish(output_directory)
     if not isinstance(points, dict):
         want_intensity = "intensity" in attributes
         hint = getattr(points, "num_points", 0)

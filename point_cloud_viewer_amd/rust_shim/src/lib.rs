@@ -69,6 +69,30 @@ type pcv_octree = c_void;
 type pcv_shapes = c_void;
 #[allow(non_camel_case_types)]
 type pcv_ingest = c_void;
+#[allow(non_camel_case_types)]
+type pcv_ooc = c_void;
+
+/// include/pcv_hip.h pcv_ooc_stats: what an out-of-core build did (points, nodes, partitions, host spill, link traffic, phase times).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct PcvOocStats {
+    pub points: u64,
+    pub nodes: u64,
+    pub partitions: u64,
+    pub largest_bucket: u64,
+    pub spill_bytes: u64,
+    pub h2d_bytes: u64,
+    pub d2h_bytes: u64,
+    pub h2d_ms: f64,
+    pub d2h_ms: f64,
+    pub stream_ms: f64,
+    pub topology_ms: f64,
+    pub build_ms: f64,
+    pub merge_ms: f64,
+    pub write_ms: f64,
+    pub split_mask: u32,
+    pub routed: u32,
+}
 
 extern "C" {
     fn pcv_abi_version() -> c_int;
@@ -82,6 +106,11 @@ extern "C" {
     fn pcv_ingest_append(ingest: *mut pcv_ingest, xyz: *const c_double, rgb: *const u8, intensity: *const c_float, n: u64) -> c_int;
     fn pcv_ingest_finish(ingest: *mut pcv_ingest, params: *const PcvBuildParams, out: *mut *mut pcv_octree) -> c_int;
     fn pcv_ingest_abort(ingest: *mut pcv_ingest);
+    // out-of-core build: the same batches, for clouds larger than the device (host spills, partitions built one after another)
+    fn pcv_ooc_begin(ctx: *mut pcv_ctx, params: *const PcvBuildParams, has_intensity: c_int, max_points_per_pass: u64, out: *mut *mut pcv_ooc) -> c_int;
+    fn pcv_ooc_append(ooc: *mut pcv_ooc, xyz: *const c_double, rgb: *const u8, intensity: *const c_float, n: u64) -> c_int;
+    fn pcv_ooc_finish(ooc: *mut pcv_ooc, directory: *const c_char, stats: *mut PcvOocStats) -> c_int;
+    fn pcv_ooc_abort(ooc: *mut pcv_ooc);
     fn pcv_build_octree_from_ply(ctx: *mut pcv_ctx, params: *const PcvBuildParams, path: *const c_char, with_intensity: c_int, out: *mut *mut pcv_octree) -> c_int;
     fn pcv_octree_write_dir(t: *mut pcv_octree, directory: *const c_char) -> c_int;
     fn pcv_octree_open_dir(ctx: *mut pcv_ctx, directory: *const c_char, out: *mut *mut pcv_octree) -> c_int;
@@ -184,6 +213,66 @@ pub fn build_octree(
         ctx.check(unsafe { pcv_octree_write_dir(tree, dir.as_ptr()) });
         unsafe { pcv_octree_free(tree) };
     });
+}
+
+/// `build_octree` for clouds larger than the device: the same batches stream through pcv_ooc_append into host spills, and
+/// pcv_ooc_finish builds the tree partition by partition of at most `max_points_per_pass` points (0 = derived from the free
+/// device memory) straight into `output_directory` — the same directory, byte for byte. Every attribute vector's length is
+/// checked against `position.len()` before its pointer crosses the boundary. Panics like the reference on any error.
+pub fn build_octree_out_of_core(
+    output_directory: impl AsRef<Path>,
+    resolution: f64,
+    bounding_box: Aabb,
+    input: impl Iterator<Item = PointsBatch>,
+    attributes: &[&str],
+    max_points_per_pass: u64,
+) -> PcvOocStats {
+    let want_intensity = attributes.contains(&"intensity");
+    CONTEXT.with(|ctx| {
+        let params = PcvBuildParams {
+            resolution,
+            bbox_min: [bounding_box.min().x, bounding_box.min().y, bounding_box.min().z],
+            bbox_max: [bounding_box.max().x, bounding_box.max().y, bounding_box.max().z],
+            max_points_per_node: 0,
+            flags: 0,
+        };
+        let mut ooc = std::ptr::null_mut();
+        ctx.check(unsafe { pcv_ooc_begin(ctx.0, &params, want_intensity as c_int, max_points_per_pass, &mut ooc) });
+        for batch in input {
+            let n = batch.position.len();
+            let color = match batch.attributes.get("color") {
+                Some(AttributeData::U8Vec3(c)) if c.len() == n => c.as_ptr() as *const u8,
+                Some(AttributeData::U8Vec3(c)) => {
+                    unsafe { pcv_ooc_abort(ooc) };
+                    panic!("color has {} entries for {} positions", c.len(), n)
+                }
+                _ => {
+                    unsafe { pcv_ooc_abort(ooc) };
+                    panic!("color attribute (U8Vec3) is required") // on_disk.rs:20-22
+                }
+            };
+            let intensity = if want_intensity {
+                match batch.attributes.get("intensity") {
+                    Some(AttributeData::F32(i)) if i.len() == n => i.as_ptr(),
+                    _ => {
+                        unsafe { pcv_ooc_abort(ooc) };
+                        panic!("intensity requested but missing or not one value per position") // generation.rs:167-177
+                    }
+                }
+            } else {
+                std::ptr::null()
+            };
+            let rc = unsafe { pcv_ooc_append(ooc, batch.position.as_ptr() as *const c_double, color, intensity, n as u64) };
+            if rc != 0 {
+                unsafe { pcv_ooc_abort(ooc) };
+                ctx.check(rc);
+            }
+        }
+        let dir = CString::new(output_directory.as_ref().to_str().unwrap()).unwrap();
+        let mut stats = PcvOocStats::default();
+        ctx.check(unsafe { pcv_ooc_finish(ooc, dir.as_ptr(), &mut stats) }); // consumes the handle whatever it returns
+        stats
+    })
 }
 
 /// Same signature and behaviour as `point_viewer::octree::build_octree_from_file` (generation.rs:272-287), which is what
