@@ -231,7 +231,8 @@ int pcv_build_finish(pcv_octree* tree, const pcv_top_layout* top /* nullable */)
  *                   when one unit alone is larger; every partition is built twice (topology, then pcv_build_finish with the
  *                   global pcv_top_layout), its nodes of level >= 2 written as it finishes; the root / level-1 files and meta.pb
  *                   come last (a failed build leaves no meta.pb). The same directory as pcv_build_octree + pcv_octree_write_dir
- *                   of the whole cloud, byte for byte, whatever the partitioning. ALWAYS consumes the handle.
+ *                   of the whole cloud, byte for byte, whatever the partitioning; an empty stream writes meta.pb without
+ *                   nodes and returns stats with points == 0, like the in-core build of it. ALWAYS consumes the handle.
  *   pcv_ooc_abort   drops the build; releases all device and host memory.
  * Counts on the host are 64-bit: the total may exceed 2^32. Other calls on the context between appends are allowed. */
 typedef struct pcv_ooc pcv_ooc;

@@ -404,12 +404,12 @@ extern "C" int pcv_ingest_bbox(pcv_ingest* g, double bbox_min[3], double bbox_ma
   }
   PCV_HIP_CHECK(ctx, hipMemcpyAsync(ctx->mailbox, g->acc, 48, hipMemcpyDeviceToHost, ctx->stream));
   PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  const double inf = std::numeric_limits<double>::infinity();
   for (int a = 0; a < 3; ++a) {
     bbox_min[a] = ordered_value(ctx->mailbox[a]);
     bbox_max[a] = ordered_value(ctx->mailbox[3 + a]);
-    // no (non-NaN) point yet: Aabb::zero() (generation.rs:269), what pcv_aabb_reduce reports for n == 0
-    if (g->n == 0 || bbox_min[a] == inf) bbox_min[a] = bbox_max[a] = 0.0;
+    // no point yet: Aabb::zero() (generation.rs:269), what pcv_aabb_reduce reports for n == 0. Otherwise the fold as it stands,
+    // like K1's: a column of +inf only is [+inf, +inf], one of NaN only [+inf, -inf] (fmin / fmax skip NaN)
+    if (g->n == 0) bbox_min[a] = bbox_max[a] = 0.0;
   }
   return PCV_OK;
 }

@@ -654,7 +654,13 @@ int ooc_finish(pcv_ooc* g, const char* directory) {
     for (int p = 0; p < g->nplanes; ++p) g->st.spill_bytes += g->spill[b][p].size();
   }
   for (int o = 0; o < 8; ++o) g->st.spill_bytes += g->oseq[o].size();
-  if (total == 0) return ctx->fail(PCV_E_INVALID, "pcv_ooc_finish: no points were appended");
+  if (total == 0) {  // an empty stream: meta.pb without nodes, what pcv_octree_write_dir writes for the in-core build of it
+    const double t0 = now_ms();
+    if (pcv_write_meta(directory, g->params.resolution, g->params.bbox_min, g->params.bbox_max, nullptr, 0))
+      return ctx->fail(PCV_E_IO, "pcv_ooc_finish: cannot write meta.pb");
+    g->st.write_ms = now_ms() - t0;
+    return PCV_OK;
+  }
   // plan
   uint32_t part_of[64], nparts = 0, split_mask = 0;
   char err[256] = {};

@@ -98,9 +98,10 @@ def test_degenerate_inputs(ctx):
                 assert_same(got, want)
 
 
-def test_special_coordinates_take_the_guarded_chain(ctx):
-    """Signed zeros, denormals, huge values, NaN and infinities mixed into an ordinary cloud: the kernels route such
-    points through the guarded division variant; the bytes must not change."""
+def special_coordinates_cloud():
+    """An ordinary cloud with signed zeros, denormals, huge values, NaN and infinities mixed in, and the boxes it is built in:
+    [(bbox_min, bbox_max, resolutions)]. The second box cuts the cloud in half: the outside points collapse onto its faces
+    (clamped codes) and the tree gets deep — at 1e-7 m 28 levels, i.e. the two-word key path."""
     n = 60_000
     x, y, z, rgb, bmin, bmax = synthetic.gaussian_clusters(n, seed=41, num_clusters=4, extent=16.0, sigma_range=(0.01, 1.5))
     special = np.array([-0.0, 0.0, 5e-324, 1e-310, 2.0 ** -701, 2.0 ** -699, 1e-300, 1e200, -1e200, 2.0 ** 501,
@@ -109,11 +110,17 @@ def test_special_coordinates_take_the_guarded_chain(ctx):
     for coords in (x, y, z):
         idx = rng.choice(n, 3000, replace=False)
         coords[idx] = rng.choice(special, idx.size)
-    # the second box cuts the cloud in half: the outside points collapse onto its faces (clamped codes) and the tree gets
-    # deep — at 1e-7 m 28 levels, i.e. the two-word key path
-    for lo, hi, resolutions in ((bmin, bmax, (0.001, 1e-7)),
-                                (np.array([-8.0, -8.0, -8.0]), np.array([8.0, 8.0, 8.0]), (0.001, 1e-7)),
-                                (np.array([0.0, -0.0, -8.0]), np.array([8.0, 8.0, 8.0]), (0.001, 1e-7))):
+    boxes = [(bmin, bmax, (0.001, 1e-7)),
+             (np.array([-8.0, -8.0, -8.0]), np.array([8.0, 8.0, 8.0]), (0.001, 1e-7)),
+             (np.array([0.0, -0.0, -8.0]), np.array([8.0, 8.0, 8.0]), (0.001, 1e-7))]
+    return x, y, z, rgb, boxes
+
+
+def test_special_coordinates_take_the_guarded_chain(ctx):
+    """Signed zeros, denormals, huge values, NaN and infinities mixed into an ordinary cloud: the kernels route such
+    points through the guarded division variant; the bytes must not change."""
+    x, y, z, rgb, boxes = special_coordinates_cloud()
+    for lo, hi, resolutions in boxes:
         for res in resolutions:
             with O.max_points_per_node(900):
                 want = O.build_closed(res, lo, hi, x, y, z, rgb, threads=4)
