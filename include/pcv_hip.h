@@ -608,6 +608,33 @@ int pcv_query_node_points(pcv_ctx* ctx, const pcv_shapes* shapes, uint32_t shape
                           const double* interval, uint64_t capacity, int mem, double* x, double* y, double* z, uint8_t* rgb,
                           float* intensity, uint64_t* count);
 
+/* Point queries of MANY locations over one octree in one run: what ParallelIterator does per
+ * location, for S shapes at once, with the result kept on the device as a segment table. One segment per (shape, node
+ * that pcv_nodes_in_location reports for it), in that list's order, shapes one after another — nodes without points and
+ * nodes where nothing passes included; a frustum whose matrix is not invertible has none. Segment k holds exactly the
+ * points pcv_query_node_points(shape, node, interval) returns, so a shape's segments, concatenated, are its
+ * pcv_query_points result.
+ *   intervals      nullable: 2 x S doubles (lo, hi), the ClosedInterval on intensity of each shape;
+ *   interval_used  nullable: S flags, which shapes the interval applies to (NULL with intervals != NULL: all).
+ * An interval on an octree without intensity is PCV_E_INVALID. `shapes` may be freed after the run; `tree` must outlive
+ * the batch (pcv_query_batch_points reads its device blobs); pcv_query_batch_free touches neither. A failed run frees
+ * what it allocated. Works on built octrees and on octrees opened with pcv_octree_open_dir. */
+typedef struct pcv_query_batch pcv_query_batch;
+int pcv_query_batch_run(pcv_ctx* ctx, const pcv_shapes* shapes, pcv_octree* tree, const double* intervals,
+                        const uint8_t* interval_used, pcv_query_batch** out);
+int pcv_query_batch_sizes(const pcv_query_batch* b, uint64_t* num_segments, uint64_t* num_points);
+/* Host arrays, each nullable: shape s's segments are shape_first_segment[s] .. shape_first_segment[s + 1] (S + 1 entries),
+ * segment_node[k] the node index (num_segments entries), segment_offset[k] its first point, a u64 exclusive scan over all
+ * segments (num_segments + 1 entries; the last is num_points). */
+int pcv_query_batch_segments(const pcv_query_batch* b, uint64_t* shape_first_segment, uint32_t* segment_node,
+                             uint64_t* segment_offset);
+/* The points of segments [first_segment, first_segment + num_segments): decoded f64 x/y/z, rgb (3 B per point) and, when
+ * non-null and the octree has it, intensity, into buffers of `capacity` points that live where `mem` says. A range past
+ * the end or with more than `capacity` points is PCV_E_INVALID and writes nothing. */
+int pcv_query_batch_points(pcv_query_batch* b, uint64_t first_segment, uint64_t num_segments, uint64_t capacity, int mem,
+                           double* x, double* y, double* z, uint8_t* rgb, float* intensity);
+void pcv_query_batch_free(pcv_query_batch* b);
+
 /* The `/nodes_data` reply blob of octree_web_viewer (octree_web_viewer/src/backend.rs:90-177) for a list of nodes:
  * per node min xyz (3 x f64 LE), edge (f64), num_points (u32), bytes per coordinate (u8), pad to 8, raw .xyz, pad
  * to 8, raw .rgb, pad to 8. *needed = blob size; the blob is written when out != NULL and capacity >= *needed. */

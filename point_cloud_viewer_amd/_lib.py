@@ -212,6 +212,11 @@ _SIGNATURES = {
                                    _vp, C.POINTER(C.c_uint64)]),
     "pcv_query_node_points": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_double), C.c_uint64, C.c_int, _vp, _vp,
                                         _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
+    "pcv_query_batch_run": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(_vp)]),
+    "pcv_query_batch_sizes": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "pcv_query_batch_segments": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "pcv_query_batch_points": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "pcv_query_batch_free": (None, [_vp]),
     "pcv_octree_nodes_blob": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pcv_transform_points": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(Points), _vp, _vp, _vp]),
 }

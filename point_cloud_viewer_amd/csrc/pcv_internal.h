@@ -121,6 +121,11 @@ enum PcvKernelId {
   PCV_K_CULL_NODES_SPARSE,
   PCV_K_SORT_SETTLE,  // the record sort's second pass settling the leaves' points itself (PcvSortFuse)
   PCV_K_INGEST,       // pcv_ingest_append: AoS -> SoA transposition + attribute copies + bounding-box fold of one batch
+  PCV_K_QUERY_BATCH_NODES,    // pcv_query_batch_run: node lists of every shape (count pass + write pass)
+  PCV_K_QUERY_BATCH_CHUNKS,   // pcv_query_batch_run: per-segment sizes and the chunk descriptors
+  PCV_K_QUERY_BATCH_FLAGS,    // pcv_query_batch_run: keep flags of every chunk of every shape
+  PCV_K_QUERY_BATCH_SCAN,     // pcv_query_batch_run: the u64 scans (segments, flags, chunks, kept points)
+  PCV_K_QUERY_BATCH_COMPACT,  // pcv_query_batch_points: stable compaction of a segment range
   PCV_K_COUNT
 };
 

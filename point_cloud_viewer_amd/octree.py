@@ -881,6 +881,24 @@ class OctreeResult:
         n = min(count.value, cap)
         return dict(count=count.value, x=x[:n], y=y[:n], z=z[:n], rgb=rgb[:n], intensity=inten[:n] if has_int else None)
 
+    def query_batch(self, shapes, intervals=None):
+        """The points of every shape of `shapes` in one run (pcv_query_batch_run), kept on the device as one segment per
+        (shape, node of nodes_in_location). intervals: None, or one entry per shape, None or (lo, hi) on intensity."""
+        iv = used = None
+        if intervals is not None:
+            intervals = list(intervals)
+            if len(intervals) != shapes.count:
+                raise ValueError(f"intervals: expected {shapes.count} entries (one per shape), got {len(intervals)}")
+            iv = (C.c_double * max(1, 2 * shapes.count))()
+            used = (C.c_uint8 * max(1, shapes.count))()
+            for s, v in enumerate(intervals):
+                if v is not None:
+                    lo, hi = v
+                    iv[2 * s], iv[2 * s + 1], used[s] = float(lo), float(hi), 1
+        h = C.c_void_p()
+        self.ctx._check(self.lib.pcv_query_batch_run(self.ctx.handle, shapes.handle, self.handle, iv, used, C.byref(h)))
+        return QueryBatch(self, h, shapes.count)
+
     def nodes_blob(self, node_indices):
         """octree_web_viewer's /nodes_data reply body for the given nodes."""
         idx = np.ascontiguousarray(node_indices, dtype=np.uint64)
@@ -933,6 +951,99 @@ class OctreeResult:
                              intensity=self.node_data(i, 2) if has_int else b"",
                              cube_min=tuple(nd.cube_min), cube_edge=nd.cube_edge)
         return out
+
+
+class QueryBatch:
+    """The result of OctreeResult.query_batch: segment k holds what query_points(shape, node=segment_node[k]) returns.
+    Holds its octree: the tree's device blobs are read when points are copied out."""
+
+    def __init__(self, tree, handle, num_shapes):
+        self.tree, self.ctx, self.lib, self.handle = tree, tree.ctx, tree.lib, handle
+        self.num_shapes = num_shapes
+        ns, npt = C.c_uint64(), C.c_uint64()
+        self.lib.pcv_query_batch_sizes(handle, C.byref(ns), C.byref(npt))
+        self.num_segments, self.num_points = ns.value, npt.value
+        self._has_int = bool(self.lib.pcv_octree_has_intensity(tree.handle))
+        self._segments = None
+        self.ctx._children.add(self)
+
+    def _live(self):
+        if not self.handle or not self.ctx.handle:
+            raise L.PcvError(L.PCV_E_INVALID, "the query batch was freed")
+        if not self.tree.handle:
+            raise L.PcvError(L.PCV_E_INVALID, "the query batch's octree was freed")
+
+    def segments(self):
+        """(shape_first[S + 1], node[num_segments], offset[num_segments + 1]) as numpy arrays (u64, u32, u64)."""
+        self._live()
+        if self._segments is None:
+            first = np.zeros(self.num_shapes + 1, dtype=np.uint64)
+            node = np.zeros(max(1, self.num_segments), dtype=np.uint32)
+            off = np.zeros(self.num_segments + 1, dtype=np.uint64)
+            self.ctx._check(self.lib.pcv_query_batch_segments(self.handle, first.ctypes.data, node.ctypes.data, off.ctypes.data))
+            self._segments = (first, node[:self.num_segments], off)
+        return self._segments
+
+    def points(self, first_segment=0, num_segments=None, out=None):
+        """The points of segments [first_segment, first_segment + num_segments) (default: to the end), as query_points
+        returns them. out: dict of x, y, z (f64), rgb (u8, 3 per point), optionally intensity — torch device tensors or numpy
+        arrays of at least `count` points — filled in place and returned in the result."""
+        self._live()
+        _, _, off = self.segments()
+        first = int(first_segment)
+        num = self.num_segments - first if num_segments is None else int(num_segments)
+        if not (0 <= first <= self.num_segments and 0 <= num <= self.num_segments - first):
+            # the library's own range check (PCV_E_INVALID, nothing written)
+            self.ctx._check(self.lib.pcv_query_batch_points(self.handle, max(first, 0), max(num, 0) or (1 << 63), 0, L.MEM_HOST,
+                                                            None, None, None, None, None))
+        n = int(off[first + num] - off[first])
+        if out is None:
+            x, y, z = np.zeros(n), np.zeros(n), np.zeros(n)
+            rgb = np.zeros((n, 3), dtype=np.uint8)
+            inten = np.zeros(n, dtype=np.float32) if self._has_int else None
+            mem, cap = L.MEM_HOST, n
+        else:
+            x, y, z, rgb, inten = out["x"], out["y"], out["z"], out["rgb"], out.get("intensity")
+            bufs = [_Buf(x, np.float64, "x"), _Buf(y, np.float64, "y"), _Buf(z, np.float64, "z"), _Buf(rgb, np.uint8, "rgb")]
+            if inten is not None:
+                bufs.append(_Buf(inten, np.float32, "intensity"))
+            if any(b.keep is not a for b, a in zip(bufs, (x, y, z, rgb, inten))):
+                raise TypeError("out: arrays must be contiguous and of the result's dtypes")
+            if len({b.device for b in bufs}) != 1:
+                raise ValueError("out: all host or all device")
+            mem = L.MEM_DEVICE if bufs[0].device else L.MEM_HOST
+            cap = min(bufs[0].size, bufs[1].size, bufs[2].size, bufs[3].size // 3, bufs[4].size if inten is not None else bufs[0].size)
+        ptr = lambda a: None if a is None else (a.data_ptr() if _is_torch(a) else a.ctypes.data)
+        if_int = inten if self._has_int else None
+        if mem == L.MEM_DEVICE:
+            self.ctx.wait_torch()
+        self.ctx._check(self.lib.pcv_query_batch_points(self.handle, first, num, cap, mem, ptr(x), ptr(y), ptr(z), ptr(rgb), ptr(if_int)))
+        return dict(count=n, x=x[:n], y=y[:n], z=z[:n], rgb=rgb[:n] if rgb.ndim == 2 else rgb[:3 * n],
+                    intensity=if_int[:n] if if_int is not None else None)
+
+    def shape_points(self, s):
+        """Everything shape s selected: its segments, concatenated (== query_points(shapes, s))."""
+        first, _, _ = self.segments()
+        return self.points(int(first[s]), int(first[s + 1] - first[s]))
+
+    def node_points(self, s, node):
+        """Shape s's points in one node of its nodes_in_location list (== query_points(shapes, s, node=node))."""
+        first, nodes, _ = self.segments()
+        hit = np.flatnonzero(nodes[int(first[s]):int(first[s + 1])] == node)
+        if hit.size == 0:
+            raise KeyError(f"node {node} is not among shape {s}'s nodes")
+        return self.points(int(first[s]) + int(hit[0]), 1)
+
+    def free(self):
+        if self.handle and self.ctx.handle:
+            self.lib.pcv_query_batch_free(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 def write_meta(directory, resolution, bbox_min, bbox_max, nodes):

@@ -41,6 +41,7 @@ pub struct PcvBuildParams {
 }
 
 #[repr(C)]
+#[derive(Clone, Copy)]
 pub struct PcvShape {
     kind: i32,
     reserved: i32,
@@ -71,6 +72,8 @@ type pcv_shapes = c_void;
 type pcv_ingest = c_void;
 #[allow(non_camel_case_types)]
 type pcv_ooc = c_void;
+#[allow(non_camel_case_types)]
+type pcv_query_batch = c_void;
 
 /// include/pcv_hip.h pcv_ooc_stats: what an out-of-core build did (points, nodes, partitions, host spill, link traffic, phase times).
 #[repr(C)]
@@ -126,6 +129,11 @@ extern "C" {
     fn pcv_nodes_in_location(ctx: *mut pcv_ctx, shapes: *const pcv_shapes, t: *mut pcv_octree, capacity: u32, counts: *mut u32, node_indices: *mut u32) -> c_int;
     fn pcv_query_node_points(ctx: *mut pcv_ctx, shapes: *const pcv_shapes, shape_index: u32, t: *mut pcv_octree, node: u64, interval: *const c_double, capacity: u64, mem: c_int, x: *mut c_double, y: *mut c_double, z: *mut c_double, rgb: *mut u8, intensity: *mut c_float, count: *mut u64) -> c_int;
     fn pcv_octree_has_intensity(t: *const pcv_octree) -> c_int;
+    fn pcv_query_batch_run(ctx: *mut pcv_ctx, shapes: *const pcv_shapes, t: *mut pcv_octree, intervals: *const c_double, interval_used: *const u8, out: *mut *mut pcv_query_batch) -> c_int;
+    fn pcv_query_batch_sizes(b: *const pcv_query_batch, num_segments: *mut u64, num_points: *mut u64) -> c_int;
+    fn pcv_query_batch_segments(b: *const pcv_query_batch, shape_first_segment: *mut u64, segment_node: *mut u32, segment_offset: *mut u64) -> c_int;
+    fn pcv_query_batch_points(b: *mut pcv_query_batch, first_segment: u64, num_segments: u64, capacity: u64, mem: c_int, x: *mut c_double, y: *mut c_double, z: *mut c_double, rgb: *mut u8, intensity: *mut c_float) -> c_int;
+    fn pcv_query_batch_free(b: *mut pcv_query_batch);
 }
 
 pub struct HipContext(*mut pcv_ctx);
@@ -334,7 +342,7 @@ pub fn get_visible_nodes(ctx: &HipContext, directory: &Path, projection_matrix: 
 pub struct HipOctree {
     ctx: HipContext,
     tree: *mut pcv_octree,
-    lock: Mutex<()>, // a pcv_ctx is not thread-safe; ParallelIterator calls from several workers
+    lock: Mutex<BatchCache>, // a pcv_ctx is not thread-safe; ParallelIterator calls from several workers
     ids: Vec<NodeId>,
     index_of: HashMap<NodeId, u64>,
     infos: Vec<PcvNodeInfo>,
@@ -367,7 +375,7 @@ impl HipOctree {
             infos.push(info);
         }
         let inner = Octree::from_data_provider(Box::new(OnDiskDataProvider { directory: directory.as_ref().to_path_buf() }))?;
-        Ok(HipOctree { ctx, tree, lock: Mutex::new(()), ids, index_of, infos, inner })
+        Ok(HipOctree { ctx, tree, lock: Mutex::new(BatchCache::default()), ids, index_of, infos, inner })
     }
 
     /// PointLocation -> pcv_shape (include/pcv_hip.h). None: a location the library has no kernel for.
@@ -411,7 +419,161 @@ impl HipOctree {
 
 impl Drop for HipOctree {
     fn drop(&mut self) {
+        for e in self.lock.get_mut().unwrap().entries.drain(..) {
+            unsafe { pcv_query_batch_free(e.batch) } // before the tree its points are read from
+        }
         unsafe { pcv_octree_free(self.tree) } // before the context (field order: ctx is dropped after this body)
+    }
+}
+
+/// One live pcv_query_batch: a query's points of every node of its location, culled once and kept on the device.
+struct BatchEntry {
+    key: String, // Debug form of (location, intervals, attributes)
+    batch: *mut pcv_query_batch,
+    node_segment: HashMap<u64, u64>, // node index -> segment (the segments of one shape)
+    offset: Vec<u64>,
+}
+
+/// The few most recent queries' batches: `stream_points_for_query_in_node` is called once per node of the same query.
+#[derive(Default)]
+struct BatchCache {
+    entries: Vec<BatchEntry>,
+}
+const BATCH_CACHE_ENTRIES: usize = 4;
+
+fn query_key(query: &PointQuery) -> String {
+    format!("{:?}|{:?}|{:?}", query.location, query.filter_intervals, query.attributes)
+}
+
+/// Shape + intensity interval of a query the library serves; None: the reference's host path.
+fn library_query(query: &PointQuery) -> Option<(PcvShape, Option<[f64; 2]>)> {
+    if !query.filter_intervals.keys().all(|k| *k == "intensity") {
+        return None; // an interval on another attribute
+    }
+    let shape = HipOctree::shape_of(&query.location)?;
+    Some((shape, query.filter_intervals.get("intensity").map(|iv| [iv.lower_bound, iv.upper_bound])))
+}
+
+/// Host arrays of n points handed to `callback` as PointsBatches of `batch_size` with the query's attributes.
+fn emit_points<F>(query: &PointQuery, p: &HostPoints, batch_size: usize, mut callback: F) -> Result<()>
+where
+    F: FnMut(PointsBatch) -> Result<()>,
+{
+    let want_intensity = query.attributes.contains(&"intensity");
+    let mut at = 0;
+    while at < p.n {
+        let end = (at + batch_size).min(p.n);
+        let position = (at..end).map(|i| Point3::new(p.x[i], p.y[i], p.z[i])).collect();
+        let mut attributes = BTreeMap::new();
+        if query.attributes.contains(&"color") {
+            attributes.insert("color".to_string(), AttributeData::U8Vec3((at..end).map(|i| Vector3::new(p.rgb[3 * i], p.rgb[3 * i + 1], p.rgb[3 * i + 2])).collect()));
+        }
+        if want_intensity {
+            attributes.insert("intensity".to_string(), AttributeData::F32(p.intensity[at..end].to_vec()));
+        }
+        callback(PointsBatch { position, attributes })?;
+        at = end;
+    }
+    Ok(())
+}
+
+struct HostPoints {
+    n: usize,
+    x: Vec<f64>,
+    y: Vec<f64>,
+    z: Vec<f64>,
+    rgb: Vec<u8>,
+    intensity: Vec<f32>,
+}
+
+impl HipOctree {
+    /// Runs one batch over `shapes` (with per-shape intensity intervals) and returns it with its segment table.
+    fn run_batch(&self, shapes: &[PcvShape], intervals: &[Option<[f64; 2]>]) -> (*mut pcv_query_batch, Vec<u64>, Vec<u32>, Vec<u64>) {
+        let mut handle = std::ptr::null_mut();
+        let mut prepared = std::ptr::null_mut();
+        self.ctx.check(unsafe { pcv_shapes_create(self.ctx.0, shapes.as_ptr(), shapes.len() as u32, &mut prepared) });
+        let flat: Vec<f64> = intervals.iter().flat_map(|iv| iv.unwrap_or([0.0, 0.0])).collect();
+        let used: Vec<u8> = intervals.iter().map(|iv| iv.is_some() as u8).collect();
+        let rc = unsafe { pcv_query_batch_run(self.ctx.0, prepared, self.tree, flat.as_ptr(), used.as_ptr(), &mut handle) };
+        unsafe { pcv_shapes_free(prepared) }; // the batch does not need the shapes
+        self.ctx.check(rc);
+        let (mut nseg, mut npts) = (0u64, 0u64);
+        self.ctx.check(unsafe { pcv_query_batch_sizes(handle, &mut nseg, &mut npts) });
+        let mut first = vec![0u64; shapes.len() + 1];
+        let mut node = vec![0u32; nseg as usize];
+        let mut offset = vec![0u64; nseg as usize + 1];
+        self.ctx.check(unsafe { pcv_query_batch_segments(handle, first.as_mut_ptr(), node.as_mut_ptr(), offset.as_mut_ptr()) });
+        (handle, first, node, offset)
+    }
+
+    /// One node through pcv_query_node_points (a node the query's location does not list). Called under `lock`.
+    fn node_points_single(&self, shape: &PcvShape, interval: Option<[f64; 2]>, node: u64, want_intensity: bool) -> HostPoints {
+        let cap = self.infos[node as usize].num_points as usize;
+        let mut p = HostPoints { n: 0, x: vec![0f64; cap], y: vec![0f64; cap], z: vec![0f64; cap], rgb: vec![0u8; 3 * cap], intensity: vec![0f32; if want_intensity { cap } else { 0 }] };
+        let has_int = unsafe { pcv_octree_has_intensity(self.tree) } != 0;
+        let mut count = 0u64;
+        self.with_shape(shape, |shapes| {
+            self.ctx.check(unsafe {
+                pcv_query_node_points(self.ctx.0, shapes, 0, self.tree, node, interval.as_ref().map_or(std::ptr::null(), |iv| iv.as_ptr()), cap as u64, 0,
+                                      p.x.as_mut_ptr(), p.y.as_mut_ptr(), p.z.as_mut_ptr(), p.rgb.as_mut_ptr(),
+                                      if want_intensity && has_int { p.intensity.as_mut_ptr() } else { std::ptr::null_mut() }, &mut count)
+            })
+        });
+        p.n = count as usize;
+        p
+    }
+
+    /// Segments [first, first + count) of a batch to host arrays.
+    fn batch_points(&self, batch: *mut pcv_query_batch, offset: &[u64], first: u64, count: u64, want_intensity: bool) -> HostPoints {
+        let n = (offset[(first + count) as usize] - offset[first as usize]) as usize;
+        let mut p = HostPoints { n, x: vec![0f64; n], y: vec![0f64; n], z: vec![0f64; n], rgb: vec![0u8; 3 * n], intensity: vec![0f32; if want_intensity { n } else { 0 }] };
+        if n > 0 {
+            let has_int = unsafe { pcv_octree_has_intensity(self.tree) } != 0;
+            self.ctx.check(unsafe {
+                pcv_query_batch_points(batch, first, count, n as u64, 0, p.x.as_mut_ptr(), p.y.as_mut_ptr(), p.z.as_mut_ptr(), p.rgb.as_mut_ptr(),
+                                       if want_intensity && has_int { p.intensity.as_mut_ptr() } else { std::ptr::null_mut() })
+            });
+        }
+        p
+    }
+
+    /// xray-style tile batches: the points of every query, `f(query index, batch)` in query order. The queries the library
+    /// serves go through pcv_query_batch_run together; the others keep the reference's host path, node by node.
+    pub fn query_many<F>(&self, queries: &[PointQuery], batch_size: usize, mut f: F) -> Result<()>
+    where
+        F: FnMut(usize, PointsBatch) -> Result<()>,
+    {
+        let served: Vec<Option<(PcvShape, Option<[f64; 2]>)>> = queries.iter().map(library_query).collect();
+        let shapes: Vec<PcvShape> = served.iter().flatten().map(|(s, _)| *s).collect();
+        let intervals: Vec<Option<[f64; 2]>> = served.iter().flatten().map(|(_, iv)| *iv).collect();
+        let mut batch = None;
+        if !shapes.is_empty() {
+            let _g = self.lock.lock().unwrap();
+            batch = Some(self.run_batch(&shapes, &intervals));
+        }
+        let mut s = 0usize;
+        let mut result = Ok(());
+        for (q, query) in queries.iter().enumerate() {
+            result = if served[q].is_some() {
+                let (handle, first, _, offset) = batch.as_ref().unwrap();
+                let p = {
+                    let _g = self.lock.lock().unwrap();
+                    self.batch_points(*handle, offset, first[s], first[s + 1] - first[s], query.attributes.contains(&"intensity"))
+                };
+                s += 1;
+                emit_points(query, &p, batch_size, |b| f(q, b))
+            } else {
+                self.nodes_in_location(&query.location).into_iter().try_for_each(|id| self.stream_points_for_query_in_node(query, id, batch_size, |b| f(q, b)))
+            };
+            if result.is_err() {
+                break;
+            }
+        }
+        if let Some((handle, ..)) = batch {
+            let _g = self.lock.lock().unwrap();
+            unsafe { pcv_query_batch_free(handle) };
+        }
+        result
     }
 }
 
@@ -461,56 +623,42 @@ impl PointCloud for HipOctree {
     where
         F: FnMut(PointsBatch) -> Result<()>,
     {
-        let only_intensity = query.filter_intervals.keys().all(|k| *k == "intensity");
-        let shape = match (Self::shape_of(&query.location), only_intensity) {
-            (Some(s), true) => s,
-            _ => {
+        let (shape, interval) = match library_query(query) {
+            Some(v) => v,
+            None => {
                 // no kernel for this location / an interval on another attribute: the reference's host path
                 let it = self.inner.points_in_node(&query.attributes, node_id, batch_size)?;
                 return point_viewer::iterator::stream_dispatch(&query.location, &query.filter_intervals, it, callback);
             }
         };
         let node = self.index_of[&node_id];
-        let cap = self.infos[node as usize].num_points as usize;
-        if cap == 0 {
+        if self.infos[node as usize].num_points == 0 {
             return Ok(());
         }
-        let interval = query.filter_intervals.get("intensity").map(|iv| [iv.lower_bound, iv.upper_bound]);
-        let (mut x, mut y, mut z) = (vec![0f64; cap], vec![0f64; cap], vec![0f64; cap]);
-        let mut rgb = vec![0u8; 3 * cap];
-        let want_intensity = query.attributes.contains(&"intensity");
-        let mut inten = vec![0f32; if want_intensity { cap } else { 0 }];
-        let mut count = 0u64;
-        {
-            let _g = self.lock.lock().unwrap();
-            let has_int = unsafe { pcv_octree_has_intensity(self.tree) } != 0;
-            self.with_shape(&shape, |shapes| {
-                self.ctx.check(unsafe {
-                    pcv_query_node_points(
-                        self.ctx.0, shapes, 0, self.tree, node,
-                        interval.as_ref().map_or(std::ptr::null(), |iv| iv.as_ptr()),
-                        cap as u64, 0, x.as_mut_ptr(), y.as_mut_ptr(), z.as_mut_ptr(), rgb.as_mut_ptr(),
-                        if want_intensity && has_int { inten.as_mut_ptr() } else { std::ptr::null_mut() }, &mut count,
-                    )
-                })
-            });
-        }
-        let n = count as usize;
-        let mut at = 0;
-        while at < n {
-            let end = (at + batch_size).min(n);
-            let position = (at..end).map(|i| Point3::new(x[i], y[i], z[i])).collect();
-            let mut attributes = BTreeMap::new();
-            if query.attributes.contains(&"color") {
-                attributes.insert("color".to_string(), AttributeData::U8Vec3((at..end).map(|i| Vector3::new(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2])).collect()));
+        // one pcv_query_batch_run per distinct query (ParallelIterator hands its nodes over one by one); each node then costs
+        // one copy of its segment — no shape, no cull
+        let key = query_key(query);
+        let points = {
+            let mut cache = self.lock.lock().unwrap();
+            let k = match cache.entries.iter().position(|e| e.key == key) {
+                Some(k) => k,
+                None => {
+                    let (batch, _, nodes, offset) = self.run_batch(&[shape], &[interval]);
+                    let node_segment = nodes.iter().enumerate().map(|(k, &n)| (n as u64, k as u64)).collect();
+                    if cache.entries.len() == BATCH_CACHE_ENTRIES {
+                        unsafe { pcv_query_batch_free(cache.entries.remove(0).batch) };
+                    }
+                    cache.entries.push(BatchEntry { key, batch, node_segment, offset });
+                    cache.entries.len() - 1
+                }
+            };
+            let e = &cache.entries[k];
+            match e.node_segment.get(&node) {
+                Some(&seg) => self.batch_points(e.batch, &e.offset, seg, 1, query.attributes.contains(&"intensity")),
+                None => self.node_points_single(&shape, interval, node, query.attributes.contains(&"intensity")), // not in the location's list
             }
-            if want_intensity {
-                attributes.insert("intensity".to_string(), AttributeData::F32(inten[at..end].to_vec()));
-            }
-            callback(PointsBatch { position, attributes })?;
-            at = end;
-        }
-        Ok(())
+        };
+        emit_points(query, &points, batch_size, callback)
     }
 }
 
