@@ -635,6 +635,78 @@ int pcv_query_batch_points(pcv_query_batch* b, uint64_t first_segment, uint64_t 
                            double* x, double* y, double* z, uint8_t* rgb, float* intensity);
 void pcv_query_batch_free(pcv_query_batch* b);
 
+/* ---- xray leaf tiles (xray/src/generation.rs) ----------------------------------------------------------------------
+ * The leaf level of build_xray_quadtree (:557-600) for one octree: the quadtree geometry on the host, one point query per
+ * leaf tile through pcv_query_batch_run, and the points rasterised on the device into RGBA8 tiles that stay there. */
+#define PCV_XRAY_XRAY 0          /* XRayColoringStrategy (:159-199): distinct z buckets per pixel */
+#define PCV_XRAY_COLORED 1       /* PointColorColoringStrategy without binning (:294-345) */
+#define PCV_XRAY_HEIGHT_STDDEV 2 /* HeightStddevColoringStrategy (:365-408) */
+#define PCV_XRAY_JET 0           /* colormap.rs Jet */
+#define PCV_XRAY_PURPLISH 1      /* colormap.rs Monochrome(PURPLISH) */
+#define PCV_XRAY_BG_WHITE 0      /* TileBackgroundColorArgument (:46-55) */
+#define PCV_XRAY_BG_TRANSPARENT 1
+
+/* XrayParameters (:452-461) + the coloring strategy. Binning, ColoredWithIntensity, parent levels, several octrees and
+ * filters on attributes other than intensity are not offered. */
+typedef struct pcv_xray_params {
+  uint32_t tile_size_px;        /* W = H, 1 ..= 32768 */
+  uint32_t strategy;            /* PCV_XRAY_XRAY / _COLORED / _HEIGHT_STDDEV */
+  uint32_t colormap;            /* height_stddev: PCV_XRAY_JET / PCV_XRAY_PURPLISH */
+  uint32_t background;          /* PCV_XRAY_BG_WHITE / PCV_XRAY_BG_TRANSPARENT: assign_background_color (:684) */
+  double pixel_size_m;
+  float max_stddev;             /* height_stddev: > 0 */
+  uint32_t root_level;          /* root_node_id (quadtree NodeId): level and index; r = (0, 0) */
+  uint64_t root_index;
+  int32_t has_query_from_global;
+  int32_t reserved;
+  double query_from_global[7];  /* Isometry3: translation xyz, unit quaternion ijkw */
+  const char* interval_attribute; /* NULL: no filter; "intensity": ClosedInterval [interval[0], interval[1]] on every tile */
+  double interval[2];
+  uint64_t max_workspace_bytes; /* device workspace of one tile group (records + bucket tables); 0: 2 GiB */
+} pcv_xray_params;
+typedef struct pcv_xray pcv_xray;
+
+/* Host only, no context: get_bounding_box (:550, Aabb::transform aabb.rs:58-66 with an isometry),
+ * find_quadtree_bounding_rect_and_levels (:515), Node::from_node_id_and_root_bounding_rect + get_child
+ * (quadtree/src/lib.rs:59-97) and get_nodes_at_level (:534) below (root_level, root_index). rect = min x, min y, edge.
+ * *num_leaves = 4^(deepest_level - root_level); the first `capacity` leaves are written in get_nodes_at_level's order:
+ * leaf_index (their NodeId index at deepest_level), tile_bbox (6 per leaf: the Aabb of create_leaf_nodes :625-629, min xyz,
+ * max xyz) and, with an isometry, query_obb (10 per leaf: Obb::from(tile).transformed(global_from_query) of
+ * xray_from_points :470-476 as a pcv_shape OBB: translation, quaternion ijkw, half extent). More than 2^24 leaves, a
+ * root_node_id outside the quadtree, tile_size_px == 0 or pixel_size_m <= 0 is PCV_E_INVALID (message in err). */
+int pcv_xray_leaf_tiles(uint32_t tile_size_px, double pixel_size_m, const double bbox_min[3], const double bbox_max[3],
+                        const double* query_from_global, uint32_t root_level, uint64_t root_index, uint64_t capacity, double rect[3],
+                        uint32_t* deepest_level, uint64_t* num_leaves, uint64_t* leaf_index, double* tile_bbox, double* query_obb,
+                        char* err, uint64_t errcap);
+/* create_leaf_nodes (:618-648) + assign_background_color (:684) for the whole leaf level of `tree` (its meta bounding box).
+ * A tile is created iff its query kept a point (xray_from_points :499-501); a created tile whose points all fall outside
+ * its image is all background. The images stay on the device. An unknown strategy / colormap / background,
+ * max_stddev <= 0, a filter attribute other than "intensity", a filter on an octree without intensity and more than 2^24
+ * leaves are PCV_E_INVALID; a tile whose records alone exceed max_workspace_bytes is PCV_E_OOM. */
+int pcv_xray_run(pcv_ctx* ctx, pcv_octree* tree, const pcv_xray_params* params, pcv_xray** out);
+/* Host only, no context: the parameter checks pcv_xray_run makes before any device work (strategy, colormap,
+ * max_stddev, background, filter attribute; tree_has_intensity: whether the octree carries intensity). PCV_E_INVALID
+ * with a message in err, or PCV_OK. */
+int pcv_xray_check_params(const pcv_xray_params* params, int tree_has_intensity, char* err, uint64_t errcap);
+int pcv_xray_info(const pcv_xray* x, uint32_t* deepest_level, double rect[3], uint64_t* num_leaves, uint64_t* num_created);
+/* Host arrays, each nullable: leaf_index (num_leaves: the leaf list), created (num_created: positions in the leaf list, in
+ * leaf order), kept (points the tile's query kept) and drawn (points that landed inside the image). */
+int pcv_xray_tiles(const pcv_xray* x, uint64_t* leaf_index, uint64_t* created, uint64_t* kept, uint64_t* drawn);
+/* Created tiles [first, first + count) as RGBA8, W x W each, rows top to bottom (RgbaImage), into `capacity` bytes
+ * that live where `mem` says. */
+int pcv_xray_images(pcv_xray* x, uint64_t first, uint64_t count, uint64_t capacity, int mem, uint8_t* rgba);
+void pcv_xray_free(pcv_xray* x);
+/* The finalisation functions of the raster kernel, on the host (same code): fn = PCV_XRAY_FN_XRAY: in[i] = number of
+ * distinct z buckets (0: no point); _COLORED: in[4i..4i+3] = exact r, g, b sums and the point count; _JET / _PURPLISH:
+ * in[i] = value in [0, 1] (as f32); _TO_U8: in[4i..4i+3] = a Color<f32> (src/color.rs:29-36). Writes count RGBA8 pixels
+ * before any background is applied. */
+#define PCV_XRAY_FN_XRAY 0
+#define PCV_XRAY_FN_COLORED 1
+#define PCV_XRAY_FN_JET 2
+#define PCV_XRAY_FN_PURPLISH 3
+#define PCV_XRAY_FN_TO_U8 4
+int pcv_xray_finalize(int fn, uint64_t count, const double* in, uint8_t* rgba);
+
 /* The `/nodes_data` reply blob of octree_web_viewer (octree_web_viewer/src/backend.rs:90-177) for a list of nodes:
  * per node min xyz (3 x f64 LE), edge (f64), num_points (u32), bytes per coordinate (u8), pad to 8, raw .xyz, pad
  * to 8, raw .rgb, pad to 8. *needed = blob size; the blob is written when out != NULL and capacity >= *needed. */

@@ -6,9 +6,9 @@ libpcv_hip.so (point_cloud_viewer_amd/csrc). Importing does not require a GPU; c
 from . import _lib
 from ._lib import (PCV_E_DEPTH, PCV_E_HIP, PCV_E_INVALID, PCV_E_IO, PCV_E_NOT_FOUND, PCV_E_OOM, PCV_OK,  # noqa: F401
                    PcvError, load_library)
-from .octree import (Aabb, Context, OctreeResult, QueryBatch, Shapes, build_octree, build_octree_from_file, level_shortcuts,  # noqa: F401
-                     level_table,
-                     node_name, read_ply)
+from .octree import (Aabb, Context, OctreeResult, QueryBatch, Shapes, XrayTiles, build_octree, build_octree_from_file,  # noqa: F401
+                     level_shortcuts, level_table, node_name, quadtree_node_id, quadtree_node_name, read_ply, xray_check_params,
+                     xray_finalize, xray_leaf_tiles, xray_params)
 
-__all__ = ["Aabb", "Context", "OctreeResult", "QueryBatch", "build_octree", "level_table", "node_name", "PcvError",
+__all__ = ["Aabb", "Context", "OctreeResult", "QueryBatch", "XrayTiles", "build_octree", "level_table", "node_name", "PcvError",
            "load_library"]

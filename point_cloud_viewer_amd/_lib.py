@@ -58,6 +58,19 @@ class Shape(C.Structure):
 
 
 SHAPE_ALL, SHAPE_AABB, SHAPE_FRUSTUM, SHAPE_OBB, SHAPE_FRUSTUM_WITH_INVERSE = 0, 1, 2, 3, 4
+
+
+class XrayParams(C.Structure):
+    _fields_ = [("tile_size_px", C.c_uint32), ("strategy", C.c_uint32), ("colormap", C.c_uint32), ("background", C.c_uint32),
+                ("pixel_size_m", C.c_double), ("max_stddev", C.c_float), ("root_level", C.c_uint32), ("root_index", C.c_uint64),
+                ("has_query_from_global", C.c_int32), ("reserved", C.c_int32), ("query_from_global", C.c_double * 7),
+                ("interval_attribute", C.c_char_p), ("interval", C.c_double * 2), ("max_workspace_bytes", C.c_uint64)]
+
+
+XRAY_XRAY, XRAY_COLORED, XRAY_HEIGHT_STDDEV = 0, 1, 2
+XRAY_JET, XRAY_PURPLISH = 0, 1
+XRAY_BG_WHITE, XRAY_BG_TRANSPARENT = 0, 1
+XRAY_FN_XRAY, XRAY_FN_COLORED, XRAY_FN_JET, XRAY_FN_PURPLISH, XRAY_FN_TO_U8 = 0, 1, 2, 3, 4
 REL_IN, REL_CROSS, REL_OUT = 0, 1, 2
 
 
@@ -217,6 +230,16 @@ _SIGNATURES = {
     "pcv_query_batch_segments": (C.c_int, [_vp, _vp, _vp, _vp]),
     "pcv_query_batch_points": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "pcv_query_batch_free": (None, [_vp]),
+    "pcv_xray_leaf_tiles": (C.c_int, [C.c_uint32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                      C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_uint32),
+                                      C.POINTER(C.c_uint64), _vp, _vp, _vp, C.c_char_p, C.c_uint64]),
+    "pcv_xray_run": (C.c_int, [_vp, _vp, C.POINTER(XrayParams), C.POINTER(_vp)]),
+    "pcv_xray_check_params": (C.c_int, [C.POINTER(XrayParams), C.c_int, C.c_char_p, C.c_uint64]),
+    "pcv_xray_info": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "pcv_xray_tiles": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "pcv_xray_images": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _vp]),
+    "pcv_xray_free": (None, [_vp]),
+    "pcv_xray_finalize": (C.c_int, [C.c_int, C.c_uint64, _vp, _vp]),
     "pcv_octree_nodes_blob": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pcv_transform_points": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(Points), _vp, _vp, _vp]),
 }

@@ -126,6 +126,9 @@ enum PcvKernelId {
   PCV_K_QUERY_BATCH_FLAGS,    // pcv_query_batch_run: keep flags of every chunk of every shape
   PCV_K_QUERY_BATCH_SCAN,     // pcv_query_batch_run: the u64 scans (segments, flags, chunks, kept points)
   PCV_K_QUERY_BATCH_COMPACT,  // pcv_query_batch_points: stable compaction of a segment range
+  PCV_K_XRAY_BIN,             // pcv_xray_run: drawable points per (tile, pixel block)
+  PCV_K_XRAY_SCATTER,         // pcv_xray_run: one record per drawable point into its bucket
+  PCV_K_XRAY_ACCUM,           // pcv_xray_run: per-pixel state in LDS, colour, background, RGBA rows
   PCV_K_COUNT
 };
 

@@ -20,21 +20,11 @@
 #include <cstring>
 #include <vector>
 
-#include "pcv_chain_dev.h"
+#include "pcv_query_dev.h"
 
 // ---------------------------------------------------------------------------------------------
 // device math
 // ---------------------------------------------------------------------------------------------
-struct V3d {
-  double x, y, z;
-};
-__host__ __device__ __forceinline__ V3d v_sub(V3d a, V3d b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__host__ __device__ __forceinline__ V3d v_add(V3d a, V3d b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__host__ __device__ __forceinline__ double v_dot(V3d a, V3d b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__host__ __device__ __forceinline__ V3d v_cross(V3d a, V3d b) {
-  return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-__host__ __device__ __forceinline__ V3d v_scale(V3d a, double s) { return {a.x * s, a.y * s, a.z * s}; }
 __device__ __forceinline__ V3d v_normalize(V3d v) {
   double n = sqrt(v_dot(v, v));
   return {v.x / n, v.y / n, v.z / n};
@@ -76,12 +66,6 @@ __device__ __forceinline__ V3d m4_transform_point(const double* m, V3d p) {
   return {r0, r1, r2};
 }
 
-__device__ __forceinline__ V3d quat_rotate(const double* q, V3d v) {  // UnitQuaternion * Vector3
-  V3d qv = {q[0], q[1], q[2]};
-  V3d t = v_scale(v_cross(qv, v), 2.0);
-  V3d c = v_cross(qv, t);
-  return v_add(v_add(v_scale(t, q[3]), c), v);
-}
 
 // ---------------------------------------------------------------------------------------------
 // prepared shapes
@@ -792,55 +776,6 @@ __global__ __launch_bounds__(64) void nodes_in_location_kernel(const PcvShapeDev
   counts[f] = nout;
 }
 
-// K8: keep mask. Positions either raw f64 SoA or a node's encoded bytes.
-struct PointsView {
-  uint64_t n;
-  const double *x, *y, *z;
-  const uint8_t* encoded;  // non-null: node bytes, `enc`, cube
-  uint32_t enc;
-  double cube_min[3];
-  double cube_edge;
-  const float* attr;       // optional f32 attribute with closed interval
-  double lo, hi;
-  int has_interval;
-};
-
-__device__ __forceinline__ V3d load_point(const PointsView& v, uint64_t i) {
-  if (!v.encoded) return {v.x[i], v.y[i], v.z[i]};
-  uint64_t c[3];
-  switch (v.enc) {
-    case PCV_ENC_UINT8: {
-      const uint8_t* p = v.encoded + 3 * i;
-      c[0] = p[0];
-      c[1] = p[1];
-      c[2] = p[2];
-      break;
-    }
-    case PCV_ENC_UINT16: {
-      const uint16_t* p = reinterpret_cast<const uint16_t*>(v.encoded) + 3 * i;
-      c[0] = p[0];
-      c[1] = p[1];
-      c[2] = p[2];
-      break;
-    }
-    case PCV_ENC_FLOAT32: {
-      const uint32_t* p = reinterpret_cast<const uint32_t*>(v.encoded) + 3 * i;
-      c[0] = p[0];
-      c[1] = p[1];
-      c[2] = p[2];
-      break;
-    }
-    default: {
-      const uint64_t* p = reinterpret_cast<const uint64_t*>(v.encoded) + 3 * i;
-      c[0] = p[0];
-      c[1] = p[1];
-      c[2] = p[2];
-      break;
-    }
-  }
-  return {pcv_decode_coord(v.enc, c[0], v.cube_min[0], v.cube_edge), pcv_decode_coord(v.enc, c[1], v.cube_min[1], v.cube_edge),
-          pcv_decode_coord(v.enc, c[2], v.cube_min[2], v.cube_edge)};
-}
 
 // What contains() needs of a shape, fetched once per wave (wave-uniform: it lives in scalar registers) instead of
 // once per point: the clip matrix (frustum), mins / maxs (AABB) or isometry + half extents (OBB). The point kernels
@@ -1117,18 +1052,6 @@ struct QueryJob {
   uint32_t pad;
 };
 
-// pass 0 writes one descriptor per chunk, so that pass 1 has a single scalar load between "which chunk" and the
-// staging loads
-struct ChunkDesc {
-  uint64_t src;         // offset of the chunk's first encoded byte in the xyz blob
-  uint64_t attr_index;  // index of its first point in the rgb / intensity blobs
-  double cube_min[3];
-  double cube_edge;
-  uint64_t keep_off;  // offset of its first flag
-  uint32_t enc;
-  uint32_t cnt;  // points
-};
-static_assert(sizeof(ChunkDesc) == 64, "one descriptor per s_load_dwordx16");
 
 // the descriptor of chunk c, which belongs to job jb; chunks hold (LDS slice / stride) >> shift points
 __host__ __device__ inline ChunkDesc make_chunk_desc(const QueryJob& jb, uint32_t c, uint32_t shift) {
@@ -2067,7 +1990,6 @@ struct BatchIval {  // ClosedInterval of one shape on intensity
   double lo, hi;
   uint32_t used, pad;
 };
-constexpr uint32_t kBatchShapeBits = 24;  // ChunkDesc::enc = encoding | kind << 4 | shape << 8
 
 // per segment: flags (padded to 4, so that every segment's flags start on a dword) and chunks at shift 0, 1, 2
 __global__ __launch_bounds__(256) void batch_seg_sizes_kernel(const uint32_t* __restrict__ seg_node, uint64_t nseg,
@@ -2316,20 +2238,7 @@ int batch_scan(pcv_ctx* ctx, PcvScratch& sc, const uint32_t* in, uint64_t n, uin
 
 }  // namespace
 
-struct pcv_query_batch {
-  pcv_ctx* ctx = nullptr;
-  pcv_octree* tree = nullptr;  // read by pcv_query_batch_points, never by pcv_query_batch_free
-  bool has_intensity = false;
-  uint32_t nshapes = 0;
-  uint64_t nseg = 0, npoints = 0, nchunks = 0;
-  std::vector<uint64_t> shape_first;  // S + 1
-  std::vector<uint64_t> seg_chunk;    // nseg + 1: first chunk of each segment
-  std::vector<uint64_t> seg_off;      // nseg + 1: first point of each segment
-  uint32_t* d_seg_node = nullptr;
-  void* d_desc = nullptr;  // ChunkDesc[nchunks]
-  uint8_t* d_keep = nullptr;
-  uint64_t* d_chunk_off = nullptr;  // nchunks + 1
-};
+int pcv_batch_scan(pcv_ctx* ctx, PcvScratch& sc, const uint32_t* in, uint64_t n, uint64_t* out) { return batch_scan(ctx, sc, in, n, out); }
 
 extern "C" void pcv_query_batch_free(pcv_query_batch* b) {
   if (!b) return;

@@ -899,6 +899,18 @@ class OctreeResult:
         self.ctx._check(self.lib.pcv_query_batch_run(self.ctx.handle, shapes.handle, self.handle, iv, used, C.byref(h)))
         return QueryBatch(self, h, shapes.count)
 
+    def xray_tiles(self, tile_size_px=256, pixel_size_m=None, strategy="xray", query_from_global=None, intensity_interval=None,
+                   background="white", root_node_id="r", max_workspace_bytes=None):
+        """The leaf level of xray's build_xray_quadtree (xray/src/generation.rs:557-648) rasterised on the device.
+        strategy: "xray", "colored" or ("height_stddev", max_stddev, "jet" | "purplish"); query_from_global: None or
+        translation xyz + unit quaternion ijkw; intensity_interval: None or (lo, hi); background: "white" | "transparent";
+        root_node_id: a quadtree node name ("r" + base-4 digits). Returns an XrayTiles; its images stay on the device."""
+        p = xray_params(tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background, root_node_id,
+                        max_workspace_bytes)
+        h = C.c_void_p()
+        self.ctx._check(self.lib.pcv_xray_run(self.ctx.handle, self.handle, C.byref(p), C.byref(h)))
+        return XrayTiles(self.ctx, h, int(tile_size_px))
+
     def nodes_blob(self, node_indices):
         """octree_web_viewer's /nodes_data reply body for the given nodes."""
         idx = np.ascontiguousarray(node_indices, dtype=np.uint64)
@@ -1037,6 +1049,154 @@ class QueryBatch:
     def free(self):
         if self.handle and self.ctx.handle:
             self.lib.pcv_query_batch_free(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def xray_params(tile_size_px=256, pixel_size_m=None, strategy="xray", query_from_global=None, intensity_interval=None,
+                background="white", root_node_id="r", max_workspace_bytes=None):
+    """The pcv_xray_params of OctreeResult.xray_tiles (same arguments); unknown names raise ValueError."""
+    if pixel_size_m is None:
+        raise ValueError("pixel_size_m is required")
+    p = L.XrayParams()
+    p.tile_size_px, p.pixel_size_m = int(tile_size_px), float(pixel_size_m)
+    if isinstance(strategy, str):
+        kinds = {"xray": L.XRAY_XRAY, "colored": L.XRAY_COLORED}
+        if strategy not in kinds:
+            raise ValueError(f"unknown strategy {strategy!r}")
+        p.strategy = kinds[strategy]
+    else:
+        kind, max_stddev, cmap = strategy
+        if kind != "height_stddev" or cmap not in ("jet", "purplish"):
+            raise ValueError(f"unknown strategy {strategy!r}")
+        p.strategy, p.max_stddev = L.XRAY_HEIGHT_STDDEV, float(max_stddev)
+        p.colormap = L.XRAY_JET if cmap == "jet" else L.XRAY_PURPLISH
+    if background not in ("white", "transparent"):
+        raise ValueError(f"unknown background {background!r}")
+    p.background = L.XRAY_BG_WHITE if background == "white" else L.XRAY_BG_TRANSPARENT
+    p.root_level, p.root_index = quadtree_node_id(root_node_id)
+    if query_from_global is not None:
+        p.has_query_from_global = 1
+        for i, v in enumerate(query_from_global):
+            p.query_from_global[i] = float(v)
+    if intensity_interval is not None:
+        p.interval_attribute = b"intensity"
+        p.interval[0], p.interval[1] = float(intensity_interval[0]), float(intensity_interval[1])
+    p.max_workspace_bytes = int(max_workspace_bytes or 0)
+    return p
+
+
+def xray_check_params(params, tree_has_intensity=True):
+    """pcv_xray_check_params (host only): raises PcvError for what pcv_xray_run would refuse before any device work."""
+    err = C.create_string_buffer(256)
+    rc = L.load_library().pcv_xray_check_params(C.byref(params), int(bool(tree_has_intensity)), err, 256)
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, err.value.decode())
+
+
+def quadtree_node_id(name):
+    """quadtree NodeId from its Display form ("r" + base-4 digits, quadtree/src/lib.rs:199-234) -> (level, index)."""
+    if not name or name[0] != "r" or any(c not in "0123" for c in name[1:]):
+        raise ValueError(f"not a quadtree node id: {name!r}")
+    return len(name) - 1, (int(name[1:], 4) if len(name) > 1 else 0)
+
+
+def quadtree_node_name(level, index):
+    """NodeId's Display (quadtree/src/lib.rs:218-234): "r" and one base-4 digit per level, most significant first."""
+    return "r" + "".join(str((int(index) >> (2 * l)) & 3) for l in range(int(level) - 1, -1, -1))
+
+
+def xray_leaf_tiles(tile_size_px, pixel_size_m, bbox_min, bbox_max, query_from_global=None, root_node_id="r"):
+    """pcv_xray_leaf_tiles (host only): dict(rect=(min x, min y, edge), deepest_level, leaf_index (u64), leaf_ids,
+    tile_bbox (n x 6: min xyz, max xyz), query_obb (n x 10, with an isometry; else None))."""
+    level, index = quadtree_node_id(root_node_id)
+    lib = L.load_library()
+    d3 = lambda v: (C.c_double * 3)(*[float(a) for a in v])
+    iso = (C.c_double * 7)(*[float(a) for a in query_from_global]) if query_from_global is not None else None
+    rect, deepest, n = (C.c_double * 3)(), C.c_uint32(), C.c_uint64()
+    err = C.create_string_buffer(256)
+    rc = lib.pcv_xray_leaf_tiles(int(tile_size_px), float(pixel_size_m), d3(bbox_min), d3(bbox_max), iso, level, index, 0, rect,
+                                 C.byref(deepest), C.byref(n), None, None, None, err, 256)
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, err.value.decode())
+    cnt = n.value
+    idx = np.zeros(max(cnt, 1), dtype=np.uint64)
+    boxes = np.zeros((max(cnt, 1), 6))
+    obb = np.zeros((max(cnt, 1), 10)) if iso is not None else None
+    rc = lib.pcv_xray_leaf_tiles(int(tile_size_px), float(pixel_size_m), d3(bbox_min), d3(bbox_max), iso, level, index, cnt, rect,
+                                 C.byref(deepest), C.byref(n), idx.ctypes.data, boxes.ctypes.data,
+                                 obb.ctypes.data if obb is not None else None, err, 256)
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, err.value.decode())
+    return dict(rect=tuple(rect), deepest_level=deepest.value, leaf_index=idx[:cnt],
+                leaf_ids=[quadtree_node_name(deepest.value, i) for i in idx[:cnt]], tile_bbox=boxes[:cnt],
+                query_obb=obb[:cnt] if obb is not None else None)
+
+
+def xray_finalize(fn, values):
+    """pcv_xray_finalize: the raster kernel's colour functions on the host. fn: "xray" (values = distinct z bucket counts),
+    "colored" (n x 4: exact r, g, b sums, count), "jet" / "purplish" (values in [0, 1]), "to_u8" (n x 4 f32 colours).
+    Returns (n, 4) uint8 RGBA, before any background."""
+    fns = {"xray": L.XRAY_FN_XRAY, "colored": L.XRAY_FN_COLORED, "jet": L.XRAY_FN_JET, "purplish": L.XRAY_FN_PURPLISH,
+           "to_u8": L.XRAY_FN_TO_U8}
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    n = v.shape[0] if v.ndim else 1
+    out = np.zeros((n, 4), dtype=np.uint8)
+    rc = L.load_library().pcv_xray_finalize(fns[fn], n, v.ctypes.data, out.ctypes.data)
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, f"pcv_xray_finalize({fn})")
+    return out
+
+
+class XrayTiles:
+    """The result of OctreeResult.xray_tiles: the leaf list of the quadtree and the created tiles' RGBA8 images (device)."""
+
+    def __init__(self, ctx, handle, tile_size_px):
+        self.ctx, self.lib, self.handle, self.tile_size_px = ctx, ctx.lib, handle, tile_size_px
+        dl, rect, nl, nc = C.c_uint32(), (C.c_double * 3)(), C.c_uint64(), C.c_uint64()
+        self.lib.pcv_xray_info(handle, C.byref(dl), rect, C.byref(nl), C.byref(nc))
+        self.deepest_level, self.bounding_rect = dl.value, tuple(rect)
+        self.leaf_index = np.zeros(max(nl.value, 1), dtype=np.uint64)
+        self.created = np.zeros(max(nc.value, 1), dtype=np.uint64)
+        self.kept = np.zeros(max(nc.value, 1), dtype=np.uint64)
+        self.drawn = np.zeros(max(nc.value, 1), dtype=np.uint64)
+        self.lib.pcv_xray_tiles(handle, self.leaf_index.ctypes.data, self.created.ctypes.data, self.kept.ctypes.data,
+                                self.drawn.ctypes.data)
+        self.leaf_index, self.created = self.leaf_index[:nl.value], self.created[:nc.value]
+        self.kept, self.drawn = self.kept[:nc.value], self.drawn[:nc.value]
+        self.leaf_ids = [quadtree_node_name(self.deepest_level, i) for i in self.leaf_index]
+        self.created_ids = [self.leaf_ids[int(c)] for c in self.created]
+        self.num_created = int(nc.value)
+        ctx._children.add(self)
+
+    def images(self, first=0, count=None, device=False):
+        """Created tiles [first, first + count) as a (count, H, W, 4) uint8 array (numpy, or a torch tensor on the
+        context's device with device=True); rows top to bottom."""
+        if not self.handle or not self.ctx.handle:
+            raise L.PcvError(L.PCV_E_INVALID, "the xray tiles were freed")
+        count = self.num_created - int(first) if count is None else int(count)
+        W = self.tile_size_px
+        if device:
+            import torch
+            out = torch.empty((max(count, 0), W, W, 4), dtype=torch.uint8, device=f"cuda:{self.ctx.device}")
+            ptr, cap, mem = out.data_ptr(), out.numel(), L.MEM_DEVICE
+        else:
+            out = np.zeros((max(count, 0), W, W, 4), dtype=np.uint8)
+            ptr, cap, mem = out.ctypes.data, out.nbytes, L.MEM_HOST
+        self.ctx._check(self.lib.pcv_xray_images(self.handle, int(first), count, cap, mem, ptr))
+        return out
+
+    def image(self, i):
+        return self.images(i, 1)[0]
+
+    def free(self):
+        if self.handle and self.ctx.handle:
+            self.lib.pcv_xray_free(self.handle)
         self.handle = None
 
     def __del__(self):
