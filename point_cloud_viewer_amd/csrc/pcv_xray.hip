@@ -710,7 +710,10 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* tree, const pcv_xray_params* p, pc
                          (uint64_t*)nullptr, (double*)nullptr);
     }
     PCV_HIP_CHECK(ctx, hipGetLastError());
-    if ((rc = pcv_batch_scan(ctx, sc, d_counts, nb, d_off))) return rc;
+    {
+      PcvProf prof(ctx, PCV_K_QUERY_BATCH_SCAN);
+      if ((rc = pcv_batch_scan(ctx, sc, d_counts, nb, d_off))) return rc;
+    }
     PCV_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, 4 * nb, ctx->stream));
     {
       PcvProf prof(ctx, PCV_K_XRAY_SCATTER);
