@@ -1242,14 +1242,30 @@ static int single_chain_topology(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, cons
   ctx->stage_begin(PCV_STAGE_CHAIN_KEYS);
   // The sample keys cover `sample_levels` levels first (below); a sample tree that wants to go deeper is keyed again at
   // full depth.
-  // The predicted tree is built on the device (sample split -> spec_tree kernels): the one chain pass starts without a
+  // The predicted tree is built on the device (from the sorted sample keys, pcv_launch_spec_sample_tree): the one chain pass starts without a
   // host round trip, and the host mirrors the tree (one small asynchronous copy) while that pass runs.
   constexpr uint32_t kFirst = 16384;  // T'' nodes mirrored by the first copy (a 100 M-point tree has ~7 500)
   // T'' nodes at most (at least 4 096 records: the chain pass may mirror the table's first 2 048 in LDS without asking how many exist)
   const size_t tcap = std::max<size_t>(1 + 8 * (size_t)nt.capacity, 4096);
   uint32_t *d_ord, *d_walk, *d_sparent, *d_info, *d_counts, *d_map, *d_pool_ctr;
   uint8_t* d_slevel;
-  if ((rc = sc.get(&d_ord, nt.capacity)) || (rc = sc.get(&d_walk, tcap)) || (rc = sc.get(&d_sparent, tcap)) ||
+  // the sample tree straight from the sorted sample keys (pcv_launch_spec_sample_tree: two launches); the split into a node
+  // table + spec_tree_scan / emit (fifteen launches for the 100 M bench cloud) stays in the experiment library
+  // (PCV_SAMPLE_TREE_SPLIT=1, or PCV_SPLIT2=0 for the one-level split kernels) — same T'' either way
+  static const bool tree_by_split = [] {
+    const char* e = pcv_experiment("PCV_SAMPLE_TREE_SPLIT");
+    const char* e2 = pcv_experiment("PCV_SPLIT2");
+    return (e && atoi(e) != 0) || (e2 && atoi(e2) == 0);
+  }();
+#ifdef PCV_EXPERIMENTS
+  const bool table_tree = true;  // (the sample tree by counting, below, builds a node table as well)
+#else
+  const bool table_tree = tree_by_split;
+#endif
+  uint64_t* d_open = nullptr;  // the open sample nodes (at most nt.capacity: T'' holds 1 + 8 x that many nodes)
+  d_ord = nullptr;
+  if ((!tree_by_split && (rc = sc.get(&d_open, nt.capacity))) || (table_tree && (rc = sc.get(&d_ord, nt.capacity)))) return rc;
+  if ((rc = sc.get(&d_walk, tcap)) || (rc = sc.get(&d_sparent, tcap)) ||
       (rc = sc.get(&d_slevel, tcap)) || (rc = sc.get(&d_info, 64)) || (rc = sc.get(&d_pool_ctr, kPcvPoolRegions + tcap + 4)) ||
       (rc = sc.get(&d_map, tcap)))
     return rc;
@@ -1320,21 +1336,27 @@ static int single_chain_topology(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, cons
       const char* e = pcv_experiment("PCV_SAMPLE_CLUMP_SHIFT");  // experiments: 0 = single points
       return e ? (uint32_t)std::min(6, std::max(0, atoi(e))) : 3u;
     }();
-    uint32_t* one = nullptr;  // (scratch of the one-launch-per-digit key sort: libpcv_hip_exp.so, PCV_SAMPLE_ONESWEEP=1; pcv_sort.hip)
-    size_t one_zero_words = 0;
+    size_t one_zero_words = 0, one_words = 0;
 #ifdef PCV_EXPERIMENTS
+    uint32_t* one = nullptr;  // (scratch of the one-launch-per-digit key sort: libpcv_hip_exp.so, PCV_SAMPLE_ONESWEEP=1; pcv_sort.hip)
     static const bool onesweep_on = [] {
       const char* e = pcv_experiment("PCV_SAMPLE_ONESWEEP");
       return e && atoi(e) != 0;
     }();
     const int sbits = 3 * sample_levels;
     if (onesweep_on && pcv_onesweep_fits(ns, sbits)) {
-      if ((rc = sc.get(&one, pcv_onesweep_scratch_words(ns, sbits) + 4))) return rc;
+      one_words = pcv_onesweep_scratch_words(ns, sbits) + 4;
       one_zero_words = pcv_onesweep_zero_words(ns, sbits);
     }
 #endif
+    // cleared by the chain-keys launch on its way: [64 words: the counters of the sample tree kernels][the onesweep scratch]
+    uint32_t* zero;
+    if ((rc = sc.get(&zero, 64 + one_words))) return rc;
+#ifdef PCV_EXPERIMENTS
+    if (one_words) one = zero + 64;
+#endif
     host_lap("bbox -> sample keys");
-    pcv_launch_chain_keys(ctx, lv, ns, stride, d.x, d.y, d.z, skeys_a, false, d.routed, stride > 1 ? clump_shift : 0u, one, one_zero_words);
+    pcv_launch_chain_keys(ctx, lv, ns, stride, d.x, d.y, d.z, skeys_a, false, d.routed, stride > 1 ? clump_shift : 0u, zero, 64 + one_zero_words);
     bool in_a = true;
     host_lap("", true);
     // PCV_SAMPLE_COUNTS=1 (libpcv_hip_exp.so only): the sample tree by COUNTING the keys, three levels per launch pair
@@ -1367,10 +1389,18 @@ static int single_chain_topology(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, cons
                                  bs->sort_scratch, &in_a);
     if (rc) return rc;
     host_lap("sample sort queued");
-    pcv_launch_node_split(ctx, nt, in_a ? skeys_a : skeys_b, false, (uint32_t)ns, lv, params->resolution, thr_s, sp.force_mask);
-    host_lap("sample split queued");
     }
-    pcv_launch_spec_tree(ctx, nt, upper, sp.force_mask, d_ord, d_walk, d_sparent, d_slevel, d_info, d_pool_ctr);
+    if (!counted && !tree_by_split) {
+      if ((rc = pcv_launch_spec_sample_tree(ctx, in_a ? skeys_a : skeys_b, (uint32_t)ns, lv, params->resolution, thr_s, upper, sp.force_mask,
+                                            d_open, nt.capacity, zero, d_walk, d_sparent, d_slevel, d_info, d_pool_ctr)))
+        return rc;
+    } else {
+      if (!counted) {
+        pcv_launch_node_split(ctx, nt, in_a ? skeys_a : skeys_b, false, (uint32_t)ns, lv, params->resolution, thr_s, sp.force_mask);
+        host_lap("sample split queued");
+      }
+      pcv_launch_spec_tree(ctx, nt, upper, sp.force_mask, d_ord, d_walk, d_sparent, d_slevel, d_info, d_pool_ctr);
+    }
     host_lap("spec tree queued");
     uint8_t* hs = (uint8_t*)ctx->pinned_spec;
     const size_t first = tcap < kFirst ? tcap : kFirst;

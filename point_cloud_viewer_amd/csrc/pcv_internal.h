@@ -442,6 +442,13 @@ void pcv_launch_sample_tree_counts(pcv_ctx* ctx, const PcvNodeTableDev& t, const
 // any candidate)
 void pcv_launch_spec_tree(pcv_ctx* ctx, const PcvNodeTableDev& t, double upper, uint32_t force_mask, uint32_t* ord, uint32_t* walk,
                           uint32_t* sparent, uint8_t* slevel, uint32_t* info, uint32_t* pool_ctr /* kPcvPoolRegions counters, zeroed here; may be null */);
+// single-chain build: the same T'' (same walk / sparent / slevel, info [0] nodes, [1] error flags, [3] any candidate; [2] is the
+// number of open sample nodes here) straight from the sorted sample keys, two launches and no node table. list: list_cap u64 of
+// scratch (more open sample nodes set error bit 2, as a full node table does; walk etc. then hold 1 + 8 x list_cap entries);
+// ctr: 2 u32 that are ZERO when the launch runs (the sample's chain-keys launch clears them)
+int pcv_launch_spec_sample_tree(pcv_ctx* ctx, const uint64_t* sorted_keys, uint32_t ns, const PcvLevels& lv, double resolution, uint32_t thr,
+                                double upper, uint32_t force_mask, uint64_t* list, uint32_t list_cap, uint32_t* ctr, uint32_t* walk,
+                                uint32_t* sparent, uint8_t* slevel, uint32_t* info, uint32_t* pool_ctr);
 // single-chain build: the predicted-leaf -> true-leaf rank map on the device, from the exact counts (`counts`: one u32 per
 // T'' node, leaf entries filled by pcv_launch_rank_hist, inner entries zero). tn = number of T'' nodes (the host knows it
 // from its mirror of the tree); nst / base: tn u32 of scratch each; out: [0] number of true leaves, [1] 1 = prediction too

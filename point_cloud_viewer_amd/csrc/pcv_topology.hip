@@ -704,6 +704,220 @@ __global__ __launch_bounds__(256) void spec_tree_emit_kernel(PcvNodeTableDev t, 
   }
 }
 
+// ---- single-chain build: T'' straight from the SORTED SAMPLE KEYS, two launches -----------------------------------------
+// The sample split rule (split2_assign above; generation.rs:128-150) opens a nonempty node of level k >= 1 iff
+// count > thr && edge[k] > resolution, or k == 1 and its digit is in force_mask. Both conditions are monotone down a path
+// (a child holds at most its parent's keys, edges halve), so a node that passes them has an open parent: whether a node is
+// open depends on its own count alone and every open node can be found without the level-by-level descent:
+//   spec_sample_open_kernel   one lane per sorted key i. Key i starts a run (a node) at every level below the first one on
+//                             which it differs from key i - 1; such a run holds more than t keys iff key i + t still shares
+//                             its prefix. One load of key i + thr answers the count test for all those levels at once, one
+//                             load of key i + floor(upper) the candidate test. The open runs (level, i, candidate) go to a
+//                             list in any order (wave-aggregated appends); bit 1 of the error word where the rule wants a
+//                             node at level >= nlevels open (as split2_assign);
+//   spec_tree_build_kernel    one workgroup sorts the list by (level, start) — within a level the start order is the prefix
+//                             order, so this is the table order of the sample's open nodes and a node's position is its
+//                             ordinal — and writes walk / sparent / slevel exactly as spec_tree_scan + spec_tree_emit do
+//                             (a child is found by binary search among the next level's prefixes).
+// The two counters (ctr[0] list entries, ctr[1] error bits) must be zero when the first kernel starts: the chain-keys launch
+// of the sample clears them on its way (pcv_launch_chain_keys' zero block).
+constexpr uint32_t kSpecTreeLdsEntries = 16384;  // list entries sorted in LDS (128 KB); longer lists are sorted in place in global memory
+
+// leading levels on which two (left-aligned) path keys agree, 0..PCV_MAX_KEY_LEVELS (bit 63 of a key is never set)
+__device__ __forceinline__ int pcv_key_common_levels(uint64_t a, uint64_t b) {
+  const uint64_t x = a ^ b;
+  return x == 0 ? PCV_MAX_KEY_LEVELS : PCV_MAX_KEY_LEVELS - 1 - (63 - (int)__clzll(x)) / 3;
+}
+__device__ __forceinline__ uint64_t pcv_level_prefix_mask(int k) { return k == 0 ? 0ull : ~0ull << (3 * (PCV_MAX_KEY_LEVELS - k)); }
+
+// list entry: level << 40 | start << 1 | candidate
+__global__ __launch_bounds__(256) void spec_sample_open_kernel(const uint64_t* __restrict__ keys, uint32_t ns, int nlevels,
+                                                                uint32_t edge_ok /* bit k: lv.edge[k] > resolution */, uint32_t thr,
+                                                                uint32_t upper_floor, uint32_t force_mask, uint64_t* __restrict__ list,
+                                                                uint32_t list_cap, uint32_t* __restrict__ ctr) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  int first = 1, last = 1;  // the open runs starting at key i: levels [first, last)
+  uint64_t key = 0;
+  if (i < ns) {
+    key = keys[i];
+    first = i == 0 ? 1 : pcv_key_common_levels(keys[i - 1], key) + 1;
+    last = first;
+    if (first <= nlevels) {
+      const int more = (uint64_t)i + thr < ns ? pcv_key_common_levels(key, keys[i + thr]) : 0;  // count > thr down to this level
+      const bool forced1 = (force_mask >> (uint32_t)(key >> (3 * (PCV_MAX_KEY_LEVELS - 1)))) & 1u;
+      for (int k = first; k <= nlevels; ++k) {
+        const bool open = (k == 1 && forced1) || (k <= more && ((edge_ok >> k) & 1u));
+        if (!open) break;  // nothing below a closed run can be open
+        if (k >= nlevels) {  // would need digits beyond the sample keys
+          atomicOr(&ctr[1], 1u);
+          break;
+        }
+        last = k + 1;
+      }
+    }
+  }
+  const uint32_t cnt = (uint32_t)(last - first) + (i == 0 ? 1u : 0u);  // key 0 also emits the root
+  if (__ballot(cnt != 0) == 0) return;  // wave-uniform: almost every wave
+  uint32_t inc = cnt;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t v = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += v;
+  }
+  uint32_t wbase = 0;
+  if (lane == 63) wbase = atomicAdd(&ctr[0], inc);
+  wbase = (uint32_t)__shfl((int)wbase, 63, 64);
+  if (cnt == 0) return;
+  uint32_t slot = wbase + inc - cnt;
+  if (i == 0) {
+    if (slot < list_cap) list[slot] = 0;  // the root: level 0, start 0, never a candidate
+    ++slot;
+  }
+  // count <= floor(upper) iff key i + floor(upper) leaves the run (or the sample)
+  const int within_upper = (uint64_t)i + upper_floor < ns ? pcv_key_common_levels(key, keys[i + upper_floor]) : 0;
+  const bool forced1 = (force_mask >> (uint32_t)(key >> (3 * (PCV_MAX_KEY_LEVELS - 1)))) & 1u;
+  for (int k = first; k < last; ++k, ++slot) {
+    const bool cand = k > within_upper && !(k == 1 && forced1);
+    if (slot < list_cap) list[slot] = ((uint64_t)k << 40) | ((uint64_t)i << 1) | (cand ? 1ull : 0ull);
+  }
+}
+
+// sorts e[0, m) ascending in place, one workgroup: bitonic network in the form whose comparators all put the smaller value
+// at the lower index, so the entries beyond m of the padded power of two count as +inf and are never touched
+__device__ __forceinline__ void spec_tree_sort(uint64_t* e, uint32_t m) {
+  uint32_t p = 1;
+  while (p < m) p <<= 1;
+  for (uint32_t k = 2; k <= p; k <<= 1) {
+    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+      for (uint32_t t = threadIdx.x; t < p / 2; t += blockDim.x) {
+        uint32_t lo, hi;
+        if (j == k >> 1) {  // first step of a merge: the mirror partner in the block of k
+          const uint32_t blk = (t / j) * k, r = t % j;
+          lo = blk + r;
+          hi = blk + k - 1 - r;
+        } else {
+          lo = (t / j) * 2 * j + t % j;
+          hi = lo + j;
+        }
+        if (hi < m) {
+          const uint64_t a = e[lo], b = e[hi];
+          if (a > b) e[lo] = b, e[hi] = a;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// position of `prefix` among e[lo, hi) (prefixes of one level, ascending; bit 63 is the candidate flag), hi if absent
+__device__ __forceinline__ uint32_t spec_tree_lower_bound(const uint64_t* e, uint32_t lo, uint32_t hi, uint64_t prefix) {
+  constexpr uint64_t kVal = ~(1ull << 63);
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if ((e[mid] & kVal) < prefix) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// T'' from the sorted list; the same records, numbering and info block as spec_tree_scan_kernel + spec_tree_emit_kernel,
+// except info[2]: open sample nodes here (the host reads info[0] and info[1] only)
+__device__ __forceinline__ void spec_tree_build(uint64_t* e, uint32_t m, const uint64_t* __restrict__ keys, uint32_t* __restrict__ walk,
+                                                uint32_t* __restrict__ sparent, uint8_t* __restrict__ slevel, uint32_t* lstart) {
+  constexpr uint64_t kCand = 1ull << 63;
+  spec_tree_sort(e, m);
+  for (uint32_t j = threadIdx.x; j < m; j += blockDim.x) {  // first entry of every level (levels 0 .. deepest are all present)
+    const uint32_t lev = (uint32_t)(e[j] >> 40);
+    if (j == 0 || lev != (uint32_t)(e[j - 1] >> 40)) lstart[lev] = j;
+  }
+  __syncthreads();
+  for (uint32_t j = threadIdx.x; j < m; j += blockDim.x) {  // (level, start, candidate) -> prefix | candidate << 63
+    const uint64_t v = e[j];
+    const int lev = (int)(v >> 40);
+    e[j] = (keys[(uint32_t)(v >> 1)] & pcv_level_prefix_mask(lev)) | ((v & 1ull) ? kCand : 0ull);
+  }
+  __syncthreads();
+  for (uint32_t j = threadIdx.x; j < m; j += blockDim.x) {
+    int k = 0;
+    while (k < PCV_MAX_KEY_LEVELS && lstart[k + 1] <= j) ++k;
+    const uint64_t p = e[j] & ~kCand;
+    uint32_t id = 0;
+    if (j == 0) {  // the root is always split and never a candidate
+      walk[0] = 1u;
+      sparent[0] = 0xffffffffu;
+      slevel[0] = 0;
+    } else {
+      const uint32_t parent = spec_tree_lower_bound(e, lstart[k - 1], lstart[k], p & pcv_level_prefix_mask(k - 1));
+      id = 1u + 8u * parent + ((uint32_t)(p >> (3 * (PCV_MAX_KEY_LEVELS - k))) & 7u);
+    }
+    // the open children: the next level's entries from the first one at or after p that still carry p's prefix
+    const int sh = 3 * (PCV_MAX_KEY_LEVELS - k - 1);  // (an open node sits above the last key level: k + 1 <= 21)
+    const uint32_t cend = lstart[k + 2];
+    const uint32_t base = 1u + 8u * j;
+    uint32_t rec[8];
+#pragma unroll
+    for (uint32_t c = 0; c < 8; ++c) rec[c] = (base + c) | PCV_SPEC_LEAF;
+    const uint64_t pmask = pcv_level_prefix_mask(k);
+    for (uint32_t t = spec_tree_lower_bound(e, lstart[k + 1], cend, p); t < cend; ++t) {
+      const uint64_t v = e[t];
+      if (((v & ~kCand) & pmask) != p) break;
+      const uint32_t c = (uint32_t)(v >> sh) & 7u, r = (1u + 8u * t) | ((v & kCand) ? PCV_SPEC_CANDIDATE : 0u);
+#pragma unroll
+      for (uint32_t q = 0; q < 8; ++q) rec[q] = q == c ? r : rec[q];  // (no dynamic index into the register array)
+    }
+#pragma unroll
+    for (uint32_t c = 0; c < 8; ++c) {
+      walk[base + c] = rec[c];
+      sparent[base + c] = id;
+      slevel[base + c] = (uint8_t)(k + 1);
+    }
+  }
+}
+
+__global__ __launch_bounds__(1024) void spec_tree_build_kernel(uint64_t* __restrict__ list, uint32_t list_cap, const uint64_t* __restrict__ keys,
+                                                                const uint32_t* __restrict__ ctr, uint32_t* __restrict__ walk,
+                                                                uint32_t* __restrict__ sparent, uint8_t* __restrict__ slevel,
+                                                                uint32_t* __restrict__ info, uint32_t* __restrict__ pool_ctr) {
+  static_assert(kPcvPoolRegions <= 1024, "one counter per lane");
+  extern __shared__ uint64_t lds_list[];
+  __shared__ uint32_t lstart[PCV_MAX_KEY_LEVELS + 3];
+  // the chain pass's pool counters (as spec_tree_scan_kernel): zero before every pass
+  if (pool_ctr && threadIdx.x < kPcvPoolRegions) pool_ctr[threadIdx.x] = 0;
+  const uint32_t m = ctr[0];
+  uint32_t err = ctr[1];
+  if (threadIdx.x < PCV_MAX_KEY_LEVELS + 3) lstart[threadIdx.x] = m;
+  if (m > list_cap) {  // more open nodes than the tables hold: the host hands the build to the exact pipeline; the chain pass
+                       // that is already queued walks a root with eight leaves meanwhile
+    err |= 2u;
+    if (threadIdx.x < 9) {
+      walk[threadIdx.x] = threadIdx.x == 0 ? 1u : threadIdx.x | PCV_SPEC_LEAF;
+      sparent[threadIdx.x] = threadIdx.x == 0 ? 0xffffffffu : 0u;
+      slevel[threadIdx.x] = threadIdx.x == 0 ? 0 : 1;
+    }
+    if (threadIdx.x == 0) info[0] = 9u, info[1] = err, info[2] = m, info[3] = 0;
+    return;
+  }
+  bool cand = false;
+  if (m <= kSpecTreeLdsEntries) {
+    for (uint32_t j = threadIdx.x; j < m; j += 1024) lds_list[j] = list[j];
+    __syncthreads();
+    spec_tree_build(lds_list, m, keys, walk, sparent, slevel, lstart);
+    for (uint32_t j = 1 + threadIdx.x; j < m; j += 1024) cand = cand || (lds_list[j] >> 63);
+  } else {
+    __syncthreads();
+    spec_tree_build(list, m, keys, walk, sparent, slevel, lstart);
+    for (uint32_t j = 1 + threadIdx.x; j < m; j += 1024) cand = cand || (list[j] >> 63);
+  }
+  cand = __syncthreads_or(cand);
+  if (threadIdx.x == 0) {
+    info[0] = 1u + 8u * m;
+    info[1] = err;
+    info[2] = m;
+    info[3] = cand ? 1u : 0u;
+  }
+}
+
 
 // ---- single-chain build: the rank map ON THE DEVICE (what pcv_spec_resolve computes on the host, pcv_spec.cpp) ----------
 // Exact counts per predicted leaf in, predicted-leaf -> true-leaf map out, so that the record sort can start without the
@@ -867,6 +1081,33 @@ void pcv_launch_spec_tree(pcv_ctx* ctx, const PcvNodeTableDev& t, double upper, 
   hipLaunchKernelGGL(spec_tree_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, t, ord, info, pool_ctr);
   hipLaunchKernelGGL(spec_tree_emit_kernel, dim3(64), dim3(256), 0, ctx->stream, t, ord, upper, force_mask, walk, sparent, slevel,
                      info);
+}
+
+int pcv_launch_spec_sample_tree(pcv_ctx* ctx, const uint64_t* sorted_keys, uint32_t ns, const PcvLevels& lv, double resolution, uint32_t thr,
+                                double upper, uint32_t force_mask, uint64_t* list, uint32_t list_cap, uint32_t* ctr, uint32_t* walk,
+                                uint32_t* sparent, uint8_t* slevel, uint32_t* info, uint32_t* pool_ctr) {
+  if (ns == 0 || lv.nlevels < 1 || lv.nlevels > PCV_MAX_KEY_LEVELS) return ctx->fail(PCV_E_INVALID, "sample tree: levels");
+  // the LDS list is 128 KB: above the 64 KB a kernel gets without asking (the opt-in is made once)
+  static const bool lds_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&spec_tree_build_kernel),
+                                                  hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                  (int)(kSpecTreeLdsEntries * sizeof(uint64_t))) == hipSuccess;
+  if (!lds_ok) return ctx->fail(PCV_E_HIP, "sample tree: LDS");
+  uint32_t edge_ok = 0;
+  for (int k = 1; k <= lv.nlevels; ++k)
+    if (lv.edge[k] > resolution) edge_ok |= 1u << k;
+  const double uf = std::floor(upper);
+  const uint32_t upper_floor = uf <= 0.0 ? 0u : (uf >= 4294967295.0 ? 0xffffffffu : (uint32_t)uf);  // count <= upper iff count <= floor(upper)
+  {
+    PcvProf prof(ctx, PCV_K_SPLIT_SEARCH);
+    hipLaunchKernelGGL(spec_sample_open_kernel, dim3((ns + 255u) / 256u), dim3(256), 0, ctx->stream, sorted_keys, ns, (int)lv.nlevels,
+                       edge_ok, thr, upper_floor, force_mask, list, list_cap, ctr);
+  }
+  {
+    PcvProf prof(ctx, PCV_K_SPLIT_ASSIGN);
+    hipLaunchKernelGGL(spec_tree_build_kernel, dim3(1), dim3(1024), kSpecTreeLdsEntries * sizeof(uint64_t), ctx->stream, list, list_cap,
+                       sorted_keys, ctr, walk, sparent, slevel, info, pool_ctr);
+  }
+  return PCV_OK;
 }
 
 #ifdef PCV_EXPERIMENTS
