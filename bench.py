@@ -7,8 +7,7 @@ the finished node table and node-contiguous .xyz/.rgb bytes in HBM. Inputs are r
 starts; nothing is read back except the node table.
 
 Workload at N=1: BASELINE config 2 — 100 M synthetic Gaussian-cluster points (64 clusters in a 1000 m cube,
-sigma in [1, 20] m), f64 SoA xyz + u8 rgb, resolution 1 mm; after the timed region the closed-form CPU oracle builds
-the same cloud and every node of one more GPU build is compared with it byte for byte (`parity`).
+sigma in [1, 20] m), f64 SoA xyz + u8 rgb, resolution 1 mm.
 With --gpus N>1: BASELINE config 3 — ONE cloud of 1 B points of the same distribution (seed 2), rank r holds the
 contiguous slice [r, r + 1) * 1e9 / N of it (strong scaling; --points P gives every rank P points instead), points are
 routed to their owner with ONE all-to-all (point_cloud_viewer_amd/distributed.py) and each rank builds its subtrees.
@@ -16,9 +15,17 @@ routed to their owner with ONE all-to-all (point_cloud_viewer_amd/distributed.py
 torch.distributed) and compares the merged octree with a single-GPU build of the whole cloud (and, with --verify, with
 the CPU oracle): the config-3 dress rehearsal for boxes with one GPU.
 
+A plain run (`--gpus 1 --steps K --warmup W`) does only what its headline figure needs: it generates the cloud, warms
+up, times the K steps, writes --dump-outputs if asked and prints its lines. --full adds, after the timed region,
+everything else the benchmark measures or checks: the rocm-smi box record, stage times from two more builds, the
+roofline and encode+sort figures, the closed-form CPU oracle building the same cloud with every node of one more GPU
+build compared with it byte for byte (`parity`), the CPU baseline, the end-to-end leg (host arrays / batches / PLY to
+files) and the legs of the other BASELINE configs (`sharded`, `query`, `config5`, `intensity`, `config1`); with --gpus
+N>1 the unsharded N = 1 reference build of the same cloud (`n1_same_cloud`).
+
 Other modes (never the driver's default): --verify forces the oracle comparison wherever it is off by default
-(sharded path, --ecef ...); --ecef is BASELINE config 5; --query is BASELINE config 4 (frustum path) with parity of all
-frusta; --config1 is BASELINE config 1 (CPU plumbing line, no GPU work timed).
+(plain runs, sharded path, --ecef ...); --ecef is BASELINE config 5; --query is BASELINE config 4 (frustum path) with
+parity of all frusta; --config1 is BASELINE config 1 (CPU plumbing line, no GPU work timed).
 
 Rank 0 writes the whole record to bench_detail.json, prints a trimmed copy of it and then, as the LAST stdout line, the
 line of record (<= 4 KB: contract fields + roofline + cpu_baseline + one parity verdict per BASELINE config).
@@ -1172,7 +1179,11 @@ def main():
     ap.add_argument("--points", type=int, default=0,
                     help="points per GPU (default: 100 M on one GPU = config 2; 1e9 / N on N GPUs = config 3)")
     ap.add_argument("--resolution", type=float, default=0.001)
-    ap.add_argument("--cpu-sample", type=int, default=100_000_000, help="points of the workload timed on the CPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, everything beyond the headline figure: box record, stage times, roofline, "
+                         "oracle parity, CPU baseline, end-to-end leg and the other BASELINE configs' legs at N=1, the N = 1 "
+                         "reference at N > 1 (a plain run does none of it)")
+    ap.add_argument("--cpu-sample", type=int, default=100_000_000, help="points of the workload timed on the CPU (--full)")
     ap.add_argument("--ecef", action="store_true",
                     help="BASELINE config 5: place the cloud at ECEF magnitudes (|p| ~ 6.4e6 m)")
     ap.add_argument("--force-sharded", action="store_true",
@@ -1188,8 +1199,9 @@ def main():
                          "--force-sharded this is the --gpus N code path at world size 1")
     ap.add_argument("--verify", action="store_true",
                     help="after the timed region: one more build compared byte for byte with the CPU oracle (default at N=1 "
-                         "on the plain config-2 run; this flag forces it elsewhere, incl. the sharded path)")
-    ap.add_argument("--no-parity", action="store_true", help="skip the default oracle comparison of the N=1 run (A/B timing runs)")
+                         "on the config-2 run with --full; this flag forces it elsewhere, incl. plain runs and the sharded path)")
+    ap.add_argument("--no-parity", action="store_true",
+                    help="--full: skip the oracle comparison of the N=1 run and the legs after it (A/B timing runs)")
     ap.add_argument("--digest", action="store_true", help="print a digest of the built octree (no oracle): A/B runs compare it")
     ap.add_argument("--query", action="store_true", help="BASELINE config 4 (frustum path) instead of the build")
     ap.add_argument("--frusta", type=int, default=10_000)
@@ -1199,14 +1211,15 @@ def main():
     ap.add_argument("--query-steps", type=int, default=5, help="timed repetitions of the node-cull launch sequence (config 4)")
     ap.add_argument("--config1", action="store_true", help="BASELINE config 1 (CPU plumbing line)")
     ap.add_argument("--no-legs", action="store_true",
-                    help="default N=1 line only: skip the config-4 (`query`) and config-5 (`config5`) legs after the timed region")
+                    help="--full at N=1: skip the legs after the timed region (`sharded`, `query`, `config5`, `intensity`, "
+                         "`config1`)")
     ap.add_argument("--intensity-points", type=int, default=20_000_000,
-                    help="points of the colour + intensity leg of the default line (the reference binary's payload); 100000000 for the full-size record")
+                    help="points of the colour + intensity leg of --full (the reference binary's payload); 100000000 for the full-size record")
     ap.add_argument("--only-intensity", action="store_true", help="run the colour + intensity leg alone (with --intensity-points) and print its record")
     ap.add_argument("--config5-points", type=int, default=500_000_000)
     ap.add_argument("--config5-steps", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the host-to-files end-to-end leg (N=1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the host-to-files end-to-end leg (N=1 only)")
     ap.add_argument("--kernel-events", choices=["major", "all", "none"], default="major",
                     help="HIP events around kernel launches inside the timed region: the kernels that pass over the whole "
                          "cloud (default), every launch (~100 per build, costs the step a few percent), or none")
@@ -1214,7 +1227,8 @@ def main():
     ap.add_argument("--exact-pipeline", action="store_true",
                     help="force the exact two-chain pipeline (K2 keys + key sort + node split + K5) instead of the single-chain build")
     ap.add_argument("--n1-same-cloud", action="store_true",
-                    help="config 3: also build the whole cloud unsharded on rank 0 before the timed region (default with N > 1)")
+                    help="config 3: also build the whole cloud unsharded on rank 0 before the timed region (default with N > 1 "
+                         "and --full)")
     ap.add_argument("--no-n1", action="store_true", help="N > 1: skip the unsharded reference build of the same cloud on rank 0")
     ap.add_argument("--no-n1-digest", action="store_true", help="N > 1: no digest comparison of the merged octree with the unsharded one")
     ap.add_argument("--full-line", action="store_true",
@@ -1298,7 +1312,7 @@ def main():
         x, y, z, rgb = make_cloud(torch, n, seed=1 + rank, device=dev, offset=offset)  # ends with a device synchronize
     ctx = pcv.Context(local_rank)  # the library's own stream; torch work is ordered explicitly (wait_torch)
     n1 = None
-    if config3 and rank == 0 and (world > 1 or args.n1_same_cloud) and not args.no_n1:
+    if config3 and rank == 0 and ((world > 1 and args.full) or args.n1_same_cloud) and not args.no_n1:
         # the SAME cloud built unsharded on this one GPU (own context, released afterwards) while the other ranks wait at the
         # warm-up's first collective: the line then carries its own N = 1 reference (VERDICT r05 #2b)
         n1 = n1_same_cloud_leg(args, torch, pcv, dev, local_rank, total)
@@ -1340,7 +1354,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    box = {"idle_before_warmup": box_info()} if rank == 0 else None
+    box = {"idle_before_warmup": box_info()} if rank == 0 and args.full else None
     if args.kernel_events != "none":
         ctx.set_profiling("major" if args.kernel_events == "major" else True)  # during warmup: the event pool exists before the timed region
     import gc
@@ -1363,7 +1377,7 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     gc.enable()
-    if rank == 0:
+    if box is not None:
         box["right_after_timed_region"] = box_info()
     if last is not None:
         dumped = dump_outputs(last, args.dump_outputs)
@@ -1377,13 +1391,14 @@ def main():
     ctx.set_profiling(False)
     kstats = ctx.kernel_stats()
     # stage times: the 16 stage events of a build cost its stream ~0.1 ms (PCV_BUILD_STAGE_TIMES, off by default and off in
-    # the timed region); `stage_ms` comes from two more builds AFTER the timed region with the stage events on
-    timed_gpu_ms = list(info.get("gpu_ms") or [])
-    ctx.stage_times = True
-    for _ in range(2):
-        step()
-    ctx.stage_times = False
-    info["gpu_ms"] = timed_gpu_ms
+    # the timed region); `stage_ms` comes from two more builds AFTER the timed region with the stage events on (--full)
+    if args.full:
+        timed_gpu_ms = list(info.get("gpu_ms") or [])
+        ctx.stage_times = True
+        for _ in range(2):
+            step()
+        ctx.stage_times = False
+        info["gpu_ms"] = timed_gpu_ms
     per_rank = None
     if dist is not None:  # every rank's view of its last step: rows / bytes moved and the stage times (exchange, local build, merge)
         per_rank = [None] * world
@@ -1396,7 +1411,7 @@ def main():
     timed = {k: v for k, v in kstats.items() if v[0] > 0}
     plain = n == 100_000_000 and world == 1 and not sharded and not args.ecef and not args.exact_pipeline
     bhash = build_hash()
-    if timed:
+    if timed and args.full:  # (the encode+sort figure reads the stage times of the builds above)
         # packed 12-byte records (single-chain build, build_info record_bytes == 12): u32 key + uint2 payload
         rec_b = float((info.get("build") or {}).get("record_bytes") or 20)
         if rec_b == 12.0:
@@ -1542,14 +1557,14 @@ def main():
                                              "GB/s": round(n * passes * 3 * key_bytes / (sort_ms * 1e-3) / 1e9, 1) if sort_ms else None},
                            "record_sort": record_sort}
 
-    # ---- parity: one more build compared with the CPU oracle on the same cloud (default on the plain N=1 run) ----
+    # ---- parity: one more build compared with the CPU oracle on the same cloud (default on the config-2 N=1 run with --full) ----
     parity = None
     tree_digest = None
-    if not sharded and rank == 0 and (args.verify or (plain and not args.no_parity)):
+    if not sharded and rank == 0 and (args.verify or (args.full and plain and not args.no_parity)):
         parity = verify_build(ctx, args.resolution, x, y, z, rgb)
         tree_digest = parity.get("tree_digest")
     elif sharded and (args.verify or args.digest or (n1 is not None and "tree_digest" in n1) or
-                      (world > 1 and not args.no_n1 and not args.no_n1_digest)):
+                      (world > 1 and args.full and not args.no_n1 and not args.no_n1_digest)):
         # sharded path: every rank hashes its subtrees, rank 0 merges them with the all-reduced top nodes; --verify:
         # rank 0 regenerates the whole cloud (the block generator makes any slice reproducible) for the oracle
         r = builder.build(args.resolution, builder.global_bbox(x, y, z), x, y, z, rgb)
@@ -1590,7 +1605,7 @@ def main():
         t.free()
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not sharded:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not sharded:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import shutil
         import tempfile
@@ -1624,7 +1639,7 @@ def main():
                        "end_to_end.Mpoints_per_s_incl_files"}
 
     e2e = None
-    if rank == 0 and world == 1 and not args.no_e2e and not sharded:
+    if args.full and rank == 0 and world == 1 and not args.no_e2e and not sharded:
         # One untimed-region pass from HOST arrays to files on tmpfs: H2D staging + build, D2H of the node blobs,
         # threaded file writes. Never part of `value` (tier rule (4)); reported so the PCIe / file-system cost is visible.
         import shutil
@@ -1723,10 +1738,10 @@ def main():
                        "on the device; creating the node files in ONE directory serialises on the directory lock "
                        "(reference layout); not part of `value`"}
 
-    # ---- the other single-GPU BASELINE configs, after the timed region of the default line: config 4 (frustum path on the
+    # ---- the other single-GPU BASELINE configs, after the timed region of --full: config 4 (frustum path on the
     # octree of this cloud) and config 5 (500 M ECEF points), each with its own timing and oracle parity ----
     query, config5, sharded_out, config1_out, intensity_out = None, None, None, None, None
-    if plain and rank == 0 and not args.no_parity and not args.no_legs:
+    if args.full and plain and rank == 0 and not args.no_parity and not args.no_legs:
         try:  # the multi-GPU code path on this cloud: RCCL at world size 1 + 8 thread-ranks, digests against the verified one
             sharded_out = sharded_leg(args, torch, pcv, ctx, dev, x, y, z, rgb, tree_digest)
         except Exception as e:  # noqa: BLE001 - the leg reports its failure, the line of record still prints
@@ -1788,7 +1803,8 @@ def main():
             "n1_same_cloud": n1,
             "sharded_stage_ms": None if not sharded else {k: round(v, 3) for k, v in (info.get("stages") or {}).items()
                                                           if k in ("bbox", "exchange", "local_build", "top_merge")},
-            "stage_ms": {k: round(v, 3) for k, v in (info.get("stages") or {}).items()},
+            # (unsharded, the stage events are only on in the two builds of --full)
+            "stage_ms": {k: round(v, 3) for k, v in (info.get("stages") or {}).items()} if args.full or sharded else None,
             "wall_ms_each_step": per_step_ms, "gpu_ms_each_step": (info.get("gpu_ms") or [])[-args.steps:],
             "kernel_ms_per_step": {k: round(v[1] / args.steps, 3) for k, v in kstats.items() if v[0] > 0},
         }
