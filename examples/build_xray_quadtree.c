@@ -1,0 +1,108 @@
+/* build_xray_quadtree.c — xray's build_xray_quadtree over the C ABI in plain C11: an octree directory is opened, the
+ * leaf tiles are rasterised on the device (pcv_xray_run), every level above them up to the root node is built on the
+ * device (pcv_xray_build_parents), and the quadtree directory the xray viewer loads is written: one <node>.png per node
+ * and the meta file (pcv_xray_write_dir). A subset of the reference binary's flags; one octree, no binning.
+ *
+ *   build_xray_quadtree <octree dir> --output-directory <dir> --resolution <m per px> [--tile-size <px>]
+ *                       [--coloring-strategy xray|colored|colored_with_height_stddev] [--max-stddev <m>]
+ *                       [--colormap jet|purplish] [--tile-background-color white|transparent]
+ *                       [--filter-interval intensity=<lo>,<hi>] [--root-node-id <r...>]
+ */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "pcv_layout_check.h"
+
+static int usage(void) {
+  fprintf(stderr,
+          "usage: build_xray_quadtree <octree dir> --output-directory <dir> --resolution <m per px> [--tile-size <px>]\n"
+          "       [--coloring-strategy xray|colored|colored_with_height_stddev] [--max-stddev <m>] [--colormap jet|purplish]\n"
+          "       [--tile-background-color white|transparent] [--filter-interval intensity=<lo>,<hi>] [--root-node-id <r...>]\n");
+  return 2;
+}
+
+int main(int argc, char** argv) {
+  const char* input = NULL;
+  const char* output = NULL;
+  const char* root = "r";
+  char attribute[16] = "";
+  pcv_xray_params p;
+  memset(&p, 0, sizeof(p));
+  p.tile_size_px = 256;
+  p.strategy = PCV_XRAY_XRAY;
+  p.max_stddev = 1.0f;
+  for (int i = 1; i < argc; ++i) {
+    const char* a = argv[i];
+    const char* v = i + 1 < argc ? argv[i + 1] : NULL;
+    if (a[0] != '-') {
+      if (input) return usage();
+      input = a;
+      continue;
+    }
+    if (!v) return usage();
+    ++i;
+    if (!strcmp(a, "--output-directory")) {
+      output = v;
+    } else if (!strcmp(a, "--resolution")) {
+      p.pixel_size_m = strtod(v, NULL);
+    } else if (!strcmp(a, "--tile-size")) {
+      p.tile_size_px = (uint32_t)strtoul(v, NULL, 10);
+    } else if (!strcmp(a, "--coloring-strategy")) {
+      if (!strcmp(v, "xray")) p.strategy = PCV_XRAY_XRAY;
+      else if (!strcmp(v, "colored")) p.strategy = PCV_XRAY_COLORED;
+      else if (!strcmp(v, "colored_with_height_stddev")) p.strategy = PCV_XRAY_HEIGHT_STDDEV;
+      else return usage();
+    } else if (!strcmp(a, "--max-stddev")) {
+      p.max_stddev = strtof(v, NULL);
+    } else if (!strcmp(a, "--colormap")) {
+      if (!strcmp(v, "jet")) p.colormap = PCV_XRAY_JET;
+      else if (!strcmp(v, "purplish")) p.colormap = PCV_XRAY_PURPLISH;
+      else return usage();
+    } else if (!strcmp(a, "--tile-background-color")) {
+      if (!strcmp(v, "white")) p.background = PCV_XRAY_BG_WHITE;
+      else if (!strcmp(v, "transparent")) p.background = PCV_XRAY_BG_TRANSPARENT;
+      else return usage();
+    } else if (!strcmp(a, "--filter-interval")) {
+      const char* eq = strchr(v, '=');
+      if (!eq || (size_t)(eq - v) >= sizeof(attribute) || sscanf(eq + 1, "%lf,%lf", &p.interval[0], &p.interval[1]) != 2) return usage();
+      memcpy(attribute, v, (size_t)(eq - v));
+      attribute[eq - v] = '\0';
+      p.interval_attribute = attribute;
+    } else if (!strcmp(a, "--root-node-id")) {
+      root = v;
+    } else {
+      return usage();
+    }
+  }
+  if (!input || !output || !(p.pixel_size_m > 0.0)) return usage();
+  /* quadtree NodeId from its Display form: "r" and one base-4 digit per level */
+  if (root[0] != 'r') return usage();
+  for (const char* c = root + 1; *c; ++c) {
+    if (*c < '0' || *c > '3') return usage();
+    p.root_index = (p.root_index << 2) | (uint64_t)(*c - '0');
+    ++p.root_level;
+  }
+  pcv_ctx* ctx = NULL;
+  pcv_octree* tree = NULL;
+  pcv_xray* x = NULL;
+  int rc = pcv_ctx_create(0, NULL, &ctx);
+  if (rc == PCV_OK) rc = pcv_octree_open_dir(ctx, input, &tree);
+  if (rc == PCV_OK) rc = pcv_xray_run(ctx, tree, &p, &x);
+  if (rc == PCV_OK) rc = pcv_xray_build_parents(x);
+  if (rc == PCV_OK) rc = pcv_xray_write_dir(x, output);
+  if (rc == PCV_OK) {
+    uint64_t nodes = 0, created = 0;
+    uint32_t deepest = 0;
+    pcv_xray_nodes(x, &nodes, 0, NULL, NULL);
+    pcv_xray_info(x, &deepest, NULL, NULL, &created);
+    printf("%llu nodes (%llu leaf tiles at level %u) written to %s\n", (unsigned long long)nodes, (unsigned long long)created, deepest,
+           output);
+  } else {
+    fprintf(stderr, "build_xray_quadtree: %s (%d)\n", ctx ? pcv_last_error(ctx) : "no context", rc);
+  }
+  pcv_xray_free(x);
+  if (tree) pcv_octree_free(tree);
+  if (ctx) pcv_ctx_destroy(ctx);
+  return rc == PCV_OK ? 0 : 1;
+}

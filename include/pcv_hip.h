@@ -646,8 +646,8 @@ void pcv_query_batch_free(pcv_query_batch* b);
 #define PCV_XRAY_BG_WHITE 0      /* TileBackgroundColorArgument (:46-55) */
 #define PCV_XRAY_BG_TRANSPARENT 1
 
-/* XrayParameters (:452-461) + the coloring strategy. Binning, ColoredWithIntensity, parent levels, several octrees and
- * filters on attributes other than intensity are not offered. */
+/* XrayParameters (:452-461) + the coloring strategy. Binning, ColoredWithIntensity, several octrees and filters on
+ * attributes other than intensity are not offered. */
 typedef struct pcv_xray_params {
   uint32_t tile_size_px;        /* W = H, 1 ..= 32768 */
   uint32_t strategy;            /* PCV_XRAY_XRAY / _COLORED / _HEIGHT_STDDEV */
@@ -706,6 +706,36 @@ void pcv_xray_free(pcv_xray* x);
 #define PCV_XRAY_FN_PURPLISH 3
 #define PCV_XRAY_FN_TO_U8 4
 int pcv_xray_finalize(int fn, uint64_t count, const double* in, uint8_t* rgba);
+
+/* ---- xray parent levels and the quadtree directory (create_non_leaf_nodes :656-682, build_node :726-759) -------------
+ * Every level above the leaves up to root_node_id, on the device: a parent is build_parent (:410-450) of its four
+ * children (a missing child is the background) shrunk from 2W x 2W to W x W by image 0.23.10's Lanczos3 resize, restated
+ * bit for bit: the taps below, the vertical pass first into an f32 intermediate, then the horizontal pass, clamp to
+ * [0, 255] and round half away from zero. All parent images are allocated before any launch: PCV_E_OOM leaves the
+ * leaves valid. A second call is a no-op; with root_level == deepest_level or no created leaf there are no parents. */
+int pcv_xray_build_parents(pcv_xray* x);
+/* Meta.nodes in a fixed order: the created leaves (the positions of pcv_xray_images), then each parent level from
+ * deepest_level - 1 up to root_level in ascending index. Before pcv_xray_build_parents only the leaves. *num_nodes is
+ * the total; the first `capacity` are written (level and index of their quadtree NodeId, each array nullable). */
+int pcv_xray_nodes(const pcv_xray* x, uint64_t* num_nodes, uint64_t capacity, uint32_t* level, uint64_t* index);
+/* Nodes [first, first + count) of pcv_xray_nodes' order as RGBA8, W x W each, rows top to bottom, into `capacity`
+ * bytes that live where `mem` says. A range past the end is PCV_E_INVALID and writes nothing. */
+int pcv_xray_node_images(pcv_xray* x, uint64_t first, uint64_t count, uint64_t capacity, int mem, uint8_t* rgba);
+/* build_xray_quadtree's output directory (created if missing, files overwritten): one "<NodeId>.png" per node ("r" and
+ * base-4 digits) and get_meta_pb_path's meta file (root id with "r" -> "meta", ".pb": meta.pb for r, meta01.pb for
+ * r01), xray_proto Meta version 3 as rust-protobuf 2.x writes proto3 (fields in number order, zero scalars omitted):
+ * the root node's bounding rect, deepest_level, tile_size and every node in pcv_xray_nodes' order. The PNGs are those of
+ * pcv_xray_png_encode: the same pixels as the reference's png 0.16.7 encoder, not the same bytes. PCV_E_INVALID when
+ * parents exist but pcv_xray_build_parents has not run; PCV_E_IO when a file cannot be written. */
+int pcv_xray_write_dir(pcv_xray* x, const char* directory);
+/* Host only, no context: the taps of the 2:1 resize for a tile of tile_size_px = W (1 ..= 32768) pixels: for output
+ * index o, left[o] and count[o] (the input rows / columns [left, left + count) of 2W), and weights[12 o ..= 12 o + 11]
+ * (normalised, zero past count). Arrays of W entries (12 W weights), each nullable. */
+int pcv_xray_lanczos_taps(uint32_t tile_size_px, uint32_t* left, uint32_t* count, float* weights);
+/* Host only, no context: a w x h RGBA8 image (rows top to bottom) as PNG: colour type 6, depth 8, one IDAT, filter byte
+ * 0 on every row, zlib with stored deflate blocks. *needed = the file size; it is written when out != NULL and
+ * capacity >= *needed. w or h == 0 is PCV_E_INVALID. */
+int pcv_xray_png_encode(const uint8_t* rgba, uint32_t w, uint32_t h, uint8_t* out, uint64_t capacity, uint64_t* needed);
 
 /* The `/nodes_data` reply blob of octree_web_viewer (octree_web_viewer/src/backend.rs:90-177) for a list of nodes:
  * per node min xyz (3 x f64 LE), edge (f64), num_points (u32), bytes per coordinate (u8), pad to 8, raw .xyz, pad

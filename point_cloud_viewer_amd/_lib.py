@@ -240,6 +240,12 @@ _SIGNATURES = {
     "pcv_xray_images": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _vp]),
     "pcv_xray_free": (None, [_vp]),
     "pcv_xray_finalize": (C.c_int, [C.c_int, C.c_uint64, _vp, _vp]),
+    "pcv_xray_build_parents": (C.c_int, [_vp]),
+    "pcv_xray_nodes": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_uint64, _vp, _vp]),
+    "pcv_xray_node_images": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _vp]),
+    "pcv_xray_write_dir": (C.c_int, [_vp, C.c_char_p]),
+    "pcv_xray_lanczos_taps": (C.c_int, [C.c_uint32, _vp, _vp, _vp]),
+    "pcv_xray_png_encode": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pcv_octree_nodes_blob": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pcv_transform_points": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(Points), _vp, _vp, _vp]),
 }

@@ -1,5 +1,6 @@
-// pcv_xray.hip — xray leaf tiles on the device: the leaf level of build_xray_quadtree (xray/src/generation.rs:557-600),
-// rasterised straight from a batched point query (pcv_query.hip) without materialising its points.
+// pcv_xray.hip — xray's build_xray_quadtree (xray/src/generation.rs:557-616) on the device: the leaf level rasterised
+// straight from a batched point query (pcv_query.hip) without materialising its points, then every parent level (second
+// half of the file) and the quadtree directory.
 //
 //   host   leaf geometry   get_bounding_box :550 (Aabb::transform, src/geometry/aabb.rs:58-66),
 //                          find_quadtree_bounding_rect_and_levels :515, Node::from_node_id_and_root_bounding_rect and
@@ -478,9 +479,19 @@ struct pcv_xray {
   pcv_ctx* ctx = nullptr;
   uint32_t W = 0;
   LeafGeometry geo;
+  uint32_t root_level = 0;
+  uint64_t root_index = 0;
+  uint32_t bg = 0;                // tile_background_color.to_u8(), packed RGBA8
   std::vector<uint64_t> created;  // positions in the leaf list
   std::vector<uint64_t> kept, drawn;
   uint32_t* d_images = nullptr;
+  // parent levels (pcv_xray_build_parents): the node list after the created leaves, deepest - 1 up to root_level, each
+  // level in ascending index; level_first[k] is the first parent of level deepest - 1 - k in that list
+  bool parents_built = false;
+  std::vector<uint32_t> parent_level;
+  std::vector<uint64_t> parent_index;
+  std::vector<uint64_t> level_first;
+  uint32_t* d_parents = nullptr;
 };
 
 extern "C" int pcv_xray_leaf_tiles(uint32_t tile_size_px, double pixel_size_m, const double bbox_min[3], const double bbox_max[3],
@@ -538,6 +549,7 @@ extern "C" int pcv_xray_finalize(int fn, uint64_t count, const double* in, uint8
 extern "C" void pcv_xray_free(pcv_xray* x) {
   if (!x) return;
   x->ctx->dev_free(x->d_images);
+  x->ctx->dev_free(x->d_parents);
   delete x;
 }
 
@@ -550,6 +562,9 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* tree, const pcv_xray_params* p, pc
   const LeafGeometry& g = x->geo;
   const uint32_t S = (uint32_t)g.index.size(), W = p->tile_size_px;
   x->W = W;
+  x->root_level = p->root_level;
+  x->root_index = p->root_index;
+  x->bg = p->background == PCV_XRAY_BG_TRANSPARENT ? 0x00ffffffu : 0xffffffffu;  // TRANSPARENT / WHITE .to_u8()
   // one shape per leaf tile (xray_from_points :470-476)
   std::vector<pcv_shape> shapes(S);
   for (uint32_t i = 0; i < S; ++i) {
@@ -679,7 +694,7 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* tree, const pcv_xray_params* p, pc
   aa.W = W;
   aa.nbx = nbx;
   aa.nblocks = nblocks;
-  aa.bg = p->background == PCV_XRAY_BG_TRANSPARENT ? 0x00ffffffu : 0xffffffffu;  // TRANSPARENT / WHITE .to_u8()
+  aa.bg = x->bg;
   aa.colormap = p->colormap;
   aa.max_stddev = p->max_stddev;
   // accumulation: as many workgroups as are resident at once, striding over the group's buckets (the experiment build
@@ -809,4 +824,601 @@ extern "C" int pcv_xray_images(pcv_xray* x, uint64_t first, uint64_t count, uint
                                     mem == PCV_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
   PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PCV_OK;
+}
+
+// ---- parent levels: create_non_leaf_nodes (:656-682), build_node (:726-759), build_parent (:410-450) -------------------
+//
+//   host   parent sets     parent_id of the level below, from deepest - 1 up to root_level (create_non_leaf_nodes)
+//   host   2:1 Lanczos3    the taps of image 0.23.10 imageops::resize(FilterType::Lanczos3) for a square 2W -> W resize,
+//                          as DynamicImage::resize reaches it (sample.rs vertical_sample, then horizontal_sample): a
+//                          restatement of the pinned crate version, computed once per W with libm's sinf
+//   K_xp   xray_parent     per (parent, 32 x 32 output block): the virtual 2W x 2W image of build_parent (children 1, 0,
+//                          3, 2 at (0, 0), (0, W), (W, 0), (W, W); a missing child is the background) over the block's
+//                          window into LDS, the vertical pass into LDS as f32, the horizontal pass, clamp, round, u8
+//
+// Every output pixel is a fixed sequence of f32 multiplies and adds (no FMA: -ffp-contract=off), so the images do not
+// depend on scheduling and equal a host evaluation of the same sequence bit for bit.
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <atomic>
+#include <mutex>
+#include <thread>
+
+namespace {
+
+constexpr uint32_t kTaps = 12;        // 2 x support 6: taps of an interior output index
+constexpr uint32_t kWin = 2 * (kBlk - 1) + kTaps;  // 74: input rows / columns a 32-pixel output block reads
+
+struct LanczosTap {  // one output index o: input [left, left + count), normalised weights
+  uint32_t left, count;
+  float w[kTaps];
+};
+
+// image::imageops::sample sinc / lanczos3: f32 throughout, sin = libm sinf (what f32::sin calls on linux-gnu)
+float sinc_f32(float t) {
+  if (t == 0.0f) return 1.0f;
+  const float a = t * 3.14159265358979323846264338327950288f;  // f32::consts::PI
+  return ::sinf(a) / a;
+}
+float lanczos3_f32(float x) { return std::fabs(x) < 3.0f ? sinc_f32(x) * sinc_f32(x / 3.0f) : 0.0f; }
+
+// vertical_sample / horizontal_sample's filter table for 2W -> W: ratio 2, support 3 x 2 = 6
+void lanczos_taps(uint32_t W, std::vector<LanczosTap>& taps) {
+  taps.assign(W, LanczosTap{});
+  const float ratio = 2.0f, sratio = 2.0f, support = 3.0f * sratio;
+  const int64_t n = 2 * (int64_t)W;
+  for (uint32_t o = 0; o < W; ++o) {
+    const float c = ((float)o + 0.5f) * ratio;
+    const int64_t left = std::min<int64_t>(std::max<int64_t>((int64_t)std::floor(c - support), 0), n - 1);
+    const int64_t right = std::min<int64_t>(std::max<int64_t>((int64_t)std::ceil(c + support), left + 1), n);
+    const float ci = c - 0.5f;
+    LanczosTap& t = taps[o];
+    t.left = (uint32_t)left;
+    t.count = (uint32_t)(right - left);
+    float sum = 0.0f;
+    for (int64_t i = left; i < right; ++i) {
+      const float w = lanczos3_f32(((float)i - ci) / sratio);
+      t.w[i - left] = w;
+      sum += w;
+    }
+    for (uint32_t k = 0; k < t.count; ++k) t.w[k] /= sum;
+  }
+}
+
+struct XrayParentArgs {
+  const uint32_t* leaves;   // created leaf images, node positions [0, nleaves)
+  const uint32_t* parents;  // parent images, node positions [nleaves, ...)
+  uint64_t nleaves;
+  const int64_t* slots;     // 4 per parent of the level: node position of child c, -1 where it is missing
+  uint32_t* out;            // the level's first parent image
+  uint64_t nparents;
+  const LanczosTap* taps;   // W entries, rows and columns alike
+  uint32_t W, nbx, bg;
+};
+
+__device__ __forceinline__ float4 unpack_f4(uint32_t p) {
+  return make_float4((float)(p & 255u), (float)((p >> 8) & 255u), (float)((p >> 16) & 255u), (float)(p >> 24));
+}
+// horizontal_sample's store: clamp(t, 0, 255) then FloatNearest (round half away from zero) as u8
+__device__ __forceinline__ uint32_t to_u8_round(float t) {
+  t = t < 0.0f ? 0.0f : (t > 255.0f ? 255.0f : t);
+  return (uint32_t)roundf(t);
+}
+
+// 256 threads per (parent, output block); the grid strides over parents x blocks
+__global__ __launch_bounds__(256) void xray_parent_kernel(XrayParentArgs a) {
+  __shared__ uint32_t win[kWin * kWin];   // input window of the virtual image, RGBA8
+  __shared__ float4 mid[kBlk * kWin];     // vertical pass: block rows x window columns, f32 RGBA
+  const uint32_t nblocks = a.nbx * a.nbx;
+  const uint64_t total = a.nparents * nblocks;
+  const uint32_t W = a.W;
+  for (uint64_t b = blockIdx.x; b < total; b += gridDim.x) {
+    const uint64_t parent = b / nblocks;
+    const uint32_t blk = (uint32_t)(b % nblocks), by = blk / a.nbx, bx = blk % a.nbx;
+    const uint32_t oy0 = by * kBlk, ox0 = bx * kBlk;
+    const uint32_t oy1 = min(oy0 + kBlk, W), ox1 = min(ox0 + kBlk, W);  // exclusive
+    const LanczosTap& ty0 = a.taps[oy0];
+    const LanczosTap& ty1 = a.taps[oy1 - 1];
+    const LanczosTap& tx0 = a.taps[ox0];
+    const LanczosTap& tx1 = a.taps[ox1 - 1];
+    const uint32_t row0 = ty0.left, nrow = ty1.left + ty1.count - row0;  // <= kWin: left and right never decrease
+    const uint32_t col0 = tx0.left, ncol = tx1.left + tx1.count - col0;
+    const int64_t* slot = a.slots + 4 * parent;
+    // the window: child pixel or background (build_parent's from_pixel + copy_from)
+    for (uint32_t i = threadIdx.x; i < nrow * ncol; i += blockDim.x) {
+      const uint32_t vy = row0 + i / ncol, vx = col0 + i % ncol;
+      const uint32_t top = vy < W, lft = vx < W;
+      const uint32_t child = lft ? (top ? 1u : 0u) : (top ? 3u : 2u);
+      const int64_t s = slot[child];
+      uint32_t px = a.bg;
+      if (s >= 0) {
+        const uint32_t* img = (uint64_t)s < a.nleaves ? a.leaves + (uint64_t)s * W * W : a.parents + ((uint64_t)s - a.nleaves) * W * W;
+        px = img[(uint64_t)(vy - (top ? 0u : W)) * W + (vx - (lft ? 0u : W))];
+      }
+      win[(i / ncol) * kWin + i % ncol] = px;
+    }
+    __syncthreads();
+    // vertical pass: t = t + p * w in tap order, f32, neither clamped nor rounded
+    for (uint32_t i = threadIdx.x; i < (oy1 - oy0) * ncol; i += blockDim.x) {
+      const uint32_t r = i / ncol, c = i % ncol;
+      const LanczosTap& t = a.taps[oy0 + r];
+      float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      const uint32_t* src = win + (t.left - row0) * kWin + c;
+      for (uint32_t k = 0; k < t.count; ++k) {
+        const float4 p = unpack_f4(src[k * kWin]);
+        const float w = t.w[k];
+        acc.x = acc.x + p.x * w;
+        acc.y = acc.y + p.y * w;
+        acc.z = acc.z + p.z * w;
+        acc.w = acc.w + p.w * w;
+      }
+      mid[r * kWin + c] = acc;
+    }
+    __syncthreads();
+    // horizontal pass over the intermediate, then clamp, round, u8
+    uint32_t* out = a.out + parent * W * W;
+    for (uint32_t i = threadIdx.x; i < kBlkPx; i += blockDim.x) {
+      const uint32_t r = i / kBlk, c = i % kBlk;
+      const uint32_t oy = oy0 + r, ox = ox0 + c;
+      if (oy >= oy1 || ox >= ox1) continue;
+      const LanczosTap& t = a.taps[ox];
+      float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      const float4* src = mid + r * kWin + (t.left - col0);
+      for (uint32_t k = 0; k < t.count; ++k) {
+        const float4 p = src[k];
+        const float w = t.w[k];
+        acc.x = acc.x + p.x * w;
+        acc.y = acc.y + p.y * w;
+        acc.z = acc.z + p.z * w;
+        acc.w = acc.w + p.w * w;
+      }
+      out[(uint64_t)oy * W + ox] = to_u8_round(acc.x) | to_u8_round(acc.y) << 8 | to_u8_round(acc.z) << 16 | to_u8_round(acc.w) << 24;
+    }
+    __syncthreads();  // the next block overwrites the window and the intermediate
+  }
+}
+
+// ---- PNG (RGBA8, colour type 6, depth 8, one IDAT, filter 0, stored deflate blocks) and meta.pb ---------------------
+uint32_t crc32_table[256];
+std::once_flag crc32_once;
+uint32_t crc32_update(uint32_t crc, const uint8_t* p, size_t n) {
+  std::call_once(crc32_once, [] {
+    for (uint32_t i = 0; i < 256; ++i) {
+      uint32_t c = i;
+      for (int k = 0; k < 8; ++k) c = c & 1 ? 0xedb88320u ^ (c >> 1) : c >> 1;
+      crc32_table[i] = c;
+    }
+  });
+  for (size_t i = 0; i < n; ++i) crc = crc32_table[(crc ^ p[i]) & 255u] ^ (crc >> 8);
+  return crc;
+}
+
+constexpr uint64_t kStored = 65535;  // bytes per stored deflate block
+uint64_t png_size(uint32_t w, uint32_t h) {
+  const uint64_t raw = (uint64_t)h * (1 + 4ull * w);
+  const uint64_t blocks = (raw + kStored - 1) / kStored;
+  return 8 + (12 + 13) + (12 + 2 + 5 * blocks + raw + 4) + 12;
+}
+
+void put_be32(uint8_t* o, uint32_t v) {
+  o[0] = (uint8_t)(v >> 24);
+  o[1] = (uint8_t)(v >> 16);
+  o[2] = (uint8_t)(v >> 8);
+  o[3] = (uint8_t)v;
+}
+
+// writes png_size(w, h) bytes
+void png_encode(const uint8_t* rgba, uint32_t w, uint32_t h, uint8_t* out) {
+  static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+  uint8_t* o = out;
+  std::memcpy(o, sig, 8);
+  o += 8;
+  auto chunk_end = [&](uint8_t* type_at) {  // data follows the 4-byte type; the CRC covers type and data
+    const uint32_t len = (uint32_t)(o - type_at - 4);
+    put_be32(type_at - 4, len);
+    put_be32(o, crc32_update(0xffffffffu, type_at, (size_t)(o - type_at)) ^ 0xffffffffu);
+    o += 4;
+  };
+  // IHDR
+  uint8_t* t = o + 4;
+  std::memcpy(t, "IHDR", 4);
+  o = t + 4;
+  put_be32(o, w);
+  put_be32(o + 4, h);
+  o[8] = 8;   // bit depth
+  o[9] = 6;   // RGBA
+  o[10] = 0;  // deflate
+  o[11] = 0;  // adaptive filtering (every row: filter 0)
+  o[12] = 0;  // no interlace
+  o += 13;
+  chunk_end(t);
+  // IDAT: zlib header (deflate, 32 K window, no dictionary, FCHECK), stored blocks, Adler-32
+  t = o + 4;
+  std::memcpy(t, "IDAT", 4);
+  o = t + 4;
+  *o++ = 0x78;
+  *o++ = 0x01;
+  const uint64_t row = 1 + 4ull * w, raw = (uint64_t)h * row;
+  uint32_t s1 = 1, s2 = 0;
+  uint64_t done = 0;
+  uint8_t* blk = nullptr;
+  uint64_t room = 0;
+  auto put = [&](const uint8_t* p, uint64_t n) {  // appends scanline bytes, opening stored blocks as they fill
+    while (n) {
+      if (room == 0) {
+        const uint64_t len = std::min<uint64_t>(kStored, raw - done);
+        blk = o;
+        blk[0] = done + len == raw ? 1 : 0;  // BFINAL, BTYPE = 00
+        blk[1] = (uint8_t)len;
+        blk[2] = (uint8_t)(len >> 8);
+        blk[3] = (uint8_t)~len;
+        blk[4] = (uint8_t)(~len >> 8);
+        o += 5;
+        room = len;
+      }
+      const uint64_t k = std::min(n, room);
+      std::memcpy(o, p, k);
+      for (uint64_t i = 0; i < k;) {  // Adler-32, reduced at most every 5 552 bytes
+        const uint64_t m = std::min<uint64_t>(5552, k - i);
+        for (uint64_t j = 0; j < m; ++j) {
+          s1 += p[i + j];
+          s2 += s1;
+        }
+        s1 %= 65521u;
+        s2 %= 65521u;
+        i += m;
+      }
+      o += k;
+      p += k;
+      n -= k;
+      room -= k;
+      done += k;
+    }
+  };
+  const uint8_t filter = 0;
+  for (uint32_t y = 0; y < h; ++y) {
+    put(&filter, 1);
+    put(rgba + (uint64_t)y * 4 * w, 4ull * w);
+  }
+  put_be32(o, s2 << 16 | s1);
+  o += 4;
+  chunk_end(t);
+  t = o + 4;
+  std::memcpy(t, "IEND", 4);
+  o = t + 4;
+  chunk_end(t);
+}
+
+// rust-protobuf 2.x, proto3: fields in number order, zero scalars omitted, set message fields always written
+void pb_varint(std::vector<uint8_t>& o, uint64_t v) {
+  while (v >= 0x80) {
+    o.push_back((uint8_t)(v | 0x80));
+    v >>= 7;
+  }
+  o.push_back((uint8_t)v);
+}
+void pb_double(std::vector<uint8_t>& o, uint32_t field, double v) {
+  if (v == 0.0) return;
+  pb_varint(o, field << 3 | 1);
+  uint8_t b[8];
+  std::memcpy(b, &v, 8);
+  o.insert(o.end(), b, b + 8);
+}
+void pb_uint(std::vector<uint8_t>& o, uint32_t field, uint64_t v) {
+  if (v == 0) return;
+  pb_varint(o, field << 3);
+  pb_varint(o, v);
+}
+void pb_bytes(std::vector<uint8_t>& o, uint32_t field, const std::vector<uint8_t>& m) {
+  pb_varint(o, field << 3 | 2);
+  pb_varint(o, m.size());
+  o.insert(o.end(), m.begin(), m.end());
+}
+
+std::string quad_name(uint32_t level, uint64_t index) {  // NodeId Display (quadtree/src/lib.rs:218-234)
+  std::string s = "r";
+  for (int l = (int)level - 1; l >= 0; --l) s.push_back((char)('0' + ((index >> (2 * l)) & 3u)));
+  return s;
+}
+
+bool write_at(int dirfd, const std::string& name, const uint8_t* data, uint64_t len) {
+  const int fd = openat(dirfd, name.c_str(), O_CREAT | O_WRONLY | O_TRUNC | O_CLOEXEC, 0666);
+  if (fd < 0) return false;
+  bool ok = true;
+  while (len) {
+    const ssize_t w = ::write(fd, data, (size_t)len);
+    if (w <= 0) {
+      ok = false;
+      break;
+    }
+    data += w;
+    len -= (uint64_t)w;
+  }
+  return ::close(fd) == 0 && ok;
+}
+
+}  // namespace
+
+extern "C" int pcv_xray_lanczos_taps(uint32_t tile_size_px, uint32_t* left, uint32_t* count, float* weights) {
+  if (tile_size_px == 0 || tile_size_px > kMaxTilePx) return PCV_E_INVALID;
+  std::vector<LanczosTap> taps;
+  lanczos_taps(tile_size_px, taps);
+  for (uint32_t o = 0; o < tile_size_px; ++o) {
+    if (left) left[o] = taps[o].left;
+    if (count) count[o] = taps[o].count;
+    if (weights)
+      for (uint32_t k = 0; k < kTaps; ++k) weights[(uint64_t)o * kTaps + k] = k < taps[o].count ? taps[o].w[k] : 0.0f;
+  }
+  return PCV_OK;
+}
+
+extern "C" int pcv_xray_png_encode(const uint8_t* rgba, uint32_t w, uint32_t h, uint8_t* out, uint64_t capacity, uint64_t* needed) {
+  if (w == 0 || h == 0 || w > (1u << 30) / 4 || (!rgba && out)) return PCV_E_INVALID;
+  const uint64_t n = png_size(w, h);
+  if (needed) *needed = n;
+  if (out && capacity >= n) png_encode(rgba, w, h, out);
+  return PCV_OK;
+}
+
+static int xray_build_parents(pcv_xray* x) {
+  pcv_ctx* ctx = x->ctx;
+  const uint32_t deepest = x->geo.deepest_level, W = x->W;
+  const uint64_t nc = x->created.size();
+  std::vector<uint32_t> plevel;
+  std::vector<uint64_t> pindex, first;
+  // create_non_leaf_nodes: the parent ids of the level below, root_level ..= deepest - 1 (ascending index per level)
+  std::vector<uint64_t> below(nc);
+  for (uint64_t c = 0; c < nc; ++c) below[c] = x->geo.index[x->created[c]];
+  for (uint32_t level = deepest; nc && level > x->root_level; --level) {
+    std::vector<uint64_t> up(below.size());
+    for (size_t i = 0; i < below.size(); ++i) up[i] = below[i] >> 2;
+    std::sort(up.begin(), up.end());
+    up.erase(std::unique(up.begin(), up.end()), up.end());
+    first.push_back(pindex.size());
+    for (uint64_t i : up) {
+      plevel.push_back(level - 1);
+      pindex.push_back(i);
+    }
+    below.swap(up);
+  }
+  first.push_back(pindex.size());
+  const uint64_t np = pindex.size();
+  if (np == 0) return PCV_OK;
+  // child slots: node positions of (index << 2) + c one level down, -1 where that child was not created
+  std::vector<std::pair<uint64_t, uint64_t>> leaf_pos(nc);  // (leaf index, node position)
+  for (uint64_t c = 0; c < nc; ++c) leaf_pos[c] = {x->geo.index[x->created[c]], c};
+  std::sort(leaf_pos.begin(), leaf_pos.end());
+  std::vector<int64_t> slots(4 * np, -1);
+  for (size_t k = 0; k + 1 < first.size(); ++k) {
+    for (uint64_t p = first[k]; p < first[k + 1]; ++p)
+      for (uint64_t c = 0; c < 4; ++c) {
+        const uint64_t child = (pindex[p] << 2) + c;
+        if (k == 0) {
+          auto it = std::lower_bound(leaf_pos.begin(), leaf_pos.end(), std::make_pair(child, (uint64_t)0));
+          if (it != leaf_pos.end() && it->first == child) slots[4 * p + c] = (int64_t)it->second;
+        } else {
+          auto b = pindex.begin() + (ptrdiff_t)first[k - 1], e = pindex.begin() + (ptrdiff_t)first[k];
+          auto it = std::lower_bound(b, e, child);
+          if (it != e && *it == child) slots[4 * p + c] = (int64_t)(nc + (uint64_t)(it - pindex.begin()));
+        }
+      }
+  }
+  std::vector<LanczosTap> taps;
+  lanczos_taps(W, taps);
+  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  int rc;
+  uint32_t* d_parents = nullptr;
+  if ((rc = ctx->dev_alloc((void**)&d_parents, 4ull * W * W * np)))  // every parent image before any launch
+    return ctx->fail(PCV_E_OOM, "xray: no device memory for " + std::to_string(np) + " parent images (" + ctx->last_error + ")");
+  PcvScratch sc(ctx);
+  int64_t* d_slots;
+  LanczosTap* d_taps;
+  if ((rc = sc.get(&d_slots, 4 * np)) || (rc = sc.get(&d_taps, W))) {
+    ctx->dev_free(d_parents);
+    return rc;
+  }
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_slots, slots.data(), 8 * slots.size(), hipMemcpyHostToDevice, ctx->stream));
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_taps, taps.data(), sizeof(LanczosTap) * W, hipMemcpyHostToDevice, ctx->stream));
+  int cus = 0, per_cu = 0;
+  PCV_HIP_CHECK(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+  PCV_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xray_parent_kernel, 256, 0));
+  const uint64_t resident = (uint64_t)std::max(cus, 1) * (uint64_t)std::max(per_cu, 1);
+  XrayParentArgs a{};
+  a.leaves = x->d_images;
+  a.parents = d_parents;
+  a.nleaves = nc;
+  a.taps = d_taps;
+  a.W = W;
+  a.nbx = (W + kBlk - 1) / kBlk;
+  a.bg = x->bg;
+  for (size_t k = 0; k + 1 < first.size(); ++k) {  // a level reads the one below: one launch each, in order
+    a.slots = d_slots + 4 * first[k];
+    a.out = d_parents + first[k] * W * W;
+    a.nparents = first[k + 1] - first[k];
+    const uint64_t work = a.nparents * a.nbx * a.nbx;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(work, 4 * resident);
+    {
+      PcvProf prof(ctx, PCV_K_XRAY_PARENT);
+      hipLaunchKernelGGL(xray_parent_kernel, dim3(grid), dim3(256), 0, ctx->stream, a);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+      (void)hipStreamSynchronize(ctx->stream);
+      ctx->dev_free(d_parents);
+      return ctx->fail(PCV_E_HIP, std::string("xray_parent_kernel: ") + hipGetErrorString(e));
+    }
+  }
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
+    ctx->dev_free(d_parents);
+    return ctx->fail(PCV_E_HIP, "xray: parent levels failed");
+  }
+  x->d_parents = d_parents;
+  x->parent_level.swap(plevel);
+  x->parent_index.swap(pindex);
+  x->level_first.swap(first);
+  return PCV_OK;
+}
+
+extern "C" int pcv_xray_build_parents(pcv_xray* x) {
+  if (!x) return PCV_E_INVALID;
+  if (x->parents_built) return PCV_OK;
+  const int rc = xray_build_parents(x);
+  if (rc) return rc;
+  x->parents_built = true;
+  x->ctx->prof_resolve();
+  return PCV_OK;
+}
+
+extern "C" int pcv_xray_nodes(const pcv_xray* x, uint64_t* num_nodes, uint64_t capacity, uint32_t* level, uint64_t* index) {
+  if (!x) return PCV_E_INVALID;
+  const uint64_t nc = x->created.size(), n = nc + x->parent_index.size();
+  if (num_nodes) *num_nodes = n;
+  for (uint64_t i = 0; i < std::min(n, capacity); ++i) {
+    if (level) level[i] = i < nc ? x->geo.deepest_level : x->parent_level[i - nc];
+    if (index) index[i] = i < nc ? x->geo.index[x->created[i]] : x->parent_index[i - nc];
+  }
+  return PCV_OK;
+}
+
+// node images [first, first + count) of the node list into dst (host or device), no synchronisation
+static int queue_node_images(pcv_xray* x, uint64_t first, uint64_t count, uint8_t* dst, hipMemcpyKind kind) {
+  pcv_ctx* ctx = x->ctx;
+  const uint64_t nc = x->created.size(), tile_bytes = 4ull * x->W * x->W;
+  const uint64_t nl = first < nc ? std::min(count, nc - first) : 0;
+  if (nl)
+    PCV_HIP_CHECK(ctx, hipMemcpyAsync(dst, reinterpret_cast<const uint8_t*>(x->d_images) + first * tile_bytes, nl * tile_bytes, kind, ctx->stream));
+  if (count > nl)
+    PCV_HIP_CHECK(ctx, hipMemcpyAsync(dst + nl * tile_bytes, reinterpret_cast<const uint8_t*>(x->d_parents) + (first + nl - nc) * tile_bytes,
+                                      (count - nl) * tile_bytes, kind, ctx->stream));
+  return PCV_OK;
+}
+
+extern "C" int pcv_xray_node_images(pcv_xray* x, uint64_t first, uint64_t count, uint64_t capacity, int mem, uint8_t* rgba) {
+  if (!x) return PCV_E_INVALID;
+  pcv_ctx* ctx = x->ctx;
+  const uint64_t n = x->created.size() + x->parent_index.size();
+  if (first > n || count > n - first) return ctx->fail(PCV_E_INVALID, "xray: node range past the end");
+  if (mem != PCV_MEM_HOST && mem != PCV_MEM_DEVICE) return ctx->fail(PCV_E_INVALID, "bad mem");
+  const uint64_t tile_bytes = 4ull * x->W * x->W;
+  if (count * tile_bytes > capacity) return ctx->fail(PCV_E_INVALID, "xray: capacity below count x W x W x 4 bytes");
+  if (count == 0) return PCV_OK;
+  if (!rgba) return ctx->fail(PCV_E_INVALID, "null output");
+  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  int rc = queue_node_images(x, first, count, rgba, mem == PCV_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice);
+  if (rc) return rc;
+  PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return PCV_OK;
+}
+
+extern "C" int pcv_xray_write_dir(pcv_xray* x, const char* directory) {
+  if (!x) return PCV_E_INVALID;
+  pcv_ctx* ctx = x->ctx;
+  if (!directory) return ctx->fail(PCV_E_INVALID, "null directory");
+  const uint64_t nc = x->created.size(), n = nc + x->parent_index.size();
+  if (!x->parents_built && nc && x->root_level < x->geo.deepest_level)
+    return ctx->fail(PCV_E_INVALID, "xray: parent levels are not built (pcv_xray_build_parents)");
+  const std::string dir(directory);
+  ::mkdir(dir.c_str(), 0777);  // build_xray_quadtree :565 ignores errors: the directory may be there
+  struct stat st;
+  if (stat(dir.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) return ctx->fail(PCV_E_IO, "cannot create directory " + dir);
+  const int dirfd = open(dir.c_str(), O_RDONLY | O_DIRECTORY | O_CLOEXEC);
+  if (dirfd < 0) return ctx->fail(PCV_E_IO, "cannot open directory " + dir);
+  // the node images come down in chunks through two pinned buffers: chunk k + 1 is copied while a pool of host threads
+  // encodes and writes chunk k (no HIP call in a writer thread)
+  const uint32_t W = x->W;
+  const uint64_t tile_bytes = 4ull * W * W;
+  const uint64_t per_chunk = std::max<uint64_t>(1, std::min<uint64_t>(n, (64ull << 20) / tile_bytes));
+  const uint64_t chunks = (n + per_chunk - 1) / per_chunk;
+  uint8_t* host[2] = {nullptr, nullptr};
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  int rc = PCV_OK;
+  if (n) {
+    if (hipSetDevice(ctx->device) != hipSuccess) rc = ctx->fail(PCV_E_HIP, "hipSetDevice");
+    for (int k = 0; !rc && k < 2 && (uint64_t)k < chunks; ++k) {
+      rc = ctx->host_alloc((void**)&host[k], per_chunk * tile_bytes);
+      if (!rc && hipEventCreateWithFlags(&ev[k], hipEventDisableTiming) != hipSuccess) rc = ctx->fail(PCV_E_HIP, "hipEventCreate");
+    }
+  }
+  unsigned nthreads = std::thread::hardware_concurrency();
+  if (nthreads == 0) nthreads = 4;
+  if (nthreads > 8) nthreads = 8;  // one directory: more writers queue on its lock (pcv_io.cpp)
+  std::atomic<int> failed{0};
+  std::string first_error;
+  std::mutex err_mu;
+  auto queue = [&](uint64_t k) -> int {
+    const uint64_t f = k * per_chunk, c = std::min(per_chunk, n - f);
+    int r = queue_node_images(x, f, c, host[k & 1], hipMemcpyDeviceToHost);
+    if (!r && hipEventRecord(ev[k & 1], ctx->stream) != hipSuccess) r = ctx->fail(PCV_E_HIP, "hipEventRecord");
+    return r;
+  };
+  if (!rc && chunks) rc = queue(0);
+  for (uint64_t k = 0; !rc && k < chunks; ++k) {
+    if (k + 1 < chunks && (rc = queue(k + 1))) break;  // its buffer's writers (chunk k - 1) have finished
+    if (hipEventSynchronize(ev[k & 1]) != hipSuccess) {
+      rc = ctx->fail(PCV_E_HIP, "xray: image download failed");
+      break;
+    }
+    const uint64_t f = k * per_chunk, c = std::min(per_chunk, n - f);
+    const uint8_t* buf = host[k & 1];
+    std::atomic<uint64_t> next{0};
+    auto worker = [&]() {
+      std::vector<uint8_t> png(png_size(W, W));
+      for (;;) {
+        const uint64_t i = next.fetch_add(1);
+        if (i >= c || failed.load()) return;
+        const uint64_t node = f + i;
+        const std::string name = node < nc ? quad_name(x->geo.deepest_level, x->geo.index[x->created[node]]) + ".png"
+                                           : quad_name(x->parent_level[node - nc], x->parent_index[node - nc]) + ".png";
+        png_encode(buf + i * tile_bytes, W, W, png.data());
+        if (!write_at(dirfd, name, png.data(), png.size())) {
+          std::lock_guard<std::mutex> g(err_mu);
+          if (!failed.exchange(1)) first_error = "cannot write " + dir + "/" + name;
+        }
+      }
+    };
+    const unsigned nt = (unsigned)std::min<uint64_t>(nthreads, c);
+    std::vector<std::thread> pool;
+    for (unsigned t = 1; t < nt; ++t) pool.emplace_back(worker);
+    worker();
+    for (auto& th : pool) th.join();
+    if (failed.load()) break;
+  }
+  (void)hipStreamSynchronize(ctx->stream);
+  for (int k = 0; k < 2; ++k) {
+    if (ev[k]) (void)hipEventDestroy(ev[k]);
+    if (host[k]) ctx->host_release(host[k]);
+  }
+  if (!rc && failed.load()) rc = ctx->fail(PCV_E_IO, first_error);
+  if (!rc) {
+    // Meta (xray_proto Meta, CURRENT_VERSION 3) to get_meta_pb_path: the root id with "r" -> "meta", + ".pb"
+    double rect[3] = {x->geo.rect[0], x->geo.rect[1], x->geo.rect[2]};
+    for (int l = (int)x->root_level - 1; l >= 0; --l) {  // root_node.bounding_rect
+      const uint32_t ci = (uint32_t)(x->root_index >> (2 * l)) & 3u;
+      const double half = rect[2] / 2.0;
+      if (ci & 1u) rect[1] += half;
+      if (ci & 2u) rect[0] += half;
+      rect[2] = half;
+    }
+    std::vector<uint8_t> meta, r, mn;
+    pb_uint(meta, 1, 3);
+    pb_double(mn, 1, rect[0]);
+    pb_double(mn, 2, rect[1]);
+    pb_bytes(r, 3, mn);
+    pb_double(r, 4, rect[2]);
+    pb_bytes(meta, 2, r);
+    pb_uint(meta, 3, x->geo.deepest_level);
+    pb_uint(meta, 4, W);
+    for (uint64_t i = 0; i < n; ++i) {
+      std::vector<uint8_t> id;
+      pb_uint(id, 1, i < nc ? x->geo.deepest_level : x->parent_level[i - nc]);
+      pb_uint(id, 2, i < nc ? x->geo.index[x->created[i]] : x->parent_index[i - nc]);
+      pb_bytes(meta, 5, id);
+    }
+    const std::string name = "meta" + quad_name(x->root_level, x->root_index).substr(1) + ".pb";
+    if (!write_at(dirfd, name, meta.data(), meta.size())) rc = ctx->fail(PCV_E_IO, "cannot write " + dir + "/" + name);
+  }
+  ::close(dirfd);
+  return rc;
 }

@@ -5,6 +5,7 @@ Reference names kept: `build_octree(output_directory, resolution, bounding_box, 
 Inputs may be numpy arrays (host) or torch CUDA tensors (device-resident; zero copy).
 """
 import ctypes as C
+import os
 import weakref
 
 import numpy as np
@@ -911,6 +912,15 @@ class OctreeResult:
         self.ctx._check(self.lib.pcv_xray_run(self.ctx.handle, self.handle, C.byref(p), C.byref(h)))
         return XrayTiles(self.ctx, h, int(tile_size_px))
 
+    def xray_quadtree(self, tile_size_px=256, pixel_size_m=None, strategy="xray", query_from_global=None, intensity_interval=None,
+                      background="white", root_node_id="r", max_workspace_bytes=None):
+        """xray_tiles (same arguments) with every level above the leaves up to root_node_id built on the device
+        (create_non_leaf_nodes, generation.rs:656-682): the whole quadtree; XrayTiles.write puts it on disk."""
+        xt = self.xray_tiles(tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background, root_node_id,
+                             max_workspace_bytes)
+        xt.build_parents()
+        return xt
+
     def nodes_blob(self, node_indices):
         """octree_web_viewer's /nodes_data reply body for the given nodes."""
         idx = np.ascontiguousarray(node_indices, dtype=np.uint64)
@@ -1153,6 +1163,31 @@ def xray_finalize(fn, values):
     return out
 
 
+def xray_lanczos_taps(tile_size_px):
+    """pcv_xray_lanczos_taps (host only): (left (W,) u32, count (W,) u32, weights (W, 12) f32) of the 2:1 resize."""
+    W = int(tile_size_px)
+    left, count = np.zeros(max(W, 1), dtype=np.uint32), np.zeros(max(W, 1), dtype=np.uint32)
+    w = np.zeros((max(W, 1), 12), dtype=np.float32)
+    rc = L.load_library().pcv_xray_lanczos_taps(W, left.ctypes.data, count.ctypes.data, w.ctypes.data)
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, f"pcv_xray_lanczos_taps({W})")
+    return left[:W], count[:W], w[:W]
+
+
+def xray_png_encode(rgba):
+    """pcv_xray_png_encode (host only): an (h, w, 4) uint8 image as PNG bytes (stored deflate, filter 0)."""
+    img = np.ascontiguousarray(rgba, dtype=np.uint8)
+    h, w = int(img.shape[0]), int(img.shape[1])
+    lib = L.load_library()
+    need = C.c_uint64()
+    rc = lib.pcv_xray_png_encode(img.ctypes.data, w, h, None, 0, C.byref(need))
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, f"pcv_xray_png_encode({w} x {h})")
+    out = np.zeros(need.value, dtype=np.uint8)
+    lib.pcv_xray_png_encode(img.ctypes.data, w, h, out.ctypes.data, out.nbytes, C.byref(need))
+    return out.tobytes()
+
+
 class XrayTiles:
     """The result of OctreeResult.xray_tiles: the leaf list of the quadtree and the created tiles' RGBA8 images (device)."""
 
@@ -1193,6 +1228,54 @@ class XrayTiles:
 
     def image(self, i):
         return self.images(i, 1)[0]
+
+    def build_parents(self):
+        """Every level above the leaves up to root_node_id (pcv_xray_build_parents); a second call does nothing."""
+        self._alive()
+        self.ctx._check(self.lib.pcv_xray_build_parents(self.handle))
+
+    def nodes(self):
+        """(level, index) arrays of Meta.nodes in pcv_xray_nodes' order: created leaves, then parents level by level."""
+        self._alive()
+        n = C.c_uint64()
+        self.lib.pcv_xray_nodes(self.handle, C.byref(n), 0, None, None)
+        level, index = np.zeros(max(n.value, 1), dtype=np.uint32), np.zeros(max(n.value, 1), dtype=np.uint64)
+        self.lib.pcv_xray_nodes(self.handle, C.byref(n), n.value, level.ctypes.data, index.ctypes.data)
+        return level[:n.value], index[:n.value]
+
+    @property
+    def node_ids(self):
+        """Names of the nodes ("r" + base-4 digits) in node_images' order."""
+        level, index = self.nodes()
+        return [quadtree_node_name(int(l), int(i)) for l, i in zip(level, index)]
+
+    def node_images(self, first=0, count=None, device=False):
+        """Nodes [first, first + count) of node_ids as a (count, W, W, 4) uint8 array (numpy, or a torch tensor on the
+        context's device with device=True)."""
+        self._alive()
+        if count is None:
+            n = C.c_uint64()
+            self.lib.pcv_xray_nodes(self.handle, C.byref(n), 0, None, None)
+            count = n.value - int(first)
+        count, W = int(count), self.tile_size_px
+        if device:
+            import torch
+            out = torch.empty((max(count, 0), W, W, 4), dtype=torch.uint8, device=f"cuda:{self.ctx.device}")
+            ptr, cap, mem = out.data_ptr(), out.numel(), L.MEM_DEVICE
+        else:
+            out = np.zeros((max(count, 0), W, W, 4), dtype=np.uint8)
+            ptr, cap, mem = out.ctypes.data, out.nbytes, L.MEM_HOST
+        self.ctx._check(self.lib.pcv_xray_node_images(self.handle, int(first), count, cap, mem, ptr))
+        return out
+
+    def write(self, directory):
+        """build_xray_quadtree's output directory: <node>.png per node and the meta file (pcv_xray_write_dir)."""
+        self._alive()
+        self.ctx._check(self.lib.pcv_xray_write_dir(self.handle, os.fsencode(str(directory))))
+
+    def _alive(self):
+        if not self.handle or not self.ctx.handle:
+            raise L.PcvError(L.PCV_E_INVALID, "the xray tiles were freed")
 
     def free(self):
         if self.handle and self.ctx.handle:
