@@ -1,9 +1,10 @@
-/* build_xray_quadtree.c — xray's build_xray_quadtree over the C ABI in plain C11: an octree directory is opened, the
- * leaf tiles are rasterised on the device (pcv_xray_run), every level above them up to the root node is built on the
- * device (pcv_xray_build_parents), and the quadtree directory the xray viewer loads is written: one <node>.png per node
- * and the meta file (pcv_xray_write_dir). A subset of the reference binary's flags; one octree, no binning.
+/* build_xray_quadtree.c — xray's build_xray_quadtree over the C ABI in plain C11: one or more octree directories (the
+ * reference's point_cloud_locations) are opened, the leaf tiles over all of them are rasterised on the device
+ * (pcv_xray_run_many), every level above them up to the root node is built on the device (pcv_xray_build_parents), and
+ * the quadtree directory the xray viewer loads is written: one <node>.png per node and the meta file
+ * (pcv_xray_write_dir). A subset of the reference binary's flags; no binning.
  *
- *   build_xray_quadtree <octree dir> --output-directory <dir> --resolution <m per px> [--tile-size <px>]
+ *   build_xray_quadtree <octree dir>... --output-directory <dir> --resolution <m per px> [--tile-size <px>]
  *                       [--coloring-strategy xray|colored|colored_with_height_stddev] [--max-stddev <m>]
  *                       [--colormap jet|purplish] [--tile-background-color white|transparent]
  *                       [--filter-interval intensity=<lo>,<hi>] [--root-node-id <r...>]
@@ -16,14 +17,15 @@
 
 static int usage(void) {
   fprintf(stderr,
-          "usage: build_xray_quadtree <octree dir> --output-directory <dir> --resolution <m per px> [--tile-size <px>]\n"
+          "usage: build_xray_quadtree <octree dir>... --output-directory <dir> --resolution <m per px> [--tile-size <px>]\n"
           "       [--coloring-strategy xray|colored|colored_with_height_stddev] [--max-stddev <m>] [--colormap jet|purplish]\n"
           "       [--tile-background-color white|transparent] [--filter-interval intensity=<lo>,<hi>] [--root-node-id <r...>]\n");
   return 2;
 }
 
 int main(int argc, char** argv) {
-  const char* input = NULL;
+  const char** inputs = (const char**)calloc((size_t)argc, sizeof(const char*));
+  uint32_t num_inputs = 0;
   const char* output = NULL;
   const char* root = "r";
   char attribute[16] = "";
@@ -36,8 +38,7 @@ int main(int argc, char** argv) {
     const char* a = argv[i];
     const char* v = i + 1 < argc ? argv[i + 1] : NULL;
     if (a[0] != '-') {
-      if (input) return usage();
-      input = a;
+      inputs[num_inputs++] = a;
       continue;
     }
     if (!v) return usage();
@@ -75,7 +76,7 @@ int main(int argc, char** argv) {
       return usage();
     }
   }
-  if (!input || !output || !(p.pixel_size_m > 0.0)) return usage();
+  if (!inputs || num_inputs == 0 || !output || !(p.pixel_size_m > 0.0)) return usage();
   /* quadtree NodeId from its Display form: "r" and one base-4 digit per level */
   if (root[0] != 'r') return usage();
   for (const char* c = root + 1; *c; ++c) {
@@ -84,11 +85,11 @@ int main(int argc, char** argv) {
     ++p.root_level;
   }
   pcv_ctx* ctx = NULL;
-  pcv_octree* tree = NULL;
+  pcv_octree** trees = (pcv_octree**)calloc(num_inputs, sizeof(pcv_octree*));
   pcv_xray* x = NULL;
-  int rc = pcv_ctx_create(0, NULL, &ctx);
-  if (rc == PCV_OK) rc = pcv_octree_open_dir(ctx, input, &tree);
-  if (rc == PCV_OK) rc = pcv_xray_run(ctx, tree, &p, &x);
+  int rc = trees ? pcv_ctx_create(0, NULL, &ctx) : PCV_E_OOM;
+  for (uint32_t t = 0; t < num_inputs && rc == PCV_OK; ++t) rc = pcv_octree_open_dir(ctx, inputs[t], &trees[t]);
+  if (rc == PCV_OK) rc = pcv_xray_run_many(ctx, trees, num_inputs, &p, &x);
   if (rc == PCV_OK) rc = pcv_xray_build_parents(x);
   if (rc == PCV_OK) rc = pcv_xray_write_dir(x, output);
   if (rc == PCV_OK) {
@@ -102,7 +103,10 @@ int main(int argc, char** argv) {
     fprintf(stderr, "build_xray_quadtree: %s (%d)\n", ctx ? pcv_last_error(ctx) : "no context", rc);
   }
   pcv_xray_free(x);
-  if (tree) pcv_octree_free(tree);
+  for (uint32_t t = 0; trees && t < num_inputs; ++t)
+    if (trees[t]) pcv_octree_free(trees[t]);
+  free(trees);
+  free(inputs);
   if (ctx) pcv_ctx_destroy(ctx);
   return rc == PCV_OK ? 0 : 1;
 }

@@ -646,8 +646,8 @@ void pcv_query_batch_free(pcv_query_batch* b);
 #define PCV_XRAY_BG_WHITE 0      /* TileBackgroundColorArgument (:46-55) */
 #define PCV_XRAY_BG_TRANSPARENT 1
 
-/* XrayParameters (:452-461) + the coloring strategy. Binning, ColoredWithIntensity, several octrees and filters on
- * attributes other than intensity are not offered. */
+/* XrayParameters (:452-461) + the coloring strategy. Binning, ColoredWithIntensity and filters on attributes other than
+ * intensity are not offered; several octrees go through pcv_xray_run_many. */
 typedef struct pcv_xray_params {
   uint32_t tile_size_px;        /* W = H, 1 ..= 32768 */
   uint32_t strategy;            /* PCV_XRAY_XRAY / _COLORED / _HEIGHT_STDDEV */
@@ -684,6 +684,22 @@ int pcv_xray_leaf_tiles(uint32_t tile_size_px, double pixel_size_m, const double
  * max_stddev <= 0, a filter attribute other than "intensity", a filter on an octree without intensity and more than 2^24
  * leaves are PCV_E_INVALID; a tile whose records alone exceed max_workspace_bytes is PCV_E_OOM. */
 int pcv_xray_run(pcv_ctx* ctx, pcv_octree* tree, const pcv_xray_params* params, pcv_xray** out);
+/* pcv_xray_run over several octrees at once, as build_xray_quadtree runs with several point_cloud_locations
+ * (xray/src/build_quadtree.rs:84, :187-196) through one PointCloudClient (point_cloud_client/src/lib.rs). The bounding box
+ * is the union of PointCloudClientBuilder::build (:102-125): the first octree's meta box grown by every octree's min and
+ * then its max in list order (Aabb::grow), each octree included even where it keeps no point; query_from_global then
+ * applies to the union as in pcv_xray_run. Every octree runs the same shape list through pcv_query_batch_run, and a tile
+ * is created iff the sum of kept points over the octrees is > 0 (ParallelIterator::try_for_each_batch takes every cloud's
+ * jobs, src/iterator.rs:262-270). kept and drawn are sums over the octrees; a created tile's image is the strategy over
+ * the union of their kept points: exact for xray and colored, whose colours do not depend on point order, and for
+ * height_stddev within the tolerance of pcv_xray_run. Octrees may differ in resolution and encodings, and one may appear
+ * more than once. All num_trees query batches are alive at once, with the raster workspace; each raster pass is one
+ * launch per tile group whatever num_trees. The result is a pcv_xray like pcv_xray_run's. num_trees == 0 ("No locations
+ * specified"), more than PCV_XRAY_MAX_TREES octrees, a null octree, an octree of another context and an intensity filter
+ * when some octree has no intensity are PCV_E_INVALID with a message, as are pcv_xray_run's own checks; nothing is
+ * allocated then. Out of device memory is PCV_E_OOM with nothing left allocated. */
+#define PCV_XRAY_MAX_TREES 4096
+int pcv_xray_run_many(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t num_trees, const pcv_xray_params* params, pcv_xray** out);
 /* Host only, no context: the parameter checks pcv_xray_run makes before any device work (strategy, colormap,
  * max_stddev, background, filter attribute; tree_has_intensity: whether the octree carries intensity). PCV_E_INVALID
  * with a message in err, or PCV_OK. */

@@ -70,6 +70,7 @@ class XrayParams(C.Structure):
 XRAY_XRAY, XRAY_COLORED, XRAY_HEIGHT_STDDEV = 0, 1, 2
 XRAY_JET, XRAY_PURPLISH = 0, 1
 XRAY_BG_WHITE, XRAY_BG_TRANSPARENT = 0, 1
+XRAY_MAX_TREES = 4096  # PCV_XRAY_MAX_TREES: octrees of one pcv_xray_run_many
 XRAY_FN_XRAY, XRAY_FN_COLORED, XRAY_FN_JET, XRAY_FN_PURPLISH, XRAY_FN_TO_U8 = 0, 1, 2, 3, 4
 REL_IN, REL_CROSS, REL_OUT = 0, 1, 2
 
@@ -234,6 +235,7 @@ _SIGNATURES = {
                                       C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_uint32),
                                       C.POINTER(C.c_uint64), _vp, _vp, _vp, C.c_char_p, C.c_uint64]),
     "pcv_xray_run": (C.c_int, [_vp, _vp, C.POINTER(XrayParams), C.POINTER(_vp)]),
+    "pcv_xray_run_many": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(XrayParams), C.POINTER(_vp)]),
     "pcv_xray_check_params": (C.c_int, [C.POINTER(XrayParams), C.c_int, C.c_char_p, C.c_uint64]),
     "pcv_xray_info": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "pcv_xray_tiles": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),

@@ -1,6 +1,6 @@
 // pcv_xray.hip — xray's build_xray_quadtree (xray/src/generation.rs:557-616) on the device: the leaf level rasterised
-// straight from a batched point query (pcv_query.hip) without materialising its points, then every parent level (second
-// half of the file) and the quadtree directory.
+// straight from batched point queries (pcv_query.hip), one per octree of the run, without materialising their points, then
+// every parent level (second half of the file) and the quadtree directory.
 //
 //   host   leaf geometry   get_bounding_box :550 (Aabb::transform, src/geometry/aabb.rs:58-66),
 //                          find_quadtree_bounding_rect_and_levels :515, Node::from_node_id_and_root_bounding_rect and
@@ -17,7 +17,8 @@
 //                          assign_background_color (:684) and the block's RGBA rows
 //
 // Tiles are processed in groups so that the records of a group fit `max_workspace_bytes`. xray and colored are
-// order-independent (a set union, integer sums), so their bytes do not depend on grouping or scheduling.
+// order-independent (a set union, integer sums), so their bytes do not depend on grouping, scheduling or which octree of
+// a several-octree run (PointCloudClient, point_cloud_client/src/lib.rs:102-125) a point came from.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -107,14 +108,29 @@ struct XrayTileDev {  // discretisation frame of one created tile: its bbox min 
   double min[3];
   double diag[3];
 };
+// The device reads the pointers of XrayTreeChunks as global ones: a pointer read from memory is otherwise generic, every
+// access through it a flat one and the chunk descriptor a vector load
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PCV_GLOBAL __attribute__((address_space(1)))
+#else
+#define PCV_GLOBAL
+#endif
+// one octree's share of a tile group: its query batch's chunks [c0, c0 + n) for the group's shapes sit at [first,
+// first + n) of the group's chunk list, and n is the next entry's first minus this one's (the last: nchunks)
+struct XrayTreeChunks {
+  const PCV_GLOBAL ChunkDesc* desc;
+  const PCV_GLOBAL uint8_t* keep;
+  const PCV_GLOBAL uint8_t* xyz;
+  const PCV_GLOBAL uint8_t* rgb;
+  uint64_t c0;
+  uint64_t first;
+};
 struct XrayBinArgs {
-  const ChunkDesc* desc;
-  const uint8_t* xyz;
-  const uint8_t* rgb;
-  const uint8_t* keep;
-  const int32_t* created_of_shape;  // created-tile index of each shape, -1 where the query kept nothing
+  const XrayTreeChunks* trees;      // the group's octrees with at least one chunk, in list order
+  uint32_t ntrees;
+  uint64_t nchunks;                 // chunks of the group over all its octrees
+  const int32_t* created_of_shape;  // created-tile index of each shape, -1 where no octree's query kept anything
   const XrayTileDev* tiles;         // by created index
-  uint64_t c0, c1;                  // the group's chunks
   uint32_t created0;                // the group's first created tile
   uint32_t W, nbx, nblocks;         // tile edge in pixels, blocks per row, blocks per tile
   uint32_t strategy;
@@ -129,8 +145,8 @@ struct XrayPoint {
   uint64_t rec;  // low 32 bits: pixel in block | z << 10; high 32: r | g << 8 | b << 16
   double z;
 };
-__device__ __forceinline__ XrayPoint xray_point(const XrayBinArgs& a, const ChunkDesc& d, const PointsView& v, const XrayTileDev& t,
-                                                uint32_t bbase, uint32_t q, bool kept) {
+__device__ __forceinline__ XrayPoint xray_point(const XrayBinArgs& a, const uint8_t* rgb, const ChunkDesc& d, const PointsView& v,
+                                                const XrayTileDev& t, uint32_t bbase, uint32_t q, bool kept) {
   XrayPoint o{false, 0u, 0ull, 0.0};
   if (!kept) return o;
   V3d p = load_point(v, q);
@@ -144,7 +160,7 @@ __device__ __forceinline__ XrayPoint xray_point(const XrayBinArgs& a, const Chun
   o.bucket = bbase + (y / kBlk) * a.nbx + x / kBlk;
   uint64_t rec = (uint64_t)((y % kBlk) * kBlk + x % kBlk) | (uint64_t)(z < kZMax ? z : kZMax) << 10;
   if (a.strategy == PCV_XRAY_COLORED) {
-    const uint8_t* c = a.rgb + 3 * (d.attr_index + q);
+    const uint8_t* c = rgb + 3 * (d.attr_index + q);
     rec |= ((uint64_t)c[0] | (uint64_t)c[1] << 8 | (uint64_t)c[2] << 16) << 32;
   }
   o.rec = rec;
@@ -152,29 +168,44 @@ __device__ __forceinline__ XrayPoint xray_point(const XrayBinArgs& a, const Chun
   return o;
 }
 
-// a wave per chunk of the group. COUNT: one counter add per distinct bucket of the 64 points (wave match on the bucket);
-// SCATTER: the same adds reserve each point's slot in its bucket
+// a wave per chunk of the group, whose chunks are those of all its octrees one after another. COUNT: one counter add per
+// distinct bucket of the 64 points (wave match on the bucket); SCATTER: the same adds reserve each point's slot in its
+// bucket. A wave's chunk index only grows, so its octree is found by a wave-uniform search forward from the last one.
 template <bool SCATTER>
 __global__ __launch_bounds__(256) void xray_bin_kernel(XrayBinArgs a, uint32_t* __restrict__ counts, const uint64_t* __restrict__ offsets,
                                                        uint64_t* __restrict__ rec, double* __restrict__ recz) {
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-  for (uint64_t ci = a.c0 + (uint64_t)blockIdx.x * 4 + wave; ci < a.c1; ci += (uint64_t)gridDim.x * 4) {
-    const ChunkDesc d = a.desc[ci];
+  uint32_t k = 0;
+  uint64_t kend = a.ntrees > 1 ? a.trees[1].first : a.nchunks;  // first chunk past octree k
+  for (uint64_t gi = (uint64_t)blockIdx.x * 4 + wave; gi < a.nchunks; gi += (uint64_t)gridDim.x * 4) {
+    if (gi >= kend) {  // the last entry in (k, ntrees) whose first <= gi
+      uint32_t lo = k + 1, hi = a.ntrees - 1;
+      while (lo < hi) {
+        const uint32_t m = (lo + hi + 1) >> 1;
+        if (a.trees[m].first <= gi) lo = m;
+        else hi = m - 1;
+      }
+      k = (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
+      kend = k + 1 < a.ntrees ? a.trees[k + 1].first : a.nchunks;
+    }
+    const XrayTreeChunks tr = a.trees[k];
+    const ChunkDesc d = tr.desc[tr.c0 + (gi - tr.first)];
     const int32_t created = a.created_of_shape[d.enc >> 8];
-    if (created < 0) continue;  // wave-uniform: this tile's query kept nothing
+    if (created < 0) continue;  // wave-uniform: no octree's query kept anything for this tile
     const XrayTileDev t = a.tiles[created];
     const uint32_t bbase = ((uint32_t)created - a.created0) * a.nblocks;
     PointsView v{};
-    v.encoded = a.xyz + d.src;
+    v.encoded = (const uint8_t*)(tr.xyz + d.src);
     v.enc = d.enc & 15u;
     v.cube_min[0] = d.cube_min[0];
     v.cube_min[1] = d.cube_min[1];
     v.cube_min[2] = d.cube_min[2];
     v.cube_edge = d.cube_edge;
-    const uint8_t* kp = a.keep + d.keep_off;
+    const PCV_GLOBAL uint8_t* kp = tr.keep + d.keep_off;
+    const uint8_t* rgb = (const uint8_t*)tr.rgb;
     for (uint32_t q0 = 0; q0 < d.cnt; q0 += 64) {
       const uint32_t q = q0 + lane;
-      const XrayPoint pt = xray_point(a, d, v, t, bbase, q, q < d.cnt && kp[q]);
+      const XrayPoint pt = xray_point(a, rgb, d, v, t, bbase, q, q < d.cnt && kp[q]);
       unsigned long long live = __ballot(pt.draw);
       while (live) {
         const int leader = __ffsll(live) - 1;
@@ -553,10 +584,29 @@ extern "C" void pcv_xray_free(pcv_xray* x) {
   delete x;
 }
 
-static int xray_run(pcv_ctx* ctx, pcv_octree* tree, const pcv_xray_params* p, pcv_xray* x) {
+// PointCloudClientBuilder::build's bounding box (point_cloud_client/src/lib.rs:101-125): the first octree's meta box, grown
+// by every octree's min and then its max in list order (Aabb::grow, aabb.rs:41-44: Point3::inf / sup per component)
+static void union_box(pcv_octree* const* trees, uint32_t K, double lo[3], double hi[3]) {
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = trees[0]->bbox_min[a];
+    hi[a] = trees[0]->bbox_max[a];
+  }
+  for (uint32_t t = 0; t < K; ++t)
+    for (const double* q : {trees[t]->bbox_min, trees[t]->bbox_max})
+      for (int a = 0; a < 3; ++a) {
+        lo[a] = q[a] < lo[a] ? q[a] : lo[a];
+        hi[a] = q[a] > hi[a] ? q[a] : hi[a];
+      }
+}
+
+// the leaf level over K octrees (K = 1: pcv_xray_run): one shape list, one query batch per octree, every raster pass one
+// launch per tile group over the chunks of all K batches
+static int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pcv_xray_params* p, pcv_xray* x) {
   const bool filter = p->interval_attribute != nullptr;
   char err[256] = {0};
-  int rc = leaf_geometry(p->tile_size_px, p->pixel_size_m, tree->bbox_min, tree->bbox_max, p->has_query_from_global ? p->query_from_global : nullptr,
+  double bmin[3], bmax[3];
+  union_box(trees, K, bmin, bmax);
+  int rc = leaf_geometry(p->tile_size_px, p->pixel_size_m, bmin, bmax, p->has_query_from_global ? p->query_from_global : nullptr,
                          p->root_level, p->root_index, true, &x->geo, err, sizeof(err));
   if (rc) return ctx->fail(rc, err);
   const LeafGeometry& g = x->geo;
@@ -591,18 +641,29 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* tree, const pcv_xray_params* p, pc
   }
   pcv_shapes* sh = nullptr;
   if ((rc = pcv_shapes_create(ctx, shapes.data(), S, &sh))) return rc;
-  pcv_query_batch* b = nullptr;
-  rc = pcv_query_batch_run(ctx, sh, tree, filter ? ivals.data() : nullptr, nullptr, &b);
+  // the same shapes through every octree (try_for_each_batch's jobs, src/iterator.rs:262-270); all K batches stay alive
+  // until the raster passes are done
+  struct BatchGuard {
+    std::vector<pcv_query_batch*> b;
+    ~BatchGuard() {
+      for (pcv_query_batch* q : b) pcv_query_batch_free(q);
+    }
+  } guard;
+  guard.b.reserve(K);
+  for (uint32_t t = 0; t < K && rc == PCV_OK; ++t) {
+    pcv_query_batch* b = nullptr;
+    rc = pcv_query_batch_run(ctx, sh, trees[t], filter ? ivals.data() : nullptr, nullptr, &b);
+    if (rc == PCV_OK) guard.b.push_back(b);
+  }
   pcv_shapes_free(sh);
   if (rc) return rc;
-  struct BatchGuard {
-    pcv_query_batch* b;
-    ~BatchGuard() { pcv_query_batch_free(b); }
-  } guard{b};
-  // a tile is created iff its query kept a point (PointStream::callback never delivers an empty batch, iterator.rs:148-151)
+  const std::vector<pcv_query_batch*>& batches = guard.b;
+  // a tile is created iff the queries kept a point (PointStream::callback never delivers an empty batch,
+  // iterator.rs:148-151); kept is the sum over the octrees
   std::vector<int32_t> created_of_shape(S, -1);
   for (uint32_t s = 0; s < S; ++s) {
-    const uint64_t k = b->seg_off[b->shape_first[s + 1]] - b->seg_off[b->shape_first[s]];
+    uint64_t k = 0;
+    for (const pcv_query_batch* b : batches) k += b->seg_off[b->shape_first[s + 1]] - b->seg_off[b->shape_first[s]];
     if (k == 0) continue;
     created_of_shape[s] = (int32_t)x->created.size();
     x->created.push_back(s);
@@ -644,17 +705,43 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* tree, const pcv_xray_params* p, pc
     max_tiles = std::max<uint64_t>(max_tiles, c + 1 - group_first.back());
   }
   group_first.push_back(nc);
+  // per group, the octrees that have chunks for its shapes, in list order, their chunk ranges end to end (u64 prefix)
+  std::vector<XrayTreeChunks> h_trees;
+  std::vector<size_t> tree_first(1, 0);
+  std::vector<uint64_t> group_chunks;
+  for (size_t gi = 0; gi + 1 < group_first.size(); ++gi) {
+    const uint64_t s0 = x->created[group_first[gi]], s1 = x->created[group_first[gi + 1] - 1] + 1;
+    uint64_t n = 0;
+    for (uint32_t t = 0; t < K; ++t) {
+      const pcv_query_batch* b = batches[t];
+      const uint64_t c0 = b->seg_chunk[b->shape_first[s0]], c1 = b->seg_chunk[b->shape_first[s1]];
+      if (c1 == c0) continue;
+      XrayTreeChunks e{};
+      e.desc = (decltype(e.desc))b->d_desc;
+      e.keep = (decltype(e.keep))b->d_keep;
+      e.xyz = (decltype(e.xyz))trees[t]->d_xyz;
+      e.rgb = (decltype(e.rgb))trees[t]->d_rgb;
+      e.c0 = c0;
+      e.first = n;
+      h_trees.push_back(e);
+      n += c1 - c0;
+    }
+    tree_first.push_back(h_trees.size());
+    group_chunks.push_back(n);
+  }
   PcvScratch sc(ctx);
   int32_t* d_cos;
   XrayTileDev* d_tiles;
+  XrayTreeChunks* d_trees;
   uint8_t* d_table;
   unsigned long long* d_drawn;
   uint32_t* d_counts;
   uint64_t *d_off, *d_rec;
   double* d_recz = nullptr;
   const uint64_t max_buckets = max_tiles * nblocks;
-  if ((rc = sc.get(&d_cos, S)) || (rc = sc.get(&d_tiles, nc)) || (rc = sc.get(&d_table, kZWords * 32 + 1)) || (rc = sc.get(&d_drawn, nc)) ||
-      (rc = sc.get(&d_counts, max_buckets)) || (rc = sc.get(&d_off, max_buckets + 1)) || (rc = sc.get(&d_rec, std::max<uint64_t>(max_pts, 1))))
+  if ((rc = sc.get(&d_cos, S)) || (rc = sc.get(&d_tiles, nc)) || (rc = sc.get(&d_trees, std::max<size_t>(h_trees.size(), 1))) ||
+      (rc = sc.get(&d_table, kZWords * 32 + 1)) || (rc = sc.get(&d_drawn, nc)) || (rc = sc.get(&d_counts, max_buckets)) ||
+      (rc = sc.get(&d_off, max_buckets + 1)) || (rc = sc.get(&d_rec, std::max<uint64_t>(max_pts, 1))))
     return rc;
   if (p->strategy == PCV_XRAY_HEIGHT_STDDEV && (rc = sc.get(&d_recz, std::max<uint64_t>(max_pts, 1)))) return rc;
   std::vector<XrayTileDev> h_tiles(nc);
@@ -670,13 +757,11 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* tree, const pcv_xray_params* p, pc
   xray_value_table(table);
   PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_cos, created_of_shape.data(), 4 * (size_t)S, hipMemcpyHostToDevice, ctx->stream));
   PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_tiles, h_tiles.data(), sizeof(XrayTileDev) * nc, hipMemcpyHostToDevice, ctx->stream));
+  if (!h_trees.empty())
+    PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_trees, h_trees.data(), sizeof(XrayTreeChunks) * h_trees.size(), hipMemcpyHostToDevice, ctx->stream));
   PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_table, table, sizeof(table), hipMemcpyHostToDevice, ctx->stream));
   PCV_HIP_CHECK(ctx, hipMemsetAsync(d_drawn, 0, 8 * nc, ctx->stream));
   XrayBinArgs ba{};
-  ba.desc = (const ChunkDesc*)b->d_desc;
-  ba.xyz = tree->d_xyz;
-  ba.rgb = tree->d_rgb;
-  ba.keep = b->d_keep;
   ba.created_of_shape = d_cos;
   ba.tiles = d_tiles;
   ba.W = W;
@@ -711,13 +796,13 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* tree, const pcv_xray_params* p, pc
   if (const char* e = pcv_experiment("PCV_XRAY_ACCUM_GRID")) accum_grid = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
   for (size_t gi = 0; gi + 1 < group_first.size(); ++gi) {
     const uint64_t f = group_first[gi], l = group_first[gi + 1];  // created tiles [f, l)
-    const uint64_t s0 = x->created[f], s1 = x->created[l - 1] + 1;
-    ba.c0 = b->seg_chunk[b->shape_first[s0]];
-    ba.c1 = b->seg_chunk[b->shape_first[s1]];
+    ba.trees = d_trees + tree_first[gi];
+    ba.ntrees = (uint32_t)(tree_first[gi + 1] - tree_first[gi]);
+    ba.nchunks = group_chunks[gi];
     ba.created0 = (uint32_t)f;
     aa.created0 = (uint32_t)f;
     const uint64_t nb = (l - f) * nblocks;
-    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((ba.c1 - ba.c0 + 3) / 4, 1u << 16));
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((ba.nchunks + 3) / 4, 1u << 16));
     PCV_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, 4 * nb, ctx->stream));
     {
       PcvProf prof(ctx, PCV_K_XRAY_BIN);
@@ -750,7 +835,23 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* tree, const pcv_xray_params* p, pc
     PCV_HIP_CHECK(ctx, hipGetLastError());
   }
   PCV_HIP_CHECK(ctx, hipMemcpyAsync(x->drawn.data(), d_drawn, 8 * nc, hipMemcpyDeviceToHost, ctx->stream));
-  PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // the scratch and the batch are released on return
+  PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // the scratch and the batches are released on return
+  return PCV_OK;
+}
+
+// the object of a checked run, or nothing (a failed run frees what it allocated)
+static int xray_new(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pcv_xray_params* p, pcv_xray** out) {
+  pcv_xray* x = new pcv_xray();
+  x->ctx = ctx;
+  const int rc = xray_run(ctx, trees, K, p, x);
+  if (rc != PCV_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipGetLastError();
+    pcv_xray_free(x);
+    return rc;
+  }
+  ctx->prof_resolve();
+  *out = x;
   return PCV_OK;
 }
 
@@ -777,18 +878,30 @@ extern "C" int pcv_xray_run(pcv_ctx* ctx, pcv_octree* tree, const pcv_xray_param
   char err[256] = {0};
   const int vrc = pcv_xray_check_params(p, tree->has_intensity ? 1 : 0, err, sizeof(err));
   if (vrc) return ctx->fail(vrc, err);
-  pcv_xray* x = new pcv_xray();
-  x->ctx = ctx;
-  const int rc = xray_run(ctx, tree, p, x);
-  if (rc != PCV_OK) {
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipGetLastError();
-    pcv_xray_free(x);
-    return rc;
+  return xray_new(ctx, &tree, 1, p, out);
+}
+
+extern "C" int pcv_xray_run_many(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t num_trees, const pcv_xray_params* p, pcv_xray** out) {
+  if (!ctx) return PCV_E_INVALID;
+  if (!p || !out) return ctx->fail(PCV_E_INVALID, "null argument");
+  *out = nullptr;
+  // PointCloudClientBuilder::build (point_cloud_client/src/lib.rs:92-95)
+  if (num_trees == 0) return ctx->fail(PCV_E_INVALID, "xray: No locations specified for point cloud client.");
+  if (!trees) return ctx->fail(PCV_E_INVALID, "null argument");
+  if (num_trees > PCV_XRAY_MAX_TREES)
+    return ctx->fail(PCV_E_INVALID, "xray: " + std::to_string(num_trees) + " octrees, more than PCV_XRAY_MAX_TREES (" +
+                                        std::to_string(PCV_XRAY_MAX_TREES) + ")");
+  char err[256] = {0};
+  int vrc = pcv_xray_check_params(p, 1, err, sizeof(err));
+  if (vrc) return ctx->fail(vrc, err);
+  for (uint32_t t = 0; t < num_trees; ++t) {
+    const std::string which = "xray: octree " + std::to_string(t);
+    if (!trees[t]) return ctx->fail(PCV_E_INVALID, which + " is null");
+    if (trees[t]->ctx != ctx) return ctx->fail(PCV_E_INVALID, which + " belongs to another context");
+    if (p->interval_attribute && !trees[t]->has_intensity)
+      return ctx->fail(PCV_E_INVALID, which + " has no intensity attribute to filter on");
   }
-  ctx->prof_resolve();
-  *out = x;
-  return PCV_OK;
+  return xray_new(ctx, trees, num_trees, p, out);
 }
 
 extern "C" int pcv_xray_info(const pcv_xray* x, uint32_t* deepest_level, double rect[3], uint64_t* num_leaves, uint64_t* num_created) {

@@ -272,6 +272,29 @@ class Context:
         self._check(self.lib.pcv_octree_open_dir(self.handle, str(directory).encode(), C.byref(h)))
         return OctreeResult(self, h)
 
+    def xray_tiles(self, trees, tile_size_px=256, pixel_size_m=None, strategy="xray", query_from_global=None, intensity_interval=None,
+                   background="white", root_node_id="r", max_workspace_bytes=None):
+        """OctreeResult.xray_tiles (same keywords) over several octrees of this context, as build_xray_quadtree with several
+        point_cloud_locations (pcv_xray_run_many): the union of their bounding boxes, every tile's points from all of them.
+        Returns an XrayTiles."""
+        trees = list(trees)
+        if not trees:
+            raise ValueError("xray_tiles: no octrees given")
+        p = xray_params(tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background, root_node_id,
+                        max_workspace_bytes)
+        arr = (C.c_void_p * len(trees))(*[t.handle for t in trees])
+        h = C.c_void_p()
+        self._check(self.lib.pcv_xray_run_many(self.handle, arr, len(trees), C.byref(p), C.byref(h)))
+        return XrayTiles(self, h, int(tile_size_px))
+
+    def xray_quadtree(self, trees, tile_size_px=256, pixel_size_m=None, strategy="xray", query_from_global=None,
+                      intensity_interval=None, background="white", root_node_id="r", max_workspace_bytes=None):
+        """xray_tiles over several octrees (same arguments) with every level above the leaves built on the device."""
+        xt = self.xray_tiles(trees, tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background,
+                             root_node_id, max_workspace_bytes)
+        xt.build_parents()
+        return xt
+
     def shapes(self, shapes):
         """Prepare query shapes on the device. Each entry: ("all",), ("aabb", min3, max3), ("frustum", clip_from_query16),
         ("frustum2", clip_from_query16, query_from_clip16), ("obb", translation3, quat_ijkw4, half_extent3)."""
