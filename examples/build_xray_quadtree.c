@@ -1,11 +1,12 @@
 /* build_xray_quadtree.c — xray's build_xray_quadtree over the C ABI in plain C11: one or more octree directories (the
  * reference's point_cloud_locations) are opened, the leaf tiles over all of them are rasterised on the device
- * (pcv_xray_run_many), every level above them up to the root node is built on the device (pcv_xray_build_parents), and
+ * (pcv_xray_run_ex), every level above them up to the root node is built on the device (pcv_xray_build_parents), and
  * the quadtree directory the xray viewer loads is written: one <node>.png per node and the meta file
- * (pcv_xray_write_dir). A subset of the reference binary's flags; no binning.
+ * (pcv_xray_write_dir). A subset of the reference binary's flags.
  *
  *   build_xray_quadtree <octree dir>... --output-directory <dir> --resolution <m per px> [--tile-size <px>]
- *                       [--coloring-strategy xray|colored|colored_with_height_stddev] [--max-stddev <m>]
+ *                       [--coloring-strategy xray|colored|colored_with_intensity|colored_with_height_stddev]
+ *                       [--min-intensity <f>] [--max-intensity <f>] [--binning intensity=<size>] [--max-stddev <m>]
  *                       [--colormap jet|purplish] [--tile-background-color white|transparent]
  *                       [--filter-interval intensity=<lo>,<hi>] [--root-node-id <r...>]
  */
@@ -18,7 +19,8 @@
 static int usage(void) {
   fprintf(stderr,
           "usage: build_xray_quadtree <octree dir>... --output-directory <dir> --resolution <m per px> [--tile-size <px>]\n"
-          "       [--coloring-strategy xray|colored|colored_with_height_stddev] [--max-stddev <m>] [--colormap jet|purplish]\n"
+          "       [--coloring-strategy xray|colored|colored_with_intensity|colored_with_height_stddev] [--min-intensity <f>]\n"
+          "       [--max-intensity <f>] [--binning intensity=<size>] [--max-stddev <m>] [--colormap jet|purplish]\n"
           "       [--tile-background-color white|transparent] [--filter-interval intensity=<lo>,<hi>] [--root-node-id <r...>]\n");
   return 2;
 }
@@ -29,6 +31,11 @@ int main(int argc, char** argv) {
   const char* output = NULL;
   const char* root = "r";
   char attribute[16] = "";
+  char bin_attribute[16] = "";
+  pcv_xray_coloring col;
+  memset(&col, 0, sizeof(col));
+  col.min_intensity = 0.0f; /* the reference's defaults (build_quadtree.rs:49-66) */
+  col.max_intensity = 1.0f;
   pcv_xray_params p;
   memset(&p, 0, sizeof(p));
   p.tile_size_px = 256;
@@ -52,8 +59,20 @@ int main(int argc, char** argv) {
     } else if (!strcmp(a, "--coloring-strategy")) {
       if (!strcmp(v, "xray")) p.strategy = PCV_XRAY_XRAY;
       else if (!strcmp(v, "colored")) p.strategy = PCV_XRAY_COLORED;
+      else if (!strcmp(v, "colored_with_intensity")) p.strategy = PCV_XRAY_COLORED_WITH_INTENSITY;
       else if (!strcmp(v, "colored_with_height_stddev")) p.strategy = PCV_XRAY_HEIGHT_STDDEV;
       else return usage();
+    } else if (!strcmp(a, "--min-intensity")) {
+      col.min_intensity = strtof(v, NULL);
+    } else if (!strcmp(a, "--max-intensity")) {
+      col.max_intensity = strtof(v, NULL);
+    } else if (!strcmp(a, "--binning")) {
+      const char* eq = strchr(v, '=');
+      if (!eq || (size_t)(eq - v) >= sizeof(bin_attribute)) return usage();
+      memcpy(bin_attribute, v, (size_t)(eq - v));
+      bin_attribute[eq - v] = '\0';
+      col.binning_attribute = bin_attribute;
+      col.bin_size = strtod(eq + 1, NULL);
     } else if (!strcmp(a, "--max-stddev")) {
       p.max_stddev = strtof(v, NULL);
     } else if (!strcmp(a, "--colormap")) {
@@ -89,7 +108,7 @@ int main(int argc, char** argv) {
   pcv_xray* x = NULL;
   int rc = trees ? pcv_ctx_create(0, NULL, &ctx) : PCV_E_OOM;
   for (uint32_t t = 0; t < num_inputs && rc == PCV_OK; ++t) rc = pcv_octree_open_dir(ctx, inputs[t], &trees[t]);
-  if (rc == PCV_OK) rc = pcv_xray_run_many(ctx, trees, num_inputs, &p, &x);
+  if (rc == PCV_OK) rc = pcv_xray_run_ex(ctx, trees, num_inputs, &p, &col, &x);
   if (rc == PCV_OK) rc = pcv_xray_build_parents(x);
   if (rc == PCV_OK) rc = pcv_xray_write_dir(x, output);
   if (rc == PCV_OK) {

@@ -641,16 +641,18 @@ void pcv_query_batch_free(pcv_query_batch* b);
 #define PCV_XRAY_XRAY 0          /* XRayColoringStrategy (:159-199): distinct z buckets per pixel */
 #define PCV_XRAY_COLORED 1       /* PointColorColoringStrategy without binning (:294-345) */
 #define PCV_XRAY_HEIGHT_STDDEV 2 /* HeightStddevColoringStrategy (:365-408) */
+#define PCV_XRAY_COLORED_WITH_INTENSITY 3 /* IntensityColoringStrategy (:210-292): only through pcv_xray_run_ex */
 #define PCV_XRAY_JET 0           /* colormap.rs Jet */
 #define PCV_XRAY_PURPLISH 1      /* colormap.rs Monochrome(PURPLISH) */
 #define PCV_XRAY_BG_WHITE 0      /* TileBackgroundColorArgument (:46-55) */
 #define PCV_XRAY_BG_TRANSPARENT 1
 
-/* XrayParameters (:452-461) + the coloring strategy. Binning, ColoredWithIntensity and filters on attributes other than
- * intensity are not offered; several octrees go through pcv_xray_run_many. */
+/* XrayParameters (:452-461) + the coloring strategy. ColoredWithIntensity and binning take the extra pcv_xray_coloring of
+ * pcv_xray_run_ex; filters on attributes other than intensity are not offered; several octrees go through
+ * pcv_xray_run_many or pcv_xray_run_ex. */
 typedef struct pcv_xray_params {
   uint32_t tile_size_px;        /* W = H, 1 ..= 32768 */
-  uint32_t strategy;            /* PCV_XRAY_XRAY / _COLORED / _HEIGHT_STDDEV */
+  uint32_t strategy;            /* PCV_XRAY_XRAY / _COLORED / _HEIGHT_STDDEV / _COLORED_WITH_INTENSITY (pcv_xray_run_ex only) */
   uint32_t colormap;            /* height_stddev: PCV_XRAY_JET / PCV_XRAY_PURPLISH */
   uint32_t background;          /* PCV_XRAY_BG_WHITE / PCV_XRAY_BG_TRANSPARENT: assign_background_color (:684) */
   double pixel_size_m;
@@ -704,6 +706,52 @@ int pcv_xray_run_many(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t num_trees
  * max_stddev, background, filter attribute; tree_has_intensity: whether the octree carries intensity). PCV_E_INVALID
  * with a message in err, or PCV_OK. */
 int pcv_xray_check_params(const pcv_xray_params* params, int tree_has_intensity, char* err, uint64_t errcap);
+/* What the reference's --coloring-strategy colored_with_intensity and --binning <attr>=<size> add
+ * (xray/src/build_quadtree.rs:44-106, :141-158):
+ *   min_intensity, max_intensity  IntensityColoringStrategy's min / max: read by PCV_XRAY_COLORED_WITH_INTENSITY only, any
+ *                                 f32 (NaN and min > max included: the colour follows Rust's f32 rules, see
+ *                                 PCV_XRAY_FN_INTENSITY);
+ *   binning_attribute, bin_size   NULL: no binning; "intensity": bin = (intensity as f64 / bin_size) as i64 (Rust `as`:
+ *                                 truncating, saturating, NaN -> 0; bin_size is not validated), generation.rs:138-157.
+ *                                 Only "intensity" can be binned on ("color" is a U8Vec3, on which the reference panics,
+ *                                 src/attributes.rs:128). Binning applies to PCV_XRAY_COLORED (per pixel: the mean over
+ *                                 bins, in ascending bin order, of each bin's mean colour, :294-362) and
+ *                                 PCV_XRAY_COLORED_WITH_INTENSITY (the mean over bins of each bin's mean intensity,
+ *                                 :210-292); xray and height_stddev never read it (attributes() :133) and their bytes do
+ *                                 not change.
+ * Both strategies, binned or not, reduce each (pixel, bin) in a fixed key order, so their images do not depend on
+ * scheduling, tile grouping or octree order. */
+typedef struct pcv_xray_coloring {
+  float min_intensity, max_intensity;
+  const char* binning_attribute;
+  double bin_size;
+} pcv_xray_coloring;
+/* pcv_xray_run_many with a coloring (nullable: then exactly pcv_xray_run_many). Every octree must carry intensity when
+ * the strategy is colored_with_intensity or binning applies. IntensityColoringStrategy stops processing a PointsBatch
+ * at its first intensity < 0 (generation.rs:248), and the reference's batch boundaries depend on thread scheduling, so a
+ * tile that keeps a negative intensity has no defined reference image: here such a tile is drawn from its points with
+ * intensity >= 0 (NaN included, as NaN < 0 is false); the negative points are neither drawn nor counted in drawn, and
+ * pcv_xray_negative reports how many there were. */
+int pcv_xray_run_ex(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t num_trees, const pcv_xray_params* params,
+                    const pcv_xray_coloring* coloring, pcv_xray** out);
+/* pcv_xray_check_params with a coloring (nullable): strategy colored_with_intensity needs one; a binning attribute other
+ * than "intensity" is PCV_E_INVALID for every strategy; binning with colored / colored_with_intensity and
+ * colored_with_intensity itself need tree_has_intensity. pcv_xray_run, pcv_xray_run_many and pcv_xray_check_params
+ * refuse colored_with_intensity (it needs the coloring of the _ex entry points). */
+int pcv_xray_check_params_ex(const pcv_xray_params* params, const pcv_xray_coloring* coloring, int tree_has_intensity, char* err,
+                             uint64_t errcap);
+/* Per created tile: the kept points with intensity < 0 (colored_with_intensity only; 0 elsewhere), counted over every kept
+ * point of the tile, inside its image or not (:108-127). num_created entries. */
+int pcv_xray_negative(const pcv_xray* x, uint64_t* negative);
+/* Host only, no context: the tile groups a run makes for created tiles that keep kept[0 .. num_tiles) points, with
+ * these params (tile_size_px, strategy, max_workspace_bytes) and coloring (nullable). Consecutive tiles whose records and
+ * bucket tables fit max_workspace_bytes form a group; *num_groups is their count and the first `capacity` entries of
+ * group_first (nullable) their first tiles. A tile whose records alone exceed the workspace is PCV_E_OOM. A tile of
+ * colored_with_intensity or binned colored that keeps more than PCV_XRAY_MAX_SORTED_TILE_POINTS points is PCV_E_INVALID:
+ * its one-workgroup sort has u32 indices. The same checks refuse such a run. Message in err. */
+#define PCV_XRAY_MAX_SORTED_TILE_POINTS 1073741824ull
+int pcv_xray_plan_groups(const uint64_t* kept, uint64_t num_tiles, const pcv_xray_params* params, const pcv_xray_coloring* coloring,
+                         uint64_t capacity, uint64_t* num_groups, uint64_t* group_first, char* err, uint64_t errcap);
 int pcv_xray_info(const pcv_xray* x, uint32_t* deepest_level, double rect[3], uint64_t* num_leaves, uint64_t* num_created);
 /* Host arrays, each nullable: leaf_index (num_leaves: the leaf list), created (num_created: positions in the leaf list, in
  * leaf order), kept (points the tile's query kept) and drawn (points that landed inside the image). */
@@ -721,6 +769,10 @@ void pcv_xray_free(pcv_xray* x);
 #define PCV_XRAY_FN_JET 2
 #define PCV_XRAY_FN_PURPLISH 3
 #define PCV_XRAY_FN_TO_U8 4
+/* _INTENSITY: in[3i..3i+2] = mean, min, max (each as f32): IntensityColoringStrategy::get_pixel_color after the mean
+ * (:270-284): mean.max(min).min(max) with Rust's NaN rules, then ln(mean - min) / ln(max - min) in f32, through the
+ * kernel's own ln (an f64 series rounded to f32 once, no libm), as Color{b, b, b, 1}.to_u8(). */
+#define PCV_XRAY_FN_INTENSITY 5
 int pcv_xray_finalize(int fn, uint64_t count, const double* in, uint8_t* rgba);
 
 /* ---- xray parent levels and the quadtree directory (create_non_leaf_nodes :656-682, build_node :726-759) -------------

@@ -8,7 +8,7 @@ from ._lib import (PCV_E_DEPTH, PCV_E_HIP, PCV_E_INVALID, PCV_E_IO, PCV_E_NOT_FO
                    PcvError, load_library)
 from .octree import (Aabb, Context, OctreeResult, QueryBatch, Shapes, XrayTiles, build_octree, build_octree_from_file,  # noqa: F401
                      level_shortcuts, level_table, node_name, quadtree_node_id, quadtree_node_name, read_ply, xray_check_params,
-                     xray_finalize, xray_lanczos_taps, xray_leaf_tiles, xray_params, xray_png_encode)
+                     xray_coloring, xray_finalize, xray_lanczos_taps, xray_leaf_tiles, xray_params, xray_png_encode)
 
 __all__ = ["Aabb", "Context", "OctreeResult", "QueryBatch", "XrayTiles", "build_octree", "level_table", "node_name", "PcvError",
            "load_library"]

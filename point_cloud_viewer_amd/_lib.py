@@ -67,11 +67,16 @@ class XrayParams(C.Structure):
                 ("interval_attribute", C.c_char_p), ("interval", C.c_double * 2), ("max_workspace_bytes", C.c_uint64)]
 
 
-XRAY_XRAY, XRAY_COLORED, XRAY_HEIGHT_STDDEV = 0, 1, 2
+class XrayColoring(C.Structure):
+    _fields_ = [("min_intensity", C.c_float), ("max_intensity", C.c_float), ("binning_attribute", C.c_char_p),
+                ("bin_size", C.c_double)]
+
+
+XRAY_XRAY, XRAY_COLORED, XRAY_HEIGHT_STDDEV, XRAY_COLORED_WITH_INTENSITY = 0, 1, 2, 3
 XRAY_JET, XRAY_PURPLISH = 0, 1
 XRAY_BG_WHITE, XRAY_BG_TRANSPARENT = 0, 1
 XRAY_MAX_TREES = 4096  # PCV_XRAY_MAX_TREES: octrees of one pcv_xray_run_many
-XRAY_FN_XRAY, XRAY_FN_COLORED, XRAY_FN_JET, XRAY_FN_PURPLISH, XRAY_FN_TO_U8 = 0, 1, 2, 3, 4
+XRAY_FN_XRAY, XRAY_FN_COLORED, XRAY_FN_JET, XRAY_FN_PURPLISH, XRAY_FN_TO_U8, XRAY_FN_INTENSITY = 0, 1, 2, 3, 4, 5
 REL_IN, REL_CROSS, REL_OUT = 0, 1, 2
 
 
@@ -237,6 +242,11 @@ _SIGNATURES = {
     "pcv_xray_run": (C.c_int, [_vp, _vp, C.POINTER(XrayParams), C.POINTER(_vp)]),
     "pcv_xray_run_many": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(XrayParams), C.POINTER(_vp)]),
     "pcv_xray_check_params": (C.c_int, [C.POINTER(XrayParams), C.c_int, C.c_char_p, C.c_uint64]),
+    "pcv_xray_run_ex": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(XrayParams), C.POINTER(XrayColoring), C.POINTER(_vp)]),
+    "pcv_xray_check_params_ex": (C.c_int, [C.POINTER(XrayParams), C.POINTER(XrayColoring), C.c_int, C.c_char_p, C.c_uint64]),
+    "pcv_xray_negative": (C.c_int, [_vp, _vp]),
+    "pcv_xray_plan_groups": (C.c_int, [_vp, C.c_uint64, C.POINTER(XrayParams), C.POINTER(XrayColoring), C.c_uint64,
+                                       C.POINTER(C.c_uint64), _vp, C.c_char_p, C.c_uint64]),
     "pcv_xray_info": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "pcv_xray_tiles": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "pcv_xray_images": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _vp]),

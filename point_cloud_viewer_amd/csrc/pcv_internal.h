@@ -130,6 +130,7 @@ enum PcvKernelId {
   PCV_K_XRAY_SCATTER,         // pcv_xray_run: one record per drawable point into its bucket
   PCV_K_XRAY_ACCUM,           // pcv_xray_run: per-pixel state in LDS, colour, background, RGBA rows
   PCV_K_XRAY_PARENT,          // pcv_xray_build_parents: one quadtree level of parents from their children (2:1 Lanczos3)
+  PCV_K_XRAY_SORTED,          // pcv_xray_run_ex: colored_with_intensity / binned colored, the bucket sorted, then per pixel
   PCV_K_COUNT
 };
 

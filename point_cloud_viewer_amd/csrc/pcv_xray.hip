@@ -15,10 +15,14 @@
 //   K_xa   xray_accum      one workgroup per bucket: per-pixel state in LDS (run-aggregated atomics), then the strategy's
 //                          colour (:159-199, :294-345, :365-408, colormap.rs, src/color.rs:29-36), the background of
 //                          assign_background_color (:684) and the block's RGBA rows
+//   K_xo   xray_sorted     instead of K_xa for colored_with_intensity and binned colored: the bucket sorted by (pixel, bin,
+//                          record) in LDS or, above the LDS limit, in place in the workspace; then per pixel the bin means
+//                          in ascending bin order (:138-157, :210-292, :294-362)
 //
 // Tiles are processed in groups so that the records of a group fit `max_workspace_bytes`. xray and colored are
-// order-independent (a set union, integer sums), so their bytes do not depend on grouping, scheduling or which octree of
-// a several-octree run (PointCloudClient, point_cloud_client/src/lib.rs:102-125) a point came from.
+// order-independent (a set union, integer sums), and xray_sorted reduces in key order, so their bytes do not depend on
+// grouping, scheduling or which octree of a several-octree run (PointCloudClient, point_cloud_client/src/lib.rs:102-125)
+// a point came from.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -96,6 +100,47 @@ __host__ __device__ inline uint32_t pack(Rgba8 c) { return (uint32_t)c.r | (uint
 // assign_background_color (:684-708): alpha < 128 -> the background colour
 __host__ __device__ inline uint32_t with_background(Rgba8 c, uint32_t bg) { return c.a < 128 ? bg : pack(c); }
 
+// f32 ln shared by the kernel and pcv_xray_finalize: x = m 2^e with m in [sqrt(1/2), sqrt(2)), ln m = 2 atanh(s) with
+// s = (m - 1) / (m + 1) as an odd series to s^17 in f64, e ln 2 + ln m rounded to f32 once. Plain f64 arithmetic (no libm,
+// no contraction), so host and device agree bit for bit; within an ulp of libm's logf. ln 1 = 0 exactly.
+__host__ __device__ inline float ln_f32(float x) {
+  if (x != x) return x;
+  if (x < 0.0f) return __builtin_nanf("");
+  if (x == 0.0f) return -__builtin_inff();
+  if (x == __builtin_inff()) return x;
+  double m = (double)x;
+  uint64_t bits;
+  memcpy(&bits, &m, 8);
+  int e = (int)((bits >> 52) & 0x7ffu) - 1023;
+  bits = (bits & 0x000fffffffffffffull) | 0x3ff0000000000000ull;
+  memcpy(&m, &bits, 8);
+  if (m > 1.4142135623730951) {
+    m = m * 0.5;
+    e = e + 1;
+  }
+  const double s = (m - 1.0) / (m + 1.0), s2 = s * s;
+  const double poly =
+      s2 * (1.0 / 3.0 + s2 * (1.0 / 5.0 + s2 * (1.0 / 7.0 + s2 * (1.0 / 9.0 + s2 * (1.0 / 11.0 + s2 * (1.0 / 13.0 + s2 * (1.0 / 15.0 + s2 * (1.0 / 17.0))))))));
+  const double lnm = 2.0 * s + 2.0 * s * poly;
+  return (float)((double)e * 0.6931471805599453 + lnm);
+}
+// Rust's f32::max / f32::min: a NaN operand yields the other one
+__host__ __device__ inline float rust_max(float a, float b) { return a != a ? b : (b != b ? a : (a > b ? a : b)); }
+__host__ __device__ inline float rust_min(float a, float b) { return a != a ? b : (b != b ? a : (a < b ? a : b)); }
+// IntensityColoringStrategy::get_pixel_color after the mean (:270-284)
+__host__ __device__ inline Rgba8 intensity_color(float mean, float lo, float hi) {
+  const float m = rust_min(rust_max(mean, lo), hi);
+  const float b = ln_f32(m - lo) / ln_f32(hi - lo);
+  return to_u8(b, b, b, 1.0f);
+}
+// Rust `f64 as i64`: truncation, saturating; NaN -> 0 (the bin of generation.rs:150)
+__host__ __device__ inline int64_t rust_i64(double v) {
+  if (v != v) return 0;
+  if (v >= 9223372036854775808.0) return INT64_MAX;
+  if (v < -9223372036854775808.0) return INT64_MIN;
+  return (int64_t)v;
+}
+
 // Rust `f64 as u32`: truncation, saturating; NaN -> 0
 __device__ __forceinline__ uint32_t sat_u32(double v) {
   if (!(v > 0.0)) return 0;
@@ -122,6 +167,7 @@ struct XrayTreeChunks {
   const PCV_GLOBAL uint8_t* keep;
   const PCV_GLOBAL uint8_t* xyz;
   const PCV_GLOBAL uint8_t* rgb;
+  const PCV_GLOBAL uint8_t* inten;  // f32 per point; set only when the strategy or the binning reads intensity
   uint64_t c0;
   uint64_t first;
 };
@@ -136,19 +182,34 @@ struct XrayBinArgs {
   uint32_t strategy;
   int32_t has_iso;
   double iso[7];                    // query_from_global: translation xyz, quaternion ijkw
+  int32_t binned;                   // colored / colored_with_intensity with binning on intensity
+  double bin_size;
+  unsigned long long* negative;     // colored_with_intensity: kept points with intensity < 0 per created tile (count pass)
 };
 
-// per 64 points of a chunk: is the point drawn, its bucket (tile in group x block), its record and (stddev) its z
+// per 64 points of a chunk: is the point drawn, its bucket (tile in group x block), its record, (stddev) its z, (binning)
+// its bin and (colored_with_intensity) whether its intensity is < 0
 struct XrayPoint {
-  bool draw;
+  bool draw, neg;
   uint32_t bucket;
-  uint64_t rec;  // low 32 bits: pixel in block | z << 10; high 32: r | g << 8 | b << 16
+  uint64_t rec;  // low 32 bits: pixel in block | z << 10; high 32: r | g << 8 | b << 16, or the intensity's f32 bits
   double z;
+  int64_t bin;
 };
-__device__ __forceinline__ XrayPoint xray_point(const XrayBinArgs& a, const uint8_t* rgb, const ChunkDesc& d, const PointsView& v,
-                                                const XrayTileDev& t, uint32_t bbase, uint32_t q, bool kept) {
-  XrayPoint o{false, 0u, 0ull, 0.0};
+__device__ __forceinline__ XrayPoint xray_point(const XrayBinArgs& a, const uint8_t* rgb, const float* inten, const ChunkDesc& d,
+                                                const PointsView& v, const XrayTileDev& t, uint32_t bbase, uint32_t q, bool kept) {
+  XrayPoint o{false, false, 0u, 0ull, 0.0, 0};
   if (!kept) return o;
+  float in = 0.0f;
+  if (inten) {
+    in = inten[d.attr_index + q];
+    // the `< 0` check runs on every kept point, inside the image or not (:108-127, :248); such points are not drawn
+    if (a.strategy == PCV_XRAY_COLORED_WITH_INTENSITY && in < 0.0f) {
+      o.neg = true;
+      return o;
+    }
+    if (a.binned) o.bin = rust_i64((double)in / a.bin_size);  // BinnedColoringStrategy::bins (:138-157)
+  }
   V3d p = load_point(v, q);
   if (a.has_iso) p = v_add(quat_rotate(a.iso + 3, p), V3d{a.iso[0], a.iso[1], a.iso[2]});
   const double W = (double)a.W;
@@ -162,6 +223,8 @@ __device__ __forceinline__ XrayPoint xray_point(const XrayBinArgs& a, const uint
   if (a.strategy == PCV_XRAY_COLORED) {
     const uint8_t* c = rgb + 3 * (d.attr_index + q);
     rec |= ((uint64_t)c[0] | (uint64_t)c[1] << 8 | (uint64_t)c[2] << 16) << 32;
+  } else if (a.strategy == PCV_XRAY_COLORED_WITH_INTENSITY) {
+    rec |= (uint64_t)__float_as_uint(in) << 32;
   }
   o.rec = rec;
   o.z = p.z;
@@ -173,7 +236,8 @@ __device__ __forceinline__ XrayPoint xray_point(const XrayBinArgs& a, const uint
 // bucket. A wave's chunk index only grows, so its octree is found by a wave-uniform search forward from the last one.
 template <bool SCATTER>
 __global__ __launch_bounds__(256) void xray_bin_kernel(XrayBinArgs a, uint32_t* __restrict__ counts, const uint64_t* __restrict__ offsets,
-                                                       uint64_t* __restrict__ rec, double* __restrict__ recz) {
+                                                       uint64_t* __restrict__ rec, double* __restrict__ recz,
+                                                       int64_t* __restrict__ recb) {
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
   uint32_t k = 0;
   uint64_t kend = a.ntrees > 1 ? a.trees[1].first : a.nchunks;  // first chunk past octree k
@@ -203,9 +267,14 @@ __global__ __launch_bounds__(256) void xray_bin_kernel(XrayBinArgs a, uint32_t* 
     v.cube_edge = d.cube_edge;
     const PCV_GLOBAL uint8_t* kp = tr.keep + d.keep_off;
     const uint8_t* rgb = (const uint8_t*)tr.rgb;
+    const float* inten = (const float*)tr.inten;
     for (uint32_t q0 = 0; q0 < d.cnt; q0 += 64) {
       const uint32_t q = q0 + lane;
-      const XrayPoint pt = xray_point(a, rgb, d, v, t, bbase, q, q < d.cnt && kp[q]);
+      const XrayPoint pt = xray_point(a, rgb, inten, d, v, t, bbase, q, q < d.cnt && kp[q]);
+      if (!SCATTER && a.negative) {
+        const unsigned long long negs = __ballot(pt.neg);
+        if (negs && lane == 0) atomicAdd(a.negative + created, (unsigned long long)__popcll(negs));
+      }
       unsigned long long live = __ballot(pt.draw);
       while (live) {
         const int leader = __ffsll(live) - 1;
@@ -221,6 +290,7 @@ __global__ __launch_bounds__(256) void xray_bin_kernel(XrayBinArgs a, uint32_t* 
             if (pos < offsets[k + 1]) {  // always true: both passes compute the same buckets
               rec[pos] = pt.rec;
               if (recz) recz[pos] = pt.z;
+              if (recb) recb[pos] = pt.bin;
             }
           }
         }
@@ -260,6 +330,8 @@ struct XrayAccArgs {
   uint32_t bg;
   uint32_t colormap;
   float max_stddev;
+  uint32_t strategy;  // xray_sorted: PCV_XRAY_COLORED (binned) or PCV_XRAY_COLORED_WITH_INTENSITY
+  float min_intensity, max_intensity;
 };
 
 template <int STRAT>
@@ -357,6 +429,200 @@ __global__ __launch_bounds__(NT) void xray_accum_kernel(XrayAccArgs a, const uin
   }
   if (threadIdx.x == 0 && end > beg) atomicAdd(a.drawn + a.created0 + slot, (unsigned long long)(end - beg));
   __syncthreads();  // the next bucket clears the LDS the finalisation above reads
+  }
+}
+
+// ---- colored_with_intensity and binning: every (pixel, bin) reduced in a fixed key order ---------------------------------
+// A pixel may hold any number of bins, so per-pixel LDS state does not do. Instead a bucket's records are sorted by the key
+// (pixel, bin, record) — a total order on their contents, so the sorted bucket, and every f32 sum taken along it, does not
+// depend on the order the scatter wrote them in (scheduling, tile grouping, octree order). A bucket of at most `lds_cap`
+// records is sorted in LDS; a larger one in place in the group's workspace by the same network, its steps of distance
+// below lds_cap on LDS-sized chunks. Then one thread per pixel walks its run: per bin the count and the sum, per pixel the
+// bin means in ascending bin order.
+constexpr uint32_t kSortCapBinned = 4096;  // 16-byte records: 64 KiB of LDS
+constexpr uint32_t kSortCapPlain = 8192;   // 8-byte records
+constexpr uint32_t kSortThreads = 512;
+// at most this many kept points in one tile of the sorted strategies (checked by the group planning, pcv_xray_plan_groups):
+// a bucket then has at most 2^30 records, so the u32 indices and powers of two of the network below cannot overflow
+constexpr uint64_t kMaxSortedTilePoints = PCV_XRAY_MAX_SORTED_TILE_POINTS;
+static_assert(kMaxSortedTilePoints == 1ull << 30, "xray_sorted's u32 indices need a bucket of at most 2^30 records");
+
+template <bool BINNED>
+__device__ __forceinline__ bool key_less(uint64_t ra, int64_t ba, uint64_t rb, int64_t bb) {
+  const uint32_t pa = (uint32_t)ra & (kBlkPx - 1), pb = (uint32_t)rb & (kBlkPx - 1);
+  if (pa != pb) return pa < pb;
+  if (BINNED && ba != bb) return ba < bb;
+  return ra < rb;
+}
+// one step of the bitonic network over [0, n) with the elements past n taken as +inf: every comparator puts the smaller key
+// at the lower index (the first step of each merge compares mirrored pairs, i ^ (k - 1)), so the missing tail never
+// moves and comparators that reach it are skipped. `comparators` = (n rounded up to a power of two) / 2.
+template <bool BINNED>
+__device__ __forceinline__ void bitonic_step(uint64_t* R, int64_t* B, uint32_t n, uint32_t comparators, uint32_t k, uint32_t j) {
+  for (uint32_t c = threadIdx.x; c < comparators; c += kSortThreads) {
+    const uint32_t i = ((c & ~(j - 1)) << 1) | (c & (j - 1));
+    const uint32_t p = j == (k >> 1) ? (i ^ (k - 1)) : i + j;
+    if (p >= n) continue;
+    const uint64_t ri = R[i], rp = R[p];
+    const int64_t bi = BINNED ? B[i] : 0, bp = BINNED ? B[p] : 0;
+    if (key_less<BINNED>(rp, bp, ri, bi)) {
+      R[i] = rp;
+      R[p] = ri;
+      if (BINNED) {
+        B[i] = bp;
+        B[p] = bi;
+      }
+    }
+  }
+}
+__device__ __forceinline__ uint32_t pow2_ceil(uint32_t n) { return n <= 1 ? 1u : 1u << (32 - __clz(n - 1)); }
+// stages k = 2 .. kmax of the network on [0, n) (kmax = the power of two >= n: a whole sort)
+template <bool BINNED>
+__device__ void bitonic_stages(uint64_t* R, int64_t* B, uint32_t n, uint32_t kmax) {
+  const uint32_t comparators = pow2_ceil(n) >> 1;
+  for (uint32_t k = 2; k <= kmax; k <<= 1)
+    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+      bitonic_step<BINNED>(R, B, n, comparators, k, j);
+      __syncthreads();
+    }
+}
+template <bool BINNED>
+__device__ void chunk_load(uint64_t* sr, int64_t* sb, const uint64_t* R, const int64_t* B, uint32_t m) {
+  for (uint32_t i = threadIdx.x; i < m; i += kSortThreads) {
+    sr[i] = R[i];
+    if (BINNED) sb[i] = B[i];
+  }
+  __syncthreads();
+}
+template <bool BINNED>
+__device__ void chunk_store(const uint64_t* sr, const int64_t* sb, uint64_t* R, int64_t* B, uint32_t m) {
+  for (uint32_t i = threadIdx.x; i < m; i += kSortThreads) {
+    R[i] = sr[i];
+    if (BINNED) B[i] = sb[i];
+  }
+  __syncthreads();
+}
+// the bucket [0, n) in global memory, n > L (a power of two): each L-chunk sorted in LDS, then the merges above L, their
+// steps of distance >= L in global memory and the rest per chunk in LDS. Global writes of this workgroup are visible to
+// its own later loads after the barrier (one CU, workgroup scope).
+template <bool BINNED>
+__device__ void sort_global(uint64_t* R, int64_t* B, uint32_t n, uint32_t L, uint64_t* sr, int64_t* sb) {
+  for (uint32_t c0 = 0; c0 < n; c0 += L) {
+    const uint32_t m = min(L, n - c0);
+    chunk_load<BINNED>(sr, sb, R + c0, BINNED ? B + c0 : nullptr, m);
+    bitonic_stages<BINNED>(sr, sb, m, pow2_ceil(m));
+    chunk_store<BINNED>(sr, sb, R + c0, BINNED ? B + c0 : nullptr, m);
+  }
+  const uint32_t np = pow2_ceil(n);  // <= 2^30 (kMaxSortedTilePoints): k below stops at 2^31 at most
+  for (uint64_t k = 2 * (uint64_t)L; k <= np; k <<= 1) {
+    for (uint32_t j = k >> 1; j >= L; j >>= 1) {
+      bitonic_step<BINNED>(R, B, n, np >> 1, (uint32_t)k, j);
+      __syncthreads();
+    }
+    for (uint32_t c0 = 0; c0 < n; c0 += L) {
+      const uint32_t m = min(L, n - c0);
+      chunk_load<BINNED>(sr, sb, R + c0, BINNED ? B + c0 : nullptr, m);
+      for (uint32_t j = L >> 1; j > 0; j >>= 1) {  // half-cleaners only: j < k / 2
+        bitonic_step<BINNED>(sr, sb, m, L >> 1, 0u, j);
+        __syncthreads();
+      }
+      chunk_store<BINNED>(sr, sb, R + c0, BINNED ? B + c0 : nullptr, m);
+    }
+  }
+}
+// first index in [0, n) whose pixel is >= p (the records are sorted by pixel first)
+__device__ __forceinline__ uint32_t pixel_lower_bound(const uint64_t* R, uint32_t n, uint32_t p) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (((uint32_t)R[mid] & (kBlkPx - 1)) < p) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+// one pixel's sorted run [lo, hi), bins ascending: IntensityColoringStrategy (:269-291) or PointColorColoringStrategy
+// (:347-355). Per bin, `sum / count as f32`; the bin means are added in ascending bin order and divided by `len() as f32`.
+// colored's bin sums are exact integers, each bin mean rounded once to f32 as in the unbinned `colored`.
+template <bool BINNED>
+__device__ Rgba8 sorted_pixel(const XrayAccArgs& a, const uint64_t* R, const int64_t* B, uint32_t lo, uint32_t hi) {
+  uint64_t nb = 0;
+  if (a.strategy == PCV_XRAY_COLORED_WITH_INTENSITY) {
+    float acc = 0.0f;
+    for (uint32_t i = lo; i < hi;) {
+      const int64_t bin = BINNED ? B[i] : 0;
+      float sum = 0.0f;
+      uint64_t c = 0;
+      do {
+        sum += __uint_as_float((uint32_t)(R[i] >> 32));
+        ++c;
+        ++i;
+      } while (i < hi && (!BINNED || B[i] == bin));
+      acc += sum / (float)c;
+      ++nb;
+    }
+    return intensity_color(acc / (float)nb, a.min_intensity, a.max_intensity);
+  }
+  float ar = 0.0f, ag = 0.0f, ab = 0.0f, aa = 0.0f;
+  for (uint32_t i = lo; i < hi;) {
+    const int64_t bin = BINNED ? B[i] : 0;
+    uint64_t sr = 0, sg = 0, sb = 0, c = 0;
+    do {
+      const uint32_t col = (uint32_t)(R[i] >> 32);
+      sr += col & 255u;
+      sg += (col >> 8) & 255u;
+      sb += (col >> 16) & 255u;
+      ++c;
+      ++i;
+    } while (i < hi && (!BINNED || B[i] == bin));
+    const double dn = 255.0 * (double)c;
+    ar += (float)((double)sr / dn);
+    ag += (float)((double)sg / dn);
+    ab += (float)((double)sb / dn);
+    aa += (float)(c < (1ull << 24) ? c : (1ull << 24)) / (float)c;
+    ++nb;
+  }
+  const float fn = (float)nb;
+  return to_u8(ar / fn, ag / fn, ab / fn, aa / fn);
+}
+
+// a grid of resident workgroups striding over the group's buckets, like xray_accum; `rec` / `recb` are written (the
+// global path sorts in place)
+template <bool BINNED>
+__global__ __launch_bounds__(kSortThreads) void xray_sorted_kernel(XrayAccArgs a, uint64_t* __restrict__ rec, int64_t* __restrict__ recb,
+                                                                   uint32_t lds_cap) {
+  constexpr uint32_t kCap = BINNED ? kSortCapBinned : kSortCapPlain;
+  __shared__ uint64_t sr[kCap];
+  __shared__ int64_t sb[BINNED ? kCap : 1];
+  const uint32_t L = lds_cap < kCap ? lds_cap : kCap;  // a power of two >= 2
+  for (uint32_t b = blockIdx.x; b < a.nbuckets; b += gridDim.x) {
+    const uint32_t slot = b / a.nblocks, blk = b % a.nblocks;
+    const uint64_t beg = a.offsets[b], end = a.offsets[b + 1];
+    const uint32_t n = (uint32_t)(end - beg);  // <= kMaxSortedTilePoints: the host refuses larger tiles
+    int64_t* gb = BINNED ? recb + beg : nullptr;
+    const uint64_t* R;
+    const int64_t* B;
+    if (n <= L) {
+      chunk_load<BINNED>(sr, sb, rec + beg, gb, n);
+      bitonic_stages<BINNED>(sr, sb, n, pow2_ceil(n));
+      R = sr;
+      B = sb;
+    } else {
+      sort_global<BINNED>(rec + beg, gb, n, L, sr, sb);
+      R = rec + beg;
+      B = gb;
+    }
+    const uint32_t by = blk / a.nbx, bx = blk % a.nbx;
+    uint32_t* img = a.image + (uint64_t)(a.created0 + slot) * a.W * a.W;
+    for (uint32_t p = threadIdx.x; p < kBlkPx; p += kSortThreads) {
+      const uint32_t gx = bx * kBlk + (p % kBlk), gy = by * kBlk + (p / kBlk);
+      if (gx >= a.W || gy >= a.W) continue;
+      Rgba8 c{255, 255, 255, 0};  // TRANSPARENT.to_u8()
+      const uint32_t lo = pixel_lower_bound(R, n, p), hi = pixel_lower_bound(R, n, p + 1);
+      if (hi > lo) c = sorted_pixel<BINNED>(a, R, B, lo, hi);
+      img[(uint64_t)gy * a.W + gx] = with_background(c, a.bg);
+    }
+    if (threadIdx.x == 0 && end > beg) atomicAdd(a.drawn + a.created0 + slot, (unsigned long long)(end - beg));
+    __syncthreads();  // the next bucket overwrites the LDS the finalisation above reads
   }
 }
 
@@ -515,6 +781,7 @@ struct pcv_xray {
   uint32_t bg = 0;                // tile_background_color.to_u8(), packed RGBA8
   std::vector<uint64_t> created;  // positions in the leaf list
   std::vector<uint64_t> kept, drawn;
+  std::vector<uint64_t> negative;  // colored_with_intensity: kept points with intensity < 0 per created tile
   uint32_t* d_images = nullptr;
   // parent levels (pcv_xray_build_parents): the node list after the created leaves, deepest - 1 up to root_level, each
   // level in ascending index; level_first[k] is the first parent of level deepest - 1 - k in that list
@@ -552,7 +819,7 @@ extern "C" int pcv_xray_leaf_tiles(uint32_t tile_size_px, double pixel_size_m, c
 }
 
 extern "C" int pcv_xray_finalize(int fn, uint64_t count, const double* in, uint8_t* rgba) {
-  if ((count && (!in || !rgba)) || fn < PCV_XRAY_FN_XRAY || fn > PCV_XRAY_FN_TO_U8) return PCV_E_INVALID;
+  if ((count && (!in || !rgba)) || fn < PCV_XRAY_FN_XRAY || fn > PCV_XRAY_FN_INTENSITY) return PCV_E_INVALID;
   uint8_t table[kZWords * 32 + 1];
   xray_value_table(table);
   for (uint64_t i = 0; i < count; ++i) {
@@ -568,6 +835,9 @@ extern "C" int pcv_xray_finalize(int fn, uint64_t count, const double* in, uint8
       c = jet((float)in[i]);
     } else if (fn == PCV_XRAY_FN_PURPLISH) {
       c = purplish((float)in[i]);
+    } else if (fn == PCV_XRAY_FN_INTENSITY) {
+      const double* s = in + 3 * i;
+      c = intensity_color((float)s[0], (float)s[1], (float)s[2]);
     } else {
       const double* s = in + 4 * i;
       c = to_u8((float)s[0], (float)s[1], (float)s[2], (float)s[3]);
@@ -599,10 +869,87 @@ static void union_box(pcv_octree* const* trees, uint32_t K, double lo[3], double
       }
 }
 
+// whether colored / colored_with_intensity bin on intensity (xray and height_stddev ignore binning, attributes() :133)
+static bool coloring_binned(const pcv_xray_params* p, const pcv_xray_coloring* col) {
+  return col && col->binning_attribute && (p->strategy == PCV_XRAY_COLORED || p->strategy == PCV_XRAY_COLORED_WITH_INTENSITY);
+}
+
+// tile groups: consecutive created tiles whose records (8 B per kept point, 16 B for height_stddev and with binning: the
+// z or the bin plane) and bucket tables fit the workspace, at most max_group_buckets buckets each. group_first gets the
+// first tile of every group and nc at the end. A tile over the workspace is PCV_E_OOM; a tile of colored_with_intensity or
+// binned colored with more than kMaxSortedTilePoints kept points is PCV_E_INVALID (xray_sorted's u32 bucket indices).
+// leaf_pos (nullable) names the tiles in messages.
+static int plan_groups(const uint64_t* kept, uint64_t nc, const uint64_t* leaf_pos, uint32_t W, const pcv_xray_params* p,
+                       const pcv_xray_coloring* col, std::vector<uint64_t>& group_first, uint64_t* max_pts_out, uint64_t* max_tiles_out,
+                       char* err, uint64_t errcap) {
+  const bool binned = coloring_binned(p, col);
+  const bool sorted = binned || p->strategy == PCV_XRAY_COLORED_WITH_INTENSITY;
+  const uint32_t nbx = (W + kBlk - 1) / kBlk, nblocks = nbx * nbx;
+  const uint64_t budget = p->max_workspace_bytes ? p->max_workspace_bytes : kDefaultWorkspace;
+  const uint64_t rec_bytes = p->strategy == PCV_XRAY_HEIGHT_STDDEV || binned ? 16 : 8, bucket_bytes = 16ull * nblocks;
+  // a group also holds at most kMaxGroupBuckets buckets; the experiment build can lower that (tests of the grouping)
+  uint64_t max_group_buckets = kMaxGroupBuckets;
+  if (const char* e = pcv_experiment("PCV_XRAY_MAX_GROUP_BUCKETS")) max_group_buckets = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+  const uint64_t max_group_tiles = std::max<uint64_t>(1, max_group_buckets / nblocks);
+  group_first.assign(1, 0);
+  uint64_t cur = 0, max_pts = 0, max_tiles = 0, pts = 0;
+  for (uint64_t c = 0; c < nc; ++c) {
+    const unsigned long long name = (unsigned long long)(leaf_pos ? leaf_pos[c] : c);
+    if (sorted && kept[c] > kMaxSortedTilePoints) {
+      char m[256];
+      std::snprintf(m, sizeof(m), "xray: leaf tile %llu keeps %llu points, more than %llu for colored_with_intensity or binning: "
+                    "use a smaller pixel_size_m or tile_size_px", name, (unsigned long long)kept[c], (unsigned long long)kMaxSortedTilePoints);
+      fail_msg(err, errcap, m);
+      return PCV_E_INVALID;
+    }
+    const uint64_t need = kept[c] * rec_bytes + bucket_bytes + 16;
+    if (need > budget) {
+      char m[256];
+      std::snprintf(m, sizeof(m), "xray: leaf tile %llu keeps %llu points, %llu bytes of workspace > max_workspace_bytes %llu",
+                    name, (unsigned long long)kept[c], (unsigned long long)need, (unsigned long long)budget);
+      fail_msg(err, errcap, m);
+      return PCV_E_OOM;
+    }
+    if (cur + need > budget || c - group_first.back() == max_group_tiles) {
+      group_first.push_back(c);
+      cur = 0;
+      pts = 0;
+    }
+    cur += need;
+    pts += kept[c];
+    max_pts = std::max(max_pts, pts);
+    max_tiles = std::max<uint64_t>(max_tiles, c + 1 - group_first.back());
+  }
+  group_first.push_back(nc);
+  if (max_pts_out) *max_pts_out = max_pts;
+  if (max_tiles_out) *max_tiles_out = max_tiles;
+  return PCV_OK;
+}
+
+extern "C" int pcv_xray_plan_groups(const uint64_t* kept, uint64_t num_tiles, const pcv_xray_params* params,
+                                    const pcv_xray_coloring* coloring, uint64_t capacity, uint64_t* num_groups, uint64_t* group_first,
+                                    char* err, uint64_t errcap) {
+  if (!params || (num_tiles && !kept)) return fail_msg(err, errcap, "null argument");
+  if (params->tile_size_px == 0 || params->tile_size_px > kMaxTilePx) return fail_msg(err, errcap, "xray: tile_size_px must be in 1 ..= 32768");
+  std::vector<uint64_t> first;
+  const int rc = plan_groups(kept, num_tiles, nullptr, params->tile_size_px, params, coloring, first, nullptr, nullptr, err, errcap);
+  if (rc) return rc;
+  const uint64_t n = num_tiles ? first.size() - 1 : 0;
+  if (num_groups) *num_groups = n;
+  if (group_first) std::memcpy(group_first, first.data(), 8 * std::min<uint64_t>(n, capacity));
+  return PCV_OK;
+}
+
 // the leaf level over K octrees (K = 1: pcv_xray_run): one shape list, one query batch per octree, every raster pass one
 // launch per tile group over the chunks of all K batches
-static int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pcv_xray_params* p, pcv_xray* x) {
+static int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pcv_xray_params* p, const pcv_xray_coloring* col,
+                    pcv_xray* x) {
   const bool filter = p->interval_attribute != nullptr;
+  // colored_with_intensity, and colored with binning, take the sorted accumulation (xray_sorted); binning is ignored by
+  // xray and height_stddev (attributes() :133)
+  const bool cwi = p->strategy == PCV_XRAY_COLORED_WITH_INTENSITY;
+  const bool binned = coloring_binned(p, col);
+  const bool sorted = cwi || binned;
   char err[256] = {0};
   double bmin[3], bmax[3];
   union_box(trees, K, bmin, bmax);
@@ -671,40 +1018,19 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pc
   }
   const uint64_t nc = x->created.size();
   x->drawn.assign(nc, 0);
+  x->negative.assign(nc, 0);
   if (nc == 0) return PCV_OK;
   PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const uint32_t nbx = (W + kBlk - 1) / kBlk, nblocks = nbx * nbx;
   const uint64_t img_px = (uint64_t)W * W;
-  if ((rc = ctx->dev_alloc((void**)&x->d_images, 4 * img_px * nc))) return rc;
-  // tile groups: consecutive created tiles whose records (8 B per kept point, 16 B for height_stddev) and bucket tables
-  // fit the workspace
-  const uint64_t budget = p->max_workspace_bytes ? p->max_workspace_bytes : kDefaultWorkspace;
-  const uint64_t rec_bytes = p->strategy == PCV_XRAY_HEIGHT_STDDEV ? 16 : 8, bucket_bytes = 16ull * nblocks;
-  // a group also holds at most kMaxGroupBuckets buckets; the experiment build can lower that (tests of the grouping)
-  uint64_t max_group_buckets = kMaxGroupBuckets;
-  if (const char* e = pcv_experiment("PCV_XRAY_MAX_GROUP_BUCKETS")) max_group_buckets = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
-  const uint64_t max_group_tiles = std::max<uint64_t>(1, max_group_buckets / nblocks);
-  std::vector<uint64_t> group_first(1, 0);
-  uint64_t cur = 0, max_pts = 0, max_tiles = 0, pts = 0;
-  for (uint64_t c = 0; c < nc; ++c) {
-    const uint64_t need = x->kept[c] * rec_bytes + bucket_bytes + 16;
-    if (need > budget) {
-      char m[256];
-      std::snprintf(m, sizeof(m), "xray: leaf tile %llu keeps %llu points, %llu bytes of workspace > max_workspace_bytes %llu",
-                    (unsigned long long)x->created[c], (unsigned long long)x->kept[c], (unsigned long long)need, (unsigned long long)budget);
-      return ctx->fail(PCV_E_OOM, m);
-    }
-    if (cur + need > budget || c - group_first.back() == max_group_tiles) {
-      group_first.push_back(c);
-      cur = 0;
-      pts = 0;
-    }
-    cur += need;
-    pts += x->kept[c];
-    max_pts = std::max(max_pts, pts);
-    max_tiles = std::max<uint64_t>(max_tiles, c + 1 - group_first.back());
+  std::vector<uint64_t> group_first;
+  uint64_t max_pts = 0, max_tiles = 0;
+  {
+    char m[256] = {0};
+    if ((rc = plan_groups(x->kept.data(), nc, x->created.data(), W, p, col, group_first, &max_pts, &max_tiles, m, sizeof(m))))
+      return ctx->fail(rc, m);
   }
-  group_first.push_back(nc);
+  if ((rc = ctx->dev_alloc((void**)&x->d_images, 4 * img_px * nc))) return rc;
   // per group, the octrees that have chunks for its shapes, in list order, their chunk ranges end to end (u64 prefix)
   std::vector<XrayTreeChunks> h_trees;
   std::vector<size_t> tree_first(1, 0);
@@ -721,6 +1047,7 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pc
       e.keep = (decltype(e.keep))b->d_keep;
       e.xyz = (decltype(e.xyz))trees[t]->d_xyz;
       e.rgb = (decltype(e.rgb))trees[t]->d_rgb;
+      e.inten = sorted ? (decltype(e.inten))trees[t]->d_int : nullptr;
       e.c0 = c0;
       e.first = n;
       h_trees.push_back(e);
@@ -738,12 +1065,16 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pc
   uint32_t* d_counts;
   uint64_t *d_off, *d_rec;
   double* d_recz = nullptr;
+  int64_t* d_recb = nullptr;
+  unsigned long long* d_neg = nullptr;
   const uint64_t max_buckets = max_tiles * nblocks;
   if ((rc = sc.get(&d_cos, S)) || (rc = sc.get(&d_tiles, nc)) || (rc = sc.get(&d_trees, std::max<size_t>(h_trees.size(), 1))) ||
       (rc = sc.get(&d_table, kZWords * 32 + 1)) || (rc = sc.get(&d_drawn, nc)) || (rc = sc.get(&d_counts, max_buckets)) ||
       (rc = sc.get(&d_off, max_buckets + 1)) || (rc = sc.get(&d_rec, std::max<uint64_t>(max_pts, 1))))
     return rc;
   if (p->strategy == PCV_XRAY_HEIGHT_STDDEV && (rc = sc.get(&d_recz, std::max<uint64_t>(max_pts, 1)))) return rc;
+  if (binned && (rc = sc.get(&d_recb, std::max<uint64_t>(max_pts, 1)))) return rc;
+  if (cwi && (rc = sc.get(&d_neg, nc))) return rc;
   std::vector<XrayTileDev> h_tiles(nc);
   for (uint64_t c = 0; c < nc; ++c) {
     double mn[3], mx[3];
@@ -761,6 +1092,7 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pc
     PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_trees, h_trees.data(), sizeof(XrayTreeChunks) * h_trees.size(), hipMemcpyHostToDevice, ctx->stream));
   PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_table, table, sizeof(table), hipMemcpyHostToDevice, ctx->stream));
   PCV_HIP_CHECK(ctx, hipMemsetAsync(d_drawn, 0, 8 * nc, ctx->stream));
+  if (d_neg) PCV_HIP_CHECK(ctx, hipMemsetAsync(d_neg, 0, 8 * nc, ctx->stream));
   XrayBinArgs ba{};
   ba.created_of_shape = d_cos;
   ba.tiles = d_tiles;
@@ -770,6 +1102,9 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pc
   ba.strategy = p->strategy;
   ba.has_iso = p->has_query_from_global ? 1 : 0;
   for (int i = 0; i < 7; ++i) ba.iso[i] = p->has_query_from_global ? p->query_from_global[i] : 0.0;
+  ba.binned = binned ? 1 : 0;
+  ba.bin_size = binned ? col->bin_size : 1.0;
+  ba.negative = d_neg;
   XrayAccArgs aa{};
   aa.rec = d_rec;
   aa.recz = d_recz;
@@ -782,11 +1117,26 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pc
   aa.bg = x->bg;
   aa.colormap = p->colormap;
   aa.max_stddev = p->max_stddev;
+  aa.strategy = p->strategy;
+  aa.min_intensity = cwi ? col->min_intensity : 0.0f;
+  aa.max_intensity = cwi ? col->max_intensity : 0.0f;
+  // the sorted accumulation's LDS bucket limit (records, a power of two); the experiment build can lower it so that
+  // small buckets take the global path
+  uint32_t sort_cap = binned ? kSortCapBinned : kSortCapPlain;
+  if (const char* e = pcv_experiment("PCV_XRAY_SORT_LDS_RECORDS")) {
+    const uint64_t v = std::min<uint64_t>(std::max<uint64_t>(2, strtoull(e, nullptr, 10)), sort_cap);
+    sort_cap = 2;
+    while ((uint64_t)sort_cap * 2 <= v) sort_cap *= 2;
+  }
   // accumulation: as many workgroups as are resident at once, striding over the group's buckets (the experiment build
   // can lower the grid, to test the stride with few tiles)
   int cus = 0, per_cu = 0;
   PCV_HIP_CHECK(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-  if (p->strategy == PCV_XRAY_XRAY)
+  if (binned)
+    PCV_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xray_sorted_kernel<true>, kSortThreads, 0));
+  else if (sorted)
+    PCV_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xray_sorted_kernel<false>, kSortThreads, 0));
+  else if (p->strategy == PCV_XRAY_XRAY)
     PCV_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xray_accum_kernel<PCV_XRAY_XRAY, 1024>, 1024, 0));
   else if (p->strategy == PCV_XRAY_COLORED)
     PCV_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xray_accum_kernel<PCV_XRAY_COLORED, 256>, 256, 0));
@@ -807,7 +1157,7 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pc
     {
       PcvProf prof(ctx, PCV_K_XRAY_BIN);
       hipLaunchKernelGGL(xray_bin_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, ba, d_counts, (const uint64_t*)nullptr,
-                         (uint64_t*)nullptr, (double*)nullptr);
+                         (uint64_t*)nullptr, (double*)nullptr, (int64_t*)nullptr);
     }
     PCV_HIP_CHECK(ctx, hipGetLastError());
     {
@@ -817,14 +1167,21 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pc
     PCV_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, 4 * nb, ctx->stream));
     {
       PcvProf prof(ctx, PCV_K_XRAY_SCATTER);
-      hipLaunchKernelGGL(xray_bin_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, ba, d_counts, (const uint64_t*)d_off, d_rec, d_recz);
+      XrayBinArgs bs = ba;
+      bs.negative = nullptr;  // counted once, in the count pass
+      hipLaunchKernelGGL(xray_bin_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, bs, d_counts, (const uint64_t*)d_off, d_rec, d_recz,
+                         d_recb);
     }
     PCV_HIP_CHECK(ctx, hipGetLastError());
     aa.nbuckets = (uint32_t)nb;
     {
-      PcvProf prof(ctx, PCV_K_XRAY_ACCUM);
+      PcvProf prof(ctx, sorted ? PCV_K_XRAY_SORTED : PCV_K_XRAY_ACCUM);
       const uint32_t ag = (uint32_t)std::min<uint64_t>(nb, accum_grid);
-      if (p->strategy == PCV_XRAY_XRAY)
+      if (binned)
+        hipLaunchKernelGGL(xray_sorted_kernel<true>, dim3(ag), dim3(kSortThreads), 0, ctx->stream, aa, d_rec, d_recb, sort_cap);
+      else if (sorted)
+        hipLaunchKernelGGL(xray_sorted_kernel<false>, dim3(ag), dim3(kSortThreads), 0, ctx->stream, aa, d_rec, d_recb, sort_cap);
+      else if (p->strategy == PCV_XRAY_XRAY)
         hipLaunchKernelGGL((xray_accum_kernel<PCV_XRAY_XRAY, 1024>), dim3(ag), dim3(1024), 0, ctx->stream, aa, (const uint8_t*)d_table);
       else if (p->strategy == PCV_XRAY_COLORED)
         hipLaunchKernelGGL((xray_accum_kernel<PCV_XRAY_COLORED, 256>), dim3(ag), dim3(256), 0, ctx->stream, aa, (const uint8_t*)d_table);
@@ -835,15 +1192,17 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pc
     PCV_HIP_CHECK(ctx, hipGetLastError());
   }
   PCV_HIP_CHECK(ctx, hipMemcpyAsync(x->drawn.data(), d_drawn, 8 * nc, hipMemcpyDeviceToHost, ctx->stream));
+  if (d_neg) PCV_HIP_CHECK(ctx, hipMemcpyAsync(x->negative.data(), d_neg, 8 * nc, hipMemcpyDeviceToHost, ctx->stream));
   PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // the scratch and the batches are released on return
   return PCV_OK;
 }
 
 // the object of a checked run, or nothing (a failed run frees what it allocated)
-static int xray_new(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pcv_xray_params* p, pcv_xray** out) {
+static int xray_new(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pcv_xray_params* p, const pcv_xray_coloring* col,
+                    pcv_xray** out) {
   pcv_xray* x = new pcv_xray();
   x->ctx = ctx;
-  const int rc = xray_run(ctx, trees, K, p, x);
+  const int rc = xray_run(ctx, trees, K, p, col, x);
   if (rc != PCV_OK) {
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipGetLastError();
@@ -855,9 +1214,27 @@ static int xray_new(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pc
   return PCV_OK;
 }
 
-extern "C" int pcv_xray_check_params(const pcv_xray_params* p, int tree_has_intensity, char* err, uint64_t errcap) {
+// whether the run reads intensity beyond a filter: colored_with_intensity, or binning where the strategy uses it
+static bool coloring_needs_intensity(const pcv_xray_params* p, const pcv_xray_coloring* col) {
+  return p->strategy == PCV_XRAY_COLORED_WITH_INTENSITY ||
+         (col && col->binning_attribute && p->strategy == PCV_XRAY_COLORED);
+}
+
+extern "C" int pcv_xray_check_params_ex(const pcv_xray_params* p, const pcv_xray_coloring* col, int tree_has_intensity, char* err,
+                                        uint64_t errcap) {
   if (!p) return fail_msg(err, errcap, "null argument");
-  if (p->strategy > PCV_XRAY_HEIGHT_STDDEV) return fail_msg(err, errcap, "xray: unknown strategy");
+  if (p->strategy > PCV_XRAY_COLORED_WITH_INTENSITY) return fail_msg(err, errcap, "xray: unknown strategy");
+  if (p->strategy == PCV_XRAY_COLORED_WITH_INTENSITY && !col)
+    return fail_msg(err, errcap, "xray: colored_with_intensity needs a pcv_xray_coloring (min_intensity, max_intensity)");
+  if (col && col->binning_attribute) {
+    // BinnedColoringStrategy::bins reads a 1-d attribute (match_1d_attr_data panics on U8Vec3, src/attributes.rs:128);
+    // an octree carries only color and intensity
+    if (std::strcmp(col->binning_attribute, "intensity") != 0)
+      return fail_msg(err, errcap, std::string("xray: binning on attribute '") + col->binning_attribute + "': only intensity can be binned on");
+  }
+  if (coloring_needs_intensity(p, col) && !tree_has_intensity)
+    return fail_msg(err, errcap, p->strategy == PCV_XRAY_COLORED_WITH_INTENSITY ? "xray: octree has no intensity attribute to color by"
+                                                                                : "xray: octree has no intensity attribute to bin on");
   if (p->strategy == PCV_XRAY_HEIGHT_STDDEV) {
     if (!(p->max_stddev > 0.0f) || !std::isfinite(p->max_stddev)) return fail_msg(err, errcap, "xray: height_stddev needs 0 < max_stddev < inf");
     if (p->colormap > PCV_XRAY_PURPLISH) return fail_msg(err, errcap, "xray: unknown colormap");
@@ -871,6 +1248,12 @@ extern "C" int pcv_xray_check_params(const pcv_xray_params* p, int tree_has_inte
   return PCV_OK;
 }
 
+extern "C" int pcv_xray_check_params(const pcv_xray_params* p, int tree_has_intensity, char* err, uint64_t errcap) {
+  if (p && p->strategy == PCV_XRAY_COLORED_WITH_INTENSITY)
+    return fail_msg(err, errcap, "xray: colored_with_intensity needs min / max intensity: use pcv_xray_run_ex (pcv_xray_check_params_ex)");
+  return pcv_xray_check_params_ex(p, nullptr, tree_has_intensity, err, errcap);
+}
+
 extern "C" int pcv_xray_run(pcv_ctx* ctx, pcv_octree* tree, const pcv_xray_params* p, pcv_xray** out) {
   if (!ctx) return PCV_E_INVALID;
   if (!tree || !p || !out) return ctx->fail(PCV_E_INVALID, "null argument");
@@ -878,10 +1261,12 @@ extern "C" int pcv_xray_run(pcv_ctx* ctx, pcv_octree* tree, const pcv_xray_param
   char err[256] = {0};
   const int vrc = pcv_xray_check_params(p, tree->has_intensity ? 1 : 0, err, sizeof(err));
   if (vrc) return ctx->fail(vrc, err);
-  return xray_new(ctx, &tree, 1, p, out);
+  return xray_new(ctx, &tree, 1, p, nullptr, out);
 }
 
-extern "C" int pcv_xray_run_many(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t num_trees, const pcv_xray_params* p, pcv_xray** out) {
+// pcv_xray_run_many (ex = false: colored_with_intensity refused, coloring ignored) and pcv_xray_run_ex
+static int xray_run_checked(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t num_trees, const pcv_xray_params* p,
+                            const pcv_xray_coloring* col, bool ex, pcv_xray** out) {
   if (!ctx) return PCV_E_INVALID;
   if (!p || !out) return ctx->fail(PCV_E_INVALID, "null argument");
   *out = nullptr;
@@ -892,7 +1277,7 @@ extern "C" int pcv_xray_run_many(pcv_ctx* ctx, pcv_octree* const* trees, uint32_
     return ctx->fail(PCV_E_INVALID, "xray: " + std::to_string(num_trees) + " octrees, more than PCV_XRAY_MAX_TREES (" +
                                         std::to_string(PCV_XRAY_MAX_TREES) + ")");
   char err[256] = {0};
-  int vrc = pcv_xray_check_params(p, 1, err, sizeof(err));
+  int vrc = ex ? pcv_xray_check_params_ex(p, col, 1, err, sizeof(err)) : pcv_xray_check_params(p, 1, err, sizeof(err));
   if (vrc) return ctx->fail(vrc, err);
   for (uint32_t t = 0; t < num_trees; ++t) {
     const std::string which = "xray: octree " + std::to_string(t);
@@ -900,8 +1285,26 @@ extern "C" int pcv_xray_run_many(pcv_ctx* ctx, pcv_octree* const* trees, uint32_
     if (trees[t]->ctx != ctx) return ctx->fail(PCV_E_INVALID, which + " belongs to another context");
     if (p->interval_attribute && !trees[t]->has_intensity)
       return ctx->fail(PCV_E_INVALID, which + " has no intensity attribute to filter on");
+    if (ex && coloring_needs_intensity(p, col) && !trees[t]->has_intensity)
+      return ctx->fail(PCV_E_INVALID, which + " has no intensity attribute to color or bin by");
   }
-  return xray_new(ctx, trees, num_trees, p, out);
+  return xray_new(ctx, trees, num_trees, p, ex ? col : nullptr, out);
+}
+
+extern "C" int pcv_xray_run_many(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t num_trees, const pcv_xray_params* p, pcv_xray** out) {
+  return xray_run_checked(ctx, trees, num_trees, p, nullptr, false, out);
+}
+
+extern "C" int pcv_xray_run_ex(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t num_trees, const pcv_xray_params* p,
+                               const pcv_xray_coloring* coloring, pcv_xray** out) {
+  if (!coloring) return xray_run_checked(ctx, trees, num_trees, p, nullptr, false, out);
+  return xray_run_checked(ctx, trees, num_trees, p, coloring, true, out);
+}
+
+extern "C" int pcv_xray_negative(const pcv_xray* x, uint64_t* negative) {
+  if (!x) return PCV_E_INVALID;
+  if (negative) std::memcpy(negative, x->negative.data(), 8 * x->negative.size());
+  return PCV_OK;
 }
 
 extern "C" int pcv_xray_info(const pcv_xray* x, uint32_t* deepest_level, double rect[3], uint64_t* num_leaves, uint64_t* num_created) {

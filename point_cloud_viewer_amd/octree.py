@@ -273,25 +273,31 @@ class Context:
         return OctreeResult(self, h)
 
     def xray_tiles(self, trees, tile_size_px=256, pixel_size_m=None, strategy="xray", query_from_global=None, intensity_interval=None,
-                   background="white", root_node_id="r", max_workspace_bytes=None):
+                   background="white", root_node_id="r", max_workspace_bytes=None, min_intensity=0.0, max_intensity=1.0,
+                   binning=None):
         """OctreeResult.xray_tiles (same keywords) over several octrees of this context, as build_xray_quadtree with several
-        point_cloud_locations (pcv_xray_run_many): the union of their bounding boxes, every tile's points from all of them.
-        Returns an XrayTiles."""
+        point_cloud_locations (pcv_xray_run_many, or pcv_xray_run_ex with colored_with_intensity or binning): the union of
+        their bounding boxes, every tile's points from all of them. Returns an XrayTiles."""
         trees = list(trees)
         if not trees:
             raise ValueError("xray_tiles: no octrees given")
         p = xray_params(tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background, root_node_id,
                         max_workspace_bytes)
+        col = xray_coloring(strategy, min_intensity, max_intensity, binning)
         arr = (C.c_void_p * len(trees))(*[t.handle for t in trees])
         h = C.c_void_p()
-        self._check(self.lib.pcv_xray_run_many(self.handle, arr, len(trees), C.byref(p), C.byref(h)))
+        if col is None:
+            self._check(self.lib.pcv_xray_run_many(self.handle, arr, len(trees), C.byref(p), C.byref(h)))
+        else:
+            self._check(self.lib.pcv_xray_run_ex(self.handle, arr, len(trees), C.byref(p), C.byref(col), C.byref(h)))
         return XrayTiles(self, h, int(tile_size_px))
 
     def xray_quadtree(self, trees, tile_size_px=256, pixel_size_m=None, strategy="xray", query_from_global=None,
-                      intensity_interval=None, background="white", root_node_id="r", max_workspace_bytes=None):
+                      intensity_interval=None, background="white", root_node_id="r", max_workspace_bytes=None, min_intensity=0.0,
+                      max_intensity=1.0, binning=None):
         """xray_tiles over several octrees (same arguments) with every level above the leaves built on the device."""
         xt = self.xray_tiles(trees, tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background,
-                             root_node_id, max_workspace_bytes)
+                             root_node_id, max_workspace_bytes, min_intensity, max_intensity, binning)
         xt.build_parents()
         return xt
 
@@ -924,23 +930,33 @@ class OctreeResult:
         return QueryBatch(self, h, shapes.count)
 
     def xray_tiles(self, tile_size_px=256, pixel_size_m=None, strategy="xray", query_from_global=None, intensity_interval=None,
-                   background="white", root_node_id="r", max_workspace_bytes=None):
+                   background="white", root_node_id="r", max_workspace_bytes=None, min_intensity=0.0, max_intensity=1.0,
+                   binning=None):
         """The leaf level of xray's build_xray_quadtree (xray/src/generation.rs:557-648) rasterised on the device.
-        strategy: "xray", "colored" or ("height_stddev", max_stddev, "jet" | "purplish"); query_from_global: None or
-        translation xyz + unit quaternion ijkw; intensity_interval: None or (lo, hi); background: "white" | "transparent";
-        root_node_id: a quadtree node name ("r" + base-4 digits). Returns an XrayTiles; its images stay on the device."""
+        strategy: "xray", "colored", "colored_with_intensity" (IntensityColoringStrategy with min_intensity /
+        max_intensity, the reference's defaults 0 and 1) or ("height_stddev", max_stddev, "jet" | "purplish");
+        binning: None or ("intensity", bin size), read by colored and colored_with_intensity (pcv_xray_run_ex);
+        query_from_global: None or translation xyz + unit quaternion ijkw; intensity_interval: None or (lo, hi); background:
+        "white" | "transparent"; root_node_id: a quadtree node name ("r" + base-4 digits). Returns an XrayTiles; its images
+        stay on the device."""
         p = xray_params(tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background, root_node_id,
                         max_workspace_bytes)
+        col = xray_coloring(strategy, min_intensity, max_intensity, binning)
         h = C.c_void_p()
-        self.ctx._check(self.lib.pcv_xray_run(self.ctx.handle, self.handle, C.byref(p), C.byref(h)))
+        if col is None:
+            self.ctx._check(self.lib.pcv_xray_run(self.ctx.handle, self.handle, C.byref(p), C.byref(h)))
+        else:
+            arr = (C.c_void_p * 1)(self.handle)
+            self.ctx._check(self.lib.pcv_xray_run_ex(self.ctx.handle, arr, 1, C.byref(p), C.byref(col), C.byref(h)))
         return XrayTiles(self.ctx, h, int(tile_size_px))
 
     def xray_quadtree(self, tile_size_px=256, pixel_size_m=None, strategy="xray", query_from_global=None, intensity_interval=None,
-                      background="white", root_node_id="r", max_workspace_bytes=None):
+                      background="white", root_node_id="r", max_workspace_bytes=None, min_intensity=0.0, max_intensity=1.0,
+                      binning=None):
         """xray_tiles (same arguments) with every level above the leaves up to root_node_id built on the device
         (create_non_leaf_nodes, generation.rs:656-682): the whole quadtree; XrayTiles.write puts it on disk."""
         xt = self.xray_tiles(tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background, root_node_id,
-                             max_workspace_bytes)
+                             max_workspace_bytes, min_intensity, max_intensity, binning)
         xt.build_parents()
         return xt
 
@@ -1099,7 +1115,7 @@ def xray_params(tile_size_px=256, pixel_size_m=None, strategy="xray", query_from
     p = L.XrayParams()
     p.tile_size_px, p.pixel_size_m = int(tile_size_px), float(pixel_size_m)
     if isinstance(strategy, str):
-        kinds = {"xray": L.XRAY_XRAY, "colored": L.XRAY_COLORED}
+        kinds = {"xray": L.XRAY_XRAY, "colored": L.XRAY_COLORED, "colored_with_intensity": L.XRAY_COLORED_WITH_INTENSITY}
         if strategy not in kinds:
             raise ValueError(f"unknown strategy {strategy!r}")
         p.strategy = kinds[strategy]
@@ -1124,10 +1140,33 @@ def xray_params(tile_size_px=256, pixel_size_m=None, strategy="xray", query_from
     return p
 
 
-def xray_check_params(params, tree_has_intensity=True):
-    """pcv_xray_check_params (host only): raises PcvError for what pcv_xray_run would refuse before any device work."""
+def xray_coloring(strategy="xray", min_intensity=0.0, max_intensity=1.0, binning=None):
+    """The pcv_xray_coloring of pcv_xray_run_ex, or None where pcv_xray_run / _run_many do: strategy
+    "colored_with_intensity" or a binning. binning: None or (attribute name, bin size); the library checks the name."""
+    if binning is not None:
+        if isinstance(binning, (str, bytes)) or len(binning) != 2:
+            raise ValueError(f"binning must be (attribute, bin size), not {binning!r}")
+        attr, size = binning
+        if not isinstance(attr, str):
+            raise ValueError(f"binning attribute must be a str, not {attr!r}")
+    if strategy != "colored_with_intensity" and binning is None:
+        return None
+    col = L.XrayColoring()
+    col.min_intensity, col.max_intensity = float(min_intensity), float(max_intensity)
+    if binning is not None:
+        col.binning_attribute, col.bin_size = binning[0].encode(), float(binning[1])
+    return col
+
+
+def xray_check_params(params, tree_has_intensity=True, coloring=None):
+    """pcv_xray_check_params (pcv_xray_check_params_ex with a coloring; host only): raises PcvError for what pcv_xray_run
+    (pcv_xray_run_ex) would refuse before any device work."""
     err = C.create_string_buffer(256)
-    rc = L.load_library().pcv_xray_check_params(C.byref(params), int(bool(tree_has_intensity)), err, 256)
+    lib = L.load_library()
+    if coloring is None:
+        rc = lib.pcv_xray_check_params(C.byref(params), int(bool(tree_has_intensity)), err, 256)
+    else:
+        rc = lib.pcv_xray_check_params_ex(C.byref(params), C.byref(coloring), int(bool(tree_has_intensity)), err, 256)
     if rc != L.PCV_OK:
         raise L.PcvError(rc, err.value.decode())
 
@@ -1173,10 +1212,10 @@ def xray_leaf_tiles(tile_size_px, pixel_size_m, bbox_min, bbox_max, query_from_g
 
 def xray_finalize(fn, values):
     """pcv_xray_finalize: the raster kernel's colour functions on the host. fn: "xray" (values = distinct z bucket counts),
-    "colored" (n x 4: exact r, g, b sums, count), "jet" / "purplish" (values in [0, 1]), "to_u8" (n x 4 f32 colours).
-    Returns (n, 4) uint8 RGBA, before any background."""
+    "colored" (n x 4: exact r, g, b sums, count), "jet" / "purplish" (values in [0, 1]), "to_u8" (n x 4 f32 colours),
+    "intensity" (n x 3: mean, min, max, each as f32). Returns (n, 4) uint8 RGBA, before any background."""
     fns = {"xray": L.XRAY_FN_XRAY, "colored": L.XRAY_FN_COLORED, "jet": L.XRAY_FN_JET, "purplish": L.XRAY_FN_PURPLISH,
-           "to_u8": L.XRAY_FN_TO_U8}
+           "to_u8": L.XRAY_FN_TO_U8, "intensity": L.XRAY_FN_INTENSITY}
     v = np.ascontiguousarray(values, dtype=np.float64)
     n = v.shape[0] if v.ndim else 1
     out = np.zeros((n, 4), dtype=np.uint8)
@@ -1227,6 +1266,10 @@ class XrayTiles:
                                 self.drawn.ctypes.data)
         self.leaf_index, self.created = self.leaf_index[:nl.value], self.created[:nc.value]
         self.kept, self.drawn = self.kept[:nc.value], self.drawn[:nc.value]
+        # colored_with_intensity: kept points with intensity < 0 per created tile (not drawn; 0 for other strategies)
+        self.negative = np.zeros(max(nc.value, 1), dtype=np.uint64)
+        self.lib.pcv_xray_negative(handle, self.negative.ctypes.data)
+        self.negative = self.negative[:nc.value]
         self.leaf_ids = [quadtree_node_name(self.deepest_level, i) for i in self.leaf_index]
         self.created_ids = [self.leaf_ids[int(c)] for c in self.created]
         self.num_created = int(nc.value)
