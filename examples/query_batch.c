@@ -4,6 +4,11 @@
  * a tile would be copied out with pcv_query_batch_points over its segments.
  *
  *   query_batch <dir> <tiles>
+ *   query_batch <dir> --map-tiles <zoom>
+ *
+ * --map-tiles: the octree is an ECEF cloud; the slippy-map tiles of zoom level <zoom> (8..23: a WebMercatorRect is at most one
+ * pixel of zoom 0 wide, i.e. one tile of zoom 8) that the projection of the bounding box's corners spans go to the batch as
+ * PCV_SHAPE_WEB_MERCATOR_RECT shapes made by pcv_wmr_from_zoomed, row by row; one line "<tile x> <tile y> <count>" per tile.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -12,13 +17,19 @@
 #include "pcv_layout_check.h"
 
 int main(int argc, char** argv) {
-  if (argc < 3) {
-    fprintf(stderr, "usage: query_batch <dir> <tiles>\n");
+  const int map_tiles = argc >= 4 && strcmp(argv[2], "--map-tiles") == 0;
+  if (argc < 3 || (argc >= 4 && !map_tiles)) {
+    fprintf(stderr, "usage: query_batch <dir> <tiles> | query_batch <dir> --map-tiles <zoom>\n");
     return 2;
   }
-  const unsigned tiles = (unsigned)strtoul(argv[2], NULL, 10);
+  const unsigned tiles = map_tiles ? 1u : (unsigned)strtoul(argv[2], NULL, 10);
+  const unsigned zoom = map_tiles ? (unsigned)strtoul(argv[3], NULL, 10) : 0u;
   if (tiles == 0) {
     fprintf(stderr, "tiles must be positive\n");
+    return 2;
+  }
+  if (map_tiles && (zoom < 8 || zoom > 23)) {
+    fprintf(stderr, "zoom must be 8..23\n");
     return 2;
   }
   pcv_ctx* ctx = NULL;
@@ -34,9 +45,50 @@ int main(int argc, char** argv) {
     double res, bmin[3], bmax[3];
     int version;
     pcv_octree_meta(tree, &res, bmin, bmax, &version);
-    const unsigned count = tiles * tiles;
-    grid = (pcv_shape*)calloc(count, sizeof(pcv_shape));
-    for (unsigned i = 0; rc == PCV_OK && i < tiles; ++i)
+    unsigned count = tiles * tiles;
+    unsigned tx0 = 0, ty0 = 0, ntx = 0;
+    if (map_tiles) { /* the tiles under the projection of the box's eight corners */
+      double cx[8], cy[8], cz[8], u[8], v[8];
+      for (int c = 0; c < 8; ++c) {
+        cx[c] = (c & 1) ? bmax[0] : bmin[0];
+        cy[c] = (c & 2) ? bmax[1] : bmin[1];
+        cz[c] = (c & 4) ? bmax[2] : bmin[2];
+      }
+      rc = pcv_wmr_project(8, cx, cy, cz, u, v);
+      double ulo = u[0], uhi = u[0], vlo = v[0], vhi = v[0];
+      for (int c = 1; c < 8; ++c) {
+        ulo = u[c] < ulo ? u[c] : ulo;
+        uhi = u[c] > uhi ? u[c] : uhi;
+        vlo = v[c] < vlo ? v[c] : vlo;
+        vhi = v[c] > vhi ? v[c] : vhi;
+      }
+      const double n = (double)(1u << zoom);
+      const unsigned last = (1u << zoom) - 1u;
+      tx0 = (unsigned)(ulo * n);
+      ty0 = (unsigned)(vlo * n);
+      unsigned tx1 = (unsigned)(uhi * n), ty1 = (unsigned)(vhi * n);
+      tx1 = tx1 > last ? last : tx1;
+      ty1 = ty1 > last ? last : ty1;
+      ntx = tx1 - tx0 + 1;
+      if (rc == PCV_OK && (uint64_t)ntx * (ty1 - ty0 + 1) > (1u << 20)) {
+        fprintf(stderr, "more than 2^20 tiles at this zoom\n");
+        rc = PCV_E_INVALID;
+      }
+      count = rc == PCV_OK ? ntx * (ty1 - ty0 + 1) : 0;
+    }
+    grid = (pcv_shape*)calloc(count ? count : 1, sizeof(pcv_shape));
+    for (unsigned k = 0; map_tiles && rc == PCV_OK && k < count; ++k) {
+      /* a tile's south-east corner belongs to the next tile (contains() is half-open); the map's last row / column ends one
+       * representable step inside the map, where from_zoomed still accepts it */
+      const double px = 256.0 * (tx0 + k % ntx), py = 256.0 * (ty0 + k / ntx), edge = 256.0 * (double)(1u << zoom);
+      const double mn[2] = {px, py};
+      double mx[2] = {px + 256.0, py + 256.0};
+      if (mx[0] >= edge) mx[0] = edge * (1.0 - 1.1102230246251565e-16);
+      if (mx[1] >= edge) mx[1] = edge * (1.0 - 1.1102230246251565e-16);
+      grid[k].kind = PCV_SHAPE_WEB_MERCATOR_RECT;
+      rc = pcv_wmr_from_zoomed(mn, mx, zoom, grid[k].params);
+    }
+    for (unsigned i = 0; !map_tiles && rc == PCV_OK && i < tiles; ++i)
       for (unsigned j = 0; j < tiles; ++j) {
         pcv_shape* s = &grid[i * tiles + j];
         s->kind = PCV_SHAPE_AABB;
@@ -58,7 +110,8 @@ int main(int argc, char** argv) {
       rc = pcv_query_batch_segments(batch, first, NULL, offset);
     }
     for (unsigned k = 0; rc == PCV_OK && k < count; ++k)
-      printf("%u %u %llu\n", k / tiles, k % tiles, (unsigned long long)(offset[first[k + 1]] - offset[first[k]]));
+      printf("%u %u %llu\n", map_tiles ? tx0 + k % ntx : k / tiles, map_tiles ? ty0 + k / ntx : k % tiles,
+             (unsigned long long)(offset[first[k + 1]] - offset[first[k]]));
   }
   if (rc != PCV_OK) fprintf(stderr, "query_batch: %s (%d)\n", ctx ? pcv_last_error(ctx) : "no context", rc);
   free(first);

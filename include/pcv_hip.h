@@ -527,12 +527,18 @@ int pcv_octree_open_dir(pcv_ctx* ctx, const char* directory, pcv_octree** out);
  *   PCV_SHAPE_FRUSTUM_WITH_INVERSE  clip_from_query (16) then query_from_clip (16), as Frustum::new stores them
  *                                   (frustum.rs:101-108)
  *   PCV_SHAPE_OBB                   query_from_obb isometry: translation xyz, unit quaternion i j k w; then the
- *                                   half extent xyz (src/geometry/obb.rs:13-45) */
+ *                                   half extent xyz (src/geometry/obb.rs:13-45)
+ *   PCV_SHAPE_WEB_MERCATOR_RECT     north_west.normalized (x, y) then south_east.normalized (x, y), each in [0, 1): the
+ *                                   fields of geometry::WebMercatorRect (src/geometry/web_mercator_rect.rs:30-33); make
+ *                                   them with pcv_wmr_from_zoomed. The query space is ECEF. pcv_shapes_create takes the
+ *                                   four doubles as given, like the other kinds' parameters: it does not repeat the
+ *                                   constructor's checks (NaN or inverted bounds give a shape that contains nothing). */
 #define PCV_SHAPE_ALL 0
 #define PCV_SHAPE_AABB 1
 #define PCV_SHAPE_FRUSTUM 2
 #define PCV_SHAPE_OBB 3
 #define PCV_SHAPE_FRUSTUM_WITH_INVERSE 4
+#define PCV_SHAPE_WEB_MERCATOR_RECT 5
 typedef struct pcv_shape {
   int32_t kind;
   int32_t reserved;
@@ -550,12 +556,46 @@ typedef struct pcv_shapes pcv_shapes;
 int pcv_shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t count, pcv_shapes** out);
 void pcv_shapes_free(pcv_shapes* shapes);
 uint32_t pcv_shapes_count(const pcv_shapes* shapes);
-/* Inspect one prepared shape (tests): 8 corners, up to 26 axes. valid == 0: the matrix is not invertible. */
+/* Inspect one prepared shape (tests): 8 corners, up to 26 axes. valid == 0: the matrix is not invertible. PCV_E_INVALID for
+ * a shape with more than 26 axes (a web-mercator rectangle may have up to 45): use pcv_shapes_get_ex. */
 int pcv_shapes_get(pcv_shapes* shapes, uint32_t i, double corners[24], double axes[78], uint32_t* num_axes, int* valid);
+/* The same for any shape: `axes` holds 3 * axes_capacity doubles (PCV_MAX_SHAPE_AXES always suffices); *num_axes is the
+ * shape's count, of which the first min(count, axes_capacity) are written. */
+#define PCV_MAX_SHAPE_AXES 45
+int pcv_shapes_get_ex(pcv_shapes* shapes, uint32_t i, double corners[24], double* axes, uint32_t axes_capacity,
+                      uint32_t* num_axes, int* valid);
+
+/* ---- web-mercator rectangles: host-only helpers (no device, no context) ------------------------------------------ */
+/* WebMercatorRect::from_zoomed_coordinates (src/geometry/web_mercator_rect.rs:40-53, src/math/web_mercator.rs:84-97):
+ * min / max are (x, y) map coordinates at zoom z, in [0, 256 * 2^z). PCV_E_INVALID where the reference returns None:
+ * z > 23, a coordinate out of range, (max - min) / 2^z wider than 1 in x (after rem_euclid(256): x may wrap) or outside
+ * [0, 1] in y. params receives the shape's four doubles. A rectangle that wraps in x (nw.x > se.x) is accepted and then
+ * contains no point — the reference's behaviour (web_mercator_rect.rs:121-127). */
+int pcv_wmr_from_zoomed(const double min[2], const double max[2], uint32_t z, double params[4]);
+/* ConvexPolyhedron::compute_corners (web_mercator_rect.rs:61-83): to_lat_lng of both coordinates (web_mercator.rs:55-64,
+ * both clamps), then WGS84 -> ECEF at -500 m and 10 000 m: NW NE SE SW down, NW NE SE SW up. Uses the host's libm. */
+int pcv_wmr_corners(const double params[4], double corners[24]);
+/* PointCulling::contains (web_mercator_rect.rs:121-127) on the host, point by point: ECEF -> WGS84,
+ * WebMercatorCoord::from_lat_lng (web_mercator.rs:38-50), then nw.x <= u && nw.y <= v && u < se.x && v < se.y.
+ * pcv_wmr_project hands out (u, v). The device's keep flag of every point query equals pcv_wmr_contains bit for bit: both
+ * run the same arithmetic (no libm on either side). */
+int pcv_wmr_project(uint64_t n, const double* x, const double* y, const double* z, double* u, double* v);
+int pcv_wmr_contains(const double params[4], uint64_t n, const double* x, const double* y, const double* z, uint8_t* keep);
+/* TEST HOOKS, not part of the query interface (the suite restates the reference's unit tests and measures the chain's
+ * transcendentals through them): WebMercatorCoord::from_lat_lng (web_mercator.rs:38-50; radians) with the library's own
+ * sin / ln, to_lat_lng (web_mercator.rs:55-64) with libm, as pcv_wmr_corners uses it, and pcv_wmr_math below. */
+int pcv_wmr_from_lat_lng(uint64_t n, const double* lat, const double* lng, double* u, double* v);
+int pcv_wmr_to_lat_lng(uint64_t n, const double* u, const double* v, double* lat, double* lng);
+/* (test hook) The transcendentals of the per-point chain: out = atan2(a, b); out = sin a, out2 = cos a; out = ln a. */
+#define PCV_WMR_FN_ATAN2 0
+#define PCV_WMR_FN_SINCOS 1
+#define PCV_WMR_FN_LN 2
+int pcv_wmr_math(int fn, uint64_t n, const double* a, const double* b, double* out, double* out2);
 
 /* Q2: Relation of every node cube against every shape (CachedAxesIntersector::intersect, sat.rs:167-194), row
  * major [shape][node] (node order as pcv_octree_node), host buffers. size_on_screen (nullable, same shape) is
- * relative_size_on_screen (src/octree/mod.rs:119-139) for the shape's clip_from_query; NaN where w == 0. */
+ * relative_size_on_screen (src/octree/mod.rs:119-139) for the shape's clip_from_query; NaN where w == 0 — so NaN for
+ * every shape without a clip matrix (Aabb, Obb, web-mercator rectangle). */
 int pcv_cull_nodes(pcv_ctx* ctx, const pcv_shapes* shapes, pcv_octree* tree, uint8_t* relation, double* size_on_screen);
 /* Q2 as a list per shape (round 5): the nodes whose Relation is not Out (sat.rs:174-194), in node order —
  * node_indices / relation / size_on_screen are [shape][capacity] host arrays, counts[shape] the number of such nodes

@@ -57,7 +57,9 @@ class Shape(C.Structure):
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("params", C.c_double * 32)]
 
 
-SHAPE_ALL, SHAPE_AABB, SHAPE_FRUSTUM, SHAPE_OBB, SHAPE_FRUSTUM_WITH_INVERSE = 0, 1, 2, 3, 4
+SHAPE_ALL, SHAPE_AABB, SHAPE_FRUSTUM, SHAPE_OBB, SHAPE_FRUSTUM_WITH_INVERSE, SHAPE_WEB_MERCATOR_RECT = 0, 1, 2, 3, 4, 5
+MAX_SHAPE_AXES = 45  # PCV_MAX_SHAPE_AXES
+WMR_FN_ATAN2, WMR_FN_SINCOS, WMR_FN_LN = 0, 1, 2
 
 
 class XrayParams(C.Structure):
@@ -219,6 +221,15 @@ _SIGNATURES = {
     "pcv_shapes_count": (C.c_uint32, [_vp]),
     "pcv_shapes_get": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                  C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
+    "pcv_shapes_get_ex": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint32,
+                                    C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
+    "pcv_wmr_from_zoomed": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double)]),
+    "pcv_wmr_corners": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "pcv_wmr_project": (C.c_int, [C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
+    "pcv_wmr_contains": (C.c_int, [C.POINTER(C.c_double), C.c_uint64, _vp, _vp, _vp, _vp]),
+    "pcv_wmr_from_lat_lng": (C.c_int, [C.c_uint64, _vp, _vp, _vp, _vp]),
+    "pcv_wmr_to_lat_lng": (C.c_int, [C.c_uint64, _vp, _vp, _vp, _vp]),
+    "pcv_wmr_math": (C.c_int, [C.c_int, C.c_uint64, _vp, _vp, _vp, _vp]),
     "pcv_cull_nodes": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "pcv_cull_nodes_sparse": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp]),
     "pcv_visible_nodes": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),

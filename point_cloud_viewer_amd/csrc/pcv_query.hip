@@ -17,10 +17,12 @@
 // Bounds: K7 is f64-VALU bound (about 1 kflop per pair on 128 B of data), K8/K9 are HBM streams.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <vector>
 
 #include "pcv_query_dev.h"
+#include "pcv_wmr_dev.h"
 
 // ---------------------------------------------------------------------------------------------
 // device math
@@ -74,10 +76,13 @@ __device__ __forceinline__ V3d m4_transform_point(const double* m, V3d p) {
 struct PcvShapeDev {
   int32_t kind;   // PCV_SHAPE_*
   int32_t valid;  // 0: matrix not invertible (Frustum::from_matrix4 -> None)
-  int32_t naxes;
+  int32_t naxes;  // 0 for a web-mercator rectangle: its axes live in its PcvShapeWide
   int32_t pad;
   double clip_from_query[16];
-  double query_from_clip[16];
+  union {
+    double query_from_clip[16];
+    struct PcvShapeWide* wide;  // web-mercator rectangle (no matrices): its record beside the table
+  };
   double iso[7];   // obb_from_query (translation xyz, quaternion ijkw) for contains()
   double half[3];
   double bmin[3], bmax[3];
@@ -87,10 +92,27 @@ struct PcvShapeDev {
   double amax[PCV_MAX_AXES];
 };
 
+// A web-mercator rectangle has 12 edges and 6 face normals: up to 6 + 3 + 36 = 45 axes (sat.rs:111-143). They live beside the
+// shape table, one record per such shape, so that PcvShapeDev keeps its layout and stride for the other kinds. The flat
+// kernels' WIDE instances read them (sat_cube<true>); the instances the four older kinds run, and the wave-per-shape walks, whose
+// lanes hold at most 32 axes, are what they were: to them such a shape has no axes, and what they write for it is overwritten by
+// the WIDE instance launched behind them on the same stream.
+#define PCV_WIDE_AXES 45
+struct PcvShapeWide {
+  int32_t naxes;
+  int32_t pad;
+  double axes[PCV_WIDE_AXES * 3];
+  double amin[PCV_WIDE_AXES];
+  double amax[PCV_WIDE_AXES];
+};
+static_assert(PCV_WIDE_AXES == PCV_MAX_SHAPE_AXES, "pcv_shapes_get_ex's capacity");
+static_assert(sizeof(PcvShapeDev) == 1632 && offsetof(PcvShapeDev, iso) == 272, "the union keeps the layout of the four older kinds");
+
 struct pcv_shapes {
   pcv_ctx* ctx;
   uint32_t count;
   PcvShapeDev* dev;
+  PcvShapeWide* wide = nullptr;  // one per web-mercator rectangle, in shape order
   std::vector<int32_t> kinds;  // host copy: the point kernels are compiled per shape kind
 };
 
@@ -108,7 +130,7 @@ __device__ void project8(const double* corners, V3d axis, double* mn, double* mx
 }
 
 // cache_separating_axes against the unit edges / normals of an AABB (sat.rs:111-143)
-__device__ void cache_axes_for_aabb(PcvShapeDev* s, const V3d* edges, int ne, const V3d* normals, int nn) {
+__device__ int cache_axes_for_aabb(double* axes, int cap, const V3d* edges, int ne, const V3d* normals, int nn) {
   const V3d unit[3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
   V3d all[6 + 3 + 36];
   int na = 0;
@@ -123,7 +145,7 @@ __device__ void cache_axes_for_aabb(PcvShapeDev* s, const V3d* edges, int ne, co
   for (int i = 0; i < na; ++i) {
     bool dupe = false;
     for (int j = 0; j < nd; ++j) {
-      V3d a2 = {s->axes[3 * j], s->axes[3 * j + 1], s->axes[3 * j + 2]};
+      V3d a2 = {axes[3 * j], axes[3 * j + 1], axes[3 * j + 2]};
       V3d dm = v_sub(all[i], a2), dp = v_add(all[i], a2);
       double d1 = v_dot(dm, dm), d2 = v_dot(dp, dp);
       if (fmin(d1, d2) < 2.220446049250313e-16) {
@@ -131,14 +153,14 @@ __device__ void cache_axes_for_aabb(PcvShapeDev* s, const V3d* edges, int ne, co
         break;
       }
     }
-    if (!dupe && nd < PCV_MAX_AXES) {
-      s->axes[3 * nd] = all[i].x;
-      s->axes[3 * nd + 1] = all[i].y;
-      s->axes[3 * nd + 2] = all[i].z;
+    if (!dupe && nd < cap) {
+      axes[3 * nd] = all[i].x;
+      axes[3 * nd + 1] = all[i].y;
+      axes[3 * nd + 2] = all[i].z;
       ++nd;
     }
   }
-  s->naxes = nd;
+  return nd;
 }
 
 __global__ __launch_bounds__(64) void shape_setup_kernel(PcvShapeDev* shapes, uint32_t count) {
@@ -179,7 +201,7 @@ __global__ __launch_bounds__(64) void shape_setup_kernel(PcvShapeDev* shapes, ui
     n[2] = v_normalize(v_cross(e[0], e[3]));
     n[3] = v_normalize(v_cross(e[1], e[2]));
     n[4] = v_normalize(v_cross(e[1], e[4]));
-    cache_axes_for_aabb(s, e, 6, n, 5);
+    s->naxes = cache_axes_for_aabb(s->axes, PCV_MAX_AXES, e, 6, n, 5);
   } else if (s->kind == PCV_SHAPE_OBB) {
     // s->iso holds query_from_obb on entry; corners/edges use it, contains() needs the inverse (obb.rs:35-41)
     const double* q = s->iso + 3;
@@ -195,7 +217,7 @@ __global__ __launch_bounds__(64) void shape_setup_kernel(PcvShapeDev* shapes, ui
     e[0] = v_normalize(quat_rotate(q, V3d{1, 0, 0}));
     e[1] = v_normalize(quat_rotate(q, V3d{0, 1, 0}));
     e[2] = v_normalize(quat_rotate(q, V3d{0, 0, 1}));
-    cache_axes_for_aabb(s, e, 3, e, 3);
+    s->naxes = cache_axes_for_aabb(s->axes, PCV_MAX_AXES, e, 3, e, 3);
     double qi[4] = {-q[0], -q[1], -q[2], q[3]};  // Isometry3::inverse
     V3d ti = quat_rotate(qi, V3d{-t.x, -t.y, -t.z});
     s->iso[0] = ti.x;
@@ -214,6 +236,25 @@ __global__ __launch_bounds__(64) void shape_setup_kernel(PcvShapeDev* shapes, ui
     const double ax[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     for (int i = 0; i < 9; ++i) s->axes[i] = ax[i];
     s->naxes = 3;
+  } else if (s->kind == PCV_SHAPE_WEB_MERCATOR_RECT) {
+    // s->corners came up from the host (pcv_wmr_corners); edges and face normals in intersector()'s order
+    // (web_mercator_rect.rs:85-116)
+    V3d k[8];
+    for (int i = 0; i < 8; ++i) k[i] = V3d{s->corners[3 * i], s->corners[3 * i + 1], s->corners[3 * i + 2]};
+    V3d e[12], n[6];
+    for (int i = 0; i < 4; ++i) {
+      e[i] = v_normalize(v_sub(k[(i + 1) & 3], k[i]));              // N E S W edge, down
+      e[4 + i] = v_normalize(v_sub(k[4 + ((i + 1) & 3)], k[4 + i]));  // N E S W edge, up
+      e[8 + i] = v_normalize(v_sub(k[4 + i], k[i]));                // NW NE SE SW edge
+    }
+    for (int i = 0; i < 4; ++i) n[i] = v_normalize(v_cross(e[i], e[8 + i]));  // N E S W face
+    n[4] = v_normalize(v_cross(e[1], e[0]));                                  // down face
+    n[5] = v_normalize(v_cross(e[5], e[4]));                                  // up face
+    PcvShapeWide* w = s->wide;
+    w->naxes = cache_axes_for_aabb(w->axes, PCV_WIDE_AXES, e, 12, n, 6);
+    for (int a = 0; a < w->naxes; ++a)
+      project8(s->corners, V3d{w->axes[3 * a], w->axes[3 * a + 1], w->axes[3 * a + 2]}, &w->amin[a], &w->amax[a]);
+    s->naxes = 0;
   } else {
     s->naxes = 0;  // AllPoints
   }
@@ -245,6 +286,7 @@ __device__ __forceinline__ void sat_axis_interval(double lx, double hx, double l
     bmax = fmax(fmax(fmax(fmax(fmax(fmax(fmax(fmax(-1.7976931348623157e308, c0), c1), c2), c3), c4), c5), c6), c7);
   }
 }
+template <bool WIDE = false>
 __device__ __forceinline__ int sat_cube(const PcvShapeDev* __restrict__ s, double mnx, double mny, double mnz, double edge) {
   if (s->kind == PCV_SHAPE_ALL) return 1;  // AllPoints intersects everything (math/mod.rs:139-160) -> "not Out"
   // Cube::to_aabb: Aabb::new(min, min + edge) (inf / sup)
@@ -253,11 +295,14 @@ __device__ __forceinline__ int sat_cube(const PcvShapeDev* __restrict__ s, doubl
   const double ly = fmin(mny, ay_), hy = fmax(mny, ay_);
   const double lz = fmin(mnz, az_), hz = fmax(mnz, az_);
   bool cross = false;
-  const int na = s->naxes;
+  const int na = WIDE ? s->wide->naxes : s->naxes;
+  const double* axes = WIDE ? s->wide->axes : s->axes;
+  const double* amins = WIDE ? s->wide->amin : s->amin;
+  const double* amaxs = WIDE ? s->wide->amax : s->amax;
   for (int a = 0; a < na; ++a) {
     double bmin, bmax, mag;
-    sat_axis_interval(lx, hx, ly, hy, lz, hz, s->axes[3 * a], s->axes[3 * a + 1], s->axes[3 * a + 2], bmin, bmax, mag);
-    const double amin = s->amin[a], amax = s->amax[a];
+    sat_axis_interval(lx, hx, ly, hy, lz, hz, axes[3 * a], axes[3 * a + 1], axes[3 * a + 2], bmin, bmax, mag);
+    const double amin = amins[a], amax = amaxs[a];
     if (bmin > amax || bmax < amin) return 2;
     cross = cross || (amin > bmin || bmax > amax);
   }
@@ -293,16 +338,18 @@ __device__ double size_on_screen(const double* __restrict__ m, double mnx, doubl
   return (hix - lox) * (hiy - loy);
 }
 
-// K7: grid.y = shape, grid.x covers the nodes.
+// K7: grid.y = shape, grid.x covers the nodes. WIDE: the web-mercator rectangles only, with their own axes.
+template <bool WIDE = false>
 __global__ __launch_bounds__(256) void cull_nodes_kernel(const PcvShapeDev* __restrict__ shapes, uint32_t m,
                                                           const double* __restrict__ cubes /* m x 4 */,
                                                           uint8_t* __restrict__ relation, double* __restrict__ sizes) {
   const PcvShapeDev* s = shapes + blockIdx.y;
+  if (WIDE && s->kind != PCV_SHAPE_WEB_MERCATOR_RECT) return;
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= m) return;
   const double4 c = *reinterpret_cast<const double4*>(cubes + 4 * (uint64_t)i);
   const uint64_t o = (uint64_t)blockIdx.y * m + i;
-  relation[o] = s->valid ? (uint8_t)sat_cube(s, c.x, c.y, c.z, c.w) : (uint8_t)2;
+  relation[o] = s->valid ? (uint8_t)sat_cube<WIDE>(s, c.x, c.y, c.z, c.w) : (uint8_t)2;
   if (sizes) sizes[o] = size_on_screen(s->clip_from_query, c.x, c.y, c.z, c.w);
 }
 
@@ -311,14 +358,16 @@ __global__ __launch_bounds__(256) void cull_nodes_kernel(const PcvShapeDev* __re
 // its 546 MB on the way to the host. One workgroup per shape walks the node table in tiles of 256 and appends the nodes
 // that are not Out IN NODE ORDER: {node index, relation, relative_size_on_screen} — the size is computed for those only,
 // which is exactly where the reference computes it (octree/mod.rs:261-272: a node is projected when it is pushed).
+template <bool WIDE = false>  // WIDE: every web-mercator rectangle (no `redo`), with its own axes
 __global__ __launch_bounds__(256) void cull_nodes_sparse_kernel(const PcvShapeDev* __restrict__ shapes, uint32_t m,
                                                                  const double* __restrict__ cubes /* m x 4 */, uint32_t capacity,
                                                                  uint32_t* __restrict__ counts, uint32_t* __restrict__ out_node,
                                                                  uint8_t* __restrict__ out_rel, double* __restrict__ out_size,
                                                                  const uint32_t* __restrict__ redo /* set: only the flagged shapes */) {
   __shared__ uint32_t wave_tot[4];
-  if (redo && !redo[blockIdx.x]) return;  // (uniform) the tree walk finished this shape
+  if (!WIDE && redo && !redo[blockIdx.x]) return;  // (uniform) the tree walk finished this shape
   const PcvShapeDev* s = shapes + blockIdx.x;
+  if (WIDE && s->kind != PCV_SHAPE_WEB_MERCATOR_RECT) return;
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint64_t row = (uint64_t)blockIdx.x * capacity;
   uint32_t base = 0;  // entries of this shape so far (uniform)
@@ -329,7 +378,7 @@ __global__ __launch_bounds__(256) void cull_nodes_sparse_kernel(const PcvShapeDe
     int rel = 2;
     if (i < m && valid) {
       c = *reinterpret_cast<const double4*>(cubes + 4 * (uint64_t)i);
-      rel = sat_cube(s, c.x, c.y, c.z, c.w);
+      rel = sat_cube<WIDE>(s, c.x, c.y, c.z, c.w);
     }
     const bool keep = rel != 2;
     const uint64_t b = __ballot(keep);
@@ -745,7 +794,8 @@ __global__ __launch_bounds__(256) void visible_nodes_kernel(const PcvShapeDev* _
   }
 }
 
-// K7c: BFS of NodeIdsIterator; queue in global scratch.
+// K7c: BFS of NodeIdsIterator; queue in global scratch. WIDE: every web-mercator rectangle (no `redo`), with its own axes.
+template <bool WIDE = false>
 __global__ __launch_bounds__(64) void nodes_in_location_kernel(const PcvShapeDev* __restrict__ shapes, uint32_t first_shape,
                                                                 uint32_t nshapes, QTree t, const double* __restrict__ fb_cubes,
                                                                 uint32_t* __restrict__ queues, uint32_t capacity,
@@ -755,8 +805,9 @@ __global__ __launch_bounds__(64) void nodes_in_location_kernel(const PcvShapeDev
   const uint32_t li = blockIdx.x * 64 + threadIdx.x;
   if (li >= nshapes) return;
   const uint32_t f = first_shape + li;
-  if (redo && !redo[f]) return;  // the wave-per-shape walk finished this one
+  if (!WIDE && redo && !redo[f]) return;  // the wave-per-shape walk finished this one
   const PcvShapeDev* s = shapes + f;
+  if (WIDE && s->kind != PCV_SHAPE_WEB_MERCATOR_RECT) return;
   uint32_t* q = queues + (uint64_t)li * t.m;
   uint32_t* o = out + (rows ? rows[f] : (uint64_t)f * capacity);
   if (rows) capacity = (uint32_t)(rows[f + 1] - rows[f]);
@@ -765,7 +816,7 @@ __global__ __launch_bounds__(64) void nodes_in_location_kernel(const PcvShapeDev
   while (head < tail) {
     const uint32_t cur = q[head++];
     const double* cb = fb_cubes + 4 * (uint64_t)cur;  // NodeMeta::bounding_cube = find_bounding_cube (octree/mod.rs:205)
-    if (sat_cube(s, cb[0], cb[1], cb[2], cb[3]) == 2) continue;
+    if (sat_cube<WIDE>(s, cb[0], cb[1], cb[2], cb[3]) == 2) continue;
     const uint32_t mask = t.child_mask[cur];
     uint32_t cidx = t.first_child[cur];
     for (uint32_t ci = 0; ci < 8; ++ci)
@@ -782,7 +833,7 @@ __global__ __launch_bounds__(64) void nodes_in_location_kernel(const PcvShapeDev
 // are compiled per KIND (PCV_SHAPE_FRUSTUM stands for both frustum kinds), so the inner loops carry no shape switch.
 template <int KIND>
 struct ContainParams {
-  double p[KIND == PCV_SHAPE_FRUSTUM ? 16 : KIND == PCV_SHAPE_OBB ? 10 : KIND == PCV_SHAPE_AABB ? 6 : 1];
+  double p[KIND == PCV_SHAPE_FRUSTUM ? 16 : KIND == PCV_SHAPE_OBB ? 10 : KIND == PCV_SHAPE_AABB ? 6 : KIND == PCV_SHAPE_WEB_MERCATOR_RECT ? 4 : 1];
 };
 template <int KIND>
 __device__ __forceinline__ ContainParams<KIND> load_contain(const PcvShapeDev* __restrict__ shape) {
@@ -801,6 +852,11 @@ __device__ __forceinline__ ContainParams<KIND> load_contain(const PcvShapeDev* _
     for (int i = 0; i < 7; ++i) c.p[i] = shape->iso[i];
 #pragma unroll
     for (int i = 0; i < 3; ++i) c.p[7 + i] = shape->half[i];
+  } else if (KIND == PCV_SHAPE_WEB_MERCATOR_RECT) {  // north_west in bmin[0..1], south_east in bmax[0..1]
+    c.p[0] = shape->bmin[0];
+    c.p[1] = shape->bmin[1];
+    c.p[2] = shape->bmax[0];
+    c.p[3] = shape->bmax[1];
   } else {
     c.p[0] = 0.0;
   }
@@ -817,6 +873,8 @@ __device__ __forceinline__ bool shape_contains(const ContainParams<KIND>& s, V3d
   } else if (KIND == PCV_SHAPE_OBB) {  // obb.rs:83-90
     const V3d q = v_add(quat_rotate(s.p + 3, p), V3d{s.p[0], s.p[1], s.p[2]});
     return fabs(q.x) <= s.p[7] && fabs(q.y) <= s.p[8] && fabs(q.z) <= s.p[9];
+  } else if (KIND == PCV_SHAPE_WEB_MERCATOR_RECT) {  // web_mercator_rect.rs:121-127: the chain of pcv_wmr_dev.h
+    return wmr::contains(s.p, p.x, p.y, p.z);
   }
   return true;  // AllPoints
 }
@@ -827,6 +885,7 @@ __device__ __forceinline__ bool shape_contains(const ContainParams<KIND>& s, V3d
     case PCV_SHAPE_FRUSTUM:                                            \
     case PCV_SHAPE_FRUSTUM_WITH_INVERSE: CALL(PCV_SHAPE_FRUSTUM); break; \
     case PCV_SHAPE_OBB: CALL(PCV_SHAPE_OBB); break;                    \
+    case PCV_SHAPE_WEB_MERCATOR_RECT: CALL(PCV_SHAPE_WEB_MERCATOR_RECT); break; \
     default: CALL(PCV_SHAPE_ALL); break;                               \
   }
 
@@ -957,20 +1016,65 @@ __device__ __forceinline__ uint32_t staged_keep_enc(const ContainParams<KIND>& s
   }
   return tot;
 }
+// The same for a web-mercator rectangle. The test is some hundreds of f64 operations per point (three atan2, two sin / cos,
+// a ln, a sqrt and nine divisions), so the kernel is bound by the f64 pipe, not by HBM: the decode is the (wave-uniform) switch
+// and the chain exists ONCE in the instance — not once per encoding and unrolled ballot, which would be 16 copies of it.
+__device__ __forceinline__ uint32_t staged_keep_wmr(const ContainParams<PCV_SHAPE_WEB_MERCATOR_RECT>& shape, const uint4* stage,
+                                                    uint32_t skew, uint32_t enc, const double* cube_min, double cube_edge,
+                                                    uint32_t cnt, const float* __restrict__ attr, double lo, double hi,
+                                                    uint32_t lane, uint8_t* __restrict__ keep) {
+  const uint8_t* bytes = reinterpret_cast<const uint8_t*>(stage) + skew;
+  uint32_t tot = 0;
+  for (uint32_t g0 = 0; g0 < cnt; g0 += kGroup) {
+    unsigned long long b[4] = {0, 0, 0, 0};
+#pragma unroll 1
+    for (uint32_t r = 0; r < 4; ++r) {
+      const uint32_t q = g0 + r * 64 + lane;
+      bool k = false;
+      if (q < cnt) {
+        V3d p;
+        switch (enc) {  // wave-uniform
+          case PCV_ENC_UINT8: p = staged_point<PCV_ENC_UINT8>(bytes + q * 3u, cube_min, cube_edge); break;
+          case PCV_ENC_UINT16: p = staged_point<PCV_ENC_UINT16>(bytes + q * 6u, cube_min, cube_edge); break;
+          case PCV_ENC_FLOAT32: p = staged_point<PCV_ENC_FLOAT32>(bytes + q * 12u, cube_min, cube_edge); break;
+          default: p = staged_point<PCV_ENC_FLOAT64>(bytes + q * 24u, cube_min, cube_edge); break;
+        }
+        k = true;
+        if (attr) {  // iterator.rs:82-91 + math/mod.rs:86-88 — first: a point outside the interval skips the chain
+          const double a = (double)attr[q];
+          k = lo <= a && a <= hi;
+        }
+        if (k) k = wmr::contains(shape.p, p.x, p.y, p.z);
+      }
+      const unsigned long long bal = __ballot(k);
+      b[0] = r == 0 ? bal : b[0];
+      b[1] = r == 1 ? bal : b[1];
+      b[2] = r == 2 ? bal : b[2];
+      b[3] = r == 3 ? bal : b[3];
+    }
+    store_keep(keep + g0, cnt - g0, b, lane);
+    tot += (uint32_t)(__popcll(b[0]) + __popcll(b[1]) + __popcll(b[2]) + __popcll(b[3]));
+  }
+  return tot;
+}
 template <int KIND>
 __device__ __forceinline__ uint32_t staged_keep(const ContainParams<KIND>& shape, const uint4* stage, uint32_t skew,
                                                 uint32_t enc, const double* cube_min, double cube_edge, uint32_t cnt,
                                                 const float* __restrict__ attr, double lo, double hi, uint32_t lane,
                                                 uint8_t* __restrict__ keep) {
-  switch (enc) {  // wave-uniform
-    case PCV_ENC_UINT8:
-      return staged_keep_enc<KIND, PCV_ENC_UINT8>(shape, stage, skew, cube_min, cube_edge, cnt, attr, lo, hi, lane, keep);
-    case PCV_ENC_UINT16:
-      return staged_keep_enc<KIND, PCV_ENC_UINT16>(shape, stage, skew, cube_min, cube_edge, cnt, attr, lo, hi, lane, keep);
-    case PCV_ENC_FLOAT32:
-      return staged_keep_enc<KIND, PCV_ENC_FLOAT32>(shape, stage, skew, cube_min, cube_edge, cnt, attr, lo, hi, lane, keep);
-    default:
-      return staged_keep_enc<KIND, PCV_ENC_FLOAT64>(shape, stage, skew, cube_min, cube_edge, cnt, attr, lo, hi, lane, keep);
+  if constexpr (KIND == PCV_SHAPE_WEB_MERCATOR_RECT) {
+    return staged_keep_wmr(shape, stage, skew, enc, cube_min, cube_edge, cnt, attr, lo, hi, lane, keep);
+  } else {
+    switch (enc) {  // wave-uniform
+      case PCV_ENC_UINT8:
+        return staged_keep_enc<KIND, PCV_ENC_UINT8>(shape, stage, skew, cube_min, cube_edge, cnt, attr, lo, hi, lane, keep);
+      case PCV_ENC_UINT16:
+        return staged_keep_enc<KIND, PCV_ENC_UINT16>(shape, stage, skew, cube_min, cube_edge, cnt, attr, lo, hi, lane, keep);
+      case PCV_ENC_FLOAT32:
+        return staged_keep_enc<KIND, PCV_ENC_FLOAT32>(shape, stage, skew, cube_min, cube_edge, cnt, attr, lo, hi, lane, keep);
+      default:
+        return staged_keep_enc<KIND, PCV_ENC_FLOAT64>(shape, stage, skew, cube_min, cube_edge, cnt, attr, lo, hi, lane, keep);
+    }
   }
 }
 
@@ -1116,6 +1220,12 @@ __device__ __forceinline__ uint32_t query_keep_chunk(const PcvShapeDev* __restri
   const BatchIval iv = ivals[s];
   const float* attr = iv.used ? inten_blob + d.attr_index : nullptr;
   uint8_t* kp = keep + d.keep_off;
+  // A web-mercator rectangle has its own instance only. In a mixed batch (KIND < 0) the chain stays out of the instance the other
+  // kinds run in, whose code is what it was: to it such a chunk is the default case (every flag 1), and query_flags_wmr_kernel,
+  // launched behind it on the same stream, stages the chunk again and overwrites its flags and its count.
+  if constexpr (KIND == PCV_SHAPE_WEB_MERCATOR_RECT)
+    return staged_keep<PCV_SHAPE_WEB_MERCATOR_RECT>(load_contain<PCV_SHAPE_WEB_MERCATOR_RECT>(sh), stage, skew, enc, d.cube_min,
+                                                    d.cube_edge, d.cnt, attr, iv.lo, iv.hi, lane, kp);
   switch (kind) {
     case PCV_SHAPE_AABB:
       return staged_keep<PCV_SHAPE_AABB>(load_contain<PCV_SHAPE_AABB>(sh), stage, skew, enc, d.cube_min, d.cube_edge, d.cnt, attr,
@@ -1164,6 +1274,31 @@ __global__ __launch_bounds__(256) void query_flags_kernel(const PcvShapeDev* __r
     c = cn;
     d = dn;
     dn = dnn;
+  }
+}
+
+// The web-mercator chunks of a mixed batch: query_flags_kernel<-1> treated them as AllPoints chunks (their bytes are read twice,
+// 3..24 B per point against the chain's 358 f64 instructions); this kernel, behind it on the stream, overwrites flags and counts. A wave per chunk, grid-stride, the other kinds' chunks skipped at the cost of their descriptor's scalar load. No prefetch of the next chunk: the f64 work of a chunk
+// (some 10^5 operations per wave) dwarfs its 6 KiB of loads, and the waves of a SIMD overlap the rest.
+__global__ __launch_bounds__(256) void query_flags_wmr_kernel(const PcvShapeDev* __restrict__ shapes, const BatchIval* __restrict__ ivals,
+                                                               const ChunkDesc* __restrict__ desc, uint32_t nchunks,
+                                                               const uint8_t* __restrict__ xyz_blob, const float* __restrict__ inten_blob,
+                                                               uint8_t* __restrict__ keep, uint32_t* __restrict__ chunk_counts) {
+  __shared__ uint4 stage_all[4][kStageSlots];
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  uint4* stage = stage_all[wave];
+  const uint32_t nwaves = gridDim.x * 4;
+  for (uint32_t c = blockIdx.x * 4 + wave; c < nchunks; c += nwaves) {
+    const ChunkDesc d = desc[c];  // wave-uniform: scalar loads
+    if (((d.enc >> 4) & 15u) != (uint32_t)PCV_SHAPE_WEB_MERCATOR_RECT) continue;
+    const StageRegs sr = stage_issue(xyz_blob, d.src, d.cnt * enc_stride(d.enc & 15u), lane);
+    stage_commit(sr, stage, lane);
+    const uint32_t tot =
+        query_keep_chunk<PCV_SHAPE_WEB_MERCATOR_RECT>(shapes + (d.enc >> 8), ivals + (d.enc >> 8), d, stage, sr.skew, inten_blob, keep, lane);
+    if (lane == 0) chunk_counts[c] = tot;
+    // the LDS slice is rewritten by the next commit: every lane must be done reading it
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
   }
 }
 
@@ -1329,6 +1464,19 @@ int launch_query_flags(pcv_ctx* ctx, int32_t kind, const PcvShapeDev* shapes, co
   return PCV_OK;
 }
 
+// the web-mercator chunks of a mixed batch, after launch_query_flags(kind < 0) on the same stream
+int launch_query_flags_wmr(pcv_ctx* ctx, const PcvShapeDev* shapes, const BatchIval* ivals, const ChunkDesc* desc, uint32_t nchunks,
+                           const pcv_octree* tree, uint8_t* keep, uint32_t* chunk_counts) {
+  int cus = 0, per_cu = 0;
+  PCV_HIP_CHECK(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+  PCV_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, query_flags_wmr_kernel, 256, 0));
+  const uint32_t nb = (uint32_t)std::min<uint64_t>((nchunks + 3ull) / 4, (uint64_t)std::max(cus, 1) * (uint64_t)std::max(per_cu, 1));
+  hipLaunchKernelGGL(query_flags_wmr_kernel, dim3(nb), dim3(256), 0, ctx->stream, shapes, ivals, desc, nchunks, tree->d_xyz,
+                     (const float*)tree->d_int, keep, chunk_counts);
+  PCV_HIP_CHECK(ctx, hipGetLastError());
+  return PCV_OK;
+}
+
 // the kept points of the chunks [c0, c1), which start at scanned offset `base`, the first `np` of them, into the caller's host
 // or device buffers; `label` names the compaction in the profile
 int compact_chunks(pcv_ctx* ctx, int label, const pcv_octree* tree, const ChunkDesc* desc, const uint8_t* keep, const uint64_t* chunk_off,
@@ -1390,6 +1538,7 @@ extern "C" int pcv_shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t
   *out = nullptr;
   PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   std::vector<PcvShapeDev> h(count);
+  std::vector<uint32_t> wide_of;  // the shapes with a PcvShapeWide
   for (uint32_t i = 0; i < count; ++i) {
     const pcv_shape& s = shapes[i];
     PcvShapeDev& d = h[i];
@@ -1416,6 +1565,14 @@ extern "C" int pcv_shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t
         for (int a = 0; a < 7; ++a) d.iso[a] = s.params[a];
         for (int a = 0; a < 3; ++a) d.half[a] = s.params[7 + a];
         break;
+      case PCV_SHAPE_WEB_MERCATOR_RECT:  // the corners on the host (libm), everything after them on the device
+        d.bmin[0] = s.params[0];
+        d.bmin[1] = s.params[1];
+        d.bmax[0] = s.params[2];
+        d.bmax[1] = s.params[3];
+        if (pcv_wmr_corners(s.params, d.corners) != PCV_OK) return ctx->fail(PCV_E_INVALID, "web-mercator rectangle: corners");
+        wide_of.push_back(i);
+        break;
       default: return ctx->fail(PCV_E_INVALID, "unknown shape kind");
     }
   }
@@ -1432,6 +1589,17 @@ extern "C" int pcv_shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t
     return rc;
   }
   r->dev = (PcvShapeDev*)p;
+  if (!wide_of.empty()) {
+    if ((rc = ctx->dev_alloc(&p, sizeof(PcvShapeWide) * wide_of.size()))) {
+      ctx->dev_free(r->dev);
+      delete r;
+      return rc;
+    }
+    r->wide = (PcvShapeWide*)p;
+    for (size_t w = 0; w < wide_of.size(); ++w) {
+      h[wide_of[w]].wide = r->wide + w;
+    }
+  }
   if (count) {
     hipError_t e = hipMemcpyAsync(r->dev, h.data(), sizeof(PcvShapeDev) * count, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
@@ -1439,6 +1607,7 @@ extern "C" int pcv_shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t
       e = hipStreamSynchronize(ctx->stream);  // `h` must outlive the copy
     }
     if (e != hipSuccess) {
+      if (r->wide) ctx->dev_free(r->wide);
       ctx->dev_free(r->dev);
       delete r;
       return ctx->fail(PCV_E_HIP, hipGetErrorString(e));
@@ -1450,6 +1619,7 @@ extern "C" int pcv_shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t
 
 extern "C" void pcv_shapes_free(pcv_shapes* s) {
   if (!s) return;
+  if (s->wide) s->ctx->dev_free(s->wide);
   s->ctx->dev_free(s->dev);
   delete s;
 }
@@ -1459,12 +1629,44 @@ extern "C" uint32_t pcv_shapes_count(const pcv_shapes* s) { return s ? s->count 
 extern "C" int pcv_shapes_get(pcv_shapes* s, uint32_t i, double corners[24], double axes[78], uint32_t* num_axes,
                               int* valid) {
   if (!s || i >= s->count) return PCV_E_INVALID;
+  if (s->kinds[i] != PCV_SHAPE_WEB_MERCATOR_RECT) {  // (all 78 doubles, as ever)
+    pcv_ctx* ctx = s->ctx;
+    PcvShapeDev h;
+    PCV_HIP_CHECK(ctx, hipMemcpy(&h, s->dev + i, sizeof(h), hipMemcpyDeviceToHost));
+    if (corners) std::memcpy(corners, h.corners, sizeof(h.corners));
+    if (axes) std::memcpy(axes, h.axes, sizeof(h.axes));
+    if (num_axes) *num_axes = (uint32_t)h.naxes;
+    if (valid) *valid = h.valid;
+    return PCV_OK;
+  }
+  uint32_t na = 0;
+  double wide_axes[3 * PCV_WIDE_AXES];
+  const int rc = pcv_shapes_get_ex(s, i, corners, wide_axes, PCV_WIDE_AXES, &na, valid);
+  if (rc) return rc;
+  if (na > PCV_MAX_AXES) return s->ctx->fail(PCV_E_INVALID, "shape has more than 26 axes: use pcv_shapes_get_ex");
+  if (axes) std::memcpy(axes, wide_axes, sizeof(double) * 3 * na);
+  if (num_axes) *num_axes = na;
+  return PCV_OK;
+}
+
+extern "C" int pcv_shapes_get_ex(pcv_shapes* s, uint32_t i, double corners[24], double* axes, uint32_t axes_capacity,
+                                 uint32_t* num_axes, int* valid) {
+  if (!s || i >= s->count) return PCV_E_INVALID;
   pcv_ctx* ctx = s->ctx;
+  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   PcvShapeDev h;
   PCV_HIP_CHECK(ctx, hipMemcpy(&h, s->dev + i, sizeof(h), hipMemcpyDeviceToHost));
   if (corners) std::memcpy(corners, h.corners, sizeof(h.corners));
-  if (axes) std::memcpy(axes, h.axes, sizeof(h.axes));
-  if (num_axes) *num_axes = (uint32_t)h.naxes;
+  uint32_t na = (uint32_t)h.naxes;
+  const double* src = h.axes;
+  PcvShapeWide w;
+  if (h.kind == PCV_SHAPE_WEB_MERCATOR_RECT) {
+    PCV_HIP_CHECK(ctx, hipMemcpy(&w, h.wide, sizeof(w), hipMemcpyDeviceToHost));
+    na = (uint32_t)w.naxes;
+    src = w.axes;
+  }
+  if (axes) std::memcpy(axes, src, sizeof(double) * 3 * std::min(na, axes_capacity));
+  if (num_axes) *num_axes = na;
   if (valid) *valid = h.valid;
   return PCV_OK;
 }
@@ -1600,8 +1802,11 @@ extern "C" int pcv_cull_nodes(pcv_ctx* ctx, const pcv_shapes* shapes, pcv_octree
     PcvProf prof(ctx, PCV_K_CULL_NODES);
     // cull against NodeMeta cubes (find_bounding_cube), as nodes_in_location does; get_visible_nodes' own
     // get_child cubes differ at most in the sign of zero
-    hipLaunchKernelGGL(cull_nodes_kernel, dim3((m + 255) / 256, f), dim3(256), 0, ctx->stream, shapes->dev, m,
+    hipLaunchKernelGGL(cull_nodes_kernel<false>, dim3((m + 255) / 256, f), dim3(256), 0, ctx->stream, shapes->dev, m,
                        tree->query->fb_cubes, d_rel, d_sz);
+    if (shapes->wide)  // the web-mercator rectangles' rows, over what the launch above wrote for them
+      hipLaunchKernelGGL(cull_nodes_kernel<true>, dim3((m + 255) / 256, f), dim3(256), 0, ctx->stream, shapes->dev, m,
+                         tree->query->fb_cubes, d_rel, d_sz);
   }
   PCV_HIP_CHECK(ctx, hipGetLastError());
   PCV_HIP_CHECK(ctx, hipMemcpyAsync(relation, d_rel, (size_t)f * m, hipMemcpyDeviceToHost, ctx->stream));
@@ -1650,8 +1855,11 @@ extern "C" int pcv_cull_nodes_sparse(pcv_ctx* ctx, const pcv_shapes* shapes, pcv
                            tree->query->first_child, tree->query->child_mask, capacity, d_cnt, d_node, d_rel, d_sz, d_redo,
                            (const uint64_t*)nullptr);
     }
-    hipLaunchKernelGGL(cull_nodes_sparse_kernel, dim3(f), dim3(256), 0, ctx->stream, shapes->dev, m, tree->query->fb_cubes, capacity, d_cnt,
+    hipLaunchKernelGGL(cull_nodes_sparse_kernel<false>, dim3(f), dim3(256), 0, ctx->stream, shapes->dev, m, tree->query->fb_cubes, capacity, d_cnt,
                        d_node, d_rel, d_sz, flat_only ? (const uint32_t*)nullptr : (const uint32_t*)d_redo);
+    if (shapes->wide)  // the web-mercator rectangles' lists and counts, over what the launches above wrote for them
+      hipLaunchKernelGGL(cull_nodes_sparse_kernel<true>, dim3(f), dim3(256), 0, ctx->stream, shapes->dev, m, tree->query->fb_cubes, capacity,
+                         d_cnt, d_node, d_rel, d_sz, (const uint32_t*)nullptr);
   }
 #ifdef PCV_EXPERIMENTS
   if (!flat_only && pcv_experiment("PCV_CULL_DEBUG")) {  // how many shapes the tree walk handed to the flat kernel
@@ -1714,8 +1922,12 @@ static int traverse(pcv_ctx* ctx, const pcv_shapes* shapes, pcv_octree* tree, ui
       hipLaunchKernelGGL(visible_nodes_kernel, dim3((nb + 3) / 4), dim3(256), 0, ctx->stream, shapes->dev, first, nb, qt,
                          (HeapEntry*)scratch, capacity, d_counts, d_out, d_status);
     else
-      hipLaunchKernelGGL(nodes_in_location_kernel, dim3((nb + 63) / 64), dim3(64), 0, ctx->stream, shapes->dev, first, nb,
+      hipLaunchKernelGGL(nodes_in_location_kernel<false>, dim3((nb + 63) / 64), dim3(64), 0, ctx->stream, shapes->dev, first, nb,
                          qt, tree->query->fb_cubes, (uint32_t*)scratch, capacity, d_counts, d_out, (const uint32_t*)d_redo,
+                         (const uint64_t*)nullptr);
+    if (!visible && shapes->wide)  // the web-mercator rectangles' lists and counts, over what the launches above wrote for them
+      hipLaunchKernelGGL(nodes_in_location_kernel<true>, dim3((nb + 63) / 64), dim3(64), 0, ctx->stream, shapes->dev, first, nb,
+                         qt, tree->query->fb_cubes, (uint32_t*)scratch, capacity, d_counts, d_out, (const uint32_t*)nullptr,
                          (const uint64_t*)nullptr);
   }
   PCV_HIP_CHECK(ctx, hipGetLastError());
@@ -1918,8 +2130,12 @@ static int query_points_impl(pcv_ctx* ctx, const pcv_shapes* shapes, uint32_t sh
   if ((rc = sc.get(&d_rel, m))) return rc;
   {
     PcvProf prof(ctx, PCV_K_CULL_NODES);
-    hipLaunchKernelGGL(cull_nodes_kernel, dim3((m + 255) / 256, 1), dim3(256), 0, ctx->stream, shapes->dev + shape_index, m,
-                       tree->query->fb_cubes, d_rel, (double*)nullptr);
+    if (shapes->kinds[shape_index] == PCV_SHAPE_WEB_MERCATOR_RECT)
+      hipLaunchKernelGGL(cull_nodes_kernel<true>, dim3((m + 255) / 256, 1), dim3(256), 0, ctx->stream, shapes->dev + shape_index, m,
+                         tree->query->fb_cubes, d_rel, (double*)nullptr);
+    else
+      hipLaunchKernelGGL(cull_nodes_kernel<false>, dim3((m + 255) / 256, 1), dim3(256), 0, ctx->stream, shapes->dev + shape_index, m,
+                         tree->query->fb_cubes, d_rel, (double*)nullptr);
   }
   std::vector<uint8_t> rel(m);
   PCV_HIP_CHECK(ctx, hipMemcpyAsync(rel.data(), d_rel, m, hipMemcpyDeviceToHost, ctx->stream));
@@ -2163,8 +2379,13 @@ static int query_batch_run(pcv_ctx* ctx, const pcv_shapes* shapes, pcv_octree* t
     hipLaunchKernelGGL((cull_nodes_tree_kernel<false, true>), dim3((S + 3) / 4), dim3(256), 0, ctx->stream, shapes->dev, S, m, q->fb_cubes,
                        q->first_child, q->child_mask, capacity, d_cnt, out, (uint8_t*)nullptr, (double*)nullptr, d_redo, rows);
     for (uint32_t first = 0; first < S; first += fb_batch)
-      hipLaunchKernelGGL(nodes_in_location_kernel, dim3((std::min(fb_batch, S - first) + 63) / 64), dim3(64), 0, ctx->stream, shapes->dev,
+      hipLaunchKernelGGL(nodes_in_location_kernel<false>, dim3((std::min(fb_batch, S - first) + 63) / 64), dim3(64), 0, ctx->stream, shapes->dev,
                          first, std::min(fb_batch, S - first), qt, q->fb_cubes, d_queues, capacity, d_cnt, out, (const uint32_t*)d_redo, rows);
+    if (shapes->wide)  // the web-mercator rectangles' lists and counts, over what the launches above wrote for them
+      for (uint32_t first = 0; first < S; first += fb_batch)
+        hipLaunchKernelGGL(nodes_in_location_kernel<true>, dim3((std::min(fb_batch, S - first) + 63) / 64), dim3(64), 0, ctx->stream,
+                           shapes->dev, first, std::min(fb_batch, S - first), qt, q->fb_cubes, d_queues, capacity, d_cnt, out,
+                           (const uint32_t*)nullptr, rows);
   };
   auto scan = [&](const uint32_t* in, uint64_t n, uint64_t* out) {
     PcvProf prof(ctx, PCV_K_QUERY_BATCH_SCAN);
@@ -2225,6 +2446,9 @@ static int query_batch_run(pcv_ctx* ctx, const pcv_shapes* shapes, pcv_octree* t
     // 3. keep flags
     PcvProf prof(ctx, PCV_K_QUERY_BATCH_FLAGS);
     if ((rc = launch_query_flags(ctx, -1, shapes->dev, d_iv, desc, (uint32_t)nchunks, tree, b->d_keep, d_cc))) return rc;
+    if (std::find(shapes->kinds.begin(), shapes->kinds.end(), (int32_t)PCV_SHAPE_WEB_MERCATOR_RECT) != shapes->kinds.end() &&
+        (rc = launch_query_flags_wmr(ctx, shapes->dev, d_iv, desc, (uint32_t)nchunks, tree, b->d_keep, d_cc)))
+      return rc;
   }
   // 4. kept points per chunk -> u64 offsets; segment offsets from the first chunk of each segment
   if ((rc = scan(d_cc, nchunks, b->d_chunk_off))) return rc;

@@ -303,11 +303,13 @@ class Context:
 
     def shapes(self, shapes):
         """Prepare query shapes on the device. Each entry: ("all",), ("aabb", min3, max3), ("frustum", clip_from_query16),
-        ("frustum2", clip_from_query16, query_from_clip16), ("obb", translation3, quat_ijkw4, half_extent3)."""
+        ("frustum2", clip_from_query16, query_from_clip16), ("obb", translation3, quat_ijkw4, half_extent3),
+        ("web_mercator_rect", north_west2, south_east2) — normalised map coordinates, as web_mercator_rect_from_zoomed
+        returns them; the query space is ECEF."""
         arr = (L.Shape * max(1, len(shapes)))()
         for i, sh in enumerate(shapes):
             kind = {"all": L.SHAPE_ALL, "aabb": L.SHAPE_AABB, "frustum": L.SHAPE_FRUSTUM, "obb": L.SHAPE_OBB,
-                    "frustum2": L.SHAPE_FRUSTUM_WITH_INVERSE}[sh[0]]
+                    "frustum2": L.SHAPE_FRUSTUM_WITH_INVERSE, "web_mercator_rect": L.SHAPE_WEB_MERCATOR_RECT}[sh[0]]
             arr[i].kind = kind
             flat = [float(v) for part in sh[1:] for v in np.asarray(part, dtype=np.float64).ravel()]
             for j, v in enumerate(flat):
@@ -746,9 +748,9 @@ class Shapes:
         ctx._children.add(self)
 
     def get(self, i):
-        corners, axes = (C.c_double * 24)(), (C.c_double * 78)()
+        corners, axes = (C.c_double * 24)(), (C.c_double * (3 * L.MAX_SHAPE_AXES))()
         n, valid = C.c_uint32(), C.c_int()
-        self.ctx._check(self.ctx.lib.pcv_shapes_get(self.handle, i, corners, axes, C.byref(n), C.byref(valid)))
+        self.ctx._check(self.ctx.lib.pcv_shapes_get_ex(self.handle, i, corners, axes, L.MAX_SHAPE_AXES, C.byref(n), C.byref(valid)))
         return np.array(corners[:]).reshape(8, 3), np.array(axes[:3 * n.value]).reshape(n.value, 3), bool(valid.value)
 
     def free(self):
@@ -1223,6 +1225,90 @@ def xray_finalize(fn, values):
     if rc != L.PCV_OK:
         raise L.PcvError(rc, f"pcv_xray_finalize({fn})")
     return out
+
+
+def web_mercator_rect_from_zoomed(min_xy, max_xy, z):
+    """WebMercatorRect::from_zoomed_coordinates (host only): ("web_mercator_rect", north_west, south_east) for
+    Context.shapes, or None where the reference returns None."""
+    mn, mx = (C.c_double * 2)(*[float(v) for v in min_xy]), (C.c_double * 2)(*[float(v) for v in max_xy])
+    out = (C.c_double * 4)()
+    if int(z) < 0 or L.load_library().pcv_wmr_from_zoomed(mn, mx, int(z), out) != L.PCV_OK:
+        return None
+    return ("web_mercator_rect", np.array(out[0:2]), np.array(out[2:4]))
+
+
+def _wmr_params(rect):
+    if isinstance(rect, tuple) and rect and rect[0] == "web_mercator_rect":
+        rect = rect[1:]
+    return (C.c_double * 4)(*[float(v) for part in rect for v in np.asarray(part, dtype=np.float64).ravel()])
+
+
+def _wmr_xyz(x, y, z):
+    x, y, z = (np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (x, y, z))
+    if not (x.size == y.size == z.size):
+        raise ValueError("x, y, z differ in length")
+    return x, y, z
+
+
+def wmr_corners(rect):
+    """pcv_wmr_corners (host only): the (8, 3) ECEF corners of a rectangle's polyhedron, in the reference's order."""
+    out = (C.c_double * 24)()
+    rc = L.load_library().pcv_wmr_corners(_wmr_params(rect), out)
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, "pcv_wmr_corners")
+    return np.array(out[:]).reshape(8, 3)
+
+
+def wmr_project(x, y, z):
+    """pcv_wmr_project (host only): normalised web-mercator (u, v) of ECEF points, the chain the device runs."""
+    x, y, z = _wmr_xyz(x, y, z)
+    u, v = np.zeros(x.size), np.zeros(x.size)
+    rc = L.load_library().pcv_wmr_project(x.size, x.ctypes.data, y.ctypes.data, z.ctypes.data, u.ctypes.data, v.ctypes.data)
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, "pcv_wmr_project")
+    return u, v
+
+
+def wmr_contains(rect, x, y, z):
+    """pcv_wmr_contains (host only): WebMercatorRect::contains per ECEF point, as uint8 flags."""
+    x, y, z = _wmr_xyz(x, y, z)
+    keep = np.zeros(x.size, dtype=np.uint8)
+    rc = L.load_library().pcv_wmr_contains(_wmr_params(rect), x.size, x.ctypes.data, y.ctypes.data, z.ctypes.data, keep.ctypes.data)
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, "pcv_wmr_contains")
+    return keep
+
+
+def wmr_from_lat_lng(lat, lng):
+    """WebMercatorCoord::from_lat_lng (radians) with the library's own sin / ln: (u, v)."""
+    lat, lng = (np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (lat, lng))
+    u, v = np.zeros(lat.size), np.zeros(lat.size)
+    rc = L.load_library().pcv_wmr_from_lat_lng(lat.size, lat.ctypes.data, lng.ctypes.data, u.ctypes.data, v.ctypes.data)
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, "pcv_wmr_from_lat_lng")
+    return u, v
+
+
+def wmr_to_lat_lng(u, v):
+    """WebMercatorCoord::to_lat_lng: (latitude, longitude) in radians."""
+    u, v = (np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (u, v))
+    lat, lng = np.zeros(u.size), np.zeros(u.size)
+    rc = L.load_library().pcv_wmr_to_lat_lng(u.size, u.ctypes.data, v.ctypes.data, lat.ctypes.data, lng.ctypes.data)
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, "pcv_wmr_to_lat_lng")
+    return lat, lng
+
+
+def wmr_math(fn, a, b=None):
+    """pcv_wmr_math (tests): the chain's own atan2(a, b), (sin a, cos a) or ln a."""
+    a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+    b = np.ascontiguousarray(b, dtype=np.float64).ravel() if b is not None else None
+    out, out2 = np.zeros(a.size), np.zeros(a.size)
+    rc = L.load_library().pcv_wmr_math(int(fn), a.size, a.ctypes.data, b.ctypes.data if b is not None else None, out.ctypes.data,
+                                       out2.ctypes.data)
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, "pcv_wmr_math")
+    return (out, out2) if int(fn) == L.WMR_FN_SINCOS else out
 
 
 def xray_lanczos_taps(tile_size_px):

@@ -380,7 +380,8 @@ impl HipOctree {
 
     /// PointLocation -> pcv_shape (include/pcv_hip.h). None: a location the library has no kernel for.
     /// Needs `Frustum::clip_from_query()/query_from_clip()` and `Obb::query_from_obb()/half_extent()` accessors on
-    /// the reference types (their fields are private; INTEGRATION.md lists the four one-liners).
+    /// the reference types (their fields are private; INTEGRATION.md lists the four one-liners), and
+    /// `WebMercatorRect::north_west()/south_east()` (two more).
     fn shape_of(location: &PointLocation) -> Option<PcvShape> {
         let mut s = PcvShape { kind: 0, reserved: 0, params: [0.0; 32] };
         match location {
@@ -403,7 +404,15 @@ impl HipOctree {
                 s.params[3..7].copy_from_slice(&[q.x, q.y, q.z, q.w]); // i j k w
                 s.params[7..10].copy_from_slice(&[h.x, h.y, h.z]);
             }
-            PointLocation::S2Cells(_) | PointLocation::WebMercatorRect(_) => return None,
+            PointLocation::WebMercatorRect(r) => {
+                // PCV_SHAPE_WEB_MERCATOR_RECT: the two normalized coordinates. WebMercatorCoord's field is private too, but
+                // to_zoomed_coordinate(0) is 256 * normalized (web_mercator.rs:70-78) and a division by 256 undoes it exactly.
+                s.kind = 5;
+                let nw = r.north_west().to_zoomed_coordinate(0)? / 256.0;
+                let se = r.south_east().to_zoomed_coordinate(0)? / 256.0;
+                s.params[..4].copy_from_slice(&[nw.x, nw.y, se.x, se.y]);
+            }
+            PointLocation::S2Cells(_) => return None, // needs the s2 crate's cell unions: no kernel
         }
         Some(s)
     }
