@@ -39,82 +39,6 @@ void* PcvPool::alloc(size_t bytes, hipError_t* err) {
     return p;
   }
   void* p = nullptr;
-#ifdef PCV_EXPERIMENTS  // placement experiments (profiles/r05_placement_probe.json): neither helps, neither ships
-  // PCV_POOL_VMM=<chunk MiB> (libpcv_hip_exp.so, tools/placement_probe.py): big blocks assembled from physical chunks of that
-  // size mapped in a scrambled order. The scatter kernels of the build run 1.0-1.25 ms on whatever hipMalloc returns and
-  // 1.36-1.53 ms on physically CONTIGUOUS memory (PCV_POOL_CONTIG=1): their 131 072 write streams meet in the same
-  // memory channels when the physical addresses follow the virtual ones too regularly.
-  static const size_t vmm_chunk = [] {
-    const char* e = pcv_experiment("PCV_POOL_VMM");
-    return e ? (size_t)std::max(0, atoi(e)) << 20 : (size_t)0;
-  }();
-  if (vmm_chunk && bytes >= (64u << 20)) {
-    hipMemAllocationProp prop = {};
-    prop.type = hipMemAllocationTypePinned;
-    prop.location.type = hipMemLocationTypeDevice;
-    prop.location.id = device;
-    size_t gran = 0;
-    if (hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended) == hipSuccess && gran) {
-      const size_t chunk = (vmm_chunk + gran - 1) / gran * gran;
-      const size_t size = (bytes + chunk - 1) / chunk * chunk;
-      const size_t nchunks = size / chunk;
-      void* va = nullptr;
-      PcvVmmBlock blk;
-      blk.size = size;
-      bool ok = hipMemAddressReserve(&va, size, 0, nullptr, 0) == hipSuccess;
-      for (size_t k = 0; ok && k < nchunks; ++k) {
-        hipMemGenericAllocationHandle_t h;
-        ok = hipMemCreate(&h, chunk, &prop, 0) == hipSuccess;
-        if (ok) blk.handles.push_back(h);
-      }
-      if (ok) {
-        // slot k of the address range gets chunk perm(k): a multiplicative scramble (odd multiplier modulo a power of two,
-        // values past nchunks skipped) — deterministic, no two slots share a chunk
-        size_t pow2 = 1;
-        while (pow2 < nchunks) pow2 <<= 1;
-        size_t slot = 0;
-        for (size_t v = 0; ok && v < pow2; ++v) {
-          const size_t c = (v * 0x9E3779B1ull + 12345u) & (pow2 - 1);
-          if (c >= nchunks) continue;
-          ok = hipMemMap((char*)va + slot * chunk, chunk, 0, blk.handles[c], 0) == hipSuccess;
-          ++slot;
-        }
-        ok = ok && slot == nchunks;
-      }
-      if (ok) {
-        hipMemAccessDesc ad = {};
-        ad.location.type = hipMemLocationTypeDevice;
-        ad.location.id = device;
-        ad.flags = hipMemAccessFlagsProtReadWrite;
-        ok = hipMemSetAccess(va, size, &ad, 1) == hipSuccess;
-      }
-      if (ok) {
-        vmm[va] = blk;
-        live[va] = bytes;
-        return va;
-      }
-      (void)hipGetLastError();
-      if (va) {
-        (void)hipMemUnmap(va, size);
-        for (auto h : blk.handles) (void)hipMemRelease(h);
-        (void)hipMemAddressFree(va, size);
-      }
-    }
-  }
-  // PCV_POOL_CONTIG=1 (libpcv_hip_exp.so, tools/placement_probe.py): big blocks asked for as physically contiguous memory
-  static const bool contig = [] {
-    const char* e = pcv_experiment("PCV_POOL_CONTIG");
-    return e && atoi(e) != 0;
-  }();
-  if (contig && bytes >= (8u << 20)) {
-    if (hipExtMallocWithFlags(&p, bytes, hipDeviceMallocContiguous) == hipSuccess) {
-      live[p] = bytes;
-      return p;
-    }
-    (void)hipGetLastError();
-    p = nullptr;
-  }
-#endif
   *err = hipMalloc(&p, bytes);
   if (*err != hipSuccess) {
     // drop the cache and retry once
@@ -132,19 +56,8 @@ void PcvPool::release(void* p) {
   free_blocks.insert({it->second, p});
   live.erase(it);
 }
-void PcvPool::free_block(void* p) {
-  auto it = vmm.find(p);
-  if (it == vmm.end()) {
-    (void)hipFree(p);
-    return;
-  }
-  (void)hipMemUnmap(p, it->second.size);
-  for (auto h : it->second.handles) (void)hipMemRelease(h);
-  (void)hipMemAddressFree(p, it->second.size);
-  vmm.erase(it);
-}
 void PcvPool::trim() {
-  for (auto& kv : free_blocks) free_block(kv.second);
+  for (auto& kv : free_blocks) (void)hipFree(kv.second);
   free_blocks.clear();
 }
 
@@ -292,7 +205,6 @@ int pcv_ctx::ring_ensure() {
   unsigned hw = std::thread::hardware_concurrency();
   // copies into pinned memory saturate the link with 7 threads; preads from a file (pcv_build_octree_from_ply) want more
   unsigned workers = hw >= 64 ? 15 : (hw >= 16 ? 7 : (hw > 2 ? hw / 2 - 1 : 0));
-  if (const char* e = pcv_experiment("PCV_H2D_THREADS")) workers = (unsigned)std::max(0, atoi(e));
   host_pool.start(workers);
   return PCV_OK;
 }
@@ -307,39 +219,20 @@ int pcv_ctx::h2d_fill(void* dst, size_t bytes, const std::function<bool(uint8_t*
   const size_t nworkers = host_pool.threads.size() + 1;
   const size_t kPart = std::max<size_t>(256u << 10, ((kRingChunk + nworkers - 1) / nworkers + 4095) & ~(size_t)4095);
   std::atomic<int> bad{0};
-#ifdef PCV_EXPERIMENTS
-  static const bool trace = pcv_experiment("PCV_H2D_TRACE") != nullptr;
-  double t_wait = 0, t_fill = 0, t_issue = 0;
-  const auto t_begin = std::chrono::steady_clock::now();
-#define PCV_H2D_T(acc, stmt)                                                                          \
-  {                                                                                                   \
-    const auto t0_ = std::chrono::steady_clock::now();                                                \
-    stmt;                                                                                             \
-    acc += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0_).count(); \
-  }
-#else
-#define PCV_H2D_T(acc, stmt) stmt;
-#endif
   for (size_t off = 0; off < bytes; off += kRingChunk) {
     const size_t len = bytes - off < kRingChunk ? bytes - off : kRingChunk;
     const int slot = ring_take();
-    if (ring_busy[slot]) PCV_H2D_T(t_wait, PCV_HIP_CHECK(this, hipEventSynchronize(ring_ev[slot])))  // its previous DMA has left the chunk
+    if (ring_busy[slot]) PCV_HIP_CHECK(this, hipEventSynchronize(ring_ev[slot]));  // its previous DMA has left the chunk
     uint8_t* chunk = (uint8_t*)ring[slot];
-    PCV_H2D_T(t_fill, host_pool.run((len + kPart - 1) / kPart, [&](size_t p) {
+    host_pool.run((len + kPart - 1) / kPart, [&](size_t p) {
       const size_t b = p * kPart, e = b + kPart < len ? b + kPart : len;
       if (!fill(chunk + b, off + b, e - b)) bad.store(1);
-    }))
+    });
     if (bad.load()) return fail(PCV_E_IO, "reading the source of a host-to-device copy failed");
-    PCV_H2D_T(t_issue, PCV_HIP_CHECK(this, hipMemcpyAsync((uint8_t*)dst + off, chunk, len, hipMemcpyHostToDevice, stream));
-              PCV_HIP_CHECK(this, hipEventRecord(ring_ev[slot], stream)))
+    PCV_HIP_CHECK(this, hipMemcpyAsync((uint8_t*)dst + off, chunk, len, hipMemcpyHostToDevice, stream));
+    PCV_HIP_CHECK(this, hipEventRecord(ring_ev[slot], stream));
     ring_busy[slot] = true;
   }
-#undef PCV_H2D_T
-#ifdef PCV_EXPERIMENTS
-  if (trace)
-    fprintf(stderr, "[pcv h2d] %.1f MB: total %.2f ms (waiting for a ring slot %.2f, filling %.2f, issuing %.2f)\n", bytes / 1e6,
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(), t_wait, t_fill, t_issue);
-#endif
   return PCV_OK;
 }
 
@@ -418,7 +311,6 @@ extern "C" int pcv_ctx_create(int device, void* stream, pcv_ctx** out) {
   if (hipSetDevice(device) != hipSuccess) return PCV_E_HIP;
   pcv_ctx* c = new pcv_ctx();
   c->device = device;
-  c->pool.device = device;
   if (hipHostMalloc((void**)&c->mailbox, 136 * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess) {
     delete c;
     return PCV_E_OOM;
@@ -467,9 +359,7 @@ extern "C" void pcv_ctx_destroy(pcv_ctx* ctx) {
   (void)hipStreamSynchronize(ctx->stream);
   ctx->pool.trim();
   {
-    std::vector<void*> still;
-    for (auto& kv : ctx->pool.live) still.push_back(kv.first);
-    for (void* q : still) ctx->pool.free_block(q);
+    for (auto& kv : ctx->pool.live) (void)hipFree(kv.first);
   }
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);
   if (ctx->pinned_spec) (void)hipHostFree(ctx->pinned_spec);
@@ -596,11 +486,7 @@ int pcv_make_levels(const double bmin[3], const double bmax[3], double resolutio
       tame = tame && lv->inv_edge[j] != 0.0;
       // pcv_digit_from_codes: valid where 1.01 u (2.5 A / e + 3) < 1 / (2 M) (u = 2^-53); required here with a factor
       // of two in hand. Level 0 has no codes (the chain starts from the raw position).
-      static const bool digit_shortcut = [] {  // PCV_DIGIT_SHORTCUT=0: always compare against the centre (experiments)
-        const char* ev = pcv_experiment("PCV_DIGIT_SHORTCUT");
-        return !ev || atoi(ev) != 0;
-      }();
-      if (digit_shortcut && j >= 1 && (c[j] == PCV_ENC_UINT8 || c[j] == PCV_ENC_UINT16) && std::isfinite(amax) && e[j] > 0.0) {
+      if (j >= 1 && (c[j] == PCV_ENC_UINT8 || c[j] == PCV_ENC_UINT16) && std::isfinite(amax) && e[j] > 0.0) {
         const double m = c[j] == PCV_ENC_UINT8 ? 255.0 : 65535.0;
         if ((2.5 * amax / e[j] + 3.0) * 4.04 * m < 0x1p+53) {
           lv->digit_half[j] = c[j] == PCV_ENC_UINT8 ? 127.0 : 32767.0;
@@ -609,7 +495,7 @@ int pcv_make_levels(const double bmin[3], const double bmax[3], double resolutio
       }
       // pcv_f32 codes (pcv_chain_dev.h, pcv_bits_from_codes / pcv_f32_code_tie): the same inequality with M = 2^24 — the
       // floats next to 1/2 are 2^-25 away; only the single chain pass looks at digit_mode
-      if (digit_shortcut && j >= 1 && c[j] == PCV_ENC_FLOAT32 && std::isfinite(amax) && e[j] > 0.0 &&
+      if (j >= 1 && c[j] == PCV_ENC_FLOAT32 && std::isfinite(amax) && e[j] > 0.0 &&
           (2.5 * amax / e[j] + 3.0) * 4.04 * 0x1p+24 < 0x1p+53) {
         lv->digit_half[j] = 0.5;
         lv->digit_mode[j] = 2;
@@ -625,13 +511,9 @@ int pcv_make_levels(const double bmin[3], const double bmax[3], double resolutio
     // w are at least thr 2^-24 away. The table stores the high word of the smallest such thr with a factor of two in hand;
     // steps whose thr would exceed 2^-8 are not admitted (most waves would hold a code below it).
     {
-      static const bool code_steps = [] {  // PCV_CODE_STEPS=0: every level step in full (experiments)
-        const char* ev = pcv_experiment("PCV_CODE_STEPS");
-        return !ev || atoi(ev) != 0;
-      }();
       const int none = 1 << 20;  // "no such step"
       int cb = none, ce = none;
-      if (code_steps && tame && std::isfinite(amax) && amax > 0.0) {
+      if (pcv_switches().code_steps && tame && std::isfinite(amax) && amax > 0.0) {
         const double H = std::ldexp(1.0, std::ilogb(amax * (1.0 + 0x1p-40)) - 52);
         for (int j = 1; j + 1 <= filled && j + 1 < (int)e.size() && j <= PCV_MAX_KEY_LEVELS; ++j) {
           if (c[j] != PCV_ENC_FLOAT32 || c[j + 1] != PCV_ENC_FLOAT32 || lv->digit_mode[j] != 2 || !(e[j + 1] > 0.0)) continue;
@@ -763,7 +645,6 @@ static int stage_points(pcv_ctx* ctx, PcvScratch& sc, const pcv_points* p, bool 
   return PCV_OK;
 }
 
-static void host_lap(const char* what, bool reset = false);
 // K1 in two halves, so that the caller can do host work (allocations) while the reduction runs.
 // The final kernel stores the six doubles straight into the pinned mailbox (host memory the device can write), which holds a
 // sentinel until then: the host polls the mailbox instead of waiting for the stream — the blocked wait of a stream synchronize
@@ -791,24 +672,16 @@ static int device_aabb_launch(pcv_ctx* ctx, PcvScratch& sc, const DevPoints& d) 
   return PCV_OK;
 }
 static int device_aabb_wait(pcv_ctx* ctx, double bmin[3], double bmax[3]) {
-  static const bool poll_on = [] {
-    const char* e = pcv_experiment("PCV_AABB_POLL");  // experiments: 0 = wait for the stream
-    return !e || atoi(e) != 0;
-  }();
-  host_lap("", true);
   volatile uint64_t* box = ctx->mailbox;
   bool seen = false;
-  if (poll_on) {
-    for (uint32_t spin = 0; !seen; ++spin) {
-      seen = true;
-      for (int a = 0; a < 6; ++a) seen = seen && box[a] != kAabbSentinel;
-      // every few thousand reads: is the stream still alive? (a failed launch would never deliver)
-      if (!seen && (spin & 0xfff) == 0xfff && hipStreamQuery(ctx->stream) != hipErrorNotReady) break;
-    }
-    __atomic_thread_fence(__ATOMIC_SEQ_CST);
+  for (uint32_t spin = 0; !seen; ++spin) {
+    seen = true;
+    for (int a = 0; a < 6; ++a) seen = seen && box[a] != kAabbSentinel;
+    // every few thousand reads: is the stream still alive? (a failed launch would never deliver)
+    if (!seen && (spin & 0xfff) == 0xfff && hipStreamQuery(ctx->stream) != hipErrorNotReady) break;
   }
+  __atomic_thread_fence(__ATOMIC_SEQ_CST);
   if (!seen) PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  host_lap("bbox: wait");
   double h[6];
   std::memcpy(h, ctx->mailbox, sizeof(h));
   for (int a = 0; a < 3; ++a) {
@@ -1073,29 +946,10 @@ extern "C" int pcv_build_begin_routed(pcv_ctx* ctx, const pcv_build_params* para
 // keys_a, payload in bs->spec_payload, intensity bits in the second half of keys_a) are what K5 would have produced and
 // `tt` is the node table K4 would have produced. *used == false: the prediction did not cover the tree (or the sample
 // says the tree is deeper than one key word): the caller runs the exact pipeline; nothing of this attempt is kept.
-// PCV_HOST_TIMING=1: host-side lap times of the single-chain build's critical section (counts on the host -> first
-// sort kernel queued), printed to stderr
-#include <atomic>
-#include <chrono>
-static void host_lap(const char* what, bool reset) {
-  static const bool on = pcv_experiment("PCV_HOST_TIMING") != nullptr;
-  static std::chrono::steady_clock::time_point t0;
-  if (!on) return;
-  const auto now = std::chrono::steady_clock::now();
-  if (!reset) fprintf(stderr, "[host] %-24s %8.1f us\n", what, std::chrono::duration<double, std::micro>(now - t0).count());
-  t0 = now;
-}
 
 // The record sort's second pass settles the leaves' points itself (PcvSortFuse) where it can: the pass is held back until the
-// node tables are on the device. PCV_SETTLE_IN_SORT=0 (libpcv_hip_exp.so): the sort runs to its end, `settle` reads the records.
-static bool pcv_settle_in_sort() {
-  static const bool on = [] {
-    const char* e = pcv_experiment("PCV_SETTLE_IN_SORT");
-    const char* l = pcv_experiment("PCV_SETTLE_BY_LEAF");
-    return (!e || atoi(e) != 0) && (!l || atoi(l) != 0) && pcv_climb16_enabled();
-  }();
-  return on;
-}
+// node tables are on the device. Otherwise the sort runs to its end and `settle` reads the records.
+static bool pcv_settle_in_sort() { return pcv_switches().settle_in_sort && pcv_switches().settle_by_leaf; }
 
 // K5 (exact pipeline only: `wt` set) + K3 stable record sort by leaf rank, queued on the stream; the outcome is left in
 // the build state for K6. num_leaves only sizes the digits: any upper bound of the number of true leaves will do.
@@ -1223,7 +1077,6 @@ static int single_chain_topology(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, cons
   // 96 -> 5.02 / 4.97 / 4.95-4.98 / 4.96 ms per build — the sample phase shrinks by 0.07 ms, 1.5 M more points continue
   // their chain in the settle pass, the prediction holds either way (profiles/r05_ab_sample_stride.json)
   uint64_t stride = 64;
-  if (const char* e = pcv_experiment("PCV_SPEC_STRIDE")) stride = (uint64_t)std::max(1, atoi(e));  // experiments
   while (stride > 1 && n / stride < 4096) stride >>= 1;
   // a node at the capacity must still hold a few dozen sample points, or the band around the capacity (five standard
   // deviations of the scaled count) swallows every node and the prediction opens all of them (tiny capacities in tests)
@@ -1252,17 +1105,9 @@ static int single_chain_topology(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, cons
   uint8_t* d_slevel;
   // the sample tree straight from the sorted sample keys (pcv_launch_spec_sample_tree: two launches); the split into a node
   // table + spec_tree_scan / emit (fifteen launches for the 100 M bench cloud) stays in the experiment library
-  // (PCV_SAMPLE_TREE_SPLIT=1, or PCV_SPLIT2=0 for the one-level split kernels) — same T'' either way
-  static const bool tree_by_split = [] {
-    const char* e = pcv_experiment("PCV_SAMPLE_TREE_SPLIT");
-    const char* e2 = pcv_experiment("PCV_SPLIT2");
-    return (e && atoi(e) != 0) || (e2 && atoi(e2) == 0);
-  }();
-#ifdef PCV_EXPERIMENTS
-  const bool table_tree = true;  // (the sample tree by counting, below, builds a node table as well)
-#else
-  const bool table_tree = tree_by_split;
-#endif
+  // (sample_tree_split, or the one-level split kernels) — same T'' either way
+  const bool tree_by_split = pcv_switches().sample_tree_split || !pcv_switches().split2;
+  const bool table_tree = tree_by_split || pcv_switches().sample_counts;  // (the sample tree by counting builds a node table as well)
   uint64_t* d_open = nullptr;  // the open sample nodes (at most nt.capacity: T'' holds 1 + 8 x that many nodes)
   d_ord = nullptr;
   if ((!tree_by_split && (rc = sc.get(&d_open, nt.capacity))) || (table_tree && (rc = sc.get(&d_ord, nt.capacity)))) return rc;
@@ -1273,15 +1118,11 @@ static int single_chain_topology(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, cons
   d_counts = d_pool_ctr + kPcvPoolRegions;  // the pool counters and the exact counts travel to the host in ONE copy
   uint32_t* rank = (uint32_t*)bs->keys_a;
   uint4* payload;
-  // 12-byte records (pcv_internal.h) unless switched off (PCV_COMPACT_RECORDS=0, experiments) or the predicted tree could
-  // outgrow the 24 rank bits of the key
-  static const bool compact_on = [] {
-    const char* e = pcv_experiment("PCV_COMPACT_RECORDS");
-    return !e || atoi(e) != 0;
-  }();
+  // 12-byte records (pcv_internal.h) unless switched off (experiments) or the predicted tree could outgrow the 24 rank
+  // bits of the key
   // ... or the pool of Float32 codes (kPcvPoolRegions regions, pcv_internal.h) could outgrow 32-bit entry numbers
   const uint64_t pool_cap = pcv_pool_region_entries(n), pool_entries = pool_cap * kPcvPoolRegions;
-  const bool compact = compact_on && tcap <= (1u << 24) && pool_entries <= 0xffffffffull;
+  const bool compact = pcv_switches().compact_records && tcap <= (1u << 24) && pool_entries <= 0xffffffffull;
   uint4* wide = nullptr;
   uint64_t wide_levels = 0;
   for (int k = 0; k <= full_levels && k < 64; ++k)
@@ -1317,7 +1158,6 @@ static int single_chain_topology(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, cons
     int uniform = 0;
     for (uint64_t per_node = n / (uint64_t)max_points + 1; per_node > 1; per_node = (per_node + 7) / 8) ++uniform;
     sample_levels = std::min(14, std::max(10, uniform + 8));
-    if (const char* e = pcv_experiment("PCV_SAMPLE_LEVELS")) sample_levels = std::max(1, atoi(e));
     if (sample_levels > full_levels) sample_levels = full_levels;
   }
   for (;;) {
@@ -1333,64 +1173,31 @@ static int single_chain_topology(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, cons
     }
     // The sample is taken in clumps of 8 consecutive points (one clump every 8 x stride): read one by one, every
     // sampled coordinate costs a full cache line (1.2 GB and 0.23 ms for the 3.1 M sample points of a 100 M cloud)
-    static const uint32_t clump_shift = [] {
-      const char* e = pcv_experiment("PCV_SAMPLE_CLUMP_SHIFT");  // experiments: 0 = single points
-      return e ? (uint32_t)std::min(6, std::max(0, atoi(e))) : 3u;
-    }();
-    size_t one_zero_words = 0, one_words = 0;
-#ifdef PCV_EXPERIMENTS
-    uint32_t* one = nullptr;  // (scratch of the one-launch-per-digit key sort: libpcv_hip_exp.so, PCV_SAMPLE_ONESWEEP=1; pcv_sort.hip)
-    static const bool onesweep_on = [] {
-      const char* e = pcv_experiment("PCV_SAMPLE_ONESWEEP");
-      return e && atoi(e) != 0;
-    }();
-    const int sbits = 3 * sample_levels;
-    if (onesweep_on && pcv_onesweep_fits(ns, sbits)) {
-      one_words = pcv_onesweep_scratch_words(ns, sbits) + 4;
-      one_zero_words = pcv_onesweep_zero_words(ns, sbits);
-    }
-#endif
-    // cleared by the chain-keys launch on its way: [64 words: the counters of the sample tree kernels][the onesweep scratch]
+    constexpr uint32_t clump_shift = 3;
+    // cleared by the chain-keys launch on its way: 64 words, the counters of the sample tree kernels
     uint32_t* zero;
-    if ((rc = sc.get(&zero, 64 + one_words))) return rc;
-#ifdef PCV_EXPERIMENTS
-    if (one_words) one = zero + 64;
-#endif
-    host_lap("bbox -> sample keys");
-    pcv_launch_chain_keys(ctx, lv, ns, stride, d.x, d.y, d.z, skeys_a, false, d.routed, stride > 1 ? clump_shift : 0u, zero, 64 + one_zero_words);
+    if ((rc = sc.get(&zero, 64))) return rc;
+    pcv_launch_chain_keys(ctx, lv, ns, stride, d.x, d.y, d.z, skeys_a, false, d.routed, stride > 1 ? clump_shift : 0u, zero, 64);
     bool in_a = true;
-    host_lap("", true);
-    // PCV_SAMPLE_COUNTS=1 (libpcv_hip_exp.so only): the sample tree by COUNTING the keys, three levels per launch pair
+    // sample_counts (libpcv_hip_exp.so only): the sample tree by COUNTING the keys, three levels per launch pair
     // (pcv_topology.hip): 9 launches instead of 27 and no sort — and 2-3 x SLOWER, measured: the 1.5 M keys cost 4.7 M
     // device-scope atomics per group of levels and this part retires ~9 G of those per second (0.54 + 0.38 ms for the two
     // middle groups against 0.28 ms for the whole key sort + split; profiles/r05_ab_sample_tree_by_counting_dropped.json)
     const uint32_t thr_s = pcv_spec_sample_threshold(sp);
     bool counted = false;
 #ifdef PCV_EXPERIMENTS
-    static const bool counts_on = [] {
-      const char* e = pcv_experiment("PCV_SAMPLE_COUNTS");
-      return e && atoi(e) != 0;
-    }();
-    if (counts_on && thr_s > 0 && nt.max_open >= ns / thr_s + 16 && sample_levels <= PCV_MAX_KEY_LEVELS) {
+    if (pcv_switches().sample_counts && thr_s > 0 && nt.max_open >= ns / thr_s + 16 && sample_levels <= PCV_MAX_KEY_LEVELS) {
       if (!d_sample_counts && (rc = sc.get(&d_sample_counts, pcv_sample_count_scratch_words(nt.capacity, nt.max_open, full_levels)))) return rc;
       // (a count only matters up to the larger of the split threshold and the candidate band's upper end)
       const double sat_d = std::fmax((double)thr_s, std::ceil(upper)) + 2.0;
       const uint32_t sat = sat_d >= 4294967000.0 ? 0xfffffff0u : (uint32_t)sat_d;
       pcv_launch_sample_tree_counts(ctx, nt, skeys_a, (uint32_t)ns, lv, params->resolution, thr_s, sp.force_mask, d_sample_counts, sat);
-      host_lap("sample tree (counting) queued");
       counted = true;
     }
 #endif
-    if (!counted) {
-#ifdef PCV_EXPERIMENTS
-    if (one) rc = pcv_sort_keys_onesweep(ctx, skeys_a, skeys_b, ns, 3 * (PCV_MAX_KEY_LEVELS - sample_levels), 3 * PCV_MAX_KEY_LEVELS, one, &in_a);
-    else
-#endif
-      rc = pcv_radix_sort_u64(ctx, skeys_a, skeys_b, ns, 3 * (PCV_MAX_KEY_LEVELS - sample_levels), 3 * PCV_MAX_KEY_LEVELS, nullptr,
-                                 bs->sort_scratch, &in_a);
-    if (rc) return rc;
-    host_lap("sample sort queued");
-    }
+    if (!counted && (rc = pcv_radix_sort_u64(ctx, skeys_a, skeys_b, ns, 3 * (PCV_MAX_KEY_LEVELS - sample_levels), 3 * PCV_MAX_KEY_LEVELS,
+                                             nullptr, bs->sort_scratch, &in_a)))
+      return rc;
     if (!counted && !tree_by_split) {
       if ((rc = pcv_launch_spec_sample_tree(ctx, in_a ? skeys_a : skeys_b, (uint32_t)ns, lv, params->resolution, thr_s, upper, sp.force_mask,
                                             d_open, nt.capacity, zero, d_walk, d_sparent, d_slevel, d_info, d_pool_ctr)))
@@ -1398,11 +1205,9 @@ static int single_chain_topology(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, cons
     } else {
       if (!counted) {
         pcv_launch_node_split(ctx, nt, in_a ? skeys_a : skeys_b, false, (uint32_t)ns, lv, params->resolution, thr_s, sp.force_mask);
-        host_lap("sample split queued");
       }
       pcv_launch_spec_tree(ctx, nt, upper, sp.force_mask, d_ord, d_walk, d_sparent, d_slevel, d_info, d_pool_ctr);
     }
-    host_lap("spec tree queued");
     uint8_t* hs = (uint8_t*)ctx->pinned_spec;
     const size_t first = tcap < kFirst ? tcap : kFirst;
     // The host's mirror of the tree and the zeroed counters travel on the side stream: on `stream` each of these small
@@ -1415,16 +1220,12 @@ static int single_chain_topology(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, cons
     // ---- the one chain pass (queued before the host has seen the tree) ----
     ctx->stage_begin(PCV_STAGE_LEAF_ENCODE);
     lv.nlevels = full_levels;
-    // round 6, measured and NOT shipped (PCV_COLOR_LATE=1, libpcv_hip_exp.so; profiles/r06_ab_colour_joins_in_the_sort_dropped.json):
+    // round 6, measured and NOT shipped (color_late, libpcv_hip_exp.so; profiles/r06_ab_colour_joins_in_the_sort_dropped.json):
     // the 12-byte records leave the pass without their colour and the record sort's first pass — which reads every record in
     // input order anyway — fetches it from the caller's array. The chain pass gains 0.13 ms (1.86 -> 1.73 at 100 M points), the
     // sort's first pass loses 0.31 (0.59 -> 0.90): eight more (unaligned) loads per lane on top of its sixteen — that pass is
     // bound by the issue of its vector-memory instructions, not by bytes. Same octree either way.
-    static const bool color_late_on = [] {
-      const char* e = pcv_experiment("PCV_COLOR_LATE");
-      return e && atoi(e) != 0;
-    }();
-    bs->color_late = color_late_on && compact;
+    bs->color_late = pcv_switches().color_late && compact;
     // the exact counters (d_counts) are cleared by the depth-grid kernel in front of the pass where there is one; small builds
     // clear them with a fill on `stream`
     const size_t counts_words = (tcap + 3) & ~(size_t)3;
@@ -1434,7 +1235,6 @@ static int single_chain_topology(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, cons
                            inten_bits, depth_grid, wide, d_pool_ctr /* zeroed by the spec_tree kernels */, d_info, bs->color_late,
                            zero_in_grid ? d_counts : nullptr, zero_in_grid ? counts_words : 0);
     ctx->stage_end(PCV_STAGE_LEAF_ENCODE);
-    host_lap("chain pass queued");
 
     PCV_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->side, ctx->side_fork, 0));
     PCV_HIP_CHECK(ctx, hipMemcpyAsync(hs, d_info, 16, hipMemcpyDeviceToHost, ctx->side));
@@ -1479,13 +1279,9 @@ static int single_chain_topology(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, cons
   // (up to 16 384 nodes: clouds of up to ~250 M points at the default capacity):
   // the count runs over the record sort's own workgroups and keeps every workgroup's histogram, from which the sort's first
   // pass derives its digit histogram (the keys are then read by its downsweep only, which applies the map itself).
-  // PCV_SORT_ROWS=0 (libpcv_hip_exp.so): the first pass counts (and maps) the keys in a pass of its own.
-  static const bool rows_on = [] {
-    const char* e = pcv_experiment("PCV_SORT_ROWS");
-    return !e || atoi(e) != 0;
-  }();
+  // sort_rows off (libpcv_hip_exp.so): the first pass counts (and maps) the keys in a pass of its own.
   bs->spec_rows = nullptr;
-  if (rows_on && compact && tree.num_leaves <= pcv_rank_hist_max_bins()) {
+  if (pcv_switches().sort_rows && compact && tree.num_leaves <= pcv_rank_hist_max_bins()) {
     int sgroups;
     uint64_t schunk;
     pcv_sort_rec12_geometry(n, &sgroups, &schunk);
@@ -1505,7 +1301,6 @@ static int single_chain_topology(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, cons
   // block on the device, one copy (every small operation on `stream` costs a hand-over of ~10 us between two kernels)
   uint32_t* h_pool = (uint32_t*)hp;
   uint32_t* h_counts = h_pool + kPcvPoolRegions;
-  const size_t map_off = (((size_t)kPcvPoolRegions + tree.num_leaves) * 4 + 255) & ~(size_t)255;
   // (the copy travels on the side stream, behind an event of `stream`: a copy command between the count and the resolve kernel costs
   // `stream` two hand-overs of ~10 us; nothing queued on `stream` later writes these counters)
   if (ctx->side_begin() != PCV_OK) return ctx->fail(PCV_E_HIP, "single-chain build: side stream");
@@ -1514,11 +1309,7 @@ static int single_chain_topology(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, cons
   // The map the record sort needs is computed on the device (spec_resolve_kernel), and the sort is queued behind it right
   // away: the counts' trip to the host, the host's own resolve and the table building all happen beside the sort instead
   // of in front of it. The sort's digit widths come from the number of PREDICTED leaves (an upper bound of the true
-  // leaves, known since the host mirrored T''). PCV_DEVICE_RESOLVE=0 (libpcv_hip_exp.so): the map comes from the host.
-  static const bool device_resolve = [] {
-    const char* e = pcv_experiment("PCV_DEVICE_RESOLVE");
-    return !e || atoi(e) != 0;
-  }();
+  // leaves, known since the host mirrored T'').
   bs->spec_wide = wide;
   bs->wide_levels = wide_levels;
   bs->spec_map_dev = d_map;
@@ -1557,7 +1348,7 @@ static int single_chain_topology(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, cons
       ctx->dev_free(wide);
     }
   };
-  if (device_resolve) {
+  {
     uint32_t *d_nst, *d_base, *d_out;
     const uint32_t tn = (uint32_t)tree.prefix.size();
     if ((rc = sc.get(&d_nst, tn)) || (rc = sc.get(&d_base, tn))) return rc;
@@ -1576,12 +1367,9 @@ static int single_chain_topology(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, cons
     ctx->stage_end(PCV_STAGE_NODE_SPLIT);
     const uint32_t predicted_leaves = (uint32_t)std::count(tree.inner.begin(), tree.inner.end(), (uint8_t)0);
     if ((rc = queue_record_sort(ctx, bs, t, nullptr, predicted_leaves, false))) return rc;
-    host_lap("record sort queued");
   }
   PCV_HIP_CHECK(ctx, hipEventSynchronize(ctx->spec_ev));
-  host_lap("", true);
   const PcvSpecStatus resolved = pcv_spec_resolve(sp, tree, h_counts, tt);
-  host_lap("resolve");
   if (resolved != PCV_SPEC_OK) {
     give_up();
     return PCV_OK;  // *used stays false
@@ -1614,16 +1402,6 @@ static int single_chain_topology(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, cons
   bs->cont_from = tt->cont_from;
   // leaves whose points still have to replay the chain: contiguous once the records are sorted ([lo, hi) of the leaf)
   for (uint32_t k : tt->fix_nodes) bs->fix_ranges.push_back({tt->lo[k], tt->hi[k] - tt->lo[k], (uint32_t)tt->level[k]});
-  if (!device_resolve) {
-    // the host's map goes up and is applied by the first upsweep of the record sort; no synchronisation: the upload reads
-    // ctx->pinned_spec, the caller stages the node table in ctx->pinned
-    std::memcpy(hp + map_off, tt->spec_map.data(), (size_t)tree.num_leaves * 4);
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_map, hp + map_off, (size_t)tree.num_leaves * 4, hipMemcpyHostToDevice, st));
-    ctx->stage_end(PCV_STAGE_NODE_SPLIT);
-    host_lap("map upload, fix ranges");
-    if ((rc = queue_record_sort(ctx, bs, t, nullptr, tt->num_leaves, false))) return rc;
-    host_lap("record sort queued");
-  }
   // replayed leaves rewrite their SORTED records: with the sort's second pass held back (PcvSortSecond) the replay is queued
   // behind that pass, in pcv_build_finish
   if (!bs->sort_second.pending && (rc = queue_replay(ctx, bs))) return rc;
@@ -2168,12 +1946,9 @@ extern "C" int pcv_build_finish(pcv_octree* t, const pcv_top_layout* top) {
   }
   for (uint32_t r = 0; r < num_leaves; ++r) u_leaf_rec[r] = u_node_rec[leaves[r]];
   // climbers of K6 (every 8th point of every leaf; the root is never a leaf): dense index = climb_base[leaf] + j / 8,
-  // and the work lists of the leaf-wise settle / climb kernels (pcv_spec.h; PCV_SETTLE_BY_LEAF=0: the slot-wise settle
+  // and the work lists of the leaf-wise settle / climb kernels (pcv_spec.h; settle_by_leaf off: the slot-wise settle
   // kernel and the flat climb launch, experiments)
-  static const bool by_leaf = [] {
-    const char* e = pcv_experiment("PCV_SETTLE_BY_LEAF");
-    return !e || atoi(e) != 0;
-  }();
+  const bool by_leaf = pcv_switches().settle_by_leaf;
   const bool fuse_sort = bs->spec && bs->sort_second.pending && (bs->sort_second.nbits <= 7 || !t->has_intensity) && by_leaf && !wide && bs->spec_wide;
   std::vector<uint8_t> fused_leaf;
   uint64_t settled_points = 0;
@@ -2319,11 +2094,7 @@ extern "C" int pcv_build_finish(pcv_octree* t, const pcv_top_layout* top) {
   }
   // leaves below a split first candidate: the leaf-wise settle kernel continues their chain itself (its items name the
   // range); the slot-wise kernel (experiments) gets the codes rewritten by a pass of its own first
-  static const bool fuse_cont = [] {  // PCV_CONT_IN_SETTLE=0 (libpcv_hip_exp.so): the stand-alone continuation kernel
-    const char* e = pcv_experiment("PCV_CONT_IN_SETTLE");
-    return !e || atoi(e) != 0;
-  }();
-  const bool cont_in_settle = by_leaf && fuse_cont && num_cont_items > 0;
+  const bool cont_in_settle = by_leaf && num_cont_items > 0;
   if (num_cont_items && !cont_in_settle)
     pcv_launch_spec_continue(ctx, lv, d_up + walk_bytes + cont_off, (const PcvSettleItem*)(d_up + walk_bytes + cont_items_off), num_cont_items,
                              (void*)s_pay, bs->spec_wide);

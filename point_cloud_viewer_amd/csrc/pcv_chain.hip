@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256) void chain_keys_kernel(PcvLevels lv, uint64_t 
                                                           const double* __restrict__ z, PcvRouted routed,
                                                           KeyT* __restrict__ keys, uint4* __restrict__ zero, uint32_t zero_vecs) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  // the counters of the sort that takes these keys next (pcv_sort_keys_onesweep) are cleared on the way: no launch of their own
+  // the counters of the sample tree kernels that take these keys next are cleared on the way: no launch of their own
   for (uint64_t j = i; j < zero_vecs; j += (uint64_t)gridDim.x * 256) zero[j] = make_uint4(0u, 0u, 0u, 0u);
   if (i >= n) return;
   // sample i of a strided sample taken in clumps of 2^clump_shift consecutive points (same density: one clump every
@@ -882,7 +882,6 @@ int pcv_launch_aabb(pcv_ctx* ctx, uint64_t n, const double* x, const double* y, 
   uint64_t want = (n + (uint64_t)kAabbBlock * 2 * 8 - 1) / ((uint64_t)kAabbBlock * 2 * 8);
   // two resident workgroups per CU stream best: 512 blocks read 100 M points at 6.3 TB/s, 2048 at 5.5, 256 at 4.6
   static const int maxb = [] {
-    if (const char* e = pcv_experiment("PCV_AABB_BLOCKS")) return std::min(2048, std::max(1, atoi(e)));  // experiments
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
       cus = 256;

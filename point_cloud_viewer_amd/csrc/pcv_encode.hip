@@ -699,17 +699,6 @@ __global__ __launch_bounds__(256) void spec_replay_kernel(PcvLevels lv, const Pc
 // their records into a COMPACT array (climber k of leaf r sits at climb_base[r] + k, so the array is dense and in slot
 // order) and `climb` runs one lane per entry — its waves are full of climbers and it reads 32 bytes per climber instead
 // of touching every sector of the 16-byte payload array to use an eighth of it.
-#ifdef PCV_EXPERIMENTS
-// (libpcv_hip_exp.so, PCV_WIDE_MASK=m) the wide-code gathers of `settle` fold onto the first m + 1 entries: WRONG output,
-// it only times the kernel without the line fetches the sparse gather costs (the bound of any fix for them)
-__constant__ uint32_t pcv_exp_wide_mask = 0xffffffffu;
-// (PCV_SETTLE_XCD=1) number of settle items when workgroup b takes item (b % 8) * ceil(items / 8) + b / 8: workgroups go
-// round-robin over the 8 XCDs, so consecutive items (slices of one leaf, neighbouring leaves) then share one L2
-__constant__ uint32_t pcv_exp_settle_items = 0;
-#define PCV_WIDE_INDEX(i) ((i) & pcv_exp_wide_mask)
-#else
-#define PCV_WIDE_INDEX(i) (i)
-#endif
 // (PcvClimber: pcv_settle_dev.h)
 
 // one sorted slot of `settle`: finish it in its leaf, or hand it to `climb`
@@ -726,7 +715,7 @@ __device__ __forceinline__ void settle_one(const PcvPromoteTables& pt, uint64_t 
       p.y = p.x >> 16;
       p.x &= 0xffffu;
     } else {  // Float32-coded leaf: p.x is the input index
-      const uint4 w = wide[PCV_WIDE_INDEX(p.x)];
+      const uint4 w = wide[p.x];
       p.x = w.x, p.y = w.y, p.z = w.z;
     }
   }
@@ -802,14 +791,7 @@ __global__ __launch_bounds__(256) void promote_settle_leaf_kernel(
     PcvClimber* __restrict__ climbers, PromoteOut o, const uint4* __restrict__ wide, PcvLevels lv,
     const PcvContRange* __restrict__ cont_ranges) {
   constexpr int kSlots = (int)kPcvSettleTile / 256;
-  uint32_t item = blockIdx.x;
-#ifdef PCV_EXPERIMENTS
-  if (pcv_exp_settle_items) {
-    item = (blockIdx.x & 7u) * ((pcv_exp_settle_items + 7u) / 8u) + (blockIdx.x >> 3);
-    if (item >= pcv_exp_settle_items) return;
-  }
-#endif
-  const PcvSettleItem it = items[item];
+  const PcvSettleItem it = items[blockIdx.x];
   // every record load is issued before anything is consumed; dead lanes of the leaf's last tile re-read the tile's
   // first slot (an item is never empty) so that no load sits behind a branch
   uint32_t key[kSlots], h[kSlots][3], in[kSlots];
@@ -851,7 +833,7 @@ __global__ __launch_bounds__(256) void promote_settle_leaf_kernel(
         if (fe <= PCV_ENC_UINT16) {
           u.x = q[k].x & 0xffffu, u.y = q[k].x >> 16, u.z = q[k].y & 0xffffu;
         } else {
-          const uint4 w = wide[PCV_WIDE_INDEX(q[k].x)];
+          const uint4 w = wide[q[k].x];
           u.x = w.x, u.y = w.y, u.z = w.z;
         }
       }
@@ -1007,27 +989,11 @@ void pcv_launch_spec_encode(pcv_ctx* ctx, const PcvLevels& lv, const uint32_t* w
   // the first kTop walk records (levels 0-3 of T'' and the start of level 4: the table is level-major) are mirrored in LDS: with
   // the Float32 code steps a shallow level step is shorter than the L2 round trip of its child gather. One call, 100 M points:
   // 0 / 512 / 1 024 / 1 536 / 2 048 / 3 072 records -> 1.92-1.95 / 1.88 / 1.88 / 1.85 / 1.83-1.85 / 2.11 ms (3 072: 39 KB of LDS,
-  // registers); profiles/r05_ab_chain_pass_walk_top_in_lds.json. PCV_CHAIN_TOP (libpcv_hip_exp.so): another size, 0 = none.
+  // registers); profiles/r05_ab_chain_pass_walk_top_in_lds.json.
   constexpr int kTop = 2048;
 #define PCV_CHAIN_TOP_LAUNCH(RAWIN, T)                                                                                                  \
   hipLaunchKernelGGL((chain_pass_kernel<true, RAWIN, kBlock, T>), grid, dim3(kBlock), 0, ctx->stream, lv, walk, n, x, y, z, routed, color, \
                      color_stride, intensity, rank, (uint4*)payload, inten_bits, depth_grid, cells, (uint4*)wide, pool_ctr, pool_cap)
-#ifdef PCV_EXPERIMENTS
-  static const int chain_top = [] {
-    const char* e = pcv_experiment("PCV_CHAIN_TOP");
-    return e ? atoi(e) : kTop;
-  }();
-  if (!routed.oct && chain_top != kTop) {
-    switch (chain_top) {
-      case 0: PCV_CHAIN_TOP_LAUNCH(true, 0); return;
-      case 512: PCV_CHAIN_TOP_LAUNCH(true, 512); return;
-      case 1024: PCV_CHAIN_TOP_LAUNCH(true, 1024); return;
-      case 1536: PCV_CHAIN_TOP_LAUNCH(true, 1536); return;
-      case 3072: PCV_CHAIN_TOP_LAUNCH(true, 3072); return;
-      default: break;
-    }
-  }
-#endif
 #ifdef PCV_EXPERIMENTS  // (PCV_COLOR_LATE=1: measured, slower overall, not instantiated in libpcv_hip.so)
 #define PCV_CHAIN_LATE_LAUNCH(RAWIN)                                                                                                     \
   hipLaunchKernelGGL((chain_pass_kernel<true, RAWIN, kBlock, kTop, 1>), grid, dim3(kBlock), 0, ctx->stream, lv, walk, n, x, y, z, routed, color, \
@@ -1122,13 +1088,6 @@ void pcv_launch_spec_replay(pcv_ctx* ctx, const PcvLevels& lv, const void* range
 }
 
 size_t pcv_climber_bytes(uint64_t num_climbers) { return (size_t)(num_climbers + 1) * sizeof(PcvClimber); }
-bool pcv_climb16_enabled() {
-  static const bool climb16_on = [] {  // PCV_CLIMB16=0 (libpcv_hip_exp.so): 32-byte climber records everywhere
-    const char* e = pcv_experiment("PCV_CLIMB16");
-    return !e || atoi(e) != 0;
-  }();
-  return climb16_on;
-}
 
 void pcv_launch_promote_encode(pcv_ctx* ctx, const PcvLevels& lv, const PcvPromoteTables& pt, uint64_t n,
                                const uint32_t* rank, const void* payload, const uint32_t* cx_hi, const uint32_t* cy_hi,
@@ -1139,32 +1098,11 @@ void pcv_launch_promote_encode(pcv_ctx* ctx, const PcvLevels& lv, const PcvPromo
   if (n == 0) return;
   PromoteOut o{xyz_blob, rgb_blob, inten_blob};
   // 16-byte climbers: leaf-wise kernels, no intensity plane, no Float64 high words
-#ifdef PCV_EXPERIMENTS
-  static const bool wide_mask_set = [] {
-    if (const char* e = pcv_experiment("PCV_WIDE_MASK")) {
-      const uint32_t m = (uint32_t)strtoul(e, nullptr, 0);
-      (void)hipMemcpyToSymbol(HIP_SYMBOL(pcv_exp_wide_mask), &m, sizeof(m));
-    }
-    return true;
-  }();
-  (void)wide_mask_set;
-#endif
-  const bool climb16 = pcv_climb16_enabled() && items && climb_items && !inten_bits && !cx_hi;
+  const bool climb16 = items && climb_items && !inten_bits && !cx_hi;
   if (items) {
-    uint32_t settle_grid = num_items;
-#ifdef PCV_EXPERIMENTS
-    static const bool xcd = [] {
-      const char* e = pcv_experiment("PCV_SETTLE_XCD");
-      return e && atoi(e) != 0;
-    }();
-    if (xcd) {
-      settle_grid = (num_items + 7u) / 8u * 8u;
-      (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(pcv_exp_settle_items), &num_items, sizeof(num_items), 0, hipMemcpyHostToDevice, ctx->stream);
-    }
-#endif
     PcvProf prof(ctx, PCV_K_PROMOTE_ENCODE);
 #define PCV_SETTLE_LEAF(C, K, W)                                                                                              \
-  hipLaunchKernelGGL((promote_settle_leaf_kernel<C, K>), dim3(settle_grid), dim3(256), 0, ctx->stream, pt, items, rank,         \
+  hipLaunchKernelGGL((promote_settle_leaf_kernel<C, K>), dim3(num_items), dim3(256), 0, ctx->stream, pt, items, rank,           \
                      (const uint4*)payload, cx_hi, cy_hi, cz_hi, inten_bits, climb_base, (PcvClimber*)climbers, o, (const uint4*)(W), lv, \
                      (const PcvContRange*)cont_ranges)
     if (num_items && wide && climb16) PCV_SETTLE_LEAF(true, true, wide);
@@ -1174,19 +1112,11 @@ void pcv_launch_promote_encode(pcv_ctx* ctx, const PcvLevels& lv, const PcvPromo
 #undef PCV_SETTLE_LEAF
   } else {
     PcvProf prof(ctx, PCV_K_PROMOTE_ENCODE);
-    static const int slots = [] {  // PCV_SETTLE_SLOTS (experiments): 1, 2 or 4 sorted slots per lane
-      const char* e = pcv_experiment("PCV_SETTLE_SLOTS");
-      return e ? atoi(e) : 2;
-    }();
 #define PCV_SETTLE(S, C)                                                                                                 \
   hipLaunchKernelGGL((promote_settle_kernel<S, C>), dim3((unsigned)((n + 256 * S - 1) / (256 * S))), dim3(256), 0, ctx->stream, pt, \
                      n, rank, (const uint4*)payload, cx_hi, cy_hi, cz_hi, inten_bits, climb_base, (PcvClimber*)climbers, o,       \
                      (const uint4*)wide)
-    if (wide && slots == 1) PCV_SETTLE(1, true);
-    else if (wide && slots == 4) PCV_SETTLE(4, true);
-    else if (wide) PCV_SETTLE(2, true);
-    else if (slots == 1) PCV_SETTLE(1, false);
-    else if (slots == 4) PCV_SETTLE(4, false);
+    if (wide) PCV_SETTLE(2, true);  // two sorted slots per lane
     else PCV_SETTLE(2, false);
 #undef PCV_SETTLE
   }

@@ -21,7 +21,6 @@
 #include <limits>
 
 #include "pcv_internal.h"
-#include <chrono>
 #include <vector>
 
 namespace {
@@ -253,26 +252,18 @@ extern "C" int pcv_ingest_begin(pcv_ctx* ctx, uint64_t num_points_hint, int has_
 
 extern "C" uint64_t pcv_ingest_num_points(const pcv_ingest* g) { return g ? g->n : 0; }
 
-// PCV_INGEST_TRACE=1 (libpcv_hip_exp.so): where an append's host time goes, summed over the ingest and printed by finish
-static double g_trace_us[4];  // wait for the ring slot, copy into the pinned chunk, queue DMA + kernel, whole call
-static inline double trace_now() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 // The pinned chunk in hand goes up: one DMA, one transposition kernel per batch in it.
 // The DMAs travel on the side stream, the kernels on `stream`: on ONE stream every DMA pays two hand-overs between the copy
 // engine and the compute queue (DMA k+1 cannot start before kernel k has ended). The kernels wait for their DMA (ring_ev), the DMA
 // that refills a staging chunk for the kernels that read it (read_ev); the stream order of `stream` is what keeps the
-// destination arrays (and their growth, ingest_reserve) consistent. PCV_INGEST_ONE_STREAM=1 (libpcv_hip_exp.so): everything on `stream`.
+// destination arrays (and their growth, ingest_reserve) consistent.
 static int ingest_flush(pcv_ingest* g) {
   if (g->cur_slot < 0) return PCV_OK;
   pcv_ctx* ctx = g->ctx;
   const int slot = g->cur_slot;
   g->cur_slot = -1;
   if (ctx->ring_held == slot) ctx->ring_held = -1;
-  static const bool one_stream = [] {
-    const char* e = pcv_experiment("PCV_INGEST_ONE_STREAM");
-    return (e && atoi(e) != 0);
-  }();
-  hipStream_t cs = one_stream || !ctx->side ? ctx->stream : ctx->side;
+  hipStream_t cs = !ctx->side ? ctx->stream : ctx->side;
   uint8_t* st = g->stage[slot];
   bool ok = true;
   if (cs != ctx->stream && g->read_busy[slot]) ok = hipStreamWaitEvent(cs, g->read_ev[slot], 0) == hipSuccess;
@@ -305,8 +296,6 @@ static int ingest_flush(pcv_ingest* g) {
 
 extern "C" int pcv_ingest_append(pcv_ingest* g, const double* xyz, const uint8_t* rgb, const float* intensity, uint64_t n) {
   if (!g) return PCV_E_INVALID;
-  static const bool trace = pcv_experiment("PCV_INGEST_TRACE") != nullptr;
-  const double tr0 = trace ? trace_now() : 0.0;
   pcv_ctx* ctx = g->ctx;
   if (g->failed) return ctx->fail(PCV_E_INVALID, "pcv_ingest_append after a failed append: the ingest can only be finished or aborted");
   if (n == 0) return PCV_OK;
@@ -330,11 +319,9 @@ extern "C" int pcv_ingest_append(pcv_ingest* g, const double* xyz, const uint8_t
       total = int_off + int_bytes;
     };
     place(g->cur_slot >= 0 ? g->cur_fill : 0);
-    double tr1 = trace ? trace_now() : 0.0, tr2 = tr1;
     if (g->cur_slot >= 0 && total > pcv_ctx::kRingChunk) {  // the chunk in hand is full: up it goes
       if ((rc = ingest_flush(g))) return rc;
       place(0);
-      if (trace) g_trace_us[2] += trace_now() - tr1, tr1 = tr2 = trace_now();
     }
     if (g->cur_slot < 0) {
       const int slot = ctx->ring_take();
@@ -342,7 +329,6 @@ extern "C" int pcv_ingest_append(pcv_ingest* g, const double* xyz, const uint8_t
       g->cur_slot = slot;
       g->cur_fill = 0;
       if (ctx->ring_held < 0) ctx->ring_held = slot;  // (one ingest fills a chunk at a time: a second ingest on the same context flushes as it goes, below)
-      tr2 = trace ? trace_now() : 0.0;
     }
     uint8_t* chunk = (uint8_t*)ctx->ring[g->cur_slot];
     const uint8_t* sx = (const uint8_t*)(xyz + done * 3);
@@ -379,9 +365,7 @@ extern "C" int pcv_ingest_append(pcv_ingest* g, const double* xyz, const uint8_t
     g->cur_fill = total;
     g->n += m;
     if (ctx->ring_held != g->cur_slot && (rc = ingest_flush(g))) return rc;  // another ingest of this context holds the marker
-    if (trace) g_trace_us[0] += tr2 - tr1, g_trace_us[1] += trace_now() - tr2;
   }
-  if (trace) g_trace_us[3] += trace_now() - tr0;
   return PCV_OK;
 }
 
@@ -415,11 +399,6 @@ extern "C" int pcv_ingest_bbox(pcv_ingest* g, double bbox_min[3], double bbox_ma
 }
 
 extern "C" int pcv_ingest_finish(pcv_ingest* g, const pcv_build_params* params, pcv_octree** out) {
-  if (pcv_experiment("PCV_INGEST_TRACE")) {
-    fprintf(stderr, "[ingest] wait slot %.1f ms, copy to pinned %.1f ms, queue %.1f ms, appends in all %.1f ms\n", g_trace_us[0] * 1e-3,
-            g_trace_us[1] * 1e-3, g_trace_us[2] * 1e-3, g_trace_us[3] * 1e-3);
-    g_trace_us[0] = g_trace_us[1] = g_trace_us[2] = g_trace_us[3] = 0.0;
-  }
   if (!g) return PCV_E_INVALID;
   pcv_ctx* ctx = g->ctx;
   int rc = PCV_OK;

@@ -71,18 +71,9 @@ struct PcvHostPool {
 };
 
 // Caching device allocator + pinned host scratch, one per context. Steady-state builds allocate nothing.
-// A pool block assembled from separately created physical chunks mapped into one address range in a scrambled order
-// (HIP virtual memory management; PcvPool::alloc explains why).
-struct PcvVmmBlock {
-  size_t size = 0;
-  std::vector<hipMemGenericAllocationHandle_t> handles;
-};
 struct PcvPool {
   std::multimap<size_t, void*> free_blocks;
   std::map<void*, size_t> live;
-  std::map<void*, PcvVmmBlock> vmm;  // blocks that must be unmapped / released instead of hipFree'd
-  int device = 0;
-  void free_block(void* p);
   void* alloc(size_t bytes, hipError_t* err);
   void release(void* p);
   void trim();
@@ -353,16 +344,6 @@ int pcv_radix_sort_u64(pcv_ctx* ctx, uint64_t* keys_a, uint64_t* keys_b, uint64_
                        PcvSortPayload* payload, void* scratch, bool* result_in_a);
 int pcv_radix_sort_u32(pcv_ctx* ctx, uint32_t* keys_a, uint32_t* keys_b, uint64_t n, int begin_bit, int end_bit,
                        PcvSortPayload* payload, void* scratch, bool* result_in_a);
-#ifdef PCV_EXPERIMENTS
-// The sample's key sort, one launch per 9-bit digit (pcv_sort.hip: onesweep_keys_kernel). `scratch`: pcv_onesweep_scratch_words
-// words whose first pcv_onesweep_zero_words are zero when the sort starts.
-bool pcv_onesweep_fits(uint64_t n, int bits);
-size_t pcv_onesweep_zero_words(uint64_t n, int bits);
-size_t pcv_onesweep_scratch_words(uint64_t n, int bits);
-int pcv_sort_keys_onesweep(pcv_ctx* ctx, uint64_t* keys_a, uint64_t* keys_b, uint64_t n, int begin_bit, int end_bit, uint32_t* scratch,
-                           bool* result_in_a, int diag = 0 /* timing-only variants (pcv_exp_time_key_sort, libpcv_hip_exp.so) */);
-#endif
-
 // rows (pcv_launch_rank_hist_rows, map_entries counters per sort workgroup): the first pass takes its histogram from them and
 // applies the map inside its downsweep — the keys are not read an extra time
 // `second` set: a sort that takes the two-pass form with both histograms from the rank counts queues its first pass (and the
@@ -545,7 +526,6 @@ struct PcvPromoteTables {
 // climb_base[leaf rank] = number of climbers (every 8th point of a non-root leaf) in the leaves before it; climbers:
 // pcv_climber_bytes(num_climbers) bytes of scratch that `settle` fills and `climb` consumes
 size_t pcv_climber_bytes(uint64_t num_climbers);
-bool pcv_climb16_enabled();  // leaf-wise kernels without intensity / Float64 planes keep 16-byte climber records
 void pcv_launch_promote_encode(pcv_ctx* ctx, const PcvLevels& lv, const PcvPromoteTables& pt, uint64_t n,
                                const uint32_t* rank, const void* payload /* uint4[n] */, const uint32_t* cx_hi,
                                const uint32_t* cy_hi, const uint32_t* cz_hi, const uint32_t* inten_bits,

@@ -1838,39 +1838,22 @@ extern "C" int pcv_cull_nodes_sparse(pcv_ctx* ctx, const pcv_shapes* shapes, pcv
   if (size_on_screen_out && (rc = sc.get(&d_sz, rows))) return rc;
   uint32_t* d_redo;
   if ((rc = sc.get(&d_redo, f))) return rc;
-  // PCV_CULL_FLAT=1 (libpcv_hip_exp.so): the flat kernel alone, as round 5 shipped it (the checker of the tree walk's lists)
-  static const bool flat_only = [] {
-    const char* e = pcv_experiment("PCV_CULL_FLAT");
-    return e && atoi(e) != 0;
-  }();
   {
     PcvProf prof(ctx, PCV_K_CULL_NODES_SPARSE);
-    if (!flat_only) {
-      if (d_sz)
-        hipLaunchKernelGGL(cull_nodes_tree_kernel<true>, dim3((f + 3) / 4), dim3(256), 0, ctx->stream, shapes->dev, f, m, tree->query->fb_cubes,
-                           tree->query->first_child, tree->query->child_mask, capacity, d_cnt, d_node, d_rel, d_sz, d_redo,
-                           (const uint64_t*)nullptr);
-      else
-        hipLaunchKernelGGL(cull_nodes_tree_kernel<false>, dim3((f + 3) / 4), dim3(256), 0, ctx->stream, shapes->dev, f, m, tree->query->fb_cubes,
-                           tree->query->first_child, tree->query->child_mask, capacity, d_cnt, d_node, d_rel, d_sz, d_redo,
-                           (const uint64_t*)nullptr);
-    }
+    if (d_sz)
+      hipLaunchKernelGGL(cull_nodes_tree_kernel<true>, dim3((f + 3) / 4), dim3(256), 0, ctx->stream, shapes->dev, f, m, tree->query->fb_cubes,
+                         tree->query->first_child, tree->query->child_mask, capacity, d_cnt, d_node, d_rel, d_sz, d_redo,
+                         (const uint64_t*)nullptr);
+    else
+      hipLaunchKernelGGL(cull_nodes_tree_kernel<false>, dim3((f + 3) / 4), dim3(256), 0, ctx->stream, shapes->dev, f, m, tree->query->fb_cubes,
+                         tree->query->first_child, tree->query->child_mask, capacity, d_cnt, d_node, d_rel, d_sz, d_redo,
+                         (const uint64_t*)nullptr);
     hipLaunchKernelGGL(cull_nodes_sparse_kernel<false>, dim3(f), dim3(256), 0, ctx->stream, shapes->dev, m, tree->query->fb_cubes, capacity, d_cnt,
-                       d_node, d_rel, d_sz, flat_only ? (const uint32_t*)nullptr : (const uint32_t*)d_redo);
+                       d_node, d_rel, d_sz, (const uint32_t*)d_redo);
     if (shapes->wide)  // the web-mercator rectangles' lists and counts, over what the launches above wrote for them
       hipLaunchKernelGGL(cull_nodes_sparse_kernel<true>, dim3(f), dim3(256), 0, ctx->stream, shapes->dev, m, tree->query->fb_cubes, capacity,
                          d_cnt, d_node, d_rel, d_sz, (const uint32_t*)nullptr);
   }
-#ifdef PCV_EXPERIMENTS
-  if (!flat_only && pcv_experiment("PCV_CULL_DEBUG")) {  // how many shapes the tree walk handed to the flat kernel
-    std::vector<uint32_t> h(f);
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(h.data(), d_redo, (size_t)f * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    uint32_t r = 0;
-    for (uint32_t v : h) r += v;
-    fprintf(stderr, "[pcv cull] %u of %u shapes redone by the flat kernel\n", r, f);
-  }
-#endif
   PCV_HIP_CHECK(ctx, hipGetLastError());
   PCV_HIP_CHECK(ctx, hipMemcpyAsync(counts, d_cnt, (size_t)f * 4, hipMemcpyDeviceToHost, ctx->stream));
   if (capacity) {

@@ -1207,9 +1207,7 @@ __global__ __launch_bounds__(256) void msd_offsets_kernel(uint32_t* __restrict__
 //   tiles of 8 192: 1 024 x 8 1.20 ms (ships), 512 x 16 1.25; non-temporal stores +35 %
 //   tiles of 16 384 by staging keys and payloads one after the other through the same LDS: 1.27-1.29 against 1.01-1.11
 //   (two more barriers per tile, one workgroup per CU) — dropped
-// PCV_REC_VARIANT (libpcv_hip_exp.so): 3 = 1 024 x 8 (default), 4 = 512 x 16, 2 = 512 x 8 (tiles of 4 096), 0 = the
-// 256-lane kernel above
-static void rec12_launch(pcv_ctx* ctx, int variant, const SortGeom& g, const uint32_t* src, uint32_t* dst, uint64_t n, int shift,
+static void rec12_launch(pcv_ctx* ctx, const SortGeom& g, const uint32_t* src, uint32_t* dst, uint64_t n, int shift,
                          int nbits, const uint32_t* hist, const uint32_t* totals, const uint2* vin, uint2* vout,
                          const uint32_t* pin = nullptr, uint32_t* pout = nullptr) {
 #define PCV_REC12(B, K, R, W, NT)                                                                                              \
@@ -1227,34 +1225,15 @@ static void rec12_launch(pcv_ctx* ctx, int variant, const SortGeom& g, const uin
                          (const uint32_t*)nullptr, pin, pout);
     return;
   }
-  switch (variant) {
-    case 2:
-      if (narrow) PCV_REC12(512, 8, 128, 4, false);
-      else PCV_REC12(512, 8, 256, 4, false);
-      break;
-    case 4:
-      if (narrow) PCV_REC12(512, 16, 128, 2, false);
-      else PCV_REC12(512, 16, 256, 2, false);
-      break;
-    default:
-      if (narrow) PCV_REC12(1024, 8, 128, 4, false);
-      else PCV_REC12(1024, 8, 256, 4, false);
-  }
+  if (narrow) PCV_REC12(1024, 8, 128, 4, false);
+  else PCV_REC12(1024, 8, 256, 4, false);
 #undef PCV_REC12
 }
 
 // true-rank counters per sort workgroup the scratch holds (hist12_from_rows_kernel): 2^14, and 2^15 for clouds big enough to have
 // that many leaves (128 MB of scratch instead of 64), 2^16 from 500 M points on (256 MB)
 static uint32_t rows_true_bins(uint64_t n) {
-#ifdef PCV_EXPERIMENTS
-  // PCV_ROWS_TRUE_BINS=32768 / 65536 (libpcv_hip_exp.so): the 15- / 16-bit rank geometries on a cloud small enough for the CPU
-  // oracle to check them (tests/test_gpu_single_chain.py)
-  static const uint32_t forced = [] {
-    const char* e = pcv_experiment("PCV_ROWS_TRUE_BINS");
-    return e ? (uint32_t)atoi(e) : 0u;
-  }();
-  if (forced) return forced;
-#endif
+  if (pcv_switches().rows_true_bins) return pcv_switches().rows_true_bins;
   return n >= 500000000ull ? 65536u : n >= 200000000ull ? 32768u : 16384u;
 }
 
@@ -1269,15 +1248,11 @@ int radix_sort(pcv_ctx* ctx, KeyT* a, KeyT* b, uint64_t n, int begin_bit, int en
   const bool records = payload && (payload->vec_in || payload->nwords > 0);
   if (records && sizeof(KeyT) != 4) return ctx->fail(PCV_E_INVALID, "record sort needs 32-bit keys");
   const bool compact = records && payload->vec_in && payload->vec_bytes == 8;  // 12-byte records
-  // geometry of the 12-byte record downsweep: 1 024 lanes x 8 records, tiles of 8 192 (rec12_launch)
-  static const int rec_variant = [] {
-    const char* e = pcv_experiment("PCV_REC_VARIANT");
-    return e ? atoi(e) : 3;
-  }();
   // 12-byte records, alone or with ONE 4-byte plane (intensity); more planes (the exact pipeline's wide codes) take the 256-lane kernel
-  const bool with_plane = compact && payload->nwords == 1 && rec_variant == 3;
-  const bool rec12 = compact && (payload->nwords == 0 || with_plane) && rec_variant > 0;
-  SortGeom g = make_geom(n, rec12 && rec_variant != 2 ? 8192 : kTileUnit);
+  const bool with_plane = compact && payload->nwords == 1;
+  const bool rec12 = compact && (payload->nwords == 0 || with_plane);
+  // geometry of the 12-byte record downsweep: 1 024 lanes x 8 records, tiles of 8 192 (rec12_launch)
+  SortGeom g = make_geom(n, rec12 ? 8192 : kTileUnit);
   uint32_t* hist = (uint32_t*)scratch;
   uint32_t* totals = hist + (size_t)kRadix * kMaxGroups;
   bool in_a = true;
@@ -1286,21 +1261,7 @@ int radix_sort(pcv_ctx* ctx, KeyT* a, KeyT* b, uint64_t n, int begin_bit, int en
   // sectors. Keys-only sorts keep full 8-bit digits (fewest passes is what counts there).
   const int total_bits = end_bit - begin_bit;
   const int passes = (total_bits + 7) / 8;
-  int width = records ? (total_bits + passes - 1) / passes : 8;
-#ifdef PCV_EXPERIMENTS
-  // PCV_SORT_FLIP=1 (libpcv_hip_exp.so): a two-pass record sort takes the NARROWER digit first (13 bits -> 6 + 7 instead of 7 + 6):
-  // with PCV_REC_BLOCK=512 the first pass then runs two workgroups per CU on tiles of 4 096 with the runs of 64 records it has today
-  static const bool flip = [] {
-    const char* e = pcv_experiment("PCV_SORT_FLIP");
-    return e && atoi(e) != 0;
-  }();
-  const bool flipped = flip && records && passes == 2 && (total_bits & 1) && map && rows;
-  const int width2 = width;  // the second pass's width when flipped
-  if (flipped) width = total_bits / 2;
-#else
-  constexpr bool flipped = false;
-  const int width2 = width;
-#endif
+  const int width = records ? (total_bits + passes - 1) / passes : 8;
   for (int shift = begin_bit; shift < end_bit; shift += width) {
     int nbits = end_bit - shift < width ? end_bit - shift : width;
     uint32_t mask = (1u << nbits) - 1u;
@@ -1308,28 +1269,16 @@ int radix_sort(pcv_ctx* ctx, KeyT* a, KeyT* b, uint64_t n, int begin_bit, int en
     KeyT* dst = in_a ? b : a;
     // the histogram from the rank counts, the map applied inside the downsweep (12-byte records in tiles of 8 192; the map in
     // dynamic LDS next to the kernel's 107-117 KB: up to 16 384 half-word entries)
-    const bool from_rows = map && rows && shift == begin_bit && rec12 && rec_variant == 3 && nbits <= 8;
+    const bool from_rows = map && rows && shift == begin_bit && rec12 && nbits <= 8;
     // half words in <= 32 KB beside the kernel's 107-117 KB; with a plane the kernel holds 137-146 KB: <= 20 / 10 KB of map (bigger maps are gathered)
     // (static LDS with a plane: 128 KB of tiles + 9.1 / 18.1 KB of digit state for 128 / 256 digit values)
     const bool map_in_lds = map_entries <= (with_plane ? (nbits <= 7 ? 10000u : 5000u) : 16384u);
     if (from_rows) {
-      static const bool pass2_rows_on = [] {
-        const char* e = pcv_experiment("PCV_SORT_ROWS2");  // 0 = the second pass counts its keys itself (experiments)
-        return !e || atoi(e) != 0;
-      }();
-      const int nbits2 = flipped ? width2 : (end_bit - (shift + width) < width ? end_bit - (shift + width) : width);
-      bool msd = false;
-#ifdef PCV_EXPERIMENTS
-      static const bool msd_on = [] {
-        const char* e = pcv_experiment("PCV_SORT_MSD");  // 1: upper digit first, the second pass sorts inside every bucket
-        return e && atoi(e) != 0;
-      }();
-      msd = msd_on;
-#endif
+      const int nbits2 = end_bit - (shift + width) < width ? end_bit - (shift + width) : width;
       // (ranks of 15 bits — trees of up to 32 768 leaves — where the scratch holds their counters: rows_true_bins)
-      const bool two = pass2_rows_on && map_entries <= rows_true_bins(n) && shift + width < end_bit && shift + width + nbits2 >= end_bit &&
+      const bool two = pcv_switches().sort_rows2 && map_entries <= rows_true_bins(n) && shift + width < end_bit && shift + width + nbits2 >= end_bit &&
                        (1u << total_bits) <= rows_true_bins(n) && nbits2 >= 1 && g.groups >= 8;
-      msd = msd && two;
+      const bool msd = pcv_switches().sort_msd && two;  // upper digit first, the second pass sorts inside every bucket
       // first / second pass: (shift, bits) of their digits — the lower digit first, unless msd
       const int p1_shift = msd ? shift + width : shift, p1_bits = msd ? nbits2 : nbits;
       const int p2_shift = msd ? shift : shift + width, p2_bits = msd ? nbits : nbits2;
@@ -1375,33 +1324,14 @@ int radix_sort(pcv_ctx* ctx, KeyT* a, KeyT* b, uint64_t n, int begin_bit, int en
                        (const uint32_t*)src, (uint32_t*)dst, n, g.chunk, g.groups, p1_shift, p1_bits, hist, totals, vin, vout, map,       \
                        map_entries, (const uint2*)nullptr, (const uint32_t*)nullptr, pin, pout, payload->color_in, payload->color_stride); \
   }
-        // PCV_REC_WC (libpcv_hip_exp.so; bit 0: first pass, bit 1: second pass): the write-combining form of the downsweep
-        // measured slower than the kernel that ships (profiles/r05_sort_same_box.json): not instantiated in libpcv_hip.so
+        // rec_wc (bit 0: first pass, bit 1: second pass): the write-combining form of the downsweep measured slower than the
+        // kernel that ships (profiles/r05_sort_same_box.json): not instantiated in libpcv_hip.so
         bool wc_done = false;
 #ifdef PCV_EXPERIMENTS
-        static const int rec_wc = [] {
-          const char* e = pcv_experiment("PCV_REC_WC");
-          return e ? atoi(e) : 0;
-        }();
-        if ((rec_wc & 1) && !with_plane && p1_bits <= 7 && !payload->color_in) {
+        if ((pcv_switches().rec_wc & 1) && !with_plane && p1_bits <= 7 && !payload->color_in) {
           hipLaunchKernelGGL((downsweep_rec12_kernel<1024, 8, 128, 4, false, 2, false, true>), dim3(g.groups), dim3(1024), 0, ctx->stream,
                              (const uint32_t*)src, (uint32_t*)dst, n, g.chunk, g.groups, p1_shift, p1_bits, hist, totals, vin, vout, map, map_entries,
                              (const uint2*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-          wc_done = true;
-        }
-#endif
-#ifdef PCV_EXPERIMENTS
-        static const int rec_block = [] {  // PCV_REC_BLOCK=512: the first pass in tiles of 4 096, two workgroups per CU
-          const char* e = pcv_experiment("PCV_REC_BLOCK");
-          return e ? atoi(e) : 1024;
-        }();
-        if (!wc_done && rec_block == 512 && !with_plane && p1_bits <= 7 && map_in_lds && dyn <= 28672 && !payload->color_in) {
-          static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&downsweep_rec12_kernel<512, 8, 128, 4, false, 1, false>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 28672) == hipSuccess;
-          (void)ok;
-          hipLaunchKernelGGL((downsweep_rec12_kernel<512, 8, 128, 4, false, 1, false>), dim3(g.groups), dim3(512), dyn, ctx->stream,
-                             (const uint32_t*)src, (uint32_t*)dst, n, g.chunk, g.groups, p1_shift, p1_bits, hist, totals, vin, vout, map,
-                             map_entries, (const uint2*)nullptr, (const uint32_t*)nullptr, pin, pout);
           wc_done = true;
         }
 #endif
@@ -1472,11 +1402,7 @@ int radix_sort(pcv_ctx* ctx, KeyT* a, KeyT* b, uint64_t n, int begin_bit, int en
                      (const uint32_t*)order, pin2, pout2)
         bool wc2_done = false;
 #ifdef PCV_EXPERIMENTS
-        static const int rec_wc2 = [] {
-          const char* e = pcv_experiment("PCV_REC_WC");
-          return e ? atoi(e) : 0;
-        }();
-        if ((rec_wc2 & 2) && !with_plane && p2_bits <= 7) {
+        if ((pcv_switches().rec_wc & 2) && !with_plane && p2_bits <= 7) {
           hipLaunchKernelGGL((downsweep_rec12_kernel<1024, 8, 128, 4, false, 0, false, true>), dim3(pieces), dim3(1024), 0, ctx->stream, src2, dst2, n,
                              g.chunk, pieces, p2_shift, p2_bits, hist2, totals2, vin2, vout2, (const uint32_t*)nullptr, 0u, (const uint2*)ranges,
                              (const uint32_t*)order, (const uint32_t*)nullptr, (uint32_t*)nullptr);
@@ -1511,11 +1437,7 @@ int radix_sort(pcv_ctx* ctx, KeyT* a, KeyT* b, uint64_t n, int begin_bit, int en
 #undef PCV_UPSWEEP_MAP
     } else {
       PcvProf prof(ctx, sizeof(KeyT) == 8 ? PCV_K_SORT_UPSWEEP64 : PCV_K_SORT_UPSWEEP32);
-      static const bool plain_on = [] {
-        const char* e = pcv_experiment("PCV_UPSWEEP_PLAIN");  // 0 = the ballot match everywhere (experiments)
-        return !e || atoi(e) != 0;
-      }();
-      if (plain_on && records && shift != begin_bit)  // the upper digits of a record sort, after a pass has mixed them
+      if (records && shift != begin_bit)  // the upper digits of a record sort, after a pass has mixed them
         hipLaunchKernelGGL((upsweep_kernel<KeyT, true>), dim3(g.groups), dim3(kBlock), 0, ctx->stream, src, n, g.chunk, g.groups, shift,
                            mask, hist);
       else
@@ -1540,22 +1462,15 @@ int radix_sort(pcv_ctx* ctx, KeyT* a, KeyT* b, uint64_t n, int begin_bit, int en
         rp.plane_out[w] = in_a ? payload->out[w] : payload->in[w];
       }
       if (shift == begin_bit && payload->nwords > 0 && payload->first_in0) rp.plane_in[0] = payload->first_in0;
-      static const bool prefetch = [] {
-        const char* e = pcv_experiment("PCV_REC_PREFETCH");  // 0 = the unpipelined kernel (experiments)
-        return !e || atoi(e) != 0;
-      }();
       PcvProf prof(ctx, PCV_K_SORT_DOWNSWEEP_REC);
       if (rec12)
-        rec12_launch(ctx, rec_variant, g, (const uint32_t*)src, (uint32_t*)dst, n, shift, nbits, hist, totals, (const uint2*)rp.vec_in,
+        rec12_launch(ctx, g, (const uint32_t*)src, (uint32_t*)dst, n, shift, nbits, hist, totals, (const uint2*)rp.vec_in,
                      (uint2*)rp.vec_out, with_plane ? rp.plane_in[0] : nullptr, with_plane ? rp.plane_out[0] : nullptr);
       else if (compact)
         hipLaunchKernelGGL((downsweep_rec_kernel<true, true, uint2>), dim3(g.groups), dim3(kBlock), 0, ctx->stream, (const uint32_t*)src,
                            (uint32_t*)dst, n, g.chunk, g.groups, shift, nbits, hist, totals, rp);
-      else if (payload->vec_in && prefetch)
-        hipLaunchKernelGGL((downsweep_rec_kernel<true, true>), dim3(g.groups), dim3(kBlock), 0, ctx->stream, (const uint32_t*)src,
-                           (uint32_t*)dst, n, g.chunk, g.groups, shift, nbits, hist, totals, rp);
       else if (payload->vec_in)
-        hipLaunchKernelGGL(downsweep_rec_kernel<true>, dim3(g.groups), dim3(kBlock), 0, ctx->stream, (const uint32_t*)src,
+        hipLaunchKernelGGL((downsweep_rec_kernel<true, true>), dim3(g.groups), dim3(kBlock), 0, ctx->stream, (const uint32_t*)src,
                            (uint32_t*)dst, n, g.chunk, g.groups, shift, nbits, hist, totals, rp);
       else
         hipLaunchKernelGGL(downsweep_rec_kernel<false>, dim3(g.groups), dim3(kBlock), 0, ctx->stream, (const uint32_t*)src,
@@ -1568,276 +1483,7 @@ int radix_sort(pcv_ctx* ctx, KeyT* a, KeyT* b, uint64_t n, int begin_bit, int en
   return PCV_OK;
 }
 
-
-// ---- the sample's key sort with ONE launch per digit ("onesweep"): measured, no faster, libpcv_hip_exp.so only --------------
-// Round 6: upsweep + scan + downsweep per 8-bit digit are fifteen dependent launches of 6-14 us for the 1.5 M sample keys of a
-// 100 M-point build. One kernel per 9-bit digit (tiles of 8 192 keys, digit counts published per tile, a look-back over the tiles
-// before) is four launches + one counting pass — and takes the same time (tools/key_sort_probe.py, 1.56 M keys of 36 bits:
-// 110 us either way; 15.6 M keys: 495 against 610): the kernel without its look-back runs 14 us per pass, the look-back costs
-// another 11 — what one workgroup publishes reaches another XCD's workgroup through memory, not through its L2 (an agent-scope
-// release fence writes the whole L2 back: 25 us), so two dependent hand-overs inside the kernel cost what the two extra launches
-// did. Kept for the record (PCV_SAMPLE_ONESWEEP=1); profiles/r06_ab_sample_key_sort_one_launch_per_digit_dropped.json.
-#ifdef PCV_EXPERIMENTS
-// The sample of the single-chain build is 1.5 M keys (12.5 MB) at 100 M points: upsweep + scan + downsweep per 8-bit digit
-// were fifteen dependent launches of 6-14 us each, every one of them bound by its own launch and drain. Here the digit counts
-// of ALL passes are taken once (key_hist_kernel), and every pass is
-// ONE kernel over tiles of 8 192 keys: a tile ranks its keys in LDS, publishes its digit counts (512 values + one flag word), adds
-// up the counts of the tiles before it — back to the nearest tile whose inclusive prefix is already there; with all 191 tiles of
-// a 100 M-point build's sample resident at once that is usually tile 0, and the sum is 190 independent loads per lane instead of
-// a chain of dependent ones (a look-back over value+flag words, 32 at a time, cost 11 us per pass; this one ~3) — and writes its runs.
-// Tiles are handed out by a ticket, so a tile only ever waits for tiles that are already running. Digits are up to 9 bits wide
-// (512 lanes, lane t owns digit t): 36 bits of key are four launches.
-constexpr int kOneBlock = 512, kOneKpt = 16, kOneTile = kOneBlock * kOneKpt, kOneWaves = kOneBlock / 64, kOneRadix = 512;
-constexpr int kOneHistGroups = 128;   // workgroups of key_hist_kernel
-constexpr int kOneMaxPasses = 8;
-
-struct OnePasses {
-  int passes;
-  int shift[kOneMaxPasses], bits[kOneMaxPasses];
-};
-
-__global__ __launch_bounds__(kOneBlock) void key_hist_kernel(const uint64_t* __restrict__ keys, uint32_t n, OnePasses ps,
-                                                             uint32_t* __restrict__ ghist /* [passes][512], zero */) {
-  __shared__ uint32_t h[kOneMaxPasses][kOneRadix];
-  for (int i = threadIdx.x; i < ps.passes * kOneRadix; i += kOneBlock) (&h[0][0])[i] = 0;
-  __syncthreads();
-  const uint32_t per = ((n + kOneHistGroups - 1) / kOneHistGroups + 1u) & ~1u;  // even: 16-byte loads stay aligned
-  const uint32_t begin = min(n, blockIdx.x * per), end = min(n, begin + per);
-  typedef uint64_t Vec2 __attribute__((ext_vector_type(2)));
-  uint32_t i = begin + 2u * threadIdx.x;
-  for (; i + 2u * kOneBlock * 3u + 2u <= end; i += 2u * kOneBlock * 4u) {  // four loads in flight
-    Vec2 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const Vec2*>(keys + i + 2u * kOneBlock * u);
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int k = 0; k < 2; ++k)
-        for (int p = 0; p < ps.passes; ++p) atomicAdd(&h[p][(uint32_t)(v[u][k] >> ps.shift[p]) & ((1u << ps.bits[p]) - 1u)], 1u);
-  }
-  for (; i < end; i += 2u * kOneBlock)
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-      if (i + k < end) {
-        const uint64_t key = keys[i + k];
-        for (int p = 0; p < ps.passes; ++p) atomicAdd(&h[p][(uint32_t)(key >> ps.shift[p]) & ((1u << ps.bits[p]) - 1u)], 1u);
-      }
-  __syncthreads();
-  for (int j = threadIdx.x; j < ps.passes * kOneRadix; j += kOneBlock) {
-    const uint32_t c = (&h[0][0])[j];
-    if (c) atomicAdd(&ghist[j], c);  // 128 workgroups x (a few hundred non-empty digits): ghist was cleared with the tickets
-  }
-}
-
-// exclusive prefix over the 512 lanes of the workgroup (lane t -> sum of v of lanes < t); `tot` (8 words of LDS) is scratch
-__device__ __forceinline__ uint32_t one_block_exclusive(uint32_t v, uint32_t* tot, int lane, int wave) {
-  uint32_t inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t u = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += u;
-  }
-  if (lane == 63) tot[wave] = inc;
-  __syncthreads();
-  uint32_t woff = 0;
-#pragma unroll
-  for (int w = 0; w < kOneWaves; ++w) woff += w < wave ? tot[w] : 0u;
-  __syncthreads();
-  return woff + inc - v;
-}
-
-// keeps in (plo, phi) the lanes whose digit agrees with this lane's in bit B
-template <int B>
-__device__ __forceinline__ void one_match_bit(uint32_t d, uint32_t& plo, uint32_t& phi) {
-  int m;  // all ones when bit B of the digit is set
-  asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(m) : "v"(d), "n"(B));
-  const uint64_t bal = __builtin_amdgcn_ballot_w64(m != 0);
-  plo = __builtin_amdgcn_bitop3_b32(plo, (uint32_t)bal, (uint32_t)m, 0x90);  // p & ~(ballot ^ m)
-  phi = __builtin_amdgcn_bitop3_b32(phi, (uint32_t)(bal >> 32), (uint32_t)m, 0x90);
-}
-
-__global__ __launch_bounds__(kOneBlock) void onesweep_keys_kernel(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, uint32_t n,
-                                                                  int shift, int nbits, const uint32_t* __restrict__ ghist /* [512] of this pass */,
-                                                                  uint32_t* __restrict__ ticket, uint32_t* __restrict__ flags /* [tiles], zero */,
-                                                                  uint32_t* __restrict__ vals /* [tiles][2][512] */, int diag) {
-  extern __shared__ uint64_t skeys[];  // kOneTile keys (64 KB)
-  __shared__ uint32_t whist[kOneWaves][kOneRadix];
-  __shared__ uint32_t delta[kOneRadix];
-  __shared__ uint32_t tot[kOneWaves];
-  __shared__ uint32_t s_tile;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (t == 0) s_tile = atomicAdd(ticket, 1u);
-#pragma unroll
-  for (int w = 0; w < kOneWaves; ++w) whist[w][t] = 0;
-  const uint32_t gcount = ghist[t];  // the digit's count over the whole input (key_hist_kernel)
-  __syncthreads();
-  const uint32_t tile = s_tile;
-  const uint32_t base = tile * (uint32_t)kOneTile;
-  const uint32_t tile_n = min((uint32_t)kOneTile, n - base);
-  const uint32_t mask = (1u << nbits) - 1u;
-  const uint32_t wbase = wave * 64 * kOneKpt + lane;
-  uint64_t key[kOneKpt];
-#pragma unroll
-  for (int i = 0; i < kOneKpt; ++i) {
-    const uint32_t li = wbase + i * 64;
-    key[i] = li < tile_n ? in[base + li] : 0ull;
-    if (diag & 8) key[i] = (uint64_t)li << shift;  // timing only (pcv_exp_time_key_sort)
-  }
-  // rank of every key among the earlier keys of its digit inside the wave's slice (stable: iteration-major, lane-minor)
-  uint16_t lpos[kOneKpt];
-#pragma unroll
-  for (int i = 0; i < kOneKpt; ++i) {
-    const bool valid = wbase + i * 64 < tile_n;
-    const uint32_t d = (uint32_t)(key[i] >> shift) & mask;
-    if (diag & 2) {
-      lpos[i] = 0;
-      continue;
-    }
-    const uint64_t vm = __ballot(valid);
-    uint32_t plo = (uint32_t)vm, phi = (uint32_t)(vm >> 32);
-    one_match_bit<0>(d, plo, phi), one_match_bit<1>(d, plo, phi), one_match_bit<2>(d, plo, phi), one_match_bit<3>(d, plo, phi);
-    one_match_bit<4>(d, plo, phi);  // (bits above the digit's width are zero in every lane: matching them changes nothing)
-    if (nbits > 5) one_match_bit<5>(d, plo, phi);  // wave-uniform
-    if (nbits > 6) one_match_bit<6>(d, plo, phi);
-    if (nbits > 7) one_match_bit<7>(d, plo, phi);
-    if (nbits > 8) one_match_bit<8>(d, plo, phi);
-    const uint32_t below = __builtin_amdgcn_mbcnt_hi(phi, __builtin_amdgcn_mbcnt_lo(plo, 0u));
-    uint32_t* slot = &whist[wave][d];
-    const uint32_t pre = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (valid && below == 0)
-      (void)__hip_atomic_fetch_add(slot, (uint32_t)(__popc(plo) + __popc(phi)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    lpos[i] = (uint16_t)(pre + below);
-  }
-  __syncthreads();
-  uint32_t pre_w[kOneWaves], mine = 0;
-#pragma unroll
-  for (int w = 0; w < kOneWaves; ++w) {
-    pre_w[w] = mine;
-    mine += whist[w][t];
-  }
-  // This tile's digit counts for the tiles after it: the 512 values first, then ONE flag word (1 = counts there, 2 = inclusive
-  // prefix there too). Polling touches the flags only; the values are summed with independent loads once they are known to be there.
-  uint32_t* agg = vals + (size_t)tile * 2u * kOneRadix;  // [tile][0] counts, [tile][1] inclusive prefix
-  __hip_atomic_store(agg + t, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (tile == 0) __hip_atomic_store(agg + kOneRadix + t, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  // No fence: an agent-scope release writes back the whole L2 of the XCD (25 us here). The values are agent-scope atomic stores
-  // (written through on their own); once they are acknowledged (vmcnt 0) in every lane, the flag may follow.
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (t == 0) __hip_atomic_store(flags + tile, tile == 0 ? 2u : 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  uint32_t excl = 0;
-  if (tile > 0 && !(diag & 1)) {
-    if (wave == 0) {  // lane l looks at tile hi - l: the nearest tile with a prefix, once every tile after it has its counts
-      int64_t hi = (int64_t)tile - 1, found = -1;
-      uint32_t spins = 0;
-      while (found < 0) {
-        const int64_t j = hi - lane;
-        const uint32_t f = j >= 0 ? __hip_atomic_load(flags + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 1u;
-        const uint64_t pm = __ballot(f == 2u);
-        const int first = pm ? (int)__builtin_ctzll(pm) : 64;
-        if (__ballot(f == 0u && lane < first)) {  // counts missing in front of it: look again
-          if (++spins > (1u << 24)) __builtin_trap();  // a tile that never publishes: fail loudly, never hang
-          __builtin_amdgcn_s_sleep(2);
-          continue;
-        }
-        if (first < 64) found = hi - first;
-        else hi -= 64;
-      }
-      if (lane == 0) s_tile = (uint32_t)found;
-    }
-    __syncthreads();
-    const uint32_t from = s_tile;
-    excl = __hip_atomic_load(vals + ((size_t)from * 2u + 1u) * kOneRadix + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    uint32_t j = from + 1u;
-    for (; j + 16u <= tile; j += 16u) {
-      uint32_t v[16];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) v[u] = __hip_atomic_load(vals + (size_t)(j + u) * 2u * kOneRadix + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-      for (int u = 0; u < 16; ++u) excl += v[u];
-    }
-    for (; j < tile; ++j) excl += __hip_atomic_load(vals + (size_t)j * 2u * kOneRadix + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(agg + kOneRadix + t, excl + mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (t == 0) __hip_atomic_store(flags + tile, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  const uint32_t gstart = one_block_exclusive(gcount, tot, lane, wave);  // keys of smaller digits in the whole input
-  const uint32_t lstart = one_block_exclusive(mine, tot, lane, wave);    // ... in this tile
-#pragma unroll
-  for (int w = 0; w < kOneWaves; ++w) whist[w][t] = lstart + pre_w[w];
-  delta[t] = gstart + excl - lstart;
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < kOneKpt; ++i)
-    if (wbase + i * 64 < tile_n) skeys[whist[wave][(uint32_t)(key[i] >> shift) & mask] + lpos[i]] = key[i];
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < kOneKpt; ++j) {
-    const uint32_t p = j * kOneBlock + t;
-    if (p < tile_n) {
-      const uint64_t k = skeys[diag & 2 ? p : p];
-      uint32_t at = delta[(uint32_t)(k >> shift) & mask] + p;
-      if (diag) at = (diag & 4) ? p : min(at, n - 1u);  // timing-only variants: anywhere inside the buffer
-      out[at] = k;
-    }
-  }
-}
-
-#endif  // PCV_EXPERIMENTS (onesweep kernels)
-
 }  // namespace
-
-#ifdef PCV_EXPERIMENTS
-// The sample's key sort (see onesweep_keys_kernel). scratch: [tickets 64 words | digit counts passes x 512 | flags passes x tiles |
-// values passes x tiles x 2 x 512]; everything in front of the values ZERO when key_hist_kernel starts — pcv_onesweep_zero_words(n,
-// bits) words (the caller lets the kernel that writes the keys clear them: no launch of its own).
-static int onesweep_passes(int bits) { return (bits + 8) / 9; }
-bool pcv_onesweep_fits(uint64_t n, int bits) { return n > 0 && n < (1ull << 30) && bits > 0 && onesweep_passes(bits) <= kOneMaxPasses; }
-size_t pcv_onesweep_zero_words(uint64_t n, int bits) {
-  const size_t tiles = (size_t)((n + kOneTile - 1) / kOneTile);
-  return 64 + (size_t)onesweep_passes(bits) * (kOneRadix + ((tiles + 3) & ~(size_t)3));
-}
-size_t pcv_onesweep_scratch_words(uint64_t n, int bits) {
-  const size_t tiles = (size_t)((n + kOneTile - 1) / kOneTile);
-  return ((pcv_onesweep_zero_words(n, bits) + 63) & ~(size_t)63) + (size_t)onesweep_passes(bits) * tiles * 2 * kOneRadix;
-}
-int pcv_sort_keys_onesweep(pcv_ctx* ctx, uint64_t* keys_a, uint64_t* keys_b, uint64_t n, int begin_bit, int end_bit, uint32_t* scratch,
-                           bool* result_in_a, int diag) {
-  const int bits = end_bit - begin_bit;
-  if (!pcv_onesweep_fits(n, bits)) return ctx->fail(PCV_E_INVALID, "onesweep key sort: size");
-  OnePasses ps{};
-  ps.passes = onesweep_passes(bits);
-  for (int p = 0, at = begin_bit; p < ps.passes; ++p) {  // digits as even as they come: 36 bits = 4 x 9, 39 = 5 x 8 (the last one 7)
-    const int w = (end_bit - at + (ps.passes - p) - 1) / (ps.passes - p);
-    ps.shift[p] = at, ps.bits[p] = w, at += w;
-  }
-  const uint32_t tiles = (uint32_t)((n + kOneTile - 1) / kOneTile);
-  uint32_t* tickets = scratch;
-  const size_t tiles4 = ((size_t)tiles + 3) & ~(size_t)3;
-  uint32_t* ghist = scratch + 64;
-  uint32_t* flags = ghist + (size_t)ps.passes * kOneRadix;
-  uint32_t* vals = scratch + ((pcv_onesweep_zero_words(n, bits) + 63) & ~(size_t)63);
-  static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&onesweep_keys_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  kOneTile * 8) == hipSuccess;
-  if (!attr_ok) return ctx->fail(PCV_E_HIP, "onesweep key sort: LDS");
-  {
-    PcvProf prof(ctx, PCV_K_SORT_UPSWEEP64);
-    hipLaunchKernelGGL(key_hist_kernel, dim3(kOneHistGroups), dim3(kOneBlock), 0, ctx->stream, keys_a, (uint32_t)n, ps, ghist);
-  }
-  bool in_a = true;
-  for (int p = 0; p < ps.passes; ++p) {
-    PcvProf prof(ctx, PCV_K_SORT_DOWNSWEEP64);
-    hipLaunchKernelGGL(onesweep_keys_kernel, dim3(tiles), dim3(kOneBlock), kOneTile * 8, ctx->stream, in_a ? keys_a : keys_b, in_a ? keys_b : keys_a,
-                       (uint32_t)n, ps.shift[p], ps.bits[p], ghist + (size_t)p * kOneRadix, tickets + p,
-                       flags + (size_t)p * tiles4, vals + (size_t)p * tiles * 2 * kOneRadix, diag);
-    in_a = !in_a;
-  }
-  PCV_HIP_CHECK(ctx, hipGetLastError());
-  *result_in_a = in_a;
-  return PCV_OK;
-}
-#endif  // PCV_EXPERIMENTS (onesweep host side)
 
 // two histograms + totals, the second pass's piece ranges, and the rank counts re-indexed by true rank (16 384 per sort
 // workgroup, 64 MB) — the last only for inputs whose record sort can take the two-pass rows path at all (12-byte records in
@@ -1848,15 +1494,8 @@ size_t pcv_sort_scratch_bytes(uint64_t n) {
 }
 
 // Does the first pass of a mapped 12-byte record sort with rank-count rows read the records' colour itself (PcvSortPayload::color_in)?
-// It does in the form that ships (the rows-based downsweep_rec12_kernel<..., MAP != 0>); the experiment variants of the record
-// kernel (PCV_REC_VARIANT, libpcv_hip_exp.so) do not.
-bool pcv_sort_first_pass_joins_color(uint64_t n) {
-  static const int rec_variant = [] {
-    const char* e = pcv_experiment("PCV_REC_VARIANT");
-    return e ? atoi(e) : 3;
-  }();
-  return n > 0 && rec_variant == 3;
-}
+// The rows-based downsweep_rec12_kernel<..., MAP != 0> does.
+bool pcv_sort_first_pass_joins_color(uint64_t n) { return n > 0; }
 
 int pcv_radix_sort_u64(pcv_ctx* ctx, uint64_t* keys_a, uint64_t* keys_b, uint64_t n, int begin_bit, int end_bit,
                        PcvSortPayload* payload, void* scratch, bool* result_in_a) {
@@ -1894,36 +1533,15 @@ int pcv_radix_sort_records_second(pcv_ctx* ctx, PcvSortSecond* sd, const PcvSort
     // colour-only records: tiles of 4 096 (512 lanes), TWO workgroups per CU — the pass is bound by its own phases (loads, LDS
     // ranking, barriers), not by bytes, and a second workgroup fills them: 0.69-0.70 -> 0.63-0.64 ms at 100 M points in one call
     // (tiles of 2 048, four workgroups: 0.75). With the intensity plane two workgroups' LDS does not fit: tiles of 8 192.
-    int settle_block = 512;
-#ifdef PCV_EXPERIMENTS
-    static const int settle_block_env = [] {  // PCV_SETTLE_BLOCK=1024 / 256 (libpcv_hip_exp.so)
-      const char* e = pcv_experiment("PCV_SETTLE_BLOCK");
-      return e ? atoi(e) : 0;
-    }();
-    if (settle_block_env) settle_block = settle_block_env;
-#endif
-#define PCV_REC12_SETTLE_B(B)                                                                                                            \
-  hipLaunchKernelGGL((downsweep_settle_kernel<false, B>), dim3(sd->pieces), dim3(B), 0, ctx->stream, sd->src, sd->dst, sd->n, sd->chunk,  \
-                     sd->pieces, sd->shift, sd->nbits, sd->hist, sd->totals, (const uint2*)sd->vec_src, (uint2*)sd->vec_dst,              \
-                     (const uint2*)sd->ranges, sd->order, sd->plane_src, sd->plane_dst, fz)
     if (sd->nbits > 7)  // ranks of 16 bits, colour-only: 256 digit values, tiles of 8 192
       hipLaunchKernelGGL((downsweep_settle_kernel<false, 1024, 256>), dim3(sd->pieces), dim3(1024), 0, ctx->stream, sd->src, sd->dst, sd->n,
                          sd->chunk, sd->pieces, sd->shift, sd->nbits, sd->hist, sd->totals, (const uint2*)sd->vec_src, (uint2*)sd->vec_dst,
                          (const uint2*)sd->ranges, sd->order, sd->plane_src, sd->plane_dst, fz);
-#ifdef PCV_EXPERIMENTS
-    else if (plane && settle_block == 512 && settle_block_env == 512)  // PCV_SETTLE_BLOCK=512 with the plane: two workgroups fill the LDS exactly
-      hipLaunchKernelGGL((downsweep_settle_kernel<true, 512>), dim3(sd->pieces), dim3(512), 0, ctx->stream, sd->src, sd->dst, sd->n, sd->chunk,
+    else if (plane) PCV_REC12_SETTLE(true, fz);
+    else
+      hipLaunchKernelGGL((downsweep_settle_kernel<false, 512>), dim3(sd->pieces), dim3(512), 0, ctx->stream, sd->src, sd->dst, sd->n, sd->chunk,
                          sd->pieces, sd->shift, sd->nbits, sd->hist, sd->totals, (const uint2*)sd->vec_src, (uint2*)sd->vec_dst,
                          (const uint2*)sd->ranges, sd->order, sd->plane_src, sd->plane_dst, fz);
-#endif
-    else if (plane) PCV_REC12_SETTLE(true, fz);
-#ifdef PCV_EXPERIMENTS
-    else if (settle_block == 1024) PCV_REC12_SETTLE_B(1024);
-    else if (settle_block == 256) PCV_REC12_SETTLE_B(256);
-#endif
-    else PCV_REC12_SETTLE_B(512);
-#undef PCV_REC12_SETTLE_B
-    (void)settle_block;
   } else {
     // (the caller decides with the same condition whether to pass `fuse`, pcv_build_finish `fuse_sort`; should the two ever drift
     // apart the build must not degrade silently into leaves nobody settles: one message per cause)
@@ -1946,39 +1564,3 @@ void pcv_sort_rec12_geometry(uint64_t n, int* groups, uint64_t* chunk) {
   *chunk = g.chunk;
 }
 
-#ifdef PCV_EXPERIMENTS
-// libpcv_hip_exp.so only: times `iters` key sorts of n pseudo-random `bits`-bit keys (HIP events around each sort);
-// onesweep != 0: pcv_sort_keys_onesweep (diag = timing-only variants of its kernel), else the three-kernel radix sort.
-__global__ void exp_fill_keys_kernel(uint64_t* k, uint32_t n, int bits, int top) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  uint64_t x = (uint64_t)i * 0x9e3779b97f4a7c15ull + 0x1234567ull;
-  x ^= x >> 29, x *= 0xbf58476d1ce4e5b9ull, x ^= x >> 32;
-  k[i] = (x & ((1ull << bits) - 1ull)) << (top - bits);
-}
-extern "C" int pcv_exp_time_key_sort(pcv_ctx* ctx, uint64_t n, int bits, int onesweep, int diag, int iters, float* ms_out) {
-  void *a = nullptr, *b = nullptr, *sc = nullptr, *sc2 = nullptr;
-  const int top = 3 * PCV_MAX_KEY_LEVELS;
-  int rc;
-  if ((rc = ctx->dev_alloc(&a, n * 8 + 256)) || (rc = ctx->dev_alloc(&b, n * 8 + 256)) ||
-      (rc = ctx->dev_alloc(&sc, pcv_onesweep_scratch_words(n, bits) * 4 + 64)) || (rc = ctx->dev_alloc(&sc2, pcv_sort_scratch_bytes(n))))
-    return rc;
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0), (void)hipEventCreate(&e1);
-  for (int it = 0; it < iters; ++it) {
-    hipLaunchKernelGGL(exp_fill_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (uint64_t*)a, (uint32_t)n, bits, top);
-    (void)hipMemsetAsync(sc, 0, pcv_onesweep_zero_words(n, bits) * 4, ctx->stream);
-    (void)hipEventRecord(e0, ctx->stream);
-    bool in_a;
-    if (onesweep) rc = pcv_sort_keys_onesweep(ctx, (uint64_t*)a, (uint64_t*)b, n, top - bits, top, (uint32_t*)sc, &in_a, diag);
-    else rc = pcv_radix_sort_u64(ctx, (uint64_t*)a, (uint64_t*)b, n, top - bits, top, nullptr, sc2, &in_a);
-    (void)hipEventRecord(e1, ctx->stream);
-    (void)hipEventSynchronize(e1);
-    (void)hipEventElapsedTime(&ms_out[it], e0, e1);
-    if (rc) break;
-  }
-  (void)hipEventDestroy(e0), (void)hipEventDestroy(e1);
-  ctx->dev_free(a), ctx->dev_free(b), ctx->dev_free(sc), ctx->dev_free(sc2);
-  return rc;
-}
-#endif

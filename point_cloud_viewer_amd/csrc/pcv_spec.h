@@ -23,19 +23,9 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-// Experiment switches (environment variables, each read once per process) exist only in libpcv_hip_exp.so, the build made
-// with -DPCV_EXPERIMENTS for the A/B scripts under tools/ and for the tests of the alternative kernels. The shipped
-// library reads no environment variable.
-inline const char* pcv_experiment(const char* name) {
-#ifdef PCV_EXPERIMENTS
-  return getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
-
 #include <vector>
+
+#include "pcv_switches.h"
 
 // Walk record of a T'' node (device, 32 bits so that the table of a 100 M-point tree fits the 32 KiB vector L1): inner:
 // first child index in bits 0..29 (the eight children are consecutive), leaf: predicted-leaf rank in bits 0..29.

@@ -1157,11 +1157,7 @@ void pcv_launch_node_split(pcv_ctx* ctx, const PcvNodeTableDev& t, const void* s
   int k = 1;
   // two levels per launch pair (u64 keys of one word; the scratch holds the lists of every open node a level can have:
   // an open node holds more than `max_points_per_node` keys, + the root and the forced level-1 nodes)
-  static const bool two_levels = [] {
-    const char* e = pcv_experiment("PCV_SPLIT2");  // experiments: 0 = one level per launch pair
-    return !e || atoi(e) != 0;
-  }();
-  if (two_levels && !keys32 && !sorted_lo && max_points_per_node > 0 && t.max_open >= (uint64_t)n / max_points_per_node + 16) {
+  if (pcv_switches().split2 && !keys32 && !sorted_lo && max_points_per_node > 0 && t.max_open >= (uint64_t)n / max_points_per_node + 16) {
     const unsigned grid = (unsigned)std::min<uint64_t>(t.max_open, (uint64_t)n / max_points_per_node + 16);
     int cur = 0;
     while (k <= lv.nlevels && k <= PCV_MAX_KEY_LEVELS) {

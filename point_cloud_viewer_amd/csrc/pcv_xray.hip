@@ -31,7 +31,7 @@
 #include <vector>
 
 #include "pcv_query_dev.h"
-#include "pcv_spec.h"  // pcv_experiment
+#include "pcv_switches.h"
 
 namespace {
 
@@ -889,7 +889,7 @@ static int plan_groups(const uint64_t* kept, uint64_t nc, const uint64_t* leaf_p
   const uint64_t rec_bytes = p->strategy == PCV_XRAY_HEIGHT_STDDEV || binned ? 16 : 8, bucket_bytes = 16ull * nblocks;
   // a group also holds at most kMaxGroupBuckets buckets; the experiment build can lower that (tests of the grouping)
   uint64_t max_group_buckets = kMaxGroupBuckets;
-  if (const char* e = pcv_experiment("PCV_XRAY_MAX_GROUP_BUCKETS")) max_group_buckets = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+  if (pcv_switches().xray_max_group_buckets) max_group_buckets = pcv_switches().xray_max_group_buckets;
   const uint64_t max_group_tiles = std::max<uint64_t>(1, max_group_buckets / nblocks);
   group_first.assign(1, 0);
   uint64_t cur = 0, max_pts = 0, max_tiles = 0, pts = 0;
@@ -1123,8 +1123,8 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pc
   // the sorted accumulation's LDS bucket limit (records, a power of two); the experiment build can lower it so that
   // small buckets take the global path
   uint32_t sort_cap = binned ? kSortCapBinned : kSortCapPlain;
-  if (const char* e = pcv_experiment("PCV_XRAY_SORT_LDS_RECORDS")) {
-    const uint64_t v = std::min<uint64_t>(std::max<uint64_t>(2, strtoull(e, nullptr, 10)), sort_cap);
+  if (pcv_switches().xray_sort_lds_records) {
+    const uint64_t v = std::min<uint64_t>(std::max<uint64_t>(2, pcv_switches().xray_sort_lds_records), sort_cap);
     sort_cap = 2;
     while ((uint64_t)sort_cap * 2 <= v) sort_cap *= 2;
   }
@@ -1143,7 +1143,7 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pc
   else
     PCV_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xray_accum_kernel<PCV_XRAY_HEIGHT_STDDEV, 256>, 256, 0));
   uint64_t accum_grid = (uint64_t)std::max(cus, 1) * (uint64_t)std::max(per_cu, 1);
-  if (const char* e = pcv_experiment("PCV_XRAY_ACCUM_GRID")) accum_grid = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+  if (pcv_switches().xray_accum_grid) accum_grid = pcv_switches().xray_accum_grid;
   for (size_t gi = 0; gi + 1 < group_first.size(); ++gi) {
     const uint64_t f = group_first[gi], l = group_first[gi + 1];  // created tiles [f, l)
     ba.trees = d_trees + tree_first[gi];
