@@ -1,23 +1,24 @@
 """pcv_xray_* (xray leaf tiles rasterised on the device) against xray_oracle, the numpy restatement of
 xray/src/generation.rs over the CPU oracle's octree: the created set, every tile's RGBA, the drawn-point counts, and their
-agreement with the batched point query."""
+agreement with the batched point query. `colored` is held byte for byte to xray_truth's exact-integer oracle and
+`height_stddev` to its interval truth; the arrival-order restatement stays beside them as the tie to the reference."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
 import point_cloud_viewer_amd as pcv
+import xray_many_oracle as M
 import xray_oracle as X
+import xray_truth as T
 from point_cloud_viewer_amd import synthetic
 from test_gpu_query import ctx, scene  # noqa: F401  (module fixtures)
 from test_gpu_query_batch import scene_of
 
 pytestmark = pytest.mark.gpu
 W, PX = 64, 0.25  # the 300 000-point scene of test_gpu_query: 3 levels, 64 leaf tiles of 16 m
-QN = np.array([0.1, -0.2, 0.3, 0.9])
-ISO = [-2_700_123.25, -4_300_456.5, 3_800_789.75] + list(QN / math.sqrt(float(QN @ QN)))  # config 5 scale
+ISO = T.ISO  # config 5 scale
 
 
 def tree_points(s):
@@ -59,6 +60,8 @@ def test_xray_matches_oracle(scene, tp, background):  # noqa: F811
 
 
 def check_close(got, want, exact_share):
+    """against the arrival-order oracle (one order the reference may take): within 1, and `exact_share` of the pixels equal.
+    Every caller also holds the same run to xray_truth, which leaves no such slack."""
     assert set(got) == set(want)
     exact = total = 0
     for name, (img, drawn) in want.items():
@@ -73,16 +76,33 @@ def check_close(got, want, exact_share):
     assert total > 0 and exact >= exact_share * total, (exact, total)
 
 
-def test_colored_matches_oracle(scene, tp):  # noqa: F811
+def check_colored_exact(got, g, pts, tile_px=W, background="white"):
+    """every byte of every created tile against the exact-integer oracle"""
+    want = T.colored_tiles(g, pts, tile_px, background)
+    check_exact(got, want)
+    px = sum(int((img[..., 3] == 255).sum()) for img, _ in want.values()) if background == "transparent" else len(want) * tile_px ** 2
+    print(f"colored: {len(want)} tiles, {px} pixels compared, all equal")
+
+
+@pytest.fixture(scope="module")
+def pts(tp):
+    return M.tile_points([tp], W, PX)
+
+
+def test_colored_matches_oracle(scene, tp, pts):  # noqa: F811
     _, got = run(scene["tree"], "colored")
+    check_colored_exact(got, *pts)
+    _, got_t = run(scene["tree"], "colored", background="transparent")
+    check_colored_exact(got_t, *pts, background="transparent")
     want, _ = X.xray_tiles(tp, W, PX, "colored")
     check_close(got, want, 0.99)
 
 
 @pytest.mark.parametrize("cmap", ["jet", "purplish"])
-def test_height_stddev_matches_oracle(scene, tp, cmap):  # noqa: F811
+def test_height_stddev_matches_oracle(scene, tp, pts, cmap):  # noqa: F811
     strat = ("height_stddev", 1.5, cmap)
     _, got = run(scene["tree"], strat, background="transparent")
+    T.stddev_check(got, *pts, W, 1.5, cmap, "transparent")
     want, _ = X.xray_tiles(tp, W, PX, strat, background="transparent")
     check_close(got, want, 0.0)
 
@@ -149,28 +169,12 @@ def test_batch_agreement(ctx, scene, tp):  # noqa: F811
 
 def test_edge_cloud(ctx):  # noqa: F811
     """Points on tile faces and on the min.y face (y == H: never drawn), a pixel with all 1 024 z buckets of a half-open
-    box, 10^6 points in one pixel, and a sorted copy of the same cloud (same bytes)."""
-    rng = np.random.default_rng(5)
-    edge = 16.0  # W x PX
-    pts = []
-    # tile (0, 0) of a 2 x 2 grid: a column in one pixel with a point in each of the 1 024 z buckets, and 10^6 points in
-    # another pixel
-    zs = (np.arange(1024) + 0.5) / 1024 * 8.0
-    pts.append(np.stack([np.full(1024, 3.1), np.full(1024, 5.1), zs], 1))
-    dense = np.stack([np.full(1_000_000, 1.05), np.full(1_000_000, 1.05), rng.uniform(0, 8.0, 1_000_000)], 1)
-    pts.append(dense)
-    # tile (1, 0): only points on its min.y face (y == tile min y == 0): created, nothing drawn
-    pts.append(np.stack([rng.uniform(edge, 2 * edge - 0.01, 300), np.zeros(300), rng.uniform(0, 8.0, 300)], 1))
-    # tile (0, 1) and (1, 1): points on the shared x face and on pixel lines (off the y == 16 face, whose points could
-    # decode a quantum lower, into tile (1, 0))
-    gx, gy = np.meshgrid(np.arange(0.0, 2 * edge, 0.25), np.arange(edge + 0.125, 2 * edge, 0.25))
-    pts.append(np.stack([gx.ravel(), gy.ravel(), np.full(gx.size, 4.0)], 1))
-    p = np.concatenate(pts)
-    p = np.concatenate([p, [[0.0, 0.0, 0.0], [2 * edge - 1e-9, 2 * edge - 1e-9, 8.0]]])  # pin the box
-    rgb = rng.integers(0, 256, (p.shape[0], 3)).astype(np.uint8)
-    bmin, bmax = p.min(0), p.max(0)
+    box, 10^6 points in one pixel, pixels of one point and pixels whose points share one z (deviation 0), and a sorted copy
+    of the same cloud (same bytes). colored byte for byte against the exact-integer oracle, height_stddev against the
+    interval truth."""
+    p, rgb, bmin, bmax, orders = T.edge_cloud()
     results = []
-    for order in (rng.permutation(p.shape[0]), np.lexsort((p[:, 2], p[:, 1], p[:, 0]))):
+    for order in orders:
         x, y, z = (np.ascontiguousarray(p[order, a]) for a in range(3))
         s = scene_of(ctx, x, y, z, np.ascontiguousarray(rgb[order]), None, bmin, bmax, 20_000)
         tpp = tree_points(s)
@@ -185,6 +189,14 @@ def test_edge_cloud(ctx):  # noqa: F811
         col = got["r0"][0]
         assert tuple(col[W - 1 - int(5.1 / PX), int(3.1 / PX)]) == (0, 0, 0, 255)  # n = 1 024: ln(n) / ln(1024) = 1
         _, cgot = run(s["tree"], "colored")
+        tile_pts = M.tile_points([tpp], W, PX)
+        check_colored_exact(cgot, *tile_pts)
+        for cmap in ("jet", "purplish"):
+            _, sgot = run(s["tree"], ("height_stddev", 1.5, cmap))
+            T.stddev_check(sgot, *tile_pts, W, 1.5, cmap)
+        # equal z, n = 2 and 3: deviation 0 (an interval from 0 up, where only the colour of 0 passes), purplish(0) = (204, 204, 255)
+        for i in range(2):
+            assert tuple(sgot["r0"][0][W - 1 - int(9.1 / PX), int((7.1 + 0.5 * i) / PX)]) == (204, 204, 255, 255), i
         results.append((got, cgot))
         s["tree"].free()
     (a, ca), (b, cb) = results
@@ -192,21 +204,19 @@ def test_edge_cloud(ctx):  # noqa: F811
         assert np.array_equal(a[n][0], b[n][0]) and np.array_equal(ca[n][0], cb[n][0]), n
 
 
-def test_four_encodings_and_opened_directory(ctx, tmp_path):  # noqa: F811
-    x, y, z, rgb, bmin, bmax = synthetic.gaussian_clusters(340_000, seed=12, num_clusters=6, extent=30000.0,
-                                                           sigma_range=(5.0, 400.0), offset=(-2.7e6, -4.3e6, 3.8e6))
-    rng = np.random.default_rng(13)
-    c = np.array([x[0], y[0], z[0]])
-    x = np.concatenate([x, c[0] + rng.normal(0.0, 0.03, 60_000)])
-    y = np.concatenate([y, c[1] + rng.normal(0.0, 0.03, 60_000)])
-    z = np.concatenate([z, c[2] + rng.normal(0.0, 0.03, 60_000)])
-    rgb = synthetic.index_colors(x.size)
-    bmin, bmax = np.array([x.min(), y.min(), z.min()]), np.array([x.max(), y.max(), z.max()])
-    inten = (np.arange(x.size) % 251).astype(np.float32)
-    s = scene_of(ctx, x, y, z, rgb, inten, bmin, bmax, 1500)
-    tree = s["tree"]
+@pytest.fixture(scope="module")
+def ecef(ctx):  # noqa: F811
+    x, y, z, rgb, inten, bmin, bmax, cap = T.ecef_cloud()
+    s = scene_of(ctx, x, y, z, rgb, inten, bmin, bmax, cap)
+    s.update(x=x, y=y, z=z, rgb=rgb, inten=inten, tp=tree_points(s))
+    yield s
+    s["tree"].free()
+
+
+def test_four_encodings_and_opened_directory(ctx, ecef, tmp_path):  # noqa: F811
+    s, tree, tpp = ecef, ecef["tree"], ecef["tp"]
+    x, y, z, rgb, inten, bmin, bmax = (s[k] for k in ("x", "y", "z", "rgb", "inten", "bmin", "bmax"))
     assert {tree.node(i).encoding for i in range(tree.num_nodes) if tree.node(i).num_points > 0} == {1, 2, 3, 4}
-    tpp = tree_points(s)
     _, got = run(tree, "xray", tile_size_px=128, pixel_size_m=32.0)
     want, _ = X.xray_tiles(tpp, 128, 32.0, "xray")
     check_exact(got, want)
@@ -224,7 +234,20 @@ def test_four_encodings_and_opened_directory(ctx, tmp_path):  # noqa: F811
     dev = xt.images(0, 2, device=True)
     assert np.array_equal(dev.cpu().numpy(), xt.images(0, 2))
     opened.free()
-    tree.free()
+
+
+@pytest.mark.parametrize("iso", [None, ISO], ids=["plain", "query_from_global"])
+def test_colored_and_height_stddev_at_ecef_scale(ecef, iso):
+    """The four-encodings cloud, z of order 10^6 in both frames: colored byte for byte, height_stddev (two passes; one
+    pass would lose the deviation here) against the interval truth."""
+    kw = dict(tile_size_px=T.ECEF_W, pixel_size_m=T.ECEF_PX, **({} if iso is None else dict(query_from_global=iso)))
+    tile_pts = M.tile_points([ecef["tp"]], T.ECEF_W, T.ECEF_PX, iso)
+    _, got = run(ecef["tree"], "colored", **kw)
+    check_colored_exact(got, *tile_pts, tile_px=T.ECEF_W)
+    intervals = T.stddev_intervals(*tile_pts, T.ECEF_W)
+    for cmap in ("jet", "purplish"):
+        _, got = run(ecef["tree"], ("height_stddev", T.ECEF_MAX_STDDEV, cmap), background="transparent", **kw)
+        T.stddev_check(got, *tile_pts, T.ECEF_W, T.ECEF_MAX_STDDEV, cmap, "transparent", intervals)
 
 
 def test_closed_query_faces_with_identity_transform(ctx):  # noqa: F811

@@ -1,6 +1,7 @@
 """colored_with_intensity and binning on the device (pcv_xray_run_ex, OctreeResult / Context .xray_tiles with
 min_intensity / max_intensity / binning) against tests/xray_intensity_oracle.py: the created set, drawn and negative counts,
-alpha exactly and RGB within 1; binned colored; bytes independent of scheduling, tile grouping, the LDS limit of the
+and every byte of every tile (the oracle takes the device's documented order: f32 sums in ascending (pixel, bin, value
+bits) order, exact integer colour sums); binned colored; bytes independent of scheduling, tile grouping, the LDS limit of the
 sorted accumulation and octree order; an edge cloud of negative, NaN and infinite intensities; two octrees; the quadtree
 and its PNG files."""
 import hashlib
@@ -38,23 +39,18 @@ def run(tree, strategy, **kw):
     return got
 
 
-def check(got, want, exact_share=None, exact_tiles=False):
+def check(got, want):
+    """byte for byte: the sorted strategies reduce in key order, which the oracle restates"""
     assert set(got) == set(want)
-    exact = total = 0
+    total = 0
     for name, (img, drawn, neg) in want.items():
         g = got[name][0]
         assert got[name][1] == drawn and got[name][2] == neg, name
-        assert np.array_equal(g[..., 3], img[..., 3]), name
         d = np.abs(g.astype(int) - img.astype(int))
-        if exact_tiles:
-            assert d.max() == 0, (name, int((d > 0).any(-1).sum()))
-        assert d.max() <= 1, name
-        px = img[..., 3] == 255
-        exact += int((d[px] == 0).all(-1).sum())
-        total += int(px.sum())
+        assert d.max() == 0, (name, int((d > 0).any(-1).sum()), int(d.max()))
+        total += int((img[..., 3] == 255).sum())
     assert total > 0
-    if exact_share is not None:
-        assert exact >= exact_share * total, (exact, total)
+    print(f"sorted: {len(want)} tiles, {total} drawn pixels, all equal")
 
 
 def digest(got):
@@ -68,15 +64,14 @@ def test_colored_with_intensity_matches_oracle(scene, tp, lo, hi, bin_size):  # 
     got = run(scene["tree"], "colored_with_intensity", min_intensity=lo, max_intensity=hi, binning=binning)
     want, _ = I.xray_tiles([tp], W, PX, "colored_with_intensity", lo, hi, bin_size)
     assert 8 < len(want) < 64 and all(v[2] == 0 for v in want.values())
-    # integer intensities (i % 251): with one bin the f32 sums are exact, so nearly every pixel is
-    check(got, want, exact_share=0.99 if bin_size is None else None)
+    check(got, want)
 
 
 @pytest.mark.parametrize("bin_size", [16.0, 1e-3])
 def test_binned_colored_matches_oracle(scene, tp, bin_size):  # noqa: F811
     got = run(scene["tree"], "colored", binning=("intensity", bin_size))
     want, _ = I.xray_tiles([tp], W, PX, "colored", bin_size=bin_size)
-    check(got, want, exact_share=0.99)
+    check(got, want)
     # one bin (every i % 251 / 1e30 truncates to 0) through xray_sorted equals unbinned colored through xray_accum byte for
     # byte: the same exact channel sums, rounded once
     plain = run(scene["tree"], "colored")
@@ -133,7 +128,7 @@ def test_determinism_grouping_and_global_path(ctx, tmp_path):  # noqa: F811
         ref[key] = digest(a)
         want, _ = I.xray_tiles([tpp], W, PX, strategy, kw.get("min_intensity", 0.0), kw.get("max_intensity", 1.0),
                                binning[1] if binning else None)
-        check(a, want, exact_share=0.99)
+        check(a, want)
         # the 60 000 points of the 1 m square fall into at most 4 buckets of 8 m, so one holds more than 8 192 records,
         # the LDS limit: the global path ran
         assert sum(v[1] for v in want.values()) > 60_000 and max(v[1] for v in want.values()) > 15_000
@@ -174,12 +169,12 @@ def test_edge_intensities(ctx):  # noqa: F811
             want, _ = I.xray_tiles([tpp], W, PX, "colored_with_intensity", lo, hi, bin_size)
             assert sum(v[2] for v in want.values()) == idx.size
             # one point per pixel: every mean is exact, so every pixel is, in tiles with and without negatives
-            check(got, want, exact_tiles=True)
+            check(got, want)
             neg_tiles = {n for n, v in want.items() if v[2]}
             assert neg_tiles == {"r0"}
         got = run(s["tree"], "colored", binning=("intensity", 0.0))
         want, _ = I.xray_tiles([tpp], W, PX, "colored", bin_size=0.0)
-        check(got, want, exact_tiles=True)
+        check(got, want)
         assert all(v[2] == 0 for v in got.values())
     s["tree"].free()
 

@@ -13,7 +13,8 @@ import point_cloud_viewer_amd as pcv
 import xray_many_oracle as M
 from point_cloud_viewer_amd import synthetic
 from test_gpu_query import ctx  # noqa: F401  (module fixture)
-from test_gpu_xray import ISO, check_close, tree_points
+import xray_truth as T
+from test_gpu_xray import ISO, check_close, check_colored_exact, tree_points
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,11 +22,7 @@ W, PX = 64, 1.0  # the union below spans 256 ..= 512 m: 3 levels, 64 leaf tiles 
 
 
 def make_scene(ctx, n, seed, res, offset, extent, with_intensity, cap, pad=None):  # noqa: F811
-    x, y, z, rgb, bmin, bmax = synthetic.gaussian_clusters(n, seed=seed, num_clusters=5, extent=extent, sigma_range=(0.5, 6.0),
-                                                           offset=offset)
-    if pad is not None:  # a meta box larger than the points: the union must still take all of it
-        bmin, bmax = bmin - np.asarray(pad[0]), bmax + np.asarray(pad[1])
-    inten = (np.arange(x.size) % 251).astype(np.float32) if with_intensity else None
+    x, y, z, rgb, inten, bmin, bmax = T.many_cloud(n, seed, res, offset, extent, with_intensity, cap, pad)
     tree = ctx.build(res, pcv.Aabb(bmin, bmax), x, y, z, rgb, inten, max_points_per_node=cap)
     with O.max_points_per_node(cap):
         want = O.build_closed(res, bmin, bmax, x, y, z, rgb, inten, threads=4)
@@ -37,10 +34,7 @@ def make_scene(ctx, n, seed, res, offset, extent, with_intensity, cap, pad=None)
 def scenes(ctx):  # noqa: F811
     """a: 0.001 m, intensity; b: 0.05 m (other node encodings), no intensity, overlapping a, its meta box padded by 100 m
     in +y (the union's max y, with no point near it); c: 0.002 m, intensity, disjoint from both"""
-    a = make_scene(ctx, 150_000, 21, 0.001, (0.0, 0.0, 0.0), 100.0, True, 2000)
-    b = make_scene(ctx, 120_000, 22, 0.05, (50.0, 30.0, 5.0), 60.0, False, 1500, pad=([0.0, 0.0, 0.0], [0.0, 100.0, 0.0]))
-    c = make_scene(ctx, 80_000, 23, 0.002, (250.0, -80.0, 0.0), 40.0, True, 1000)
-    return [a, b, c]
+    return [make_scene(ctx, *args) for args in T.MANY]
 
 
 @pytest.fixture(scope="module")
@@ -115,11 +109,15 @@ def test_colored_and_height_stddev_over_three_octrees(ctx, scenes, tps, points):
     xt, got = run(ctx, trees, "colored")
     want, _ = M.xray_tiles(tps, W, "colored", points=points("plain"))
     assert [int(k) for k in xt.kept] == [want[n][2] for n in xt.created_ids]
+    check_colored_exact(got, *points("plain"))
     check_close(got, {n: v[:2] for n, v in want.items()}, 0.98)
-    strat = ("height_stddev", 1.5, "jet")
-    _, got = run(ctx, trees, strat, background="transparent")
-    want, _ = M.xray_tiles(tps, W, strat, "transparent", points=points("plain"))
-    check_close(got, {n: v[:2] for n, v in want.items()}, 0.0)
+    intervals = T.stddev_intervals(*points("plain"), W)
+    for cmap in ("jet", "purplish"):
+        strat = ("height_stddev", 1.5, cmap)
+        _, got = run(ctx, trees, strat, background="transparent")
+        T.stddev_check(got, *points("plain"), W, 1.5, cmap, "transparent", intervals)
+        want, _ = M.xray_tiles(tps, W, strat, "transparent", points=points("plain"))
+        check_close(got, {n: v[:2] for n, v in want.items()}, 0.0)
 
 
 def same_quadtree(a, b, exact=True):
@@ -148,6 +146,8 @@ def test_one_octree_list_equals_xray_run(ctx, scenes, kw):  # noqa: F811
         a, _ = run(ctx, [tree], strat, pixel_size_m=0.25, **kw)  # 16 m tiles over tree a's ~110 m
         b, _ = run_one(tree, strat, pixel_size_m=0.25, **kw)
         assert a.num_created > 8
+        # height_stddev keeps the slack: its leaves are pinned to an interval of the true deviation, not to bytes, and two
+        # runs may round an ambiguous pixel differently (f64 LDS atomics in scheduling order)
         same_quadtree(a, b, exact=isinstance(strat, str))
         a.free()
         b.free()
