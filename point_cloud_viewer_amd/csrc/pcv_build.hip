@@ -21,6 +21,7 @@
 
 #include "pcv_internal.h"
 #include "pcv_spec.h"
+#include "pcv_tables.h"
 
 // ------------------------------------------------------------------------------------------------
 // context, pool
@@ -714,7 +715,6 @@ struct PcvBuild {
   uint64_t *keys_a = nullptr, *keys_b = nullptr;
   void* sort_scratch = nullptr;
   uint32_t M = 0;
-  size_t host_bytes = 0;
   std::vector<uint64_t> pre;  // |pre(node)| stream lengths, bottom-up
   bool deep = false;          // more than PCV_MAX_KEY_LEVELS levels: second key word, prefix_lo in the node table
   int levels = 0;             // levels the level tables are valid for in K5/K6 (full depth, or the deep depth)
@@ -726,10 +726,7 @@ struct PcvBuild {
   const uint32_t* spec_rows = nullptr;  // rank counts per sort workgroup (pcv_launch_rank_hist_rows), or null
   PcvSortSecond sort_second;            // the record sort's second pass, held back until the node tables are up (pcv_build_finish)
   uint64_t wide_levels = 0;      // bit k: level k is Float32-coded
-  struct FixRange {
-    uint32_t lo, count, level;
-  };
-  std::vector<FixRange> fix_ranges;  // sorted slots whose points replay the chain after the record sort
+  std::vector<PcvFixRange> fix_ranges;  // sorted slots whose points replay the chain after the record sort
   const uint32_t* spec_map_dev = nullptr;  // set: the record sort's first upsweep applies the rank map
   uint32_t spec_map_entries = 0;
   // true leaves below a split first candidate (PcvTrueTree::cont_nodes / cont_from): their chain is continued after the sort
@@ -915,8 +912,6 @@ extern "C" int pcv_octree_copy_nodes(const pcv_octree* t, const pcv_node_copy* c
 // ------------------------------------------------------------------------------------------------
 // the build
 // ------------------------------------------------------------------------------------------------
-static uint64_t ceil8(uint64_t v) { return (v + 7) / 8; }
-
 static int build_begin_impl(pcv_ctx* ctx, const pcv_build_params* params, const pcv_points* points,
                             const pcv_routed_points* routed, pcv_octree** out, const PcvTrueTree* given_tree = nullptr);
 extern "C" int pcv_build_begin(pcv_ctx* ctx, const pcv_build_params* params, const pcv_points* points,
@@ -1415,6 +1410,143 @@ static int single_chain_topology(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, cons
   return PCV_OK;
 }
 
+// Scratch for the device node table of a build of n points: capacity for every level down to `max_level` (incl. the deep retry).
+static int alloc_node_table(PcvScratch& sc, uint64_t n, uint32_t max_points, int max_level, PcvNodeTableDev* out) {
+  int rc;
+  PcvNodeTableDev& nt = *out;
+  const int deepest = max_level < PCV_MAX_LEVELS ? max_level : PCV_MAX_LEVELS;
+  uint64_t cap64 = 8ull * (uint64_t)(deepest + 1) * (n / max_points + 1) + 64;
+  if (cap64 > (1ull << 26)) cap64 = 1ull << 26;
+  const uint32_t cap = (uint32_t)cap64;
+  nt.capacity = cap;
+  nt.prefix_lo = nullptr;
+  if ((rc = sc.get(&nt.prefix, cap)) || (rc = sc.get(&nt.lo, cap)) || (rc = sc.get(&nt.hi, cap)) ||
+      (rc = sc.get(&nt.parent, cap)) || (rc = sc.get(&nt.first_child, cap)) || (rc = sc.get(&nt.level, cap)) ||
+      (rc = sc.get(&nt.child_mask, cap)) || (rc = sc.get(&nt.open, cap)) ||
+      (rc = sc.get(&nt.counters, 64)))
+    return rc;
+  // (the sample tree of the single-chain build splits at a LOWERED threshold: twice the open nodes the capacity allows)
+  nt.max_open = (uint32_t)std::min<uint64_t>(2 * (n / max_points + 1) + 64, 1u << 22);
+  return sc.get(&nt.bounds, std::max((size_t)cap * 9, (size_t)nt.max_open * 85));
+}
+
+// Depth speculation of the exact build: full-depth keys of a strided sample (2^18 points), sorted; *levels = the key levels the
+// main pass needs if the sample is right (K4 verifies), left alone when that is the full depth.
+static int probe_depth(pcv_ctx* ctx, PcvBuild* bs, uint32_t max_points, int full_levels, int* levels) {
+  int rc;
+  hipStream_t st = ctx->stream;
+  const DevPoints& d = bs->d;
+  const uint64_t n = bs->n;
+  const uint32_t ns = 1u << 18;
+  const uint64_t stride = n / ns;
+  uint32_t* d_max;
+  if ((rc = bs->sc.get(&d_max, 64))) return rc;
+  PCV_HIP_CHECK(ctx, hipMemsetAsync(d_max, 0, 4, st));
+  pcv_launch_chain_keys(ctx, bs->lv, ns, stride, d.x, d.y, d.z, bs->keys_a, false, d.routed);
+  bool s_in_a = true;
+  // the probe only has to tell depths up to kProbeLevels apart (deeper -> no speculation): sort those digits only
+  const int kProbeLevels = 14;
+  const int probe_levels = full_levels < kProbeLevels ? full_levels : kProbeLevels;
+  if ((rc = pcv_radix_sort_u64(ctx, bs->keys_a, bs->keys_b, ns, 3 * (PCV_MAX_KEY_LEVELS - probe_levels), 3 * PCV_MAX_KEY_LEVELS,
+                               nullptr, bs->sort_scratch, &s_in_a)))
+    return rc;
+  double gapd = 0.6 * (double)max_points * (double)ns / (double)n;
+  uint32_t gap = gapd < 1.0 ? 1u : (uint32_t)gapd;
+  pcv_launch_depth_probe(ctx, s_in_a ? bs->keys_a : bs->keys_b, ns, gap, d_max);
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(ctx->mailbox, d_max, 4, hipMemcpyDeviceToHost, st));
+  PCV_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  const uint32_t shared = *(const uint32_t*)ctx->mailbox;
+  // a level-`shared` node is (probably) split -> nodes of level shared + 1 exist -> that many digits are needed;
+  // a prefix shared down to the last sorted level says nothing about the levels below it
+  int want = (int)shared >= probe_levels ? full_levels : (int)shared + 1;
+  if (want < 3) want = 3;
+  if (want < full_levels) *levels = want;
+  return PCV_OK;
+}
+
+// Deep tree: a second key word for levels 22..40 (heavy duplicates in a cube with edge/resolution > 2^21). Rare path, built
+// from existing pieces: digits as four 32-bit words, four stable LSD sorts (one per word, least significant first, the other
+// three travel as payload planes), then the split with both words.
+static int split_deep_tree(pcv_ctx* ctx, PcvBuild* bs, const pcv_build_params* params, uint32_t max_points, int deep_levels,
+                           PcvNodeTableDev* nt) {
+  int rc;
+  PcvScratch& sc = bs->sc;
+  const DevPoints& d = bs->d;
+  const uint64_t n = bs->n;
+  bs->deep = true;
+  bs->lv.nlevels = deep_levels;
+  uint32_t* W[4][2];
+  for (int j = 0; j < 4; ++j)
+    for (int sd = 0; sd < 2; ++sd)
+      if ((rc = sc.get(&W[j][sd], n))) return rc;
+  uint32_t* first[4] = {W[0][0], W[1][0], W[2][0], W[3][0]};
+  pcv_launch_chain_keys_deep(ctx, bs->lv, n, d.x, d.y, d.z, d.routed, first);
+  int side = 0;
+  for (int j = 3; j >= 0; --j) {
+    PcvSortPayload pl;
+    pl.nwords = 3;
+    int w = 0;
+    for (int o = 0; o < 4; ++o) {
+      if (o == j) continue;
+      pl.in[w] = W[o][side];
+      pl.out[w] = W[o][1 - side];
+      ++w;
+    }
+    bool in_a = true;
+    if ((rc = pcv_radix_sort_u32(ctx, W[j][side], W[j][1 - side], n, 0, 32, &pl, bs->sort_scratch, &in_a))) return rc;
+    if (!in_a) side = 1 - side;
+  }
+  const uint32_t* sorted_words[4] = {W[0][side], W[1][side], W[2][side], W[3][side]};
+  pcv_launch_combine_words(ctx, n, sorted_words, bs->keys_a, bs->keys_b);  // keys_a = first word, keys_b = second word
+  if ((rc = sc.get(&nt->prefix_lo, nt->capacity))) return rc;
+  bs->d_prefix_lo = nt->prefix_lo;
+  pcv_launch_node_split(ctx, *nt, bs->keys_a, false, (uint32_t)n, bs->lv, params->resolution, max_points,
+                        (params->flags >> 8) & 0xffu, bs->keys_b);
+  ctx->stage_end(PCV_STAGE_NODE_SPLIT);
+  ctx->stage_begin(PCV_STAGE_TABLE);
+  return PCV_OK;
+}
+
+// What the node split left in its counters ([0] nodes, [1] bit 0: a node at the last key level would still be split), through
+// the pinned mailbox; a full node table is an error here.
+static int read_split_counters(pcv_ctx* ctx, const PcvNodeTableDev& nt, uint32_t counters[64]) {
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(ctx->mailbox, nt.counters, 64 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  std::memcpy(counters, ctx->mailbox, 64 * sizeof(uint32_t));
+  if (counters[1] & 2u) return ctx->fail(PCV_E_OOM, "node table capacity exceeded");
+  return PCV_OK;
+}
+
+// The tree's node table into the context's pinned block (pcv_tables.h), reserved here for everything pcv_build_finish will put
+// behind it: downloaded from the device table, or copied from the true tree the single-chain build derived on the host.
+static int stage_node_table(pcv_ctx* ctx, const PcvBuild* bs, const PcvNodeTableDev& nt, const PcvTrueTree* tt) {
+  int rc;
+  const uint32_t M = bs->M;
+  if ((rc = ctx->pinned_reserve(pcv_table_pinned_bytes(M, bs->n, bs->deep)))) return rc;
+  const PcvStagedTable tb = pcv_staged_table(ctx->pinned, M, bs->deep);
+  if (tt) {
+    std::memcpy(tb.prefix, tt->prefix.data(), (size_t)M * 8);
+    std::memcpy(tb.lo, tt->lo.data(), (size_t)M * 4);
+    std::memcpy(tb.hi, tt->hi.data(), (size_t)M * 4);
+    std::memcpy(tb.first_child, tt->first_child.data(), (size_t)M * 4);
+    std::memcpy(tb.level, tt->level.data(), (size_t)M);
+    std::memcpy(tb.child_mask, tt->child_mask.data(), (size_t)M);
+    std::memcpy(tb.open, tt->open.data(), (size_t)M);
+    return PCV_OK;
+  }
+  hipStream_t st = ctx->stream;
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(tb.prefix, nt.prefix, (size_t)M * 8, hipMemcpyDeviceToHost, st));
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(tb.lo, nt.lo, (size_t)M * 4, hipMemcpyDeviceToHost, st));
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(tb.hi, nt.hi, (size_t)M * 4, hipMemcpyDeviceToHost, st));
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(tb.first_child, nt.first_child, (size_t)M * 4, hipMemcpyDeviceToHost, st));
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(tb.level, nt.level, (size_t)M, hipMemcpyDeviceToHost, st));
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(tb.child_mask, nt.child_mask, (size_t)M, hipMemcpyDeviceToHost, st));
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(tb.open, nt.open, (size_t)M, hipMemcpyDeviceToHost, st));
+  if (bs->deep) PCV_HIP_CHECK(ctx, hipMemcpyAsync(tb.prefix_lo, nt.prefix_lo, (size_t)M * 8, hipMemcpyDeviceToHost, st));
+  PCV_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  return PCV_OK;
+}
+
 static int build_begin_impl(pcv_ctx* ctx, const pcv_build_params* params, const pcv_points* points,
                             const pcv_routed_points* routed, pcv_octree** out, const PcvTrueTree* given_tree) {
   int rc;
@@ -1440,6 +1572,8 @@ static int build_begin_impl(pcv_ctx* ctx, const pcv_build_params* params, const 
     }
   } guard{t};
   PCV_HIP_CHECK(ctx, hipEventRecord(ctx->ev[0], st));
+  // (input placement and box stay inline: they hand on the staged points, the box, both key buffers and the sort scratch, and
+  // take three of those while K1 runs — too wide an interface for a function of its own)
   for (bool& on : ctx->stage_on) on = false;
   for (bool& open : ctx->stage_open) open = false;
   ctx->stage_times = bs->stage_times = (params->flags & PCV_BUILD_STAGE_TIMES) != 0;
@@ -1515,22 +1649,7 @@ static int build_begin_impl(pcv_ctx* ctx, const pcv_build_params* params, const 
 
   // device node table (the sample tree of the single-chain build, the tree itself in the exact build)
   PcvNodeTableDev nt;
-  {
-    const int deepest = max_level < PCV_MAX_LEVELS ? max_level : PCV_MAX_LEVELS;  // incl. the deep retry
-    uint64_t cap64 = 8ull * (uint64_t)(deepest + 1) * (n / max_points + 1) + 64;
-    if (cap64 > (1ull << 26)) cap64 = 1ull << 26;
-    const uint32_t cap = (uint32_t)cap64;
-    nt.capacity = cap;
-    nt.prefix_lo = nullptr;
-    if ((rc = sc.get(&nt.prefix, cap)) || (rc = sc.get(&nt.lo, cap)) || (rc = sc.get(&nt.hi, cap)) ||
-        (rc = sc.get(&nt.parent, cap)) || (rc = sc.get(&nt.first_child, cap)) || (rc = sc.get(&nt.level, cap)) ||
-        (rc = sc.get(&nt.child_mask, cap)) || (rc = sc.get(&nt.open, cap)) ||
-        (rc = sc.get(&nt.counters, 64)))
-      return rc;
-    // (the sample tree of the single-chain build splits at a LOWERED threshold: twice the open nodes the capacity allows)
-    nt.max_open = (uint32_t)std::min<uint64_t>(2 * (n / max_points + 1) + 64, 1u << 22);
-    if ((rc = sc.get(&nt.bounds, std::max((size_t)cap * 9, (size_t)nt.max_open * 85)))) return rc;
-  }
+  if ((rc = alloc_node_table(sc, n, max_points, max_level, &nt))) return rc;
   uint32_t counters[64];
   bool keys32 = false;
   int attempts = 0;
@@ -1555,32 +1674,9 @@ static int build_begin_impl(pcv_ctx* ctx, const pcv_build_params* params, const 
     }
   }
 
-  if (!spec_used && n >= (1ull << 22) && full_levels > 4 && !(params->flags & PCV_BUILD_NO_SPECULATION)) {
-    const uint32_t ns = 1u << 18;
-    const uint64_t stride = n / ns;
-    uint32_t* d_max;
-    if ((rc = sc.get(&d_max, 64))) return rc;
-    PCV_HIP_CHECK(ctx, hipMemsetAsync(d_max, 0, 4, st));
-    pcv_launch_chain_keys(ctx, lv, ns, stride, d.x, d.y, d.z, keys_a, false, d.routed);
-    bool s_in_a = true;
-    // the probe only has to tell depths up to kProbeLevels apart (deeper -> no speculation): sort those digits only
-    const int kProbeLevels = 14;
-    const int probe_levels = full_levels < kProbeLevels ? full_levels : kProbeLevels;
-    if ((rc = pcv_radix_sort_u64(ctx, keys_a, keys_b, ns, 3 * (PCV_MAX_KEY_LEVELS - probe_levels), 3 * PCV_MAX_KEY_LEVELS,
-                                 nullptr, sort_scratch, &s_in_a)))
-      return rc;
-    double gapd = 0.6 * (double)max_points * (double)ns / (double)n;
-    uint32_t gap = gapd < 1.0 ? 1u : (uint32_t)gapd;
-    pcv_launch_depth_probe(ctx, s_in_a ? keys_a : keys_b, ns, gap, d_max);
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(ctx->mailbox, d_max, 4, hipMemcpyDeviceToHost, st));
-    PCV_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    const uint32_t shared = *(const uint32_t*)ctx->mailbox;
-    // a level-`shared` node is (probably) split -> nodes of level shared + 1 exist -> that many digits are needed;
-    // a prefix shared down to the last sorted level says nothing about the levels below it
-    int want = (int)shared >= probe_levels ? full_levels : (int)shared + 1;
-    if (want < 3) want = 3;
-    if (want < full_levels) spec_levels = want;
-  }
+  if (!spec_used && n >= (1ull << 22) && full_levels > 4 && !(params->flags & PCV_BUILD_NO_SPECULATION) &&
+      (rc = probe_depth(ctx, bs, max_points, full_levels, &spec_levels)))
+    return rc;
 
   for (; !spec_used;) {
     ++attempts;
@@ -1607,57 +1703,17 @@ static int build_begin_impl(pcv_ctx* ctx, const pcv_build_params* params, const 
     ctx->stage_end(PCV_STAGE_NODE_SPLIT);
     ctx->stage_begin(PCV_STAGE_TABLE);
 
-    // ---- node table to host ----
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(ctx->mailbox, nt.counters, sizeof(counters), hipMemcpyDeviceToHost, st));
-    PCV_HIP_CHECK(ctx, hipStreamSynchronize(st));
-    std::memcpy(counters, ctx->mailbox, sizeof(counters));
-    if (counters[1] & 2u) return ctx->fail(PCV_E_OOM, "node table capacity exceeded");
+    if ((rc = read_split_counters(ctx, nt, counters))) return rc;
     if (counters[1] & 1u) {
       if (spec_levels < full_levels) {  // speculation too shallow: redo at full depth
         spec_levels = full_levels;
         continue;
       }
       if (max_level > PCV_MAX_KEY_LEVELS) {
-        // ---- deep tree: a second key word for levels 22..40 (heavy duplicates in a cube with edge/resolution > 2^21).
-        // Rare path, built from existing pieces: digits as four 32-bit words, four stable LSD sorts (one per word,
-        // least significant first, the other three travel as payload planes), then the split with both words.
-        ++attempts;
+        ++attempts;  // deep tree: a second key word for levels 22..40
         const int deep_levels = max_level < PCV_MAX_LEVELS ? max_level : PCV_MAX_LEVELS;
-        bs->deep = true;
-        lv.nlevels = deep_levels;
-        uint32_t* W[4][2];
-        for (int j = 0; j < 4; ++j)
-          for (int sd = 0; sd < 2; ++sd)
-            if ((rc = sc.get(&W[j][sd], n))) return rc;
-        uint32_t* first[4] = {W[0][0], W[1][0], W[2][0], W[3][0]};
-        pcv_launch_chain_keys_deep(ctx, lv, n, d.x, d.y, d.z, d.routed, first);
-        int side = 0;
-        for (int j = 3; j >= 0; --j) {
-          PcvSortPayload pl;
-          pl.nwords = 3;
-          int w = 0;
-          for (int o = 0; o < 4; ++o) {
-            if (o == j) continue;
-            pl.in[w] = W[o][side];
-            pl.out[w] = W[o][1 - side];
-            ++w;
-          }
-          bool in_a = true;
-          if ((rc = pcv_radix_sort_u32(ctx, W[j][side], W[j][1 - side], n, 0, 32, &pl, sort_scratch, &in_a))) return rc;
-          if (!in_a) side = 1 - side;
-        }
-        const uint32_t* sorted_words[4] = {W[0][side], W[1][side], W[2][side], W[3][side]};
-        pcv_launch_combine_words(ctx, n, sorted_words, keys_a, keys_b);  // keys_a = first word, keys_b = second word
-        if ((rc = sc.get(&nt.prefix_lo, nt.capacity))) return rc;
-        bs->d_prefix_lo = nt.prefix_lo;
-        pcv_launch_node_split(ctx, nt, keys_a, false, (uint32_t)n, lv, params->resolution, max_points,
-                              (params->flags >> 8) & 0xffu, keys_b);
-        ctx->stage_end(PCV_STAGE_NODE_SPLIT);
-        ctx->stage_begin(PCV_STAGE_TABLE);
-        PCV_HIP_CHECK(ctx, hipMemcpyAsync(ctx->mailbox, nt.counters, sizeof(counters), hipMemcpyDeviceToHost, st));
-        PCV_HIP_CHECK(ctx, hipStreamSynchronize(st));
-        std::memcpy(counters, ctx->mailbox, sizeof(counters));
-        if (counters[1] & 2u) return ctx->fail(PCV_E_OOM, "node table capacity exceeded");
+        if ((rc = split_deep_tree(ctx, bs, params, max_points, deep_levels, &nt))) return rc;
+        if ((rc = read_split_counters(ctx, nt, counters))) return rc;
         if (!(counters[1] & 1u)) {
           spec_levels = deep_levels;
           break;
@@ -1675,77 +1731,9 @@ static int build_begin_impl(pcv_ctx* ctx, const pcv_build_params* params, const 
   lv.nlevels = bs->levels;  // K5/K6 index the level tables by node level; the walk stops at leaves anyway
   const uint32_t M = counters[0];
   bs->M = M;
-  // pinned staging: prefix(8) lo hi parent first_child (4 each) level mask open (1 each)
-  const size_t lo_off = (((size_t)M * (8 + 4 * 4 + 3) + 64) + 7) & ~(size_t)7;  // deep trees: second prefix word
-  const size_t host_bytes = lo_off + (bs->deep ? (size_t)M * 8 : 0);
-  bs->host_bytes = host_bytes;
-  if ((rc = ctx->pinned_reserve(host_bytes * 4 + (size_t)M * 72 + (size_t)M * 2 * sizeof(PcvNodeRec) + 1024 +
-                                (2 * (bs->n / kPcvSettleTile) + bs->n / (8 * kPcvClimbTile) + 3 * (size_t)M + 8) * sizeof(PcvSettleItem) +
-                                (size_t)M * pcv_cont_range_bytes() + (size_t)M + 64)))
-    return rc;
-  uint8_t* hp = (uint8_t*)ctx->pinned;
-  uint64_t* h_prefix = (uint64_t*)hp;
-  uint32_t* h_lo = (uint32_t*)(h_prefix + M);
-  uint32_t* h_hi = h_lo + M;
-  uint32_t* h_first = h_hi + M;
-  uint8_t* h_level = (uint8_t*)(h_first + M);
-  uint8_t* h_mask = h_level + M;
-  uint8_t* h_open = h_mask + M;
-  if (spec_used) {  // the true tree was derived on the host from the exact per-leaf counts: same layout, no download
-    std::memcpy(h_prefix, true_tree.prefix.data(), (size_t)M * 8);
-    std::memcpy(h_lo, true_tree.lo.data(), (size_t)M * 4);
-    std::memcpy(h_hi, true_tree.hi.data(), (size_t)M * 4);
-    std::memcpy(h_first, true_tree.first_child.data(), (size_t)M * 4);
-    std::memcpy(h_level, true_tree.level.data(), (size_t)M);
-    std::memcpy(h_mask, true_tree.child_mask.data(), (size_t)M);
-    std::memcpy(h_open, true_tree.open.data(), (size_t)M);
-  } else {
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(h_prefix, nt.prefix, (size_t)M * 8, hipMemcpyDeviceToHost, st));
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(h_lo, nt.lo, (size_t)M * 4, hipMemcpyDeviceToHost, st));
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(h_hi, nt.hi, (size_t)M * 4, hipMemcpyDeviceToHost, st));
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(h_first, nt.first_child, (size_t)M * 4, hipMemcpyDeviceToHost, st));
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(h_level, nt.level, (size_t)M, hipMemcpyDeviceToHost, st));
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(h_mask, nt.child_mask, (size_t)M, hipMemcpyDeviceToHost, st));
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(h_open, nt.open, (size_t)M, hipMemcpyDeviceToHost, st));
-    if (bs->deep)
-      PCV_HIP_CHECK(ctx, hipMemcpyAsync(hp + lo_off, nt.prefix_lo, (size_t)M * 8, hipMemcpyDeviceToHost, st));
-    PCV_HIP_CHECK(ctx, hipStreamSynchronize(st));
-  }
-
-  // upload area (pinned, after the download area)
-  uint8_t* up = hp + ((host_bytes + 255) & ~(size_t)255);
-  uint64_t* u_walk = (uint64_t*)up;                 // M
-  uint64_t* u_xyz_off = u_walk + M;                  // M
-  uint64_t* u_point_off = u_xyz_off + M;             // M
-  double* u_node_min = (double*)(u_point_off + M);   // 3M
-  uint32_t* u_parent = (uint32_t*)(u_node_min + 3 * (size_t)M);  // M
-  uint32_t* u_child_off = u_parent + M;              // M
-  uint32_t* u_leaf_lo = u_child_off + M;             // <= M
-  uint32_t* u_leaf_node = u_leaf_lo + M;             // <= M
-  uint8_t* u_level = (uint8_t*)(u_leaf_node + M);    // M
-  (void)u_walk; (void)u_leaf_lo; (void)u_level;
-
-  std::vector<uint64_t>& pre = bs->pre;
-  pre.assign(M, 0);
-  // bottom-up stream lengths: |pre(inner)| = sum ceil(|pre(child)| / 8)
-  for (uint32_t i = M; i-- > 0;) {
-    if (!h_open[i]) {
-      pre[i] = (uint64_t)h_hi[i] - h_lo[i];
-    } else {
-      uint64_t acc = 0;
-      uint32_t c = h_first[i];
-      for (int dgt = 0; dgt < 8; ++dgt)
-        if ((h_mask[i] >> dgt) & 1) {
-          u_child_off[c] = (uint32_t)acc;
-          u_parent[c] = i;
-          acc += ceil8(pre[c]);
-          ++c;
-        }
-      pre[i] = acc;
-    }
-  }
-  u_parent[0] = 0xffffffffu;
-  u_child_off[0] = 0;
+  if ((rc = stage_node_table(ctx, bs, nt, spec_used ? &true_tree : nullptr))) return rc;
+  bs->pre.resize(M);
+  pcv_table_stream_lengths(pcv_staged_table(ctx->pinned, M, bs->deep), bs->pre.data());
   *out = t;
   guard.t = nullptr;
   return PCV_OK;
@@ -1756,23 +1744,71 @@ extern "C" int pcv_build_top_streams(const pcv_octree* t, pcv_top_streams* out) 
   std::memset(out, 0, sizeof(*out));
   const PcvBuild* bs = t->pending;
   if (!bs) return t->nodes.empty() ? PCV_OK : t->ctx->fail(PCV_E_INVALID, "pcv_build_top_streams needs a tree between pcv_build_begin and pcv_build_finish");
-  pcv_ctx* ctx = t->ctx;
-  const uint32_t M = bs->M;
-  const uint8_t* hp = (const uint8_t*)ctx->pinned;  // the node table staged by pcv_build_begin
-  const uint32_t* h_first = (const uint32_t*)(hp + (size_t)M * 16);
-  const uint8_t* h_mask = hp + (size_t)M * 21;
-  const uint8_t* h_open = hp + (size_t)M * 22;
-  uint32_t c1 = h_first[0];
-  for (int c = 0; c < 8; ++c) {
-    if (!((h_mask[0] >> c) & 1)) continue;
-    const uint32_t i = c1++;
-    out->l1[c] = bs->pre[i];
-    if (!h_open[i]) continue;
-    out->l1_split_mask |= 1u << c;
-    uint32_t c2 = h_first[i];
-    for (int dg = 0; dg < 8; ++dg)
-      if ((h_mask[i] >> dg) & 1) out->l2[c * 8 + dg] = bs->pre[c2++];
+  pcv_table_top_streams(pcv_staged_table(t->ctx->pinned, bs->M, bs->deep), bs->pre.data(), out);  // the table staged by pcv_build_begin
+  return PCV_OK;
+}
+
+// The node-contiguous blobs K6 writes. Global-size top nodes (multi-GPU build: the first top_nodes nodes) are only partly
+// filled by this rank: the rest must read as zero.
+static int alloc_blobs(pcv_ctx* ctx, pcv_octree* t, const PcvStagedTable& tb, uint32_t top_nodes) {
+  int rc;
+  void *bx, *br, *bi = nullptr;
+  if ((rc = ctx->dev_alloc(&bx, t->xyz_bytes))) return rc;
+  t->d_xyz = (uint8_t*)bx;
+  if ((rc = ctx->dev_alloc(&br, t->rgb_bytes))) return rc;
+  t->d_rgb = (uint8_t*)br;
+  if (t->has_intensity) {
+    if ((rc = ctx->dev_alloc(&bi, t->int_bytes))) return rc;
+    t->d_int = (uint8_t*)bi;
   }
+  if (top_nodes) {
+    const uint64_t tx = top_nodes < tb.M ? tb.xyz_off[top_nodes] : t->xyz_bytes;
+    const uint64_t tp = top_nodes < tb.M ? tb.point_off[top_nodes] : t->num_points;
+    if (tx) PCV_HIP_CHECK(ctx, hipMemsetAsync(t->d_xyz, 0, tx, ctx->stream));
+    if (tp) PCV_HIP_CHECK(ctx, hipMemsetAsync(t->d_rgb, 0, tp * 3, ctx->stream));
+    if (tp && t->d_int) PCV_HIP_CHECK(ctx, hipMemsetAsync(t->d_int, 0, tp * 4, ctx->stream));
+  }
+  return PCV_OK;
+}
+
+// Where `settle` leaves the compact climber records for `climb`: in the payload buffer the sort left unused
+// (32 B x n / 8 < 16 B x n) unless that buffer is taken or too small.
+static int place_climbers(pcv_ctx* ctx, PcvBuild* bs, const pcv_octree* t, bool fuse_sort, uint64_t num_climbers, void** out) {
+  int rc;
+  const uint64_t n = bs->n;
+  void* climbers = bs->rec_in_a ? bs->pay_b : bs->pay_a;
+  if (fuse_sort) {  // that buffer is the held-back pass's SOURCE: the (16-byte) climbers go to the free half of a key buffer — with
+                    // an intensity plane that half carries the plane, and the (32-byte) climbers get a block of their own
+    const size_t half = ((size_t)n * 4 + 15) & ~(size_t)15;
+    climbers = (void*)((uint8_t*)(bs->rec_in_a ? bs->keys_b : bs->keys_a) + half);
+    const size_t need = t->has_intensity ? pcv_climber_bytes(num_climbers) : (size_t)(num_climbers + 1) * 16;
+    if (t->has_intensity || half + need > (uint64_t)n * 8) {
+      if ((rc = ctx->dev_alloc(&climbers, need))) return rc;
+      bs->sc.ptrs.push_back(climbers);
+    }
+  } else if (pcv_climber_bytes(num_climbers) > (size_t)n * (bs->spec_wide ? 8 : 16)) {
+    if ((rc = ctx->dev_alloc(&climbers, pcv_climber_bytes(num_climbers)))) return rc;
+    bs->sc.ptrs.push_back(climbers);
+  }
+  *out = climbers;
+  return PCV_OK;
+}
+
+// single-chain build: the record sort ran on the device's rank map, the node tables come from the host's resolve. Both apply
+// the same integer rules to the same counts, so a difference is a bug — reported. Call with the stream drained.
+static int check_device_resolve(pcv_ctx* ctx, const PcvBuild* bs) {
+  if (!bs->spec || !bs->resolve_on_device) return PCV_OK;
+  uint32_t dev[2];
+  std::memcpy(dev, ctx->mailbox + kMailboxResolve, sizeof(dev));
+  if (dev[0] == 0xffffffffu && dev[1] == 0xffffffffu)  // the sentinel: the resolve kernel never delivered a verdict
+    return ctx->fail(PCV_E_HIP, "single-chain build: the device's resolve kernel wrote no verdict");
+  bool same = dev[0] == bs->resolve_host_leaves && dev[1] == 0u;
+  if (same && bs->resolve_check_map && !bs->resolve_host_map.empty()) {
+    std::vector<uint32_t> dm(bs->resolve_host_map.size());
+    PCV_HIP_CHECK(ctx, hipMemcpy(dm.data(), bs->spec_map_dev, dm.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t k = 0; same && k < dm.size(); ++k) same = bs->resolve_host_inner[k] || dm[k] == bs->resolve_host_map[k];
+  }
+  if (!same) return ctx->fail(PCV_E_HIP, "single-chain build: the device's resolve of the predicted tree disagrees with the host's");
   return PCV_OK;
 }
 
@@ -1791,84 +1827,20 @@ extern "C" int pcv_build_finish(pcv_octree* t, const pcv_top_layout* top) {
       t->pending = nullptr;
     }
   } done{t};
-  PcvScratch& sc = bs->sc;
   PcvLevels& lv = bs->lv;
   const uint64_t n = bs->n;
   const uint32_t M = bs->M;
-  const size_t host_bytes = bs->host_bytes;
   ctx->stage_times = bs->stage_times;  // the flag of this build, whatever the context has begun since
 
   uint64_t* keys_a = bs->keys_a;
   uint64_t* keys_b = bs->keys_b;
   std::vector<uint64_t>& pre = bs->pre;
-  double bmin[3] = {t->bbox_min[0], t->bbox_min[1], t->bbox_min[2]};
-  uint8_t* hp = (uint8_t*)ctx->pinned;
-  uint64_t* h_prefix = (uint64_t*)hp;
-  uint32_t* h_lo = (uint32_t*)(h_prefix + M);
-  uint32_t* h_hi = h_lo + M;
-  uint32_t* h_first = h_hi + M;
-  uint8_t* h_level = (uint8_t*)(h_first + M);
-  uint8_t* h_mask = h_level + M;
-  uint8_t* h_open = h_mask + M;
-  // upload area (pinned, after the download area)
-  uint8_t* up = hp + ((host_bytes + 255) & ~(size_t)255);
-  uint64_t* u_walk = (uint64_t*)up;                 // M
-  uint64_t* u_xyz_off = u_walk + M;                  // M
-  uint64_t* u_point_off = u_xyz_off + M;             // M
-  double* u_node_min = (double*)(u_point_off + M);   // 3M
-  uint32_t* u_parent = (uint32_t*)(u_node_min + 3 * (size_t)M);  // M
-  uint32_t* u_child_off = u_parent + M;              // M
-  uint32_t* u_leaf_lo = u_child_off + M;             // <= M
-  uint32_t* u_leaf_node = u_leaf_lo + M;             // <= M
-  uint8_t* u_level = (uint8_t*)(u_leaf_node + M);    // M
-  const size_t up_bytes = (size_t)M * (8 * 3 + 24 + 4 * 4 + 1);
-  const uint64_t* h_prefix_lo = (const uint64_t*)(hp + ((((size_t)M * (8 + 4 * 4 + 3) + 64) + 7) & ~(size_t)7));  // deep only
-
-  uint32_t top_nodes = 0;  // nodes of level <= 1 hold GLOBAL streams when a layout is given (multi-GPU build)
-  if (top) {
-    pre[0] = top->root_points;
-    uint32_t c1 = h_first[0];
-    top_nodes = 1;
-    for (int c = 0; c < 8; ++c) {
-      if (!((h_mask[0] >> c) & 1)) continue;
-      const uint32_t i = c1++;
-      ++top_nodes;
-      pre[i] = top->l1_stream[c];
-      u_child_off[i] = top->l1_offset[c];
-      if (!h_open[i]) continue;
-      uint32_t c2 = h_first[i];
-      for (int dg = 0; dg < 8; ++dg)
-        if ((h_mask[i] >> dg) & 1) u_child_off[c2++] = top->l2_offset[c * 8 + dg];
-    }
-  }
-  // leaves in key order == order of their sorted ranges: depth-first, children in digit order (no sort needed)
-  std::vector<uint32_t> leaves;
-  leaves.reserve(M);
-  {
-    std::vector<uint32_t> stack;
-    stack.reserve(8 * (PCV_MAX_KEY_LEVELS + 1));
-    stack.push_back(0);
-    while (!stack.empty()) {
-      const uint32_t i = stack.back();
-      stack.pop_back();
-      if (!h_open[i]) {
-        leaves.push_back(i);
-        continue;
-      }
-      const uint32_t nchild = (uint32_t)__builtin_popcount(h_mask[i]);
-      for (uint32_t c = nchild; c-- > 0;) stack.push_back(h_first[i] + c);  // reversed: digit 0 is popped first
-    }
-  }
-  const uint32_t num_leaves = (uint32_t)leaves.size();
-  std::vector<uint32_t> rank_of(M, 0);
+  const PcvStagedTable tb = pcv_staged_table(ctx->pinned, M, bs->deep);  // the node table staged by pcv_build_begin
+  // nodes of level <= 1 hold GLOBAL streams when a layout is given (multi-GPU build)
+  const uint32_t top_nodes = top ? pcv_table_apply_top_layout(tb, *top, pre.data()) : 0u;
+  std::vector<uint32_t> rank_of(M);
   bool wide = false;
-  for (uint32_t r = 0; r < num_leaves; ++r) {
-    uint32_t i = leaves[r];
-    rank_of[i] = r;
-    u_leaf_lo[r] = h_lo[i];
-    u_leaf_node[r] = i;
-    if (lv.enc[h_level[i]] == PCV_ENC_FLOAT64) wide = true;
-  }
+  const uint32_t num_leaves = pcv_table_leaf_order(tb, lv, rank_of.data(), &wide);
   // The single-chain build queued its record sort as soon as the rank map was on the device (queue_record_sort): the
   // host work from here to K6 — node tables and their upload — hides behind the two sort passes.
   const int w_int = t->has_intensity ? 0 : -1;
@@ -1879,159 +1851,45 @@ extern "C" int pcv_build_finish(pcv_octree* t, const pcv_top_layout* top) {
     if ((rc = queue_record_sort(ctx, bs, t, nullptr, num_leaves, wide))) return rc;
   }
   t->nodes.resize(M);
-  uint64_t xyz_off = 0, point_off = 0;
-  for (uint32_t i = 0; i < M; ++i) {
-    const int level = h_level[i];
-    u_level[i] = (uint8_t)level;
-    u_walk[i] = h_open[i] ? ((uint64_t)h_first[i] | ((uint64_t)h_mask[i] << 32) | ((uint64_t)level << 48))
-                          : ((uint64_t)rank_of[i] | (1ull << 40) | ((uint64_t)level << 48));
-    // NodeId::find_bounding_cube recurrence (node.rs:157-172): parents precede children in the table
-    if (i == 0) {
-      for (int a = 0; a < 3; ++a) u_node_min[a] = bmin[a];
-    } else {
-      const uint32_t p = u_parent[i];
-      const unsigned dgt = level <= PCV_MAX_KEY_LEVELS
-                               ? (unsigned)(h_prefix[i] >> (3 * (PCV_MAX_KEY_LEVELS - level))) & 7u
-                               : (unsigned)(h_prefix_lo[i] >> (3 * (2 * PCV_MAX_KEY_LEVELS - level))) & 7u;
-      const double e = lv.edge[level];
-      u_node_min[3 * (size_t)i + 0] = u_node_min[3 * (size_t)p + 0] + (double)((dgt >> 2) & 1) * e;
-      u_node_min[3 * (size_t)i + 1] = u_node_min[3 * (size_t)p + 1] + (double)((dgt >> 1) & 1) * e;
-      u_node_min[3 * (size_t)i + 2] = u_node_min[3 * (size_t)p + 2] + (double)(dgt & 1) * e;
-    }
-    const uint64_t np = i == 0 ? pre[0] : pre[i] - ceil8(pre[i]);
-    pcv_node_info& ni = t->nodes[i];
-    // u128 NodeId = level << 120 | index (node.rs:108-111); the index is the octal path, 3 bits per level
-    unsigned __int128 index = 0;
-    if (level > PCV_MAX_KEY_LEVELS)
-      index = ((unsigned __int128)h_prefix[i] << (3 * (level - PCV_MAX_KEY_LEVELS))) |
-              (h_prefix_lo[i] >> (3 * (2 * PCV_MAX_KEY_LEVELS - level)));
-    else if (level)
-      index = h_prefix[i] >> (3 * (PCV_MAX_KEY_LEVELS - level));
-    ni.id_high = ((uint64_t)level << 56) | (uint64_t)(index >> 64);
-    ni.id_low = (uint64_t)index;
-    ni.num_points = (int64_t)np;
-    ni.level = (uint32_t)level;
-    ni.encoding = lv.enc[level];
-    for (int a = 0; a < 3; ++a) ni.cube_min[a] = u_node_min[3 * (size_t)i + a];
-    ni.cube_edge = lv.edge[level];
-    ni.xyz_offset = xyz_off;
-    ni.point_offset = point_off;
-    u_xyz_off[i] = xyz_off;
-    u_point_off[i] = point_off;
-    xyz_off += (np * 3 * (uint64_t)pcv_bytes_per_coordinate(ni.encoding) + 15) & ~15ull;
-    point_off += np;
-  }
-  t->num_points = point_off;
-  t->xyz_bytes = xyz_off;
-  t->rgb_bytes = point_off * 3;
-  t->int_bytes = t->has_intensity ? point_off * 4 : 0;
+  pcv_table_node_infos(tb, lv, t->bbox_min, pre.data(), rank_of.data(), t->nodes.data(), &t->num_points, &t->xyz_bytes);
+  t->rgb_bytes = t->num_points * 3;
+  t->int_bytes = t->has_intensity ? t->num_points * 4 : 0;
 
-  // device tables: walk records for K5, 64-byte node / leaf records for K6 (one contiguous upload)
-  uint8_t* rec_base = up + ((up_bytes + 255) & ~(size_t)255);
-  PcvNodeRec* u_node_rec = (PcvNodeRec*)rec_base;
-  PcvNodeRec* u_leaf_rec = u_node_rec + M;
-  for (uint32_t i = 0; i < M; ++i) {
-    PcvNodeRec& nr = u_node_rec[i];
-    nr.lo = h_lo[i];
-    nr.parent = u_parent[i];
-    nr.child_off = u_child_off[i];
-    nr.enc = lv.enc[u_level[i]];
-    nr.edge = lv.edge[u_level[i]];
-    // 0 = "no unchecked exact division here": also when the root cube's min is not tame (PcvLevels::fast_ok)
-    nr.inv_edge = lv.fast_ok ? lv.inv_edge[u_level[i]] : 0.0;
-    nr.inv_edge_lo = lv.fast_ok ? lv.inv_edge_lo[u_level[i]] : 0.0;
-    nr.xyz_off = u_xyz_off[i];
-    nr.point_off = u_point_off[i];
-    for (int a = 0; a < 3; ++a) nr.mn[a] = u_node_min[3 * (size_t)i + a];
-  }
-  for (uint32_t r = 0; r < num_leaves; ++r) u_leaf_rec[r] = u_node_rec[leaves[r]];
-  // climbers of K6 (every 8th point of every leaf; the root is never a leaf): dense index = climb_base[leaf] + j / 8,
-  // and the work lists of the leaf-wise settle / climb kernels (pcv_spec.h; settle_by_leaf off: the slot-wise settle
-  // kernel and the flat climb launch, experiments)
+  // device tables: walk records for K5, 64-byte node / leaf records and the work lists for K6 (pcv_tables.h). settle_by_leaf
+  // off: the slot-wise settle kernel and the flat climb launch, experiments
   const bool by_leaf = pcv_switches().settle_by_leaf;
   const bool fuse_sort = bs->spec && bs->sort_second.pending && (bs->sort_second.nbits <= 7 || !t->has_intensity) && by_leaf && !wide && bs->spec_wide;
-  std::vector<uint8_t> fused_leaf;
-  uint64_t settled_points = 0;
-  uint32_t* u_climb_base = (uint32_t*)(u_leaf_rec + num_leaves);
-  const size_t items_off = (((size_t)(M + num_leaves) * sizeof(PcvNodeRec) + (size_t)num_leaves * 4) + 15) & ~(size_t)15;
-  PcvSettleItem* u_items = (PcvSettleItem*)((uint8_t*)u_node_rec + items_off);
-  uint32_t num_items = 0, num_citems = 0;
-  uint64_t num_climbers = 0;
-  {
-    std::vector<uint32_t> cnt(num_leaves);
-    std::vector<uint8_t> climbs(num_leaves);
-    for (uint32_t r = 0; r < num_leaves; ++r) {
-      cnt[r] = h_hi[leaves[r]] - h_lo[leaves[r]];
-      climbs[r] = u_leaf_rec[r].parent != 0xffffffffu;
-    }
-    // the record sort's held-back second pass settles these leaves itself (PcvSortFuse): integer codes, not the root, no chain
-    // to continue; `settle` gets items for the others only (replayed leaves: the pass was queued unfused in front of the replay)
-    if (fuse_sort) {
-      fused_leaf.assign(num_leaves, 0);
-      std::vector<uint8_t> cont_leaf(num_leaves, 0);
-      for (uint32_t leaf : bs->cont_nodes) cont_leaf[rank_of[leaf]] = 1;
-      for (const auto& fr : bs->fix_ranges) {  // replayed leaves: their records get their codes after the sort (queue_replay)
-        uint32_t r = (uint32_t)(std::lower_bound(u_leaf_lo, u_leaf_lo + num_leaves, fr.lo) - u_leaf_lo);
-        for (; r < num_leaves && u_leaf_lo[r] == fr.lo; ++r) cont_leaf[r] = 1;  // (empty leaves share their neighbour's first slot)
-      }
-      std::vector<uint32_t> cnt_left(cnt);
-      for (uint32_t r = 0; r < num_leaves; ++r)
-        if (climbs[r] && !cont_leaf[r] && u_leaf_rec[r].enc <= PCV_ENC_UINT16) {
-          fused_leaf[r] = 1;
-          cnt_left[r] = 0;
-          settled_points += cnt[r];
-        }
-      num_items = pcv_settle_items(u_leaf_lo, cnt_left.data(), num_leaves, u_items);
-    } else if (by_leaf) {
-      num_items = pcv_settle_items(u_leaf_lo, cnt.data(), num_leaves, u_items);
-    }
-    num_climbers = pcv_climb_layout(cnt.data(), climbs.data(), num_leaves, u_climb_base, u_items + num_items, &num_citems);
-    if (!by_leaf) num_citems = 0;
-  }
-  // single-chain build: leaves below a split first candidate continue their chain from the candidate's codes
-  // (spec_continue_kernel): one range per leaf (levels + the candidate's cube min) and one item per <= 512 of its slots
-  const size_t cont_off = items_off + (size_t)(num_items + num_citems) * sizeof(PcvSettleItem);
   const uint32_t num_cont = bs->spec ? (uint32_t)bs->cont_nodes.size() : 0u;
-  uint8_t* u_cont_ranges = (uint8_t*)u_node_rec + cont_off;
-  const size_t cont_items_off = cont_off + (((size_t)num_cont * pcv_cont_range_bytes() + 15) & ~(size_t)15);
-  PcvSettleItem* u_cont_items = (PcvSettleItem*)((uint8_t*)u_node_rec + cont_items_off);
-  uint32_t num_cont_items = 0;
-  {
-    std::vector<uint32_t> cont_of_rank;
-    if (num_cont && by_leaf) cont_of_rank.assign(num_leaves, 0u);
-    for (uint32_t k = 0; k < num_cont; ++k) {
-      const uint32_t leaf = bs->cont_nodes[k], from = bs->cont_from[k];
-      pcv_fill_cont_range(u_cont_ranges + (size_t)k * pcv_cont_range_bytes(), h_level[from], h_level[leaf], u_node_min + 3 * (size_t)from);
-      if (by_leaf) cont_of_rank[rank_of[leaf]] = k + 1;
-      for (uint64_t b = h_lo[leaf]; b < h_hi[leaf]; b += kPcvSettleTile)
-        u_cont_items[num_cont_items++] = PcvSettleItem{k, (uint32_t)b, (uint32_t)std::min<uint64_t>(b + kPcvSettleTile, h_hi[leaf]), 0u};
-    }
-    if (num_cont && by_leaf)  // the leaf-wise settle kernel continues these leaves' chains itself (it ignores the mark when it
-                              // is launched without the ranges)
-      for (uint32_t j = 0; j < num_items; ++j) u_items[j].pad = cont_of_rank[u_items[j].rank];
-  }
-  const size_t walk_bytes = ((size_t)M * 8 + 255) & ~(size_t)255;
-  const size_t fused_off = cont_items_off + (size_t)num_cont_items * sizeof(PcvSettleItem);
-  if (fuse_sort) std::memcpy((uint8_t*)u_node_rec + fused_off, fused_leaf.data(), num_leaves);
-  const size_t rec_bytes = fused_off + (fuse_sort ? ((size_t)num_leaves + 15) & ~(size_t)15 : 0);
+  PcvWorkLists work;
+  pcv_table_plan_work(tb, lv, num_leaves, rank_of.data(), by_leaf, fuse_sort, bs->cont_nodes.data(), num_cont, bs->fix_ranges.data(),
+                      bs->fix_ranges.size(), &work);
+  const PcvRecordBlock rec = pcv_record_block(tb.records, work.counts);
+  // (the block cannot grow here: that would free the staged table)
+  if ((size_t)(tb.records - (uint8_t*)ctx->pinned) + rec.bytes > ctx->pinned_bytes)
+    return ctx->fail(PCV_E_OOM, "node tables: the record block of " + std::to_string(rec.bytes) + " bytes does not fit the pinned reservation");
+  pcv_table_fill_records(tb, lv, rank_of.data(), bs->cont_nodes.data(), bs->cont_from.data(), rec, &work);
+  const uint32_t num_items = work.counts.num_items, num_citems = by_leaf ? work.counts.num_citems : 0u;
+  const uint32_t num_cont_items = work.counts.num_cont_items;
+  const uint64_t num_climbers = work.num_climbers;
   // the tables live in a context-owned block; with the record sort already running they go up on the side stream (the
   // copy would otherwise queue behind the sort and sit, with its hand-over, between the sort and K6)
-  if ((rc = ctx->table_dev_reserve(walk_bytes + rec_bytes + 256))) return rc;
+  const size_t walk_bytes = pcv_table_dev_walk_bytes(M);
+  if ((rc = ctx->table_dev_reserve(walk_bytes + rec.bytes + 256))) return rc;
   uint8_t* d_up = (uint8_t*)ctx->table_dev;
+  const PcvRecordBlock d_rec = pcv_record_block(d_up + walk_bytes, work.counts);
   const bool up_side = bs->spec && bs->sort_queued;
   hipStream_t up_st = up_side ? ctx->side : st;
-  if (!bs->spec) PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_up, u_walk, (size_t)M * 8, hipMemcpyHostToDevice, up_st));  // K5 only
-  PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_up + walk_bytes, u_node_rec, rec_bytes, hipMemcpyHostToDevice, up_st));
+  if (!bs->spec) PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_up, tb.walk, (size_t)M * 8, hipMemcpyHostToDevice, up_st));  // K5 only
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_rec.node_rec, rec.node_rec, rec.bytes, hipMemcpyHostToDevice, up_st));
   if (up_side && (rc = ctx->side_end())) return ctx->fail(rc, "side stream");
   // (the side stream is in order: this join also covers the layout of the record sort's held-back pass, queued there before the
   // tables — one cross-stream wait in front of that pass instead of two, each ~10 us of idle stream)
   if (up_side) bs->sort_second.join_side = false;
-  const uint32_t* d_climb_base = (const uint32_t*)(d_up + walk_bytes + (size_t)(M + num_leaves) * sizeof(PcvNodeRec));
   wt.walk = (const uint64_t*)d_up;
   wt.num_nodes = M;
   PcvPromoteTables pt;
-  pt.node_rec = (const PcvNodeRec*)(d_up + walk_bytes);
-  pt.leaf_rec = pt.node_rec + M;
+  pt.node_rec = d_rec.node_rec;
+  pt.leaf_rec = d_rec.leaf_rec;
   ctx->stage_end(PCV_STAGE_TABLE);  // single-chain build: what is left of the table work once the sort has drained
 
   if (!bs->spec && (rc = queue_record_sort(ctx, bs, t, &wt, num_leaves, wide))) return rc;
@@ -2044,43 +1902,15 @@ extern "C" int pcv_build_finish(pcv_octree* t, const pcv_top_layout* top) {
   ctx->stage_begin(PCV_STAGE_PROMOTE_ENCODE);
 
   // ---- K6 promotion + final encode into node-contiguous blobs ----
-  void *bx, *br, *bi = nullptr;
-  if ((rc = ctx->dev_alloc(&bx, t->xyz_bytes))) return rc;
-  t->d_xyz = (uint8_t*)bx;
-  if ((rc = ctx->dev_alloc(&br, t->rgb_bytes))) return rc;
-  t->d_rgb = (uint8_t*)br;
-  if (t->has_intensity) {
-    if ((rc = ctx->dev_alloc(&bi, t->int_bytes))) return rc;
-    t->d_int = (uint8_t*)bi;
-  }
-  if (top_nodes) {  // global-size top nodes are only partly filled by this rank: the rest must read as zero
-    const uint64_t tx = top_nodes < M ? u_xyz_off[top_nodes] : t->xyz_bytes;
-    const uint64_t tp = top_nodes < M ? u_point_off[top_nodes] : t->num_points;
-    if (tx) PCV_HIP_CHECK(ctx, hipMemsetAsync(t->d_xyz, 0, tx, st));
-    if (tp) PCV_HIP_CHECK(ctx, hipMemsetAsync(t->d_rgb, 0, tp * 3, st));
-    if (tp && t->d_int) PCV_HIP_CHECK(ctx, hipMemsetAsync(t->d_int, 0, tp * 4, st));
-  }
-  // the compact climber records live in the payload buffer the sort left unused (32 B x n / 8 < 16 B x n)
-  void* climbers = rec_in_a ? (void*)pay_b : (void*)pay_a;
-  if (fuse_sort) {  // that buffer is the held-back pass's SOURCE: the (16-byte) climbers go to the free half of a key buffer — with
-                    // an intensity plane that half carries the plane, and the (32-byte) climbers get a block of their own
-    const size_t half = ((size_t)n * 4 + 15) & ~(size_t)15;
-    climbers = (void*)((uint8_t*)(rec_in_a ? keys_b : keys_a) + half);
-    const size_t need = t->has_intensity ? pcv_climber_bytes(num_climbers) : (size_t)(num_climbers + 1) * 16;
-    if (t->has_intensity || half + need > (uint64_t)n * 8) {
-      if ((rc = ctx->dev_alloc(&climbers, need))) return rc;
-      sc.ptrs.push_back(climbers);
-    }
-  } else if (pcv_climber_bytes(num_climbers) > (size_t)n * (bs->spec_wide ? 8 : 16)) {
-    if ((rc = ctx->dev_alloc(&climbers, pcv_climber_bytes(num_climbers)))) return rc;
-    sc.ptrs.push_back(climbers);
-  }
-  t->settled_in_sort = fuse_sort ? settled_points : 0;
+  if ((rc = alloc_blobs(ctx, t, tb, top_nodes))) return rc;
+  void* climbers = nullptr;
+  if ((rc = place_climbers(ctx, bs, t, fuse_sort, num_climbers, &climbers))) return rc;
+  t->settled_in_sort = work.settled_points;
   if (bs->sort_second.pending) {  // the second pass of the record sort, now that tables and blobs exist
     PcvSortFuse fz;
-    fz.leaf_rec = pt.leaf_rec;
-    fz.leaf_fused = d_up + walk_bytes + fused_off;
-    fz.climb_base = d_climb_base;
+    fz.leaf_rec = d_rec.leaf_rec;
+    fz.leaf_fused = d_rec.fused;
+    fz.climb_base = d_rec.climb_base;
     fz.climbers = climbers;
     fz.xyz_blob = t->d_xyz;
     fz.rgb_blob = t->d_rgb;
@@ -2096,40 +1926,20 @@ extern "C" int pcv_build_finish(pcv_octree* t, const pcv_top_layout* top) {
   // range); the slot-wise kernel (experiments) gets the codes rewritten by a pass of its own first
   const bool cont_in_settle = by_leaf && num_cont_items > 0;
   if (num_cont_items && !cont_in_settle)
-    pcv_launch_spec_continue(ctx, lv, d_up + walk_bytes + cont_off, (const PcvSettleItem*)(d_up + walk_bytes + cont_items_off), num_cont_items,
-                             (void*)s_pay, bs->spec_wide);
+    pcv_launch_spec_continue(ctx, lv, d_rec.cont_ranges, d_rec.cont_items, num_cont_items, (void*)s_pay, bs->spec_wide);
   pcv_launch_promote_encode(ctx, lv, pt, n, s_rank, s_pay, wide ? s_plane[w_hi] : nullptr,
                             wide ? s_plane[w_hi + 1] : nullptr, wide ? s_plane[w_hi + 2] : nullptr,
-                            w_int >= 0 ? s_plane[w_int] : nullptr, d_climb_base, (uint32_t)num_climbers, climbers, t->d_xyz,
-                            t->d_rgb, t->d_int, bs->spec_wide,
-                            by_leaf ? (const PcvSettleItem*)(d_up + walk_bytes + items_off) : nullptr, num_items,
-                            by_leaf ? (const PcvSettleItem*)(d_up + walk_bytes + items_off) + num_items : nullptr, num_citems,
-                            cont_in_settle ? (const void*)(d_up + walk_bytes + cont_off) : nullptr);
+                            w_int >= 0 ? s_plane[w_int] : nullptr, d_rec.climb_base, (uint32_t)num_climbers, climbers, t->d_xyz,
+                            t->d_rgb, t->d_int, bs->spec_wide, by_leaf ? d_rec.items : nullptr, num_items,
+                            by_leaf ? d_rec.citems : nullptr, num_citems, cont_in_settle ? d_rec.cont_ranges : nullptr);
   ctx->stage_end(PCV_STAGE_PROMOTE_ENCODE);
   PCV_HIP_CHECK(ctx, hipEventRecord(ctx->ev[8], st));
   PCV_HIP_CHECK(ctx, hipGetLastError());
   PCV_HIP_CHECK(ctx, hipStreamSynchronize(st));
-  if (bs->spec && bs->resolve_on_device) {
-    // the record sort ran on the device's rank map, the tables above come from the host's resolve: both apply the same
-    // integer rules to the same counts, so a difference is a bug — reported, never handed out as an octree
-    uint32_t dev[2];
-    std::memcpy(dev, ctx->mailbox + kMailboxResolve, sizeof(dev));
-    if (dev[0] == 0xffffffffu && dev[1] == 0xffffffffu) {  // the sentinel: the resolve kernel never delivered a verdict
-      t->nodes.clear();
-      t->num_points = 0;
-      return ctx->fail(PCV_E_HIP, "single-chain build: the device's resolve kernel wrote no verdict");
-    }
-    bool same = dev[0] == bs->resolve_host_leaves && dev[1] == 0u;
-    if (same && bs->resolve_check_map && !bs->resolve_host_map.empty()) {
-      std::vector<uint32_t> dm(bs->resolve_host_map.size());
-      PCV_HIP_CHECK(ctx, hipMemcpy(dm.data(), bs->spec_map_dev, dm.size() * 4, hipMemcpyDeviceToHost));
-      for (size_t k = 0; same && k < dm.size(); ++k) same = bs->resolve_host_inner[k] || dm[k] == bs->resolve_host_map[k];
-    }
-    if (!same) {
-      t->nodes.clear();
-      t->num_points = 0;
-      return ctx->fail(PCV_E_HIP, "single-chain build: the device's resolve of the predicted tree disagrees with the host's");
-    }
+  if ((rc = check_device_resolve(ctx, bs))) {  // never handed out as an octree
+    t->nodes.clear();
+    t->num_points = 0;
+    return rc;
   }
   ctx->prof_resolve();
   for (int sidx = 0; sidx < PCV_STAGE_TOTAL; ++sidx) {
@@ -2340,14 +2150,14 @@ extern "C" int pcv_promote_assign(const pcv_split_node* nodes, uint64_t num_node
       const uint32_t nchild = (uint32_t)__builtin_popcount(nodes[i].child_mask & 0xffu);
       for (uint32_t c = 0; c < nchild; ++c) {
         per_node[nodes[i].first_child + c].child_offset = acc;
-        acc += ceil8(per_node[nodes[i].first_child + c].stream_len);
+        acc += pcv_ceil8(per_node[nodes[i].first_child + c].stream_len);
       }
       per_node[i].stream_len = acc;
     }
   }
   per_node[0].child_offset = 0;
   for (uint32_t i = 0; i < m; ++i)
-    per_node[i].num_points = i == 0 ? per_node[0].stream_len : per_node[i].stream_len - ceil8(per_node[i].stream_len);
+    per_node[i].num_points = i == 0 ? per_node[0].stream_len : per_node[i].stream_len - pcv_ceil8(per_node[i].stream_len);
   if (!node_of_slot) return PCV_OK;
   for (uint32_t i = 0; i < m; ++i) {
     if (!nodes[i].is_leaf) continue;

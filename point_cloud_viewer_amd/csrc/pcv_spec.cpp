@@ -249,8 +249,8 @@ uint32_t pcv_settle_items(const uint32_t* lo, const uint32_t* count, uint32_t nu
   uint32_t n = 0;
   for (uint32_t r = 0; r < num_leaves; ++r) {
     const uint64_t b0 = lo[r], e = b0 + count[r];
-    for (uint64_t b = b0; b < e; b += kPcvSettleTile)
-      out[n++] = PcvSettleItem{r, (uint32_t)b, (uint32_t)std::min<uint64_t>(b + kPcvSettleTile, e), 0u};
+    for (uint64_t b = b0; b < e; b += kPcvSettleTile, ++n)
+      if (out) out[n] = PcvSettleItem{r, (uint32_t)b, (uint32_t)std::min<uint64_t>(b + kPcvSettleTile, e), 0u};
   }
   return n;
 }
@@ -260,11 +260,12 @@ uint64_t pcv_climb_layout(const uint32_t* count, const uint8_t* climbs, uint32_t
   uint64_t total = 0;
   uint32_t n = 0;
   for (uint32_t r = 0; r < num_leaves; ++r) {
-    climb_base[r] = (uint32_t)total;
+    if (climb_base) climb_base[r] = (uint32_t)total;
     if (!climbs[r]) continue;
     const uint64_t k8 = ((uint64_t)count[r] + 7) / 8;
-    for (uint64_t b = 0; b < k8; b += kPcvClimbTile)
-      out[n++] = PcvSettleItem{r, (uint32_t)(total + b), (uint32_t)(total + std::min<uint64_t>(b + kPcvClimbTile, k8)),
+    for (uint64_t b = 0; b < k8; b += kPcvClimbTile, ++n)
+      if (out)
+        out[n] = PcvSettleItem{r, (uint32_t)(total + b), (uint32_t)(total + std::min<uint64_t>(b + kPcvClimbTile, k8)),
                                (uint32_t)total /* == climb_base[r]: the leaf's first climber record */};
     total += k8;
   }
@@ -287,11 +288,12 @@ extern "C" int pcv_worklist_selftest(const uint32_t* lo, const uint32_t* count, 
 // ---- CPU self-test hook (tests/test_spec_cpu.py) --------------------------------------------------------------------
 // Runs the whole host logic on given full-depth path keys (from the oracle): strided sample -> sample tree (a plain
 // CPU restatement of what the device node split produces) -> T'' -> walk every key down T'' -> exact counts -> true tree.
-// Returns the status; the true tree comes back as (prefix, level, point count before promotion, open) per node.
-extern "C" int pcv_spec_selftest(const uint64_t* keys, uint64_t n, uint32_t stride, uint32_t cap, double delta,
-                                 double resolution, const double* edge, int nlevels, uint32_t force_mask,
-                                 uint64_t node_capacity, uint64_t* out_prefix, uint8_t* out_level, uint64_t* out_count,
-                                 uint8_t* out_open, uint64_t* out_num_nodes, uint64_t* out_stats /* [4] */) {
+// Returns the status; the true tree comes back as (prefix, level, point count before promotion, open) per node and, where
+// out_table is given, as the node table the build stages: lo, hi, first_child (u32 each) and child_mask per node.
+static int spec_selftest(const uint64_t* keys, uint64_t n, uint32_t stride, uint32_t cap, double delta, double resolution,
+                         const double* edge, int nlevels, uint32_t force_mask, uint64_t node_capacity, uint64_t* out_prefix,
+                         uint8_t* out_level, uint64_t* out_count, uint8_t* out_open, uint64_t* out_num_nodes, uint64_t* out_stats /* [4] */,
+                         uint32_t* const out_table[3], uint8_t* out_mask) {
   PcvSpecParams p;
   p.cap = cap;
   p.resolution = resolution;
@@ -434,6 +436,12 @@ extern "C" int pcv_spec_selftest(const uint64_t* keys, uint64_t n, uint32_t stri
     out_level[k] = tt.level[k];
     out_count[k] = tt.hi[k] - tt.lo[k];
     out_open[k] = tt.open[k];
+    if (out_table) {
+      out_table[0][k] = tt.lo[k];
+      out_table[1][k] = tt.hi[k];
+      out_table[2][k] = tt.first_child[k];
+      out_mask[k] = tt.child_mask[k];
+    }
   }
   // the map must send every predicted leaf's points into the true leaf that spans them
   std::vector<uint64_t> per_leaf(tt.num_leaves, 0);
@@ -451,4 +459,21 @@ extern "C" int pcv_spec_selftest(const uint64_t* keys, uint64_t n, uint32_t stri
     }
   }
   return 0;
+}
+extern "C" int pcv_spec_selftest(const uint64_t* keys, uint64_t n, uint32_t stride, uint32_t cap, double delta,
+                                 double resolution, const double* edge, int nlevels, uint32_t force_mask,
+                                 uint64_t node_capacity, uint64_t* out_prefix, uint8_t* out_level, uint64_t* out_count,
+                                 uint8_t* out_open, uint64_t* out_num_nodes, uint64_t* out_stats /* [4] */) {
+  return spec_selftest(keys, n, stride, cap, delta, resolution, edge, nlevels, force_mask, node_capacity, out_prefix, out_level,
+                       out_count, out_open, out_num_nodes, out_stats, nullptr, nullptr);
+}
+// The same with the whole node table (tests/test_tables_cpu.py feeds it to pcv_tables_selftest).
+extern "C" int pcv_spec_selftest_table(const uint64_t* keys, uint64_t n, uint32_t stride, uint32_t cap, double delta,
+                                       double resolution, const double* edge, int nlevels, uint32_t force_mask,
+                                       uint64_t node_capacity, uint64_t* out_prefix, uint8_t* out_level, uint64_t* out_count,
+                                       uint8_t* out_open, uint64_t* out_num_nodes, uint64_t* out_stats /* [4] */, uint32_t* out_lo,
+                                       uint32_t* out_hi, uint32_t* out_first_child, uint8_t* out_child_mask) {
+  uint32_t* const table[3] = {out_lo, out_hi, out_first_child};
+  return spec_selftest(keys, n, stride, cap, delta, resolution, edge, nlevels, force_mask, node_capacity, out_prefix, out_level,
+                       out_count, out_open, out_num_nodes, out_stats, table, out_child_mask);
 }
