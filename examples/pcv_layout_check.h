@@ -48,5 +48,10 @@ PCV_SA(sizeof(pcv_ooc_stats) == 120, "pcv_ooc_stats");
 PCV_SA(offsetof(pcv_ooc_stats, spill_bytes) == 32 && offsetof(pcv_ooc_stats, h2d_ms) == 56 && offsetof(pcv_ooc_stats, write_ms) == 104 &&
            offsetof(pcv_ooc_stats, split_mask) == 112 && offsetof(pcv_ooc_stats, routed) == 116,
        "pcv_ooc_stats fields");
+PCV_SA(sizeof(pcv_render_params) == 32, "pcv_render_params");
+PCV_SA(offsetof(pcv_render_params, width) == 0 && offsetof(pcv_render_params, height) == 4 && offsetof(pcv_render_params, point_size) == 8 &&
+           offsetof(pcv_render_params, gamma) == 12 && offsetof(pcv_render_params, max_nodes) == 16 &&
+           offsetof(pcv_render_params, max_workspace_bytes) == 24,
+       "pcv_render_params fields");
 
 #endif

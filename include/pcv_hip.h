@@ -845,6 +845,50 @@ int pcv_xray_lanczos_taps(uint32_t tile_size_px, uint32_t* left, uint32_t* count
  * capacity >= *needed. w or h == 0 is PCV_E_INVALID. */
 int pcv_xray_png_encode(const uint8_t* rgba, uint32_t w, uint32_t h, uint8_t* out, uint64_t capacity, uint64_t* needed);
 
+/* ---- the viewer's frame (sdl_viewer/src/lib.rs:158-209, node_drawer.rs:124-160, shaders/points.vs, points.fs) ----------
+ * V cameras over one octree in one call, rasterised on the device into RGBA8 images that stay there. OpenGL leaves sub-pixel
+ * snapping, the depth format and fused arithmetic to the driver, so the frame is a stated restatement:
+ *  - nodes: the frustum's visible list in heap pop order, cut to its first max_nodes entries (take(max_nodes_to_display),
+ *    lib.rs:180-186; 0 = all); level of detail 1, every point of a drawn node (lib.rs:194-199, node_drawer.rs:132-134);
+ *  - position (points.vs): the vertex attribute as GL delivers it (Uint8 c / 255 and Uint16 c / 65535 in f32, Float32, Float64
+ *    as f64), times edge_length plus min in f64; gl_Position = vec4(world_to_gl * dvec4) with the frustum's clip_from_query,
+ *    f64, left to right, one rounding to f32;
+ *  - a point is drawn iff 0 < w < inf and -w <= x, y, z <= w in f32; window coordinates in f32; it covers the pixels whose
+ *    centre lies in [xw - point_size / 2, xw + point_size / 2) in x and likewise in y (PROGRAM_POINT_SIZE, node_drawer.rs:139);
+ *  - DEPTH_TEST with the default GL_LESS over a black clear (node_drawer.rs:140, lib.rs:172-178): per pixel the smallest
+ *    window depth wins, equal depths go to the point drawn first (position of its node in the cut list, then index in the node);
+ *  - colour (points.vs): table[c] = round(255 * pow(c / 255, 1 / gamma)) in f32 per channel, alpha 255; background (0, 0, 0, 255). */
+#define PCV_RENDER_MAX_POINT_SIZE 64
+typedef struct pcv_render_params {
+  uint32_t width, height;        /* 1 ..= 16384 each */
+  float point_size;              /* 1 ..= PCV_RENDER_MAX_POINT_SIZE (the viewer's own floor is 1, lib.rs:152-156) */
+  float gamma;                   /* finite, > 0 */
+  uint32_t max_nodes;            /* max_nodes_to_display; 0: every visible node */
+  uint64_t max_workspace_bytes;  /* the u64 key planes of one group of views; 0: 2 GiB */
+} pcv_render_params;
+typedef struct pcv_render pcv_render;
+/* Host only, no context: PCV_E_INVALID for a width or height outside 1 ..= 16384, a point_size outside
+ * 1 ..= PCV_RENDER_MAX_POINT_SIZE (or NaN), a gamma that is not a finite number > 0. */
+int pcv_render_check_params(const pcv_render_params* params);
+/* Host only, no context: the colour table of points.vs for `gamma` (finite, > 0), computed with the host's powf. */
+int pcv_render_gamma_lut(float gamma, uint8_t lut[256]);
+/* One frame per frustum of `frusta` (a shape of another kind is PCV_E_INVALID), as the viewer's draw loop produces it
+ * (lib.rs:158-209). A frustum whose visible-node status is 1 or 2 (the reference panics there) yields a cleared image and
+ * reports that status. A view whose drawn nodes hold 2^32 - 1 points or more is PCV_E_INVALID; a single view whose key plane
+ * (8 bytes per pixel) exceeds max_workspace_bytes is PCV_E_OOM. A failed call leaves nothing allocated. The octree may be a
+ * built one or one opened from a directory; it and `frusta` may be freed after the call. */
+int pcv_render_views(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree, const pcv_render_params* params, pcv_render** out);
+/* Per view (each output nullable): the visible-node status, the length of the visible list, the nodes drawn after the cut,
+ * the points of the drawn nodes (node_drawer.rs:132-134), the points inside the clip volume, the pixels some point covers. */
+int pcv_render_info(pcv_render* r, uint32_t view, int32_t* status, uint32_t* nodes_visible, uint32_t* nodes_drawn,
+                    uint64_t* points_submitted, uint64_t* points_drawn, uint64_t* pixels_covered);
+/* Views [first, first + count) as RGBA8, height x width each, rows top to bottom (the frame a window would show,
+ * lib.rs:158-209), into memory that lives where `mem` says. A range past the end is PCV_E_INVALID and writes nothing. */
+int pcv_render_images(pcv_render* r, uint32_t first, uint32_t count, void* rgba, int mem);
+/* The same views' window depth as f32 (the depth buffer behind node_drawer.rs:140), 1.0 where no point was drawn. */
+int pcv_render_depth(pcv_render* r, uint32_t first, uint32_t count, void* zw_f32, int mem);
+void pcv_render_free(pcv_render* r);
+
 /* The `/nodes_data` reply blob of octree_web_viewer (octree_web_viewer/src/backend.rs:90-177) for a list of nodes:
  * per node min xyz (3 x f64 LE), edge (f64), num_points (u32), bytes per coordinate (u8), pad to 8, raw .xyz, pad
  * to 8, raw .rgb, pad to 8. *needed = blob size; the blob is written when out != NULL and capacity >= *needed. */

@@ -6,10 +6,11 @@ libpcv_hip.so (point_cloud_viewer_amd/csrc). Importing does not require a GPU; c
 from . import _lib
 from ._lib import (PCV_E_DEPTH, PCV_E_HIP, PCV_E_INVALID, PCV_E_IO, PCV_E_NOT_FOUND, PCV_E_OOM, PCV_OK,  # noqa: F401
                    PcvError, load_library)
-from .octree import (Aabb, Context, OctreeResult, QueryBatch, Shapes, XrayTiles, build_octree, build_octree_from_file,  # noqa: F401
+from .octree import (Aabb, Context, OctreeResult, QueryBatch, RenderedViews, Shapes, XrayTiles, build_octree, build_octree_from_file,  # noqa: F401
                      level_shortcuts, level_table, node_name, quadtree_node_id, quadtree_node_name, read_ply,
+                     render_check_params, render_gamma_lut, render_params,
                      web_mercator_rect_from_zoomed, wmr_contains, wmr_corners, wmr_from_lat_lng, wmr_math, wmr_project, wmr_to_lat_lng,
                      xray_check_params, xray_coloring, xray_finalize, xray_lanczos_taps, xray_leaf_tiles, xray_params, xray_png_encode)
 
-__all__ = ["Aabb", "Context", "OctreeResult", "QueryBatch", "XrayTiles", "build_octree", "level_table", "node_name", "PcvError",
+__all__ = ["Aabb", "Context", "OctreeResult", "QueryBatch", "RenderedViews", "XrayTiles", "build_octree", "level_table", "node_name", "PcvError",
            "load_library"]

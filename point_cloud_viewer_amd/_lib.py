@@ -74,6 +74,12 @@ class XrayColoring(C.Structure):
                 ("bin_size", C.c_double)]
 
 
+class RenderParams(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("point_size", C.c_float), ("gamma", C.c_float),
+                ("max_nodes", C.c_uint32), ("max_workspace_bytes", C.c_uint64)]
+
+
+RENDER_MAX_POINT_SIZE = 64  # PCV_RENDER_MAX_POINT_SIZE
 XRAY_XRAY, XRAY_COLORED, XRAY_HEIGHT_STDDEV, XRAY_COLORED_WITH_INTENSITY = 0, 1, 2, 3
 XRAY_JET, XRAY_PURPLISH = 0, 1
 XRAY_BG_WHITE, XRAY_BG_TRANSPARENT = 0, 1
@@ -269,6 +275,14 @@ _SIGNATURES = {
     "pcv_xray_write_dir": (C.c_int, [_vp, C.c_char_p]),
     "pcv_xray_lanczos_taps": (C.c_int, [C.c_uint32, _vp, _vp, _vp]),
     "pcv_xray_png_encode": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "pcv_render_check_params": (C.c_int, [C.POINTER(RenderParams)]),
+    "pcv_render_gamma_lut": (C.c_int, [C.c_float, _vp]),
+    "pcv_render_views": (C.c_int, [_vp, _vp, _vp, C.POINTER(RenderParams), C.POINTER(_vp)]),
+    "pcv_render_info": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "pcv_render_images": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_int]),
+    "pcv_render_depth": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_int]),
+    "pcv_render_free": (None, [_vp]),
     "pcv_octree_nodes_blob": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pcv_transform_points": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(Points), _vp, _vp, _vp]),
 }

@@ -122,6 +122,9 @@ enum PcvKernelId {
   PCV_K_XRAY_ACCUM,           // pcv_xray_run: per-pixel state in LDS, colour, background, RGBA rows
   PCV_K_XRAY_PARENT,          // pcv_xray_build_parents: one quadtree level of parents from their children (2:1 Lanczos3)
   PCV_K_XRAY_SORTED,          // pcv_xray_run_ex: colored_with_intensity / binned colored, the bucket sorted, then per pixel
+  PCV_K_RENDER_CHUNKS,        // pcv_render_views: one chunk descriptor per chunk of every (view, drawn node)
+  PCV_K_RENDER_SPLAT,         // pcv_render_views: shader decode, clip, window, atomicMin of depth | rank per covered pixel
+  PCV_K_RENDER_RESOLVE,       // pcv_render_views: key -> point -> gamma table -> RGBA8, depth plane, covered pixels
   PCV_K_COUNT
 };
 

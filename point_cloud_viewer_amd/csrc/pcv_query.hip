@@ -72,49 +72,7 @@ __device__ __forceinline__ V3d m4_transform_point(const double* m, V3d p) {
 // ---------------------------------------------------------------------------------------------
 // prepared shapes
 // ---------------------------------------------------------------------------------------------
-#define PCV_MAX_AXES 26
-struct PcvShapeDev {
-  int32_t kind;   // PCV_SHAPE_*
-  int32_t valid;  // 0: matrix not invertible (Frustum::from_matrix4 -> None)
-  int32_t naxes;  // 0 for a web-mercator rectangle: its axes live in its PcvShapeWide
-  int32_t pad;
-  double clip_from_query[16];
-  union {
-    double query_from_clip[16];
-    struct PcvShapeWide* wide;  // web-mercator rectangle (no matrices): its record beside the table
-  };
-  double iso[7];   // obb_from_query (translation xyz, quaternion ijkw) for contains()
-  double half[3];
-  double bmin[3], bmax[3];
-  double corners[24];
-  double axes[PCV_MAX_AXES * 3];
-  double amin[PCV_MAX_AXES];  // projection interval of the shape's own corners on each axis
-  double amax[PCV_MAX_AXES];
-};
-
-// A web-mercator rectangle has 12 edges and 6 face normals: up to 6 + 3 + 36 = 45 axes (sat.rs:111-143). They live beside the
-// shape table, one record per such shape, so that PcvShapeDev keeps its layout and stride for the other kinds. The flat
-// kernels' WIDE instances read them (sat_cube<true>); the instances the four older kinds run, and the wave-per-shape walks, whose
-// lanes hold at most 32 axes, are what they were: to them such a shape has no axes, and what they write for it is overwritten by
-// the WIDE instance launched behind them on the same stream.
-#define PCV_WIDE_AXES 45
-struct PcvShapeWide {
-  int32_t naxes;
-  int32_t pad;
-  double axes[PCV_WIDE_AXES * 3];
-  double amin[PCV_WIDE_AXES];
-  double amax[PCV_WIDE_AXES];
-};
-static_assert(PCV_WIDE_AXES == PCV_MAX_SHAPE_AXES, "pcv_shapes_get_ex's capacity");
-static_assert(sizeof(PcvShapeDev) == 1632 && offsetof(PcvShapeDev, iso) == 272, "the union keeps the layout of the four older kinds");
-
-struct pcv_shapes {
-  pcv_ctx* ctx;
-  uint32_t count;
-  PcvShapeDev* dev;
-  PcvShapeWide* wide = nullptr;  // one per web-mercator rectangle, in shape order
-  std::vector<int32_t> kinds;  // host copy: the point kernels are compiled per shape kind
-};
+// PcvShapeDev, PcvShapeWide and pcv_shapes: pcv_query_dev.h (the frame renderer reads the frusta's clip matrices)
 
 namespace {
 
@@ -1148,12 +1106,6 @@ __global__ __launch_bounds__(256) void transform_points_kernel(uint64_t n, const
 //   flags    keep flag per point + kept count per chunk (query_flags_kernel)
 //   scan     kept points per chunk -> u64 offsets (pcv_batch_scan)
 //   compact  the kept points of a range of chunks into the caller's buffers (query_compact_kernel)
-struct BatchNode {  // what the descriptors need of one node
-  uint64_t xyz_off, point_off;
-  double cube_min[3];
-  double cube_edge;
-  uint32_t n, enc;
-};
 struct BatchIval {  // ClosedInterval of one shape on intensity
   double lo, hi;
   uint32_t used, pad;
@@ -1683,6 +1635,8 @@ struct PcvOctreeQuery {
   std::vector<uint32_t> h_first_child;  // host copies for host-side traversals
   std::vector<uint8_t> h_child_mask;
 };
+
+const BatchNode* pcv_octree_query_nodes(const pcv_octree* t) { return t->query ? t->query->nodes : nullptr; }
 
 int pcv_octree_prepare_query(pcv_octree* t) {
   if (t->query) return PCV_OK;

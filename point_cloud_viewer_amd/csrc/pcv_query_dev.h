@@ -1,6 +1,7 @@
 // pcv_query_dev.h — what the batched point query shares with its consumers on the device (pcv_query.hip, pcv_xray.hip):
 // the f64 vector helpers, Isometry3 rotation, the per-point decode of a node's bytes, the chunk descriptor and the batch.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
@@ -73,6 +74,60 @@ __device__ __forceinline__ V3d load_point(const PointsView& v, uint64_t i) {
   return {pcv_decode_coord(v.enc, c[0], v.cube_min[0], v.cube_edge), pcv_decode_coord(v.enc, c[1], v.cube_min[1], v.cube_edge),
           pcv_decode_coord(v.enc, c[2], v.cube_min[2], v.cube_edge)};
 }
+
+// ---- prepared shapes (pcv_shapes_create, pcv_query.hip) ------------------------------------------------------------
+#define PCV_MAX_AXES 26
+struct PcvShapeDev {
+  int32_t kind;   // PCV_SHAPE_*
+  int32_t valid;  // 0: matrix not invertible (Frustum::from_matrix4 -> None)
+  int32_t naxes;  // 0 for a web-mercator rectangle: its axes live in its PcvShapeWide
+  int32_t pad;
+  double clip_from_query[16];
+  union {
+    double query_from_clip[16];
+    struct PcvShapeWide* wide;  // web-mercator rectangle (no matrices): its record beside the table
+  };
+  double iso[7];   // obb_from_query (translation xyz, quaternion ijkw) for contains()
+  double half[3];
+  double bmin[3], bmax[3];
+  double corners[24];
+  double axes[PCV_MAX_AXES * 3];
+  double amin[PCV_MAX_AXES];  // projection interval of the shape's own corners on each axis
+  double amax[PCV_MAX_AXES];
+};
+
+// A web-mercator rectangle has 12 edges and 6 face normals: up to 6 + 3 + 36 = 45 axes (sat.rs:111-143). They live beside the
+// shape table, one record per such shape, so that PcvShapeDev keeps its layout and stride for the other kinds. The flat
+// kernels' WIDE instances read them (sat_cube<true>); the instances the four older kinds run, and the wave-per-shape walks, whose
+// lanes hold at most 32 axes, are what they were: to them such a shape has no axes, and what they write for it is overwritten by
+// the WIDE instance launched behind them on the same stream.
+#define PCV_WIDE_AXES 45
+struct PcvShapeWide {
+  int32_t naxes;
+  int32_t pad;
+  double axes[PCV_WIDE_AXES * 3];
+  double amin[PCV_WIDE_AXES];
+  double amax[PCV_WIDE_AXES];
+};
+static_assert(PCV_WIDE_AXES == PCV_MAX_SHAPE_AXES, "pcv_shapes_get_ex's capacity");
+static_assert(sizeof(PcvShapeDev) == 1632 && offsetof(PcvShapeDev, iso) == 272, "the union keeps the layout of the four older kinds");
+
+struct pcv_shapes {
+  pcv_ctx* ctx;
+  uint32_t count;
+  PcvShapeDev* dev;
+  PcvShapeWide* wide = nullptr;  // one per web-mercator rectangle, in shape order
+  std::vector<int32_t> kinds;  // host copy: the point kernels are compiled per shape kind
+};
+
+struct BatchNode {  // what the descriptors need of one node
+  uint64_t xyz_off, point_off;
+  double cube_min[3];
+  double cube_edge;
+  uint32_t n, enc;
+};
+// the node table of a prepared octree on the device (pcv_octree_prepare_query), in node order
+const BatchNode* pcv_octree_query_nodes(const pcv_octree* t);
 
 // pass 0 writes one descriptor per chunk, so that pass 1 has a single scalar load between "which chunk" and the
 // staging loads

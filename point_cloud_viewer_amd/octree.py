@@ -962,6 +962,16 @@ class OctreeResult:
         xt.build_parents()
         return xt
 
+    def render(self, frusta, width, height, point_size=1.0, gamma=1.0, max_nodes=0, depth=False, max_workspace_bytes=None):
+        """The viewer's frame for every frustum of `frusta` (a Shapes of "frustum" / "frustum2" entries), rasterised on the
+        device (pcv_render_views; sdl_viewer/src/lib.rs:158-209): get_visible_nodes, its first max_nodes entries (0: all)
+        drawn as points of `point_size` pixels under a depth test, colours through `gamma`, over black. depth=True fetches
+        the window-depth planes with the call (they are kept on the device either way). Returns a RenderedViews."""
+        p = render_params(width, height, point_size, gamma, max_nodes, max_workspace_bytes)
+        h = C.c_void_p()
+        self.ctx._check(self.lib.pcv_render_views(self.ctx.handle, frusta.handle, self.handle, C.byref(p), C.byref(h)))
+        return RenderedViews(self.ctx, h, frusta.count, int(width), int(height), bool(depth))
+
     def nodes_blob(self, node_indices):
         """octree_web_viewer's /nodes_data reply body for the given nodes."""
         idx = np.ascontiguousarray(node_indices, dtype=np.uint64)
@@ -1334,6 +1344,101 @@ def xray_png_encode(rgba):
     out = np.zeros(need.value, dtype=np.uint8)
     lib.pcv_xray_png_encode(img.ctypes.data, w, h, out.ctypes.data, out.nbytes, C.byref(need))
     return out.tobytes()
+
+
+def render_params(width, height, point_size=1.0, gamma=1.0, max_nodes=0, max_workspace_bytes=None):
+    """The pcv_render_params of OctreeResult.render (same arguments)."""
+    p = L.RenderParams()
+    p.width, p.height, p.point_size, p.gamma = int(width), int(height), float(point_size), float(gamma)
+    p.max_nodes, p.max_workspace_bytes = int(max_nodes), int(max_workspace_bytes or 0)
+    return p
+
+
+def render_check_params(params):
+    """pcv_render_check_params (host only): raises PcvError for what pcv_render_views would refuse before any device work."""
+    rc = L.load_library().pcv_render_check_params(C.byref(params))
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, "pcv_render_check_params")
+
+
+def render_gamma_lut(gamma):
+    """pcv_render_gamma_lut (host only): the 256-entry colour table of the frame for `gamma`."""
+    lut = np.zeros(256, dtype=np.uint8)
+    rc = L.load_library().pcv_render_gamma_lut(float(gamma), lut.ctypes.data)
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, f"pcv_render_gamma_lut({gamma})")
+    return lut
+
+
+class RenderedViews:
+    """The result of OctreeResult.render: one RGBA8 frame and one window-depth plane per view, on the device."""
+
+    def __init__(self, ctx, handle, num_views, width, height, depth):
+        self.ctx, self.lib, self.handle = ctx, ctx.lib, handle
+        self.num_views, self.width, self.height = num_views, width, height
+        ctx._children.add(self)
+        self._depth = None
+        if depth:
+            self._depth = self.depth()
+
+    def _alive(self):
+        if not self.handle or not self.ctx.handle:
+            raise L.PcvError(L.PCV_E_INVALID, "the rendered views were freed")
+
+    def _planes(self, fn, shape_tail, dtype, first, count):
+        import torch
+        self._alive()
+        count = self.num_views - int(first) if count is None else int(count)
+        out = torch.empty((max(count, 0), self.height, self.width) + shape_tail, dtype=dtype, device=f"cuda:{self.ctx.device}")
+        self.ctx._check(fn(self.handle, int(first), count, out.data_ptr(), L.MEM_DEVICE))
+        return out
+
+    def images(self, first=0, count=None):
+        """Views [first, first + count) as a torch uint8 tensor [count, H, W, 4] on the context's device; rows top to bottom."""
+        import torch
+        return self._planes(self.lib.pcv_render_images, (4,), torch.uint8, first, count)
+
+    def depth(self, first=0, count=None):
+        """The same views' window depth as a torch float32 tensor [count, H, W] on the device; 1.0 where nothing was drawn."""
+        import torch
+        if self._depth is not None and first == 0 and count is None:
+            return self._depth
+        return self._planes(self.lib.pcv_render_depth, (), torch.float32, first, count)
+
+    def info(self, view):
+        """dict(status, nodes_visible, nodes_drawn, points_submitted, points_drawn, pixels_covered) of one view."""
+        self._alive()
+        st, nv, nd = C.c_int32(), C.c_uint32(), C.c_uint32()
+        ps, pd, pc = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self.ctx._check(self.lib.pcv_render_info(self.handle, int(view), C.byref(st), C.byref(nv), C.byref(nd), C.byref(ps),
+                                                 C.byref(pd), C.byref(pc)))
+        return dict(status=st.value, nodes_visible=nv.value, nodes_drawn=nd.value, points_submitted=ps.value,
+                    points_drawn=pd.value, pixels_covered=pc.value)
+
+    def write_png(self, directory):
+        """One view_<index>.png per view (pcv_xray_png_encode's stored-deflate PNG); returns the paths."""
+        os.makedirs(str(directory), exist_ok=True)
+        paths = []
+        for v in range(self.num_views):
+            path = os.path.join(str(directory), f"view_{v:05d}.png")
+            with open(path, "wb") as f:
+                f.write(xray_png_encode(self.images(v, 1)[0].cpu().numpy()))
+            paths.append(path)
+        return paths
+
+    def close(self):
+        if self.handle and self.ctx.handle:
+            self.lib.pcv_render_free(self.handle)
+        self.handle = None
+        self._depth = None
+
+    free = close
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class XrayTiles:

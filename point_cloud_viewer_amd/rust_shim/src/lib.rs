@@ -74,6 +74,20 @@ type pcv_ingest = c_void;
 type pcv_ooc = c_void;
 #[allow(non_camel_case_types)]
 type pcv_query_batch = c_void;
+#[allow(non_camel_case_types)]
+type pcv_render = c_void;
+
+/// include/pcv_hip.h pcv_render_params: one frame of the viewer (sdl_viewer/src/lib.rs:158-209).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct PcvRenderParams {
+    pub width: u32,
+    pub height: u32,
+    pub point_size: c_float,
+    pub gamma: c_float,
+    pub max_nodes: u32,
+    pub max_workspace_bytes: u64,
+}
 
 /// include/pcv_hip.h pcv_ooc_stats: what an out-of-core build did (points, nodes, partitions, host spill, link traffic, phase times).
 #[repr(C)]
@@ -134,6 +148,10 @@ extern "C" {
     fn pcv_query_batch_segments(b: *const pcv_query_batch, shape_first_segment: *mut u64, segment_node: *mut u32, segment_offset: *mut u64) -> c_int;
     fn pcv_query_batch_points(b: *mut pcv_query_batch, first_segment: u64, num_segments: u64, capacity: u64, mem: c_int, x: *mut c_double, y: *mut c_double, z: *mut c_double, rgb: *mut u8, intensity: *mut c_float) -> c_int;
     fn pcv_query_batch_free(b: *mut pcv_query_batch);
+    // the viewer's frame: get_visible_nodes + GL_POINTS under a depth test, rasterised on the device
+    fn pcv_render_views(ctx: *mut pcv_ctx, frusta: *const pcv_shapes, t: *mut pcv_octree, params: *const PcvRenderParams, out: *mut *mut pcv_render) -> c_int;
+    fn pcv_render_images(r: *mut pcv_render, first: u32, count: u32, rgba: *mut c_void, mem: c_int) -> c_int;
+    fn pcv_render_free(r: *mut pcv_render);
 }
 
 pub struct HipContext(*mut pcv_ctx);
@@ -685,6 +703,26 @@ impl HipOctree {
             self.ctx.check(unsafe { pcv_visible_nodes(self.ctx.0, shapes, self.tree, m as u32, &mut count, idx.as_mut_ptr(), &mut status) });
             assert!(status == 0, "Invalid projection matrix."); // octree/mod.rs:230 .expect(...)
             idx[..count as usize].iter().map(|&i| self.ids[i as usize]).collect()
+        })
+    }
+
+    /// One frame as `sdl_viewer` draws it (src/lib.rs:158-209: the visible nodes' points as GL_POINTS of `point_size`
+    /// pixels under a depth test, colours through `gamma`, over black) for the camera `world_to_gl`, rasterised on the
+    /// device: RGBA8, `height` rows of `width` pixels, top row first. Panics like the reference on a matrix that cannot
+    /// be inverted.
+    pub fn render(&self, world_to_gl: &Matrix4<f64>, width: u32, height: u32, point_size: f32, gamma: f32, max_nodes_to_display: usize) -> Vec<u8> {
+        let mut shape = PcvShape { kind: 2, reserved: 0, params: [0.0; 32] };
+        shape.params[..16].copy_from_slice(world_to_gl.as_slice()); // nalgebra storage is column-major
+        let params = PcvRenderParams { width, height, point_size, gamma, max_nodes: max_nodes_to_display.min(u32::MAX as usize) as u32, max_workspace_bytes: 0 };
+        let _g = self.lock.lock().unwrap();
+        self.with_shape(&shape, |shapes| {
+            let mut frame = std::ptr::null_mut();
+            self.ctx.check(unsafe { pcv_render_views(self.ctx.0, shapes, self.tree, &params, &mut frame) });
+            let mut rgba = vec![0u8; 4 * width as usize * height as usize];
+            let rc = unsafe { pcv_render_images(frame, 0, 1, rgba.as_mut_ptr() as *mut c_void, 0) };
+            unsafe { pcv_render_free(frame) };
+            self.ctx.check(rc);
+            rgba
         })
     }
 }
