@@ -610,8 +610,13 @@ int pcv_cull_nodes_sparse(pcv_ctx* ctx, const pcv_shapes* shapes, pcv_octree* tr
 
 /* Q3: Octree::get_visible_nodes (src/octree/mod.rs:228-283) for every frustum: node indices in the order the
  * reference's BinaryHeap pops them. counts[f] = number of visible nodes (may exceed `capacity`; only the first
- * `capacity` are written to node_indices[f * capacity ..]). status[f]: 0 ok, 1 matrix not invertible
- * (the reference panics), 2 a projected corner had w == 0 (the reference panics). */
+ * min(counts[f], capacity) entries of node_indices[f * capacity ..] are meaningful, the rest of the row is unspecified;
+ * capacity 0 writes no list, node_indices may be NULL). status[f]: 0 ok; 1 matrix not invertible (the reference panics
+ * before the traversal; counts[f] = 0); 2 the traversal pushed a node with a projected corner at w == 0 (the reference
+ * panics at that push: a node that is Out or not in the tree is never projected). With status 2 the traversal stops
+ * there: counts[f] and the list are the nodes with points popped until then, the one whose child panicked included.
+ * The reference returns nothing in either case: where status[f] != 0 the list is not a visible-node list and must not
+ * be drawn. */
 int pcv_visible_nodes(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree, uint32_t capacity, uint32_t* counts,
                       uint32_t* node_indices, int32_t* status);
 /* PointCloud::nodes_in_location (src/octree/mod.rs:309-331, src/octree/octree_iterator.rs): breadth-first, a node

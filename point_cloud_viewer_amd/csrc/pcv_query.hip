@@ -403,7 +403,10 @@ __device__ __forceinline__ double size_on_screen_by_corner(const double* __restr
     hix = fmax(hix, __shfl_xor(hix, o, 64));
     loy = fmin(loy, __shfl_xor(loy, o, 64));
     hiy = fmax(hiy, __shfl_xor(hiy, o, 64));
-    bad = bad || (__shfl_xor((int)bad, o, 64) != 0);
+    // the exchange first, on every lane: under `bad ||` a lane that is already bad would sit the shuffle out and its partner
+    // would read nothing, so a w == 0 on any corner but the first never reached the lane whose result is used
+    const int theirs = __shfl_xor((int)bad, o, 64);
+    bad = bad || theirs != 0;
   }
   if (bad) return __longlong_as_double(0x7ff8000000000000LL);
   return (hix - lox) * (hiy - loy);

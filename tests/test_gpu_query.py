@@ -185,7 +185,7 @@ def test_visible_nodes_match_reference_traversal_order(ctx, scene):
     for f, (c, _) in enumerate(fr):
         want = O.get_visible_nodes(scene["bmin"], scene["bmax"], scene["oracle"].nodes, c)
         if want is None:
-            assert status[f] != 0
+            assert status[f] == 2  # a valid matrix: the reference panics at a push, not at Frustum::from_matrix4
             continue
         assert status[f] == 0
         assert [names[i] for i in vis[f]] == want, f  # same nodes, same BinaryHeap pop order
