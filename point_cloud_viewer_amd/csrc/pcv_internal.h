@@ -539,7 +539,7 @@ void pcv_launch_promote_encode(pcv_ctx* ctx, const PcvLevels& lv, const PcvPromo
                                const void* cont_ranges = nullptr /* leaf-wise settle: items with pad != 0 continue their chain
                                                                     from range pad - 1 (pcv_fill_cont_range) */);
 
-struct PcvOctreeQuery;  // device-resident traversal tables (pcv_query.hip)
+struct PcvOctreeQuery;  // device-resident query tables (pcv_query_dev.h, pcv_cull.hip)
 
 // The finished octree (node table + node-contiguous blobs).
 struct PcvBuild;  // pcv_build.hip: state between pcv_build_begin and pcv_build_finish

@@ -1,20 +1,15 @@
-// pcv_query.hip — batched frustum / OBB / AABB transform-and-cull for gfx950.
+// pcv_query.hip — per-point culling, the point queries and the batch for gfx950.
 //
-//   K7a shape_setup      Frustum::from_matrix4 / intersector / cache_separating_axes_for_aabb
-//                        (reference src/geometry/frustum.rs:111-166, src/math/sat.rs:111-143), Obb (obb.rs:48-80)
-//   K7  cull_nodes       sat() of every (shape, node cube) pair (sat.rs:174-205) + relative_size_on_screen
-//                        (src/octree/mod.rs:119-139)
-//   K7b visible_nodes    Octree::get_visible_nodes — best-first traversal with Rust's BinaryHeap order
-//                        (octree/mod.rs:228-283,360-404), one wave per frustum
-//   K7c nodes_in_location  NodeIdsIterator BFS (src/octree/octree_iterator.rs, octree/mod.rs:309-323)
 //   K8  cull_points      FilteredIterator keep mask (src/iterator.rs:96-119; frustum.rs:120-125, obb.rs:83-90,
 //                        aabb.rs:46-48), on raw f64 positions or on a node's encoded bytes decoded on the fly
 //                        (src/read_write/codec.rs:124-139)
 //   K9  transform_points Isometry3 * Point3 (xray/src/generation.rs:493-497)
+//   N3  pcv_query_points / _node_points, N3b pcv_query_batch_*, N4 pcv_octree_nodes_blob
 //
+// The shapes come prepared from pcv_shapes.hip. Node culling is pcv_cull.hip's: the point query reaches it through
+// pcv_launch_relation_row and pcv_launch_node_lists (pcv_query_dev.h), never through a kernel.
 // Arithmetic follows the nalgebra 0.22 formulas restated in DESIGN.md ("query arithmetic"): left-to-right dot
-// products, gemv column accumulation, division by the norm, no fused multiply-add (-ffp-contract=off).
-// Bounds: K7 is f64-VALU bound (about 1 kflop per pair on 128 B of data), K8/K9 are HBM streams.
+// products, gemv column accumulation, no fused multiply-add (-ffp-contract=off). Bound: K8 / K9 are HBM streams.
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -24,770 +19,7 @@
 #include "pcv_query_dev.h"
 #include "pcv_wmr_dev.h"
 
-// ---------------------------------------------------------------------------------------------
-// device math
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ V3d v_normalize(V3d v) {
-  double n = sqrt(v_dot(v, v));
-  return {v.x / n, v.y / n, v.z / n};
-}
-#define M4(m, r, c) (m)[(c) * 4 + (r)]
-
-__device__ bool m4_try_inverse(const double* m, double* out) {
-  double inv[16];
-  inv[0] = m[5] * m[10] * m[15] - m[5] * m[11] * m[14] - m[9] * m[6] * m[15] + m[9] * m[7] * m[14] + m[13] * m[6] * m[11] - m[13] * m[7] * m[10];
-  inv[1] = -m[1] * m[10] * m[15] + m[1] * m[11] * m[14] + m[9] * m[2] * m[15] - m[9] * m[3] * m[14] - m[13] * m[2] * m[11] + m[13] * m[3] * m[10];
-  inv[2] = m[1] * m[6] * m[15] - m[1] * m[7] * m[14] - m[5] * m[2] * m[15] + m[5] * m[3] * m[14] + m[13] * m[2] * m[7] - m[13] * m[3] * m[6];
-  inv[3] = -m[1] * m[6] * m[11] + m[1] * m[7] * m[10] + m[5] * m[2] * m[11] - m[5] * m[3] * m[10] - m[9] * m[2] * m[7] + m[9] * m[3] * m[6];
-  inv[4] = -m[4] * m[10] * m[15] + m[4] * m[11] * m[14] + m[8] * m[6] * m[15] - m[8] * m[7] * m[14] - m[12] * m[6] * m[11] + m[12] * m[7] * m[10];
-  inv[5] = m[0] * m[10] * m[15] - m[0] * m[11] * m[14] - m[8] * m[2] * m[15] + m[8] * m[3] * m[14] + m[12] * m[2] * m[11] - m[12] * m[3] * m[10];
-  inv[6] = -m[0] * m[6] * m[15] + m[0] * m[7] * m[14] + m[4] * m[2] * m[15] - m[4] * m[3] * m[14] - m[12] * m[2] * m[7] + m[12] * m[3] * m[6];
-  inv[7] = m[0] * m[6] * m[11] - m[0] * m[7] * m[10] - m[4] * m[2] * m[11] + m[4] * m[3] * m[10] + m[8] * m[2] * m[7] - m[8] * m[3] * m[6];
-  inv[8] = m[4] * m[9] * m[15] - m[4] * m[11] * m[13] - m[8] * m[5] * m[15] + m[8] * m[7] * m[13] + m[12] * m[5] * m[11] - m[12] * m[7] * m[9];
-  inv[9] = -m[0] * m[9] * m[15] + m[0] * m[11] * m[13] + m[8] * m[1] * m[15] - m[8] * m[3] * m[13] - m[12] * m[1] * m[11] + m[12] * m[3] * m[9];
-  inv[10] = m[0] * m[5] * m[15] - m[0] * m[7] * m[13] - m[4] * m[1] * m[15] + m[4] * m[3] * m[13] + m[12] * m[1] * m[7] - m[12] * m[3] * m[5];
-  inv[11] = -m[0] * m[5] * m[11] + m[0] * m[7] * m[9] + m[4] * m[1] * m[11] - m[4] * m[3] * m[9] - m[8] * m[1] * m[7] + m[8] * m[3] * m[5];
-  inv[12] = -m[4] * m[9] * m[14] + m[4] * m[10] * m[13] + m[8] * m[5] * m[14] - m[8] * m[6] * m[13] - m[12] * m[5] * m[10] + m[12] * m[6] * m[9];
-  inv[13] = m[0] * m[9] * m[14] - m[0] * m[10] * m[13] - m[8] * m[1] * m[14] + m[8] * m[2] * m[13] + m[12] * m[1] * m[10] - m[12] * m[2] * m[9];
-  inv[14] = -m[0] * m[5] * m[14] + m[0] * m[6] * m[13] + m[4] * m[1] * m[14] - m[4] * m[2] * m[13] - m[12] * m[1] * m[6] + m[12] * m[2] * m[5];
-  inv[15] = m[0] * m[5] * m[10] - m[0] * m[6] * m[9] - m[4] * m[1] * m[10] + m[4] * m[2] * m[9] + m[8] * m[1] * m[6] - m[8] * m[2] * m[5];
-  double det = m[0] * inv[0] + m[1] * inv[4] + m[2] * inv[8] + m[3] * inv[12];
-  if (det == 0.0) return false;
-  double inv_det = 1.0 / det;
-  for (int i = 0; i < 16; ++i) out[i] = inv[i] * inv_det;
-  return true;
-}
-
-// nalgebra Matrix4::transform_point
-__device__ __forceinline__ V3d m4_transform_point(const double* m, V3d p) {
-  double r0 = ((M4(m, 0, 0) * p.x + M4(m, 0, 1) * p.y) + M4(m, 0, 2) * p.z) + M4(m, 0, 3);
-  double r1 = ((M4(m, 1, 0) * p.x + M4(m, 1, 1) * p.y) + M4(m, 1, 2) * p.z) + M4(m, 1, 3);
-  double r2 = ((M4(m, 2, 0) * p.x + M4(m, 2, 1) * p.y) + M4(m, 2, 2) * p.z) + M4(m, 2, 3);
-  double n = ((M4(m, 3, 0) * p.x + M4(m, 3, 1) * p.y) + M4(m, 3, 2) * p.z) + M4(m, 3, 3);
-  if (n != 0.0) return {r0 / n, r1 / n, r2 / n};
-  return {r0, r1, r2};
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// prepared shapes
-// ---------------------------------------------------------------------------------------------
-// PcvShapeDev, PcvShapeWide and pcv_shapes: pcv_query_dev.h (the frame renderer reads the frusta's clip matrices)
-
 namespace {
-
-__device__ void project8(const double* corners, V3d axis, double* mn, double* mx) {  // sat.rs:196-205
-  double lo = 1.7976931348623157e308, hi = -1.7976931348623157e308;
-  for (int i = 0; i < 8; ++i) {
-    double p = v_dot(V3d{corners[3 * i], corners[3 * i + 1], corners[3 * i + 2]}, axis);
-    lo = fmin(lo, p);
-    hi = fmax(hi, p);
-  }
-  *mn = lo;
-  *mx = hi;
-}
-
-// cache_separating_axes against the unit edges / normals of an AABB (sat.rs:111-143)
-__device__ int cache_axes_for_aabb(double* axes, int cap, const V3d* edges, int ne, const V3d* normals, int nn) {
-  const V3d unit[3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-  V3d all[6 + 3 + 36];
-  int na = 0;
-  for (int i = 0; i < nn; ++i) all[na++] = normals[i];
-  for (int i = 0; i < 3; ++i) all[na++] = unit[i];
-  for (int i = 0; i < ne; ++i)
-    for (int j = 0; j < 3; ++j) {
-      V3d c = v_normalize(v_cross(edges[i], unit[j]));
-      if (isfinite(c.x) && isfinite(c.y) && isfinite(c.z)) all[na++] = c;
-    }
-  int nd = 0;
-  for (int i = 0; i < na; ++i) {
-    bool dupe = false;
-    for (int j = 0; j < nd; ++j) {
-      V3d a2 = {axes[3 * j], axes[3 * j + 1], axes[3 * j + 2]};
-      V3d dm = v_sub(all[i], a2), dp = v_add(all[i], a2);
-      double d1 = v_dot(dm, dm), d2 = v_dot(dp, dp);
-      if (fmin(d1, d2) < 2.220446049250313e-16) {
-        dupe = true;
-        break;
-      }
-    }
-    if (!dupe && nd < cap) {
-      axes[3 * nd] = all[i].x;
-      axes[3 * nd + 1] = all[i].y;
-      axes[3 * nd + 2] = all[i].z;
-      ++nd;
-    }
-  }
-  return nd;
-}
-
-__global__ __launch_bounds__(64) void shape_setup_kernel(PcvShapeDev* shapes, uint32_t count) {
-  uint32_t f = blockIdx.x * 64 + threadIdx.x;
-  if (f >= count) return;
-  PcvShapeDev* s = shapes + f;
-  s->valid = 1;
-  if (s->kind == PCV_SHAPE_FRUSTUM || s->kind == PCV_SHAPE_FRUSTUM_WITH_INVERSE) {
-    if (s->kind == PCV_SHAPE_FRUSTUM) {
-      double inv[16];
-      if (!m4_try_inverse(s->clip_from_query, inv)) {
-        s->valid = 0;
-        s->naxes = 0;
-        return;
-      }
-      for (int i = 0; i < 16; ++i) s->query_from_clip[i] = inv[i];
-    }
-    const double sg[2] = {-1.0, 1.0};
-    V3d k[8];
-    int c = 0;
-    for (int ix = 0; ix < 2; ++ix)
-      for (int iy = 0; iy < 2; ++iy)
-        for (int iz = 0; iz < 2; ++iz) k[c++] = m4_transform_point(s->query_from_clip, V3d{sg[ix], sg[iy], sg[iz]});
-    for (int i = 0; i < 8; ++i) {
-      s->corners[3 * i] = k[i].x;
-      s->corners[3 * i + 1] = k[i].y;
-      s->corners[3 * i + 2] = k[i].z;
-    }
-    V3d e[6], n[5];
-    e[0] = v_normalize(v_sub(k[4], k[0]));
-    e[1] = v_normalize(v_sub(k[2], k[0]));
-    e[2] = v_normalize(v_sub(k[1], k[0]));
-    e[3] = v_normalize(v_sub(k[3], k[2]));
-    e[4] = v_normalize(v_sub(k[5], k[4]));
-    e[5] = v_normalize(v_sub(k[7], k[6]));
-    n[0] = v_normalize(v_cross(e[0], e[1]));
-    n[1] = v_normalize(v_cross(e[0], e[2]));
-    n[2] = v_normalize(v_cross(e[0], e[3]));
-    n[3] = v_normalize(v_cross(e[1], e[2]));
-    n[4] = v_normalize(v_cross(e[1], e[4]));
-    s->naxes = cache_axes_for_aabb(s->axes, PCV_MAX_AXES, e, 6, n, 5);
-  } else if (s->kind == PCV_SHAPE_OBB) {
-    // s->iso holds query_from_obb on entry; corners/edges use it, contains() needs the inverse (obb.rs:35-41)
-    const double* q = s->iso + 3;
-    V3d t = {s->iso[0], s->iso[1], s->iso[2]};
-    const double sx[8] = {-1, 1, -1, 1, -1, 1, -1, 1}, sy[8] = {-1, -1, 1, 1, -1, -1, 1, 1}, sz[8] = {-1, -1, -1, -1, 1, 1, 1, 1};
-    for (int c = 0; c < 8; ++c) {
-      V3d p = v_add(quat_rotate(q, V3d{sx[c] * s->half[0], sy[c] * s->half[1], sz[c] * s->half[2]}), t);
-      s->corners[3 * c] = p.x;
-      s->corners[3 * c + 1] = p.y;
-      s->corners[3 * c + 2] = p.z;
-    }
-    V3d e[3];
-    e[0] = v_normalize(quat_rotate(q, V3d{1, 0, 0}));
-    e[1] = v_normalize(quat_rotate(q, V3d{0, 1, 0}));
-    e[2] = v_normalize(quat_rotate(q, V3d{0, 0, 1}));
-    s->naxes = cache_axes_for_aabb(s->axes, PCV_MAX_AXES, e, 3, e, 3);
-    double qi[4] = {-q[0], -q[1], -q[2], q[3]};  // Isometry3::inverse
-    V3d ti = quat_rotate(qi, V3d{-t.x, -t.y, -t.z});
-    s->iso[0] = ti.x;
-    s->iso[1] = ti.y;
-    s->iso[2] = ti.z;
-    s->iso[3] = qi[0];
-    s->iso[4] = qi[1];
-    s->iso[5] = qi[2];
-    s->iso[6] = qi[3];
-  } else if (s->kind == PCV_SHAPE_AABB) {  // aabb.rs:98-125
-    const double* mn = s->bmin;
-    const double* mx = s->bmax;
-    const double cs[24] = {mn[0], mn[1], mn[2], mx[0], mn[1], mn[2], mn[0], mx[1], mn[2], mx[0], mx[1], mn[2],
-                           mn[0], mn[1], mx[2], mx[0], mn[1], mx[2], mn[0], mx[1], mx[2], mx[0], mx[1], mx[2]};
-    for (int i = 0; i < 24; ++i) s->corners[i] = cs[i];
-    const double ax[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    for (int i = 0; i < 9; ++i) s->axes[i] = ax[i];
-    s->naxes = 3;
-  } else if (s->kind == PCV_SHAPE_WEB_MERCATOR_RECT) {
-    // s->corners came up from the host (pcv_wmr_corners); edges and face normals in intersector()'s order
-    // (web_mercator_rect.rs:85-116)
-    V3d k[8];
-    for (int i = 0; i < 8; ++i) k[i] = V3d{s->corners[3 * i], s->corners[3 * i + 1], s->corners[3 * i + 2]};
-    V3d e[12], n[6];
-    for (int i = 0; i < 4; ++i) {
-      e[i] = v_normalize(v_sub(k[(i + 1) & 3], k[i]));              // N E S W edge, down
-      e[4 + i] = v_normalize(v_sub(k[4 + ((i + 1) & 3)], k[4 + i]));  // N E S W edge, up
-      e[8 + i] = v_normalize(v_sub(k[4 + i], k[i]));                // NW NE SE SW edge
-    }
-    for (int i = 0; i < 4; ++i) n[i] = v_normalize(v_cross(e[i], e[8 + i]));  // N E S W face
-    n[4] = v_normalize(v_cross(e[1], e[0]));                                  // down face
-    n[5] = v_normalize(v_cross(e[5], e[4]));                                  // up face
-    PcvShapeWide* w = s->wide;
-    w->naxes = cache_axes_for_aabb(w->axes, PCV_WIDE_AXES, e, 12, n, 6);
-    for (int a = 0; a < w->naxes; ++a)
-      project8(s->corners, V3d{w->axes[3 * a], w->axes[3 * a + 1], w->axes[3 * a + 2]}, &w->amin[a], &w->amax[a]);
-    s->naxes = 0;
-  } else {
-    s->naxes = 0;  // AllPoints
-  }
-  for (int a = 0; a < s->naxes; ++a)
-    project8(s->corners, V3d{s->axes[3 * a], s->axes[3 * a + 1], s->axes[3 * a + 2]}, &s->amin[a], &s->amax[a]);
-}
-
-// sat() of one cube against one prepared shape: Out if any axis separates, else Cross if B sticks out on any axis,
-// else In (sat.rs:174-194) — so the walk over the axes stops at the first separating one, like the reference's early
-// return, and the Relation does not depend on where it stops.
-// The interval of the cube's 8 corners on an axis: each corner is fl(fl(x a_x + y a_y) + z a_z) with x, y, z the low or
-// high bound; rounding is monotone, so the least (greatest) corner is the one built from the three least (greatest)
-// products — 6 min/max + 4 adds instead of 16 adds + 16 min/max. Only when a bound comes out non-finite (inf / NaN
-// inputs) are the 8 corners folded literally, in aabb.rs:114-125 order, so that f64::min / max skip NaNs as they do
-// in the reference.
-// the interval of the cube [l, h]^3 on one axis (see sat_cube): its three least / greatest products, or — non-finite bounds — its
-// eight corners folded literally
-__device__ __forceinline__ void sat_axis_interval(double lx, double hx, double ly, double hy, double lz, double hz, double ax, double ay,
-                                                  double az, double& bmin, double& bmax, double& magnitude) {
-  const double plx = lx * ax, phx = hx * ax, ply = ly * ay, phy = hy * ay, plz = lz * az, phz = hz * az;
-  bmin = (fmin(plx, phx) + fmin(ply, phy)) + fmin(plz, phz);
-  bmax = (fmax(plx, phx) + fmax(ply, phy)) + fmax(plz, phz);
-  magnitude = ((fabs(plx) + fabs(phx)) + (fabs(ply) + fabs(phy))) + (fabs(plz) + fabs(phz));
-  if (!(fabs(bmin) <= 1.7976931348623157e308 && fabs(bmax) <= 1.7976931348623157e308)) {
-    // corners in aabb.rs:114-125 order: (l,l,l) (h,l,l) (l,h,l) (h,h,l) (l,l,h) (h,l,h) (l,h,h) (h,h,h)
-    double c0 = (plx + ply) + plz, c1 = (phx + ply) + plz, c2 = (plx + phy) + plz, c3 = (phx + phy) + plz;
-    double c4 = (plx + ply) + phz, c5 = (phx + ply) + phz, c6 = (plx + phy) + phz, c7 = (phx + phy) + phz;
-    bmin = fmin(fmin(fmin(fmin(fmin(fmin(fmin(fmin(1.7976931348623157e308, c0), c1), c2), c3), c4), c5), c6), c7);
-    bmax = fmax(fmax(fmax(fmax(fmax(fmax(fmax(fmax(-1.7976931348623157e308, c0), c1), c2), c3), c4), c5), c6), c7);
-  }
-}
-template <bool WIDE = false>
-__device__ __forceinline__ int sat_cube(const PcvShapeDev* __restrict__ s, double mnx, double mny, double mnz, double edge) {
-  if (s->kind == PCV_SHAPE_ALL) return 1;  // AllPoints intersects everything (math/mod.rs:139-160) -> "not Out"
-  // Cube::to_aabb: Aabb::new(min, min + edge) (inf / sup)
-  const double ax_ = mnx + edge, ay_ = mny + edge, az_ = mnz + edge;
-  const double lx = fmin(mnx, ax_), hx = fmax(mnx, ax_);
-  const double ly = fmin(mny, ay_), hy = fmax(mny, ay_);
-  const double lz = fmin(mnz, az_), hz = fmax(mnz, az_);
-  bool cross = false;
-  const int na = WIDE ? s->wide->naxes : s->naxes;
-  const double* axes = WIDE ? s->wide->axes : s->axes;
-  const double* amins = WIDE ? s->wide->amin : s->amin;
-  const double* amaxs = WIDE ? s->wide->amax : s->amax;
-  for (int a = 0; a < na; ++a) {
-    double bmin, bmax, mag;
-    sat_axis_interval(lx, hx, ly, hy, lz, hz, axes[3 * a], axes[3 * a + 1], axes[3 * a + 2], bmin, bmax, mag);
-    const double amin = amins[a], amax = amaxs[a];
-    if (bmin > amax || bmax < amin) return 2;
-    cross = cross || (amin > bmin || bmax > amax);
-  }
-  return cross ? 1 : 0;
-}
-
-__device__ __forceinline__ double clamp_num(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// octree/mod.rs:103-139. NaN marks the cases where the reference panics (w == 0).
-__device__ double size_on_screen(const double* __restrict__ m, double mnx, double mny, double mnz, double edge) {
-  const double mxx = mnx + edge, mxy = mny + edge, mxz = mnz + edge;
-  const double px[8] = {mnx, mxx, mxx, mnx, mxx, mnx, mxx, mnx};
-  const double py[8] = {mny, mxy, mny, mxy, mxy, mny, mny, mxy};
-  const double pz[8] = {mnz, mxz, mnz, mnz, mnz, mxz, mxz, mxz};
-  double lox = 0, hix = 0, loy = 0, hiy = 0;
-  bool bad = false;
-  for (int i = 0; i < 8; ++i) {
-    double v[4];
-    for (int r = 0; r < 4; ++r) v[r] = ((M4(m, r, 0) * px[i] + M4(m, r, 1) * py[i]) + M4(m, r, 2) * pz[i]) + M4(m, r, 3) * 1.0;
-    if (v[3] == 0.0) bad = true;
-    const double cx = clamp_num(v[0] / v[3], -1., 1.), cy = clamp_num(v[1] / v[3], -1., 1.);
-    if (i == 0) {
-      lox = hix = cx;
-      loy = hiy = cy;
-    } else {
-      lox = fmin(lox, cx);
-      hix = fmax(hix, cx);
-      loy = fmin(loy, cy);
-      hiy = fmax(hiy, cy);
-    }
-  }
-  if (bad) return __longlong_as_double(0x7ff8000000000000LL);
-  return (hix - lox) * (hiy - loy);
-}
-
-// K7: grid.y = shape, grid.x covers the nodes. WIDE: the web-mercator rectangles only, with their own axes.
-template <bool WIDE = false>
-__global__ __launch_bounds__(256) void cull_nodes_kernel(const PcvShapeDev* __restrict__ shapes, uint32_t m,
-                                                          const double* __restrict__ cubes /* m x 4 */,
-                                                          uint8_t* __restrict__ relation, double* __restrict__ sizes) {
-  const PcvShapeDev* s = shapes + blockIdx.y;
-  if (WIDE && s->kind != PCV_SHAPE_WEB_MERCATOR_RECT) return;
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= m) return;
-  const double4 c = *reinterpret_cast<const double4*>(cubes + 4 * (uint64_t)i);
-  const uint64_t o = (uint64_t)blockIdx.y * m + i;
-  relation[o] = s->valid ? (uint8_t)sat_cube<WIDE>(s, c.x, c.y, c.z, c.w) : (uint8_t)2;
-  if (sizes) sizes[o] = size_on_screen(s->clip_from_query, c.x, c.y, c.z, c.w);
-}
-
-// K7s (round 5): the same relations as a LIST per shape. 99.8 % of the (frustum, node) pairs of BASELINE config 4 are Out; the
-// dense matrix spends most of its time on the size on screen of pairs nobody looks at (two IEEE divisions per corner) and
-// its 546 MB on the way to the host. One workgroup per shape walks the node table in tiles of 256 and appends the nodes
-// that are not Out IN NODE ORDER: {node index, relation, relative_size_on_screen} — the size is computed for those only,
-// which is exactly where the reference computes it (octree/mod.rs:261-272: a node is projected when it is pushed).
-template <bool WIDE = false>  // WIDE: every web-mercator rectangle (no `redo`), with its own axes
-__global__ __launch_bounds__(256) void cull_nodes_sparse_kernel(const PcvShapeDev* __restrict__ shapes, uint32_t m,
-                                                                 const double* __restrict__ cubes /* m x 4 */, uint32_t capacity,
-                                                                 uint32_t* __restrict__ counts, uint32_t* __restrict__ out_node,
-                                                                 uint8_t* __restrict__ out_rel, double* __restrict__ out_size,
-                                                                 const uint32_t* __restrict__ redo /* set: only the flagged shapes */) {
-  __shared__ uint32_t wave_tot[4];
-  if (!WIDE && redo && !redo[blockIdx.x]) return;  // (uniform) the tree walk finished this shape
-  const PcvShapeDev* s = shapes + blockIdx.x;
-  if (WIDE && s->kind != PCV_SHAPE_WEB_MERCATOR_RECT) return;
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint64_t row = (uint64_t)blockIdx.x * capacity;
-  uint32_t base = 0;  // entries of this shape so far (uniform)
-  const bool valid = s->valid != 0;
-  for (uint32_t t0 = 0; t0 < m; t0 += 256) {
-    const uint32_t i = t0 + threadIdx.x;
-    double4 c = make_double4(0, 0, 0, 0);
-    int rel = 2;
-    if (i < m && valid) {
-      c = *reinterpret_cast<const double4*>(cubes + 4 * (uint64_t)i);
-      rel = sat_cube<WIDE>(s, c.x, c.y, c.z, c.w);
-    }
-    const bool keep = rel != 2;
-    const uint64_t b = __ballot(keep);
-    if (lane == 0) wave_tot[wave] = (uint32_t)__popcll(b);
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < 4; ++w) {
-      const uint32_t v = wave_tot[w];
-      before += w < wave ? v : 0u;
-      total += v;
-    }
-    if (keep) {
-      const uint32_t pos = base + before + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-      if (pos < capacity) {
-        out_node[row + pos] = i;
-        out_rel[row + pos] = (uint8_t)rel;
-        if (out_size) out_size[row + pos] = size_on_screen(s->clip_from_query, c.x, c.y, c.z, c.w);
-      }
-    }
-    base += total;
-    __syncthreads();  // wave_tot is rewritten by the next tile
-  }
-  if (threadIdx.x == 0) counts[blockIdx.x] = base;
-}
-
-// K7t (round 6): the same lists, descending the tree like the reference's own traversals do (octree_iterator.rs:30-43,
-// octree/mod.rs:261-272: children are only tested under a parent that is not Out). 99.76 % of the pairs of BASELINE config 4 are
-// Out and nearly all of them sit under an Out ancestor. One WAVE per shape walks the tree breadth first — node order is
-// (level, index), so the breadth-first order of the kept nodes IS the list's order.
-//   * The wave's lanes are the shape's AXES, not the children: lane l holds axis l mod 32 of the shape (<= 26) in registers for
-//     the whole walk, lanes 0-31 test one child of the popped node, lanes 32-63 the next, and three ballots give both Relations
-//     (Out if any axis separates, else Cross if the cube sticks out on any axis, else In: sat.rs:174-194 does not depend on the
-//     order of the axes). A first form with one child per lane and the loop over the axes inside ran 286-370 us for the 10 000
-//     frusta: every round paid all 26 axes for a handful of busy lanes; the flat kernel needed 431.
-//   * The queue (LDS) holds the kept INNER nodes only (87 % of a tree's nodes are leaves: listed, never expanded), each with its
-//     cube, first child and child mask, so a popped node costs no dependent global load: its children's cubes are the recurrence
-//     step NodeId::find_bounding_cube takes (node.rs:160-170: edge /= 2; min += bit * edge) — how the table's own cubes were
-//     made (tests/test_gpu_query.py checks it on the node table) — and the children's own masks are requested (lanes 0-7) before
-//     the tests and used after them.
-//   * relative_size_on_screen of a popped node's kept children: eight lanes per child, one corner each (size_on_screen_by_corner).
-// A subtree is skipped only under a node that is Out BY A MARGIN: some axis separates it by more than 1e-9 of the magnitudes
-// involved — ~10^6 times the rounding error of any cube inside this one (a descendant's bounds lie within a few ulps of its
-// ancestor's: min += bit * edge only adds, max = min + edge) — so every descendant is Out for the flat evaluation too. A shape
-// that meets an Out node without that margin (a face within an ulp of a cube face, non-finite bounds), whose frontier outgrows
-// the queue, or that is AllPoints, is flagged and redone by the flat kernel (cull_nodes_sparse_kernel with `redo`): the lists
-// are the flat kernel's in every case.
-__device__ __forceinline__ double size_on_screen_by_corner(const double* __restrict__ m, double mnx, double mny, double mnz, double edge,
-                                                           uint32_t corner) {
-  // lanes 8 g .. 8 g + 7 take the eight corners of cube g (size_on_screen's order), each its own projection and its two divisions;
-  // the corners' clamped x / y are folded with min / max across the eight lanes (a min / max over a set: the order of the fold only
-  // decides the sign of a zero)
-  const double px = ((0x56u >> corner) & 1u) ? mnx + edge : mnx, py = ((0x9au >> corner) & 1u) ? mny + edge : mny,
-               pz = ((0xe2u >> corner) & 1u) ? mnz + edge : mnz;
-  double v[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) v[r] = ((M4(m, r, 0) * px + M4(m, r, 1) * py) + M4(m, r, 2) * pz) + M4(m, r, 3) * 1.0;
-  bool bad = v[3] == 0.0;
-  double lox = clamp_num(v[0] / v[3], -1., 1.), loy = clamp_num(v[1] / v[3], -1., 1.);
-  double hix = lox, hiy = loy;
-#pragma unroll
-  for (int o = 1; o < 8; o <<= 1) {
-    lox = fmin(lox, __shfl_xor(lox, o, 64));
-    hix = fmax(hix, __shfl_xor(hix, o, 64));
-    loy = fmin(loy, __shfl_xor(loy, o, 64));
-    hiy = fmax(hiy, __shfl_xor(hiy, o, 64));
-    // the exchange first, on every lane: under `bad ||` a lane that is already bad would sit the shuffle out and its partner
-    // would read nothing, so a w == 0 on any corner but the first never reached the lane whose result is used
-    const int theirs = __shfl_xor((int)bad, o, 64);
-    bad = bad || theirs != 0;
-  }
-  if (bad) return __longlong_as_double(0x7ff8000000000000LL);
-  return (hix - lox) * (hiy - loy);
-}
-struct CullEntry {
-  double mnx, mny, mnz, edge;
-  uint32_t first_child, mask;
-};
-constexpr uint32_t kCullQueue = 128;  // kept inner nodes waiting for their children to be tested, per wave (5 KiB: LDS does not bound the occupancy)
-// this lane's axis against the cube (mn, mn + edge): does it separate (Out), does the cube stick out (Cross), does it separate by
-// the margin
-struct AxisTest {
-  bool sep, cross, robust;
-};
-__device__ __forceinline__ AxisTest cull_axis_test(bool on, double ax, double ay, double az, double amin, double amax, double mnx,
-                                                   double mny, double mnz, double edge) {
-  const double ax_ = mnx + edge, ay_ = mny + edge, az_ = mnz + edge;  // Cube::to_aabb, as sat_cube
-  const double lx = fmin(mnx, ax_), hx = fmax(mnx, ax_), ly = fmin(mny, ay_), hy = fmax(mny, ay_), lz = fmin(mnz, az_), hz = fmax(mnz, az_);
-  double bmin, bmax, mag;
-  sat_axis_interval(lx, hx, ly, hy, lz, hz, ax, ay, az, bmin, bmax, mag);
-  AxisTest t;
-  t.sep = on && (bmin > amax || bmax < amin);
-  t.cross = on && (amin > bmin || bmax > amax);
-  const double scale = mag + (fabs(amin) + fabs(amax));
-  t.robust = on && fmax(bmin - amax, amin - bmax) > 1e-9 * scale && scale <= 1.7976931348623157e308;  // (NaN / inf anywhere: no)
-  return t;
-}
-// HIER: the walk IS the answer — PointCloud::nodes_in_location (octree/mod.rs:309-323, NodeIdsIterator: a node's children are
-// visited iff the node is not Out): every Out node prunes its subtree, margin or not; node indices only.
-template <bool SIZES, bool HIER = false>
-__global__ __launch_bounds__(256) void cull_nodes_tree_kernel(const PcvShapeDev* __restrict__ shapes, uint32_t nshapes, uint32_t m,
-                                                               const double* __restrict__ cubes /* m x 4, find_bounding_cube */,
-                                                               const uint32_t* __restrict__ first_child, const uint8_t* __restrict__ child_mask,
-                                                               uint32_t capacity, uint32_t* __restrict__ counts, uint32_t* __restrict__ out_node,
-                                                               uint8_t* __restrict__ out_rel, double* __restrict__ out_size,
-                                                               uint32_t* __restrict__ redo,
-                                                               const uint64_t* __restrict__ rows /* set: shape f's list at rows[f] .. rows[f + 1] */) {
-  __shared__ CullEntry queue[4][kCullQueue];
-  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-  const uint32_t f = blockIdx.x * 4 + wave;
-  if (f >= nshapes) return;  // wave-uniform
-  const PcvShapeDev* s = shapes + f;
-  const uint64_t row = rows ? rows[f] : (uint64_t)f * capacity;
-  if (rows) capacity = (uint32_t)(rows[f + 1] - rows[f]);
-  CullEntry* q = queue[wave];
-  uint32_t head = 0, tail = 0;  // queue of kept inner nodes
-  uint32_t nout = 0;            // listed nodes
-  const int na = s->naxes;
-  bool again = s->kind == PCV_SHAPE_ALL;  // (every node: the flat kernel lists them as fast)
-  // this lane's axis, for the whole walk
-  const uint32_t axis = lane & 31u;
-  const bool on = (int)axis < na;
-  double ax = 0, ay = 0, az = 0, amin = 0, amax = 0;
-  if (on) {
-    ax = s->axes[3 * axis], ay = s->axes[3 * axis + 1], az = s->axes[3 * axis + 2];
-    amin = s->amin[axis], amax = s->amax[axis];
-  }
-  if (s->valid && !again) {
-    {  // the root (both halves of the wave test it: the lower one's ballot bits are read)
-      const double4 c = *reinterpret_cast<const double4*>(cubes);
-      const AxisTest t = cull_axis_test(on, ax, ay, az, amin, amax, c.x, c.y, c.z, c.w);
-      const uint32_t sep = (uint32_t)__ballot(t.sep), cross = (uint32_t)__ballot(t.cross), rob = (uint32_t)__ballot(t.robust);
-      if (sep == 0u) {
-        const uint32_t cm = child_mask[0];
-        if (lane == 0) {
-          if (capacity) {  // (entries past `capacity` are dropped, the count is not: capacity 0 only counts)
-            out_node[row] = 0;
-            if (!HIER) out_rel[row] = (uint8_t)(cross ? 1 : 0);
-            if (SIZES) out_size[row] = size_on_screen(s->clip_from_query, c.x, c.y, c.z, c.w);
-          }
-          q[0] = CullEntry{c.x, c.y, c.z, c.w, first_child[0], cm};
-        }
-        nout = 1;
-        tail = cm ? 1u : 0u;
-      } else {
-        again = !HIER && rob == 0u;
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    while (head < tail && !again) {
-      const CullEntry e = q[head & (kCullQueue - 1u)];  // (one address: a broadcast)
-      const uint32_t pmask = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.mask);
-      const uint32_t pfirst = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.first_child);
-      // the children's own masks / first children: requested now (lanes 0-7), used after the tests
-      uint32_t cm = 0, cf = 0;
-      const uint32_t mychild = pfirst + (uint32_t)__popc(pmask & ((1u << (lane & 7u)) - 1u));
-      if (lane < 8u && ((pmask >> lane) & 1u)) {
-        cm = child_mask[mychild];
-        cf = first_child[mychild];
-      }
-      const double half = e.edge / 2.0;  // node.rs:160-170
-      uint32_t kept_mask = 0, cross_mask = 0;  // per digit (wave-uniform)
-      for (uint32_t rest = pmask; rest != 0u && !again;) {
-        const uint32_t d0 = (uint32_t)__builtin_ctz(rest);
-        rest &= rest - 1u;
-        const uint32_t d1 = rest ? (uint32_t)__builtin_ctz(rest) : 8u;
-        rest &= rest - 1u;  // (0 & anything stays 0)
-        const uint32_t digit = lane < 32u ? d0 : d1;
-        const bool lane_on = on && digit < 8u;
-        const double cx = e.mnx + ((digit & 4u) ? half : 0.0), cy = e.mny + ((digit & 2u) ? half : 0.0), cz = e.mnz + ((digit & 1u) ? half : 0.0);
-        const AxisTest t = cull_axis_test(lane_on, ax, ay, az, amin, amax, cx, cy, cz, half);
-        const uint64_t sep = __ballot(t.sep), cross = __ballot(t.cross), rob = __ballot(t.robust);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const uint32_t d = h ? d1 : d0;
-          if (d >= 8u) continue;
-          const uint32_t sp = (uint32_t)(sep >> (32 * h)), cr = (uint32_t)(cross >> (32 * h)), rb = (uint32_t)(rob >> (32 * h));
-          if (sp == 0u) {
-            kept_mask |= 1u << d;
-            if (cr) cross_mask |= 1u << d;
-          } else if (!HIER && rb == 0u) {
-            again = true;  // Out without the margin: its subtree cannot be skipped
-          }
-        }
-      }
-      const uint32_t kept = (uint32_t)__popc(kept_mask);
-      if (again) break;
-      const bool mine = lane < 8u && ((kept_mask >> lane) & 1u);
-      const uint32_t k = (uint32_t)__popc(kept_mask & ((1u << (lane & 7u)) - 1u));
-      if (mine && nout + k < capacity) {  // (entries past `capacity` are dropped, the count is not)
-        out_node[row + nout + k] = mychild;
-        if (!HIER) out_rel[row + nout + k] = (uint8_t)((cross_mask >> lane) & 1u);
-      }
-      if (SIZES && kept && nout < capacity) {  // lanes 8 g .. 8 g + 7: the eight corners of the g-th kept child
-        const uint32_t g = lane >> 3;
-        uint32_t mk = kept_mask;
-        for (uint32_t i = 0; i < g && mk; ++i) mk &= mk - 1u;  // drop the g lowest set bits
-        const uint32_t d = mk ? (uint32_t)__builtin_ctz(mk) : (uint32_t)__builtin_ctz(kept_mask);  // (idle groups redo the first: no divergence)
-        const double cx = e.mnx + ((d & 4u) ? half : 0.0), cy = e.mny + ((d & 2u) ? half : 0.0), cz = e.mnz + ((d & 1u) ? half : 0.0);
-        const double sz = size_on_screen_by_corner(s->clip_from_query, cx, cy, cz, half, lane & 7u);
-        if (g < kept && nout + g < capacity && (lane & 7u) == 0u) out_size[row + nout + g] = sz;
-      }
-      const bool inner = mine && cm != 0u;
-      const uint32_t inner_mask = (uint32_t)__ballot(inner);
-      const uint32_t pushed = (uint32_t)__popc(inner_mask);
-      if (tail + pushed - (head + 1u) > kCullQueue) {  // a frontier wider than the queue: the flat kernel
-        again = true;
-        break;
-      }
-      if (inner) {
-        const double cx = e.mnx + ((lane & 4u) ? half : 0.0), cy = e.mny + ((lane & 2u) ? half : 0.0), cz = e.mnz + ((lane & 1u) ? half : 0.0);
-        q[(tail + (uint32_t)__popc(inner_mask & ((1u << lane) - 1u))) & (kCullQueue - 1u)] = CullEntry{cx, cy, cz, half, cf, cm};
-      }
-      nout += kept;
-      tail += pushed;
-      head += 1u;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-  }
-  if (lane == 0) {
-    counts[f] = nout;
-    redo[f] = again ? 1u : 0u;
-  }
-}
-
-struct QTree {
-  uint32_t m;
-  const double* cubes;         // get_child-style cubes (min xyz, edge), node order = (level, index)
-  const uint32_t* first_child;
-  const uint8_t* child_mask;
-  const uint8_t* empty;        // num_points == 0
-};
-
-// K7b: one wave per frustum. Lanes 0..7 run the SAT + size_on_screen of the popped node's children side by side;
-// lane 0 owns the BinaryHeap (std's pop / push sift order restated, so the pop order is the reference's). The first
-// kHeapLds heap slots live in LDS, anything deeper in the frustum's global scratch (m entries).
-// Round 6: an entry carries what popping it needs — the node's first child, its child mask, whether it holds points — fetched
-// when the node was PUSHED (beside the SAT / size arithmetic of its siblings), so a pop is followed by ONE global load (the node's
-// cube; its children's cubes are Node::get_child steps from it, node.rs:190-211) instead of two dependent rounds of them.
-struct HeapEntry {
-  double size;
-  uint32_t node;
-  uint32_t first_child;
-  uint32_t bits;  // child mask in bits 0..7, bit 8: Relation::Cross (else In), bit 9: the node holds no points
-  uint32_t pad;
-};
-constexpr uint32_t kHeapLds = 256;  // 24 B entries: 4 waves x 6 KiB per workgroup
-struct WaveHeap {
-  HeapEntry* lds;
-  HeapEntry* glb;  // indexed by heap slot too (its first kHeapLds slots stay unused)
-  __device__ __forceinline__ HeapEntry get(uint32_t i) const { return i < kHeapLds ? lds[i] : glb[i]; }
-  __device__ __forceinline__ void set(uint32_t i, const HeapEntry& e) const {
-    if (i < kHeapLds) lds[i] = e;
-    else glb[i] = e;
-  }
-};
-__device__ __forceinline__ void heap_sift_up(const WaveHeap& d, uint32_t start, uint32_t pos) {
-  HeapEntry elt = d.get(pos);
-  while (pos > start) {
-    uint32_t parent = (pos - 1) / 2;
-    HeapEntry pe = d.get(parent);
-    if (elt.size <= pe.size) break;
-    d.set(pos, pe);
-    pos = parent;
-  }
-  d.set(pos, elt);
-}
-// BinaryHeap::pop: swap the last element in, sift_down_to_bottom, sift_up
-__device__ __forceinline__ HeapEntry heap_pop(const WaveHeap& d, uint32_t& len) {
-  HeapEntry item = d.get(len - 1);
-  --len;
-  if (len > 0) {
-    HeapEntry top = d.get(0);
-    d.set(0, item);
-    item = top;
-    const uint32_t end = len;
-    uint32_t pos = 0, child = 1;
-    HeapEntry elt = d.get(0);
-    while (child + 1 < end) {
-      HeapEntry l = d.get(child), r = d.get(child + 1);
-      const bool right = l.size <= r.size;
-      child += right ? 1u : 0u;
-      d.set(pos, right ? r : l);
-      pos = child;
-      child = 2 * pos + 1;
-    }
-    if (child == end - 1) {
-      d.set(pos, d.get(child));
-      pos = child;
-    }
-    d.set(pos, elt);
-    heap_sift_up(d, 0, pos);
-  }
-  return item;
-}
-__global__ __launch_bounds__(256) void visible_nodes_kernel(const PcvShapeDev* __restrict__ shapes, uint32_t first_shape,
-                                                             uint32_t nshapes, QTree t, HeapEntry* __restrict__ heaps,
-                                                             uint32_t capacity, uint32_t* __restrict__ counts,
-                                                             uint32_t* __restrict__ out, int32_t* __restrict__ status) {
-  __shared__ HeapEntry lds_heap[4][kHeapLds];
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const uint32_t li = blockIdx.x * 4 + wave;
-  if (li >= nshapes) return;  // wave-uniform
-  const uint32_t f = first_shape + li;
-  const PcvShapeDev* s = shapes + f;
-  const WaveHeap d{lds_heap[wave], heaps + (uint64_t)li * t.m};
-  uint32_t* o = out + (uint64_t)f * capacity;
-  uint32_t len = 0, nout = 0;  // lane 0's
-  int32_t st = 0;
-  // this lane's axis of the shape, for the whole traversal (lanes 0-31 and 32-63 hold the same axes)
-  const bool on = (int)(lane & 31u) < s->naxes;
-  double ax = 0, ay = 0, az = 0, amin = 0, amax = 0;
-  if (on) {
-    ax = s->axes[3 * (lane & 31u)], ay = s->axes[3 * (lane & 31u) + 1], az = s->axes[3 * (lane & 31u) + 2];
-    amin = s->amin[lane & 31u], amax = s->amax[lane & 31u];
-  }
-  if (!s->valid) {  // .expect("Invalid projection matrix.")
-    if (lane == 0) {
-      counts[f] = 0;
-      status[f] = 1;
-    }
-    return;
-  }
-  if (t.m > 0 && lane == 0) {  // maybe_push_node(root, Cross)
-    double sz = size_on_screen(s->clip_from_query, t.cubes[0], t.cubes[1], t.cubes[2], t.cubes[3]);
-    if (sz != sz) st = 2;
-    d.set(0, HeapEntry{sz, 0u, t.first_child[0], (uint32_t)t.child_mask[0] | 0x100u | (t.empty[0] ? 0x200u : 0u), 0u});
-    len = 1;
-  }
-  const bool all_points = s->kind == PCV_SHAPE_ALL;
-  for (;;) {
-    if (!__shfl((int)(len > 0 && st == 0), 0)) break;
-    uint32_t node = 0, first = 0, bits = 0;
-    if (lane == 0) {
-      const HeapEntry item = heap_pop(d, len);
-      node = item.node;
-      first = item.first_child;
-      bits = item.bits;
-    }
-    node = (uint32_t)__builtin_amdgcn_readfirstlane((int)node);  // (lane 0 is the first active lane)
-    first = (uint32_t)__builtin_amdgcn_readfirstlane((int)first);
-    bits = (uint32_t)__builtin_amdgcn_readfirstlane((int)bits);
-    const uint32_t mask = bits & 0xffu;
-    const bool cross_parent = (bits & 0x100u) != 0u;
-    // the popped node's cube (one address for the wave) — the only load a pop waits for
-    const double4 pc = *reinterpret_cast<const double4*>(t.cubes + 4 * (uint64_t)node);
-    // what the children's own entries will need, requested now (lanes 0-7), used when they are pushed
-    const uint32_t c = first + (uint32_t)__popc(mask & ((1u << (lane & 7)) - 1u));
-    uint32_t cbits = 0, cfirst = 0;
-    if (lane < 8 && ((mask >> lane) & 1u)) {
-      cbits = (uint32_t)t.child_mask[c] | (t.empty[c] ? 0x200u : 0u);
-      cfirst = t.first_child[c];
-    }
-    const double half = pc.w / 2.;  // Node::get_child (node.rs:190-211): min += half only where the bit is set
-    // maybe_push_node on the children that exist: the wave's lanes are the shape's AXES — lanes 0-31 test one child, lanes 32-63
-    // the next, two ballots give both Relations — and a kept child's size on screen is computed by eight lanes, one corner each
-    // (one lane per child with the 26 axes and the 8 corners in loops left 56 lanes idle for ~3 000 instructions per pop)
-    uint32_t kept_mask = mask, cross_mask = 0;  // children of an In node are In without a test (octree/mod.rs:261-272)
-    if (cross_parent && all_points) {
-      cross_mask = mask;  // sat_cube: AllPoints is "not Out" of everything, reported as Cross
-    } else if (cross_parent) {
-      kept_mask = 0;
-      for (uint32_t rest = mask; rest != 0u;) {
-        const uint32_t d0 = (uint32_t)__builtin_ctz(rest);
-        rest &= rest - 1u;
-        const uint32_t d1 = rest ? (uint32_t)__builtin_ctz(rest) : 8u;
-        rest &= rest - 1u;
-        const uint32_t digit = lane < 32u ? d0 : d1;
-        const double cx = (digit & 4u) ? pc.x + half : pc.x, cy = (digit & 2u) ? pc.y + half : pc.y, cz = (digit & 1u) ? pc.z + half : pc.z;
-        const AxisTest at = cull_axis_test(on && digit < 8u, ax, ay, az, amin, amax, cx, cy, cz, half);
-        const uint64_t sep = __ballot(at.sep), cross = __ballot(at.cross);
-        if ((uint32_t)sep == 0u) {
-          kept_mask |= 1u << d0;
-          if ((uint32_t)cross) cross_mask |= 1u << d0;
-        }
-        if (d1 < 8u && (uint32_t)(sep >> 32) == 0u) {
-          kept_mask |= 1u << d1;
-          if ((uint32_t)(cross >> 32)) cross_mask |= 1u << d1;
-        }
-      }
-    }
-    double sz = 0.0;  // lane 8 g: the size of the g-th kept child
-    if (kept_mask) {
-      const uint32_t g = lane >> 3;
-      uint32_t mk = kept_mask;
-      for (uint32_t i = 0; i < g && mk; ++i) mk &= mk - 1u;
-      const uint32_t dg = (uint32_t)(mk ? __builtin_ctz(mk) : __builtin_ctz(kept_mask));  // (idle groups redo the first: no divergence)
-      const double cx = (dg & 4u) ? pc.x + half : pc.x, cy = (dg & 2u) ? pc.y + half : pc.y, cz = (dg & 1u) ? pc.z + half : pc.z;
-      sz = size_on_screen_by_corner(s->clip_from_query, cx, cy, cz, half, lane & 7u);
-    }
-    uint32_t g = 0;
-    for (int ci = 0; ci < 8; ++ci) {  // pushes in child order, like the reference's loop
-      if (!((kept_mask >> ci) & 1u)) continue;  // (wave-uniform)
-      const double z = __shfl(sz, (int)(8u * g));
-      const uint32_t cc = (uint32_t)__shfl((int)c, ci), cf = (uint32_t)__shfl((int)cfirst, ci), cb = (uint32_t)__shfl((int)cbits, ci);
-      ++g;
-      if (lane == 0) {
-        if (z != z) st = 2;
-        d.set(len, HeapEntry{z, cc, cf, cb | (((cross_mask >> ci) & 1u) << 8), 0u});
-        heap_sift_up(d, 0, len);
-        ++len;
-      }
-    }
-    if (lane == 0 && !(bits & 0x200u)) {
-      if (nout < capacity) o[nout] = node;
-      ++nout;
-    }
-  }
-  if (lane == 0) {
-    counts[f] = nout;
-    status[f] = st;
-  }
-}
-
-// K7c: BFS of NodeIdsIterator; queue in global scratch. WIDE: every web-mercator rectangle (no `redo`), with its own axes.
-template <bool WIDE = false>
-__global__ __launch_bounds__(64) void nodes_in_location_kernel(const PcvShapeDev* __restrict__ shapes, uint32_t first_shape,
-                                                                uint32_t nshapes, QTree t, const double* __restrict__ fb_cubes,
-                                                                uint32_t* __restrict__ queues, uint32_t capacity,
-                                                                uint32_t* __restrict__ counts, uint32_t* __restrict__ out,
-                                                                const uint32_t* __restrict__ redo /* set: only the flagged shapes */,
-                                                                const uint64_t* __restrict__ rows /* set: shape f's list at rows[f] .. rows[f + 1] */) {
-  const uint32_t li = blockIdx.x * 64 + threadIdx.x;
-  if (li >= nshapes) return;
-  const uint32_t f = first_shape + li;
-  if (!WIDE && redo && !redo[f]) return;  // the wave-per-shape walk finished this one
-  const PcvShapeDev* s = shapes + f;
-  if (WIDE && s->kind != PCV_SHAPE_WEB_MERCATOR_RECT) return;
-  uint32_t* q = queues + (uint64_t)li * t.m;
-  uint32_t* o = out + (rows ? rows[f] : (uint64_t)f * capacity);
-  if (rows) capacity = (uint32_t)(rows[f + 1] - rows[f]);
-  uint32_t head = 0, tail = 0, nout = 0;
-  if (t.m > 0 && s->valid) q[tail++] = 0;
-  while (head < tail) {
-    const uint32_t cur = q[head++];
-    const double* cb = fb_cubes + 4 * (uint64_t)cur;  // NodeMeta::bounding_cube = find_bounding_cube (octree/mod.rs:205)
-    if (sat_cube<WIDE>(s, cb[0], cb[1], cb[2], cb[3]) == 2) continue;
-    const uint32_t mask = t.child_mask[cur];
-    uint32_t cidx = t.first_child[cur];
-    for (uint32_t ci = 0; ci < 8; ++ci)
-      if ((mask >> ci) & 1u) q[tail++] = cidx++;
-    if (nout < capacity) o[nout] = cur;
-    ++nout;
-  }
-  counts[f] = nout;
-}
-
 
 // What contains() needs of a shape, fetched once per wave (wave-uniform: it lives in scalar registers) instead of
 // once per point: the clip matrix (frustum), mins / maxs (AABB) or isometry + half extents (OBB). The point kernels
@@ -1380,55 +612,52 @@ inline uint32_t stride_grid(uint64_t n, uint32_t per_block) {
   return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + per_block - 1) / per_block, 1u << 16));
 }
 
-// what the descriptors need of one node of the table
-inline BatchNode batch_node(const pcv_node_info& nd) {
-  BatchNode o;
-  o.xyz_off = nd.xyz_offset;
-  o.point_off = nd.point_offset;
-  for (int a = 0; a < 3; ++a) o.cube_min[a] = nd.cube_min[a];
-  o.cube_edge = nd.cube_edge;
-  o.n = (uint32_t)std::max<int64_t>(nd.num_points, 0);
-  o.enc = nd.encoding;
-  return o;
-}
-
-// keep flags of `nchunks` chunks, their kept counts in chunk_counts: persistent, as many workgroups as are resident at once.
-// kind < 0: the chunks' own shapes and kinds; otherwise one location (shape 0 of every descriptor) of that kind
-int launch_query_flags(pcv_ctx* ctx, int32_t kind, const PcvShapeDev* shapes, const BatchIval* ivals, const ChunkDesc* desc,
-                       uint32_t nchunks, const pcv_octree* tree, uint8_t* keep, uint32_t* chunk_counts) {
+// keep flags of `nchunks` chunks, their kept counts in chunk_counts, by `kernel` (an instance of query_flags_kernel, or
+// query_flags_wmr_kernel): persistent, as many workgroups as are resident at once
+int launch_flags(pcv_ctx* ctx, decltype(&query_flags_wmr_kernel) kernel, const PcvShapeDev* shapes, const BatchIval* ivals,
+                 const ChunkDesc* desc, uint32_t nchunks, const pcv_octree* tree, uint8_t* keep, uint32_t* chunk_counts) {
   int cus = 0, per_cu = 0;
   PCV_HIP_CHECK(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-#define PCV_CALL(K) PCV_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, query_flags_kernel<K>, 256, 0))
-  if (kind < 0) {
-    PCV_CALL(-1);
-  } else {
-    PCV_DISPATCH_KIND(kind, PCV_CALL)
-  }
-#undef PCV_CALL
+  PCV_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0));
   const uint32_t nb = (uint32_t)std::min<uint64_t>((nchunks + 3ull) / 4, (uint64_t)std::max(cus, 1) * (uint64_t)std::max(per_cu, 1));
-#define PCV_CALL(K)                                                                                                               \
-  hipLaunchKernelGGL(query_flags_kernel<K>, dim3(nb), dim3(256), 0, ctx->stream, shapes, ivals, desc, nchunks, tree->d_xyz, \
-                     (const float*)tree->d_int, keep, chunk_counts)
-  if (kind < 0) {
-    PCV_CALL(-1);
-  } else {
-    PCV_DISPATCH_KIND(kind, PCV_CALL)
-  }
-#undef PCV_CALL
+  hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, ctx->stream, shapes, ivals, desc, nchunks, tree->d_xyz, (const float*)tree->d_int, keep,
+                     chunk_counts);
   PCV_HIP_CHECK(ctx, hipGetLastError());
   return PCV_OK;
 }
+// kind < 0: the chunks' own shapes and kinds; otherwise one location (shape 0 of every descriptor) of that kind
+int launch_query_flags(pcv_ctx* ctx, int32_t kind, const PcvShapeDev* shapes, const BatchIval* ivals, const ChunkDesc* desc,
+                       uint32_t nchunks, const pcv_octree* tree, uint8_t* keep, uint32_t* chunk_counts) {
+  auto kernel = query_flags_kernel<-1>;
+#define PCV_CALL(K) kernel = query_flags_kernel<K>
+  if (kind >= 0) {
+    PCV_DISPATCH_KIND(kind, PCV_CALL)
+  }
+#undef PCV_CALL
+  return launch_flags(ctx, kernel, shapes, ivals, desc, nchunks, tree, keep, chunk_counts);
+}
 
-// the web-mercator chunks of a mixed batch, after launch_query_flags(kind < 0) on the same stream
-int launch_query_flags_wmr(pcv_ctx* ctx, const PcvShapeDev* shapes, const BatchIval* ivals, const ChunkDesc* desc, uint32_t nchunks,
-                           const pcv_octree* tree, uint8_t* keep, uint32_t* chunk_counts) {
-  int cus = 0, per_cu = 0;
-  PCV_HIP_CHECK(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-  PCV_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, query_flags_wmr_kernel, 256, 0));
-  const uint32_t nb = (uint32_t)std::min<uint64_t>((nchunks + 3ull) / 4, (uint64_t)std::max(cus, 1) * (uint64_t)std::max(per_cu, 1));
-  hipLaunchKernelGGL(query_flags_wmr_kernel, dim3(nb), dim3(256), 0, ctx->stream, shapes, ivals, desc, nchunks, tree->d_xyz,
-                     (const float*)tree->d_int, keep, chunk_counts);
-  PCV_HIP_CHECK(ctx, hipGetLastError());
+// The planes of a set of points, in host or device memory: x / y / z and, where set, rgb (3 bytes per point) and intensity.
+struct PointPlanes {
+  double *x = nullptr, *y = nullptr, *z = nullptr;
+  uint8_t* rgb = nullptr;
+  float* intensity = nullptr;
+};
+// device scratch for the planes `like` has
+int planes_alloc(PcvScratch& sc, uint64_t n, const PointPlanes& like, PointPlanes* d) {
+  int rc;
+  if ((rc = sc.get(&d->x, n)) || (rc = sc.get(&d->y, n)) || (rc = sc.get(&d->z, n))) return rc;
+  if (like.rgb && (rc = sc.get(&d->rgb, 3 * n))) return rc;
+  if (like.intensity && (rc = sc.get(&d->intensity, n))) return rc;
+  return PCV_OK;
+}
+// the planes `dst` has, from `src`, on ctx->stream
+int planes_copy(pcv_ctx* ctx, const PointPlanes& dst, const PointPlanes& src, uint64_t n, hipMemcpyKind kind) {
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(dst.x, src.x, 8 * n, kind, ctx->stream));
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(dst.y, src.y, 8 * n, kind, ctx->stream));
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(dst.z, src.z, 8 * n, kind, ctx->stream));
+  if (dst.rgb) PCV_HIP_CHECK(ctx, hipMemcpyAsync(dst.rgb, src.rgb, 3 * n, kind, ctx->stream));
+  if (dst.intensity) PCV_HIP_CHECK(ctx, hipMemcpyAsync(dst.intensity, src.intensity, 4 * n, kind, ctx->stream));
   return PCV_OK;
 }
 
@@ -1437,29 +666,18 @@ int launch_query_flags_wmr(pcv_ctx* ctx, const PcvShapeDev* shapes, const BatchI
 int compact_chunks(pcv_ctx* ctx, int label, const pcv_octree* tree, const ChunkDesc* desc, const uint8_t* keep, const uint64_t* chunk_off,
                    uint64_t c0, uint64_t c1, uint64_t base, uint64_t np, int mem, double* x, double* y, double* z, uint8_t* rgb,
                    float* intensity) {
-  const bool want_int = intensity != nullptr && tree->has_intensity;
   PcvScratch sc(ctx);
   int rc;
-  double *dx = x, *dy = y, *dz = z;
-  uint8_t* drgb = rgb;
-  float* dint = intensity;
-  if (mem == PCV_MEM_HOST) {
-    if ((rc = sc.get(&dx, np)) || (rc = sc.get(&dy, np)) || (rc = sc.get(&dz, np)) || (rc = sc.get(&drgb, 3 * np))) return rc;
-    if (want_int && (rc = sc.get(&dint, np))) return rc;
-  }
+  const PointPlanes out{x, y, z, rgb, tree->has_intensity ? intensity : nullptr};
+  PointPlanes d = out;
+  if (mem == PCV_MEM_HOST && (rc = planes_alloc(sc, np, out, &d))) return rc;
   {
     PcvProf prof(ctx, label);
     hipLaunchKernelGGL(query_compact_kernel, dim3(stride_grid(c1 - c0, 4)), dim3(256), 0, ctx->stream, desc, c0, c1, tree->d_xyz,
-                       tree->d_rgb, (const float*)tree->d_int, keep, chunk_off, base, np, dx, dy, dz, drgb, want_int ? dint : nullptr);
+                       tree->d_rgb, (const float*)tree->d_int, keep, chunk_off, base, np, d.x, d.y, d.z, d.rgb, d.intensity);
   }
   PCV_HIP_CHECK(ctx, hipGetLastError());
-  if (mem == PCV_MEM_HOST) {
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(x, dx, 8 * np, hipMemcpyDeviceToHost, ctx->stream));
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(y, dy, 8 * np, hipMemcpyDeviceToHost, ctx->stream));
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(z, dz, 8 * np, hipMemcpyDeviceToHost, ctx->stream));
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(rgb, drgb, 3 * np, hipMemcpyDeviceToHost, ctx->stream));
-    if (want_int) PCV_HIP_CHECK(ctx, hipMemcpyAsync(intensity, dint, 4 * np, hipMemcpyDeviceToHost, ctx->stream));
-  }
+  if (mem == PCV_MEM_HOST && (rc = planes_copy(ctx, out, d, np, hipMemcpyDeviceToHost))) return rc;
   PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return PCV_OK;
 }
@@ -1487,407 +705,6 @@ int pcv_batch_scan(pcv_ctx* ctx, PcvScratch& sc, const uint32_t* in, uint64_t n,
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-extern "C" int pcv_shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t count, pcv_shapes** out) {
-  if (!ctx) return PCV_E_INVALID;
-  if (!out || (count && !shapes)) return ctx->fail(PCV_E_INVALID, "null argument");
-  *out = nullptr;
-  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  std::vector<PcvShapeDev> h(count);
-  std::vector<uint32_t> wide_of;  // the shapes with a PcvShapeWide
-  for (uint32_t i = 0; i < count; ++i) {
-    const pcv_shape& s = shapes[i];
-    PcvShapeDev& d = h[i];
-    std::memset(&d, 0, sizeof(d));
-    d.kind = s.kind;
-    switch (s.kind) {
-      case PCV_SHAPE_ALL: break;
-      case PCV_SHAPE_AABB:
-        for (int a = 0; a < 3; ++a) {  // Aabb::new: inf / sup of the two corners (aabb.rs:21-26)
-          d.bmin[a] = std::fmin(s.params[a], s.params[3 + a]);
-          d.bmax[a] = std::fmax(s.params[a], s.params[3 + a]);
-        }
-        break;
-      case PCV_SHAPE_FRUSTUM:
-        for (int a = 0; a < 16; ++a) d.clip_from_query[a] = s.params[a];
-        break;
-      case PCV_SHAPE_FRUSTUM_WITH_INVERSE:
-        for (int a = 0; a < 16; ++a) {
-          d.clip_from_query[a] = s.params[a];
-          d.query_from_clip[a] = s.params[16 + a];
-        }
-        break;
-      case PCV_SHAPE_OBB:
-        for (int a = 0; a < 7; ++a) d.iso[a] = s.params[a];
-        for (int a = 0; a < 3; ++a) d.half[a] = s.params[7 + a];
-        break;
-      case PCV_SHAPE_WEB_MERCATOR_RECT:  // the corners on the host (libm), everything after them on the device
-        d.bmin[0] = s.params[0];
-        d.bmin[1] = s.params[1];
-        d.bmax[0] = s.params[2];
-        d.bmax[1] = s.params[3];
-        if (pcv_wmr_corners(s.params, d.corners) != PCV_OK) return ctx->fail(PCV_E_INVALID, "web-mercator rectangle: corners");
-        wide_of.push_back(i);
-        break;
-      default: return ctx->fail(PCV_E_INVALID, "unknown shape kind");
-    }
-  }
-  pcv_shapes* r = new pcv_shapes();
-  r->ctx = ctx;
-  r->count = count;
-  r->dev = nullptr;
-  r->kinds.resize(count);
-  for (uint32_t i = 0; i < count; ++i) r->kinds[i] = shapes[i].kind;
-  void* p = nullptr;
-  int rc = ctx->dev_alloc(&p, sizeof(PcvShapeDev) * (count ? count : 1));
-  if (rc) {
-    delete r;
-    return rc;
-  }
-  r->dev = (PcvShapeDev*)p;
-  if (!wide_of.empty()) {
-    if ((rc = ctx->dev_alloc(&p, sizeof(PcvShapeWide) * wide_of.size()))) {
-      ctx->dev_free(r->dev);
-      delete r;
-      return rc;
-    }
-    r->wide = (PcvShapeWide*)p;
-    for (size_t w = 0; w < wide_of.size(); ++w) {
-      h[wide_of[w]].wide = r->wide + w;
-    }
-  }
-  if (count) {
-    hipError_t e = hipMemcpyAsync(r->dev, h.data(), sizeof(PcvShapeDev) * count, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(shape_setup_kernel, dim3((count + 63) / 64), dim3(64), 0, ctx->stream, r->dev, count);
-      e = hipStreamSynchronize(ctx->stream);  // `h` must outlive the copy
-    }
-    if (e != hipSuccess) {
-      if (r->wide) ctx->dev_free(r->wide);
-      ctx->dev_free(r->dev);
-      delete r;
-      return ctx->fail(PCV_E_HIP, hipGetErrorString(e));
-    }
-  }
-  *out = r;
-  return PCV_OK;
-}
-
-extern "C" void pcv_shapes_free(pcv_shapes* s) {
-  if (!s) return;
-  if (s->wide) s->ctx->dev_free(s->wide);
-  s->ctx->dev_free(s->dev);
-  delete s;
-}
-
-extern "C" uint32_t pcv_shapes_count(const pcv_shapes* s) { return s ? s->count : 0; }
-
-extern "C" int pcv_shapes_get(pcv_shapes* s, uint32_t i, double corners[24], double axes[78], uint32_t* num_axes,
-                              int* valid) {
-  if (!s || i >= s->count) return PCV_E_INVALID;
-  if (s->kinds[i] != PCV_SHAPE_WEB_MERCATOR_RECT) {  // (all 78 doubles, as ever)
-    pcv_ctx* ctx = s->ctx;
-    PcvShapeDev h;
-    PCV_HIP_CHECK(ctx, hipMemcpy(&h, s->dev + i, sizeof(h), hipMemcpyDeviceToHost));
-    if (corners) std::memcpy(corners, h.corners, sizeof(h.corners));
-    if (axes) std::memcpy(axes, h.axes, sizeof(h.axes));
-    if (num_axes) *num_axes = (uint32_t)h.naxes;
-    if (valid) *valid = h.valid;
-    return PCV_OK;
-  }
-  uint32_t na = 0;
-  double wide_axes[3 * PCV_WIDE_AXES];
-  const int rc = pcv_shapes_get_ex(s, i, corners, wide_axes, PCV_WIDE_AXES, &na, valid);
-  if (rc) return rc;
-  if (na > PCV_MAX_AXES) return s->ctx->fail(PCV_E_INVALID, "shape has more than 26 axes: use pcv_shapes_get_ex");
-  if (axes) std::memcpy(axes, wide_axes, sizeof(double) * 3 * na);
-  if (num_axes) *num_axes = na;
-  return PCV_OK;
-}
-
-extern "C" int pcv_shapes_get_ex(pcv_shapes* s, uint32_t i, double corners[24], double* axes, uint32_t axes_capacity,
-                                 uint32_t* num_axes, int* valid) {
-  if (!s || i >= s->count) return PCV_E_INVALID;
-  pcv_ctx* ctx = s->ctx;
-  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  PcvShapeDev h;
-  PCV_HIP_CHECK(ctx, hipMemcpy(&h, s->dev + i, sizeof(h), hipMemcpyDeviceToHost));
-  if (corners) std::memcpy(corners, h.corners, sizeof(h.corners));
-  uint32_t na = (uint32_t)h.naxes;
-  const double* src = h.axes;
-  PcvShapeWide w;
-  if (h.kind == PCV_SHAPE_WEB_MERCATOR_RECT) {
-    PCV_HIP_CHECK(ctx, hipMemcpy(&w, h.wide, sizeof(w), hipMemcpyDeviceToHost));
-    na = (uint32_t)w.naxes;
-    src = w.axes;
-  }
-  if (axes) std::memcpy(axes, src, sizeof(double) * 3 * std::min(na, axes_capacity));
-  if (num_axes) *num_axes = na;
-  if (valid) *valid = h.valid;
-  return PCV_OK;
-}
-
-// Device-resident query view of an octree, built lazily (pcv_octree::query).
-struct PcvOctreeQuery {
-  uint32_t m = 0;
-  double* cubes = nullptr;     // Node::get_child recurrence
-  double* fb_cubes = nullptr;  // NodeId::find_bounding_cube recurrence
-  BatchNode* nodes = nullptr;  // what the point query's descriptors need of each node
-  uint32_t* first_child = nullptr;
-  uint8_t* child_mask = nullptr;
-  uint8_t* empty = nullptr;
-  std::vector<uint32_t> h_first_child;  // host copies for host-side traversals
-  std::vector<uint8_t> h_child_mask;
-};
-
-const BatchNode* pcv_octree_query_nodes(const pcv_octree* t) { return t->query ? t->query->nodes : nullptr; }
-
-int pcv_octree_prepare_query(pcv_octree* t) {
-  if (t->query) return PCV_OK;
-  pcv_ctx* ctx = t->ctx;
-  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const uint32_t m = (uint32_t)t->nodes.size();
-  std::vector<double> cubes(4 * (size_t)m + 4), fb(4 * (size_t)m + 4);
-  std::vector<uint32_t> first(m + 1, 0);
-  std::vector<uint8_t> mask(m + 1, 0), empty(m + 1, 0);
-  std::vector<BatchNode> nodes(m);
-  // nodes are sorted by (level, index): children of a node are contiguous, in digit order
-  typedef unsigned __int128 u128;
-  auto idx_of = [&](const pcv_node_info& n) { return ((u128)(n.id_high & 0x00ffffffffffffffull) << 64) | n.id_low; };
-  std::vector<uint32_t> level_start(258, m);
-  for (uint32_t i = m; i-- > 0;) level_start[t->nodes[i].level] = i;
-  for (int l = 255; l >= 0; --l)
-    if (level_start[l] == m && l + 1 < 258) level_start[l] = level_start[l + 1];
-  // root cube: Cube::bounding (aabb.rs:149-157)
-  const double root_edge =
-      std::fmax(std::fmax(t->bbox_max[0] - t->bbox_min[0], t->bbox_max[1] - t->bbox_min[1]), t->bbox_max[2] - t->bbox_min[2]);
-  std::vector<int> has_parent(m, 0);
-  for (uint32_t i = 0; i < m; ++i) {
-    const pcv_node_info& n = t->nodes[i];
-    empty[i] = n.num_points == 0;
-    nodes[i] = batch_node(n);
-    for (int a = 0; a < 3; ++a) fb[4 * (size_t)i + a] = n.cube_min[a];
-    fb[4 * (size_t)i + 3] = n.cube_edge;
-    if (n.level == 0) {
-      for (int a = 0; a < 3; ++a) cubes[a] = t->bbox_min[a];
-      cubes[3] = root_edge;
-      has_parent[i] = 1;
-    }
-    // children: binary search the next level for index * 8 .. index * 8 + 7
-    const uint32_t lo = level_start[n.level + 1], hi = level_start[n.level + 2];
-    const u128 want = idx_of(n) << 3;
-    uint32_t a = lo, b = hi;
-    while (a < b) {
-      uint32_t mid = a + (b - a) / 2;
-      if (idx_of(t->nodes[mid]) < want) a = mid + 1;
-      else b = mid;
-    }
-    first[i] = a;
-    uint32_t c = a;
-    while (c < hi && (idx_of(t->nodes[c]) >> 3) == idx_of(n) && t->nodes[c].level == n.level + 1) {
-      const unsigned digit = (unsigned)(idx_of(t->nodes[c]) & 7);
-      mask[i] |= (uint8_t)(1u << digit);
-      if (has_parent[i]) {  // Node::get_child (node.rs:190-211): min += half only where the bit is set
-        const double half = cubes[4 * (size_t)i + 3] / 2.;
-        double* cc = &cubes[4 * (size_t)c];
-        cc[0] = cubes[4 * (size_t)i + 0];
-        cc[1] = cubes[4 * (size_t)i + 1];
-        cc[2] = cubes[4 * (size_t)i + 2];
-        if (digit & 1) cc[2] += half;
-        if (digit & 2) cc[1] += half;
-        if (digit & 4) cc[0] += half;
-        cc[3] = half;
-        has_parent[c] = 1;
-      }
-      ++c;
-    }
-  }
-  PcvOctreeQuery* q = new PcvOctreeQuery();
-  q->m = m;
-  q->h_first_child = first;
-  q->h_child_mask = mask;
-  void* p;
-  int rc;
-  size_t bytes = (size_t)(m + 1) * (64 + sizeof(BatchNode) + 4 + 2);
-  if ((rc = ctx->dev_alloc(&p, bytes))) {
-    delete q;
-    return rc;
-  }
-  uint8_t* base = (uint8_t*)p;
-  q->cubes = (double*)base;
-  q->fb_cubes = q->cubes + 4 * (size_t)(m + 1);
-  q->nodes = (BatchNode*)(q->fb_cubes + 4 * (size_t)(m + 1));
-  q->first_child = (uint32_t*)(q->nodes + (m + 1));
-  q->child_mask = (uint8_t*)(q->first_child + (m + 1));
-  q->empty = q->child_mask + (m + 1);
-  hipError_t e = hipMemcpy(q->cubes, cubes.data(), 32 * (size_t)m, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(q->fb_cubes, fb.data(), 32 * (size_t)m, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(q->nodes, nodes.data(), sizeof(BatchNode) * (size_t)m, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(q->first_child, first.data(), 4 * (size_t)m, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(q->child_mask, mask.data(), (size_t)m, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(q->empty, empty.data(), (size_t)m, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    ctx->dev_free(p);
-    delete q;
-    return ctx->fail(PCV_E_HIP, hipGetErrorString(e));
-  }
-  t->query = q;
-  return PCV_OK;
-}
-
-void pcv_octree_release_query(pcv_octree* t) {
-  if (!t->query) return;
-  t->ctx->dev_free(t->query->cubes);
-  delete t->query;
-  t->query = nullptr;
-}
-
-extern "C" int pcv_cull_nodes(pcv_ctx* ctx, const pcv_shapes* shapes, pcv_octree* tree, uint8_t* relation,
-                              double* size_on_screen_out) {
-  if (!ctx) return PCV_E_INVALID;
-  if (!shapes || !tree || !relation) return ctx->fail(PCV_E_INVALID, "null argument");
-  int rc = pcv_octree_prepare_query(tree);
-  if (rc) return rc;
-  const uint32_t m = tree->query->m, f = shapes->count;
-  if (m == 0 || f == 0) return PCV_OK;
-  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  PcvScratch sc(ctx);
-  uint8_t* d_rel;
-  double* d_sz = nullptr;
-  if ((rc = sc.get(&d_rel, (size_t)f * m))) return rc;
-  if (size_on_screen_out && (rc = sc.get(&d_sz, (size_t)f * m))) return rc;
-  {
-    PcvProf prof(ctx, PCV_K_CULL_NODES);
-    // cull against NodeMeta cubes (find_bounding_cube), as nodes_in_location does; get_visible_nodes' own
-    // get_child cubes differ at most in the sign of zero
-    hipLaunchKernelGGL(cull_nodes_kernel<false>, dim3((m + 255) / 256, f), dim3(256), 0, ctx->stream, shapes->dev, m,
-                       tree->query->fb_cubes, d_rel, d_sz);
-    if (shapes->wide)  // the web-mercator rectangles' rows, over what the launch above wrote for them
-      hipLaunchKernelGGL(cull_nodes_kernel<true>, dim3((m + 255) / 256, f), dim3(256), 0, ctx->stream, shapes->dev, m,
-                         tree->query->fb_cubes, d_rel, d_sz);
-  }
-  PCV_HIP_CHECK(ctx, hipGetLastError());
-  PCV_HIP_CHECK(ctx, hipMemcpyAsync(relation, d_rel, (size_t)f * m, hipMemcpyDeviceToHost, ctx->stream));
-  if (d_sz) PCV_HIP_CHECK(ctx, hipMemcpyAsync(size_on_screen_out, d_sz, (size_t)f * m * 8, hipMemcpyDeviceToHost, ctx->stream));
-  PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->prof_resolve();
-  return PCV_OK;
-}
-
-extern "C" int pcv_cull_nodes_sparse(pcv_ctx* ctx, const pcv_shapes* shapes, pcv_octree* tree, uint32_t capacity, uint32_t* counts,
-                                     uint32_t* node_indices, uint8_t* relation, double* size_on_screen_out) {
-  if (!ctx) return PCV_E_INVALID;
-  if (!shapes || !tree || !counts || (capacity && (!node_indices || !relation))) return ctx->fail(PCV_E_INVALID, "null argument");
-  int rc = pcv_octree_prepare_query(tree);
-  if (rc) return rc;
-  const uint32_t m = tree->query->m, f = shapes->count;
-  if (f == 0) return PCV_OK;
-  if (m == 0) {
-    std::memset(counts, 0, (size_t)f * 4);
-    return PCV_OK;
-  }
-  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  PcvScratch sc(ctx);
-  const size_t rows = (size_t)f * (capacity ? capacity : 1);
-  uint32_t *d_cnt, *d_node;
-  uint8_t* d_rel;
-  double* d_sz = nullptr;
-  if ((rc = sc.get(&d_cnt, f)) || (rc = sc.get(&d_node, rows)) || (rc = sc.get(&d_rel, rows))) return rc;
-  if (size_on_screen_out && (rc = sc.get(&d_sz, rows))) return rc;
-  uint32_t* d_redo;
-  if ((rc = sc.get(&d_redo, f))) return rc;
-  {
-    PcvProf prof(ctx, PCV_K_CULL_NODES_SPARSE);
-    if (d_sz)
-      hipLaunchKernelGGL(cull_nodes_tree_kernel<true>, dim3((f + 3) / 4), dim3(256), 0, ctx->stream, shapes->dev, f, m, tree->query->fb_cubes,
-                         tree->query->first_child, tree->query->child_mask, capacity, d_cnt, d_node, d_rel, d_sz, d_redo,
-                         (const uint64_t*)nullptr);
-    else
-      hipLaunchKernelGGL(cull_nodes_tree_kernel<false>, dim3((f + 3) / 4), dim3(256), 0, ctx->stream, shapes->dev, f, m, tree->query->fb_cubes,
-                         tree->query->first_child, tree->query->child_mask, capacity, d_cnt, d_node, d_rel, d_sz, d_redo,
-                         (const uint64_t*)nullptr);
-    hipLaunchKernelGGL(cull_nodes_sparse_kernel<false>, dim3(f), dim3(256), 0, ctx->stream, shapes->dev, m, tree->query->fb_cubes, capacity, d_cnt,
-                       d_node, d_rel, d_sz, (const uint32_t*)d_redo);
-    if (shapes->wide)  // the web-mercator rectangles' lists and counts, over what the launches above wrote for them
-      hipLaunchKernelGGL(cull_nodes_sparse_kernel<true>, dim3(f), dim3(256), 0, ctx->stream, shapes->dev, m, tree->query->fb_cubes, capacity,
-                         d_cnt, d_node, d_rel, d_sz, (const uint32_t*)nullptr);
-  }
-  PCV_HIP_CHECK(ctx, hipGetLastError());
-  PCV_HIP_CHECK(ctx, hipMemcpyAsync(counts, d_cnt, (size_t)f * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (capacity) {
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(node_indices, d_node, rows * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(relation, d_rel, rows, hipMemcpyDeviceToHost, ctx->stream));
-    if (d_sz) PCV_HIP_CHECK(ctx, hipMemcpyAsync(size_on_screen_out, d_sz, rows * 8, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->prof_resolve();
-  return PCV_OK;
-}
-
-static int traverse(pcv_ctx* ctx, const pcv_shapes* shapes, pcv_octree* tree, uint32_t capacity, uint32_t* counts,
-                    uint32_t* node_indices, int32_t* status, bool visible) {
-  if (!ctx) return PCV_E_INVALID;
-  if (!shapes || !tree || !counts || (capacity && !node_indices)) return ctx->fail(PCV_E_INVALID, "null argument");
-  int rc = pcv_octree_prepare_query(tree);
-  if (rc) return rc;
-  const uint32_t m = tree->query->m, f = shapes->count;
-  if (f == 0) return PCV_OK;
-  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  PcvScratch sc(ctx);
-  uint32_t *d_counts, *d_out;
-  int32_t* d_status;
-  if ((rc = sc.get(&d_counts, f)) || (rc = sc.get(&d_out, (size_t)f * (capacity ? capacity : 1))) || (rc = sc.get(&d_status, f))) return rc;
-  PCV_HIP_CHECK(ctx, hipMemsetAsync(d_status, 0, 4 * (size_t)f, ctx->stream));
-  // scratch per in-flight shape: m heap entries (16 B) or m queue slots (4 B); bound it to ~256 MiB per batch
-  const size_t per = visible ? sizeof(HeapEntry) * (size_t)(m ? m : 1) : 4 * (size_t)(m ? m : 1);
-  uint32_t batch = (uint32_t)std::min<size_t>(f, std::max<size_t>(64, ((size_t)256 << 20) / per));
-  void* scratch;
-  if ((rc = ctx->dev_alloc(&scratch, per * batch))) return rc;
-  sc.ptrs.push_back(scratch);
-  QTree qt{m, tree->query->cubes, tree->query->first_child, tree->query->child_mask, tree->query->empty};
-  uint32_t* d_redo = nullptr;
-  if (!visible && m > 0) {
-    // round 6: one WAVE per shape walks the tree with the lanes as the shape's axes (cull_nodes_tree_kernel<.., HIER>): the
-    // one-lane-per-shape walk below took 3.1 ms for 10 000 frusta; it stays for the shapes whose frontier outgrows the wave's
-    // queue and for AllPoints
-    if ((rc = sc.get(&d_redo, f))) return rc;
-    PcvProf prof(ctx, PCV_K_NODES_IN_LOCATION);
-    hipLaunchKernelGGL((cull_nodes_tree_kernel<false, true>), dim3((f + 3) / 4), dim3(256), 0, ctx->stream, shapes->dev, f, m, tree->query->fb_cubes,
-                       tree->query->first_child, tree->query->child_mask, capacity, d_counts, d_out, (uint8_t*)nullptr, (double*)nullptr, d_redo,
-                       (const uint64_t*)nullptr);
-  }
-  for (uint32_t first = 0; first < f; first += batch) {
-    const uint32_t nb = std::min(batch, f - first);
-    PcvProf prof(ctx, visible ? PCV_K_VISIBLE_NODES : PCV_K_NODES_IN_LOCATION);
-    if (visible)
-      hipLaunchKernelGGL(visible_nodes_kernel, dim3((nb + 3) / 4), dim3(256), 0, ctx->stream, shapes->dev, first, nb, qt,
-                         (HeapEntry*)scratch, capacity, d_counts, d_out, d_status);
-    else
-      hipLaunchKernelGGL(nodes_in_location_kernel<false>, dim3((nb + 63) / 64), dim3(64), 0, ctx->stream, shapes->dev, first, nb,
-                         qt, tree->query->fb_cubes, (uint32_t*)scratch, capacity, d_counts, d_out, (const uint32_t*)d_redo,
-                         (const uint64_t*)nullptr);
-    if (!visible && shapes->wide)  // the web-mercator rectangles' lists and counts, over what the launches above wrote for them
-      hipLaunchKernelGGL(nodes_in_location_kernel<true>, dim3((nb + 63) / 64), dim3(64), 0, ctx->stream, shapes->dev, first, nb,
-                         qt, tree->query->fb_cubes, (uint32_t*)scratch, capacity, d_counts, d_out, (const uint32_t*)nullptr,
-                         (const uint64_t*)nullptr);
-  }
-  PCV_HIP_CHECK(ctx, hipGetLastError());
-  PCV_HIP_CHECK(ctx, hipMemcpyAsync(counts, d_counts, 4 * (size_t)f, hipMemcpyDeviceToHost, ctx->stream));
-  if (capacity) PCV_HIP_CHECK(ctx, hipMemcpyAsync(node_indices, d_out, 4 * (size_t)f * capacity, hipMemcpyDeviceToHost, ctx->stream));
-  if (status) PCV_HIP_CHECK(ctx, hipMemcpyAsync(status, d_status, 4 * (size_t)f, hipMemcpyDeviceToHost, ctx->stream));
-  PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->prof_resolve();
-  return PCV_OK;
-}
-
-extern "C" int pcv_visible_nodes(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree, uint32_t capacity,
-                                 uint32_t* counts, uint32_t* node_indices, int32_t* status) {
-  return traverse(ctx, frusta, tree, capacity, counts, node_indices, status, true);
-}
-extern "C" int pcv_nodes_in_location(pcv_ctx* ctx, const pcv_shapes* shapes, pcv_octree* tree, uint32_t capacity,
-                                     uint32_t* counts, uint32_t* node_indices) {
-  return traverse(ctx, shapes, tree, capacity, counts, node_indices, nullptr, false);
-}
-
 // K8 on a view whose positions and attribute are on the device: keep flags into `keep` (a host buffer if keep_host), the
 // kept count into *kept
 static int launch_cull_points(pcv_ctx* ctx, PcvScratch& sc, const pcv_shapes* shapes, uint32_t shape_index, const PointsView& v,
@@ -1915,8 +732,10 @@ static int launch_cull_points(pcv_ctx* ctx, PcvScratch& sc, const pcv_shapes* sh
   return PCV_OK;
 }
 
+// K8 on a view whose positions are on the device: the closed interval on `attr` (n floats in `attr_mem`), the flags into
+// `keep` (a host buffer if keep_host)
 static int run_cull_points(pcv_ctx* ctx, const pcv_shapes* shapes, uint32_t shape_index, PointsView v, const float* attr,
-                           const double* interval, int mem, uint8_t* keep, uint64_t* kept) {
+                           const double* interval, int attr_mem, bool keep_host, uint8_t* keep, uint64_t* kept) {
   if (!shapes || shape_index >= shapes->count || !keep) return ctx->fail(PCV_E_INVALID, "bad shape / null output");
   PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   PcvScratch sc(ctx);
@@ -1928,7 +747,7 @@ static int run_cull_points(pcv_ctx* ctx, const pcv_shapes* shapes, uint32_t shap
     v.has_interval = 1;
     v.lo = interval[0];
     v.hi = interval[1];
-    if (mem == PCV_MEM_HOST) {
+    if (attr_mem == PCV_MEM_HOST) {
       float* da;
       if ((rc = sc.get(&da, v.n))) return rc;
       PCV_HIP_CHECK(ctx, hipMemcpyAsync(da, attr, v.n * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -1937,7 +756,7 @@ static int run_cull_points(pcv_ctx* ctx, const pcv_shapes* shapes, uint32_t shap
       v.attr = attr;
     }
   }
-  return launch_cull_points(ctx, sc, shapes, shape_index, v, mem == PCV_MEM_HOST, keep, kept);
+  return launch_cull_points(ctx, sc, shapes, shape_index, v, keep_host, keep, kept);
 }
 
 extern "C" int pcv_cull_points(pcv_ctx* ctx, const pcv_shapes* shapes, uint32_t shape_index, const pcv_points* points,
@@ -1947,33 +766,26 @@ extern "C" int pcv_cull_points(pcv_ctx* ctx, const pcv_shapes* shapes, uint32_t 
   if (points->n > 0 && (!points->x || !points->y || !points->z)) return ctx->fail(PCV_E_INVALID, "x/y/z must be non-null");
   PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   PcvScratch sc(ctx);
+  const PointPlanes in{const_cast<double*>(points->x), const_cast<double*>(points->y), const_cast<double*>(points->z)};
+  PointPlanes d = in;
+  int rc;
+  if (points->mem == PCV_MEM_HOST && points->n &&
+      ((rc = planes_alloc(sc, points->n, in, &d)) || (rc = planes_copy(ctx, d, in, points->n, hipMemcpyHostToDevice))))
+    return rc;
   PointsView v{};
   v.n = points->n;
-  v.x = points->x;
-  v.y = points->y;
-  v.z = points->z;
-  int rc;
-  if (points->mem == PCV_MEM_HOST && points->n) {
-    double *x, *y, *z;
-    if ((rc = sc.get(&x, v.n)) || (rc = sc.get(&y, v.n)) || (rc = sc.get(&z, v.n))) return rc;
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(x, points->x, v.n * 8, hipMemcpyHostToDevice, ctx->stream));
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(y, points->y, v.n * 8, hipMemcpyHostToDevice, ctx->stream));
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(z, points->z, v.n * 8, hipMemcpyHostToDevice, ctx->stream));
-    v.x = x;
-    v.y = y;
-    v.z = z;
-  }
-  return run_cull_points(ctx, shapes, shape_index, v, points->intensity, interval, points->mem, keep, kept);
+  v.x = d.x;
+  v.y = d.y;
+  v.z = d.z;
+  return run_cull_points(ctx, shapes, shape_index, v, points->intensity, interval, points->mem, points->mem == PCV_MEM_HOST, keep, kept);
 }
 
 extern "C" int pcv_cull_node_points(pcv_ctx* ctx, const pcv_shapes* shapes, uint32_t shape_index, pcv_octree* tree,
                                     uint64_t node, const double* interval, uint8_t* keep, uint64_t* kept) {
   if (!ctx) return PCV_E_INVALID;
   if (!tree || node >= tree->nodes.size()) return ctx->fail(PCV_E_INVALID, "bad node");
-  if (!tree->d_xyz) {  // an octree opened from a directory: node files are uploaded on first use
-    int lrc = pcv_octree_load_device(tree);
-    if (lrc) return lrc;
-  }
+  int rc = pcv_octree_ensure_query(tree);
+  if (rc) return rc;
   const pcv_node_info& n = tree->nodes[node];
   PointsView v{};
   v.n = (uint64_t)n.num_points;
@@ -1983,19 +795,10 @@ extern "C" int pcv_cull_node_points(pcv_ctx* ctx, const pcv_shapes* shapes, uint
   v.cube_edge = n.cube_edge;
   const float* attr = tree->has_intensity ? reinterpret_cast<const float*>(tree->d_int) + n.point_offset : nullptr;
   if (interval && !attr) return ctx->fail(PCV_E_INVALID, "octree has no intensity attribute to filter on");
-  // keep is a HOST buffer here; the attribute already lives on the device
-  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  PcvScratch sc(ctx);
   if (kept) *kept = 0;
   if (v.n == 0) return PCV_OK;
-  if (!shapes || shape_index >= shapes->count || !keep) return ctx->fail(PCV_E_INVALID, "bad shape / null output");
-  if (interval) {
-    v.has_interval = 1;
-    v.lo = interval[0];
-    v.hi = interval[1];
-    v.attr = attr;
-  }
-  return launch_cull_points(ctx, sc, shapes, shape_index, v, true, keep, kept);
+  // keep is a HOST buffer here; the attribute already lives on the device
+  return run_cull_points(ctx, shapes, shape_index, v, attr, interval, PCV_MEM_DEVICE, true, keep, kept);
 }
 
 extern "C" int pcv_transform_points(pcv_ctx* ctx, const double iso[7], const pcv_points* points, double* ox, double* oy,
@@ -2006,32 +809,19 @@ extern "C" int pcv_transform_points(pcv_ctx* ctx, const double iso[7], const pcv
   if (n == 0) return PCV_OK;
   PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   PcvScratch sc(ctx);
-  const double *x = points->x, *y = points->y, *z = points->z;
-  double *dx = ox, *dy = oy, *dz = oz;
+  const PointPlanes in{const_cast<double*>(points->x), const_cast<double*>(points->y), const_cast<double*>(points->z)}, out{ox, oy, oz};
+  PointPlanes di = in, d = out;
   int rc;
-  if (points->mem == PCV_MEM_HOST) {
-    double *ix, *iy, *iz;
-    if ((rc = sc.get(&ix, n)) || (rc = sc.get(&iy, n)) || (rc = sc.get(&iz, n)) || (rc = sc.get(&dx, n)) ||
-        (rc = sc.get(&dy, n)) || (rc = sc.get(&dz, n)))
-      return rc;
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(ix, x, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(iy, y, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(iz, z, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    x = ix;
-    y = iy;
-    z = iz;
-  }
+  if (points->mem == PCV_MEM_HOST && ((rc = planes_alloc(sc, n, in, &di)) || (rc = planes_alloc(sc, n, out, &d)) ||
+                                      (rc = planes_copy(ctx, di, in, n, hipMemcpyHostToDevice))))
+    return rc;
   {
     PcvProf prof(ctx, PCV_K_TRANSFORM_POINTS);
-    hipLaunchKernelGGL(transform_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, x, y, z,
-                       iso[0], iso[1], iso[2], iso[3], iso[4], iso[5], iso[6], dx, dy, dz);
+    hipLaunchKernelGGL(transform_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, di.x, di.y, di.z,
+                       iso[0], iso[1], iso[2], iso[3], iso[4], iso[5], iso[6], d.x, d.y, d.z);
   }
   PCV_HIP_CHECK(ctx, hipGetLastError());
-  if (points->mem == PCV_MEM_HOST) {
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(ox, dx, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(oy, dy, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(oz, dz, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-  }
+  if (points->mem == PCV_MEM_HOST && (rc = planes_copy(ctx, out, d, n, hipMemcpyDeviceToHost))) return rc;
   PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   ctx->prof_resolve();
   return PCV_OK;
@@ -2049,12 +839,8 @@ static int query_points_impl(pcv_ctx* ctx, const pcv_shapes* shapes, uint32_t sh
   if (mem != PCV_MEM_HOST && mem != PCV_MEM_DEVICE) return ctx->fail(PCV_E_INVALID, "bad mem");
   *count = 0;
   if (tree->nodes.empty()) return PCV_OK;
-  if (!tree->d_xyz) {  // an octree opened from a directory: node files are uploaded on first use
-    int lrc = pcv_octree_load_device(tree);
-    if (lrc) return lrc;
-  }
   if (interval && !tree->has_intensity) return ctx->fail(PCV_E_INVALID, "octree has no intensity attribute to filter on");
-  int rc = pcv_octree_prepare_query(tree);
+  int rc = pcv_octree_ensure_query(tree);
   if (rc) return rc;
   PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   PcvScratch sc(ctx);
@@ -2064,36 +850,14 @@ static int query_points_impl(pcv_ctx* ctx, const pcv_shapes* shapes, uint32_t sh
     if (*only_node >= tree->nodes.size()) return ctx->fail(PCV_E_INVALID, "bad node");
     nodes.push_back((uint32_t)*only_node);
   } else {
-  // 1. PointCloud::nodes_in_location for this one shape: the Relation of every node cube in one dense launch
-  //    (same sat() as the traversal kernel), then the breadth-first walk of NodeIdsIterator on the host.
-  uint8_t* d_rel;
-  if ((rc = sc.get(&d_rel, m))) return rc;
-  {
-    PcvProf prof(ctx, PCV_K_CULL_NODES);
-    if (shapes->kinds[shape_index] == PCV_SHAPE_WEB_MERCATOR_RECT)
-      hipLaunchKernelGGL(cull_nodes_kernel<true>, dim3((m + 255) / 256, 1), dim3(256), 0, ctx->stream, shapes->dev + shape_index, m,
-                         tree->query->fb_cubes, d_rel, (double*)nullptr);
-    else
-      hipLaunchKernelGGL(cull_nodes_kernel<false>, dim3((m + 255) / 256, 1), dim3(256), 0, ctx->stream, shapes->dev + shape_index, m,
-                         tree->query->fb_cubes, d_rel, (double*)nullptr);
-  }
-  std::vector<uint8_t> rel(m);
-  PCV_HIP_CHECK(ctx, hipMemcpyAsync(rel.data(), d_rel, m, hipMemcpyDeviceToHost, ctx->stream));
-  PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  nodes.reserve(m);
-  {
-    std::vector<uint32_t> queue;
-    queue.reserve(m);
-    queue.push_back(0);
-    for (size_t head = 0; head < queue.size(); ++head) {
-      const uint32_t cur = queue[head];
-      if (rel[cur] == 2) continue;
-      uint32_t c = tree->query->h_first_child[cur];
-      for (int ci = 0; ci < 8; ++ci)
-        if ((tree->query->h_child_mask[cur] >> ci) & 1) queue.push_back(c++);
-      nodes.push_back(cur);
-    }
-  }
+    // 1. PointCloud::nodes_in_location for this one shape: the Relation of every node cube in one dense launch
+    //    (same sat() as the traversal kernel), then the breadth-first walk of NodeIdsIterator on the host.
+    uint8_t* d_rel;
+    if ((rc = sc.get(&d_rel, m)) || (rc = pcv_launch_relation_row(ctx, shapes, shape_index, tree, d_rel))) return rc;
+    std::vector<uint8_t> rel(m);
+    PCV_HIP_CHECK(ctx, hipMemcpyAsync(rel.data(), d_rel, m, hipMemcpyDeviceToHost, ctx->stream));
+    PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    pcv_query_walk(rel.data(), tree->query->h_first_child.data(), tree->query->h_child_mask.data(), m, &nodes);
   }
   const uint32_t nn = (uint32_t)nodes.size();
   // 2. one segment per non-empty node, in traversal order, chunked as the batch chunks its segments (shape 0 of
@@ -2284,11 +1048,7 @@ static int query_batch_run(pcv_ctx* ctx, const pcv_shapes* shapes, pcv_octree* t
   b->seg_chunk.assign(1, 0);
   b->seg_off.assign(1, 0);
   if (S == 0 || tree->nodes.empty()) return PCV_OK;
-  if (!tree->d_xyz) {  // an octree opened from a directory: node files are uploaded on first use
-    int lrc = pcv_octree_load_device(tree);
-    if (lrc) return lrc;
-  }
-  int rc = pcv_octree_prepare_query(tree);
+  int rc = pcv_octree_ensure_query(tree);
   if (rc) return rc;
   PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   PcvScratch sc(ctx);
@@ -2301,47 +1061,28 @@ static int query_batch_run(pcv_ctx* ctx, const pcv_shapes* shapes, pcv_octree* t
     h_iv[s] = BatchIval{used ? intervals[2 * (size_t)s] : 0.0, used ? intervals[2 * (size_t)s + 1] : 0.0, used ? 1u : 0u, 0u};
   }
   BatchIval* d_iv;
-  uint32_t *d_cnt, *d_redo;
+  uint32_t *d_cnt, *d_lists;
   uint64_t* d_shape_first;
-  if ((rc = sc.get(&d_iv, S)) || (rc = sc.get(&d_cnt, S)) || (rc = sc.get(&d_redo, S)) ||
+  if ((rc = sc.get(&d_iv, S)) || (rc = sc.get(&d_cnt, S)) || (rc = sc.get(&d_lists, pcv_node_lists_scratch(S, m))) ||
       (rc = sc.get(&d_shape_first, (size_t)S + 1)))
     return rc;
   PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_iv, h_iv.data(), sizeof(BatchIval) * S, hipMemcpyHostToDevice, ctx->stream));
-  // 1. node lists: counts, rows, lists. The one-lane-per-shape fallback keeps m queue slots per shape in flight: bounded to
-  //    ~256 MiB per launch, as traverse() does
-  QTree qt{m, q->cubes, q->first_child, q->child_mask, q->empty};
-  const size_t per_shape = 4 * (size_t)m;
-  const uint32_t fb_batch = (uint32_t)std::min<size_t>(S, std::max<size_t>(64, ((size_t)256 << 20) / per_shape));
-  uint32_t* d_queues;
-  if ((rc = sc.get(&d_queues, per_shape / 4 * fb_batch))) return rc;
-  auto node_lists = [&](uint32_t capacity, uint32_t* out, const uint64_t* rows) {
-    PcvProf prof(ctx, PCV_K_QUERY_BATCH_NODES);
-    hipLaunchKernelGGL((cull_nodes_tree_kernel<false, true>), dim3((S + 3) / 4), dim3(256), 0, ctx->stream, shapes->dev, S, m, q->fb_cubes,
-                       q->first_child, q->child_mask, capacity, d_cnt, out, (uint8_t*)nullptr, (double*)nullptr, d_redo, rows);
-    for (uint32_t first = 0; first < S; first += fb_batch)
-      hipLaunchKernelGGL(nodes_in_location_kernel<false>, dim3((std::min(fb_batch, S - first) + 63) / 64), dim3(64), 0, ctx->stream, shapes->dev,
-                         first, std::min(fb_batch, S - first), qt, q->fb_cubes, d_queues, capacity, d_cnt, out, (const uint32_t*)d_redo, rows);
-    if (shapes->wide)  // the web-mercator rectangles' lists and counts, over what the launches above wrote for them
-      for (uint32_t first = 0; first < S; first += fb_batch)
-        hipLaunchKernelGGL(nodes_in_location_kernel<true>, dim3((std::min(fb_batch, S - first) + 63) / 64), dim3(64), 0, ctx->stream,
-                           shapes->dev, first, std::min(fb_batch, S - first), qt, q->fb_cubes, d_queues, capacity, d_cnt, out,
-                           (const uint32_t*)nullptr, rows);
+  // 1. node lists: counts, rows, lists
+  auto node_lists = [&](uint32_t* out, const uint64_t* rows) {
+    return pcv_launch_node_lists(ctx, PCV_K_QUERY_BATCH_NODES, false, shapes, tree, 0, d_cnt, out, d_lists, rows);
   };
   auto scan = [&](const uint32_t* in, uint64_t n, uint64_t* out) {
     PcvProf prof(ctx, PCV_K_QUERY_BATCH_SCAN);
     return pcv_batch_scan(ctx, sc, in, n, out);
   };
-  node_lists(0, nullptr, nullptr);
-  PCV_HIP_CHECK(ctx, hipGetLastError());
-  if ((rc = scan(d_cnt, S, d_shape_first))) return rc;
+  if ((rc = node_lists(nullptr, nullptr)) || (rc = scan(d_cnt, S, d_shape_first))) return rc;
   PCV_HIP_CHECK(ctx, hipMemcpyAsync(b->shape_first.data(), d_shape_first, 8 * ((size_t)S + 1), hipMemcpyDeviceToHost, ctx->stream));
   PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // read-back 1: the segment count
   const uint64_t nseg = b->shape_first[S];
   b->nseg = nseg;
   if (nseg == 0) return PCV_OK;
   if ((rc = ctx->dev_alloc((void**)&b->d_seg_node, 4 * nseg))) return rc;
-  node_lists(0, b->d_seg_node, d_shape_first);
-  PCV_HIP_CHECK(ctx, hipGetLastError());
+  if ((rc = node_lists(b->d_seg_node, d_shape_first))) return rc;
   // 2. segment sizes: flags (padded) and chunks at shift 0, 1, 2; the shift is chosen from the total below, as
   //    query_points_impl chooses it
   uint32_t *d_seg_flags32, *d_seg_chunks32;
@@ -2387,7 +1128,7 @@ static int query_batch_run(pcv_ctx* ctx, const pcv_shapes* shapes, pcv_octree* t
     PcvProf prof(ctx, PCV_K_QUERY_BATCH_FLAGS);
     if ((rc = launch_query_flags(ctx, -1, shapes->dev, d_iv, desc, (uint32_t)nchunks, tree, b->d_keep, d_cc))) return rc;
     if (std::find(shapes->kinds.begin(), shapes->kinds.end(), (int32_t)PCV_SHAPE_WEB_MERCATOR_RECT) != shapes->kinds.end() &&
-        (rc = launch_query_flags_wmr(ctx, shapes->dev, d_iv, desc, (uint32_t)nchunks, tree, b->d_keep, d_cc)))
+        (rc = launch_flags(ctx, query_flags_wmr_kernel, shapes->dev, d_iv, desc, (uint32_t)nchunks, tree, b->d_keep, d_cc)))
       return rc;
   }
   // 4. kept points per chunk -> u64 offsets; segment offsets from the first chunk of each segment

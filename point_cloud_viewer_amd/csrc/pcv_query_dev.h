@@ -1,11 +1,15 @@
-// pcv_query_dev.h — what the batched point query shares with its consumers on the device (pcv_query.hip, pcv_xray.hip):
-// the f64 vector helpers, Isometry3 rotation, the per-point decode of a node's bytes, the chunk descriptor and the batch.
+// pcv_query_dev.h — what the query sources (pcv_shapes.hip, pcv_cull.hip, pcv_query.hip) share with each other and with
+// their consumers on the device (pcv_xray.hip, pcv_render.hip): the f64 vector helpers, Isometry3 rotation, the per-point
+// decode of a node's bytes, the prepared shapes, the tree's query tables on the device, the chunk descriptor and the batch.
+// No kernel is shared across translation units: the point query reaches node culling through the two host functions at the
+// end.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <vector>
 
 #include "pcv_chain_dev.h"
+#include "pcv_query_tables.h"
 
 struct V3d {
   double x, y, z;
@@ -23,6 +27,17 @@ __host__ __device__ __forceinline__ V3d quat_rotate(const double* q, V3d v) {  /
   V3d t = v_scale(v_cross(qv, v), 2.0);
   V3d c = v_cross(qv, t);
   return v_add(v_add(v_scale(t, q[3]), c), v);
+}
+
+#define M4(m, r, c) (m)[(c) * 4 + (r)]
+// nalgebra Matrix4::transform_point
+__device__ __forceinline__ V3d m4_transform_point(const double* m, V3d p) {
+  double r0 = ((M4(m, 0, 0) * p.x + M4(m, 0, 1) * p.y) + M4(m, 0, 2) * p.z) + M4(m, 0, 3);
+  double r1 = ((M4(m, 1, 0) * p.x + M4(m, 1, 1) * p.y) + M4(m, 1, 2) * p.z) + M4(m, 1, 3);
+  double r2 = ((M4(m, 2, 0) * p.x + M4(m, 2, 1) * p.y) + M4(m, 2, 2) * p.z) + M4(m, 2, 3);
+  double n = ((M4(m, 3, 0) * p.x + M4(m, 3, 1) * p.y) + M4(m, 3, 2) * p.z) + M4(m, 3, 3);
+  if (n != 0.0) return {r0 / n, r1 / n, r2 / n};
+  return {r0, r1, r2};
 }
 
 // K8: keep mask. Positions either raw f64 SoA or a node's encoded bytes.
@@ -75,7 +90,7 @@ __device__ __forceinline__ V3d load_point(const PointsView& v, uint64_t i) {
           pcv_decode_coord(v.enc, c[2], v.cube_min[2], v.cube_edge)};
 }
 
-// ---- prepared shapes (pcv_shapes_create, pcv_query.hip) ------------------------------------------------------------
+// ---- prepared shapes (pcv_shapes_create, pcv_shapes.hip) ------------------------------------------------------------
 #define PCV_MAX_AXES 26
 struct PcvShapeDev {
   int32_t kind;   // PCV_SHAPE_*
@@ -120,14 +135,23 @@ struct pcv_shapes {
   std::vector<int32_t> kinds;  // host copy: the point kernels are compiled per shape kind
 };
 
-struct BatchNode {  // what the descriptors need of one node
-  uint64_t xyz_off, point_off;
-  double cube_min[3];
-  double cube_edge;
-  uint32_t n, enc;
+// Device-resident query view of an octree, built lazily (pcv_octree::query, pcv_octree_prepare_query in pcv_cull.hip): one
+// block laid out by PcvQueryLayout, the tables of pcv_query_tables.
+struct PcvOctreeQuery {
+  uint32_t m = 0;
+  double* cubes = nullptr;     // Node::get_child recurrence (the block starts here)
+  double* fb_cubes = nullptr;  // NodeId::find_bounding_cube recurrence
+  BatchNode* nodes = nullptr;  // what the point query's descriptors need of each node
+  uint32_t* first_child = nullptr;
+  uint8_t* child_mask = nullptr;
+  uint8_t* empty = nullptr;
+  std::vector<uint32_t> h_first_child;  // host copies for the host-side walk
+  std::vector<uint8_t> h_child_mask;
 };
 // the node table of a prepared octree on the device (pcv_octree_prepare_query), in node order
 const BatchNode* pcv_octree_query_nodes(const pcv_octree* t);
+// the tree's blobs (an octree opened from a directory: node files are uploaded on first use) and its query tables on the device
+int pcv_octree_ensure_query(pcv_octree* t);
 
 // pass 0 writes one descriptor per chunk, so that pass 1 has a single scalar load between "which chunk" and the
 // staging loads
@@ -160,3 +184,15 @@ struct pcv_query_batch {
 
 // out[0 .. n] = exclusive u64 scan of in[0 .. n), out[n] the total (asynchronous on ctx->stream)
 int pcv_batch_scan(pcv_ctx* ctx, PcvScratch& sc, const uint32_t* in, uint64_t n, uint64_t* out);
+
+// ---- node culling for the point query (pcv_cull.hip) ---------------------------------------------------------------
+// The Relation of every node cube (find_bounding_cube) to shape `shape_index`, dense, into d_rel[m] on ctx->stream: the
+// shape's own instance of cull_nodes_kernel, under the PCV_K_CULL_NODES label.
+int pcv_launch_relation_row(pcv_ctx* ctx, const pcv_shapes* shapes, uint32_t shape_index, const pcv_octree* tree, uint8_t* d_rel);
+// PointCloud::nodes_in_location of every shape, on ctx->stream: counts[f] and shape f's list at out + rows[f], of at most
+// rows[f + 1] - rows[f] entries (rows null: at out + f * capacity, of at most capacity; entries past the end are dropped,
+// the count is not). scratch: pcv_node_lists_scratch(shapes->count, m) u32. Profile brackets carry `label`: one per batch of
+// the one-lane walk, and one for the wave walk — its own (walk_bracket) or the first batch's.
+size_t pcv_node_lists_scratch(uint32_t nshapes, uint32_t m);
+int pcv_launch_node_lists(pcv_ctx* ctx, int label, bool walk_bracket, const pcv_shapes* shapes, const pcv_octree* tree,
+                          uint32_t capacity, uint32_t* counts, uint32_t* out, uint32_t* scratch, const uint64_t* rows);

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""Per-kernel comparison of two device-assembly files of one translation unit: which kernels are identical, differ, went or came.
+"""Per-kernel comparison of the device assembly of one translation unit before and after a change — or, when a source was
+split or merged, of several (comma-separated files per side): which kernels are identical, differ, went or came.
 
   hipcc <CXXFLAGS of csrc/Makefile> [-DPCV_EXPERIMENTS] --offload-device-only -S pcv_sort.hip -o before/pcv_sort.s   (old tree)
   hipcc ... -o after/pcv_sort.s                                                                                        (new tree)
   tools/kernel_asm_diff.py before/pcv_sort.s after/pcv_sort.s
+  tools/kernel_asm_diff.py before/pcv_query.s after/pcv_shapes.s,after/pcv_cull.s,after/pcv_query.s
 
 A kernel is its function body plus its .amdhsa_kernel descriptor. Assembler comments, .file / .loc / .ident lines and the
 per-file function index inside local labels (.LBB<i>_<n>, .Lfunc_end<i>, .LJTI<i>_<n>) are dropped: they move when another
@@ -12,7 +14,18 @@ import re
 import sys
 
 
-def kernels(path):
+def kernels(paths):
+    out = {}
+    for path in paths.split(","):
+        one = kernels_of(path)
+        dup = set(out) & set(one)
+        if dup:
+            sys.exit(f"{path}: kernels of another file of the same side: {sorted(dup)}")
+        out.update(one)
+    return out
+
+
+def kernels_of(path):
     body, desc, cur, into = {}, {}, None, None
     for line in open(path, errors="replace"):
         line = line.rstrip("\n")

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Tabulate hipcc's -Rpass-analysis=kernel-resource-usage remarks: one row per kernel.
 
-  hipcc ... -Rpass-analysis=kernel-resource-usage -c pcv_query.hip -o /dev/null 2> report.txt
+  hipcc ... -Rpass-analysis=kernel-resource-usage -c pcv_cull.hip -o /dev/null 2> report.txt
   tools/kernel_resources.py report.txt [other_report.txt]     # with two reports: the rows that differ are marked
 
 Runs without a GPU (the report comes from the compiler)."""
