@@ -22,7 +22,9 @@
 extern "C" {
 #endif
 
-/* 2 (round 6): pcv_ingest_*, PCV_ROUTE_OCTANTS_ONLY, PCV_STAGE_SORT_SECOND (PCV_STAGE_TOTAL moved from 8 to 9) */
+/* additions that leave every existing entry as it was (pcv_png_decode, pcv_xray_open_dir, pcv_xray_merge, ...) do not
+ * move the version.
+ * 2 (round 6): pcv_ingest_*, PCV_ROUTE_OCTANTS_ONLY, PCV_STAGE_SORT_SECOND (PCV_STAGE_TOTAL moved from 8 to 9) */
 #define PCV_ABI_VERSION 2
 
 /* status codes (reference: error-chain kinds src/errors.rs:18-48; the builder itself panics) */
@@ -849,6 +851,71 @@ int pcv_xray_lanczos_taps(uint32_t tile_size_px, uint32_t* left, uint32_t* count
  * 0 on every row, zlib with stored deflate blocks. *needed = the file size; it is written when out != NULL and
  * capacity >= *needed. w or h == 0 is PCV_E_INVALID. */
 int pcv_xray_png_encode(const uint8_t* rgba, uint32_t w, uint32_t h, uint8_t* out, uint64_t capacity, uint64_t* needed);
+
+/* ---- reading a quadtree directory back, and merge_xray_quadtrees (xray/src/bin/merge_xray_quadtrees.rs) ----------------
+ * Host only, no context: one PNG file as RGBA8, rows top to bottom, for the tiles the reference's png encoder or
+ * pcv_xray_png_encode wrote (what image::open does for build_node, xray/src/generation.rs:742-750). Read: the signature,
+ * every chunk CRC, IHDR colour type 6 at depth 8, not interlaced, any number of IDAT chunks, ancillary chunks skipped; the
+ * zlib header, stored, fixed-Huffman and dynamic-Huffman deflate blocks (an inflate of the library's own: zlib is not
+ * linked), the Adler-32; the row filters None, Sub, Up, Average and Paeth. *w and *h (each nullable) are set once the header
+ * is accepted; with rgba == NULL nothing else happens. Another colour type, depth or interlacing, and capacity below
+ * 4 * w * h, are PCV_E_INVALID; anything truncated or corrupt (a bad CRC or Adler-32, an invalid Huffman code, a distance
+ * before the start of the output, more or fewer than h * (1 + 4 w) scanline bytes) is PCV_E_IO. The input is never read
+ * past len, rgba is written only by a successful call and never past capacity. The message of a failure is
+ * pcv_host_last_error's. */
+int pcv_png_decode(const uint8_t* file, uint64_t len, uint32_t* w, uint32_t* h, uint8_t* rgba, uint64_t capacity);
+/* The message of the calling thread's last failed call that had no context to keep it: pcv_png_decode, and the pcv_xray_*
+ * calls on handles that pcv_xray_open_dir made without a context. */
+const char* pcv_host_last_error(void);
+/* Every meta*.pb of `directory` (read_metadata_from_directory :54-61) as one "opened" pcv_xray each, in ascending file
+ * name order (the reference takes them in directory-walk order, which is not defined). xray_proto's Meta is parsed as
+ * Meta::from_proto does (xray/src/lib.rs:81-116): version 3; version 2 with the deprecated f32 min / edge_length where
+ * Rect.min is absent; any other version, and bytes that are no Meta, are PCV_E_INVALID (the reference panics on the
+ * version). *num_parts is the number of meta files; handles are made only when capacity >= *num_parts. A directory that
+ * cannot be read is PCV_E_IO.
+ * An opened handle serves pcv_xray_info (rect: the file's bounding_rect, that of its root node; num_leaves and num_created:
+ * the nodes at deepest_level), pcv_xray_tile_size, pcv_xray_nodes (descending level, then ascending index: a file keeps no
+ * order, the reference holds a hash set) and pcv_xray_node_images, which decodes "<NodeId>.png" on demand: a missing or
+ * undecodable file is PCV_E_IO, an image that is not tile_size x tile_size PCV_E_INVALID. pcv_xray_tiles, _images,
+ * _negative and _build_parents on it are PCV_E_INVALID, and pcv_xray_write_dir too (merge it: a lone part merges to itself
+ * plus the levels above its root).
+ * ctx may be NULL: the handles are then host only (PCV_MEM_HOST images), can be passed to pcv_xray_merge_check and to a
+ * pcv_xray_merge of any context, and report failures through pcv_host_last_error. */
+int pcv_xray_open_dir(pcv_ctx* ctx, const char* directory, uint32_t capacity, pcv_xray** parts, uint32_t* num_parts);
+/* Meta.tile_size of any quadtree handle; 0 for NULL. */
+uint32_t pcv_xray_tile_size(const pcv_xray* x);
+/* Host only, no context: validate_and_merge_metadata (:129-186) over `parts` in argument order. PCV_E_INVALID with the
+ * reference's message in err for: num_parts == 0 ("No subquadtrees meta files found."); every part without nodes ("All
+ * subquadtress are empty."); two parts with the same root ("Not all roots are unique."); roots of different levels ("Not
+ * all roots have the same level."); different deepest_level or tile_size, empty parts included ("Not all meta files have
+ * the same deepest level." / "... the same tile size."). A part's root is its node of minimum level
+ * (Meta::get_root_node, xray/src/lib.rs:139-147); a part that holds several nodes at that level is PCV_E_INVALID here (the
+ * reference takes whichever its hash set yields first). Also PCV_E_INVALID: a null or freed part, a device-built part
+ * whose parents are not built, a root level above deepest_level.
+ * *root_level = the roots' level L. rect = the merged bounding rect: the rect of the first non-empty part's root node
+ * (an opened part: the file's; a built part: what pcv_xray_write_dir writes) under Node::parent (quadtree/src/lib.rs:100-120)
+ * L times, each step min.y -= edge when child_index & 1, min.x -= edge when child_index & 2, then edge *= 2, in f64 and in
+ * that order. */
+int pcv_xray_merge_check(pcv_xray* const* parts, uint32_t num_parts, uint32_t* root_level, double rect[3], char* err,
+                         uint64_t errcap);
+/* merge (:188-205): the quadtree with root r over parts that passed pcv_xray_merge_check, device-built (pcv_xray_run*,
+ * parents built) and opened ones mixed; a part of another context is PCV_E_INVALID. The levels L - 1 .. 0 above the roots
+ * are create_non_leaf_nodes(roots, L, 0) (generation.rs:656-682): per level the parents of the level below in ascending
+ * index, each build_parent of its four children and the Lanczos3 2:1 resize of pcv_xray_build_parents, on the device. A
+ * child that is in no part is `background` (PCV_XRAY_BG_*): the reference asks whether the child's file exists in the
+ * output directory (:742), which in a directory that holds only the merged trees is membership in the node set. The parts'
+ * own images are never re-backgrounded. The root tiles are staged into one level array on the context's stream (device to
+ * device from built parts, one pinned upload for opened ones), every new image is allocated before any launch
+ * (PCV_E_OOM leaves nothing allocated), and L == 0 builds nothing.
+ * The result serves pcv_xray_info (rect: the merged rect; leaves: the nodes at deepest_level), pcv_xray_nodes (every part's
+ * nodes in part order, each in its own order, then the new levels L - 1 .. 0 in ascending index; unique roots at one level
+ * make the parts disjoint), pcv_xray_node_images (a part's node is forwarded to the part) and pcv_xray_write_dir: the PNG
+ * of an opened part's node is copied byte for byte from the part's directory (copy_images :28-46; not when that is the
+ * output directory), the others are encoded by pcv_xray_png_encode, and meta.pb holds the merged rect, deepest_level,
+ * tile_size and the union node list; other meta*.pb files of an in-place merge stay, as in the reference. It owns the new
+ * images only: the parts must outlive it, and once one of them is freed the image calls and pcv_xray_write_dir return
+ * PCV_E_INVALID. pcv_xray_tiles, _images, _negative and _build_parents on it are PCV_E_INVALID. */
+int pcv_xray_merge(pcv_ctx* ctx, pcv_xray* const* parts, uint32_t num_parts, uint32_t background, pcv_xray** out);
 
 /* ---- the viewer's frame (sdl_viewer/src/lib.rs:158-209, node_drawer.rs:124-160, shaders/points.vs, points.fs) ----------
  * V cameras over one octree in one call, rasterised on the device into RGBA8 images that stay there. OpenGL leaves sub-pixel

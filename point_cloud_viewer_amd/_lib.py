@@ -275,6 +275,12 @@ _SIGNATURES = {
     "pcv_xray_write_dir": (C.c_int, [_vp, C.c_char_p]),
     "pcv_xray_lanczos_taps": (C.c_int, [C.c_uint32, _vp, _vp, _vp]),
     "pcv_xray_png_encode": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "pcv_png_decode": (C.c_int, [_vp, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _vp, C.c_uint64]),
+    "pcv_host_last_error": (C.c_char_p, []),
+    "pcv_xray_open_dir": (C.c_int, [_vp, C.c_char_p, C.c_uint32, C.POINTER(_vp), C.POINTER(C.c_uint32)]),
+    "pcv_xray_tile_size": (C.c_uint32, [_vp]),
+    "pcv_xray_merge_check": (C.c_int, [C.POINTER(_vp), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.c_char_p, C.c_uint64]),
+    "pcv_xray_merge": (C.c_int, [_vp, C.POINTER(_vp), C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
     "pcv_render_check_params": (C.c_int, [C.POINTER(RenderParams)]),
     "pcv_render_gamma_lut": (C.c_int, [C.c_float, _vp]),
     "pcv_render_views": (C.c_int, [_vp, _vp, _vp, C.POINTER(RenderParams), C.POINTER(_vp)]),

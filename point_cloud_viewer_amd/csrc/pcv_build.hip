@@ -271,7 +271,8 @@ static const char* kKernelNames[PCV_K_COUNT] = {
     "hist_from_rows_kernel", "cull_nodes_sparse_kernel", "downsweep_settle_kernel", "ingest_batch_kernel",
     "batch_nodes_kernel", "batch_chunks_kernel", "batch_flags_kernel", "batch_scan_kernel", "batch_compact_kernel",
     "xray_bin_kernel", "xray_scatter_kernel", "xray_accum_kernel", "xray_parent_kernel",
-    "xray_sorted_kernel", "render_chunks_kernel", "render_splat_kernel", "render_resolve_kernel"};
+    "xray_sorted_kernel", "render_chunks_kernel", "render_splat_kernel", "render_resolve_kernel",
+    "xray_merge_stage_copy", "xray_merge_parent_kernel"};
 static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == PCV_K_COUNT, "kernel name table out of sync");
 
 extern "C" int pcv_ctx_set_profiling(pcv_ctx* ctx, int enabled) {

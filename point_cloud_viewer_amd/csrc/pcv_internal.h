@@ -125,6 +125,8 @@ enum PcvKernelId {
   PCV_K_RENDER_CHUNKS,        // pcv_render_views: one chunk descriptor per chunk of every (view, drawn node)
   PCV_K_RENDER_SPLAT,         // pcv_render_views: shader decode, clip, window, atomicMin of depth | rank per covered pixel
   PCV_K_RENDER_RESOLVE,       // pcv_render_views: key -> point -> gamma table -> RGBA8, depth plane, covered pixels
+  PCV_K_XRAY_MERGE_STAGE,     // pcv_xray_merge: the parts' root tiles copied into one level array (device copies and one upload)
+  PCV_K_XRAY_MERGE_PARENT,    // pcv_xray_merge: xray_parent_kernel over the levels above the parts' roots
   PCV_K_COUNT
 };
 
@@ -583,3 +585,6 @@ int pcv_bytes_per_coordinate(uint32_t enc);
 // host helpers (pcv_build.hip)
 int pcv_make_levels(const double bmin[3], const double bmax[3], double resolution, int cap, PcvLevels* lv,
                     int* max_level, std::vector<double>* edges, std::vector<int32_t>* encs);
+
+// A failure of a call that has no context to keep the message (pcv_png.cpp): kept per thread for pcv_host_last_error.
+int pcv_host_fail(int code, const std::string& msg);

@@ -27,7 +27,9 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "pcv_query_dev.h"
@@ -772,8 +774,40 @@ void tile_obb(const double* iso, const double mn[3], const double mx[3], double 
 
 }  // namespace
 
+// Every live pcv_xray by address with a serial number of its own: a merged quadtree refers to its parts, and asks here
+// whether a part is still the object it was given before it touches it (pcv_xray_merge)
+namespace {
+std::mutex g_xray_mu;
+std::unordered_map<const pcv_xray*, uint64_t> g_xray_live;
+uint64_t g_xray_serial = 0;
+}  // namespace
+
+enum XrayKind : uint32_t { kXrayBuilt = 0, kXrayOpened = 1, kXrayMerged = 2 };
+
+struct XrayPartRef {  // one part of a merged quadtree: its nodes are [first, first + count) of the merged node list
+  pcv_xray* part;
+  uint64_t serial, first, count;
+};
+
 struct pcv_xray {
-  pcv_ctx* ctx = nullptr;
+  pcv_xray() {
+    std::lock_guard<std::mutex> g(g_xray_mu);
+    g_xray_live[this] = serial = ++g_xray_serial;
+  }
+  ~pcv_xray() {
+    std::lock_guard<std::mutex> g(g_xray_mu);
+    g_xray_live.erase(this);
+  }
+  uint64_t serial = 0;
+  XrayKind kind = kXrayBuilt;
+  // opened (pcv_xray_open_dir) and merged (pcv_xray_merge) quadtrees: the node list itself; of `geo` only deepest_level
+  // and rect are set (the meta's bounding rect), geo.index / created list the nodes at deepest_level
+  std::vector<uint32_t> node_level;
+  std::vector<uint64_t> node_index;
+  uint64_t root_count = 0;   // nodes at the minimum level (a merge needs exactly one, or no node at all)
+  std::string dir;           // opened: the directory the PNGs are read from
+  std::vector<XrayPartRef> parts;  // merged; the new levels follow the parts' nodes and live in d_parents
+  pcv_ctx* ctx = nullptr;    // null: opened without a context (host only)
   uint32_t W = 0;
   LeafGeometry geo;
   uint32_t root_level = 0;
@@ -849,9 +883,19 @@ extern "C" int pcv_xray_finalize(int fn, uint64_t count, const double* in, uint8
 
 extern "C" void pcv_xray_free(pcv_xray* x) {
   if (!x) return;
-  x->ctx->dev_free(x->d_images);
-  x->ctx->dev_free(x->d_parents);
+  if (x->ctx) {
+    x->ctx->dev_free(x->d_images);
+    x->ctx->dev_free(x->d_parents);
+  }
   delete x;
+}
+
+// a failure on a handle that may have no context (opened host only): the message goes where the caller can read it
+static int xray_fail(const pcv_xray* x, int code, const std::string& msg) {
+  return x->ctx ? x->ctx->fail(code, msg) : pcv_host_fail(code, msg);
+}
+static int xray_not_built(const pcv_xray* x, const char* what) {
+  return xray_fail(x, PCV_E_INVALID, std::string("xray: ") + what + " needs a quadtree built by pcv_xray_run, not an opened or merged one");
 }
 
 // PointCloudClientBuilder::build's bounding box (point_cloud_client/src/lib.rs:101-125): the first octree's meta box, grown
@@ -1303,6 +1347,7 @@ extern "C" int pcv_xray_run_ex(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t 
 
 extern "C" int pcv_xray_negative(const pcv_xray* x, uint64_t* negative) {
   if (!x) return PCV_E_INVALID;
+  if (x->kind != kXrayBuilt) return xray_not_built(x, "pcv_xray_negative");
   if (negative) std::memcpy(negative, x->negative.data(), 8 * x->negative.size());
   return PCV_OK;
 }
@@ -1318,6 +1363,7 @@ extern "C" int pcv_xray_info(const pcv_xray* x, uint32_t* deepest_level, double 
 
 extern "C" int pcv_xray_tiles(const pcv_xray* x, uint64_t* leaf_index, uint64_t* created, uint64_t* kept, uint64_t* drawn) {
   if (!x) return PCV_E_INVALID;
+  if (x->kind != kXrayBuilt) return xray_not_built(x, "pcv_xray_tiles");
   if (leaf_index) std::memcpy(leaf_index, x->geo.index.data(), 8 * x->geo.index.size());
   if (created) std::memcpy(created, x->created.data(), 8 * x->created.size());
   if (kept) std::memcpy(kept, x->kept.data(), 8 * x->kept.size());
@@ -1327,6 +1373,7 @@ extern "C" int pcv_xray_tiles(const pcv_xray* x, uint64_t* leaf_index, uint64_t*
 
 extern "C" int pcv_xray_images(pcv_xray* x, uint64_t first, uint64_t count, uint64_t capacity, int mem, uint8_t* rgba) {
   if (!x) return PCV_E_INVALID;
+  if (x->kind != kXrayBuilt) return xray_not_built(x, "pcv_xray_images");
   pcv_ctx* ctx = x->ctx;
   const uint64_t nc = x->created.size();
   if (first > nc || count > nc - first) return ctx->fail(PCV_E_INVALID, "xray: tile range past the end");
@@ -1678,16 +1725,25 @@ extern "C" int pcv_xray_png_encode(const uint8_t* rgba, uint32_t w, uint32_t h, 
   return PCV_OK;
 }
 
-static int xray_build_parents(pcv_xray* x) {
-  pcv_ctx* ctx = x->ctx;
-  const uint32_t deepest = x->geo.deepest_level, W = x->W;
-  const uint64_t nc = x->created.size();
+// The levels above a set of nodes: the node list after them (plevel, pindex; first[k] = the first parent of level
+// from - 1 - k in it) and their images on the device
+struct XrayLevels {
   std::vector<uint32_t> plevel;
   std::vector<uint64_t> pindex, first;
-  // create_non_leaf_nodes: the parent ids of the level below, root_level ..= deepest - 1 (ascending index per level)
-  std::vector<uint64_t> below(nc);
-  for (uint64_t c = 0; c < nc; ++c) below[c] = x->geo.index[x->created[c]];
-  for (uint32_t level = deepest; nc && level > x->root_level; --level) {
+  uint32_t* d_parents = nullptr;
+};
+
+// create_non_leaf_nodes(base, from, to) for the nodes `base` of level `from` (node positions 0 .. base.size() - 1, their
+// images at d_base), one xray_parent_kernel launch per level under the kernel-stat id `prof_id`: the parent levels of a
+// built quadtree (base = the created leaves) and the upper levels of a merged one (base = the parts' roots)
+static int xray_build_levels(pcv_ctx* ctx, uint32_t W, uint32_t bg, const std::vector<uint64_t>& base, uint32_t from, uint32_t to,
+                             const uint32_t* d_base, int prof_id, XrayLevels* out) {
+  const uint64_t nc = base.size();
+  std::vector<uint32_t> plevel;
+  std::vector<uint64_t> pindex, first;
+  // create_non_leaf_nodes: the parent ids of the level below, to ..= from - 1 (ascending index per level)
+  std::vector<uint64_t> below(base);
+  for (uint32_t level = from; nc && level > to; --level) {
     std::vector<uint64_t> up(below.size());
     for (size_t i = 0; i < below.size(); ++i) up[i] = below[i] >> 2;
     std::sort(up.begin(), up.end());
@@ -1704,7 +1760,7 @@ static int xray_build_parents(pcv_xray* x) {
   if (np == 0) return PCV_OK;
   // child slots: node positions of (index << 2) + c one level down, -1 where that child was not created
   std::vector<std::pair<uint64_t, uint64_t>> leaf_pos(nc);  // (leaf index, node position)
-  for (uint64_t c = 0; c < nc; ++c) leaf_pos[c] = {x->geo.index[x->created[c]], c};
+  for (uint64_t c = 0; c < nc; ++c) leaf_pos[c] = {base[c], c};
   std::sort(leaf_pos.begin(), leaf_pos.end());
   std::vector<int64_t> slots(4 * np, -1);
   for (size_t k = 0; k + 1 < first.size(); ++k) {
@@ -1742,13 +1798,13 @@ static int xray_build_parents(pcv_xray* x) {
   PCV_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xray_parent_kernel, 256, 0));
   const uint64_t resident = (uint64_t)std::max(cus, 1) * (uint64_t)std::max(per_cu, 1);
   XrayParentArgs a{};
-  a.leaves = x->d_images;
+  a.leaves = d_base;
   a.parents = d_parents;
   a.nleaves = nc;
   a.taps = d_taps;
   a.W = W;
   a.nbx = (W + kBlk - 1) / kBlk;
-  a.bg = x->bg;
+  a.bg = bg;
   for (size_t k = 0; k + 1 < first.size(); ++k) {  // a level reads the one below: one launch each, in order
     a.slots = d_slots + 4 * first[k];
     a.out = d_parents + first[k] * W * W;
@@ -1756,7 +1812,7 @@ static int xray_build_parents(pcv_xray* x) {
     const uint64_t work = a.nparents * a.nbx * a.nbx;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(work, 4 * resident);
     {
-      PcvProf prof(ctx, PCV_K_XRAY_PARENT);
+      PcvProf prof(ctx, prof_id);
       hipLaunchKernelGGL(xray_parent_kernel, dim3(grid), dim3(256), 0, ctx->stream, a);
     }
     hipError_t e = hipGetLastError();
@@ -1770,15 +1826,30 @@ static int xray_build_parents(pcv_xray* x) {
     ctx->dev_free(d_parents);
     return ctx->fail(PCV_E_HIP, "xray: parent levels failed");
   }
-  x->d_parents = d_parents;
-  x->parent_level.swap(plevel);
-  x->parent_index.swap(pindex);
-  x->level_first.swap(first);
+  out->d_parents = d_parents;
+  out->plevel.swap(plevel);
+  out->pindex.swap(pindex);
+  out->first.swap(first);
+  return PCV_OK;
+}
+
+static int xray_build_parents(pcv_xray* x) {
+  const uint64_t nc = x->created.size();
+  std::vector<uint64_t> leaves(nc);
+  for (uint64_t c = 0; c < nc; ++c) leaves[c] = x->geo.index[x->created[c]];
+  XrayLevels lv;
+  const int rc = xray_build_levels(x->ctx, x->W, x->bg, leaves, x->geo.deepest_level, x->root_level, x->d_images, PCV_K_XRAY_PARENT, &lv);
+  if (rc) return rc;
+  x->d_parents = lv.d_parents;
+  x->parent_level.swap(lv.plevel);
+  x->parent_index.swap(lv.pindex);
+  x->level_first.swap(lv.first);
   return PCV_OK;
 }
 
 extern "C" int pcv_xray_build_parents(pcv_xray* x) {
   if (!x) return PCV_E_INVALID;
+  if (x->kind != kXrayBuilt) return xray_not_built(x, "pcv_xray_build_parents");
   if (x->parents_built) return PCV_OK;
   const int rc = xray_build_parents(x);
   if (rc) return rc;
@@ -1789,16 +1860,19 @@ extern "C" int pcv_xray_build_parents(pcv_xray* x) {
 
 extern "C" int pcv_xray_nodes(const pcv_xray* x, uint64_t* num_nodes, uint64_t capacity, uint32_t* level, uint64_t* index) {
   if (!x) return PCV_E_INVALID;
-  const uint64_t nc = x->created.size(), n = nc + x->parent_index.size();
+  const bool listed = x->kind != kXrayBuilt;
+  const uint64_t nc = x->created.size(), n = listed ? x->node_index.size() : nc + x->parent_index.size();
   if (num_nodes) *num_nodes = n;
   for (uint64_t i = 0; i < std::min(n, capacity); ++i) {
-    if (level) level[i] = i < nc ? x->geo.deepest_level : x->parent_level[i - nc];
-    if (index) index[i] = i < nc ? x->geo.index[x->created[i]] : x->parent_index[i - nc];
+    if (level) level[i] = listed ? x->node_level[i] : (i < nc ? x->geo.deepest_level : x->parent_level[i - nc]);
+    if (index) index[i] = listed ? x->node_index[i] : (i < nc ? x->geo.index[x->created[i]] : x->parent_index[i - nc]);
   }
   return PCV_OK;
 }
 
-// node images [first, first + count) of the node list into dst (host or device), no synchronisation
+extern "C" uint32_t pcv_xray_tile_size(const pcv_xray* x) { return x ? x->W : 0; }
+
+// node images [first, first + count) of a built quadtree's node list into dst (host or device), no synchronisation
 static int queue_node_images(pcv_xray* x, uint64_t first, uint64_t count, uint8_t* dst, hipMemcpyKind kind) {
   pcv_ctx* ctx = x->ctx;
   const uint64_t nc = x->created.size(), tile_bytes = 4ull * x->W * x->W;
@@ -1811,27 +1885,621 @@ static int queue_node_images(pcv_xray* x, uint64_t first, uint64_t count, uint8_
   return PCV_OK;
 }
 
+static bool read_file(const std::string& path, std::vector<uint8_t>& data) {
+  FILE* f = std::fopen(path.c_str(), "rb");
+  if (!f) return false;
+  data.clear();
+  uint8_t buf[1 << 16];
+  size_t k;
+  while ((k = std::fread(buf, 1, sizeof(buf), f)) > 0) data.insert(data.end(), buf, buf + k);
+  const bool ok = !std::ferror(f);
+  std::fclose(f);
+  return ok;
+}
+
+// node `node` of an opened quadtree, decoded from its file into W x W x 4 host bytes
+static int opened_node_to_host(const pcv_xray* x, uint64_t node, uint8_t* dst) {
+  const std::string path = x->dir + "/" + quad_name(x->node_level[node], x->node_index[node]) + ".png";
+  std::vector<uint8_t> file;
+  if (!read_file(path, file)) return xray_fail(x, PCV_E_IO, "xray: cannot read " + path);
+  uint32_t w = 0, h = 0;
+  int rc = pcv_png_decode(file.data(), file.size(), &w, &h, nullptr, 0);
+  if (rc) return xray_fail(x, rc == PCV_E_INVALID ? PCV_E_IO : rc, path + ": " + pcv_host_last_error());
+  if (w != x->W || h != x->W)
+    return xray_fail(x, PCV_E_INVALID, path + " is " + std::to_string(w) + " x " + std::to_string(h) + ", the meta's tile_size is " + std::to_string(x->W));
+  rc = pcv_png_decode(file.data(), file.size(), &w, &h, dst, 4ull * x->W * x->W);
+  if (rc) return xray_fail(x, PCV_E_IO, path + ": " + pcv_host_last_error());
+  return PCV_OK;
+}
+
+static bool xray_part_alive(const XrayPartRef& r) {
+  std::lock_guard<std::mutex> g(g_xray_mu);
+  auto it = g_xray_live.find(r.part);
+  return it != g_xray_live.end() && it->second == r.serial;
+}
+
+// node images of any kind of quadtree into checked arguments; returns after the copies have completed
+static int xray_node_images(pcv_xray* x, uint64_t first, uint64_t count, int mem, uint8_t* rgba) {
+  pcv_ctx* ctx = x->ctx;
+  const uint64_t tile_bytes = 4ull * x->W * x->W;
+  if (mem == PCV_MEM_DEVICE && !ctx) return xray_fail(x, PCV_E_INVALID, "xray: a quadtree opened without a context has host images only");
+  if (ctx) PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (x->kind == kXrayBuilt) {
+    const int rc = queue_node_images(x, first, count, rgba, mem == PCV_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice);
+    if (rc) return rc;
+    PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return PCV_OK;
+  }
+  if (x->kind == kXrayOpened) {
+    if (mem == PCV_MEM_HOST) {
+      for (uint64_t i = 0; i < count; ++i)
+        if (int rc = opened_node_to_host(x, first + i, rgba + i * tile_bytes)) return rc;
+      return PCV_OK;
+    }
+    uint8_t* host = nullptr;  // decoded into pinned memory, one upload
+    int rc = ctx->host_alloc((void**)&host, count * tile_bytes);
+    if (rc) return rc;
+    for (uint64_t i = 0; !rc && i < count; ++i) rc = opened_node_to_host(x, first + i, host + i * tile_bytes);
+    if (!rc) {
+      hipError_t e = hipMemcpyAsync(rgba, host, count * tile_bytes, hipMemcpyHostToDevice, ctx->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+      if (e != hipSuccess) rc = ctx->fail(PCV_E_HIP, std::string("xray: image upload: ") + hipGetErrorString(e));
+    }
+    ctx->host_release(host);
+    return rc;
+  }
+  // merged: runs of nodes that belong to one part go to that part; the new levels are this object's own
+  for (const XrayPartRef& r : x->parts)
+    if (!xray_part_alive(r)) return ctx->fail(PCV_E_INVALID, "xray: a part of this merged quadtree was freed before it");
+  const uint64_t own_first = x->node_index.size() - x->parent_index.size();
+  uint64_t at = first;
+  const uint64_t end = first + count;
+  for (const XrayPartRef& r : x->parts) {
+    if (at >= end) break;
+    if (at >= r.first + r.count || r.count == 0) continue;
+    const uint64_t k = std::min(end, r.first + r.count) - at;
+    const int rc = xray_node_images(r.part, at - r.first, k, mem, rgba + (at - first) * tile_bytes);
+    if (rc) return r.part->ctx ? rc : ctx->fail(rc, pcv_host_last_error());
+    at += k;
+  }
+  if (at < end) {
+    PCV_HIP_CHECK(ctx, hipMemcpyAsync(rgba + (at - first) * tile_bytes, reinterpret_cast<const uint8_t*>(x->d_parents) + (at - own_first) * tile_bytes,
+                                      (end - at) * tile_bytes, mem == PCV_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                                      ctx->stream));
+    PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return PCV_OK;
+}
+
 extern "C" int pcv_xray_node_images(pcv_xray* x, uint64_t first, uint64_t count, uint64_t capacity, int mem, uint8_t* rgba) {
   if (!x) return PCV_E_INVALID;
-  pcv_ctx* ctx = x->ctx;
-  const uint64_t n = x->created.size() + x->parent_index.size();
-  if (first > n || count > n - first) return ctx->fail(PCV_E_INVALID, "xray: node range past the end");
-  if (mem != PCV_MEM_HOST && mem != PCV_MEM_DEVICE) return ctx->fail(PCV_E_INVALID, "bad mem");
+  uint64_t n = 0;
+  pcv_xray_nodes(x, &n, 0, nullptr, nullptr);
+  if (first > n || count > n - first) return xray_fail(x, PCV_E_INVALID, "xray: node range past the end");
+  if (mem != PCV_MEM_HOST && mem != PCV_MEM_DEVICE) return xray_fail(x, PCV_E_INVALID, "bad mem");
   const uint64_t tile_bytes = 4ull * x->W * x->W;
-  if (count * tile_bytes > capacity) return ctx->fail(PCV_E_INVALID, "xray: capacity below count x W x W x 4 bytes");
+  if (count * tile_bytes > capacity) return xray_fail(x, PCV_E_INVALID, "xray: capacity below count x W x W x 4 bytes");
   if (count == 0) return PCV_OK;
-  if (!rgba) return ctx->fail(PCV_E_INVALID, "null output");
-  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  int rc = queue_node_images(x, first, count, rgba, mem == PCV_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice);
-  if (rc) return rc;
-  PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  if (!rgba) return xray_fail(x, PCV_E_INVALID, "null output");
+  return xray_node_images(x, first, count, mem, rgba);
+}
+
+// root_node.bounding_rect of a built quadtree: Node::from_node_id_and_root_bounding_rect(root_node_id, rect), what its
+// meta file holds
+static void built_root_rect(const pcv_xray* x, double rect[3]) {
+  std::memcpy(rect, x->geo.rect, sizeof(x->geo.rect));
+  for (int l = (int)x->root_level - 1; l >= 0; --l) {
+    const uint32_t ci = (uint32_t)(x->root_index >> (2 * l)) & 3u;
+    const double half = rect[2] / 2.0;
+    if (ci & 1u) rect[1] += half;
+    if (ci & 2u) rect[0] += half;
+    rect[2] = half;
+  }
+}
+
+// Meta (xray_proto Meta, CURRENT_VERSION 3) to get_meta_pb_path: the root id with "r" -> "meta", + ".pb"
+static bool write_meta_file(int dirfd, const std::string& dir, uint32_t root_level, uint64_t root_index, const double rect[3],
+                            uint32_t deepest_level, uint32_t W, const std::vector<uint32_t>& level, const std::vector<uint64_t>& index,
+                            std::string* err) {
+  std::vector<uint8_t> meta, r, mn;
+  pb_uint(meta, 1, 3);
+  pb_double(mn, 1, rect[0]);
+  pb_double(mn, 2, rect[1]);
+  pb_bytes(r, 3, mn);
+  pb_double(r, 4, rect[2]);
+  pb_bytes(meta, 2, r);
+  pb_uint(meta, 3, deepest_level);
+  pb_uint(meta, 4, W);
+  for (size_t i = 0; i < index.size(); ++i) {
+    std::vector<uint8_t> id;
+    pb_uint(id, 1, level[i]);
+    pb_uint(id, 2, index[i]);
+    pb_bytes(meta, 5, id);
+  }
+  const std::string name = "meta" + quad_name(root_level, root_index).substr(1) + ".pb";
+  if (write_at(dirfd, name, meta.data(), meta.size())) return true;
+  *err = "cannot write " + dir + "/" + name;
+  return false;
+}
+
+// ---- xray_proto Meta, read (Meta::from_proto, xray/src/lib.rs:81-116) --------------------------------------------------
+// proto3 wire format of xray_proto_rust/src/proto.proto: Meta { int32 version = 1; Rect bounding_rect = 2; uint32
+// deepest_level = 3; uint32 tile_size = 4; repeated NodeId nodes = 5 }, Rect { Vector2f deprecated_min = 1; float
+// deprecated_edge_length = 2; Vector2d min = 3; double edge_length = 4 }, NodeId { uint32 level = 1; uint64 index = 2 }.
+// Fields may come in any order, a repeated scalar field keeps its last value, unknown fields are skipped.
+namespace {
+
+struct PbReader {
+  const uint8_t* p;
+  size_t n, pos = 0;
+  bool bad = false;
+  bool more() const { return !bad && pos < n; }
+  uint64_t varint() {
+    uint64_t v = 0;
+    for (int shift = 0; shift < 64; shift += 7) {
+      if (pos >= n) break;
+      const uint8_t c = p[pos++];
+      v |= (uint64_t)(c & 0x7f) << shift;
+      if (c < 0x80) return v;
+    }
+    bad = true;
+    return 0;
+  }
+  // one field: its number, wire type and value (varint / fixed bits in `v`, a length-delimited body in `sub`)
+  bool field(uint32_t* num, uint32_t* wt, uint64_t* v, PbReader* sub) {
+    const uint64_t key = varint();
+    if (bad || (key >> 3) == 0 || (key >> 3) > 0x1fffffffu) return !(bad = true);
+    *num = (uint32_t)(key >> 3);
+    *wt = (uint32_t)(key & 7);
+    *v = 0;
+    if (*wt == 0) {
+      *v = varint();
+    } else if (*wt == 1 || *wt == 5) {
+      const size_t k = *wt == 1 ? 8 : 4;
+      if (n - pos < k) return !(bad = true);
+      std::memcpy(v, p + pos, k);  // little endian, as the wire
+      pos += k;
+    } else if (*wt == 2) {
+      const uint64_t k = varint();
+      if (bad || k > n - pos) return !(bad = true);
+      *sub = PbReader{p + pos, (size_t)k};
+      pos += (size_t)k;
+    } else {
+      return !(bad = true);  // groups: not in this schema
+    }
+    return !bad;
+  }
+};
+
+struct XrayMeta {
+  int32_t version = 0;
+  bool has_min = false;
+  double min[2] = {0, 0}, edge = 0;
+  float dmin[2] = {0, 0}, dedge = 0;
+  uint32_t deepest_level = 0, tile_size = 0;
+  std::vector<std::pair<uint32_t, uint64_t>> nodes;
+};
+
+double pb_f64(uint64_t v) {
+  double d;
+  std::memcpy(&d, &v, 8);
+  return d;
+}
+float pb_f32(uint64_t v) {
+  const uint32_t u = (uint32_t)v;
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
+
+bool parse_meta(const std::vector<uint8_t>& data, XrayMeta* m) {
+  PbReader top{data.data(), data.size()};
+  uint32_t f, wt;
+  uint64_t v;
+  PbReader sub{nullptr, 0};
+  while (top.more()) {
+    if (!top.field(&f, &wt, &v, &sub)) return false;
+    if (f == 1 && wt == 0) m->version = (int32_t)v;
+    if (f == 3 && wt == 0) m->deepest_level = (uint32_t)v;
+    if (f == 4 && wt == 0) m->tile_size = (uint32_t)v;
+    if ((f == 1 || f == 3 || f == 4) && wt != 0) return false;
+    if ((f == 2 || f == 5) && wt != 2) return false;
+    if (f == 2) {
+      PbReader rect = sub, vec{nullptr, 0};
+      while (rect.more()) {
+        uint32_t g, gw;
+        if (!rect.field(&g, &gw, &v, &vec)) return false;
+        if ((g == 1 || g == 3) && gw != 2) return false;
+        if ((g == 2 && gw != 5) || (g == 4 && gw != 1)) return false;
+        if (g == 2) m->dedge = pb_f32(v);
+        if (g == 4) m->edge = pb_f64(v);
+        if (g == 1 || g == 3) {
+          if (g == 3) m->has_min = true;
+          PbReader none{nullptr, 0};
+          while (vec.more()) {
+            uint32_t c, cw;
+            if (!vec.field(&c, &cw, &v, &none)) return false;
+            if ((c == 1 || c == 2) && cw != (g == 3 ? 1u : 5u)) return false;
+            if (c == 1 || c == 2) {
+              if (g == 3) m->min[c - 1] = pb_f64(v);
+              else m->dmin[c - 1] = pb_f32(v);
+            }
+          }
+          if (vec.bad) return false;
+        }
+      }
+      if (rect.bad) return false;
+    }
+    if (f == 5) {
+      PbReader id = sub, none{nullptr, 0};
+      uint32_t level = 0;
+      uint64_t index = 0;
+      while (id.more()) {
+        uint32_t g, gw;
+        if (!id.field(&g, &gw, &v, &none)) return false;
+        if ((g == 1 || g == 2) && gw != 0) return false;
+        if (g == 1) level = (uint32_t)v;
+        if (g == 2) index = v;
+      }
+      if (id.bad) return false;
+      m->nodes.emplace_back(level, index);
+    }
+  }
+  return !top.bad;
+}
+
+}  // namespace
+
+#include <dirent.h>
+
+extern "C" int pcv_xray_open_dir(pcv_ctx* ctx, const char* directory, uint32_t capacity, pcv_xray** parts, uint32_t* num_parts) {
+  auto fail = [&](int code, const std::string& m) { return ctx ? ctx->fail(code, m) : pcv_host_fail(code, m); };
+  if (!directory || !num_parts) return fail(PCV_E_INVALID, "null argument");
+  const std::string dir(directory);
+  DIR* d = opendir(dir.c_str());
+  if (!d) return fail(PCV_E_IO, "cannot open directory " + dir);
+  std::vector<std::string> names;  // "meta*.pb" (META_PREFIX, META_EXTENSION)
+  while (struct dirent* e = readdir(d)) {
+    const std::string name(e->d_name);
+    if (name.size() >= 7 && name.compare(0, 4, "meta") == 0 && name.compare(name.size() - 3, 3, ".pb") == 0) names.push_back(name);
+  }
+  closedir(d);
+  std::sort(names.begin(), names.end());
+  *num_parts = (uint32_t)names.size();
+  if (capacity < names.size() || names.empty()) return PCV_OK;
+  if (!parts) return fail(PCV_E_INVALID, "null argument");
+  std::vector<pcv_xray*> made;
+  auto undo = [&](int code, const std::string& m) {
+    for (pcv_xray* x : made) pcv_xray_free(x);
+    return fail(code, m);
+  };
+  for (const std::string& name : names) {
+    const std::string path = dir + "/" + name;
+    std::vector<uint8_t> data;
+    if (!read_file(path, data)) return undo(PCV_E_IO, "cannot read " + path);
+    XrayMeta m;
+    if (!parse_meta(data, &m)) return undo(PCV_E_INVALID, "Could not parse " + path);
+    if (m.version != 2 && m.version != 3)
+      return undo(PCV_E_INVALID, path + ": Invalid version. We only support 3, but found " + std::to_string(m.version) + ".");
+    if (m.tile_size == 0 || m.tile_size > kMaxTilePx) return undo(PCV_E_INVALID, path + ": tile_size outside 1 ..= 32768");
+    if (m.deepest_level > 31) return undo(PCV_E_INVALID, path + ": deepest_level above 31 (a u64 index holds 32 levels)");
+    for (const auto& nd : m.nodes)
+      if (nd.first > m.deepest_level || (nd.first < 32 && (nd.second >> (2 * nd.first)) != 0))
+        return undo(PCV_E_INVALID, path + ": a node outside the quadtree");
+    pcv_xray* x = new pcv_xray();
+    made.push_back(x);
+    x->ctx = ctx;
+    x->kind = kXrayOpened;
+    x->W = m.tile_size;
+    x->dir = dir;
+    x->geo.deepest_level = m.deepest_level;
+    // Meta::from_proto: Rect.min where present, else the deprecated f32 fields widened (version 2 files)
+    x->geo.rect[0] = m.has_min ? m.min[0] : (double)m.dmin[0];
+    x->geo.rect[1] = m.has_min ? m.min[1] : (double)m.dmin[1];
+    x->geo.rect[2] = m.has_min ? m.edge : (double)m.dedge;
+    // the node set in a stated order: descending level, then ascending index (duplicates of a file fold, as in a set)
+    std::sort(m.nodes.begin(), m.nodes.end(), [](const std::pair<uint32_t, uint64_t>& a, const std::pair<uint32_t, uint64_t>& b) {
+      return a.first != b.first ? a.first > b.first : a.second < b.second;
+    });
+    m.nodes.erase(std::unique(m.nodes.begin(), m.nodes.end()), m.nodes.end());
+    for (const auto& nd : m.nodes) {
+      x->node_level.push_back(nd.first);
+      x->node_index.push_back(nd.second);
+      if (nd.first == m.deepest_level) {
+        x->created.push_back(x->geo.index.size());
+        x->geo.index.push_back(nd.second);
+      }
+    }
+  }
+  for (size_t i = 0; i < made.size(); ++i) parts[i] = made[i];
   return PCV_OK;
+}
+
+// ---- merge_xray_quadtrees (xray/src/bin/merge_xray_quadtrees.rs:129-205) ---------------------------------------------
+namespace {
+
+struct MergePlan {
+  uint32_t L = 0, deepest = 0, W = 0;
+  double rect[3] = {0, 0, 0};
+  std::vector<int64_t> root_pos;    // per part: position of its root in its own node list, -1 for an empty part
+  std::vector<uint64_t> root_index;  // per part: index of its root at level L
+};
+
+int merge_plan(pcv_xray* const* parts, uint32_t num_parts, MergePlan* plan, std::string* err) {
+  auto bad = [&](const std::string& m) {
+    *err = m;
+    return PCV_E_INVALID;
+  };
+  if (num_parts == 0) return bad("No subquadtrees meta files found.");
+  if (!parts) return bad("xray merge: null argument");
+  struct Root {
+    uint32_t level;
+    uint64_t index;
+  };
+  std::vector<Root> roots;
+  int first_part = -1;
+  plan->root_pos.assign(num_parts, -1);
+  plan->root_index.assign(num_parts, 0);
+  for (uint32_t k = 0; k < num_parts; ++k) {
+    const pcv_xray* x = parts[k];
+    if (!x) return bad("xray merge: part " + std::to_string(k) + " is null");
+    {
+      std::lock_guard<std::mutex> g(g_xray_mu);
+      if (!g_xray_live.count(x)) return bad("xray merge: part " + std::to_string(k) + " is not a live pcv_xray");
+    }
+    if (x->kind == kXrayBuilt && !x->parents_built && !x->created.empty() && x->root_level < x->geo.deepest_level)
+      return bad("xray merge: the parent levels of part " + std::to_string(k) + " are not built (pcv_xray_build_parents)");
+    uint64_t n = 0;
+    pcv_xray_nodes(x, &n, 0, nullptr, nullptr);
+    std::vector<uint32_t> level(n);
+    std::vector<uint64_t> index(n);
+    pcv_xray_nodes(x, &n, n, level.data(), index.data());
+    if (n == 0) continue;  // get_root_nodes skips it; it still takes part in the deepest_level and tile_size checks
+    uint64_t at = 0, count = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+      if (level[i] < level[at]) at = i, count = 0;
+      if (level[i] == level[at]) ++count;
+    }
+    if (count != 1)
+      return bad("xray merge: part " + std::to_string(k) + " has " + std::to_string(count) + " nodes at its minimum level " +
+                 std::to_string(level[at]) + ": its root is not defined");
+    plan->root_pos[k] = (int64_t)at;
+    plan->root_index[k] = index[at];
+    roots.push_back(Root{level[at], index[at]});
+    if (first_part < 0) first_part = (int)k;
+  }
+  if (roots.empty()) return bad("All subquadtress are empty.");
+  for (size_t a = 0; a < roots.size(); ++a)
+    for (size_t b = a + 1; b < roots.size(); ++b)
+      if (roots[a].level == roots[b].level && roots[a].index == roots[b].index) return bad("Not all roots are unique.");
+  for (const Root& r : roots)
+    if (r.level != roots[0].level) return bad("Not all roots have the same level.");
+  for (uint32_t k = 1; k < num_parts; ++k)
+    if (parts[k]->geo.deepest_level != parts[0]->geo.deepest_level) return bad("Not all meta files have the same deepest level.");
+  for (uint32_t k = 1; k < num_parts; ++k)
+    if (parts[k]->W != parts[0]->W) return bad("Not all meta files have the same tile size.");
+  plan->L = roots[0].level;
+  plan->deepest = parts[0]->geo.deepest_level;
+  plan->W = parts[0]->W;
+  if (plan->L > plan->deepest) return bad("xray merge: the roots' level is above deepest_level");
+  // the first root's rect under Node::parent until level 0
+  const pcv_xray* x = parts[first_part];
+  if (x->kind == kXrayBuilt) built_root_rect(x, plan->rect);
+  else std::memcpy(plan->rect, x->geo.rect, sizeof(plan->rect));
+  uint64_t idx = roots[0].index;
+  for (uint32_t l = plan->L; l > 0; --l, idx >>= 2) {
+    const uint32_t ci = (uint32_t)idx & 3u;
+    if (ci & 1u) plan->rect[1] -= plan->rect[2];
+    if (ci & 2u) plan->rect[0] -= plan->rect[2];
+    plan->rect[2] *= 2.0;
+  }
+  return PCV_OK;
+}
+
+}  // namespace
+
+extern "C" int pcv_xray_merge_check(pcv_xray* const* parts, uint32_t num_parts, uint32_t* root_level, double rect[3], char* err,
+                                    uint64_t errcap) {
+  MergePlan plan;
+  std::string m;
+  const int rc = merge_plan(parts, num_parts, &plan, &m);
+  if (rc) return fail_msg(err, errcap, m);
+  if (root_level) *root_level = plan.L;
+  if (rect) std::memcpy(rect, plan.rect, sizeof(plan.rect));
+  return PCV_OK;
+}
+
+extern "C" int pcv_xray_merge(pcv_ctx* ctx, pcv_xray* const* parts, uint32_t num_parts, uint32_t background, pcv_xray** out) {
+  if (!ctx) return PCV_E_INVALID;
+  if (!out) return ctx->fail(PCV_E_INVALID, "null argument");
+  *out = nullptr;
+  if (background > PCV_XRAY_BG_TRANSPARENT) return ctx->fail(PCV_E_INVALID, "xray: unknown background");
+  MergePlan plan;
+  std::string m;
+  int rc = merge_plan(parts, num_parts, &plan, &m);
+  if (rc) return ctx->fail(rc, m);
+  for (uint32_t k = 0; k < num_parts; ++k)
+    if (parts[k]->ctx && parts[k]->ctx != ctx) return ctx->fail(PCV_E_INVALID, "xray merge: part " + std::to_string(k) + " belongs to another context");
+  const uint32_t W = plan.W;
+  const uint64_t tile_bytes = 4ull * W * W;
+  pcv_xray* x = new pcv_xray();
+  x->ctx = ctx;
+  x->kind = kXrayMerged;
+  x->W = W;
+  x->bg = background == PCV_XRAY_BG_TRANSPARENT ? 0x00ffffffu : 0xffffffffu;
+  x->geo.deepest_level = plan.deepest;
+  std::memcpy(x->geo.rect, plan.rect, sizeof(plan.rect));
+  for (uint32_t k = 0; k < num_parts; ++k) {
+    uint64_t n = 0;
+    pcv_xray_nodes(parts[k], &n, 0, nullptr, nullptr);
+    const uint64_t at = x->node_index.size();
+    x->parts.push_back(XrayPartRef{parts[k], parts[k]->serial, at, n});
+    x->node_level.resize(at + n);
+    x->node_index.resize(at + n);
+    pcv_xray_nodes(parts[k], &n, n, x->node_level.data() + at, x->node_index.data() + at);
+  }
+  // the level array of the roots: those of built parts first (device to device), then those of opened parts (decoded
+  // into one pinned block, one upload)
+  std::vector<uint32_t> order;
+  for (int opened = 0; opened < 2; ++opened)
+    for (uint32_t k = 0; k < num_parts; ++k)
+      if (plan.root_pos[k] >= 0 && (parts[k]->kind == kXrayOpened) == (opened == 1)) order.push_back(k);
+  uint64_t num_opened = 0;
+  std::vector<uint64_t> base;
+  for (uint32_t k : order) {
+    base.push_back(plan.root_index[k]);
+    num_opened += parts[k]->kind == kXrayOpened;
+  }
+  auto undo = [&](int code) {
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipGetLastError();
+    pcv_xray_free(x);
+    return code;
+  };
+  if (plan.L > 0) {
+    if (hipSetDevice(ctx->device) != hipSuccess) return undo(ctx->fail(PCV_E_HIP, "hipSetDevice"));
+    PcvScratch sc(ctx);
+    uint8_t* d_stage = nullptr;
+    uint8_t* host = nullptr;
+    if ((rc = sc.get(&d_stage, base.size() * tile_bytes)))
+      return undo(ctx->fail(PCV_E_OOM, "xray merge: no device memory for " + std::to_string(base.size()) + " root tiles"));
+    if (num_opened && (rc = ctx->host_alloc((void**)&host, num_opened * tile_bytes))) return undo(rc);
+    const uint64_t num_built = base.size() - num_opened;
+    for (uint64_t i = 0; !rc && i < num_opened; ++i) {
+      pcv_xray* part = parts[order[num_built + i]];
+      rc = opened_node_to_host(part, (uint64_t)plan.root_pos[order[num_built + i]], host + i * tile_bytes);
+      if (rc && !part->ctx) ctx->fail(rc, pcv_host_last_error());
+    }
+    if (!rc) {
+      PcvProf prof(ctx, PCV_K_XRAY_MERGE_STAGE);
+      for (uint64_t i = 0; !rc && i < num_built; ++i) {
+        pcv_xray* part = parts[order[i]];
+        if (part->kind == kXrayBuilt) {
+          rc = queue_node_images(part, (uint64_t)plan.root_pos[order[i]], 1, d_stage + i * tile_bytes, hipMemcpyDeviceToDevice);
+        } else {  // a merged part: through its own parts
+          rc = xray_node_images(part, (uint64_t)plan.root_pos[order[i]], 1, PCV_MEM_DEVICE, d_stage + i * tile_bytes);
+        }
+      }
+      if (!rc && num_opened &&
+          hipMemcpyAsync(d_stage + num_built * tile_bytes, host, num_opened * tile_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        rc = ctx->fail(PCV_E_HIP, "xray merge: root tile upload");
+    }
+    XrayLevels lv;
+    if (!rc)
+      rc = xray_build_levels(ctx, W, x->bg, base, plan.L, 0, reinterpret_cast<const uint32_t*>(d_stage), PCV_K_XRAY_MERGE_PARENT, &lv);
+    else
+      (void)hipStreamSynchronize(ctx->stream);
+    if (host) ctx->host_release(host);  // the upload has completed: xray_build_levels returns after a stream sync
+    if (rc) return undo(rc);
+    x->d_parents = lv.d_parents;
+    x->parent_level.swap(lv.plevel);
+    x->parent_index.swap(lv.pindex);
+    x->level_first.swap(lv.first);
+    x->node_level.insert(x->node_level.end(), x->parent_level.begin(), x->parent_level.end());
+    x->node_index.insert(x->node_index.end(), x->parent_index.begin(), x->parent_index.end());
+  }
+  x->parents_built = true;
+  for (size_t i = 0; i < x->node_index.size(); ++i)
+    if (x->node_level[i] == plan.deepest) {
+      x->created.push_back(x->geo.index.size());
+      x->geo.index.push_back(x->node_index[i]);
+    }
+  ctx->prof_resolve();
+  *out = x;
+  return PCV_OK;
+}
+
+static bool same_directory(const std::string& a, const std::string& b) {  // copy_images :29: canonicalize() of both
+  char* ra = realpath(a.c_str(), nullptr);
+  char* rb = realpath(b.c_str(), nullptr);
+  const bool same = ra && rb && std::strcmp(ra, rb) == 0;
+  std::free(ra);
+  std::free(rb);
+  return same;
+}
+
+// pcv_xray_write_dir of a merged quadtree
+static int xray_write_merged(pcv_xray* x, const char* directory) {
+  pcv_ctx* ctx = x->ctx;
+  for (const XrayPartRef& r : x->parts)
+    if (!xray_part_alive(r)) return ctx->fail(PCV_E_INVALID, "xray: a part of this merged quadtree was freed before it");
+  const std::string dir(directory);
+  ::mkdir(dir.c_str(), 0777);
+  struct stat st;
+  if (stat(dir.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) return ctx->fail(PCV_E_IO, "cannot create directory " + dir);
+  const int dirfd = open(dir.c_str(), O_RDONLY | O_DIRECTORY | O_CLOEXEC);
+  if (dirfd < 0) return ctx->fail(PCV_E_IO, "cannot open directory " + dir);
+  const uint32_t W = x->W;
+  const uint64_t tile_bytes = 4ull * W * W, n = x->node_index.size();
+  int rc = PCV_OK;
+  // copy_images: the files of opened parts, byte for byte; every other node is fetched and encoded
+  std::vector<uint64_t> encode;
+  std::vector<uint8_t> file;
+  for (const XrayPartRef& r : x->parts) {
+    const bool copy = r.part->kind == kXrayOpened;
+    const bool same = copy && same_directory(r.part->dir, dir);
+    for (uint64_t i = 0; !rc && i < r.count; ++i) {
+      if (!copy) {
+        encode.push_back(r.first + i);
+        continue;
+      }
+      if (same) continue;
+      const std::string name = quad_name(x->node_level[r.first + i], x->node_index[r.first + i]) + ".png";
+      if (!read_file(r.part->dir + "/" + name, file)) rc = ctx->fail(PCV_E_IO, "cannot read " + r.part->dir + "/" + name);
+      else if (!write_at(dirfd, name, file.data(), file.size())) rc = ctx->fail(PCV_E_IO, "cannot write " + dir + "/" + name);
+    }
+  }
+  for (uint64_t i = n - x->parent_index.size(); i < n; ++i) encode.push_back(i);
+  const uint64_t per_chunk = std::max<uint64_t>(1, (64ull << 20) / tile_bytes);
+  std::vector<uint8_t> images(std::min<uint64_t>(per_chunk, std::max<uint64_t>(encode.size(), 1)) * tile_bytes);
+  unsigned nthreads = std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
+  for (uint64_t f = 0; !rc && f < encode.size(); f += per_chunk) {
+    const uint64_t c = std::min<uint64_t>(per_chunk, encode.size() - f);
+    for (uint64_t i = 0; !rc && i < c;) {  // runs of consecutive nodes in one call
+      uint64_t k = 1;
+      while (i + k < c && encode[f + i + k] == encode[f + i] + k) ++k;
+      rc = xray_node_images(x, encode[f + i], k, PCV_MEM_HOST, images.data() + i * tile_bytes);
+      i += k;
+    }
+    if (rc) break;
+    std::atomic<uint64_t> next{0};
+    std::atomic<int> failed{0};
+    std::string first_error;
+    std::mutex err_mu;
+    auto worker = [&]() {
+      std::vector<uint8_t> png(png_size(W, W));
+      for (;;) {
+        const uint64_t i = next.fetch_add(1);
+        if (i >= c || failed.load()) return;
+        const uint64_t node = encode[f + i];
+        const std::string name = quad_name(x->node_level[node], x->node_index[node]) + ".png";
+        png_encode(images.data() + i * tile_bytes, W, W, png.data());
+        if (!write_at(dirfd, name, png.data(), png.size())) {
+          std::lock_guard<std::mutex> g(err_mu);
+          if (!failed.exchange(1)) first_error = "cannot write " + dir + "/" + name;
+        }
+      }
+    };
+    std::vector<std::thread> pool;
+    for (unsigned t = 1; t < (unsigned)std::min<uint64_t>(nthreads, c); ++t) pool.emplace_back(worker);
+    worker();
+    for (auto& th : pool) th.join();
+    if (failed.load()) rc = ctx->fail(PCV_E_IO, first_error);
+  }
+  std::string err;
+  if (!rc && !write_meta_file(dirfd, dir, 0, 0, x->geo.rect, x->geo.deepest_level, W, x->node_level, x->node_index, &err))
+    rc = ctx->fail(PCV_E_IO, err);
+  ::close(dirfd);
+  return rc;
 }
 
 extern "C" int pcv_xray_write_dir(pcv_xray* x, const char* directory) {
   if (!x) return PCV_E_INVALID;
+  if (!directory) return xray_fail(x, PCV_E_INVALID, "null directory");
+  if (x->kind == kXrayOpened)
+    return xray_fail(x, PCV_E_INVALID, "xray: an opened quadtree is written through pcv_xray_merge (its files are already a directory)");
+  if (x->kind == kXrayMerged) return xray_write_merged(x, directory);
   pcv_ctx* ctx = x->ctx;
-  if (!directory) return ctx->fail(PCV_E_INVALID, "null directory");
   const uint64_t nc = x->created.size(), n = nc + x->parent_index.size();
   if (!x->parents_built && nc && x->root_level < x->geo.deepest_level)
     return ctx->fail(PCV_E_INVALID, "xray: parent levels are not built (pcv_xray_build_parents)");
@@ -1908,32 +2576,13 @@ extern "C" int pcv_xray_write_dir(pcv_xray* x, const char* directory) {
   }
   if (!rc && failed.load()) rc = ctx->fail(PCV_E_IO, first_error);
   if (!rc) {
-    // Meta (xray_proto Meta, CURRENT_VERSION 3) to get_meta_pb_path: the root id with "r" -> "meta", + ".pb"
-    double rect[3] = {x->geo.rect[0], x->geo.rect[1], x->geo.rect[2]};
-    for (int l = (int)x->root_level - 1; l >= 0; --l) {  // root_node.bounding_rect
-      const uint32_t ci = (uint32_t)(x->root_index >> (2 * l)) & 3u;
-      const double half = rect[2] / 2.0;
-      if (ci & 1u) rect[1] += half;
-      if (ci & 2u) rect[0] += half;
-      rect[2] = half;
-    }
-    std::vector<uint8_t> meta, r, mn;
-    pb_uint(meta, 1, 3);
-    pb_double(mn, 1, rect[0]);
-    pb_double(mn, 2, rect[1]);
-    pb_bytes(r, 3, mn);
-    pb_double(r, 4, rect[2]);
-    pb_bytes(meta, 2, r);
-    pb_uint(meta, 3, x->geo.deepest_level);
-    pb_uint(meta, 4, W);
-    for (uint64_t i = 0; i < n; ++i) {
-      std::vector<uint8_t> id;
-      pb_uint(id, 1, i < nc ? x->geo.deepest_level : x->parent_level[i - nc]);
-      pb_uint(id, 2, i < nc ? x->geo.index[x->created[i]] : x->parent_index[i - nc]);
-      pb_bytes(meta, 5, id);
-    }
-    const std::string name = "meta" + quad_name(x->root_level, x->root_index).substr(1) + ".pb";
-    if (!write_at(dirfd, name, meta.data(), meta.size())) rc = ctx->fail(PCV_E_IO, "cannot write " + dir + "/" + name);
+    double rect[3];
+    built_root_rect(x, rect);
+    std::vector<uint32_t> level(n);
+    std::vector<uint64_t> index(n);
+    pcv_xray_nodes(x, nullptr, n, level.data(), index.data());
+    std::string err;
+    if (!write_meta_file(dirfd, dir, x->root_level, x->root_index, rect, x->geo.deepest_level, W, level, index, &err)) rc = ctx->fail(PCV_E_IO, err);
   }
   ::close(dirfd);
   return rc;

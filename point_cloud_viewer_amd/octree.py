@@ -301,6 +301,23 @@ class Context:
         xt.build_parents()
         return xt
 
+    def xray_open(self, directory):
+        """Every meta*.pb of an xray quadtree directory as an XrayTiles (pcv_xray_open_dir), in ascending file name order: the
+        node list (descending level, then ascending index) and the PNGs, decoded on demand by node_images."""
+        return _xray_open(self, directory)
+
+    def xray_merge(self, parts, background="white"):
+        """merge_xray_quadtrees over XrayTiles of this context, built (parents built) or opened, mixed (pcv_xray_merge): the
+        quadtree with root r, its levels above the parts' roots built on the device over `background`. The result keeps
+        its parts alive; freeing one by hand makes its image calls raise PCV_E_INVALID."""
+        parts = list(parts)
+        arr = (C.c_void_p * max(len(parts), 1))(*[p.handle for p in parts])
+        h = C.c_void_p()
+        self._check(self.lib.pcv_xray_merge(self.handle, arr, len(parts), _xray_background(background), C.byref(h)))
+        xt = XrayTiles(self, h, int(self.lib.pcv_xray_tile_size(h)))
+        xt._parts = parts
+        return xt
+
     def shapes(self, shapes):
         """Prepare query shapes on the device. Each entry: ("all",), ("aabb", min3, max3), ("frustum", clip_from_query16),
         ("frustum2", clip_from_query16, query_from_clip16), ("obb", translation3, quat_ijkw4, half_extent3),
@@ -1321,6 +1338,76 @@ def wmr_math(fn, a, b=None):
     return (out, out2) if int(fn) == L.WMR_FN_SINCOS else out
 
 
+def _xray_background(background):
+    if background not in ("white", "transparent"):
+        raise ValueError(f"unknown tile background {background!r}")
+    return L.XRAY_BG_WHITE if background == "white" else L.XRAY_BG_TRANSPARENT
+
+
+def _xray_open(ctx, directory):
+    lib = L.load_library()
+    handle = ctx.handle if ctx is not None else None
+
+    def check(rc):
+        if ctx is not None:
+            ctx._check(rc)
+        elif rc != L.PCV_OK:
+            raise L.PcvError(rc, (lib.pcv_host_last_error() or b"").decode(errors="replace"))
+    n = C.c_uint32()
+    check(lib.pcv_xray_open_dir(handle, os.fsencode(str(directory)), 0, None, C.byref(n)))
+    arr = (C.c_void_p * max(n.value, 1))()
+    check(lib.pcv_xray_open_dir(handle, os.fsencode(str(directory)), n.value, arr, C.byref(n)))
+    return [XrayTiles(ctx, C.c_void_p(arr[i]), int(lib.pcv_xray_tile_size(arr[i]))) for i in range(n.value)]
+
+
+def xray_open_host(directory):
+    """pcv_xray_open_dir without a context (no device): XrayTiles that serve the node list and host images only; they can
+    be passed to xray_merge_check and to any context's xray_merge."""
+    return _xray_open(None, directory)
+
+
+def xray_merge_check(parts):
+    """pcv_xray_merge_check (host only): (root level L, merged rect (min x, min y, edge)) of merge_xray_quadtrees'
+    validate_and_merge_metadata over XrayTiles, or PcvError(PCV_E_INVALID) with the reference's message."""
+    lib = L.load_library()
+    parts = list(parts)
+    arr = (C.c_void_p * max(len(parts), 1))(*[p.handle for p in parts])
+    level, rect, err = C.c_uint32(), (C.c_double * 3)(), C.create_string_buffer(256)
+    rc = lib.pcv_xray_merge_check(arr, len(parts), C.byref(level), rect, err, 256)
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, err.value.decode(errors="replace"))
+    return level.value, tuple(rect)
+
+
+def merge_xray_quadtrees(ctx, input_directories, output_directory, background="white"):
+    """The reference's merge_xray_quadtrees binary: every partial quadtree of input_directories merged into
+    output_directory (which may be one of them); returns the merged XrayTiles."""
+    for d in input_directories:
+        if not os.path.exists(d):
+            raise FileNotFoundError(f"Input directory {str(d)!r} doesn't exist.")
+        if not os.path.isdir(d):
+            raise NotADirectoryError(f"{str(d)!r} is not a directory.")
+    os.makedirs(output_directory, exist_ok=True)
+    parts = [p for d in input_directories for p in ctx.xray_open(d)]
+    merged = ctx.xray_merge(parts, background)
+    merged.write(output_directory)
+    return merged
+
+
+def png_decode(data):
+    """pcv_png_decode (host only): the bytes of an RGBA8 PNG file as an (h, w, 4) uint8 array."""
+    lib = L.load_library()
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    w, h = C.c_uint32(), C.c_uint32()
+    rc = lib.pcv_png_decode(buf.ctypes.data, buf.size, C.byref(w), C.byref(h), None, 0)
+    if rc == L.PCV_OK:
+        out = np.zeros((h.value, w.value, 4), dtype=np.uint8)
+        rc = lib.pcv_png_decode(buf.ctypes.data, buf.size, C.byref(w), C.byref(h), out.ctypes.data, out.nbytes)
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, (lib.pcv_host_last_error() or b"").decode(errors="replace"))
+    return out
+
+
 def xray_lanczos_taps(tile_size_px):
     """pcv_xray_lanczos_taps (host only): (left (W,) u32, count (W,) u32, weights (W, 12) f32) of the 2:1 resize."""
     W = int(tile_size_px)
@@ -1445,7 +1532,8 @@ class XrayTiles:
     """The result of OctreeResult.xray_tiles: the leaf list of the quadtree and the created tiles' RGBA8 images (device)."""
 
     def __init__(self, ctx, handle, tile_size_px):
-        self.ctx, self.lib, self.handle, self.tile_size_px = ctx, ctx.lib, handle, tile_size_px
+        self.ctx, self.lib, self.handle, self.tile_size_px = ctx, (ctx.lib if ctx is not None else L.load_library()), handle, tile_size_px
+        self._parts = []  # a merged quadtree keeps its parts alive
         dl, rect, nl, nc = C.c_uint32(), (C.c_double * 3)(), C.c_uint64(), C.c_uint64()
         self.lib.pcv_xray_info(handle, C.byref(dl), rect, C.byref(nl), C.byref(nc))
         self.deepest_level, self.bounding_rect = dl.value, tuple(rect)
@@ -1453,8 +1541,12 @@ class XrayTiles:
         self.created = np.zeros(max(nc.value, 1), dtype=np.uint64)
         self.kept = np.zeros(max(nc.value, 1), dtype=np.uint64)
         self.drawn = np.zeros(max(nc.value, 1), dtype=np.uint64)
-        self.lib.pcv_xray_tiles(handle, self.leaf_index.ctypes.data, self.created.ctypes.data, self.kept.ctypes.data,
-                                self.drawn.ctypes.data)
+        built = self.lib.pcv_xray_tiles(handle, self.leaf_index.ctypes.data, self.created.ctypes.data, self.kept.ctypes.data,
+                                        self.drawn.ctypes.data) == L.PCV_OK
+        if not built:  # opened or merged (pcv_xray_open_dir, pcv_xray_merge): the leaves are the nodes at deepest_level
+            level, index = self.nodes()
+            self.leaf_index[:nl.value] = index[level == dl.value]
+            self.created[:nc.value] = np.arange(nc.value, dtype=np.uint64)
         self.leaf_index, self.created = self.leaf_index[:nl.value], self.created[:nc.value]
         self.kept, self.drawn = self.kept[:nc.value], self.drawn[:nc.value]
         # colored_with_intensity: kept points with intensity < 0 per created tile (not drawn; 0 for other strategies)
@@ -1464,13 +1556,13 @@ class XrayTiles:
         self.leaf_ids = [quadtree_node_name(self.deepest_level, i) for i in self.leaf_index]
         self.created_ids = [self.leaf_ids[int(c)] for c in self.created]
         self.num_created = int(nc.value)
-        ctx._children.add(self)
+        if ctx is not None:
+            ctx._children.add(self)
 
     def images(self, first=0, count=None, device=False):
         """Created tiles [first, first + count) as a (count, H, W, 4) uint8 array (numpy, or a torch tensor on the
         context's device with device=True); rows top to bottom."""
-        if not self.handle or not self.ctx.handle:
-            raise L.PcvError(L.PCV_E_INVALID, "the xray tiles were freed")
+        self._alive()
         count = self.num_created - int(first) if count is None else int(count)
         W = self.tile_size_px
         if device:
@@ -1480,7 +1572,7 @@ class XrayTiles:
         else:
             out = np.zeros((max(count, 0), W, W, 4), dtype=np.uint8)
             ptr, cap, mem = out.ctypes.data, out.nbytes, L.MEM_HOST
-        self.ctx._check(self.lib.pcv_xray_images(self.handle, int(first), count, cap, mem, ptr))
+        self._check(self.lib.pcv_xray_images(self.handle, int(first), count, cap, mem, ptr))
         return out
 
     def image(self, i):
@@ -1489,7 +1581,7 @@ class XrayTiles:
     def build_parents(self):
         """Every level above the leaves up to root_node_id (pcv_xray_build_parents); a second call does nothing."""
         self._alive()
-        self.ctx._check(self.lib.pcv_xray_build_parents(self.handle))
+        self._check(self.lib.pcv_xray_build_parents(self.handle))
 
     def nodes(self):
         """(level, index) arrays of Meta.nodes in pcv_xray_nodes' order: created leaves, then parents level by level."""
@@ -1522,20 +1614,26 @@ class XrayTiles:
         else:
             out = np.zeros((max(count, 0), W, W, 4), dtype=np.uint8)
             ptr, cap, mem = out.ctypes.data, out.nbytes, L.MEM_HOST
-        self.ctx._check(self.lib.pcv_xray_node_images(self.handle, int(first), count, cap, mem, ptr))
+        self._check(self.lib.pcv_xray_node_images(self.handle, int(first), count, cap, mem, ptr))
         return out
 
     def write(self, directory):
         """build_xray_quadtree's output directory: <node>.png per node and the meta file (pcv_xray_write_dir)."""
         self._alive()
-        self.ctx._check(self.lib.pcv_xray_write_dir(self.handle, os.fsencode(str(directory))))
+        self._check(self.lib.pcv_xray_write_dir(self.handle, os.fsencode(str(directory))))
+
+    def _check(self, rc):
+        if self.ctx is not None:
+            self.ctx._check(rc)
+        elif rc != L.PCV_OK:
+            raise L.PcvError(rc, (self.lib.pcv_host_last_error() or b"").decode(errors="replace"))
 
     def _alive(self):
-        if not self.handle or not self.ctx.handle:
+        if not self.handle or (self.ctx is not None and not self.ctx.handle):
             raise L.PcvError(L.PCV_E_INVALID, "the xray tiles were freed")
 
     def free(self):
-        if self.handle and self.ctx.handle:
+        if self.handle and (self.ctx is None or self.ctx.handle):
             self.lib.pcv_xray_free(self.handle)
         self.handle = None
 

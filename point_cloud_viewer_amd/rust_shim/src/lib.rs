@@ -726,3 +726,64 @@ impl HipOctree {
         })
     }
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// merge_xray_quadtrees (xray/src/bin/merge_xray_quadtrees.rs): partial quadtrees of several directories into one.
+// ------------------------------------------------------------------------------------------------------------------
+#[repr(C)]
+pub struct PcvXray {
+    _private: [u8; 0],
+}
+
+extern "C" {
+    fn pcv_xray_open_dir(ctx: *mut pcv_ctx, directory: *const std::os::raw::c_char, capacity: u32, parts: *mut *mut PcvXray, num_parts: *mut u32) -> i32;
+    fn pcv_xray_merge(ctx: *mut pcv_ctx, parts: *const *mut PcvXray, num_parts: u32, background: u32, out: *mut *mut PcvXray) -> i32;
+    fn pcv_xray_write_dir(x: *mut PcvXray, directory: *const std::os::raw::c_char) -> i32;
+    fn pcv_xray_free(x: *mut PcvXray);
+}
+
+/// The body of the reference binary after argument parsing (:207-223): every `meta*.pb` of `input_directories` is opened,
+/// validated and merged on the device, and the quadtree with root `r` is written to `output_directory`, which may be one
+/// of the inputs. `transparent_background` is `--tile-background-color transparent`. Errors carry the library's message,
+/// which for the reference's own checks is the reference's text.
+pub fn merge_xray_quadtrees(device: i32, input_directories: &[std::path::PathBuf], output_directory: &std::path::Path, transparent_background: bool) -> std::io::Result<()> {
+    use std::os::unix::ffi::OsStrExt;
+    let c = |p: &std::path::Path| std::ffi::CString::new(p.as_os_str().as_bytes()).expect("path with a NUL byte");
+    let ctx = HipContext::new(device).map_err(|e| std::io::Error::new(std::io::ErrorKind::Other, e))?;
+    let mut parts: Vec<*mut PcvXray> = Vec::new();
+    let mut rc = 0;
+    for dir in input_directories {
+        let (name, mut n) = (c(dir), 0u32);
+        rc = unsafe { pcv_xray_open_dir(ctx.0, name.as_ptr(), 0, std::ptr::null_mut(), &mut n) };
+        if rc != 0 {
+            break;
+        }
+        let at = parts.len();
+        parts.resize(at + n as usize, std::ptr::null_mut());
+        rc = unsafe { pcv_xray_open_dir(ctx.0, name.as_ptr(), n, parts[at..].as_mut_ptr(), &mut n) };
+        if rc != 0 {
+            parts.truncate(at);
+            break;
+        }
+    }
+    let mut merged = std::ptr::null_mut();
+    if rc == 0 {
+        rc = unsafe { pcv_xray_merge(ctx.0, parts.as_ptr(), parts.len() as u32, transparent_background as u32, &mut merged) };
+    }
+    if rc == 0 {
+        std::fs::create_dir_all(output_directory)?;
+        rc = unsafe { pcv_xray_write_dir(merged, c(output_directory).as_ptr()) };
+    }
+    let message = if rc == 0 { String::new() } else { unsafe { CStr::from_ptr(pcv_last_error(ctx.0)) }.to_string_lossy().into_owned() };
+    unsafe {
+        pcv_xray_free(merged);
+        for p in parts {
+            pcv_xray_free(p);
+        }
+    }
+    if rc == 0 {
+        Ok(())
+    } else {
+        Err(std::io::Error::new(if rc == -3 { std::io::ErrorKind::Other } else { std::io::ErrorKind::InvalidData }, message))
+    }
+}
