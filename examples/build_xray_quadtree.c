@@ -2,13 +2,14 @@
  * reference's point_cloud_locations) are opened, the leaf tiles over all of them are rasterised on the device
  * (pcv_xray_run_ex), every level above them up to the root node is built on the device (pcv_xray_build_parents), and
  * the quadtree directory the xray viewer loads is written: one <node>.png per node and the meta file
- * (pcv_xray_write_dir). A subset of the reference binary's flags.
+ * (pcv_xray_write_dir_ex). A subset of the reference binary's flags, and --png: stored (the default) or deflate, the
+ * tiles compressed on the device.
  *
  *   build_xray_quadtree <octree dir>... --output-directory <dir> --resolution <m per px> [--tile-size <px>]
  *                       [--coloring-strategy xray|colored|colored_with_intensity|colored_with_height_stddev]
  *                       [--min-intensity <f>] [--max-intensity <f>] [--binning intensity=<size>] [--max-stddev <m>]
  *                       [--colormap jet|purplish] [--tile-background-color white|transparent]
- *                       [--filter-interval intensity=<lo>,<hi>] [--root-node-id <r...>]
+ *                       [--filter-interval intensity=<lo>,<hi>] [--root-node-id <r...>] [--png stored|deflate]
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -21,7 +22,8 @@ static int usage(void) {
           "usage: build_xray_quadtree <octree dir>... --output-directory <dir> --resolution <m per px> [--tile-size <px>]\n"
           "       [--coloring-strategy xray|colored|colored_with_intensity|colored_with_height_stddev] [--min-intensity <f>]\n"
           "       [--max-intensity <f>] [--binning intensity=<size>] [--max-stddev <m>] [--colormap jet|purplish]\n"
-          "       [--tile-background-color white|transparent] [--filter-interval intensity=<lo>,<hi>] [--root-node-id <r...>]\n");
+          "       [--tile-background-color white|transparent] [--filter-interval intensity=<lo>,<hi>] [--root-node-id <r...>]\n"
+          "       [--png stored|deflate]\n");
   return 2;
 }
 
@@ -30,6 +32,7 @@ int main(int argc, char** argv) {
   uint32_t num_inputs = 0;
   const char* output = NULL;
   const char* root = "r";
+  int png = PCV_XRAY_PNG_STORED;
   char attribute[16] = "";
   char bin_attribute[16] = "";
   pcv_xray_coloring col;
@@ -91,6 +94,10 @@ int main(int argc, char** argv) {
       p.interval_attribute = attribute;
     } else if (!strcmp(a, "--root-node-id")) {
       root = v;
+    } else if (!strcmp(a, "--png")) {
+      if (!strcmp(v, "stored")) png = PCV_XRAY_PNG_STORED;
+      else if (!strcmp(v, "deflate")) png = PCV_XRAY_PNG_DEFLATE;
+      else return usage();
     } else {
       return usage();
     }
@@ -110,7 +117,7 @@ int main(int argc, char** argv) {
   for (uint32_t t = 0; t < num_inputs && rc == PCV_OK; ++t) rc = pcv_octree_open_dir(ctx, inputs[t], &trees[t]);
   if (rc == PCV_OK) rc = pcv_xray_run_ex(ctx, trees, num_inputs, &p, &col, &x);
   if (rc == PCV_OK) rc = pcv_xray_build_parents(x);
-  if (rc == PCV_OK) rc = pcv_xray_write_dir(x, output);
+  if (rc == PCV_OK) rc = pcv_xray_write_dir_ex(x, output, png);
   if (rc == PCV_OK) {
     uint64_t nodes = 0, created = 0;
     uint32_t deepest = 0;

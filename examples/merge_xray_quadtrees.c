@@ -1,10 +1,11 @@
 /* merge_xray_quadtrees.c — xray's merge_xray_quadtrees (xray/src/bin/merge_xray_quadtrees.rs) over the C ABI in plain
  * C11: every partial quadtree (meta*.pb) of the input directories is opened (pcv_xray_open_dir), checked and merged with
  * the levels above the parts' roots built on the device (pcv_xray_merge), and the quadtree with root r is written
- * (pcv_xray_write_dir): the parts' PNGs copied, the new levels encoded, meta.pb with the union node list. The output
- * directory may be one of the inputs.
+ * (pcv_xray_write_dir_ex): the parts' PNGs copied, the new levels encoded (--png deflate: compressed on the device),
+ * meta.pb with the union node list. The output directory may be one of the inputs.
  *
- *   merge_xray_quadtrees --output-directory <dir> [--tile-background-color white|transparent] <input dir>...
+ *   merge_xray_quadtrees --output-directory <dir> [--tile-background-color white|transparent] [--png stored|deflate]
+ *                        <input dir>...
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,7 +15,7 @@
 #include "pcv_layout_check.h"
 
 static int usage(void) {
-  fprintf(stderr, "usage: merge_xray_quadtrees --output-directory <dir> [--tile-background-color white|transparent] <input dir>...\n");
+  fprintf(stderr, "usage: merge_xray_quadtrees --output-directory <dir> [--tile-background-color white|transparent] [--png stored|deflate] <input dir>...\n");
   return 2;
 }
 
@@ -22,6 +23,7 @@ int main(int argc, char** argv) {
   const char** inputs = (const char**)calloc((size_t)argc + 1, sizeof(const char*));
   uint32_t num_inputs = 0, background = PCV_XRAY_BG_WHITE;
   const char* output = NULL;
+  int png = PCV_XRAY_PNG_STORED;
   for (int i = 1; i < argc; ++i) {
     const char* a = argv[i];
     if (a[0] != '-') {
@@ -35,6 +37,10 @@ int main(int argc, char** argv) {
     } else if (!strcmp(a, "--tile-background-color")) {
       if (!strcmp(v, "white")) background = PCV_XRAY_BG_WHITE;
       else if (!strcmp(v, "transparent")) background = PCV_XRAY_BG_TRANSPARENT;
+      else return usage();
+    } else if (!strcmp(a, "--png")) {
+      if (!strcmp(v, "stored")) png = PCV_XRAY_PNG_STORED;
+      else if (!strcmp(v, "deflate")) png = PCV_XRAY_PNG_DEFLATE;
       else return usage();
     } else {
       return usage();
@@ -72,7 +78,7 @@ int main(int argc, char** argv) {
   }
   pcv_xray* merged = NULL;
   if (rc == PCV_OK) rc = pcv_xray_merge(ctx, parts, total, background, &merged);
-  if (rc == PCV_OK) rc = pcv_xray_write_dir(merged, output);
+  if (rc == PCV_OK) rc = pcv_xray_write_dir_ex(merged, output, png);
   if (rc == PCV_OK) {
     uint64_t nodes = 0;
     uint32_t deepest = 0;

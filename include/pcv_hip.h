@@ -852,6 +852,53 @@ int pcv_xray_lanczos_taps(uint32_t tile_size_px, uint32_t* left, uint32_t* count
  * capacity >= *needed. w or h == 0 is PCV_E_INVALID. */
 int pcv_xray_png_encode(const uint8_t* rgba, uint32_t w, uint32_t h, uint8_t* out, uint64_t capacity, uint64_t* needed);
 
+/* ---- opt-in compressed tiles: run-length deflate, encoded on the device ------------------------------------------------
+ * PCV_XRAY_PNG_STORED is what pcv_xray_png_encode and pcv_xray_write_dir write, byte for byte. PCV_XRAY_PNG_DEFLATE keeps
+ * the signature, IHDR (filter method 0), one IDAT and IEND, and compresses the scanlines without a match search:
+ *   scanlines  row 0 has filter byte 1 (Sub, 4 bytes per pixel), every other row filter byte 2 (Up)
+ *   bands      PCV_XRAY_PNG_BAND_ROWS(w) consecutive rows (the last band may be shorter), each one deflate block with the
+ *              fixed Huffman codes and BFINAL 0, followed by an empty stored block (3 header bits, padding, 00 00 FF FF):
+ *              every band starts and ends on a byte boundary; the stored block after the last band carries BFINAL 1
+ *   tokens     per maximal run of L equal bytes inside a band: one literal, then with r = L - 1 matches of min(r, 258)
+ *              bytes at distance 1 while r >= 3, then r (0, 1 or 2) literals; end-of-block closes the band
+ *   zlib       78 01, the bands, the Adler-32 of the scanlines
+ * A band of n scanline bytes takes at most ceil((3 + 9 n + 7) / 8) + 5 bytes, a stream 2 + its bands + 4; every buffer is
+ * sized from that bound (noise grows by about 6 %). Width or height above PCV_XRAY_PNG_DEFLATE_MAX_EDGE is
+ * PCV_E_INVALID in deflate mode: one row must fit a band. */
+#define PCV_XRAY_PNG_STORED 0
+#define PCV_XRAY_PNG_DEFLATE 1
+#define PCV_XRAY_PNG_BAND_BYTES 40960u /* scanline bytes a band may hold: its bit buffer (46 087 bytes) fits 48 KiB of LDS */
+#define PCV_XRAY_PNG_DEFLATE_MAX_EDGE 8192u
+/* rows per band: 8, fewer once 8 rows of 1 + 4 w bytes pass PCV_XRAY_PNG_BAND_BYTES, never less than 1 */
+#define PCV_XRAY_PNG_BAND_ROWS(w)                                                   \
+  (PCV_XRAY_PNG_BAND_BYTES / (1u + 4u * (uint32_t)(w)) >= 8u ? 8u                   \
+   : PCV_XRAY_PNG_BAND_BYTES / (1u + 4u * (uint32_t)(w)) >= 1u ? PCV_XRAY_PNG_BAND_BYTES / (1u + 4u * (uint32_t)(w)) : 1u)
+/* Host only, no context: pcv_xray_png_encode with the mode chosen. *needed is the size of this image's file (in deflate
+ * mode it depends on the pixels, so rgba is read even when out == NULL; rgba == NULL then reports the bound). Nothing is
+ * written unless out != NULL and capacity >= *needed. */
+int pcv_xray_png_encode_ex(const uint8_t* rgba, uint32_t w, uint32_t h, int mode, uint8_t* out, uint64_t capacity, uint64_t* needed);
+/* Host only: the largest file pcv_xray_png_encode_ex can make of a w x h image in `mode`; 0 for bad arguments. */
+uint64_t pcv_xray_png_bound(uint32_t w, uint32_t h, int mode);
+/* The complete PNG files of nodes [first, first + count) of pcv_xray_nodes' order, back to back in host memory:
+ * offsets[i] .. offsets[i + 1] is node first + i (count + 1 offsets). out == NULL: the offsets alone. capacity below
+ * offsets[count] is PCV_E_INVALID (the content of out is then unspecified). Built quadtrees, and the levels a merged
+ * quadtree built itself, are compressed on the device in deflate mode and only compressed bytes come down; stored mode
+ * gives the bytes of pcv_xray_write_dir. The nodes of opened quadtrees are handed out as the bytes of their files, whatever
+ * the mode. Equal to pcv_xray_png_encode_ex of pcv_xray_node_images, byte for byte, for every node that is encoded. */
+int pcv_xray_node_pngs(pcv_xray* x, uint64_t first, uint64_t count, int mode, uint64_t capacity, uint8_t* out, uint64_t* offsets);
+/* pcv_xray_write_dir with the PNG mode chosen; pcv_xray_write_dir(x, d) is pcv_xray_write_dir_ex(x, d, PCV_XRAY_PNG_STORED).
+ * File names and the meta file do not depend on the mode. In deflate mode the tiles are compressed on the device, chunk by
+ * chunk through the same two pinned buffers, and the writer threads only wrap and write; a merged quadtree still copies the
+ * files of opened parts byte for byte and applies the mode to the nodes it encodes. */
+int pcv_xray_write_dir_ex(pcv_xray* x, const char* directory, int mode);
+/* `count` w x w RGBA8 tiles (host or device memory, back to back) through the device encoder, as pcv_xray_node_pngs hands
+ * nodes out (deflate mode, out / offsets / capacity alike). chunk_tiles > 0: tiles per device chunk (0: the context's). */
+int pcv_xray_png_encode_tiles(pcv_ctx* ctx, const uint8_t* rgba, int mem, uint32_t w, uint64_t count, uint64_t chunk_tiles,
+                              uint64_t capacity, uint8_t* out, uint64_t* offsets);
+/* Bytes of node images per download chunk of pcv_xray_write_dir* and pcv_xray_node_pngs (default 64 MiB, at least one
+ * tile; 0 restores the default). */
+int pcv_ctx_set_xray_chunk_bytes(pcv_ctx* ctx, uint64_t bytes);
+
 /* ---- reading a quadtree directory back, and merge_xray_quadtrees (xray/src/bin/merge_xray_quadtrees.rs) ----------------
  * Host only, no context: one PNG file as RGBA8, rows top to bottom, for the tiles the reference's png encoder or
  * pcv_xray_png_encode wrote (what image::open does for build_node, xray/src/generation.rs:742-750). Read: the signature,

@@ -83,6 +83,7 @@ RENDER_MAX_POINT_SIZE = 64  # PCV_RENDER_MAX_POINT_SIZE
 XRAY_XRAY, XRAY_COLORED, XRAY_HEIGHT_STDDEV, XRAY_COLORED_WITH_INTENSITY = 0, 1, 2, 3
 XRAY_JET, XRAY_PURPLISH = 0, 1
 XRAY_BG_WHITE, XRAY_BG_TRANSPARENT = 0, 1
+XRAY_PNG_STORED, XRAY_PNG_DEFLATE = 0, 1  # PCV_XRAY_PNG_*: the mode of pcv_xray_write_dir_ex / _node_pngs / _png_encode_ex
 XRAY_MAX_TREES = 4096  # PCV_XRAY_MAX_TREES: octrees of one pcv_xray_run_many
 XRAY_FN_XRAY, XRAY_FN_COLORED, XRAY_FN_JET, XRAY_FN_PURPLISH, XRAY_FN_TO_U8, XRAY_FN_INTENSITY = 0, 1, 2, 3, 4, 5
 REL_IN, REL_CROSS, REL_OUT = 0, 1, 2
@@ -275,6 +276,12 @@ _SIGNATURES = {
     "pcv_xray_write_dir": (C.c_int, [_vp, C.c_char_p]),
     "pcv_xray_lanczos_taps": (C.c_int, [C.c_uint32, _vp, _vp, _vp]),
     "pcv_xray_png_encode": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "pcv_xray_png_encode_ex": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_int, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "pcv_xray_png_bound": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_int]),
+    "pcv_xray_node_pngs": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, _vp, _vp]),
+    "pcv_xray_write_dir_ex": (C.c_int, [_vp, C.c_char_p, C.c_int]),
+    "pcv_xray_png_encode_tiles": (C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp]),
+    "pcv_ctx_set_xray_chunk_bytes": (C.c_int, [_vp, C.c_uint64]),
     "pcv_png_decode": (C.c_int, [_vp, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _vp, C.c_uint64]),
     "pcv_host_last_error": (C.c_char_p, []),
     "pcv_xray_open_dir": (C.c_int, [_vp, C.c_char_p, C.c_uint32, C.POINTER(_vp), C.POINTER(C.c_uint32)]),

@@ -127,6 +127,9 @@ enum PcvKernelId {
   PCV_K_RENDER_RESOLVE,       // pcv_render_views: key -> point -> gamma table -> RGBA8, depth plane, covered pixels
   PCV_K_XRAY_MERGE_STAGE,     // pcv_xray_merge: the parts' root tiles copied into one level array (device copies and one upload)
   PCV_K_XRAY_MERGE_PARENT,    // pcv_xray_merge: xray_parent_kernel over the levels above the parts' roots
+  PCV_K_XRAY_PNG_BAND,        // pcv_xray_png.hip: one wave per (tile, band): filter, run tokens, bit buffer in LDS, the band's slot
+  PCV_K_XRAY_PNG_LAYOUT,      // pcv_xray_png.hip: band offsets and Adler-32 per tile, tile offsets of the chunk
+  PCV_K_XRAY_PNG_GATHER,      // pcv_xray_png.hip: the bands of every tile into one contiguous zlib stream
   PCV_K_COUNT
 };
 
@@ -218,6 +221,8 @@ struct pcv_ctx {
   double prof_ms[PCV_K_COUNT] = {};
   hipEvent_t prof_event();
   void prof_resolve();
+
+  uint64_t xray_chunk_bytes = 64ull << 20;  // node images per download chunk of the xray directory writers (pcv_ctx_set_xray_chunk_bytes)
 
   int fail(int code, const std::string& msg) {
     last_error = msg;

@@ -1,6 +1,7 @@
 // pcv_png.cpp — host-only PNG reader for xray quadtree tiles (pcv_png_decode): what the reference reads back with the
-// image crate when it merges partial quadtrees (xray/src/generation.rs:726-759 build_node -> image::open). No HIP, no
-// context, no zlib: the file compiles with a plain C++ compiler, which is how the sanitizer driver of the tests builds it.
+// image crate when it merges partial quadtrees (xray/src/generation.rs:726-759 build_node -> image::open), and the host
+// PNG writers (pcv_xray_png_encode_ex: stored blocks, or the run-length deflate stream of pcv_xray_png_dev.h). No HIP, no
+// context, no zlib: the file compiles with a plain C++ compiler, which is how the sanitizer drivers of the tests build it.
 //
 //   container   signature, chunk walk with every CRC checked, IHDR first, IDAT bodies concatenated, IEND required;
 //               ancillary chunks (lower-case first letter) and PLTE are skipped
@@ -11,13 +12,16 @@
 //
 // Inflate is sequential and dominates; Average and Paeth are serial along both axes; a tile is 256 KiB. That is why the
 // whole reader stays on the host.
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <mutex>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/pcv_hip.h"
+#include "pcv_xray_png_dev.h"
 
 namespace {
 
@@ -353,4 +357,241 @@ extern "C" int pcv_png_decode(const uint8_t* file, uint64_t len, uint32_t* w, ui
   for (uint32_t y = 0; y < H; ++y) std::memcpy(rgba + (uint64_t)y * 4 * W, raw + (uint64_t)y * (1 + 4ull * W) + 1, 4ull * W);
   delete[] raw;
   return PCV_OK;
+}
+
+// ---- writers: RGBA8, colour type 6, depth 8, one IDAT --------------------------------------------------------------------
+namespace {
+
+uint32_t crc32_table[256];
+std::once_flag crc32_once;
+
+constexpr uint64_t kStored = 65535;  // bytes per stored deflate block
+
+void put_be32(uint8_t* o, uint32_t v) {
+  o[0] = (uint8_t)(v >> 24);
+  o[1] = (uint8_t)(v >> 16);
+  o[2] = (uint8_t)(v >> 8);
+  o[3] = (uint8_t)v;
+}
+
+// signature and IHDR: 33 bytes
+uint8_t* put_head(uint8_t* o, uint32_t w, uint32_t h) {
+  static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+  std::memcpy(o, sig, 8);
+  o += 8;
+  put_be32(o, 13);
+  uint8_t* t = o + 4;
+  std::memcpy(t, "IHDR", 4);
+  put_be32(t + 4, w);
+  put_be32(t + 8, h);
+  t[12] = 8;  // bit depth
+  t[13] = 6;  // RGBA
+  t[14] = 0;  // deflate
+  t[15] = 0;  // adaptive filtering (a filter byte per row)
+  t[16] = 0;  // no interlace
+  put_be32(t + 17, pcv_crc32_update(0xffffffffu, t, 17) ^ 0xffffffffu);
+  return t + 21;
+}
+
+uint8_t* put_iend(uint8_t* o) {
+  put_be32(o, 0);
+  std::memcpy(o + 4, "IEND", 4);
+  put_be32(o + 8, pcv_crc32_update(0xffffffffu, o + 4, 4) ^ 0xffffffffu);
+  return o + 12;
+}
+
+// LSB-first bit writer into a buffer sized by the caller from pcv_png_band_bound
+struct BitWriter {
+  uint8_t* o;
+  uint64_t acc = 0;
+  uint32_t cnt = 0;
+  void put(uint32_t bits, uint32_t nbits) {
+    acc |= (uint64_t)bits << cnt;
+    cnt += nbits;
+    while (cnt >= 8) {
+      *o++ = (uint8_t)acc;
+      acc >>= 8;
+      cnt -= 8;
+    }
+  }
+  void pad() {
+    if (cnt) {
+      *o++ = (uint8_t)acc;
+      acc = 0;
+      cnt = 0;
+    }
+  }
+};
+
+// the zlib stream of pcv_xray_png_dev.h into z (pcv_png_stream_bound(w, h) bytes); returns its length
+uint64_t deflate_stream(const uint8_t* rgba, uint32_t w, uint32_t h, uint8_t* z) {
+  const uint64_t row = 1 + 4ull * w;
+  const uint32_t per_band = PCV_XRAY_PNG_BAND_ROWS(w);
+  std::vector<uint8_t> band(per_band * row);
+  BitWriter bw{z};
+  bw.put(0x78, 8);
+  bw.put(0x01, 8);
+  uint32_t s1 = 1, s2 = 0;
+  for (uint32_t y0 = 0; y0 < h; y0 += per_band) {
+    const uint32_t rows = std::min(per_band, h - y0);
+    const uint64_t n = rows * row;
+    for (uint64_t j = 0; j < n; ++j) band[j] = (uint8_t)pcv_png_filtered(rgba, w, y0 + (uint32_t)(j / row), (uint32_t)(j % row));
+    for (uint64_t i = 0; i < n;) {  // Adler-32, reduced at most every 5 552 bytes
+      const uint64_t m = std::min<uint64_t>(5552, n - i);
+      for (uint64_t j = 0; j < m; ++j) {
+        s1 += band[i + j];
+        s2 += s1;
+      }
+      s1 %= 65521u;
+      s2 %= 65521u;
+      i += m;
+    }
+    bw.put(2, 3);  // BFINAL 0, BTYPE 01
+    for (uint64_t j = 0; j < n;) {
+      uint64_t e = j + 1;
+      while (e < n && band[e] == band[j]) ++e;
+      pcv_png_run_emit((uint32_t)(e - j), band[j], [&](uint32_t bits, uint32_t nbits) { bw.put(bits, nbits); });
+      j = e;
+    }
+    bw.put(0, 7);                                 // end of block
+    bw.put(y0 + rows == h ? 1u : 0u, 3);          // the empty stored block
+    bw.pad();
+    bw.put(0x0000, 16);
+    bw.put(0xffff, 16);
+  }
+  bw.put(s2 >> 8, 8);
+  bw.put(s2 & 255u, 8);
+  bw.put(s1 >> 8, 8);
+  bw.put(s1 & 255u, 8);
+  return (uint64_t)(bw.o - z);
+}
+
+}  // namespace
+
+uint32_t pcv_crc32_update(uint32_t crc, const uint8_t* p, uint64_t n) {
+  std::call_once(crc32_once, [] {
+    for (uint32_t i = 0; i < 256; ++i) {
+      uint32_t c = i;
+      for (int k = 0; k < 8; ++k) c = c & 1 ? 0xedb88320u ^ (c >> 1) : c >> 1;
+      crc32_table[i] = c;
+    }
+  });
+  for (uint64_t i = 0; i < n; ++i) crc = crc32_table[(crc ^ p[i]) & 255u] ^ (crc >> 8);
+  return crc;
+}
+
+uint64_t pcv_png_stored_size(uint32_t w, uint32_t h) {
+  const uint64_t raw = (uint64_t)h * (1 + 4ull * w);
+  const uint64_t blocks = (raw + kStored - 1) / kStored;
+  return kPcvPngWrap + 2 + 5 * blocks + raw + 4;
+}
+
+// filter byte 0 on every row, zlib with stored deflate blocks
+void pcv_png_stored_encode(const uint8_t* rgba, uint32_t w, uint32_t h, uint8_t* out) {
+  uint8_t* o = put_head(out, w, h);
+  // IDAT: zlib header (deflate, 32 K window, no dictionary, FCHECK), stored blocks, Adler-32
+  uint8_t* t = o + 4;
+  std::memcpy(t, "IDAT", 4);
+  o = t + 4;
+  *o++ = 0x78;
+  *o++ = 0x01;
+  const uint64_t row = 1 + 4ull * w, raw = (uint64_t)h * row;
+  uint32_t s1 = 1, s2 = 0;
+  uint64_t done = 0;
+  uint8_t* blk = nullptr;
+  uint64_t room = 0;
+  auto put = [&](const uint8_t* p, uint64_t n) {  // appends scanline bytes, opening stored blocks as they fill
+    while (n) {
+      if (room == 0) {
+        const uint64_t len = std::min<uint64_t>(kStored, raw - done);
+        blk = o;
+        blk[0] = done + len == raw ? 1 : 0;  // BFINAL, BTYPE = 00
+        blk[1] = (uint8_t)len;
+        blk[2] = (uint8_t)(len >> 8);
+        blk[3] = (uint8_t)~len;
+        blk[4] = (uint8_t)(~len >> 8);
+        o += 5;
+        room = len;
+      }
+      const uint64_t k = std::min(n, room);
+      std::memcpy(o, p, k);
+      for (uint64_t i = 0; i < k;) {  // Adler-32, reduced at most every 5 552 bytes
+        const uint64_t m = std::min<uint64_t>(5552, k - i);
+        for (uint64_t j = 0; j < m; ++j) {
+          s1 += p[i + j];
+          s2 += s1;
+        }
+        s1 %= 65521u;
+        s2 %= 65521u;
+        i += m;
+      }
+      o += k;
+      p += k;
+      n -= k;
+      room -= k;
+      done += k;
+    }
+  };
+  const uint8_t filter = 0;
+  for (uint32_t y = 0; y < h; ++y) {
+    put(&filter, 1);
+    put(rgba + (uint64_t)y * 4 * w, 4ull * w);
+  }
+  put_be32(o, s2 << 16 | s1);
+  o += 4;
+  put_be32(t - 4, (uint32_t)(o - t - 4));
+  put_be32(o, pcv_crc32_update(0xffffffffu, t, (uint64_t)(o - t)) ^ 0xffffffffu);
+  put_iend(o + 4);
+}
+
+void pcv_png_wrap(uint32_t w, uint32_t h, const uint8_t* z, uint64_t zlen, uint8_t* out) {
+  uint8_t* o = put_head(out, w, h);
+  put_be32(o, (uint32_t)zlen);
+  std::memcpy(o + 4, "IDAT", 4);
+  if (o + 8 != z) std::memmove(o + 8, z, zlen);  // the stream may have been made in place
+  put_be32(o + 8 + zlen, pcv_crc32_update(0xffffffffu, o + 4, 4 + zlen) ^ 0xffffffffu);
+  put_iend(o + 12 + zlen);
+}
+
+extern "C" uint64_t pcv_xray_png_bound(uint32_t w, uint32_t h, int mode) {
+  if (w == 0 || h == 0 || w > (1u << 30) / 4) return 0;
+  if (mode == PCV_XRAY_PNG_STORED) return pcv_png_stored_size(w, h);
+  if (mode != PCV_XRAY_PNG_DEFLATE || w > PCV_XRAY_PNG_DEFLATE_MAX_EDGE || h > PCV_XRAY_PNG_DEFLATE_MAX_EDGE) return 0;
+  return kPcvPngWrap + pcv_png_stream_bound(w, h);
+}
+
+extern "C" int pcv_xray_png_encode_ex(const uint8_t* rgba, uint32_t w, uint32_t h, int mode, uint8_t* out, uint64_t capacity,
+                                      uint64_t* needed) {
+  if (w == 0 || h == 0 || w > (1u << 30) / 4 || (!rgba && out)) return pcv_host_fail(PCV_E_INVALID, "png: bad image arguments");
+  if (mode == PCV_XRAY_PNG_STORED) {
+    const uint64_t n = pcv_png_stored_size(w, h);
+    if (needed) *needed = n;
+    if (out && capacity >= n) pcv_png_stored_encode(rgba, w, h, out);
+    return PCV_OK;
+  }
+  if (mode != PCV_XRAY_PNG_DEFLATE) return pcv_host_fail(PCV_E_INVALID, "png: unknown mode");
+  if (w > PCV_XRAY_PNG_DEFLATE_MAX_EDGE || h > PCV_XRAY_PNG_DEFLATE_MAX_EDGE)
+    return pcv_host_fail(PCV_E_INVALID, "png: deflate mode takes images of at most 8192 x 8192 pixels");
+  const uint64_t bound = kPcvPngWrap + pcv_png_stream_bound(w, h);
+  if (!rgba) {
+    if (needed) *needed = bound;
+    return PCV_OK;
+  }
+  uint8_t* file = new (std::nothrow) uint8_t[bound];
+  if (!file) return pcv_host_fail(PCV_E_OOM, "png: no host memory for the stream");
+  uint8_t* z = file + 8 + 25 + 8;  // where the IDAT's data goes
+  const uint64_t zlen = deflate_stream(rgba, w, h, z);
+  const uint64_t n = kPcvPngWrap + zlen;
+  if (needed) *needed = n;
+  if (out && capacity >= n) {
+    pcv_png_wrap(w, h, z, zlen, file);
+    std::memcpy(out, file, n);
+  }
+  delete[] file;
+  return PCV_OK;
+}
+
+extern "C" int pcv_xray_png_encode(const uint8_t* rgba, uint32_t w, uint32_t h, uint8_t* out, uint64_t capacity, uint64_t* needed) {
+  if (w == 0 || h == 0 || w > (1u << 30) / 4 || (!rgba && out)) return PCV_E_INVALID;
+  return pcv_xray_png_encode_ex(rgba, w, h, PCV_XRAY_PNG_STORED, out, capacity, needed);
 }

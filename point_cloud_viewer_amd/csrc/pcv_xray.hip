@@ -34,6 +34,7 @@
 
 #include "pcv_query_dev.h"
 #include "pcv_switches.h"
+#include "pcv_xray_png.h"
 
 namespace {
 
@@ -1543,117 +1544,7 @@ __global__ __launch_bounds__(256) void xray_parent_kernel(XrayParentArgs a) {
   }
 }
 
-// ---- PNG (RGBA8, colour type 6, depth 8, one IDAT, filter 0, stored deflate blocks) and meta.pb ---------------------
-uint32_t crc32_table[256];
-std::once_flag crc32_once;
-uint32_t crc32_update(uint32_t crc, const uint8_t* p, size_t n) {
-  std::call_once(crc32_once, [] {
-    for (uint32_t i = 0; i < 256; ++i) {
-      uint32_t c = i;
-      for (int k = 0; k < 8; ++k) c = c & 1 ? 0xedb88320u ^ (c >> 1) : c >> 1;
-      crc32_table[i] = c;
-    }
-  });
-  for (size_t i = 0; i < n; ++i) crc = crc32_table[(crc ^ p[i]) & 255u] ^ (crc >> 8);
-  return crc;
-}
-
-constexpr uint64_t kStored = 65535;  // bytes per stored deflate block
-uint64_t png_size(uint32_t w, uint32_t h) {
-  const uint64_t raw = (uint64_t)h * (1 + 4ull * w);
-  const uint64_t blocks = (raw + kStored - 1) / kStored;
-  return 8 + (12 + 13) + (12 + 2 + 5 * blocks + raw + 4) + 12;
-}
-
-void put_be32(uint8_t* o, uint32_t v) {
-  o[0] = (uint8_t)(v >> 24);
-  o[1] = (uint8_t)(v >> 16);
-  o[2] = (uint8_t)(v >> 8);
-  o[3] = (uint8_t)v;
-}
-
-// writes png_size(w, h) bytes
-void png_encode(const uint8_t* rgba, uint32_t w, uint32_t h, uint8_t* out) {
-  static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
-  uint8_t* o = out;
-  std::memcpy(o, sig, 8);
-  o += 8;
-  auto chunk_end = [&](uint8_t* type_at) {  // data follows the 4-byte type; the CRC covers type and data
-    const uint32_t len = (uint32_t)(o - type_at - 4);
-    put_be32(type_at - 4, len);
-    put_be32(o, crc32_update(0xffffffffu, type_at, (size_t)(o - type_at)) ^ 0xffffffffu);
-    o += 4;
-  };
-  // IHDR
-  uint8_t* t = o + 4;
-  std::memcpy(t, "IHDR", 4);
-  o = t + 4;
-  put_be32(o, w);
-  put_be32(o + 4, h);
-  o[8] = 8;   // bit depth
-  o[9] = 6;   // RGBA
-  o[10] = 0;  // deflate
-  o[11] = 0;  // adaptive filtering (every row: filter 0)
-  o[12] = 0;  // no interlace
-  o += 13;
-  chunk_end(t);
-  // IDAT: zlib header (deflate, 32 K window, no dictionary, FCHECK), stored blocks, Adler-32
-  t = o + 4;
-  std::memcpy(t, "IDAT", 4);
-  o = t + 4;
-  *o++ = 0x78;
-  *o++ = 0x01;
-  const uint64_t row = 1 + 4ull * w, raw = (uint64_t)h * row;
-  uint32_t s1 = 1, s2 = 0;
-  uint64_t done = 0;
-  uint8_t* blk = nullptr;
-  uint64_t room = 0;
-  auto put = [&](const uint8_t* p, uint64_t n) {  // appends scanline bytes, opening stored blocks as they fill
-    while (n) {
-      if (room == 0) {
-        const uint64_t len = std::min<uint64_t>(kStored, raw - done);
-        blk = o;
-        blk[0] = done + len == raw ? 1 : 0;  // BFINAL, BTYPE = 00
-        blk[1] = (uint8_t)len;
-        blk[2] = (uint8_t)(len >> 8);
-        blk[3] = (uint8_t)~len;
-        blk[4] = (uint8_t)(~len >> 8);
-        o += 5;
-        room = len;
-      }
-      const uint64_t k = std::min(n, room);
-      std::memcpy(o, p, k);
-      for (uint64_t i = 0; i < k;) {  // Adler-32, reduced at most every 5 552 bytes
-        const uint64_t m = std::min<uint64_t>(5552, k - i);
-        for (uint64_t j = 0; j < m; ++j) {
-          s1 += p[i + j];
-          s2 += s1;
-        }
-        s1 %= 65521u;
-        s2 %= 65521u;
-        i += m;
-      }
-      o += k;
-      p += k;
-      n -= k;
-      room -= k;
-      done += k;
-    }
-  };
-  const uint8_t filter = 0;
-  for (uint32_t y = 0; y < h; ++y) {
-    put(&filter, 1);
-    put(rgba + (uint64_t)y * 4 * w, 4ull * w);
-  }
-  put_be32(o, s2 << 16 | s1);
-  o += 4;
-  chunk_end(t);
-  t = o + 4;
-  std::memcpy(t, "IEND", 4);
-  o = t + 4;
-  chunk_end(t);
-}
-
+// ---- meta.pb (the PNG encoders live in pcv_png.cpp and pcv_xray_png.hip) -----------------------------------------------
 // rust-protobuf 2.x, proto3: fields in number order, zero scalars omitted, set message fields always written
 void pb_varint(std::vector<uint8_t>& o, uint64_t v) {
   while (v >= 0x80) {
@@ -1714,14 +1605,6 @@ extern "C" int pcv_xray_lanczos_taps(uint32_t tile_size_px, uint32_t* left, uint
     if (weights)
       for (uint32_t k = 0; k < kTaps; ++k) weights[(uint64_t)o * kTaps + k] = k < taps[o].count ? taps[o].w[k] : 0.0f;
   }
-  return PCV_OK;
-}
-
-extern "C" int pcv_xray_png_encode(const uint8_t* rgba, uint32_t w, uint32_t h, uint8_t* out, uint64_t capacity, uint64_t* needed) {
-  if (w == 0 || h == 0 || w > (1u << 30) / 4 || (!rgba && out)) return PCV_E_INVALID;
-  const uint64_t n = png_size(w, h);
-  if (needed) *needed = n;
-  if (out && capacity >= n) png_encode(rgba, w, h, out);
   return PCV_OK;
 }
 
@@ -1871,6 +1754,10 @@ extern "C" int pcv_xray_nodes(const pcv_xray* x, uint64_t* num_nodes, uint64_t c
 }
 
 extern "C" uint32_t pcv_xray_tile_size(const pcv_xray* x) { return x ? x->W : 0; }
+
+// takes the finished file of a node; false: it could not be kept (PCV_E_IO). May be called from several threads at once
+// where xray_node_files is asked to work in parallel
+using XrayFileSink = std::function<bool(uint64_t node, const uint8_t* file, uint64_t len)>;
 
 // node images [first, first + count) of a built quadtree's node list into dst (host or device), no synchronisation
 static int queue_node_images(pcv_xray* x, uint64_t first, uint64_t count, uint8_t* dst, hipMemcpyKind kind) {
@@ -2418,8 +2305,10 @@ static bool same_directory(const std::string& a, const std::string& b) {  // cop
   return same;
 }
 
-// pcv_xray_write_dir of a merged quadtree
-static int xray_write_merged(pcv_xray* x, const char* directory) {
+static int xray_node_files(pcv_xray* x, uint64_t first, uint64_t count, int mode, bool parallel, const XrayFileSink& sink);
+
+// pcv_xray_write_dir_ex of a merged quadtree
+static int xray_write_merged(pcv_xray* x, const char* directory, int mode) {
   pcv_ctx* ctx = x->ctx;
   for (const XrayPartRef& r : x->parts)
     if (!xray_part_alive(r)) return ctx->fail(PCV_E_INVALID, "xray: a part of this merged quadtree was freed before it");
@@ -2450,7 +2339,26 @@ static int xray_write_merged(pcv_xray* x, const char* directory) {
     }
   }
   for (uint64_t i = n - x->parent_index.size(); i < n; ++i) encode.push_back(i);
-  const uint64_t per_chunk = std::max<uint64_t>(1, (64ull << 20) / tile_bytes);
+  if (mode == PCV_XRAY_PNG_DEFLATE) {  // compressed where the images live; the threads below only write
+    std::mutex err_mu;
+    std::string first_error;
+    const XrayFileSink write = [&](uint64_t node, const uint8_t* file, uint64_t len) {
+      const std::string name = quad_name(x->node_level[node], x->node_index[node]) + ".png";
+      if (write_at(dirfd, name, file, len)) return true;
+      std::lock_guard<std::mutex> g(err_mu);
+      if (first_error.empty()) first_error = "cannot write " + dir + "/" + name;
+      return false;
+    };
+    for (uint64_t i = 0; !rc && i < encode.size();) {  // runs of consecutive nodes in one call
+      uint64_t k = 1;
+      while (i + k < encode.size() && encode[i + k] == encode[i] + k) ++k;
+      rc = xray_node_files(x, encode[i], k, mode, true, write);
+      if (rc == PCV_E_IO && !first_error.empty()) ctx->fail(rc, first_error);
+      i += k;
+    }
+    encode.clear();
+  }
+  const uint64_t per_chunk = std::max<uint64_t>(1, ctx->xray_chunk_bytes / tile_bytes);
   std::vector<uint8_t> images(std::min<uint64_t>(per_chunk, std::max<uint64_t>(encode.size(), 1)) * tile_bytes);
   unsigned nthreads = std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
   for (uint64_t f = 0; !rc && f < encode.size(); f += per_chunk) {
@@ -2467,13 +2375,13 @@ static int xray_write_merged(pcv_xray* x, const char* directory) {
     std::string first_error;
     std::mutex err_mu;
     auto worker = [&]() {
-      std::vector<uint8_t> png(png_size(W, W));
+      std::vector<uint8_t> png(pcv_png_stored_size(W, W));
       for (;;) {
         const uint64_t i = next.fetch_add(1);
         if (i >= c || failed.load()) return;
         const uint64_t node = encode[f + i];
         const std::string name = quad_name(x->node_level[node], x->node_index[node]) + ".png";
-        png_encode(images.data() + i * tile_bytes, W, W, png.data());
+        pcv_png_stored_encode(images.data() + i * tile_bytes, W, W, png.data());
         if (!write_at(dirfd, name, png.data(), png.size())) {
           std::lock_guard<std::mutex> g(err_mu);
           if (!failed.exchange(1)) first_error = "cannot write " + dir + "/" + name;
@@ -2493,12 +2401,19 @@ static int xray_write_merged(pcv_xray* x, const char* directory) {
   return rc;
 }
 
-extern "C" int pcv_xray_write_dir(pcv_xray* x, const char* directory) {
+static int xray_write_built_deflate(pcv_xray* x, int dirfd, const std::string& dir);
+
+extern "C" int pcv_xray_write_dir(pcv_xray* x, const char* directory) { return pcv_xray_write_dir_ex(x, directory, PCV_XRAY_PNG_STORED); }
+
+extern "C" int pcv_xray_write_dir_ex(pcv_xray* x, const char* directory, int mode) {
   if (!x) return PCV_E_INVALID;
   if (!directory) return xray_fail(x, PCV_E_INVALID, "null directory");
+  if (mode != PCV_XRAY_PNG_STORED && mode != PCV_XRAY_PNG_DEFLATE) return xray_fail(x, PCV_E_INVALID, "xray: unknown PNG mode");
   if (x->kind == kXrayOpened)
     return xray_fail(x, PCV_E_INVALID, "xray: an opened quadtree is written through pcv_xray_merge (its files are already a directory)");
-  if (x->kind == kXrayMerged) return xray_write_merged(x, directory);
+  if (mode == PCV_XRAY_PNG_DEFLATE && x->W > PCV_XRAY_PNG_DEFLATE_MAX_EDGE)
+    return xray_fail(x, PCV_E_INVALID, "xray: compressed tiles are at most " + std::to_string(PCV_XRAY_PNG_DEFLATE_MAX_EDGE) + " pixels wide");
+  if (x->kind == kXrayMerged) return xray_write_merged(x, directory, mode);
   pcv_ctx* ctx = x->ctx;
   const uint64_t nc = x->created.size(), n = nc + x->parent_index.size();
   if (!x->parents_built && nc && x->root_level < x->geo.deepest_level)
@@ -2513,12 +2428,13 @@ extern "C" int pcv_xray_write_dir(pcv_xray* x, const char* directory) {
   // encodes and writes chunk k (no HIP call in a writer thread)
   const uint32_t W = x->W;
   const uint64_t tile_bytes = 4ull * W * W;
-  const uint64_t per_chunk = std::max<uint64_t>(1, std::min<uint64_t>(n, (64ull << 20) / tile_bytes));
-  const uint64_t chunks = (n + per_chunk - 1) / per_chunk;
+  const uint64_t per_chunk = std::max<uint64_t>(1, std::min<uint64_t>(n, ctx->xray_chunk_bytes / tile_bytes));
+  const uint64_t chunks = mode == PCV_XRAY_PNG_DEFLATE ? 0 : (n + per_chunk - 1) / per_chunk;
   uint8_t* host[2] = {nullptr, nullptr};
   hipEvent_t ev[2] = {nullptr, nullptr};
   int rc = PCV_OK;
-  if (n) {
+  if (mode == PCV_XRAY_PNG_DEFLATE && n) rc = xray_write_built_deflate(x, dirfd, dir);
+  if (n && chunks) {
     if (hipSetDevice(ctx->device) != hipSuccess) rc = ctx->fail(PCV_E_HIP, "hipSetDevice");
     for (int k = 0; !rc && k < 2 && (uint64_t)k < chunks; ++k) {
       rc = ctx->host_alloc((void**)&host[k], per_chunk * tile_bytes);
@@ -2538,7 +2454,7 @@ extern "C" int pcv_xray_write_dir(pcv_xray* x, const char* directory) {
     return r;
   };
   if (!rc && chunks) rc = queue(0);
-  for (uint64_t k = 0; !rc && k < chunks; ++k) {
+  for (uint64_t k = 0; !rc && k < chunks; ++k) {  // stored mode only: in deflate mode there are no chunks here
     if (k + 1 < chunks && (rc = queue(k + 1))) break;  // its buffer's writers (chunk k - 1) have finished
     if (hipEventSynchronize(ev[k & 1]) != hipSuccess) {
       rc = ctx->fail(PCV_E_HIP, "xray: image download failed");
@@ -2548,14 +2464,14 @@ extern "C" int pcv_xray_write_dir(pcv_xray* x, const char* directory) {
     const uint8_t* buf = host[k & 1];
     std::atomic<uint64_t> next{0};
     auto worker = [&]() {
-      std::vector<uint8_t> png(png_size(W, W));
+      std::vector<uint8_t> png(pcv_png_stored_size(W, W));
       for (;;) {
         const uint64_t i = next.fetch_add(1);
         if (i >= c || failed.load()) return;
         const uint64_t node = f + i;
         const std::string name = node < nc ? quad_name(x->geo.deepest_level, x->geo.index[x->created[node]]) + ".png"
                                            : quad_name(x->parent_level[node - nc], x->parent_index[node - nc]) + ".png";
-        png_encode(buf + i * tile_bytes, W, W, png.data());
+        pcv_png_stored_encode(buf + i * tile_bytes, W, W, png.data());
         if (!write_at(dirfd, name, png.data(), png.size())) {
           std::lock_guard<std::mutex> g(err_mu);
           if (!failed.exchange(1)) first_error = "cannot write " + dir + "/" + name;
@@ -2569,7 +2485,7 @@ extern "C" int pcv_xray_write_dir(pcv_xray* x, const char* directory) {
     for (auto& th : pool) th.join();
     if (failed.load()) break;
   }
-  (void)hipStreamSynchronize(ctx->stream);
+  if (n) (void)hipStreamSynchronize(ctx->stream);
   for (int k = 0; k < 2; ++k) {
     if (ev[k]) (void)hipEventDestroy(ev[k]);
     if (host[k]) ctx->host_release(host[k]);
@@ -2586,4 +2502,287 @@ extern "C" int pcv_xray_write_dir(pcv_xray* x, const char* directory) {
   }
   ::close(dirfd);
   return rc;
+}
+
+// ---- compressed tiles: the host side of pcv_xray_png.hip ----------------------------------------------------------------
+namespace {
+
+template <typename Fn>
+void xray_parallel_for(uint64_t n, bool parallel, Fn&& fn) {
+  unsigned nt = parallel ? std::min(8u, std::max(1u, std::thread::hardware_concurrency())) : 1u;
+  nt = (unsigned)std::min<uint64_t>(nt, n);
+  std::atomic<uint64_t> next{0};
+  auto worker = [&]() {
+    for (uint64_t i; (i = next.fetch_add(1)) < n;) fn(i);
+  };
+  std::vector<std::thread> pool;
+  for (unsigned t = 1; t < nt; ++t) pool.emplace_back(worker);
+  worker();
+  for (auto& th : pool) th.join();
+}
+
+// One chunk in flight on the device and one on the host: the scratch of pcv_xray_png_launch and two pinned buffers, each
+// for the compacted streams of a chunk and their offsets. Only offsets and compressed bytes are copied down.
+struct XrayPngPipe {
+  pcv_ctx* ctx = nullptr;
+  PcvPngWork wk;
+  uint8_t* host[2] = {nullptr, nullptr};
+  uint64_t* tab[2] = {nullptr, nullptr};
+  hipEvent_t ev_tab[2] = {nullptr, nullptr}, ev_bytes[2] = {nullptr, nullptr};
+  int open(pcv_ctx* c, uint32_t W, uint64_t tiles, int buffers) {
+    ctx = c;
+    int rc = pcv_xray_png_work_alloc(ctx, W, tiles, &wk);
+    for (int k = 0; !rc && k < buffers; ++k) {
+      if ((rc = ctx->host_alloc((void**)&host[k], tiles * wk.tile_bound)) || (rc = ctx->host_alloc((void**)&tab[k], 8 * (tiles + 1)))) break;
+      if (hipEventCreateWithFlags(&ev_tab[k], hipEventDisableTiming) != hipSuccess ||
+          hipEventCreateWithFlags(&ev_bytes[k], hipEventDisableTiming) != hipSuccess)
+        rc = ctx->fail(PCV_E_HIP, "hipEventCreate");
+    }
+    return rc;
+  }
+  // kernels of a chunk, then its offsets on their way down
+  int launch(int s, const uint8_t* a, uint64_t na, const uint8_t* b, uint64_t count) {
+    if (int rc = pcv_xray_png_launch(ctx, wk, a, na, b, count)) return rc;
+    PCV_HIP_CHECK(ctx, hipMemcpyAsync(tab[s], wk.offsets, 8 * (count + 1), hipMemcpyDeviceToHost, ctx->stream));
+    PCV_HIP_CHECK(ctx, hipEventRecord(ev_tab[s], ctx->stream));
+    return PCV_OK;
+  }
+  // once the offsets are here: exactly the compressed bytes on their way down
+  int fetch(int s, uint64_t count) {
+    PCV_HIP_CHECK(ctx, hipEventSynchronize(ev_tab[s]));
+    const uint64_t total = tab[s][count];
+    if (total > count * wk.tile_bound) return ctx->fail(PCV_E_HIP, "xray: compressed chunk larger than its bound");
+    PCV_HIP_CHECK(ctx, hipMemcpyAsync(host[s], wk.out, total, hipMemcpyDeviceToHost, ctx->stream));
+    PCV_HIP_CHECK(ctx, hipEventRecord(ev_bytes[s], ctx->stream));
+    return PCV_OK;
+  }
+  int wait(int s) {
+    PCV_HIP_CHECK(ctx, hipEventSynchronize(ev_bytes[s]));
+    return PCV_OK;
+  }
+  void close() {
+    if (!ctx) return;
+    (void)hipStreamSynchronize(ctx->stream);
+    for (int k = 0; k < 2; ++k) {
+      if (ev_tab[k]) (void)hipEventDestroy(ev_tab[k]);
+      if (ev_bytes[k]) (void)hipEventDestroy(ev_bytes[k]);
+      if (host[k]) ctx->host_release(host[k]);
+      if (tab[k]) ctx->host_release(tab[k]);
+    }
+    pcv_xray_png_work_free(ctx, &wk);
+  }
+};
+
+// The zlib streams of `count` device tiles, per_chunk at a time: src(f, c, &a, &na, &b) names tiles [f, f + c) for
+// pcv_xray_png_launch; use(f, c, streams, offsets) runs on the host while the next chunk is compressed and copied.
+template <typename Src, typename Use>
+int xray_deflate_chunks(pcv_ctx* ctx, uint32_t W, uint64_t count, uint64_t per_chunk, Src&& src, Use&& use) {
+  if (count == 0) return PCV_OK;
+  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  per_chunk = std::max<uint64_t>(1, std::min(per_chunk, count));
+  const uint64_t chunks = (count + per_chunk - 1) / per_chunk;
+  XrayPngPipe pipe;
+  int rc = pipe.open(ctx, W, per_chunk, chunks > 1 ? 2 : 1);
+  auto start = [&](uint64_t k) -> int {
+    const uint64_t f = k * per_chunk, c = std::min(per_chunk, count - f);
+    const uint8_t *a = nullptr, *b = nullptr;
+    uint64_t na = 0;
+    src(f, c, &a, &na, &b);
+    if (int r = pipe.launch((int)(k & 1), a, na, b, c)) return r;
+    return pipe.fetch((int)(k & 1), c);
+  };
+  if (!rc) rc = start(0);
+  for (uint64_t k = 0; !rc && k < chunks; ++k) {
+    if (k + 1 < chunks && (rc = start(k + 1))) break;  // its buffer's users (chunk k - 1) have finished
+    if ((rc = pipe.wait((int)(k & 1)))) break;
+    const uint64_t f = k * per_chunk, c = std::min(per_chunk, count - f);
+    rc = use(f, c, pipe.host[k & 1], pipe.tab[k & 1]);
+  }
+  pipe.close();
+  return rc;
+}
+
+// the device tiles of nodes [f, f + c): a built quadtree's leaves then parents, a merged quadtree's own levels
+void xray_device_tiles(const pcv_xray* x, uint64_t f, uint64_t c, const uint8_t** a, uint64_t* na, const uint8_t** b) {
+  const uint64_t tile_bytes = 4ull * x->W * x->W;
+  if (x->kind == kXrayMerged) {
+    *na = 0;
+    *b = reinterpret_cast<const uint8_t*>(x->d_parents) + (f - (x->node_index.size() - x->parent_index.size())) * tile_bytes;
+    return;
+  }
+  const uint64_t nc = x->created.size();
+  *na = f < nc ? std::min(c, nc - f) : 0;
+  *a = reinterpret_cast<const uint8_t*>(x->d_images) + f * tile_bytes;
+  *b = reinterpret_cast<const uint8_t*>(x->d_parents) + (f + *na - nc) * tile_bytes;
+}
+
+// nodes [first, first + count) whose images are on x's device, encoded in `mode`, each file to the sink
+int xray_device_node_files(pcv_xray* x, uint64_t first, uint64_t count, int mode, bool parallel, const XrayFileSink& sink) {
+  pcv_ctx* ctx = x->ctx;
+  const uint32_t W = x->W;
+  const uint64_t tile_bytes = 4ull * W * W;
+  const uint64_t per_chunk = std::max<uint64_t>(1, std::min(count, ctx->xray_chunk_bytes / tile_bytes));
+  std::atomic<int> failed{0};
+  if (mode == PCV_XRAY_PNG_DEFLATE) {
+    const int rc = xray_deflate_chunks(
+        ctx, W, count, per_chunk,
+        [&](uint64_t f, uint64_t c, const uint8_t** a, uint64_t* na, const uint8_t** b) { xray_device_tiles(x, first + f, c, a, na, b); },
+        [&](uint64_t f, uint64_t c, const uint8_t* streams, const uint64_t* offs) {
+          xray_parallel_for(c, parallel, [&](uint64_t i) {
+            if (failed.load()) return;
+            std::vector<uint8_t> png(kPcvPngWrap + offs[i + 1] - offs[i]);
+            pcv_png_wrap(W, W, streams + offs[i], offs[i + 1] - offs[i], png.data());
+            if (!sink(first + f + i, png.data(), png.size())) failed.store(1);
+          });
+          return failed.load() ? PCV_E_IO : PCV_OK;
+        });
+    return rc;
+  }
+  std::vector<uint8_t> images(per_chunk * tile_bytes);
+  for (uint64_t f = 0; f < count; f += per_chunk) {
+    const uint64_t c = std::min(per_chunk, count - f);
+    if (int rc = xray_node_images(x, first + f, c, PCV_MEM_HOST, images.data())) return rc;
+    xray_parallel_for(c, parallel, [&](uint64_t i) {
+      if (failed.load()) return;
+      std::vector<uint8_t> png(pcv_png_stored_size(W, W));
+      pcv_png_stored_encode(images.data() + i * tile_bytes, W, W, png.data());
+      if (!sink(first + f + i, png.data(), png.size())) failed.store(1);
+    });
+    if (failed.load()) return PCV_E_IO;
+  }
+  return PCV_OK;
+}
+
+}  // namespace
+
+// the files of nodes [first, first + count) of any kind of quadtree: opened nodes as their files are, the others encoded
+static int xray_node_files(pcv_xray* x, uint64_t first, uint64_t count, int mode, bool parallel, const XrayFileSink& sink) {
+  if (count == 0) return PCV_OK;
+  if (x->kind == kXrayBuilt) return xray_device_node_files(x, first, count, mode, parallel, sink);
+  if (x->kind == kXrayOpened) {
+    std::vector<uint8_t> file;
+    for (uint64_t i = first; i < first + count; ++i) {
+      const std::string path = x->dir + "/" + quad_name(x->node_level[i], x->node_index[i]) + ".png";
+      if (!read_file(path, file)) return xray_fail(x, PCV_E_IO, "xray: cannot read " + path);
+      if (!sink(i, file.data(), file.size())) return PCV_E_IO;
+    }
+    return PCV_OK;
+  }
+  pcv_ctx* ctx = x->ctx;
+  for (const XrayPartRef& r : x->parts)
+    if (!xray_part_alive(r)) return ctx->fail(PCV_E_INVALID, "xray: a part of this merged quadtree was freed before it");
+  uint64_t at = first;
+  const uint64_t end = first + count;
+  for (const XrayPartRef& r : x->parts) {
+    if (at >= end) break;
+    if (at >= r.first + r.count || r.count == 0) continue;
+    const uint64_t k = std::min(end, r.first + r.count) - at;
+    const uint64_t shift = r.first;
+    const int rc = xray_node_files(r.part, at - r.first, k, mode, parallel,
+                                   [&](uint64_t node, const uint8_t* file, uint64_t len) { return sink(node + shift, file, len); });
+    if (rc) return r.part->ctx == ctx || rc == PCV_E_IO ? rc : ctx->fail(rc, r.part->ctx ? r.part->ctx->last_error : pcv_host_last_error());
+    at += k;
+  }
+  return at < end ? xray_device_node_files(x, at, end - at, mode, parallel, sink) : PCV_OK;
+}
+
+// pcv_xray_write_dir_ex of a built quadtree in deflate mode: compressed chunks come down, the writer threads wrap and write
+static int xray_write_built_deflate(pcv_xray* x, int dirfd, const std::string& dir) {
+  const uint64_t nc = x->created.size(), n = nc + x->parent_index.size();
+  std::mutex err_mu;
+  std::string first_error;
+  const int rc = xray_node_files(x, 0, n, PCV_XRAY_PNG_DEFLATE, true, [&](uint64_t node, const uint8_t* file, uint64_t len) {
+    const std::string name = node < nc ? quad_name(x->geo.deepest_level, x->geo.index[x->created[node]]) + ".png"
+                                       : quad_name(x->parent_level[node - nc], x->parent_index[node - nc]) + ".png";
+    if (write_at(dirfd, name, file, len)) return true;
+    std::lock_guard<std::mutex> g(err_mu);
+    if (first_error.empty()) first_error = "cannot write " + dir + "/" + name;
+    return false;
+  });
+  return rc == PCV_E_IO && !first_error.empty() ? x->ctx->fail(rc, first_error) : rc;
+}
+
+namespace {
+// files appended to a caller's buffer with their offsets; out == nullptr: the offsets alone
+struct XrayPngAppend {
+  uint8_t* out;
+  uint64_t capacity, at = 0, index = 0;
+  uint64_t* offsets;
+  bool fits = true;
+  bool take(const uint8_t* file, uint64_t len) {
+    offsets[index++] = at;
+    if (out && len <= capacity - std::min(capacity, at)) std::memcpy(out + at, file, len);
+    else if (out) fits = false;
+    at += len;
+    offsets[index] = at;
+    return true;
+  }
+};
+}  // namespace
+
+extern "C" int pcv_xray_node_pngs(pcv_xray* x, uint64_t first, uint64_t count, int mode, uint64_t capacity, uint8_t* out, uint64_t* offsets) {
+  if (!x) return PCV_E_INVALID;
+  uint64_t n = 0;
+  pcv_xray_nodes(x, &n, 0, nullptr, nullptr);
+  if (first > n || count > n - first) return xray_fail(x, PCV_E_INVALID, "xray: node range past the end");
+  if (mode != PCV_XRAY_PNG_STORED && mode != PCV_XRAY_PNG_DEFLATE) return xray_fail(x, PCV_E_INVALID, "xray: unknown PNG mode");
+  if (!offsets) return xray_fail(x, PCV_E_INVALID, "null offsets");
+  if (mode == PCV_XRAY_PNG_DEFLATE && x->kind != kXrayOpened && x->W > PCV_XRAY_PNG_DEFLATE_MAX_EDGE)
+    return xray_fail(x, PCV_E_INVALID, "xray: compressed tiles are at most " + std::to_string(PCV_XRAY_PNG_DEFLATE_MAX_EDGE) + " pixels wide");
+  offsets[0] = 0;
+  XrayPngAppend app{out, capacity};
+  app.offsets = offsets;
+  const int rc = xray_node_files(x, first, count, mode, false, [&](uint64_t, const uint8_t* file, uint64_t len) { return app.take(file, len); });
+  if (rc) return rc;
+  if (!app.fits) return xray_fail(x, PCV_E_INVALID, "xray: capacity below the " + std::to_string(app.at) + " bytes of these files");
+  return PCV_OK;
+}
+
+extern "C" int pcv_xray_png_encode_tiles(pcv_ctx* ctx, const uint8_t* rgba, int mem, uint32_t w, uint64_t count, uint64_t chunk_tiles,
+                                         uint64_t capacity, uint8_t* out, uint64_t* offsets) {
+  if (!ctx) return PCV_E_INVALID;
+  if (!offsets || (count && !rgba) || w == 0) return ctx->fail(PCV_E_INVALID, "xray: bad arguments to pcv_xray_png_encode_tiles");
+  if (mem != PCV_MEM_HOST && mem != PCV_MEM_DEVICE) return ctx->fail(PCV_E_INVALID, "bad mem");
+  if (w > PCV_XRAY_PNG_DEFLATE_MAX_EDGE)
+    return ctx->fail(PCV_E_INVALID, "xray: compressed tiles are at most " + std::to_string(PCV_XRAY_PNG_DEFLATE_MAX_EDGE) + " pixels wide");
+  offsets[0] = 0;
+  if (count == 0) return PCV_OK;
+  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const uint64_t tile_bytes = 4ull * w * w;
+  PcvScratch sc(ctx);
+  const uint8_t* tiles = rgba;
+  if (mem == PCV_MEM_HOST) {
+    uint8_t* d = nullptr;
+    if (int rc = sc.get(&d, count * tile_bytes)) return rc;
+    PCV_HIP_CHECK(ctx, hipMemcpyAsync(d, rgba, count * tile_bytes, hipMemcpyHostToDevice, ctx->stream));
+    tiles = d;
+  }
+  XrayPngAppend app{out, capacity};
+  app.offsets = offsets;
+  const uint64_t per_chunk = chunk_tiles ? chunk_tiles : std::max<uint64_t>(1, ctx->xray_chunk_bytes / tile_bytes);
+  const int rc = xray_deflate_chunks(
+      ctx, w, count, per_chunk,
+      [&](uint64_t f, uint64_t, const uint8_t** a, uint64_t* na, const uint8_t** b) {
+        *na = 0;
+        *a = nullptr;
+        *b = tiles + f * tile_bytes;
+      },
+      [&](uint64_t, uint64_t c, const uint8_t* streams, const uint64_t* offs) {
+        std::vector<uint8_t> png;
+        for (uint64_t i = 0; i < c; ++i) {
+          png.resize(kPcvPngWrap + offs[i + 1] - offs[i]);
+          pcv_png_wrap(w, w, streams + offs[i], offs[i + 1] - offs[i], png.data());
+          app.take(png.data(), png.size());
+        }
+        return PCV_OK;
+      });
+  if (rc) return rc;
+  if (!app.fits) return ctx->fail(PCV_E_INVALID, "xray: capacity below the " + std::to_string(app.at) + " bytes of these files");
+  return PCV_OK;
+}
+
+extern "C" int pcv_ctx_set_xray_chunk_bytes(pcv_ctx* ctx, uint64_t bytes) {
+  if (!ctx) return PCV_E_INVALID;
+  ctx->xray_chunk_bytes = bytes ? bytes : 64ull << 20;
+  return PCV_OK;
 }

@@ -102,6 +102,11 @@ class Context:
         except Exception:
             pass
 
+    def set_xray_chunk_bytes(self, nbytes=0):
+        """Bytes of node images per download chunk of XrayTiles.write / node_pngs (pcv_ctx_set_xray_chunk_bytes; 0: the
+        default of 64 MiB). A chunk holds at least one tile."""
+        self._check(self.lib.pcv_ctx_set_xray_chunk_bytes(self.handle, int(nbytes)))
+
     def set_profiling(self, enabled=True):
         """Bracket kernel launches with HIP events on the ctx stream (see kernel_stats): True / 1 = every launch,
         "major" / 2 = only the kernels that pass over the whole cloud, False / 0 = off."""
@@ -294,11 +299,14 @@ class Context:
 
     def xray_quadtree(self, trees, tile_size_px=256, pixel_size_m=None, strategy="xray", query_from_global=None,
                       intensity_interval=None, background="white", root_node_id="r", max_workspace_bytes=None, min_intensity=0.0,
-                      max_intensity=1.0, binning=None):
-        """xray_tiles over several octrees (same arguments) with every level above the leaves built on the device."""
+                      max_intensity=1.0, binning=None, output_directory=None, png="stored"):
+        """xray_tiles over several octrees (same arguments) with every level above the leaves built on the device; with
+        output_directory the quadtree is also written there (XrayTiles.write, PNGs as `png` says)."""
         xt = self.xray_tiles(trees, tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background,
                              root_node_id, max_workspace_bytes, min_intensity, max_intensity, binning)
         xt.build_parents()
+        if output_directory is not None:
+            xt.write(output_directory, png=png)
         return xt
 
     def xray_open(self, directory):
@@ -971,12 +979,15 @@ class OctreeResult:
 
     def xray_quadtree(self, tile_size_px=256, pixel_size_m=None, strategy="xray", query_from_global=None, intensity_interval=None,
                       background="white", root_node_id="r", max_workspace_bytes=None, min_intensity=0.0, max_intensity=1.0,
-                      binning=None):
+                      binning=None, output_directory=None, png="stored"):
         """xray_tiles (same arguments) with every level above the leaves up to root_node_id built on the device
-        (create_non_leaf_nodes, generation.rs:656-682): the whole quadtree; XrayTiles.write puts it on disk."""
+        (create_non_leaf_nodes, generation.rs:656-682): the whole quadtree; XrayTiles.write puts it on disk, and so does
+        this call when output_directory is given (PNGs as `png` says: "stored" or "deflate")."""
         xt = self.xray_tiles(tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background, root_node_id,
                              max_workspace_bytes, min_intensity, max_intensity, binning)
         xt.build_parents()
+        if output_directory is not None:
+            xt.write(output_directory, png=png)
         return xt
 
     def render(self, frusta, width, height, point_size=1.0, gamma=1.0, max_nodes=0, depth=False, max_workspace_bytes=None):
@@ -1379,9 +1390,10 @@ def xray_merge_check(parts):
     return level.value, tuple(rect)
 
 
-def merge_xray_quadtrees(ctx, input_directories, output_directory, background="white"):
+def merge_xray_quadtrees(ctx, input_directories, output_directory, background="white", png="stored"):
     """The reference's merge_xray_quadtrees binary: every partial quadtree of input_directories merged into
-    output_directory (which may be one of them); returns the merged XrayTiles."""
+    output_directory (which may be one of them); returns the merged XrayTiles. `png` ("stored" or "deflate") applies to
+    the levels the merge builds; the parts' files are copied as they are."""
     for d in input_directories:
         if not os.path.exists(d):
             raise FileNotFoundError(f"Input directory {str(d)!r} doesn't exist.")
@@ -1390,8 +1402,14 @@ def merge_xray_quadtrees(ctx, input_directories, output_directory, background="w
     os.makedirs(output_directory, exist_ok=True)
     parts = [p for d in input_directories for p in ctx.xray_open(d)]
     merged = ctx.xray_merge(parts, background)
-    merged.write(output_directory)
+    merged.write(output_directory, png=png)
     return merged
+
+
+def _png_mode(png):
+    if png not in ("stored", "deflate"):
+        raise ValueError(f"unknown png mode {png!r} (stored or deflate)")
+    return L.XRAY_PNG_STORED if png == "stored" else L.XRAY_PNG_DEFLATE
 
 
 def png_decode(data):
@@ -1419,18 +1437,39 @@ def xray_lanczos_taps(tile_size_px):
     return left[:W], count[:W], w[:W]
 
 
-def xray_png_encode(rgba):
-    """pcv_xray_png_encode (host only): an (h, w, 4) uint8 image as PNG bytes (stored deflate, filter 0)."""
+def xray_png_encode(rgba, png="stored"):
+    """pcv_xray_png_encode_ex (host only): an (h, w, 4) uint8 image as PNG bytes; "stored" (filter 0, stored deflate
+    blocks: pcv_xray_png_encode) or "deflate" (Sub / Up filters, run-length deflate: the stream of include/pcv_hip.h)."""
     img = np.ascontiguousarray(rgba, dtype=np.uint8)
     h, w = int(img.shape[0]), int(img.shape[1])
     lib = L.load_library()
     need = C.c_uint64()
-    rc = lib.pcv_xray_png_encode(img.ctypes.data, w, h, None, 0, C.byref(need))
+    if png == "stored":
+        rc = lib.pcv_xray_png_encode(img.ctypes.data, w, h, None, 0, C.byref(need))
+    else:
+        rc = lib.pcv_xray_png_encode_ex(img.ctypes.data, w, h, _png_mode(png), None, 0, C.byref(need))
     if rc != L.PCV_OK:
         raise L.PcvError(rc, f"pcv_xray_png_encode({w} x {h})")
     out = np.zeros(need.value, dtype=np.uint8)
-    lib.pcv_xray_png_encode(img.ctypes.data, w, h, out.ctypes.data, out.nbytes, C.byref(need))
+    lib.pcv_xray_png_encode_ex(img.ctypes.data, w, h, _png_mode(png), out.ctypes.data, out.nbytes, C.byref(need))
     return out.tobytes()
+
+
+def _split_files(buf, offsets):
+    return [buf[int(offsets[i]):int(offsets[i + 1])].tobytes() for i in range(len(offsets) - 1)]
+
+
+def xray_png_encode_tiles(ctx, tiles, chunk_tiles=0):
+    """pcv_xray_png_encode_tiles: a (count, W, W, 4) uint8 array through the device encoder of the "deflate" mode; the PNG
+    files as a list of bytes. chunk_tiles: tiles per device chunk (0: the context's download chunk)."""
+    img = np.ascontiguousarray(tiles, dtype=np.uint8)
+    count, w = int(img.shape[0]), int(img.shape[1])
+    offsets = np.zeros(count + 1, dtype=np.uint64)
+    cap = count * int(ctx.lib.pcv_xray_png_bound(w, w, L.XRAY_PNG_DEFLATE))
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    ctx._check(ctx.lib.pcv_xray_png_encode_tiles(ctx.handle, img.ctypes.data, L.MEM_HOST, w, count, int(chunk_tiles), cap, out.ctypes.data,
+                                                 offsets.ctypes.data))
+    return _split_files(out, offsets)
 
 
 def render_params(width, height, point_size=1.0, gamma=1.0, max_nodes=0, max_workspace_bytes=None):
@@ -1617,10 +1656,31 @@ class XrayTiles:
         self._check(self.lib.pcv_xray_node_images(self.handle, int(first), count, cap, mem, ptr))
         return out
 
-    def write(self, directory):
-        """build_xray_quadtree's output directory: <node>.png per node and the meta file (pcv_xray_write_dir)."""
+    def write(self, directory, png="stored"):
+        """build_xray_quadtree's output directory: <node>.png per node and the meta file (pcv_xray_write_dir_ex). png:
+        "stored" (the default: filter 0, stored deflate blocks) or "deflate" (compressed on the device; same pixels, same
+        file names, same meta file)."""
         self._alive()
-        self._check(self.lib.pcv_xray_write_dir(self.handle, os.fsencode(str(directory))))
+        if png == "stored":
+            self._check(self.lib.pcv_xray_write_dir(self.handle, os.fsencode(str(directory))))
+        else:
+            self._check(self.lib.pcv_xray_write_dir_ex(self.handle, os.fsencode(str(directory)), _png_mode(png)))
+
+    def node_pngs(self, first=0, count=None, png="stored"):
+        """The complete PNG files of nodes [first, first + count) of node_ids as a list of bytes (pcv_xray_node_pngs): what
+        write puts on disk, without a file system. Nodes of opened quadtrees come as their files are."""
+        self._alive()
+        mode = _png_mode(png)
+        if count is None:
+            n = C.c_uint64()
+            self.lib.pcv_xray_nodes(self.handle, C.byref(n), 0, None, None)
+            count = n.value - int(first)
+        count = int(count)
+        offsets = np.zeros(count + 1, dtype=np.uint64)
+        self._check(self.lib.pcv_xray_node_pngs(self.handle, int(first), count, mode, 0, None, offsets.ctypes.data))
+        out = np.zeros(max(int(offsets[count]), 1), dtype=np.uint8)
+        self._check(self.lib.pcv_xray_node_pngs(self.handle, int(first), count, mode, int(offsets[count]), out.ctypes.data, offsets.ctypes.data))
+        return _split_files(out, offsets)
 
     def _check(self, rc):
         if self.ctx is not None:

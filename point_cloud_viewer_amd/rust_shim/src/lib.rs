@@ -738,7 +738,7 @@ pub struct PcvXray {
 extern "C" {
     fn pcv_xray_open_dir(ctx: *mut pcv_ctx, directory: *const std::os::raw::c_char, capacity: u32, parts: *mut *mut PcvXray, num_parts: *mut u32) -> i32;
     fn pcv_xray_merge(ctx: *mut pcv_ctx, parts: *const *mut PcvXray, num_parts: u32, background: u32, out: *mut *mut PcvXray) -> i32;
-    fn pcv_xray_write_dir(x: *mut PcvXray, directory: *const std::os::raw::c_char) -> i32;
+    fn pcv_xray_write_dir_ex(x: *mut PcvXray, directory: *const std::os::raw::c_char, mode: i32) -> i32;
     fn pcv_xray_free(x: *mut PcvXray);
 }
 
@@ -747,6 +747,12 @@ extern "C" {
 /// of the inputs. `transparent_background` is `--tile-background-color transparent`. Errors carry the library's message,
 /// which for the reference's own checks is the reference's text.
 pub fn merge_xray_quadtrees(device: i32, input_directories: &[std::path::PathBuf], output_directory: &std::path::Path, transparent_background: bool) -> std::io::Result<()> {
+    merge_xray_quadtrees_png(device, input_directories, output_directory, transparent_background, false)
+}
+
+/// `merge_xray_quadtrees` with the PNG mode of the levels the merge builds: `deflate` compresses them on the device
+/// (PCV_XRAY_PNG_DEFLATE: Sub / Up filters, run-length deflate); the parts' files are copied as they are either way.
+pub fn merge_xray_quadtrees_png(device: i32, input_directories: &[std::path::PathBuf], output_directory: &std::path::Path, transparent_background: bool, deflate: bool) -> std::io::Result<()> {
     use std::os::unix::ffi::OsStrExt;
     let c = |p: &std::path::Path| std::ffi::CString::new(p.as_os_str().as_bytes()).expect("path with a NUL byte");
     let ctx = HipContext::new(device).map_err(|e| std::io::Error::new(std::io::ErrorKind::Other, e))?;
@@ -772,7 +778,7 @@ pub fn merge_xray_quadtrees(device: i32, input_directories: &[std::path::PathBuf
     }
     if rc == 0 {
         std::fs::create_dir_all(output_directory)?;
-        rc = unsafe { pcv_xray_write_dir(merged, c(output_directory).as_ptr()) };
+        rc = unsafe { pcv_xray_write_dir_ex(merged, c(output_directory).as_ptr(), deflate as i32) };
     }
     let message = if rc == 0 { String::new() } else { unsafe { CStr::from_ptr(pcv_last_error(ctx.0)) }.to_string_lossy().into_owned() };
     unsafe {
