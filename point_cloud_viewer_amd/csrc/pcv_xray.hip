@@ -1,6 +1,7 @@
-// pcv_xray.hip — xray's build_xray_quadtree (xray/src/generation.rs:557-616) on the device: the leaf level rasterised
-// straight from batched point queries (pcv_query.hip), one per octree of the run, without materialising their points, then
-// every parent level (second half of the file) and the quadtree directory.
+// pcv_xray.hip — xray's build_xray_quadtree (xray/src/generation.rs:557-616) on the device, the leaf level: rasterised
+// straight from batched point queries (pcv_query.hip), one per octree of the run, without materialising their points. The
+// parent levels and the merge are pcv_xray_pyramid.hip, node images and the quadtree directory pcv_xray_files.hip; the
+// handle they share (pcv_xray_obj.h) is made, listed and freed here.
 //
 //   host   leaf geometry   get_bounding_box :550 (Aabb::transform, src/geometry/aabb.rs:58-66),
 //                          find_quadtree_bounding_rect_and_levels :515, Node::from_node_id_and_root_bounding_rect and
@@ -34,15 +35,13 @@
 
 #include "pcv_query_dev.h"
 #include "pcv_switches.h"
-#include "pcv_xray_png.h"
+#include "pcv_xray_obj.h"
 
 namespace {
 
-constexpr uint32_t kBlk = 32;  // pixel block edge: one accumulation workgroup per (tile, 32 x 32 pixels)
 constexpr uint32_t kBlkPx = kBlk * kBlk;
 constexpr uint32_t kZWords = 33;  // 1 056 bits per pixel: z buckets 0 ..= 1024 (NUM_Z_BUCKETS = 1024, :31)
 constexpr uint32_t kZMax = kZWords * 32 - 1;
-constexpr uint32_t kMaxTilePx = 1u << 15;
 constexpr uint64_t kDefaultWorkspace = 2ull << 30;
 constexpr uint64_t kMaxGroupBuckets = 1ull << 30;  // (tiles of a group) x blocks per tile: u32 bucket indices
 
@@ -630,15 +629,6 @@ __global__ __launch_bounds__(kSortThreads) void xray_sorted_kernel(XrayAccArgs a
 }
 
 // ---- host: quadtree geometry ----------------------------------------------------------------------------------------
-struct LeafGeometry {
-  double rect[3];  // bounding rect: min x, min y, edge
-  uint32_t deepest_level;
-  double bbox_min[3], bbox_max[3];  // get_bounding_box
-  std::vector<uint64_t> index;      // leaf node indices at deepest_level, get_nodes_at_level order
-  std::vector<double> rect_min;     // 2 per leaf
-  double leaf_edge;
-};
-
 int fail_msg(char* err, uint64_t errcap, const std::string& m) {
   if (err && errcap) std::snprintf(err, errcap, "%s", m.c_str());
   return PCV_E_INVALID;
@@ -775,57 +765,30 @@ void tile_obb(const double* iso, const double mn[3], const double mx[3], double 
 
 }  // namespace
 
-// Every live pcv_xray by address with a serial number of its own: a merged quadtree refers to its parts, and asks here
-// whether a part is still the object it was given before it touches it (pcv_xray_merge)
+// ---- the registry of live objects (pcv_xray_obj.h) -------------------------------------------------------------------
 namespace {
 std::mutex g_xray_mu;
 std::unordered_map<const pcv_xray*, uint64_t> g_xray_live;
 uint64_t g_xray_serial = 0;
 }  // namespace
 
-enum XrayKind : uint32_t { kXrayBuilt = 0, kXrayOpened = 1, kXrayMerged = 2 };
-
-struct XrayPartRef {  // one part of a merged quadtree: its nodes are [first, first + count) of the merged node list
-  pcv_xray* part;
-  uint64_t serial, first, count;
-};
-
-struct pcv_xray {
-  pcv_xray() {
-    std::lock_guard<std::mutex> g(g_xray_mu);
-    g_xray_live[this] = serial = ++g_xray_serial;
-  }
-  ~pcv_xray() {
-    std::lock_guard<std::mutex> g(g_xray_mu);
-    g_xray_live.erase(this);
-  }
-  uint64_t serial = 0;
-  XrayKind kind = kXrayBuilt;
-  // opened (pcv_xray_open_dir) and merged (pcv_xray_merge) quadtrees: the node list itself; of `geo` only deepest_level
-  // and rect are set (the meta's bounding rect), geo.index / created list the nodes at deepest_level
-  std::vector<uint32_t> node_level;
-  std::vector<uint64_t> node_index;
-  uint64_t root_count = 0;   // nodes at the minimum level (a merge needs exactly one, or no node at all)
-  std::string dir;           // opened: the directory the PNGs are read from
-  std::vector<XrayPartRef> parts;  // merged; the new levels follow the parts' nodes and live in d_parents
-  pcv_ctx* ctx = nullptr;    // null: opened without a context (host only)
-  uint32_t W = 0;
-  LeafGeometry geo;
-  uint32_t root_level = 0;
-  uint64_t root_index = 0;
-  uint32_t bg = 0;                // tile_background_color.to_u8(), packed RGBA8
-  std::vector<uint64_t> created;  // positions in the leaf list
-  std::vector<uint64_t> kept, drawn;
-  std::vector<uint64_t> negative;  // colored_with_intensity: kept points with intensity < 0 per created tile
-  uint32_t* d_images = nullptr;
-  // parent levels (pcv_xray_build_parents): the node list after the created leaves, deepest - 1 up to root_level, each
-  // level in ascending index; level_first[k] is the first parent of level deepest - 1 - k in that list
-  bool parents_built = false;
-  std::vector<uint32_t> parent_level;
-  std::vector<uint64_t> parent_index;
-  std::vector<uint64_t> level_first;
-  uint32_t* d_parents = nullptr;
-};
+pcv_xray::pcv_xray() {
+  std::lock_guard<std::mutex> g(g_xray_mu);
+  g_xray_live[this] = serial = ++g_xray_serial;
+}
+pcv_xray::~pcv_xray() {
+  std::lock_guard<std::mutex> g(g_xray_mu);
+  g_xray_live.erase(this);
+}
+bool xray_is_live(const pcv_xray* x) {
+  std::lock_guard<std::mutex> g(g_xray_mu);
+  return g_xray_live.count(x) != 0;
+}
+bool xray_part_alive(const XrayPartRef& r) {
+  std::lock_guard<std::mutex> g(g_xray_mu);
+  auto it = g_xray_live.find(r.part);
+  return it != g_xray_live.end() && it->second == r.serial;
+}
 
 extern "C" int pcv_xray_leaf_tiles(uint32_t tile_size_px, double pixel_size_m, const double bbox_min[3], const double bbox_max[3],
                                    const double* query_from_global, uint32_t root_level, uint64_t root_index, uint64_t capacity,
@@ -889,14 +852,6 @@ extern "C" void pcv_xray_free(pcv_xray* x) {
     x->ctx->dev_free(x->d_parents);
   }
   delete x;
-}
-
-// a failure on a handle that may have no context (opened host only): the message goes where the caller can read it
-static int xray_fail(const pcv_xray* x, int code, const std::string& msg) {
-  return x->ctx ? x->ctx->fail(code, msg) : pcv_host_fail(code, msg);
-}
-static int xray_not_built(const pcv_xray* x, const char* what) {
-  return xray_fail(x, PCV_E_INVALID, std::string("xray: ") + what + " needs a quadtree built by pcv_xray_run, not an opened or merged one");
 }
 
 // PointCloudClientBuilder::build's bounding box (point_cloud_client/src/lib.rs:101-125): the first octree's meta box, grown
@@ -985,29 +940,50 @@ extern "C" int pcv_xray_plan_groups(const uint64_t* kept, uint64_t num_tiles, co
   return PCV_OK;
 }
 
-// the leaf level over K octrees (K = 1: pcv_xray_run): one shape list, one query batch per octree, every raster pass one
-// launch per tile group over the chunks of all K batches
-static int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pcv_xray_params* p, const pcv_xray_coloring* col,
-                    pcv_xray* x) {
+// ---- the leaf level over K octrees (K = 1: pcv_xray_run) ----------------------------------------------------------------
+// One shape list, one query batch per octree, every raster pass one launch per tile group over the chunks of all K
+// batches: xray_query_tiles, xray_plan_tiles, xray_upload_tables, xray_raster_groups, in that order.
+
+namespace {
+
+// The accumulation a run takes. colored_with_intensity, and colored with binning, take the sorted accumulation
+// (xray_sorted); binning is ignored by xray and height_stddev (attributes() :133).
+struct XrayAccum {
+  const void* kernel;  // for the occupancy query
+  uint32_t threads;
+  int prof_id;
+  void (*launch)(uint32_t grid, hipStream_t stream, const XrayAccArgs& a, uint64_t* rec, int64_t* recb, uint32_t sort_cap, const uint8_t* table);
+};
+template <bool BINNED>
+void launch_sorted(uint32_t grid, hipStream_t stream, const XrayAccArgs& a, uint64_t* rec, int64_t* recb, uint32_t sort_cap, const uint8_t*) {
+  hipLaunchKernelGGL(xray_sorted_kernel<BINNED>, dim3(grid), dim3(kSortThreads), 0, stream, a, rec, recb, sort_cap);
+}
+template <int STRAT, int NT>
+void launch_accum(uint32_t grid, hipStream_t stream, const XrayAccArgs& a, uint64_t*, int64_t*, uint32_t, const uint8_t* table) {
+  hipLaunchKernelGGL((xray_accum_kernel<STRAT, NT>), dim3(grid), dim3(NT), 0, stream, a, table);
+}
+XrayAccum xray_accum_of(uint32_t strategy, bool binned) {
+  if (binned) return {(const void*)xray_sorted_kernel<true>, kSortThreads, PCV_K_XRAY_SORTED, launch_sorted<true>};
+  if (strategy == PCV_XRAY_COLORED_WITH_INTENSITY) return {(const void*)xray_sorted_kernel<false>, kSortThreads, PCV_K_XRAY_SORTED, launch_sorted<false>};
+  if (strategy == PCV_XRAY_XRAY) return {(const void*)xray_accum_kernel<PCV_XRAY_XRAY, 1024>, 1024, PCV_K_XRAY_ACCUM, launch_accum<PCV_XRAY_XRAY, 1024>};
+  if (strategy == PCV_XRAY_COLORED) return {(const void*)xray_accum_kernel<PCV_XRAY_COLORED, 256>, 256, PCV_K_XRAY_ACCUM, launch_accum<PCV_XRAY_COLORED, 256>};
+  return {(const void*)xray_accum_kernel<PCV_XRAY_HEIGHT_STDDEV, 256>, 256, PCV_K_XRAY_ACCUM, launch_accum<PCV_XRAY_HEIGHT_STDDEV, 256>};
+}
+
+// the same shapes through every octree (try_for_each_batch's jobs, src/iterator.rs:262-270); all K batches stay alive
+// until the raster passes are done
+struct XrayBatches {
+  std::vector<pcv_query_batch*> b;
+  ~XrayBatches() {
+    for (pcv_query_batch* q : b) pcv_query_batch_free(q);
+  }
+};
+
+// step 1: one shape per leaf tile (xray_from_points :470-476) and the K batch queries
+int xray_query_tiles(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pcv_xray_params* p, const LeafGeometry& g,
+                            XrayBatches* batches) {
   const bool filter = p->interval_attribute != nullptr;
-  // colored_with_intensity, and colored with binning, take the sorted accumulation (xray_sorted); binning is ignored by
-  // xray and height_stddev (attributes() :133)
-  const bool cwi = p->strategy == PCV_XRAY_COLORED_WITH_INTENSITY;
-  const bool binned = coloring_binned(p, col);
-  const bool sorted = cwi || binned;
-  char err[256] = {0};
-  double bmin[3], bmax[3];
-  union_box(trees, K, bmin, bmax);
-  int rc = leaf_geometry(p->tile_size_px, p->pixel_size_m, bmin, bmax, p->has_query_from_global ? p->query_from_global : nullptr,
-                         p->root_level, p->root_index, true, &x->geo, err, sizeof(err));
-  if (rc) return ctx->fail(rc, err);
-  const LeafGeometry& g = x->geo;
-  const uint32_t S = (uint32_t)g.index.size(), W = p->tile_size_px;
-  x->W = W;
-  x->root_level = p->root_level;
-  x->root_index = p->root_index;
-  x->bg = p->background == PCV_XRAY_BG_TRANSPARENT ? 0x00ffffffu : 0xffffffffu;  // TRANSPARENT / WHITE .to_u8()
-  // one shape per leaf tile (xray_from_points :470-476)
+  const uint32_t S = (uint32_t)g.index.size();
   std::vector<pcv_shape> shapes(S);
   for (uint32_t i = 0; i < S; ++i) {
     double mn[3], mx[3];
@@ -1032,56 +1008,52 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pc
     }
   }
   pcv_shapes* sh = nullptr;
-  if ((rc = pcv_shapes_create(ctx, shapes.data(), S, &sh))) return rc;
-  // the same shapes through every octree (try_for_each_batch's jobs, src/iterator.rs:262-270); all K batches stay alive
-  // until the raster passes are done
-  struct BatchGuard {
-    std::vector<pcv_query_batch*> b;
-    ~BatchGuard() {
-      for (pcv_query_batch* q : b) pcv_query_batch_free(q);
-    }
-  } guard;
-  guard.b.reserve(K);
+  int rc = pcv_shapes_create(ctx, shapes.data(), S, &sh);
+  if (rc) return rc;
+  batches->b.reserve(K);
   for (uint32_t t = 0; t < K && rc == PCV_OK; ++t) {
     pcv_query_batch* b = nullptr;
     rc = pcv_query_batch_run(ctx, sh, trees[t], filter ? ivals.data() : nullptr, nullptr, &b);
-    if (rc == PCV_OK) guard.b.push_back(b);
+    if (rc == PCV_OK) batches->b.push_back(b);
   }
   pcv_shapes_free(sh);
-  if (rc) return rc;
-  const std::vector<pcv_query_batch*>& batches = guard.b;
+  return rc;
+}
+
+// step 2: the created tiles (into x), their groups and, per group, the octrees that have chunks for its shapes, in list
+// order, their chunk ranges end to end (u64 prefix)
+struct XrayPlan {
+  std::vector<int32_t> created_of_shape;
+  std::vector<uint64_t> group_first;  // created tiles [group_first[g], group_first[g + 1]) are group g
+  uint64_t max_pts = 0, max_tiles = 0;
+  std::vector<XrayTreeChunks> trees;
+  std::vector<size_t> tree_first;  // group g's entries of `trees`: [tree_first[g], tree_first[g + 1])
+  std::vector<uint64_t> group_chunks;
+};
+void xray_created_tiles(const std::vector<pcv_query_batch*>& batches, uint32_t S, pcv_xray* x, XrayPlan* pl) {
   // a tile is created iff the queries kept a point (PointStream::callback never delivers an empty batch,
   // iterator.rs:148-151); kept is the sum over the octrees
-  std::vector<int32_t> created_of_shape(S, -1);
+  pl->created_of_shape.assign(S, -1);
   for (uint32_t s = 0; s < S; ++s) {
     uint64_t k = 0;
     for (const pcv_query_batch* b : batches) k += b->seg_off[b->shape_first[s + 1]] - b->seg_off[b->shape_first[s]];
     if (k == 0) continue;
-    created_of_shape[s] = (int32_t)x->created.size();
+    pl->created_of_shape[s] = (int32_t)x->created.size();
     x->created.push_back(s);
     x->kept.push_back(k);
   }
-  const uint64_t nc = x->created.size();
-  x->drawn.assign(nc, 0);
-  x->negative.assign(nc, 0);
-  if (nc == 0) return PCV_OK;
-  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const uint32_t nbx = (W + kBlk - 1) / kBlk, nblocks = nbx * nbx;
-  const uint64_t img_px = (uint64_t)W * W;
-  std::vector<uint64_t> group_first;
-  uint64_t max_pts = 0, max_tiles = 0;
-  {
-    char m[256] = {0};
-    if ((rc = plan_groups(x->kept.data(), nc, x->created.data(), W, p, col, group_first, &max_pts, &max_tiles, m, sizeof(m))))
-      return ctx->fail(rc, m);
-  }
-  if ((rc = ctx->dev_alloc((void**)&x->d_images, 4 * img_px * nc))) return rc;
-  // per group, the octrees that have chunks for its shapes, in list order, their chunk ranges end to end (u64 prefix)
-  std::vector<XrayTreeChunks> h_trees;
-  std::vector<size_t> tree_first(1, 0);
-  std::vector<uint64_t> group_chunks;
-  for (size_t gi = 0; gi + 1 < group_first.size(); ++gi) {
-    const uint64_t s0 = x->created[group_first[gi]], s1 = x->created[group_first[gi + 1] - 1] + 1;
+  x->drawn.assign(x->created.size(), 0);
+  x->negative.assign(x->created.size(), 0);
+}
+int xray_plan_tiles(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pcv_xray_params* p, const pcv_xray_coloring* col,
+                           const std::vector<pcv_query_batch*>& batches, bool reads_intensity, const pcv_xray* x, XrayPlan* pl) {
+  char m[256] = {0};
+  if (int rc = plan_groups(x->kept.data(), x->created.size(), x->created.data(), x->W, p, col, pl->group_first, &pl->max_pts, &pl->max_tiles, m,
+                           sizeof(m)))
+    return ctx->fail(rc, m);
+  pl->tree_first.assign(1, 0);
+  for (size_t gi = 0; gi + 1 < pl->group_first.size(); ++gi) {
+    const uint64_t s0 = x->created[pl->group_first[gi]], s1 = x->created[pl->group_first[gi + 1] - 1] + 1;
     uint64_t n = 0;
     for (uint32_t t = 0; t < K; ++t) {
       const pcv_query_batch* b = batches[t];
@@ -1092,55 +1064,76 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pc
       e.keep = (decltype(e.keep))b->d_keep;
       e.xyz = (decltype(e.xyz))trees[t]->d_xyz;
       e.rgb = (decltype(e.rgb))trees[t]->d_rgb;
-      e.inten = sorted ? (decltype(e.inten))trees[t]->d_int : nullptr;
+      e.inten = reads_intensity ? (decltype(e.inten))trees[t]->d_int : nullptr;
       e.c0 = c0;
       e.first = n;
-      h_trees.push_back(e);
+      pl->trees.push_back(e);
       n += c1 - c0;
     }
-    tree_first.push_back(h_trees.size());
-    group_chunks.push_back(n);
+    pl->tree_first.push_back(pl->trees.size());
+    pl->group_chunks.push_back(n);
   }
-  PcvScratch sc(ctx);
-  int32_t* d_cos;
-  XrayTileDev* d_tiles;
-  XrayTreeChunks* d_trees;
-  uint8_t* d_table;
-  unsigned long long* d_drawn;
-  uint32_t* d_counts;
-  uint64_t *d_off, *d_rec;
-  double* d_recz = nullptr;
-  int64_t* d_recb = nullptr;
-  unsigned long long* d_neg = nullptr;
-  const uint64_t max_buckets = max_tiles * nblocks;
-  if ((rc = sc.get(&d_cos, S)) || (rc = sc.get(&d_tiles, nc)) || (rc = sc.get(&d_trees, std::max<size_t>(h_trees.size(), 1))) ||
-      (rc = sc.get(&d_table, kZWords * 32 + 1)) || (rc = sc.get(&d_drawn, nc)) || (rc = sc.get(&d_counts, max_buckets)) ||
-      (rc = sc.get(&d_off, max_buckets + 1)) || (rc = sc.get(&d_rec, std::max<uint64_t>(max_pts, 1))))
+  return PCV_OK;
+}
+
+// step 3: the device tables of the raster passes, released with the scratch
+struct XrayTables {
+  explicit XrayTables(pcv_ctx* ctx) : sc(ctx) {}
+  PcvScratch sc;
+  int32_t* cos = nullptr;
+  XrayTileDev* tiles = nullptr;
+  XrayTreeChunks* trees = nullptr;
+  uint8_t* table = nullptr;
+  unsigned long long *drawn = nullptr, *neg = nullptr;
+  uint32_t* counts = nullptr;
+  uint64_t *off = nullptr, *rec = nullptr;
+  double* recz = nullptr;
+  int64_t* recb = nullptr;
+  std::vector<XrayTileDev> h_tiles;  // what the uploads read: alive until the raster passes have synchronised
+  uint8_t h_table[kZWords * 32 + 1];
+};
+int xray_upload_tables(pcv_ctx* ctx, const pcv_xray_params* p, bool binned, const pcv_xray* x, const XrayPlan& pl, uint32_t nblocks,
+                              XrayTables* t) {
+  const uint64_t nc = x->created.size(), S = pl.created_of_shape.size();
+  const uint64_t max_buckets = pl.max_tiles * nblocks, max_pts = std::max<uint64_t>(pl.max_pts, 1);
+  PcvScratch& sc = t->sc;
+  int rc;
+  if ((rc = sc.get(&t->cos, S)) || (rc = sc.get(&t->tiles, nc)) || (rc = sc.get(&t->trees, std::max<size_t>(pl.trees.size(), 1))) ||
+      (rc = sc.get(&t->table, kZWords * 32 + 1)) || (rc = sc.get(&t->drawn, nc)) || (rc = sc.get(&t->counts, max_buckets)) ||
+      (rc = sc.get(&t->off, max_buckets + 1)) || (rc = sc.get(&t->rec, max_pts)))
     return rc;
-  if (p->strategy == PCV_XRAY_HEIGHT_STDDEV && (rc = sc.get(&d_recz, std::max<uint64_t>(max_pts, 1)))) return rc;
-  if (binned && (rc = sc.get(&d_recb, std::max<uint64_t>(max_pts, 1)))) return rc;
-  if (cwi && (rc = sc.get(&d_neg, nc))) return rc;
-  std::vector<XrayTileDev> h_tiles(nc);
+  if (p->strategy == PCV_XRAY_HEIGHT_STDDEV && (rc = sc.get(&t->recz, max_pts))) return rc;
+  if (binned && (rc = sc.get(&t->recb, max_pts))) return rc;
+  if (p->strategy == PCV_XRAY_COLORED_WITH_INTENSITY && (rc = sc.get(&t->neg, nc))) return rc;
+  t->h_tiles.resize(nc);
   for (uint64_t c = 0; c < nc; ++c) {
     double mn[3], mx[3];
-    tile_box(g, x->created[c], mn, mx);
+    tile_box(x->geo, x->created[c], mn, mx);
     for (int a = 0; a < 3; ++a) {
-      h_tiles[c].min[a] = mn[a];
-      h_tiles[c].diag[a] = mx[a] - mn[a];  // Aabb::diag
+      t->h_tiles[c].min[a] = mn[a];
+      t->h_tiles[c].diag[a] = mx[a] - mn[a];  // Aabb::diag
     }
   }
-  uint8_t table[kZWords * 32 + 1];
-  xray_value_table(table);
-  PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_cos, created_of_shape.data(), 4 * (size_t)S, hipMemcpyHostToDevice, ctx->stream));
-  PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_tiles, h_tiles.data(), sizeof(XrayTileDev) * nc, hipMemcpyHostToDevice, ctx->stream));
-  if (!h_trees.empty())
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_trees, h_trees.data(), sizeof(XrayTreeChunks) * h_trees.size(), hipMemcpyHostToDevice, ctx->stream));
-  PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_table, table, sizeof(table), hipMemcpyHostToDevice, ctx->stream));
-  PCV_HIP_CHECK(ctx, hipMemsetAsync(d_drawn, 0, 8 * nc, ctx->stream));
-  if (d_neg) PCV_HIP_CHECK(ctx, hipMemsetAsync(d_neg, 0, 8 * nc, ctx->stream));
+  xray_value_table(t->h_table);
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(t->cos, pl.created_of_shape.data(), 4 * (size_t)S, hipMemcpyHostToDevice, ctx->stream));
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(t->tiles, t->h_tiles.data(), sizeof(XrayTileDev) * nc, hipMemcpyHostToDevice, ctx->stream));
+  if (!pl.trees.empty())
+    PCV_HIP_CHECK(ctx, hipMemcpyAsync(t->trees, pl.trees.data(), sizeof(XrayTreeChunks) * pl.trees.size(), hipMemcpyHostToDevice, ctx->stream));
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(t->table, t->h_table, sizeof(t->h_table), hipMemcpyHostToDevice, ctx->stream));
+  PCV_HIP_CHECK(ctx, hipMemsetAsync(t->drawn, 0, 8 * nc, ctx->stream));
+  if (t->neg) PCV_HIP_CHECK(ctx, hipMemsetAsync(t->neg, 0, 8 * nc, ctx->stream));
+  return PCV_OK;
+}
+
+// step 4: per tile group count, scan, scatter and accumulate, then the per-tile counters
+int xray_raster_groups(pcv_ctx* ctx, const pcv_xray_params* p, const pcv_xray_coloring* col, bool binned, pcv_xray* x, const XrayPlan& pl,
+                              uint32_t nbx, XrayTables& t) {
+  const bool cwi = p->strategy == PCV_XRAY_COLORED_WITH_INTENSITY;
+  const uint32_t W = x->W, nblocks = nbx * nbx;
+  const uint64_t nc = x->created.size();
   XrayBinArgs ba{};
-  ba.created_of_shape = d_cos;
-  ba.tiles = d_tiles;
+  ba.created_of_shape = t.cos;
+  ba.tiles = t.tiles;
   ba.W = W;
   ba.nbx = nbx;
   ba.nblocks = nblocks;
@@ -1149,13 +1142,13 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pc
   for (int i = 0; i < 7; ++i) ba.iso[i] = p->has_query_from_global ? p->query_from_global[i] : 0.0;
   ba.binned = binned ? 1 : 0;
   ba.bin_size = binned ? col->bin_size : 1.0;
-  ba.negative = d_neg;
+  ba.negative = t.neg;
   XrayAccArgs aa{};
-  aa.rec = d_rec;
-  aa.recz = d_recz;
-  aa.offsets = d_off;
+  aa.rec = t.rec;
+  aa.recz = t.recz;
+  aa.offsets = t.off;
   aa.image = x->d_images;
-  aa.drawn = d_drawn;
+  aa.drawn = t.drawn;
   aa.W = W;
   aa.nbx = nbx;
   aa.nblocks = nblocks;
@@ -1175,72 +1168,84 @@ static int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pc
   }
   // accumulation: as many workgroups as are resident at once, striding over the group's buckets (the experiment build
   // can lower the grid, to test the stride with few tiles)
+  const XrayAccum acc = xray_accum_of(p->strategy, binned);
   int cus = 0, per_cu = 0;
   PCV_HIP_CHECK(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-  if (binned)
-    PCV_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xray_sorted_kernel<true>, kSortThreads, 0));
-  else if (sorted)
-    PCV_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xray_sorted_kernel<false>, kSortThreads, 0));
-  else if (p->strategy == PCV_XRAY_XRAY)
-    PCV_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xray_accum_kernel<PCV_XRAY_XRAY, 1024>, 1024, 0));
-  else if (p->strategy == PCV_XRAY_COLORED)
-    PCV_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xray_accum_kernel<PCV_XRAY_COLORED, 256>, 256, 0));
-  else
-    PCV_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xray_accum_kernel<PCV_XRAY_HEIGHT_STDDEV, 256>, 256, 0));
+  PCV_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, acc.kernel, (int)acc.threads, 0));
   uint64_t accum_grid = (uint64_t)std::max(cus, 1) * (uint64_t)std::max(per_cu, 1);
   if (pcv_switches().xray_accum_grid) accum_grid = pcv_switches().xray_accum_grid;
-  for (size_t gi = 0; gi + 1 < group_first.size(); ++gi) {
-    const uint64_t f = group_first[gi], l = group_first[gi + 1];  // created tiles [f, l)
-    ba.trees = d_trees + tree_first[gi];
-    ba.ntrees = (uint32_t)(tree_first[gi + 1] - tree_first[gi]);
-    ba.nchunks = group_chunks[gi];
+  for (size_t gi = 0; gi + 1 < pl.group_first.size(); ++gi) {
+    const uint64_t f = pl.group_first[gi], l = pl.group_first[gi + 1];  // created tiles [f, l)
+    ba.trees = t.trees + pl.tree_first[gi];
+    ba.ntrees = (uint32_t)(pl.tree_first[gi + 1] - pl.tree_first[gi]);
+    ba.nchunks = pl.group_chunks[gi];
     ba.created0 = (uint32_t)f;
     aa.created0 = (uint32_t)f;
     const uint64_t nb = (l - f) * nblocks;
     const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((ba.nchunks + 3) / 4, 1u << 16));
-    PCV_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, 4 * nb, ctx->stream));
+    PCV_HIP_CHECK(ctx, hipMemsetAsync(t.counts, 0, 4 * nb, ctx->stream));
     {
       PcvProf prof(ctx, PCV_K_XRAY_BIN);
-      hipLaunchKernelGGL(xray_bin_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, ba, d_counts, (const uint64_t*)nullptr,
+      hipLaunchKernelGGL(xray_bin_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, ba, t.counts, (const uint64_t*)nullptr,
                          (uint64_t*)nullptr, (double*)nullptr, (int64_t*)nullptr);
     }
     PCV_HIP_CHECK(ctx, hipGetLastError());
     {
       PcvProf prof(ctx, PCV_K_QUERY_BATCH_SCAN);
-      if ((rc = pcv_batch_scan(ctx, sc, d_counts, nb, d_off))) return rc;
+      if (int rc = pcv_batch_scan(ctx, t.sc, t.counts, nb, t.off)) return rc;
     }
-    PCV_HIP_CHECK(ctx, hipMemsetAsync(d_counts, 0, 4 * nb, ctx->stream));
+    PCV_HIP_CHECK(ctx, hipMemsetAsync(t.counts, 0, 4 * nb, ctx->stream));
     {
       PcvProf prof(ctx, PCV_K_XRAY_SCATTER);
       XrayBinArgs bs = ba;
       bs.negative = nullptr;  // counted once, in the count pass
-      hipLaunchKernelGGL(xray_bin_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, bs, d_counts, (const uint64_t*)d_off, d_rec, d_recz,
-                         d_recb);
+      hipLaunchKernelGGL(xray_bin_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, bs, t.counts, (const uint64_t*)t.off, t.rec, t.recz,
+                         t.recb);
     }
     PCV_HIP_CHECK(ctx, hipGetLastError());
     aa.nbuckets = (uint32_t)nb;
     {
-      PcvProf prof(ctx, sorted ? PCV_K_XRAY_SORTED : PCV_K_XRAY_ACCUM);
-      const uint32_t ag = (uint32_t)std::min<uint64_t>(nb, accum_grid);
-      if (binned)
-        hipLaunchKernelGGL(xray_sorted_kernel<true>, dim3(ag), dim3(kSortThreads), 0, ctx->stream, aa, d_rec, d_recb, sort_cap);
-      else if (sorted)
-        hipLaunchKernelGGL(xray_sorted_kernel<false>, dim3(ag), dim3(kSortThreads), 0, ctx->stream, aa, d_rec, d_recb, sort_cap);
-      else if (p->strategy == PCV_XRAY_XRAY)
-        hipLaunchKernelGGL((xray_accum_kernel<PCV_XRAY_XRAY, 1024>), dim3(ag), dim3(1024), 0, ctx->stream, aa, (const uint8_t*)d_table);
-      else if (p->strategy == PCV_XRAY_COLORED)
-        hipLaunchKernelGGL((xray_accum_kernel<PCV_XRAY_COLORED, 256>), dim3(ag), dim3(256), 0, ctx->stream, aa, (const uint8_t*)d_table);
-      else
-        hipLaunchKernelGGL((xray_accum_kernel<PCV_XRAY_HEIGHT_STDDEV, 256>), dim3(ag), dim3(256), 0, ctx->stream, aa,
-                           (const uint8_t*)d_table);
+      PcvProf prof(ctx, acc.prof_id);
+      acc.launch((uint32_t)std::min<uint64_t>(nb, accum_grid), ctx->stream, aa, t.rec, t.recb, sort_cap, t.table);
     }
     PCV_HIP_CHECK(ctx, hipGetLastError());
   }
-  PCV_HIP_CHECK(ctx, hipMemcpyAsync(x->drawn.data(), d_drawn, 8 * nc, hipMemcpyDeviceToHost, ctx->stream));
-  if (d_neg) PCV_HIP_CHECK(ctx, hipMemcpyAsync(x->negative.data(), d_neg, 8 * nc, hipMemcpyDeviceToHost, ctx->stream));
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(x->drawn.data(), t.drawn, 8 * nc, hipMemcpyDeviceToHost, ctx->stream));
+  if (t.neg) PCV_HIP_CHECK(ctx, hipMemcpyAsync(x->negative.data(), t.neg, 8 * nc, hipMemcpyDeviceToHost, ctx->stream));
   PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // the scratch and the batches are released on return
   return PCV_OK;
 }
+
+int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pcv_xray_params* p, const pcv_xray_coloring* col,
+                    pcv_xray* x) {
+  const bool binned = coloring_binned(p, col);
+  const bool sorted = binned || p->strategy == PCV_XRAY_COLORED_WITH_INTENSITY;
+  char err[256] = {0};
+  double bmin[3], bmax[3];
+  union_box(trees, K, bmin, bmax);
+  int rc = leaf_geometry(p->tile_size_px, p->pixel_size_m, bmin, bmax, p->has_query_from_global ? p->query_from_global : nullptr,
+                         p->root_level, p->root_index, true, &x->geo, err, sizeof(err));
+  if (rc) return ctx->fail(rc, err);
+  const uint32_t W = p->tile_size_px, nbx = (W + kBlk - 1) / kBlk;
+  x->W = W;
+  x->root_level = p->root_level;
+  x->root_index = p->root_index;
+  x->bg = p->background == PCV_XRAY_BG_TRANSPARENT ? 0x00ffffffu : 0xffffffffu;  // TRANSPARENT / WHITE .to_u8()
+  XrayBatches batches;
+  if ((rc = xray_query_tiles(ctx, trees, K, p, x->geo, &batches))) return rc;
+  XrayPlan pl;
+  xray_created_tiles(batches.b, (uint32_t)x->geo.index.size(), x, &pl);
+  const uint64_t nc = x->created.size();
+  if (nc == 0) return PCV_OK;
+  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if ((rc = xray_plan_tiles(ctx, trees, K, p, col, batches.b, sorted, x, &pl))) return rc;
+  if ((rc = ctx->dev_alloc((void**)&x->d_images, 4ull * W * W * nc))) return rc;
+  XrayTables t(ctx);
+  if ((rc = xray_upload_tables(ctx, p, binned, x, pl, nbx * nbx, &t))) return rc;
+  return xray_raster_groups(ctx, p, col, binned, x, pl, nbx, t);
+}
+
+}  // namespace
 
 // the object of a checked run, or nothing (a failed run frees what it allocated)
 static int xray_new(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pcv_xray_params* p, const pcv_xray_coloring* col,
@@ -1390,1399 +1395,16 @@ extern "C" int pcv_xray_images(pcv_xray* x, uint64_t first, uint64_t count, uint
   return PCV_OK;
 }
 
-// ---- parent levels: create_non_leaf_nodes (:656-682), build_node (:726-759), build_parent (:410-450) -------------------
-//
-//   host   parent sets     parent_id of the level below, from deepest - 1 up to root_level (create_non_leaf_nodes)
-//   host   2:1 Lanczos3    the taps of image 0.23.10 imageops::resize(FilterType::Lanczos3) for a square 2W -> W resize,
-//                          as DynamicImage::resize reaches it (sample.rs vertical_sample, then horizontal_sample): a
-//                          restatement of the pinned crate version, computed once per W with libm's sinf
-//   K_xp   xray_parent     per (parent, 32 x 32 output block): the virtual 2W x 2W image of build_parent (children 1, 0,
-//                          3, 2 at (0, 0), (0, W), (W, 0), (W, W); a missing child is the background) over the block's
-//                          window into LDS, the vertical pass into LDS as f32, the horizontal pass, clamp, round, u8
-//
-// Every output pixel is a fixed sequence of f32 multiplies and adds (no FMA: -ffp-contract=off), so the images do not
-// depend on scheduling and equal a host evaluation of the same sequence bit for bit.
-#include <fcntl.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
-#include <atomic>
-#include <mutex>
-#include <thread>
-
-namespace {
-
-constexpr uint32_t kTaps = 12;        // 2 x support 6: taps of an interior output index
-constexpr uint32_t kWin = 2 * (kBlk - 1) + kTaps;  // 74: input rows / columns a 32-pixel output block reads
-
-struct LanczosTap {  // one output index o: input [left, left + count), normalised weights
-  uint32_t left, count;
-  float w[kTaps];
-};
-
-// image::imageops::sample sinc / lanczos3: f32 throughout, sin = libm sinf (what f32::sin calls on linux-gnu)
-float sinc_f32(float t) {
-  if (t == 0.0f) return 1.0f;
-  const float a = t * 3.14159265358979323846264338327950288f;  // f32::consts::PI
-  return ::sinf(a) / a;
-}
-float lanczos3_f32(float x) { return std::fabs(x) < 3.0f ? sinc_f32(x) * sinc_f32(x / 3.0f) : 0.0f; }
-
-// vertical_sample / horizontal_sample's filter table for 2W -> W: ratio 2, support 3 x 2 = 6
-void lanczos_taps(uint32_t W, std::vector<LanczosTap>& taps) {
-  taps.assign(W, LanczosTap{});
-  const float ratio = 2.0f, sratio = 2.0f, support = 3.0f * sratio;
-  const int64_t n = 2 * (int64_t)W;
-  for (uint32_t o = 0; o < W; ++o) {
-    const float c = ((float)o + 0.5f) * ratio;
-    const int64_t left = std::min<int64_t>(std::max<int64_t>((int64_t)std::floor(c - support), 0), n - 1);
-    const int64_t right = std::min<int64_t>(std::max<int64_t>((int64_t)std::ceil(c + support), left + 1), n);
-    const float ci = c - 0.5f;
-    LanczosTap& t = taps[o];
-    t.left = (uint32_t)left;
-    t.count = (uint32_t)(right - left);
-    float sum = 0.0f;
-    for (int64_t i = left; i < right; ++i) {
-      const float w = lanczos3_f32(((float)i - ci) / sratio);
-      t.w[i - left] = w;
-      sum += w;
-    }
-    for (uint32_t k = 0; k < t.count; ++k) t.w[k] /= sum;
-  }
-}
-
-struct XrayParentArgs {
-  const uint32_t* leaves;   // created leaf images, node positions [0, nleaves)
-  const uint32_t* parents;  // parent images, node positions [nleaves, ...)
-  uint64_t nleaves;
-  const int64_t* slots;     // 4 per parent of the level: node position of child c, -1 where it is missing
-  uint32_t* out;            // the level's first parent image
-  uint64_t nparents;
-  const LanczosTap* taps;   // W entries, rows and columns alike
-  uint32_t W, nbx, bg;
-};
-
-__device__ __forceinline__ float4 unpack_f4(uint32_t p) {
-  return make_float4((float)(p & 255u), (float)((p >> 8) & 255u), (float)((p >> 16) & 255u), (float)(p >> 24));
-}
-// horizontal_sample's store: clamp(t, 0, 255) then FloatNearest (round half away from zero) as u8
-__device__ __forceinline__ uint32_t to_u8_round(float t) {
-  t = t < 0.0f ? 0.0f : (t > 255.0f ? 255.0f : t);
-  return (uint32_t)roundf(t);
-}
-
-// 256 threads per (parent, output block); the grid strides over parents x blocks
-__global__ __launch_bounds__(256) void xray_parent_kernel(XrayParentArgs a) {
-  __shared__ uint32_t win[kWin * kWin];   // input window of the virtual image, RGBA8
-  __shared__ float4 mid[kBlk * kWin];     // vertical pass: block rows x window columns, f32 RGBA
-  const uint32_t nblocks = a.nbx * a.nbx;
-  const uint64_t total = a.nparents * nblocks;
-  const uint32_t W = a.W;
-  for (uint64_t b = blockIdx.x; b < total; b += gridDim.x) {
-    const uint64_t parent = b / nblocks;
-    const uint32_t blk = (uint32_t)(b % nblocks), by = blk / a.nbx, bx = blk % a.nbx;
-    const uint32_t oy0 = by * kBlk, ox0 = bx * kBlk;
-    const uint32_t oy1 = min(oy0 + kBlk, W), ox1 = min(ox0 + kBlk, W);  // exclusive
-    const LanczosTap& ty0 = a.taps[oy0];
-    const LanczosTap& ty1 = a.taps[oy1 - 1];
-    const LanczosTap& tx0 = a.taps[ox0];
-    const LanczosTap& tx1 = a.taps[ox1 - 1];
-    const uint32_t row0 = ty0.left, nrow = ty1.left + ty1.count - row0;  // <= kWin: left and right never decrease
-    const uint32_t col0 = tx0.left, ncol = tx1.left + tx1.count - col0;
-    const int64_t* slot = a.slots + 4 * parent;
-    // the window: child pixel or background (build_parent's from_pixel + copy_from)
-    for (uint32_t i = threadIdx.x; i < nrow * ncol; i += blockDim.x) {
-      const uint32_t vy = row0 + i / ncol, vx = col0 + i % ncol;
-      const uint32_t top = vy < W, lft = vx < W;
-      const uint32_t child = lft ? (top ? 1u : 0u) : (top ? 3u : 2u);
-      const int64_t s = slot[child];
-      uint32_t px = a.bg;
-      if (s >= 0) {
-        const uint32_t* img = (uint64_t)s < a.nleaves ? a.leaves + (uint64_t)s * W * W : a.parents + ((uint64_t)s - a.nleaves) * W * W;
-        px = img[(uint64_t)(vy - (top ? 0u : W)) * W + (vx - (lft ? 0u : W))];
-      }
-      win[(i / ncol) * kWin + i % ncol] = px;
-    }
-    __syncthreads();
-    // vertical pass: t = t + p * w in tap order, f32, neither clamped nor rounded
-    for (uint32_t i = threadIdx.x; i < (oy1 - oy0) * ncol; i += blockDim.x) {
-      const uint32_t r = i / ncol, c = i % ncol;
-      const LanczosTap& t = a.taps[oy0 + r];
-      float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      const uint32_t* src = win + (t.left - row0) * kWin + c;
-      for (uint32_t k = 0; k < t.count; ++k) {
-        const float4 p = unpack_f4(src[k * kWin]);
-        const float w = t.w[k];
-        acc.x = acc.x + p.x * w;
-        acc.y = acc.y + p.y * w;
-        acc.z = acc.z + p.z * w;
-        acc.w = acc.w + p.w * w;
-      }
-      mid[r * kWin + c] = acc;
-    }
-    __syncthreads();
-    // horizontal pass over the intermediate, then clamp, round, u8
-    uint32_t* out = a.out + parent * W * W;
-    for (uint32_t i = threadIdx.x; i < kBlkPx; i += blockDim.x) {
-      const uint32_t r = i / kBlk, c = i % kBlk;
-      const uint32_t oy = oy0 + r, ox = ox0 + c;
-      if (oy >= oy1 || ox >= ox1) continue;
-      const LanczosTap& t = a.taps[ox];
-      float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      const float4* src = mid + r * kWin + (t.left - col0);
-      for (uint32_t k = 0; k < t.count; ++k) {
-        const float4 p = src[k];
-        const float w = t.w[k];
-        acc.x = acc.x + p.x * w;
-        acc.y = acc.y + p.y * w;
-        acc.z = acc.z + p.z * w;
-        acc.w = acc.w + p.w * w;
-      }
-      out[(uint64_t)oy * W + ox] = to_u8_round(acc.x) | to_u8_round(acc.y) << 8 | to_u8_round(acc.z) << 16 | to_u8_round(acc.w) << 24;
-    }
-    __syncthreads();  // the next block overwrites the window and the intermediate
-  }
-}
-
-// ---- meta.pb (the PNG encoders live in pcv_png.cpp and pcv_xray_png.hip) -----------------------------------------------
-// rust-protobuf 2.x, proto3: fields in number order, zero scalars omitted, set message fields always written
-void pb_varint(std::vector<uint8_t>& o, uint64_t v) {
-  while (v >= 0x80) {
-    o.push_back((uint8_t)(v | 0x80));
-    v >>= 7;
-  }
-  o.push_back((uint8_t)v);
-}
-void pb_double(std::vector<uint8_t>& o, uint32_t field, double v) {
-  if (v == 0.0) return;
-  pb_varint(o, field << 3 | 1);
-  uint8_t b[8];
-  std::memcpy(b, &v, 8);
-  o.insert(o.end(), b, b + 8);
-}
-void pb_uint(std::vector<uint8_t>& o, uint32_t field, uint64_t v) {
-  if (v == 0) return;
-  pb_varint(o, field << 3);
-  pb_varint(o, v);
-}
-void pb_bytes(std::vector<uint8_t>& o, uint32_t field, const std::vector<uint8_t>& m) {
-  pb_varint(o, field << 3 | 2);
-  pb_varint(o, m.size());
-  o.insert(o.end(), m.begin(), m.end());
-}
-
-std::string quad_name(uint32_t level, uint64_t index) {  // NodeId Display (quadtree/src/lib.rs:218-234)
-  std::string s = "r";
-  for (int l = (int)level - 1; l >= 0; --l) s.push_back((char)('0' + ((index >> (2 * l)) & 3u)));
-  return s;
-}
-
-bool write_at(int dirfd, const std::string& name, const uint8_t* data, uint64_t len) {
-  const int fd = openat(dirfd, name.c_str(), O_CREAT | O_WRONLY | O_TRUNC | O_CLOEXEC, 0666);
-  if (fd < 0) return false;
-  bool ok = true;
-  while (len) {
-    const ssize_t w = ::write(fd, data, (size_t)len);
-    if (w <= 0) {
-      ok = false;
-      break;
-    }
-    data += w;
-    len -= (uint64_t)w;
-  }
-  return ::close(fd) == 0 && ok;
-}
-
-}  // namespace
-
-extern "C" int pcv_xray_lanczos_taps(uint32_t tile_size_px, uint32_t* left, uint32_t* count, float* weights) {
-  if (tile_size_px == 0 || tile_size_px > kMaxTilePx) return PCV_E_INVALID;
-  std::vector<LanczosTap> taps;
-  lanczos_taps(tile_size_px, taps);
-  for (uint32_t o = 0; o < tile_size_px; ++o) {
-    if (left) left[o] = taps[o].left;
-    if (count) count[o] = taps[o].count;
-    if (weights)
-      for (uint32_t k = 0; k < kTaps; ++k) weights[(uint64_t)o * kTaps + k] = k < taps[o].count ? taps[o].w[k] : 0.0f;
-  }
-  return PCV_OK;
-}
-
-// The levels above a set of nodes: the node list after them (plevel, pindex; first[k] = the first parent of level
-// from - 1 - k in it) and their images on the device
-struct XrayLevels {
-  std::vector<uint32_t> plevel;
-  std::vector<uint64_t> pindex, first;
-  uint32_t* d_parents = nullptr;
-};
-
-// create_non_leaf_nodes(base, from, to) for the nodes `base` of level `from` (node positions 0 .. base.size() - 1, their
-// images at d_base), one xray_parent_kernel launch per level under the kernel-stat id `prof_id`: the parent levels of a
-// built quadtree (base = the created leaves) and the upper levels of a merged one (base = the parts' roots)
-static int xray_build_levels(pcv_ctx* ctx, uint32_t W, uint32_t bg, const std::vector<uint64_t>& base, uint32_t from, uint32_t to,
-                             const uint32_t* d_base, int prof_id, XrayLevels* out) {
-  const uint64_t nc = base.size();
-  std::vector<uint32_t> plevel;
-  std::vector<uint64_t> pindex, first;
-  // create_non_leaf_nodes: the parent ids of the level below, to ..= from - 1 (ascending index per level)
-  std::vector<uint64_t> below(base);
-  for (uint32_t level = from; nc && level > to; --level) {
-    std::vector<uint64_t> up(below.size());
-    for (size_t i = 0; i < below.size(); ++i) up[i] = below[i] >> 2;
-    std::sort(up.begin(), up.end());
-    up.erase(std::unique(up.begin(), up.end()), up.end());
-    first.push_back(pindex.size());
-    for (uint64_t i : up) {
-      plevel.push_back(level - 1);
-      pindex.push_back(i);
-    }
-    below.swap(up);
-  }
-  first.push_back(pindex.size());
-  const uint64_t np = pindex.size();
-  if (np == 0) return PCV_OK;
-  // child slots: node positions of (index << 2) + c one level down, -1 where that child was not created
-  std::vector<std::pair<uint64_t, uint64_t>> leaf_pos(nc);  // (leaf index, node position)
-  for (uint64_t c = 0; c < nc; ++c) leaf_pos[c] = {base[c], c};
-  std::sort(leaf_pos.begin(), leaf_pos.end());
-  std::vector<int64_t> slots(4 * np, -1);
-  for (size_t k = 0; k + 1 < first.size(); ++k) {
-    for (uint64_t p = first[k]; p < first[k + 1]; ++p)
-      for (uint64_t c = 0; c < 4; ++c) {
-        const uint64_t child = (pindex[p] << 2) + c;
-        if (k == 0) {
-          auto it = std::lower_bound(leaf_pos.begin(), leaf_pos.end(), std::make_pair(child, (uint64_t)0));
-          if (it != leaf_pos.end() && it->first == child) slots[4 * p + c] = (int64_t)it->second;
-        } else {
-          auto b = pindex.begin() + (ptrdiff_t)first[k - 1], e = pindex.begin() + (ptrdiff_t)first[k];
-          auto it = std::lower_bound(b, e, child);
-          if (it != e && *it == child) slots[4 * p + c] = (int64_t)(nc + (uint64_t)(it - pindex.begin()));
-        }
-      }
-  }
-  std::vector<LanczosTap> taps;
-  lanczos_taps(W, taps);
-  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  int rc;
-  uint32_t* d_parents = nullptr;
-  if ((rc = ctx->dev_alloc((void**)&d_parents, 4ull * W * W * np)))  // every parent image before any launch
-    return ctx->fail(PCV_E_OOM, "xray: no device memory for " + std::to_string(np) + " parent images (" + ctx->last_error + ")");
-  PcvScratch sc(ctx);
-  int64_t* d_slots;
-  LanczosTap* d_taps;
-  if ((rc = sc.get(&d_slots, 4 * np)) || (rc = sc.get(&d_taps, W))) {
-    ctx->dev_free(d_parents);
-    return rc;
-  }
-  PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_slots, slots.data(), 8 * slots.size(), hipMemcpyHostToDevice, ctx->stream));
-  PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_taps, taps.data(), sizeof(LanczosTap) * W, hipMemcpyHostToDevice, ctx->stream));
-  int cus = 0, per_cu = 0;
-  PCV_HIP_CHECK(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-  PCV_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xray_parent_kernel, 256, 0));
-  const uint64_t resident = (uint64_t)std::max(cus, 1) * (uint64_t)std::max(per_cu, 1);
-  XrayParentArgs a{};
-  a.leaves = d_base;
-  a.parents = d_parents;
-  a.nleaves = nc;
-  a.taps = d_taps;
-  a.W = W;
-  a.nbx = (W + kBlk - 1) / kBlk;
-  a.bg = bg;
-  for (size_t k = 0; k + 1 < first.size(); ++k) {  // a level reads the one below: one launch each, in order
-    a.slots = d_slots + 4 * first[k];
-    a.out = d_parents + first[k] * W * W;
-    a.nparents = first[k + 1] - first[k];
-    const uint64_t work = a.nparents * a.nbx * a.nbx;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(work, 4 * resident);
-    {
-      PcvProf prof(ctx, prof_id);
-      hipLaunchKernelGGL(xray_parent_kernel, dim3(grid), dim3(256), 0, ctx->stream, a);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-      (void)hipStreamSynchronize(ctx->stream);
-      ctx->dev_free(d_parents);
-      return ctx->fail(PCV_E_HIP, std::string("xray_parent_kernel: ") + hipGetErrorString(e));
-    }
-  }
-  if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
-    ctx->dev_free(d_parents);
-    return ctx->fail(PCV_E_HIP, "xray: parent levels failed");
-  }
-  out->d_parents = d_parents;
-  out->plevel.swap(plevel);
-  out->pindex.swap(pindex);
-  out->first.swap(first);
-  return PCV_OK;
-}
-
-static int xray_build_parents(pcv_xray* x) {
-  const uint64_t nc = x->created.size();
-  std::vector<uint64_t> leaves(nc);
-  for (uint64_t c = 0; c < nc; ++c) leaves[c] = x->geo.index[x->created[c]];
-  XrayLevels lv;
-  const int rc = xray_build_levels(x->ctx, x->W, x->bg, leaves, x->geo.deepest_level, x->root_level, x->d_images, PCV_K_XRAY_PARENT, &lv);
-  if (rc) return rc;
-  x->d_parents = lv.d_parents;
-  x->parent_level.swap(lv.plevel);
-  x->parent_index.swap(lv.pindex);
-  x->level_first.swap(lv.first);
-  return PCV_OK;
-}
-
-extern "C" int pcv_xray_build_parents(pcv_xray* x) {
-  if (!x) return PCV_E_INVALID;
-  if (x->kind != kXrayBuilt) return xray_not_built(x, "pcv_xray_build_parents");
-  if (x->parents_built) return PCV_OK;
-  const int rc = xray_build_parents(x);
-  if (rc) return rc;
-  x->parents_built = true;
-  x->ctx->prof_resolve();
-  return PCV_OK;
-}
-
 extern "C" int pcv_xray_nodes(const pcv_xray* x, uint64_t* num_nodes, uint64_t capacity, uint32_t* level, uint64_t* index) {
   if (!x) return PCV_E_INVALID;
-  const bool listed = x->kind != kXrayBuilt;
-  const uint64_t nc = x->created.size(), n = listed ? x->node_index.size() : nc + x->parent_index.size();
+  const uint64_t n = xray_num_nodes(x);
   if (num_nodes) *num_nodes = n;
   for (uint64_t i = 0; i < std::min(n, capacity); ++i) {
-    if (level) level[i] = listed ? x->node_level[i] : (i < nc ? x->geo.deepest_level : x->parent_level[i - nc]);
-    if (index) index[i] = listed ? x->node_index[i] : (i < nc ? x->geo.index[x->created[i]] : x->parent_index[i - nc]);
+    const XrayNodeId id = xray_node_id(x, i);
+    if (level) level[i] = id.level;
+    if (index) index[i] = id.index;
   }
   return PCV_OK;
 }
 
 extern "C" uint32_t pcv_xray_tile_size(const pcv_xray* x) { return x ? x->W : 0; }
-
-// takes the finished file of a node; false: it could not be kept (PCV_E_IO). May be called from several threads at once
-// where xray_node_files is asked to work in parallel
-using XrayFileSink = std::function<bool(uint64_t node, const uint8_t* file, uint64_t len)>;
-
-// node images [first, first + count) of a built quadtree's node list into dst (host or device), no synchronisation
-static int queue_node_images(pcv_xray* x, uint64_t first, uint64_t count, uint8_t* dst, hipMemcpyKind kind) {
-  pcv_ctx* ctx = x->ctx;
-  const uint64_t nc = x->created.size(), tile_bytes = 4ull * x->W * x->W;
-  const uint64_t nl = first < nc ? std::min(count, nc - first) : 0;
-  if (nl)
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(dst, reinterpret_cast<const uint8_t*>(x->d_images) + first * tile_bytes, nl * tile_bytes, kind, ctx->stream));
-  if (count > nl)
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(dst + nl * tile_bytes, reinterpret_cast<const uint8_t*>(x->d_parents) + (first + nl - nc) * tile_bytes,
-                                      (count - nl) * tile_bytes, kind, ctx->stream));
-  return PCV_OK;
-}
-
-static bool read_file(const std::string& path, std::vector<uint8_t>& data) {
-  FILE* f = std::fopen(path.c_str(), "rb");
-  if (!f) return false;
-  data.clear();
-  uint8_t buf[1 << 16];
-  size_t k;
-  while ((k = std::fread(buf, 1, sizeof(buf), f)) > 0) data.insert(data.end(), buf, buf + k);
-  const bool ok = !std::ferror(f);
-  std::fclose(f);
-  return ok;
-}
-
-// node `node` of an opened quadtree, decoded from its file into W x W x 4 host bytes
-static int opened_node_to_host(const pcv_xray* x, uint64_t node, uint8_t* dst) {
-  const std::string path = x->dir + "/" + quad_name(x->node_level[node], x->node_index[node]) + ".png";
-  std::vector<uint8_t> file;
-  if (!read_file(path, file)) return xray_fail(x, PCV_E_IO, "xray: cannot read " + path);
-  uint32_t w = 0, h = 0;
-  int rc = pcv_png_decode(file.data(), file.size(), &w, &h, nullptr, 0);
-  if (rc) return xray_fail(x, rc == PCV_E_INVALID ? PCV_E_IO : rc, path + ": " + pcv_host_last_error());
-  if (w != x->W || h != x->W)
-    return xray_fail(x, PCV_E_INVALID, path + " is " + std::to_string(w) + " x " + std::to_string(h) + ", the meta's tile_size is " + std::to_string(x->W));
-  rc = pcv_png_decode(file.data(), file.size(), &w, &h, dst, 4ull * x->W * x->W);
-  if (rc) return xray_fail(x, PCV_E_IO, path + ": " + pcv_host_last_error());
-  return PCV_OK;
-}
-
-static bool xray_part_alive(const XrayPartRef& r) {
-  std::lock_guard<std::mutex> g(g_xray_mu);
-  auto it = g_xray_live.find(r.part);
-  return it != g_xray_live.end() && it->second == r.serial;
-}
-
-// node images of any kind of quadtree into checked arguments; returns after the copies have completed
-static int xray_node_images(pcv_xray* x, uint64_t first, uint64_t count, int mem, uint8_t* rgba) {
-  pcv_ctx* ctx = x->ctx;
-  const uint64_t tile_bytes = 4ull * x->W * x->W;
-  if (mem == PCV_MEM_DEVICE && !ctx) return xray_fail(x, PCV_E_INVALID, "xray: a quadtree opened without a context has host images only");
-  if (ctx) PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (x->kind == kXrayBuilt) {
-    const int rc = queue_node_images(x, first, count, rgba, mem == PCV_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice);
-    if (rc) return rc;
-    PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return PCV_OK;
-  }
-  if (x->kind == kXrayOpened) {
-    if (mem == PCV_MEM_HOST) {
-      for (uint64_t i = 0; i < count; ++i)
-        if (int rc = opened_node_to_host(x, first + i, rgba + i * tile_bytes)) return rc;
-      return PCV_OK;
-    }
-    uint8_t* host = nullptr;  // decoded into pinned memory, one upload
-    int rc = ctx->host_alloc((void**)&host, count * tile_bytes);
-    if (rc) return rc;
-    for (uint64_t i = 0; !rc && i < count; ++i) rc = opened_node_to_host(x, first + i, host + i * tile_bytes);
-    if (!rc) {
-      hipError_t e = hipMemcpyAsync(rgba, host, count * tile_bytes, hipMemcpyHostToDevice, ctx->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-      if (e != hipSuccess) rc = ctx->fail(PCV_E_HIP, std::string("xray: image upload: ") + hipGetErrorString(e));
-    }
-    ctx->host_release(host);
-    return rc;
-  }
-  // merged: runs of nodes that belong to one part go to that part; the new levels are this object's own
-  for (const XrayPartRef& r : x->parts)
-    if (!xray_part_alive(r)) return ctx->fail(PCV_E_INVALID, "xray: a part of this merged quadtree was freed before it");
-  const uint64_t own_first = x->node_index.size() - x->parent_index.size();
-  uint64_t at = first;
-  const uint64_t end = first + count;
-  for (const XrayPartRef& r : x->parts) {
-    if (at >= end) break;
-    if (at >= r.first + r.count || r.count == 0) continue;
-    const uint64_t k = std::min(end, r.first + r.count) - at;
-    const int rc = xray_node_images(r.part, at - r.first, k, mem, rgba + (at - first) * tile_bytes);
-    if (rc) return r.part->ctx ? rc : ctx->fail(rc, pcv_host_last_error());
-    at += k;
-  }
-  if (at < end) {
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(rgba + (at - first) * tile_bytes, reinterpret_cast<const uint8_t*>(x->d_parents) + (at - own_first) * tile_bytes,
-                                      (end - at) * tile_bytes, mem == PCV_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
-                                      ctx->stream));
-    PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return PCV_OK;
-}
-
-extern "C" int pcv_xray_node_images(pcv_xray* x, uint64_t first, uint64_t count, uint64_t capacity, int mem, uint8_t* rgba) {
-  if (!x) return PCV_E_INVALID;
-  uint64_t n = 0;
-  pcv_xray_nodes(x, &n, 0, nullptr, nullptr);
-  if (first > n || count > n - first) return xray_fail(x, PCV_E_INVALID, "xray: node range past the end");
-  if (mem != PCV_MEM_HOST && mem != PCV_MEM_DEVICE) return xray_fail(x, PCV_E_INVALID, "bad mem");
-  const uint64_t tile_bytes = 4ull * x->W * x->W;
-  if (count * tile_bytes > capacity) return xray_fail(x, PCV_E_INVALID, "xray: capacity below count x W x W x 4 bytes");
-  if (count == 0) return PCV_OK;
-  if (!rgba) return xray_fail(x, PCV_E_INVALID, "null output");
-  return xray_node_images(x, first, count, mem, rgba);
-}
-
-// root_node.bounding_rect of a built quadtree: Node::from_node_id_and_root_bounding_rect(root_node_id, rect), what its
-// meta file holds
-static void built_root_rect(const pcv_xray* x, double rect[3]) {
-  std::memcpy(rect, x->geo.rect, sizeof(x->geo.rect));
-  for (int l = (int)x->root_level - 1; l >= 0; --l) {
-    const uint32_t ci = (uint32_t)(x->root_index >> (2 * l)) & 3u;
-    const double half = rect[2] / 2.0;
-    if (ci & 1u) rect[1] += half;
-    if (ci & 2u) rect[0] += half;
-    rect[2] = half;
-  }
-}
-
-// Meta (xray_proto Meta, CURRENT_VERSION 3) to get_meta_pb_path: the root id with "r" -> "meta", + ".pb"
-static bool write_meta_file(int dirfd, const std::string& dir, uint32_t root_level, uint64_t root_index, const double rect[3],
-                            uint32_t deepest_level, uint32_t W, const std::vector<uint32_t>& level, const std::vector<uint64_t>& index,
-                            std::string* err) {
-  std::vector<uint8_t> meta, r, mn;
-  pb_uint(meta, 1, 3);
-  pb_double(mn, 1, rect[0]);
-  pb_double(mn, 2, rect[1]);
-  pb_bytes(r, 3, mn);
-  pb_double(r, 4, rect[2]);
-  pb_bytes(meta, 2, r);
-  pb_uint(meta, 3, deepest_level);
-  pb_uint(meta, 4, W);
-  for (size_t i = 0; i < index.size(); ++i) {
-    std::vector<uint8_t> id;
-    pb_uint(id, 1, level[i]);
-    pb_uint(id, 2, index[i]);
-    pb_bytes(meta, 5, id);
-  }
-  const std::string name = "meta" + quad_name(root_level, root_index).substr(1) + ".pb";
-  if (write_at(dirfd, name, meta.data(), meta.size())) return true;
-  *err = "cannot write " + dir + "/" + name;
-  return false;
-}
-
-// ---- xray_proto Meta, read (Meta::from_proto, xray/src/lib.rs:81-116) --------------------------------------------------
-// proto3 wire format of xray_proto_rust/src/proto.proto: Meta { int32 version = 1; Rect bounding_rect = 2; uint32
-// deepest_level = 3; uint32 tile_size = 4; repeated NodeId nodes = 5 }, Rect { Vector2f deprecated_min = 1; float
-// deprecated_edge_length = 2; Vector2d min = 3; double edge_length = 4 }, NodeId { uint32 level = 1; uint64 index = 2 }.
-// Fields may come in any order, a repeated scalar field keeps its last value, unknown fields are skipped.
-namespace {
-
-struct PbReader {
-  const uint8_t* p;
-  size_t n, pos = 0;
-  bool bad = false;
-  bool more() const { return !bad && pos < n; }
-  uint64_t varint() {
-    uint64_t v = 0;
-    for (int shift = 0; shift < 64; shift += 7) {
-      if (pos >= n) break;
-      const uint8_t c = p[pos++];
-      v |= (uint64_t)(c & 0x7f) << shift;
-      if (c < 0x80) return v;
-    }
-    bad = true;
-    return 0;
-  }
-  // one field: its number, wire type and value (varint / fixed bits in `v`, a length-delimited body in `sub`)
-  bool field(uint32_t* num, uint32_t* wt, uint64_t* v, PbReader* sub) {
-    const uint64_t key = varint();
-    if (bad || (key >> 3) == 0 || (key >> 3) > 0x1fffffffu) return !(bad = true);
-    *num = (uint32_t)(key >> 3);
-    *wt = (uint32_t)(key & 7);
-    *v = 0;
-    if (*wt == 0) {
-      *v = varint();
-    } else if (*wt == 1 || *wt == 5) {
-      const size_t k = *wt == 1 ? 8 : 4;
-      if (n - pos < k) return !(bad = true);
-      std::memcpy(v, p + pos, k);  // little endian, as the wire
-      pos += k;
-    } else if (*wt == 2) {
-      const uint64_t k = varint();
-      if (bad || k > n - pos) return !(bad = true);
-      *sub = PbReader{p + pos, (size_t)k};
-      pos += (size_t)k;
-    } else {
-      return !(bad = true);  // groups: not in this schema
-    }
-    return !bad;
-  }
-};
-
-struct XrayMeta {
-  int32_t version = 0;
-  bool has_min = false;
-  double min[2] = {0, 0}, edge = 0;
-  float dmin[2] = {0, 0}, dedge = 0;
-  uint32_t deepest_level = 0, tile_size = 0;
-  std::vector<std::pair<uint32_t, uint64_t>> nodes;
-};
-
-double pb_f64(uint64_t v) {
-  double d;
-  std::memcpy(&d, &v, 8);
-  return d;
-}
-float pb_f32(uint64_t v) {
-  const uint32_t u = (uint32_t)v;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
-bool parse_meta(const std::vector<uint8_t>& data, XrayMeta* m) {
-  PbReader top{data.data(), data.size()};
-  uint32_t f, wt;
-  uint64_t v;
-  PbReader sub{nullptr, 0};
-  while (top.more()) {
-    if (!top.field(&f, &wt, &v, &sub)) return false;
-    if (f == 1 && wt == 0) m->version = (int32_t)v;
-    if (f == 3 && wt == 0) m->deepest_level = (uint32_t)v;
-    if (f == 4 && wt == 0) m->tile_size = (uint32_t)v;
-    if ((f == 1 || f == 3 || f == 4) && wt != 0) return false;
-    if ((f == 2 || f == 5) && wt != 2) return false;
-    if (f == 2) {
-      PbReader rect = sub, vec{nullptr, 0};
-      while (rect.more()) {
-        uint32_t g, gw;
-        if (!rect.field(&g, &gw, &v, &vec)) return false;
-        if ((g == 1 || g == 3) && gw != 2) return false;
-        if ((g == 2 && gw != 5) || (g == 4 && gw != 1)) return false;
-        if (g == 2) m->dedge = pb_f32(v);
-        if (g == 4) m->edge = pb_f64(v);
-        if (g == 1 || g == 3) {
-          if (g == 3) m->has_min = true;
-          PbReader none{nullptr, 0};
-          while (vec.more()) {
-            uint32_t c, cw;
-            if (!vec.field(&c, &cw, &v, &none)) return false;
-            if ((c == 1 || c == 2) && cw != (g == 3 ? 1u : 5u)) return false;
-            if (c == 1 || c == 2) {
-              if (g == 3) m->min[c - 1] = pb_f64(v);
-              else m->dmin[c - 1] = pb_f32(v);
-            }
-          }
-          if (vec.bad) return false;
-        }
-      }
-      if (rect.bad) return false;
-    }
-    if (f == 5) {
-      PbReader id = sub, none{nullptr, 0};
-      uint32_t level = 0;
-      uint64_t index = 0;
-      while (id.more()) {
-        uint32_t g, gw;
-        if (!id.field(&g, &gw, &v, &none)) return false;
-        if ((g == 1 || g == 2) && gw != 0) return false;
-        if (g == 1) level = (uint32_t)v;
-        if (g == 2) index = v;
-      }
-      if (id.bad) return false;
-      m->nodes.emplace_back(level, index);
-    }
-  }
-  return !top.bad;
-}
-
-}  // namespace
-
-#include <dirent.h>
-
-extern "C" int pcv_xray_open_dir(pcv_ctx* ctx, const char* directory, uint32_t capacity, pcv_xray** parts, uint32_t* num_parts) {
-  auto fail = [&](int code, const std::string& m) { return ctx ? ctx->fail(code, m) : pcv_host_fail(code, m); };
-  if (!directory || !num_parts) return fail(PCV_E_INVALID, "null argument");
-  const std::string dir(directory);
-  DIR* d = opendir(dir.c_str());
-  if (!d) return fail(PCV_E_IO, "cannot open directory " + dir);
-  std::vector<std::string> names;  // "meta*.pb" (META_PREFIX, META_EXTENSION)
-  while (struct dirent* e = readdir(d)) {
-    const std::string name(e->d_name);
-    if (name.size() >= 7 && name.compare(0, 4, "meta") == 0 && name.compare(name.size() - 3, 3, ".pb") == 0) names.push_back(name);
-  }
-  closedir(d);
-  std::sort(names.begin(), names.end());
-  *num_parts = (uint32_t)names.size();
-  if (capacity < names.size() || names.empty()) return PCV_OK;
-  if (!parts) return fail(PCV_E_INVALID, "null argument");
-  std::vector<pcv_xray*> made;
-  auto undo = [&](int code, const std::string& m) {
-    for (pcv_xray* x : made) pcv_xray_free(x);
-    return fail(code, m);
-  };
-  for (const std::string& name : names) {
-    const std::string path = dir + "/" + name;
-    std::vector<uint8_t> data;
-    if (!read_file(path, data)) return undo(PCV_E_IO, "cannot read " + path);
-    XrayMeta m;
-    if (!parse_meta(data, &m)) return undo(PCV_E_INVALID, "Could not parse " + path);
-    if (m.version != 2 && m.version != 3)
-      return undo(PCV_E_INVALID, path + ": Invalid version. We only support 3, but found " + std::to_string(m.version) + ".");
-    if (m.tile_size == 0 || m.tile_size > kMaxTilePx) return undo(PCV_E_INVALID, path + ": tile_size outside 1 ..= 32768");
-    if (m.deepest_level > 31) return undo(PCV_E_INVALID, path + ": deepest_level above 31 (a u64 index holds 32 levels)");
-    for (const auto& nd : m.nodes)
-      if (nd.first > m.deepest_level || (nd.first < 32 && (nd.second >> (2 * nd.first)) != 0))
-        return undo(PCV_E_INVALID, path + ": a node outside the quadtree");
-    pcv_xray* x = new pcv_xray();
-    made.push_back(x);
-    x->ctx = ctx;
-    x->kind = kXrayOpened;
-    x->W = m.tile_size;
-    x->dir = dir;
-    x->geo.deepest_level = m.deepest_level;
-    // Meta::from_proto: Rect.min where present, else the deprecated f32 fields widened (version 2 files)
-    x->geo.rect[0] = m.has_min ? m.min[0] : (double)m.dmin[0];
-    x->geo.rect[1] = m.has_min ? m.min[1] : (double)m.dmin[1];
-    x->geo.rect[2] = m.has_min ? m.edge : (double)m.dedge;
-    // the node set in a stated order: descending level, then ascending index (duplicates of a file fold, as in a set)
-    std::sort(m.nodes.begin(), m.nodes.end(), [](const std::pair<uint32_t, uint64_t>& a, const std::pair<uint32_t, uint64_t>& b) {
-      return a.first != b.first ? a.first > b.first : a.second < b.second;
-    });
-    m.nodes.erase(std::unique(m.nodes.begin(), m.nodes.end()), m.nodes.end());
-    for (const auto& nd : m.nodes) {
-      x->node_level.push_back(nd.first);
-      x->node_index.push_back(nd.second);
-      if (nd.first == m.deepest_level) {
-        x->created.push_back(x->geo.index.size());
-        x->geo.index.push_back(nd.second);
-      }
-    }
-  }
-  for (size_t i = 0; i < made.size(); ++i) parts[i] = made[i];
-  return PCV_OK;
-}
-
-// ---- merge_xray_quadtrees (xray/src/bin/merge_xray_quadtrees.rs:129-205) ---------------------------------------------
-namespace {
-
-struct MergePlan {
-  uint32_t L = 0, deepest = 0, W = 0;
-  double rect[3] = {0, 0, 0};
-  std::vector<int64_t> root_pos;    // per part: position of its root in its own node list, -1 for an empty part
-  std::vector<uint64_t> root_index;  // per part: index of its root at level L
-};
-
-int merge_plan(pcv_xray* const* parts, uint32_t num_parts, MergePlan* plan, std::string* err) {
-  auto bad = [&](const std::string& m) {
-    *err = m;
-    return PCV_E_INVALID;
-  };
-  if (num_parts == 0) return bad("No subquadtrees meta files found.");
-  if (!parts) return bad("xray merge: null argument");
-  struct Root {
-    uint32_t level;
-    uint64_t index;
-  };
-  std::vector<Root> roots;
-  int first_part = -1;
-  plan->root_pos.assign(num_parts, -1);
-  plan->root_index.assign(num_parts, 0);
-  for (uint32_t k = 0; k < num_parts; ++k) {
-    const pcv_xray* x = parts[k];
-    if (!x) return bad("xray merge: part " + std::to_string(k) + " is null");
-    {
-      std::lock_guard<std::mutex> g(g_xray_mu);
-      if (!g_xray_live.count(x)) return bad("xray merge: part " + std::to_string(k) + " is not a live pcv_xray");
-    }
-    if (x->kind == kXrayBuilt && !x->parents_built && !x->created.empty() && x->root_level < x->geo.deepest_level)
-      return bad("xray merge: the parent levels of part " + std::to_string(k) + " are not built (pcv_xray_build_parents)");
-    uint64_t n = 0;
-    pcv_xray_nodes(x, &n, 0, nullptr, nullptr);
-    std::vector<uint32_t> level(n);
-    std::vector<uint64_t> index(n);
-    pcv_xray_nodes(x, &n, n, level.data(), index.data());
-    if (n == 0) continue;  // get_root_nodes skips it; it still takes part in the deepest_level and tile_size checks
-    uint64_t at = 0, count = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-      if (level[i] < level[at]) at = i, count = 0;
-      if (level[i] == level[at]) ++count;
-    }
-    if (count != 1)
-      return bad("xray merge: part " + std::to_string(k) + " has " + std::to_string(count) + " nodes at its minimum level " +
-                 std::to_string(level[at]) + ": its root is not defined");
-    plan->root_pos[k] = (int64_t)at;
-    plan->root_index[k] = index[at];
-    roots.push_back(Root{level[at], index[at]});
-    if (first_part < 0) first_part = (int)k;
-  }
-  if (roots.empty()) return bad("All subquadtress are empty.");
-  for (size_t a = 0; a < roots.size(); ++a)
-    for (size_t b = a + 1; b < roots.size(); ++b)
-      if (roots[a].level == roots[b].level && roots[a].index == roots[b].index) return bad("Not all roots are unique.");
-  for (const Root& r : roots)
-    if (r.level != roots[0].level) return bad("Not all roots have the same level.");
-  for (uint32_t k = 1; k < num_parts; ++k)
-    if (parts[k]->geo.deepest_level != parts[0]->geo.deepest_level) return bad("Not all meta files have the same deepest level.");
-  for (uint32_t k = 1; k < num_parts; ++k)
-    if (parts[k]->W != parts[0]->W) return bad("Not all meta files have the same tile size.");
-  plan->L = roots[0].level;
-  plan->deepest = parts[0]->geo.deepest_level;
-  plan->W = parts[0]->W;
-  if (plan->L > plan->deepest) return bad("xray merge: the roots' level is above deepest_level");
-  // the first root's rect under Node::parent until level 0
-  const pcv_xray* x = parts[first_part];
-  if (x->kind == kXrayBuilt) built_root_rect(x, plan->rect);
-  else std::memcpy(plan->rect, x->geo.rect, sizeof(plan->rect));
-  uint64_t idx = roots[0].index;
-  for (uint32_t l = plan->L; l > 0; --l, idx >>= 2) {
-    const uint32_t ci = (uint32_t)idx & 3u;
-    if (ci & 1u) plan->rect[1] -= plan->rect[2];
-    if (ci & 2u) plan->rect[0] -= plan->rect[2];
-    plan->rect[2] *= 2.0;
-  }
-  return PCV_OK;
-}
-
-}  // namespace
-
-extern "C" int pcv_xray_merge_check(pcv_xray* const* parts, uint32_t num_parts, uint32_t* root_level, double rect[3], char* err,
-                                    uint64_t errcap) {
-  MergePlan plan;
-  std::string m;
-  const int rc = merge_plan(parts, num_parts, &plan, &m);
-  if (rc) return fail_msg(err, errcap, m);
-  if (root_level) *root_level = plan.L;
-  if (rect) std::memcpy(rect, plan.rect, sizeof(plan.rect));
-  return PCV_OK;
-}
-
-extern "C" int pcv_xray_merge(pcv_ctx* ctx, pcv_xray* const* parts, uint32_t num_parts, uint32_t background, pcv_xray** out) {
-  if (!ctx) return PCV_E_INVALID;
-  if (!out) return ctx->fail(PCV_E_INVALID, "null argument");
-  *out = nullptr;
-  if (background > PCV_XRAY_BG_TRANSPARENT) return ctx->fail(PCV_E_INVALID, "xray: unknown background");
-  MergePlan plan;
-  std::string m;
-  int rc = merge_plan(parts, num_parts, &plan, &m);
-  if (rc) return ctx->fail(rc, m);
-  for (uint32_t k = 0; k < num_parts; ++k)
-    if (parts[k]->ctx && parts[k]->ctx != ctx) return ctx->fail(PCV_E_INVALID, "xray merge: part " + std::to_string(k) + " belongs to another context");
-  const uint32_t W = plan.W;
-  const uint64_t tile_bytes = 4ull * W * W;
-  pcv_xray* x = new pcv_xray();
-  x->ctx = ctx;
-  x->kind = kXrayMerged;
-  x->W = W;
-  x->bg = background == PCV_XRAY_BG_TRANSPARENT ? 0x00ffffffu : 0xffffffffu;
-  x->geo.deepest_level = plan.deepest;
-  std::memcpy(x->geo.rect, plan.rect, sizeof(plan.rect));
-  for (uint32_t k = 0; k < num_parts; ++k) {
-    uint64_t n = 0;
-    pcv_xray_nodes(parts[k], &n, 0, nullptr, nullptr);
-    const uint64_t at = x->node_index.size();
-    x->parts.push_back(XrayPartRef{parts[k], parts[k]->serial, at, n});
-    x->node_level.resize(at + n);
-    x->node_index.resize(at + n);
-    pcv_xray_nodes(parts[k], &n, n, x->node_level.data() + at, x->node_index.data() + at);
-  }
-  // the level array of the roots: those of built parts first (device to device), then those of opened parts (decoded
-  // into one pinned block, one upload)
-  std::vector<uint32_t> order;
-  for (int opened = 0; opened < 2; ++opened)
-    for (uint32_t k = 0; k < num_parts; ++k)
-      if (plan.root_pos[k] >= 0 && (parts[k]->kind == kXrayOpened) == (opened == 1)) order.push_back(k);
-  uint64_t num_opened = 0;
-  std::vector<uint64_t> base;
-  for (uint32_t k : order) {
-    base.push_back(plan.root_index[k]);
-    num_opened += parts[k]->kind == kXrayOpened;
-  }
-  auto undo = [&](int code) {
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipGetLastError();
-    pcv_xray_free(x);
-    return code;
-  };
-  if (plan.L > 0) {
-    if (hipSetDevice(ctx->device) != hipSuccess) return undo(ctx->fail(PCV_E_HIP, "hipSetDevice"));
-    PcvScratch sc(ctx);
-    uint8_t* d_stage = nullptr;
-    uint8_t* host = nullptr;
-    if ((rc = sc.get(&d_stage, base.size() * tile_bytes)))
-      return undo(ctx->fail(PCV_E_OOM, "xray merge: no device memory for " + std::to_string(base.size()) + " root tiles"));
-    if (num_opened && (rc = ctx->host_alloc((void**)&host, num_opened * tile_bytes))) return undo(rc);
-    const uint64_t num_built = base.size() - num_opened;
-    for (uint64_t i = 0; !rc && i < num_opened; ++i) {
-      pcv_xray* part = parts[order[num_built + i]];
-      rc = opened_node_to_host(part, (uint64_t)plan.root_pos[order[num_built + i]], host + i * tile_bytes);
-      if (rc && !part->ctx) ctx->fail(rc, pcv_host_last_error());
-    }
-    if (!rc) {
-      PcvProf prof(ctx, PCV_K_XRAY_MERGE_STAGE);
-      for (uint64_t i = 0; !rc && i < num_built; ++i) {
-        pcv_xray* part = parts[order[i]];
-        if (part->kind == kXrayBuilt) {
-          rc = queue_node_images(part, (uint64_t)plan.root_pos[order[i]], 1, d_stage + i * tile_bytes, hipMemcpyDeviceToDevice);
-        } else {  // a merged part: through its own parts
-          rc = xray_node_images(part, (uint64_t)plan.root_pos[order[i]], 1, PCV_MEM_DEVICE, d_stage + i * tile_bytes);
-        }
-      }
-      if (!rc && num_opened &&
-          hipMemcpyAsync(d_stage + num_built * tile_bytes, host, num_opened * tile_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-        rc = ctx->fail(PCV_E_HIP, "xray merge: root tile upload");
-    }
-    XrayLevels lv;
-    if (!rc)
-      rc = xray_build_levels(ctx, W, x->bg, base, plan.L, 0, reinterpret_cast<const uint32_t*>(d_stage), PCV_K_XRAY_MERGE_PARENT, &lv);
-    else
-      (void)hipStreamSynchronize(ctx->stream);
-    if (host) ctx->host_release(host);  // the upload has completed: xray_build_levels returns after a stream sync
-    if (rc) return undo(rc);
-    x->d_parents = lv.d_parents;
-    x->parent_level.swap(lv.plevel);
-    x->parent_index.swap(lv.pindex);
-    x->level_first.swap(lv.first);
-    x->node_level.insert(x->node_level.end(), x->parent_level.begin(), x->parent_level.end());
-    x->node_index.insert(x->node_index.end(), x->parent_index.begin(), x->parent_index.end());
-  }
-  x->parents_built = true;
-  for (size_t i = 0; i < x->node_index.size(); ++i)
-    if (x->node_level[i] == plan.deepest) {
-      x->created.push_back(x->geo.index.size());
-      x->geo.index.push_back(x->node_index[i]);
-    }
-  ctx->prof_resolve();
-  *out = x;
-  return PCV_OK;
-}
-
-static bool same_directory(const std::string& a, const std::string& b) {  // copy_images :29: canonicalize() of both
-  char* ra = realpath(a.c_str(), nullptr);
-  char* rb = realpath(b.c_str(), nullptr);
-  const bool same = ra && rb && std::strcmp(ra, rb) == 0;
-  std::free(ra);
-  std::free(rb);
-  return same;
-}
-
-static int xray_node_files(pcv_xray* x, uint64_t first, uint64_t count, int mode, bool parallel, const XrayFileSink& sink);
-
-// pcv_xray_write_dir_ex of a merged quadtree
-static int xray_write_merged(pcv_xray* x, const char* directory, int mode) {
-  pcv_ctx* ctx = x->ctx;
-  for (const XrayPartRef& r : x->parts)
-    if (!xray_part_alive(r)) return ctx->fail(PCV_E_INVALID, "xray: a part of this merged quadtree was freed before it");
-  const std::string dir(directory);
-  ::mkdir(dir.c_str(), 0777);
-  struct stat st;
-  if (stat(dir.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) return ctx->fail(PCV_E_IO, "cannot create directory " + dir);
-  const int dirfd = open(dir.c_str(), O_RDONLY | O_DIRECTORY | O_CLOEXEC);
-  if (dirfd < 0) return ctx->fail(PCV_E_IO, "cannot open directory " + dir);
-  const uint32_t W = x->W;
-  const uint64_t tile_bytes = 4ull * W * W, n = x->node_index.size();
-  int rc = PCV_OK;
-  // copy_images: the files of opened parts, byte for byte; every other node is fetched and encoded
-  std::vector<uint64_t> encode;
-  std::vector<uint8_t> file;
-  for (const XrayPartRef& r : x->parts) {
-    const bool copy = r.part->kind == kXrayOpened;
-    const bool same = copy && same_directory(r.part->dir, dir);
-    for (uint64_t i = 0; !rc && i < r.count; ++i) {
-      if (!copy) {
-        encode.push_back(r.first + i);
-        continue;
-      }
-      if (same) continue;
-      const std::string name = quad_name(x->node_level[r.first + i], x->node_index[r.first + i]) + ".png";
-      if (!read_file(r.part->dir + "/" + name, file)) rc = ctx->fail(PCV_E_IO, "cannot read " + r.part->dir + "/" + name);
-      else if (!write_at(dirfd, name, file.data(), file.size())) rc = ctx->fail(PCV_E_IO, "cannot write " + dir + "/" + name);
-    }
-  }
-  for (uint64_t i = n - x->parent_index.size(); i < n; ++i) encode.push_back(i);
-  if (mode == PCV_XRAY_PNG_DEFLATE) {  // compressed where the images live; the threads below only write
-    std::mutex err_mu;
-    std::string first_error;
-    const XrayFileSink write = [&](uint64_t node, const uint8_t* file, uint64_t len) {
-      const std::string name = quad_name(x->node_level[node], x->node_index[node]) + ".png";
-      if (write_at(dirfd, name, file, len)) return true;
-      std::lock_guard<std::mutex> g(err_mu);
-      if (first_error.empty()) first_error = "cannot write " + dir + "/" + name;
-      return false;
-    };
-    for (uint64_t i = 0; !rc && i < encode.size();) {  // runs of consecutive nodes in one call
-      uint64_t k = 1;
-      while (i + k < encode.size() && encode[i + k] == encode[i] + k) ++k;
-      rc = xray_node_files(x, encode[i], k, mode, true, write);
-      if (rc == PCV_E_IO && !first_error.empty()) ctx->fail(rc, first_error);
-      i += k;
-    }
-    encode.clear();
-  }
-  const uint64_t per_chunk = std::max<uint64_t>(1, ctx->xray_chunk_bytes / tile_bytes);
-  std::vector<uint8_t> images(std::min<uint64_t>(per_chunk, std::max<uint64_t>(encode.size(), 1)) * tile_bytes);
-  unsigned nthreads = std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
-  for (uint64_t f = 0; !rc && f < encode.size(); f += per_chunk) {
-    const uint64_t c = std::min<uint64_t>(per_chunk, encode.size() - f);
-    for (uint64_t i = 0; !rc && i < c;) {  // runs of consecutive nodes in one call
-      uint64_t k = 1;
-      while (i + k < c && encode[f + i + k] == encode[f + i] + k) ++k;
-      rc = xray_node_images(x, encode[f + i], k, PCV_MEM_HOST, images.data() + i * tile_bytes);
-      i += k;
-    }
-    if (rc) break;
-    std::atomic<uint64_t> next{0};
-    std::atomic<int> failed{0};
-    std::string first_error;
-    std::mutex err_mu;
-    auto worker = [&]() {
-      std::vector<uint8_t> png(pcv_png_stored_size(W, W));
-      for (;;) {
-        const uint64_t i = next.fetch_add(1);
-        if (i >= c || failed.load()) return;
-        const uint64_t node = encode[f + i];
-        const std::string name = quad_name(x->node_level[node], x->node_index[node]) + ".png";
-        pcv_png_stored_encode(images.data() + i * tile_bytes, W, W, png.data());
-        if (!write_at(dirfd, name, png.data(), png.size())) {
-          std::lock_guard<std::mutex> g(err_mu);
-          if (!failed.exchange(1)) first_error = "cannot write " + dir + "/" + name;
-        }
-      }
-    };
-    std::vector<std::thread> pool;
-    for (unsigned t = 1; t < (unsigned)std::min<uint64_t>(nthreads, c); ++t) pool.emplace_back(worker);
-    worker();
-    for (auto& th : pool) th.join();
-    if (failed.load()) rc = ctx->fail(PCV_E_IO, first_error);
-  }
-  std::string err;
-  if (!rc && !write_meta_file(dirfd, dir, 0, 0, x->geo.rect, x->geo.deepest_level, W, x->node_level, x->node_index, &err))
-    rc = ctx->fail(PCV_E_IO, err);
-  ::close(dirfd);
-  return rc;
-}
-
-static int xray_write_built_deflate(pcv_xray* x, int dirfd, const std::string& dir);
-
-extern "C" int pcv_xray_write_dir(pcv_xray* x, const char* directory) { return pcv_xray_write_dir_ex(x, directory, PCV_XRAY_PNG_STORED); }
-
-extern "C" int pcv_xray_write_dir_ex(pcv_xray* x, const char* directory, int mode) {
-  if (!x) return PCV_E_INVALID;
-  if (!directory) return xray_fail(x, PCV_E_INVALID, "null directory");
-  if (mode != PCV_XRAY_PNG_STORED && mode != PCV_XRAY_PNG_DEFLATE) return xray_fail(x, PCV_E_INVALID, "xray: unknown PNG mode");
-  if (x->kind == kXrayOpened)
-    return xray_fail(x, PCV_E_INVALID, "xray: an opened quadtree is written through pcv_xray_merge (its files are already a directory)");
-  if (mode == PCV_XRAY_PNG_DEFLATE && x->W > PCV_XRAY_PNG_DEFLATE_MAX_EDGE)
-    return xray_fail(x, PCV_E_INVALID, "xray: compressed tiles are at most " + std::to_string(PCV_XRAY_PNG_DEFLATE_MAX_EDGE) + " pixels wide");
-  if (x->kind == kXrayMerged) return xray_write_merged(x, directory, mode);
-  pcv_ctx* ctx = x->ctx;
-  const uint64_t nc = x->created.size(), n = nc + x->parent_index.size();
-  if (!x->parents_built && nc && x->root_level < x->geo.deepest_level)
-    return ctx->fail(PCV_E_INVALID, "xray: parent levels are not built (pcv_xray_build_parents)");
-  const std::string dir(directory);
-  ::mkdir(dir.c_str(), 0777);  // build_xray_quadtree :565 ignores errors: the directory may be there
-  struct stat st;
-  if (stat(dir.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) return ctx->fail(PCV_E_IO, "cannot create directory " + dir);
-  const int dirfd = open(dir.c_str(), O_RDONLY | O_DIRECTORY | O_CLOEXEC);
-  if (dirfd < 0) return ctx->fail(PCV_E_IO, "cannot open directory " + dir);
-  // the node images come down in chunks through two pinned buffers: chunk k + 1 is copied while a pool of host threads
-  // encodes and writes chunk k (no HIP call in a writer thread)
-  const uint32_t W = x->W;
-  const uint64_t tile_bytes = 4ull * W * W;
-  const uint64_t per_chunk = std::max<uint64_t>(1, std::min<uint64_t>(n, ctx->xray_chunk_bytes / tile_bytes));
-  const uint64_t chunks = mode == PCV_XRAY_PNG_DEFLATE ? 0 : (n + per_chunk - 1) / per_chunk;
-  uint8_t* host[2] = {nullptr, nullptr};
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  int rc = PCV_OK;
-  if (mode == PCV_XRAY_PNG_DEFLATE && n) rc = xray_write_built_deflate(x, dirfd, dir);
-  if (n && chunks) {
-    if (hipSetDevice(ctx->device) != hipSuccess) rc = ctx->fail(PCV_E_HIP, "hipSetDevice");
-    for (int k = 0; !rc && k < 2 && (uint64_t)k < chunks; ++k) {
-      rc = ctx->host_alloc((void**)&host[k], per_chunk * tile_bytes);
-      if (!rc && hipEventCreateWithFlags(&ev[k], hipEventDisableTiming) != hipSuccess) rc = ctx->fail(PCV_E_HIP, "hipEventCreate");
-    }
-  }
-  unsigned nthreads = std::thread::hardware_concurrency();
-  if (nthreads == 0) nthreads = 4;
-  if (nthreads > 8) nthreads = 8;  // one directory: more writers queue on its lock (pcv_io.cpp)
-  std::atomic<int> failed{0};
-  std::string first_error;
-  std::mutex err_mu;
-  auto queue = [&](uint64_t k) -> int {
-    const uint64_t f = k * per_chunk, c = std::min(per_chunk, n - f);
-    int r = queue_node_images(x, f, c, host[k & 1], hipMemcpyDeviceToHost);
-    if (!r && hipEventRecord(ev[k & 1], ctx->stream) != hipSuccess) r = ctx->fail(PCV_E_HIP, "hipEventRecord");
-    return r;
-  };
-  if (!rc && chunks) rc = queue(0);
-  for (uint64_t k = 0; !rc && k < chunks; ++k) {  // stored mode only: in deflate mode there are no chunks here
-    if (k + 1 < chunks && (rc = queue(k + 1))) break;  // its buffer's writers (chunk k - 1) have finished
-    if (hipEventSynchronize(ev[k & 1]) != hipSuccess) {
-      rc = ctx->fail(PCV_E_HIP, "xray: image download failed");
-      break;
-    }
-    const uint64_t f = k * per_chunk, c = std::min(per_chunk, n - f);
-    const uint8_t* buf = host[k & 1];
-    std::atomic<uint64_t> next{0};
-    auto worker = [&]() {
-      std::vector<uint8_t> png(pcv_png_stored_size(W, W));
-      for (;;) {
-        const uint64_t i = next.fetch_add(1);
-        if (i >= c || failed.load()) return;
-        const uint64_t node = f + i;
-        const std::string name = node < nc ? quad_name(x->geo.deepest_level, x->geo.index[x->created[node]]) + ".png"
-                                           : quad_name(x->parent_level[node - nc], x->parent_index[node - nc]) + ".png";
-        pcv_png_stored_encode(buf + i * tile_bytes, W, W, png.data());
-        if (!write_at(dirfd, name, png.data(), png.size())) {
-          std::lock_guard<std::mutex> g(err_mu);
-          if (!failed.exchange(1)) first_error = "cannot write " + dir + "/" + name;
-        }
-      }
-    };
-    const unsigned nt = (unsigned)std::min<uint64_t>(nthreads, c);
-    std::vector<std::thread> pool;
-    for (unsigned t = 1; t < nt; ++t) pool.emplace_back(worker);
-    worker();
-    for (auto& th : pool) th.join();
-    if (failed.load()) break;
-  }
-  if (n) (void)hipStreamSynchronize(ctx->stream);
-  for (int k = 0; k < 2; ++k) {
-    if (ev[k]) (void)hipEventDestroy(ev[k]);
-    if (host[k]) ctx->host_release(host[k]);
-  }
-  if (!rc && failed.load()) rc = ctx->fail(PCV_E_IO, first_error);
-  if (!rc) {
-    double rect[3];
-    built_root_rect(x, rect);
-    std::vector<uint32_t> level(n);
-    std::vector<uint64_t> index(n);
-    pcv_xray_nodes(x, nullptr, n, level.data(), index.data());
-    std::string err;
-    if (!write_meta_file(dirfd, dir, x->root_level, x->root_index, rect, x->geo.deepest_level, W, level, index, &err)) rc = ctx->fail(PCV_E_IO, err);
-  }
-  ::close(dirfd);
-  return rc;
-}
-
-// ---- compressed tiles: the host side of pcv_xray_png.hip ----------------------------------------------------------------
-namespace {
-
-template <typename Fn>
-void xray_parallel_for(uint64_t n, bool parallel, Fn&& fn) {
-  unsigned nt = parallel ? std::min(8u, std::max(1u, std::thread::hardware_concurrency())) : 1u;
-  nt = (unsigned)std::min<uint64_t>(nt, n);
-  std::atomic<uint64_t> next{0};
-  auto worker = [&]() {
-    for (uint64_t i; (i = next.fetch_add(1)) < n;) fn(i);
-  };
-  std::vector<std::thread> pool;
-  for (unsigned t = 1; t < nt; ++t) pool.emplace_back(worker);
-  worker();
-  for (auto& th : pool) th.join();
-}
-
-// One chunk in flight on the device and one on the host: the scratch of pcv_xray_png_launch and two pinned buffers, each
-// for the compacted streams of a chunk and their offsets. Only offsets and compressed bytes are copied down.
-struct XrayPngPipe {
-  pcv_ctx* ctx = nullptr;
-  PcvPngWork wk;
-  uint8_t* host[2] = {nullptr, nullptr};
-  uint64_t* tab[2] = {nullptr, nullptr};
-  hipEvent_t ev_tab[2] = {nullptr, nullptr}, ev_bytes[2] = {nullptr, nullptr};
-  int open(pcv_ctx* c, uint32_t W, uint64_t tiles, int buffers) {
-    ctx = c;
-    int rc = pcv_xray_png_work_alloc(ctx, W, tiles, &wk);
-    for (int k = 0; !rc && k < buffers; ++k) {
-      if ((rc = ctx->host_alloc((void**)&host[k], tiles * wk.tile_bound)) || (rc = ctx->host_alloc((void**)&tab[k], 8 * (tiles + 1)))) break;
-      if (hipEventCreateWithFlags(&ev_tab[k], hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&ev_bytes[k], hipEventDisableTiming) != hipSuccess)
-        rc = ctx->fail(PCV_E_HIP, "hipEventCreate");
-    }
-    return rc;
-  }
-  // kernels of a chunk, then its offsets on their way down
-  int launch(int s, const uint8_t* a, uint64_t na, const uint8_t* b, uint64_t count) {
-    if (int rc = pcv_xray_png_launch(ctx, wk, a, na, b, count)) return rc;
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(tab[s], wk.offsets, 8 * (count + 1), hipMemcpyDeviceToHost, ctx->stream));
-    PCV_HIP_CHECK(ctx, hipEventRecord(ev_tab[s], ctx->stream));
-    return PCV_OK;
-  }
-  // once the offsets are here: exactly the compressed bytes on their way down
-  int fetch(int s, uint64_t count) {
-    PCV_HIP_CHECK(ctx, hipEventSynchronize(ev_tab[s]));
-    const uint64_t total = tab[s][count];
-    if (total > count * wk.tile_bound) return ctx->fail(PCV_E_HIP, "xray: compressed chunk larger than its bound");
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(host[s], wk.out, total, hipMemcpyDeviceToHost, ctx->stream));
-    PCV_HIP_CHECK(ctx, hipEventRecord(ev_bytes[s], ctx->stream));
-    return PCV_OK;
-  }
-  int wait(int s) {
-    PCV_HIP_CHECK(ctx, hipEventSynchronize(ev_bytes[s]));
-    return PCV_OK;
-  }
-  void close() {
-    if (!ctx) return;
-    (void)hipStreamSynchronize(ctx->stream);
-    for (int k = 0; k < 2; ++k) {
-      if (ev_tab[k]) (void)hipEventDestroy(ev_tab[k]);
-      if (ev_bytes[k]) (void)hipEventDestroy(ev_bytes[k]);
-      if (host[k]) ctx->host_release(host[k]);
-      if (tab[k]) ctx->host_release(tab[k]);
-    }
-    pcv_xray_png_work_free(ctx, &wk);
-  }
-};
-
-// The zlib streams of `count` device tiles, per_chunk at a time: src(f, c, &a, &na, &b) names tiles [f, f + c) for
-// pcv_xray_png_launch; use(f, c, streams, offsets) runs on the host while the next chunk is compressed and copied.
-template <typename Src, typename Use>
-int xray_deflate_chunks(pcv_ctx* ctx, uint32_t W, uint64_t count, uint64_t per_chunk, Src&& src, Use&& use) {
-  if (count == 0) return PCV_OK;
-  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  per_chunk = std::max<uint64_t>(1, std::min(per_chunk, count));
-  const uint64_t chunks = (count + per_chunk - 1) / per_chunk;
-  XrayPngPipe pipe;
-  int rc = pipe.open(ctx, W, per_chunk, chunks > 1 ? 2 : 1);
-  auto start = [&](uint64_t k) -> int {
-    const uint64_t f = k * per_chunk, c = std::min(per_chunk, count - f);
-    const uint8_t *a = nullptr, *b = nullptr;
-    uint64_t na = 0;
-    src(f, c, &a, &na, &b);
-    if (int r = pipe.launch((int)(k & 1), a, na, b, c)) return r;
-    return pipe.fetch((int)(k & 1), c);
-  };
-  if (!rc) rc = start(0);
-  for (uint64_t k = 0; !rc && k < chunks; ++k) {
-    if (k + 1 < chunks && (rc = start(k + 1))) break;  // its buffer's users (chunk k - 1) have finished
-    if ((rc = pipe.wait((int)(k & 1)))) break;
-    const uint64_t f = k * per_chunk, c = std::min(per_chunk, count - f);
-    rc = use(f, c, pipe.host[k & 1], pipe.tab[k & 1]);
-  }
-  pipe.close();
-  return rc;
-}
-
-// the device tiles of nodes [f, f + c): a built quadtree's leaves then parents, a merged quadtree's own levels
-void xray_device_tiles(const pcv_xray* x, uint64_t f, uint64_t c, const uint8_t** a, uint64_t* na, const uint8_t** b) {
-  const uint64_t tile_bytes = 4ull * x->W * x->W;
-  if (x->kind == kXrayMerged) {
-    *na = 0;
-    *b = reinterpret_cast<const uint8_t*>(x->d_parents) + (f - (x->node_index.size() - x->parent_index.size())) * tile_bytes;
-    return;
-  }
-  const uint64_t nc = x->created.size();
-  *na = f < nc ? std::min(c, nc - f) : 0;
-  *a = reinterpret_cast<const uint8_t*>(x->d_images) + f * tile_bytes;
-  *b = reinterpret_cast<const uint8_t*>(x->d_parents) + (f + *na - nc) * tile_bytes;
-}
-
-// nodes [first, first + count) whose images are on x's device, encoded in `mode`, each file to the sink
-int xray_device_node_files(pcv_xray* x, uint64_t first, uint64_t count, int mode, bool parallel, const XrayFileSink& sink) {
-  pcv_ctx* ctx = x->ctx;
-  const uint32_t W = x->W;
-  const uint64_t tile_bytes = 4ull * W * W;
-  const uint64_t per_chunk = std::max<uint64_t>(1, std::min(count, ctx->xray_chunk_bytes / tile_bytes));
-  std::atomic<int> failed{0};
-  if (mode == PCV_XRAY_PNG_DEFLATE) {
-    const int rc = xray_deflate_chunks(
-        ctx, W, count, per_chunk,
-        [&](uint64_t f, uint64_t c, const uint8_t** a, uint64_t* na, const uint8_t** b) { xray_device_tiles(x, first + f, c, a, na, b); },
-        [&](uint64_t f, uint64_t c, const uint8_t* streams, const uint64_t* offs) {
-          xray_parallel_for(c, parallel, [&](uint64_t i) {
-            if (failed.load()) return;
-            std::vector<uint8_t> png(kPcvPngWrap + offs[i + 1] - offs[i]);
-            pcv_png_wrap(W, W, streams + offs[i], offs[i + 1] - offs[i], png.data());
-            if (!sink(first + f + i, png.data(), png.size())) failed.store(1);
-          });
-          return failed.load() ? PCV_E_IO : PCV_OK;
-        });
-    return rc;
-  }
-  std::vector<uint8_t> images(per_chunk * tile_bytes);
-  for (uint64_t f = 0; f < count; f += per_chunk) {
-    const uint64_t c = std::min(per_chunk, count - f);
-    if (int rc = xray_node_images(x, first + f, c, PCV_MEM_HOST, images.data())) return rc;
-    xray_parallel_for(c, parallel, [&](uint64_t i) {
-      if (failed.load()) return;
-      std::vector<uint8_t> png(pcv_png_stored_size(W, W));
-      pcv_png_stored_encode(images.data() + i * tile_bytes, W, W, png.data());
-      if (!sink(first + f + i, png.data(), png.size())) failed.store(1);
-    });
-    if (failed.load()) return PCV_E_IO;
-  }
-  return PCV_OK;
-}
-
-}  // namespace
-
-// the files of nodes [first, first + count) of any kind of quadtree: opened nodes as their files are, the others encoded
-static int xray_node_files(pcv_xray* x, uint64_t first, uint64_t count, int mode, bool parallel, const XrayFileSink& sink) {
-  if (count == 0) return PCV_OK;
-  if (x->kind == kXrayBuilt) return xray_device_node_files(x, first, count, mode, parallel, sink);
-  if (x->kind == kXrayOpened) {
-    std::vector<uint8_t> file;
-    for (uint64_t i = first; i < first + count; ++i) {
-      const std::string path = x->dir + "/" + quad_name(x->node_level[i], x->node_index[i]) + ".png";
-      if (!read_file(path, file)) return xray_fail(x, PCV_E_IO, "xray: cannot read " + path);
-      if (!sink(i, file.data(), file.size())) return PCV_E_IO;
-    }
-    return PCV_OK;
-  }
-  pcv_ctx* ctx = x->ctx;
-  for (const XrayPartRef& r : x->parts)
-    if (!xray_part_alive(r)) return ctx->fail(PCV_E_INVALID, "xray: a part of this merged quadtree was freed before it");
-  uint64_t at = first;
-  const uint64_t end = first + count;
-  for (const XrayPartRef& r : x->parts) {
-    if (at >= end) break;
-    if (at >= r.first + r.count || r.count == 0) continue;
-    const uint64_t k = std::min(end, r.first + r.count) - at;
-    const uint64_t shift = r.first;
-    const int rc = xray_node_files(r.part, at - r.first, k, mode, parallel,
-                                   [&](uint64_t node, const uint8_t* file, uint64_t len) { return sink(node + shift, file, len); });
-    if (rc) return r.part->ctx == ctx || rc == PCV_E_IO ? rc : ctx->fail(rc, r.part->ctx ? r.part->ctx->last_error : pcv_host_last_error());
-    at += k;
-  }
-  return at < end ? xray_device_node_files(x, at, end - at, mode, parallel, sink) : PCV_OK;
-}
-
-// pcv_xray_write_dir_ex of a built quadtree in deflate mode: compressed chunks come down, the writer threads wrap and write
-static int xray_write_built_deflate(pcv_xray* x, int dirfd, const std::string& dir) {
-  const uint64_t nc = x->created.size(), n = nc + x->parent_index.size();
-  std::mutex err_mu;
-  std::string first_error;
-  const int rc = xray_node_files(x, 0, n, PCV_XRAY_PNG_DEFLATE, true, [&](uint64_t node, const uint8_t* file, uint64_t len) {
-    const std::string name = node < nc ? quad_name(x->geo.deepest_level, x->geo.index[x->created[node]]) + ".png"
-                                       : quad_name(x->parent_level[node - nc], x->parent_index[node - nc]) + ".png";
-    if (write_at(dirfd, name, file, len)) return true;
-    std::lock_guard<std::mutex> g(err_mu);
-    if (first_error.empty()) first_error = "cannot write " + dir + "/" + name;
-    return false;
-  });
-  return rc == PCV_E_IO && !first_error.empty() ? x->ctx->fail(rc, first_error) : rc;
-}
-
-namespace {
-// files appended to a caller's buffer with their offsets; out == nullptr: the offsets alone
-struct XrayPngAppend {
-  uint8_t* out;
-  uint64_t capacity, at = 0, index = 0;
-  uint64_t* offsets;
-  bool fits = true;
-  bool take(const uint8_t* file, uint64_t len) {
-    offsets[index++] = at;
-    if (out && len <= capacity - std::min(capacity, at)) std::memcpy(out + at, file, len);
-    else if (out) fits = false;
-    at += len;
-    offsets[index] = at;
-    return true;
-  }
-};
-}  // namespace
-
-extern "C" int pcv_xray_node_pngs(pcv_xray* x, uint64_t first, uint64_t count, int mode, uint64_t capacity, uint8_t* out, uint64_t* offsets) {
-  if (!x) return PCV_E_INVALID;
-  uint64_t n = 0;
-  pcv_xray_nodes(x, &n, 0, nullptr, nullptr);
-  if (first > n || count > n - first) return xray_fail(x, PCV_E_INVALID, "xray: node range past the end");
-  if (mode != PCV_XRAY_PNG_STORED && mode != PCV_XRAY_PNG_DEFLATE) return xray_fail(x, PCV_E_INVALID, "xray: unknown PNG mode");
-  if (!offsets) return xray_fail(x, PCV_E_INVALID, "null offsets");
-  if (mode == PCV_XRAY_PNG_DEFLATE && x->kind != kXrayOpened && x->W > PCV_XRAY_PNG_DEFLATE_MAX_EDGE)
-    return xray_fail(x, PCV_E_INVALID, "xray: compressed tiles are at most " + std::to_string(PCV_XRAY_PNG_DEFLATE_MAX_EDGE) + " pixels wide");
-  offsets[0] = 0;
-  XrayPngAppend app{out, capacity};
-  app.offsets = offsets;
-  const int rc = xray_node_files(x, first, count, mode, false, [&](uint64_t, const uint8_t* file, uint64_t len) { return app.take(file, len); });
-  if (rc) return rc;
-  if (!app.fits) return xray_fail(x, PCV_E_INVALID, "xray: capacity below the " + std::to_string(app.at) + " bytes of these files");
-  return PCV_OK;
-}
-
-extern "C" int pcv_xray_png_encode_tiles(pcv_ctx* ctx, const uint8_t* rgba, int mem, uint32_t w, uint64_t count, uint64_t chunk_tiles,
-                                         uint64_t capacity, uint8_t* out, uint64_t* offsets) {
-  if (!ctx) return PCV_E_INVALID;
-  if (!offsets || (count && !rgba) || w == 0) return ctx->fail(PCV_E_INVALID, "xray: bad arguments to pcv_xray_png_encode_tiles");
-  if (mem != PCV_MEM_HOST && mem != PCV_MEM_DEVICE) return ctx->fail(PCV_E_INVALID, "bad mem");
-  if (w > PCV_XRAY_PNG_DEFLATE_MAX_EDGE)
-    return ctx->fail(PCV_E_INVALID, "xray: compressed tiles are at most " + std::to_string(PCV_XRAY_PNG_DEFLATE_MAX_EDGE) + " pixels wide");
-  offsets[0] = 0;
-  if (count == 0) return PCV_OK;
-  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const uint64_t tile_bytes = 4ull * w * w;
-  PcvScratch sc(ctx);
-  const uint8_t* tiles = rgba;
-  if (mem == PCV_MEM_HOST) {
-    uint8_t* d = nullptr;
-    if (int rc = sc.get(&d, count * tile_bytes)) return rc;
-    PCV_HIP_CHECK(ctx, hipMemcpyAsync(d, rgba, count * tile_bytes, hipMemcpyHostToDevice, ctx->stream));
-    tiles = d;
-  }
-  XrayPngAppend app{out, capacity};
-  app.offsets = offsets;
-  const uint64_t per_chunk = chunk_tiles ? chunk_tiles : std::max<uint64_t>(1, ctx->xray_chunk_bytes / tile_bytes);
-  const int rc = xray_deflate_chunks(
-      ctx, w, count, per_chunk,
-      [&](uint64_t f, uint64_t, const uint8_t** a, uint64_t* na, const uint8_t** b) {
-        *na = 0;
-        *a = nullptr;
-        *b = tiles + f * tile_bytes;
-      },
-      [&](uint64_t, uint64_t c, const uint8_t* streams, const uint64_t* offs) {
-        std::vector<uint8_t> png;
-        for (uint64_t i = 0; i < c; ++i) {
-          png.resize(kPcvPngWrap + offs[i + 1] - offs[i]);
-          pcv_png_wrap(w, w, streams + offs[i], offs[i + 1] - offs[i], png.data());
-          app.take(png.data(), png.size());
-        }
-        return PCV_OK;
-      });
-  if (rc) return rc;
-  if (!app.fits) return ctx->fail(PCV_E_INVALID, "xray: capacity below the " + std::to_string(app.at) + " bytes of these files");
-  return PCV_OK;
-}
-
-extern "C" int pcv_ctx_set_xray_chunk_bytes(pcv_ctx* ctx, uint64_t bytes) {
-  if (!ctx) return PCV_E_INVALID;
-  ctx->xray_chunk_bytes = bytes ? bytes : 64ull << 20;
-  return PCV_OK;
-}

@@ -1,4 +1,4 @@
-// pcv_xray_png.h — the device encoder of compressed xray tiles (pcv_xray_png.hip) as pcv_xray.hip drives it.
+// pcv_xray_png.h — the device encoder of compressed xray tiles (pcv_xray_png.hip) as pcv_xray_files.hip drives it.
 #pragma once
 #include "pcv_internal.h"
 #include "pcv_xray_png_dev.h"

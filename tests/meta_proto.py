@@ -14,7 +14,7 @@ from google.protobuf import descriptor_pb2, descriptor_pool, message_factory
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_proto_schema.json")
 _T = descriptor_pb2.FieldDescriptorProto
 _SCALAR = {"double": _T.TYPE_DOUBLE, "float": _T.TYPE_FLOAT, "int32": _T.TYPE_INT32, "int64": _T.TYPE_INT64,
-           "uint64": _T.TYPE_UINT64, "string": _T.TYPE_STRING}
+           "uint64": _T.TYPE_UINT64, "uint32": _T.TYPE_UINT32, "string": _T.TYPE_STRING}
 
 # message -> [(name, number, type, repeated)]; types: scalar name, or message / enum name
 SCHEMA = {
@@ -37,17 +37,36 @@ SCHEMA = {
 ENUMS = {"PositionEncoding": [("INVALID", 0), ("Uint8", 1), ("Uint16", 2), ("Float32", 3), ("Float64", 4)]}
 ONEOF = {"Meta": ("data", ("octree", "s2"))}
 
-_classes = None
+# the xray quadtree's Meta (xray_proto_rust/src/proto.proto:21-54), package xray.proto
+XRAY_SCHEMA = {
+    "Vector2f": [("x", 1, "float", False), ("y", 2, "float", False)],
+    "Vector2d": [("x", 1, "double", False), ("y", 2, "double", False)],
+    "Rect": [("min", 3, "Vector2d", False), ("edge_length", 4, "double", False), ("deprecated_min", 1, "Vector2f", False),
+             ("deprecated_edge_length", 2, "float", False)],
+    "NodeId": [("level", 1, "uint32", False), ("index", 2, "uint64", False)],
+    "Meta": [("version", 1, "int32", False), ("bounding_rect", 2, "Rect", False), ("deepest_level", 3, "uint32", False),
+             ("tile_size", 4, "uint32", False), ("nodes", 5, "NodeId", True)],
+}
+
+_classes = {}
 
 
 def classes():
     """{message name: generated class} for package point_viewer.proto."""
-    global _classes
-    if _classes is not None:
-        return _classes
+    return _build("point_viewer.proto", SCHEMA, ENUMS, ONEOF)
+
+
+def xray_classes():
+    """{message name: generated class} for package xray.proto."""
+    return _build("xray.proto", XRAY_SCHEMA, {}, {})
+
+
+def _build(package, SCHEMA, ENUMS, ONEOF):
+    if package in _classes:
+        return _classes[package]
     fd = descriptor_pb2.FileDescriptorProto()
-    fd.name = "pcv_test_meta.proto"
-    fd.package = "point_viewer.proto"
+    fd.name = "pcv_test_%s.proto" % package.replace(".", "_")
+    fd.package = package
     fd.syntax = "proto3"
     for ename, values in ENUMS.items():
         e = fd.enum_type.add()
@@ -67,15 +86,15 @@ def classes():
             if typ in _SCALAR:
                 f.type = _SCALAR[typ]
             elif typ in ENUMS:
-                f.type, f.type_name = _T.TYPE_ENUM, ".point_viewer.proto." + typ
+                f.type, f.type_name = _T.TYPE_ENUM, "." + package + "." + typ
             else:
-                f.type, f.type_name = _T.TYPE_MESSAGE, ".point_viewer.proto." + typ
+                f.type, f.type_name = _T.TYPE_MESSAGE, "." + package + "." + typ
             if mname in ONEOF and fname in ONEOF[mname][1]:
                 f.oneof_index = 0
     pool = descriptor_pool.DescriptorPool()
     pool.Add(fd)
-    _classes = {m: message_factory.GetMessageClass(pool.FindMessageTypeByName("point_viewer.proto." + m)) for m in SCHEMA}
-    return _classes
+    _classes[package] = {m: message_factory.GetMessageClass(pool.FindMessageTypeByName(package + "." + m)) for m in SCHEMA}
+    return _classes[package]
 
 
 def read_proto(path):

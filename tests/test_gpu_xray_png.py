@@ -109,6 +109,45 @@ def test_chunk_boundary(ctx, trees, tmp_path):  # noqa: F811
         ctx.set_xray_chunk_bytes(0)
 
 
+def test_stored_chunk_boundary(ctx, trees, cloud, tmp_path):  # noqa: F811
+    """Stored mode through the chunked download it shares with every kind of quadtree: built, a live merge, a merge of
+    opened and live parts, and a range across the leaves | parents seam, three tiles a chunk and then one."""
+    xt = trees[16]
+    want = host_pngs(xt, "stored")
+    nc = len(xt.created_ids)
+    assert len(want) > 7 and nc % 3 != 0 and len(want) % 3 != 0  # a chunk across leaves | parents, a ragged last one
+    xt.write(tmp_path / "default")
+    parts = shards(cloud, 1, "colored", "transparent")
+    live = ctx.xray_merge(parts, "transparent")
+    live_want = host_pngs(live, "stored")
+    dirs = write_parts(parts[:2], tmp_path / "parts")
+    mixed = ctx.xray_merge([parts[3], ctx.xray_open(dirs[1])[0], parts[2], ctx.xray_open(dirs[0])[0]], "transparent")
+    copied = {f: (d / f).read_bytes() for d in dirs for f in os.listdir(d) if f.endswith(".png")}
+    assert len(copied) > 2 and len(live.node_ids) == len(mixed.node_ids) > len(copied) + 2
+
+    def files(d, ids):
+        assert set(os.listdir(d)) == {n + ".png" for n in ids} | {"meta.pb"}
+        return [(d / (n + ".png")).read_bytes() for n in ids]
+    try:
+        for k, chunk_bytes in enumerate((3 * 4 * W * W, 1)):  # three tiles a chunk; below a tile: one tile a chunk
+            ctx.set_xray_chunk_bytes(chunk_bytes)
+            xt.write(tmp_path / f"built{k}")
+            assert files(tmp_path / f"built{k}", xt.node_ids) == want
+            assert (tmp_path / f"built{k}" / "meta.pb").read_bytes() == (tmp_path / "default" / "meta.pb").read_bytes()
+            live.write(tmp_path / f"live{k}")
+            assert files(tmp_path / f"live{k}", live.node_ids) == live_want
+            for png in ("stored", "deflate"):
+                out = tmp_path / f"mixed{k}_{png}"
+                mixed.write(out, png=png)
+                encoded = dict(zip(mixed.node_ids, host_pngs(mixed, png)))
+                for name, got in zip(mixed.node_ids, files(out, mixed.node_ids)):
+                    assert got == copied.get(name + ".png", encoded[name]), (png, name)
+            assert xt.node_pngs(nc - 2, 5, png="stored") == want[nc - 2:nc + 3]
+            assert xt.node_pngs(png="stored") == want and live.node_pngs(png="stored") == live_want
+    finally:
+        ctx.set_xray_chunk_bytes(0)
+
+
 def test_merge_of_deflate_shards(ctx, cloud, tmp_path):  # noqa: F811
     whole = build(cloud, "xray", "white")
     parts = shards(cloud, 1, "xray", "white")

@@ -136,6 +136,40 @@ def test_sanitizer_build_of_the_decoder_runs_clean(tmp_path):
     assert decodes > 1000 + 3 * len((tmp_path / "good.png").read_bytes()) and 0 < accepted < decodes
 
 
+def test_sanitizer_build_of_the_meta_code_runs_clean(tmp_path):
+    """csrc/pcv_xray_meta.cpp and tests/xray_meta_driver.cpp as one stand-alone program with ASan and UBSan: a Meta of 20
+    nodes encoded equal to the protobuf runtime's bytes (tests/meta_proto.py) and parsed back, then every truncation and
+    every single-byte change of that file and of a version-2 file with the deprecated f32 fields: each fails or gives a
+    Meta inside the ranges."""
+    import meta_proto
+    X = meta_proto.xray_classes()
+    nodes = [(i % 6, (i * 2654435761) % 4 ** (i % 6)) for i in range(20)]
+    files = []
+    for version in (3, 2):
+        m = X["Meta"](version=version, deepest_level=5, tile_size=256)
+        if version == 3:
+            m.bounding_rect.min.x, m.bounding_rect.min.y, m.bounding_rect.edge_length = 0.1, -333333.25, 0.3
+        else:
+            r = m.bounding_rect
+            r.deprecated_min.x, r.deprecated_min.y, r.deprecated_edge_length = 0.5, -1024.25, 2048.0
+        for level, index in nodes:
+            m.nodes.add(level=level, index=index)
+        files.append(m.SerializeToString(deterministic=True))
+        (tmp_path / ("v%d.pb" % version)).write_bytes(files[-1])
+    # the hand-written test encoder of the directories below agrees with the runtime too
+    assert files[0] == MO.encode_meta((0.1, -333333.25, 0.3), 5, 256, nodes)
+    assert files[1] == MO.encode_meta((0.5, -1024.25, 2048.0), 5, 256, nodes, version=2, deprecated=True)
+    exe = tmp_path / "xray_meta_driver"
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-static-libasan", "-static-libubsan",  # the runtimes inside the program: nothing to preload
+                           os.path.join(ROOT, "tests", "xray_meta_driver.cpp"),
+                           os.path.join(ROOT, "point_cloud_viewer_amd", "csrc", "pcv_xray_meta.cpp"), "-o", str(exe)])
+    p = subprocess.run([str(exe), str(tmp_path / "v3.pb"), str(tmp_path / "v2.pb")], capture_output=True, text=True)
+    assert p.returncode == 0, (p.stdout + p.stderr)[-2000:]
+    parses, accepted = (int(t) for t in p.stdout.split())
+    assert parses == sum(len(f) + 1 + 255 * len(f) for f in files) and 0 < accepted < parses
+
+
 # ---- directories ---------------------------------------------------------------------------------------------------
 RECT = (0.1, -1e6 / 3, 0.3)
 
