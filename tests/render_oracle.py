@@ -45,12 +45,14 @@ def clip_f32(matrix, p):
 
 def draw_nodes(nodes, matrix, W, H, point_size, lut):
     """One frame from its drawn nodes, in draw order: nodes = [dict(encoding, xyz, rgb, cube_min, cube_edge)].
-    Returns dict(image (H, W, 4) u8, depth (H, W) f32, points_submitted, points_drawn, pixels_covered)."""
+    Returns dict(image (H, W, 4) u8, depth (H, W) f32, winner (H, W) i64: the draw rank of the pixel's point or -1,
+    points_submitted, points_drawn, pixels_covered)."""
     assert 1 <= point_size <= MAX_POINT_SIZE
     image = np.zeros((H, W, 4), np.uint8)
     image[..., 3] = 255
     depth = np.ones((H, W), F32)
-    out = dict(image=image, depth=depth, points_submitted=0, points_drawn=0, pixels_covered=0)
+    winner = np.full((H, W), -1, np.int64)
+    out = dict(image=image, depth=depth, winner=winner, points_submitted=0, points_drawn=0, pixels_covered=0)
     if not nodes:
         return out
     p = np.concatenate([attribute(nd["encoding"], nd["xyz"]) * float(nd["cube_edge"]) + np.asarray(nd["cube_min"], np.float64)[None, :]
@@ -104,6 +106,7 @@ def draw_nodes(nodes, matrix, W, H, point_size, lut):
     win = (keys & np.uint64(0xffffffff)).astype(np.int64)
     flat = image.reshape(-1, 4)
     flat[pix, :3] = lut[rgb[win]]
+    winner.reshape(-1)[pix] = win
     depth.reshape(-1)[pix] = (keys >> np.uint64(32)).astype(np.uint32).view(F32)
     out["pixels_covered"] = int(pix.size)
     return out
