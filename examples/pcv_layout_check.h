@@ -53,5 +53,7 @@ PCV_SA(offsetof(pcv_render_params, width) == 0 && offsetof(pcv_render_params, he
            offsetof(pcv_render_params, gamma) == 12 && offsetof(pcv_render_params, max_nodes) == 16 &&
            offsetof(pcv_render_params, max_workspace_bytes) == 24,
        "pcv_render_params fields");
+PCV_SA(sizeof(pcv_render_overlay) == 8, "pcv_render_overlay");
+PCV_SA(offsetof(pcv_render_overlay, flags) == 0 && offsetof(pcv_render_overlay, outline_rgba) == 4, "pcv_render_overlay fields");
 
 #endif

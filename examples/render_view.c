@@ -1,12 +1,15 @@
 /* render_view.c — one frame of the viewer over the C ABI in plain C11: an octree directory is opened, one camera goes to
  * pcv_render_views (the draw loop of sdl_viewer/src/lib.rs:158-209 on the device), and the frame is written as a PNG.
  *
- *   render_view <octree dir> --matrix <16 doubles> --size WxH [--point-size s] [--gamma g] [--max-nodes n] -o out.png
+ *   render_view <octree dir> --matrix <16 doubles> --size WxH [--point-size s] [--gamma g] [--max-nodes n]
+ *               [--show-octree-nodes] -o out.png
  *   render_view <octree dir> --look-at <eye xyz> <target xyz> <fovy radians> --size WxH [...] -o out.png
  *
  * --matrix: world_to_gl, column-major, as the viewer uploads it. --look-at: a right-handed look-at view with +z up (+y when
  * looking along z) under Perspective3::new(W / H, fovy, near, far), far = the distance to the farthest corner of the octree's
- * bounding box, near = far / 10 000. Prints "<nodes visible> <nodes drawn> <points submitted> <points drawn> <pixels covered>".
+ * bounding box, near = far / 10 000. --show-octree-nodes: the viewer's `O` key, the yellow wireframe of every drawn node's cube
+ * (pcv_render_views_ex with PCV_RENDER_OUTLINE_NODES). Prints "<nodes visible> <nodes drawn> <points submitted> <points drawn>
+ * <pixels covered>", and with outlines " <segments submitted> <segments drawn> <outline pixels>" after them.
  */
 #include <math.h>
 #include <stdio.h>
@@ -50,13 +53,14 @@ static void look_at(const double eye[3], const double target[3], double fovy, do
 int main(int argc, char** argv) {
   const char* usage =
       "usage: render_view <octree dir> --matrix <16 doubles> | --look-at <eye xyz> <target xyz> <fovy> --size WxH "
-      "[--point-size s] [--gamma g] [--max-nodes n] -o out.png\n";
+      "[--point-size s] [--gamma g] [--max-nodes n] [--show-octree-nodes] -o out.png\n";
   double matrix[16], eye[3] = {0, 0, 0}, target[3] = {0, 0, 0}, fovy = 0.0;
   int have_matrix = 0, have_look = 0;
   pcv_render_params params;
   memset(&params, 0, sizeof(params));
   params.point_size = 1.0f;
   params.gamma = 1.0f;
+  pcv_render_overlay overlay = {0, PCV_RENDER_OUTLINE_YELLOW};
   const char* out = NULL;
   if (argc < 2) {
     fputs(usage, stderr);
@@ -79,6 +83,8 @@ int main(int argc, char** argv) {
       params.gamma = strtof(argv[++i], NULL);
     } else if (strcmp(argv[i], "--max-nodes") == 0 && i + 1 < argc) {
       params.max_nodes = (uint32_t)strtoul(argv[++i], NULL, 10);
+    } else if (strcmp(argv[i], "--show-octree-nodes") == 0) {
+      overlay.flags |= PCV_RENDER_OUTLINE_NODES;
     } else if (strcmp(argv[i], "-o") == 0 && i + 1 < argc) {
       out = argv[++i];
     } else {
@@ -111,11 +117,12 @@ int main(int argc, char** argv) {
     memcpy(shape.params, matrix, sizeof(matrix));
     rc = pcv_shapes_create(ctx, &shape, 1, &frusta);
   }
-  if (rc == PCV_OK) rc = pcv_render_views(ctx, frusta, tree, &params, &frame);
+  if (rc == PCV_OK) rc = pcv_render_views_ex(ctx, frusta, tree, &params, &overlay, &frame);
   int32_t status = 0;
   uint32_t visible = 0, drawn_nodes = 0;
-  uint64_t submitted = 0, drawn = 0, covered = 0, need = 0;
+  uint64_t submitted = 0, drawn = 0, covered = 0, need = 0, seg_submitted = 0, seg_drawn = 0, outline_pixels = 0;
   if (rc == PCV_OK) rc = pcv_render_info(frame, 0, &status, &visible, &drawn_nodes, &submitted, &drawn, &covered);
+  if (rc == PCV_OK) rc = pcv_render_outline_info(frame, 0, &seg_submitted, &seg_drawn, &outline_pixels);
   if (rc == PCV_OK && status != 0) fprintf(stderr, "render_view: the matrix is not a camera (status %d): the frame is empty\n", (int)status);
   if (rc == PCV_OK) {
     rgba = (uint8_t*)malloc((size_t)4 * params.width * params.height);
@@ -131,9 +138,12 @@ int main(int argc, char** argv) {
     if (!f || fwrite(png, 1, (size_t)need, f) != (size_t)need) rc = PCV_E_IO;
     if (f && fclose(f) != 0) rc = PCV_E_IO;
   }
-  if (rc == PCV_OK)
-    printf("%u %u %llu %llu %llu\n", visible, drawn_nodes, (unsigned long long)submitted, (unsigned long long)drawn, (unsigned long long)covered);
-  else
+  if (rc == PCV_OK) {
+    printf("%u %u %llu %llu %llu", visible, drawn_nodes, (unsigned long long)submitted, (unsigned long long)drawn, (unsigned long long)covered);
+    if (overlay.flags & PCV_RENDER_OUTLINE_NODES)
+      printf(" %llu %llu %llu", (unsigned long long)seg_submitted, (unsigned long long)seg_drawn, (unsigned long long)outline_pixels);
+    printf("\n");
+  } else
     fprintf(stderr, "render_view: %s (%d)\n", ctx && rc != PCV_E_IO ? pcv_last_error(ctx) : "cannot write the PNG", rc);
   free(png);
   free(rgba);

@@ -997,6 +997,33 @@ int pcv_render_gamma_lut(float gamma, uint8_t lut[256]);
  * (8 bytes per pixel) exceeds max_workspace_bytes is PCV_E_OOM. A failed call leaves nothing allocated. The octree may be a
  * built one or one opened from a directory; it and `frusta` may be freed after the call. */
 int pcv_render_views(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree, const pcv_render_params* params, pcv_render** out);
+/* show_octree_nodes (lib.rs:202-208, box_drawer.rs): what pcv_render_views_ex draws on top of the points. With
+ * PCV_RENDER_OUTLINE_NODES the wireframe of every drawn node's bounding cube is drawn right after the node's points, under
+ * the same depth test, in outline_rgba stored as given (the outline shader applies no gamma; the viewer's YELLOW is
+ * PCV_RENDER_OUTLINE_YELLOW). The restatement: the cube's 12 edges in box_drawer.rs's index order,
+ * corners min | min + edge to clip space as a point's position; Liang-Barsky in f32 against w > 0, w + x, w - x, w + y,
+ * w - y, w + z, w - z >= 0 in that order (t = d0 / (d0 - d1), endpoints a + t * (b - a)); a segment with a non-finite clip
+ * coordinate, a clipped w outside (0, inf) or a non-finite window coordinate is dropped; width 1 along the major axis (a tie
+ * goes to x): every pixel centre in [min, max), the other coordinate and zw interpolated in f32, zw clamped to [0, 1]. A
+ * node owns n + 1 consecutive draw ranks, the last for its outline: at equal depth an outline loses to its own node's points
+ * and to everything drawn before, and wins against every later node. The limit of 2^32 - 1 ranks per view includes them. */
+#define PCV_RENDER_OUTLINE_NODES 1u
+#define PCV_RENDER_OUTLINE_YELLOW {255, 255, 0, 255}
+typedef struct pcv_render_overlay {
+  uint32_t flags;           /* PCV_RENDER_OUTLINE_NODES or 0; any other bit is PCV_E_INVALID */
+  uint8_t outline_rgba[4];  /* read only with PCV_RENDER_OUTLINE_NODES */
+} pcv_render_overlay;
+/* Host only, no context: PCV_E_INVALID for unknown flag bits, with the reason in `message` (NUL-terminated, cut to
+ * `capacity`; nullable). A null overlay is valid: nothing is drawn on top. */
+int pcv_render_check_overlay(const pcv_render_overlay* overlay, char* message, uint64_t capacity);
+/* pcv_render_views with an overlay. A null overlay or flags == 0 is pcv_render_views itself: the same launches, the same
+ * bytes. With outlines on, pixels_covered of pcv_render_info counts every pixel that is not background. */
+int pcv_render_views_ex(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree, const pcv_render_params* params,
+                        const pcv_render_overlay* overlay, pcv_render** out);
+/* Per view (each output nullable): 12 per drawn node, the segments that survived the clip, the pixels of the final image an
+ * outline won. All zero without PCV_RENDER_OUTLINE_NODES and for a view whose status is not 0. */
+int pcv_render_outline_info(pcv_render* r, uint32_t view, uint64_t* segments_submitted, uint64_t* segments_drawn,
+                            uint64_t* outline_pixels);
 /* Per view (each output nullable): the visible-node status, the length of the visible list, the nodes drawn after the cut,
  * the points of the drawn nodes (node_drawer.rs:132-134), the points inside the clip volume, the pixels some point covers. */
 int pcv_render_info(pcv_render* r, uint32_t view, int32_t* status, uint32_t* nodes_visible, uint32_t* nodes_drawn,

@@ -8,7 +8,7 @@ from ._lib import (PCV_E_DEPTH, PCV_E_HIP, PCV_E_INVALID, PCV_E_IO, PCV_E_NOT_FO
                    PcvError, load_library)
 from .octree import (Aabb, Context, OctreeResult, QueryBatch, RenderedViews, Shapes, XrayTiles, build_octree, build_octree_from_file,  # noqa: F401
                      level_shortcuts, level_table, node_name, quadtree_node_id, quadtree_node_name, read_ply,
-                     render_check_params, render_gamma_lut, render_params,
+                     render_check_overlay, render_check_params, render_gamma_lut, render_overlay, render_params,
                      web_mercator_rect_from_zoomed, wmr_contains, wmr_corners, wmr_from_lat_lng, wmr_math, wmr_project, wmr_to_lat_lng,
                      merge_xray_quadtrees, png_decode, xray_check_params, xray_coloring, xray_finalize, xray_lanczos_taps, xray_leaf_tiles,
                      xray_merge_check, xray_open_host, xray_params, xray_png_encode, xray_png_encode_tiles)

@@ -79,7 +79,13 @@ class RenderParams(C.Structure):
                 ("max_nodes", C.c_uint32), ("max_workspace_bytes", C.c_uint64)]
 
 
+class RenderOverlay(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("outline_rgba", C.c_uint8 * 4)]
+
+
 RENDER_MAX_POINT_SIZE = 64  # PCV_RENDER_MAX_POINT_SIZE
+RENDER_OUTLINE_NODES = 1  # PCV_RENDER_OUTLINE_NODES
+RENDER_OUTLINE_YELLOW = (255, 255, 0, 255)  # PCV_RENDER_OUTLINE_YELLOW: the viewer's YELLOW
 XRAY_XRAY, XRAY_COLORED, XRAY_HEIGHT_STDDEV, XRAY_COLORED_WITH_INTENSITY = 0, 1, 2, 3
 XRAY_JET, XRAY_PURPLISH = 0, 1
 XRAY_BG_WHITE, XRAY_BG_TRANSPARENT = 0, 1
@@ -296,6 +302,9 @@ _SIGNATURES = {
     "pcv_render_images": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_int]),
     "pcv_render_depth": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_int]),
     "pcv_render_free": (None, [_vp]),
+    "pcv_render_check_overlay": (C.c_int, [C.POINTER(RenderOverlay), C.c_char_p, C.c_uint64]),
+    "pcv_render_views_ex": (C.c_int, [_vp, _vp, _vp, C.POINTER(RenderParams), C.POINTER(RenderOverlay), C.POINTER(_vp)]),
+    "pcv_render_outline_info": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "pcv_octree_nodes_blob": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pcv_transform_points": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(Points), _vp, _vp, _vp]),
 }

@@ -130,6 +130,7 @@ enum PcvKernelId {
   PCV_K_XRAY_PNG_BAND,        // pcv_xray_png.hip: one wave per (tile, band): filter, run tokens, bit buffer in LDS, the band's slot
   PCV_K_XRAY_PNG_LAYOUT,      // pcv_xray_png.hip: band offsets and Adler-32 per tile, tile offsets of the chunk
   PCV_K_XRAY_PNG_GATHER,      // pcv_xray_png.hip: the bands of every tile into one contiguous zlib stream
+  PCV_K_RENDER_OUTLINE,       // pcv_render_views_ex: the node cubes' edges clipped and rasterised into the key planes
   PCV_K_COUNT
 };
 

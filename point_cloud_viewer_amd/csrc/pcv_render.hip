@@ -12,6 +12,13 @@
 //   K_rr  render_resolve  a thread per pixel: key -> rank -> (node, index) by binary search in the view's u64 prefix of
 //                         point counts -> colour bytes -> gamma table -> RGBA8, zw to the depth plane, covered pixels
 //
+// With show_octree_nodes (pcv_render_views_ex, PCV_RENDER_OUTLINE_NODES; lib.rs:202-208, box_drawer.rs) one more runs between
+// the two, and the prefix counts n + 1 ranks per node: the last rank of a node is its outline's:
+//
+//   K_ro  render_outline  a lane per (view, drawn node, edge): the cube's two corners to clip space as a point's position,
+//                         Liang-Barsky against the seven half-spaces in f32, window transform, width-1 raster along the
+//                         major axis, one atomicMin of (bits(zw) << 32 | outline rank) per fragment
+//
 // An integer minimum does not depend on the order the atomics arrive in, so a frame's bytes do not depend on scheduling.
 // Every f32 step is a single correctly rounded operation (-ffp-contract=off, correctly rounded f32 division, denormals
 // kept); no libm call is made on the device: the gamma table comes from the host.
@@ -19,6 +26,7 @@
 // pixel (L2 atomics); which of the two binds depends on how much of the view's points the frustum keeps.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <vector>
 
@@ -164,12 +172,120 @@ __global__ __launch_bounds__(256) void render_splat_kernel(RenderSplatArgs a) {
   }
 }
 
+// box_drawer.rs:63-98, a nibble per entry: the corners as picks (bit 0 x, bit 1 y, bit 2 z: set takes min + edge, the
+// table's +1), and the two corners of each of the 12 edges in index order
+constexpr uint32_t kCornerPick = 0x23106754u;
+constexpr uint64_t kEdgeFrom = 0x346176543210ull, kEdgeTo = 0x702547650321ull;
+constexpr float kF32Max = 3.40282347e+38f;
+
+struct RenderOutlineArgs {
+  const uint32_t* seg_node;
+  const uint32_t* seg_view;
+  const uint64_t* seg_rank;      // nseg + 1: ranks before each segment (n + 1 per segment), over all views
+  const uint64_t* view_seg;      // V + 1
+  uint64_t s0, s1;               // the group's segments
+  const BatchNode* nodes;
+  const PcvShapeDev* shapes;
+  unsigned long long* keys;      // the group's key planes
+  unsigned long long* seg_drawn; // per view of the call: segments that survived the clip
+  uint32_t view0;
+  uint32_t W, H;
+  float half_w, half_h;
+};
+
+// a corner of the node's cube in clip space: steps 2-3 of a point with the attribute at 0 or 1
+__device__ __forceinline__ void outline_corner(const BatchNode& nd, const double* mm, uint32_t pick, float c[4]) {
+  const double px = (pick & 1u) ? nd.cube_min[0] + nd.cube_edge : nd.cube_min[0];
+  const double py = (pick & 2u) ? nd.cube_min[1] + nd.cube_edge : nd.cube_min[1];
+  const double pz = (pick & 4u) ? nd.cube_min[2] + nd.cube_edge : nd.cube_min[2];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) c[r] = (float)(((mm[r] * px + mm[4 + r] * py) + mm[8 + r] * pz) + mm[12 + r]);
+}
+
+__device__ __forceinline__ bool f32_finite(float v) { return __builtin_fabsf(v) <= kF32Max; }  // (a NaN fails)
+
+// one half-space of Liang-Barsky: d0, d1 the endpoints' distances, `strict` for w > 0. Returns false when both are outside.
+__device__ __forceinline__ bool clip_plane(float d0, float d1, bool strict, float& t_in, float& t_out) {
+  const bool in0 = strict ? d0 > 0.0f : d0 >= 0.0f, in1 = strict ? d1 > 0.0f : d1 >= 0.0f;
+  const float t = d0 / (d0 - d1);  // read only where one end is outside (a NaN fails both comparisons)
+  if (in0 && !in1 && t < t_out) t_out = t;
+  if (!in0 && in1 && t > t_in) t_in = t;
+  return in0 || in1;
+}
+
+// K_ro: item = segment * 12 + edge over the group's segments; the grid strides over the items
+__global__ __launch_bounds__(256) void render_outline_kernel(RenderOutlineArgs a) {
+  const uint64_t items = (a.s1 - a.s0) * 12, plane = (uint64_t)a.W * a.H;
+  for (uint64_t it = (uint64_t)blockIdx.x * 256 + threadIdx.x; it < items; it += (uint64_t)gridDim.x * 256) {
+    const uint64_t s = a.s0 + it / 12;
+    const uint32_t e = (uint32_t)(it % 12), view = a.seg_view[s];
+    const BatchNode nd = a.nodes[a.seg_node[s]];
+    const double* mm = a.shapes[view].clip_from_query;
+    float p[4], q[4];
+    outline_corner(nd, mm, (kCornerPick >> (4u * (uint32_t)((kEdgeFrom >> (4u * e)) & 15u))) & 7u, p);
+    outline_corner(nd, mm, (kCornerPick >> (4u * (uint32_t)((kEdgeTo >> (4u * e)) & 15u))) & 7u, q);
+    bool alive = true;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) alive = alive && f32_finite(p[r]) && f32_finite(q[r]);
+    if (!alive) continue;
+    // w > 0, then w + x, w - x, w + y, w - y, w + z, w - z >= 0: every distance one f32 operation on the unclipped endpoints
+    float t_in = 0.0f, t_out = 1.0f;
+    alive = clip_plane(p[3], q[3], true, t_in, t_out);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      alive = clip_plane(p[3] + p[r], q[3] + q[r], false, t_in, t_out) && alive;
+      alive = clip_plane(p[3] - p[r], q[3] - q[r], false, t_in, t_out) && alive;
+    }
+    if (!alive || t_in > t_out) continue;
+    float c0[4], c1[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float d = q[r] - p[r];
+      c0[r] = t_in > 0.0f ? p[r] + t_in * d : p[r];
+      c1[r] = t_out < 1.0f ? p[r] + t_out * d : q[r];
+    }
+    if (!(c0[3] > 0.0f && c0[3] <= kF32Max && c1[3] > 0.0f && c1[3] <= kF32Max)) continue;
+    const float x0 = (c0[0] / c0[3] + 1.0f) * a.half_w, y0 = (c0[1] / c0[3] + 1.0f) * a.half_h, z0 = (c0[2] / c0[3]) * 0.5f + 0.5f;
+    const float x1 = (c1[0] / c1[3] + 1.0f) * a.half_w, y1 = (c1[1] / c1[3] + 1.0f) * a.half_h, z1 = (c1[2] / c1[3]) * 0.5f + 0.5f;
+    if (!(f32_finite(x0) && f32_finite(y0) && f32_finite(z0) && f32_finite(x1) && f32_finite(y1) && f32_finite(z1))) continue;
+    atomicAdd(a.seg_drawn + view, 1ull);
+    // width 1: the pixel centres of the major axis inside [min, max), one fragment each
+    const bool x_major = __builtin_fabsf(x1 - x0) >= __builtin_fabsf(y1 - y0);
+    const float m0 = x_major ? x0 : y0, m1 = x_major ? x1 : y1, n0 = x_major ? y0 : x0, n1 = x_major ? y1 : x1;
+    const uint32_t size_m = x_major ? a.W : a.H, size_n = x_major ? a.H : a.W;
+    const float lo = m0 < m1 ? m0 : m1, hi = m0 < m1 ? m1 : m0;
+    if (!(lo < hi)) continue;
+    // both ends are brought into [-1, size + 1] before the conversion, then found by testing the predicate itself
+    const float top = (float)size_m + 1.0f;
+    int32_t i0 = (int32_t)(lo < -1.0f ? -1.0f : lo > top ? top : lo) - 1, i1 = (int32_t)(hi < -1.0f ? -1.0f : hi > top ? top : hi) + 1;
+    if (i0 < 0) i0 = 0;
+    if (i1 > (int32_t)size_m - 1) i1 = (int32_t)size_m - 1;
+    while (i0 <= i1 && !(lo <= (float)i0 + 0.5f)) ++i0;
+    while (i1 >= i0 && !((float)i1 + 0.5f < hi)) --i1;
+    // the outline's rank is the last of its node's n + 1
+    const unsigned long long rank = (unsigned long long)(uint32_t)(a.seg_rank[s + 1] - 1 - a.seg_rank[a.view_seg[view]]);
+    unsigned long long* keys = a.keys + (uint64_t)(view - a.view0) * plane;
+    const float dm = m1 - m0, dn = n1 - n0, dz = z1 - z0, limit = (float)size_n;
+    for (int32_t i = i0; i <= i1; ++i) {
+      const float t = (((float)i + 0.5f) - m0) / dm;
+      const float n = n0 + t * dn;
+      if (!(n >= 0.0f && n < limit)) continue;  // outside the image (or NaN); inside, the conversion below is floorf
+      const uint32_t j = (uint32_t)(int32_t)n;
+      float zw = z0 + t * dz;
+      if (!(zw > 0.0f)) zw = 0.0f;  // (a NaN and -0.0f too: the key orders by the bit pattern)
+      if (zw > 1.0f) zw = 1.0f;
+      const uint32_t gx = x_major ? (uint32_t)i : j, gy = x_major ? j : (uint32_t)i;
+      atomicMin(keys + (uint64_t)(a.H - 1u - gy) * a.W + gx, ((unsigned long long)__float_as_uint(zw) << 32) | rank);
+    }
+  }
+}
+
 struct RenderResolveArgs {
   const unsigned long long* keys;  // the group's key planes
   uint64_t npix, plane;            // pixels of the group, of one view
   uint32_t view0;
   const uint64_t* view_seg;        // V + 1: first segment of each view
-  const uint64_t* seg_pts;         // nseg + 1: points before each segment (over all views)
+  const uint64_t* seg_pts;         // nseg + 1: points before each segment (over all views); with outlines: ranks, n + 1 per segment
   const uint32_t* seg_node;
   const BatchNode* nodes;
   const uint8_t* rgb;
@@ -177,15 +293,19 @@ struct RenderResolveArgs {
   uint32_t* image;                 // all views of the call
   float* depth;                    // all views of the call
   unsigned long long* covered;     // per view of the call
+  unsigned long long* outlined;    // OUTLINE: per view of the call, the pixels an outline won
+  uint32_t outline_px;             // OUTLINE: outline_rgba as the image stores it
 };
 
-// K_rr: a thread per pixel of the group
+// K_rr: a thread per pixel of the group. OUTLINE: the rank after a node's points is its outline's, in outline_px as given
+template <bool OUTLINE>
 __global__ __launch_bounds__(256) void render_resolve_kernel(RenderResolveArgs a) {
   const uint32_t lane = threadIdx.x & 63;
   for (uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x; p < a.npix; p += (uint64_t)gridDim.x * 256) {
     const uint32_t view = a.view0 + (uint32_t)(p / a.plane);
     const unsigned long long key = a.keys[p];
     const bool cov = key != kEmptyKey;
+    bool box = false;
     uint32_t px = 0xff000000u;  // (0, 0, 0, 255)
     float zw = 1.0f;
     if (cov) {
@@ -197,8 +317,14 @@ __global__ __launch_bounds__(256) void render_resolve_kernel(RenderResolveArgs a
         if (a.seg_pts[mid] <= g) lo = mid;
         else hi = mid;
       }
-      const uint8_t* c = a.rgb + 3 * (a.nodes[a.seg_node[lo]].point_off + (g - a.seg_pts[lo]));
-      px = (uint32_t)a.lut[c[0]] | (uint32_t)a.lut[c[1]] << 8 | (uint32_t)a.lut[c[2]] << 16 | 0xff000000u;
+      const BatchNode* nd = a.nodes + a.seg_node[lo];
+      if constexpr (OUTLINE) box = g - a.seg_pts[lo] == nd->n;
+      if (box) {
+        px = a.outline_px;
+      } else {
+        const uint8_t* c = a.rgb + 3 * (nd->point_off + (g - a.seg_pts[lo]));
+        px = (uint32_t)a.lut[c[0]] | (uint32_t)a.lut[c[1]] << 8 | (uint32_t)a.lut[c[2]] << 16 | 0xff000000u;
+      }
       zw = __uint_as_float((uint32_t)(key >> 32));
     }
     const uint64_t at = (uint64_t)a.view0 * a.plane + p;
@@ -207,10 +333,19 @@ __global__ __launch_bounds__(256) void render_resolve_kernel(RenderResolveArgs a
     // covered pixels per view: one add per wave where the wave's pixels are of one view
     const unsigned long long act = __ballot(true), cv = __ballot(cov);
     const uint32_t v0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)view);
-    if (__ballot(view == v0) == act) {
+    const bool one_view = __ballot(view == v0) == act;
+    if (one_view) {
       if (cv && lane == (uint32_t)(__ffsll(act) - 1)) atomicAdd(a.covered + v0, (unsigned long long)__popcll(cv));
     } else if (cov) {
       atomicAdd(a.covered + view, 1ull);
+    }
+    if constexpr (OUTLINE) {  // the pixels an outline won, counted the same way
+      const unsigned long long bx = __ballot(box);
+      if (one_view) {
+        if (bx && lane == (uint32_t)(__ffsll(act) - 1)) atomicAdd(a.outlined + v0, (unsigned long long)__popcll(bx));
+      } else if (box) {
+        atomicAdd(a.outlined + view, 1ull);
+      }
     }
   }
 }
@@ -219,6 +354,7 @@ struct ViewInfo {
   int32_t status = 0;
   uint32_t nodes_visible = 0, nodes_drawn = 0;
   uint64_t points_submitted = 0, points_drawn = 0, pixels_covered = 0;
+  uint64_t segments_submitted = 0, segments_drawn = 0, outline_pixels = 0;  // show_octree_nodes
 };
 
 int resident_grid(pcv_ctx* ctx, const void* kernel, int* grid) {
@@ -261,7 +397,9 @@ extern "C" void pcv_render_free(pcv_render* r) {
   delete r;
 }
 
-static int render_views(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree, const pcv_render_params* p, pcv_render* r) {
+static int render_views(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree, const pcv_render_params* p,
+                        const pcv_render_overlay* overlay, pcv_render* r) {
+  const bool outline = overlay && (overlay->flags & PCV_RENDER_OUTLINE_NODES);
   const uint32_t V = frusta->count, W = p->width, H = p->height;
   const uint64_t plane = (uint64_t)W * H;
   r->V = V;
@@ -289,6 +427,7 @@ static int render_views(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree
   if ((rc = pcv_visible_nodes(ctx, frusta, tree, cap, counts.data(), lists.data(), status.data()))) return rc;
   // 2. one segment per (view, drawn node); u64 prefixes of chunks and of points
   std::vector<uint32_t> seg_node, seg_view;
+  // with outlines a node owns n + 1 ranks (its points, then its outline): seg_pts then counts ranks, not points
   std::vector<uint64_t> seg_chunk(1, 0), seg_pts(1, 0), view_seg(V + 1, 0), view_chunk(V + 1, 0);
   for (uint32_t v = 0; v < V; ++v) {
     ViewInfo& vi = r->info[v];
@@ -305,10 +444,13 @@ static int render_views(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree
         seg_node.push_back(node);
         seg_view.push_back(v);
         seg_chunk.push_back(seg_chunk.back() + (n + per - 1) / per);
-        seg_pts.push_back(seg_pts.back() + n);
+        seg_pts.push_back(seg_pts.back() + n + (outline ? 1 : 0));
         vi.points_submitted += n;
+        if (outline) vi.segments_submitted += 12;
       }
       if (vi.points_submitted >= 0xffffffffull) return ctx->fail(PCV_E_INVALID, "render: a view draws 2^32 - 1 points or more");
+      if (vi.points_submitted + vi.segments_submitted / 12 >= 0xffffffffull)
+        return ctx->fail(PCV_E_INVALID, "render: a view's points and node outlines take 2^32 - 1 draw ranks or more");
     }
     view_seg[v + 1] = seg_node.size();
     view_chunk[v + 1] = seg_chunk.back();
@@ -317,12 +459,13 @@ static int render_views(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree
   // 3. the images of all views, and the scratch
   if ((rc = ctx->dev_alloc((void**)&r->d_images, 4 * plane * V)) || (rc = ctx->dev_alloc((void**)&r->d_depth, 4 * plane * V))) return rc;
   PcvScratch sc(ctx);
+  const size_t ncounters = outline ? 4 : 2;  // per view: points drawn, pixels covered; segments drawn, outline pixels
   unsigned long long *d_keys, *d_counters;
   uint8_t* d_lut;
   uint32_t *d_seg_node, *d_seg_view;
   uint64_t *d_seg_chunk, *d_seg_pts, *d_view_seg;
   ChunkDesc* d_desc;
-  if ((rc = sc.get(&d_keys, group_views * plane)) || (rc = sc.get(&d_counters, 2 * (size_t)V)) || (rc = sc.get(&d_lut, 256)) ||
+  if ((rc = sc.get(&d_keys, group_views * plane)) || (rc = sc.get(&d_counters, ncounters * (size_t)V)) || (rc = sc.get(&d_lut, 256)) ||
       (rc = sc.get(&d_seg_node, std::max<uint64_t>(nseg, 1))) || (rc = sc.get(&d_seg_view, std::max<uint64_t>(nseg, 1))) ||
       (rc = sc.get(&d_seg_chunk, nseg + 1)) || (rc = sc.get(&d_seg_pts, nseg + 1)) || (rc = sc.get(&d_view_seg, (size_t)V + 1)) ||
       (rc = sc.get(&d_desc, std::max<uint64_t>(nchunks, 1))))
@@ -330,7 +473,7 @@ static int render_views(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree
   uint8_t lut[256];
   if ((rc = pcv_render_gamma_lut(p->gamma, lut))) return ctx->fail(rc, "render: gamma");
   PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_lut, lut, 256, hipMemcpyHostToDevice, ctx->stream));
-  PCV_HIP_CHECK(ctx, hipMemsetAsync(d_counters, 0, 16 * (size_t)V, ctx->stream));
+  PCV_HIP_CHECK(ctx, hipMemsetAsync(d_counters, 0, 8 * ncounters * (size_t)V, ctx->stream));
   if (nseg) {
     PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_seg_node, seg_node.data(), 4 * nseg, hipMemcpyHostToDevice, ctx->stream));
     PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_seg_view, seg_view.data(), 4 * nseg, hipMemcpyHostToDevice, ctx->stream));
@@ -340,10 +483,11 @@ static int render_views(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree
   PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_view_seg, view_seg.data(), 8 * ((size_t)V + 1), hipMemcpyHostToDevice, ctx->stream));
   const BatchNode* d_nodes = pcv_octree_query_nodes(tree);
   // grids of resident size that stride over chunks / pixels: no dispatch grows with V or with the node count
-  int splat_grid = 1, resolve_grid = 1, chunks_grid = 1;
-  if ((rc = resident_grid(ctx, (const void*)render_splat_kernel, &splat_grid)) ||
-      (rc = resident_grid(ctx, (const void*)render_resolve_kernel, &resolve_grid)) ||
-      (rc = resident_grid(ctx, (const void*)render_chunks_kernel, &chunks_grid)))
+  int splat_grid = 1, resolve_grid = 1, chunks_grid = 1, outline_grid = 1;
+  const void* resolve = outline ? (const void*)render_resolve_kernel<true> : (const void*)render_resolve_kernel<false>;
+  if ((rc = resident_grid(ctx, (const void*)render_splat_kernel, &splat_grid)) || (rc = resident_grid(ctx, resolve, &resolve_grid)) ||
+      (rc = resident_grid(ctx, (const void*)render_chunks_kernel, &chunks_grid)) ||
+      (outline && (rc = resident_grid(ctx, (const void*)render_outline_kernel, &outline_grid))))
     return rc;
   if (nchunks) {
     PcvProf prof(ctx, PCV_K_RENDER_CHUNKS);
@@ -374,6 +518,24 @@ static int render_views(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree
   ra.image = r->d_images;
   ra.depth = r->d_depth;
   ra.covered = d_counters + V;
+  RenderOutlineArgs oa{};
+  if (outline) {
+    const uint8_t* c = overlay->outline_rgba;
+    ra.outline_px = (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16 | (uint32_t)c[3] << 24;  // as given: no gamma
+    ra.outlined = d_counters + 3 * (size_t)V;
+    oa.seg_node = d_seg_node;
+    oa.seg_view = d_seg_view;
+    oa.seg_rank = d_seg_pts;
+    oa.view_seg = d_view_seg;
+    oa.nodes = d_nodes;
+    oa.shapes = frusta->dev;
+    oa.keys = d_keys;
+    oa.seg_drawn = d_counters + 2 * (size_t)V;
+    oa.W = W;
+    oa.H = H;
+    oa.half_w = sa.half_w;
+    oa.half_h = sa.half_h;
+  }
   for (uint32_t v0 = 0; v0 < V; v0 += (uint32_t)group_views) {
     const uint32_t nv = (uint32_t)std::min<uint64_t>(group_views, V - v0);
     PCV_HIP_CHECK(ctx, hipMemsetAsync(d_keys, 0xff, 8 * plane * nv, ctx->stream));
@@ -386,29 +548,60 @@ static int render_views(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree
                          ctx->stream, sa);
       PCV_HIP_CHECK(ctx, hipGetLastError());
     }
+    oa.s0 = view_seg[v0];
+    oa.s1 = view_seg[v0 + nv];
+    oa.view0 = v0;
+    if (outline && oa.s1 > oa.s0) {  // after the group's points, before its pixels are resolved
+      PcvProf prof(ctx, PCV_K_RENDER_OUTLINE);
+      hipLaunchKernelGGL(render_outline_kernel, dim3((uint32_t)std::min<uint64_t>(((oa.s1 - oa.s0) * 12 + 255) / 256, (uint64_t)outline_grid)),
+                         dim3(256), 0, ctx->stream, oa);
+      PCV_HIP_CHECK(ctx, hipGetLastError());
+    }
     ra.npix = plane * nv;
     ra.view0 = v0;
     {
       PcvProf prof(ctx, PCV_K_RENDER_RESOLVE);
-      hipLaunchKernelGGL(render_resolve_kernel, dim3((uint32_t)std::min<uint64_t>((ra.npix + 255) / 256, (uint64_t)resolve_grid)), dim3(256), 0,
-                         ctx->stream, ra);
+      const dim3 grid((uint32_t)std::min<uint64_t>((ra.npix + 255) / 256, (uint64_t)resolve_grid));
+      if (outline) hipLaunchKernelGGL(render_resolve_kernel<true>, grid, dim3(256), 0, ctx->stream, ra);
+      else hipLaunchKernelGGL(render_resolve_kernel<false>, grid, dim3(256), 0, ctx->stream, ra);
       PCV_HIP_CHECK(ctx, hipGetLastError());
     }
   }
-  std::vector<unsigned long long> h_counters(2 * (size_t)V);
-  PCV_HIP_CHECK(ctx, hipMemcpyAsync(h_counters.data(), d_counters, 16 * (size_t)V, hipMemcpyDeviceToHost, ctx->stream));
+  std::vector<unsigned long long> h_counters(ncounters * (size_t)V);
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(h_counters.data(), d_counters, 8 * ncounters * (size_t)V, hipMemcpyDeviceToHost, ctx->stream));
   PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // the scratch is released on return
   for (uint32_t v = 0; v < V; ++v) {
     r->info[v].points_drawn = h_counters[v];
     r->info[v].pixels_covered = h_counters[(size_t)V + v];
+    if (outline) {
+      r->info[v].segments_drawn = h_counters[2 * (size_t)V + v];
+      r->info[v].outline_pixels = h_counters[3 * (size_t)V + v];
+    }
   }
   return PCV_OK;
 }
 
+static const char* overlay_error(const pcv_render_overlay* o) {
+  if (o && (o->flags & ~(uint32_t)PCV_RENDER_OUTLINE_NODES)) return "render: unknown overlay flag bits (only PCV_RENDER_OUTLINE_NODES is defined)";
+  return nullptr;
+}
+
+extern "C" int pcv_render_check_overlay(const pcv_render_overlay* overlay, char* message, uint64_t capacity) {
+  const char* why = overlay_error(overlay);
+  if (message && capacity) snprintf(message, (size_t)capacity, "%s", why ? why : "");
+  return why ? PCV_E_INVALID : PCV_OK;
+}
+
 extern "C" int pcv_render_views(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree, const pcv_render_params* params, pcv_render** out) {
+  return pcv_render_views_ex(ctx, frusta, tree, params, nullptr, out);
+}
+
+extern "C" int pcv_render_views_ex(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree, const pcv_render_params* params,
+                                   const pcv_render_overlay* overlay, pcv_render** out) {
   if (!ctx) return PCV_E_INVALID;
   if (!frusta || !tree || !params || !out) return ctx->fail(PCV_E_INVALID, "null argument");
   *out = nullptr;
+  if (const char* why = overlay_error(overlay)) return ctx->fail(PCV_E_INVALID, why);
   if (pcv_render_check_params(params) != PCV_OK)
     return ctx->fail(PCV_E_INVALID, "render: width and height in 1 ..= 16384, point_size in 1 ..= 64, gamma finite and > 0");
   if (frusta->ctx != ctx || tree->ctx != ctx) return ctx->fail(PCV_E_INVALID, "render: shapes and octree must belong to the context");
@@ -417,7 +610,7 @@ extern "C" int pcv_render_views(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octr
     if (kind != PCV_SHAPE_FRUSTUM && kind != PCV_SHAPE_FRUSTUM_WITH_INVERSE) return ctx->fail(PCV_E_INVALID, "render: every shape must be a frustum");
   pcv_render* r = new pcv_render();
   r->ctx = ctx;
-  const int rc = render_views(ctx, frusta, tree, params, r);
+  const int rc = render_views(ctx, frusta, tree, params, overlay, r);
   if (rc != PCV_OK) {
     (void)hipStreamSynchronize(ctx->stream);  // nothing queued may still write into what is freed here
     (void)hipGetLastError();
@@ -440,6 +633,17 @@ extern "C" int pcv_render_info(pcv_render* r, uint32_t view, int32_t* status, ui
   if (points_submitted) *points_submitted = vi.points_submitted;
   if (points_drawn) *points_drawn = vi.points_drawn;
   if (pixels_covered) *pixels_covered = vi.pixels_covered;
+  return PCV_OK;
+}
+
+extern "C" int pcv_render_outline_info(pcv_render* r, uint32_t view, uint64_t* segments_submitted, uint64_t* segments_drawn,
+                                       uint64_t* outline_pixels) {
+  if (!r) return PCV_E_INVALID;
+  if (view >= r->V) return r->ctx->fail(PCV_E_INVALID, "render: view past the end");
+  const ViewInfo& vi = r->info[view];
+  if (segments_submitted) *segments_submitted = vi.segments_submitted;
+  if (segments_drawn) *segments_drawn = vi.segments_drawn;
+  if (outline_pixels) *outline_pixels = vi.outline_pixels;
   return PCV_OK;
 }
 

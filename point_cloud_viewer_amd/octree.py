@@ -990,14 +990,21 @@ class OctreeResult:
             xt.write(output_directory, png=png)
         return xt
 
-    def render(self, frusta, width, height, point_size=1.0, gamma=1.0, max_nodes=0, depth=False, max_workspace_bytes=None):
+    def render(self, frusta, width, height, point_size=1.0, gamma=1.0, max_nodes=0, depth=False, max_workspace_bytes=None,
+               show_octree_nodes=False, outline_color=L.RENDER_OUTLINE_YELLOW):
         """The viewer's frame for every frustum of `frusta` (a Shapes of "frustum" / "frustum2" entries), rasterised on the
         device (pcv_render_views; sdl_viewer/src/lib.rs:158-209): get_visible_nodes, its first max_nodes entries (0: all)
         drawn as points of `point_size` pixels under a depth test, colours through `gamma`, over black. depth=True fetches
-        the window-depth planes with the call (they are kept on the device either way). Returns a RenderedViews."""
+        the window-depth planes with the call (they are kept on the device either way). show_octree_nodes (the viewer's `O`
+        key, lib.rs:202-208) draws the wireframe of every drawn node's cube right after the node's points, under the same
+        depth test, in `outline_color` (r, g, b, a) as given (pcv_render_views_ex). Returns a RenderedViews."""
         p = render_params(width, height, point_size, gamma, max_nodes, max_workspace_bytes)
         h = C.c_void_p()
-        self.ctx._check(self.lib.pcv_render_views(self.ctx.handle, frusta.handle, self.handle, C.byref(p), C.byref(h)))
+        if show_octree_nodes:
+            o = render_overlay(True, outline_color)
+            self.ctx._check(self.lib.pcv_render_views_ex(self.ctx.handle, frusta.handle, self.handle, C.byref(p), C.byref(o), C.byref(h)))
+        else:
+            self.ctx._check(self.lib.pcv_render_views(self.ctx.handle, frusta.handle, self.handle, C.byref(p), C.byref(h)))
         return RenderedViews(self.ctx, h, frusta.count, int(width), int(height), bool(depth))
 
     def nodes_blob(self, node_indices):
@@ -1487,6 +1494,25 @@ def render_check_params(params):
         raise L.PcvError(rc, "pcv_render_check_params")
 
 
+def render_overlay(show_octree_nodes=False, outline_color=L.RENDER_OUTLINE_YELLOW, flags=None):
+    """The pcv_render_overlay of OctreeResult.render; `flags` overrides the flag word (for the checks of the flag word)."""
+    color = [int(c) for c in outline_color]
+    if len(color) != 4 or not all(0 <= c <= 255 for c in color):
+        raise L.PcvError(L.PCV_E_INVALID, "outline_color: four values in 0 ..= 255 (r, g, b, a)")
+    o = L.RenderOverlay()
+    o.flags = (L.RENDER_OUTLINE_NODES if show_octree_nodes else 0) if flags is None else int(flags)
+    o.outline_rgba[:] = color
+    return o
+
+
+def render_check_overlay(overlay):
+    """pcv_render_check_overlay (host only): raises PcvError with the library's message for unknown flag bits."""
+    msg = C.create_string_buffer(256)
+    rc = L.load_library().pcv_render_check_overlay(C.byref(overlay) if overlay is not None else None, msg, 256)
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, msg.value.decode())
+
+
 def render_gamma_lut(gamma):
     """pcv_render_gamma_lut (host only): the 256-entry colour table of the frame for `gamma`."""
     lut = np.zeros(256, dtype=np.uint8)
@@ -1540,6 +1566,14 @@ class RenderedViews:
                                                  C.byref(pd), C.byref(pc)))
         return dict(status=st.value, nodes_visible=nv.value, nodes_drawn=nd.value, points_submitted=ps.value,
                     points_drawn=pd.value, pixels_covered=pc.value)
+
+    def outline_info(self, view):
+        """dict(segments_submitted, segments_drawn, outline_pixels) of one view: 12 per drawn node, the segments that survived
+        the clip, the pixels of the image an outline won; all zero when the views were rendered without show_octree_nodes."""
+        self._alive()
+        ss, sd, op = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self.ctx._check(self.lib.pcv_render_outline_info(self.handle, int(view), C.byref(ss), C.byref(sd), C.byref(op)))
+        return dict(segments_submitted=ss.value, segments_drawn=sd.value, outline_pixels=op.value)
 
     def write_png(self, directory):
         """One view_<index>.png per view (pcv_xray_png_encode's stored-deflate PNG); returns the paths."""

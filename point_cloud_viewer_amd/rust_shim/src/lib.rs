@@ -89,6 +89,15 @@ pub struct PcvRenderParams {
     pub max_workspace_bytes: u64,
 }
 
+/// include/pcv_hip.h pcv_render_overlay: what pcv_render_views_ex draws on top of the points (flags: 1 =
+/// PCV_RENDER_OUTLINE_NODES, the viewer's show_octree_nodes, sdl_viewer/src/lib.rs:202-208).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct PcvRenderOverlay {
+    pub flags: u32,
+    pub outline_rgba: [u8; 4],
+}
+
 /// include/pcv_hip.h pcv_ooc_stats: what an out-of-core build did (points, nodes, partitions, host spill, link traffic, phase times).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -150,6 +159,7 @@ extern "C" {
     fn pcv_query_batch_free(b: *mut pcv_query_batch);
     // the viewer's frame: get_visible_nodes + GL_POINTS under a depth test, rasterised on the device
     fn pcv_render_views(ctx: *mut pcv_ctx, frusta: *const pcv_shapes, t: *mut pcv_octree, params: *const PcvRenderParams, out: *mut *mut pcv_render) -> c_int;
+    fn pcv_render_views_ex(ctx: *mut pcv_ctx, frusta: *const pcv_shapes, t: *mut pcv_octree, params: *const PcvRenderParams, overlay: *const PcvRenderOverlay, out: *mut *mut pcv_render) -> c_int;
     fn pcv_render_images(r: *mut pcv_render, first: u32, count: u32, rgba: *mut c_void, mem: c_int) -> c_int;
     fn pcv_render_free(r: *mut pcv_render);
 }
@@ -708,16 +718,19 @@ impl HipOctree {
 
     /// One frame as `sdl_viewer` draws it (src/lib.rs:158-209: the visible nodes' points as GL_POINTS of `point_size`
     /// pixels under a depth test, colours through `gamma`, over black) for the camera `world_to_gl`, rasterised on the
-    /// device: RGBA8, `height` rows of `width` pixels, top row first. Panics like the reference on a matrix that cannot
-    /// be inverted.
-    pub fn render(&self, world_to_gl: &Matrix4<f64>, width: u32, height: u32, point_size: f32, gamma: f32, max_nodes_to_display: usize) -> Vec<u8> {
+    /// device: RGBA8, `height` rows of `width` pixels, top row first. `show_octree_nodes` (the viewer's `O` key,
+    /// lib.rs:202-208) draws every drawn node's cube as BoxDrawer::draw_outlines does, in the viewer's YELLOW. Panics like
+    /// the reference on a matrix that cannot be inverted.
+    pub fn render(&self, world_to_gl: &Matrix4<f64>, width: u32, height: u32, point_size: f32, gamma: f32, max_nodes_to_display: usize,
+                  show_octree_nodes: bool) -> Vec<u8> {
         let mut shape = PcvShape { kind: 2, reserved: 0, params: [0.0; 32] };
         shape.params[..16].copy_from_slice(world_to_gl.as_slice()); // nalgebra storage is column-major
         let params = PcvRenderParams { width, height, point_size, gamma, max_nodes: max_nodes_to_display.min(u32::MAX as usize) as u32, max_workspace_bytes: 0 };
         let _g = self.lock.lock().unwrap();
         self.with_shape(&shape, |shapes| {
             let mut frame = std::ptr::null_mut();
-            self.ctx.check(unsafe { pcv_render_views(self.ctx.0, shapes, self.tree, &params, &mut frame) });
+            let overlay = PcvRenderOverlay { flags: show_octree_nodes as u32, outline_rgba: [255, 255, 0, 255] };
+            self.ctx.check(unsafe { pcv_render_views_ex(self.ctx.0, shapes, self.tree, &params, &overlay, &mut frame) });
             let mut rgba = vec![0u8; 4 * width as usize * height as usize];
             let rc = unsafe { pcv_render_images(frame, 0, 1, rgba.as_mut_ptr() as *mut c_void, 0) };
             unsafe { pcv_render_free(frame) };

@@ -11,12 +11,21 @@ View 0 is checked against the numpy oracle (tests/render_oracle.py) run over the
 of the oracle's own visible list: the SHA-256 of both images is recorded, and whether they are equal.
 Prints one JSON line and writes it to --out.
 
-usage: python tools/render_bench.py [--points N] [--views V] [--size WxH] [--steps K] [--out FILE]"""
+--outlines: the same case with show_octree_nodes off and on in one process (profiles/render_outline_bench.json): per point
+size and setting the wall time, the per-kernel times (render_outline_kernel among them), outline_pixels and the segments, and
+view 0 against tests/render_outline_oracle.py. With --parent-library (a libpcv_hip.so built from the parent commit) the
+outlines-off wall time is also measured next to the parent's: fresh processes, one library each, alternating --ab-reps
+times (the way tools/ab_libs.sh alternates variants), each building the cloud itself. The off path launches the instances
+the parent launches, so a difference beyond the spread of those runs is a finding, recorded with the figures.
+
+usage: python tools/render_bench.py [--points N] [--views V] [--size WxH] [--steps K] [--out FILE]
+       python tools/render_bench.py --outlines [--parent-library FILE] [--ab-reps R] [...]"""
 import argparse
 import hashlib
 import json
 import math
 import os
+import subprocess
 import sys
 import time
 
@@ -29,14 +38,15 @@ import torch  # noqa: E402
 import oracle_lib as O  # noqa: E402
 import point_cloud_viewer_amd as pcv  # noqa: E402
 import render_oracle as R  # noqa: E402
+import render_outline_oracle as RO  # noqa: E402
 from bench import build_hash, make_cloud  # noqa: E402
 
 HBM_PEAK = 8.0e12
 ATOMIC_PEAK_BYTES = 1.3e12  # chip-wide no-return global atomics, operand bytes per second
-KERNELS = ("visible_nodes_kernel", "render_chunks_kernel", "render_splat_kernel", "render_resolve_kernel")
+KERNELS = ("visible_nodes_kernel", "render_chunks_kernel", "render_splat_kernel", "render_outline_kernel", "render_resolve_kernel")
 
 
-def oracle_view(tree, matrix, W, H, point_size, gamma):
+def oracle_view(tree, matrix, W, H, point_size, gamma, outlines=False):
     """View `matrix` by the numpy oracle over the library's node bytes (the tree's own bytes are checked by the suite)."""
     m = tree.num_nodes
     infos = [tree.node(i) for i in range(m)]
@@ -47,20 +57,11 @@ def oracle_view(tree, matrix, W, H, point_size, gamma):
     visible = O.get_visible_nodes(meta["bbox_min"], meta["bbox_max"], nodes, matrix)
     drawn = [dict(encoding=infos[index[n]].encoding, xyz=tree.node_data(index[n], 0), rgb=tree.node_data(index[n], 1),
                   cube_min=np.array(infos[index[n]].cube_min[:]), cube_edge=infos[index[n]].cube_edge) for n in (visible or [])]
-    return R.draw_nodes(drawn, matrix, W, H, point_size, R.gamma_lut(gamma))
+    return (RO if outlines else R).draw_nodes(drawn, matrix, W, H, point_size, R.gamma_lut(gamma))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--points", type=int, default=100_000_000)
-    ap.add_argument("--resolution", type=float, default=0.001)
-    ap.add_argument("--views", type=int, default=100)
-    ap.add_argument("--size", default="1920x1080")
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "render_bench.json"))
-    args = ap.parse_args()
-    W, H = (int(v) for v in args.size.split("x"))
-
+def setup(args):
+    """The config-2 tree and the config-4 frusta of the case: (ctx, tree, mats, shapes)."""
     dev = torch.device("cuda", 0)
     x, y, z, rgb = make_cloud(torch, args.points, seed=1, device=dev)
     ctx = pcv.Context(0)
@@ -77,7 +78,134 @@ def main():
         q = rng.normal(size=4)
         q = q / math.sqrt(float(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]))
         mats.append(O.frustum_new(eye, q, persp)[0])
-    shapes = ctx.shapes([("frustum", m) for m in mats])
+    return ctx, tree, mats, ctx.shapes([("frustum", m) for m in mats])
+
+
+def measure(ctx, tree, shapes, W, H, steps, point_size, **render_kw):
+    """steps calls after a warm-up: (wall times in ms, kernel split of the last call, its infos, its outline infos, view 0)."""
+    walls, split, infos, oinfos, img0 = [], None, None, None, None
+    for step in range(steps + 1):
+        ctx.reset_kernel_stats()
+        t0 = time.perf_counter()
+        rv = tree.render(shapes, W, H, point_size=point_size, **render_kw)
+        wall = (time.perf_counter() - t0) * 1e3
+        if step:
+            walls.append(wall)
+        if step == steps:
+            st = ctx.kernel_stats()
+            split = {k.replace("_kernel", ""): round(st[k][1], 3) for k in KERNELS if k in st and st[k][0]}
+            infos = [rv.info(v) for v in range(shapes.count)]
+            oinfos = [rv.outline_info(v) for v in range(shapes.count)] if hasattr(rv, "outline_info") and render_kw else None
+            img0 = rv.images(0, 1)[0].cpu().numpy()
+        rv.close()
+    return walls, split, infos, oinfos, img0
+
+
+def wall_only(args, W, H):
+    """One process of the parent comparison: outlines off, wall times only, through the library PCV_HIP_LIBRARY names."""
+    if os.environ.get("PCV_HIP_LIBRARY"):  # a library of an earlier commit lacks the entry points added since: they leave
+        import ctypes                      # this process's binding table, which otherwise refuses such a library
+        from point_cloud_viewer_amd import _lib
+        older = ctypes.CDLL(_lib.LIB_PATH)
+        for name in [n for n in _lib._SIGNATURES if not hasattr(older, n)]:
+            del _lib._SIGNATURES[name]
+    ctx, tree, _, shapes = setup(args)
+    out = {"library": os.environ.get("PCV_HIP_LIBRARY") or "this tree's", "build_hash": build_hash(), "runs": []}
+    for point_size in (1.0, 3.0):
+        walls = measure(ctx, tree, shapes, W, H, args.steps, point_size)[0]
+        out["runs"].append(dict(point_size=point_size, wall_ms_median=round(float(np.median(walls)), 3), wall_ms=[round(w, 3) for w in walls]))
+    print(json.dumps(out))
+    tree.free()
+    ctx.close()
+    return 0
+
+
+def against_parent(args):
+    """Outlines off, this tree's library and the parent's alternating in fresh processes; the figures and their spread."""
+    base = [sys.executable, os.path.abspath(__file__), "--wall-only", "--points", str(args.points), "--resolution", str(args.resolution),
+            "--views", str(args.views), "--size", args.size, "--steps", str(args.steps)]
+    runs = {"parent": [], "this": []}
+    for _ in range(args.ab_reps):
+        for name in ("parent", "this"):
+            env = dict(os.environ)
+            env.pop("PCV_HIP_LIBRARY", None)
+            if name == "parent":
+                env["PCV_HIP_LIBRARY"] = os.path.abspath(args.parent_library)
+            p = subprocess.run(base, env=env, capture_output=True, text=True, timeout=600)
+            if p.returncode != 0:
+                raise SystemExit(f"render_bench: the {name} run failed ({p.returncode}): {p.stderr[-2000:]}")
+            runs[name].append(json.loads(p.stdout.strip().splitlines()[-1])["runs"])
+    out = []
+    for k, point_size in enumerate((1.0, 3.0)):
+        med = {name: [r[k]["wall_ms_median"] for r in runs[name]] for name in runs}
+        spread = max(max(v) - min(v) for v in med.values())
+        diff = float(np.median(med["this"]) - np.median(med["parent"]))
+        out.append(dict(point_size=point_size, parent_wall_ms_medians=med["parent"], this_wall_ms_medians=med["this"],
+                        run_to_run_spread_ms=round(spread, 3), this_minus_parent_ms=round(diff, 3),
+                        finding=("within the run-to-run spread of this job" if abs(diff) <= spread else
+                                 "beyond the run-to-run spread of this job: the off path launches the parent's instances, so the "
+                                 "difference is not explained by the kernels; see the per-run figures")))
+    return out
+
+
+def outlines(args, W, H):
+    """--outlines: show_octree_nodes off and on in one process."""
+    versus = against_parent(args) if args.parent_library else None  # before this process opens the device
+    ctx, tree, mats, shapes = setup(args)
+    ctx.set_profiling(True)
+    runs, ok = [], True
+    for point_size in (1.0, 3.0):
+        for on in (False, True):
+            kw = dict(show_octree_nodes=True) if on else {}
+            walls, split, infos, oinfos, img0 = measure(ctx, tree, shapes, W, H, args.steps, point_size, **kw)
+            want = oracle_view(tree, mats[0], W, H, point_size, 1.0, outlines=on)
+            digest, want_digest = hashlib.sha256(img0.tobytes()).hexdigest(), hashlib.sha256(want["image"].tobytes()).hexdigest()
+            ok = ok and digest == want_digest
+            rec = dict(point_size=point_size, outlines=on, wall_ms_median=round(float(np.median(walls)), 3), wall_ms=[round(w, 3) for w in walls],
+                       kernel_ms=split, nodes_drawn=sum(i["nodes_drawn"] for i in infos), points_submitted=sum(i["points_submitted"] for i in infos),
+                       points_drawn=sum(i["points_drawn"] for i in infos), pixels_covered=sum(i["pixels_covered"] for i in infos),
+                       view0_digest=digest, view0_oracle_digest=want_digest, view0_equals_oracle=digest == want_digest)
+            if on:
+                rec.update(segments_submitted=sum(i["segments_submitted"] for i in oinfos), segments_drawn=sum(i["segments_drawn"] for i in oinfos),
+                           outline_pixels=sum(i["outline_pixels"] for i in oinfos), view0_outline_pixels=want["outline_pixels"])
+            runs.append(rec)
+    out = {"tool": "tools/render_bench.py --outlines", "build_hash": build_hash(), "device": torch.cuda.get_device_name(0),
+           "cloud": f"config 2: {args.points} Gaussian-cluster points (bench.make_cloud, seed 1), resolution {args.resolution}",
+           "nodes": tree.num_nodes, "views": args.views, "size": [W, H], "steps": args.steps, "runs": runs}
+    if versus is not None:
+        out["outlines_off_vs_parent"] = dict(method=f"fresh processes alternating parent / this, {args.ab_reps} of each, median of {args.steps} calls per run",
+                                            runs=versus)
+    print(json.dumps(out))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(json.dumps(out, indent=1) + "\n")
+    tree.free()
+    ctx.close()
+    return 0 if ok else 1
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--points", type=int, default=100_000_000)
+    ap.add_argument("--resolution", type=float, default=0.001)
+    ap.add_argument("--views", type=int, default=100)
+    ap.add_argument("--size", default="1920x1080")
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--outlines", action="store_true")
+    ap.add_argument("--parent-library", default=None)
+    ap.add_argument("--ab-reps", type=int, default=2)
+    ap.add_argument("--wall-only", action="store_true", help="one process of the parent comparison (used by --outlines)")
+    args = ap.parse_args()
+    W, H = (int(v) for v in args.size.split("x"))
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "render_outline_bench.json" if args.outlines else "render_bench.json")
+    if args.wall_only:
+        return wall_only(args, W, H)
+    if args.outlines:
+        return outlines(args, W, H)
+
+    ctx, tree, mats, shapes = setup(args)
     stride = {1: 3, 2: 6, 3: 12, 4: 24}
     node_stride = np.array([stride[tree.node(i).encoding] for i in range(tree.num_nodes)], dtype=np.int64)
     node_points = np.array([tree.node(i).num_points for i in range(tree.num_nodes)], dtype=np.int64)
@@ -87,21 +215,8 @@ def main():
 
     runs, ok = [], True
     for point_size in (1.0, 3.0):
-        walls, split, infos, digest = [], None, None, None
-        for step in range(args.steps + 1):  # the first is a warm-up
-            ctx.reset_kernel_stats()
-            t0 = time.perf_counter()
-            rv = tree.render(shapes, W, H, point_size=point_size)
-            wall = (time.perf_counter() - t0) * 1e3
-            if step:
-                walls.append(wall)
-            if step == args.steps:
-                st = ctx.kernel_stats()
-                split = {k.replace("_kernel", ""): round(st[k][1], 3) for k in KERNELS if st[k][0]}
-                infos = [rv.info(v) for v in range(args.views)]
-                img0 = rv.images(0, 1)[0].cpu().numpy()
-                digest = hashlib.sha256(img0.tobytes()).hexdigest()
-            rv.close()
+        walls, split, infos, _, img0 = measure(ctx, tree, shapes, W, H, args.steps, point_size)
+        digest = hashlib.sha256(img0.tobytes()).hexdigest()
         want = oracle_view(tree, mats[0], W, H, point_size, 1.0)
         want_digest = hashlib.sha256(want["image"].tobytes()).hexdigest()
         ok = ok and digest == want_digest
