@@ -3,13 +3,16 @@
  * (pcv_xray_run_ex), every level above them up to the root node is built on the device (pcv_xray_build_parents), and
  * the quadtree directory the xray viewer loads is written: one <node>.png per node and the meta file
  * (pcv_xray_write_dir_ex). A subset of the reference binary's flags, and --png: stored (the default) or deflate, the
- * tiles compressed on the device.
+ * tiles compressed on the device. With --inpaint-distance-px the leaves are built with the transparent background,
+ * inpainted on the device (pcv_xray_inpaint; the fill is not the reference's texture synthesis) and given
+ * --tile-background-color afterwards: build_xray_quadtree and inpaint_xray_quadtree in one run, no directory between.
  *
  *   build_xray_quadtree <octree dir>... --output-directory <dir> --resolution <m per px> [--tile-size <px>]
  *                       [--coloring-strategy xray|colored|colored_with_intensity|colored_with_height_stddev]
  *                       [--min-intensity <f>] [--max-intensity <f>] [--binning intensity=<size>] [--max-stddev <m>]
  *                       [--colormap jet|purplish] [--tile-background-color white|transparent]
  *                       [--filter-interval intensity=<lo>,<hi>] [--root-node-id <r...>] [--png stored|deflate]
+ *                       [--inpaint-distance-px <0..254>]
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -23,7 +26,7 @@ static int usage(void) {
           "       [--coloring-strategy xray|colored|colored_with_intensity|colored_with_height_stddev] [--min-intensity <f>]\n"
           "       [--max-intensity <f>] [--binning intensity=<size>] [--max-stddev <m>] [--colormap jet|purplish]\n"
           "       [--tile-background-color white|transparent] [--filter-interval intensity=<lo>,<hi>] [--root-node-id <r...>]\n"
-          "       [--png stored|deflate]\n");
+          "       [--png stored|deflate] [--inpaint-distance-px <0..254>]\n");
   return 2;
 }
 
@@ -33,6 +36,7 @@ int main(int argc, char** argv) {
   const char* output = NULL;
   const char* root = "r";
   int png = PCV_XRAY_PNG_STORED;
+  long inpaint = -1; /* no inpainting */
   char attribute[16] = "";
   char bin_attribute[16] = "";
   pcv_xray_coloring col;
@@ -94,6 +98,9 @@ int main(int argc, char** argv) {
       p.interval_attribute = attribute;
     } else if (!strcmp(a, "--root-node-id")) {
       root = v;
+    } else if (!strcmp(a, "--inpaint-distance-px")) {
+      inpaint = strtol(v, NULL, 10);
+      if (inpaint < 0 || inpaint > 255) return usage();
     } else if (!strcmp(a, "--png")) {
       if (!strcmp(v, "stored")) png = PCV_XRAY_PNG_STORED;
       else if (!strcmp(v, "deflate")) png = PCV_XRAY_PNG_DEFLATE;
@@ -113,10 +120,21 @@ int main(int argc, char** argv) {
   pcv_ctx* ctx = NULL;
   pcv_octree** trees = (pcv_octree**)calloc(num_inputs, sizeof(pcv_octree*));
   pcv_xray* x = NULL;
+  const uint32_t background = p.background;
+  if (inpaint >= 0) p.background = PCV_XRAY_BG_TRANSPARENT; /* the holes must survive until they are filled */
   int rc = trees ? pcv_ctx_create(0, NULL, &ctx) : PCV_E_OOM;
   for (uint32_t t = 0; t < num_inputs && rc == PCV_OK; ++t) rc = pcv_octree_open_dir(ctx, inputs[t], &trees[t]);
   if (rc == PCV_OK) rc = pcv_xray_run_ex(ctx, trees, num_inputs, &p, &col, &x);
-  if (rc == PCV_OK) rc = pcv_xray_build_parents(x);
+  if (rc == PCV_OK && inpaint >= 0) { /* the result carries its own parent levels */
+    pcv_xray* filled = NULL;
+    rc = pcv_xray_inpaint(ctx, x, NULL, 0, (uint32_t)inpaint, background, &filled);
+    if (rc == PCV_OK) {
+      pcv_xray_free(x);
+      x = filled;
+    }
+  } else if (rc == PCV_OK) {
+    rc = pcv_xray_build_parents(x);
+  }
   if (rc == PCV_OK) rc = pcv_xray_write_dir_ex(x, output, png);
   if (rc == PCV_OK) {
     uint64_t nodes = 0, created = 0;

@@ -964,6 +964,63 @@ int pcv_xray_merge_check(pcv_xray* const* parts, uint32_t num_parts, uint32_t* r
  * PCV_E_INVALID. pcv_xray_tiles, _images, _negative and _build_parents on it are PCV_E_INVALID. */
 int pcv_xray_merge(pcv_ctx* ctx, pcv_xray* const* parts, uint32_t num_parts, uint32_t background, pcv_xray** out);
 
+/* ---- inpaint_xray_quadtree (xray/src/bin/inpaint_xray_quadtree.rs, xray/src/inpaint.rs): hole filling for leaf tiles ------
+ * The leaves of a quadtree x whose background is transparent are stitched with their eight neighbours into tiles twice as
+ * wide and high, the holes that a morphological close of the alpha mask covers are filled, overlapping enlarged tiles are
+ * blended, the centre is cropped, the background is assigned and every parent level is rebuilt.
+ * PARITY: the adjacent leaves (step 1, bin :41-71), the stitch (2, inpaint.rs:90-121), the masks (3, :27-31), the blend (5,
+ * :132-161 with utils.rs:46-60), the crop (6, :163-173), assign_background_color and create_non_leaf_nodes (7,
+ * generation.rs:684-708, :656-682) are the reference's, byte for byte. The fill (4) is NOT: the reference hands the target
+ * pixels to the texture-synthesis crate (inpaint.rs:32-43); here a target pixel is a distance-weighted mean of the known
+ * pixels around it. So the pixels that were filled, and what the blend and the Lanczos resize make of them, differ from the
+ * reference's; every other pixel of every tile does not.
+ * x and up to four neighbour quadtrees are device-built with PCV_XRAY_BG_TRANSPARENT (pcv_xray_run*), opened from a
+ * directory, or results of pcv_xray_inpaint with a transparent background; a merged quadtree is refused. Leaves of diagonal
+ * quadtrees are never taken: that is the reference's separate-directory mode (its in-place mode would find their files on
+ * disk). distance_px is inpaint_distance_px, a u8: 0 inpaints nothing (perform_inpainting :222 returns early; the leaves
+ * are re-backgrounded and the parents rebuilt); 255 is PCV_E_INVALID, because imageproc 0.21.0's distance transform saturates
+ * at 255 and its close (Norm::LInf) is then no longer the morphological one. */
+#define PCV_XRAY_INPAINT_MAX_TILE 8192u /* tile size of an inpainted quadtree: a group's target list has u32 pixel numbers */
+/* Peak device bytes of pcv_xray_inpaint for tiles of w pixels: the result holds 4 w w per leaf and parent and an opened x is
+ * staged whole (4 w w per leaf), the adjacent leaves of the neighbours likewise; the work of one enlarged tile (RGBA 16 w w,
+ * three masks 3 x 4 w w, the target list 16 w w) is held for one group of leaves at a time: consecutive leaves whose
+ * enlarged tiles (at most 9 per leaf: the leaf's and those it blends with) fit pcv_ctx_set_xray_chunk_bytes, at least one
+ * leaf per group. */
+#define PCV_XRAY_INPAINT_WORK_BYTES(w) (44ull * (uint64_t)(w) * (uint64_t)(w))
+/* Host only, no context: what pcv_xray_inpaint refuses before any device work, PCV_E_INVALID with a message in err: a null,
+ * freed or merged handle; a built x or neighbour whose background is white (its holes are gone); a tile size that is not a
+ * power of two >= 2 (w = W / 2 must halve again, inpaint.rs:92-94) or above PCV_XRAY_INPAINT_MAX_TILE; distance_px >= 255;
+ * more than four neighbours; a neighbour with another tile size or deepest level; a neighbour whose root is not
+ * root.neighbor(Left / Top / Right / Bottom) at the root's level (bin :53-57), or two neighbours on one side; an opened
+ * handle without nodes or with several nodes at its minimum level. */
+int pcv_xray_inpaint_check(const pcv_xray* x, pcv_xray* const* neighbours, uint32_t num_neighbours, uint32_t distance_px, char* err,
+                           uint64_t errcap);
+/* Host only, no context: steps 1 and 2 as a table. get_adjacent_leaf_node_ids (bin :41-71): a leaf n of the neighbour in
+ * direction D is taken iff n.neighbor(D.opposite()) is a leaf of x (Top is y + 1, quadtree/src/lib.rs:290-302);
+ * *num_adjacent is their number. stitched_image (inpaint.rs:90-121): for the first `capacity` leaves of x, in
+ * pcv_xray_nodes' order, 9 slots of 2 entries each (18 uint32_t per leaf), in the order TopLeft, Top, TopRight, Left, the
+ * leaf itself, Right, BottomLeft, Bottom, BottomRight: (part, node) with part 0 = x and k + 1 = neighbours[k], node = the
+ * position among that part's leaves (its pcv_xray_nodes order), or (0xffffffff, 0xffffffff) where no tile contributes. A
+ * slot is filled by a leaf of x or by a taken leaf of a neighbour. The checks of pcv_xray_inpaint_check apply. */
+int pcv_xray_inpaint_plan(const pcv_xray* x, pcv_xray* const* neighbours, uint32_t num_neighbours, uint64_t capacity, uint32_t* slots,
+                          uint64_t* num_adjacent, char* err, uint64_t errcap);
+/* Steps 1-7 on the device. background (PCV_XRAY_BG_*) is --tile-background-color: pixels whose alpha is below 128 after the
+ * blend take it (generation.rs:697-701), and it is the missing child of the parent levels. A handle of another context and
+ * an unknown background are PCV_E_INVALID, with pcv_xray_inpaint_check's refusals. Every image and work buffer is allocated
+ * before the first launch: PCV_E_OOM leaves nothing allocated. x and the neighbours may be freed after the call.
+ * The result owns its leaf and parent images. It serves pcv_xray_info (rect: that of x's root node), pcv_xray_tile_size,
+ * pcv_xray_nodes (x's leaves in x's order, then each parent level from deepest_level - 1 up to the root in ascending
+ * index: the node ids of x), pcv_xray_node_images, pcv_xray_node_pngs and pcv_xray_write_dir[_ex] (the meta file is named
+ * after x's root, get_meta_pb_path); pcv_xray_merge_check and pcv_xray_merge take it as a part whose parents are built.
+ * pcv_xray_tiles, _images, _negative and _build_parents on it are PCV_E_INVALID, as for a merged quadtree. */
+int pcv_xray_inpaint(pcv_ctx* ctx, pcv_xray* x, pcv_xray* const* neighbours, uint32_t num_neighbours, uint32_t distance_px,
+                     uint32_t background, pcv_xray** out);
+/* Per leaf of the result (num_leaves entries each, nullable), counted within the final tile, the cropped centre of the
+ * leaf's enlarged tile: target_pixels = pixels of the target mask (step 3); filled_pixels = pixels that were not known
+ * (alpha 0 in x) and whose alpha after the blend is >= 128, so that they keep their colour; blended_pixels = pixels that
+ * step 5 changed in any channel. All zero for distance_px == 0. PCV_E_INVALID for any other kind of handle. */
+int pcv_xray_inpaint_info(const pcv_xray* x, uint64_t* target_pixels, uint64_t* filled_pixels, uint64_t* blended_pixels);
+
 /* ---- the viewer's frame (sdl_viewer/src/lib.rs:158-209, node_drawer.rs:124-160, shaders/points.vs, points.fs) ----------
  * V cameras over one octree in one call, rasterised on the device into RGBA8 images that stay there. OpenGL leaves sub-pixel
  * snapping, the depth format and fused arithmetic to the driver, so the frame is a stated restatement:

@@ -90,6 +90,8 @@ XRAY_XRAY, XRAY_COLORED, XRAY_HEIGHT_STDDEV, XRAY_COLORED_WITH_INTENSITY = 0, 1,
 XRAY_JET, XRAY_PURPLISH = 0, 1
 XRAY_BG_WHITE, XRAY_BG_TRANSPARENT = 0, 1
 XRAY_PNG_STORED, XRAY_PNG_DEFLATE = 0, 1  # PCV_XRAY_PNG_*: the mode of pcv_xray_write_dir_ex / _node_pngs / _png_encode_ex
+XRAY_INPAINT_MAX_TILE = 8192  # PCV_XRAY_INPAINT_MAX_TILE
+XRAY_INPAINT_ABSENT = 0xFFFFFFFF  # an empty slot of pcv_xray_inpaint_plan
 XRAY_MAX_TREES = 4096  # PCV_XRAY_MAX_TREES: octrees of one pcv_xray_run_many
 XRAY_FN_XRAY, XRAY_FN_COLORED, XRAY_FN_JET, XRAY_FN_PURPLISH, XRAY_FN_TO_U8, XRAY_FN_INTENSITY = 0, 1, 2, 3, 4, 5
 REL_IN, REL_CROSS, REL_OUT = 0, 1, 2
@@ -294,6 +296,10 @@ _SIGNATURES = {
     "pcv_xray_tile_size": (C.c_uint32, [_vp]),
     "pcv_xray_merge_check": (C.c_int, [C.POINTER(_vp), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.c_char_p, C.c_uint64]),
     "pcv_xray_merge": (C.c_int, [_vp, C.POINTER(_vp), C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
+    "pcv_xray_inpaint_check": (C.c_int, [_vp, C.POINTER(_vp), C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64]),
+    "pcv_xray_inpaint_plan": (C.c_int, [_vp, C.POINTER(_vp), C.c_uint32, C.c_uint64, _vp, C.POINTER(C.c_uint64), C.c_char_p, C.c_uint64]),
+    "pcv_xray_inpaint": (C.c_int, [_vp, _vp, C.POINTER(_vp), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
+    "pcv_xray_inpaint_info": (C.c_int, [_vp, _vp, _vp, _vp]),
     "pcv_render_check_params": (C.c_int, [C.POINTER(RenderParams)]),
     "pcv_render_gamma_lut": (C.c_int, [C.c_float, _vp]),
     "pcv_render_views": (C.c_int, [_vp, _vp, _vp, C.POINTER(RenderParams), C.POINTER(_vp)]),

@@ -131,6 +131,12 @@ enum PcvKernelId {
   PCV_K_XRAY_PNG_LAYOUT,      // pcv_xray_png.hip: band offsets and Adler-32 per tile, tile offsets of the chunk
   PCV_K_XRAY_PNG_GATHER,      // pcv_xray_png.hip: the bands of every tile into one contiguous zlib stream
   PCV_K_RENDER_OUTLINE,       // pcv_render_views_ex: the node cubes' edges clipped and rasterised into the key planes
+  PCV_K_XRAY_INPAINT_STITCH,  // pcv_xray_inpaint: enlarged tiles gathered from a leaf and its eight neighbours, the known mask
+  PCV_K_XRAY_INPAINT_ROWS,    // pcv_xray_inpaint: one row pass of the close (distance to the nearest feature along the row)
+  PCV_K_XRAY_INPAINT_COLS,    // pcv_xray_inpaint: one column pass of the close; the last one leaves the target mask
+  PCV_K_XRAY_INPAINT_LIST,    // pcv_xray_inpaint: the target pixels of a group compacted into one list
+  PCV_K_XRAY_INPAINT_FILL,    // pcv_xray_inpaint: one thread per target pixel, weighted mean of the known pixels around it
+  PCV_K_XRAY_INPAINT_BLEND,   // pcv_xray_inpaint: horizontal and vertical blend, crop, background, counters
   PCV_K_COUNT
 };
 

@@ -99,7 +99,7 @@ int xray_node_images(pcv_xray* x, uint64_t first, uint64_t count, int mem, uint8
   const uint64_t tile_bytes = 4ull * x->W * x->W;
   if (mem == PCV_MEM_DEVICE && !ctx) return xray_fail(x, PCV_E_INVALID, "xray: a quadtree opened without a context has host images only");
   if (ctx) PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (x->kind == kXrayBuilt) {
+  if (xray_owns_tiles(x)) {
     const int rc = queue_node_images(x, first, count, rgba, mem == PCV_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice);
     if (rc) return rc;
     PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -417,7 +417,7 @@ int xray_device_node_files(pcv_xray* x, uint64_t first, uint64_t count, int mode
 // the files of nodes [first, first + count) of any kind of quadtree: opened nodes as their files are, the others encoded
 int xray_node_files(pcv_xray* x, uint64_t first, uint64_t count, int mode, bool parallel, const XrayFileSink& sink) {
   if (count == 0) return PCV_OK;
-  if (x->kind == kXrayBuilt) return xray_device_node_files(x, first, count, mode, parallel, sink);
+  if (xray_owns_tiles(x)) return xray_device_node_files(x, first, count, mode, parallel, sink);
   if (x->kind == kXrayOpened) {
     std::vector<uint8_t> file;
     for (uint64_t i = first; i < first + count; ++i) {
@@ -571,7 +571,7 @@ extern "C" int pcv_xray_write_dir_ex(pcv_xray* x, const char* directory, int mod
   if (rc) return rc;
   XrayMeta m;
   double rect[3];
-  if (merged) std::memcpy(rect, x->geo.rect, sizeof(rect));
+  if (merged || x->kind == kXrayInpainted) std::memcpy(rect, x->geo.rect, sizeof(rect));  // kept as the root's rect
   else built_root_rect(x, rect);
   m.min[0] = rect[0];
   m.min[1] = rect[1];

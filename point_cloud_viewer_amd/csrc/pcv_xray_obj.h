@@ -1,5 +1,6 @@
 // pcv_xray_obj.h — the xray quadtree handle as its sources share it: pcv_xray.hip (leaf level, the handle's life),
-// pcv_xray_pyramid.hip (parent levels, merge) and pcv_xray_files.hip (node images and files of any kind of quadtree).
+// pcv_xray_pyramid.hip (parent levels, merge), pcv_xray_inpaint.hip (hole filling) and pcv_xray_files.hip (node images and
+// files of any kind of quadtree).
 #pragma once
 #include <cstring>
 #include <string>
@@ -19,7 +20,9 @@ struct PCV_XRAY_LOCAL LeafGeometry {
   double leaf_edge;
 };
 
-enum XrayKind : uint32_t { kXrayBuilt = 0, kXrayOpened = 1, kXrayMerged = 2 };
+// kXrayInpainted (pcv_xray_inpaint): owns leaf and parent images like a built quadtree (d_images, d_parents, created =
+// 0 .. n - 1) and carries its node list and its root's rect like an opened one
+enum XrayKind : uint32_t { kXrayBuilt = 0, kXrayOpened = 1, kXrayMerged = 2, kXrayInpainted = 3 };
 
 struct XrayPartRef {  // one part of a merged quadtree: its nodes are [first, first + count) of the merged node list
   pcv_xray* part;
@@ -55,6 +58,8 @@ struct pcv_xray {
   std::vector<uint64_t> parent_index;
   std::vector<uint64_t> level_first;
   uint32_t* d_parents = nullptr;
+  // inpainted (pcv_xray_inpaint_info): per leaf, within the final tile
+  std::vector<uint64_t> inpaint_target, inpaint_filled, inpaint_blended;
 };
 
 // Every live pcv_xray is known by address with its serial number: a merged quadtree refers to its parts, and asks here
@@ -65,8 +70,10 @@ PCV_XRAY_LOCAL bool xray_part_alive(const XrayPartRef& r);
 // a failure on a handle that may have no context (opened host only): the message goes where the caller can read it
 PCV_XRAY_LOCAL inline int xray_fail(const pcv_xray* x, int code, const std::string& msg) { return x->ctx ? x->ctx->fail(code, msg) : pcv_host_fail(code, msg); }
 PCV_XRAY_LOCAL inline int xray_not_built(const pcv_xray* x, const char* what) {
-  return xray_fail(x, PCV_E_INVALID, std::string("xray: ") + what + " needs a quadtree built by pcv_xray_run, not an opened or merged one");
+  return xray_fail(x, PCV_E_INVALID, std::string("xray: ") + what + " needs a quadtree built by pcv_xray_run, not an opened, merged or inpainted one");
 }
+// the node images live on the device in d_images (leaves) and d_parents: built and inpainted quadtrees
+PCV_XRAY_LOCAL inline bool xray_owns_tiles(const pcv_xray* x) { return x->kind == kXrayBuilt || x->kind == kXrayInpainted; }
 
 // The node list of any kind of quadtree: a built one's created leaves then its parents, an opened or merged one's own list
 struct XrayNodeId {
@@ -94,6 +101,21 @@ PCV_XRAY_LOCAL inline void built_root_rect(const pcv_xray* x, double rect[3]) {
     rect[2] = half;
   }
 }
+
+// pcv_xray_pyramid.hip. The levels above a set of nodes: the node list after them (plevel, pindex; first[k] = the first
+// parent of level from - 1 - k in it) and their images on the device
+struct XrayLevels {
+  std::vector<uint32_t> plevel;
+  std::vector<uint64_t> pindex, first;
+  uint32_t* d_parents = nullptr;
+};
+// the number of nodes create_non_leaf_nodes(base, from, to) makes
+PCV_XRAY_LOCAL uint64_t xray_count_levels(const std::vector<uint64_t>& base, uint32_t from, uint32_t to);
+// create_non_leaf_nodes(base, from, to) for the nodes `base` of level `from` (node positions 0 .. base.size() - 1, their
+// images at d_base), one xray_parent_kernel launch per level under the kernel-stat id `prof_id`. images: null (the parent
+// images are allocated here, before any launch, and freed on failure) or the caller's block of xray_count_levels tiles
+PCV_XRAY_LOCAL int xray_build_levels(pcv_ctx* ctx, uint32_t W, uint32_t bg, const std::vector<uint64_t>& base, uint32_t from, uint32_t to,
+                                     const uint32_t* d_base, int prof_id, uint32_t* images, XrayLevels* out);
 
 // pcv_xray_files.hip, for the merge's staging of root tiles (pcv_xray_pyramid.hip)
 // node images [first, first + count) of a built quadtree's node list into dst (host or device), no synchronisation

@@ -170,19 +170,22 @@ extern "C" int pcv_xray_lanczos_taps(uint32_t tile_size_px, uint32_t* left, uint
   return PCV_OK;
 }
 
-// The levels above a set of nodes: the node list after them (plevel, pindex; first[k] = the first parent of level
-// from - 1 - k in it) and their images on the device
-struct XrayLevels {
-  std::vector<uint32_t> plevel;
-  std::vector<uint64_t> pindex, first;
-  uint32_t* d_parents = nullptr;
-};
+uint64_t xray_count_levels(const std::vector<uint64_t>& base, uint32_t from, uint32_t to) {
+  uint64_t n = 0;
+  std::vector<uint64_t> below(base);
+  for (uint32_t level = from; !below.empty() && level > to; --level) {
+    for (uint64_t& i : below) i >>= 2;
+    std::sort(below.begin(), below.end());
+    below.erase(std::unique(below.begin(), below.end()), below.end());
+    n += below.size();
+  }
+  return n;
+}
 
-// create_non_leaf_nodes(base, from, to) for the nodes `base` of level `from` (node positions 0 .. base.size() - 1, their
-// images at d_base), one xray_parent_kernel launch per level under the kernel-stat id `prof_id`: the parent levels of a
-// built quadtree (base = the created leaves) and the upper levels of a merged one (base = the parts' roots)
-static int xray_build_levels(pcv_ctx* ctx, uint32_t W, uint32_t bg, const std::vector<uint64_t>& base, uint32_t from, uint32_t to,
-                             const uint32_t* d_base, int prof_id, XrayLevels* out) {
+// the parent levels of a built quadtree (base = the created leaves), the upper levels of a merged one (base = the parts'
+// roots) and the parents of an inpainted one (base = its leaves)
+int xray_build_levels(pcv_ctx* ctx, uint32_t W, uint32_t bg, const std::vector<uint64_t>& base, uint32_t from, uint32_t to,
+                      const uint32_t* d_base, int prof_id, uint32_t* images, XrayLevels* out) {
   const uint64_t nc = base.size();
   std::vector<uint32_t> plevel;
   std::vector<uint64_t> pindex, first;
@@ -226,14 +229,14 @@ static int xray_build_levels(pcv_ctx* ctx, uint32_t W, uint32_t bg, const std::v
   lanczos_taps(W, taps);
   PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   int rc;
-  uint32_t* d_parents = nullptr;
-  if ((rc = ctx->dev_alloc((void**)&d_parents, 4ull * W * W * np)))  // every parent image before any launch
+  uint32_t* d_parents = images;
+  if (!images && (rc = ctx->dev_alloc((void**)&d_parents, 4ull * W * W * np)))  // every parent image before any launch
     return ctx->fail(PCV_E_OOM, "xray: no device memory for " + std::to_string(np) + " parent images (" + ctx->last_error + ")");
   PcvScratch sc(ctx);
   int64_t* d_slots;
   LanczosTap* d_taps;
   if ((rc = sc.get(&d_slots, 4 * np)) || (rc = sc.get(&d_taps, W))) {
-    ctx->dev_free(d_parents);
+    if (!images) ctx->dev_free(d_parents);
     return rc;
   }
   PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_slots, slots.data(), 8 * slots.size(), hipMemcpyHostToDevice, ctx->stream));
@@ -263,12 +266,12 @@ static int xray_build_levels(pcv_ctx* ctx, uint32_t W, uint32_t bg, const std::v
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
       (void)hipStreamSynchronize(ctx->stream);
-      ctx->dev_free(d_parents);
+      if (!images) ctx->dev_free(d_parents);
       return ctx->fail(PCV_E_HIP, std::string("xray_parent_kernel: ") + hipGetErrorString(e));
     }
   }
   if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
-    ctx->dev_free(d_parents);
+    if (!images) ctx->dev_free(d_parents);
     return ctx->fail(PCV_E_HIP, "xray: parent levels failed");
   }
   out->d_parents = d_parents;
@@ -283,7 +286,7 @@ static int xray_build_parents(pcv_xray* x) {
   std::vector<uint64_t> leaves(nc);
   for (uint64_t c = 0; c < nc; ++c) leaves[c] = x->geo.index[x->created[c]];
   XrayLevels lv;
-  const int rc = xray_build_levels(x->ctx, x->W, x->bg, leaves, x->geo.deepest_level, x->root_level, x->d_images, PCV_K_XRAY_PARENT, &lv);
+  const int rc = xray_build_levels(x->ctx, x->W, x->bg, leaves, x->geo.deepest_level, x->root_level, x->d_images, PCV_K_XRAY_PARENT, nullptr, &lv);
   if (rc) return rc;
   x->d_parents = lv.d_parents;
   x->parent_level.swap(lv.plevel);
@@ -461,7 +464,7 @@ extern "C" int pcv_xray_merge(pcv_ctx* ctx, pcv_xray* const* parts, uint32_t num
       PcvProf prof(ctx, PCV_K_XRAY_MERGE_STAGE);
       for (uint64_t i = 0; !rc && i < num_built; ++i) {
         pcv_xray* part = parts[order[i]];
-        if (part->kind == kXrayBuilt) {
+        if (xray_owns_tiles(part)) {
           rc = queue_node_images(part, (uint64_t)plan.root_pos[order[i]], 1, d_stage + i * tile_bytes, hipMemcpyDeviceToDevice);
         } else {  // a merged part: through its own parts
           rc = xray_node_images(part, (uint64_t)plan.root_pos[order[i]], 1, PCV_MEM_DEVICE, d_stage + i * tile_bytes);
@@ -473,7 +476,7 @@ extern "C" int pcv_xray_merge(pcv_ctx* ctx, pcv_xray* const* parts, uint32_t num
     }
     XrayLevels lv;
     if (!rc)
-      rc = xray_build_levels(ctx, W, x->bg, base, plan.L, 0, reinterpret_cast<const uint32_t*>(d_stage), PCV_K_XRAY_MERGE_PARENT, &lv);
+      rc = xray_build_levels(ctx, W, x->bg, base, plan.L, 0, reinterpret_cast<const uint32_t*>(d_stage), PCV_K_XRAY_MERGE_PARENT, nullptr, &lv);
     else
       (void)hipStreamSynchronize(ctx->stream);
     if (host) ctx->host_release(host);  // the upload has completed: xray_build_levels returns after a stream sync

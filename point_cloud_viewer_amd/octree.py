@@ -6,6 +6,7 @@ Inputs may be numpy arrays (host) or torch CUDA tensors (device-resident; zero c
 """
 import ctypes as C
 import os
+import sys
 import weakref
 
 import numpy as np
@@ -1413,6 +1414,86 @@ def merge_xray_quadtrees(ctx, input_directories, output_directory, background="w
     return merged
 
 
+def _xray_handles(parts):
+    parts = list(parts)
+    return parts, (C.c_void_p * max(len(parts), 1))(*[p.handle for p in parts])
+
+
+def xray_inpaint_check(x, distance_px, neighbors=()):
+    """pcv_xray_inpaint_check (host only): raises PcvError(PCV_E_INVALID) with the message of what XrayTiles.inpaint would
+    refuse (a white background, a tile size that is no power of two, distance 255, a neighbour that does not fit)."""
+    lib = L.load_library()
+    nbs, arr = _xray_handles(neighbors)
+    err = C.create_string_buffer(512)
+    rc = lib.pcv_xray_inpaint_check(x.handle, arr, len(nbs), int(distance_px), err, 512)
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, err.value.decode(errors="replace"))
+
+
+def xray_inpaint_plan(x, neighbors=()):
+    """pcv_xray_inpaint_plan (host only): (slots, num_adjacent). slots is a (leaves, 9, 2) uint32 array of (part, node) per
+    slot of the stitched image (TopLeft, Top, TopRight, Left, the leaf, Right, BottomLeft, Bottom, BottomRight; part 0 = x,
+    k + 1 = neighbors[k]; node = position among that part's leaves), XRAY_INPAINT_ABSENT twice where no tile contributes;
+    num_adjacent is the number of neighbour leaves taken."""
+    lib = L.load_library()
+    nbs, arr = _xray_handles(neighbors)
+    n = x.num_created  # the leaves that exist: a built quadtree's created tiles
+    slots = np.zeros((max(n, 1), 9, 2), dtype=np.uint32)
+    na, err = C.c_uint64(), C.create_string_buffer(512)
+    rc = lib.pcv_xray_inpaint_plan(x.handle, arr, len(nbs), n, slots.ctypes.data, C.byref(na), err, 512)
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, err.value.decode(errors="replace"))
+    return slots[:n], int(na.value)
+
+
+def inpaint_xray_quadtree(ctx, input_directory, output_directory, inpaint_distance_px, background="white", root_node_id="r",
+                          png="stored"):
+    """The reference's inpaint_xray_quadtree binary: the (possibly partial) quadtree with root root_node_id of
+    input_directory, inpainted with the leaves of the up to four adjacent quadtrees found there, written to
+    output_directory (which may be the input). Returns the inpainted XrayTiles. The fill differs from the reference's
+    texture synthesis (XrayTiles.inpaint); diagonal quadtrees are never read."""
+    level, index = quadtree_node_id(root_node_id)
+    parts = ctx.xray_open(input_directory)
+    roots = {}
+    for p in parts:
+        pl, pi = p.nodes()
+        if len(pl):
+            at = int(np.argmin(pl))
+            roots[(int(pl[at]), int(pi[at]))] = p
+    if (level, index) not in roots:
+        raise FileNotFoundError(f"no quadtree with root {root_node_id!r} in {str(input_directory)!r}")
+    x = roots[(level, index)]
+    rx, ry = _quadtree_xy(level, index)
+    neighbors = []
+    for dx, dy in ((-1, 0), (0, 1), (1, 0), (0, -1)):  # Left, Top, Right, Bottom
+        nx, ny = rx + dx, ry + dy
+        if 0 <= nx < (1 << level) and 0 <= ny < (1 << level) and (level, _quadtree_index(level, nx, ny)) in roots:
+            neighbors.append(roots[(level, _quadtree_index(level, nx, ny))])
+    if level != 0 and xray_inpaint_plan(x, neighbors)[1] == 0:
+        print(f"No adjacent leaf nodes found in neighboring quadtrees. Did you forget to copy them into {str(input_directory)!r}?",
+              file=sys.stderr)
+    os.makedirs(output_directory, exist_ok=True)
+    out = x.inpaint(inpaint_distance_px, background=background, neighbors=neighbors)
+    out.write(output_directory, png=png)
+    return out
+
+
+def _quadtree_xy(level, index):
+    """SpatialNodeId::from(NodeId) (quadtree/src/lib.rs:314-331)."""
+    x = y = 0
+    for b in range(level):
+        y |= ((index >> (2 * b)) & 1) << b
+        x |= ((index >> (2 * b + 1)) & 1) << b
+    return x, y
+
+
+def _quadtree_index(level, x, y):
+    index = 0
+    for b in range(level):
+        index |= ((y >> b) & 1) << (2 * b) | ((x >> b) & 1) << (2 * b + 1)
+    return index
+
+
 def _png_mode(png):
     if png not in ("stored", "deflate"):
         raise ValueError(f"unknown png mode {png!r} (stored or deflate)")
@@ -1715,6 +1796,32 @@ class XrayTiles:
         out = np.zeros(max(int(offsets[count]), 1), dtype=np.uint8)
         self._check(self.lib.pcv_xray_node_pngs(self.handle, int(first), count, mode, int(offsets[count]), out.ctypes.data, offsets.ctypes.data))
         return _split_files(out, offsets)
+
+    def inpaint(self, distance_px, background="white", neighbors=(), ctx=None):
+        """inpaint_xray_quadtree on the device (pcv_xray_inpaint): the holes of these leaf tiles (transparent background)
+        that a close of the alpha mask by distance_px covers are filled, overlapping enlarged tiles blended, the
+        background assigned and every parent level rebuilt; neighbors are the up to four quadtrees whose roots are Left,
+        Top, Right or Bottom of this one's. Everything but the fill equals the reference byte for byte; the fill is a
+        distance-weighted mean of the known pixels, not the reference's texture synthesis. Returns a new XrayTiles that
+        owns its images; this one and the neighbors may be freed. ctx: the context, for tiles opened without one."""
+        self._alive()
+        ctx = ctx if ctx is not None else self.ctx
+        if ctx is None:
+            raise ValueError("inpaint needs a context (these tiles were opened host only)")
+        nbs, arr = _xray_handles(neighbors)
+        h = C.c_void_p()
+        ctx._check(self.lib.pcv_xray_inpaint(ctx.handle, self.handle, arr, len(nbs), int(distance_px), _xray_background(background),
+                                             C.byref(h)))
+        return XrayTiles(ctx, h, int(self.lib.pcv_xray_tile_size(h)))
+
+    def inpaint_info(self):
+        """pcv_xray_inpaint_info of an inpainted quadtree: per leaf arrays target_pixels, filled_pixels, blended_pixels
+        (counted within the final tile) as a dict."""
+        self._alive()
+        n = self.num_created
+        t, f, b = (np.zeros(max(n, 1), dtype=np.uint64) for _ in range(3))
+        self._check(self.lib.pcv_xray_inpaint_info(self.handle, t.ctypes.data, f.ctypes.data, b.ctypes.data))
+        return {"target_pixels": t[:n], "filled_pixels": f[:n], "blended_pixels": b[:n]}
 
     def _check(self, rc):
         if self.ctx is not None:
