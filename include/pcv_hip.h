@@ -1102,6 +1102,57 @@ int pcv_octree_nodes_blob(pcv_octree* t, const uint64_t* node_indices, uint64_t 
  * same product). iso = translation xyz, unit quaternion i j k w. Outputs live where the inputs live. */
 int pcv_transform_points(pcv_ctx* ctx, const double iso[7], const pcv_points* points, double* ox, double* oy, double* oz);
 
+/* ---- S2 cell clouds ------------------------------------------------------------------ */
+/* `CellID::from_point(p).parent(level)` of the s2 crate for every point (what S2Splitter::write asks of it,
+ * src/read_write/s2.rs:75), restated from the public S2 definition: normalise, cube face, (u, v), the quadratic st, ij, the
+ * Hilbert curve. level 0 ..= 30 (30 = leaf cells); anything else is PCV_E_INVALID. No validity test: any point gets an id.
+ * `ids` lives where `mem` says; the points where points->mem says (colour and intensity are not read). The device's ids equal
+ * pcv_s2_cell_ids_host's bit for bit: one chain of correctly rounded f64 operations on both sides. */
+int pcv_s2_cell_ids(pcv_ctx* ctx, const pcv_points* points, uint32_t level, uint64_t* ids, int mem);
+/* Host only, no context (failures: pcv_host_last_error). */
+int pcv_s2_cell_ids_host(uint64_t n, const double* x, const double* y, const double* z, uint32_t level, uint64_t* ids);
+/* CellID::to_token (the stem of a cell's files, s2.rs:122): 16 lower-case hex digits without trailing zeros, "X" for 0. */
+int pcv_s2_cell_token(uint64_t id, char out[17]);
+
+/* CellUnion::contains(p) per point (the point test of S2Cells' cell-union queries, src/s2_cells/mod.rs): contains_cellid of
+ * the point's leaf cell over `cells`, num_cells cell ids of any levels in HOST memory, ascending by id (a list that descends
+ * anywhere, or holds a 0, is PCV_E_INVALID). keep[i] = 1 / 0 lives where `mem` says. Node culling for cell unions
+ * (normalize, rect_bound, Rect::intersects_cell) is not provided. */
+int pcv_s2_union_contains(pcv_ctx* ctx, const uint64_t* cells, uint32_t num_cells, const pcv_points* points, uint8_t* keep, int mem);
+/* Host only, no context: the same flags, bit for bit. */
+int pcv_s2_union_contains_host(const uint64_t* cells, uint32_t num_cells, uint64_t n, const double* x, const double* y,
+                               const double* z, uint8_t* keep);
+
+/* S2Splitter::write + get_meta (src/read_write/s2.rs:60-173) for ONE batch: the points grouped by their cell at
+ * split_level (0 ..= 30; DEFAULT_S2_SPLIT_LEVEL is 20), cells ascending by id, the points of a cell in input order, as
+ * cell-contiguous device blobs: xyz as 24-byte AoS f64 (Encoding::Plain), rgb at 3 bytes, intensity at 4 bytes when
+ * points->intensity is set. points->color is required. Fewer than 2^32 - 1 points per call.
+ * A point whose radius sqrt(x*x + y*y + z*z) is above 6 384 400 or below 6 352 800 (s2.rs:64-65), or that has a NaN coordinate
+ * (a departure: the reference lets NaN through both comparisons), is invalid: PCV_E_INVALID, pcv_last_error names the FIRST such
+ * point in input order with its index and coordinates, *out is NULL. The bounding box is the exact min / max of the points.
+ * Appending batches across calls and OpenMode::Append are not provided. */
+typedef struct pcv_s2_cloud pcv_s2_cloud;
+int pcv_s2_split(pcv_ctx* ctx, const pcv_points* points, uint32_t split_level, pcv_s2_cloud** out);
+/* Any output may be NULL. */
+int pcv_s2_info(const pcv_s2_cloud* cloud, uint64_t* num_cells, uint64_t* num_points, double bbox_min[3], double bbox_max[3],
+                int* has_intensity, uint32_t* level);
+/* Per cell (S2CellMeta, src/s2_cells/mod.rs): id, num_points, and the offset of its first point in the blobs (host arrays of
+ * num_cells entries; any may be NULL). */
+int pcv_s2_cells(const pcv_s2_cloud* cloud, uint64_t* ids, uint64_t* counts, uint64_t* offsets);
+/* The permutation: input_index[slot] = index in the input of the point at `slot` of the blobs (num_points entries where `mem`
+ * says) — a stable sort of the points by cell id. */
+int pcv_s2_order(pcv_s2_cloud* cloud, uint32_t* input_index, int mem);
+/* The points of cells [first_cell, first_cell + num_cells) as they would stand in the cells' files, one after the other, into
+ * memory that lives where `mem` says (any output may be NULL). A range past the end, more points than `capacity`, or
+ * `intensity` on a cloud without it is PCV_E_INVALID and writes nothing. */
+int pcv_s2_cell_points(pcv_s2_cloud* cloud, uint64_t first_cell, uint64_t num_cells, uint64_t capacity, int mem, double* xyz,
+                       uint8_t* rgb, float* intensity);
+/* `<token>.xyz/.rgb[/.intensity]` per cell (s2.rs:121-136 over RawNodeWriter, Encoding::Plain) + meta.pb: version 13,
+ * bounding_box, s2 { cells, attributes: color = U8Vec3 (27), intensity = F32 (11) } (proto.proto:92-133). The reference emits
+ * cells and attributes in hash order; here cells ascend by id and color precedes intensity. PCV_E_IO names the file. */
+int pcv_s2_write_dir(pcv_s2_cloud* cloud, const char* directory);
+void pcv_s2_free(pcv_s2_cloud* cloud);
+
 #ifdef __cplusplus
 }
 #endif

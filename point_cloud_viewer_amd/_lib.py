@@ -313,6 +313,19 @@ _SIGNATURES = {
     "pcv_render_outline_info": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "pcv_octree_nodes_blob": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pcv_transform_points": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(Points), _vp, _vp, _vp]),
+    "pcv_s2_cell_ids": (C.c_int, [_vp, C.POINTER(Points), C.c_uint32, _vp, C.c_int]),
+    "pcv_s2_cell_ids_host": (C.c_int, [C.c_uint64, _vp, _vp, _vp, C.c_uint32, _vp]),
+    "pcv_s2_cell_token": (C.c_int, [C.c_uint64, C.c_char_p]),
+    "pcv_s2_union_contains": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(Points), _vp, C.c_int]),
+    "pcv_s2_union_contains_host": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "pcv_s2_split": (C.c_int, [_vp, C.POINTER(Points), C.c_uint32, C.POINTER(_vp)]),
+    "pcv_s2_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                              C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
+    "pcv_s2_cells": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "pcv_s2_order": (C.c_int, [_vp, _vp, C.c_int]),
+    "pcv_s2_cell_points": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _vp, _vp, _vp]),
+    "pcv_s2_write_dir": (C.c_int, [_vp, C.c_char_p]),
+    "pcv_s2_free": (None, [_vp]),
 }
 
 _lib = None

@@ -137,6 +137,11 @@ enum PcvKernelId {
   PCV_K_XRAY_INPAINT_LIST,    // pcv_xray_inpaint: the target pixels of a group compacted into one list
   PCV_K_XRAY_INPAINT_FILL,    // pcv_xray_inpaint: one thread per target pixel, weighted mean of the known pixels around it
   PCV_K_XRAY_INPAINT_BLEND,   // pcv_xray_inpaint: horizontal and vertical blend, crop, background, counters
+  PCV_K_S2_IDS,               // pcv_s2.hip: the cell id of every point at the split level, the first invalid point's index
+  PCV_K_S2_UNIQUE,            // pcv_s2.hip: distinct cells and their first slots from the sorted ids (count, scan, write)
+  PCV_K_S2_RANK,              // pcv_s2.hip: every point's dense cell rank by binary search, paired with its input index
+  PCV_K_S2_GATHER,            // pcv_s2.hip: xyz (24-byte AoS), rgb and intensity of every point into the cell-contiguous blobs
+  PCV_K_S2_UNION,             // pcv_s2.hip: CellUnion::contains per point
   PCV_K_COUNT
 };
 
@@ -600,3 +605,10 @@ int pcv_make_levels(const double bmin[3], const double bmax[3], double resolutio
 
 // A failure of a call that has no context to keep the message (pcv_png.cpp): kept per thread for pcv_host_last_error.
 int pcv_host_fail(int code, const std::string& msg);
+
+// pcv_io.cpp — an S2 cell cloud's directory from host copies of the cell-contiguous blobs: <token>.xyz / .rgb / .intensity per
+// cell and meta.pb with the s2 arm (cells ascending by id, `color` before `intensity`); *error names the file that failed
+int pcv_s2_write_files(const char* directory, const double bbox_min[3], const double bbox_max[3], uint64_t num_cells,
+                       const uint64_t* ids, const uint64_t* counts, const uint64_t* offsets, const uint8_t* xyz, const uint8_t* rgb,
+                       const uint8_t* intensity /* null: no intensity attribute */, std::string* error);
+std::string pcv_s2_token(uint64_t id);

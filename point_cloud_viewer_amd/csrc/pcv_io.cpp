@@ -282,6 +282,77 @@ static int write_nodes(pcv_octree* t, const char* directory, uint32_t min_level,
 }
 
 // ------------------------------------------------------------------------------------------------
+// S2 cell clouds (src/read_write/s2.rs, src/s2_cells/mod.rs): <token>.xyz (Encoding::Plain: f64 AoS) / .rgb / .intensity per
+// cell, meta.pb = Meta { version, bounding_box, s2 { cells { id, num_points }, attributes { name, data_type } } }
+// (proto.proto:92-133, 143)
+// ------------------------------------------------------------------------------------------------
+// CellID::to_token: 16 lower-case hex digits without their trailing zeros, "X" for 0
+std::string pcv_s2_token(uint64_t id) {
+  if (id == 0) return "X";
+  char hex[17];
+  snprintf(hex, sizeof(hex), "%016llx", (unsigned long long)id);
+  std::string s(hex);
+  while (!s.empty() && s.back() == '0') s.pop_back();
+  return s;
+}
+
+int pcv_s2_write_files(const char* directory, const double bbox_min[3], const double bbox_max[3], uint64_t num_cells,
+                       const uint64_t* ids, const uint64_t* counts, const uint64_t* offsets, const uint8_t* xyz, const uint8_t* rgb,
+                       const uint8_t* intensity, std::string* error) {
+  const std::string dir(directory);
+  ::mkdir(dir.c_str(), 0777);
+  struct stat st;
+  if (stat(dir.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) {
+    *error = "cannot create directory " + dir;
+    return PCV_E_IO;
+  }
+  const int dirfd = open(dir.c_str(), O_RDONLY | O_DIRECTORY | O_CLOEXEC);
+  if (dirfd < 0) {
+    *error = "cannot open directory " + dir;
+    return PCV_E_IO;
+  }
+  std::vector<uint8_t> s2;
+  for (uint64_t k = 0; k < num_cells && error->empty(); ++k) {
+    const std::string stem = pcv_s2_token(ids[k]);
+    const uint64_t at = offsets[k], np = counts[k];
+    if (!write_file_at(dirfd, stem + ".xyz", xyz + at * 24, np * 24)) *error = "cannot write " + dir + "/" + stem + ".xyz";
+    else if (!write_file_at(dirfd, stem + ".rgb", rgb + at * 3, np * 3)) *error = "cannot write " + dir + "/" + stem + ".rgb";
+    else if (intensity && !write_file_at(dirfd, stem + ".intensity", intensity + at * 4, np * 4))
+      *error = "cannot write " + dir + "/" + stem + ".intensity";
+    std::vector<uint8_t> cell;  // S2Cell
+    tag(cell, 1, 0);
+    varint(cell, ids[k]);
+    tag(cell, 2, 0);
+    varint(cell, np);
+    bytes_field(s2, 1, cell);
+  }
+  ::close(dirfd);
+  if (!error->empty()) return PCV_E_IO;
+  auto attribute = [&](const char* name, int data_type) {
+    std::vector<uint8_t> a;
+    bytes_field(a, 1, std::vector<uint8_t>(name, name + strlen(name)));
+    tag(a, 2, 0);
+    varint(a, (uint64_t)data_type);
+    bytes_field(s2, 2, a);
+  };
+  attribute("color", 27);                      // AttributeDataType::U8Vec3
+  if (intensity) attribute("intensity", 11);   // AttributeDataType::F32
+  std::vector<uint8_t> cuboid;
+  bytes_field(cuboid, 3, vec3d(bbox_min));
+  bytes_field(cuboid, 4, vec3d(bbox_max));
+  std::vector<uint8_t> meta;
+  tag(meta, 1, 0);
+  varint(meta, 13);  // CURRENT_VERSION src/lib.rs:48
+  bytes_field(meta, 4, cuboid);
+  bytes_field(meta, 7, s2);
+  if (!write_file(dir + "/meta.pb", meta.data(), meta.size())) {
+    *error = "cannot write " + dir + "/meta.pb";
+    return PCV_E_IO;
+  }
+  return PCV_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Loading: Octree::from_data_provider over a directory (src/octree/mod.rs:156-215, data_provider/on_disk.rs)
 // ------------------------------------------------------------------------------------------------
 namespace {

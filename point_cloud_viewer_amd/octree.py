@@ -373,6 +373,44 @@ class Context:
         self._check(self.lib.pcv_transform_points(self.handle, iso, C.byref(p), *ptrs))
         return out
 
+    # ---- S2 cell clouds --------------------------------------------------------------
+    def s2_cell_ids(self, x, y, z, level=30):
+        """pcv_s2_cell_ids: CellID::from_point(p).parent(level) per point on the device, as uint64 (numpy for host
+        inputs; for device tensors an int64 tensor holding the same 64 bits)."""
+        p, keep_alive = self._points(x, y, z)
+        if p.mem == L.MEM_DEVICE:
+            import torch
+            ids = torch.empty(p.n, dtype=torch.int64, device=x.device)
+            self._check(self.lib.pcv_s2_cell_ids(self.handle, C.byref(p), int(level), ids.data_ptr(), L.MEM_DEVICE))
+            return ids
+        ids = np.zeros(p.n, dtype=np.uint64)
+        self._check(self.lib.pcv_s2_cell_ids(self.handle, C.byref(p), int(level), ids.ctypes.data, L.MEM_HOST))
+        return ids
+
+    def s2_union_contains(self, cells, x, y, z):
+        """pcv_s2_union_contains: CellUnion::contains per point for `cells`, cell ids ascending; uint8 flags that live
+        where the points live."""
+        cells = np.ascontiguousarray(cells, dtype=np.uint64).ravel()
+        p, keep_alive = self._points(x, y, z)
+        if p.mem == L.MEM_DEVICE:
+            import torch
+            keep = torch.empty(p.n, dtype=torch.uint8, device=x.device)
+            ptr = keep.data_ptr()
+        else:
+            keep = np.zeros(p.n, dtype=np.uint8)
+            ptr = keep.ctypes.data
+        self._check(self.lib.pcv_s2_union_contains(self.handle, cells.ctypes.data, cells.size, C.byref(p), ptr, p.mem))
+        return keep
+
+    def s2_split(self, points, split_level=20):
+        """S2Splitter::write for one batch: `points` = dict(x=, y=, z=, color=[, intensity=]) of ECEF points (host arrays or
+        device tensors) grouped by their S2 cell at split_level -> S2Cloud. An invalid ECEF point raises PcvError
+        (PCV_E_INVALID) naming the first one."""
+        p, keep_alive = self._points(points["x"], points["y"], points["z"], points["color"], points.get("intensity"))
+        h = C.c_void_p()
+        self._check(self.lib.pcv_s2_split(self.handle, C.byref(p), int(split_level), C.byref(h)))
+        return S2Cloud(self, h)
+
     # ---- stage-level entry points ----------------------------------------------------------------
     def aabb_reduce(self, x, y, z):
         p, keep = self._points(x, y, z)
@@ -1922,6 +1960,119 @@ def build_octree_from_file(output_directory, resolution, filename, attributes=("
 
 
 _default_ctx = None
+
+
+class S2Cloud:
+    """An S2 cell cloud held by the library (pcv_s2_cloud): the cells ascending by id and cell-contiguous device blobs."""
+
+    def __init__(self, ctx, handle):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.handle = handle
+        ctx._children.add(self)
+        nc, n, has_int, level = C.c_uint64(), C.c_uint64(), C.c_int(), C.c_uint32()
+        bmin, bmax = (C.c_double * 3)(), (C.c_double * 3)()
+        ctx._check(self.lib.pcv_s2_info(handle, C.byref(nc), C.byref(n), bmin, bmax, C.byref(has_int), C.byref(level)))
+        self.num_cells, self.num_points, self.has_intensity, self.split_level = nc.value, n.value, bool(has_int.value), level.value
+        self.bbox_min, self.bbox_max = np.array(bmin[:]), np.array(bmax[:])
+        self._cells = None
+
+    def _alive(self):
+        if not self.handle or not self.ctx.handle:
+            raise ValueError("this S2 cell cloud has been freed")
+
+    @property
+    def cells(self):
+        """(ids, counts, offsets): uint64 arrays, one entry per cell, ascending by id; offsets count points."""
+        if self._cells is None:
+            self._alive()
+            ids, counts, offsets = (np.zeros(self.num_cells, dtype=np.uint64) for _ in range(3))
+            self.ctx._check(self.lib.pcv_s2_cells(self.handle, ids.ctypes.data, counts.ctypes.data, offsets.ctypes.data))
+            self._cells = (ids, counts, offsets)
+        return self._cells
+
+    @property
+    def order(self):
+        """The permutation: order[slot] = input index of the point at `slot` (a stable sort of the input by cell id)."""
+        self._alive()
+        out = np.zeros(self.num_points, dtype=np.uint32)
+        self.ctx._check(self.lib.pcv_s2_order(self.handle, out.ctypes.data, L.MEM_HOST))
+        return out
+
+    def tokens(self):
+        return [s2_cell_token(int(i)) for i in self.cells[0]]
+
+    def cell_points(self, first=0, count=None):
+        """(xyz (m, 3) f64, rgb (m, 3) u8, intensity (m,) f32 or None) of cells [first, first + count), as in their files."""
+        self._alive()
+        count = self.num_cells - first if count is None else count
+        if first < 0 or count < 0 or first + count > self.num_cells:
+            raise ValueError("cell range past the end")
+        m = int(self.cells[1][first:first + count].sum())
+        xyz, rgb = np.zeros((m, 3)), np.zeros((m, 3), dtype=np.uint8)
+        inten = np.zeros(m, dtype=np.float32) if self.has_intensity else None
+        self.ctx._check(self.lib.pcv_s2_cell_points(self.handle, first, count, m, L.MEM_HOST, xyz.ctypes.data, rgb.ctypes.data,
+                                                    inten.ctypes.data if inten is not None else None))
+        return xyz, rgb, inten
+
+    def write(self, directory):
+        """<token>.xyz/.rgb[/.intensity] per cell + meta.pb (pcv_s2_write_dir)."""
+        self._alive()
+        self.ctx._check(self.lib.pcv_s2_write_dir(self.handle, os.fsencode(directory)))
+
+    def free(self):
+        if self.handle and self.ctx.handle:
+            self.lib.pcv_s2_free(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _host_check(rc, what):
+    if rc != L.PCV_OK:
+        msg = L.load_library().pcv_host_last_error()
+        raise L.PcvError(rc, (msg.decode() if msg else "") or what)
+
+
+def s2_cell_ids(x, y, z, level=30):
+    """pcv_s2_cell_ids_host (host only): CellID::from_point(p).parent(level) per point, the chain the device runs."""
+    x, y, z = _wmr_xyz(x, y, z)
+    ids = np.zeros(x.size, dtype=np.uint64)
+    if not 0 <= int(level) <= 0xFFFFFFFF:
+        raise L.PcvError(L.PCV_E_INVALID, "an S2 level is 0 ..= 30")
+    _host_check(L.load_library().pcv_s2_cell_ids_host(x.size, x.ctypes.data, y.ctypes.data, z.ctypes.data, int(level), ids.ctypes.data),
+                "pcv_s2_cell_ids_host")
+    return ids
+
+
+def s2_cell_token(cell_id):
+    """CellID::to_token: the stem of a cell's files."""
+    out = C.create_string_buffer(17)
+    _host_check(L.load_library().pcv_s2_cell_token(int(cell_id), out), "pcv_s2_cell_token")
+    return out.value.decode()
+
+
+def s2_union_contains(cells, x, y, z):
+    """pcv_s2_union_contains_host (host only): CellUnion::contains per point for cell ids ascending, as uint8 flags."""
+    cells = np.ascontiguousarray(cells, dtype=np.uint64).ravel()
+    x, y, z = _wmr_xyz(x, y, z)
+    keep = np.zeros(x.size, dtype=np.uint8)
+    _host_check(L.load_library().pcv_s2_union_contains_host(cells.ctypes.data, cells.size, x.size, x.ctypes.data, y.ctypes.data,
+                                                            z.ctypes.data, keep.ctypes.data), "pcv_s2_union_contains_host")
+    return keep
+
+
+def build_s2_cells(output_directory, points, split_level=20, ctx=None):
+    """An S2 cell cloud directory from one batch of ECEF points, as S2Splitter (src/read_write/s2.rs) writes it: `points` =
+    dict(x=, y=, z=, color=[, intensity=]). Returns the S2Cloud."""
+    ctx = ctx or default_context()
+    cloud = ctx.s2_split(points, split_level)
+    cloud.write(output_directory)
+    return cloud
 
 
 def default_context():

@@ -440,7 +440,7 @@ impl HipOctree {
                 let se = r.south_east().to_zoomed_coordinate(0)? / 256.0;
                 s.params[..4].copy_from_slice(&[nw.x, nw.y, se.x, se.y]);
             }
-            PointLocation::S2Cells(_) => return None, // needs the s2 crate's cell unions: no kernel
+            PointLocation::S2Cells(_) => return None, // pcv_s2_union_contains tests points, but there is no node culling for a cell union
         }
         Some(s)
     }
