@@ -1116,8 +1116,8 @@ int pcv_s2_cell_token(uint64_t id, char out[17]);
 
 /* CellUnion::contains(p) per point (the point test of S2Cells' cell-union queries, src/s2_cells/mod.rs): contains_cellid of
  * the point's leaf cell over `cells`, num_cells cell ids of any levels in HOST memory, ascending by id (a list that descends
- * anywhere, or holds a 0, is PCV_E_INVALID). keep[i] = 1 / 0 lives where `mem` says. Node culling for cell unions
- * (normalize, rect_bound, Rect::intersects_cell) is not provided. */
+ * anywhere, or holds a 0, is PCV_E_INVALID). keep[i] = 1 / 0 lives where `mem` says. The cells of a cloud under a union:
+ * pcv_s2_cells_in_location. */
 int pcv_s2_union_contains(pcv_ctx* ctx, const uint64_t* cells, uint32_t num_cells, const pcv_points* points, uint8_t* keep, int mem);
 /* Host only, no context: the same flags, bit for bit. */
 int pcv_s2_union_contains_host(const uint64_t* cells, uint32_t num_cells, uint64_t n, const double* x, const double* y,
@@ -1151,7 +1151,83 @@ int pcv_s2_cell_points(pcv_s2_cloud* cloud, uint64_t first_cell, uint64_t num_ce
  * bounding_box, s2 { cells, attributes: color = U8Vec3 (27), intensity = F32 (11) } (proto.proto:92-133). The reference emits
  * cells and attributes in hash order; here cells ascend by id and color precedes intensity. PCV_E_IO names the file. */
 int pcv_s2_write_dir(pcv_s2_cloud* cloud, const char* directory);
+/* S2Cells::from_data_provider + S2Meta::from_proto (src/s2_cells/mod.rs:107-154, 199-212) over a directory: the same object
+ * that pcv_s2_split makes; pcv_s2_info / _cells / _cell_points / _write_dir / _cells_in_location / _free work on it unchanged
+ * (pcv_s2_order does not: there is no input). meta.pb of version < 12: PCV_E_INVALID "No S2 point cloud supported with version
+ * N"; without the s2 arm: PCV_E_INVALID "This meta does not describe S2 point clouds" (the reference's messages). The cells
+ * may be listed in any order and come out ascending by id; `color` (U8Vec3) is required, `intensity` (F32) optional, other
+ * attributes are ignored. *level of pcv_s2_info is the common level of the ids, 0xffffffff when they differ. The cell files
+ * are read and uploaded on first use (cell_points, write_dir): a file whose size is not that of the cell's num_points (24 / 3 /
+ * 4 bytes each), or a missing file of a cell with points, is PCV_E_IO naming the file.
+ * ctx may be NULL (as for pcv_xray_open_dir): a host-only cloud, whose failures go to pcv_host_last_error; info, cells,
+ * cell_points into host memory and write_dir work, anything that needs the device is PCV_E_INVALID. */
+int pcv_s2_open_dir(pcv_ctx* ctx, const char* directory, pcv_s2_cloud** out);
 void pcv_s2_free(pcv_s2_cloud* cloud);
+
+/* ---- S2 cell clouds: the region side -------------------------------------------------- */
+/* What S2Cells::nodes_in_location (src/s2_cells/mod.rs:160-241) asks of the s2 crate, restated from the public S2 definition
+ * as one chain of correctly rounded f64 operations (no libm), so that the device's decisions are these host twins', bit for
+ * bit. A rect is four doubles: lat.lo, lat.hi (empty when lo > hi), lng.lo, lng.hi (an interval on the circle: inverted when
+ * lo > hi, empty = (pi, -pi), full = (-pi, pi)). Cells of level 0 (the six faces) have no geometry here: PCV_E_INVALID.
+ * Host only, no context (failures: pcv_host_last_error).
+ *
+ * Cell::from(id) as far as Rect::intersects_cell reads it, 30 doubles: rect_bound [0..4), lat / lng of the centre [4..6),
+ * the face's (u, v) bounds u.lo u.hi v.lo v.hi [6..10), the four unit vertices (lo,lo) (hi,lo) (hi,hi) (lo,hi) [10..22), their
+ * lat / lng [22..30). */
+int pcv_s2_cell_geometry_host(uint64_t cell, double geometry[30]);
+/* Cell::rect_bound alone. */
+int pcv_s2_cell_rect_host(uint64_t cell, double rect[4]);
+/* The region of cells_in_convex_polyhedron (mod.rs:224-231): CellID::from_point of the 8 corners (xyz each), normalize,
+ * rect_bound of the union. */
+int pcv_s2_corners_rect_host(const double corners[24], double rect[4]);
+/* Rect::intersects_cell: *intersects = 1 / 0. */
+int pcv_s2_rect_intersects_cell_host(const double rect[4], uint64_t cell, int* intersects);
+/* CellUnion::normalize in place: sorted, cells inside another dropped, four siblings merged into their parent;
+ * *num_cells is the length going in and coming out. */
+int pcv_s2_union_normalize_host(uint64_t* cells, uint32_t* num_cells);
+/* CellUnion::intersects_cellid for n cell ids against `cells` (ascending, as pcv_s2_union_contains takes them). */
+int pcv_s2_union_intersects_host(const uint64_t* cells, uint32_t num_cells, uint64_t n, const uint64_t* ids, uint8_t* intersects);
+
+/* S2Cells::nodes_in_location (mod.rs:160-241) for many locations in one call: first the shapes (nullable), then num_unions
+ * cell unions, union u being union_cells[union_first[u] .. union_first[u + 1]) in HOST memory, ascending by id, union_first[0] = 0.
+ *   AllPoints                                 every cell of the cloud
+ *   Aabb / Obb / Frustum / WebMercatorRect    the cells that the rect of pcv_s2_corners_rect_host(corners of the shape) intersects
+ *                                             (Rect::intersects_cell); a frustum whose matrix is not invertible has none
+ *   a cell union                              the cells with CellUnion::intersects_cellid
+ * counts[l] = number of cells of location l (may exceed `capacity`); cells[l * capacity ..] = the first min(counts[l],
+ * capacity) of them as indices into pcv_s2_cells' arrays, ASCENDING (the reference lists them in its hash map's order); the
+ * rest of a row is unspecified. counts and cells are host arrays. The first geometric call builds the cloud's cell table on the
+ * device (240 bytes per cell) and keeps it. A cloud with a level-0 cell takes AllPoints and unions only. The lists equal
+ * pcv_s2_cells_in_location_host's, bit for bit. */
+int pcv_s2_cells_in_location(pcv_s2_cloud* cloud, const pcv_shapes* shapes, uint32_t num_unions, const uint32_t* union_first,
+                             const uint64_t* union_cells, uint32_t capacity, uint32_t* counts, uint32_t* cells);
+/* The same over plain host arrays: the cloud's cell ids (ascending), and per shape its PCV_SHAPE_* kind, the `valid` flag and
+ * the 24 doubles of its corners as pcv_shapes_get_ex returns them. */
+int pcv_s2_cells_in_location_host(uint64_t num_cells, const uint64_t* cell_ids, uint32_t num_shapes, const int32_t* kinds,
+                                  const int32_t* valid, const double* corners, uint32_t num_unions, const uint32_t* union_first,
+                                  const uint64_t* union_cells, uint32_t capacity, uint32_t* counts, uint32_t* cells);
+
+/* The batched point query over an S2 cell cloud, shaped like pcv_query_batch_*: FilteredIterator over NodeIterator with
+ * Encoding::Plain (src/iterator.rs:96-119, src/s2_cells/mod.rs:171-191, stream_points_for_query_in_node) for every location
+ * of one call — the shapes (nullable) first, then the unions, given as for pcv_s2_cells_in_location. intervals: NULL, or 2
+ * doubles per location, a closed interval on intensity, read where interval_used is NULL or interval_used[l] != 0; an
+ * interval on a cloud without intensity is PCV_E_INVALID. One segment per (location, cell of its pcv_s2_cells_in_location
+ * list), locations one after another, cells ascending; a segment holds the cell's points, in file order, that pass
+ * `contains` (the per-point tests of pcv_cull_points, pcv_wmr_contains, pcv_s2_union_contains) and the interval — positions are
+ * the stored f64, untouched. Segments without points are present. The batch reads the cloud's blobs: free it first. */
+typedef struct pcv_s2_query pcv_s2_query;
+int pcv_s2_query_run(pcv_s2_cloud* cloud, const pcv_shapes* shapes, uint32_t num_unions, const uint32_t* union_first,
+                     const uint64_t* union_cells, const double* intervals, const uint8_t* interval_used, pcv_s2_query** out);
+int pcv_s2_query_sizes(const pcv_s2_query* q, uint64_t* num_segments, uint64_t* num_points);
+/* location_first_segment[locations + 1], segment_cell[num_segments] (indices into pcv_s2_cells' arrays),
+ * segment_offset[num_segments + 1] (the u64 scan of the segments' sizes); host arrays, any may be NULL. */
+int pcv_s2_query_segments(const pcv_s2_query* q, uint64_t* location_first_segment, uint32_t* segment_cell, uint64_t* segment_offset);
+/* The points of segments [first_segment, first_segment + num_segments) into buffers that live where `mem` says (any may be
+ * NULL): x / y / z planes, rgb at 3 bytes, intensity. A range past the end, more points than `capacity`, or `intensity` on a
+ * cloud without it is PCV_E_INVALID and writes nothing. */
+int pcv_s2_query_points(pcv_s2_query* q, uint64_t first_segment, uint64_t num_segments, uint64_t capacity, int mem, double* x,
+                        double* y, double* z, uint8_t* rgb, float* intensity);
+void pcv_s2_query_free(pcv_s2_query* q);
 
 #ifdef __cplusplus
 }

@@ -325,7 +325,21 @@ _SIGNATURES = {
     "pcv_s2_order": (C.c_int, [_vp, _vp, C.c_int]),
     "pcv_s2_cell_points": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _vp, _vp, _vp]),
     "pcv_s2_write_dir": (C.c_int, [_vp, C.c_char_p]),
+    "pcv_s2_query_run": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "pcv_s2_query_sizes": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "pcv_s2_query_segments": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "pcv_s2_query_points": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "pcv_s2_query_free": (None, [_vp]),
+    "pcv_s2_open_dir": (C.c_int, [_vp, C.c_char_p, C.POINTER(_vp)]),
     "pcv_s2_free": (None, [_vp]),
+    "pcv_s2_cell_geometry_host": (C.c_int, [C.c_uint64, _vp]),
+    "pcv_s2_cell_rect_host": (C.c_int, [C.c_uint64, _vp]),
+    "pcv_s2_corners_rect_host": (C.c_int, [_vp, _vp]),
+    "pcv_s2_rect_intersects_cell_host": (C.c_int, [_vp, C.c_uint64, C.POINTER(C.c_int)]),
+    "pcv_s2_union_normalize_host": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
+    "pcv_s2_union_intersects_host": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _vp, _vp]),
+    "pcv_s2_cells_in_location": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp]),
+    "pcv_s2_cells_in_location_host": (C.c_int, [C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp]),
 }
 
 _lib = None

@@ -142,6 +142,11 @@ enum PcvKernelId {
   PCV_K_S2_RANK,              // pcv_s2.hip: every point's dense cell rank by binary search, paired with its input index
   PCV_K_S2_GATHER,            // pcv_s2.hip: xyz (24-byte AoS), rgb and intensity of every point into the cell-contiguous blobs
   PCV_K_S2_UNION,             // pcv_s2.hip: CellUnion::contains per point
+  PCV_K_S2_CELL_TABLE,        // pcv_s2_query.hip: once per cloud, the planes of every cell's rect bound, centre, vertices
+  PCV_K_S2_LOCATIONS,         // pcv_s2_query.hip: one lane per shape, the rect bound of its corners' normalized cell union
+  PCV_K_S2_PAIRS,             // pcv_s2_query.hip: one wave per location over the cell table, the list ascending by cell id
+  PCV_K_S2_FLAGS,             // pcv_s2_points.hip: keep flags of every candidate point of every (location, listed cell)
+  PCV_K_S2_GATHER_POINTS,     // pcv_s2_points.hip: the kept points of a segment range into the caller's planes
   PCV_K_COUNT
 };
 

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "pcv_internal.h"
+#include "pcv_s2_obj.h"
 
 namespace {
 
@@ -469,6 +470,128 @@ bool read_file(const std::string& path, std::vector<uint8_t>* out, bool* missing
 }
 
 }  // namespace
+
+// ------------------------------------------------------------------------------------------------
+// S2Meta::from_proto + S2Cells::from_data_provider over a directory (src/s2_cells/mod.rs:107-154, 199-212)
+// ------------------------------------------------------------------------------------------------
+int pcv_s2_read_meta(const char* directory, PcvS2Dir* out, std::string* error) {
+  const std::string dir(directory);
+  std::vector<uint8_t> buf;
+  bool missing;
+  if (!read_file(dir + "/meta.pb", &buf, &missing)) {
+    *error = "cannot read " + dir + "/meta.pb";
+    return missing ? PCV_E_NOT_FOUND : PCV_E_IO;
+  }
+  int64_t version = 0;
+  bool has_s2 = false, has_color = false;
+  out->has_intensity = false;
+  for (int a = 0; a < 3; ++a) out->bbox_min[a] = out->bbox_max[a] = 0.0;
+  std::vector<std::pair<uint64_t, uint64_t>> cells;
+  Reader r{buf.data(), buf.data() + buf.size()};
+  while (r.p < r.end && r.ok) {
+    const uint64_t t = r.varint();
+    const int f = (int)(t >> 3), w = (int)(t & 7);
+    if (f == 1 && w == 0) version = (int64_t)r.varint();
+    else if (f == 4 && w == 2) read_cuboid(r.sub(), out->bbox_min, out->bbox_max);
+    else if (f == 7 && w == 2) {
+      has_s2 = true;
+      Reader s = r.sub();
+      while (s.p < s.end && s.ok) {
+        const uint64_t st = s.varint();
+        const int sf = (int)(st >> 3), sw = (int)(st & 7);
+        if (sf == 1 && sw == 2) {  // S2Cell { id, num_points }
+          Reader c = s.sub();
+          uint64_t id = 0, np = 0;
+          while (c.p < c.end && c.ok) {
+            const uint64_t ct = c.varint();
+            const int cf = (int)(ct >> 3), cw = (int)(ct & 7);
+            if (cf == 1 && cw == 0) id = c.varint();
+            else if (cf == 2 && cw == 0) np = c.varint();
+            else c.skip(cw);
+          }
+          if (!c.ok) s.ok = false;
+          cells.emplace_back(id, np);
+        } else if (sf == 2 && sw == 2) {  // Attribute { name, data_type }
+          Reader a = s.sub();
+          std::string name;
+          uint64_t type = 0;
+          while (a.p < a.end && a.ok) {
+            const uint64_t at = a.varint();
+            const int af = (int)(at >> 3), aw = (int)(at & 7);
+            if (af == 1 && aw == 2) {
+              Reader n = a.sub();
+              name.assign((const char*)n.p, (size_t)(n.end - n.p));
+            } else if (af == 2 && aw == 0) type = a.varint();
+            else a.skip(aw);
+          }
+          if (!a.ok) s.ok = false;
+          if (name == "color" && type == 27) has_color = true;            // AttributeDataType::U8Vec3
+          else if (name == "intensity" && type == 11) out->has_intensity = true;  // AttributeDataType::F32
+        } else s.skip(sw);
+      }
+      if (!s.ok) r.ok = false;
+    } else r.skip(w);
+  }
+  if (!r.ok) {
+    *error = dir + "/meta.pb is not a Meta message";
+    return PCV_E_IO;
+  }
+  if (version < 12) {  // mod.rs:109-116
+    *error = "No S2 point cloud supported with version " + std::to_string(version);
+    return PCV_E_INVALID;
+  }
+  if (!has_s2) {  // mod.rs:117-122
+    *error = "This meta does not describe S2 point clouds";
+    return PCV_E_INVALID;
+  }
+  if (!has_color) {
+    *error = dir + "/meta.pb lists no `color` attribute of type U8Vec3";
+    return PCV_E_INVALID;
+  }
+  // the reference keeps the cells in a hash map (a repeated id: the last entry stays); here they ascend by id
+  std::stable_sort(cells.begin(), cells.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+  out->ids.clear();
+  out->counts.clear();
+  for (size_t k = 0; k < cells.size(); ++k) {
+    if (k + 1 < cells.size() && cells[k + 1].first == cells[k].first) continue;
+    out->ids.push_back(cells[k].first);
+    out->counts.push_back(cells[k].second);
+  }
+  return PCV_OK;
+}
+
+int pcv_s2_read_cells(const char* directory, const PcvS2Dir& meta, uint8_t* xyz, uint8_t* rgb, uint8_t* intensity, std::string* error) {
+  const std::string dir(directory);
+  uint64_t at = 0;
+  std::vector<uint8_t> buf;
+  for (size_t k = 0; k < meta.ids.size(); ++k) {
+    const uint64_t np = meta.counts[k];
+    const std::string stem = dir + "/" + pcv_s2_token(meta.ids[k]);
+    struct Part {
+      const char* ext;
+      uint8_t* to;
+      uint64_t stride;
+    } parts[3] = {{".xyz", xyz, 24}, {".rgb", rgb, 3}, {".intensity", meta.has_intensity ? intensity : nullptr, 4}};
+    for (const Part& part : parts) {
+      if (!part.to) continue;
+      bool missing;
+      const std::string path = stem + part.ext;
+      if (!read_file(path, &buf, &missing)) {
+        if (missing && np == 0) continue;
+        *error = (missing ? "missing cell file " : "cannot read ") + path;
+        return PCV_E_IO;
+      }
+      if (buf.size() != np * part.stride) {
+        *error = path + " holds " + std::to_string(buf.size()) + " bytes, " + std::to_string(np) + " points need " +
+                 std::to_string(np * part.stride);
+        return PCV_E_IO;
+      }
+      if (np) std::memcpy(part.to + at * part.stride, buf.data(), buf.size());
+    }
+    at += np;
+  }
+  return PCV_OK;
+}
 
 extern "C" int pcv_octree_open_dir(pcv_ctx* ctx, const char* directory, pcv_octree** out) {
   if (!ctx) return PCV_E_INVALID;

@@ -12,17 +12,9 @@
 
 #include "pcv_internal.h"
 #include "pcv_s2_dev.h"
+#include "pcv_s2_obj.h"
 
-struct pcv_s2_cloud {
-  pcv_ctx* ctx = nullptr;
-  uint64_t n = 0;
-  uint32_t level = 0;
-  bool has_intensity = false;
-  double bbox_min[3] = {0, 0, 0}, bbox_max[3] = {0, 0, 0};
-  std::vector<uint64_t> ids, counts, offsets;  // per cell, ascending by id; offsets in points
-  uint32_t* d_order = nullptr;                 // slot -> input index
-  uint8_t *d_xyz = nullptr, *d_rgb = nullptr, *d_int = nullptr;
-};
+int pcv_s2_cloud::fail(int code, const std::string& msg) const { return ctx ? ctx->fail(code, msg) : pcv_host_fail(code, msg); }
 
 namespace {
 
@@ -247,8 +239,53 @@ void release_cloud(pcv_s2_cloud* c) {
     if (c->d_xyz) c->ctx->dev_free(c->d_xyz);
     if (c->d_rgb) c->ctx->dev_free(c->d_rgb);
     if (c->d_int) c->ctx->dev_free(c->d_int);
+    if (c->d_ids) c->ctx->dev_free(c->d_ids);
+    if (c->d_table) c->ctx->dev_free(c->d_table);
   }
   delete c;
+}
+
+// an opened cloud's cell files, read and uploaded on first use (as an opened octree's node files are)
+int ensure_resident(pcv_s2_cloud* c) {
+  if (c->resident) return PCV_OK;
+  pcv_ctx* ctx = c->ctx;
+  if (c->n) {
+    PcvS2Dir meta;
+    meta.ids = c->ids, meta.counts = c->counts, meta.has_intensity = c->has_intensity;
+    std::vector<uint8_t> xyz, rgb, inten;
+    try {
+      xyz.resize(c->n * 24);
+      rgb.resize(c->n * 3);
+      if (c->has_intensity) inten.resize(c->n * 4);
+    } catch (...) {
+      return c->fail(PCV_E_OOM, "no host memory for the cell files of " + c->directory);
+    }
+    std::string error;
+    int rc = pcv_s2_read_cells(c->directory.c_str(), meta, xyz.data(), rgb.data(), c->has_intensity ? inten.data() : nullptr, &error);
+    if (rc != PCV_OK) return c->fail(rc, error);
+    if (!ctx) {  // host only: the blobs stay where they are
+      c->h_xyz.swap(xyz), c->h_rgb.swap(rgb), c->h_int.swap(inten);
+      c->resident = true;
+      return PCV_OK;
+    }
+    PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    uint8_t *d_xyz = nullptr, *d_rgb = nullptr, *d_int = nullptr;
+    if ((rc = ctx->dev_alloc((void**)&d_xyz, c->n * 24)) == PCV_OK && (rc = ctx->dev_alloc((void**)&d_rgb, c->n * 3)) == PCV_OK && c->has_intensity)
+      rc = ctx->dev_alloc((void**)&d_int, c->n * 4);
+    if (rc == PCV_OK && (rc = ctx->h2d(d_xyz, xyz.data(), c->n * 24)) == PCV_OK && (rc = ctx->h2d(d_rgb, rgb.data(), c->n * 3)) == PCV_OK && d_int)
+      rc = ctx->h2d(d_int, inten.data(), c->n * 4);
+    if (rc == PCV_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = ctx->fail(PCV_E_HIP, "uploading the cell files failed");
+    if (rc != PCV_OK) {
+      (void)hipStreamSynchronize(ctx->stream);
+      if (d_xyz) ctx->dev_free(d_xyz);
+      if (d_rgb) ctx->dev_free(d_rgb);
+      if (d_int) ctx->dev_free(d_int);
+      return rc;
+    }
+    c->d_xyz = d_xyz, c->d_rgb = d_rgb, c->d_int = d_int;
+  }
+  c->resident = true;
+  return PCV_OK;
 }
 
 int split_impl(pcv_ctx* ctx, const pcv_points* points, uint32_t level, pcv_s2_cloud* c) {
@@ -371,7 +408,9 @@ int split_impl(pcv_ctx* ctx, const pcv_points* points, uint32_t level, pcv_s2_cl
   return PCV_OK;
 }
 
-int check_union(const uint64_t* cells, uint32_t num_cells, std::string* why) {
+}  // namespace
+
+int pcv_s2_check_union(const uint64_t* cells, uint32_t num_cells, std::string* why) {
   if (num_cells && !cells) {
     *why = "cells is null";
     return PCV_E_INVALID;
@@ -389,7 +428,7 @@ int check_union(const uint64_t* cells, uint32_t num_cells, std::string* why) {
   return PCV_OK;
 }
 
-}  // namespace
+int pcv_s2_make_resident(pcv_s2_cloud* c) { return ensure_resident(c); }
 
 // ---- host twins (no context) --------------------------------------------------------------------------------------------
 extern "C" int pcv_s2_cell_ids_host(uint64_t n, const double* x, const double* y, const double* z, uint32_t level, uint64_t* ids) {
@@ -409,7 +448,7 @@ extern "C" int pcv_s2_cell_token(uint64_t id, char out[17]) {
 extern "C" int pcv_s2_union_contains_host(const uint64_t* cells, uint32_t num_cells, uint64_t n, const double* x, const double* y,
                                           const double* z, uint8_t* keep) {
   std::string why;
-  if (check_union(cells, num_cells, &why)) return pcv_host_fail(PCV_E_INVALID, why);
+  if (pcv_s2_check_union(cells, num_cells, &why)) return pcv_host_fail(PCV_E_INVALID, why);
   if (n && (!x || !y || !z || !keep)) return pcv_host_fail(PCV_E_INVALID, "null argument");
   for (uint64_t i = 0; i < n; ++i) keep[i] = s2::union_contains(cells, num_cells, s2::leaf_from_point(x[i], y[i], z[i])) ? 1 : 0;
   return PCV_OK;
@@ -448,7 +487,7 @@ extern "C" int pcv_s2_union_contains(pcv_ctx* ctx, const uint64_t* cells, uint32
   int rc = check_points(ctx, points, false);
   if (rc) return rc;
   std::string why;
-  if (check_union(cells, num_cells, &why)) return ctx->fail(PCV_E_INVALID, why);
+  if (pcv_s2_check_union(cells, num_cells, &why)) return ctx->fail(PCV_E_INVALID, why);
   if (mem != PCV_MEM_HOST && mem != PCV_MEM_DEVICE) return ctx->fail(PCV_E_INVALID, "bad mem");
   const uint64_t n = points->n;
   if (n == 0) return PCV_OK;
@@ -491,6 +530,40 @@ extern "C" int pcv_s2_split(pcv_ctx* ctx, const pcv_points* points, uint32_t spl
   return PCV_OK;
 }
 
+// S2Cells::from_data_provider (src/s2_cells/mod.rs:199-212) over a directory
+extern "C" int pcv_s2_open_dir(pcv_ctx* ctx, const char* directory, pcv_s2_cloud** out) {
+  auto fail = [&](int code, const std::string& m) { return ctx ? ctx->fail(code, m) : pcv_host_fail(code, m); };
+  if (!directory || !out) return fail(PCV_E_INVALID, "null argument");
+  *out = nullptr;
+  PcvS2Dir meta;
+  std::string error;
+  const int rc = pcv_s2_read_meta(directory, &meta, &error);
+  if (rc != PCV_OK) return fail(rc, error);
+  pcv_s2_cloud* c = new pcv_s2_cloud();
+  c->ctx = ctx;
+  c->directory = directory;
+  c->opened = true;
+  c->has_intensity = meta.has_intensity;
+  std::memcpy(c->bbox_min, meta.bbox_min, 24);
+  std::memcpy(c->bbox_max, meta.bbox_max, 24);
+  c->ids = meta.ids;
+  c->counts = meta.counts;
+  c->offsets.resize(c->ids.size());
+  c->level = 0xffffffffu;  // the common level of the ids; 0xffffffff when they differ (legal for the reader) or there are none
+  for (size_t k = 0; k < c->ids.size(); ++k) {
+    c->offsets[k] = c->n;
+    c->n += c->counts[k];
+    const uint64_t id = c->ids[k];
+    const uint32_t tz = id ? (uint32_t)__builtin_ctzll(id) : 1u;
+    const uint32_t level = (tz & 1u) || tz > 60u ? 0xffffffffu : (uint32_t)s2::kMaxLevel - (tz >> 1);
+    if (k == 0) c->level = level;
+    else if (c->level != level) c->level = 0xffffffffu;
+  }
+  c->resident = c->n == 0;
+  *out = c;
+  return PCV_OK;
+}
+
 extern "C" int pcv_s2_info(const pcv_s2_cloud* c, uint64_t* num_cells, uint64_t* num_points, double bbox_min[3], double bbox_max[3],
                            int* has_intensity, uint32_t* level) {
   if (!c) return PCV_E_INVALID;
@@ -518,6 +591,7 @@ extern "C" int pcv_s2_cells(const pcv_s2_cloud* c, uint64_t* ids, uint64_t* coun
 
 extern "C" int pcv_s2_order(pcv_s2_cloud* c, uint32_t* input_index, int mem) {
   if (!c) return PCV_E_INVALID;
+  if (c->opened) return c->fail(PCV_E_INVALID, "an S2 cell cloud opened from a directory has no input order");
   pcv_ctx* ctx = c->ctx;
   if (mem != PCV_MEM_HOST && mem != PCV_MEM_DEVICE) return ctx->fail(PCV_E_INVALID, "bad mem");
   if (c->n == 0) return PCV_OK;
@@ -533,15 +607,23 @@ extern "C" int pcv_s2_cell_points(pcv_s2_cloud* c, uint64_t first_cell, uint64_t
                                   uint8_t* rgb, float* intensity) {
   if (!c) return PCV_E_INVALID;
   pcv_ctx* ctx = c->ctx;
-  if (mem != PCV_MEM_HOST && mem != PCV_MEM_DEVICE) return ctx->fail(PCV_E_INVALID, "bad mem");
+  if (mem != PCV_MEM_HOST && mem != PCV_MEM_DEVICE) return c->fail(PCV_E_INVALID, "bad mem");
+  if (!ctx && mem != PCV_MEM_HOST) return c->fail(PCV_E_INVALID, "a cloud opened without a context serves host memory only");
   const uint64_t cells = c->ids.size();
-  if (first_cell > cells || num_cells > cells - first_cell) return ctx->fail(PCV_E_INVALID, "cell range past the end");
+  if (first_cell > cells || num_cells > cells - first_cell) return c->fail(PCV_E_INVALID, "cell range past the end");
   if (num_cells == 0) return PCV_OK;
   const uint64_t begin = c->offsets[first_cell];
   const uint64_t end = first_cell + num_cells < cells ? c->offsets[first_cell + num_cells] : c->n;
   const uint64_t count = end - begin;
-  if (count > capacity) return ctx->fail(PCV_E_INVALID, "the cells hold " + std::to_string(count) + " points, capacity is " + std::to_string(capacity));
-  if (intensity && !c->has_intensity) return ctx->fail(PCV_E_INVALID, "this S2 cell cloud has no intensity attribute");
+  if (count > capacity) return c->fail(PCV_E_INVALID, "the cells hold " + std::to_string(count) + " points, capacity is " + std::to_string(capacity));
+  if (intensity && !c->has_intensity) return c->fail(PCV_E_INVALID, "this S2 cell cloud has no intensity attribute");
+  if (int rc = ensure_resident(c)) return rc;
+  if (!ctx) {
+    if (xyz && count) std::memcpy(xyz, c->h_xyz.data() + begin * 24, count * 24);
+    if (rgb && count) std::memcpy(rgb, c->h_rgb.data() + begin * 3, count * 3);
+    if (intensity && count) std::memcpy(intensity, c->h_int.data() + begin * 4, count * 4);
+    return PCV_OK;
+  }
   PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const hipMemcpyKind kind = mem == PCV_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
   if (xyz) PCV_HIP_CHECK(ctx, hipMemcpyAsync(xyz, c->d_xyz + begin * 24, count * 24, kind, ctx->stream));
@@ -554,9 +636,16 @@ extern "C" int pcv_s2_cell_points(pcv_s2_cloud* c, uint64_t first_cell, uint64_t
 extern "C" int pcv_s2_write_dir(pcv_s2_cloud* c, const char* directory) {
   if (!c) return PCV_E_INVALID;
   pcv_ctx* ctx = c->ctx;
-  if (!directory) return ctx->fail(PCV_E_INVALID, "directory is null");
+  if (!directory) return c->fail(PCV_E_INVALID, "directory is null");
   uint8_t *h_xyz = nullptr, *h_rgb = nullptr, *h_int = nullptr;
-  int rc = PCV_OK;
+  int rc = ensure_resident(c);
+  if (rc != PCV_OK) return rc;
+  if (!ctx) {
+    std::string error;
+    rc = pcv_s2_write_files(directory, c->bbox_min, c->bbox_max, c->ids.size(), c->ids.data(), c->counts.data(), c->offsets.data(),
+                            c->h_xyz.data(), c->h_rgb.data(), c->has_intensity ? (c->n ? c->h_int.data() : (const uint8_t*)"") : nullptr, &error);
+    return rc == PCV_OK ? rc : c->fail(rc, error);
+  }
   if (c->n) {
     PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     if ((rc = ctx->host_alloc((void**)&h_xyz, c->n * 24)) == PCV_OK && (rc = ctx->host_alloc((void**)&h_rgb, c->n * 3)) == PCV_OK &&

@@ -342,7 +342,7 @@ class Context:
                 arr[i].params[j] = v
         h = C.c_void_p()
         self._check(self.lib.pcv_shapes_create(self.handle, arr, len(shapes), C.byref(h)))
-        return Shapes(self, h, len(shapes))
+        return Shapes(self, h, len(shapes), [int(arr[i].kind) for i in range(len(shapes))])
 
     def cull_points(self, shapes, shape_index, x, y, z, intensity=None, interval=None):
         """FilteredIterator keep mask for raw positions. Returns (keep uint8 array/tensor, kept count)."""
@@ -409,6 +409,13 @@ class Context:
         p, keep_alive = self._points(points["x"], points["y"], points["z"], points["color"], points.get("intensity"))
         h = C.c_void_p()
         self._check(self.lib.pcv_s2_split(self.handle, C.byref(p), int(split_level), C.byref(h)))
+        return S2Cloud(self, h)
+
+    def s2_open(self, directory):
+        """S2Cells::from_data_provider over a directory (pcv_s2_open_dir): the S2Cloud that s2_split makes, its cell files read
+        and uploaded on first use. PcvError carries the reference's messages for a meta.pb that is too old or not S2."""
+        h = C.c_void_p()
+        self._check(self.lib.pcv_s2_open_dir(self.handle, os.fsencode(str(directory)), C.byref(h)))
         return S2Cloud(self, h)
 
     # ---- stage-level entry points ----------------------------------------------------------------
@@ -807,8 +814,9 @@ class PendingBuild:
 class Shapes:
     """Prepared query shapes (device resident)."""
 
-    def __init__(self, ctx, handle, count):
+    def __init__(self, ctx, handle, count, kinds=None):
         self.ctx, self.handle, self.count = ctx, handle, count
+        self.kinds = kinds  # PCV_SHAPE_* per shape, as given
         ctx._children.add(self)
 
     def get(self, i):
@@ -1104,6 +1112,11 @@ class QueryBatch:
     """The result of OctreeResult.query_batch: segment k holds what query_points(shape, node=segment_node[k]) returns.
     Holds its octree: the tree's device blobs are read when points are copied out."""
 
+    _prefix = "pcv_query_batch"  # the entry points' family (S2QueryBatch: pcv_s2_query)
+
+    def _fn(self, name):
+        return getattr(self.lib, f"{self._prefix}_{name}")
+
     def __init__(self, tree, handle, num_shapes):
         self.tree, self.ctx, self.lib, self.handle = tree, tree.ctx, tree.lib, handle
         self.num_shapes = num_shapes
@@ -1127,7 +1140,7 @@ class QueryBatch:
             first = np.zeros(self.num_shapes + 1, dtype=np.uint64)
             node = np.zeros(max(1, self.num_segments), dtype=np.uint32)
             off = np.zeros(self.num_segments + 1, dtype=np.uint64)
-            self.ctx._check(self.lib.pcv_query_batch_segments(self.handle, first.ctypes.data, node.ctypes.data, off.ctypes.data))
+            self.ctx._check(self._fn("segments")(self.handle, first.ctypes.data, node.ctypes.data, off.ctypes.data))
             self._segments = (first, node[:self.num_segments], off)
         return self._segments
 
@@ -1141,7 +1154,7 @@ class QueryBatch:
         num = self.num_segments - first if num_segments is None else int(num_segments)
         if not (0 <= first <= self.num_segments and 0 <= num <= self.num_segments - first):
             # the library's own range check (PCV_E_INVALID, nothing written)
-            self.ctx._check(self.lib.pcv_query_batch_points(self.handle, max(first, 0), max(num, 0) or (1 << 63), 0, L.MEM_HOST,
+            self.ctx._check(self._fn("points")(self.handle, max(first, 0), max(num, 0) or (1 << 63), 0, L.MEM_HOST,
                                                             None, None, None, None, None))
         n = int(off[first + num] - off[first])
         if out is None:
@@ -1164,7 +1177,7 @@ class QueryBatch:
         if_int = inten if self._has_int else None
         if mem == L.MEM_DEVICE:
             self.ctx.wait_torch()
-        self.ctx._check(self.lib.pcv_query_batch_points(self.handle, first, num, cap, mem, ptr(x), ptr(y), ptr(z), ptr(rgb), ptr(if_int)))
+        self.ctx._check(self._fn("points")(self.handle, first, num, cap, mem, ptr(x), ptr(y), ptr(z), ptr(rgb), ptr(if_int)))
         return dict(count=n, x=x[:n], y=y[:n], z=z[:n], rgb=rgb[:n] if rgb.ndim == 2 else rgb[:3 * n],
                     intensity=if_int[:n] if if_int is not None else None)
 
@@ -1183,7 +1196,7 @@ class QueryBatch:
 
     def free(self):
         if self.handle and self.ctx.handle:
-            self.lib.pcv_query_batch_free(self.handle)
+            self._fn("free")(self.handle)
         self.handle = None
 
     def __del__(self):
@@ -1962,23 +1975,47 @@ def build_octree_from_file(output_directory, resolution, filename, attributes=("
 _default_ctx = None
 
 
+class S2QueryBatch(QueryBatch):
+    """The result of S2Cloud.query_batch, with QueryBatch's methods: segment k holds the points of cell segments()[1][k] (an
+    index into S2Cloud.cells) that location s selected, for the locations (shapes, then unions) one after another. Holds its
+    cloud: the cloud's device blobs are read when points are copied out."""
+    _prefix = "pcv_s2_query"
+
+    def __init__(self, cloud, handle, num_locations):
+        self.tree, self.ctx, self.lib, self.handle = cloud, cloud.ctx, cloud.lib, handle
+        self.num_shapes = num_locations
+        ns, npt = C.c_uint64(), C.c_uint64()
+        self.lib.pcv_s2_query_sizes(handle, C.byref(ns), C.byref(npt))
+        self.num_segments, self.num_points = ns.value, npt.value
+        self._has_int = cloud.has_intensity
+        self._segments = None
+        self.ctx._children.add(self)
+
+
 class S2Cloud:
     """An S2 cell cloud held by the library (pcv_s2_cloud): the cells ascending by id and cell-contiguous device blobs."""
 
     def __init__(self, ctx, handle):
-        self.ctx = ctx
-        self.lib = ctx.lib
+        self.ctx = ctx  # None: opened without a context (s2_open_host), host only
+        self.lib = ctx.lib if ctx is not None else L.load_library()
         self.handle = handle
-        ctx._children.add(self)
+        if ctx is not None:
+            ctx._children.add(self)
         nc, n, has_int, level = C.c_uint64(), C.c_uint64(), C.c_int(), C.c_uint32()
         bmin, bmax = (C.c_double * 3)(), (C.c_double * 3)()
-        ctx._check(self.lib.pcv_s2_info(handle, C.byref(nc), C.byref(n), bmin, bmax, C.byref(has_int), C.byref(level)))
+        self._check(self.lib.pcv_s2_info(handle, C.byref(nc), C.byref(n), bmin, bmax, C.byref(has_int), C.byref(level)))
         self.num_cells, self.num_points, self.has_intensity, self.split_level = nc.value, n.value, bool(has_int.value), level.value
         self.bbox_min, self.bbox_max = np.array(bmin[:]), np.array(bmax[:])
         self._cells = None
 
+    def _check(self, rc):
+        if self.ctx is not None:
+            self.ctx._check(rc)
+        else:
+            _host_check(rc, "S2Cloud")
+
     def _alive(self):
-        if not self.handle or not self.ctx.handle:
+        if not self.handle or (self.ctx is not None and not self.ctx.handle):
             raise ValueError("this S2 cell cloud has been freed")
 
     @property
@@ -1987,7 +2024,7 @@ class S2Cloud:
         if self._cells is None:
             self._alive()
             ids, counts, offsets = (np.zeros(self.num_cells, dtype=np.uint64) for _ in range(3))
-            self.ctx._check(self.lib.pcv_s2_cells(self.handle, ids.ctypes.data, counts.ctypes.data, offsets.ctypes.data))
+            self._check(self.lib.pcv_s2_cells(self.handle, ids.ctypes.data, counts.ctypes.data, offsets.ctypes.data))
             self._cells = (ids, counts, offsets)
         return self._cells
 
@@ -1996,7 +2033,7 @@ class S2Cloud:
         """The permutation: order[slot] = input index of the point at `slot` (a stable sort of the input by cell id)."""
         self._alive()
         out = np.zeros(self.num_points, dtype=np.uint32)
-        self.ctx._check(self.lib.pcv_s2_order(self.handle, out.ctypes.data, L.MEM_HOST))
+        self._check(self.lib.pcv_s2_order(self.handle, out.ctypes.data, L.MEM_HOST))
         return out
 
     def tokens(self):
@@ -2011,17 +2048,53 @@ class S2Cloud:
         m = int(self.cells[1][first:first + count].sum())
         xyz, rgb = np.zeros((m, 3)), np.zeros((m, 3), dtype=np.uint8)
         inten = np.zeros(m, dtype=np.float32) if self.has_intensity else None
-        self.ctx._check(self.lib.pcv_s2_cell_points(self.handle, first, count, m, L.MEM_HOST, xyz.ctypes.data, rgb.ctypes.data,
+        self._check(self.lib.pcv_s2_cell_points(self.handle, first, count, m, L.MEM_HOST, xyz.ctypes.data, rgb.ctypes.data,
                                                     inten.ctypes.data if inten is not None else None))
         return xyz, rgb, inten
+
+    def cells_in_location(self, shapes=None, unions=None):
+        """S2Cells::nodes_in_location for every location of one call (pcv_s2_cells_in_location): the prepared `shapes`
+        first, then `unions`, each a sequence of cell ids ascending. One uint64 array of cell ids per location, ascending;
+        `cells_in_location_indices` gives the same lists as indices into `cells`."""
+        return [self.cells[0][idx] for idx in self.cells_in_location_indices(shapes, unions)]
+
+    def cells_in_location_indices(self, shapes=None, unions=None):
+        self._alive()
+        first, flat = _s2_unions(unions)
+        locations = (shapes.count if shapes is not None else 0) + first.size - 1
+        capacity = max(1, self.num_cells)
+        counts, out = np.zeros(max(1, locations), dtype=np.uint32), np.zeros((max(1, locations), capacity), dtype=np.uint32)
+        self._check(self.lib.pcv_s2_cells_in_location(self.handle, shapes.handle if shapes is not None else None, first.size - 1,
+                                                          first.ctypes.data, flat.ctypes.data, capacity, counts.ctypes.data, out.ctypes.data))
+        return [out[l, :counts[l]].copy() for l in range(locations)]
+
+    def query_batch(self, shapes=None, unions=None, intervals=None):
+        """The points of every location of one call (pcv_s2_query_run): the prepared `shapes`, then `unions`; intervals: None,
+        or one entry per location, None or (lo, hi) on intensity. Returns an S2QueryBatch."""
+        self._alive()
+        first, flat = _s2_unions(unions)
+        locations = (shapes.count if shapes is not None else 0) + first.size - 1
+        iv = used = None
+        if intervals is not None:
+            intervals = list(intervals)
+            if len(intervals) != locations:
+                raise ValueError(f"intervals: expected {locations} entries (one per location), got {len(intervals)}")
+            iv, used = (C.c_double * max(1, 2 * locations))(), (C.c_uint8 * max(1, locations))()
+            for s, v in enumerate(intervals):
+                if v is not None:
+                    iv[2 * s], iv[2 * s + 1], used[s] = float(v[0]), float(v[1]), 1
+        h = C.c_void_p()
+        self._check(self.lib.pcv_s2_query_run(self.handle, shapes.handle if shapes is not None else None, first.size - 1, first.ctypes.data,
+                                              flat.ctypes.data, iv, used, C.byref(h)))
+        return S2QueryBatch(self, h, locations)
 
     def write(self, directory):
         """<token>.xyz/.rgb[/.intensity] per cell + meta.pb (pcv_s2_write_dir)."""
         self._alive()
-        self.ctx._check(self.lib.pcv_s2_write_dir(self.handle, os.fsencode(directory)))
+        self._check(self.lib.pcv_s2_write_dir(self.handle, os.fsencode(directory)))
 
     def free(self):
-        if self.handle and self.ctx.handle:
+        if self.handle and (self.ctx is None or self.ctx.handle):
             self.lib.pcv_s2_free(self.handle)
         self.handle = None
 
@@ -2064,6 +2137,94 @@ def s2_union_contains(cells, x, y, z):
     _host_check(L.load_library().pcv_s2_union_contains_host(cells.ctypes.data, cells.size, x.size, x.ctypes.data, y.ctypes.data,
                                                             z.ctypes.data, keep.ctypes.data), "pcv_s2_union_contains_host")
     return keep
+
+
+def _s2_unions(unions):
+    """(union_first uint32[U + 1], union_cells uint64) of a sequence of cell-id sequences."""
+    unions = [np.ascontiguousarray(u, dtype=np.uint64).ravel() for u in (unions if unions is not None else [])]
+    first = np.zeros(len(unions) + 1, dtype=np.uint32)
+    first[1:] = np.cumsum([u.size for u in unions], dtype=np.uint64)
+    flat = np.ascontiguousarray(np.concatenate(unions) if unions else np.zeros(0), dtype=np.uint64)
+    return first, flat
+
+
+def s2_cell_geometry(cell_id):
+    """pcv_s2_cell_geometry_host: dict(rect (4), center (lat, lng), uv (4), vertices (4, 3), vertex_lat_lng (4, 2)) of a cell of
+    level 1 ..= 30, as Rect::intersects_cell reads it."""
+    g = np.zeros(30)
+    _host_check(L.load_library().pcv_s2_cell_geometry_host(int(cell_id), g.ctypes.data), "pcv_s2_cell_geometry_host")
+    return dict(rect=g[0:4], center=g[4:6], uv=g[6:10], vertices=g[10:22].reshape(4, 3), vertex_lat_lng=g[22:30].reshape(4, 2))
+
+
+def s2_cell_rect(cell_id):
+    """pcv_s2_cell_rect_host: Cell::rect_bound as (lat.lo, lat.hi, lng.lo, lng.hi)."""
+    r = np.zeros(4)
+    _host_check(L.load_library().pcv_s2_cell_rect_host(int(cell_id), r.ctypes.data), "pcv_s2_cell_rect_host")
+    return r
+
+
+def s2_corners_rect(corners):
+    """pcv_s2_corners_rect_host: the rect of cells_in_convex_polyhedron for the (8, 3) corners of a shape."""
+    c = np.ascontiguousarray(corners, dtype=np.float64).ravel()
+    if c.size != 24:
+        raise ValueError("corners must be (8, 3)")
+    r = np.zeros(4)
+    _host_check(L.load_library().pcv_s2_corners_rect_host(c.ctypes.data, r.ctypes.data), "pcv_s2_corners_rect_host")
+    return r
+
+
+def s2_rect_intersects_cell(rect, cell_id):
+    """pcv_s2_rect_intersects_cell_host: Rect::intersects_cell."""
+    r = np.ascontiguousarray(rect, dtype=np.float64).ravel()
+    if r.size != 4:
+        raise ValueError("a rect is (lat.lo, lat.hi, lng.lo, lng.hi)")
+    out = C.c_int()
+    _host_check(L.load_library().pcv_s2_rect_intersects_cell_host(r.ctypes.data, int(cell_id), C.byref(out)), "pcv_s2_rect_intersects_cell_host")
+    return bool(out.value)
+
+
+def s2_union_normalize(cells):
+    """pcv_s2_union_normalize_host: CellUnion::normalize of cell ids in any order, as a new uint64 array."""
+    c = np.array(cells, dtype=np.uint64).ravel()
+    n = C.c_uint32(c.size)
+    _host_check(L.load_library().pcv_s2_union_normalize_host(c.ctypes.data, C.byref(n)), "pcv_s2_union_normalize_host")
+    return c[:n.value].copy()
+
+
+def s2_union_intersects(cells, ids):
+    """pcv_s2_union_intersects_host: CellUnion::intersects_cellid per id for cell ids ascending, as uint8 flags."""
+    cells = np.ascontiguousarray(cells, dtype=np.uint64).ravel()
+    ids = np.ascontiguousarray(ids, dtype=np.uint64).ravel()
+    out = np.zeros(ids.size, dtype=np.uint8)
+    _host_check(L.load_library().pcv_s2_union_intersects_host(cells.ctypes.data, cells.size, ids.size, ids.ctypes.data, out.ctypes.data),
+                "pcv_s2_union_intersects_host")
+    return out
+
+
+def s2_cells_in_location(cell_ids, kinds=None, valid=None, corners=None, unions=None):
+    """pcv_s2_cells_in_location_host: the lists of S2Cloud.cells_in_location_indices over plain arrays — the cloud's cell ids
+    (ascending); per shape its PCV_SHAPE_* kind, valid flag and (8, 3) corners (Shapes.kinds, Shapes.get); then the unions."""
+    ids = np.ascontiguousarray(cell_ids, dtype=np.uint64).ravel()
+    kinds = np.ascontiguousarray(kinds if kinds is not None else [], dtype=np.int32).ravel()
+    valid = np.ascontiguousarray(valid if valid is not None else np.ones(kinds.size), dtype=np.int32).ravel()
+    corners = np.ascontiguousarray(corners if corners is not None else np.zeros((0, 8, 3)), dtype=np.float64).reshape(-1, 24)
+    if not (kinds.size == valid.size == corners.shape[0]):
+        raise ValueError("kinds, valid and corners differ in length")
+    first, flat = _s2_unions(unions)
+    locations = kinds.size + first.size - 1
+    capacity = max(1, ids.size)
+    counts, out = np.zeros(max(1, locations), dtype=np.uint32), np.zeros((max(1, locations), capacity), dtype=np.uint32)
+    _host_check(L.load_library().pcv_s2_cells_in_location_host(ids.size, ids.ctypes.data, kinds.size, kinds.ctypes.data, valid.ctypes.data,
+                                                               corners.ctypes.data, first.size - 1, first.ctypes.data, flat.ctypes.data,
+                                                               capacity, counts.ctypes.data, out.ctypes.data), "pcv_s2_cells_in_location_host")
+    return [out[l, :counts[l]].copy() for l in range(locations)]
+
+
+def s2_open_host(directory):
+    """pcv_s2_open_dir without a context (no device): an S2Cloud that serves cells, cell_points and write only."""
+    h = C.c_void_p()
+    _host_check(L.load_library().pcv_s2_open_dir(None, os.fsencode(str(directory)), C.byref(h)), "pcv_s2_open_dir")
+    return S2Cloud(None, h)
 
 
 def build_s2_cells(output_directory, points, split_level=20, ctx=None):

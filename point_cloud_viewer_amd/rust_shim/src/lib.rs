@@ -158,6 +158,16 @@ extern "C" {
     fn pcv_query_batch_points(b: *mut pcv_query_batch, first_segment: u64, num_segments: u64, capacity: u64, mem: c_int, x: *mut c_double, y: *mut c_double, z: *mut c_double, rgb: *mut u8, intensity: *mut c_float) -> c_int;
     fn pcv_query_batch_free(b: *mut pcv_query_batch);
     // the viewer's frame: get_visible_nodes + GL_POINTS under a depth test, rasterised on the device
+    fn pcv_s2_open_dir(ctx: *mut pcv_ctx, directory: *const c_char, out: *mut *mut pcv_s2_cloud) -> c_int;
+    fn pcv_s2_info(c: *const pcv_s2_cloud, num_cells: *mut u64, num_points: *mut u64, bbox_min: *mut c_double, bbox_max: *mut c_double, has_intensity: *mut c_int, level: *mut u32) -> c_int;
+    fn pcv_s2_cells(c: *const pcv_s2_cloud, ids: *mut u64, counts: *mut u64, offsets: *mut u64) -> c_int;
+    fn pcv_s2_cells_in_location(c: *mut pcv_s2_cloud, shapes: *const pcv_shapes, num_unions: u32, union_first: *const u32, union_cells: *const u64, capacity: u32, counts: *mut u32, cells: *mut u32) -> c_int;
+    fn pcv_s2_query_run(c: *mut pcv_s2_cloud, shapes: *const pcv_shapes, num_unions: u32, union_first: *const u32, union_cells: *const u64, intervals: *const c_double, interval_used: *const u8, out: *mut *mut pcv_s2_query) -> c_int;
+    fn pcv_s2_query_segments(q: *const pcv_s2_query, location_first_segment: *mut u64, segment_cell: *mut u32, segment_offset: *mut u64) -> c_int;
+    fn pcv_s2_query_sizes(q: *const pcv_s2_query, num_segments: *mut u64, num_points: *mut u64) -> c_int;
+    fn pcv_s2_query_points(q: *mut pcv_s2_query, first_segment: u64, num_segments: u64, capacity: u64, mem: c_int, x: *mut c_double, y: *mut c_double, z: *mut c_double, rgb: *mut u8, intensity: *mut c_float) -> c_int;
+    fn pcv_s2_query_free(q: *mut pcv_s2_query);
+    fn pcv_s2_free(c: *mut pcv_s2_cloud);
     fn pcv_render_views(ctx: *mut pcv_ctx, frusta: *const pcv_shapes, t: *mut pcv_octree, params: *const PcvRenderParams, out: *mut *mut pcv_render) -> c_int;
     fn pcv_render_views_ex(ctx: *mut pcv_ctx, frusta: *const pcv_shapes, t: *mut pcv_octree, params: *const PcvRenderParams, overlay: *const PcvRenderOverlay, out: *mut *mut pcv_render) -> c_int;
     fn pcv_render_images(r: *mut pcv_render, first: u32, count: u32, rgba: *mut c_void, mem: c_int) -> c_int;
@@ -440,7 +450,7 @@ impl HipOctree {
                 let se = r.south_east().to_zoomed_coordinate(0)? / 256.0;
                 s.params[..4].copy_from_slice(&[nw.x, nw.y, se.x, se.y]);
             }
-            PointLocation::S2Cells(_) => return None, // pcv_s2_union_contains tests points, but there is no node culling for a cell union
+            PointLocation::S2Cells(_) => return None, // no octree node culling for a cell union (HipS2Cells below serves S2 clouds)
         }
         Some(s)
     }
@@ -804,5 +814,166 @@ pub fn merge_xray_quadtrees_png(device: i32, input_directories: &[std::path::Pat
         Ok(())
     } else {
         Err(std::io::Error::new(if rc == -3 { std::io::ErrorKind::Other } else { std::io::ErrorKind::InvalidData }, message))
+    }
+}
+
+
+// ------------------------------------------------------------------------------------------------------------------
+// PointCloud over an S2 cell cloud directory (src/s2_cells/mod.rs): S2Cells::from_data_provider, nodes_in_location and
+// stream_points_for_query_in_node on the GPU library (include/pcv_hip.h, "S2 cell clouds: the region side"). Like the rest
+// of this file it is written against the reference's types and has not been compiled here.
+// ------------------------------------------------------------------------------------------------------------------
+#[repr(C)]
+pub struct pcv_s2_cloud {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct pcv_s2_query {
+    _private: [u8; 0],
+}
+
+/// An S2 cell cloud on disk served by the GPU library. The reference `S2Cells` is kept alongside for `points_in_node` (a plain
+/// `NodeIterator` over one cell's files) and for intervals on attributes other than intensity.
+pub struct HipS2Cells {
+    ctx: HipContext,
+    cloud: *mut pcv_s2_cloud,
+    lock: Mutex<()>, // a pcv_ctx is not thread-safe; ParallelIterator calls from several workers
+    ids: Vec<s2::cellid::CellID>,
+    index_of: HashMap<s2::cellid::CellID, u32>,
+    inner: point_viewer::s2_cells::S2Cells,
+}
+
+unsafe impl Send for HipS2Cells {}
+unsafe impl Sync for HipS2Cells {}
+
+impl HipS2Cells {
+    pub fn from_directory(directory: impl AsRef<Path>) -> Result<Self> {
+        let ctx = HipContext::new(0).map_err(|e| ErrorKind::InvalidInput(e))?;
+        let dir = CString::new(directory.as_ref().to_str().unwrap()).unwrap();
+        let mut cloud = std::ptr::null_mut();
+        if unsafe { pcv_s2_open_dir(ctx.0, dir.as_ptr(), &mut cloud) } != 0 {
+            // the reference's own messages ("No S2 point cloud supported with version N", "This meta does not describe ...")
+            let msg = unsafe { CStr::from_ptr(pcv_last_error(ctx.0)) }.to_string_lossy().into_owned();
+            return Err(ErrorKind::InvalidInput(msg).into());
+        }
+        let mut n = 0u64;
+        unsafe { pcv_s2_info(cloud, &mut n, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut()) };
+        let mut raw = vec![0u64; n as usize];
+        unsafe { pcv_s2_cells(cloud, raw.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut()) };
+        let ids: Vec<_> = raw.iter().map(|&id| s2::cellid::CellID(id)).collect();
+        let index_of = ids.iter().enumerate().map(|(k, id)| (*id, k as u32)).collect();
+        let inner = point_viewer::s2_cells::S2Cells::from_data_provider(Box::new(OnDiskDataProvider { directory: directory.as_ref().to_path_buf() }))?;
+        Ok(HipS2Cells { ctx, cloud, lock: Mutex::new(()), ids, index_of, inner })
+    }
+
+    /// The cells of one location: a prepared shape, or the ascending cell ids of a union (`CellUnion.0`, sorted).
+    fn cells_of(&self, shape: Option<&PcvShape>, union: &[u64]) -> Vec<u32> {
+        let cap = self.ids.len().max(1);
+        let (mut count, mut idx) = (0u32, vec![0u32; cap]);
+        let first = [0u32, union.len() as u32];
+        let mut shapes = std::ptr::null_mut();
+        if let Some(s) = shape {
+            self.ctx.check(unsafe { pcv_shapes_create(self.ctx.0, s, 1, &mut shapes) });
+        }
+        let unions = if shape.is_some() { 0 } else { 1 };
+        self.ctx.check(unsafe { pcv_s2_cells_in_location(self.cloud, shapes, unions, first.as_ptr(), union.as_ptr(), cap as u32, &mut count, idx.as_mut_ptr()) });
+        if !shapes.is_null() {
+            unsafe { pcv_shapes_free(shapes) };
+        }
+        idx.truncate(count as usize);
+        idx
+    }
+
+    fn sorted_union(location: &PointLocation) -> Option<Vec<u64>> {
+        match location {
+            PointLocation::S2Cells(u) => {
+                let mut v: Vec<u64> = u.0.iter().map(|c| c.0).collect();
+                v.sort_unstable();
+                Some(v)
+            }
+            _ => None,
+        }
+    }
+}
+
+impl Drop for HipS2Cells {
+    fn drop(&mut self) {
+        unsafe { pcv_s2_free(self.cloud) } // before the context
+    }
+}
+
+impl PointCloud for HipS2Cells {
+    type Id = s2::cellid::CellID;
+
+    /// src/s2_cells/mod.rs:160-169; the list ascends by cell id (the reference: its hash map's order).
+    fn nodes_in_location(&self, location: &PointLocation) -> Vec<Self::Id> {
+        let _g = self.lock.lock().unwrap();
+        let idx = match Self::sorted_union(location) {
+            Some(u) => self.cells_of(None, &u),
+            None => self.cells_of(Some(&HipOctree::shape_of(location).expect("every other location has a shape")), &[]),
+        };
+        idx.iter().map(|&i| self.ids[i as usize]).collect()
+    }
+
+    fn encoding_for_node(&self, _: Self::Id) -> Encoding {
+        Encoding::Plain
+    }
+
+    fn points_in_node(&self, attributes: &[&str], node_id: Self::Id, batch_size: usize) -> Result<NodeIterator> {
+        self.inner.points_in_node(attributes, node_id, batch_size)
+    }
+
+    fn bounding_box(&self) -> &Aabb {
+        self.inner.bounding_box()
+    }
+
+    /// src/iterator.rs:185-205 for ONE cell: one pcv_s2_query_run over the query's location, the cell's segment copied out.
+    /// (A caller that streams many cells of one query should keep the batch, as HipOctree's BatchCache does.)
+    fn stream_points_for_query_in_node<F>(&self, query: &PointQuery, node_id: Self::Id, batch_size: usize, callback: F) -> Result<()>
+    where
+        F: FnMut(PointsBatch) -> Result<()>,
+    {
+        if !query.filter_intervals.keys().all(|k| *k == "intensity") {
+            // an interval on another attribute: the reference's host path
+            let it = self.inner.points_in_node(&query.attributes, node_id, batch_size)?;
+            return point_viewer::iterator::stream_dispatch(&query.location, &query.filter_intervals, it, callback);
+        }
+        let interval = query.filter_intervals.get("intensity").map(|iv| [iv.lower_bound, iv.upper_bound]);
+        let _g = self.lock.lock().unwrap();
+        let union = Self::sorted_union(&query.location);
+        let shape = if union.is_none() { HipOctree::shape_of(&query.location) } else { None };
+        let mut shapes = std::ptr::null_mut();
+        if let Some(s) = &shape {
+            self.ctx.check(unsafe { pcv_shapes_create(self.ctx.0, s, 1, &mut shapes) });
+        }
+        let cells = union.unwrap_or_default();
+        let first = [0u32, cells.len() as u32];
+        let iv = interval.unwrap_or([0.0, 0.0]);
+        let used = [interval.is_some() as u8];
+        let mut batch = std::ptr::null_mut();
+        self.ctx.check(unsafe {
+            pcv_s2_query_run(self.cloud, shapes, if shape.is_some() { 0 } else { 1 }, first.as_ptr(), cells.as_ptr(), iv.as_ptr(), used.as_ptr(), &mut batch)
+        });
+        let (mut nseg, mut kept) = (0u64, 0u64);
+        unsafe { pcv_s2_query_sizes(batch, &mut nseg, &mut kept) };
+        let (mut loc_first, mut seg_cell, mut offset) = ([0u64; 2], vec![0u32; nseg as usize], vec![0u64; nseg as usize + 1]);
+        unsafe { pcv_s2_query_segments(batch, loc_first.as_mut_ptr(), seg_cell.as_mut_ptr(), offset.as_mut_ptr()) };
+        let want = self.index_of[&node_id];
+        let want_intensity = query.attributes.contains(&"intensity");
+        let mut points = HostPoints { n: 0, x: vec![], y: vec![], z: vec![], rgb: vec![], intensity: vec![] };
+        if let Some(seg) = seg_cell.iter().position(|&c| c == want) {
+            let n = (offset[seg + 1] - offset[seg]) as usize;
+            points = HostPoints { n, x: vec![0.0; n], y: vec![0.0; n], z: vec![0.0; n], rgb: vec![0; 3 * n], intensity: vec![0.0; if want_intensity { n } else { 0 }] };
+            let ip = if want_intensity { points.intensity.as_mut_ptr() } else { std::ptr::null_mut() };
+            self.ctx.check(unsafe {
+                pcv_s2_query_points(batch, seg as u64, 1, n as u64, 0, points.x.as_mut_ptr(), points.y.as_mut_ptr(), points.z.as_mut_ptr(), points.rgb.as_mut_ptr(), ip)
+            });
+        }
+        unsafe { pcv_s2_query_free(batch) };
+        if !shapes.is_null() {
+            unsafe { pcv_shapes_free(shapes) };
+        }
+        drop(_g);
+        emit_points(query, &points, batch_size, callback)
     }
 }
