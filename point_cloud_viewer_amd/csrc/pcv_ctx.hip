@@ -1,0 +1,423 @@
+// pcv_ctx.hip — the context behind every entry point of the C ABI (include/pcv_hip.h): the caching device pool, the pinned
+// blocks, the host-thread pool and the host-to-device staging ring, the per-launch profile and its name table, and
+// pcv_ctx_create / destroy / synchronize / wait_stream / signal_stream / trim. Host code only.
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+
+#include "pcv_internal.h"
+
+// ------------------------------------------------------------------------------------------------
+// context, pool
+// ------------------------------------------------------------------------------------------------
+void* PcvPool::alloc(size_t bytes, hipError_t* err) {
+  *err = hipSuccess;
+  if (bytes == 0) bytes = 256;
+  bytes = (bytes + 255) & ~(size_t)255;
+  // Reuse a cached block only if it is about the requested size: a loose match lets a small request grab a big block
+  // and the big request that follows pays a multi-millisecond hipMalloc in the middle of a build.
+  auto it = free_blocks.lower_bound(bytes);
+  if (it != free_blocks.end() && it->first <= bytes + bytes / 8 + (64u << 10)) {
+    void* p = it->second;
+    live[p] = it->first;
+    free_blocks.erase(it);
+    return p;
+  }
+  void* p = nullptr;
+  *err = hipMalloc(&p, bytes);
+  if (*err != hipSuccess) {
+    // drop the cache and retry once
+    trim();
+    *err = hipMalloc(&p, bytes);
+    if (*err != hipSuccess) return nullptr;
+  }
+  live[p] = bytes;
+  return p;
+}
+void PcvPool::release(void* p) {
+  if (!p) return;
+  auto it = live.find(p);
+  if (it == live.end()) return;
+  free_blocks.insert({it->second, p});
+  live.erase(it);
+}
+void PcvPool::trim() {
+  for (auto& kv : free_blocks) (void)hipFree(kv.second);
+  free_blocks.clear();
+}
+
+int pcv_ctx::dev_alloc(void** p, size_t bytes) {
+  hipError_t e;
+  *p = pool.alloc(bytes, &e);
+  if (!*p) return fail(e == hipErrorOutOfMemory ? PCV_E_OOM : PCV_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+  return PCV_OK;
+}
+void pcv_ctx::dev_free(void* p) { pool.release(p); }
+int pcv_ctx::host_alloc(void** p, size_t bytes) {
+  if (bytes == 0) bytes = 256;
+  auto it = host_free.lower_bound(bytes);
+  if (it != host_free.end() && it->first <= bytes * 2 + (1u << 20)) {
+    *p = it->second;
+    host_live[*p] = it->first;
+    host_free.erase(it);
+    return PCV_OK;
+  }
+  hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault);
+  if (e != hipSuccess) return fail(PCV_E_OOM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
+  host_live[*p] = bytes;
+  return PCV_OK;
+}
+void pcv_ctx::host_release(void* p) {
+  if (!p) return;
+  auto it = host_live.find(p);
+  if (it == host_live.end()) return;
+  host_free.insert({it->second, p});
+  host_live.erase(it);
+}
+int pcv_ctx::pinned_reserve(size_t bytes) {
+  if (bytes <= pinned_bytes) return PCV_OK;
+  if (pinned) (void)hipHostFree(pinned);
+  pinned = nullptr;
+  pinned_bytes = 0;
+  hipError_t e = hipHostMalloc(&pinned, bytes, hipHostMallocDefault);
+  if (e != hipSuccess) return fail(PCV_E_OOM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
+  pinned_bytes = bytes;
+  return PCV_OK;
+}
+
+int pcv_ctx::table_dev_reserve(size_t bytes) {
+  if (bytes <= table_dev_bytes) return PCV_OK;
+  // the old block may still be read by work in flight: drain both streams before it goes away
+  if (table_dev) {
+    (void)hipStreamSynchronize(stream);
+    (void)hipStreamSynchronize(side);
+    (void)hipFree(table_dev);
+    table_dev = nullptr;
+    table_dev_bytes = 0;
+  }
+  const size_t want = (bytes + (bytes >> 1) + 4095) & ~(size_t)4095;
+  if (hipMalloc(&table_dev, want) != hipSuccess) return fail(PCV_E_OOM, "out of device memory (node tables)");
+  table_dev_bytes = want;
+  return PCV_OK;
+}
+
+int pcv_ctx::pinned_spec_reserve(size_t bytes) {
+  if (bytes <= pinned_spec_bytes) return PCV_OK;
+  bytes += bytes / 2;  // the size follows the node count of the input: leave room so that similar builds do not regrow it
+  if (pinned_spec) (void)hipHostFree(pinned_spec);  // waits for copies in flight
+  pinned_spec = nullptr;
+  pinned_spec_bytes = 0;
+  hipError_t e = hipHostMalloc(&pinned_spec, bytes, hipHostMallocDefault);
+  if (e != hipSuccess) return fail(PCV_E_OOM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
+  pinned_spec_bytes = bytes;
+  return PCV_OK;
+}
+
+void PcvHostPool::start(unsigned n) {
+  if (!threads.empty()) return;
+  for (unsigned k = 0; k < n; ++k)
+    threads.emplace_back([this] {
+      uint64_t seen = 0;
+      for (;;) {
+        std::unique_lock<std::mutex> lk(mu);
+        wake.wait(lk, [&] { return stop || (generation != seen && next < count); });
+        if (stop) return;
+        while (next < count) {
+          const size_t i = next++;
+          lk.unlock();
+          job(i);
+          lk.lock();
+          if (++finished == count) done.notify_all();
+        }
+        seen = generation;
+      }
+    });
+}
+void PcvHostPool::run(size_t n, const std::function<void(size_t)>& fn) {
+  if (n == 0) return;
+  if (threads.empty() || n == 1) {
+    for (size_t i = 0; i < n; ++i) fn(i);
+    return;
+  }
+  std::unique_lock<std::mutex> lk(mu);
+  job = fn;
+  next = 0;
+  count = n;
+  finished = 0;
+  ++generation;
+  wake.notify_all();
+  while (next < count) {  // the caller works too
+    const size_t i = next++;
+    lk.unlock();
+    fn(i);
+    lk.lock();
+    ++finished;
+  }
+  done.wait(lk, [&] { return finished == count; });
+  count = 0;
+}
+PcvHostPool::~PcvHostPool() {
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    stop = true;
+  }
+  wake.notify_all();
+  for (auto& th : threads) th.join();
+}
+
+// Pageable caller memory -> device: the runtime's own staging of a pageable hipMemcpy runs on one thread (~45 GB/s
+// here); several host threads filling a ring of pinned chunks keep the link busy instead (every chunk is one DMA).
+int pcv_ctx::h2d(void* dst, const void* src, size_t bytes) {
+  if (bytes == 0) return PCV_OK;
+  if (bytes < (4u << 20)) {  // small arrays: not worth the ring
+    PCV_HIP_CHECK(this, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream));
+    return PCV_OK;
+  }
+  const uint8_t* from = (const uint8_t*)src;
+  return h2d_fill(dst, bytes, [from](uint8_t* to, size_t off, size_t len) {
+    std::memcpy(to, from + off, len);
+    return true;
+  });
+}
+
+// The ring of pinned chunks and the host threads that fill them, created on first use (h2d_fill, pcv_ingest_begin).
+int pcv_ctx::ring_ensure() {
+  if (ring[0]) return PCV_OK;
+  for (int k = 0; k < kRingSlots; ++k) {
+    if (hipHostMalloc(&ring[k], kRingChunk, hipHostMallocDefault) != hipSuccess) return fail(PCV_E_OOM, "hipHostMalloc (staging ring)");
+    if (hipEventCreateWithFlags(&ring_ev[k], hipEventDisableTiming) != hipSuccess) return fail(PCV_E_HIP, "hipEventCreate");
+  }
+  unsigned hw = std::thread::hardware_concurrency();
+  // copies into pinned memory saturate the link with 7 threads; preads from a file (pcv_build_octree_from_ply) want more
+  unsigned workers = hw >= 64 ? 15 : (hw >= 16 ? 7 : (hw > 2 ? hw / 2 - 1 : 0));
+  host_pool.start(workers);
+  return PCV_OK;
+}
+
+// Host -> device through the ring of pinned chunks: `fill(to, off, len)` produces bytes [off, off + len) of the source
+// into pinned memory (a memcpy from pageable memory, a pread from a file) and is called from the context's host threads,
+// 2 MiB per call, several calls in parallel; one DMA per 32 MiB chunk follows. false from `fill` -> PCV_E_IO.
+int pcv_ctx::h2d_fill(void* dst, size_t bytes, const std::function<bool(uint8_t*, size_t, size_t)>& fill) {
+  if (bytes == 0) return PCV_OK;
+  if (int rc = ring_ensure()) return rc;
+  // one part per worker (the caller works too) and chunk, not less than 256 KiB
+  const size_t nworkers = host_pool.threads.size() + 1;
+  const size_t kPart = std::max<size_t>(256u << 10, ((kRingChunk + nworkers - 1) / nworkers + 4095) & ~(size_t)4095);
+  std::atomic<int> bad{0};
+  for (size_t off = 0; off < bytes; off += kRingChunk) {
+    const size_t len = bytes - off < kRingChunk ? bytes - off : kRingChunk;
+    const int slot = ring_take();
+    if (ring_busy[slot]) PCV_HIP_CHECK(this, hipEventSynchronize(ring_ev[slot]));  // its previous DMA has left the chunk
+    uint8_t* chunk = (uint8_t*)ring[slot];
+    host_pool.run((len + kPart - 1) / kPart, [&](size_t p) {
+      const size_t b = p * kPart, e = b + kPart < len ? b + kPart : len;
+      if (!fill(chunk + b, off + b, e - b)) bad.store(1);
+    });
+    if (bad.load()) return fail(PCV_E_IO, "reading the source of a host-to-device copy failed");
+    PCV_HIP_CHECK(this, hipMemcpyAsync((uint8_t*)dst + off, chunk, len, hipMemcpyHostToDevice, stream));
+    PCV_HIP_CHECK(this, hipEventRecord(ring_ev[slot], stream));
+    ring_busy[slot] = true;
+  }
+  return PCV_OK;
+}
+
+hipEvent_t pcv_ctx::prof_event() {
+  if (!prof_free.empty()) {
+    hipEvent_t e = prof_free.back();
+    prof_free.pop_back();
+    return e;
+  }
+  hipEvent_t e = nullptr;
+  (void)hipEventCreate(&e);
+  return e;
+}
+// Call only after the stream has been synchronised.
+void pcv_ctx::prof_resolve() {
+  for (auto& p : prof_pending) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
+      prof_ms[p.id] += ms;
+      prof_launches[p.id] += 1;
+    }
+    prof_free.push_back(p.a);
+    prof_free.push_back(p.b);
+  }
+  prof_pending.clear();
+}
+
+static const char* kKernelNames[PCV_K_COUNT] = {
+    "aabb_partial_kernel", "chain_keys_kernel",  "upsweep_kernel<u64>",   "scan_kernel",
+    "downsweep_kernel<u64>", "split_search_kernel", "split_assign_kernel", "leaf_encode_kernel",
+    "upsweep_kernel<u32>", "downsweep_kernel<u32>", "promote_settle_kernel", "downsweep_rec_kernel", "cull_nodes_kernel",
+    "visible_nodes_kernel", "nodes_in_location_kernel", "cull_points_kernel", "transform_points_kernel",
+    "query_compact_kernel", "route_bucket_kernel", "partition_count_kernel", "partition_scatter_kernel",
+    "promote_climb_kernel", "spec_encode_kernel", "rank_hist_kernel", "spec_continue_kernel", "spec_replay_kernel", "upsweep_map_kernel",
+    "hist_from_rows_kernel", "cull_nodes_sparse_kernel", "downsweep_settle_kernel", "ingest_batch_kernel",
+    "batch_nodes_kernel", "batch_chunks_kernel", "batch_flags_kernel", "batch_scan_kernel", "batch_compact_kernel",
+    "xray_bin_kernel", "xray_scatter_kernel", "xray_accum_kernel", "xray_parent_kernel",
+    "xray_sorted_kernel", "render_chunks_kernel", "render_splat_kernel", "render_resolve_kernel",
+    "xray_merge_stage_copy", "xray_merge_parent_kernel", "xray_png_band_kernel", "xray_png_layout_kernel",
+    "xray_png_gather_kernel", "render_outline_kernel", "xray_inpaint_stitch_kernel", "xray_inpaint_row_kernel",
+    "xray_inpaint_col_kernel", "xray_inpaint_list_kernel", "xray_inpaint_fill_kernel", "xray_inpaint_blend_kernel",
+    "s2_ids_kernel", "s2_unique_kernel", "s2_rank_kernel", "s2_gather_kernel", "s2_union_kernel",
+    "s2_cell_table_kernel", "s2_location_kernel", "s2_pair_kernel", "s2_flags_kernel", "s2_gather_points_kernel"};
+static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == PCV_K_COUNT, "kernel name table out of sync");
+
+extern "C" int pcv_ctx_set_profiling(pcv_ctx* ctx, int enabled) {
+  if (!ctx) return PCV_E_INVALID;
+  ctx->profiling = enabled == 2 ? 2 : (enabled != 0 ? 1 : 0);
+  return PCV_OK;
+}
+extern "C" int pcv_ctx_reset_kernel_stats(pcv_ctx* ctx) {
+  if (!ctx) return PCV_E_INVALID;
+  for (int i = 0; i < PCV_K_COUNT; ++i) {
+    ctx->prof_launches[i] = 0;
+    ctx->prof_ms[i] = 0;
+  }
+  return PCV_OK;
+}
+extern "C" int pcv_ctx_kernel_stats(pcv_ctx* ctx, int kernel_id, const char** name, uint64_t* launches,
+                                    double* total_ms) {
+  if (!ctx) return PCV_E_INVALID;
+  if (kernel_id < 0 || kernel_id >= PCV_K_COUNT) return PCV_K_COUNT;
+  if (!ctx->prof_pending.empty()) {  // launches of the stage-level entry points are resolved on first read
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    ctx->prof_resolve();
+  }
+  if (name) *name = kKernelNames[kernel_id];
+  if (launches) *launches = ctx->prof_launches[kernel_id];
+  if (total_ms) *total_ms = ctx->prof_ms[kernel_id];
+  return PCV_K_COUNT;
+}
+
+extern "C" int pcv_abi_version(void) { return PCV_ABI_VERSION; }
+
+extern "C" int pcv_ctx_create(int device, void* stream, pcv_ctx** out) {
+  if (!out) return PCV_E_INVALID;
+  *out = nullptr;
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count) return PCV_E_HIP;
+  if (hipSetDevice(device) != hipSuccess) return PCV_E_HIP;
+  pcv_ctx* c = new pcv_ctx();
+  c->device = device;
+  if (hipHostMalloc((void**)&c->mailbox, kPcvMailboxSlots * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess) {
+    delete c;
+    return PCV_E_OOM;
+  }
+  if (hipHostGetDevicePointer((void**)&c->mailbox_dev, c->mailbox, 0) != hipSuccess) c->mailbox_dev = c->mailbox;
+  if (stream) {
+    c->stream = (hipStream_t)stream;
+  } else {
+    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
+      delete c;
+      return PCV_E_HIP;
+    }
+    c->own_stream = true;
+  }
+  for (auto& e : c->ev)
+    if (hipEventCreate(&e) != hipSuccess) {
+      delete c;
+      return PCV_E_HIP;
+    }
+  for (int k = 0; k < PCV_NUM_STAGES; ++k)
+    if (hipEventCreate(&c->stage_b[k]) != hipSuccess || hipEventCreate(&c->stage_e[k]) != hipSuccess) {
+      delete c;
+      return PCV_E_HIP;
+    }
+  if (hipEventCreateWithFlags(&c->spec_ev, hipEventDisableTiming) != hipSuccess) {
+    delete c;
+    return PCV_E_HIP;
+  }
+  if (hipEventCreateWithFlags(&c->xev, hipEventDisableTiming) != hipSuccess) {
+    delete c;
+    return PCV_E_HIP;
+  }
+  if (hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreateWithFlags(&c->side_fork, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&c->side_join, hipEventDisableTiming) != hipSuccess) {
+    delete c;
+    return PCV_E_HIP;
+  }
+  *out = c;
+  return PCV_OK;
+}
+
+extern "C" void pcv_ctx_destroy(pcv_ctx* ctx) {
+  if (!ctx) return;
+  (void)hipSetDevice(ctx->device);
+  (void)hipStreamSynchronize(ctx->stream);
+  ctx->pool.trim();
+  {
+    for (auto& kv : ctx->pool.live) (void)hipFree(kv.first);
+  }
+  if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+  if (ctx->pinned_spec) (void)hipHostFree(ctx->pinned_spec);
+  for (int k = 0; k < pcv_ctx::kRingSlots; ++k) {
+    if (ctx->ring[k]) (void)hipHostFree(ctx->ring[k]);
+    if (ctx->ring_ev[k]) (void)hipEventDestroy(ctx->ring_ev[k]);
+  }
+  if (ctx->mailbox) (void)hipHostFree(ctx->mailbox);
+  for (auto& kv : ctx->host_free) (void)hipHostFree(kv.second);
+  for (auto& kv : ctx->host_live) (void)hipHostFree(kv.first);
+  for (auto& e : ctx->ev)
+    if (e) (void)hipEventDestroy(e);
+  if (ctx->xev) (void)hipEventDestroy(ctx->xev);
+  if (ctx->spec_ev) (void)hipEventDestroy(ctx->spec_ev);
+  if (ctx->side) {
+    (void)hipStreamSynchronize(ctx->side);
+    (void)hipStreamDestroy(ctx->side);
+  }
+  if (ctx->side_fork) (void)hipEventDestroy(ctx->side_fork);
+  if (ctx->side_join) (void)hipEventDestroy(ctx->side_join);
+  if (ctx->table_dev) (void)hipFree(ctx->table_dev);
+  for (int k = 0; k < PCV_NUM_STAGES; ++k) {
+    if (ctx->stage_b[k]) (void)hipEventDestroy(ctx->stage_b[k]);
+    if (ctx->stage_e[k]) (void)hipEventDestroy(ctx->stage_e[k]);
+  }
+  for (auto& p : ctx->prof_pending) {
+    (void)hipEventDestroy(p.a);
+    (void)hipEventDestroy(p.b);
+  }
+  for (auto& e : ctx->prof_free) (void)hipEventDestroy(e);
+  if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
+  delete ctx;
+}
+
+extern "C" const char* pcv_last_error(const pcv_ctx* ctx) { return ctx ? ctx->last_error.c_str() : "null context"; }
+
+extern "C" int pcv_ctx_synchronize(pcv_ctx* ctx) {
+  if (!ctx) return PCV_E_INVALID;
+  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return PCV_OK;
+}
+
+// Stream hand-off with the caller's runtime (torch, RCCL): order the context's stream after / before another stream
+// of the same device without blocking the host. `stream` may be NULL: the legacy default stream (torch's default).
+extern "C" int pcv_ctx_wait_stream(pcv_ctx* ctx, void* stream) {
+  if (!ctx) return PCV_E_INVALID;
+  if ((hipStream_t)stream == ctx->stream) return PCV_OK;
+  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  PCV_HIP_CHECK(ctx, hipEventRecord(ctx->xev, (hipStream_t)stream));
+  PCV_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->xev, 0));
+  return PCV_OK;
+}
+extern "C" int pcv_ctx_signal_stream(pcv_ctx* ctx, void* stream) {
+  if (!ctx) return PCV_E_INVALID;
+  if ((hipStream_t)stream == ctx->stream) return PCV_OK;
+  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  PCV_HIP_CHECK(ctx, hipEventRecord(ctx->xev, ctx->stream));
+  PCV_HIP_CHECK(ctx, hipStreamWaitEvent((hipStream_t)stream, ctx->xev, 0));
+  return PCV_OK;
+}
+
+extern "C" int pcv_ctx_trim(pcv_ctx* ctx) {
+  if (!ctx) return PCV_E_INVALID;
+  (void)hipSetDevice(ctx->device);
+  (void)hipStreamSynchronize(ctx->stream);
+  ctx->pool.trim();
+  for (auto& kv : ctx->host_free) (void)hipHostFree(kv.second);
+  ctx->host_free.clear();
+  return PCV_OK;
+}

@@ -281,7 +281,7 @@ __global__ __launch_bounds__(1024) void split2_assign_kernel(PcvNodeTableDev t, 
   }
 }
 
-#ifdef PCV_EXPERIMENTS  // measured slower than sort + split (see the note at the call site, pcv_build.hip): experiment library only
+#ifdef PCV_EXPERIMENTS  // measured slower than sort + split (see the note at the call site, pcv_single_chain.hip): experiment library only
 // ---- the sample tree by COUNTING (round 5) -----------------------------------------------------------------------------------
 // MEASURED AND DROPPED (2-3 x slower than what it replaces: global atomics). The idea:
 // The sample tree of the single-chain build comes out of a five-pass key sort (15 launches) and a node split by binary search

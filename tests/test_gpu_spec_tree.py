@@ -24,7 +24,7 @@ INFO_KEYS = ("single_chain", "predicted_nodes", "predicted_leaves", "kept_code_p
 
 
 def _sample_bounds(n, cap):
-    """stride, split threshold and floor(upper) of the sample as single_chain_topology derives them (pcv_build.hip)."""
+    """stride, split threshold and floor(upper) of the sample as plan_sample derives them (pcv_single_chain.hip)."""
     stride = 64
     while stride > 1 and n // stride < 4096:
         stride >>= 1
