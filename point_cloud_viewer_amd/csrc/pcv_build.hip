@@ -612,7 +612,8 @@ extern "C" int pcv_build_finish(pcv_octree* t, const pcv_top_layout* top) {
   // device tables: walk records for K5, 64-byte node / leaf records and the work lists for K6 (pcv_tables.h). settle_by_leaf
   // off: the slot-wise settle kernel and the flat climb launch, experiments
   const bool by_leaf = pcv_switches().settle_by_leaf;
-  const bool fuse_sort = bs->spec && bs->sort_second.pending && (bs->sort_second.nbits <= 7 || !t->has_intensity) && by_leaf && !wide && bs->spec_wide;
+  const bool fuse_sort = bs->spec && bs->sort_second.pending &&
+                         pcv_sort_second_settles(bs->sort_second.nbits, bs->sort_second.plane_src != nullptr, t->has_intensity) && by_leaf && !wide && bs->spec_wide;
   const uint32_t num_cont = bs->spec ? (uint32_t)bs->cont_nodes.size() : 0u;
   PcvWorkLists work;
   pcv_table_plan_work(tb, lv, num_leaves, rank_of.data(), by_leaf, fuse_sort, bs->cont_nodes.data(), num_cont, bs->fix_ranges.data(),

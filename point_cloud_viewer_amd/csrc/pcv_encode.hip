@@ -1042,7 +1042,7 @@ void pcv_launch_rank_hist(pcv_ctx* ctx, const uint32_t* rank, uint64_t n, uint32
 }
 
 // The same count over the workgroups and chunks of the record sort (pcv_sort_rec12_geometry), every workgroup's histogram kept
-// as a row: the sort's first pass derives its digit histogram from the rows and the rank map (pcv_sort.hip) instead of
+// as a row: the sort's first pass derives its digit histogram from the rows and the rank map (pcv_sort_rec12.hip) instead of
 // reading the keys once more. Up to 32 768 bins per launch (128 KB of LDS, one workgroup per CU: the sort's own occupancy);
 // bigger trees (1 B points: ~50 000 predicted nodes) take one launch per 32 768 bins. num_bins <= pcv_rank_hist_max_bins().
 uint32_t pcv_rank_hist_max_bins() { return 1u << 18; }

@@ -13,6 +13,7 @@
 
 #include "../../include/pcv_hip.h"
 #include "pcv_levels.h"
+#include "pcv_sort_plan.h"
 #include "pcv_spec.h"
 
 #define PCV_HIP_CHECK(ctx, expr)                                                                   \
@@ -317,7 +318,9 @@ void pcv_launch_chain_keys(pcv_ctx* ctx, const PcvLevels& lv, uint64_t n, uint64
                            size_t zero_words = 0);
 void pcv_launch_depth_probe(pcv_ctx* ctx, const uint64_t* sorted, uint32_t n, uint32_t gap, uint32_t* out);
 
-// pcv_sort.hip — stable LSD radix sort, 8-bit digits, reduce-then-scan with LDS histograms.
+// pcv_sort.hip, pcv_sort_rec12.hip — stable LSD radix sort, 8-bit digits, reduce-then-scan with LDS histograms: the keys-only
+// and generic record sorts in the first file, everything for the single-chain build's 12-byte records in the second; what a sort
+// launches is planned in pcv_sort_plan.h.
 struct PcvSortPayload {
   void* vec_in = nullptr;   // optional 16-byte payload word per key (uint4), ping-pong partner in vec_out
   void* vec_out = nullptr;
@@ -334,8 +337,7 @@ struct PcvSortPayload {
   const uint8_t* color_in = nullptr;
   uint32_t color_stride = 3;
 };
-size_t pcv_sort_scratch_bytes(uint64_t n);
-bool pcv_sort_first_pass_joins_color(uint64_t n);
+size_t pcv_sort_scratch_bytes(uint64_t n);  // PcvSortScratch::end + slack
 // Sorts keys_in -> ... ping-pong between (keys_a, payload.in) and (keys_b, payload.out). Returns in
 // *result_in_a whether the final sorted data is in the a-side (true) or b-side (false).
 int pcv_radix_sort_u64(pcv_ctx* ctx, uint64_t* keys_a, uint64_t* keys_b, uint64_t n, int begin_bit, int end_bit,
@@ -383,6 +385,68 @@ int pcv_radix_sort_records_mapped(pcv_ctx* ctx, uint32_t* keys_a, uint32_t* keys
                                   PcvSortPayload* payload, void* scratch, const uint32_t* map, uint32_t map_entries,
                                   bool* result_in_a, const uint32_t* rows = nullptr, PcvSortSecond* second = nullptr);
 int pcv_radix_sort_records_second(pcv_ctx* ctx, PcvSortSecond* second, const PcvSortFuse* fuse /* or null: a plain pass */);
+
+// ---- between pcv_sort.hip and pcv_sort_rec12.hip: every kernel is compiled in one of the two, the other goes through these ----
+// The ping-pong sides as pass k of a sort sees them (every pass flips them; pass 0 reads the a-side): keys, payload words and
+// plane 0 of the side it reads and of the side it writes. Pass 0 reads plane 0 from PcvSortPayload::first_in0 where that is set.
+struct PcvSortSides {
+  void *src, *dst;
+  void *vec_in, *vec_out;
+  const uint32_t* plane_in;
+  uint32_t* plane_out;
+};
+inline PcvSortSides pcv_sort_sides(void* a, void* b, const PcvSortPayload* pl, int k) {
+  const bool in_a = k % 2 == 0, planes = pl && pl->nwords > 0;
+  PcvSortSides s;
+  s.src = in_a ? a : b, s.dst = in_a ? b : a;
+  s.vec_in = !pl ? nullptr : in_a ? pl->vec_in : pl->vec_out;
+  s.vec_out = !pl ? nullptr : in_a ? pl->vec_out : pl->vec_in;
+  s.plane_in = !planes ? nullptr : k == 0 && pl->first_in0 ? pl->first_in0 : in_a ? pl->in[0] : pl->out[0];
+  s.plane_out = !planes ? nullptr : in_a ? pl->out[0] : pl->in[0];
+  return s;
+}
+template <typename T>
+inline T* pcv_sort_scratch_at(void* scratch, size_t offset) {  // offset: a field of PcvSortScratch
+  return reinterpret_cast<T*>(static_cast<char*>(scratch) + offset);
+}
+// the facts of a sort that do not depend on who calls it (pcv_sort_plan.h): sizes, bits, the payload's shape, the switches
+inline PcvSortFacts pcv_sort_facts(uint64_t n, int key_bytes, int begin_bit, int end_bit, const PcvSortPayload* pl) {
+  PcvSortFacts f;
+  f.n = n, f.key_bytes = key_bytes, f.begin_bit = begin_bit, f.end_bit = end_bit;
+  if (pl) f.vec_in = pl->vec_in != nullptr, f.vec_bytes = pl->vec_bytes, f.nwords = pl->nwords, f.color_in = pl->color_in != nullptr;
+  f.sort_rows2 = pcv_switches().sort_rows2, f.sort_msd = pcv_switches().sort_msd, f.rows_true_bins = pcv_switches().rows_true_bins;
+  return f;
+}
+// One launch of the 12-byte record downsweep (pcv_sort_rec12.hip): the instantiation as the plan's pass names it, or the
+// settling form of a held-back second pass (`fuse` set: PcvSortSettleForm by nbits and the plane).
+struct PcvSortRec12Args {
+  int R = 128, MAP = 0;
+  bool PL = false, WC = false;
+  const PcvSortFuse* fuse = nullptr;
+  int grid = 0;  // workgroups: the sort's groups (chunks), or the pieces of a second pass
+  size_t dyn_lds = 0;
+  const uint32_t* src = nullptr;
+  uint32_t* dst = nullptr;
+  uint64_t n = 0, chunk = 0;
+  int shift = 0, nbits = 0;
+  const uint32_t *hist = nullptr, *totals = nullptr;
+  const void* vec_in = nullptr;  // uint2 per record
+  void* vec_out = nullptr;
+  const uint32_t* plane_in = nullptr;
+  uint32_t* plane_out = nullptr;
+  const uint32_t* map = nullptr;
+  uint32_t map_entries = 0;
+  const void* ranges = nullptr;  // uint2 per piece
+  const uint32_t* order = nullptr;
+  const uint8_t* color_in = nullptr;
+  uint32_t color_stride = 3;
+};
+void pcv_sort_launch_rec12(pcv_ctx* ctx, const PcvSortRec12Args& a);
+// pcv_sort.hip: scan_kernel over a histogram of `groups` columns; passes [first, plan.npasses) of a 32-bit sort, each upsweep
+// -> scan -> downsweep
+void pcv_sort_launch_scan(pcv_ctx* ctx, uint32_t* hist, int groups, uint32_t* totals);
+void pcv_sort_generic_passes_u32(pcv_ctx* ctx, const PcvSortPlan& plan, int first, uint32_t* keys_a, uint32_t* keys_b,
+                                 PcvSortPayload* payload, void* scratch, const uint32_t* map, uint32_t map_entries);
 
 // pcv_topology.hip — node split (topology from sorted keys).
 // Device node table, structure of arrays, BFS order (level-major, prefix-sorted inside a level).

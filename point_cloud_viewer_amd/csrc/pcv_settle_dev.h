@@ -1,6 +1,6 @@
 // pcv_settle_dev.h — device code shared by the kernels that finish sorted records: the final rewrite and store of a point that
 // stays in its node (K6, generation.rs:195-253,335-387). Used by `settle` / `climb` (pcv_encode.hip) and by the
-// record sort's last pass when it settles the leaves' points itself (pcv_sort.hip). Include after pcv_chain_dev.h.
+// record sort's last pass when it settles the leaves' points itself (pcv_sort_rec12.hip). Include after pcv_chain_dev.h.
 #pragma once
 #include "pcv_chain_dev.h"
 

@@ -1,6 +1,6 @@
 // pcv_single_chain.hip — the single-chain build's host side (pcv_spec.h): the record sort and the replay it
 // queues, and the topology found from a sample in named steps. Host code only: the kernels are in pcv_chain.hip,
-// pcv_topology.hip, pcv_sort.hip and pcv_encode.hip.
+// pcv_topology.hip, pcv_sort.hip, pcv_sort_rec12.hip and pcv_encode.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -68,7 +68,7 @@ int pcv_queue_record_sort(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, const PcvWa
   if (bs->spec && bs->color_late) {
     // the first pass of the rows form reads the colour as it loads the records; any other form of the sort (the rank-count rows
     // did not fit, experiments) gets it joined in place first
-    const bool first_pass_joins = bs->spec_map_dev && compact && pl.nwords <= 1 && bs->spec_rows && pcv_sort_first_pass_joins_color(n);
+    const bool first_pass_joins = bs->spec_map_dev && compact && pl.nwords <= 1 && bs->spec_rows;
     if (first_pass_joins) {
       pl.color_in = d.color;
       pl.color_stride = d.color_stride;

@@ -6,6 +6,7 @@ split or merged, of several (comma-separated files per side): which kernels are 
   hipcc ... -o after/pcv_sort.s                                                                                        (new tree)
   tools/kernel_asm_diff.py before/pcv_sort.s after/pcv_sort.s
   tools/kernel_asm_diff.py before/pcv_query.s after/pcv_shapes.s,after/pcv_cull.s,after/pcv_query.s
+  tools/kernel_asm_diff.py before/pcv_sort.s after/pcv_sort.s,after/pcv_sort_rec12.s
 
 A kernel is its function body plus its .amdhsa_kernel descriptor. Assembler comments, .file / .loc / .ident lines and the
 per-file function index inside local labels (.LBB<i>_<n>, .Lfunc_end<i>, .LJTI<i>_<n>) are dropped: they move when another
