@@ -1,13 +1,15 @@
-/* build_xray_quadtree.c — xray's build_xray_quadtree over the C ABI in plain C11: one or more octree directories (the
- * reference's point_cloud_locations) are opened, the leaf tiles over all of them are rasterised on the device
- * (pcv_xray_run_ex), every level above them up to the root node is built on the device (pcv_xray_build_parents), and
+/* build_xray_quadtree.c — xray's build_xray_quadtree over the C ABI in plain C11: one or more point cloud directories (the
+ * reference's point_cloud_locations) are opened — all as octrees, or all as S2 cell clouds when the first directory's
+ * meta.pb says so (pcv_cloud_kind, as PointCloudClientBuilder::build decides) — the leaf tiles over all of them are
+ * rasterised on the device (pcv_xray_run_ex, or pcv_s2_open_dir + pcv_xray_run_s2; every flag works for both kinds),
+ * every level above them up to the root node is built on the device (pcv_xray_build_parents), and
  * the quadtree directory the xray viewer loads is written: one <node>.png per node and the meta file
  * (pcv_xray_write_dir_ex). A subset of the reference binary's flags, and --png: stored (the default) or deflate, the
  * tiles compressed on the device. With --inpaint-distance-px the leaves are built with the transparent background,
  * inpainted on the device (pcv_xray_inpaint; the fill is not the reference's texture synthesis) and given
  * --tile-background-color afterwards: build_xray_quadtree and inpaint_xray_quadtree in one run, no directory between.
  *
- *   build_xray_quadtree <octree dir>... --output-directory <dir> --resolution <m per px> [--tile-size <px>]
+ *   build_xray_quadtree <octree dir | S2 cell cloud dir>... --output-directory <dir> --resolution <m per px> [--tile-size <px>]
  *                       [--coloring-strategy xray|colored|colored_with_intensity|colored_with_height_stddev]
  *                       [--min-intensity <f>] [--max-intensity <f>] [--binning intensity=<size>] [--max-stddev <m>]
  *                       [--colormap jet|purplish] [--tile-background-color white|transparent]
@@ -22,11 +24,13 @@
 
 static int usage(void) {
   fprintf(stderr,
-          "usage: build_xray_quadtree <octree dir>... --output-directory <dir> --resolution <m per px> [--tile-size <px>]\n"
+          "usage: build_xray_quadtree <octree dir | S2 cell cloud dir>... --output-directory <dir> --resolution <m per px>\n"
+          "       [--tile-size <px>]\n"
           "       [--coloring-strategy xray|colored|colored_with_intensity|colored_with_height_stddev] [--min-intensity <f>]\n"
           "       [--max-intensity <f>] [--binning intensity=<size>] [--max-stddev <m>] [--colormap jet|purplish]\n"
           "       [--tile-background-color white|transparent] [--filter-interval intensity=<lo>,<hi>] [--root-node-id <r...>]\n"
-          "       [--png stored|deflate] [--inpaint-distance-px <0..254>]\n");
+          "       [--png stored|deflate] [--inpaint-distance-px <0..254>]\n"
+          "       the first directory's meta.pb decides: octrees, or S2 directories (S2 cell clouds); all are opened as that kind\n");
   return 2;
 }
 
@@ -119,12 +123,24 @@ int main(int argc, char** argv) {
   }
   pcv_ctx* ctx = NULL;
   pcv_octree** trees = (pcv_octree**)calloc(num_inputs, sizeof(pcv_octree*));
+  pcv_s2_cloud** clouds = (pcv_s2_cloud**)calloc(num_inputs, sizeof(pcv_s2_cloud*));
+  int kind = PCV_CLOUD_OCTREE;
   pcv_xray* x = NULL;
   const uint32_t background = p.background;
   if (inpaint >= 0) p.background = PCV_XRAY_BG_TRANSPARENT; /* the holes must survive until they are filled */
-  int rc = trees ? pcv_ctx_create(0, NULL, &ctx) : PCV_E_OOM;
-  for (uint32_t t = 0; t < num_inputs && rc == PCV_OK; ++t) rc = pcv_octree_open_dir(ctx, inputs[t], &trees[t]);
-  if (rc == PCV_OK) rc = pcv_xray_run_ex(ctx, trees, num_inputs, &p, &col, &x);
+  int rc = trees && clouds ? pcv_cloud_kind(inputs[0], &kind) : PCV_E_OOM;
+  if (rc != PCV_OK) {
+    fprintf(stderr, "build_xray_quadtree: %s (%d)\n", trees && clouds ? pcv_host_last_error() : "out of memory", rc);
+    free(trees);
+    free(clouds);
+    free(inputs);
+    return 1;
+  }
+  rc = pcv_ctx_create(0, NULL, &ctx);
+  for (uint32_t t = 0; t < num_inputs && rc == PCV_OK; ++t)
+    rc = kind == PCV_CLOUD_S2 ? pcv_s2_open_dir(ctx, inputs[t], &clouds[t]) : pcv_octree_open_dir(ctx, inputs[t], &trees[t]);
+  if (rc == PCV_OK)
+    rc = kind == PCV_CLOUD_S2 ? pcv_xray_run_s2(ctx, clouds, num_inputs, &p, &col, &x) : pcv_xray_run_ex(ctx, trees, num_inputs, &p, &col, &x);
   if (rc == PCV_OK && inpaint >= 0) { /* the result carries its own parent levels */
     pcv_xray* filled = NULL;
     rc = pcv_xray_inpaint(ctx, x, NULL, 0, (uint32_t)inpaint, background, &filled);
@@ -147,9 +163,12 @@ int main(int argc, char** argv) {
     fprintf(stderr, "build_xray_quadtree: %s (%d)\n", ctx ? pcv_last_error(ctx) : "no context", rc);
   }
   pcv_xray_free(x);
-  for (uint32_t t = 0; trees && t < num_inputs; ++t)
+  for (uint32_t t = 0; t < num_inputs; ++t) {
     if (trees[t]) pcv_octree_free(trees[t]);
+    if (clouds[t]) pcv_s2_free(clouds[t]);
+  }
   free(trees);
+  free(clouds);
   free(inputs);
   if (ctx) pcv_ctx_destroy(ctx);
   return rc == PCV_OK ? 0 : 1;

@@ -1229,6 +1229,34 @@ int pcv_s2_query_points(pcv_s2_query* q, uint64_t first_segment, uint64_t num_se
                         double* y, double* z, uint8_t* rgb, float* intensity);
 void pcv_s2_query_free(pcv_s2_query* q);
 
+/* ---- xray over S2 cell clouds -------------------------------------------------------- */
+/* build_xray_quadtree's leaf level over S2 cell clouds: PointCloudClient opens every location as an S2Cells cloud when the
+ * first one's meta.pb says so (point_cloud_client/src/lib.rs:107-132), and the tile queries run over either kind
+ * (xray/src/generation.rs:464-513, 557-648). pcv_xray_run_ex with the clouds in place of the octrees (coloring nullable: then
+ * colored_with_intensity is refused, as by pcv_xray_run_many): the bounding box is the first cloud's meta box grown by every
+ * cloud's min and then its max in list order; query_from_global, root_level / root_index, leaf geometry and backgrounds as
+ * in pcv_xray_run. One location per leaf tile (an Aabb, or an Obb with query_from_global), the intensity interval on every
+ * location, every cloud through the machinery of pcv_s2_query_run: a tile sees the points of the cells that
+ * pcv_s2_cells_in_location lists for its shape, and only those (the reference's misses included), filtered by `contains` and
+ * the interval, their stored f64 positions untouched. A tile is created iff the kept points summed over the clouds are
+ * > 0; kept, drawn and negative are sums over the clouds. All four strategies, binning and the negative-intensity rule
+ * of pcv_xray_run_ex apply unchanged; each raster pass is one launch per tile group whatever num_clouds. The result is
+ * an ordinary built pcv_xray, on which parents, node images, directories, merge and inpaint work, and holds no reference to
+ * the clouds. PCV_E_INVALID with a message and nothing left allocated: num_clouds == 0 ("No locations specified for point
+ * cloud client."), more than PCV_XRAY_MAX_TREES clouds, a null cloud, a cloud of another context, a host-only cloud
+ * (opened with a NULL context), a strategy, filter or binning that reads intensity when some cloud has none,
+ * pcv_xray_check_params_ex's own refusals, and a cloud with a level-0 cell (pcv_s2_cells_in_location's refusal of
+ * geometric locations). Out of device memory is PCV_E_OOM with nothing left allocated. */
+int pcv_xray_run_s2(pcv_ctx* ctx, pcv_s2_cloud* const* clouds, uint32_t num_clouds, const pcv_xray_params* params,
+                    const pcv_xray_coloring* coloring /* nullable */, pcv_xray** out);
+/* Host only: which arm PointCloudClientBuilder::build (point_cloud_client/src/lib.rs:107-132) would take for this
+ * directory's meta.pb: `version <= 11 || has_octree()` is PCV_CLOUD_OCTREE, anything else PCV_CLOUD_S2. The reference
+ * opens every location as the first one's kind; the entry points here take one kind each, and the caller decides. A missing
+ * or unreadable meta.pb is PCV_E_IO naming the file (pcv_host_last_error). */
+#define PCV_CLOUD_OCTREE 0
+#define PCV_CLOUD_S2 1
+int pcv_cloud_kind(const char* directory, int* kind);
+
 #ifdef __cplusplus
 }
 #endif

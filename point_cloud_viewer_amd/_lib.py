@@ -93,6 +93,7 @@ XRAY_PNG_STORED, XRAY_PNG_DEFLATE = 0, 1  # PCV_XRAY_PNG_*: the mode of pcv_xray
 XRAY_INPAINT_MAX_TILE = 8192  # PCV_XRAY_INPAINT_MAX_TILE
 XRAY_INPAINT_ABSENT = 0xFFFFFFFF  # an empty slot of pcv_xray_inpaint_plan
 XRAY_MAX_TREES = 4096  # PCV_XRAY_MAX_TREES: octrees of one pcv_xray_run_many
+CLOUD_OCTREE, CLOUD_S2 = 0, 1  # pcv_cloud_kind
 XRAY_FN_XRAY, XRAY_FN_COLORED, XRAY_FN_JET, XRAY_FN_PURPLISH, XRAY_FN_TO_U8, XRAY_FN_INTENSITY = 0, 1, 2, 3, 4, 5
 REL_IN, REL_CROSS, REL_OUT = 0, 1, 2
 
@@ -340,6 +341,8 @@ _SIGNATURES = {
     "pcv_s2_union_intersects_host": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _vp, _vp]),
     "pcv_s2_cells_in_location": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp]),
     "pcv_s2_cells_in_location_host": (C.c_int, [C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp]),
+    "pcv_xray_run_s2": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(XrayParams), C.POINTER(XrayColoring), C.POINTER(_vp)]),
+    "pcv_cloud_kind": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
 }
 
 _lib = None

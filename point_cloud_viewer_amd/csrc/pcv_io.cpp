@@ -593,6 +593,32 @@ int pcv_s2_read_cells(const char* directory, const PcvS2Dir& meta, uint8_t* xyz,
   return PCV_OK;
 }
 
+// PointCloudClientBuilder::build's choice (point_cloud_client/src/lib.rs:107-132): the first location's meta.pb says how
+// every location is opened — `version <= 11 || has_octree()` as octrees, anything else as S2 cell clouds
+extern "C" int pcv_cloud_kind(const char* directory, int* kind) {
+  if (!directory || !kind) return pcv_host_fail(PCV_E_INVALID, "null argument");
+  const std::string dir(directory);
+  std::vector<uint8_t> buf;
+  bool missing;
+  if (!read_file(dir + "/meta.pb", &buf, &missing)) return pcv_host_fail(PCV_E_IO, "cannot read " + dir + "/meta.pb");
+  int64_t version = 0;
+  bool has_octree = false;
+  Reader r{buf.data(), buf.data() + buf.size()};
+  while (r.p < r.end && r.ok) {
+    const uint64_t t = r.varint();
+    const int f = (int)(t >> 3), w = (int)(t & 7);
+    if (f == 1 && w == 0) version = (int64_t)r.varint();
+    else {
+      // oneof data { octree = 6; s2 = 7 } (proto.proto:136-149): the arm that comes last in the message is the one set
+      if ((f == 6 || f == 7) && w == 2) has_octree = f == 6;
+      r.skip(w);
+    }
+  }
+  if (!r.ok) return pcv_host_fail(PCV_E_IO, dir + "/meta.pb is not a Meta message");
+  *kind = version <= 11 || has_octree ? PCV_CLOUD_OCTREE : PCV_CLOUD_S2;
+  return PCV_OK;
+}
+
 extern "C" int pcv_octree_open_dir(pcv_ctx* ctx, const char* directory, pcv_octree** out) {
   if (!ctx) return PCV_E_INVALID;
   if (!directory || !out) return ctx->fail(PCV_E_INVALID, "null argument");

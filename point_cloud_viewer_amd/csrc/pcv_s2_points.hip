@@ -1,8 +1,9 @@
 // pcv_s2_points.hip — the batched point query over an S2 cell cloud: FilteredIterator over NodeIterator with Encoding::Plain
 // (reference src/iterator.rs:96-119, src/s2_cells/mod.rs:171-191) for every (location, listed cell) of one call.
 //
-//   cells    the lists of pcv_s2_query.hip (pcv_s2_launch_cell_lists), read back once: one segment per (location, listed cell),
-//            locations one after another, cells ascending; the segments' candidates laid out back to back in chunks of 1 024
+//   cells    the lists of pcv_s2_query.hip (pcv_s2_cells_in_location), read back: the counts, then the lists at the longest
+//            one's length; one segment per (location, listed cell), locations one after another, cells ascending; the
+//            segments' candidates laid out back to back in chunks of 1 024 (pcv_s2_query_dev.h)
 //   flags    s2_flags_kernel<KIND>: one workgroup per chunk, an instance per shape kind (PCV_SHAPE_FRUSTUM for both frusta, the
 //            web-mercator chain and the cell-union search in instances of their own, so the others keep their registers); the
 //            points are the cloud's 24-byte AoS f64, a wave's 64 points one contiguous 1 536-byte run, untouched
@@ -15,28 +16,12 @@
 #include "pcv_contain_dev.h"
 #include "pcv_s2_obj.h"
 #include "pcv_s2_dev.h"
-
-struct pcv_s2_query {
-  pcv_s2_cloud* cloud = nullptr;
-  uint64_t nseg = 0, kept = 0, candidates = 0;
-  std::vector<uint64_t> location_first;  // [locations + 1]
-  std::vector<uint32_t> seg_cell;        // [nseg]
-  std::vector<uint64_t> seg_offset;      // [nseg + 1] kept points before the segment
-  std::vector<uint64_t> seg_first_chunk; // [nseg + 1]
-  struct Chunk* d_chunks = nullptr;      // in candidate order
-  uint32_t* d_flags = nullptr;           // one per candidate
-  uint64_t* d_offsets = nullptr;         // [candidates + 1]
-};
-
-struct Chunk {
-  uint64_t src;    // first point in the cloud's blobs
-  uint64_t first;  // first candidate
-  uint32_t count, location;
-};
+#include "pcv_s2_query_dev.h"
 
 namespace {
 
-constexpr uint32_t kChunkPoints = 1024;
+using Chunk = PcvS2Chunk;
+constexpr uint32_t kChunkPoints = kS2ChunkPoints;
 constexpr int kKindUnion = 100;  // a cell union: not a PCV_SHAPE_*
 
 struct Ival {  // ClosedInterval of one location on intensity
@@ -137,8 +122,13 @@ int run_impl(pcv_s2_cloud* c, const pcv_shapes* shapes, uint32_t num_unions, con
   if (locations == 0 || ncells == 0) return PCV_OK;
   int rc;
   // ---- cell lists, read back: the segments ----
-  std::vector<uint32_t> counts(locations), lists((size_t)locations * ncells);
-  if ((rc = pcv_s2_cells_in_location(c, shapes, num_unions, union_first, union_cells, ncells, counts.data(), lists.data()))) return rc;
+  // the counts first, then the lists at the longest one's length: rows of `cap`, not of every cell of the cloud (many small
+  // locations over many cells, xray's leaf tiles, would otherwise cost locations x cells on the host and the device)
+  std::vector<uint32_t> counts(locations);
+  if ((rc = pcv_s2_cells_in_location(c, shapes, num_unions, union_first, union_cells, 0, counts.data(), nullptr))) return rc;
+  const uint32_t cap = *std::max_element(counts.begin(), counts.end());
+  std::vector<uint32_t> lists((size_t)locations * cap);
+  if (cap && (rc = pcv_s2_cells_in_location(c, shapes, num_unions, union_first, union_cells, cap, counts.data(), lists.data()))) return rc;
   if ((rc = pcv_s2_make_resident(c))) return rc;
   std::vector<Chunk> chunks;
   std::vector<uint64_t> seg_candidate(1, 0);
@@ -146,7 +136,7 @@ int run_impl(pcv_s2_cloud* c, const pcv_shapes* shapes, uint32_t num_unions, con
   for (uint64_t l = 0; l < locations; ++l) {
     const int kind = kind_of(shapes, num_shapes, (uint32_t)l);
     for (uint32_t k = 0; k < counts[l]; ++k) {
-      const uint32_t cell = lists[l * ncells + k];
+      const uint32_t cell = lists[l * cap + k];
       b->seg_cell.push_back(cell);
       uint64_t left = c->counts[cell], src = c->offsets[cell];
       while (left) {

@@ -1,15 +1,16 @@
 // pcv_xray.hip — xray's build_xray_quadtree (xray/src/generation.rs:557-616) on the device, the leaf level: rasterised
-// straight from batched point queries (pcv_query.hip), one per octree of the run, without materialising their points. The
-// parent levels and the merge are pcv_xray_pyramid.hip, node images and the quadtree directory pcv_xray_files.hip; the
-// handle they share (pcv_xray_obj.h) is made, listed and freed here.
+// straight from batched point queries, one per cloud of the run — octrees (pcv_query.hip) or S2 cell clouds
+// (pcv_s2_points.hip, as pcv_s2_query_dev.h states its result) — without materialising their points. The parent levels
+// and the merge are pcv_xray_pyramid.hip, node images and the quadtree directory pcv_xray_files.hip; the handle they
+// share (pcv_xray_obj.h) is made, listed and freed here.
 //
 //   host   leaf geometry   get_bounding_box :550 (Aabb::transform, src/geometry/aabb.rs:58-66),
 //                          find_quadtree_bounding_rect_and_levels :515, Node::from_node_id_and_root_bounding_rect and
 //                          Node::get_child (quadtree/src/lib.rs:59-97), get_nodes_at_level :534 (DFS pop order)
 //   host   one query per leaf tile   xray_from_points :464 — Aabb(tile) or Obb::from(tile).transformed(global_from_query)
 //                          (src/geometry/obb.rs:20-47), intensity interval on every shape, through pcv_query_batch_run
-//   K_xb   xray_bin        per kept point: decode (the batch's own decode), query_from_global (:493-497), discretise
-//                          (:119-123); count per (tile, 32 x 32 pixel block), aggregated per wave before the atomic
+//   K_xb   xray_bin        per kept point: decode (the batch's own decode; an S2 candidate: its stored f64),
+//                          query_from_global (:493-497), discretise (:119-123); count per (tile, 32 x 32 pixel block), aggregated per wave before the atomic
 //   scan   bucket counts -> u64 offsets (pcv_batch_scan)
 //   K_xs   xray_scatter    the same walk again, writing one 8-byte record per drawable point into its bucket (+ z as f64
 //                          for height_stddev)
@@ -30,10 +31,13 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
 #include "pcv_query_dev.h"
+#include "pcv_s2_obj.h"
+#include "pcv_s2_query_dev.h"
 #include "pcv_switches.h"
 #include "pcv_xray_obj.h"
 
@@ -198,13 +202,41 @@ struct XrayPoint {
   double z;
   int64_t bin;
 };
-__device__ __forceinline__ XrayPoint xray_point(const XrayBinArgs& a, const uint8_t* rgb, const float* inten, const ChunkDesc& d,
-                                                const PointsView& v, const XrayTileDev& t, uint32_t bbase, uint32_t q, bool kept) {
+// Where a chunk's points come from. An octree batch's chunk: a node's encoded bytes, decoded by the batch's own decode, u8
+// keep flags, attributes at attr_index. An S2 query's chunk: up to 1 024 candidates of one cell, the stored f64 positions
+// untouched (24-byte AoS: a wave's 64 points are one contiguous 1 536-byte run), u32 keep flags, colour and intensity at
+// the same point index.
+struct XrayNodeSource {
+  const uint8_t* rgb;
+  const float* inten;
+  const ChunkDesc& d;
+  const PointsView& v;
+  const PCV_GLOBAL uint8_t* kp;
+  __device__ __forceinline__ bool kept(uint32_t q) const { return kp[q]; }
+  __device__ __forceinline__ bool has_intensity() const { return inten != nullptr; }
+  __device__ __forceinline__ float intensity(uint32_t q) const { return inten[d.attr_index + q]; }
+  __device__ __forceinline__ V3d position(uint32_t q) const { return load_point(v, q); }
+  __device__ __forceinline__ const uint8_t* color(uint32_t q) const { return rgb + 3 * (d.attr_index + q); }
+};
+struct XrayS2Source {
+  const PCV_GLOBAL double* xyz;   // the chunk's first point
+  const PCV_GLOBAL uint8_t* rgb;
+  const PCV_GLOBAL float* inten;  // null unless the strategy or the binning reads intensity
+  const PCV_GLOBAL uint32_t* kp;
+  __device__ __forceinline__ bool kept(uint32_t q) const { return kp[q] != 0u; }
+  __device__ __forceinline__ bool has_intensity() const { return inten != nullptr; }
+  __device__ __forceinline__ float intensity(uint32_t q) const { return inten[q]; }
+  __device__ __forceinline__ V3d position(uint32_t q) const { return {xyz[3 * q], xyz[3 * q + 1], xyz[3 * q + 2]}; }
+  __device__ __forceinline__ const PCV_GLOBAL uint8_t* color(uint32_t q) const { return rgb + 3 * q; }
+};
+template <class Source>
+__device__ __forceinline__ XrayPoint xray_point(const XrayBinArgs& a, const Source& src, const XrayTileDev& t, uint32_t bbase, uint32_t q,
+                                                bool kept) {
   XrayPoint o{false, false, 0u, 0ull, 0.0, 0};
   if (!kept) return o;
   float in = 0.0f;
-  if (inten) {
-    in = inten[d.attr_index + q];
+  if (src.has_intensity()) {
+    in = src.intensity(q);
     // the `< 0` check runs on every kept point, inside the image or not (:108-127, :248); such points are not drawn
     if (a.strategy == PCV_XRAY_COLORED_WITH_INTENSITY && in < 0.0f) {
       o.neg = true;
@@ -212,7 +244,7 @@ __device__ __forceinline__ XrayPoint xray_point(const XrayBinArgs& a, const uint
     }
     if (a.binned) o.bin = rust_i64((double)in / a.bin_size);  // BinnedColoringStrategy::bins (:138-157)
   }
-  V3d p = load_point(v, q);
+  V3d p = src.position(q);
   if (a.has_iso) p = v_add(quat_rotate(a.iso + 3, p), V3d{a.iso[0], a.iso[1], a.iso[2]});
   const double W = (double)a.W;
   const uint32_t x = sat_u32(((p.x - t.min[0]) / t.diag[0]) * W);
@@ -223,7 +255,7 @@ __device__ __forceinline__ XrayPoint xray_point(const XrayBinArgs& a, const uint
   o.bucket = bbase + (y / kBlk) * a.nbx + x / kBlk;
   uint64_t rec = (uint64_t)((y % kBlk) * kBlk + x % kBlk) | (uint64_t)(z < kZMax ? z : kZMax) << 10;
   if (a.strategy == PCV_XRAY_COLORED) {
-    const uint8_t* c = rgb + 3 * (d.attr_index + q);
+    const auto* c = src.color(q);
     rec |= ((uint64_t)c[0] | (uint64_t)c[1] << 8 | (uint64_t)c[2] << 16) << 32;
   } else if (a.strategy == PCV_XRAY_COLORED_WITH_INTENSITY) {
     rec |= (uint64_t)__float_as_uint(in) << 32;
@@ -233,16 +265,55 @@ __device__ __forceinline__ XrayPoint xray_point(const XrayBinArgs& a, const uint
   return o;
 }
 
-// a wave per chunk of the group, whose chunks are those of all its octrees one after another. COUNT: one counter add per
-// distinct bucket of the 64 points (wave match on the bucket); SCATTER: the same adds reserve each point's slot in its
-// bucket. A wave's chunk index only grows, so its octree is found by a wave-uniform search forward from the last one.
-template <bool SCATTER>
+// one chunk by one wave, 64 points a step. COUNT: one counter add per distinct bucket of the 64 points (wave match on the
+// bucket); SCATTER: the same adds reserve each point's slot in its bucket.
+template <bool SCATTER, class Source>
+__device__ __forceinline__ void xray_bin_chunk(const XrayBinArgs& a, const Source& src, uint32_t cnt, int32_t created, const XrayTileDev& t,
+                                               uint32_t bbase, uint32_t lane, uint32_t* __restrict__ counts,
+                                               const uint64_t* __restrict__ offsets, uint64_t* __restrict__ rec, double* __restrict__ recz,
+                                               int64_t* __restrict__ recb) {
+  for (uint32_t q0 = 0; q0 < cnt; q0 += 64) {
+    const uint32_t q = q0 + lane;
+    const XrayPoint pt = xray_point(a, src, t, bbase, q, q < cnt && src.kept(q));
+    if (!SCATTER && a.negative) {
+      const unsigned long long negs = __ballot(pt.neg);
+      if (negs && lane == 0) atomicAdd(a.negative + created, (unsigned long long)__popcll(negs));
+    }
+    unsigned long long live = __ballot(pt.draw);
+    while (live) {
+      const int leader = __ffsll(live) - 1;
+      const uint32_t k = __shfl(pt.bucket, leader);
+      const bool peer = pt.draw && pt.bucket == k;
+      const unsigned long long peers = __ballot(peer);
+      uint32_t base = 0;
+      if ((uint32_t)leader == lane) base = atomicAdd(counts + k, (uint32_t)__popcll(peers));
+      if (SCATTER) {
+        base = __shfl(base, leader);
+        if (peer) {
+          const uint64_t pos = offsets[k] + base + (uint64_t)__popcll(peers & ((1ull << lane) - 1ull));
+          if (pos < offsets[k + 1]) {  // always true: both passes compute the same buckets
+            rec[pos] = pt.rec;
+            if (recz) recz[pos] = pt.z;
+            if (recb) recb[pos] = pt.bin;
+          }
+        }
+      }
+      live &= ~peers;
+    }
+  }
+}
+
+// a wave per chunk of the group, whose chunks are those of all its clouds one after another. A wave's chunk index only
+// grows, so its cloud is found by a wave-uniform search forward from the last one. S2: the chunks are those of S2 queries
+// (XrayTreeChunks::desc is a PcvS2Chunk list, keep the u32 flags, xyz the cloud's f64 positions); past the chunk's
+// descriptor the instances of both kinds run xray_bin_chunk.
+template <bool SCATTER, bool S2>
 __global__ __launch_bounds__(256) void xray_bin_kernel(XrayBinArgs a, uint32_t* __restrict__ counts, const uint64_t* __restrict__ offsets,
                                                        uint64_t* __restrict__ rec, double* __restrict__ recz,
                                                        int64_t* __restrict__ recb) {
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
   uint32_t k = 0;
-  uint64_t kend = a.ntrees > 1 ? a.trees[1].first : a.nchunks;  // first chunk past octree k
+  uint64_t kend = a.ntrees > 1 ? a.trees[1].first : a.nchunks;  // first chunk past cloud k
   for (uint64_t gi = (uint64_t)blockIdx.x * 4 + wave; gi < a.nchunks; gi += (uint64_t)gridDim.x * 4) {
     if (gi >= kend) {  // the last entry in (k, ntrees) whose first <= gi
       uint32_t lo = k + 1, hi = a.ntrees - 1;
@@ -255,49 +326,30 @@ __global__ __launch_bounds__(256) void xray_bin_kernel(XrayBinArgs a, uint32_t* 
       kend = k + 1 < a.ntrees ? a.trees[k + 1].first : a.nchunks;
     }
     const XrayTreeChunks tr = a.trees[k];
-    const ChunkDesc d = tr.desc[tr.c0 + (gi - tr.first)];
-    const int32_t created = a.created_of_shape[d.enc >> 8];
-    if (created < 0) continue;  // wave-uniform: no octree's query kept anything for this tile
-    const XrayTileDev t = a.tiles[created];
-    const uint32_t bbase = ((uint32_t)created - a.created0) * a.nblocks;
-    PointsView v{};
-    v.encoded = (const uint8_t*)(tr.xyz + d.src);
-    v.enc = d.enc & 15u;
-    v.cube_min[0] = d.cube_min[0];
-    v.cube_min[1] = d.cube_min[1];
-    v.cube_min[2] = d.cube_min[2];
-    v.cube_edge = d.cube_edge;
-    const PCV_GLOBAL uint8_t* kp = tr.keep + d.keep_off;
-    const uint8_t* rgb = (const uint8_t*)tr.rgb;
-    const float* inten = (const float*)tr.inten;
-    for (uint32_t q0 = 0; q0 < d.cnt; q0 += 64) {
-      const uint32_t q = q0 + lane;
-      const XrayPoint pt = xray_point(a, rgb, inten, d, v, t, bbase, q, q < d.cnt && kp[q]);
-      if (!SCATTER && a.negative) {
-        const unsigned long long negs = __ballot(pt.neg);
-        if (negs && lane == 0) atomicAdd(a.negative + created, (unsigned long long)__popcll(negs));
-      }
-      unsigned long long live = __ballot(pt.draw);
-      while (live) {
-        const int leader = __ffsll(live) - 1;
-        const uint32_t k = __shfl(pt.bucket, leader);
-        const bool peer = pt.draw && pt.bucket == k;
-        const unsigned long long peers = __ballot(peer);
-        uint32_t base = 0;
-        if ((uint32_t)leader == lane) base = atomicAdd(counts + k, (uint32_t)__popcll(peers));
-        if (SCATTER) {
-          base = __shfl(base, leader);
-          if (peer) {
-            const uint64_t pos = offsets[k] + base + (uint64_t)__popcll(peers & ((1ull << lane) - 1ull));
-            if (pos < offsets[k + 1]) {  // always true: both passes compute the same buckets
-              rec[pos] = pt.rec;
-              if (recz) recz[pos] = pt.z;
-              if (recb) recb[pos] = pt.bin;
-            }
-          }
-        }
-        live &= ~peers;
-      }
+    if constexpr (S2) {
+      const PcvS2Chunk c = ((const PCV_GLOBAL PcvS2Chunk*)tr.desc)[tr.c0 + (gi - tr.first)];
+      const int32_t created = a.created_of_shape[c.location];
+      if (created < 0) continue;  // wave-uniform: no cloud's query kept anything for this tile
+      const XrayTileDev t = a.tiles[created];
+      const uint32_t bbase = ((uint32_t)created - a.created0) * a.nblocks;
+      const XrayS2Source src{(const PCV_GLOBAL double*)tr.xyz + 3 * c.src, tr.rgb + 3 * c.src,
+                             tr.inten ? (const PCV_GLOBAL float*)tr.inten + c.src : nullptr, (const PCV_GLOBAL uint32_t*)tr.keep + c.first};
+      xray_bin_chunk<SCATTER>(a, src, c.count, created, t, bbase, lane, counts, offsets, rec, recz, recb);
+    } else {
+      const ChunkDesc d = tr.desc[tr.c0 + (gi - tr.first)];
+      const int32_t created = a.created_of_shape[d.enc >> 8];
+      if (created < 0) continue;  // wave-uniform: no octree's query kept anything for this tile
+      const XrayTileDev t = a.tiles[created];
+      const uint32_t bbase = ((uint32_t)created - a.created0) * a.nblocks;
+      PointsView v{};
+      v.encoded = (const uint8_t*)(tr.xyz + d.src);
+      v.enc = d.enc & 15u;
+      v.cube_min[0] = d.cube_min[0];
+      v.cube_min[1] = d.cube_min[1];
+      v.cube_min[2] = d.cube_min[2];
+      v.cube_edge = d.cube_edge;
+      const XrayNodeSource src{(const uint8_t*)tr.rgb, (const float*)tr.inten, d, v, tr.keep + d.keep_off};
+      xray_bin_chunk<SCATTER>(a, src, d.cnt, created, t, bbase, lane, counts, offsets, rec, recz, recb);
     }
   }
 }
@@ -855,8 +907,10 @@ extern "C" void pcv_xray_free(pcv_xray* x) {
 }
 
 // PointCloudClientBuilder::build's bounding box (point_cloud_client/src/lib.rs:101-125): the first octree's meta box, grown
-// by every octree's min and then its max in list order (Aabb::grow, aabb.rs:41-44: Point3::inf / sup per component)
-static void union_box(pcv_octree* const* trees, uint32_t K, double lo[3], double hi[3]) {
+// by every octree's min and then its max in list order (Aabb::grow, aabb.rs:41-44: Point3::inf / sup per component); the
+// same over S2 cell clouds (:121-131)
+template <class Cloud>
+static void union_box(Cloud* const* trees, uint32_t K, double lo[3], double hi[3]) {
   for (int a = 0; a < 3; ++a) {
     lo[a] = trees[0]->bbox_min[a];
     hi[a] = trees[0]->bbox_max[a];
@@ -970,18 +1024,37 @@ XrayAccum xray_accum_of(uint32_t strategy, bool binned) {
   return {(const void*)xray_accum_kernel<PCV_XRAY_HEIGHT_STDDEV, 256>, 256, PCV_K_XRAY_ACCUM, launch_accum<PCV_XRAY_HEIGHT_STDDEV, 256>};
 }
 
-// the same shapes through every octree (try_for_each_batch's jobs, src/iterator.rs:262-270); all K batches stay alive
+// the clouds of a run, all of one kind (PointClouds::Octrees or ::S2Cells, point_cloud_client/src/lib.rs:107-132)
+struct XrayClouds {
+  pcv_octree* const* trees = nullptr;
+  pcv_s2_cloud* const* s2 = nullptr;
+  uint32_t K = 0;
+};
+// what the planning reads of one cloud's query over the tile shapes, an octree batch or an S2 query alike: shape -> segments
+// -> kept points and chunks, and the pointers the raster passes read the chunks through
+struct XraySource {
+  const uint64_t* shape_first;  // [S + 1] first segment of each shape
+  const uint64_t* seg_kept;     // [segments + 1] kept points before each segment
+  const uint64_t* seg_chunk;    // [segments + 1] first chunk of each segment
+  XrayTreeChunks chunks;        // desc, keep, xyz, rgb, inten (c0 and first are per tile group)
+  uint64_t kept(uint64_t s) const { return seg_kept[shape_first[s + 1]] - seg_kept[shape_first[s]]; }
+  uint64_t chunk_of(uint64_t s) const { return seg_chunk[shape_first[s]]; }
+};
+// the same shapes through every cloud (try_for_each_batch's jobs, src/iterator.rs:262-270); all K queries stay alive
 // until the raster passes are done
 struct XrayBatches {
   std::vector<pcv_query_batch*> b;
+  std::vector<pcv_s2_query*> s2;
+  std::vector<XraySource> src;  // one per cloud, in list order
   ~XrayBatches() {
     for (pcv_query_batch* q : b) pcv_query_batch_free(q);
+    for (pcv_s2_query* q : s2) pcv_s2_query_free(q);
   }
 };
 
-// step 1: one shape per leaf tile (xray_from_points :470-476) and the K batch queries
-int xray_query_tiles(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pcv_xray_params* p, const LeafGeometry& g,
-                            XrayBatches* batches) {
+// step 1: one shape per leaf tile (xray_from_points :470-476) and the K queries, pcv_query_batch_run or pcv_s2_query_run
+int xray_query_tiles(pcv_ctx* ctx, const XrayClouds& clouds, const pcv_xray_params* p, const LeafGeometry& g, bool reads_intensity,
+                     XrayBatches* batches) {
   const bool filter = p->interval_attribute != nullptr;
   const uint32_t S = (uint32_t)g.index.size();
   std::vector<pcv_shape> shapes(S);
@@ -1010,17 +1083,43 @@ int xray_query_tiles(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const p
   pcv_shapes* sh = nullptr;
   int rc = pcv_shapes_create(ctx, shapes.data(), S, &sh);
   if (rc) return rc;
-  batches->b.reserve(K);
-  for (uint32_t t = 0; t < K && rc == PCV_OK; ++t) {
-    pcv_query_batch* b = nullptr;
-    rc = pcv_query_batch_run(ctx, sh, trees[t], filter ? ivals.data() : nullptr, nullptr, &b);
-    if (rc == PCV_OK) batches->b.push_back(b);
+  batches->src.reserve(clouds.K);
+  for (uint32_t t = 0; t < clouds.K && rc == PCV_OK; ++t) {
+    XraySource e{};
+    if (clouds.s2) {
+      pcv_s2_cloud* c = clouds.s2[t];
+      pcv_s2_query* q = nullptr;
+      if ((rc = pcv_s2_query_run(c, sh, 0, nullptr, nullptr, filter ? ivals.data() : nullptr, nullptr, &q))) break;
+      batches->s2.push_back(q);
+      e.shape_first = q->location_first.data();
+      e.seg_kept = q->seg_offset.data();
+      e.seg_chunk = q->seg_first_chunk.data();
+      e.chunks.desc = (decltype(e.chunks.desc))q->d_chunks;
+      e.chunks.keep = (decltype(e.chunks.keep))q->d_flags;
+      e.chunks.xyz = (decltype(e.chunks.xyz))c->d_xyz;
+      e.chunks.rgb = (decltype(e.chunks.rgb))c->d_rgb;
+      e.chunks.inten = reads_intensity ? (decltype(e.chunks.inten))c->d_int : nullptr;
+    } else {
+      pcv_octree* tree = clouds.trees[t];
+      pcv_query_batch* b = nullptr;
+      if ((rc = pcv_query_batch_run(ctx, sh, tree, filter ? ivals.data() : nullptr, nullptr, &b))) break;
+      batches->b.push_back(b);
+      e.shape_first = b->shape_first.data();
+      e.seg_kept = b->seg_off.data();
+      e.seg_chunk = b->seg_chunk.data();
+      e.chunks.desc = (decltype(e.chunks.desc))b->d_desc;
+      e.chunks.keep = (decltype(e.chunks.keep))b->d_keep;
+      e.chunks.xyz = (decltype(e.chunks.xyz))tree->d_xyz;
+      e.chunks.rgb = (decltype(e.chunks.rgb))tree->d_rgb;
+      e.chunks.inten = reads_intensity ? (decltype(e.chunks.inten))tree->d_int : nullptr;
+    }
+    batches->src.push_back(e);
   }
   pcv_shapes_free(sh);
   return rc;
 }
 
-// step 2: the created tiles (into x), their groups and, per group, the octrees that have chunks for its shapes, in list
+// step 2: the created tiles (into x), their groups and, per group, the clouds that have chunks for its shapes, in list
 // order, their chunk ranges end to end (u64 prefix)
 struct XrayPlan {
   std::vector<int32_t> created_of_shape;
@@ -1030,13 +1129,13 @@ struct XrayPlan {
   std::vector<size_t> tree_first;  // group g's entries of `trees`: [tree_first[g], tree_first[g + 1])
   std::vector<uint64_t> group_chunks;
 };
-void xray_created_tiles(const std::vector<pcv_query_batch*>& batches, uint32_t S, pcv_xray* x, XrayPlan* pl) {
+void xray_created_tiles(const std::vector<XraySource>& sources, uint32_t S, pcv_xray* x, XrayPlan* pl) {
   // a tile is created iff the queries kept a point (PointStream::callback never delivers an empty batch,
-  // iterator.rs:148-151); kept is the sum over the octrees
+  // iterator.rs:148-151); kept is the sum over the clouds
   pl->created_of_shape.assign(S, -1);
   for (uint32_t s = 0; s < S; ++s) {
     uint64_t k = 0;
-    for (const pcv_query_batch* b : batches) k += b->seg_off[b->shape_first[s + 1]] - b->seg_off[b->shape_first[s]];
+    for (const XraySource& b : sources) k += b.kept(s);
     if (k == 0) continue;
     pl->created_of_shape[s] = (int32_t)x->created.size();
     x->created.push_back(s);
@@ -1045,8 +1144,8 @@ void xray_created_tiles(const std::vector<pcv_query_batch*>& batches, uint32_t S
   x->drawn.assign(x->created.size(), 0);
   x->negative.assign(x->created.size(), 0);
 }
-int xray_plan_tiles(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pcv_xray_params* p, const pcv_xray_coloring* col,
-                           const std::vector<pcv_query_batch*>& batches, bool reads_intensity, const pcv_xray* x, XrayPlan* pl) {
+int xray_plan_tiles(pcv_ctx* ctx, const pcv_xray_params* p, const pcv_xray_coloring* col, const std::vector<XraySource>& sources,
+                    const pcv_xray* x, XrayPlan* pl) {
   char m[256] = {0};
   if (int rc = plan_groups(x->kept.data(), x->created.size(), x->created.data(), x->W, p, col, pl->group_first, &pl->max_pts, &pl->max_tiles, m,
                            sizeof(m)))
@@ -1055,16 +1154,10 @@ int xray_plan_tiles(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pc
   for (size_t gi = 0; gi + 1 < pl->group_first.size(); ++gi) {
     const uint64_t s0 = x->created[pl->group_first[gi]], s1 = x->created[pl->group_first[gi + 1] - 1] + 1;
     uint64_t n = 0;
-    for (uint32_t t = 0; t < K; ++t) {
-      const pcv_query_batch* b = batches[t];
-      const uint64_t c0 = b->seg_chunk[b->shape_first[s0]], c1 = b->seg_chunk[b->shape_first[s1]];
+    for (const XraySource& b : sources) {
+      const uint64_t c0 = b.chunk_of(s0), c1 = b.chunk_of(s1);
       if (c1 == c0) continue;
-      XrayTreeChunks e{};
-      e.desc = (decltype(e.desc))b->d_desc;
-      e.keep = (decltype(e.keep))b->d_keep;
-      e.xyz = (decltype(e.xyz))trees[t]->d_xyz;
-      e.rgb = (decltype(e.rgb))trees[t]->d_rgb;
-      e.inten = reads_intensity ? (decltype(e.inten))trees[t]->d_int : nullptr;
+      XrayTreeChunks e = b.chunks;
       e.c0 = c0;
       e.first = n;
       pl->trees.push_back(e);
@@ -1126,8 +1219,8 @@ int xray_upload_tables(pcv_ctx* ctx, const pcv_xray_params* p, bool binned, cons
 }
 
 // step 4: per tile group count, scan, scatter and accumulate, then the per-tile counters
-int xray_raster_groups(pcv_ctx* ctx, const pcv_xray_params* p, const pcv_xray_coloring* col, bool binned, pcv_xray* x, const XrayPlan& pl,
-                              uint32_t nbx, XrayTables& t) {
+int xray_raster_groups(pcv_ctx* ctx, const pcv_xray_params* p, const pcv_xray_coloring* col, bool binned, bool s2, pcv_xray* x,
+                       const XrayPlan& pl, uint32_t nbx, XrayTables& t) {
   const bool cwi = p->strategy == PCV_XRAY_COLORED_WITH_INTENSITY;
   const uint32_t W = x->W, nblocks = nbx * nbx;
   const uint64_t nc = x->created.size();
@@ -1186,8 +1279,8 @@ int xray_raster_groups(pcv_ctx* ctx, const pcv_xray_params* p, const pcv_xray_co
     PCV_HIP_CHECK(ctx, hipMemsetAsync(t.counts, 0, 4 * nb, ctx->stream));
     {
       PcvProf prof(ctx, PCV_K_XRAY_BIN);
-      hipLaunchKernelGGL(xray_bin_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, ba, t.counts, (const uint64_t*)nullptr,
-                         (uint64_t*)nullptr, (double*)nullptr, (int64_t*)nullptr);
+      hipLaunchKernelGGL((s2 ? xray_bin_kernel<false, true> : xray_bin_kernel<false, false>), dim3(grid), dim3(256), 0, ctx->stream, ba,
+                         t.counts, (const uint64_t*)nullptr, (uint64_t*)nullptr, (double*)nullptr, (int64_t*)nullptr);
     }
     PCV_HIP_CHECK(ctx, hipGetLastError());
     {
@@ -1199,8 +1292,8 @@ int xray_raster_groups(pcv_ctx* ctx, const pcv_xray_params* p, const pcv_xray_co
       PcvProf prof(ctx, PCV_K_XRAY_SCATTER);
       XrayBinArgs bs = ba;
       bs.negative = nullptr;  // counted once, in the count pass
-      hipLaunchKernelGGL(xray_bin_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, bs, t.counts, (const uint64_t*)t.off, t.rec, t.recz,
-                         t.recb);
+      hipLaunchKernelGGL((s2 ? xray_bin_kernel<true, true> : xray_bin_kernel<true, false>), dim3(grid), dim3(256), 0, ctx->stream, bs,
+                         t.counts, (const uint64_t*)t.off, t.rec, t.recz, t.recb);
     }
     PCV_HIP_CHECK(ctx, hipGetLastError());
     aa.nbuckets = (uint32_t)nb;
@@ -1216,13 +1309,13 @@ int xray_raster_groups(pcv_ctx* ctx, const pcv_xray_params* p, const pcv_xray_co
   return PCV_OK;
 }
 
-int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pcv_xray_params* p, const pcv_xray_coloring* col,
-                    pcv_xray* x) {
+int xray_run(pcv_ctx* ctx, const XrayClouds& clouds, const pcv_xray_params* p, const pcv_xray_coloring* col, pcv_xray* x) {
   const bool binned = coloring_binned(p, col);
   const bool sorted = binned || p->strategy == PCV_XRAY_COLORED_WITH_INTENSITY;
   char err[256] = {0};
   double bmin[3], bmax[3];
-  union_box(trees, K, bmin, bmax);
+  if (clouds.s2) union_box(clouds.s2, clouds.K, bmin, bmax);
+  else union_box(clouds.trees, clouds.K, bmin, bmax);
   int rc = leaf_geometry(p->tile_size_px, p->pixel_size_m, bmin, bmax, p->has_query_from_global ? p->query_from_global : nullptr,
                          p->root_level, p->root_index, true, &x->geo, err, sizeof(err));
   if (rc) return ctx->fail(rc, err);
@@ -1232,27 +1325,26 @@ int xray_run(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pcv_xray_
   x->root_index = p->root_index;
   x->bg = p->background == PCV_XRAY_BG_TRANSPARENT ? 0x00ffffffu : 0xffffffffu;  // TRANSPARENT / WHITE .to_u8()
   XrayBatches batches;
-  if ((rc = xray_query_tiles(ctx, trees, K, p, x->geo, &batches))) return rc;
+  if ((rc = xray_query_tiles(ctx, clouds, p, x->geo, sorted, &batches))) return rc;
   XrayPlan pl;
-  xray_created_tiles(batches.b, (uint32_t)x->geo.index.size(), x, &pl);
+  xray_created_tiles(batches.src, (uint32_t)x->geo.index.size(), x, &pl);
   const uint64_t nc = x->created.size();
   if (nc == 0) return PCV_OK;
   PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if ((rc = xray_plan_tiles(ctx, trees, K, p, col, batches.b, sorted, x, &pl))) return rc;
+  if ((rc = xray_plan_tiles(ctx, p, col, batches.src, x, &pl))) return rc;
   if ((rc = ctx->dev_alloc((void**)&x->d_images, 4ull * W * W * nc))) return rc;
   XrayTables t(ctx);
   if ((rc = xray_upload_tables(ctx, p, binned, x, pl, nbx * nbx, &t))) return rc;
-  return xray_raster_groups(ctx, p, col, binned, x, pl, nbx, t);
+  return xray_raster_groups(ctx, p, col, binned, clouds.s2 != nullptr, x, pl, nbx, t);
 }
 
 }  // namespace
 
 // the object of a checked run, or nothing (a failed run frees what it allocated)
-static int xray_new(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t K, const pcv_xray_params* p, const pcv_xray_coloring* col,
-                    pcv_xray** out) {
+static int xray_new(pcv_ctx* ctx, const XrayClouds& clouds, const pcv_xray_params* p, const pcv_xray_coloring* col, pcv_xray** out) {
   pcv_xray* x = new pcv_xray();
   x->ctx = ctx;
-  const int rc = xray_run(ctx, trees, K, p, col, x);
+  const int rc = xray_run(ctx, clouds, p, col, x);
   if (rc != PCV_OK) {
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipGetLastError();
@@ -1311,11 +1403,16 @@ extern "C" int pcv_xray_run(pcv_ctx* ctx, pcv_octree* tree, const pcv_xray_param
   char err[256] = {0};
   const int vrc = pcv_xray_check_params(p, tree->has_intensity ? 1 : 0, err, sizeof(err));
   if (vrc) return ctx->fail(vrc, err);
-  return xray_new(ctx, &tree, 1, p, nullptr, out);
+  XrayClouds clouds;
+  clouds.trees = &tree;
+  clouds.K = 1;
+  return xray_new(ctx, clouds, p, nullptr, out);
 }
 
-// pcv_xray_run_many (ex = false: colored_with_intensity refused, coloring ignored) and pcv_xray_run_ex
-static int xray_run_checked(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t num_trees, const pcv_xray_params* p,
+// pcv_xray_run_many (ex = false: colored_with_intensity refused, coloring ignored), pcv_xray_run_ex and pcv_xray_run_s2:
+// `what` names the kind of cloud in messages; a cloud without a context of its own is a host-only S2 cloud
+template <class Cloud>
+static int xray_run_checked(pcv_ctx* ctx, Cloud* const* trees, uint32_t num_trees, const char* what, const pcv_xray_params* p,
                             const pcv_xray_coloring* col, bool ex, pcv_xray** out) {
   if (!ctx) return PCV_E_INVALID;
   if (!p || !out) return ctx->fail(PCV_E_INVALID, "null argument");
@@ -1324,31 +1421,43 @@ static int xray_run_checked(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t num
   if (num_trees == 0) return ctx->fail(PCV_E_INVALID, "xray: No locations specified for point cloud client.");
   if (!trees) return ctx->fail(PCV_E_INVALID, "null argument");
   if (num_trees > PCV_XRAY_MAX_TREES)
-    return ctx->fail(PCV_E_INVALID, "xray: " + std::to_string(num_trees) + " octrees, more than PCV_XRAY_MAX_TREES (" +
+    return ctx->fail(PCV_E_INVALID, "xray: " + std::to_string(num_trees) + " " + what + "s, more than PCV_XRAY_MAX_TREES (" +
                                         std::to_string(PCV_XRAY_MAX_TREES) + ")");
   char err[256] = {0};
   int vrc = ex ? pcv_xray_check_params_ex(p, col, 1, err, sizeof(err)) : pcv_xray_check_params(p, 1, err, sizeof(err));
   if (vrc) return ctx->fail(vrc, err);
   for (uint32_t t = 0; t < num_trees; ++t) {
-    const std::string which = "xray: octree " + std::to_string(t);
+    const std::string which = std::string("xray: ") + what + " " + std::to_string(t);
     if (!trees[t]) return ctx->fail(PCV_E_INVALID, which + " is null");
+    if (!trees[t]->ctx) return ctx->fail(PCV_E_INVALID, which + " was opened without a context and has no device");
     if (trees[t]->ctx != ctx) return ctx->fail(PCV_E_INVALID, which + " belongs to another context");
     if (p->interval_attribute && !trees[t]->has_intensity)
       return ctx->fail(PCV_E_INVALID, which + " has no intensity attribute to filter on");
     if (ex && coloring_needs_intensity(p, col) && !trees[t]->has_intensity)
       return ctx->fail(PCV_E_INVALID, which + " has no intensity attribute to color or bin by");
   }
-  return xray_new(ctx, trees, num_trees, p, ex ? col : nullptr, out);
+  XrayClouds clouds;
+  if constexpr (std::is_same<Cloud, pcv_s2_cloud>::value) clouds.s2 = trees;
+  else clouds.trees = trees;
+  clouds.K = num_trees;
+  return xray_new(ctx, clouds, p, ex ? col : nullptr, out);
 }
 
 extern "C" int pcv_xray_run_many(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t num_trees, const pcv_xray_params* p, pcv_xray** out) {
-  return xray_run_checked(ctx, trees, num_trees, p, nullptr, false, out);
+  return xray_run_checked(ctx, trees, num_trees, "octree", p, nullptr, false, out);
 }
 
 extern "C" int pcv_xray_run_ex(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t num_trees, const pcv_xray_params* p,
                                const pcv_xray_coloring* coloring, pcv_xray** out) {
-  if (!coloring) return xray_run_checked(ctx, trees, num_trees, p, nullptr, false, out);
-  return xray_run_checked(ctx, trees, num_trees, p, coloring, true, out);
+  if (!coloring) return xray_run_checked(ctx, trees, num_trees, "octree", p, nullptr, false, out);
+  return xray_run_checked(ctx, trees, num_trees, "octree", p, coloring, true, out);
+}
+
+// build_xray_quadtree's leaf level over S2 cell clouds (PointClouds::S2Cells, point_cloud_client/src/lib.rs:120-131): the
+// same run with every tile's points from pcv_s2_query_run's machinery
+extern "C" int pcv_xray_run_s2(pcv_ctx* ctx, pcv_s2_cloud* const* clouds, uint32_t num_clouds, const pcv_xray_params* p,
+                               const pcv_xray_coloring* coloring, pcv_xray** out) {
+  return xray_run_checked(ctx, clouds, num_clouds, "S2 cloud", p, coloring, coloring != nullptr, out);
 }
 
 extern "C" int pcv_xray_negative(const pcv_xray* x, uint64_t* negative) {

@@ -283,10 +283,17 @@ class Context:
                    binning=None):
         """OctreeResult.xray_tiles (same keywords) over several octrees of this context, as build_xray_quadtree with several
         point_cloud_locations (pcv_xray_run_many, or pcv_xray_run_ex with colored_with_intensity or binning): the union of
-        their bounding boxes, every tile's points from all of them. Returns an XrayTiles."""
+        their bounding boxes, every tile's points from all of them. `trees` may instead be a list of S2Cloud
+        (pcv_xray_run_s2); a list that mixes the two kinds raises ValueError. Returns an XrayTiles."""
         trees = list(trees)
         if not trees:
             raise ValueError("xray_tiles: no octrees given")
+        s2 = [isinstance(t, S2Cloud) for t in trees]
+        if any(s2) and not all(s2):
+            raise ValueError("xray_tiles: a list of octrees or a list of S2 cell clouds, not a mix of both")
+        if all(s2):
+            return self._xray_tiles_s2(trees, tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background,
+                                       root_node_id, max_workspace_bytes, min_intensity, max_intensity, binning)
         p = xray_params(tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background, root_node_id,
                         max_workspace_bytes)
         col = xray_coloring(strategy, min_intensity, max_intensity, binning)
@@ -298,11 +305,24 @@ class Context:
             self._check(self.lib.pcv_xray_run_ex(self.handle, arr, len(trees), C.byref(p), C.byref(col), C.byref(h)))
         return XrayTiles(self, h, int(tile_size_px))
 
+    def _xray_tiles_s2(self, clouds, tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background,
+                       root_node_id, max_workspace_bytes, min_intensity, max_intensity, binning):
+        for c in clouds:
+            c._alive()
+        p = xray_params(tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background, root_node_id,
+                        max_workspace_bytes)
+        col = xray_coloring(strategy, min_intensity, max_intensity, binning)
+        arr = (C.c_void_p * len(clouds))(*[c.handle for c in clouds])
+        h = C.c_void_p()
+        self._check(self.lib.pcv_xray_run_s2(self.handle, arr, len(clouds), C.byref(p), C.byref(col) if col is not None else None,
+                                             C.byref(h)))
+        return XrayTiles(self, h, int(tile_size_px))
+
     def xray_quadtree(self, trees, tile_size_px=256, pixel_size_m=None, strategy="xray", query_from_global=None,
                       intensity_interval=None, background="white", root_node_id="r", max_workspace_bytes=None, min_intensity=0.0,
                       max_intensity=1.0, binning=None, output_directory=None, png="stored"):
-        """xray_tiles over several octrees (same arguments) with every level above the leaves built on the device; with
-        output_directory the quadtree is also written there (XrayTiles.write, PNGs as `png` says)."""
+        """xray_tiles over several octrees, or several S2 cell clouds (same arguments), with every level above the leaves
+        built on the device; with output_directory the quadtree is also written there (XrayTiles.write, PNGs as `png` says)."""
         xt = self.xray_tiles(trees, tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background,
                              root_node_id, max_workspace_bytes, min_intensity, max_intensity, binning)
         xt.build_parents()
@@ -2088,6 +2108,29 @@ class S2Cloud:
                                               flat.ctypes.data, iv, used, C.byref(h)))
         return S2QueryBatch(self, h, locations)
 
+    def xray_tiles(self, tile_size_px=256, pixel_size_m=None, strategy="xray", query_from_global=None, intensity_interval=None,
+                   background="white", root_node_id="r", max_workspace_bytes=None, min_intensity=0.0, max_intensity=1.0,
+                   binning=None):
+        """OctreeResult.xray_tiles (same keywords) over this S2 cell cloud (pcv_xray_run_s2): every leaf tile's points are
+        those of the cells that cells_in_location lists for the tile's shape, filtered as query_batch filters them.
+        Returns an XrayTiles that does not depend on the cloud."""
+        if self.ctx is None:
+            raise ValueError("xray_tiles: this S2 cell cloud was opened without a context (s2_open_host) and has no device")
+        return self.ctx.xray_tiles([self], tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background,
+                                   root_node_id, max_workspace_bytes, min_intensity, max_intensity, binning)
+
+    def xray_quadtree(self, tile_size_px=256, pixel_size_m=None, strategy="xray", query_from_global=None, intensity_interval=None,
+                      background="white", root_node_id="r", max_workspace_bytes=None, min_intensity=0.0, max_intensity=1.0,
+                      binning=None, output_directory=None, png="stored"):
+        """xray_tiles (same arguments) with every level above the leaves built on the device, written to output_directory
+        when one is given (OctreeResult.xray_quadtree)."""
+        xt = self.xray_tiles(tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background, root_node_id,
+                             max_workspace_bytes, min_intensity, max_intensity, binning)
+        xt.build_parents()
+        if output_directory is not None:
+            xt.write(output_directory, png=png)
+        return xt
+
     def write(self, directory):
         """<token>.xyz/.rgb[/.intensity] per cell + meta.pb (pcv_s2_write_dir)."""
         self._alive()
@@ -2225,6 +2268,34 @@ def s2_open_host(directory):
     h = C.c_void_p()
     _host_check(L.load_library().pcv_s2_open_dir(None, os.fsencode(str(directory)), C.byref(h)), "pcv_s2_open_dir")
     return S2Cloud(None, h)
+
+
+def cloud_kind(directory):
+    """"octree" or "s2": how PointCloudClientBuilder::build (point_cloud_client/src/lib.rs:107-132) would open this
+    directory, by its meta.pb (pcv_cloud_kind; host only). A missing or unreadable meta.pb raises PcvError (PCV_E_IO)."""
+    kind = C.c_int()
+    _host_check(L.load_library().pcv_cloud_kind(os.fsencode(str(directory)), C.byref(kind)), "pcv_cloud_kind")
+    return "s2" if kind.value == L.CLOUD_S2 else "octree"
+
+
+def build_xray_quadtree(ctx, point_cloud_locations, output_directory, tile_size_px=256, pixel_size_m=None, strategy="xray",
+                        query_from_global=None, intensity_interval=None, background="white", root_node_id="r",
+                        max_workspace_bytes=None, min_intensity=0.0, max_intensity=1.0, binning=None, png="stored"):
+    """The reference's build_xray_quadtree binary over directories: the kind of the first one (cloud_kind) decides, every
+    directory is opened as that kind (one of the other kind fails with the opener's own message), leaves and parents are
+    built on the device and the quadtree is written to output_directory. Returns the XrayTiles."""
+    locations = list(point_cloud_locations)
+    if not locations:
+        raise ValueError("No locations specified for point cloud client.")
+    opener = ctx.s2_open if cloud_kind(locations[0]) == "s2" else ctx.open_dir
+    clouds = [opener(d) for d in locations]
+    try:
+        return ctx.xray_quadtree(clouds, tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background,
+                                 root_node_id, max_workspace_bytes, min_intensity, max_intensity, binning,
+                                 output_directory=output_directory, png=png)
+    finally:
+        for c in clouds:
+            c.free()
 
 
 def build_s2_cells(output_directory, points, split_level=20, ctx=None):

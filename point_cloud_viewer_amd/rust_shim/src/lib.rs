@@ -832,6 +832,39 @@ pub struct pcv_s2_query {
     _private: [u8; 0],
 }
 
+/// pcv_xray_params / pcv_xray_coloring of include/pcv_hip.h, field for field.
+#[repr(C)]
+pub struct PcvXrayParams {
+    pub tile_size_px: u32,
+    pub strategy: u32,
+    pub colormap: u32,
+    pub background: u32,
+    pub pixel_size_m: c_double,
+    pub max_stddev: c_float,
+    pub root_level: u32,
+    pub root_index: u64,
+    pub has_query_from_global: i32,
+    pub reserved: i32,
+    pub query_from_global: [c_double; 7],
+    pub interval_attribute: *const c_char,
+    pub interval: [c_double; 2],
+    pub max_workspace_bytes: u64,
+}
+#[repr(C)]
+pub struct PcvXrayColoring {
+    pub min_intensity: c_float,
+    pub max_intensity: c_float,
+    pub binning_attribute: *const c_char,
+    pub bin_size: c_double,
+}
+
+extern "C" {
+    fn pcv_xray_run_s2(ctx: *mut pcv_ctx, clouds: *const *mut pcv_s2_cloud, num_clouds: u32, params: *const PcvXrayParams, coloring: *const PcvXrayColoring, out: *mut *mut PcvXray) -> c_int;
+    fn pcv_xray_build_parents(x: *mut PcvXray) -> c_int;
+    /// PointCloudClientBuilder::build's choice for a directory (0: octree, 1: S2 cells), by its meta.pb
+    pub fn pcv_cloud_kind(directory: *const c_char, kind: *mut c_int) -> c_int;
+}
+
 /// An S2 cell cloud on disk served by the GPU library. The reference `S2Cells` is kept alongside for `points_in_node` (a plain
 /// `NodeIterator` over one cell's files) and for intervals on attributes other than intensity.
 pub struct HipS2Cells {
@@ -882,6 +915,32 @@ impl HipS2Cells {
         }
         idx.truncate(count as usize);
         idx
+    }
+
+    /// `build_xray_quadtree` over this cloud (PointClouds::S2Cells, point_cloud_client/src/lib.rs:120-131): the leaf tiles
+    /// rasterised on the device from the S2 query's candidates (pcv_xray_run_s2), the parents built, the quadtree written to
+    /// `output_directory`. `coloring` is needed by colored_with_intensity and binning, as for pcv_xray_run_ex. Several
+    /// clouds of one context go through pcv_xray_run_s2 in one call; this veneer holds one.
+    pub fn build_xray_quadtree(&self, params: &PcvXrayParams, coloring: Option<&PcvXrayColoring>, output_directory: &Path, deflate: bool) -> Result<()> {
+        use std::os::unix::ffi::OsStrExt;
+        let _guard = self.lock.lock().unwrap();
+        let dir = CString::new(output_directory.as_os_str().as_bytes()).expect("path with a NUL byte");
+        let clouds = [self.cloud];
+        let mut x = std::ptr::null_mut();
+        let mut rc = unsafe { pcv_xray_run_s2(self.ctx.0, clouds.as_ptr(), 1, params, coloring.map_or(std::ptr::null(), |c| c as *const _), &mut x) };
+        if rc == 0 {
+            rc = unsafe { pcv_xray_build_parents(x) };
+        }
+        if rc == 0 {
+            rc = unsafe { pcv_xray_write_dir_ex(x, dir.as_ptr(), deflate as i32) };
+        }
+        let message = if rc == 0 { String::new() } else { unsafe { CStr::from_ptr(pcv_last_error(self.ctx.0)) }.to_string_lossy().into_owned() };
+        unsafe { pcv_xray_free(x) };
+        if rc == 0 {
+            Ok(())
+        } else {
+            Err(ErrorKind::InvalidInput(message).into())
+        }
     }
 
     fn sorted_union(location: &PointLocation) -> Option<Vec<u64>> {
