@@ -43,6 +43,13 @@ PCV_SA(sizeof(pcv_split_node) == 56 && offsetof(pcv_split_node, first) == 16 && 
            offsetof(pcv_split_node, is_leaf) == 48,
        "pcv_split_node");
 PCV_SA(sizeof(pcv_promote_node) == 24 && offsetof(pcv_promote_node, child_offset) == 16, "pcv_promote_node");
+PCV_SA(sizeof(pcv_sort_records_args) == 160 && offsetof(pcv_sort_records_args, planes) == 24 &&
+           offsetof(pcv_sort_records_args, plane0_in) == 88 && offsetof(pcv_sort_records_args, rows) == 112 &&
+           offsetof(pcv_sort_records_args, key_bits) == 120 && offsetof(pcv_sort_records_args, flags) == 152,
+       "pcv_sort_records_args");
+PCV_SA(sizeof(pcv_sort_pass_info) == 40 && offsetof(pcv_sort_pass_info, dyn_lds) == 32, "pcv_sort_pass_info");
+PCV_SA(sizeof(pcv_sort_plan_info) == 360 && offsetof(pcv_sort_plan_info, chunk) == 32 && offsetof(pcv_sort_plan_info, pass) == 40,
+       "pcv_sort_plan_info");
 
 PCV_SA(sizeof(pcv_ooc_stats) == 120, "pcv_ooc_stats");
 PCV_SA(offsetof(pcv_ooc_stats, spill_bytes) == 32 && offsetof(pcv_ooc_stats, h2d_ms) == 56 && offsetof(pcv_ooc_stats, write_ms) == 104 &&

@@ -485,6 +485,77 @@ int pcv_sort_keys32(pcv_ctx* ctx, uint32_t* keys, uint64_t n, int begin_bit, int
 int pcv_sort_pairs32(pcv_ctx* ctx, uint32_t* keys, uint32_t* values, uint64_t n, int begin_bit, int end_bit,
                      int mem);
 
+/* K3: the stable record sort of the build (leaf rank -> records), on its own. `keys` (n words), the payload and the planes
+ * are sorted in place by the rank field of the key; everything else in a record only travels.
+ *   record formats
+ *     vec_bytes 0:  key + nwords planes (1..8).
+ *     vec_bytes 16: key + one 16-byte payload (`vec`: n x 4 words) + nwords planes (0..8): the 20-byte records.
+ *     vec_bytes 8:  key = rank << 8 | blue, one 8-byte payload (`vec`: n x 2 words; red | green << 8 in the upper half of the
+ *                   second word) + nwords planes (0..8): the 12-byte records of the single-chain build. With at most one
+ *                   plane they take the 12-byte record kernels (tiles of 8 192), otherwise the generic ones.
+ *   the rank field: bits [8, 8 + key_bits) of the key with vec_bytes 8 (key_bits <= 24), bits [0, key_bits) otherwise
+ *     (key_bits <= 32); key_bits >= 1.
+ *   map (map_entries words, or null): the keys carry PREDICTED ranks < map_entries (needs a payload: vec_bytes 8 or 16); the
+ *     sort's first pass replaces each by map[rank] & 0x3fffffff, which must be < 2^key_bits, and where map[rank] has bit 30 set
+ *     (the replay mark) the record's first payload word becomes its input index. A map of <= 16 384 entries (10 000 / 5 000
+ *     with a plane and digits of <= 7 / 8 bits) travels as half words in LDS when rows are given: key_bits <= 15 then.
+ *   rows (map, 12-byte records with at most one plane): per sort workgroup g of pcv_sort_rec12_geometry the number of keys
+ *     of chunk g with predicted rank b, rows[g * map_entries + b]. PCV_SORT_ROWS_GIVEN: the caller's, groups x map_entries
+ *     words; PCV_SORT_ROWS_DEVICE: counted on the device as the build does, and copied to `rows` where that is not null.
+ *   plane0_in (nwords >= 1, or null): the first pass reads plane 0 from this array, which is left as it is; planes[0]
+ *     only receives the sorted plane.
+ *   color_in (rows, or null): the keys arrive as rank << 8 and the upper half of the payload's second word empty; the first
+ *     pass reads red, green, blue of record i at color_in + i * color_stride (3 or 4; n * color_stride bytes in all).
+ *   hold_second: the sort gets a place to hold its second pass back in (the two-pass rows form does), and the entry then runs
+ *     that pass in its plain form, as pcv_build_finish does for leaves the pass does not settle itself.
+ *   flags & PCV_SORT_RECORDS_CHECK_KEYS: every predicted rank is compared with map_entries first (a pass of its own; a
+ *     device array is copied to the host for it). Without it a rank outside the map reads outside the map.
+ * `plan` (nullable) receives what the sort launched: the values of PcvSortHist / PcvSortDown of csrc/pcv_sort_plan.h.
+ * PCV_E_INVALID (nothing is touched): null arrays, nwords > 8, a shape outside the list above, what the plan refuses. */
+#define PCV_SORT_ROWS_NONE 0
+#define PCV_SORT_ROWS_GIVEN 1
+#define PCV_SORT_ROWS_DEVICE 2
+#define PCV_SORT_RECORDS_CHECK_KEYS 1u
+typedef struct pcv_sort_records_args {
+  uint64_t n;
+  uint32_t* keys;
+  void* vec;
+  uint32_t* planes[8];
+  const uint32_t* plane0_in;
+  const uint8_t* color_in;
+  const uint32_t* map;
+  uint32_t* rows;
+  int32_t key_bits;
+  int32_t vec_bytes;
+  int32_t nwords;
+  uint32_t color_stride;
+  uint32_t map_entries;
+  int32_t rows_mode;
+  int32_t hold_second;
+  int32_t mem;
+  uint32_t flags;
+  uint32_t reserved;
+} pcv_sort_records_args;
+typedef struct pcv_sort_pass_info {
+  int32_t shift, nbits;
+  int32_t hist, down;   /* PcvSortHist, PcvSortDown */
+  int32_t R, MAP, PL;   /* 12-byte record kernels: digit values, the map's place (0 none, 1 LDS, 2 global memory), the plane */
+  int32_t map_lds;      /* a counting pass that applies the map: the map in LDS */
+  uint64_t dyn_lds;
+} pcv_sort_pass_info;
+typedef struct pcv_sort_plan_info {
+  int32_t npasses;
+  int32_t two_pass, held_back; /* the two-pass rows form; its second pass was left to the caller of the sort */
+  int32_t pieces, blocks, gpb;
+  int32_t groups;              /* geom.groups, geom.chunk */
+  int32_t second_ran;          /* the entry ran the held-back pass */
+  uint64_t chunk;
+  pcv_sort_pass_info pass[8];
+} pcv_sort_plan_info;
+int pcv_sort_records(pcv_ctx* ctx, const pcv_sort_records_args* args, pcv_sort_plan_info* plan);
+/* groups and chunk of the 12-byte record sort of n records (the shape of `rows`). */
+void pcv_sort_records_geometry(uint64_t n, int32_t* groups, uint64_t* chunk);
+
 /* Device self-test of the exact constant-divisor division used by the chain kernels (see pcv_chain_dev.h):
  * compares it bit-for-bit with IEEE f64 division for every integer code / 255 and / 65535 and for
  * samples_per_divisor pseudo-random numerators per divisor; *mismatches must come back 0. */

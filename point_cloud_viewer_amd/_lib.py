@@ -140,6 +140,28 @@ class NodeInfo(C.Structure):
                 ("xyz_offset", C.c_uint64), ("point_offset", C.c_uint64)]
 
 
+SORT_ROWS_NONE, SORT_ROWS_GIVEN, SORT_ROWS_DEVICE = 0, 1, 2  # PCV_SORT_ROWS_*
+SORT_RECORDS_CHECK_KEYS = 1  # PCV_SORT_RECORDS_CHECK_KEYS
+
+
+class SortRecordsArgs(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("keys", C.c_void_p), ("vec", C.c_void_p), ("planes", C.c_void_p * 8), ("plane0_in", C.c_void_p),
+                ("color_in", C.c_void_p), ("map", C.c_void_p), ("rows", C.c_void_p), ("key_bits", C.c_int32), ("vec_bytes", C.c_int32),
+                ("nwords", C.c_int32), ("color_stride", C.c_uint32), ("map_entries", C.c_uint32), ("rows_mode", C.c_int32),
+                ("hold_second", C.c_int32), ("mem", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SortPassInfo(C.Structure):
+    _fields_ = [("shift", C.c_int32), ("nbits", C.c_int32), ("hist", C.c_int32), ("down", C.c_int32), ("R", C.c_int32),
+                ("MAP", C.c_int32), ("PL", C.c_int32), ("map_lds", C.c_int32), ("dyn_lds", C.c_uint64)]
+
+
+class SortPlanInfo(C.Structure):
+    _fields_ = [("npasses", C.c_int32), ("two_pass", C.c_int32), ("held_back", C.c_int32), ("pieces", C.c_int32),
+                ("blocks", C.c_int32), ("gpb", C.c_int32), ("groups", C.c_int32), ("second_ran", C.c_int32), ("chunk", C.c_uint64),
+                ("passes", SortPassInfo * 8)]
+
+
 class OocStats(C.Structure):
     _fields_ = [("points", C.c_uint64), ("nodes", C.c_uint64), ("partitions", C.c_uint64), ("largest_bucket", C.c_uint64),
                 ("spill_bytes", C.c_uint64), ("h2d_bytes", C.c_uint64), ("d2h_bytes", C.c_uint64), ("h2d_ms", C.c_double),
@@ -225,6 +247,8 @@ _SIGNATURES = {
     "pcv_sort_keys64": (C.c_int, [_vp, _vp, C.c_uint64, C.c_int, C.c_int, C.c_int]),
     "pcv_sort_keys32": (C.c_int, [_vp, _vp, C.c_uint64, C.c_int, C.c_int, C.c_int]),
     "pcv_sort_pairs32": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_int, C.c_int, C.c_int]),
+    "pcv_sort_records": (C.c_int, [_vp, C.POINTER(SortRecordsArgs), C.POINTER(SortPlanInfo)]),
+    "pcv_sort_records_geometry": (None, [C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     "pcv_selftest_division": (C.c_int, [_vp, C.POINTER(C.c_double), C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pcv_ply_read": (C.c_int, [C.c_char_p, C.POINTER(_vp), C.c_char_p, C.c_uint64]),
     "pcv_ply_num_points": (C.c_uint64, [_vp]),

@@ -2,9 +2,11 @@
 // its own, for tests and for callers that hold the intermediate arrays themselves. Host code only.
 #include <algorithm>
 #include <cstring>
+#include <vector>
 
 #include "pcv_build_state.h"
 #include "pcv_internal.h"
+#include "pcv_sort_records_check.h"
 #include "pcv_tables.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -93,6 +95,121 @@ extern "C" int pcv_sort_pairs32(pcv_ctx* ctx, uint32_t* keys, uint32_t* values, 
                                 int mem) {
   if (ctx && !values) return ctx->fail(PCV_E_INVALID, "values is null");
   return sort_api<uint32_t>(ctx, keys, values, n, begin_bit, end_bit, mem);
+}
+
+// The build's record sort on the caller's arrays: the payload set up as pcv_queue_record_sort sets it up, the rows counted as
+// count_and_queue_sort counts them, the sort and its held-back second pass called as the build calls them. The checks and the
+// plan handed back are pcv_sort_records_check.cpp's (host only).
+extern "C" int pcv_sort_records(pcv_ctx* ctx, const pcv_sort_records_args* args, pcv_sort_plan_info* plan_out) {
+  if (!ctx) return PCV_E_INVALID;
+  PcvSortRecordsSwitches sw;
+  sw.sort_rows2 = pcv_switches().sort_rows2, sw.sort_msd = pcv_switches().sort_msd, sw.rows_true_bins = pcv_switches().rows_true_bins;
+  PcvSortFacts facts;
+  PcvSortPlan plan;
+  if (const char* why = pcv_sort_records_check(args, sw, &facts, &plan)) return ctx->fail(PCV_E_INVALID, why);
+  const pcv_sort_records_args& a = *args;
+  const uint64_t n = a.n;
+  const bool host = a.mem == PCV_MEM_HOST;
+  if (n && a.map && (a.flags & PCV_SORT_RECORDS_CHECK_KEYS)) {
+    std::vector<uint32_t> copy;
+    const uint32_t* hk = a.keys;
+    if (!host) {
+      copy.resize(n);
+      PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+      PCV_HIP_CHECK(ctx, hipMemcpy(copy.data(), a.keys, n * 4, hipMemcpyDeviceToHost));
+      hk = copy.data();
+    }
+    if (const char* why = pcv_sort_records_check_keys(hk, n, a.vec_bytes, a.map_entries)) return ctx->fail(PCV_E_INVALID, why);
+  }
+  if (plan_out) pcv_sort_records_plan_info(plan, plan_out);
+  if (n == 0) return PCV_OK;
+  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+  const hipMemcpyKind outk = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  PcvScratch sc(ctx);
+  int rc;
+  // a host array on the device in an allocation of its own; a device array is read where it lies
+  auto staged = [&](const void* src, size_t bytes, const void** dev) -> int {
+    *dev = src;
+    if (!host || !src) return PCV_OK;
+    uint8_t* d;
+    if (int r = sc.get(&d, bytes)) return r;
+    if (hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, st) != hipSuccess) return ctx->fail(PCV_E_HIP, "pcv_sort_records: upload");
+    *dev = d;
+    return PCV_OK;
+  };
+  uint32_t *ka, *kb;
+  if ((rc = sc.get(&ka, n)) || (rc = sc.get(&kb, n))) return rc;
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(ka, a.keys, n * 4, in, st));
+  PcvSortPayload pl;
+  const size_t vec_bytes = (size_t)a.vec_bytes;
+  if (vec_bytes) {
+    uint8_t *va, *vb;
+    if ((rc = sc.get(&va, n * vec_bytes)) || (rc = sc.get(&vb, n * vec_bytes))) return rc;
+    PCV_HIP_CHECK(ctx, hipMemcpyAsync(va, a.vec, n * vec_bytes, in, st));
+    pl.vec_in = va, pl.vec_out = vb, pl.vec_bytes = a.vec_bytes;
+  }
+  pl.nwords = a.nwords;
+  for (int w = 0; w < a.nwords; ++w) {
+    if ((rc = sc.get(&pl.in[w], n)) || (rc = sc.get(&pl.out[w], n))) return rc;
+    if (w == 0 && a.plane0_in) continue;  // (the first pass reads the caller's array)
+    PCV_HIP_CHECK(ctx, hipMemcpyAsync(pl.in[w], a.planes[w], n * 4, in, st));
+  }
+  const void* dev;
+  if ((rc = staged(a.plane0_in, n * 4, &dev))) return rc;
+  pl.first_in0 = (const uint32_t*)dev;
+  if ((rc = staged(a.color_in, n * a.color_stride, &dev))) return rc;
+  pl.color_in = (const uint8_t*)dev, pl.color_stride = a.color_in ? a.color_stride : 3;
+  if ((rc = staged(a.map, (size_t)a.map_entries * 4, &dev))) return rc;
+  const uint32_t* map = (const uint32_t*)dev;
+  const uint32_t* rows = nullptr;
+  const size_t rows_words = (size_t)plan.geom.groups * a.map_entries;
+  if (a.rows_mode == PCV_SORT_ROWS_GIVEN) {
+    if ((rc = staged(a.rows, rows_words * 4, &dev))) return rc;
+    rows = (const uint32_t*)dev;
+  } else if (a.rows_mode == PCV_SORT_ROWS_DEVICE) {
+    int sgroups;
+    uint64_t schunk;
+    pcv_sort_rec12_geometry(n, &sgroups, &schunk);
+    uint32_t *counted, *counts;
+    if ((rc = sc.get(&counted, rows_words)) || (rc = sc.get(&counts, a.map_entries))) return rc;
+    PCV_HIP_CHECK(ctx, hipMemsetAsync(counts, 0, (size_t)a.map_entries * 4, st));
+    pcv_launch_rank_hist_rows(ctx, ka, n, a.map_entries, counts, 8, sgroups, schunk, counted);
+    PCV_HIP_CHECK(ctx, hipGetLastError());
+    if (a.rows) PCV_HIP_CHECK(ctx, hipMemcpyAsync(a.rows, counted, rows_words * 4, outk, st));
+    rows = counted;
+  }
+  void* scratch;
+  if ((rc = ctx->dev_alloc(&scratch, pcv_sort_scratch_bytes(n)))) return rc;
+  sc.ptrs.push_back(scratch);
+  bool in_a = true;
+  PcvSortSecond second;
+  if (map) {
+    rc = pcv_radix_sort_records_mapped(ctx, ka, kb, n, a.key_bits, &pl, scratch, map, a.map_entries, &in_a, rows,
+                                       a.hold_second ? &second : nullptr);
+    if (rc == PCV_OK && second.pending) {
+      if (plan_out) plan_out->second_ran = 1;
+      rc = pcv_radix_sort_records_second(ctx, &second, nullptr);
+    }
+  } else {
+    rc = pcv_radix_sort_u32(ctx, ka, kb, n, facts.begin_bit, facts.end_bit, &pl, scratch, &in_a);
+  }
+  if (rc) {
+    (void)hipStreamSynchronize(st);  // (the arrays of `sc` are released on return)
+    return rc;
+  }
+  PCV_HIP_CHECK(ctx, hipMemcpyAsync(a.keys, in_a ? ka : kb, n * 4, outk, st));
+  if (vec_bytes) PCV_HIP_CHECK(ctx, hipMemcpyAsync(a.vec, in_a ? pl.vec_in : pl.vec_out, n * vec_bytes, outk, st));
+  for (int w = 0; w < a.nwords; ++w) PCV_HIP_CHECK(ctx, hipMemcpyAsync(a.planes[w], in_a ? pl.in[w] : pl.out[w], n * 4, outk, st));
+  PCV_HIP_CHECK(ctx, hipStreamSynchronize(st));
+  return PCV_OK;
+}
+
+extern "C" void pcv_sort_records_geometry(uint64_t n, int32_t* groups, uint64_t* chunk) {
+  int g;
+  pcv_sort_rec12_geometry(n, &g, chunk);
+  *groups = g;
 }
 
 // ------------------------------------------------------------------------------------------------

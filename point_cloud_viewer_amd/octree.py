@@ -605,6 +605,60 @@ class Context:
                                               L.MEM_DEVICE if k.device else L.MEM_HOST))
         return k.keep, v.keep
 
+    def sort_records(self, keys, key_bits, vec=None, planes=(), plane0_in=None, color_in=None, color_stride=3, map=None, rows=None,
+                     hold_second=False, check_keys=True):
+        """The build's stable record sort on its own (pcv_sort_records), in place: u32 keys, a payload `vec` of shape (n, 2) (12-byte
+        records: the rank sits above a colour byte) or (n, 4) words or none, and up to 8 planes of words; all numpy arrays or all
+        device tensors. plane0_in: plane 0 is read from this array, which is left as it is (planes[0] receives the sorted plane).
+        rows: None, "device" (counted on the device and returned) or the rank counts per sort workgroup, shape (groups, len(map)).
+        Returns (keys, vec, planes, rows, plan): the sorted arrays, the rows the device counted (or None) and the plan the sort
+        ran as a dict (the fields of pcv_sort_plan_info)."""
+        k = _Buf(keys, np.uint32, "keys")
+        v = _Buf(vec, np.uint32, "vec")
+        pls = [_Buf(p, np.uint32, "plane") for p in planes]
+        p0, m = _Buf(plane0_in, np.uint32, "plane0_in"), _Buf(map, np.uint32, "map")
+        col = _Buf(color_in, np.uint8, "color_in")
+        counted = isinstance(rows, str)
+        if counted and rows != "device":
+            raise ValueError('rows: None, "device" or an array')
+        a = L.SortRecordsArgs()
+        a.n, a.key_bits, a.nwords = k.size, key_bits, len(pls)
+        a.vec_bytes = 0 if vec is None else 4 * int(vec.shape[-1]) if len(vec.shape) == 2 else -1
+        if len(pls) > 8:
+            raise ValueError("at most 8 planes")
+        groups, chunk = C.c_int32(), C.c_uint64()
+        self.lib.pcv_sort_records_geometry(k.size, C.byref(groups), C.byref(chunk))
+        if counted:
+            shape = (groups.value, m.size)
+            if k.device:
+                import torch
+                rows = torch.zeros(shape, dtype=torch.int32, device=keys.device)
+            else:
+                rows = np.zeros(shape, dtype=np.uint32)
+        r = _Buf(rows, np.uint32, "rows")
+        bufs = [b for b in [k, v, p0, m, col, r] + pls if b.keep is not None]
+        if any(b.size != k.size for b in pls + ([p0] if plane0_in is not None else [])) or (vec is not None and v.size * 4 != k.size * a.vec_bytes):
+            raise ValueError("payload and planes must have one row per key")
+        if any(bool(b.device) != bool(k.device) for b in bufs):
+            raise ValueError("all arrays in host memory or all on the device")
+        if color_in is not None and col.size != k.size * color_stride:
+            raise ValueError("color_in must hold n * color_stride bytes")
+        if rows is not None and map is not None and r.size != groups.value * m.size:
+            raise ValueError("rows must hold groups x len(map) words")
+        a.keys, a.vec, a.plane0_in, a.color_in, a.map, a.rows = k.ptr, v.ptr, p0.ptr, col.ptr, m.ptr, r.ptr
+        for w, b in enumerate(pls):
+            a.planes[w] = b.ptr
+        a.color_stride, a.map_entries = color_stride, m.size
+        a.rows_mode = L.SORT_ROWS_NONE if rows is None else L.SORT_ROWS_DEVICE if counted else L.SORT_ROWS_GIVEN
+        a.hold_second = 1 if hold_second else 0
+        a.mem = L.MEM_DEVICE if k.device else L.MEM_HOST
+        a.flags = L.SORT_RECORDS_CHECK_KEYS if check_keys else 0
+        info = L.SortPlanInfo()
+        self._check(self.lib.pcv_sort_records(self.handle, C.byref(a), C.byref(info)))
+        plan = {f: getattr(info, f) for f, _ in L.SortPlanInfo._fields_ if f != "passes"}
+        plan["passes"] = [{f: getattr(info.passes[i], f) for f, _ in L.SortPassInfo._fields_} for i in range(info.npasses)]
+        return k.keep, v.keep, [b.keep for b in pls], (r.keep if counted else None), plan
+
 
 def promote_assign(nodes, num_nodes, n=0, with_slots=False):
     """Closed form of the every-8th promotion on a node table: (stream_len, num_points, child_offset) arrays and, with

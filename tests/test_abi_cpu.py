@@ -52,3 +52,13 @@ def test_no_oracle_on_the_product_path():
             if f.endswith((".py", ".hip", ".cpp", ".h", "Makefile")):
                 text = open(os.path.join(dirpath, f), errors="ignore").read()
                 assert "oracle_lib" not in text and "pcv_oracle" not in text and "libpcv_oracle" not in text, f
+
+
+def test_abi_layout_of_the_sort_records_structs():
+    import ctypes as C
+
+    from point_cloud_viewer_amd import _lib as L
+    assert C.sizeof(L.SortRecordsArgs) == 160 and L.SortRecordsArgs.planes.offset == 24 and L.SortRecordsArgs.plane0_in.offset == 88
+    assert L.SortRecordsArgs.rows.offset == 112 and L.SortRecordsArgs.key_bits.offset == 120 and L.SortRecordsArgs.flags.offset == 152
+    assert C.sizeof(L.SortPassInfo) == 40 and L.SortPassInfo.dyn_lds.offset == 32
+    assert C.sizeof(L.SortPlanInfo) == 360 and L.SortPlanInfo.chunk.offset == 32 and L.SortPlanInfo.passes.offset == 40

@@ -3,22 +3,16 @@ one stand-alone program with ASan and UBSan. The sanitizers must stay silent; th
 sizes, bit counts, payload shapes, map sizes and switches; the cases below are pinned value for value as the sort's host code
 had them before the plan existed (radix_sort of csrc/pcv_sort.hip at the commit named in tests/golden/sort_launches.json)."""
 import json
-import os
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-UPSWEEP, UPSWEEP_MAP, ROWS, ROWS_TRUE = range(4)  # PcvSortHist
-KEYS, REC_UINT4, REC_UINT2, REC_PLANES, REC12_CHUNKS, REC12_PIECES = range(6)  # PcvSortDown
+from sort_plan_helper import (KEYS, REC12_CHUNKS, REC12_PIECES, REC_PLANES, REC_UINT2, REC_UINT4, ROWS, ROWS_TRUE, UPSWEEP, UPSWEEP_MAP,
+                              build_driver, facts, run_facts)
+
 SETTLE_512, SETTLE_1024_PLANE, SETTLE_1024_R256 = range(3)
 NS = (1, 4095, 4096, 4097, 8209, 65535, 65536, 200000, 10 ** 8, 2 * 10 ** 8, 5 * 10 ** 8, 2 ** 32 - 2)
 MAPS = (0, 1, 4999, 5000, 5001, 10000, 10001, 16384, 16385, 32768, 65536)
-
-
-def facts(n, begin, end, key_bytes=4, vec_in=0, vec_bytes=16, nwords=0, color_in=0, map=0, map_entries=0, rows=0, second=0,
-          sort_rows2=1, sort_msd=0, bins=0):
-    return (n, key_bytes, begin, end, vec_in, vec_bytes, nwords, color_in, map, map_entries, rows, second, sort_rows2, sort_msd, bins)
 
 
 def rec12(n, bits, plane=0, map_entries=8000, **kw):
@@ -51,15 +45,9 @@ PINNED = {
 def driver(tmp_path_factory):
     """One build of the sanitizer program, one run over the sweep and one over the pinned cases."""
     tmp = tmp_path_factory.mktemp("sort_plan")
-    exe = tmp / "sort_plan_driver"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-static-libasan", "-static-libubsan",  # the runtimes inside the program: nothing to preload
-                           os.path.join(ROOT, "tests", "sort_plan_driver.cpp"),
-                           os.path.join(ROOT, "point_cloud_viewer_amd", "csrc", "pcv_sort_plan.cpp"), "-o", str(exe)])
-    (tmp / "pinned.txt").write_text("".join(" ".join(str(v) for v in f) + "\n" for f in PINNED.values()))
+    exe = build_driver(tmp)
     sweep = subprocess.run([str(exe), "sweep"], capture_output=True, text=True)
-    pinned = subprocess.run([str(exe), str(tmp / "pinned.txt")], capture_output=True, text=True)
-    rows = [json.loads(line) for line in pinned.stdout.splitlines()]
+    pinned, rows = run_facts(exe, tmp, "pinned.txt", PINNED.values())
     return sweep, pinned, {name: (rows[2 * i], rows[2 * i + 1]) for i, name in enumerate(PINNED)} if len(rows) == 2 * len(PINNED) else {}
 
 
