@@ -5,10 +5,15 @@
  *
  *   query_batch <dir> <tiles>
  *   query_batch <dir> --map-tiles <zoom>
+ *   query_batch <dir> --cells <token>[,<token>...]
  *
  * --map-tiles: the octree is an ECEF cloud; the slippy-map tiles of zoom level <zoom> (8..23: a WebMercatorRect is at most one
  * pixel of zoom 0 wide, i.e. one tile of zoom 8) that the projection of the bounding box's corners spans go to the batch as
  * PCV_SHAPE_WEB_MERCATOR_RECT shapes made by pcv_wmr_from_zoomed, row by row; one line "<tile x> <tile y> <count>" per tile.
+ *
+ * --cells: the octree is an ECEF cloud; the S2 cells given as tokens (CellID::to_token: the id's hex digits without trailing
+ * zeros) are one cell union (PointLocation::S2Cells), sorted and handed to pcv_shapes_create_ex as the one shape of the batch;
+ * one line "<nodes> <points>": the nodes the union's walk lists and the points it keeps.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -16,13 +21,56 @@
 
 #include "pcv_layout_check.h"
 
+static int by_id(const void* a, const void* b) {
+  const uint64_t x = *(const uint64_t*)a, y = *(const uint64_t*)b;
+  return x < y ? -1 : (x > y ? 1 : 0);
+}
+
+/* one union from "<token>,<token>,...": ids ascending; NULL when a token is not 1..16 hex digits */
+static uint64_t* cells_of_tokens(const char* list, uint32_t* count) {
+  size_t n = 1;
+  for (const char* p = list; *p; ++p) n += *p == ',';
+  uint64_t* ids = (uint64_t*)calloc(n, sizeof(uint64_t));
+  n = 0;
+  for (const char* p = list; ids;) {
+    uint64_t id = 0;
+    int digits = 0;
+    for (; *p && *p != ','; ++p, ++digits) {
+      const int c = *p;
+      const int v = c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1;
+      if (v < 0 || digits >= 16) {
+        free(ids);
+        return NULL;
+      }
+      id = (id << 4) | (uint64_t)v;
+    }
+    if (digits == 0) {
+      free(ids);
+      return NULL;
+    }
+    ids[n++] = id << (4 * (16 - digits));
+    if (!*p) break;
+    ++p;
+  }
+  qsort(ids, n, sizeof(uint64_t), by_id);
+  *count = (uint32_t)n;
+  return ids;
+}
+
 int main(int argc, char** argv) {
   const int map_tiles = argc >= 4 && strcmp(argv[2], "--map-tiles") == 0;
-  if (argc < 3 || (argc >= 4 && !map_tiles)) {
-    fprintf(stderr, "usage: query_batch <dir> <tiles> | query_batch <dir> --map-tiles <zoom>\n");
+  const int by_cells = argc >= 4 && strcmp(argv[2], "--cells") == 0;
+  if (argc < 3 || (argc >= 4 && !map_tiles && !by_cells)) {
+    fprintf(stderr, "usage: query_batch <dir> <tiles> | query_batch <dir> --map-tiles <zoom> | query_batch <dir> --cells <token>[,<token>...]\n");
     return 2;
   }
-  const unsigned tiles = map_tiles ? 1u : (unsigned)strtoul(argv[2], NULL, 10);
+  uint32_t union_first[2] = {0, 0};
+  uint64_t* union_cells = by_cells ? cells_of_tokens(argv[3], &union_first[1]) : NULL;
+  if (by_cells && !union_cells) {
+    fprintf(stderr, "a token is 1..16 hex digits\n");
+    return 2;
+  }
+  const unsigned tiles = map_tiles || by_cells ? 1u : (unsigned)strtoul(argv[2], NULL, 10);
   const unsigned zoom = map_tiles ? (unsigned)strtoul(argv[3], NULL, 10) : 0u;
   if (tiles == 0) {
     fprintf(stderr, "tiles must be positive\n");
@@ -88,7 +136,8 @@ int main(int argc, char** argv) {
       grid[k].kind = PCV_SHAPE_WEB_MERCATOR_RECT;
       rc = pcv_wmr_from_zoomed(mn, mx, zoom, grid[k].params);
     }
-    for (unsigned i = 0; !map_tiles && rc == PCV_OK && i < tiles; ++i)
+    if (by_cells) grid[0].kind = PCV_SHAPE_S2_CELL_UNION; /* .reserved = 0: the first (and only) union */
+    for (unsigned i = 0; !map_tiles && !by_cells && rc == PCV_OK && i < tiles; ++i)
       for (unsigned j = 0; j < tiles; ++j) {
         pcv_shape* s = &grid[i * tiles + j];
         s->kind = PCV_SHAPE_AABB;
@@ -99,7 +148,8 @@ int main(int argc, char** argv) {
         s->params[4] = bmin[1] + (bmax[1] - bmin[1]) * (j + 1) / tiles;
         s->params[5] = bmax[2];
       }
-    if (rc == PCV_OK) rc = pcv_shapes_create(ctx, grid, count, &shapes);
+    if (rc == PCV_OK)
+      rc = by_cells ? pcv_shapes_create_ex(ctx, grid, count, 1, union_first, union_cells, &shapes) : pcv_shapes_create(ctx, grid, count, &shapes);
     if (rc == PCV_OK) rc = pcv_query_batch_run(ctx, shapes, tree, NULL, NULL, &batch);
     pcv_shapes_free(shapes); /* the batch does not need the shapes any more */
     uint64_t nseg = 0, npts = 0;
@@ -109,7 +159,8 @@ int main(int argc, char** argv) {
       offset = (uint64_t*)malloc(sizeof(uint64_t) * (nseg + 1));
       rc = pcv_query_batch_segments(batch, first, NULL, offset);
     }
-    for (unsigned k = 0; rc == PCV_OK && k < count; ++k)
+    if (rc == PCV_OK && by_cells) printf("%llu %llu\n", (unsigned long long)nseg, (unsigned long long)npts);
+    for (unsigned k = 0; rc == PCV_OK && !by_cells && k < count; ++k)
       printf("%u %u %llu\n", map_tiles ? tx0 + k % ntx : k / tiles, map_tiles ? ty0 + k / ntx : k % tiles,
              (unsigned long long)(offset[first[k + 1]] - offset[first[k]]));
   }
@@ -117,6 +168,7 @@ int main(int argc, char** argv) {
   free(first);
   free(offset);
   free(grid);
+  free(union_cells);
   pcv_query_batch_free(batch);
   if (tree) pcv_octree_free(tree);
   if (ctx) pcv_ctx_destroy(ctx);

@@ -605,16 +605,20 @@ int pcv_octree_open_dir(pcv_ctx* ctx, const char* directory, pcv_octree** out);
  *                                   fields of geometry::WebMercatorRect (src/geometry/web_mercator_rect.rs:30-33); make
  *                                   them with pcv_wmr_from_zoomed. The query space is ECEF. pcv_shapes_create takes the
  *                                   four doubles as given, like the other kinds' parameters: it does not repeat the
- *                                   constructor's checks (NaN or inverted bounds give a shape that contains nothing). */
+ *                                   constructor's checks (NaN or inverted bounds give a shape that contains nothing).
+ *   PCV_SHAPE_S2_CELL_UNION         -  (no params)                             PointLocation::S2Cells(CellUnion): `reserved`
+ *                                   is the index of the shape's union among the unions handed to pcv_shapes_create_ex. The
+ *                                   query space is ECEF. Every other kind ignores `reserved`. */
 #define PCV_SHAPE_ALL 0
 #define PCV_SHAPE_AABB 1
 #define PCV_SHAPE_FRUSTUM 2
 #define PCV_SHAPE_OBB 3
 #define PCV_SHAPE_FRUSTUM_WITH_INVERSE 4
 #define PCV_SHAPE_WEB_MERCATOR_RECT 5
+#define PCV_SHAPE_S2_CELL_UNION 6
 typedef struct pcv_shape {
   int32_t kind;
-  int32_t reserved;
+  int32_t reserved; /* PCV_SHAPE_S2_CELL_UNION: index of the shape's union (pcv_shapes_create_ex); otherwise unused */
   double params[32];
 } pcv_shape;
 typedef struct pcv_shapes pcv_shapes;
@@ -627,10 +631,31 @@ typedef struct pcv_shapes pcv_shapes;
 /* Q1: prepares `count` shapes on the device: corners, unique edges / face normals and the deduplicated
  * separating axes against AABBs (Intersector::cache_separating_axes_for_aabb, src/math/sat.rs:111-143). */
 int pcv_shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t count, pcv_shapes** out);
+/* The same with cell unions as locations over the octree (PointLocation::S2Cells; HasAabbIntersector for CellUnion,
+ * src/geometry/s2_cell_union.rs). The unions are given as pcv_s2_cells_in_location takes them: host memory, union u's
+ * cells union_cells[union_first[u] .. union_first[u + 1]), ascending, union_first[0] == 0; they are taken as given, not
+ * normalized. A shape of kind PCV_SHAPE_S2_CELL_UNION names its union by `reserved`; unions and the other kinds mix in any
+ * order, a union may be named by several shapes or by none, and an empty union is valid and contains nothing.
+ * PCV_E_INVALID with pcv_s2_cells_in_location's messages for malformed unions, "union index out of range", and "a union
+ * with a level-0 cell has no geometry" (Cell::rect_bound of a face is not provided). pcv_shapes_create itself refuses the
+ * kind. Meaning over an octree: a node is listed and descended into iff the rect bound of the normalized leaf cells of its
+ * bounding cube's 8 corners intersects a cell of the union (Rect::intersects_cell; the reference's misses, such as a corner
+ * rect that does not cover its cube, included); a point is kept iff CellUnion::contains_cellid(CellID::from_point(p)) of
+ * its decoded position, then the interval. pcv_nodes_in_location, pcv_cull_points, pcv_cull_node_points, pcv_query_points,
+ * pcv_query_node_points and pcv_query_batch_run take such shapes; pcv_cull_nodes, pcv_cull_nodes_sparse and
+ * pcv_visible_nodes refuse a table that holds one (a union has no Relation and no clip matrix), naming the first.
+ * pcv_s2_cells_in_location, pcv_s2_query_run (and through it pcv_xray_run_s2's queries) treat a union member of the table
+ * as the union location it is, at the shape's slot: CellUnion::intersects_cellid for the cells, contains_cellid per point. */
+int pcv_shapes_create_ex(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t count, uint32_t num_unions, const uint32_t* union_first,
+                         const uint64_t* union_cells, pcv_shapes** out);
+/* The cells of shape i, a PCV_SHAPE_S2_CELL_UNION: *num_cells is the union's length, of which the first
+ * min(length, capacity) are written to `cells` (nullable with capacity 0). PCV_E_INVALID for any other kind. */
+int pcv_shapes_union(pcv_shapes* shapes, uint32_t i, uint64_t capacity, uint64_t* cells, uint32_t* num_cells);
 void pcv_shapes_free(pcv_shapes* shapes);
 uint32_t pcv_shapes_count(const pcv_shapes* shapes);
 /* Inspect one prepared shape (tests): 8 corners, up to 26 axes. valid == 0: the matrix is not invertible. PCV_E_INVALID for
- * a shape with more than 26 axes (a web-mercator rectangle may have up to 45): use pcv_shapes_get_ex. */
+ * a shape with more than 26 axes (a web-mercator rectangle may have up to 45): use pcv_shapes_get_ex. Both calls are
+ * PCV_E_INVALID for a cell union, which has neither corners nor axes: pcv_shapes_union gives its cells. */
 int pcv_shapes_get(pcv_shapes* shapes, uint32_t i, double corners[24], double axes[78], uint32_t* num_axes, int* valid);
 /* The same for any shape: `axes` holds 3 * axes_capacity doubles (PCV_MAX_SHAPE_AXES always suffices); *num_axes is the
  * shape's count, of which the first min(count, axes_capacity) are written. */
@@ -1258,6 +1283,11 @@ int pcv_s2_rect_intersects_cell_host(const double rect[4], uint64_t cell, int* i
 int pcv_s2_union_normalize_host(uint64_t* cells, uint32_t* num_cells);
 /* CellUnion::intersects_cellid for n cell ids against `cells` (ascending, as pcv_s2_union_contains takes them). */
 int pcv_s2_union_intersects_host(const uint64_t* cells, uint32_t num_cells, uint64_t n, const uint64_t* ids, uint8_t* intersects);
+/* cells_intersecting_polyhedron(cells, cube.to_aabb()) for n cubes (min xyz, edge; n x 4 doubles): the 8 corners' leaf
+ * cells, normalized, their rect bound, Rect::intersects_cell against every cell of the union (ascending, level >= 1, not
+ * normalized). The chain the device walks with: a cell union's node list over an octree is the breadth-first walk over this
+ * predicate on the nodes' bounding cubes, bit for bit. */
+int pcv_s2_union_intersects_cubes_host(const uint64_t* cells, uint32_t num_cells, uint64_t n, const double* cubes, uint8_t* intersects);
 
 /* S2Cells::nodes_in_location (mod.rs:160-241) for many locations in one call: first the shapes (nullable), then num_unions
  * cell unions, union u being union_cells[union_first[u] .. union_first[u + 1]) in HOST memory, ascending by id, union_first[0] = 0.

@@ -58,6 +58,7 @@ class Shape(C.Structure):
 
 
 SHAPE_ALL, SHAPE_AABB, SHAPE_FRUSTUM, SHAPE_OBB, SHAPE_FRUSTUM_WITH_INVERSE, SHAPE_WEB_MERCATOR_RECT = 0, 1, 2, 3, 4, 5
+SHAPE_S2_CELL_UNION = 6  # PCV_SHAPE_S2_CELL_UNION: Shape.reserved is the union's index (pcv_shapes_create_ex)
 MAX_SHAPE_AXES = 45  # PCV_MAX_SHAPE_AXES
 WMR_FN_ATAN2, WMR_FN_SINCOS, WMR_FN_LN = 0, 1, 2
 
@@ -257,6 +258,8 @@ _SIGNATURES = {
     "pcv_build_octree_from_ply": (C.c_int, [_vp, C.POINTER(BuildParams), C.c_char_p, C.c_int, C.POINTER(_vp)]),
     "pcv_octree_open_dir": (C.c_int, [_vp, C.c_char_p, C.POINTER(_vp)]),
     "pcv_shapes_create": (C.c_int, [_vp, C.POINTER(Shape), C.c_uint32, C.POINTER(_vp)]),
+    "pcv_shapes_create_ex": (C.c_int, [_vp, C.POINTER(Shape), C.c_uint32, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
+    "pcv_shapes_union": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _vp, C.POINTER(C.c_uint32)]),
     "pcv_shapes_free": (None, [_vp]),
     "pcv_shapes_count": (C.c_uint32, [_vp]),
     "pcv_shapes_get": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -363,6 +366,7 @@ _SIGNATURES = {
     "pcv_s2_rect_intersects_cell_host": (C.c_int, [_vp, C.c_uint64, C.POINTER(C.c_int)]),
     "pcv_s2_union_normalize_host": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "pcv_s2_union_intersects_host": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _vp, _vp]),
+    "pcv_s2_union_intersects_cubes_host": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _vp, _vp]),
     "pcv_s2_cells_in_location": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp]),
     "pcv_s2_cells_in_location_host": (C.c_int, [C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp]),
     "pcv_xray_run_s2": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(XrayParams), C.POINTER(XrayColoring), C.POINTER(_vp)]),

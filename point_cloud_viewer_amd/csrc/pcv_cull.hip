@@ -634,6 +634,7 @@ int pcv_octree_prepare_query(pcv_octree* t) {
 
 void pcv_octree_release_query(pcv_octree* t) {
   if (!t->query) return;
+  if (t->query->node_rects) t->ctx->dev_free(t->query->node_rects);
   t->ctx->dev_free(t->query->cubes);
   delete t->query;
   t->query = nullptr;
@@ -654,7 +655,9 @@ extern "C" int pcv_cull_nodes(pcv_ctx* ctx, const pcv_shapes* shapes, pcv_octree
                               double* size_on_screen_out) {
   if (!ctx) return PCV_E_INVALID;
   if (!shapes || !tree || !relation) return ctx->fail(PCV_E_INVALID, "null argument");
-  int rc = pcv_octree_prepare_query(tree);
+  int rc = pcv_refuse_unions(ctx, shapes, "pcv_cull_nodes");
+  if (rc) return rc;
+  rc = pcv_octree_prepare_query(tree);
   if (rc) return rc;
   const uint32_t m = tree->query->m, f = shapes->count;
   if (m == 0 || f == 0) return PCV_OK;
@@ -698,7 +701,9 @@ extern "C" int pcv_cull_nodes_sparse(pcv_ctx* ctx, const pcv_shapes* shapes, pcv
                                      uint32_t* node_indices, uint8_t* relation, double* size_on_screen_out) {
   if (!ctx) return PCV_E_INVALID;
   if (!shapes || !tree || !counts || (capacity && (!node_indices || !relation))) return ctx->fail(PCV_E_INVALID, "null argument");
-  int rc = pcv_octree_prepare_query(tree);
+  int rc = pcv_refuse_unions(ctx, shapes, "pcv_cull_nodes_sparse");
+  if (rc) return rc;
+  rc = pcv_octree_prepare_query(tree);
   if (rc) return rc;
   const PcvOctreeQuery* q = tree->query;
   const uint32_t m = q->m, f = shapes->count;
@@ -752,7 +757,8 @@ size_t pcv_node_lists_scratch(uint32_t f, uint32_t m) { return f + queue_bytes(m
 // Round 6: one WAVE per shape walks the tree with the lanes as the shape's axes (cull_nodes_tree_kernel<.., HIER>): the
 // one-lane-per-shape walk took 3.1 ms for 10 000 frusta; it stays for the shapes the wave walk hands back (a frontier that
 // outgrows the wave's queue, AllPoints), batch by batch, and its WIDE instance, behind it in every batch, writes the
-// web-mercator rectangles' lists and counts over what the launches before it wrote for them.
+// web-mercator rectangles' lists and counts over what the launches before it wrote for them. Cell unions have a walk of their
+// own behind all of these (pcv_union.hip), a wave per location, which reuses the queues.
 int pcv_launch_node_lists(pcv_ctx* ctx, int label, bool walk_bracket, const pcv_shapes* shapes, const pcv_octree* tree,
                           uint32_t capacity, uint32_t* counts, uint32_t* out, uint32_t* scratch, const uint64_t* rows) {
   const PcvOctreeQuery* q = tree->query;
@@ -781,7 +787,8 @@ int pcv_launch_node_lists(pcv_ctx* ctx, int label, bool walk_bracket, const pcv_
                          q->fb_cubes, queues, capacity, counts, out, (const uint32_t*)nullptr, rows);
   }
   PCV_HIP_CHECK(ctx, hipGetLastError());
-  return PCV_OK;
+  // the cell unions' counts and lists, over the zeroes the launches above wrote for them (to those a union is not valid)
+  return pcv_launch_union_lists(ctx, label, shapes, tree, capacity, counts, out, queues, batch, rows);
 }
 
 // What the two traversals share. Before their launches: the arguments, the tree's tables, counts and lists on the device
@@ -814,7 +821,9 @@ extern "C" int pcv_visible_nodes(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_oct
   if (!ctx) return PCV_E_INVALID;
   PcvScratch sc(ctx);
   uint32_t f, *d_counts, *d_out;
-  int rc = traversal_begin(ctx, frusta, tree, capacity, counts, node_indices, sc, &f, &d_counts, &d_out);
+  int rc = frusta ? pcv_refuse_unions(ctx, frusta, "pcv_visible_nodes") : PCV_OK;
+  if (rc) return rc;
+  rc = traversal_begin(ctx, frusta, tree, capacity, counts, node_indices, sc, &f, &d_counts, &d_out);
   if (rc || f == 0) return rc;
   const PcvOctreeQuery* q = tree->query;
   const QTree qt{q->m, q->cubes, q->first_child, q->child_mask, q->empty};

@@ -114,6 +114,7 @@ enum PcvKernelId {
   PCV_K_S2_PAIRS,             // pcv_s2_query.hip: one wave per location over the cell table, the list ascending by cell id
   PCV_K_S2_FLAGS,             // pcv_s2_points.hip: keep flags of every candidate point of every (location, listed cell)
   PCV_K_S2_GATHER_POINTS,     // pcv_s2_points.hip: the kept points of a segment range into the caller's planes
+  PCV_K_UNION_NODE_RECTS,     // pcv_union.hip: once per octree, the rect of every node cube's corners (cell unions over the octree)
   PCV_K_COUNT
 };
 

@@ -101,6 +101,12 @@ struct PcvShapeDev {
   union {
     double query_from_clip[16];
     struct PcvShapeWide* wide;  // web-mercator rectangle (no matrices): its record beside the table
+    struct {                    // cell union (no matrices): its cells and their geometry beside the table (pcv_union.hip)
+      const uint64_t* cells;    // the union's own cells, ascending
+      const double* geom;       // s2::kCellPlanes planes of `stride` doubles, every union's cells back to back
+      uint32_t count, first;    // this union's cells are columns first .. first + count of the planes
+      uint32_t stride, pad;
+    } cell_union;
   };
   double iso[7];   // obb_from_query (translation xyz, quaternion ijkw) for contains()
   double half[3];
@@ -133,6 +139,15 @@ struct pcv_shapes {
   PcvShapeDev* dev;
   PcvShapeWide* wide = nullptr;  // one per web-mercator rectangle, in shape order
   std::vector<int32_t> kinds;  // host copy: the point kernels are compiled per shape kind
+  // cell unions (pcv_shapes_create_ex). On the device a union shape is `valid == 0` with no axes, so every traversal written
+  // for the other kinds reports nothing for it at once; the union walk and the union point instances, launched behind them on
+  // the same stream, write its counts, lists and flags.
+  std::vector<uint32_t> union_first;   // host copies, as given: U + 1 offsets and the cells
+  std::vector<uint64_t> union_cells;
+  std::vector<uint32_t> union_shapes;  // the shapes of kind PCV_SHAPE_S2_CELL_UNION, ascending
+  std::vector<uint32_t> union_of;      // per union shape (same order): its union
+  void* d_union = nullptr;             // one block: the cells, their geometry planes, union_shapes
+  const uint32_t* d_union_shapes = nullptr;
 };
 
 // Device-resident query view of an octree, built lazily (pcv_octree::query, pcv_octree_prepare_query in pcv_cull.hip): one
@@ -145,6 +160,7 @@ struct PcvOctreeQuery {
   uint32_t* first_child = nullptr;
   uint8_t* child_mask = nullptr;
   uint8_t* empty = nullptr;
+  double* node_rects = nullptr;  // m x 4, own block, built by the first cell-union query (pcv_union.hip): the rect of fb_cubes[i]'s corners
   std::vector<uint32_t> h_first_child;  // host copies for the host-side walk
   std::vector<uint8_t> h_child_mask;
 };
@@ -181,6 +197,20 @@ struct pcv_query_batch {
   uint8_t* d_keep = nullptr;
   uint64_t* d_chunk_off = nullptr;  // nchunks + 1
 };
+
+// ---- cell unions over the octree (pcv_union.hip) --------------------------------------------------------------------
+// `what` refused because the table holds a cell union (no Relation, no clip matrix): PCV_E_INVALID naming the first one
+int pcv_refuse_unions(pcv_ctx* ctx, const pcv_shapes* shapes, const char* what);
+// The block behind pcv_shapes::d_union for the table's unions (geometry of every cell, on the stream) and the union members of
+// `h` (the host copy of the shape table, before its upload) pointed at it.
+int pcv_union_prepare_shapes(pcv_ctx* ctx, pcv_shapes* r, PcvShapeDev* h);
+// The node lists of the table's cell unions, behind pcv_launch_node_lists' other launches and with its arguments: counts[f] and
+// the list of every union shape f, breadth first (= ascending by node index). queues: m u32 per location in flight, `batch`
+// of them. Builds the tree's rect table on first use.
+int pcv_launch_union_lists(pcv_ctx* ctx, int label, const pcv_shapes* shapes, const pcv_octree* tree, uint32_t capacity,
+                           uint32_t* counts, uint32_t* out, uint32_t* queues, uint32_t batch, const uint64_t* rows);
+// the same for one union shape into `nodes` (host), for the single-location point query
+int pcv_union_node_list(pcv_ctx* ctx, const pcv_shapes* shapes, uint32_t shape_index, const pcv_octree* tree, std::vector<uint32_t>* nodes);
 
 // out[0 .. n] = exclusive u64 scan of in[0 .. n), out[n] the total (asynchronous on ctx->stream)
 int pcv_batch_scan(pcv_ctx* ctx, PcvScratch& sc, const uint32_t* in, uint64_t n, uint64_t* out);

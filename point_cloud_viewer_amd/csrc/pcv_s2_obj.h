@@ -39,5 +39,8 @@ int pcv_s2_read_cells(const char* directory, const PcvS2Dir& meta, uint8_t* xyz,
 
 // a union's cells as the entry points take them: ascending by id, no 0 (pcv_s2.hip); *why says what is wrong
 int pcv_s2_check_union(const uint64_t* cells, uint32_t num_cells, std::string* why);
+// several unions as pcv_s2_cells_in_location takes them (pcv_s2_query.hip): union_first[0] == 0, no descent, each union as above,
+// every cell an S2 cell id
+int pcv_s2_check_unions(uint32_t num_unions, const uint32_t* union_first, const uint64_t* union_cells, std::string* why);
 // the blobs of an opened cloud on the device (pcv_s2.hip: read and uploaded on first use); nothing to do for a split
 int pcv_s2_make_resident(pcv_s2_cloud* c);

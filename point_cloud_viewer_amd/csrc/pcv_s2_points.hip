@@ -95,6 +95,7 @@ int kind_of(const pcv_shapes* shapes, uint32_t num_shapes, uint32_t location) {
     case PCV_SHAPE_FRUSTUM_WITH_INVERSE: return PCV_SHAPE_FRUSTUM;
     case PCV_SHAPE_OBB: return PCV_SHAPE_OBB;
     case PCV_SHAPE_WEB_MERCATOR_RECT: return PCV_SHAPE_WEB_MERCATOR_RECT;
+    case PCV_SHAPE_S2_CELL_UNION: return kKindUnion;  // a union member of the table: the union location it is
     default: return PCV_SHAPE_ALL;
   }
 }
@@ -159,9 +160,17 @@ int run_impl(pcv_s2_cloud* c, const pcv_shapes* shapes, uint32_t num_unions, con
   std::vector<Ival> ivals(locations, Ival{0, 0, 0, 0});
   for (uint64_t l = 0; l < locations && intervals; ++l)
     if (!interval_used || interval_used[l]) ivals[l] = Ival{intervals[2 * l], intervals[2 * l + 1], 1u, 0u};
-  std::vector<UnionRef> urefs(num_unions ? num_unions : 1, UnionRef{0, 0});
-  for (uint32_t u = 0; u < num_unions; ++u) urefs[u] = UnionRef{union_first[u], union_first[u + 1] - union_first[u]};
-  const uint32_t union_total = num_unions ? union_first[num_unions] : 0;
+  // one reference per LOCATION (the union instance is launched with num_shapes = 0): the call's unions, and the table's own
+  // union members, whose cells sit behind the call's in d_union
+  const uint32_t own_total = num_unions ? union_first[num_unions] : 0;
+  const size_t table_total = shapes ? shapes->union_cells.size() : 0;
+  std::vector<UnionRef> urefs(locations, UnionRef{0, 0});
+  for (uint32_t u = 0; u < num_unions; ++u) urefs[num_shapes + u] = UnionRef{union_first[u], union_first[u + 1] - union_first[u]};
+  for (size_t k = 0; shapes && k < shapes->union_shapes.size(); ++k) {
+    const uint32_t u = shapes->union_of[k];
+    urefs[shapes->union_shapes[k]] = UnionRef{own_total + shapes->union_first[u], shapes->union_first[u + 1] - shapes->union_first[u]};
+  }
+  const size_t union_total = own_total + table_total;
   std::vector<uint32_t> which;
   for (const auto& v : by_kind) which.insert(which.end(), v.begin(), v.end());
   Ival* d_ivals;
@@ -175,7 +184,8 @@ int run_impl(pcv_s2_cloud* c, const pcv_shapes* shapes, uint32_t num_unions, con
     return rc;
   if ((rc = ctx->h2d(b->d_chunks, chunks.data(), chunks.size() * sizeof(Chunk))) || (rc = ctx->h2d(d_ivals, ivals.data(), locations * sizeof(Ival))) ||
       (rc = ctx->h2d(d_urefs, urefs.data(), urefs.size() * sizeof(UnionRef))) || (rc = ctx->h2d(d_which, which.data(), which.size() * 4)) ||
-      (rc = ctx->h2d(d_at, seg_candidate.data(), (b->nseg + 1) * 8)) || (union_total && (rc = ctx->h2d(d_union, union_cells, (size_t)union_total * 8))))
+      (rc = ctx->h2d(d_at, seg_candidate.data(), (b->nseg + 1) * 8)) || (own_total && (rc = ctx->h2d(d_union, union_cells, (size_t)own_total * 8))) ||
+      (table_total && (rc = ctx->h2d(d_union + own_total, shapes->union_cells.data(), table_total * 8))))
     return rc;
   // ---- flags, one launch per kind that occurs ----
   {
@@ -184,7 +194,8 @@ int run_impl(pcv_s2_cloud* c, const pcv_shapes* shapes, uint32_t num_unions, con
     const PcvShapeDev* dev = shapes ? shapes->dev : nullptr;
 #define LAUNCH(KIND)                                                                                                                    \
   if (!by_kind[KIND].empty()) {                                                                                                         \
-    hipLaunchKernelGGL(s2_flags_kernel<KIND>, dim3((uint32_t)by_kind[KIND].size()), dim3(256), 0, st, b->d_chunks, w, dev, num_shapes,  \
+    hipLaunchKernelGGL(s2_flags_kernel<KIND>, dim3((uint32_t)by_kind[KIND].size()), dim3(256), 0, st, b->d_chunks, w, dev,              \
+                       KIND == kKindUnion ? 0u : num_shapes,                                                                            \
                        d_urefs, d_union, d_ivals, (const double*)c->d_xyz, (const float*)c->d_int, b->d_flags);                           \
     w += by_kind[KIND].size();                                                                                                          \
   }

@@ -38,33 +38,8 @@ __host__ __device__ inline void location_of_shape(int32_t kind, int32_t valid, c
   }
 }
 
-__host__ __device__ inline void store_geom(const s2::CellGeom& g, double* table, size_t n, size_t c) {
-  double* t = table + c;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) t[(size_t)k * n] = g.rect[k];
-  t[4 * n] = g.cll[0], t[5 * n] = g.cll[1];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) t[(size_t)(6 + k) * n] = g.uv[k];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) t[(size_t)(10 + k) * n] = g.vtx[k];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) t[(size_t)(22 + k) * n] = g.vll[k];
-}
-static_assert(s2::kCellPlanes == 30, "store_geom / load_geom write and read 30 planes");
-
-__host__ __device__ inline void load_geom(const double* table, size_t n, size_t c, uint64_t id, s2::CellGeom* g) {
-  const double* t = table + c;
-  g->face = (uint32_t)(id >> 61);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) g->rect[k] = t[(size_t)k * n];
-  g->cll[0] = t[4 * n], g->cll[1] = t[5 * n];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) g->uv[k] = t[(size_t)(6 + k) * n];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) g->vtx[k] = t[(size_t)(10 + k) * n];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) g->vll[k] = t[(size_t)(22 + k) * n];
-}
+using s2::load_geom;  // the layout of the cell table's planes: pcv_s2_region_dev.h
+using s2::store_geom;
 
 __global__ __launch_bounds__(256) void s2_cell_table_kernel(const uint64_t* __restrict__ ids, uint32_t n, double* __restrict__ table) {
   const uint32_t c = blockIdx.x * 256u + threadIdx.x;
@@ -187,6 +162,10 @@ int prepare_cloud(pcv_s2_cloud* c, bool geometric) {
 
 }  // namespace
 
+int pcv_s2_check_unions(uint32_t num_unions, const uint32_t* union_first, const uint64_t* union_cells, std::string* why) {
+  return check_unions(num_unions, union_first, union_cells, why);
+}
+
 // ---- host twins (no context) --------------------------------------------------------------------------------------------
 extern "C" int pcv_s2_cell_geometry_host(uint64_t cell, double geometry[30]) {
   if (!geometry) return pcv_host_fail(PCV_E_INVALID, "null argument");
@@ -292,8 +271,9 @@ extern "C" int pcv_s2_cells_in_location(pcv_s2_cloud* c, const pcv_shapes* shape
   if (shapes && shapes->ctx != ctx) return ctx->fail(PCV_E_INVALID, "the shapes belong to another context");
   const uint32_t num_shapes = shapes ? shapes->count : 0;
   const uint32_t n = (uint32_t)c->ids.size();
-  bool geometric = false;
-  for (uint32_t f = 0; f < num_shapes; ++f) geometric = geometric || shapes->kinds[f] != PCV_SHAPE_ALL;
+  bool geometric = false;  // (a cell union in the table asks for ids only, like the call's own unions)
+  for (uint32_t f = 0; f < num_shapes; ++f)
+    geometric = geometric || (shapes->kinds[f] != PCV_SHAPE_ALL && shapes->kinds[f] != PCV_SHAPE_S2_CELL_UNION);
   std::string why;
   if (check_cloud_cells(c->ids.size(), c->ids.data(), geometric, &why) || check_unions(num_unions, union_first, union_cells, &why))
     return ctx->fail(PCV_E_INVALID, why);
@@ -314,14 +294,31 @@ extern "C" int pcv_s2_cells_in_location(pcv_s2_cloud* c, const pcv_shapes* shape
   uint32_t *d_counts, *d_out;
   uint64_t* d_union;
   const uint32_t union_total = num_unions ? union_first[num_unions] : 0;
+  // the table's own unions (pcv_shapes_create_ex) sit behind the call's in d_union
+  const size_t table_total = shapes ? shapes->union_cells.size() : 0;
+  if ((uint64_t)union_total + table_total > 0xffffffffull) return ctx->fail(PCV_E_INVALID, "too many union cells for one call");
   if ((rc = sc.get(&d_locs, (size_t)locations)) || (rc = sc.get(&d_counts, (size_t)locations)) ||
-      (rc = sc.get(&d_out, (size_t)locations * capacity + 1)) || (rc = sc.get(&d_union, (size_t)union_total + 1)))
+      (rc = sc.get(&d_out, (size_t)locations * capacity + 1)) || (rc = sc.get(&d_union, (size_t)union_total + table_total + 1)))
     return rc;
   if (num_shapes) {
     PcvProf prof(ctx, PCV_K_S2_LOCATIONS);
     hipLaunchKernelGGL(s2_location_kernel, dim3((num_shapes + 63u) / 64u), dim3(64), 0, st, shapes->dev, num_shapes, d_locs);
   }
   PCV_HIP_CHECK(ctx, hipGetLastError());
+  // a cell union in the table is the union location it is, at its slot: over what s2_location_kernel wrote for it (none)
+  std::vector<S2Loc> t_locs(shapes ? shapes->union_shapes.size() : 0);
+  for (size_t k = 0; k < t_locs.size(); ++k) {
+    const uint32_t u = shapes->union_of[k];
+    S2Loc& loc = t_locs[k];
+    loc.mode = kLocUnion;
+    loc.union_first = union_total + shapes->union_first[u];
+    loc.union_count = shapes->union_first[u + 1] - shapes->union_first[u];
+    loc.pad = 0;
+    s2::rect_set_empty(loc.rect);
+    PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_locs + shapes->union_shapes[k], &loc, sizeof(S2Loc), hipMemcpyHostToDevice, st));
+  }
+  if (!t_locs.empty() && table_total)
+    PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_union + union_total, shapes->union_cells.data(), table_total * 8, hipMemcpyHostToDevice, st));
   std::vector<S2Loc> h_locs(num_unions);
   if (num_unions) {
     for (uint32_t u = 0; u < num_unions; ++u) {

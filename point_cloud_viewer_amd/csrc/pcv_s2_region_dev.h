@@ -315,6 +315,36 @@ __host__ __device__ inline void cell_geom(uint64_t id, CellGeom* g) {
   }
 }
 
+// a CellGeom as kCellPlanes planes of n doubles, cell c at column c (the cell table of a cloud, the cells of a shape table's
+// unions, and n = 1: pcv_s2_cell_geometry_host)
+__host__ __device__ inline void store_geom(const CellGeom& g, double* table, size_t n, size_t c) {
+  double* t = table + c;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) t[(size_t)k * n] = g.rect[k];
+  t[4 * n] = g.cll[0], t[5 * n] = g.cll[1];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) t[(size_t)(6 + k) * n] = g.uv[k];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) t[(size_t)(10 + k) * n] = g.vtx[k];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) t[(size_t)(22 + k) * n] = g.vll[k];
+}
+static_assert(kCellPlanes == 30, "store_geom / load_geom write and read 30 planes");
+
+__host__ __device__ inline void load_geom(const double* table, size_t n, size_t c, uint64_t id, CellGeom* g) {
+  const double* t = table + c;
+  g->face = (uint32_t)(id >> 61);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) g->rect[k] = t[(size_t)k * n];
+  g->cll[0] = t[4 * n], g->cll[1] = t[5 * n];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) g->uv[k] = t[(size_t)(6 + k) * n];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) g->vtx[k] = t[(size_t)(10 + k) * n];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) g->vll[k] = t[(size_t)(22 + k) * n];
+}
+
 // rect_bound of a union: the union of its cells' rects. False when a cell is of level 0.
 __host__ __device__ inline bool union_rect_bound(const uint64_t* ids, uint32_t n, double* rect) {
   rect_set_empty(rect);
@@ -329,9 +359,9 @@ __host__ __device__ inline bool union_rect_bound(const uint64_t* ids, uint32_t n
   return true;
 }
 
-// cells_in_convex_polyhedron's region (mod.rs:224-231): the corners' leaf cells, normalized, their rect bound
-__host__ __device__ inline bool corners_rect(const double* corners, double* rect) {
-  uint64_t ids[8];
+// cells_in_convex_polyhedron's region (mod.rs:224-231): the corners' leaf cells, normalized, their rect bound. `ids`: eight
+// slots of working memory (a kernel that may not spill hands in LDS: the sort and the normalization index them by variables).
+__host__ __device__ inline bool corners_rect_in(const double* corners, uint64_t* ids, double* rect) {
 #pragma unroll
   for (int k = 0; k < 8; ++k) ids[k] = leaf_from_point(corners[3 * k], corners[3 * k + 1], corners[3 * k + 2]);
   for (int a = 1; a < 8; ++a) {  // insertion sort
@@ -344,6 +374,10 @@ __host__ __device__ inline bool corners_rect(const double* corners, double* rect
     ids[b + 1] = key;
   }
   return union_rect_bound(ids, normalize_sorted(ids, 8), rect);
+}
+__host__ __device__ inline bool corners_rect(const double* corners, double* rect) {
+  uint64_t ids[8];
+  return corners_rect_in(corners, ids, rect);
 }
 
 // ---- Rect::intersects_cell ----------------------------------------------------------------------------------------------

@@ -1,4 +1,5 @@
-// pcv_shapes.hip — prepared query shapes for gfx950: pcv_shapes_create / _free / _count / _get / _get_ex.
+// pcv_shapes.hip — prepared query shapes for gfx950: pcv_shapes_create / _create_ex / _free / _count / _get /
+// _get_ex / _union.
 //
 //   K7a shape_setup      Frustum::from_matrix4 / intersector / cache_separating_axes_for_aabb
 //                        (reference src/geometry/frustum.rs:111-166, src/math/sat.rs:111-143), Obb (obb.rs:48-80),
@@ -11,9 +12,12 @@
 #include <cmath>
 #include <cstddef>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "pcv_query_dev.h"
+#include "pcv_s2_obj.h"
+#include "pcv_s2_region_dev.h"
 
 // ---------------------------------------------------------------------------------------------
 // device math
@@ -192,6 +196,11 @@ __global__ __launch_bounds__(64) void shape_setup_kernel(PcvShapeDev* shapes, ui
     for (int a = 0; a < w->naxes; ++a)
       project8(s->corners, V3d{w->axes[3 * a], w->axes[3 * a + 1], w->axes[3 * a + 2]}, &w->amin[a], &w->amax[a]);
     s->naxes = 0;
+  } else if (s->kind == PCV_SHAPE_S2_CELL_UNION) {
+    // no corners, no axes. Not valid to the traversals of the other kinds, which then report nothing for it; its own walk and
+    // point instances (pcv_union.hip, pcv_query.hip) read s->cell_union and do not look at this flag.
+    s->valid = 0;
+    s->naxes = 0;
   } else {
     s->naxes = 0;  // AllPoints
   }
@@ -201,10 +210,25 @@ __global__ __launch_bounds__(64) void shape_setup_kernel(PcvShapeDev* shapes, ui
 
 }  // namespace
 
-extern "C" int pcv_shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t count, pcv_shapes** out) {
+static void release_shapes(pcv_shapes* s) {
+  if (s->d_union) s->ctx->dev_free(s->d_union);
+  if (s->wide) s->ctx->dev_free(s->wide);
+  if (s->dev) s->ctx->dev_free(s->dev);
+  delete s;
+}
+
+static int shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t count, bool with_unions, uint32_t num_unions,
+                         const uint32_t* union_first, const uint64_t* union_cells, pcv_shapes** out) {
   if (!ctx) return PCV_E_INVALID;
   if (!out || (count && !shapes)) return ctx->fail(PCV_E_INVALID, "null argument");
   *out = nullptr;
+  std::vector<uint32_t> union_shapes, union_of;
+  if (with_unions) {
+    std::string why;
+    if (pcv_s2_check_unions(num_unions, union_first, union_cells, &why)) return ctx->fail(PCV_E_INVALID, why);
+    for (uint32_t k = 0; num_unions && k < union_first[num_unions]; ++k)
+      if (s2::level_of(union_cells[k]) == 0u) return ctx->fail(PCV_E_INVALID, "a union with a level-0 cell has no geometry");
+  }
   PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   std::vector<PcvShapeDev> h(count);
   std::vector<uint32_t> wide_of;  // the shapes with a PcvShapeWide
@@ -242,6 +266,12 @@ extern "C" int pcv_shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t
         if (pcv_wmr_corners(s.params, d.corners) != PCV_OK) return ctx->fail(PCV_E_INVALID, "web-mercator rectangle: corners");
         wide_of.push_back(i);
         break;
+      case PCV_SHAPE_S2_CELL_UNION:
+        if (!with_unions) return ctx->fail(PCV_E_INVALID, "a cell union needs its cells: pcv_shapes_create_ex");
+        if (s.reserved < 0 || (uint32_t)s.reserved >= num_unions) return ctx->fail(PCV_E_INVALID, "union index out of range");
+        union_shapes.push_back(i);
+        union_of.push_back((uint32_t)s.reserved);
+        break;
       default: return ctx->fail(PCV_E_INVALID, "unknown shape kind");
     }
   }
@@ -254,14 +284,23 @@ extern "C" int pcv_shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t
   void* p = nullptr;
   int rc = ctx->dev_alloc(&p, sizeof(PcvShapeDev) * (count ? count : 1));
   if (rc) {
-    delete r;
+    release_shapes(r);
     return rc;
   }
   r->dev = (PcvShapeDev*)p;
+  if (!union_shapes.empty()) {
+    r->union_first.assign(union_first, union_first + num_unions + 1);
+    r->union_cells.assign(union_cells, union_cells + union_first[num_unions]);
+    r->union_shapes = union_shapes;
+    r->union_of = union_of;
+    if ((rc = pcv_union_prepare_shapes(ctx, r, h.data()))) {
+      release_shapes(r);
+      return rc;
+    }
+  }
   if (!wide_of.empty()) {
     if ((rc = ctx->dev_alloc(&p, sizeof(PcvShapeWide) * wide_of.size()))) {
-      ctx->dev_free(r->dev);
-      delete r;
+      release_shapes(r);
       return rc;
     }
     r->wide = (PcvShapeWide*)p;
@@ -276,9 +315,7 @@ extern "C" int pcv_shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t
       e = hipStreamSynchronize(ctx->stream);  // `h` must outlive the copy
     }
     if (e != hipSuccess) {
-      if (r->wide) ctx->dev_free(r->wide);
-      ctx->dev_free(r->dev);
-      delete r;
+      release_shapes(r);
       return ctx->fail(PCV_E_HIP, hipGetErrorString(e));
     }
   }
@@ -286,11 +323,30 @@ extern "C" int pcv_shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t
   return PCV_OK;
 }
 
+extern "C" int pcv_shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t count, pcv_shapes** out) {
+  return shapes_create(ctx, shapes, count, false, 0, nullptr, nullptr, out);
+}
+
+extern "C" int pcv_shapes_create_ex(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t count, uint32_t num_unions, const uint32_t* union_first,
+                                    const uint64_t* union_cells, pcv_shapes** out) {
+  return shapes_create(ctx, shapes, count, true, num_unions, union_first, union_cells, out);
+}
+
 extern "C" void pcv_shapes_free(pcv_shapes* s) {
   if (!s) return;
-  if (s->wide) s->ctx->dev_free(s->wide);
-  s->ctx->dev_free(s->dev);
-  delete s;
+  release_shapes(s);
+}
+
+extern "C" int pcv_shapes_union(pcv_shapes* s, uint32_t i, uint64_t capacity, uint64_t* cells, uint32_t* num_cells) {
+  if (!s || i >= s->count) return PCV_E_INVALID;
+  const auto it = std::lower_bound(s->union_shapes.begin(), s->union_shapes.end(), i);
+  if (it == s->union_shapes.end() || *it != i) return s->ctx->fail(PCV_E_INVALID, "shape " + std::to_string(i) + " is not a cell union");
+  if (!num_cells || (capacity && !cells)) return s->ctx->fail(PCV_E_INVALID, "null argument");
+  const uint32_t u = s->union_of[it - s->union_shapes.begin()];
+  const uint32_t n = s->union_first[u + 1] - s->union_first[u];
+  *num_cells = n;
+  if (capacity && n) std::memcpy(cells, s->union_cells.data() + s->union_first[u], 8 * (size_t)std::min<uint64_t>(n, capacity));
+  return PCV_OK;
 }
 
 extern "C" uint32_t pcv_shapes_count(const pcv_shapes* s) { return s ? s->count : 0; }
@@ -298,6 +354,7 @@ extern "C" uint32_t pcv_shapes_count(const pcv_shapes* s) { return s ? s->count 
 extern "C" int pcv_shapes_get(pcv_shapes* s, uint32_t i, double corners[24], double axes[78], uint32_t* num_axes,
                               int* valid) {
   if (!s || i >= s->count) return PCV_E_INVALID;
+  if (s->kinds[i] == PCV_SHAPE_S2_CELL_UNION) return s->ctx->fail(PCV_E_INVALID, "a cell union has no corners or axes: pcv_shapes_union gives its cells");
   if (s->kinds[i] != PCV_SHAPE_WEB_MERCATOR_RECT) {  // (all 78 doubles, as ever)
     pcv_ctx* ctx = s->ctx;
     PcvShapeDev h;
@@ -322,6 +379,7 @@ extern "C" int pcv_shapes_get_ex(pcv_shapes* s, uint32_t i, double corners[24], 
                                  uint32_t* num_axes, int* valid) {
   if (!s || i >= s->count) return PCV_E_INVALID;
   pcv_ctx* ctx = s->ctx;
+  if (s->kinds[i] == PCV_SHAPE_S2_CELL_UNION) return ctx->fail(PCV_E_INVALID, "a cell union has no corners or axes: pcv_shapes_union gives its cells");
   PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   PcvShapeDev h;
   PCV_HIP_CHECK(ctx, hipMemcpy(&h, s->dev + i, sizeof(h), hipMemcpyDeviceToHost));

@@ -351,17 +351,29 @@ class Context:
         """Prepare query shapes on the device. Each entry: ("all",), ("aabb", min3, max3), ("frustum", clip_from_query16),
         ("frustum2", clip_from_query16, query_from_clip16), ("obb", translation3, quat_ijkw4, half_extent3),
         ("web_mercator_rect", north_west2, south_east2) — normalised map coordinates, as web_mercator_rect_from_zoomed
-        returns them; the query space is ECEF."""
+        returns them; the query space is ECEF; ("s2_cells", cell_ids) — PointLocation::S2Cells over an octree: S2 cell ids,
+        ascending, of level 1 or finer, taken as given (not normalized); the query space is ECEF (pcv_shapes_create_ex)."""
         arr = (L.Shape * max(1, len(shapes)))()
+        unions = []
         for i, sh in enumerate(shapes):
             kind = {"all": L.SHAPE_ALL, "aabb": L.SHAPE_AABB, "frustum": L.SHAPE_FRUSTUM, "obb": L.SHAPE_OBB,
-                    "frustum2": L.SHAPE_FRUSTUM_WITH_INVERSE, "web_mercator_rect": L.SHAPE_WEB_MERCATOR_RECT}[sh[0]]
+                    "frustum2": L.SHAPE_FRUSTUM_WITH_INVERSE, "web_mercator_rect": L.SHAPE_WEB_MERCATOR_RECT,
+                    "s2_cells": L.SHAPE_S2_CELL_UNION}[sh[0]]
             arr[i].kind = kind
+            if kind == L.SHAPE_S2_CELL_UNION:
+                arr[i].reserved = len(unions)
+                unions.append(sh[1])
+                continue
             flat = [float(v) for part in sh[1:] for v in np.asarray(part, dtype=np.float64).ravel()]
             for j, v in enumerate(flat):
                 arr[i].params[j] = v
         h = C.c_void_p()
-        self._check(self.lib.pcv_shapes_create(self.handle, arr, len(shapes), C.byref(h)))
+        if unions:
+            first, flat = _s2_unions(unions)
+            self._check(self.lib.pcv_shapes_create_ex(self.handle, arr, len(shapes), len(unions), first.ctypes.data, flat.ctypes.data,
+                                                      C.byref(h)))
+        else:
+            self._check(self.lib.pcv_shapes_create(self.handle, arr, len(shapes), C.byref(h)))
         return Shapes(self, h, len(shapes), [int(arr[i].kind) for i in range(len(shapes))])
 
     def cull_points(self, shapes, shape_index, x, y, z, intensity=None, interval=None):
@@ -898,6 +910,14 @@ class Shapes:
         n, valid = C.c_uint32(), C.c_int()
         self.ctx._check(self.ctx.lib.pcv_shapes_get_ex(self.handle, i, corners, axes, L.MAX_SHAPE_AXES, C.byref(n), C.byref(valid)))
         return np.array(corners[:]).reshape(8, 3), np.array(axes[:3 * n.value]).reshape(n.value, 3), bool(valid.value)
+
+    def union(self, i):
+        """The cell ids of shape i, an ("s2_cells", ...) entry, as given (pcv_shapes_union)."""
+        n = C.c_uint32()
+        self.ctx._check(self.ctx.lib.pcv_shapes_union(self.handle, i, 0, None, C.byref(n)))
+        cells = np.zeros(n.value, dtype=np.uint64)
+        self.ctx._check(self.ctx.lib.pcv_shapes_union(self.handle, i, cells.size, cells.ctypes.data, C.byref(n)))
+        return cells
 
     def free(self):
         if self.handle and self.ctx.handle:
@@ -2295,6 +2315,18 @@ def s2_union_intersects(cells, ids):
     out = np.zeros(ids.size, dtype=np.uint8)
     _host_check(L.load_library().pcv_s2_union_intersects_host(cells.ctypes.data, cells.size, ids.size, ids.ctypes.data, out.ctypes.data),
                 "pcv_s2_union_intersects_host")
+    return out
+
+
+def s2_union_intersects_cubes(cells, cubes):
+    """pcv_s2_union_intersects_cubes_host: cells_intersecting_polyhedron(cells, cube) per cube (n x 4: min xyz, edge) for cell
+    ids ascending, of level 1 or finer, as uint8 flags — the predicate a cell union's node list over an octree is the
+    breadth-first walk of."""
+    cells = np.ascontiguousarray(cells, dtype=np.uint64).ravel()
+    cubes = np.ascontiguousarray(cubes, dtype=np.float64).reshape(-1, 4)
+    out = np.zeros(cubes.shape[0], dtype=np.uint8)
+    _host_check(L.load_library().pcv_s2_union_intersects_cubes_host(cells.ctypes.data, cells.size, cubes.shape[0], cubes.ctypes.data,
+                                                                    out.ctypes.data), "pcv_s2_union_intersects_cubes_host")
     return out
 
 

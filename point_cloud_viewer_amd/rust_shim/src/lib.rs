@@ -144,6 +144,8 @@ extern "C" {
     fn pcv_octree_node(t: *const pcv_octree, i: u64, out: *mut PcvNodeInfo) -> c_int;
     fn pcv_octree_free(t: *mut pcv_octree);
     fn pcv_shapes_create(ctx: *mut pcv_ctx, shapes: *const PcvShape, count: u32, out: *mut *mut pcv_shapes) -> c_int;
+    fn pcv_shapes_create_ex(ctx: *mut pcv_ctx, shapes: *const PcvShape, count: u32, num_unions: u32, union_first: *const u32, union_cells: *const u64,
+                            out: *mut *mut pcv_shapes) -> c_int;
     fn pcv_shapes_free(s: *mut pcv_shapes);
     fn pcv_visible_nodes(ctx: *mut pcv_ctx, frusta: *const pcv_shapes, t: *mut pcv_octree, capacity: u32, counts: *mut u32, node_indices: *mut u32, status: *mut i32) -> c_int;
     // per frustum the nodes whose Relation is not Out, with relation and relative_size_on_screen (octree/mod.rs:119-139, 261-272)
@@ -450,14 +452,51 @@ impl HipOctree {
                 let se = r.south_east().to_zoomed_coordinate(0)? / 256.0;
                 s.params[..4].copy_from_slice(&[nw.x, nw.y, se.x, se.y]);
             }
-            PointLocation::S2Cells(_) => return None, // no octree node culling for a cell union (HipS2Cells below serves S2 clouds)
+            // PCV_SHAPE_S2_CELL_UNION: no parameters; the union's cells travel beside the shape (union_cells, create_shapes)
+            PointLocation::S2Cells(_) => s.kind = 6,
         }
         Some(s)
     }
 
-    fn with_shape<R>(&self, shape: &PcvShape, f: impl FnOnce(*mut pcv_shapes) -> R) -> R {
-        let mut shapes = std::ptr::null_mut();
-        self.ctx.check(unsafe { pcv_shapes_create(self.ctx.0, shape, 1, &mut shapes) });
+    /// The cells of a cell-union location as pcv_shapes_create_ex takes them (ascending, as given otherwise: the library does
+    /// not normalize, and neither does the reference); empty for every other location.
+    fn union_cells(location: &PointLocation) -> Vec<u64> {
+        match location {
+            PointLocation::S2Cells(u) => {
+                let mut v: Vec<u64> = u.0.iter().map(|c| c.0).collect();
+                v.sort_unstable();
+                v
+            }
+            _ => Vec::new(),
+        }
+    }
+
+    /// One prepared table: `cells[i]` are the cells of shape i where it is a cell union (each such shape gets a union of its
+    /// own, named by `reserved`), ignored otherwise.
+    fn create_shapes(&self, shapes: &[PcvShape], cells: &[Vec<u64>]) -> *mut pcv_shapes {
+        let mut table = shapes.to_vec();
+        let mut first = vec![0u32];
+        let mut flat: Vec<u64> = Vec::new();
+        for (s, c) in table.iter_mut().zip(cells) {
+            if s.kind == 6 {
+                s.reserved = (first.len() - 1) as i32;
+                flat.extend_from_slice(c);
+                first.push(flat.len() as u32);
+            }
+        }
+        let mut out = std::ptr::null_mut();
+        self.ctx.check(unsafe {
+            if first.len() == 1 {
+                pcv_shapes_create(self.ctx.0, table.as_ptr(), table.len() as u32, &mut out)
+            } else {
+                pcv_shapes_create_ex(self.ctx.0, table.as_ptr(), table.len() as u32, (first.len() - 1) as u32, first.as_ptr(), flat.as_ptr(), &mut out)
+            }
+        });
+        out
+    }
+
+    fn with_shape<R>(&self, shape: &PcvShape, cells: &[u64], f: impl FnOnce(*mut pcv_shapes) -> R) -> R {
+        let shapes = self.create_shapes(std::slice::from_ref(shape), &[cells.to_vec()]);
         let r = f(shapes);
         unsafe { pcv_shapes_free(shapes) };
         r
@@ -493,12 +532,12 @@ fn query_key(query: &PointQuery) -> String {
 }
 
 /// Shape + intensity interval of a query the library serves; None: the reference's host path.
-fn library_query(query: &PointQuery) -> Option<(PcvShape, Option<[f64; 2]>)> {
+fn library_query(query: &PointQuery) -> Option<(PcvShape, Option<[f64; 2]>, Vec<u64>)> {
     if !query.filter_intervals.keys().all(|k| *k == "intensity") {
         return None; // an interval on another attribute
     }
     let shape = HipOctree::shape_of(&query.location)?;
-    Some((shape, query.filter_intervals.get("intensity").map(|iv| [iv.lower_bound, iv.upper_bound])))
+    Some((shape, query.filter_intervals.get("intensity").map(|iv| [iv.lower_bound, iv.upper_bound]), HipOctree::union_cells(&query.location)))
 }
 
 /// Host arrays of n points handed to `callback` as PointsBatches of `batch_size` with the query's attributes.
@@ -535,10 +574,9 @@ struct HostPoints {
 
 impl HipOctree {
     /// Runs one batch over `shapes` (with per-shape intensity intervals) and returns it with its segment table.
-    fn run_batch(&self, shapes: &[PcvShape], intervals: &[Option<[f64; 2]>]) -> (*mut pcv_query_batch, Vec<u64>, Vec<u32>, Vec<u64>) {
+    fn run_batch(&self, shapes: &[PcvShape], cells: &[Vec<u64>], intervals: &[Option<[f64; 2]>]) -> (*mut pcv_query_batch, Vec<u64>, Vec<u32>, Vec<u64>) {
         let mut handle = std::ptr::null_mut();
-        let mut prepared = std::ptr::null_mut();
-        self.ctx.check(unsafe { pcv_shapes_create(self.ctx.0, shapes.as_ptr(), shapes.len() as u32, &mut prepared) });
+        let prepared = self.create_shapes(shapes, cells);
         let flat: Vec<f64> = intervals.iter().flat_map(|iv| iv.unwrap_or([0.0, 0.0])).collect();
         let used: Vec<u8> = intervals.iter().map(|iv| iv.is_some() as u8).collect();
         let rc = unsafe { pcv_query_batch_run(self.ctx.0, prepared, self.tree, flat.as_ptr(), used.as_ptr(), &mut handle) };
@@ -554,12 +592,12 @@ impl HipOctree {
     }
 
     /// One node through pcv_query_node_points (a node the query's location does not list). Called under `lock`.
-    fn node_points_single(&self, shape: &PcvShape, interval: Option<[f64; 2]>, node: u64, want_intensity: bool) -> HostPoints {
+    fn node_points_single(&self, shape: &PcvShape, cells: &[u64], interval: Option<[f64; 2]>, node: u64, want_intensity: bool) -> HostPoints {
         let cap = self.infos[node as usize].num_points as usize;
         let mut p = HostPoints { n: 0, x: vec![0f64; cap], y: vec![0f64; cap], z: vec![0f64; cap], rgb: vec![0u8; 3 * cap], intensity: vec![0f32; if want_intensity { cap } else { 0 }] };
         let has_int = unsafe { pcv_octree_has_intensity(self.tree) } != 0;
         let mut count = 0u64;
-        self.with_shape(shape, |shapes| {
+        self.with_shape(shape, cells, |shapes| {
             self.ctx.check(unsafe {
                 pcv_query_node_points(self.ctx.0, shapes, 0, self.tree, node, interval.as_ref().map_or(std::ptr::null(), |iv| iv.as_ptr()), cap as u64, 0,
                                       p.x.as_mut_ptr(), p.y.as_mut_ptr(), p.z.as_mut_ptr(), p.rgb.as_mut_ptr(),
@@ -590,13 +628,14 @@ impl HipOctree {
     where
         F: FnMut(usize, PointsBatch) -> Result<()>,
     {
-        let served: Vec<Option<(PcvShape, Option<[f64; 2]>)>> = queries.iter().map(library_query).collect();
-        let shapes: Vec<PcvShape> = served.iter().flatten().map(|(s, _)| *s).collect();
-        let intervals: Vec<Option<[f64; 2]>> = served.iter().flatten().map(|(_, iv)| *iv).collect();
+        let served: Vec<Option<(PcvShape, Option<[f64; 2]>, Vec<u64>)>> = queries.iter().map(library_query).collect();
+        let shapes: Vec<PcvShape> = served.iter().flatten().map(|(s, _, _)| *s).collect();
+        let intervals: Vec<Option<[f64; 2]>> = served.iter().flatten().map(|(_, iv, _)| *iv).collect();
+        let cells: Vec<Vec<u64>> = served.iter().flatten().map(|(_, _, c)| c.clone()).collect();
         let mut batch = None;
         if !shapes.is_empty() {
             let _g = self.lock.lock().unwrap();
-            batch = Some(self.run_batch(&shapes, &intervals));
+            batch = Some(self.run_batch(&shapes, &cells, &intervals));
         }
         let mut s = 0usize;
         let mut result = Ok(());
@@ -634,7 +673,7 @@ impl PointCloud for HipOctree {
             None => return self.inner.nodes_in_location(location),
         };
         let _g = self.lock.lock().unwrap();
-        self.with_shape(&shape, |shapes| {
+        self.with_shape(&shape, &Self::union_cells(location), |shapes| {
             let cap = self.ids.len().max(1);
             let mut count = 0u32;
             let mut idx = vec![0u32; cap];
@@ -670,7 +709,7 @@ impl PointCloud for HipOctree {
     where
         F: FnMut(PointsBatch) -> Result<()>,
     {
-        let (shape, interval) = match library_query(query) {
+        let (shape, interval, cells) = match library_query(query) {
             Some(v) => v,
             None => {
                 // no kernel for this location / an interval on another attribute: the reference's host path
@@ -690,7 +729,7 @@ impl PointCloud for HipOctree {
             let k = match cache.entries.iter().position(|e| e.key == key) {
                 Some(k) => k,
                 None => {
-                    let (batch, _, nodes, offset) = self.run_batch(&[shape], &[interval]);
+                    let (batch, _, nodes, offset) = self.run_batch(&[shape], &[cells.clone()], &[interval]);
                     let node_segment = nodes.iter().enumerate().map(|(k, &n)| (n as u64, k as u64)).collect();
                     if cache.entries.len() == BATCH_CACHE_ENTRIES {
                         unsafe { pcv_query_batch_free(cache.entries.remove(0).batch) };
@@ -702,7 +741,7 @@ impl PointCloud for HipOctree {
             let e = &cache.entries[k];
             match e.node_segment.get(&node) {
                 Some(&seg) => self.batch_points(e.batch, &e.offset, seg, 1, query.attributes.contains(&"intensity")),
-                None => self.node_points_single(&shape, interval, node, query.attributes.contains(&"intensity")), // not in the location's list
+                None => self.node_points_single(&shape, &cells, interval, node, query.attributes.contains(&"intensity")), // not in the location's list
             }
         };
         emit_points(query, &points, batch_size, callback)
@@ -716,7 +755,7 @@ impl HipOctree {
         let mut shape = PcvShape { kind: 2, reserved: 0, params: [0.0; 32] };
         shape.params[..16].copy_from_slice(projection_matrix.as_slice()); // nalgebra storage is column-major
         let _g = self.lock.lock().unwrap();
-        self.with_shape(&shape, |shapes| {
+        self.with_shape(&shape, &[], |shapes| {
             let m = self.ids.len().max(1);
             let (mut count, mut status) = (0u32, 0i32);
             let mut idx = vec![0u32; m];
@@ -737,7 +776,7 @@ impl HipOctree {
         shape.params[..16].copy_from_slice(world_to_gl.as_slice()); // nalgebra storage is column-major
         let params = PcvRenderParams { width, height, point_size, gamma, max_nodes: max_nodes_to_display.min(u32::MAX as usize) as u32, max_workspace_bytes: 0 };
         let _g = self.lock.lock().unwrap();
-        self.with_shape(&shape, |shapes| {
+        self.with_shape(&shape, &[], |shapes| {
             let mut frame = std::ptr::null_mut();
             let overlay = PcvRenderOverlay { flags: show_octree_nodes as u32, outline_rgba: [255, 255, 0, 255] };
             self.ctx.check(unsafe { pcv_render_views_ex(self.ctx.0, shapes, self.tree, &params, &overlay, &mut frame) });
