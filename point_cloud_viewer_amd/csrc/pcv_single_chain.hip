@@ -182,15 +182,10 @@ static bool plan_sample(SingleChain& s) {
   const uint64_t n = s.bs->n;
   const uint32_t max_points = s.max_points;
   const int full_levels = s.full_levels;
-  // sample stride: every 64th point (>= 1 500 sample points per full node at the reference's capacity: a candidate band of
-  // +-13 % around it); small forced builds (tests) sample more densely. Round 5, one call, 100 M points: stride 32 / 48 / 64 /
-  // 96 -> 5.02 / 4.97 / 4.95-4.98 / 4.96 ms per build — the sample phase shrinks by 0.07 ms, 1.5 M more points continue
-  // their chain in the settle pass, the prediction holds either way (profiles/r05_ab_sample_stride.json)
-  uint64_t stride = 64;
-  while (stride > 1 && n / stride < 4096) stride >>= 1;
-  // a node at the capacity must still hold a few dozen sample points, or the band around the capacity (five standard
-  // deviations of the scaled count) swallows every node and the prediction opens all of them (tiny capacities in tests)
-  while (stride > 1 && (uint64_t)max_points / stride < 64) stride >>= 1;
+  // the stride and the band rule: pcv_spec_sample_plan (pcv_spec.cpp), which the tests ask as well
+  uint32_t stride;
+  double delta;
+  pcv_spec_sample_plan(n, max_points, &stride, &delta);
   s.stride = stride;
   s.ns = n / stride;
   if (s.ns == 0) return false;
@@ -201,8 +196,7 @@ static bool plan_sample(SingleChain& s) {
   sp.nlevels = full_levels;
   sp.force_mask = (s.params->flags >> 8) & 0xffu;
   sp.scale = (double)stride;
-  // band of five standard deviations of the scaled sample count of a node that holds exactly `cap` points
-  sp.delta = stride == 1 ? 0.0 : std::fmin(0.9, std::fmax(0.02, 5.0 * std::sqrt((double)stride / (double)max_points)));
+  sp.delta = delta;
   s.upper = (double)sp.cap * (1.0 + sp.delta) / sp.scale;
   // T'' nodes at most (at least 4 096 records: the chain pass may mirror the table's first 2 048 in LDS without asking how many exist)
   s.tcap = std::max<size_t>(1 + 8 * (size_t)s.nt.capacity, 4096);

@@ -18,6 +18,21 @@ constexpr int kKeyLevels = PCV_MAX_KEY_LEVELS;  // 21 levels x 3 bits, level 1 a
 inline uint64_t digit_bits(unsigned c, int level) { return (uint64_t)c << (3 * (kKeyLevels - level)); }
 }  // namespace
 
+extern "C" void pcv_spec_sample_plan(uint64_t n, uint32_t max_points, uint32_t* stride_out, double* delta_out) {
+  // sample stride: every 64th point (>= 1 500 sample points per full node at the reference's capacity: a candidate band of
+  // +-13 % around it); small forced builds (tests) sample more densely. Round 5, one call, 100 M points: stride 32 / 48 / 64 /
+  // 96 -> 5.02 / 4.97 / 4.95-4.98 / 4.96 ms per build — the sample phase shrinks by 0.07 ms, 1.5 M more points continue
+  // their chain in the settle pass, the prediction holds either way (profiles/r05_ab_sample_stride.json)
+  uint64_t stride = 64;
+  while (stride > 1 && n / stride < 4096) stride >>= 1;
+  // a node at the capacity must still hold a few dozen sample points, or the band around the capacity (five standard
+  // deviations of the scaled count) swallows every node and the prediction opens all of them (tiny capacities in tests)
+  while (stride > 1 && (uint64_t)max_points / stride < 64) stride >>= 1;
+  *stride_out = (uint32_t)stride;
+  // band of five standard deviations of the scaled sample count of a node that holds exactly `cap` points
+  *delta_out = stride == 1 ? 0.0 : std::fmin(0.9, std::fmax(0.02, 5.0 * std::sqrt((double)stride / (double)max_points)));
+}
+
 uint32_t pcv_spec_sample_threshold(const PcvSpecParams& p) {
   // open a sample node iff count_s * scale > cap * (1 - delta)  <=>  count_s > floor(cap * (1 - delta) / scale)
   const double t = std::floor((double)p.cap * (1.0 - p.delta) / p.scale);
@@ -293,7 +308,7 @@ extern "C" int pcv_worklist_selftest(const uint32_t* lo, const uint32_t* count, 
 static int spec_selftest(const uint64_t* keys, uint64_t n, uint32_t stride, uint32_t cap, double delta, double resolution,
                          const double* edge, int nlevels, uint32_t force_mask, uint64_t node_capacity, uint64_t* out_prefix,
                          uint8_t* out_level, uint64_t* out_count, uint8_t* out_open, uint64_t* out_num_nodes, uint64_t* out_stats /* [4] */,
-                         uint32_t* const out_table[3], uint8_t* out_mask) {
+                         uint32_t* const out_table[3], uint8_t* out_mask, uint32_t clump_shift = 0) {
   PcvSpecParams p;
   p.cap = cap;
   p.resolution = resolution;
@@ -303,7 +318,12 @@ static int spec_selftest(const uint64_t* keys, uint64_t n, uint32_t stride, uint
   p.scale = (double)stride;
   p.delta = delta;
   std::vector<uint64_t> sample;
-  for (uint64_t i = 0; i < n; i += stride) sample.push_back(keys[i]);
+  if (clump_shift == 0) {
+    for (uint64_t i = 0; i < n; i += stride) sample.push_back(keys[i]);
+  } else {  // the build's own sample (chain_keys_kernel): n / stride points, 2^clump_shift consecutive ones per clump
+    for (uint64_t i = 0; i < n / stride; ++i)
+      sample.push_back(keys[(((i >> clump_shift) * stride) << clump_shift) + (i & ((1ull << clump_shift) - 1ull))]);
+  }
   std::sort(sample.begin(), sample.end());
   const uint32_t thr = pcv_spec_sample_threshold(p);
   // sample tree exactly as pcv_launch_node_split lays it out
@@ -466,6 +486,15 @@ extern "C" int pcv_spec_selftest(const uint64_t* keys, uint64_t n, uint32_t stri
                                  uint8_t* out_open, uint64_t* out_num_nodes, uint64_t* out_stats /* [4] */) {
   return spec_selftest(keys, n, stride, cap, delta, resolution, edge, nlevels, force_mask, node_capacity, out_prefix, out_level,
                        out_count, out_open, out_num_nodes, out_stats, nullptr, nullptr);
+}
+// The same with the sample the build takes on the device: clumps of 8 consecutive keys, one clump every 8 x stride keys
+// (pcv_single_chain.hip sample_round; tests/test_order_cases_cpu.py predicts what an input ORDER does to the build).
+extern "C" int pcv_spec_selftest_clumps(const uint64_t* keys, uint64_t n, uint32_t stride, uint32_t cap, double delta,
+                                        double resolution, const double* edge, int nlevels, uint32_t force_mask,
+                                        uint64_t node_capacity, uint64_t* out_prefix, uint8_t* out_level, uint64_t* out_count,
+                                        uint8_t* out_open, uint64_t* out_num_nodes, uint64_t* out_stats /* [4] */) {
+  return spec_selftest(keys, n, stride, cap, delta, resolution, edge, nlevels, force_mask, node_capacity, out_prefix, out_level,
+                       out_count, out_open, out_num_nodes, out_stats, nullptr, nullptr, stride > 1 ? 3u : 0u);
 }
 // The same with the whole node table (tests/test_tables_cpu.py feeds it to pcv_tables_selftest).
 extern "C" int pcv_spec_selftest_table(const uint64_t* keys, uint64_t n, uint32_t stride, uint32_t cap, double delta,

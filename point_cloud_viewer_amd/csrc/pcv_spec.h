@@ -46,6 +46,11 @@ struct PcvSpecParams {
   double delta = 0;         // relative half width of the candidate band around the capacity
 };
 
+// Sample plan of a build of n points at capacity max_points (the single source of plan_sample, pcv_single_chain.hip, and of
+// the tests that construct clouds around the sample: tests/order_cases.py). The device reads 8 consecutive points every
+// 8 x stride input positions (stride 1: every point); delta is PcvSpecParams::delta.
+extern "C" void pcv_spec_sample_plan(uint64_t n, uint32_t max_points, uint32_t* stride, double* delta);
+
 // Node table of the SAMPLE tree as pcv_launch_node_split leaves it (BFS order, children contiguous in digit order).
 struct PcvSampleTable {
   uint32_t num_nodes = 0;

@@ -70,8 +70,10 @@ def test_the_cases_above_covered_every_branch_of_the_prediction():
 
 
 def test_oversampled_clusters_replay_the_chain_from_their_coordinates(ctx):
-    """A sample that over-counts: six tight clusters of 700 points sit exactly at the sampled input positions (8
-    consecutive points every 256), so their level-2 nodes look like 30 k points to the prediction — above the candidate
+    """A sample that over-counts: six tight clusters of 700 points sit at input positions i % 256 < 8. The build samples 8
+    consecutive points every 512 (stride 64 at 600 000 points and capacity 20 000: pcv_spec_sample_plan, csrc/pcv_spec.cpp), so
+    half of every cluster is in the sample — 64 x 350 on top of 9 k background points —
+    and their level-2 nodes look like 30 k points to the prediction — above the candidate
     band, split without kept codes — while the exact counts (~10 k < capacity 20 k) make those nodes LEAVES. Their points
     went down to candidates below the leaf, so their records hold codes of a deeper level: the one case that still needs
     the coordinates (PCV_SPEC_MAP_REPLAY). (The clusters take a fifth of the sampled slots; more would starve the sample
