@@ -62,5 +62,13 @@ PCV_SA(offsetof(pcv_render_params, width) == 0 && offsetof(pcv_render_params, he
        "pcv_render_params fields");
 PCV_SA(sizeof(pcv_render_overlay) == 8, "pcv_render_overlay");
 PCV_SA(offsetof(pcv_render_overlay, flags) == 0 && offsetof(pcv_render_overlay, outline_rgba) == 4, "pcv_render_overlay fields");
+PCV_SA(sizeof(pcv_s2_stream_params) == 32, "pcv_s2_stream_params");
+PCV_SA(offsetof(pcv_s2_stream_params, struct_size) == 0 && offsetof(pcv_s2_stream_params, split_level) == 4 &&
+           offsetof(pcv_s2_stream_params, directory) == 8 && offsetof(pcv_s2_stream_params, open_mode) == 16 &&
+           offsetof(pcv_s2_stream_params, flush_points) == 24,
+       "pcv_s2_stream_params fields");
+PCV_SA(sizeof(pcv_s2_merge_segment) == 24 && offsetof(pcv_s2_merge_segment, src_offset) == 8 && offsetof(pcv_s2_merge_segment, part) == 16 &&
+           offsetof(pcv_s2_merge_segment, count) == 20,
+       "pcv_s2_merge_segment");
 
 #endif

@@ -1226,7 +1226,7 @@ int pcv_s2_union_contains_host(const uint64_t* cells, uint32_t num_cells, uint64
  * A point whose radius sqrt(x*x + y*y + z*z) is above 6 384 400 or below 6 352 800 (s2.rs:64-65), or that has a NaN coordinate
  * (a departure: the reference lets NaN through both comparisons), is invalid: PCV_E_INVALID, pcv_last_error names the FIRST such
  * point in input order with its index and coordinates, *out is NULL. The bounding box is the exact min / max of the points.
- * Appending batches across calls and OpenMode::Append are not provided. */
+ * A stream of batches, clouds larger than the device and OpenMode::Append: pcv_s2_stream_* below. */
 typedef struct pcv_s2_cloud pcv_s2_cloud;
 int pcv_s2_split(pcv_ctx* ctx, const pcv_points* points, uint32_t split_level, pcv_s2_cloud** out);
 /* Any output may be NULL. */
@@ -1259,6 +1259,81 @@ int pcv_s2_write_dir(pcv_s2_cloud* cloud, const char* directory);
  * cell_points into host memory and write_dir work, anything that needs the device is PCV_E_INVALID. */
 int pcv_s2_open_dir(pcv_ctx* ctx, const char* directory, pcv_s2_cloud** out);
 void pcv_s2_free(pcv_s2_cloud* cloud);
+
+/* ---- S2 cell clouds from a stream of batches ----------------------------------------- */
+/* S2Splitter as the NodeWriter<PointsBatch> it is (src/read_write/s2.rs:60-173): `write` once per batch for as long as the
+ * input lasts, `get_meta` at the end. Every batch is split as pcv_s2_split splits it and waits on the device as a part; the
+ * cloud is the parts' merge by cell, the batches in their order inside a cell (one kernel launch, planned by
+ * pcv_s2_merge_plan_host's code).
+ *   directory == NULL   in-memory: pcv_s2_stream_finish returns the cloud that pcv_s2_split of the concatenated batches returns
+ *                       (cells, bbox, level, blobs, pcv_s2_order as indices into the concatenation). Fewer than 2^32 - 1 points in
+ *                       all: the append that crosses it is PCV_E_INVALID.
+ *   directory != NULL   the cells' files are written as the stream goes: whenever the pending parts hold flush_points points or
+ *                       more (0: 2^26; at most 2^31) and once more at finish, if anything is pending, they are merged, copied to
+ *                       pinned host memory and every cell's run is appended to <token>.xyz/.rgb[/.intensity] — a file is
+ *                       truncated the first time THIS stream writes its cell and appended to afterwards (s2.rs:121-136); files of
+ *                       cells the stream never sees are left alone. Only per-cell counts (u64) and the bounding box are held
+ *                       between flushes: the total is unbounded. finish writes meta.pb as pcv_s2_write_dir does; the directory
+ *                       is byte for byte that of pcv_s2_write_dir(pcv_s2_split(concatenation)), whatever the batching and
+ *                       flush_points. No input order is kept.
+ *   PCV_S2_APPEND       (OpenMode::Append) the directory must hold an S2 meta.pb (pcv_s2_open_dir's failures and messages) whose
+ *                       cells are all of split_level (else PCV_E_INVALID); its intensity presence is the stream's; no file is
+ *                       truncated; finish writes a meta.pb whose counts are the old plus the new and whose bbox is the union. A
+ *                       departure: the reference's splitter in append mode reports only what it saw itself and leaves the
+ *                       bookkeeping to its caller.
+ * Checked in this order, each PCV_E_INVALID (with a NULL ctx the message is pcv_host_last_error's): params / out NULL,
+ * struct_size, split_level above 30, open_mode, PCV_S2_APPEND without a directory, flush_points, the directory appended to, ctx
+ * NULL. */
+#define PCV_S2_TRUNCATE 0
+#define PCV_S2_APPEND 1
+typedef struct pcv_s2_stream_params {
+  uint32_t struct_size; /* sizeof(pcv_s2_stream_params) */
+  uint32_t split_level; /* 0 ..= 30 */
+  const char* directory; /* NULL: in-memory */
+  int32_t open_mode;     /* PCV_S2_TRUNCATE / PCV_S2_APPEND */
+  uint32_t reserved;
+  uint64_t flush_points; /* directory mode: pending points that trigger a flush; 0 = the default */
+} pcv_s2_stream_params;
+typedef struct pcv_s2_stream pcv_s2_stream;
+int pcv_s2_stream_begin(pcv_ctx* ctx, const pcv_s2_stream_params* params, pcv_s2_stream** out);
+/* S2Splitter::write for one batch (host or device memory, color_stride 3 or 4; pcv_s2_split's requirements). The first
+ * non-empty batch decides whether the cloud has intensity; a later one that differs is PCV_E_INVALID "S2Splitter received
+ * incompatible data types for attribute intensity" (s2.rs:155). An invalid point refuses the batch with pcv_s2_split's
+ * message; every refusal of a batch ends in " (batch K of the stream)", K = the batches accepted so far. A refused batch
+ * leaves nothing behind and does not count; the stream stays usable. An empty batch counts as a batch and changes nothing
+ * else. A flush that fails (PCV_E_IO naming the file, PCV_E_OOM, PCV_E_HIP) leaves a stream that can only be finished (which
+ * reports the failure again) or aborted. */
+int pcv_s2_stream_append(pcv_s2_stream* stream, const pcv_points* batch);
+/* Any output may be NULL: batches accepted, points (with those of the directory appended to), distinct cells so far (likewise),
+ * points of the pending parts, flushes done. */
+int pcv_s2_stream_info(const pcv_s2_stream* stream, uint64_t* batches, uint64_t* points, uint64_t* cells, uint64_t* pending_points,
+                       uint64_t* flushes);
+/* S2Splitter::get_meta (s2.rs:139-173). Consumes the stream, success or not. In-memory: *out is the cloud (required). Directory
+ * mode: the last flush, meta.pb, and in *out (may be NULL) the cloud that pcv_s2_open_dir opens over the directory. No points at
+ * all: what pcv_s2_split / pcv_s2_write_dir make of none. PCV_E_OOM at a merge is reported as such. */
+int pcv_s2_stream_finish(pcv_s2_stream* stream, pcv_s2_cloud** out);
+/* Drops the stream and its pending parts; files already written stay. NULL is ignored. */
+void pcv_s2_stream_abort(pcv_s2_stream* stream);
+/* For tests: lowers the point limit of an in-memory stream from 2^32 - 1 to max_points (1 ..= 2^32 - 1), so that the refusal
+ * can be reached; it is decided from the host-side counts alone. */
+int pcv_s2_stream_set_memory_cap(pcv_s2_stream* stream, uint64_t max_points);
+
+/* The merge plan, host only, no context (failures: pcv_host_last_error). Input: num_parts parts, part p's cells at
+ * [part_first[p], part_first[p + 1]) of part_ids / part_counts (part_first[0] == 0), ids ascending strictly inside a part and
+ * never 0, counts above 0, fewer than 2^32 - 1 points per part — anything else is PCV_E_INVALID. chunk_points: 0 = the
+ * kernel's 2 048. Output: the merged cells (ids ascending, counts, offsets in points); one segment per (cell, part that holds
+ * it) ordered by cell, then by part, which tile [0, n) in that order; for every output chunk of chunk_points points the index of
+ * the segment that holds its first point. The three sizes are always written; arrays that are NULL are skipped (call once for
+ * the sizes, once for the arrays). Deterministic. */
+typedef struct pcv_s2_merge_segment {
+  uint64_t dst_offset; /* first point in the merged blobs */
+  uint64_t src_offset; /* first point in the part's blobs */
+  uint32_t part;
+  uint32_t count;
+} pcv_s2_merge_segment;
+int pcv_s2_merge_plan_host(uint32_t num_parts, const uint64_t* part_first, const uint64_t* part_ids, const uint64_t* part_counts,
+                           uint32_t chunk_points, uint64_t* num_cells, uint64_t* num_segments, uint64_t* num_chunks, uint64_t* ids,
+                           uint64_t* counts, uint64_t* offsets, pcv_s2_merge_segment* segments, uint64_t* chunk_first_segment);
 
 /* ---- S2 cell clouds: the region side -------------------------------------------------- */
 /* What S2Cells::nodes_in_location (src/s2_cells/mod.rs:160-241) asks of the s2 crate, restated from the public S2 definition

@@ -163,6 +163,18 @@ class SortPlanInfo(C.Structure):
                 ("passes", SortPassInfo * 8)]
 
 
+class S2StreamParams(C.Structure):  # pcv_s2_stream_params
+    _fields_ = [("struct_size", C.c_uint32), ("split_level", C.c_uint32), ("directory", C.c_char_p), ("open_mode", C.c_int32),
+                ("reserved", C.c_uint32), ("flush_points", C.c_uint64)]
+
+
+class S2MergeSegment(C.Structure):  # pcv_s2_merge_segment
+    _fields_ = [("dst_offset", C.c_uint64), ("src_offset", C.c_uint64), ("part", C.c_uint32), ("count", C.c_uint32)]
+
+
+S2_TRUNCATE, S2_APPEND = 0, 1  # pcv_s2_stream_params.open_mode
+
+
 class OocStats(C.Structure):
     _fields_ = [("points", C.c_uint64), ("nodes", C.c_uint64), ("partitions", C.c_uint64), ("largest_bucket", C.c_uint64),
                 ("spill_bytes", C.c_uint64), ("h2d_bytes", C.c_uint64), ("d2h_bytes", C.c_uint64), ("h2d_ms", C.c_double),
@@ -360,6 +372,14 @@ _SIGNATURES = {
     "pcv_s2_query_free": (None, [_vp]),
     "pcv_s2_open_dir": (C.c_int, [_vp, C.c_char_p, C.POINTER(_vp)]),
     "pcv_s2_free": (None, [_vp]),
+    "pcv_s2_stream_begin": (C.c_int, [_vp, C.POINTER(S2StreamParams), C.POINTER(_vp)]),
+    "pcv_s2_stream_append": (C.c_int, [_vp, C.POINTER(Points)]),
+    "pcv_s2_stream_info": (C.c_int, [_vp] + [C.POINTER(C.c_uint64)] * 5),
+    "pcv_s2_stream_finish": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "pcv_s2_stream_abort": (None, [_vp]),
+    "pcv_s2_stream_set_memory_cap": (C.c_int, [_vp, C.c_uint64]),
+    "pcv_s2_merge_plan_host": (C.c_int, [C.c_uint32, _vp, _vp, _vp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint64), _vp, _vp, _vp, _vp, _vp]),
     "pcv_s2_cell_geometry_host": (C.c_int, [C.c_uint64, _vp]),
     "pcv_s2_cell_rect_host": (C.c_int, [C.c_uint64, _vp]),
     "pcv_s2_corners_rect_host": (C.c_int, [_vp, _vp]),

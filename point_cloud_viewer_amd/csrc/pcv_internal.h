@@ -115,6 +115,7 @@ enum PcvKernelId {
   PCV_K_S2_FLAGS,             // pcv_s2_points.hip: keep flags of every candidate point of every (location, listed cell)
   PCV_K_S2_GATHER_POINTS,     // pcv_s2_points.hip: the kept points of a segment range into the caller's planes
   PCV_K_UNION_NODE_RECTS,     // pcv_union.hip: once per octree, the rect of every node cube's corners (cell unions over the octree)
+  PCV_K_S2_MERGE,             // pcv_s2_stream.hip: the cell-sorted parts of a stream into one cell-contiguous cloud, by output chunk
   PCV_K_COUNT
 };
 
@@ -648,4 +649,10 @@ int pcv_host_fail(int code, const std::string& msg);
 int pcv_s2_write_files(const char* directory, const double bbox_min[3], const double bbox_max[3], uint64_t num_cells,
                        const uint64_t* ids, const uint64_t* counts, const uint64_t* offsets, const uint8_t* xyz, const uint8_t* rgb,
                        const uint8_t* intensity /* null: no intensity attribute */, std::string* error);
+// its two halves, as a stream of batches needs them (pcv_s2_stream.hip): the cells' runs onto their files — truncate: null (every
+// file is written anew), or one byte per cell, 0 = the run is appended to what the file holds — and meta.pb alone
+int pcv_s2_write_cells(const char* directory, uint64_t num_cells, const uint64_t* ids, const uint64_t* counts, const uint64_t* offsets,
+                       const uint8_t* truncate, const uint8_t* xyz, const uint8_t* rgb, const uint8_t* intensity, std::string* error);
+int pcv_s2_write_meta(const char* directory, const double bbox_min[3], const double bbox_max[3], uint64_t num_cells, const uint64_t* ids,
+                      const uint64_t* counts, bool has_intensity, std::string* error);
 std::string pcv_s2_token(uint64_t id);

@@ -69,8 +69,8 @@ bool write_file(const std::string& path, const uint8_t* data, uint64_t len) {
   return fclose(f) == 0 && ok;
 }
 // one file of a node: open relative to the directory handle (no path walk), one write, close
-bool write_file_at(int dirfd, const std::string& name, const uint8_t* data, uint64_t len) {
-  const int fd = openat(dirfd, name.c_str(), O_CREAT | O_WRONLY | O_TRUNC | O_CLOEXEC, 0666);
+bool write_file_at(int dirfd, const std::string& name, const uint8_t* data, uint64_t len, bool append = false) {
+  const int fd = openat(dirfd, name.c_str(), O_CREAT | O_WRONLY | (append ? O_APPEND : O_TRUNC) | O_CLOEXEC, 0666);
   if (fd < 0) return false;
   bool ok = true;
   while (len) {
@@ -297,38 +297,54 @@ std::string pcv_s2_token(uint64_t id) {
   return s;
 }
 
-int pcv_s2_write_files(const char* directory, const double bbox_min[3], const double bbox_max[3], uint64_t num_cells,
-                       const uint64_t* ids, const uint64_t* counts, const uint64_t* offsets, const uint8_t* xyz, const uint8_t* rgb,
-                       const uint8_t* intensity, std::string* error) {
-  const std::string dir(directory);
+namespace {
+int s2_open_directory(const std::string& dir, std::string* error) {
   ::mkdir(dir.c_str(), 0777);
   struct stat st;
   if (stat(dir.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) {
     *error = "cannot create directory " + dir;
-    return PCV_E_IO;
+    return -1;
   }
   const int dirfd = open(dir.c_str(), O_RDONLY | O_DIRECTORY | O_CLOEXEC);
-  if (dirfd < 0) {
-    *error = "cannot open directory " + dir;
-    return PCV_E_IO;
-  }
-  std::vector<uint8_t> s2;
+  if (dirfd < 0) *error = "cannot open directory " + dir;
+  return dirfd;
+}
+}  // namespace
+
+// The runs of one merged flush of a stream (pcv_s2_stream.hip) onto the cells' files: S2Splitter::write's loop over its cells
+// (s2.rs:121-136) — truncate[k] set: the stream's first write of the cell in OpenMode::Truncate; otherwise the run is appended
+int pcv_s2_write_cells(const char* directory, uint64_t num_cells, const uint64_t* ids, const uint64_t* counts, const uint64_t* offsets,
+                       const uint8_t* truncate, const uint8_t* xyz, const uint8_t* rgb, const uint8_t* intensity, std::string* error) {
+  const std::string dir(directory);
+  const int dirfd = s2_open_directory(dir, error);
+  if (dirfd < 0) return PCV_E_IO;
   for (uint64_t k = 0; k < num_cells && error->empty(); ++k) {
     const std::string stem = pcv_s2_token(ids[k]);
     const uint64_t at = offsets[k], np = counts[k];
-    if (!write_file_at(dirfd, stem + ".xyz", xyz + at * 24, np * 24)) *error = "cannot write " + dir + "/" + stem + ".xyz";
-    else if (!write_file_at(dirfd, stem + ".rgb", rgb + at * 3, np * 3)) *error = "cannot write " + dir + "/" + stem + ".rgb";
-    else if (intensity && !write_file_at(dirfd, stem + ".intensity", intensity + at * 4, np * 4))
+    const bool append = truncate && !truncate[k];
+    if (!write_file_at(dirfd, stem + ".xyz", xyz + at * 24, np * 24, append)) *error = "cannot write " + dir + "/" + stem + ".xyz";
+    else if (!write_file_at(dirfd, stem + ".rgb", rgb + at * 3, np * 3, append)) *error = "cannot write " + dir + "/" + stem + ".rgb";
+    else if (intensity && !write_file_at(dirfd, stem + ".intensity", intensity + at * 4, np * 4, append))
       *error = "cannot write " + dir + "/" + stem + ".intensity";
+  }
+  ::close(dirfd);
+  return error->empty() ? PCV_OK : PCV_E_IO;
+}
+
+// meta.pb of an S2 directory: S2Splitter::get_meta (s2.rs:139-173) as Meta::to_proto serialises it
+int pcv_s2_write_meta(const char* directory, const double bbox_min[3], const double bbox_max[3], uint64_t num_cells, const uint64_t* ids,
+                      const uint64_t* counts, bool has_intensity, std::string* error) {
+  const std::string dir(directory);
+  ::mkdir(dir.c_str(), 0777);  // (a stream that saw no point has written no cell)
+  std::vector<uint8_t> s2;
+  for (uint64_t k = 0; k < num_cells; ++k) {
     std::vector<uint8_t> cell;  // S2Cell
     tag(cell, 1, 0);
     varint(cell, ids[k]);
     tag(cell, 2, 0);
-    varint(cell, np);
+    varint(cell, counts[k]);
     bytes_field(s2, 1, cell);
   }
-  ::close(dirfd);
-  if (!error->empty()) return PCV_E_IO;
   auto attribute = [&](const char* name, int data_type) {
     std::vector<uint8_t> a;
     bytes_field(a, 1, std::vector<uint8_t>(name, name + strlen(name)));
@@ -336,8 +352,8 @@ int pcv_s2_write_files(const char* directory, const double bbox_min[3], const do
     varint(a, (uint64_t)data_type);
     bytes_field(s2, 2, a);
   };
-  attribute("color", 27);                      // AttributeDataType::U8Vec3
-  if (intensity) attribute("intensity", 11);   // AttributeDataType::F32
+  attribute("color", 27);                         // AttributeDataType::U8Vec3
+  if (has_intensity) attribute("intensity", 11);  // AttributeDataType::F32
   std::vector<uint8_t> cuboid;
   bytes_field(cuboid, 3, vec3d(bbox_min));
   bytes_field(cuboid, 4, vec3d(bbox_max));
@@ -351,6 +367,14 @@ int pcv_s2_write_files(const char* directory, const double bbox_min[3], const do
     return PCV_E_IO;
   }
   return PCV_OK;
+}
+
+int pcv_s2_write_files(const char* directory, const double bbox_min[3], const double bbox_max[3], uint64_t num_cells,
+                       const uint64_t* ids, const uint64_t* counts, const uint64_t* offsets, const uint8_t* xyz, const uint8_t* rgb,
+                       const uint8_t* intensity, std::string* error) {
+  const int rc = pcv_s2_write_cells(directory, num_cells, ids, counts, offsets, nullptr, xyz, rgb, intensity, error);
+  if (rc != PCV_OK) return rc;
+  return pcv_s2_write_meta(directory, bbox_min, bbox_max, num_cells, ids, counts, intensity != nullptr, error);
 }
 
 // ------------------------------------------------------------------------------------------------

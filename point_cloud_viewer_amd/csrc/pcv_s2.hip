@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256) void s2_gather_kernel(uint64_t n, const uint32
   const uint64_t stride = (uint64_t)gridDim.x * 256u;
   for (uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x; s < n; s += stride) {
     const uint32_t src = order[s];
-    order_out[s] = src;
+    if (order_out) order_out[s] = src;  // (null: a part of a directory stream, which keeps no input order)
     xyz[3 * s + 0] = x[src];
     xyz[3 * s + 1] = y[src];
     xyz[3 * s + 2] = z[src];
@@ -288,7 +288,7 @@ int ensure_resident(pcv_s2_cloud* c) {
   return PCV_OK;
 }
 
-int split_impl(pcv_ctx* ctx, const pcv_points* points, uint32_t level, pcv_s2_cloud* c) {
+int split_impl(pcv_ctx* ctx, const pcv_points* points, uint32_t level, pcv_s2_cloud* c, bool with_order = true) {
   const uint64_t n = points->n;
   c->ctx = ctx;
   c->n = n;
@@ -388,7 +388,7 @@ int split_impl(pcv_ctx* ctx, const pcv_points* points, uint32_t level, pcv_s2_cl
   const uint32_t* order = in_a ? index_a : index_b;
 
   // ---- gather ----
-  if ((rc = ctx->dev_alloc((void**)&c->d_order, n * 4)) || (rc = ctx->dev_alloc((void**)&c->d_xyz, n * 24)) ||
+  if ((with_order && (rc = ctx->dev_alloc((void**)&c->d_order, n * 4))) || (rc = ctx->dev_alloc((void**)&c->d_xyz, n * 24)) ||
       (rc = ctx->dev_alloc((void**)&c->d_rgb, n * 3)) || (c->has_intensity && (rc = ctx->dev_alloc((void**)&c->d_int, n * 4))))
     return rc;
   {
@@ -429,6 +429,23 @@ int pcv_s2_check_union(const uint64_t* cells, uint32_t num_cells, std::string* w
 }
 
 int pcv_s2_make_resident(pcv_s2_cloud* c) { return ensure_resident(c); }
+
+// pcv_s2_split as a stream takes it (pcv_s2_stream.hip): the same checks, the same split, the slot -> input index plane on request
+int pcv_s2_split_part(pcv_ctx* ctx, const pcv_points* points, uint32_t level, bool with_order, pcv_s2_cloud** out) {
+  *out = nullptr;
+  int rc = check_points(ctx, points, true);
+  if (rc) return rc;
+  pcv_s2_cloud* c = new pcv_s2_cloud();
+  rc = split_impl(ctx, points, level, c, with_order);
+  if (rc != PCV_OK) {
+    (void)hipStreamSynchronize(ctx->stream);  // nothing queued still reads what is released now
+    release_cloud(c);
+    return rc;
+  }
+  *out = c;
+  return PCV_OK;
+}
+void pcv_s2_release(pcv_s2_cloud* c) { release_cloud(c); }
 
 // ---- host twins (no context) --------------------------------------------------------------------------------------------
 extern "C" int pcv_s2_cell_ids_host(uint64_t n, const double* x, const double* y, const double* z, uint32_t level, uint64_t* ids) {

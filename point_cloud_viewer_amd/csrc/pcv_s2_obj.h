@@ -44,3 +44,7 @@ int pcv_s2_check_union(const uint64_t* cells, uint32_t num_cells, std::string* w
 int pcv_s2_check_unions(uint32_t num_unions, const uint32_t* union_first, const uint64_t* union_cells, std::string* why);
 // the blobs of an opened cloud on the device (pcv_s2.hip: read and uploaded on first use); nothing to do for a split
 int pcv_s2_make_resident(pcv_s2_cloud* c);
+// pcv_s2_split's checks and split for one batch of a stream (pcv_s2_stream.hip); with_order false: no d_order is made.
+// pcv_s2_release frees a cloud whose device work the caller has waited for.
+int pcv_s2_split_part(pcv_ctx* ctx, const pcv_points* points, uint32_t level, bool with_order, pcv_s2_cloud** out);
+void pcv_s2_release(pcv_s2_cloud* c);

@@ -450,6 +450,27 @@ class Context:
         self._check(self.lib.pcv_s2_open_dir(self.handle, os.fsencode(str(directory)), C.byref(h)))
         return S2Cloud(self, h)
 
+    def s2_stream(self, split_level=20, directory=None, open_mode="truncate", flush_points=None):
+        """S2Splitter over a stream of batches (pcv_s2_stream_*) -> S2Stream. directory None: the cloud is merged on the
+        device at finish() and equals s2_split of the concatenated batches. With a directory the cells' files are written as
+        the stream goes (a flush whenever flush_points points are pending, None = the library's default), the total is
+        unbounded, and finish() returns the cloud that s2_open opens. open_mode "append" (OpenMode::Append) adds to the S2
+        directory that is there: no file is truncated, meta.pb counts the old points and the new."""
+        modes = {"truncate": L.S2_TRUNCATE, "append": L.S2_APPEND}
+        if open_mode not in modes:
+            raise ValueError('open_mode must be "truncate" or "append"')
+        pr = L.S2StreamParams()
+        pr.struct_size = C.sizeof(L.S2StreamParams)
+        if not 0 <= int(split_level) <= 0xFFFFFFFF:
+            raise L.PcvError(L.PCV_E_INVALID, "an S2 split level is 0 ..= 30")
+        pr.split_level = int(split_level)
+        pr.directory = os.fsencode(str(directory)) if directory is not None else None
+        pr.open_mode = modes[open_mode]
+        pr.flush_points = int(flush_points or 0)
+        h = C.c_void_p()
+        self._check(self.lib.pcv_s2_stream_begin(self.handle, C.byref(pr), C.byref(h)))
+        return S2Stream(self, h)
+
     # ---- stage-level entry points ----------------------------------------------------------------
     def aabb_reduce(self, x, y, z):
         p, keep = self._points(x, y, z)
@@ -2222,6 +2243,105 @@ class S2Cloud:
             pass
 
 
+class S2Stream:
+    """One pcv_s2_stream: `append` is S2Splitter::write for one batch, `finish` its get_meta. A context manager: leaving the
+    block on an exception aborts the stream; a stream not finished by the end of the block is aborted too."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.lib, self.handle = ctx, ctx.lib, handle
+        ctx._children.add(self)
+
+    def _alive(self):
+        if not self.handle or not self.ctx.handle:
+            raise ValueError("this S2 stream is finished")
+
+    def append(self, points):
+        """One batch: the SoA dict of s2_split (x=, y=, z=, color=[, intensity=]) or a PointsBatch dict (position= (n, 3)
+        f64, color= (n, 3) u8[, intensity= (n,) f32], src/lib.rs:102-107); host arrays or device tensors."""
+        self._alive()
+        if "position" in points:
+            pos = points["position"]
+            if len(pos.shape) != 2 or pos.shape[1] != 3:
+                raise ValueError("position must be (n, 3): one Point3<f64> per row")
+            if _is_torch(pos):
+                x, y, z = (pos[:, a].contiguous() for a in range(3))
+            else:
+                pos = np.asarray(pos, dtype=np.float64)
+                x, y, z = (np.ascontiguousarray(pos[:, a]) for a in range(3))
+        else:
+            x, y, z = points["x"], points["y"], points["z"]
+        p, keep_alive = self.ctx._points(x, y, z, points["color"], points.get("intensity"))
+        self.ctx._check(self.lib.pcv_s2_stream_append(self.handle, C.byref(p)))
+
+    @property
+    def info(self):
+        """dict(batches, points, cells, pending_points, flushes) so far (pcv_s2_stream_info)."""
+        self._alive()
+        v = [C.c_uint64() for _ in range(5)]
+        self.ctx._check(self.lib.pcv_s2_stream_info(self.handle, *[C.byref(w) for w in v]))
+        return dict(zip(("batches", "points", "cells", "pending_points", "flushes"), (w.value for w in v)))
+
+    def _set_memory_cap(self, max_points):
+        """For tests (pcv_s2_stream_set_memory_cap): the point limit of an in-memory stream, lowered."""
+        self._alive()
+        self.ctx._check(self.lib.pcv_s2_stream_set_memory_cap(self.handle, int(max_points)))
+
+    def finish(self):
+        """get_meta: the S2Cloud (in directory mode, the directory opened). Consumes the stream, success or not."""
+        self._alive()
+        h, mine = C.c_void_p(), self.handle
+        self.handle = None
+        self.ctx._check(self.lib.pcv_s2_stream_finish(mine, C.byref(h)))
+        return S2Cloud(self.ctx, h)
+
+    def abort(self):
+        if self.handle and self.ctx.handle:
+            self.lib.pcv_s2_stream_abort(self.handle)
+        self.handle = None
+
+    free = abort  # (Context.close releases its children through free)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        self.abort()
+        return False
+
+    def __del__(self):
+        try:
+            self.abort()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+def s2_merge_plan(parts, chunk_points=0):
+    """pcv_s2_merge_plan_host (host only): `parts` = a sequence of (ids, counts), one pair of uint64 arrays per part, ids
+    ascending. Returns dict(ids, counts, offsets: the merged cells; segments: a structured array with dst_offset,
+    src_offset, part, count, ordered by cell, then part; chunk_first_segment: per output chunk of chunk_points points (0 = the
+    kernel's) the segment that holds its first point)."""
+    parts = [(np.ascontiguousarray(i, dtype=np.uint64).ravel(), np.ascontiguousarray(c, dtype=np.uint64).ravel()) for i, c in parts]
+    for i, c in parts:
+        if i.size != c.size:
+            raise ValueError("a part's ids and counts must have the same length")
+    first = np.zeros(len(parts) + 1, dtype=np.uint64)
+    first[1:] = np.cumsum([i.size for i, _ in parts], dtype=np.uint64)
+    ids = np.concatenate([i for i, _ in parts]) if parts else np.zeros(0, dtype=np.uint64)
+    counts = np.concatenate([c for _, c in parts]) if parts else np.zeros(0, dtype=np.uint64)
+    lib = L.load_library()
+    nc, ns, nk = C.c_uint64(), C.c_uint64(), C.c_uint64()
+
+    def call(*arrays):
+        _host_check(lib.pcv_s2_merge_plan_host(len(parts), first.ctypes.data, ids.ctypes.data, counts.ctypes.data, int(chunk_points),
+                                               C.byref(nc), C.byref(ns), C.byref(nk), *arrays), "pcv_s2_merge_plan_host")
+    call(None, None, None, None, None)
+    out_ids, out_counts, out_offsets = (np.zeros(nc.value, dtype=np.uint64) for _ in range(3))
+    segments = np.zeros(ns.value, dtype=np.dtype([("dst_offset", "<u8"), ("src_offset", "<u8"), ("part", "<u4"), ("count", "<u4")]))
+    chunk_first = np.zeros(nk.value, dtype=np.uint64)
+    call(out_ids.ctypes.data, out_counts.ctypes.data, out_offsets.ctypes.data, segments.ctypes.data, chunk_first.ctypes.data)
+    return dict(ids=out_ids, counts=out_counts, offsets=out_offsets, segments=segments, chunk_first_segment=chunk_first)
+
+
 def _host_check(rc, what):
     if rc != L.PCV_OK:
         msg = L.load_library().pcv_host_last_error()
@@ -2384,13 +2504,21 @@ def build_xray_quadtree(ctx, point_cloud_locations, output_directory, tile_size_
             c.free()
 
 
-def build_s2_cells(output_directory, points, split_level=20, ctx=None):
-    """An S2 cell cloud directory from one batch of ECEF points, as S2Splitter (src/read_write/s2.rs) writes it: `points` =
-    dict(x=, y=, z=, color=[, intensity=]). Returns the S2Cloud."""
+def build_s2_cells(output_directory, points, split_level=20, ctx=None, open_mode="truncate", flush_points=None):
+    """An S2 cell cloud directory of ECEF points, as S2Splitter (src/read_write/s2.rs) writes it: `points` =
+    dict(x=, y=, z=, color=[, intensity=]), one batch, split and written whole — or, like the reference, an ITERATOR OF
+    BATCHES (PointsBatch dicts with position=, or SoA dicts) through a directory stream (Context.s2_stream): device memory
+    stays O(flush_points), the result is the same directory. open_mode "append" adds to the S2 directory that is there (always
+    through the stream). Returns the S2Cloud."""
     ctx = ctx or default_context()
-    cloud = ctx.s2_split(points, split_level)
-    cloud.write(output_directory)
-    return cloud
+    if isinstance(points, dict) and open_mode == "truncate" and flush_points is None:
+        cloud = ctx.s2_split(points, split_level)
+        cloud.write(output_directory)
+        return cloud
+    with ctx.s2_stream(split_level, output_directory, open_mode, flush_points) as stream:
+        for batch in ([points] if isinstance(points, dict) else points):
+            stream.append(batch)
+        return stream.finish()
 
 
 def default_context():

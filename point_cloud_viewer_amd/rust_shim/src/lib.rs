@@ -6,17 +6,17 @@
 //! pointers. Uncompiled here (no Rust toolchain in the build container) — see INTEGRATION.md for how it slots into the
 //! reference workspace and for the four accessor one-liners it needs on `Frustum` / `Obb` (their fields are private).
 use nalgebra::{Matrix4, Point3, Vector3};
-use point_viewer::data_provider::OnDiskDataProvider;
+use point_viewer::data_provider::{DataProvider, OnDiskDataProvider};
 use point_viewer::errors::{ErrorKind, Result};
 use point_viewer::geometry::Aabb;
 use point_viewer::iterator::{PointCloud, PointLocation, PointQuery};
 use point_viewer::octree::{NodeId, Octree};
-use point_viewer::read_write::{Encoding, NodeIterator, PositionEncoding};
+use point_viewer::read_write::{Encoding, NodeIterator, NodeWriter, OpenMode, PositionEncoding};
 use point_viewer::{AttributeData, NumberOfPoints, PointsBatch};
 use std::collections::{BTreeMap, HashMap};
 use std::ffi::{CStr, CString};
 use std::os::raw::{c_char, c_double, c_float, c_int, c_void};
-use std::path::Path;
+use std::path::{Path, PathBuf};
 use std::sync::Mutex;
 
 #[repr(C)]
@@ -1073,5 +1073,132 @@ impl PointCloud for HipS2Cells {
         }
         drop(_g);
         emit_points(query, &points, batch_size, callback)
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// S2Splitter over the GPU library (src/read_write/s2.rs:19-173): NodeWriter<PointsBatch> whose `write` hands one batch to
+// pcv_s2_stream_append and whose `get_meta` finishes the stream (include/pcv_hip.h, "S2 cell clouds from a stream of
+// batches"). Like the rest of this file it is written against the reference's types and has not been compiled here.
+// ------------------------------------------------------------------------------------------------------------------
+#[repr(C)]
+pub struct pcv_s2_stream {
+    _private: [u8; 0],
+}
+/// pcv_s2_stream_params of include/pcv_hip.h, field for field.
+#[repr(C)]
+pub struct PcvS2StreamParams {
+    pub struct_size: u32,
+    pub split_level: u32,
+    pub directory: *const c_char,
+    pub open_mode: i32,
+    pub reserved: u32,
+    pub flush_points: u64,
+}
+
+extern "C" {
+    fn pcv_s2_stream_begin(ctx: *mut pcv_ctx, params: *const PcvS2StreamParams, out: *mut *mut pcv_s2_stream) -> c_int;
+    fn pcv_s2_stream_append(stream: *mut pcv_s2_stream, batch: *const PcvPoints) -> c_int;
+    fn pcv_s2_stream_info(stream: *const pcv_s2_stream, batches: *mut u64, points: *mut u64, cells: *mut u64, pending_points: *mut u64, flushes: *mut u64) -> c_int;
+    fn pcv_s2_stream_finish(stream: *mut pcv_s2_stream, out: *mut *mut pcv_s2_cloud) -> c_int;
+    fn pcv_s2_stream_abort(stream: *mut pcv_s2_stream);
+}
+
+/// `S2Splitter<RawNodeWriter>` on the device: the cells' files grow flush by flush, `get_meta` writes nothing itself but
+/// returns the Meta of what `meta.pb` now says. OpenMode::Append adds to the directory that is there — and, a departure
+/// from the reference, counts its points in the Meta.
+pub struct S2Stream {
+    ctx: HipContext,
+    stream: *mut pcv_s2_stream,
+    directory: PathBuf,
+}
+
+impl S2Stream {
+    /// S2Splitter::with_split_level (s2.rs:32-54).
+    pub fn with_split_level(split_level: u8, path: impl Into<PathBuf>, open_mode: OpenMode) -> Result<Self> {
+        use std::os::unix::ffi::OsStrExt;
+        let ctx = HipContext::new(0).map_err(|e| ErrorKind::InvalidInput(e))?;
+        let directory: PathBuf = path.into();
+        let dir = CString::new(directory.as_os_str().as_bytes()).expect("path with a NUL byte");
+        let params = PcvS2StreamParams {
+            struct_size: std::mem::size_of::<PcvS2StreamParams>() as u32,
+            split_level: split_level as u32,
+            directory: dir.as_ptr(),
+            open_mode: match open_mode {
+                OpenMode::Truncate => 0,
+                OpenMode::Append => 1,
+            },
+            reserved: 0,
+            flush_points: 0,
+        };
+        let mut stream = std::ptr::null_mut();
+        if unsafe { pcv_s2_stream_begin(ctx.0, &params, &mut stream) } != 0 {
+            let msg = unsafe { CStr::from_ptr(pcv_last_error(ctx.0)) }.to_string_lossy().into_owned();
+            return Err(ErrorKind::InvalidInput(msg).into());
+        }
+        Ok(S2Stream { ctx, stream, directory })
+    }
+
+    fn io_error(&self) -> std::io::Error {
+        let msg = unsafe { CStr::from_ptr(pcv_last_error(self.ctx.0)) }.to_string_lossy().into_owned();
+        std::io::Error::new(std::io::ErrorKind::InvalidInput, msg)
+    }
+
+    /// (batches, points, cells, pending points, flushes) so far.
+    pub fn info(&self) -> (u64, u64, u64, u64, u64) {
+        let mut v = [0u64; 5];
+        let p = v.as_mut_ptr();
+        unsafe { pcv_s2_stream_info(self.stream, p, p.add(1), p.add(2), p.add(3), p.add(4)) };
+        (v[0], v[1], v[2], v[3], v[4])
+    }
+
+    /// S2Splitter::get_meta (s2.rs:139-173): the last flush, meta.pb, and the Meta read back from it.
+    pub fn get_meta(mut self) -> Result<point_viewer::s2_cells::S2Meta> {
+        let stream = std::mem::replace(&mut self.stream, std::ptr::null_mut());
+        if unsafe { pcv_s2_stream_finish(stream, std::ptr::null_mut()) } != 0 {
+            return Err(ErrorKind::InvalidInput(self.io_error().to_string()).into());
+        }
+        let provider = OnDiskDataProvider { directory: self.directory.clone() };
+        point_viewer::s2_cells::S2Meta::from_proto(provider.meta_proto()?)
+    }
+}
+
+impl NodeWriter<PointsBatch> for S2Stream {
+    /// S2Splitter::new (s2.rs:56-58): DEFAULT_S2_SPLIT_LEVEL; the cells' files are Encoding::Plain whatever `_encoding` says, as
+    /// S2Cells reads them. Panics where the stream cannot be begun (no device, OpenMode::Append on a directory that is no S2 cloud).
+    fn new(path: impl Into<PathBuf>, _encoding: Encoding, open_mode: OpenMode) -> Self {
+        Self::with_split_level(20, path, open_mode).unwrap_or_else(|e| panic!("S2Stream: {}", e))
+    }
+
+    /// S2Splitter::write (s2.rs:60-137) for one batch: the positions transposed to the planes pcv_points wants, colour and
+    /// intensity as they are.
+    fn write(&mut self, batch: &PointsBatch) -> std::io::Result<()> {
+        let n = batch.position.len();
+        let (mut x, mut y, mut z) = (Vec::with_capacity(n), Vec::with_capacity(n), Vec::with_capacity(n));
+        for p in &batch.position {
+            x.push(p.x);
+            y.push(p.y);
+            z.push(p.z);
+        }
+        let color = match batch.attributes.get("color") {
+            Some(AttributeData::U8Vec3(c)) if c.len() == n => c.as_ptr() as *const u8,
+            _ => return Err(std::io::Error::new(std::io::ErrorKind::InvalidInput, "color attribute (U8Vec3), one per position, is required")),
+        };
+        let intensity = match batch.attributes.get("intensity") {
+            Some(AttributeData::F32(i)) if i.len() == n => i.as_ptr(),
+            Some(_) => return Err(std::io::Error::new(std::io::ErrorKind::InvalidInput, "S2Splitter received incompatible data types for attribute intensity")),
+            None => std::ptr::null(),
+        };
+        let points = PcvPoints { n: n as u64, x: x.as_ptr(), y: y.as_ptr(), z: z.as_ptr(), color, color_stride: 3, intensity, mem: 0 };
+        if unsafe { pcv_s2_stream_append(self.stream, &points) } != 0 {
+            return Err(self.io_error());
+        }
+        Ok(())
+    }
+}
+
+impl Drop for S2Stream {
+    fn drop(&mut self) {
+        unsafe { pcv_s2_stream_abort(self.stream) } // (null after get_meta) before the context
     }
 }
