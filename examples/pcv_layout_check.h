@@ -70,5 +70,11 @@ PCV_SA(offsetof(pcv_s2_stream_params, struct_size) == 0 && offsetof(pcv_s2_strea
 PCV_SA(sizeof(pcv_s2_merge_segment) == 24 && offsetof(pcv_s2_merge_segment, src_offset) == 8 && offsetof(pcv_s2_merge_segment, part) == 16 &&
            offsetof(pcv_s2_merge_segment, count) == 20,
        "pcv_s2_merge_segment");
+PCV_SA(sizeof(pcv_attribute) == 24 && offsetof(pcv_attribute, name) == 0 && offsetof(pcv_attribute, data_type) == 8 &&
+           offsetof(pcv_attribute, reserved) == 12 && offsetof(pcv_attribute, data) == 16,
+       "pcv_attribute");
+PCV_SA(sizeof(pcv_s2_filter) == 32 && offsetof(pcv_s2_filter, location) == 0 && offsetof(pcv_s2_filter, reserved) == 4 &&
+           offsetof(pcv_s2_filter, attribute) == 8 && offsetof(pcv_s2_filter, lo) == 16 && offsetof(pcv_s2_filter, hi) == 24,
+       "pcv_s2_filter");
 
 #endif

@@ -1252,7 +1252,7 @@ int pcv_s2_write_dir(pcv_s2_cloud* cloud, const char* directory);
  * (pcv_s2_order does not: there is no input). meta.pb of version < 12: PCV_E_INVALID "No S2 point cloud supported with version
  * N"; without the s2 arm: PCV_E_INVALID "This meta does not describe S2 point clouds" (the reference's messages). The cells
  * may be listed in any order and come out ascending by id; `color` (U8Vec3) is required, `intensity` (F32) optional, other
- * attributes are ignored. *level of pcv_s2_info is the common level of the ids, 0xffffffff when they differ. The cell files
+ * attributes are kept as extras (pcv_s2_attributes below). *level of pcv_s2_info is the common level of the ids, 0xffffffff when they differ. The cell files
  * are read and uploaded on first use (cell_points, write_dir): a file whose size is not that of the cell's num_points (24 / 3 /
  * 4 bytes each), or a missing file of a cell with points, is PCV_E_IO naming the file.
  * ctx may be NULL (as for pcv_xray_open_dir): a host-only cloud, whose failures go to pcv_host_last_error; info, cells,
@@ -1404,6 +1404,95 @@ int pcv_s2_query_segments(const pcv_s2_query* q, uint64_t* location_first_segmen
 int pcv_s2_query_points(pcv_s2_query* q, uint64_t first_segment, uint64_t num_segments, uint64_t capacity, int mem, double* x,
                         double* y, double* z, uint8_t* rgb, float* intensity);
 void pcv_s2_query_free(pcv_s2_query* q);
+
+/* ---- S2 cell clouds: typed point attributes ------------------------------------- */
+/* S2Splitter::write regroups EVERY attribute of a PointsBatch (src/read_write/s2.rs:85-107), get_meta lists them in meta.pb
+ * (S2Meta.attributes, proto.proto:92-133) and a PointQuery filters on any scalar one (src/iterator.rs:66-119,
+ * src/s2_cells/mod.rs:171-191). `color` (U8Vec3) and `intensity` (F32) stay the built-in columns of pcv_points; every other
+ * column is an "extra": { name, data_type, data }.
+ *   data_type  the proto enum value (src/attributes.rs:8-21): U8 1, U16 2, U32 3, U64 4, I8 6, I16 7, I32 8, I64 9, F32 11,
+ *              F64 12, U8Vec3 27, F64Vec3 38 — elements of 1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 3 and 24 bytes (attributes.rs:64-73);
+ *              anything else is PCV_E_INVALID "Attribute data type invalid"
+ *   name       not `color`, `intensity`, `position`, `xyz`, `rgb` or `meta`; 1 ..= 64 bytes; no '/', '.' or NUL inside; unique;
+ *              at most PCV_S2_MAX_EXTRAS per cloud — each violation is PCV_E_INVALID with a message naming the attribute
+ *   data       n elements, little endian, where points->mem says
+ * A cell's file is `<token>.<name>`: the values of the cell's points in file order (src/lib.rs:74-80, read_write/raw.rs).
+ * Out of scope: clouds without `color`; xray filters and binning on extras (`interval_attribute` other than "intensity"
+ * stays refused); PLY properties as extras; the octree path, which is fixed to color and intensity as the reference's is
+ * (src/octree/mod.rs:63-72). */
+#define PCV_ATTR_U8 1
+#define PCV_ATTR_U16 2
+#define PCV_ATTR_U32 3
+#define PCV_ATTR_U64 4
+#define PCV_ATTR_I8 6
+#define PCV_ATTR_I16 7
+#define PCV_ATTR_I32 8
+#define PCV_ATTR_I64 9
+#define PCV_ATTR_F32 11
+#define PCV_ATTR_F64 12
+#define PCV_ATTR_U8VEC3 27
+#define PCV_ATTR_F64VEC3 38
+#define PCV_S2_MAX_EXTRAS 16
+#define PCV_S2_MAX_ATTR_NAME 64
+typedef struct pcv_attribute {
+  const char* name;
+  int32_t data_type; /* PCV_ATTR_* */
+  uint32_t reserved; /* 0 */
+  const void* data;  /* n elements where points->mem says */
+} pcv_attribute;
+/* pcv_s2_split with extras (s2.rs:85-107): every column regrouped as the points are, out[slot] = in[pcv_s2_order[slot]]. With
+ * num_attrs == 0 it is pcv_s2_split, bit for bit. */
+int pcv_s2_split_ex(pcv_ctx* ctx, const pcv_points* points, const pcv_attribute* attrs, uint32_t num_attrs, uint32_t split_level,
+                    pcv_s2_cloud** out);
+/* Host only, no context: the rules above on a list of extras (names, data types, count, repeats; `data` is not read) — what
+ * pcv_s2_split_ex and pcv_s2_stream_append_ex check first, with their messages (pcv_host_last_error). */
+int pcv_s2_attributes_check_host(const pcv_attribute* attrs, uint32_t num_attrs);
+/* pcv_s2_stream_append with extras. The first non-empty batch (in PCV_S2_APPEND mode, the directory) fixes the attribute set: a
+ * later batch whose extra has another type, or a name the stream does not know, is PCV_E_INVALID "S2Splitter received
+ * incompatible data types for attribute NAME (batch K of the stream)" (s2.rs:155). A batch that LACKS an extra of the stream is
+ * refused in the same words (a departure: the reference lets it through, and the cell's files then disagree in length). The
+ * stream stays usable after a refusal. pcv_s2_stream_append is this call with num_attrs == 0. */
+int pcv_s2_stream_append_ex(pcv_s2_stream* stream, const pcv_points* batch, const pcv_attribute* attrs, uint32_t num_attrs);
+/* The extras of a cloud, ascending by name (bytewise): *count, and — where non-NULL, PCV_S2_MAX_EXTRAS entries each — the names
+ * (owned by the cloud, valid until it is freed) and the data types. */
+int pcv_s2_attributes(const pcv_s2_cloud* cloud, uint32_t* count, const char** names, int32_t* data_types);
+/* One extra of cells [first_cell, first_cell + num_cells) as it stands in the cells' files (lib.rs:74-80), one cell after the
+ * other, into `out` where `mem` says; `capacity` counts elements. pcv_s2_cell_points' rules; an unknown name is PCV_E_INVALID
+ * "Data type for attribute 'NAME' not found." (lib.rs:94). On a cloud opened from a directory the extra's files are read (and
+ * uploaded) when a call first names that extra or the cloud is written — pcv_s2_open_dir itself reads meta.pb alone, so a
+ * directory whose extra files are damaged still opens; a file of the wrong size, or a missing file of a cell with points, is
+ * PCV_E_IO naming the file. A host-only cloud serves this call into host memory. */
+int pcv_s2_cell_attribute(pcv_s2_cloud* cloud, const char* name, uint64_t first_cell, uint64_t num_cells, uint64_t capacity, int mem,
+                          void* out);
+/* pcv_s2_write_dir, the flushes of a stream and pcv_s2_stream_finish write `<token>.<name>` per extra and list the extras in
+ * meta.pb after color and intensity, ascending by name; a cloud without extras writes the bytes it wrote before.
+ * pcv_s2_open_dir keeps the extras that meta.pb lists: entries named `color` or `intensity` of another type are skipped, as
+ * are entries that break the rules above. Writing an opened cloud reads every extra's files (a damaged one is PCV_E_IO); an
+ * extra of which the directory holds no file at all has nothing to carry over and is left out of what is written. */
+
+/* One ClosedInterval<f64> of a PointQuery's filter_intervals (iterator.rs:66-119): location `location` keeps a point only if
+ * `attribute` of it, converted as Rust's `as f64` (round to nearest even for U64 / I64, exact for every other type), lies in
+ * [lo, hi]. NaN (a value, or a bound) keeps nothing. */
+typedef struct pcv_s2_filter {
+  uint32_t location;
+  uint32_t reserved; /* 0 */
+  const char* attribute;
+  double lo, hi;
+} pcv_s2_filter;
+/* pcv_s2_query_run with filters on any scalar attribute: the filters of one location are ANDed with `contains`
+ * (iterator.rs:109-115). With num_filters == 0 it is pcv_s2_query_run with intervals == NULL; a filter on "intensity" is
+ * pcv_s2_query_run's interval. PCV_E_INVALID: an unknown name ("Data type for attribute 'NAME' not found.", lib.rs:94); a
+ * vector attribute, `color` included (the reference reaches unimplemented!()); two filters on one (location, attribute); a
+ * location past the end. */
+int pcv_s2_query_run_ex(pcv_s2_cloud* cloud, const pcv_shapes* shapes, uint32_t num_unions, const uint32_t* union_first,
+                        const uint64_t* union_cells, const pcv_s2_filter* filters, uint32_t num_filters, pcv_s2_query** out);
+/* One extra of the kept points of segments [first_segment, first_segment + num_segments), in segment order, into `out` where
+ * `mem` says; `capacity` counts elements. pcv_s2_query_points' rules. */
+int pcv_s2_query_attribute(pcv_s2_query* q, const char* name, uint64_t first_segment, uint64_t num_segments, uint64_t capacity, int mem,
+                           void* out);
+/* Host only, no context: keep[i] &= (data[i] as f64) in [lo, hi] for n values of a scalar data_type — the twin of the device's
+ * filter, from the same function. A vector type is PCV_E_INVALID. */
+int pcv_s2_filter_keep_host(int32_t data_type, uint64_t n, const void* data, double lo, double hi, uint8_t* keep);
 
 /* ---- xray over S2 cell clouds -------------------------------------------------------- */
 /* build_xray_quadtree's leaf level over S2 cell clouds: PointCloudClient opens every location as an S2Cells cloud when the

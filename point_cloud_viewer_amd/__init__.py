@@ -9,7 +9,7 @@ from ._lib import (PCV_E_DEPTH, PCV_E_HIP, PCV_E_INVALID, PCV_E_IO, PCV_E_NOT_FO
 from .octree import (Aabb, Context, OctreeResult, QueryBatch, RenderedViews, S2Cloud, S2QueryBatch, Shapes, XrayTiles, build_octree, build_octree_from_file,  # noqa: F401
                      build_s2_cells, build_xray_quadtree, cloud_kind, s2_cell_ids, s2_cell_token, s2_union_contains,
                      s2_cell_geometry, s2_cell_rect, s2_cells_in_location, s2_corners_rect, s2_rect_intersects_cell, s2_union_intersects, s2_union_intersects_cubes,
-                     s2_open_host, s2_union_normalize, S2Stream, s2_merge_plan,
+                     s2_open_host, s2_union_normalize, S2Stream, s2_merge_plan, s2_filter_keep, s2_check_attributes,
                      level_shortcuts, level_table, node_name, quadtree_node_id, quadtree_node_name, read_ply,
                      render_check_overlay, render_check_params, render_gamma_lut, render_overlay, render_params,
                      web_mercator_rect_from_zoomed, wmr_contains, wmr_corners, wmr_from_lat_lng, wmr_math, wmr_project, wmr_to_lat_lng,

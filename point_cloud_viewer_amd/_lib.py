@@ -175,6 +175,22 @@ class S2MergeSegment(C.Structure):  # pcv_s2_merge_segment
 S2_TRUNCATE, S2_APPEND = 0, 1  # pcv_s2_stream_params.open_mode
 
 
+class Attribute(C.Structure):  # pcv_attribute
+    _fields_ = [("name", C.c_char_p), ("data_type", C.c_int32), ("reserved", C.c_uint32), ("data", C.c_void_p)]
+
+
+class S2Filter(C.Structure):  # pcv_s2_filter
+    _fields_ = [("location", C.c_uint32), ("reserved", C.c_uint32), ("attribute", C.c_char_p), ("lo", C.c_double), ("hi", C.c_double)]
+
+
+# PCV_ATTR_*: type string -> (proto enum value, numpy dtype, components)
+ATTR_TYPES = {"u8": (1, "u1", 1), "u16": (2, "<u2", 1), "u32": (3, "<u4", 1), "u64": (4, "<u8", 1), "i8": (6, "i1", 1), "i16": (7, "<i2", 1),
+              "i32": (8, "<i4", 1), "i64": (9, "<i8", 1), "f32": (11, "<f4", 1), "f64": (12, "<f8", 1), "u8vec3": (27, "u1", 3),
+              "f64vec3": (38, "<f8", 3)}
+ATTR_NAMES = {v[0]: k for k, v in ATTR_TYPES.items()}
+S2_MAX_EXTRAS = 16
+
+
 class OocStats(C.Structure):
     _fields_ = [("points", C.c_uint64), ("nodes", C.c_uint64), ("partitions", C.c_uint64), ("largest_bucket", C.c_uint64),
                 ("spill_bytes", C.c_uint64), ("h2d_bytes", C.c_uint64), ("d2h_bytes", C.c_uint64), ("h2d_ms", C.c_double),
@@ -371,6 +387,14 @@ _SIGNATURES = {
     "pcv_s2_query_points": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "pcv_s2_query_free": (None, [_vp]),
     "pcv_s2_open_dir": (C.c_int, [_vp, C.c_char_p, C.POINTER(_vp)]),
+    "pcv_s2_split_ex": (C.c_int, [_vp, C.POINTER(Points), _vp, C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
+    "pcv_s2_stream_append_ex": (C.c_int, [_vp, C.POINTER(Points), _vp, C.c_uint32]),
+    "pcv_s2_attributes_check_host": (C.c_int, [_vp, C.c_uint32]),
+    "pcv_s2_attributes": (C.c_int, [_vp, C.POINTER(C.c_uint32), _vp, _vp]),
+    "pcv_s2_cell_attribute": (C.c_int, [_vp, C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _vp]),
+    "pcv_s2_query_run_ex": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32, C.POINTER(_vp)]),
+    "pcv_s2_query_attribute": (C.c_int, [_vp, C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _vp]),
+    "pcv_s2_filter_keep_host": (C.c_int, [C.c_int32, C.c_uint64, _vp, C.c_double, C.c_double, _vp]),
     "pcv_s2_free": (None, [_vp]),
     "pcv_s2_stream_begin": (C.c_int, [_vp, C.POINTER(S2StreamParams), C.POINTER(_vp)]),
     "pcv_s2_stream_append": (C.c_int, [_vp, C.POINTER(Points)]),

@@ -116,6 +116,10 @@ enum PcvKernelId {
   PCV_K_S2_GATHER_POINTS,     // pcv_s2_points.hip: the kept points of a segment range into the caller's planes
   PCV_K_UNION_NODE_RECTS,     // pcv_union.hip: once per octree, the rect of every node cube's corners (cell unions over the octree)
   PCV_K_S2_MERGE,             // pcv_s2_stream.hip: the cell-sorted parts of a stream into one cell-contiguous cloud, by output chunk
+  PCV_K_S2_ATTR_GATHER,       // pcv_s2_attr.hip: one extra attribute's column regrouped by the split's permutation
+  PCV_K_S2_ATTR_MERGE,        // pcv_s2_attr.hip: one extra attribute's column of a stream's parts merged over the plan, by output chunk
+  PCV_K_S2_ATTR_FILTER,       // pcv_s2_attr.hip: keep flags ANDed with one extra's interval test, over the chunks that filter on it
+  PCV_K_S2_ATTR_GATHER_POINTS,  // pcv_s2_attr.hip: one extra's values of the kept points of a segment range
   PCV_K_COUNT
 };
 
@@ -648,11 +652,13 @@ int pcv_host_fail(int code, const std::string& msg);
 // cell and meta.pb with the s2 arm (cells ascending by id, `color` before `intensity`); *error names the file that failed
 int pcv_s2_write_files(const char* directory, const double bbox_min[3], const double bbox_max[3], uint64_t num_cells,
                        const uint64_t* ids, const uint64_t* counts, const uint64_t* offsets, const uint8_t* xyz, const uint8_t* rgb,
-                       const uint8_t* intensity /* null: no intensity attribute */, std::string* error);
+                       const uint8_t* intensity /* null: no intensity attribute */, std::string* error,
+                       const std::vector<std::pair<std::string, int32_t>>* extras = nullptr /* listed in meta.pb; their files: pcv_s2_write_extra */);
 // its two halves, as a stream of batches needs them (pcv_s2_stream.hip): the cells' runs onto their files — truncate: null (every
 // file is written anew), or one byte per cell, 0 = the run is appended to what the file holds — and meta.pb alone
 int pcv_s2_write_cells(const char* directory, uint64_t num_cells, const uint64_t* ids, const uint64_t* counts, const uint64_t* offsets,
                        const uint8_t* truncate, const uint8_t* xyz, const uint8_t* rgb, const uint8_t* intensity, std::string* error);
 int pcv_s2_write_meta(const char* directory, const double bbox_min[3], const double bbox_max[3], uint64_t num_cells, const uint64_t* ids,
-                      const uint64_t* counts, bool has_intensity, std::string* error);
+                      const uint64_t* counts, bool has_intensity, std::string* error,
+                      const std::vector<std::pair<std::string, int32_t>>* extras = nullptr /* after color and intensity, as listed */);
 std::string pcv_s2_token(uint64_t id);

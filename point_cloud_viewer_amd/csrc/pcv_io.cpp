@@ -333,7 +333,8 @@ int pcv_s2_write_cells(const char* directory, uint64_t num_cells, const uint64_t
 
 // meta.pb of an S2 directory: S2Splitter::get_meta (s2.rs:139-173) as Meta::to_proto serialises it
 int pcv_s2_write_meta(const char* directory, const double bbox_min[3], const double bbox_max[3], uint64_t num_cells, const uint64_t* ids,
-                      const uint64_t* counts, bool has_intensity, std::string* error) {
+                      const uint64_t* counts, bool has_intensity, std::string* error,
+                      const std::vector<std::pair<std::string, int32_t>>* extras) {
   const std::string dir(directory);
   ::mkdir(dir.c_str(), 0777);  // (a stream that saw no point has written no cell)
   std::vector<uint8_t> s2;
@@ -354,6 +355,7 @@ int pcv_s2_write_meta(const char* directory, const double bbox_min[3], const dou
   };
   attribute("color", 27);                         // AttributeDataType::U8Vec3
   if (has_intensity) attribute("intensity", 11);  // AttributeDataType::F32
+  for (size_t k = 0; extras && k < extras->size(); ++k) attribute((*extras)[k].first.c_str(), (*extras)[k].second);
   std::vector<uint8_t> cuboid;
   bytes_field(cuboid, 3, vec3d(bbox_min));
   bytes_field(cuboid, 4, vec3d(bbox_max));
@@ -369,12 +371,28 @@ int pcv_s2_write_meta(const char* directory, const double bbox_min[3], const dou
   return PCV_OK;
 }
 
+// one extra's runs onto `<token>.<name>` (lib.rs:74-80): the same loop, the same truncate / append rule
+int pcv_s2_write_extra(const char* directory, uint64_t num_cells, const uint64_t* ids, const uint64_t* counts, const uint64_t* offsets,
+                       const uint8_t* truncate, const std::string& name, uint32_t elem, const uint8_t* data, std::string* error) {
+  const std::string dir(directory);
+  const int dirfd = s2_open_directory(dir, error);
+  if (dirfd < 0) return PCV_E_IO;
+  static const uint8_t none = 0;
+  for (uint64_t k = 0; k < num_cells && error->empty(); ++k) {
+    const std::string file = pcv_s2_token(ids[k]) + "." + name;
+    const bool append = truncate && !truncate[k];
+    if (!write_file_at(dirfd, file, data ? data + offsets[k] * elem : &none, counts[k] * elem, append)) *error = "cannot write " + dir + "/" + file;
+  }
+  ::close(dirfd);
+  return error->empty() ? PCV_OK : PCV_E_IO;
+}
+
 int pcv_s2_write_files(const char* directory, const double bbox_min[3], const double bbox_max[3], uint64_t num_cells,
                        const uint64_t* ids, const uint64_t* counts, const uint64_t* offsets, const uint8_t* xyz, const uint8_t* rgb,
-                       const uint8_t* intensity, std::string* error) {
+                       const uint8_t* intensity, std::string* error, const std::vector<std::pair<std::string, int32_t>>* extras) {
   const int rc = pcv_s2_write_cells(directory, num_cells, ids, counts, offsets, nullptr, xyz, rgb, intensity, error);
   if (rc != PCV_OK) return rc;
-  return pcv_s2_write_meta(directory, bbox_min, bbox_max, num_cells, ids, counts, intensity != nullptr, error);
+  return pcv_s2_write_meta(directory, bbox_min, bbox_max, num_cells, ids, counts, intensity != nullptr, error, extras);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -509,6 +527,7 @@ int pcv_s2_read_meta(const char* directory, PcvS2Dir* out, std::string* error) {
   int64_t version = 0;
   bool has_s2 = false, has_color = false;
   out->has_intensity = false;
+  out->extras.clear();
   for (int a = 0; a < 3; ++a) out->bbox_min[a] = out->bbox_max[a] = 0.0;
   std::vector<std::pair<uint64_t, uint64_t>> cells;
   Reader r{buf.data(), buf.data() + buf.size()};
@@ -551,6 +570,13 @@ int pcv_s2_read_meta(const char* directory, PcvS2Dir* out, std::string* error) {
           if (!a.ok) s.ok = false;
           if (name == "color" && type == 27) has_color = true;            // AttributeDataType::U8Vec3
           else if (name == "intensity" && type == 11) out->has_intensity = true;  // AttributeDataType::F32
+          else {  // an extra; what breaks the naming rules or names no data type is skipped, as is a repeat
+            std::string why;
+            bool seen = false;
+            for (const auto& e : out->extras) seen = seen || e.first == name;
+            if (!seen && type <= 0x7fffffffull && pcv_s2_attr_size((int32_t)type) && pcv_s2_attr_name_ok(name, &why) && out->extras.size() < 16)
+              out->extras.emplace_back(name, (int32_t)type);
+          }
         } else s.skip(sw);
       }
       if (!s.ok) r.ok = false;
@@ -572,6 +598,7 @@ int pcv_s2_read_meta(const char* directory, PcvS2Dir* out, std::string* error) {
     *error = dir + "/meta.pb lists no `color` attribute of type U8Vec3";
     return PCV_E_INVALID;
   }
+  std::sort(out->extras.begin(), out->extras.end());
   // the reference keeps the cells in a hash map (a repeated id: the last entry stays); here they ascend by id
   std::stable_sort(cells.begin(), cells.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
   out->ids.clear();
@@ -580,6 +607,43 @@ int pcv_s2_read_meta(const char* directory, PcvS2Dir* out, std::string* error) {
     if (k + 1 < cells.size() && cells[k + 1].first == cells[k].first) continue;
     out->ids.push_back(cells[k].first);
     out->counts.push_back(cells[k].second);
+  }
+  return PCV_OK;
+}
+
+int pcv_s2_read_extra(const char* directory, const std::vector<uint64_t>& ids, const std::vector<uint64_t>& counts, const std::string& name,
+                      uint32_t elem, uint8_t* out, std::string* error, bool* absent) {
+  const std::string dir(directory);
+  uint64_t at = 0;
+  std::vector<uint8_t> buf;
+  if (absent) *absent = false;
+  std::string first_missing;
+  size_t found = 0;
+  for (size_t k = 0; k < ids.size(); ++k) {
+    const uint64_t np = counts[k];
+    const std::string path = dir + "/" + pcv_s2_token(ids[k]) + "." + name;
+    bool missing;
+    if (!read_file(path, &buf, &missing)) {
+      if (missing) {  // decided at the end: no file at all is another finding than one file gone
+        if (np && first_missing.empty()) first_missing = path;
+        at += np;
+        continue;
+      }
+      *error = "cannot read " + path;
+      return PCV_E_IO;
+    }
+    ++found;
+    if (buf.size() != np * elem) {
+      *error = path + " holds " + std::to_string(buf.size()) + " bytes, " + std::to_string(np) + " points need " + std::to_string(np * elem);
+      return PCV_E_IO;
+    }
+    if (np) std::memcpy(out + at * elem, buf.data(), buf.size());
+    at += np;
+  }
+  if (!first_missing.empty()) {
+    if (absent) *absent = found == 0;
+    *error = "missing cell file " + first_missing;
+    return PCV_E_IO;
   }
   return PCV_OK;
 }

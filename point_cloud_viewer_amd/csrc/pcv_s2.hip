@@ -241,6 +241,7 @@ void release_cloud(pcv_s2_cloud* c) {
     if (c->d_int) c->ctx->dev_free(c->d_int);
     if (c->d_ids) c->ctx->dev_free(c->d_ids);
     if (c->d_table) c->ctx->dev_free(c->d_table);
+    pcv_s2_extras_release(c);
   }
   delete c;
 }
@@ -288,12 +289,14 @@ int ensure_resident(pcv_s2_cloud* c) {
   return PCV_OK;
 }
 
-int split_impl(pcv_ctx* ctx, const pcv_points* points, uint32_t level, pcv_s2_cloud* c, bool with_order = true) {
+int split_impl(pcv_ctx* ctx, const pcv_points* points, uint32_t level, pcv_s2_cloud* c, bool with_order = true,
+               std::vector<PcvS2Extra>* extras = nullptr) {
   const uint64_t n = points->n;
   c->ctx = ctx;
   c->n = n;
   c->level = level;
   c->has_intensity = points->intensity != nullptr;
+  if (extras) c->extras.swap(*extras);  // names and types hold for a cloud without points too
   if (n == 0) return PCV_OK;
   PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
@@ -397,6 +400,8 @@ int split_impl(pcv_ctx* ctx, const pcv_points* points, uint32_t level, pcv_s2_cl
                        c->d_order, (double*)c->d_xyz, c->d_rgb, (float*)c->d_int);
   }
   PCV_HIP_CHECK(ctx, hipGetLastError());
+  // the extras: one launch each over the same permutation, in pcv_s2_attr.hip
+  if (!c->extras.empty() && (rc = pcv_s2_attr_gather(ctx, sc, order, n, points->mem, c))) return rc;
   PCV_HIP_CHECK(ctx, hipStreamSynchronize(st));
   ctx->prof_resolve();
   c->offsets.resize(cells);
@@ -431,12 +436,13 @@ int pcv_s2_check_union(const uint64_t* cells, uint32_t num_cells, std::string* w
 int pcv_s2_make_resident(pcv_s2_cloud* c) { return ensure_resident(c); }
 
 // pcv_s2_split as a stream takes it (pcv_s2_stream.hip): the same checks, the same split, the slot -> input index plane on request
-int pcv_s2_split_part(pcv_ctx* ctx, const pcv_points* points, uint32_t level, bool with_order, pcv_s2_cloud** out) {
+int pcv_s2_split_part(pcv_ctx* ctx, const pcv_points* points, uint32_t level, bool with_order, pcv_s2_cloud** out,
+                      std::vector<PcvS2Extra>* extras) {
   *out = nullptr;
   int rc = check_points(ctx, points, true);
   if (rc) return rc;
   pcv_s2_cloud* c = new pcv_s2_cloud();
-  rc = split_impl(ctx, points, level, c, with_order);
+  rc = split_impl(ctx, points, level, c, with_order, extras);
   if (rc != PCV_OK) {
     (void)hipStreamSynchronize(ctx->stream);  // nothing queued still reads what is released now
     release_cloud(c);
@@ -561,6 +567,11 @@ extern "C" int pcv_s2_open_dir(pcv_ctx* ctx, const char* directory, pcv_s2_cloud
   c->directory = directory;
   c->opened = true;
   c->has_intensity = meta.has_intensity;
+  for (const auto& a : meta.extras) {  // their files are read when a call first names them (pcv_s2_extra_resident)
+    PcvS2Extra e;
+    e.name = a.first, e.data_type = a.second, e.elem = pcv_s2_attr_size(a.second), e.resident = false;
+    c->extras.push_back(std::move(e));
+  }
   std::memcpy(c->bbox_min, meta.bbox_min, 24);
   std::memcpy(c->bbox_max, meta.bbox_max, 24);
   c->ids = meta.ids;
@@ -577,6 +588,7 @@ extern "C" int pcv_s2_open_dir(pcv_ctx* ctx, const char* directory, pcv_s2_cloud
     else if (c->level != level) c->level = 0xffffffffu;
   }
   c->resident = c->n == 0;
+  for (PcvS2Extra& e : c->extras) e.resident = c->n == 0;
   *out = c;
   return PCV_OK;
 }
@@ -657,10 +669,14 @@ extern "C" int pcv_s2_write_dir(pcv_s2_cloud* c, const char* directory) {
   uint8_t *h_xyz = nullptr, *h_rgb = nullptr, *h_int = nullptr;
   int rc = ensure_resident(c);
   if (rc != PCV_OK) return rc;
+  // the extras' files first, meta.pb — which lists them — last, as before
+  std::vector<std::pair<std::string, int32_t>> extras;
+  if (!c->extras.empty() && (rc = pcv_s2_attr_write(c, directory, nullptr, &extras)) != PCV_OK) return rc;
   if (!ctx) {
     std::string error;
     rc = pcv_s2_write_files(directory, c->bbox_min, c->bbox_max, c->ids.size(), c->ids.data(), c->counts.data(), c->offsets.data(),
-                            c->h_xyz.data(), c->h_rgb.data(), c->has_intensity ? (c->n ? c->h_int.data() : (const uint8_t*)"") : nullptr, &error);
+                            c->h_xyz.data(), c->h_rgb.data(), c->has_intensity ? (c->n ? c->h_int.data() : (const uint8_t*)"") : nullptr, &error,
+                            &extras);
     return rc == PCV_OK ? rc : c->fail(rc, error);
   }
   if (c->n) {
@@ -677,7 +693,7 @@ extern "C" int pcv_s2_write_dir(pcv_s2_cloud* c, const char* directory) {
   if (rc == PCV_OK) {
     std::string error;
     rc = pcv_s2_write_files(directory, c->bbox_min, c->bbox_max, c->ids.size(), c->ids.data(), c->counts.data(), c->offsets.data(), h_xyz,
-                            h_rgb, c->has_intensity ? (h_int ? h_int : (const uint8_t*)"") : nullptr, &error);
+                            h_rgb, c->has_intensity ? (h_int ? h_int : (const uint8_t*)"") : nullptr, &error, &extras);
     if (rc != PCV_OK) ctx->fail(rc, error);
   }
   if (h_xyz) ctx->host_release(h_xyz);

@@ -7,6 +7,7 @@
 //   flags    s2_flags_kernel<KIND>: one workgroup per chunk, an instance per shape kind (PCV_SHAPE_FRUSTUM for both frusta, the
 //            web-mercator chain and the cell-union search in instances of their own, so the others keep their registers); the
 //            points are the cloud's 24-byte AoS f64, a wave's 64 points one contiguous 1 536-byte run, untouched
+//   filter   the intervals on extra attributes (pcv_s2_query_run_ex): launches of their own, pcv_s2_attr.hip, ANDed into the flags
 //   scan     flags -> u64 offsets (pcv_batch_scan); a segment's offset is the offset of its first candidate
 //   gather   s2_gather_points_kernel: the kept points of a segment range into x / y / z planes, rgb and intensity
 #include <algorithm>
@@ -111,7 +112,7 @@ void release_query(pcv_s2_query* b) {
 }
 
 int run_impl(pcv_s2_cloud* c, const pcv_shapes* shapes, uint32_t num_unions, const uint32_t* union_first, const uint64_t* union_cells,
-             const double* intervals, const uint8_t* interval_used, pcv_s2_query* b) {
+             const double* intervals, const uint8_t* interval_used, pcv_s2_query* b, const std::vector<PcvS2ExtraFilter>* extra_filters = nullptr) {
   pcv_ctx* ctx = c->ctx;
   hipStream_t st = ctx->stream;
   const uint32_t num_shapes = shapes ? shapes->count : 0;
@@ -205,6 +206,9 @@ int run_impl(pcv_s2_cloud* c, const pcv_shapes* shapes, uint32_t num_unions, con
 #undef LAUNCH
   }
   PCV_HIP_CHECK(ctx, hipGetLastError());
+  // ---- the filters on extra attributes: one launch per distinct extra, after the flags and before the scan ----
+  if (extra_filters && !extra_filters->empty() && (rc = pcv_s2_attr_filter(ctx, sc, c, b->d_chunks, chunks, locations, *extra_filters, b->d_flags)))
+    return rc;
   // ---- scan, the segments' offsets ----
   {
     PcvProf prof(ctx, PCV_K_QUERY_BATCH_SCAN);
@@ -236,6 +240,56 @@ extern "C" int pcv_s2_query_run(pcv_s2_cloud* c, const pcv_shapes* shapes, uint3
   pcv_s2_query* b = new pcv_s2_query();
   b->cloud = c;
   const int rc = run_impl(c, shapes, num_unions, union_first, union_cells, intervals, interval_used, b);
+  if (rc != PCV_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    release_query(b);
+    return rc;
+  }
+  *out = b;
+  return PCV_OK;
+}
+
+// PointQuery::filter_intervals (iterator.rs:66-119) on any scalar attribute; "intensity" is pcv_s2_query_run's interval
+extern "C" int pcv_s2_query_run_ex(pcv_s2_cloud* c, const pcv_shapes* shapes, uint32_t num_unions, const uint32_t* union_first,
+                                   const uint64_t* union_cells, const pcv_s2_filter* filters, uint32_t num_filters, pcv_s2_query** out) {
+  if (num_filters == 0) return pcv_s2_query_run(c, shapes, num_unions, union_first, union_cells, nullptr, nullptr, out);
+  if (!c) return PCV_E_INVALID;
+  if (!c->ctx) return c->fail(PCV_E_INVALID, "a cloud opened without a context has no device");
+  pcv_ctx* ctx = c->ctx;
+  if (!out) return ctx->fail(PCV_E_INVALID, "out is null");
+  *out = nullptr;
+  if (!filters) return ctx->fail(PCV_E_INVALID, "filters is null");
+  const uint64_t locations = (uint64_t)(shapes ? shapes->count : 0) + num_unions;
+  std::vector<double> intervals(2 * locations + 2, 0.0);
+  std::vector<uint8_t> used(locations + 1, 0);
+  std::vector<PcvS2ExtraFilter> extra;
+  bool on_intensity = false;
+  for (uint32_t k = 0; k < num_filters; ++k) {
+    const pcv_s2_filter& f = filters[k];
+    const std::string name(f.attribute ? f.attribute : "");
+    if (f.location >= locations)
+      return ctx->fail(PCV_E_INVALID, "filter " + std::to_string(k) + " names location " + std::to_string(f.location) + ", the call has " + std::to_string(locations));
+    if (name == "color") return ctx->fail(PCV_E_INVALID, "a filter takes a scalar attribute; 'color' is a vector attribute");
+    if (name == "intensity") {
+      if (!c->has_intensity) return ctx->fail(PCV_E_INVALID, "this S2 cell cloud has no intensity attribute to filter on");
+      if (used[f.location]) return ctx->fail(PCV_E_INVALID, "two filters on attribute 'intensity' for location " + std::to_string(f.location));
+      intervals[2 * f.location] = f.lo, intervals[2 * f.location + 1] = f.hi, used[f.location] = 1;
+      on_intensity = true;
+      continue;
+    }
+    const int e = c->find_extra(name.c_str());
+    if (e < 0) return ctx->fail(PCV_E_INVALID, "Data type for attribute '" + name + "' not found.");  // lib.rs:94
+    if (c->extras[(size_t)e].elem == 3 || c->extras[(size_t)e].elem == 24)
+      return ctx->fail(PCV_E_INVALID, "a filter takes a scalar attribute; '" + name + "' is a vector attribute");
+    for (const PcvS2ExtraFilter& o : extra)
+      if (o.location == f.location && o.extra == e)
+        return ctx->fail(PCV_E_INVALID, "two filters on attribute '" + name + "' for location " + std::to_string(f.location));
+    extra.push_back(PcvS2ExtraFilter{f.location, e, f.lo, f.hi});
+  }
+  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  pcv_s2_query* b = new pcv_s2_query();
+  b->cloud = c;
+  const int rc = run_impl(c, shapes, num_unions, union_first, union_cells, on_intensity ? intervals.data() : nullptr, used.data(), b, &extra);
   if (rc != PCV_OK) {
     (void)hipStreamSynchronize(ctx->stream);
     release_query(b);

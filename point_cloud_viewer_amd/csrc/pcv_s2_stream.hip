@@ -103,6 +103,7 @@ struct pcv_s2_stream {
   uint64_t flush_points = 0;
   uint64_t memory_cap = kMemoryPointCap;
   bool decided = false, has_intensity = false;  // the first non-empty batch (or the directory appended to) decides
+  std::vector<std::pair<std::string, int32_t>> extras;  // ... and the extra attributes, ascending by name
   bool broken = false;                          // a flush failed in the middle of an append: only finish / abort are left
   uint64_t batches = 0, points = 0, pending_points = 0, flushes = 0;
   std::vector<pcv_s2_cloud*> parts;  // pending, non-empty, in batch order
@@ -136,7 +137,7 @@ int merge_pending(pcv_s2_stream* s, pcv_s2_cloud** out) {
   pcv_ctx* ctx = s->ctx;
   *out = nullptr;
   const bool with_order = !s->dir_mode;
-  if (s->parts.size() == 1 && s->part_base[0] == 0) {
+  if (s->parts.size() == 1 && s->part_base[0] == 0) {  // (its extras come along as they are)
     *out = s->parts[0];
     s->parts.clear();
     s->drop_parts();
@@ -190,6 +191,8 @@ int merge_pending(pcv_s2_stream* s, pcv_s2_cloud** out) {
                            d_chunk_first, d_parts, (double*)c->d_xyz, c->d_rgb, (float*)c->d_int, c->d_order);
       }
       PCV_HIP_CHECK(ctx, hipGetLastError());
+      // the extras: one launch each over the same plan (pcv_s2_attr.hip)
+      if (!s->extras.empty() && (r = pcv_s2_attr_merge(ctx, sc, n, num_segments, num_chunks, d_seg_dst, d_segs, d_chunk_first, s->parts, c))) return r;
       PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // (the tables above are host vectors and scratch of this scope)
       ctx->prof_resolve();
       return PCV_OK;
@@ -231,6 +234,7 @@ int flush(pcv_s2_stream* s) {
     rc = pcv_s2_write_cells(s->directory.c_str(), c->ids.size(), c->ids.data(), c->counts.data(), c->offsets.data(), truncate.data(), h_xyz, h_rgb,
                             h_int, &error);
     if (rc != PCV_OK) ctx->fail(rc, error);
+    if (rc == PCV_OK && !c->extras.empty()) rc = pcv_s2_attr_write(c, s->directory.c_str(), truncate.data());
   }
   if (h_xyz) ctx->host_release(h_xyz);
   if (h_rgb) ctx->host_release(h_rgb);
@@ -317,6 +321,7 @@ extern "C" int pcv_s2_stream_begin(pcv_ctx* ctx, const pcv_s2_stream_params* par
     }
     if (s->points) s->fold_box(meta.bbox_min, meta.bbox_max);
     s->decided = true, s->has_intensity = meta.has_intensity;
+    s->extras = meta.extras;
   }
   if (!ctx) {
     delete s;
@@ -333,15 +338,36 @@ extern "C" int pcv_s2_stream_set_memory_cap(pcv_s2_stream* s, uint64_t max_point
   return PCV_OK;
 }
 
-extern "C" int pcv_s2_stream_append(pcv_s2_stream* s, const pcv_points* batch) {
+extern "C" int pcv_s2_stream_append(pcv_s2_stream* s, const pcv_points* batch) { return pcv_s2_stream_append_ex(s, batch, nullptr, 0); }
+
+extern "C" int pcv_s2_stream_append_ex(pcv_s2_stream* s, const pcv_points* batch, const pcv_attribute* attrs, uint32_t num_attrs) {
   if (!s) return PCV_E_INVALID;
   pcv_ctx* ctx = s->ctx;
   if (s->broken) return ctx->fail(PCV_E_INVALID, "this S2 stream failed while flushing; finish or abort it");
   if (!batch) return ctx->fail(PCV_E_INVALID, "points is null");
   const std::string which = " (batch " + std::to_string(s->batches) + " of the stream)";
+  std::vector<PcvS2Extra> extras;
+  {
+    std::string why;
+    if (pcv_s2_attr_check(attrs, num_attrs, batch->n, &extras, &why)) return ctx->fail(PCV_E_INVALID, why + which);
+  }
   if (batch->n > 0 && batch->n < kMemoryPointCap) {
     if (s->decided && s->has_intensity != (batch->intensity != nullptr))
       return ctx->fail(PCV_E_INVALID, "S2Splitter received incompatible data types for attribute intensity" + which);  // s2.rs:155
+    if (s->decided) {  // another type, an unknown name — and a missing one, which the reference lets through
+      const char* bad = nullptr;
+      for (const PcvS2Extra& e : extras) {
+        bool known = false;
+        for (const auto& have : s->extras) known = known || (have.first == e.name && have.second == e.data_type);
+        if (!known && !bad) bad = e.name.c_str();
+      }
+      for (const auto& have : s->extras) {
+        bool given = false;
+        for (const PcvS2Extra& e : extras) given = given || e.name == have.first;
+        if (!given && !bad) bad = have.first.c_str();
+      }
+      if (bad) return ctx->fail(PCV_E_INVALID, std::string("S2Splitter received incompatible data types for attribute ") + bad + which);
+    }
     if (!s->dir_mode && batch->n >= s->memory_cap - std::min(s->points, s->memory_cap))
       return ctx->fail(PCV_E_INVALID, "an in-memory S2 stream holds fewer than " + std::to_string(s->memory_cap) +
                                           " points; a stream with a directory has no such limit" + which);
@@ -355,14 +381,14 @@ extern "C" int pcv_s2_stream_append(pcv_s2_stream* s, const pcv_points* batch) {
     }
   }
   pcv_s2_cloud* part;
-  int rc = pcv_s2_split_part(ctx, batch, s->level, !s->dir_mode, &part);
+  int rc = pcv_s2_split_part(ctx, batch, s->level, !s->dir_mode, &part, &extras);
   if (rc != PCV_OK) return rc == PCV_E_INVALID ? ctx->fail(rc, ctx->last_error + which) : rc;
   s->batches += 1;
   if (part->n == 0) {
     pcv_s2_release(part);
     return PCV_OK;
   }
-  if (!s->decided) s->decided = true, s->has_intensity = part->has_intensity;
+  if (!s->decided) s->decided = true, s->has_intensity = part->has_intensity, s->extras = pcv_s2_extra_list(part);
   s->fold_box(part->bbox_min, part->bbox_max);
   for (size_t k = 0; k < part->ids.size(); ++k) s->cell_counts[part->ids[k]] += part->counts[k];
   s->parts.push_back(part);
@@ -400,6 +426,11 @@ extern "C" int pcv_s2_stream_finish(pcv_s2_stream* s, pcv_s2_cloud** out) {
       if (s->parts.empty()) {  // what pcv_s2_split makes of no points
         c = new pcv_s2_cloud();
         c->ctx = ctx, c->level = s->level, c->has_intensity = s->decided && s->has_intensity;
+        for (const auto& a : s->extras) {
+          PcvS2Extra e;
+          e.name = a.first, e.data_type = a.second, e.elem = pcv_s2_attr_size(a.second);
+          c->extras.push_back(std::move(e));
+        }
       } else {
         rc = merge_pending(s, &c);
       }
@@ -417,7 +448,7 @@ extern "C" int pcv_s2_stream_finish(pcv_s2_stream* s, pcv_s2_cloud** out) {
       for (const auto& kv : s->cell_counts) ids.push_back(kv.first), counts.push_back(kv.second);
       std::string error;
       rc = pcv_s2_write_meta(s->directory.c_str(), s->bbox_min, s->bbox_max, ids.size(), ids.data(), counts.data(), s->decided && s->has_intensity,
-                             &error);
+                             &error, &s->extras);
       if (rc != PCV_OK) ctx->fail(rc, error);
     }
     if (rc == PCV_OK && out) rc = pcv_s2_open_dir(ctx, s->directory.c_str(), out);

@@ -63,6 +63,68 @@ class _Buf:
             self.size = a.size
 
 
+def _attr_type_of(arr):
+    """The type string of an attribute column, inferred from the array: (n,) of the ten scalar dtypes, (n, 3) u8 (u8vec3),
+    (n, 3) f64 (f64vec3)."""
+    shape = tuple(arr.shape)
+    if _is_torch(arr):
+        import torch
+        names = {torch.uint8: "u8", torch.int8: "i8", torch.int16: "i16", torch.int32: "i32", torch.int64: "i64",
+                 torch.float32: "f32", torch.float64: "f64"}
+        for t, k in (("uint16", "u16"), ("uint32", "u32"), ("uint64", "u64")):
+            if hasattr(torch, t):
+                names[getattr(torch, t)] = k
+        base = names.get(arr.dtype)
+    else:
+        dt = np.asarray(arr).dtype
+        base = {("u", 1): "u8", ("u", 2): "u16", ("u", 4): "u32", ("u", 8): "u64", ("i", 1): "i8", ("i", 2): "i16", ("i", 4): "i32",
+                ("i", 8): "i64", ("f", 4): "f32", ("f", 8): "f64"}.get((dt.kind, dt.itemsize))
+    if base is None:
+        raise TypeError(f"attribute: no attribute data type for dtype {arr.dtype}")
+    if len(shape) == 1:
+        return base
+    if len(shape) == 2 and shape[1] == 3 and base in ("u8", "f64"):
+        return base + "vec3"
+    raise TypeError(f"attribute: shape {shape} of {base} is no attribute column; (n,) scalars, (n, 3) u8 or (n, 3) f64 are")
+
+
+def _attributes(attrs, n, device):
+    """dict name -> array | (array, type string) as the pcv_attribute list of a batch of n points that lives on the device or
+    not -> (ctypes array or None, count, keep-alive)."""
+    if not attrs:
+        return None, 0, []
+    out, keep = (L.Attribute * len(attrs))(), []
+    for k, (name, col) in enumerate(attrs.items()):
+        typ = None
+        if isinstance(col, tuple):
+            col, typ = col
+        if not _is_torch(col):
+            col = np.asarray(col)
+        typ = _attr_type_of(col) if typ is None else str(typ).lower()
+        if typ not in L.ATTR_TYPES:
+            raise L.PcvError(L.PCV_E_INVALID, f"Attribute data type invalid (attribute '{name}', type {typ!r})")
+        code, dtype, comps = L.ATTR_TYPES[typ]
+        if _is_torch(col):
+            if not col.is_contiguous():
+                raise ValueError(f"attribute '{name}': tensor must be contiguous")
+            if bool(col.is_cuda) != bool(device) and n > 0:
+                raise ValueError("all point arrays must live in the same memory space")
+            nbytes, ptr = col.numel() * col.element_size(), col.data_ptr()
+        else:
+            if col.dtype.itemsize != np.dtype(dtype).itemsize:
+                raise TypeError(f"attribute '{name}': dtype {col.dtype} is not of type {typ}")
+            if device and n > 0:
+                raise ValueError("all point arrays must live in the same memory space")
+            col = np.ascontiguousarray(col)
+            nbytes, ptr = col.nbytes, col.ctypes.data
+        if nbytes != n * comps * np.dtype(dtype).itemsize:
+            raise ValueError(f"attribute '{name}': {nbytes} bytes, {n} points of type {typ} need {n * comps * np.dtype(dtype).itemsize}")
+        name_b = os.fsencode(name) if isinstance(name, str) else bytes(name)
+        keep.extend((col, name_b))
+        out[k].name, out[k].data_type, out[k].reserved, out[k].data = name_b, code, 0, ptr
+    return out, len(attrs), keep
+
+
 class Context:
     """One pcv_ctx: bound to one HIP device and stream, not thread-safe (include/pcv_hip.h).
 
@@ -435,12 +497,17 @@ class Context:
         return keep
 
     def s2_split(self, points, split_level=20):
-        """S2Splitter::write for one batch: `points` = dict(x=, y=, z=, color=[, intensity=]) of ECEF points (host arrays or
-        device tensors) grouped by their S2 cell at split_level -> S2Cloud. An invalid ECEF point raises PcvError
-        (PCV_E_INVALID) naming the first one."""
+        """S2Splitter::write for one batch: `points` = dict(x=, y=, z=, color=[, intensity=][, attributes=]) of ECEF points
+        (host arrays or device tensors) grouped by their S2 cell at split_level -> S2Cloud. attributes: a dict from name to
+        column — (n,) of a scalar dtype, (n, 3) u8 or (n, 3) f64; `(tensor, "u64")` states the type where the dtype cannot
+        (pcv_s2_split_ex). An invalid ECEF point raises PcvError (PCV_E_INVALID) naming the first one."""
         p, keep_alive = self._points(points["x"], points["y"], points["z"], points["color"], points.get("intensity"))
+        attrs, num_attrs, keep_attrs = _attributes(points.get("attributes"), p.n, p.mem == L.MEM_DEVICE)
         h = C.c_void_p()
-        self._check(self.lib.pcv_s2_split(self.handle, C.byref(p), int(split_level), C.byref(h)))
+        if num_attrs:
+            self._check(self.lib.pcv_s2_split_ex(self.handle, C.byref(p), attrs, num_attrs, int(split_level), C.byref(h)))
+        else:
+            self._check(self.lib.pcv_s2_split(self.handle, C.byref(p), int(split_level), C.byref(h)))
         return S2Cloud(self, h)
 
     def s2_open(self, directory):
@@ -2106,6 +2173,26 @@ class S2QueryBatch(QueryBatch):
         self._segments = None
         self.ctx._children.add(self)
 
+    def attribute(self, name, first_segment=0, num_segments=None):
+        """One extra attribute of the kept points of segments [first_segment, first_segment + num_segments) (default: to the
+        end), in segment order (pcv_s2_query_attribute): a numpy array of the attribute's type, (m,) or (m, 3)."""
+        self._live()
+        _, _, off = self.segments()
+        first = int(first_segment)
+        num = self.num_segments - first if num_segments is None else int(num_segments)
+        name_b = os.fsencode(name)
+        if not (0 <= first <= self.num_segments and 0 <= num <= self.num_segments - first):
+            self.ctx._check(self.lib.pcv_s2_query_attribute(self.handle, name_b, max(first, 0), max(num, 0) or (1 << 63), 0, L.MEM_HOST, None))
+        m = int(off[first + num] - off[first])
+        typ = self.tree.attributes.get(name)
+        if typ is None:  # the library's own refusal
+            self.ctx._check(self.lib.pcv_s2_query_attribute(self.handle, name_b, first, num, 0, L.MEM_HOST, None))
+            raise L.PcvError(L.PCV_E_INVALID, f"Data type for attribute '{name}' not found.")
+        _, dtype, comps = L.ATTR_TYPES[typ]
+        out = np.zeros((m, comps) if comps > 1 else m, dtype=dtype)
+        self.ctx._check(self.lib.pcv_s2_query_attribute(self.handle, name_b, first, num, m, L.MEM_HOST, out.ctypes.data))
+        return out
+
 
 class S2Cloud:
     """An S2 cell cloud held by the library (pcv_s2_cloud): the cells ascending by id and cell-contiguous device blobs."""
@@ -2122,12 +2209,43 @@ class S2Cloud:
         self.num_cells, self.num_points, self.has_intensity, self.split_level = nc.value, n.value, bool(has_int.value), level.value
         self.bbox_min, self.bbox_max = np.array(bmin[:]), np.array(bmax[:])
         self._cells = None
+        self._attributes = None
 
     def _check(self, rc):
         if self.ctx is not None:
             self.ctx._check(rc)
         else:
             _host_check(rc, "S2Cloud")
+
+    @property
+    def attributes(self):
+        """The extra attributes: dict name -> type string ("u8" ... "f64", "u8vec3", "f64vec3"), ascending by name
+        (pcv_s2_attributes). `color` and `intensity` are the built-in columns and not listed."""
+        if self._attributes is None:
+            self._alive()
+            count = C.c_uint32()
+            names, types = (C.c_char_p * L.S2_MAX_EXTRAS)(), (C.c_int32 * L.S2_MAX_EXTRAS)()
+            self._check(self.lib.pcv_s2_attributes(self.handle, C.byref(count), names, types))
+            self._attributes = {os.fsdecode(names[k]): L.ATTR_NAMES[types[k]] for k in range(count.value)}
+        return dict(self._attributes)
+
+    def cell_attribute(self, name, first=0, count=None):
+        """One extra attribute of cells [first, first + count) as it stands in their `<token>.<name>` files
+        (pcv_s2_cell_attribute): a numpy array of the attribute's type, (m,) or (m, 3)."""
+        self._alive()
+        count = self.num_cells - first if count is None else count
+        if first < 0 or count < 0 or first + count > self.num_cells:
+            raise ValueError("cell range past the end")
+        name_b = os.fsencode(name)
+        typ = self.attributes.get(name)
+        if typ is None:  # the library's own refusal
+            self._check(self.lib.pcv_s2_cell_attribute(self.handle, name_b, first, count, 0, L.MEM_HOST, None))
+            raise L.PcvError(L.PCV_E_INVALID, f"Data type for attribute '{name}' not found.")
+        m = int(self.cells[1][first:first + count].sum())
+        _, dtype, comps = L.ATTR_TYPES[typ]
+        out = np.zeros((m, comps) if comps > 1 else m, dtype=dtype)
+        self._check(self.lib.pcv_s2_cell_attribute(self.handle, name_b, first, count, m, L.MEM_HOST, out.ctypes.data))
+        return out
 
     def _alive(self):
         if not self.handle or (self.ctx is not None and not self.ctx.handle):
@@ -2183,12 +2301,28 @@ class S2Cloud:
                                                           first.ctypes.data, flat.ctypes.data, capacity, counts.ctypes.data, out.ctypes.data))
         return [out[l, :counts[l]].copy() for l in range(locations)]
 
-    def query_batch(self, shapes=None, unions=None, intervals=None):
+    def query_batch(self, shapes=None, unions=None, intervals=None, filters=None):
         """The points of every location of one call (pcv_s2_query_run): the prepared `shapes`, then `unions`; intervals: None,
-        or one entry per location, None or (lo, hi) on intensity. Returns an S2QueryBatch."""
+        or one entry per location, None or (lo, hi) on intensity. filters (pcv_s2_query_run_ex): None, or one entry per
+        location, None or a dict {attribute name: (lo, hi)} of closed intervals on scalar attributes ("intensity" included),
+        ANDed; give `intervals` or `filters`, not both. Returns an S2QueryBatch."""
         self._alive()
         first, flat = _s2_unions(unions)
         locations = (shapes.count if shapes is not None else 0) + first.size - 1
+        if filters is not None:
+            if intervals is not None:
+                raise ValueError("query_batch: give intervals or filters, not both (a filter may name 'intensity')")
+            filters = list(filters)
+            if len(filters) != locations:
+                raise ValueError(f"filters: expected {locations} entries (one per location), got {len(filters)}")
+            flat_filters = [(l, os.fsencode(name), float(v[0]), float(v[1])) for l, f in enumerate(filters) if f for name, v in f.items()]
+            arr = (L.S2Filter * max(1, len(flat_filters)))()
+            for k, (l, name_b, lo, hi) in enumerate(flat_filters):
+                arr[k].location, arr[k].reserved, arr[k].attribute, arr[k].lo, arr[k].hi = l, 0, name_b, lo, hi
+            h = C.c_void_p()
+            self._check(self.lib.pcv_s2_query_run_ex(self.handle, shapes.handle if shapes is not None else None, first.size - 1,
+                                                     first.ctypes.data, flat.ctypes.data, arr, len(flat_filters), C.byref(h)))
+            return S2QueryBatch(self, h, locations)
         iv = used = None
         if intervals is not None:
             intervals = list(intervals)
@@ -2227,7 +2361,7 @@ class S2Cloud:
         return xt
 
     def write(self, directory):
-        """<token>.xyz/.rgb[/.intensity] per cell + meta.pb (pcv_s2_write_dir)."""
+        """<token>.xyz/.rgb[/.intensity] and <token>.<name> per extra attribute, per cell, + meta.pb (pcv_s2_write_dir)."""
         self._alive()
         self._check(self.lib.pcv_s2_write_dir(self.handle, os.fsencode(directory)))
 
@@ -2256,8 +2390,9 @@ class S2Stream:
             raise ValueError("this S2 stream is finished")
 
     def append(self, points):
-        """One batch: the SoA dict of s2_split (x=, y=, z=, color=[, intensity=]) or a PointsBatch dict (position= (n, 3)
-        f64, color= (n, 3) u8[, intensity= (n,) f32], src/lib.rs:102-107); host arrays or device tensors."""
+        """One batch: the SoA dict of s2_split (x=, y=, z=, color=[, intensity=][, attributes=]) or a PointsBatch dict
+        (position= (n, 3) f64, color= (n, 3) u8[, intensity= (n,) f32][, attributes=], src/lib.rs:102-107); host arrays or
+        device tensors. The first non-empty batch fixes the attribute set (pcv_s2_stream_append_ex)."""
         self._alive()
         if "position" in points:
             pos = points["position"]
@@ -2271,7 +2406,8 @@ class S2Stream:
         else:
             x, y, z = points["x"], points["y"], points["z"]
         p, keep_alive = self.ctx._points(x, y, z, points["color"], points.get("intensity"))
-        self.ctx._check(self.lib.pcv_s2_stream_append(self.handle, C.byref(p)))
+        attrs, num_attrs, keep_attrs = _attributes(points.get("attributes"), p.n, p.mem == L.MEM_DEVICE)
+        self.ctx._check(self.lib.pcv_s2_stream_append_ex(self.handle, C.byref(p), attrs, num_attrs))
 
     @property
     def info(self):
@@ -2373,6 +2509,39 @@ def s2_union_contains(cells, x, y, z):
     keep = np.zeros(x.size, dtype=np.uint8)
     _host_check(L.load_library().pcv_s2_union_contains_host(cells.ctypes.data, cells.size, x.size, x.ctypes.data, y.ctypes.data,
                                                             z.ctypes.data, keep.ctypes.data), "pcv_s2_union_contains_host")
+    return keep
+
+
+def s2_check_attributes(attributes):
+    """pcv_s2_attributes_check_host (host only): the rules of s2_split's `attributes` on a dict name -> type string (or a
+    proto enum value); raises PcvError (PCV_E_INVALID) naming the attribute that breaks one."""
+    arr, keep = (L.Attribute * max(1, len(attributes)))(), []
+    for k, (name, typ) in enumerate(attributes.items()):
+        name_b = name if isinstance(name, bytes) else os.fsencode(name)
+        keep.append(name_b)
+        arr[k].name, arr[k].data_type = name_b, typ if isinstance(typ, int) else L.ATTR_TYPES.get(str(typ).lower(), (0,))[0]
+    _host_check(L.load_library().pcv_s2_attributes_check_host(arr, len(attributes)), "pcv_s2_attributes_check_host")
+
+
+def s2_filter_keep(dtype, data, lo, hi, keep=None):
+    """pcv_s2_filter_keep_host (host only): the filter test of S2Cloud.query_batch for one scalar attribute — `data` as f64
+    (Rust's `as f64`) in [lo, hi] — ANDed into `keep` (uint8, default all ones), which is returned. dtype: a type string of
+    S2Cloud.attributes; a vector type is refused."""
+    typ = str(dtype).lower()
+    if typ not in L.ATTR_TYPES:
+        raise L.PcvError(L.PCV_E_INVALID, "Attribute data type invalid")
+    code, np_dtype, comps = L.ATTR_TYPES[typ]
+    data = np.asarray(data)
+    if comps == 1:
+        if data.dtype.itemsize != np.dtype(np_dtype).itemsize:
+            raise TypeError(f"s2_filter_keep: dtype {data.dtype} is not of type {typ}")
+        data = np.ascontiguousarray(data).ravel()
+    n = data.shape[0]
+    keep = np.ones(n, dtype=np.uint8) if keep is None else np.ascontiguousarray(keep, dtype=np.uint8)
+    if keep.size != n:
+        raise ValueError("keep must hold one byte per value")
+    data = np.ascontiguousarray(data)
+    _host_check(L.load_library().pcv_s2_filter_keep_host(code, n, data.ctypes.data, float(lo), float(hi), keep.ctypes.data), "pcv_s2_filter_keep_host")
     return keep
 
 

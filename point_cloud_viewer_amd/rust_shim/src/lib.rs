@@ -1085,6 +1085,34 @@ impl PointCloud for HipS2Cells {
 pub struct pcv_s2_stream {
     _private: [u8; 0],
 }
+/// pcv_attribute of include/pcv_hip.h, field for field: one extra attribute of a batch (every attribute of a PointsBatch but
+/// `color` and `intensity`, s2.rs:85-107); data_type is the proto enum value of AttributeDataType.
+#[repr(C)]
+pub struct PcvAttribute {
+    pub name: *const c_char,
+    pub data_type: i32,
+    pub reserved: u32,
+    pub data: *const std::ffi::c_void,
+}
+
+/// (proto enum value, first element) of an attribute's column: attributes.rs:8-21; nalgebra's Vector3 is three components in a row.
+fn attribute_column(data: &AttributeData) -> (i32, *const std::ffi::c_void, usize) {
+    match data {
+        AttributeData::U8(v) => (1, v.as_ptr() as *const _, v.len()),
+        AttributeData::U16(v) => (2, v.as_ptr() as *const _, v.len()),
+        AttributeData::U32(v) => (3, v.as_ptr() as *const _, v.len()),
+        AttributeData::U64(v) => (4, v.as_ptr() as *const _, v.len()),
+        AttributeData::I8(v) => (6, v.as_ptr() as *const _, v.len()),
+        AttributeData::I16(v) => (7, v.as_ptr() as *const _, v.len()),
+        AttributeData::I32(v) => (8, v.as_ptr() as *const _, v.len()),
+        AttributeData::I64(v) => (9, v.as_ptr() as *const _, v.len()),
+        AttributeData::F32(v) => (11, v.as_ptr() as *const _, v.len()),
+        AttributeData::F64(v) => (12, v.as_ptr() as *const _, v.len()),
+        AttributeData::U8Vec3(v) => (27, v.as_ptr() as *const _, v.len()),
+        AttributeData::F64Vec3(v) => (38, v.as_ptr() as *const _, v.len()),
+    }
+}
+
 /// pcv_s2_stream_params of include/pcv_hip.h, field for field.
 #[repr(C)]
 pub struct PcvS2StreamParams {
@@ -1099,6 +1127,7 @@ pub struct PcvS2StreamParams {
 extern "C" {
     fn pcv_s2_stream_begin(ctx: *mut pcv_ctx, params: *const PcvS2StreamParams, out: *mut *mut pcv_s2_stream) -> c_int;
     fn pcv_s2_stream_append(stream: *mut pcv_s2_stream, batch: *const PcvPoints) -> c_int;
+    fn pcv_s2_stream_append_ex(stream: *mut pcv_s2_stream, batch: *const PcvPoints, attrs: *const PcvAttribute, num_attrs: u32) -> c_int;
     fn pcv_s2_stream_info(stream: *const pcv_s2_stream, batches: *mut u64, points: *mut u64, cells: *mut u64, pending_points: *mut u64, flushes: *mut u64) -> c_int;
     fn pcv_s2_stream_finish(stream: *mut pcv_s2_stream, out: *mut *mut pcv_s2_cloud) -> c_int;
     fn pcv_s2_stream_abort(stream: *mut pcv_s2_stream);
@@ -1171,7 +1200,7 @@ impl NodeWriter<PointsBatch> for S2Stream {
     }
 
     /// S2Splitter::write (s2.rs:60-137) for one batch: the positions transposed to the planes pcv_points wants, colour and
-    /// intensity as they are.
+    /// intensity as they are, every other attribute as an extra of pcv_s2_stream_append_ex (s2.rs:85-107).
     fn write(&mut self, batch: &PointsBatch) -> std::io::Result<()> {
         let n = batch.position.len();
         let (mut x, mut y, mut z) = (Vec::with_capacity(n), Vec::with_capacity(n), Vec::with_capacity(n));
@@ -1190,7 +1219,17 @@ impl NodeWriter<PointsBatch> for S2Stream {
             None => std::ptr::null(),
         };
         let points = PcvPoints { n: n as u64, x: x.as_ptr(), y: y.as_ptr(), z: z.as_ptr(), color, color_stride: 3, intensity, mem: 0 };
-        if unsafe { pcv_s2_stream_append(self.stream, &points) } != 0 {
+        let mut names = Vec::new(); // kept alive until the call returns
+        let mut extras = Vec::new();
+        for (name, data) in batch.attributes.iter().filter(|(k, _)| k.as_str() != "color" && k.as_str() != "intensity") {
+            let (data_type, ptr, len) = attribute_column(data);
+            if len != n {
+                return Err(std::io::Error::new(std::io::ErrorKind::InvalidInput, format!("attribute {} holds {} values for {} positions", name, len, n)));
+            }
+            names.push(CString::new(name.as_str()).map_err(|e| std::io::Error::new(std::io::ErrorKind::InvalidInput, e))?);
+            extras.push(PcvAttribute { name: names.last().unwrap().as_ptr(), data_type, reserved: 0, data: ptr });
+        }
+        if unsafe { pcv_s2_stream_append_ex(self.stream, &points, extras.as_ptr(), extras.len() as u32) } != 0 {
             return Err(self.io_error());
         }
         Ok(())
