@@ -1,7 +1,8 @@
 /* build_xray_quadtree.c — xray's build_xray_quadtree over the C ABI in plain C11: one or more point cloud directories (the
  * reference's point_cloud_locations) are opened — all as octrees, or all as S2 cell clouds when the first directory's
  * meta.pb says so (pcv_cloud_kind, as PointCloudClientBuilder::build decides) — the leaf tiles over all of them are
- * rasterised on the device (pcv_xray_run_ex, or pcv_s2_open_dir + pcv_xray_run_s2; every flag works for both kinds),
+ * rasterised on the device (pcv_xray_run_ex, or pcv_s2_open_dir + pcv_xray_run_s2_ex; over S2 directories --filter-interval,
+ * repeatable, and --binning take any scalar attribute of the clouds, over octrees intensity alone),
  * every level above them up to the root node is built on the device (pcv_xray_build_parents), and
  * the quadtree directory the xray viewer loads is written: one <node>.png per node and the meta file
  * (pcv_xray_write_dir_ex). A subset of the reference binary's flags, and --png: stored (the default) or deflate, the
@@ -11,9 +12,9 @@
  *
  *   build_xray_quadtree <octree dir | S2 cell cloud dir>... --output-directory <dir> --resolution <m per px> [--tile-size <px>]
  *                       [--coloring-strategy xray|colored|colored_with_intensity|colored_with_height_stddev]
- *                       [--min-intensity <f>] [--max-intensity <f>] [--binning intensity=<size>] [--max-stddev <m>]
+ *                       [--min-intensity <f>] [--max-intensity <f>] [--binning <attribute>=<size>] [--max-stddev <m>]
  *                       [--colormap jet|purplish] [--tile-background-color white|transparent]
- *                       [--filter-interval intensity=<lo>,<hi>] [--root-node-id <r...>] [--png stored|deflate]
+ *                       [--filter-interval <attribute>=<lo>,<hi>]... [--root-node-id <r...>] [--png stored|deflate]
  *                       [--inpaint-distance-px <0..254>]
  */
 #include <stdio.h>
@@ -27,9 +28,10 @@ static int usage(void) {
           "usage: build_xray_quadtree <octree dir | S2 cell cloud dir>... --output-directory <dir> --resolution <m per px>\n"
           "       [--tile-size <px>]\n"
           "       [--coloring-strategy xray|colored|colored_with_intensity|colored_with_height_stddev] [--min-intensity <f>]\n"
-          "       [--max-intensity <f>] [--binning intensity=<size>] [--max-stddev <m>] [--colormap jet|purplish]\n"
-          "       [--tile-background-color white|transparent] [--filter-interval intensity=<lo>,<hi>] [--root-node-id <r...>]\n"
+          "       [--max-intensity <f>] [--binning <attribute>=<size>] [--max-stddev <m>] [--colormap jet|purplish]\n"
+          "       [--tile-background-color white|transparent] [--filter-interval <attribute>=<lo>,<hi>]... [--root-node-id <r...>]\n"
           "       [--png stored|deflate] [--inpaint-distance-px <0..254>]\n"
+          "       attributes: any scalar one of S2 cell clouds (timestamp=30000000000), intensity alone with octrees\n"
           "       the first directory's meta.pb decides: octrees, or S2 directories (S2 cell clouds); all are opened as that kind\n");
   return 2;
 }
@@ -41,8 +43,11 @@ int main(int argc, char** argv) {
   const char* root = "r";
   int png = PCV_XRAY_PNG_STORED;
   long inpaint = -1; /* no inpainting */
-  char attribute[16] = "";
-  char bin_attribute[16] = "";
+  /* one entry per --filter-interval; the names are copies that live until the run is over */
+  pcv_xray_filter* filters = (pcv_xray_filter*)calloc((size_t)argc, sizeof(pcv_xray_filter));
+  char** filter_names = (char**)calloc((size_t)argc, sizeof(char*));
+  uint32_t num_filters = 0;
+  char bin_attribute[PCV_S2_MAX_ATTR_NAME + 1] = "";
   pcv_xray_coloring col;
   memset(&col, 0, sizeof(col));
   col.min_intensity = 0.0f; /* the reference's defaults (build_quadtree.rs:49-66) */
@@ -96,10 +101,14 @@ int main(int argc, char** argv) {
       else return usage();
     } else if (!strcmp(a, "--filter-interval")) {
       const char* eq = strchr(v, '=');
-      if (!eq || (size_t)(eq - v) >= sizeof(attribute) || sscanf(eq + 1, "%lf,%lf", &p.interval[0], &p.interval[1]) != 2) return usage();
-      memcpy(attribute, v, (size_t)(eq - v));
-      attribute[eq - v] = '\0';
-      p.interval_attribute = attribute;
+      pcv_xray_filter* f = filters ? &filters[num_filters] : NULL;
+      if (!f || !filter_names || !eq || sscanf(eq + 1, "%lf,%lf", &f->lo, &f->hi) != 2) return usage();
+      char* name = (char*)calloc((size_t)(eq - v) + 1, 1);
+      if (!name) return usage();
+      memcpy(name, v, (size_t)(eq - v));
+      filter_names[num_filters] = name;
+      f->attribute = name;
+      ++num_filters;
     } else if (!strcmp(a, "--root-node-id")) {
       root = v;
     } else if (!strcmp(a, "--inpaint-distance-px")) {
@@ -136,11 +145,17 @@ int main(int argc, char** argv) {
     free(inputs);
     return 1;
   }
+  if (kind != PCV_CLOUD_S2 && num_filters) { /* an octree takes one interval, on intensity (the library checks the name) */
+    p.interval_attribute = filters[num_filters - 1].attribute;
+    p.interval[0] = filters[num_filters - 1].lo;
+    p.interval[1] = filters[num_filters - 1].hi;
+  }
   rc = pcv_ctx_create(0, NULL, &ctx);
   for (uint32_t t = 0; t < num_inputs && rc == PCV_OK; ++t)
     rc = kind == PCV_CLOUD_S2 ? pcv_s2_open_dir(ctx, inputs[t], &clouds[t]) : pcv_octree_open_dir(ctx, inputs[t], &trees[t]);
   if (rc == PCV_OK)
-    rc = kind == PCV_CLOUD_S2 ? pcv_xray_run_s2(ctx, clouds, num_inputs, &p, &col, &x) : pcv_xray_run_ex(ctx, trees, num_inputs, &p, &col, &x);
+    rc = kind == PCV_CLOUD_S2 ? pcv_xray_run_s2_ex(ctx, clouds, num_inputs, &p, &col, filters, num_filters, &x)
+                              : pcv_xray_run_ex(ctx, trees, num_inputs, &p, &col, &x);
   if (rc == PCV_OK && inpaint >= 0) { /* the result carries its own parent levels */
     pcv_xray* filled = NULL;
     rc = pcv_xray_inpaint(ctx, x, NULL, 0, (uint32_t)inpaint, background, &filled);
@@ -170,6 +185,9 @@ int main(int argc, char** argv) {
   free(trees);
   free(clouds);
   free(inputs);
+  for (uint32_t k = 0; k < num_filters; ++k) free(filter_names[k]);
+  free(filter_names);
+  free(filters);
   if (ctx) pcv_ctx_destroy(ctx);
   return rc == PCV_OK ? 0 : 1;
 }

@@ -76,5 +76,8 @@ PCV_SA(sizeof(pcv_attribute) == 24 && offsetof(pcv_attribute, name) == 0 && offs
 PCV_SA(sizeof(pcv_s2_filter) == 32 && offsetof(pcv_s2_filter, location) == 0 && offsetof(pcv_s2_filter, reserved) == 4 &&
            offsetof(pcv_s2_filter, attribute) == 8 && offsetof(pcv_s2_filter, lo) == 16 && offsetof(pcv_s2_filter, hi) == 24,
        "pcv_s2_filter");
+PCV_SA(sizeof(pcv_xray_filter) == 24 && offsetof(pcv_xray_filter, attribute) == 0 && offsetof(pcv_xray_filter, lo) == 8 &&
+           offsetof(pcv_xray_filter, hi) == 16,
+       "pcv_xray_filter");
 
 #endif

@@ -791,8 +791,9 @@ void pcv_query_batch_free(pcv_query_batch* b);
 #define PCV_XRAY_BG_TRANSPARENT 1
 
 /* XrayParameters (:452-461) + the coloring strategy. ColoredWithIntensity and binning take the extra pcv_xray_coloring of
- * pcv_xray_run_ex; filters on attributes other than intensity are not offered; several octrees go through
- * pcv_xray_run_many or pcv_xray_run_ex. */
+ * pcv_xray_run_ex; an octree carries only color and intensity, so interval_attribute is "intensity" or NULL (S2 cell clouds
+ * filter and bin on any scalar attribute: pcv_xray_run_s2_ex); several octrees go through pcv_xray_run_many or
+ * pcv_xray_run_ex. */
 typedef struct pcv_xray_params {
   uint32_t tile_size_px;        /* W = H, 1 ..= 32768 */
   uint32_t strategy;            /* PCV_XRAY_XRAY / _COLORED / _HEIGHT_STDDEV / _COLORED_WITH_INTENSITY (pcv_xray_run_ex only) */
@@ -856,9 +857,10 @@ int pcv_xray_check_params(const pcv_xray_params* params, int tree_has_intensity,
  *                                 PCV_XRAY_FN_INTENSITY);
  *   binning_attribute, bin_size   NULL: no binning; "intensity": bin = (intensity as f64 / bin_size) as i64 (Rust `as`:
  *                                 truncating, saturating, NaN -> 0; bin_size is not validated), generation.rs:138-157.
- *                                 Only "intensity" can be binned on ("color" is a U8Vec3, on which the reference panics,
- *                                 src/attributes.rs:128). Binning applies to PCV_XRAY_COLORED (per pixel: the mean over
- *                                 bins, in ascending bin order, of each bin's mean colour, :294-362) and
+ *                                 Only "intensity" can be binned on here ("color" is a U8Vec3, on which the reference
+ *                                 panics, src/attributes.rs:128); pcv_xray_run_s2_ex takes any scalar attribute of S2
+ *                                 clouds. Binning applies to PCV_XRAY_COLORED (per pixel: the mean over bins, in
+ *                                 ascending bin order, of each bin's mean colour, :294-362) and
  *                                 PCV_XRAY_COLORED_WITH_INTENSITY (the mean over bins of each bin's mean intensity,
  *                                 :210-292); xray and height_stddev never read it (attributes() :133) and their bytes do
  *                                 not change.
@@ -1417,9 +1419,9 @@ void pcv_s2_query_free(pcv_s2_query* q);
  *              at most PCV_S2_MAX_EXTRAS per cloud — each violation is PCV_E_INVALID with a message naming the attribute
  *   data       n elements, little endian, where points->mem says
  * A cell's file is `<token>.<name>`: the values of the cell's points in file order (src/lib.rs:74-80, read_write/raw.rs).
- * Out of scope: clouds without `color`; xray filters and binning on extras (`interval_attribute` other than "intensity"
- * stays refused); PLY properties as extras; the octree path, which is fixed to color and intensity as the reference's is
- * (src/octree/mod.rs:63-72). */
+ * xray reads the extras through pcv_xray_run_s2_ex (filters and binning on any scalar one). Out of scope: clouds without
+ * `color`; vector attributes as filters or bins; PLY properties as extras; the octree path, which is fixed to color and
+ * intensity as the reference's is (src/octree/mod.rs:63-72). */
 #define PCV_ATTR_U8 1
 #define PCV_ATTR_U16 2
 #define PCV_ATTR_U32 3
@@ -1514,6 +1516,47 @@ int pcv_s2_filter_keep_host(int32_t data_type, uint64_t n, const void* data, dou
  * geometric locations). Out of device memory is PCV_E_OOM with nothing left allocated. */
 int pcv_xray_run_s2(pcv_ctx* ctx, pcv_s2_cloud* const* clouds, uint32_t num_clouds, const pcv_xray_params* params,
                     const pcv_xray_coloring* coloring /* nullable */, pcv_xray** out);
+/* ---- xray over S2 cell clouds: filters and binning on any scalar attribute -------------- */
+/* One --filter-interval <attribute>=<min>,<max> of build_xray_quadtree (xray/src/build_quadtree.rs:94-101): a
+ * ClosedInterval<f64> on a scalar attribute of the clouds, an extra or `intensity`. */
+typedef struct pcv_xray_filter {
+  const char* attribute;
+  double lo, hi;
+} pcv_xray_filter;
+/* pcv_xray_run_s2 with a list of filters and with binning on any scalar attribute. With num_filters == 0 and a
+ * binning_attribute that is NULL or "intensity" it is pcv_xray_run_s2, byte for byte. Otherwise:
+ *   binning   coloring->binning_attribute names a scalar attribute of every cloud, an extra or `intensity`; the bin of a
+ *             point is `(value as f64 / bin_size) as i64` (BinnedColoringStrategy::bins, xray/src/generation.rs:138-157;
+ *             pcv_xray_bins_host is the same function), each cloud converting with its own data type, so two clouds may hold
+ *             one name as I64 and as U64. colored and colored_with_intensity read it; xray and height_stddev ignore it and
+ *             their bytes do not change (the name is checked all the same).
+ *   filters   every filter applies to every tile location of every cloud and is ANDed with `contains` (FilteredIterator over
+ *             filter_intervals, generation.rs:478-487), by pcv_s2_query_run_ex's test (pcv_s2_filter_keep_host);
+ *             params->interval_attribute ("intensity" or NULL) is ANDed with the list. A tile is created iff the kept points
+ *             summed over the clouds are > 0, so filters remove tiles from the created set.
+ * PCV_E_INVALID with a message and nothing left allocated: a filter attribute missing from some cloud ("Data type for
+ * attribute 'NAME' not found.", src/lib.rs:94) or a binning attribute missing from one ("Binning attribute needs to be
+ * available in points batch.", generation.rs:146), each naming the cloud's index; a vector attribute, `color` included; two
+ * filters on one attribute (an entry on `intensity` beside interval_attribute counts as such); a filter with a NULL name;
+ * and every refusal of pcv_xray_run_s2. A cloud opened from a directory loads the columns the run reads, and only those,
+ * before any raster work: a damaged or missing file is PCV_E_IO naming the file, and the cloud stays usable.
+ * Out of scope: vector attributes; the octree path (pcv_xray_run, _run_many, _run_ex and pcv_xray_check_params[_ex] keep
+ * refusing every attribute but intensity, as an octree carries nothing else); xray over clouds without `color`. */
+int pcv_xray_run_s2_ex(pcv_ctx* ctx, pcv_s2_cloud* const* clouds, uint32_t num_clouds, const pcv_xray_params* params,
+                       const pcv_xray_coloring* coloring /* nullable */, const pcv_xray_filter* filters, uint32_t num_filters,
+                       pcv_xray** out);
+/* Host only: the checks of that call that need no device, given per cloud the names and data types of its extras
+ * (cloud t's are entries [extras_first[t], extras_first[t + 1]) of names / data_types) and whether it has intensity. */
+int pcv_xray_check_attrs_host(const pcv_xray_params* params, const pcv_xray_coloring* coloring, const pcv_xray_filter* filters,
+                              uint32_t num_filters, uint32_t num_clouds, const uint32_t* extras_first /* num_clouds + 1 */,
+                              const char* const* names, const int32_t* data_types, const uint8_t* has_intensity, char* err,
+                              uint64_t errcap);
+/* Host only, no context: out[i] = (data[i] as f64 / bin_size) as i64 for n values of a scalar data_type, from the function the
+ * device compiles: `as f64` exact but for U64 / I64 (round to nearest, ties to even), a correctly rounded f64 division
+ * (bin_size is not validated: 0 gives +-inf or NaN), `as i64` truncating, saturating, NaN -> 0. A vector type is
+ * PCV_E_INVALID. */
+int pcv_xray_bins_host(int32_t data_type, uint64_t n, const void* data, double bin_size, int64_t* out);
+
 /* Host only: which arm PointCloudClientBuilder::build (point_cloud_client/src/lib.rs:107-132) would take for this
  * directory's meta.pb: `version <= 11 || has_octree()` is PCV_CLOUD_OCTREE, anything else PCV_CLOUD_S2. The reference
  * opens every location as the first one's kind; the entry points here take one kind each, and the caller decides. A missing

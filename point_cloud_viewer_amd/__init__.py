@@ -14,7 +14,7 @@ from .octree import (Aabb, Context, OctreeResult, QueryBatch, RenderedViews, S2C
                      render_check_overlay, render_check_params, render_gamma_lut, render_overlay, render_params,
                      web_mercator_rect_from_zoomed, wmr_contains, wmr_corners, wmr_from_lat_lng, wmr_math, wmr_project, wmr_to_lat_lng,
                      inpaint_xray_quadtree, merge_xray_quadtrees, png_decode, xray_check_params, xray_coloring, xray_finalize, xray_lanczos_taps, xray_leaf_tiles,
-                     xray_inpaint_check, xray_inpaint_plan, xray_merge_check, xray_open_host, xray_params, xray_png_encode, xray_png_encode_tiles)
+                     xray_bins, xray_check_attrs, xray_filters, xray_inpaint_check, xray_inpaint_plan, xray_merge_check, xray_open_host, xray_params, xray_png_encode, xray_png_encode_tiles)
 
 __all__ = ["Aabb", "Context", "OctreeResult", "QueryBatch", "RenderedViews", "XrayTiles", "build_octree", "level_table", "node_name", "PcvError",
            "load_library"]

@@ -179,6 +179,10 @@ class Attribute(C.Structure):  # pcv_attribute
     _fields_ = [("name", C.c_char_p), ("data_type", C.c_int32), ("reserved", C.c_uint32), ("data", C.c_void_p)]
 
 
+class XrayFilter(C.Structure):  # pcv_xray_filter
+    _fields_ = [("attribute", C.c_char_p), ("lo", C.c_double), ("hi", C.c_double)]
+
+
 class S2Filter(C.Structure):  # pcv_s2_filter
     _fields_ = [("location", C.c_uint32), ("reserved", C.c_uint32), ("attribute", C.c_char_p), ("lo", C.c_double), ("hi", C.c_double)]
 
@@ -414,6 +418,11 @@ _SIGNATURES = {
     "pcv_s2_cells_in_location": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp]),
     "pcv_s2_cells_in_location_host": (C.c_int, [C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp]),
     "pcv_xray_run_s2": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(XrayParams), C.POINTER(XrayColoring), C.POINTER(_vp)]),
+    "pcv_xray_run_s2_ex": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(XrayParams), C.POINTER(XrayColoring), C.POINTER(XrayFilter), C.c_uint32,
+                                     C.POINTER(_vp)]),
+    "pcv_xray_check_attrs_host": (C.c_int, [C.POINTER(XrayParams), C.POINTER(XrayColoring), C.POINTER(XrayFilter), C.c_uint32, C.c_uint32,
+                                            _vp, C.POINTER(C.c_char_p), _vp, _vp, C.c_char_p, C.c_uint64]),
+    "pcv_xray_bins_host": (C.c_int, [C.c_int32, C.c_uint64, _vp, C.c_double, _vp]),
     "pcv_cloud_kind": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
 }
 

@@ -357,8 +357,15 @@ int pcv_s2_attr_filter(pcv_ctx* ctx, PcvScratch& sc, pcv_s2_cloud* c, const PcvS
     const PcvS2Extra& e = c->extras[(size_t)extra];
     std::vector<FilterIval> ivals(locations, FilterIval{0.0, 0.0});
     std::vector<uint8_t> used(locations, 0);
-    for (const PcvS2ExtraFilter& f : filters)
-      if (f.extra == extra) ivals[f.location] = FilterIval{f.lo, f.hi}, used[f.location] = 1;
+    for (const PcvS2ExtraFilter& f : filters) {
+      if (f.extra != extra) continue;
+      if (f.location == kPcvS2EveryLocation) {  // the table filled uniformly: every chunk of the call takes the launch
+        std::fill(ivals.begin(), ivals.end(), FilterIval{f.lo, f.hi});
+        std::fill(used.begin(), used.end(), (uint8_t)1);
+      } else {
+        ivals[f.location] = FilterIval{f.lo, f.hi}, used[f.location] = 1;
+      }
+    }
     std::vector<uint32_t> which;
     for (size_t k = 0; k < chunks.size(); ++k)
       if (used[chunks[k].location]) which.push_back((uint32_t)k);

@@ -35,6 +35,23 @@ __host__ __device__ inline bool keep(T v, double lo, double hi) {
   return lo <= a && a <= hi;
 }
 
+// Rust `f64 as i64`: truncation, saturating; NaN -> 0 (the bin of xray/src/generation.rs:150)
+__host__ __device__ inline int64_t rust_i64(double v) {
+  if (v != v) return 0;
+  if (v >= 9223372036854775808.0) return INT64_MAX;
+  if (v < -9223372036854775808.0) return INT64_MIN;
+  return (int64_t)v;
+}
+
+// BinnedColoringStrategy::bins (xray/src/generation.rs:138-157) for every 1-d data type: `(e as f64 / size) as i64`. The
+// conversion is keep's; the division is one correctly rounded f64 division (no contraction, no fast math), and `size` is not
+// validated: 0 gives +-inf or NaN, which rust_i64 saturates or sends to 0. The xray raster (pcv_xray.hip) and
+// pcv_xray_bins_host both compile this.
+template <typename T>
+__host__ __device__ inline int64_t bin(T v, double size) {
+  return rust_i64((double)v / size);
+}
+
 // f(T{}) for the scalar type t; false: t is no scalar type
 template <typename F>
 inline bool dispatch_scalar(int32_t t, F&& f) {

@@ -88,6 +88,7 @@ int pcv_s2_attr_write(pcv_s2_cloud* c, const char* directory, const uint8_t* tru
                       std::vector<std::pair<std::string, int32_t>>* written = nullptr);
 // query: one filter launch per distinct filtered extra, between the flags launches and the scan (pcv_s2_points.hip)
 struct PcvS2Chunk;
+constexpr uint32_t kPcvS2EveryLocation = 0xffffffffu;  // PcvS2ExtraFilter::location: every location of the call (xray's tiles)
 struct PcvS2ExtraFilter {
   uint32_t location;
   int extra;  // index into pcv_s2_cloud::extras
@@ -95,6 +96,14 @@ struct PcvS2ExtraFilter {
 };
 int pcv_s2_attr_filter(pcv_ctx* ctx, PcvScratch& sc, pcv_s2_cloud* c, const PcvS2Chunk* d_chunks, const std::vector<PcvS2Chunk>& chunks,
                        uint64_t locations, const std::vector<PcvS2ExtraFilter>& filters, uint32_t* d_flags);
+
+// pcv_s2_query_run_ex's "every location" form (pcv_s2_points.hip), for a caller that has checked its filters itself
+// (pcv_xray_run_s2_ex): `intervals` as pcv_s2_query_run takes them (nullable, on intensity), and filters on extras whose
+// location is kPcvS2EveryLocation — no list of locations x filters is built
+struct pcv_shapes;
+struct pcv_s2_query;
+int pcv_s2_query_run_every(pcv_s2_cloud* c, const pcv_shapes* shapes, const double* intervals, const std::vector<PcvS2ExtraFilter>& filters,
+                           pcv_s2_query** out);
 
 // a union's cells as the entry points take them: ascending by id, no 0 (pcv_s2.hip); *why says what is wrong
 int pcv_s2_check_union(const uint64_t* cells, uint32_t num_cells, std::string* why);

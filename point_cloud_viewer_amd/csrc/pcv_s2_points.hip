@@ -299,6 +299,23 @@ extern "C" int pcv_s2_query_run_ex(pcv_s2_cloud* c, const pcv_shapes* shapes, ui
   return PCV_OK;
 }
 
+int pcv_s2_query_run_every(pcv_s2_cloud* c, const pcv_shapes* shapes, const double* intervals, const std::vector<PcvS2ExtraFilter>& filters,
+                           pcv_s2_query** out) {
+  pcv_ctx* ctx = c->ctx;
+  *out = nullptr;
+  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  pcv_s2_query* b = new pcv_s2_query();
+  b->cloud = c;
+  const int rc = run_impl(c, shapes, 0, nullptr, nullptr, intervals, nullptr, b, &filters);
+  if (rc != PCV_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    release_query(b);
+    return rc;
+  }
+  *out = b;
+  return PCV_OK;
+}
+
 extern "C" int pcv_s2_query_sizes(const pcv_s2_query* b, uint64_t* num_segments, uint64_t* num_points) {
   if (!b) return PCV_E_INVALID;
   if (num_segments) *num_segments = b->nseg;

@@ -13,7 +13,8 @@
 //                          query_from_global (:493-497), discretise (:119-123); count per (tile, 32 x 32 pixel block), aggregated per wave before the atomic
 //   scan   bucket counts -> u64 offsets (pcv_batch_scan)
 //   K_xs   xray_scatter    the same walk again, writing one 8-byte record per drawable point into its bucket (+ z as f64
-//                          for height_stddev)
+//                          for height_stddev, + the bin as i64 with binning: from the intensity, or over S2 clouds from any
+//                          scalar column of the cloud, pcv_xray_run_s2_ex, in an instance of its own)
 //   K_xa   xray_accum      one workgroup per bucket: per-pixel state in LDS (run-aggregated atomics), then the strategy's
 //                          colour (:159-199, :294-345, :365-408, colormap.rs, src/color.rs:29-36), the background of
 //                          assign_background_color (:684) and the block's RGBA rows
@@ -36,6 +37,7 @@
 #include <vector>
 
 #include "pcv_query_dev.h"
+#include "pcv_s2_attr_dev.h"
 #include "pcv_s2_obj.h"
 #include "pcv_s2_query_dev.h"
 #include "pcv_switches.h"
@@ -139,13 +141,7 @@ __host__ __device__ inline Rgba8 intensity_color(float mean, float lo, float hi)
   const float b = ln_f32(m - lo) / ln_f32(hi - lo);
   return to_u8(b, b, b, 1.0f);
 }
-// Rust `f64 as i64`: truncation, saturating; NaN -> 0 (the bin of generation.rs:150)
-__host__ __device__ inline int64_t rust_i64(double v) {
-  if (v != v) return 0;
-  if (v >= 9223372036854775808.0) return INT64_MAX;
-  if (v < -9223372036854775808.0) return INT64_MIN;
-  return (int64_t)v;
-}
+using s2attr::rust_i64;  // Rust `f64 as i64`, the bin of generation.rs:150: stated once, in pcv_s2_attr_dev.h
 
 // Rust `f64 as u32`: truncation, saturating; NaN -> 0
 __device__ __forceinline__ uint32_t sat_u32(double v) {
@@ -177,6 +173,13 @@ struct XrayTreeChunks {
   uint64_t c0;
   uint64_t first;
 };
+// the bin column of an S2 cloud, parallel to XrayBinArgs::trees (pcv_xray_run_s2_ex, binning on any scalar attribute): the
+// cloud's cell-contiguous column and its data type (s2attr, pcv_s2_attr_dev.h). Each cloud converts with its own type.
+struct XrayBinColumn {
+  const PCV_GLOBAL uint8_t* col;
+  int32_t data_type;
+  uint32_t pad;
+};
 struct XrayBinArgs {
   const XrayTreeChunks* trees;      // the group's octrees with at least one chunk, in list order
   uint32_t ntrees;
@@ -188,9 +191,10 @@ struct XrayBinArgs {
   uint32_t strategy;
   int32_t has_iso;
   double iso[7];                    // query_from_global: translation xyz, quaternion ijkw
-  int32_t binned;                   // colored / colored_with_intensity with binning on intensity
+  int32_t binned;                   // colored / colored_with_intensity with binning (on intensity unless `columns` is set)
   double bin_size;
   unsigned long long* negative;     // colored_with_intensity: kept points with intensity < 0 per created tile (count pass)
+  const XrayBinColumn* columns;     // S2, binning on a column: one entry per entry of `trees`; read by the COLUMN instance only
 };
 
 // per 64 points of a chunk: is the point drawn, its bucket (tile in group x block), its record, (stddev) its z, (binning)
@@ -207,6 +211,7 @@ struct XrayPoint {
 // untouched (24-byte AoS: a wave's 64 points are one contiguous 1 536-byte run), u32 keep flags, colour and intensity at
 // the same point index.
 struct XrayNodeSource {
+  static constexpr bool kBinColumn = false;
   const uint8_t* rgb;
   const float* inten;
   const ChunkDesc& d;
@@ -219,6 +224,7 @@ struct XrayNodeSource {
   __device__ __forceinline__ const uint8_t* color(uint32_t q) const { return rgb + 3 * (d.attr_index + q); }
 };
 struct XrayS2Source {
+  static constexpr bool kBinColumn = false;
   const PCV_GLOBAL double* xyz;   // the chunk's first point
   const PCV_GLOBAL uint8_t* rgb;
   const PCV_GLOBAL float* inten;  // null unless the strategy or the binning reads intensity
@@ -228,6 +234,32 @@ struct XrayS2Source {
   __device__ __forceinline__ float intensity(uint32_t q) const { return inten[q]; }
   __device__ __forceinline__ V3d position(uint32_t q) const { return {xyz[3 * q], xyz[3 * q + 1], xyz[3 * q + 2]}; }
   __device__ __forceinline__ const PCV_GLOBAL uint8_t* color(uint32_t q) const { return rgb + 3 * q; }
+};
+// An S2 chunk whose bins come from a column of the cloud: a wave's 64 candidates are consecutive elements of one cell's
+// column, one contiguous run of 64, 128, 256 or 512 bytes a step. The data type is the cloud's, so the switch is
+// wave-uniform (a scalar branch): one instance for all ten types, not one per type.
+struct XrayS2ColumnSource : XrayS2Source {
+  static constexpr bool kBinColumn = true;
+  const PCV_GLOBAL uint8_t* col;  // the chunk's first element
+  int32_t data_type;
+  template <typename T>
+  __device__ __forceinline__ int64_t bin_as(uint32_t q, double size) const {
+    return s2attr::bin<T>(((const PCV_GLOBAL T*)col)[q], size);
+  }
+  __device__ __forceinline__ int64_t bin(uint32_t q, double size) const {
+    switch (data_type) {
+      case s2attr::U8: return bin_as<uint8_t>(q, size);
+      case s2attr::U16: return bin_as<uint16_t>(q, size);
+      case s2attr::U32: return bin_as<uint32_t>(q, size);
+      case s2attr::U64: return bin_as<uint64_t>(q, size);
+      case s2attr::I8: return bin_as<int8_t>(q, size);
+      case s2attr::I16: return bin_as<int16_t>(q, size);
+      case s2attr::I32: return bin_as<int32_t>(q, size);
+      case s2attr::I64: return bin_as<int64_t>(q, size);
+      case s2attr::F32: return bin_as<float>(q, size);
+      default: return bin_as<double>(q, size);  // F64: the host admits scalar types only
+    }
+  }
 };
 template <class Source>
 __device__ __forceinline__ XrayPoint xray_point(const XrayBinArgs& a, const Source& src, const XrayTileDev& t, uint32_t bbase, uint32_t q,
@@ -242,8 +274,10 @@ __device__ __forceinline__ XrayPoint xray_point(const XrayBinArgs& a, const Sour
       o.neg = true;
       return o;
     }
-    if (a.binned) o.bin = rust_i64((double)in / a.bin_size);  // BinnedColoringStrategy::bins (:138-157)
+    if constexpr (!Source::kBinColumn)
+      if (a.binned) o.bin = rust_i64((double)in / a.bin_size);  // BinnedColoringStrategy::bins (:138-157)
   }
+  if constexpr (Source::kBinColumn) o.bin = src.bin(q, a.bin_size);  // the same, from the cloud's column
   V3d p = src.position(q);
   if (a.has_iso) p = v_add(quat_rotate(a.iso + 3, p), V3d{a.iso[0], a.iso[1], a.iso[2]});
   const double W = (double)a.W;
@@ -306,8 +340,9 @@ __device__ __forceinline__ void xray_bin_chunk(const XrayBinArgs& a, const Sourc
 // a wave per chunk of the group, whose chunks are those of all its clouds one after another. A wave's chunk index only
 // grows, so its cloud is found by a wave-uniform search forward from the last one. S2: the chunks are those of S2 queries
 // (XrayTreeChunks::desc is a PcvS2Chunk list, keep the u32 flags, xyz the cloud's f64 positions); past the chunk's
-// descriptor the instances of both kinds run xray_bin_chunk.
-template <bool SCATTER, bool S2>
+// descriptor the instances of both kinds run xray_bin_chunk. COLUMN (S2 scatter only: the count pass needs no bin): the bin
+// of a record is read from the cloud's column, a.columns[k], instead of the intensity.
+template <bool SCATTER, bool S2, bool COLUMN = false>
 __global__ __launch_bounds__(256) void xray_bin_kernel(XrayBinArgs a, uint32_t* __restrict__ counts, const uint64_t* __restrict__ offsets,
                                                        uint64_t* __restrict__ rec, double* __restrict__ recz,
                                                        int64_t* __restrict__ recb) {
@@ -332,9 +367,16 @@ __global__ __launch_bounds__(256) void xray_bin_kernel(XrayBinArgs a, uint32_t* 
       if (created < 0) continue;  // wave-uniform: no cloud's query kept anything for this tile
       const XrayTileDev t = a.tiles[created];
       const uint32_t bbase = ((uint32_t)created - a.created0) * a.nblocks;
-      const XrayS2Source src{(const PCV_GLOBAL double*)tr.xyz + 3 * c.src, tr.rgb + 3 * c.src,
-                             tr.inten ? (const PCV_GLOBAL float*)tr.inten + c.src : nullptr, (const PCV_GLOBAL uint32_t*)tr.keep + c.first};
-      xray_bin_chunk<SCATTER>(a, src, c.count, created, t, bbase, lane, counts, offsets, rec, recz, recb);
+      const XrayS2Source s2src{(const PCV_GLOBAL double*)tr.xyz + 3 * c.src, tr.rgb + 3 * c.src,
+                               tr.inten ? (const PCV_GLOBAL float*)tr.inten + c.src : nullptr, (const PCV_GLOBAL uint32_t*)tr.keep + c.first};
+      if constexpr (COLUMN) {
+        static_assert(SCATTER && S2, "a bin column is read by the S2 scatter pass only");
+        const XrayBinColumn bc = a.columns[k];
+        XrayS2ColumnSource src{s2src, bc.col + c.src * (uint64_t)s2attr::element_size(bc.data_type), bc.data_type};
+        xray_bin_chunk<SCATTER>(a, src, c.count, created, t, bbase, lane, counts, offsets, rec, recz, recb);
+      } else {
+        xray_bin_chunk<SCATTER>(a, s2src, c.count, created, t, bbase, lane, counts, offsets, rec, recz, recb);
+      }
     } else {
       const ChunkDesc d = tr.desc[tr.c0 + (gi - tr.first)];
       const int32_t created = a.created_of_shape[d.enc >> 8];
@@ -1025,10 +1067,18 @@ XrayAccum xray_accum_of(uint32_t strategy, bool binned) {
 }
 
 // the clouds of a run, all of one kind (PointClouds::Octrees or ::S2Cells, point_cloud_client/src/lib.rs:107-132)
+// what pcv_xray_run_s2_ex reads of its clouds beyond colour and intensity, after its checks
+struct XrayS2Attrs {
+  bool has_interval = false;  // an interval on intensity: params->interval, or the list's entry on "intensity"
+  double interval[2] = {0.0, 0.0};
+  std::vector<std::vector<PcvS2ExtraFilter>> filters;  // per cloud: the list's entries on its extras, every location each
+  std::vector<int> bin_extra;                          // per cloud: the extra binned on; empty: intensity, or no binning read
+};
 struct XrayClouds {
   pcv_octree* const* trees = nullptr;
   pcv_s2_cloud* const* s2 = nullptr;
   uint32_t K = 0;
+  const XrayS2Attrs* attrs = nullptr;  // pcv_xray_run_s2_ex only
 };
 // what the planning reads of one cloud's query over the tile shapes, an octree batch or an S2 query alike: shape -> segments
 // -> kept points and chunks, and the pointers the raster passes read the chunks through
@@ -1037,6 +1087,7 @@ struct XraySource {
   const uint64_t* seg_kept;     // [segments + 1] kept points before each segment
   const uint64_t* seg_chunk;    // [segments + 1] first chunk of each segment
   XrayTreeChunks chunks;        // desc, keep, xyz, rgb, inten (c0 and first are per tile group)
+  XrayBinColumn column;         // S2, binning on a column: the cloud's
   uint64_t kept(uint64_t s) const { return seg_kept[shape_first[s + 1]] - seg_kept[shape_first[s]]; }
   uint64_t chunk_of(uint64_t s) const { return seg_chunk[shape_first[s]]; }
 };
@@ -1055,7 +1106,9 @@ struct XrayBatches {
 // step 1: one shape per leaf tile (xray_from_points :470-476) and the K queries, pcv_query_batch_run or pcv_s2_query_run
 int xray_query_tiles(pcv_ctx* ctx, const XrayClouds& clouds, const pcv_xray_params* p, const LeafGeometry& g, bool reads_intensity,
                      XrayBatches* batches) {
-  const bool filter = p->interval_attribute != nullptr;
+  const XrayS2Attrs* at = clouds.attrs;
+  const bool filter = at ? at->has_interval : p->interval_attribute != nullptr;
+  const double* interval = at ? at->interval : p->interval;
   const uint32_t S = (uint32_t)g.index.size();
   std::vector<pcv_shape> shapes(S);
   for (uint32_t i = 0; i < S; ++i) {
@@ -1076,8 +1129,8 @@ int xray_query_tiles(pcv_ctx* ctx, const XrayClouds& clouds, const pcv_xray_para
   if (filter) {
     ivals.resize(2 * (size_t)S);
     for (uint32_t i = 0; i < S; ++i) {
-      ivals[2 * (size_t)i] = p->interval[0];
-      ivals[2 * (size_t)i + 1] = p->interval[1];
+      ivals[2 * (size_t)i] = interval[0];
+      ivals[2 * (size_t)i + 1] = interval[1];
     }
   }
   pcv_shapes* sh = nullptr;
@@ -1089,7 +1142,10 @@ int xray_query_tiles(pcv_ctx* ctx, const XrayClouds& clouds, const pcv_xray_para
     if (clouds.s2) {
       pcv_s2_cloud* c = clouds.s2[t];
       pcv_s2_query* q = nullptr;
-      if ((rc = pcv_s2_query_run(c, sh, 0, nullptr, nullptr, filter ? ivals.data() : nullptr, nullptr, &q))) break;
+      // the list's filters on extras: the same machinery, one launch per filtered column, on every location
+      if (at && !at->filters[t].empty()) rc = pcv_s2_query_run_every(c, sh, filter ? ivals.data() : nullptr, at->filters[t], &q);
+      else rc = pcv_s2_query_run(c, sh, 0, nullptr, nullptr, filter ? ivals.data() : nullptr, nullptr, &q);
+      if (rc) break;
       batches->s2.push_back(q);
       e.shape_first = q->location_first.data();
       e.seg_kept = q->seg_offset.data();
@@ -1099,6 +1155,10 @@ int xray_query_tiles(pcv_ctx* ctx, const XrayClouds& clouds, const pcv_xray_para
       e.chunks.xyz = (decltype(e.chunks.xyz))c->d_xyz;
       e.chunks.rgb = (decltype(e.chunks.rgb))c->d_rgb;
       e.chunks.inten = reads_intensity ? (decltype(e.chunks.inten))c->d_int : nullptr;
+      if (at && !at->bin_extra.empty()) {
+        const PcvS2Extra& x = c->extras[(size_t)at->bin_extra[t]];
+        e.column = XrayBinColumn{(decltype(e.column.col))x.d, x.data_type, 0u};
+      }
     } else {
       pcv_octree* tree = clouds.trees[t];
       pcv_query_batch* b = nullptr;
@@ -1126,6 +1186,7 @@ struct XrayPlan {
   std::vector<uint64_t> group_first;  // created tiles [group_first[g], group_first[g + 1]) are group g
   uint64_t max_pts = 0, max_tiles = 0;
   std::vector<XrayTreeChunks> trees;
+  std::vector<XrayBinColumn> columns;  // parallel to `trees`
   std::vector<size_t> tree_first;  // group g's entries of `trees`: [tree_first[g], tree_first[g + 1])
   std::vector<uint64_t> group_chunks;
 };
@@ -1161,6 +1222,7 @@ int xray_plan_tiles(pcv_ctx* ctx, const pcv_xray_params* p, const pcv_xray_color
       e.c0 = c0;
       e.first = n;
       pl->trees.push_back(e);
+      pl->columns.push_back(b.column);
       n += c1 - c0;
     }
     pl->tree_first.push_back(pl->trees.size());
@@ -1176,6 +1238,7 @@ struct XrayTables {
   int32_t* cos = nullptr;
   XrayTileDev* tiles = nullptr;
   XrayTreeChunks* trees = nullptr;
+  XrayBinColumn* columns = nullptr;  // only where the bins come from a column
   uint8_t* table = nullptr;
   unsigned long long *drawn = nullptr, *neg = nullptr;
   uint32_t* counts = nullptr;
@@ -1185,8 +1248,8 @@ struct XrayTables {
   std::vector<XrayTileDev> h_tiles;  // what the uploads read: alive until the raster passes have synchronised
   uint8_t h_table[kZWords * 32 + 1];
 };
-int xray_upload_tables(pcv_ctx* ctx, const pcv_xray_params* p, bool binned, const pcv_xray* x, const XrayPlan& pl, uint32_t nblocks,
-                              XrayTables* t) {
+int xray_upload_tables(pcv_ctx* ctx, const pcv_xray_params* p, bool binned, bool bin_column, const pcv_xray* x, const XrayPlan& pl,
+                       uint32_t nblocks, XrayTables* t) {
   const uint64_t nc = x->created.size(), S = pl.created_of_shape.size();
   const uint64_t max_buckets = pl.max_tiles * nblocks, max_pts = std::max<uint64_t>(pl.max_pts, 1);
   PcvScratch& sc = t->sc;
@@ -1197,6 +1260,7 @@ int xray_upload_tables(pcv_ctx* ctx, const pcv_xray_params* p, bool binned, cons
     return rc;
   if (p->strategy == PCV_XRAY_HEIGHT_STDDEV && (rc = sc.get(&t->recz, max_pts))) return rc;
   if (binned && (rc = sc.get(&t->recb, max_pts))) return rc;
+  if (bin_column && (rc = sc.get(&t->columns, std::max<size_t>(pl.columns.size(), 1)))) return rc;
   if (p->strategy == PCV_XRAY_COLORED_WITH_INTENSITY && (rc = sc.get(&t->neg, nc))) return rc;
   t->h_tiles.resize(nc);
   for (uint64_t c = 0; c < nc; ++c) {
@@ -1212,6 +1276,8 @@ int xray_upload_tables(pcv_ctx* ctx, const pcv_xray_params* p, bool binned, cons
   PCV_HIP_CHECK(ctx, hipMemcpyAsync(t->tiles, t->h_tiles.data(), sizeof(XrayTileDev) * nc, hipMemcpyHostToDevice, ctx->stream));
   if (!pl.trees.empty())
     PCV_HIP_CHECK(ctx, hipMemcpyAsync(t->trees, pl.trees.data(), sizeof(XrayTreeChunks) * pl.trees.size(), hipMemcpyHostToDevice, ctx->stream));
+  if (t->columns && !pl.columns.empty())
+    PCV_HIP_CHECK(ctx, hipMemcpyAsync(t->columns, pl.columns.data(), sizeof(XrayBinColumn) * pl.columns.size(), hipMemcpyHostToDevice, ctx->stream));
   PCV_HIP_CHECK(ctx, hipMemcpyAsync(t->table, t->h_table, sizeof(t->h_table), hipMemcpyHostToDevice, ctx->stream));
   PCV_HIP_CHECK(ctx, hipMemsetAsync(t->drawn, 0, 8 * nc, ctx->stream));
   if (t->neg) PCV_HIP_CHECK(ctx, hipMemsetAsync(t->neg, 0, 8 * nc, ctx->stream));
@@ -1270,6 +1336,7 @@ int xray_raster_groups(pcv_ctx* ctx, const pcv_xray_params* p, const pcv_xray_co
   for (size_t gi = 0; gi + 1 < pl.group_first.size(); ++gi) {
     const uint64_t f = pl.group_first[gi], l = pl.group_first[gi + 1];  // created tiles [f, l)
     ba.trees = t.trees + pl.tree_first[gi];
+    ba.columns = t.columns ? t.columns + pl.tree_first[gi] : nullptr;
     ba.ntrees = (uint32_t)(pl.tree_first[gi + 1] - pl.tree_first[gi]);
     ba.nchunks = pl.group_chunks[gi];
     ba.created0 = (uint32_t)f;
@@ -1292,8 +1359,8 @@ int xray_raster_groups(pcv_ctx* ctx, const pcv_xray_params* p, const pcv_xray_co
       PcvProf prof(ctx, PCV_K_XRAY_SCATTER);
       XrayBinArgs bs = ba;
       bs.negative = nullptr;  // counted once, in the count pass
-      hipLaunchKernelGGL((s2 ? xray_bin_kernel<true, true> : xray_bin_kernel<true, false>), dim3(grid), dim3(256), 0, ctx->stream, bs,
-                         t.counts, (const uint64_t*)t.off, t.rec, t.recz, t.recb);
+      hipLaunchKernelGGL((t.columns ? xray_bin_kernel<true, true, true> : s2 ? xray_bin_kernel<true, true> : xray_bin_kernel<true, false>),
+                         dim3(grid), dim3(256), 0, ctx->stream, bs, t.counts, (const uint64_t*)t.off, t.rec, t.recz, t.recb);
     }
     PCV_HIP_CHECK(ctx, hipGetLastError());
     aa.nbuckets = (uint32_t)nb;
@@ -1311,7 +1378,9 @@ int xray_raster_groups(pcv_ctx* ctx, const pcv_xray_params* p, const pcv_xray_co
 
 int xray_run(pcv_ctx* ctx, const XrayClouds& clouds, const pcv_xray_params* p, const pcv_xray_coloring* col, pcv_xray* x) {
   const bool binned = coloring_binned(p, col);
-  const bool sorted = binned || p->strategy == PCV_XRAY_COLORED_WITH_INTENSITY;
+  // the bins of an S2 run may come from a column of the clouds instead of the intensity (pcv_xray_run_s2_ex)
+  const bool bin_column = binned && clouds.attrs && !clouds.attrs->bin_extra.empty();
+  const bool reads_intensity = p->strategy == PCV_XRAY_COLORED_WITH_INTENSITY || (binned && !bin_column);
   char err[256] = {0};
   double bmin[3], bmax[3];
   if (clouds.s2) union_box(clouds.s2, clouds.K, bmin, bmax);
@@ -1325,7 +1394,7 @@ int xray_run(pcv_ctx* ctx, const XrayClouds& clouds, const pcv_xray_params* p, c
   x->root_index = p->root_index;
   x->bg = p->background == PCV_XRAY_BG_TRANSPARENT ? 0x00ffffffu : 0xffffffffu;  // TRANSPARENT / WHITE .to_u8()
   XrayBatches batches;
-  if ((rc = xray_query_tiles(ctx, clouds, p, x->geo, sorted, &batches))) return rc;
+  if ((rc = xray_query_tiles(ctx, clouds, p, x->geo, reads_intensity, &batches))) return rc;
   XrayPlan pl;
   xray_created_tiles(batches.src, (uint32_t)x->geo.index.size(), x, &pl);
   const uint64_t nc = x->created.size();
@@ -1334,7 +1403,7 @@ int xray_run(pcv_ctx* ctx, const XrayClouds& clouds, const pcv_xray_params* p, c
   if ((rc = xray_plan_tiles(ctx, p, col, batches.src, x, &pl))) return rc;
   if ((rc = ctx->dev_alloc((void**)&x->d_images, 4ull * W * W * nc))) return rc;
   XrayTables t(ctx);
-  if ((rc = xray_upload_tables(ctx, p, binned, x, pl, nbx * nbx, &t))) return rc;
+  if ((rc = xray_upload_tables(ctx, p, binned, bin_column, x, pl, nbx * nbx, &t))) return rc;
   return xray_raster_groups(ctx, p, col, binned, clouds.s2 != nullptr, x, pl, nbx, t);
 }
 
@@ -1458,6 +1527,159 @@ extern "C" int pcv_xray_run_ex(pcv_ctx* ctx, pcv_octree* const* trees, uint32_t 
 extern "C" int pcv_xray_run_s2(pcv_ctx* ctx, pcv_s2_cloud* const* clouds, uint32_t num_clouds, const pcv_xray_params* p,
                                const pcv_xray_coloring* coloring, pcv_xray** out) {
   return xray_run_checked(ctx, clouds, num_clouds, "S2 cloud", p, coloring, coloring != nullptr, out);
+}
+
+// ---- pcv_xray_run_s2_ex: filters (xray/src/build_quadtree.rs:94-101, FilteredIterator over filter_intervals) and binning
+// (:102-107, BinnedColoringStrategy::bins) on any scalar attribute of the clouds ---------------------------------------------
+namespace {
+
+// the attributes of one cloud as the checks read them: its extras (name, data type) and whether it has intensity
+struct XrayCloudAttrs {
+  const char* const* names;
+  const int32_t* data_types;
+  uint32_t count;
+  bool has_intensity;
+  int find(const char* name) const {
+    for (uint32_t k = 0; k < count; ++k)
+      if (names[k] && std::strcmp(names[k], name) == 0) return (int)k;
+    return -1;
+  }
+};
+
+bool binning_on_column(const pcv_xray_coloring* col) {
+  return col && col->binning_attribute && std::strcmp(col->binning_attribute, "intensity") != 0;
+}
+
+// every check of pcv_xray_run_s2_ex that needs no device; *out (nullable): per cloud the extras the run reads
+int check_attrs(const pcv_xray_params* p, const pcv_xray_coloring* col, const pcv_xray_filter* filters, uint32_t num_filters,
+                const std::vector<XrayCloudAttrs>& clouds, XrayS2Attrs* out, char* err, uint64_t errcap) {
+  if (!p) return fail_msg(err, errcap, "null argument");
+  if (clouds.empty()) return fail_msg(err, errcap, "xray: No locations specified for point cloud client.");
+  // the checks of pcv_xray_run_s2, which knows no binning name but intensity: the name is checked against the clouds below
+  pcv_xray_coloring known{};
+  if (col) {
+    known = *col;
+    if (binning_on_column(col)) known.binning_attribute = nullptr;
+  }
+  if (int rc = pcv_xray_check_params_ex(p, col ? &known : nullptr, 1, err, errcap)) return rc;
+  if (col && col->binning_attribute && col->binning_attribute[0] == '\0') return fail_msg(err, errcap, "xray: the binning attribute has an empty name");
+  if (num_filters && !filters) return fail_msg(err, errcap, "null argument");
+  for (uint32_t k = 0; k < num_filters; ++k) {
+    if (!filters[k].attribute) return fail_msg(err, errcap, "xray: filter " + std::to_string(k) + " has no attribute name");
+    const std::string name(filters[k].attribute);
+    bool twice = p->interval_attribute && name == "intensity";  // interval_attribute is a filter on intensity
+    for (uint32_t j = 0; j < k; ++j) twice = twice || name == filters[j].attribute;
+    if (twice) return fail_msg(err, errcap, "xray: two filters on attribute '" + name + "'");
+  }
+  const bool binned = coloring_binned(p, col), column = binning_on_column(col);
+  if (out) {
+    *out = XrayS2Attrs{};
+    out->filters.resize(clouds.size());
+    if (p->interval_attribute) out->has_interval = true, out->interval[0] = p->interval[0], out->interval[1] = p->interval[1];
+  }
+  for (size_t t = 0; t < clouds.size(); ++t) {
+    const XrayCloudAttrs& c = clouds[t];
+    const std::string which = "S2 cloud " + std::to_string(t);
+    if (p->interval_attribute && !c.has_intensity) return fail_msg(err, errcap, "xray: " + which + " has no intensity attribute to filter on");
+    if (coloring_needs_intensity(p, col) && !(column && p->strategy == PCV_XRAY_COLORED) && !c.has_intensity)
+      return fail_msg(err, errcap, "xray: " + which + " has no intensity attribute to color or bin by");
+    for (uint32_t k = 0; k < num_filters; ++k) {
+      const pcv_xray_filter& f = filters[k];
+      const std::string name(f.attribute);
+      if (name == "intensity") {
+        if (!c.has_intensity) return fail_msg(err, errcap, "xray: " + which + " has no intensity attribute to filter on");
+        if (out) out->has_interval = true, out->interval[0] = f.lo, out->interval[1] = f.hi;
+        continue;
+      }
+      const int e = name == "color" ? -1 : c.find(f.attribute);
+      if (name == "color" || (e >= 0 && !s2attr::is_scalar(c.data_types[e])))
+        return fail_msg(err, errcap, "xray: a filter takes a scalar attribute; '" + name + "' of " + which + " is a vector attribute");
+      if (e < 0) return fail_msg(err, errcap, "xray: Data type for attribute '" + name + "' not found. (" + which + ")");  // lib.rs:94
+      if (out) out->filters[t].push_back(PcvS2ExtraFilter{kPcvS2EveryLocation, e, f.lo, f.hi});
+    }
+    if (column) {  // the name is checked whatever the strategy; the column is read by colored and colored_with_intensity
+      const std::string name(col->binning_attribute);
+      const int e = name == "color" ? -1 : c.find(col->binning_attribute);
+      if (name == "color" || (e >= 0 && !s2attr::is_scalar(c.data_types[e])))
+        return fail_msg(err, errcap, "xray: binning takes a scalar attribute; '" + name + "' of " + which + " is a vector attribute");
+      if (e < 0)  // generation.rs:146
+        return fail_msg(err, errcap, "xray: Binning attribute needs to be available in points batch. (attribute '" + name + "', " + which + ")");
+      if (out && binned) out->bin_extra.push_back(e);
+    }
+  }
+  return PCV_OK;
+}
+
+}  // namespace
+
+extern "C" int pcv_xray_check_attrs_host(const pcv_xray_params* p, const pcv_xray_coloring* col, const pcv_xray_filter* filters,
+                                         uint32_t num_filters, uint32_t num_clouds, const uint32_t* extras_first, const char* const* names,
+                                         const int32_t* data_types, const uint8_t* has_intensity, char* err, uint64_t errcap) {
+  if (num_clouds && (!extras_first || !has_intensity)) return fail_msg(err, errcap, "null argument");
+  if (num_clouds && extras_first[num_clouds] && (!names || !data_types)) return fail_msg(err, errcap, "null argument");
+  std::vector<XrayCloudAttrs> clouds(num_clouds);
+  for (uint32_t t = 0; t < num_clouds; ++t) {
+    if (extras_first[t + 1] < extras_first[t]) return fail_msg(err, errcap, "xray: extras_first must not descend");
+    clouds[t] = XrayCloudAttrs{names ? names + extras_first[t] : nullptr, data_types ? data_types + extras_first[t] : nullptr,
+                               extras_first[t + 1] - extras_first[t], has_intensity[t] != 0};
+  }
+  return check_attrs(p, col, filters, num_filters, clouds, nullptr, err, errcap);
+}
+
+extern "C" int pcv_xray_run_s2_ex(pcv_ctx* ctx, pcv_s2_cloud* const* clouds, uint32_t num_clouds, const pcv_xray_params* p,
+                                  const pcv_xray_coloring* coloring, const pcv_xray_filter* filters, uint32_t num_filters, pcv_xray** out) {
+  if (num_filters == 0 && !binning_on_column(coloring)) return pcv_xray_run_s2(ctx, clouds, num_clouds, p, coloring, out);
+  if (!ctx) return PCV_E_INVALID;
+  if (!p || !out) return ctx->fail(PCV_E_INVALID, "null argument");
+  *out = nullptr;
+  if (num_clouds == 0) return ctx->fail(PCV_E_INVALID, "xray: No locations specified for point cloud client.");
+  if (!clouds) return ctx->fail(PCV_E_INVALID, "null argument");
+  if (num_clouds > PCV_XRAY_MAX_TREES)
+    return ctx->fail(PCV_E_INVALID, "xray: " + std::to_string(num_clouds) + " S2 clouds, more than PCV_XRAY_MAX_TREES (" +
+                                        std::to_string(PCV_XRAY_MAX_TREES) + ")");
+  std::vector<XrayCloudAttrs> attrs(num_clouds);
+  std::vector<std::vector<const char*>> names(num_clouds);
+  std::vector<std::vector<int32_t>> types(num_clouds);
+  for (uint32_t t = 0; t < num_clouds; ++t) {
+    const std::string which = "xray: S2 cloud " + std::to_string(t);
+    if (!clouds[t]) return ctx->fail(PCV_E_INVALID, which + " is null");
+    if (!clouds[t]->ctx) return ctx->fail(PCV_E_INVALID, which + " was opened without a context and has no device");
+    if (clouds[t]->ctx != ctx) return ctx->fail(PCV_E_INVALID, which + " belongs to another context");
+    for (const PcvS2Extra& e : clouds[t]->extras) names[t].push_back(e.name.c_str()), types[t].push_back(e.data_type);
+    attrs[t] = XrayCloudAttrs{names[t].data(), types[t].data(), (uint32_t)names[t].size(), clouds[t]->has_intensity};
+  }
+  char err[320] = {0};
+  XrayS2Attrs reads;
+  if (int rc = check_attrs(p, coloring, filters, num_filters, attrs, &reads, err, sizeof(err))) return ctx->fail(rc, err);
+  // exactly the columns the run reads, resident before any raster work: a cloud opened from a directory reads an extra's
+  // files on first use, and a damaged one is PCV_E_IO naming the file
+  for (uint32_t t = 0; t < num_clouds; ++t) {
+    for (const PcvS2ExtraFilter& f : reads.filters[t])
+      if (int rc = pcv_s2_extra_resident(clouds[t], (size_t)f.extra)) return rc;
+    if (!reads.bin_extra.empty())
+      if (int rc = pcv_s2_extra_resident(clouds[t], (size_t)reads.bin_extra[t])) return rc;
+  }
+  XrayClouds cl;
+  cl.s2 = clouds;
+  cl.K = num_clouds;
+  cl.attrs = &reads;
+  return xray_new(ctx, cl, p, coloring, out);
+}
+
+extern "C" int pcv_xray_bins_host(int32_t data_type, uint64_t n, const void* data, double bin_size, int64_t* out) {
+  if (s2attr::element_size(data_type) == 0) return pcv_host_fail(PCV_E_INVALID, "Attribute data type invalid");
+  if (!s2attr::is_scalar(data_type)) return pcv_host_fail(PCV_E_INVALID, "binning takes a scalar attribute; a vector attribute has no bins");
+  if (n && (!data || !out)) return pcv_host_fail(PCV_E_INVALID, "null argument");
+  s2attr::dispatch_scalar(data_type, [&](auto t) {
+    using T = decltype(t);
+    const uint8_t* src = (const uint8_t*)data;
+    for (uint64_t i = 0; i < n; ++i) {
+      T v;
+      std::memcpy(&v, src + i * sizeof(T), sizeof(T));  // (the caller's buffer may stand at any byte)
+      out[i] = s2attr::bin<T>(v, bin_size);
+    }
+  });
+  return PCV_OK;
 }
 
 extern "C" int pcv_xray_negative(const pcv_xray* x, uint64_t* negative) {

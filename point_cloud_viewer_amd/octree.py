@@ -342,11 +342,14 @@ class Context:
 
     def xray_tiles(self, trees, tile_size_px=256, pixel_size_m=None, strategy="xray", query_from_global=None, intensity_interval=None,
                    background="white", root_node_id="r", max_workspace_bytes=None, min_intensity=0.0, max_intensity=1.0,
-                   binning=None):
+                   binning=None, filter_intervals=None):
         """OctreeResult.xray_tiles (same keywords) over several octrees of this context, as build_xray_quadtree with several
         point_cloud_locations (pcv_xray_run_many, or pcv_xray_run_ex with colored_with_intensity or binning): the union of
         their bounding boxes, every tile's points from all of them. `trees` may instead be a list of S2Cloud
-        (pcv_xray_run_s2); a list that mixes the two kinds raises ValueError. Returns an XrayTiles."""
+        (pcv_xray_run_s2_ex); a list that mixes the two kinds raises ValueError. With S2 clouds, binning may name any scalar
+        attribute of the clouds, and filter_intervals is None or a dict {attribute: (lo, hi)} of closed intervals on scalar
+        attributes (--filter-interval), ANDed on every tile; an octree carries only color and intensity. Returns an
+        XrayTiles."""
         trees = list(trees)
         if not trees:
             raise ValueError("xray_tiles: no octrees given")
@@ -355,7 +358,10 @@ class Context:
             raise ValueError("xray_tiles: a list of octrees or a list of S2 cell clouds, not a mix of both")
         if all(s2):
             return self._xray_tiles_s2(trees, tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background,
-                                       root_node_id, max_workspace_bytes, min_intensity, max_intensity, binning)
+                                       root_node_id, max_workspace_bytes, min_intensity, max_intensity, binning, filter_intervals)
+        if filter_intervals:
+            raise ValueError("xray_tiles: filter_intervals take S2 cell clouds; an octree carries only color and intensity "
+                             "(intensity_interval)")
         p = xray_params(tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background, root_node_id,
                         max_workspace_bytes)
         col = xray_coloring(strategy, min_intensity, max_intensity, binning)
@@ -368,7 +374,7 @@ class Context:
         return XrayTiles(self, h, int(tile_size_px))
 
     def _xray_tiles_s2(self, clouds, tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background,
-                       root_node_id, max_workspace_bytes, min_intensity, max_intensity, binning):
+                       root_node_id, max_workspace_bytes, min_intensity, max_intensity, binning, filter_intervals=None):
         for c in clouds:
             c._alive()
         p = xray_params(tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background, root_node_id,
@@ -376,17 +382,18 @@ class Context:
         col = xray_coloring(strategy, min_intensity, max_intensity, binning)
         arr = (C.c_void_p * len(clouds))(*[c.handle for c in clouds])
         h = C.c_void_p()
-        self._check(self.lib.pcv_xray_run_s2(self.handle, arr, len(clouds), C.byref(p), C.byref(col) if col is not None else None,
-                                             C.byref(h)))
+        filters, _names = xray_filters(filter_intervals)
+        self._check(self.lib.pcv_xray_run_s2_ex(self.handle, arr, len(clouds), C.byref(p), C.byref(col) if col is not None else None,
+                                                filters, len(_names), C.byref(h)))
         return XrayTiles(self, h, int(tile_size_px))
 
     def xray_quadtree(self, trees, tile_size_px=256, pixel_size_m=None, strategy="xray", query_from_global=None,
                       intensity_interval=None, background="white", root_node_id="r", max_workspace_bytes=None, min_intensity=0.0,
-                      max_intensity=1.0, binning=None, output_directory=None, png="stored"):
+                      max_intensity=1.0, binning=None, output_directory=None, png="stored", filter_intervals=None):
         """xray_tiles over several octrees, or several S2 cell clouds (same arguments), with every level above the leaves
         built on the device; with output_directory the quadtree is also written there (XrayTiles.write, PNGs as `png` says)."""
         xt = self.xray_tiles(trees, tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background,
-                             root_node_id, max_workspace_bytes, min_intensity, max_intensity, binning)
+                             root_node_id, max_workspace_bytes, min_intensity, max_intensity, binning, filter_intervals)
         xt.build_parents()
         if output_directory is not None:
             xt.write(output_directory, png=png)
@@ -1439,6 +1446,68 @@ def xray_coloring(strategy="xray", min_intensity=0.0, max_intensity=1.0, binning
     return col
 
 
+def xray_filters(filter_intervals):
+    """(pcv_xray_filter array or None, the encoded names it points to) of a dict {attribute: (lo, hi)} or None."""
+    if not filter_intervals:
+        return None, []
+    items = list(filter_intervals.items())
+    arr, names = (L.XrayFilter * len(items))(), []
+    for k, (name, iv) in enumerate(items):
+        if not isinstance(name, (str, bytes)):
+            raise ValueError(f"filter_intervals: an attribute name must be a str, not {name!r}")
+        if isinstance(iv, (str, bytes)) or len(iv) != 2:
+            raise ValueError(f"filter_intervals[{name!r}] must be (lo, hi), not {iv!r}")
+        names.append(name if isinstance(name, bytes) else name.encode())
+        arr[k].attribute, arr[k].lo, arr[k].hi = names[-1], float(iv[0]), float(iv[1])
+    return arr, names
+
+
+def xray_bins(data, bin_size):
+    """pcv_xray_bins_host (host only): the bins of xray's --binning for a numpy array of one of the ten scalar attribute
+    types — `(value as f64 / bin_size) as i64` as Rust computes it, by the function the device compiles — as int64."""
+    data = np.asarray(data)
+    codes = {np.dtype(t): c for c, t, comps in L.ATTR_TYPES.values() if comps == 1}
+    if data.dtype not in codes:
+        raise L.PcvError(L.PCV_E_INVALID, f"xray_bins: dtype {data.dtype} is no scalar attribute type")
+    flat = np.ascontiguousarray(data).ravel()
+    out = np.zeros(flat.size, dtype=np.int64)
+    _host_check(L.load_library().pcv_xray_bins_host(codes[data.dtype], flat.size, flat.ctypes.data, float(bin_size), out.ctypes.data),
+                "pcv_xray_bins_host")
+    return out.reshape(data.shape)
+
+
+def xray_check_attrs(params, clouds, coloring=None, filter_intervals=None):
+    """pcv_xray_check_attrs_host (host only): raises PcvError for what the S2 forms of xray_tiles would refuse before any
+    device work. clouds: one (attributes, has_intensity) per cloud, attributes a dict name -> type string of
+    S2Cloud.attributes (or a proto enum value). filter_intervals: None, a dict {name: (lo, hi)}, or a list of
+    (name, lo, hi) whose name may be None or repeat (what the C entry can be handed)."""
+    clouds = list(clouds)
+    first, names, types = [0], [], []
+    for attrs, _ in clouds:
+        for name, typ in attrs.items():
+            names.append(name if isinstance(name, bytes) else name.encode())
+            types.append(typ if isinstance(typ, int) else L.ATTR_TYPES.get(str(typ).lower(), (0,))[0])
+        first.append(len(names))
+    first = np.asarray(first, dtype=np.uint32)
+    types = np.asarray(types, dtype=np.int32)
+    has = np.asarray([1 if h else 0 for _, h in clouds], dtype=np.uint8)
+    name_arr = (C.c_char_p * max(1, len(names)))(*names)
+    if isinstance(filter_intervals, dict) or filter_intervals is None:
+        filters, held = xray_filters(filter_intervals)
+        nf = len(held)
+    else:
+        items = list(filter_intervals)
+        filters, held, nf = (L.XrayFilter * max(1, len(items)))(), [], len(items)
+        for k, (name, lo, hi) in enumerate(items):
+            held.append(None if name is None else (name if isinstance(name, bytes) else name.encode()))
+            filters[k].attribute, filters[k].lo, filters[k].hi = held[-1], float(lo), float(hi)
+    err = C.create_string_buffer(512)
+    rc = L.load_library().pcv_xray_check_attrs_host(C.byref(params), C.byref(coloring) if coloring is not None else None, filters, nf,
+                                                    len(clouds), first.ctypes.data, name_arr, types.ctypes.data, has.ctypes.data, err, 512)
+    if rc != 0:
+        raise L.PcvError(rc, err.value.decode())
+
+
 def xray_check_params(params, tree_has_intensity=True, coloring=None):
     """pcv_xray_check_params (pcv_xray_check_params_ex with a coloring; host only): raises PcvError for what pcv_xray_run
     (pcv_xray_run_ex) would refuse before any device work."""
@@ -2339,22 +2408,24 @@ class S2Cloud:
 
     def xray_tiles(self, tile_size_px=256, pixel_size_m=None, strategy="xray", query_from_global=None, intensity_interval=None,
                    background="white", root_node_id="r", max_workspace_bytes=None, min_intensity=0.0, max_intensity=1.0,
-                   binning=None):
-        """OctreeResult.xray_tiles (same keywords) over this S2 cell cloud (pcv_xray_run_s2): every leaf tile's points are
+                   binning=None, filter_intervals=None):
+        """OctreeResult.xray_tiles (same keywords) over this S2 cell cloud (pcv_xray_run_s2_ex): every leaf tile's points are
         those of the cells that cells_in_location lists for the tile's shape, filtered as query_batch filters them.
+        binning: None or (name, bin size) on any scalar attribute of the cloud, `intensity` or an extra; filter_intervals:
+        None or {name: (lo, hi)}, closed intervals on scalar attributes that every tile's points must lie in.
         Returns an XrayTiles that does not depend on the cloud."""
         if self.ctx is None:
             raise ValueError("xray_tiles: this S2 cell cloud was opened without a context (s2_open_host) and has no device")
         return self.ctx.xray_tiles([self], tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background,
-                                   root_node_id, max_workspace_bytes, min_intensity, max_intensity, binning)
+                                   root_node_id, max_workspace_bytes, min_intensity, max_intensity, binning, filter_intervals)
 
     def xray_quadtree(self, tile_size_px=256, pixel_size_m=None, strategy="xray", query_from_global=None, intensity_interval=None,
                       background="white", root_node_id="r", max_workspace_bytes=None, min_intensity=0.0, max_intensity=1.0,
-                      binning=None, output_directory=None, png="stored"):
+                      binning=None, output_directory=None, png="stored", filter_intervals=None):
         """xray_tiles (same arguments) with every level above the leaves built on the device, written to output_directory
         when one is given (OctreeResult.xray_quadtree)."""
         xt = self.xray_tiles(tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background, root_node_id,
-                             max_workspace_bytes, min_intensity, max_intensity, binning)
+                             max_workspace_bytes, min_intensity, max_intensity, binning, filter_intervals)
         xt.build_parents()
         if output_directory is not None:
             xt.write(output_directory, png=png)
@@ -2655,10 +2726,12 @@ def cloud_kind(directory):
 
 def build_xray_quadtree(ctx, point_cloud_locations, output_directory, tile_size_px=256, pixel_size_m=None, strategy="xray",
                         query_from_global=None, intensity_interval=None, background="white", root_node_id="r",
-                        max_workspace_bytes=None, min_intensity=0.0, max_intensity=1.0, binning=None, png="stored"):
+                        max_workspace_bytes=None, min_intensity=0.0, max_intensity=1.0, binning=None, png="stored",
+                        filter_intervals=None):
     """The reference's build_xray_quadtree binary over directories: the kind of the first one (cloud_kind) decides, every
     directory is opened as that kind (one of the other kind fails with the opener's own message), leaves and parents are
-    built on the device and the quadtree is written to output_directory. Returns the XrayTiles."""
+    built on the device and the quadtree is written to output_directory. Over S2 directories, binning takes any scalar
+    attribute and filter_intervals = {name: (lo, hi)} is --filter-interval. Returns the XrayTiles."""
     locations = list(point_cloud_locations)
     if not locations:
         raise ValueError("No locations specified for point cloud client.")
@@ -2667,7 +2740,7 @@ def build_xray_quadtree(ctx, point_cloud_locations, output_directory, tile_size_
     try:
         return ctx.xray_quadtree(clouds, tile_size_px, pixel_size_m, strategy, query_from_global, intensity_interval, background,
                                  root_node_id, max_workspace_bytes, min_intensity, max_intensity, binning,
-                                 output_directory=output_directory, png=png)
+                                 output_directory=output_directory, png=png, filter_intervals=filter_intervals)
     finally:
         for c in clouds:
             c.free()

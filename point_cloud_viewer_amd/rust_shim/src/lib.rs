@@ -896,8 +896,22 @@ pub struct PcvXrayColoring {
     pub binning_attribute: *const c_char,
     pub bin_size: c_double,
 }
+/// One `--filter-interval <attribute>=<min>,<max>` (pcv_xray_filter): a ClosedInterval<f64> on a scalar attribute.
+#[repr(C)]
+pub struct PcvXrayFilter {
+    pub attribute: *const c_char,
+    pub lo: c_double,
+    pub hi: c_double,
+}
 
 extern "C" {
+    /// pcv_xray_run_s2 with filters and binning on any scalar attribute of the clouds (XrayParameters::filter_intervals,
+    /// BinnedColoringStrategy::bins); with no filter and intensity binning it is pcv_xray_run_s2
+    fn pcv_xray_run_s2_ex(ctx: *mut pcv_ctx, clouds: *const *mut pcv_s2_cloud, num_clouds: u32, params: *const PcvXrayParams, coloring: *const PcvXrayColoring, filters: *const PcvXrayFilter, num_filters: u32, out: *mut *mut PcvXray) -> c_int;
+    /// the checks of pcv_xray_run_s2_ex that need no device
+    pub fn pcv_xray_check_attrs_host(params: *const PcvXrayParams, coloring: *const PcvXrayColoring, filters: *const PcvXrayFilter, num_filters: u32, num_clouds: u32, extras_first: *const u32, names: *const *const c_char, data_types: *const i32, has_intensity: *const u8, err: *mut c_char, errcap: u64) -> c_int;
+    /// `(data[i] as f64 / bin_size) as i64` for n values of a scalar data type, from the function the device compiles
+    pub fn pcv_xray_bins_host(data_type: i32, n: u64, data: *const std::ffi::c_void, bin_size: c_double, out: *mut i64) -> c_int;
     fn pcv_xray_run_s2(ctx: *mut pcv_ctx, clouds: *const *mut pcv_s2_cloud, num_clouds: u32, params: *const PcvXrayParams, coloring: *const PcvXrayColoring, out: *mut *mut PcvXray) -> c_int;
     fn pcv_xray_build_parents(x: *mut PcvXray) -> c_int;
     /// PointCloudClientBuilder::build's choice for a directory (0: octree, 1: S2 cells), by its meta.pb
@@ -961,12 +975,24 @@ impl HipS2Cells {
     /// `output_directory`. `coloring` is needed by colored_with_intensity and binning, as for pcv_xray_run_ex. Several
     /// clouds of one context go through pcv_xray_run_s2 in one call; this veneer holds one.
     pub fn build_xray_quadtree(&self, params: &PcvXrayParams, coloring: Option<&PcvXrayColoring>, output_directory: &Path, deflate: bool) -> Result<()> {
+        self.build_xray_quadtree_filtered(params, coloring, &[], output_directory, deflate)
+    }
+
+    /// `build_xray_quadtree` with `XrayParameters::filter_intervals` (name, lower bound, upper bound) on any scalar attribute of the cloud, and with a
+    /// `coloring.binning_attribute` that may name any scalar attribute (pcv_xray_run_s2_ex).
+    pub fn build_xray_quadtree_filtered(&self, params: &PcvXrayParams, coloring: Option<&PcvXrayColoring>, filter_intervals: &[(String, f64, f64)],
+                                        output_directory: &Path, deflate: bool) -> Result<()> {
         use std::os::unix::ffi::OsStrExt;
         let _guard = self.lock.lock().unwrap();
         let dir = CString::new(output_directory.as_os_str().as_bytes()).expect("path with a NUL byte");
         let clouds = [self.cloud];
         let mut x = std::ptr::null_mut();
-        let mut rc = unsafe { pcv_xray_run_s2(self.ctx.0, clouds.as_ptr(), 1, params, coloring.map_or(std::ptr::null(), |c| c as *const _), &mut x) };
+        let names: Vec<CString> = filter_intervals.iter().map(|(name, _, _)| CString::new(name.as_str()).expect("attribute name with a NUL byte")).collect();
+        let filters: Vec<PcvXrayFilter> =
+            filter_intervals.iter().zip(&names).map(|((_, lo, hi), name)| PcvXrayFilter { attribute: name.as_ptr(), lo: *lo, hi: *hi }).collect();
+        let mut rc = unsafe {
+            pcv_xray_run_s2_ex(self.ctx.0, clouds.as_ptr(), 1, params, coloring.map_or(std::ptr::null(), |c| c as *const _), filters.as_ptr(), filters.len() as u32, &mut x)
+        };
         if rc == 0 {
             rc = unsafe { pcv_xray_build_parents(x) };
         }

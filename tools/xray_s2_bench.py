@@ -13,7 +13,12 @@ point, and the bytes the flags pass and the two bin passes read, computed from c
 baseline at the commit before the S2 path. --baseline FILE merges such a record into this run's JSON (both octree figures,
 their spreads, and whether they are apart by more than those).
 
-usage: python tools/xray_s2_bench.py [--points N] [--steps K] [--octree-only] [--baseline FILE] [--out FILE]"""
+--attr is a leg of its own (no octree is built): the same cloud with an f32 intensity, an I64 `timestamp` extra (seven 30 s
+slices and a jitter below the bin) and a U8 `ring` extra, `colored` four ways from one process, alternating: unbinned, binned
+on intensity, binned on timestamp=30000000000 (pcv_xray_run_s2_ex: the scatter pass reads the column), and that with the filter
+ring in [64, 191]. The record goes to profiles/xray_s2_attr_bench.json.
+
+usage: python tools/xray_s2_bench.py [--points N] [--steps K] [--octree-only] [--attr] [--baseline FILE] [--out FILE]"""
 import argparse
 import json
 import os
@@ -108,18 +113,77 @@ def s2_bytes(strategy, candidates, kept, drawn, ms):
                 scatter_pass_bytes_per_s=rate(scatter, "xray_scatter_kernel"))
 
 
+ATTR_KERNELS = ("s2_flags_kernel", "s2_attr_filter_kernel", "batch_scan_kernel", "xray_bin_kernel", "xray_scatter_kernel", "xray_accum_kernel",
+                "xray_sorted_kernel")
+
+
+def attr_leg(args, ctx, dev):
+    """`colored` over the S2 cloud: today's two forms against binning on an I64 extra, without and with a U8 filter"""
+    x, y, z, rgb, iso = ecef_cloud(args.points, dev)
+    i = torch.arange(args.points, dtype=torch.int64, device=dev)
+    h = (i * 2654435761) % 1000003
+    timestamp = ((h % 7) - 3) * 30000000000 + (i % 1000) * 1000000
+    ring = (h % 256).to(torch.uint8)
+    intensity = (h % 1009).to(torch.float32) * 0.25
+    del i, h
+    cloud = ctx.s2_split(dict(x=x, y=y, z=z, color=rgb, intensity=intensity, attributes={"timestamp": timestamp, "ring": ring}), LEVEL)
+    del x, y, z, rgb, intensity, timestamp, ring
+    torch.cuda.empty_cache()
+    legs = {"colored": {}, "colored_binned_intensity": dict(binning=("intensity", 16.0)),
+            "colored_binned_timestamp": dict(binning=("timestamp", 30000000000.0)),
+            "colored_binned_timestamp_filter_ring": dict(binning=("timestamp", 30000000000.0), filter_intervals={"ring": (64, 191)})}
+    run = lambda kw: cloud.xray_tiles(TILE, PIXEL, "colored", query_from_global=iso, **kw)  # noqa: E731
+    out = {"tool": "tools/xray_s2_bench.py --attr", "build_hash": build_hash(), "device": torch.cuda.get_device_name(0),
+           "cloud": f"{args.points} Gaussian-cluster points (bench.make_cloud, seed 1) placed with synthetic.ecef_from_local({LAT}, {LNG}); "
+                    "f32 intensity, I64 timestamp, U8 ring",
+           "tile_size_px": TILE, "pixel_size_m": PIXEL, "split_level": LEVEL, "steps": args.steps, "s2_cells": cloud.num_cells, "legs": {}}
+    for kw in legs.values():  # the warm-up of all four
+        run(kw).free()
+    ctx.synchronize()
+    walls = {name: [] for name in legs}
+    for _ in range(args.steps):  # alternating
+        for name, kw in legs.items():
+            xt, ms = timed(ctx, lambda: run(kw))
+            walls[name].append(ms)
+            xt.free()
+    for name, kw in legs.items():  # one profiled run per leg for the kernel split and the counts
+        ctx.set_profiling(True)
+        ctx.reset_kernel_stats()
+        xt = run(kw)
+        st = ctx.kernel_stats()
+        ctx.set_profiling(False)
+        kms = {k: round(v[1], 3) for k, v in st.items() if v[0]}
+        out["legs"][name] = dict(stats(walls[name]), kernel_ms_split={k: kms.get(k) for k in ATTR_KERNELS}, kernel_ms=kms,
+                                 kernel_launches={k: v[0] for k, v in st.items() if v[0]}, leaf_tiles=len(xt.leaf_ids),
+                                 created_tiles=xt.num_created, points_kept=int(xt.kept.sum()), points_drawn=int(xt.drawn.sum()))
+        xt.free()
+    print(json.dumps(out))
+    path = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "xray_s2_attr_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        f.write(json.dumps(out, indent=1) + "\n")
+    ctx.close()
+    return 0
+
+
+DEFAULT_OUT = os.path.join(ROOT, "profiles", "xray_s2_bench.json")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=100_000_000)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--octree-only", action="store_true")
     ap.add_argument("--baseline", default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "xray_s2_bench.json"))
+    ap.add_argument("--attr", action="store_true")
+    ap.add_argument("--out", default=DEFAULT_OUT)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/xray_s2_bench.py needs a device: there is no CPU fallback")
     dev = torch.device("cuda", 0)
     ctx = pcv.Context(0)
+    if args.attr:
+        return attr_leg(args, ctx, dev)
     x, y, z, rgb, iso = ecef_cloud(args.points, dev)
     tree = ctx.build(0.001, None, x, y, z, rgb)
     cloud = None if args.octree_only else ctx.s2_split(dict(x=x, y=y, z=z, color=rgb), LEVEL)
