@@ -73,6 +73,11 @@ PCV_SA(sizeof(pcv_s2_merge_segment) == 24 && offsetof(pcv_s2_merge_segment, src_
 PCV_SA(sizeof(pcv_attribute) == 24 && offsetof(pcv_attribute, name) == 0 && offsetof(pcv_attribute, data_type) == 8 &&
            offsetof(pcv_attribute, reserved) == 12 && offsetof(pcv_attribute, data) == 16,
        "pcv_attribute");
+PCV_SA(sizeof(pcv_ply_write_params) == 32, "pcv_ply_write_params");
+PCV_SA(offsetof(pcv_ply_write_params, struct_size) == 0 && offsetof(pcv_ply_write_params, open_mode) == 4 &&
+           offsetof(pcv_ply_write_params, attributes) == 8 && offsetof(pcv_ply_write_params, num_attributes) == 16 &&
+           offsetof(pcv_ply_write_params, chunk_points) == 24,
+       "pcv_ply_write_params fields");
 PCV_SA(sizeof(pcv_s2_filter) == 32 && offsetof(pcv_s2_filter, location) == 0 && offsetof(pcv_s2_filter, reserved) == 4 &&
            offsetof(pcv_s2_filter, attribute) == 8 && offsetof(pcv_s2_filter, lo) == 16 && offsetof(pcv_s2_filter, hi) == 24,
        "pcv_s2_filter");

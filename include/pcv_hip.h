@@ -574,6 +574,20 @@ uint64_t pcv_ply_num_points(const pcv_ply* ply);
 /* Fills `out` with host pointers owned by `ply` (color / intensity are NULL when the file has none). */
 int pcv_ply_points(const pcv_ply* ply, pcv_points* out);
 void pcv_ply_free(pcv_ply* ply);
+/* 64-bit integer properties (longlong | int64 | ulonglong | uint64) are 8 bytes wide here — a departure: the reference
+ * advances 4 bytes for them (ply.rs:262-267) and so cannot read the files its own writer makes. As the type of x / y / z they
+ * stay refused. pcv_ply_read skips them by stride, as does pcv_build_octree_from_ply.
+ * pcv_ply_read_ex with PCV_PLY_READ_EXTRAS also keeps every other scalar vertex property as an extra attribute of its own
+ * type (pcv_ply_attributes: host columns owned by `ply`, in file order, as pcv_s2_split_ex takes them). All ten scalar types
+ * come back; the reference keeps u8, i64, u64, f32, f64 and silently drops the rest (ply.rs:427-434). Never extras: x, y, z,
+ * the colour properties (red | r, green | g, blue | b, and alpha | a, which is dropped), `intensity` when it is float (it is
+ * the intensity column). Skipped, not errors: a name that ends in an ASCII digit (one component of a vector attribute, which
+ * the reference's reader panics on, ply.rs:388), a name that breaks the rules for extras below, a name that
+ * occurs twice, and whatever comes after the PCV_S2_MAX_EXTRAS-th extra. With flags == 0 it is pcv_ply_read. */
+#define PCV_PLY_READ_EXTRAS 1u
+int pcv_ply_read_ex(const char* path, uint32_t flags, pcv_ply** out, char* err, uint64_t errcap);
+struct pcv_attribute;
+int pcv_ply_attributes(const pcv_ply* ply, uint32_t* count, struct pcv_attribute* out /* nullable; PCV_S2_MAX_EXTRAS entries */);
 /* build_octree_from_file (src/octree/generation.rs:272-287) with the decode on the device: the vertex records of the
  * file go up as they are (15 bytes per point for float x y z + uchar r g b instead of the 27 of f64 SoA arrays), one HIP
  * kernel casts x / y / z to f64 and adds the header offset like ply.rs:488-493, then the build runs with
@@ -1420,7 +1434,7 @@ void pcv_s2_query_free(pcv_s2_query* q);
  *   data       n elements, little endian, where points->mem says
  * A cell's file is `<token>.<name>`: the values of the cell's points in file order (src/lib.rs:74-80, read_write/raw.rs).
  * xray reads the extras through pcv_xray_run_s2_ex (filters and binning on any scalar one). Out of scope: clouds without
- * `color`; vector attributes as filters or bins; PLY properties as extras; the octree path, which is fixed to color and
+ * `color`; vector attributes as filters or bins; the octree path, which is fixed to color and
  * intensity as the reference's is (src/octree/mod.rs:63-72). */
 #define PCV_ATTR_U8 1
 #define PCV_ATTR_U16 2
@@ -1556,6 +1570,72 @@ int pcv_xray_check_attrs_host(const pcv_xray_params* params, const pcv_xray_colo
  * (bin_size is not validated: 0 gives +-inf or NaN), `as i64` truncating, saturating, NaN -> 0. A vector type is
  * PCV_E_INVALID. */
 int pcv_xray_bins_host(int32_t data_type, uint64_t n, const void* data, double bin_size, int64_t* out);
+
+/* ---- query results as PLY files ------------------------------------------------------- */
+/* PlyNodeWriter with Encoding::Plain (src/read_write/ply.rs:559-732), the reference's way of handing a query result to another
+ * program, over the results of pcv_query_batch_run and pcv_s2_query_run[_ex]; the rows are packed on the device.
+ *   row      position as three doubles x y z, then the attributes ascending by name (bytewise: BTreeMap order), each as its
+ *            little-endian bytes, no padding; `color` and `intensity` take their place among the extras by name. Bits are
+ *            copied: NaN payloads and -0.0 survive.
+ *   header   "ply\nformat binary_little_endian 1.0\nelement vertex " + the count as 20 zero-padded digits + "\n", `property
+ *            double x|y|z`, per attribute `property uchar red|green|blue` for color, `property <type> <name>0|1|2` for any
+ *            other vector, `property <type> <name>` for a scalar (type words: ply.rs:582-593), "end_header\n".
+ *   body     the rows, then one "\n" (ply.rs:646); the count field is patched last (:647-658).
+ *   attributes  NULL: every attribute the cloud has (an octree: color, and intensity if it has it; an S2 cloud: those and every
+ *            extra). Otherwise exactly the named ones (PointQuery::attributes; none: positions only), in any order. An unknown
+ *            name is PCV_E_INVALID "Data type for attribute 'NAME' not found." (lib.rs:94), a repeated one PCV_E_INVALID. A cloud
+ *            opened from a directory loads the named extras only.
+ * The rows alone, into a host or device buffer of capacity_bytes: row r of the output is point r of segments [first_segment,
+ * first_segment + num_segments), at r * *stride. pcv_query_batch_points' rules: a range past the end, or more rows than
+ * the capacity holds, is PCV_E_INVALID and writes nothing. *stride and *num_rows (nullable) are set whenever the range and the
+ * attributes are valid, also when the capacity is too small: they say what the range needs. */
+int pcv_query_batch_ply_rows(pcv_query_batch* b, uint64_t first_segment, uint64_t num_segments, const char* const* attributes,
+                             uint32_t num_attributes, uint64_t capacity_bytes, int mem, void* out, uint32_t* stride, uint64_t* num_rows);
+int pcv_s2_query_ply_rows(pcv_s2_query* q, uint64_t first_segment, uint64_t num_segments, const char* const* attributes,
+                          uint32_t num_attributes, uint64_t capacity_bytes, int mem, void* out, uint32_t* stride, uint64_t* num_rows);
+/* The file. The rows are cut into pieces of at most chunk_points rows (0: 2^20), at any row — neither a segment nor a chunk
+ * of the query sets a piece's size; two device buffers and two pinned blocks alternate, piece k + 1 packed while piece k is
+ * copied and written by the context's host threads, so device and pinned memory are O(chunk_points * stride) whatever the
+ * result's size.
+ *   PCV_PLY_TRUNCATE  the file is written anew. A range without points leaves no file behind (DataWriter's drop,
+ *                     node_writer.rs:78-84) and touches none that is there.
+ *   PCV_PLY_APPEND    OpenMode::Append (ply.rs:663-689): the old count is read from the fixed field, the rows go over the
+ *                     trailing newline, the count becomes the sum. A missing file, or one shorter than the fixed prefix, is
+ *                     written anew. A departure: the header that the requested attributes give is first compared with the
+ *                     file's, byte for byte, and a file of other columns is PCV_E_INVALID naming the first property line that
+ *                     differs (the reference appends whatever it is given). A range without points leaves the file as it is.
+ * A failure after the file was opened removes a truncated file and cuts an appended one back to its old length and count;
+ * PCV_E_IO names the path. *written (nullable): the rows written. Out of scope: the ScaledToCube position encodings of
+ * PlyNodeWriter (node files, not an exchange format), ascii and big-endian bodies, host-only S2 clouds. */
+#define PCV_PLY_TRUNCATE 0
+#define PCV_PLY_APPEND 1
+typedef struct pcv_ply_write_params {
+  uint32_t struct_size;          /* sizeof(pcv_ply_write_params) */
+  int32_t open_mode;             /* PCV_PLY_TRUNCATE / PCV_PLY_APPEND */
+  const char* const* attributes; /* NULL: every attribute of the cloud */
+  uint32_t num_attributes;
+  uint32_t reserved;
+  uint64_t chunk_points; /* rows per piece; 0 = the default */
+} pcv_ply_write_params;
+int pcv_query_batch_write_ply(pcv_query_batch* b, uint64_t first_segment, uint64_t num_segments, const char* path,
+                              const pcv_ply_write_params* params, uint64_t* written);
+int pcv_s2_query_write_ply(pcv_s2_query* q, uint64_t first_segment, uint64_t num_segments, const char* path,
+                           const pcv_ply_write_params* params, uint64_t* written);
+/* Host only, no context (messages: pcv_host_last_error). The layout of a row for n (name, PCV_ATTR_* data type) pairs in any
+ * order: offsets[i] is where the i-th GIVEN attribute stands in the row, *stride the row's bytes (24 with n == 0). A data
+ * type of 0 is PCV_E_INVALID "Data type for attribute 'NAME' not found.", any other unknown one "Attribute data type
+ * invalid", a repeated name PCV_E_INVALID. */
+int pcv_ply_layout_host(const char* const* names, const int32_t* data_types, uint32_t n, uint32_t* offsets, uint32_t* stride);
+/* The header for `count` vertices: *len its length, the first min(cap, *len) bytes into buf (nullable with cap == 0). */
+int pcv_ply_header_host(const char* const* names, const int32_t* data_types, uint32_t n, uint64_t count, char* buf, uint64_t cap,
+                        uint64_t* len);
+/* What PCV_PLY_APPEND checks before it touches `path`: *old_count the file's count (0 for a missing file or one shorter
+ * than the fixed prefix). PCV_E_INVALID: no PLY of this writer, a header of other columns (the message names the first
+ * line that differs), a length that is not header + count rows + newline. PCV_E_IO: the file cannot be read. */
+int pcv_ply_append_check_host(const char* path, const char* const* names, const int32_t* data_types, uint32_t n, uint64_t* old_count);
+/* The device pool of a context: the bytes handed out now and the most since the last reset (reset_peak != 0 sets the mark to the
+ * current figure after reading it). Either output may be NULL. */
+int pcv_ctx_pool_stats(pcv_ctx* ctx, uint64_t* live_bytes, uint64_t* peak_bytes, int reset_peak);
 
 /* Host only: which arm PointCloudClientBuilder::build (point_cloud_client/src/lib.rs:107-132) would take for this
  * directory's meta.pb: `version <= 11 || has_octree()` is PCV_CLOUD_OCTREE, anything else PCV_CLOUD_S2. The reference

@@ -193,6 +193,13 @@ ATTR_TYPES = {"u8": (1, "u1", 1), "u16": (2, "<u2", 1), "u32": (3, "<u4", 1), "u
               "f64vec3": (38, "<f8", 3)}
 ATTR_NAMES = {v[0]: k for k, v in ATTR_TYPES.items()}
 S2_MAX_EXTRAS = 16
+PLY_TRUNCATE, PLY_APPEND = 0, 1  # pcv_ply_write_params.open_mode
+PLY_READ_EXTRAS = 1  # PCV_PLY_READ_EXTRAS
+
+
+class PlyWriteParams(C.Structure):  # pcv_ply_write_params
+    _fields_ = [("struct_size", C.c_uint32), ("open_mode", C.c_int32), ("attributes", C.POINTER(C.c_char_p)), ("num_attributes", C.c_uint32),
+                ("reserved", C.c_uint32), ("chunk_points", C.c_uint64)]
 
 
 class OocStats(C.Structure):
@@ -424,6 +431,18 @@ _SIGNATURES = {
                                             _vp, C.POINTER(C.c_char_p), _vp, _vp, C.c_char_p, C.c_uint64]),
     "pcv_xray_bins_host": (C.c_int, [C.c_int32, C.c_uint64, _vp, C.c_double, _vp]),
     "pcv_cloud_kind": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
+    "pcv_ply_read_ex": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(_vp), C.c_char_p, C.c_uint64]),
+    "pcv_ply_attributes": (C.c_int, [_vp, C.POINTER(C.c_uint32), _vp]),
+    "pcv_query_batch_ply_rows": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint64, C.c_int, _vp,
+                                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "pcv_s2_query_ply_rows": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint64, C.c_int, _vp,
+                                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "pcv_query_batch_write_ply": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_char_p, C.POINTER(PlyWriteParams), C.POINTER(C.c_uint64)]),
+    "pcv_s2_query_write_ply": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_char_p, C.POINTER(PlyWriteParams), C.POINTER(C.c_uint64)]),
+    "pcv_ply_layout_host": (C.c_int, [C.POINTER(C.c_char_p), _vp, C.c_uint32, _vp, C.POINTER(C.c_uint32)]),
+    "pcv_ply_header_host": (C.c_int, [C.POINTER(C.c_char_p), _vp, C.c_uint32, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "pcv_ply_append_check_host": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), _vp, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "pcv_ctx_pool_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
 }
 
 _lib = None

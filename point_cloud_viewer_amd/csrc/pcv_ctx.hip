@@ -20,6 +20,8 @@ void* PcvPool::alloc(size_t bytes, hipError_t* err) {
   if (it != free_blocks.end() && it->first <= bytes + bytes / 8 + (64u << 10)) {
     void* p = it->second;
     live[p] = it->first;
+    live_bytes += it->first;
+    peak_bytes = std::max(peak_bytes, live_bytes);
     free_blocks.erase(it);
     return p;
   }
@@ -32,6 +34,8 @@ void* PcvPool::alloc(size_t bytes, hipError_t* err) {
     if (*err != hipSuccess) return nullptr;
   }
   live[p] = bytes;
+  live_bytes += bytes;
+  peak_bytes = std::max(peak_bytes, live_bytes);
   return p;
 }
 void PcvPool::release(void* p) {
@@ -39,6 +43,7 @@ void PcvPool::release(void* p) {
   auto it = live.find(p);
   if (it == live.end()) return;
   free_blocks.insert({it->second, p});
+  live_bytes -= it->second;
   live.erase(it);
 }
 void PcvPool::trim() {
@@ -262,7 +267,7 @@ static const char* kKernelNames[PCV_K_COUNT] = {
     "s2_ids_kernel", "s2_unique_kernel", "s2_rank_kernel", "s2_gather_kernel", "s2_union_kernel",
     "s2_cell_table_kernel", "s2_location_kernel", "s2_pair_kernel", "s2_flags_kernel", "s2_gather_points_kernel",
     "union_node_rects_kernel", "s2_merge_kernel", "s2_attr_gather_kernel", "s2_attr_merge_kernel", "s2_attr_filter_kernel",
-    "s2_attr_gather_points_kernel"};
+    "s2_attr_gather_points_kernel", "ply_rows_kernel"};
 static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == PCV_K_COUNT, "kernel name table out of sync");
 
 extern "C" int pcv_ctx_set_profiling(pcv_ctx* ctx, int enabled) {
@@ -291,6 +296,14 @@ extern "C" int pcv_ctx_kernel_stats(pcv_ctx* ctx, int kernel_id, const char** na
   if (launches) *launches = ctx->prof_launches[kernel_id];
   if (total_ms) *total_ms = ctx->prof_ms[kernel_id];
   return PCV_K_COUNT;
+}
+
+extern "C" int pcv_ctx_pool_stats(pcv_ctx* ctx, uint64_t* live_bytes, uint64_t* peak_bytes, int reset_peak) {
+  if (!ctx) return PCV_E_INVALID;
+  if (live_bytes) *live_bytes = ctx->pool.live_bytes;
+  if (peak_bytes) *peak_bytes = ctx->pool.peak_bytes;
+  if (reset_peak) ctx->pool.peak_bytes = ctx->pool.live_bytes;
+  return PCV_OK;
 }
 
 extern "C" int pcv_abi_version(void) { return PCV_ABI_VERSION; }

@@ -41,6 +41,7 @@ struct PcvHostPool {
 struct PcvPool {
   std::multimap<size_t, void*> free_blocks;
   std::map<void*, size_t> live;
+  size_t live_bytes = 0, peak_bytes = 0;  // bytes handed out now, and the most since the last pcv_ctx_pool_stats reset
   void* alloc(size_t bytes, hipError_t* err);
   void release(void* p);
   void trim();
@@ -120,6 +121,7 @@ enum PcvKernelId {
   PCV_K_S2_ATTR_MERGE,        // pcv_s2_attr.hip: one extra attribute's column of a stream's parts merged over the plan, by output chunk
   PCV_K_S2_ATTR_FILTER,       // pcv_s2_attr.hip: keep flags ANDed with one extra's interval test, over the chunks that filter on it
   PCV_K_S2_ATTR_GATHER_POINTS,  // pcv_s2_attr.hip: one extra's values of the kept points of a segment range
+  PCV_K_PLY_ROWS,             // pcv_ply_rows.hip: the kept points of a row range packed as PLY rows (octree batch or S2 query)
   PCV_K_COUNT
 };
 

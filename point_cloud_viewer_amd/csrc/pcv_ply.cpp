@@ -5,8 +5,14 @@
 // `comment offset: x y z` is added; red|r, green|g, blue|b (uchar) form the colour; `intensity` (float) is kept;
 // a|alpha and every other property are skipped; list properties are ignored. One pass over the file fills the SoA
 // arrays the build consumes directly (the reference reads the file twice: bounding box, then batches).
-// Not supported (rejected with PCV_E_INVALID): ascii / big-endian bodies (the reference panics on them too) and
-// 64-bit integer properties (the reference advances its cursor by 4 bytes for them, ply.rs:278-283).
+// Not supported (rejected with PCV_E_INVALID): ascii / big-endian bodies (the reference panics on them too).
+// 64-bit integer properties (longlong | int64 | ulonglong | uint64) are 8 bytes wide — a departure: the reference advances
+// its cursor by 4 bytes for them (ply.rs:262-267) and so cannot read the files its own writer makes (pcv_ply_write.cpp); as
+// the type of x / y / z they stay refused.
+// pcv_ply_read_ex with PCV_PLY_READ_EXTRAS keeps every other scalar property as an extra attribute of its own type — all ten
+// types, where the reference keeps five and silently drops the rest (:427-434). Skipped, not errors: names ending in an
+// ASCII digit (a component of a vector attribute; the reference panics, :388), names that break the rules for extras
+// (include/pcv_hip.h), repeats, and anything past PCV_S2_MAX_EXTRAS.
 #include <cstdio>
 #include <cstring>
 #include <sstream>
@@ -22,13 +28,21 @@ struct pcv_ply {
   std::vector<float> intensity;
   bool has_color = false, has_intensity = false;
   double offset[3] = {0, 0, 0};
+  struct Extra {
+    std::string name;
+    int32_t data_type;  // PCV_ATTR_*
+    int elem, offset;   // bytes per point; where it stands in a vertex record
+    std::vector<uint8_t> data;
+  };
+  std::vector<Extra> extras;  // PCV_PLY_READ_EXTRAS, in file order
 };
 
 namespace {
 
-enum Type { T_I8, T_U8, T_I16, T_U16, T_I32, T_U32, T_F32, T_F64, T_BAD };  // == PcvPlyType (pcv_ply_layout.h)
+enum Type { T_I8, T_U8, T_I16, T_U16, T_I32, T_U32, T_F32, T_F64, T_I64, T_U64, T_BAD };  // == PcvPlyType (pcv_ply_layout.h)
 static_assert(T_I8 == (int)PCV_PLY_I8 && T_U8 == (int)PCV_PLY_U8 && T_I16 == (int)PCV_PLY_I16 && T_U16 == (int)PCV_PLY_U16 &&
-                  T_I32 == (int)PCV_PLY_I32 && T_U32 == (int)PCV_PLY_U32 && T_F32 == (int)PCV_PLY_F32 && T_F64 == (int)PCV_PLY_F64,
+                  T_I32 == (int)PCV_PLY_I32 && T_U32 == (int)PCV_PLY_U32 && T_F32 == (int)PCV_PLY_F32 && T_F64 == (int)PCV_PLY_F64 && T_I64 == (int)PCV_PLY_I64 &&
+                  T_U64 == (int)PCV_PLY_U64,
               "the host parser and the device decode share the type numbering");
 Type parse_type(const std::string& s) {  // ply.rs:62-80 DataType::from_str
   if (s == "char" || s == "int8") return T_I8;
@@ -39,6 +53,8 @@ Type parse_type(const std::string& s) {  // ply.rs:62-80 DataType::from_str
   if (s == "uint" || s == "uint32") return T_U32;
   if (s == "float" || s == "float32") return T_F32;
   if (s == "double" || s == "float64") return T_F64;
+  if (s == "longlong" || s == "int64") return T_I64;
+  if (s == "ulonglong" || s == "uint64") return T_U64;
   return T_BAD;
 }
 int type_size(Type t) {
@@ -62,11 +78,36 @@ double read_as_f64(Type t, const uint8_t* p) {
   }
 }
 
-struct Prop {
-  std::string name;
-  Type type;
-  int offset;
-};
+using Prop = PcvPlyProp;
+
+// the PCV_ATTR_* data type of a property's type (src/attributes.rs:8-21)
+int32_t attr_type(int t) {
+  switch (t) {
+    case T_I8: return PCV_ATTR_I8;
+    case T_U8: return PCV_ATTR_U8;
+    case T_I16: return PCV_ATTR_I16;
+    case T_U16: return PCV_ATTR_U16;
+    case T_I32: return PCV_ATTR_I32;
+    case T_U32: return PCV_ATTR_U32;
+    case T_F32: return PCV_ATTR_F32;
+    case T_F64: return PCV_ATTR_F64;
+    case T_I64: return PCV_ATTR_I64;
+    default: return PCV_ATTR_U64;
+  }
+}
+// the naming rules of an extra (include/pcv_hip.h), and no trailing digit
+bool extra_name_ok(const std::string& nm) {
+  if (nm.empty() || nm.size() > PCV_S2_MAX_ATTR_NAME) return false;
+  for (const char* reserved : {"color", "intensity", "position", "xyz", "rgb", "meta"})
+    if (nm == reserved) return false;
+  if (nm.find('/') != std::string::npos || nm.find('.') != std::string::npos) return false;
+  return !(nm.back() >= '0' && nm.back() <= '9');
+}
+bool is_builtin(const Prop& p) {
+  for (const char* b : {"x", "y", "z", "r", "red", "g", "green", "b", "blue", "a", "alpha"})
+    if (p.name == b) return true;
+  return p.name == "intensity" && p.type == T_F32;
+}
 
 int fail(char* err, size_t cap, int code, const std::string& msg) {
   if (err && cap) snprintf(err, cap, "%s", msg.c_str());
@@ -88,7 +129,7 @@ bool read_line(FILE* f, std::string* line) {
 // Header of a binary little-endian PLY (ply.rs:126-221) -> where the vertex records start and how one is laid out.
 // Leaves `f` at the first vertex record. The header is untrusted: a vertex count the rest of the file cannot hold
 // (negative, absurd) is rejected here, before anything is sized by it.
-int pcv_ply_parse_header(FILE* f, PcvPlyLayout* lay, char* err, uint64_t errcap) {
+int pcv_ply_parse_header(FILE* f, PcvPlyLayout* lay, char* err, uint64_t errcap, std::vector<PcvPlyProp>* props_out) {
   std::string line;
   if (!read_line(f, &line) || line.find("ply") != 0 || line.find_first_not_of(" \r\t", 3) != std::string::npos)
     return fail(err, errcap, PCV_E_INVALID, "Not a PLY file");
@@ -125,7 +166,7 @@ int pcv_ply_parse_header(FILE* f, PcvPlyLayout* lay, char* err, uint64_t errcap)
       if (in_vertex) {
         Type t = parse_type(e[1]);
         if (t == T_BAD) return fail(err, errcap, PCV_E_INVALID, "Invalid or unsupported data type: " + e[1]);
-        props.push_back(Prop{e[2], t, stride});
+        props.push_back(Prop{e[2], (int)t, stride});
         stride += type_size(t);
       }
     } else if (e[0] == "end_header") {
@@ -155,6 +196,9 @@ int pcv_ply_parse_header(FILE* f, PcvPlyLayout* lay, char* err, uint64_t errcap)
     else if (nm == "intensity" && props[k].type == T_F32) ii = (int)k;
   }
   if (ix < 0 || iy < 0 || iz < 0) return fail(err, errcap, PCV_E_INVALID, "PLY must contain properties 'x', 'y', 'z' for 'vertex'.");
+  for (int k : {ix, iy, iz})
+    if (props[k].type == T_I64 || props[k].type == T_U64)
+      return fail(err, errcap, PCV_E_INVALID, "Invalid or unsupported data type for '" + props[k].name + "': 64-bit integer positions");
   const bool has_color = ir >= 0 && ig >= 0 && ib >= 0;
   if (has_color && (props[ir].type != T_U8 || props[ig].type != T_U8 || props[ib].type != T_U8))
     return fail(err, errcap, PCV_E_INVALID, "colour properties must be uchar");
@@ -175,16 +219,21 @@ int pcv_ply_parse_header(FILE* f, PcvPlyLayout* lay, char* err, uint64_t errcap)
   lay->g_off = has_color ? props[ig].offset : -1;
   lay->b_off = has_color ? props[ib].offset : -1;
   lay->i_off = ii >= 0 ? props[ii].offset : -1;
+  if (props_out) *props_out = props;
   return PCV_OK;
 }
 
-extern "C" int pcv_ply_read(const char* path, pcv_ply** out, char* err, uint64_t errcap) {
+extern "C" int pcv_ply_read(const char* path, pcv_ply** out, char* err, uint64_t errcap) { return pcv_ply_read_ex(path, 0, out, err, errcap); }
+
+extern "C" int pcv_ply_read_ex(const char* path, uint32_t flags, pcv_ply** out, char* err, uint64_t errcap) {
   if (!path || !out) return PCV_E_INVALID;
   *out = nullptr;
+  if (flags & ~PCV_PLY_READ_EXTRAS) return fail(err, errcap, PCV_E_INVALID, "unknown flag bits");
   FILE* f = fopen(path, "rb");
   if (!f) return fail(err, errcap, PCV_E_IO, "Could not open input file.");
   PcvPlyLayout lay;
-  int rc = pcv_ply_parse_header(f, &lay, err, errcap);
+  std::vector<PcvPlyProp> props;
+  int rc = pcv_ply_parse_header(f, &lay, err, errcap, &props);
   if (rc != PCV_OK) {
     fclose(f);
     return rc;
@@ -198,6 +247,13 @@ extern "C" int pcv_ply_read(const char* path, pcv_ply** out, char* err, uint64_t
   for (int a = 0; a < 3; ++a) ply->offset[a] = lay.offset[a];
   ply->has_color = lay.r_off >= 0;
   ply->has_intensity = lay.i_off >= 0;
+  if (flags & PCV_PLY_READ_EXTRAS)
+    for (const PcvPlyProp& p : props) {
+      if (is_builtin(p) || !extra_name_ok(p.name) || ply->extras.size() >= PCV_S2_MAX_EXTRAS) continue;
+      bool seen = false;
+      for (const pcv_ply::Extra& e : ply->extras) seen = seen || e.name == p.name;
+      if (!seen) ply->extras.push_back(pcv_ply::Extra{p.name, attr_type(p.type), type_size((Type)p.type), p.offset, {}});
+    }
   const int stride = lay.stride;
   // no allocation failure may unwind across the C ABI
   const size_t n = (size_t)lay.vertex_count;
@@ -209,6 +265,7 @@ extern "C" int pcv_ply_read(const char* path, pcv_ply** out, char* err, uint64_t
     ply->z.resize(n);
     if (ply->has_color) ply->rgb.resize(3 * n);
     if (ply->has_intensity) ply->intensity.resize(n);
+    for (pcv_ply::Extra& e : ply->extras) e.data.resize(n * (size_t)e.elem);
     buf.resize(chunk_pts * (size_t)stride);
   } catch (...) {
     return bail(PCV_E_OOM, "out of host memory for " + std::to_string(n) + " points");
@@ -228,6 +285,7 @@ extern "C" int pcv_ply_read(const char* path, pcv_ply** out, char* err, uint64_t
         ply->rgb[3 * (done + k) + 2] = p[lay.b_off];
       }
       if (ply->has_intensity) std::memcpy(&ply->intensity[done + k], p + lay.i_off, 4);
+      for (pcv_ply::Extra& e : ply->extras) std::memcpy(e.data.data() + (done + k) * (size_t)e.elem, p + e.offset, (size_t)e.elem);
     }
     done += m;
   }
@@ -248,6 +306,13 @@ extern "C" int pcv_ply_points(const pcv_ply* p, pcv_points* out) {
   out->color_stride = 3;
   out->intensity = p->has_intensity ? p->intensity.data() : nullptr;
   out->mem = PCV_MEM_HOST;
+  return PCV_OK;
+}
+
+extern "C" int pcv_ply_attributes(const pcv_ply* p, uint32_t* count, pcv_attribute* out) {
+  if (!p) return PCV_E_INVALID;
+  if (count) *count = (uint32_t)p->extras.size();
+  for (size_t k = 0; out && k < p->extras.size(); ++k) out[k] = pcv_attribute{p->extras[k].name.c_str(), p->extras[k].data_type, 0u, p->extras[k].data.data()};
   return PCV_OK;
 }
 

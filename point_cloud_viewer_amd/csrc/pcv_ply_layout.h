@@ -4,7 +4,11 @@
 #include <stdint.h>
 #include <stdio.h>
 
-enum PcvPlyType { PCV_PLY_I8, PCV_PLY_U8, PCV_PLY_I16, PCV_PLY_U16, PCV_PLY_I32, PCV_PLY_U32, PCV_PLY_F32, PCV_PLY_F64 };
+#include <string>
+#include <vector>
+
+// (x / y / z are never of the two 64-bit integer types: the device decode knows the first eight only)
+enum PcvPlyType { PCV_PLY_I8, PCV_PLY_U8, PCV_PLY_I16, PCV_PLY_U16, PCV_PLY_I32, PCV_PLY_U32, PCV_PLY_F32, PCV_PLY_F64, PCV_PLY_I64, PCV_PLY_U64 };
 
 struct PcvPlyLayout {
   long long vertex_count = 0;
@@ -15,5 +19,12 @@ struct PcvPlyLayout {
   int i_off = -1;                          // float `intensity`, -1: none
   double offset[3] = {0, 0, 0};            // `comment offset: x y z`
 };
-// Leaves `f` at the first vertex record; rejects vertex counts the rest of the file cannot hold.
-int pcv_ply_parse_header(FILE* f, PcvPlyLayout* lay, char* err, uint64_t errcap);
+// one scalar property of element `vertex`, in file order
+struct PcvPlyProp {
+  std::string name;
+  int type;    // PcvPlyType
+  int offset;  // byte offset inside the record
+};
+// Leaves `f` at the first vertex record; rejects vertex counts the rest of the file cannot hold. props (nullable): every
+// scalar vertex property.
+int pcv_ply_parse_header(FILE* f, PcvPlyLayout* lay, char* err, uint64_t errcap, std::vector<PcvPlyProp>* props = nullptr);

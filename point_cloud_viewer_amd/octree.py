@@ -152,8 +152,16 @@ class Context:
         """Give the cached scratch blocks of the context's pool back to the driver (pcv_ctx_trim)."""
         self._check(self.lib.pcv_ctx_trim(self.handle))
 
+    def pool_stats(self, reset_peak=False):
+        """(bytes the device pool has handed out now, the most since the last reset) (pcv_ctx_pool_stats); reset_peak=True sets
+        the high-water mark to the current figure after reading it."""
+        live, peak = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.pcv_ctx_pool_stats(self.handle, C.byref(live), C.byref(peak), 1 if reset_peak else 0))
+        return live.value, peak.value
+
     def close(self):
-        for child in list(getattr(self, "_children", [])):
+        # query batches first: freeing an S2 batch reads its cloud (pcv_s2_query_free), so the cloud must still be there
+        for child in sorted(getattr(self, "_children", []), key=lambda c: 0 if isinstance(c, QueryBatch) else 1):
             child.free()
         if getattr(self, "handle", None):
             self.lib.pcv_ctx_destroy(self.handle)
@@ -1383,6 +1391,84 @@ class QueryBatch:
             raise KeyError(f"node {node} is not among shape {s}'s nodes")
         return self.points(int(first[s]) + int(hit[0]), 1)
 
+    # ---- PLY output (pcv_*_ply_rows, pcv_*_write_ply) ----
+    def _ply_available(self):
+        """The attributes a row can carry: name -> type string."""
+        have = {"color": "u8vec3"}
+        if self._has_int:
+            have["intensity"] = "f32"
+        return have
+
+    def _ply_range(self, shape, first_segment, num_segments):
+        """(first, num) as the library takes them; a range past the end goes through so that the library refuses it."""
+        if shape is not None:
+            first, _, _ = self.segments()
+            return int(first[shape]), int(first[shape + 1] - first[shape])
+        first = int(first_segment)
+        num = max(self.num_segments - first, 0) if num_segments is None else int(num_segments)
+        return first, num
+
+    def ply_layout(self, attributes=None):
+        """The row layout for `attributes` (None: every attribute of the cloud; else exactly the named ones) as ply_layout
+        returns it. An unknown name raises PcvError with the library's message."""
+        have = self._ply_available()
+        names = list(have) if attributes is None else [str(a) for a in attributes]
+        return ply_layout([(n, have.get(n)) for n in names])
+
+    def ply_rows(self, shape=None, first_segment=0, num_segments=None, attributes=None, device=False):
+        """The points of a segment range (or of shape `shape`) as packed PLY rows, packed on the device
+        (pcv_query_batch_ply_rows / pcv_s2_query_ply_rows) -> (uint8 array [rows, stride], layout). device=True: a torch
+        tensor on the context's device instead of a numpy array."""
+        self._live()
+        first, num = self._ply_range(shape, first_segment, num_segments)
+        names, count, _keep = _ply_names(attributes)
+        stride, rows = C.c_uint32(), C.c_uint64()
+        fn = self._fn("ply_rows")
+        rc = fn(self.handle, first, num, names, count, 0, L.MEM_HOST, None, C.byref(stride), C.byref(rows))
+        if rc != L.PCV_OK and (stride.value == 0 or rows.value == 0):  # anything but "capacity too small"
+            self.ctx._check(rc)
+        layout = self.ply_layout(attributes)
+        n, s = rows.value, stride.value
+        if device:
+            import torch
+            out = torch.empty((n, s), dtype=torch.uint8, device=f"cuda:{self.ctx.device}")
+            self.ctx.wait_torch()
+            ptr, mem = out.data_ptr(), L.MEM_DEVICE
+        else:
+            out = np.zeros((n, s), dtype=np.uint8)
+            ptr, mem = out.ctypes.data, L.MEM_HOST
+        if n:
+            self.ctx._check(fn(self.handle, first, num, names, count, n * s, mem, ptr, C.byref(stride), C.byref(rows)))
+        return out, layout
+
+    def write_ply(self, path, shape=None, first_segment=0, num_segments=None, attributes=None, open_mode="truncate", chunk_points=0):
+        """PlyNodeWriter over a segment range (or shape `shape`): a binary little-endian PLY with double positions and the
+        attributes ascending by name (pcv_query_batch_write_ply / pcv_s2_query_write_ply). open_mode "truncate" | "append";
+        chunk_points: rows per piece of the device-to-file pipeline (0: the default). Returns the rows written; a range
+        without points writes no file."""
+        self._live()
+        if open_mode not in ("truncate", "append"):
+            raise ValueError("open_mode: 'truncate' or 'append'")
+        first, num = self._ply_range(shape, first_segment, num_segments)
+        names, count, _keep = _ply_names(attributes)
+        pr = L.PlyWriteParams()
+        pr.struct_size = C.sizeof(L.PlyWriteParams)
+        pr.open_mode = L.PLY_APPEND if open_mode == "append" else L.PLY_TRUNCATE
+        pr.attributes, pr.num_attributes, pr.reserved, pr.chunk_points = names, count, 0, int(chunk_points)
+        written = C.c_uint64()
+        self.ctx._check(self._fn("write_ply")(self.handle, first, num, os.fsencode(str(path)), C.byref(pr), C.byref(written)))
+        return written.value
+
+    def write_ply_per_location(self, pattern, attributes=None, open_mode="truncate", chunk_points=0):
+        """One file per shape (location): pattern.format(i) holds shape i's points; shapes without points get no file.
+        Returns {i: rows written} for the files that exist afterwards because of this call."""
+        out = {}
+        for i in range(self.num_shapes):
+            n = self.write_ply(pattern.format(i), shape=i, attributes=attributes, open_mode=open_mode, chunk_points=chunk_points)
+            if n:
+                out[i] = n
+        return out
+
     def free(self):
         if self.handle and self.ctx.handle:
             self._fn("free")(self.handle)
@@ -2160,12 +2246,88 @@ def write_meta(directory, resolution, bbox_min, bbox_max, nodes):
         raise L.PcvError(rc, f"cannot write meta.pb in {directory}")
 
 
-def read_ply(path):
-    """PlyIterator in one pass (src/read_write/ply.rs): dict(x, y, z float64; color (n,3) uint8 or None; intensity or None)."""
+def _ply_names(attributes):
+    """attributes (None: every attribute of the cloud, else names) as the char** the PLY entry points take ->
+    (array or None, count, keep-alive)."""
+    if attributes is None:
+        return None, 0, []
+    keep = [os.fsencode(str(a)) for a in attributes]
+    return (C.c_char_p * max(1, len(keep)))(*keep), len(keep), keep
+
+
+def _ply_columns(attributes):
+    """dict name -> type string, or a sequence of (name, type string | None) -> (names char**, types int32[], n, keep-alive). A type
+    of None goes down as 0: the library answers "Data type for attribute 'NAME' not found."."""
+    items = list(attributes.items()) if isinstance(attributes, dict) else [tuple(a) for a in attributes]
+    names = [os.fsencode(str(n)) for n, _ in items]
+    codes = []
+    for n, t in items:
+        if t is not None and str(t).lower() not in L.ATTR_TYPES:
+            raise L.PcvError(L.PCV_E_INVALID, f"Attribute data type invalid (attribute '{n}', type {t!r})")
+        codes.append(0 if t is None else L.ATTR_TYPES[str(t).lower()][0])
+    types = np.array(codes, dtype=np.int32)
+    return (C.c_char_p * max(1, len(names)))(*names), types, len(names), (names, types, items)
+
+
+def ply_layout(attributes):
+    """The row of the PLY that write_ply writes for `attributes` — a dict name -> type string ("u8" ... "f64", "u8vec3",
+    "f64vec3") or a sequence of (name, type) in any order (pcv_ply_layout_host): dict(stride=bytes per row, names=the attributes
+    in row order (ascending by name, bytewise), offsets={name: byte offset}, types={name: type string}, dtype=the packed numpy
+    structured dtype of a row, fields named as the header's properties). Position, three doubles, is always at 0."""
+    lib = L.load_library()
+    names, types, n, keep = _ply_columns(attributes)
+    offsets, stride = np.zeros(max(1, n), dtype=np.uint32), C.c_uint32()
+    _host_check(lib.pcv_ply_layout_host(names, types.ctypes.data, n, offsets.ctypes.data, C.byref(stride)), "ply_layout")
+    items = keep[2]
+    order = sorted(range(n), key=lambda k: int(offsets[k]))
+    fields = [("x", "<f8"), ("y", "<f8"), ("z", "<f8")]
+    for k in order:
+        name, typ = str(items[k][0]), str(items[k][1]).lower()
+        _, dt, comps = L.ATTR_TYPES[typ]
+        if name in ("color", "rgb", "rgba"):
+            fields += [(c, dt) for c in ("red", "green", "blue", "alpha")[:comps]]
+        elif comps > 1:
+            fields += [(f"{name}{i}", dt) for i in range(comps)]
+        else:
+            fields.append((name, dt))
+    try:
+        dtype = np.dtype(fields, align=False)
+    except ValueError:  # property names that repeat (an attribute `red` beside color): the bytes are what they are, numpy cannot name them
+        dtype = None
+    return dict(stride=stride.value, names=[str(items[k][0]) for k in order], offsets={str(items[k][0]): int(offsets[k]) for k in range(n)},
+                types={str(items[k][0]): str(items[k][1]).lower() for k in range(n)}, dtype=dtype)
+
+
+def ply_header(attributes, count):
+    """The header write_ply writes for `attributes` (as ply_layout takes them) and `count` vertices, as bytes (pcv_ply_header_host)."""
+    lib = L.load_library()
+    names, types, n, _keep = _ply_columns(attributes)
+    need = C.c_uint64()
+    _host_check(lib.pcv_ply_header_host(names, types.ctypes.data, n, int(count), None, 0, C.byref(need)), "ply_header")
+    buf = C.create_string_buffer(need.value + 1)
+    _host_check(lib.pcv_ply_header_host(names, types.ctypes.data, n, int(count), buf, need.value, C.byref(need)), "ply_header")
+    return buf.raw[:need.value]
+
+
+def ply_append_check(path, attributes):
+    """What write_ply(open_mode="append") checks before it touches `path` (pcv_ply_append_check_host): the file's vertex count
+    (0: no file, or one shorter than the fixed prefix). PcvError: PCV_E_INVALID for a file of other columns or no PLY of this
+    writer, PCV_E_IO for one that cannot be read."""
+    lib = L.load_library()
+    names, types, n, _keep = _ply_columns(attributes)
+    old = C.c_uint64()
+    _host_check(lib.pcv_ply_append_check_host(os.fsencode(str(path)), names, types.ctypes.data, n, C.byref(old)), "ply_append_check")
+    return old.value
+
+
+def read_ply(path, extras=False):
+    """PlyIterator in one pass (src/read_write/ply.rs): dict(x, y, z float64; color (n,3) uint8 or None; intensity or None).
+    extras=True (pcv_ply_read_ex): also attributes = {name: array} of every other scalar vertex property in its own type, in the
+    form Context.s2_split takes; properties whose name ends in a digit or breaks the naming rules of extras are skipped."""
     lib = L.load_library()
     h = C.c_void_p()
     err = C.create_string_buffer(512)
-    rc = lib.pcv_ply_read(str(path).encode(), C.byref(h), err, 512)
+    rc = lib.pcv_ply_read_ex(str(path).encode(), L.PLY_READ_EXTRAS if extras else 0, C.byref(h), err, 512)
     if rc != L.PCV_OK:
         raise L.PcvError(rc, err.value.decode())
     try:
@@ -2185,6 +2347,16 @@ def read_ply(path):
             out["x"] = out["y"] = out["z"] = np.zeros(0)
         if out["color"] is not None:
             out["color"] = out["color"].reshape(-1, 3)
+        if extras:
+            count, attrs = C.c_uint32(), (L.Attribute * L.S2_MAX_EXTRAS)()
+            lib.pcv_ply_attributes(h, C.byref(count), attrs)
+            out["attributes"] = {}
+            for k in range(count.value):
+                dt = np.dtype(L.ATTR_TYPES[L.ATTR_NAMES[attrs[k].data_type]][1])
+                col = np.zeros(n, dtype=dt)
+                if n:
+                    C.memmove(col.ctypes.data, attrs[k].data, n * dt.itemsize)
+                out["attributes"][os.fsdecode(attrs[k].name)] = col
         return out
     finally:
         lib.pcv_ply_free(h)
@@ -2241,6 +2413,11 @@ class S2QueryBatch(QueryBatch):
         self._has_int = cloud.has_intensity
         self._segments = None
         self.ctx._children.add(self)
+
+    def _ply_available(self):
+        have = QueryBatch._ply_available(self)
+        have.update(self.tree.attributes)
+        return have
 
     def attribute(self, name, first_segment=0, num_segments=None):
         """One extra attribute of the kept points of segments [first_segment, first_segment + num_segments) (default: to the

@@ -159,6 +159,8 @@ extern "C" {
     fn pcv_query_batch_segments(b: *const pcv_query_batch, shape_first_segment: *mut u64, segment_node: *mut u32, segment_offset: *mut u64) -> c_int;
     fn pcv_query_batch_points(b: *mut pcv_query_batch, first_segment: u64, num_segments: u64, capacity: u64, mem: c_int, x: *mut c_double, y: *mut c_double, z: *mut c_double, rgb: *mut u8, intensity: *mut c_float) -> c_int;
     fn pcv_query_batch_free(b: *mut pcv_query_batch);
+    // PlyNodeWriter over a query's result (ply.rs:559-732): the rows packed on the device, the file written in pieces
+    fn pcv_query_batch_write_ply(b: *mut pcv_query_batch, first_segment: u64, num_segments: u64, path: *const c_char, params: *const PcvPlyWriteParams, written: *mut u64) -> c_int;
     // the viewer's frame: get_visible_nodes + GL_POINTS under a depth test, rasterised on the device
     fn pcv_s2_open_dir(ctx: *mut pcv_ctx, directory: *const c_char, out: *mut *mut pcv_s2_cloud) -> c_int;
     fn pcv_s2_info(c: *const pcv_s2_cloud, num_cells: *mut u64, num_points: *mut u64, bbox_min: *mut c_double, bbox_max: *mut c_double, has_intensity: *mut c_int, level: *mut u32) -> c_int;
@@ -174,6 +176,17 @@ extern "C" {
     fn pcv_render_views_ex(ctx: *mut pcv_ctx, frusta: *const pcv_shapes, t: *mut pcv_octree, params: *const PcvRenderParams, overlay: *const PcvRenderOverlay, out: *mut *mut pcv_render) -> c_int;
     fn pcv_render_images(r: *mut pcv_render, first: u32, count: u32, rgba: *mut c_void, mem: c_int) -> c_int;
     fn pcv_render_free(r: *mut pcv_render);
+}
+
+/// pcv_ply_write_params (include/pcv_hip.h)
+#[repr(C)]
+pub struct PcvPlyWriteParams {
+    pub struct_size: u32,
+    pub open_mode: i32,
+    pub attributes: *const *const c_char,
+    pub num_attributes: u32,
+    pub reserved: u32,
+    pub chunk_points: u64,
 }
 
 pub struct HipContext(*mut pcv_ctx);
@@ -660,6 +673,45 @@ impl HipOctree {
             unsafe { pcv_query_batch_free(handle) };
         }
         result
+    }
+
+    /// The points of every query into ONE binary PLY, query after query: what a PlyNodeWriter with Encoding::Plain fed from
+    /// stream_points_for_query would write (ply.rs:559-732) — double positions, then the attributes of the FIRST query's
+    /// `attributes` list ascending by name — with the rows packed on the device and written in pieces, so no point crosses
+    /// to the host as a PointsBatch. OpenMode::Append adds to a file of the same columns. Every query must be one the library
+    /// serves (as in query_many); queries without points leave no file. Returns the number of points written.
+    pub fn write_ply(&self, queries: &[PointQuery], path: impl AsRef<Path>, open_mode: OpenMode) -> Result<u64> {
+        let served: Vec<Option<(PcvShape, Option<[f64; 2]>, Vec<u64>)>> = queries.iter().map(library_query).collect();
+        if queries.is_empty() || served.iter().any(|s| s.is_none()) {
+            return Err(ErrorKind::InvalidInput("write_ply: every query must be one the library serves".to_string()).into());
+        }
+        let shapes: Vec<PcvShape> = served.iter().flatten().map(|(s, _, _)| *s).collect();
+        let intervals: Vec<Option<[f64; 2]>> = served.iter().flatten().map(|(_, iv, _)| *iv).collect();
+        let cells: Vec<Vec<u64>> = served.iter().flatten().map(|(_, _, c)| c.clone()).collect();
+        let names: Vec<CString> = queries[0].attributes.iter().map(|a| CString::new(*a).expect("attribute name with a NUL byte")).collect();
+        let name_ptrs: Vec<*const c_char> = names.iter().map(|n| n.as_ptr()).collect();
+        let file = CString::new(path.as_ref().to_str().unwrap()).unwrap();
+        let params = PcvPlyWriteParams {
+            struct_size: std::mem::size_of::<PcvPlyWriteParams>() as u32,
+            open_mode: match open_mode {
+                OpenMode::Truncate => 0,
+                OpenMode::Append => 1,
+            },
+            attributes: name_ptrs.as_ptr(),
+            num_attributes: name_ptrs.len() as u32,
+            reserved: 0,
+            chunk_points: 0,
+        };
+        let _g = self.lock.lock().unwrap();
+        let (handle, _, _, offset) = self.run_batch(&shapes, &cells, &intervals);
+        let mut written = 0u64;
+        let rc = unsafe { pcv_query_batch_write_ply(handle, 0, offset.len() as u64 - 1, file.as_ptr(), &params, &mut written) };
+        let msg = if rc != 0 { unsafe { CStr::from_ptr(pcv_last_error(self.ctx.0)) }.to_string_lossy().into_owned() } else { String::new() };
+        unsafe { pcv_query_batch_free(handle) };
+        if rc != 0 {
+            return Err(ErrorKind::InvalidInput(format!("write_ply failed ({}): {}", rc, msg)).into());
+        }
+        Ok(written)
     }
 }
 
