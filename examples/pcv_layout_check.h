@@ -78,6 +78,15 @@ PCV_SA(offsetof(pcv_ply_write_params, struct_size) == 0 && offsetof(pcv_ply_writ
            offsetof(pcv_ply_write_params, attributes) == 8 && offsetof(pcv_ply_write_params, num_attributes) == 16 &&
            offsetof(pcv_ply_write_params, chunk_points) == 24,
        "pcv_ply_write_params fields");
+PCV_SA(sizeof(pcv_terrain_params) == 120 && offsetof(pcv_terrain_params, tile_size) == 0 && offsetof(pcv_terrain_params, statistic) == 4 &&
+           offsetof(pcv_terrain_params, resolution_m) == 8 && offsetof(pcv_terrain_params, origin) == 16 &&
+           offsetof(pcv_terrain_params, world_from_terrain) == 40 && offsetof(pcv_terrain_params, min_points) == 96 &&
+           offsetof(pcv_terrain_params, max_pool_bytes) == 104 && offsetof(pcv_terrain_params, staging_points) == 112,
+       "pcv_terrain_params");
+PCV_SA(sizeof(pcv_terrain_info) == 72 && offsetof(pcv_terrain_info, points_added) == 0 && offsetof(pcv_terrain_info, tiles) == 32 &&
+           offsetof(pcv_terrain_info, pool_bytes) == 40 && offsetof(pcv_terrain_info, vertex_min) == 48 &&
+           offsetof(pcv_terrain_info, vertex_max) == 56 && offsetof(pcv_terrain_info, finished) == 64,
+       "pcv_terrain_info");
 PCV_SA(sizeof(pcv_s2_filter) == 32 && offsetof(pcv_s2_filter, location) == 0 && offsetof(pcv_s2_filter, reserved) == 4 &&
            offsetof(pcv_s2_filter, attribute) == 8 && offsetof(pcv_s2_filter, lo) == 16 && offsetof(pcv_s2_filter, hi) == 24,
        "pcv_s2_filter");

@@ -1637,6 +1637,105 @@ int pcv_ply_append_check_host(const char* path, const char* const* names, const 
  * current figure after reading it). Either output may be NULL. */
 int pcv_ctx_pool_stats(pcv_ctx* ctx, uint64_t* live_bytes, uint64_t* peak_bytes, int reset_peak);
 
+/* ---- terrain layers -------------------------------------------------------------------- */
+/* The directory `sdl_viewer --terrain <dir>` draws (sdl_viewer/src/terrain_drawer/{read_write,layer,mod}.rs,
+ * graphic/tiled_texture_loader.rs, shaders/terrain.{vs,gs}): a sparse, tiled elevation model, per grid vertex a height, a
+ * colour and the quad adjacency mask the geometry shader ANDs over a triangle. The reference ships the reader only; the
+ * reduction from points to vertices is this library's and is stated here.
+ *   per point, in f64, nothing fused:  d = p - t;  l = M d, each row as (m_r0 d_x + m_r1 d_y) + m_r2 d_z;
+ *     u = (l_x - o_x) / res;  v = (l_y - o_y) / res;  i = floor(u + 0.5);  j = floor(v + 0.5);  h = (float)(l_z - o_z)
+ *   with M, t the 12 doubles of pcv_terrain_frame_host (terrain_from_world). The tile of vertex (i, j) is (floor(i / T),
+ *   floor(j / T)). Dropped and counted as `outside`: u, v or h not finite (or |i|, |j| >= 2^62), a vertex outside the range
+ *   declared at begin, |l_z - o_z| >= 2^21 with PCV_TERRAIN_MEAN.
+ *   count    points on the vertex; the vertex is SET iff count >= min_points
+ *   MAX/MIN  the point with the largest / smallest h in f32 total order (-0 < +0), among equal h the largest (r, g, b);
+ *            height = its h, colour = its rgb, alpha 255: independent of order, of the split over calls and of scheduling
+ *   MEAN     hq = rint((l_z - o_z) * 1024) as i64; height = (float)(((double)sum hq / (double)count) / 1024.0);
+ *            channel = (sum_c + count / 2) / count; alpha 255; all sums exact integers
+ *   unset    height 0.0f, mask 0, colour 0 0 0 0
+ *   mask     quad (qx, qy), corners (qx .. qx + 1, qy .. qy + 1), is rendered iff its four corners are set; a vertex's mask is
+ *            the OR over its up to four adjacent rendered quads of bit (qx mod 3) + 3 (qy mod 3), floor mod on GLOBAL indices,
+ *            stored as the f32 of that integer (<= 511) in the height texture's second channel. */
+#define PCV_TERRAIN_MAX 0
+#define PCV_TERRAIN_MIN 1
+#define PCV_TERRAIN_MEAN 2
+typedef struct pcv_terrain_params {
+  uint32_t tile_size;           /* T, 1 ..= 4096 vertices per tile edge */
+  uint32_t statistic;           /* PCV_TERRAIN_MAX / _MIN / _MEAN */
+  double resolution_m;          /* > 0 */
+  double origin[3];             /* the grid origin, in the terrain frame */
+  double world_from_terrain[7]; /* Isometry3: translation xyz, unit quaternion ijkw (as pcv_xray_params.query_from_global) */
+  uint32_t min_points;          /* >= 1 */
+  uint32_t reserved;
+  uint64_t max_pool_bytes;      /* cap on the per-vertex storage of the touched tiles; 0: 2 GiB */
+  uint64_t staging_points;      /* points per piece of the two query adders; 0: 2^22 */
+} pcv_terrain_params;
+typedef struct pcv_terrain_info {
+  uint64_t points_added;   /* every point handed in, dropped ones included */
+  uint64_t outside;        /* the dropped ones */
+  uint64_t set_vertices;   /* after finish */
+  uint64_t rendered_quads; /* after finish */
+  uint64_t tiles;          /* after finish: tiles with a set vertex; before: tiles touched so far */
+  uint64_t pool_bytes;     /* per-vertex storage held for the touched tiles */
+  int32_t vertex_min[2], vertex_max[2]; /* the declared range when it fits i32 (else saturated) */
+  uint32_t finished, reserved;
+} pcv_terrain_info;
+typedef struct pcv_terrain pcv_terrain;
+/* The world box's eight corners go through the chain; the vertex range is their (i, j) hull widened by one vertex, the
+ * tile-slot table is dense over the range's tiles. PCV_E_INVALID: what pcv_terrain_check_params_host refuses, a box with a
+ * non-finite corner, tile positions outside i32, more than 2^22 tiles in the range. Per-vertex storage is allocated for the
+ * tiles a point touches only. */
+int pcv_terrain_begin(pcv_ctx* ctx, const pcv_terrain_params* params, const double bbox_min[3], const double bbox_max[3], pcv_terrain** out);
+/* n points: f64 planes and 3-byte colours that live where `mem` says. More than 2^32 - 1 points in total is PCV_E_INVALID
+ * (nothing of the call is added). Touched tiles that would take the storage past max_pool_bytes are PCV_E_OOM: everything
+ * the terrain holds on the device is released, and the handle can only be freed. */
+int pcv_terrain_add_points(pcv_terrain* t, uint64_t n, const double* x, const double* y, const double* z, const uint8_t* rgb, int mem);
+/* The points of segments [first_segment, first_segment + num_segments) of a query result, pulled into a device staging
+ * buffer piece by piece: a piece is at most staging_points rows of the result, cut at any row — neither a segment nor a chunk
+ * of the query sets its size — packed by the PLY output's packer (pcv_*_ply_rows' kernels) as x y z r g b rows and spread into
+ * planes, so the staging costs O(staging_points) (54 bytes per point) whatever the result's size. The result's bytes do not
+ * depend on the pieces. */
+int pcv_terrain_add_query_batch(pcv_terrain* t, pcv_query_batch* batch, uint64_t first_segment, uint64_t num_segments);
+int pcv_terrain_add_s2_query(pcv_terrain* t, pcv_s2_query* query, uint64_t first_segment, uint64_t num_segments);
+/* Resolves the vertices, runs the mask pass (it reads set flags through the tile table: a vertex on a tile edge depends on up
+ * to three other tiles) and keeps the tiles with a set vertex on the device, ascending by (x, y). No points after it. A finish
+ * that fails releases everything the terrain holds on the device, and the handle can only be freed. */
+int pcv_terrain_finish(pcv_terrain* t);
+int pcv_terrain_info_get(const pcv_terrain* t, pcv_terrain_info* out);
+/* After finish. positions: 2 x i32 per tile (host). heights: tiles x T x T x 2 f32 (height, mask); colors: tiles x T x T x 4
+ * u8; counts: tiles x T x T u32; row = j mod T, column = i mod T (ImageBuffer's row-major layout), into memory that lives
+ * where `mem` says. A range past the end is PCV_E_INVALID and writes nothing. */
+int pcv_terrain_tiles(const pcv_terrain* t, uint64_t capacity, int32_t* positions, uint64_t* num_tiles);
+int pcv_terrain_heights(pcv_terrain* t, uint64_t first_tile, uint64_t num_tiles, int mem, float* out);
+int pcv_terrain_colors(pcv_terrain* t, uint64_t first_tile, uint64_t num_tiles, int mem, uint8_t* out);
+int pcv_terrain_counts(pcv_terrain* t, uint64_t first_tile, uint64_t num_tiles, int mem, uint32_t* out);
+/* x{:08}_y{:08}.height (T T 2 little-endian f32) and .color (T T 4 bytes) per tile, the sign counting toward the width as in
+ * Rust's formatting of an i32, and meta.json (pcv_terrain_meta_json_host); the files are written by the context's host
+ * threads. A terrain without a set vertex writes meta.json with an empty tile list only. PCV_E_IO names the file. */
+int pcv_terrain_write_dir(pcv_terrain* t, const char* directory);
+void pcv_terrain_free(pcv_terrain* t);
+/* Host only, no context (messages: pcv_host_last_error). PCV_E_INVALID: tile_size 0 or above 4096, resolution_m <= 0 or not
+ * finite, a non-finite origin or translation, a quaternion whose squared norm is further than 1e-9 from 1, min_points 0, an
+ * unknown statistic. */
+int pcv_terrain_check_params_host(const pcv_terrain_params* params);
+/* terrain_from_world as 12 doubles: the rotation rows m00 m01 m02 m10 .. m22, then t (= the translation of
+ * world_from_terrain): l = M (p - t). The formula is in DESIGN §9g; matrices of 90-degree turns come out in {0, +-1}. */
+int pcv_terrain_frame_host(const pcv_terrain_params* params, double frame[12]);
+/* The chain for n points: i, j (0 where ok is 0), h, and ok[k] = 1 iff u, v, h are finite and |i|, |j| < 2^62. Any output
+ * may be NULL. Neither the declared range nor MEAN's height bound is applied. */
+int pcv_terrain_vertex_host(const pcv_terrain_params* params, uint64_t n, const double* x, const double* y, const double* z,
+                            int64_t* i, int64_t* j, float* h, uint8_t* ok);
+/* A set bitmap (w x h bytes, row = j - j0, column = i - i0, nonzero = set; everything outside the window unset) into the
+ * masks of its vertices (w x h u32). */
+int pcv_terrain_quad_masks_host(int64_t i0, int64_t j0, uint32_t w, uint32_t h, const uint8_t* set, uint32_t* masks);
+/* "x{:08}_y{:08}" for a tile position, NUL-terminated (at most 23 bytes with it). */
+int pcv_terrain_tile_name_host(int32_t x, int32_t y, char* buf, uint64_t cap);
+/* meta.json: {"tile_size":T,"world_from_terrain":{"rotation":[i,j,k,w],"translation":[x,y,z]},"origin":[x,y,z],
+ * "resolution_m":r,"tile_positions":[[x,y],...]} — every f64 with the fewest of 15, 16 or 17 significant digits that parse
+ * back to the same double, integral values with ".0". *len its length, the first min(cap, *len) bytes into buf. */
+int pcv_terrain_meta_json_host(const pcv_terrain_params* params, uint64_t num_tiles, const int32_t* positions, char* buf, uint64_t cap,
+                               uint64_t* len);
+
 /* Host only: which arm PointCloudClientBuilder::build (point_cloud_client/src/lib.rs:107-132) would take for this
  * directory's meta.pb: `version <= 11 || has_octree()` is PCV_CLOUD_OCTREE, anything else PCV_CLOUD_S2. The reference
  * opens every location as the first one's kind; the entry points here take one kind each, and the caller decides. A missing

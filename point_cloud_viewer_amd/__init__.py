@@ -12,6 +12,8 @@ from .octree import (Aabb, Context, OctreeResult, QueryBatch, RenderedViews, S2C
                      s2_open_host, s2_union_normalize, S2Stream, s2_merge_plan, s2_filter_keep, s2_check_attributes,
                      level_shortcuts, level_table, node_name, quadtree_node_id, quadtree_node_name, read_ply,
                      ply_append_check, ply_header, ply_layout,
+                     Terrain, build_terrain, read_terrain, terrain_check_params, terrain_frame, terrain_meta_json, terrain_params,
+                     terrain_quad_masks, terrain_tile_name, terrain_vertex,
                      render_check_overlay, render_check_params, render_gamma_lut, render_overlay, render_params,
                      web_mercator_rect_from_zoomed, wmr_contains, wmr_corners, wmr_from_lat_lng, wmr_math, wmr_project, wmr_to_lat_lng,
                      inpaint_xray_quadtree, merge_xray_quadtrees, png_decode, xray_check_params, xray_coloring, xray_finalize, xray_lanczos_taps, xray_leaf_tiles,

@@ -202,6 +202,21 @@ class PlyWriteParams(C.Structure):  # pcv_ply_write_params
                 ("reserved", C.c_uint32), ("chunk_points", C.c_uint64)]
 
 
+TERRAIN_STATISTICS = {"max": 0, "min": 1, "mean": 2}  # PCV_TERRAIN_MAX / _MIN / _MEAN
+
+
+class TerrainParams(C.Structure):  # pcv_terrain_params
+    _fields_ = [("tile_size", C.c_uint32), ("statistic", C.c_uint32), ("resolution_m", C.c_double), ("origin", C.c_double * 3),
+                ("world_from_terrain", C.c_double * 7), ("min_points", C.c_uint32), ("reserved", C.c_uint32), ("max_pool_bytes", C.c_uint64),
+                ("staging_points", C.c_uint64)]
+
+
+class TerrainInfo(C.Structure):  # pcv_terrain_info
+    _fields_ = [("points_added", C.c_uint64), ("outside", C.c_uint64), ("set_vertices", C.c_uint64), ("rendered_quads", C.c_uint64),
+                ("tiles", C.c_uint64), ("pool_bytes", C.c_uint64), ("vertex_min", C.c_int32 * 2), ("vertex_max", C.c_int32 * 2),
+                ("finished", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class OocStats(C.Structure):
     _fields_ = [("points", C.c_uint64), ("nodes", C.c_uint64), ("partitions", C.c_uint64), ("largest_bucket", C.c_uint64),
                 ("spill_bytes", C.c_uint64), ("h2d_bytes", C.c_uint64), ("d2h_bytes", C.c_uint64), ("h2d_ms", C.c_double),
@@ -443,6 +458,24 @@ _SIGNATURES = {
     "pcv_ply_header_host": (C.c_int, [C.POINTER(C.c_char_p), _vp, C.c_uint32, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pcv_ply_append_check_host": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), _vp, C.c_uint32, C.POINTER(C.c_uint64)]),
     "pcv_ctx_pool_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
+    "pcv_terrain_begin": (C.c_int, [_vp, C.POINTER(TerrainParams), _vp, _vp, C.POINTER(_vp)]),
+    "pcv_terrain_add_points": (C.c_int, [_vp, C.c_uint64, _vp, _vp, _vp, _vp, C.c_int]),
+    "pcv_terrain_add_query_batch": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
+    "pcv_terrain_add_s2_query": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
+    "pcv_terrain_finish": (C.c_int, [_vp]),
+    "pcv_terrain_info_get": (C.c_int, [_vp, C.POINTER(TerrainInfo)]),
+    "pcv_terrain_tiles": (C.c_int, [_vp, C.c_uint64, _vp, C.POINTER(C.c_uint64)]),
+    "pcv_terrain_heights": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_int, _vp]),
+    "pcv_terrain_colors": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_int, _vp]),
+    "pcv_terrain_counts": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_int, _vp]),
+    "pcv_terrain_write_dir": (C.c_int, [_vp, C.c_char_p]),
+    "pcv_terrain_free": (None, [_vp]),
+    "pcv_terrain_check_params_host": (C.c_int, [C.POINTER(TerrainParams)]),
+    "pcv_terrain_frame_host": (C.c_int, [C.POINTER(TerrainParams), _vp]),
+    "pcv_terrain_vertex_host": (C.c_int, [C.POINTER(TerrainParams), C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pcv_terrain_quad_masks_host": (C.c_int, [C.c_int64, C.c_int64, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "pcv_terrain_tile_name_host": (C.c_int, [C.c_int32, C.c_int32, C.c_char_p, C.c_uint64]),
+    "pcv_terrain_meta_json_host": (C.c_int, [C.POINTER(TerrainParams), C.c_uint64, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

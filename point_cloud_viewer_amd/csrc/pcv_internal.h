@@ -122,6 +122,12 @@ enum PcvKernelId {
   PCV_K_S2_ATTR_FILTER,       // pcv_s2_attr.hip: keep flags ANDed with one extra's interval test, over the chunks that filter on it
   PCV_K_S2_ATTR_GATHER_POINTS,  // pcv_s2_attr.hip: one extra's values of the kept points of a segment range
   PCV_K_PLY_ROWS,             // pcv_ply_rows.hip: the kept points of a row range packed as PLY rows (octree batch or S2 query)
+  PCV_K_TERRAIN_MARK,         // pcv_terrain.hip: a slot for every tile that a point of the call touches for the first time
+  PCV_K_TERRAIN_ACCUM,        // pcv_terrain.hip: one thread per point, the chain, the vertex's atomics (max / min key or exact sums, count)
+  PCV_K_TERRAIN_UNPACK,       // pcv_terrain.hip: packed x y z r g b rows of a query result's piece into the staging planes
+  PCV_K_TERRAIN_COUNT,        // pcv_terrain.hip: set vertices per touched tile
+  PCV_K_TERRAIN_RESOLVE,      // pcv_terrain.hip: accumulators -> height, colour, count of the kept tiles
+  PCV_K_TERRAIN_MASK,         // pcv_terrain.hip: quad masks from the set flags of each vertex's neighbourhood, across tile seams
   PCV_K_COUNT
 };
 
@@ -646,6 +652,12 @@ int pcv_octree_fetch_host(pcv_octree* t);
 int pcv_octree_load_device(pcv_octree* t);  // directory octrees: read + upload all node files (pcv_io.cpp)
 int pcv_octree_read_node_file(pcv_octree* t, uint64_t i, int which, const uint8_t** data, uint64_t* len);
 // (pcv_make_levels and pcv_bytes_per_coordinate: pcv_levels.h)
+
+// pcv_ply_rows.hip — a row range of a query result (an octree batch or an S2 query, the other null) packed as rows of x y z
+// (doubles) and r g b on the context's stream: the packer of the PLY output, for callers that stream a result piece by piece
+constexpr uint32_t kPcvXyzRgbRowBytes = 27;
+int pcv_ply_pack_xyz_rgb(pcv_query_batch* b, pcv_s2_query* q, uint64_t first_segment, uint64_t num_segments, uint64_t row0, uint64_t nrows,
+                         uint8_t* d_out);
 
 // A failure of a call that has no context to keep the message (pcv_png.cpp): kept per thread for pcv_host_last_error.
 int pcv_host_fail(int code, const std::string& msg);

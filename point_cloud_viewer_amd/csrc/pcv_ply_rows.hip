@@ -424,6 +424,26 @@ int write_ply(const PlySource& s, uint64_t first_segment, uint64_t num_segments,
 
 }  // namespace
 
+// pcv_internal.h: rows [row0, row0 + nrows) of the result's segments [first_segment, first_segment + num_segments) as 27-byte rows
+// (x y z as doubles, then r g b) into d_out on the context's stream, nothing waited for — any row range, for callers that
+// stream a result through a bounded buffer (pcv_terrain.hip). Exactly one of b / q is set.
+int pcv_ply_pack_xyz_rgb(pcv_query_batch* b, pcv_s2_query* q, uint64_t first_segment, uint64_t num_segments, uint64_t row0, uint64_t nrows,
+                         uint8_t* d_out) {
+  const PlySource s = b ? source_of(b) : source_of(q);
+  int rc;
+  if ((rc = check_range(s, first_segment, num_segments))) return rc;
+  const uint64_t p0 = s.seg_off[first_segment], p1 = s.seg_off[first_segment + num_segments];
+  if (row0 < p0 || row0 > p1 || nrows > p1 - row0) return s.ctx->fail(PCV_E_INVALID, "row range outside the segments");
+  if (nrows == 0) return PCV_OK;
+  static const char* const kColor[] = {"color"};
+  std::vector<PcvPlyColumn> cols;
+  uint32_t stride = 0;
+  PlyCols dev{};
+  if ((rc = resolve_columns(s, kColor, 1, &cols, &stride, &dev))) return rc;
+  if (stride != kPcvXyzRgbRowBytes) return s.ctx->fail(PCV_E_INVALID, "unexpected row layout");
+  return launch_rows(s, dev, s.seg_chunk[first_segment], s.seg_chunk[first_segment + num_segments], row0, nrows, d_out);
+}
+
 extern "C" int pcv_query_batch_ply_rows(pcv_query_batch* b, uint64_t first_segment, uint64_t num_segments, const char* const* attributes,
                                         uint32_t num_attributes, uint64_t capacity_bytes, int mem, void* out, uint32_t* stride,
                                         uint64_t* num_rows) {

@@ -223,6 +223,16 @@ class Context:
         if rc != L.PCV_OK:
             raise L.PcvError(rc, self.lib.pcv_last_error(self.handle).decode())
 
+    def terrain_begin(self, bbox_min, bbox_max, **params):
+        """An empty Terrain over the world box (pcv_terrain_begin); params: terrain_params' arguments, or params=a
+        TerrainParams."""
+        pr = params["params"] if "params" in params else terrain_params(**params)
+        lo = (C.c_double * 3)(*[float(v) for v in bbox_min])
+        hi = (C.c_double * 3)(*[float(v) for v in bbox_max])
+        h = C.c_void_p()
+        self._check(self.lib.pcv_terrain_begin(self.handle, C.byref(pr), lo, hi, C.byref(h)))
+        return Terrain(self, h, pr)
+
     def _points(self, x, y, z, color=None, intensity=None):
         bx, by, bz = _Buf(x, np.float64, "x"), _Buf(y, np.float64, "y"), _Buf(z, np.float64, "z")
         bc = _Buf(color, np.uint8, "color")
@@ -1200,6 +1210,11 @@ class OctreeResult:
         self.ctx._check(self.lib.pcv_query_batch_run(self.ctx.handle, shapes.handle, self.handle, iv, used, C.byref(h)))
         return QueryBatch(self, h, shapes.count)
 
+    def terrain(self, shapes=None, **params):
+        """A finished Terrain of the points `shapes` select (None: all points): one batched query, its segments
+        streamed into the grid on the device. params: terrain_params' arguments."""
+        return _cloud_terrain(self, shapes, params)
+
     def xray_tiles(self, tile_size_px=256, pixel_size_m=None, strategy="xray", query_from_global=None, intensity_interval=None,
                    background="white", root_node_id="r", max_workspace_bytes=None, min_intensity=0.0, max_intensity=1.0,
                    binning=None):
@@ -1468,6 +1483,20 @@ class QueryBatch:
             if n:
                 out[i] = n
         return out
+
+    def terrain(self, shape=None, bbox_min=None, bbox_max=None, **params):
+        """A finished Terrain of this result's points (of shape `shape`, or of all of them): terrain_params' arguments; the
+        box defaults to the cloud's."""
+        self._live()
+        if bbox_min is None or bbox_max is None:
+            bbox_min, bbox_max = _cloud_bbox(self.tree)
+        t = self.ctx.terrain_begin(bbox_min, bbox_max, **params)
+        try:
+            t.add(self, shape=shape)
+            return t.finish()
+        except Exception:
+            t.free()
+            raise
 
     def free(self):
         if self.handle and self.ctx.handle:
@@ -2547,6 +2576,11 @@ class S2Cloud:
                                                           first.ctypes.data, flat.ctypes.data, capacity, counts.ctypes.data, out.ctypes.data))
         return [out[l, :counts[l]].copy() for l in range(locations)]
 
+    def terrain(self, shapes=None, **params):
+        """A finished Terrain of the points `shapes` select (None: all points), as OctreeResult.terrain."""
+        self._alive()
+        return _cloud_terrain(self, shapes, params)
+
     def query_batch(self, shapes=None, unions=None, intervals=None, filters=None):
         """The points of every location of one call (pcv_s2_query_run): the prepared `shapes`, then `unions`; intervals: None,
         or one entry per location, None or (lo, hi) on intensity. filters (pcv_s2_query_run_ex): None, or one entry per
@@ -2891,6 +2925,280 @@ def s2_open_host(directory):
     h = C.c_void_p()
     _host_check(L.load_library().pcv_s2_open_dir(None, os.fsencode(str(directory)), C.byref(h)), "pcv_s2_open_dir")
     return S2Cloud(None, h)
+
+
+# ---- terrain layers (pcv_terrain_*) ----
+def terrain_params(tile_size=256, resolution_m=None, origin=(0.0, 0.0, 0.0), world_from_terrain=None, statistic="max", min_points=1,
+                   max_pool_bytes=None, staging_points=0):
+    """pcv_terrain_params. world_from_terrain: None (identity) or translation xyz + unit quaternion ijkw; statistic: "max" |
+    "min" | "mean" (or the number); max_pool_bytes None: the default of 2 GiB. Nothing is checked here: the library does."""
+    if resolution_m is None:
+        raise ValueError("resolution_m is required")
+    pr = L.TerrainParams()
+    pr.tile_size = int(tile_size)
+    pr.statistic = L.TERRAIN_STATISTICS[statistic] if isinstance(statistic, str) else int(statistic)
+    pr.resolution_m = float(resolution_m)
+    iso = [0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0] if world_from_terrain is None else [float(v) for v in world_from_terrain]
+    if len(iso) != 7 or len(origin) != 3:
+        raise ValueError("world_from_terrain: translation xyz + quaternion ijkw (7 numbers); origin: 3 numbers")
+    for a in range(3):
+        pr.origin[a] = float(origin[a])
+    for a in range(7):
+        pr.world_from_terrain[a] = iso[a]
+    pr.min_points, pr.reserved = int(min_points), 0
+    pr.max_pool_bytes = 0 if max_pool_bytes is None else int(max_pool_bytes)
+    pr.staging_points = int(staging_points)
+    return pr
+
+
+def _terrain_pr(params):
+    return params if isinstance(params, L.TerrainParams) else terrain_params(**params)
+
+
+def terrain_check_params(params):
+    """pcv_terrain_check_params_host: raises PcvError with the rule that is broken."""
+    _host_check(L.load_library().pcv_terrain_check_params_host(C.byref(_terrain_pr(params))), "pcv_terrain_check_params_host")
+
+
+def terrain_frame(params):
+    """terrain_from_world as (M [3, 3], t [3]): l = M (p - t) (pcv_terrain_frame_host)."""
+    out = np.zeros(12)
+    _host_check(L.load_library().pcv_terrain_frame_host(C.byref(_terrain_pr(params)), out.ctypes.data), "pcv_terrain_frame_host")
+    return out[:9].reshape(3, 3).copy(), out[9:].copy()
+
+
+def terrain_vertex(params, x, y, z):
+    """The grid chain on the host (pcv_terrain_vertex_host), the kernels' twin: (i, j as int64, h as float32, ok as bool)."""
+    x, y, z = (np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (x, y, z))
+    n = x.size
+    if y.size != n or z.size != n:
+        raise ValueError("x, y, z must have the same length")
+    i, j = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    h, ok = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.uint8)
+    _host_check(L.load_library().pcv_terrain_vertex_host(C.byref(_terrain_pr(params)), n, x.ctypes.data, y.ctypes.data, z.ctypes.data,
+                                                         i.ctypes.data, j.ctypes.data, h.ctypes.data, ok.ctypes.data), "pcv_terrain_vertex_host")
+    return i, j, h, ok.astype(bool)
+
+
+def terrain_quad_masks(is_set, i0=0, j0=0):
+    """The quad masks (uint32 [h, w]) of a window of set flags [h, w] (row = j - j0, column = i - i0) whose first vertex is
+    (i0, j0); nothing outside the window is set (pcv_terrain_quad_masks_host)."""
+    flags = np.ascontiguousarray(np.asarray(is_set) != 0, dtype=np.uint8)
+    if flags.ndim != 2:
+        raise ValueError("is_set: a 2-D array")
+    out = np.zeros(flags.shape, dtype=np.uint32)
+    _host_check(L.load_library().pcv_terrain_quad_masks_host(int(i0), int(j0), flags.shape[1], flags.shape[0], flags.ctypes.data,
+                                                             out.ctypes.data), "pcv_terrain_quad_masks_host")
+    return out
+
+
+def terrain_tile_name(x, y):
+    """'x{:08}_y{:08}' of a tile position, the sign counting toward the width (pcv_terrain_tile_name_host)."""
+    buf = C.create_string_buffer(32)
+    _host_check(L.load_library().pcv_terrain_tile_name_host(int(x), int(y), buf, 32), "pcv_terrain_tile_name_host")
+    return buf.value.decode()
+
+
+def terrain_meta_json(params, tile_positions=()):
+    """The text of meta.json (pcv_terrain_meta_json_host)."""
+    pos = np.ascontiguousarray(np.asarray(tile_positions, dtype=np.int32).reshape(-1, 2))
+    lib, pr, n = L.load_library(), _terrain_pr(params), C.c_uint64()
+    _host_check(lib.pcv_terrain_meta_json_host(C.byref(pr), pos.shape[0], pos.ctypes.data, None, 0, C.byref(n)), "pcv_terrain_meta_json_host")
+    buf = C.create_string_buffer(n.value + 1)
+    _host_check(lib.pcv_terrain_meta_json_host(C.byref(pr), pos.shape[0], pos.ctypes.data, buf, n.value, C.byref(n)), "pcv_terrain_meta_json_host")
+    return buf.raw[:n.value].decode()
+
+
+def read_terrain(directory):
+    """A terrain directory as the viewer's reader takes it (terrain_drawer/read_write.rs), in pure Python: dict(tile_size,
+    world_from_terrain [7: translation xyz, quaternion ijkw], origin, resolution_m, tiles int32 [n, 2], heights float32
+    [n, T, T, 2] (height, quad mask), colors uint8 [n, T, T, 4])."""
+    import json
+    with open(os.path.join(str(directory), "meta.json")) as f:
+        meta = json.load(f)
+    T = int(meta["tile_size"])
+    tiles = np.asarray(meta["tile_positions"], dtype=np.int32).reshape(-1, 2)
+    heights = np.zeros((tiles.shape[0], T, T, 2), dtype=np.float32)
+    colors = np.zeros((tiles.shape[0], T, T, 4), dtype=np.uint8)
+    for k, (x, y) in enumerate(tiles):
+        name = os.path.join(str(directory), f"x{int(x):08d}_y{int(y):08d}")
+        h = np.fromfile(name + ".height", dtype="<f4")
+        c = np.fromfile(name + ".color", dtype=np.uint8)
+        if h.size != T * T * 2 or c.size != T * T * 4:
+            raise L.PcvError(L.PCV_E_IO, f"{name}: a tile of {T} x {T} vertices has {T * T * 8} height and {T * T * 4} colour bytes")
+        heights[k], colors[k] = h.reshape(T, T, 2), c.reshape(T, T, 4)
+    iso = meta["world_from_terrain"]
+    return dict(tile_size=T, world_from_terrain=np.array(list(iso["translation"]) + list(iso["rotation"]), dtype=np.float64),
+                origin=np.array(meta["origin"], dtype=np.float64), resolution_m=float(meta["resolution_m"]), tiles=tiles,
+                heights=heights, colors=colors)
+
+
+class Terrain:
+    """One pcv_terrain: points in (add_points / add), finish, then the tiles with a set vertex — ascending by (x, y) — as
+    arrays or as the directory sdl_viewer --terrain reads."""
+
+    def __init__(self, ctx, handle, params):
+        self.ctx, self.lib, self.handle, self.params = ctx, ctx.lib, handle, params
+        self.tile_size = int(params.tile_size)
+        ctx._children.add(self)
+
+    def _live(self):
+        if not self.handle or not self.ctx.handle:
+            raise L.PcvError(L.PCV_E_INVALID, "the terrain was freed")
+
+    def add_points(self, x, y, z, rgb):
+        """f64 planes and 3-byte colours, numpy arrays or torch device tensors (pcv_terrain_add_points)."""
+        self._live()
+        bufs = [_Buf(x, np.float64, "x"), _Buf(y, np.float64, "y"), _Buf(z, np.float64, "z"), _Buf(rgb, np.uint8, "rgb")]
+        n = bufs[0].size
+        if bufs[1].size != n or bufs[2].size != n or bufs[3].size != 3 * n:
+            raise ValueError("x, y, z of n points and rgb of 3 n bytes")
+        if len({b.device for b in bufs}) != 1:
+            raise ValueError("all point arrays must live in the same memory space")
+        if bufs[0].device:
+            self.ctx.wait_torch()
+        self.ctx._check(self.lib.pcv_terrain_add_points(self.handle, n, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr,
+                                                        L.MEM_DEVICE if bufs[0].device else L.MEM_HOST))
+        return self
+
+    def add(self, batch, shape=None, first_segment=0, num_segments=None):
+        """The points of a QueryBatch or S2QueryBatch: of shape `shape`, or of a segment range (default: all), pulled through
+        a bounded staging buffer on the device (pcv_terrain_add_query_batch / pcv_terrain_add_s2_query)."""
+        self._live()
+        batch._live()
+        first, num = batch._ply_range(shape, first_segment, num_segments)
+        fn = self.lib.pcv_terrain_add_s2_query if isinstance(batch, S2QueryBatch) else self.lib.pcv_terrain_add_query_batch
+        self.ctx._check(fn(self.handle, batch.handle, first, num))
+        return self
+
+    def finish(self):
+        self._live()
+        self.ctx._check(self.lib.pcv_terrain_finish(self.handle))
+        return self
+
+    def info(self):
+        self._live()
+        inf = L.TerrainInfo()
+        self.ctx._check(self.lib.pcv_terrain_info_get(self.handle, C.byref(inf)))
+        return dict(points_added=inf.points_added, outside=inf.outside, set_vertices=inf.set_vertices, rendered_quads=inf.rendered_quads,
+                    tiles=inf.tiles, pool_bytes=inf.pool_bytes, vertex_min=tuple(inf.vertex_min), vertex_max=tuple(inf.vertex_max),
+                    finished=bool(inf.finished))
+
+    def tiles(self):
+        """Tile positions, int32 [n, 2], ascending by (x, y)."""
+        self._live()
+        n = C.c_uint64()
+        self.ctx._check(self.lib.pcv_terrain_tiles(self.handle, 0, None, C.byref(n)))
+        out = np.zeros((n.value, 2), dtype=np.int32)
+        self.ctx._check(self.lib.pcv_terrain_tiles(self.handle, n.value, out.ctypes.data, C.byref(n)))
+        return out
+
+    def _plane(self, fn, first_tile, num_tiles, tail, dtype, device):
+        self._live()
+        n = C.c_uint64()
+        self.ctx._check(self.lib.pcv_terrain_tiles(self.handle, 0, None, C.byref(n)))
+        first = int(first_tile)
+        num = max(n.value - first, 0) if num_tiles is None else int(num_tiles)
+        T = self.tile_size
+        if not (0 <= first <= n.value and 0 <= num <= n.value - first):
+            raise L.PcvError(L.PCV_E_INVALID, f"tile range past the end: tiles [{first}, {first + num}) of {n.value}")
+        if device:
+            import torch
+            out = torch.empty((num, T, T) + tail, dtype=getattr(torch, np.dtype(dtype).name), device=f"cuda:{self.ctx.device}")
+            self.ctx.wait_torch()
+            ptr, mem = out.data_ptr(), L.MEM_DEVICE
+        else:
+            out = np.zeros((num, T, T) + tail, dtype=dtype)
+            ptr, mem = out.ctypes.data, L.MEM_HOST
+        if num:
+            self.ctx._check(fn(self.handle, first, num, mem, ptr))
+        return out
+
+    def heights(self, first_tile=0, num_tiles=None, device=False):
+        """float32 [n, T, T, 2]: height and quad mask; row = j mod T, column = i mod T."""
+        return self._plane(self.lib.pcv_terrain_heights, first_tile, num_tiles, (2,), np.float32, device)
+
+    def colors(self, first_tile=0, num_tiles=None, device=False):
+        """uint8 [n, T, T, 4]: r g b 255 of a set vertex, zeros of an unset one."""
+        return self._plane(self.lib.pcv_terrain_colors, first_tile, num_tiles, (4,), np.uint8, device)
+
+    def counts(self, first_tile=0, num_tiles=None, device=False):
+        """[n, T, T] points per vertex (uint32; int32 bits on the device, torch having no uint32 everywhere)."""
+        return self._plane(self.lib.pcv_terrain_counts, first_tile, num_tiles, (), np.int32 if device else np.uint32, device)
+
+    def write(self, directory):
+        """The directory sdl_viewer --terrain reads: meta.json and x{:08}_y{:08}.height / .color per tile."""
+        self._live()
+        self.ctx._check(self.lib.pcv_terrain_write_dir(self.handle, os.fsencode(str(directory))))
+
+    def free(self):
+        if self.handle and self.ctx.handle:
+            self.lib.pcv_terrain_free(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _cloud_bbox(cloud):
+    if isinstance(cloud, S2Cloud):
+        return cloud.bbox_min, cloud.bbox_max
+    m = cloud.meta()
+    return m["bbox_min"], m["bbox_max"]
+
+
+def _cloud_terrain(cloud, shapes, params, into=None):
+    """The points `shapes` select from an octree or an S2 cloud (None: all) into `into`, or into a new finished Terrain."""
+    ctx = cloud.ctx
+    own = shapes is None
+    if own:
+        shapes = ctx.shapes([("all",)])
+    batch = t = None
+    try:
+        batch = cloud.query_batch(shapes)
+        t = into if into is not None else ctx.terrain_begin(*_cloud_bbox(cloud), **params)
+        t.add(batch)
+        return t if into is not None else t.finish()
+    except Exception:
+        if t is not None and into is None:
+            t.free()
+        raise
+    finally:
+        if batch is not None:
+            batch.free()
+        if own:
+            shapes.free()
+
+
+def build_terrain(ctx, point_cloud_locations, output_directory, **params):
+    """A terrain directory from cloud directories: the kind of the first one (cloud_kind) decides, every directory is opened
+    as that kind, all their points go into one grid over the union of their boxes, and the layer is written to
+    output_directory. params: terrain_params' arguments. Returns the finished Terrain."""
+    locations = list(point_cloud_locations)
+    if not locations:
+        raise ValueError("No locations specified for point cloud client.")
+    opener = ctx.s2_open if cloud_kind(locations[0]) == "s2" else ctx.open_dir
+    clouds = [opener(d) for d in locations]
+    t = None
+    try:
+        boxes = [_cloud_bbox(c) for c in clouds]
+        lo, hi = np.min([b[0] for b in boxes], axis=0), np.max([b[1] for b in boxes], axis=0)
+        t = ctx.terrain_begin(lo, hi, **params)
+        for c in clouds:
+            _cloud_terrain(c, None, params, into=t)
+        t.finish()
+        t.write(output_directory)
+        return t
+    except Exception:
+        if t is not None:
+            t.free()
+        raise
+    finally:
+        for c in clouds:
+            c.free()
 
 
 def cloud_kind(directory):

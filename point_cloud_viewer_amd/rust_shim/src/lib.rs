@@ -75,6 +75,8 @@ type pcv_ooc = c_void;
 #[allow(non_camel_case_types)]
 type pcv_query_batch = c_void;
 #[allow(non_camel_case_types)]
+type pcv_terrain = c_void;
+#[allow(non_camel_case_types)]
 type pcv_render = c_void;
 
 /// include/pcv_hip.h pcv_render_params: one frame of the viewer (sdl_viewer/src/lib.rs:158-209).
@@ -161,6 +163,12 @@ extern "C" {
     fn pcv_query_batch_free(b: *mut pcv_query_batch);
     // PlyNodeWriter over a query's result (ply.rs:559-732): the rows packed on the device, the file written in pieces
     fn pcv_query_batch_write_ply(b: *mut pcv_query_batch, first_segment: u64, num_segments: u64, path: *const c_char, params: *const PcvPlyWriteParams, written: *mut u64) -> c_int;
+    // terrain layers: a query's result reduced to grid vertices on the device, the directory sdl_viewer --terrain reads
+    fn pcv_terrain_begin(ctx: *mut pcv_ctx, params: *const PcvTerrainParams, bbox_min: *const c_double, bbox_max: *const c_double, out: *mut *mut pcv_terrain) -> c_int;
+    fn pcv_terrain_add_query_batch(t: *mut pcv_terrain, b: *mut pcv_query_batch, first_segment: u64, num_segments: u64) -> c_int;
+    fn pcv_terrain_finish(t: *mut pcv_terrain) -> c_int;
+    fn pcv_terrain_write_dir(t: *mut pcv_terrain, directory: *const c_char) -> c_int;
+    fn pcv_terrain_free(t: *mut pcv_terrain);
     // the viewer's frame: get_visible_nodes + GL_POINTS under a depth test, rasterised on the device
     fn pcv_s2_open_dir(ctx: *mut pcv_ctx, directory: *const c_char, out: *mut *mut pcv_s2_cloud) -> c_int;
     fn pcv_s2_info(c: *const pcv_s2_cloud, num_cells: *mut u64, num_points: *mut u64, bbox_min: *mut c_double, bbox_max: *mut c_double, has_intensity: *mut c_int, level: *mut u32) -> c_int;
@@ -187,6 +195,20 @@ pub struct PcvPlyWriteParams {
     pub num_attributes: u32,
     pub reserved: u32,
     pub chunk_points: u64,
+}
+
+/// pcv_terrain_params (include/pcv_hip.h); statistic: 0 max, 1 min, 2 mean
+#[repr(C)]
+pub struct PcvTerrainParams {
+    pub tile_size: u32,
+    pub statistic: u32,
+    pub resolution_m: f64,
+    pub origin: [f64; 3],
+    pub world_from_terrain: [f64; 7],
+    pub min_points: u32,
+    pub reserved: u32,
+    pub max_pool_bytes: u64,
+    pub staging_points: u64,
 }
 
 pub struct HipContext(*mut pcv_ctx);
@@ -712,6 +734,46 @@ impl HipOctree {
             return Err(ErrorKind::InvalidInput(format!("write_ply failed ({}): {}", rc, msg)).into());
         }
         Ok(written)
+    }
+}
+
+impl HipOctree {
+    /// The terrain layer `sdl_viewer --terrain <dir>` reads, of the points `queries` select, over this octree's bounding box:
+    /// the queries' segments go into the grid on the device, one after the other (a point that two queries select counts
+    /// twice). Every query must be one the library serves (as in query_many).
+    pub fn terrain(&self, queries: &[PointQuery], params: &PcvTerrainParams, output_directory: impl AsRef<Path>) -> Result<()> {
+        let served: Vec<Option<(PcvShape, Option<[f64; 2]>, Vec<u64>)>> = queries.iter().map(library_query).collect();
+        if queries.is_empty() || served.iter().any(|s| s.is_none()) {
+            return Err(ErrorKind::InvalidInput("terrain: every query must be one the library serves".to_string()).into());
+        }
+        let shapes: Vec<PcvShape> = served.iter().flatten().map(|(s, _, _)| *s).collect();
+        let intervals: Vec<Option<[f64; 2]>> = served.iter().flatten().map(|(_, iv, _)| *iv).collect();
+        let cells: Vec<Vec<u64>> = served.iter().flatten().map(|(_, _, c)| c.clone()).collect();
+        let dir = CString::new(output_directory.as_ref().to_str().unwrap()).unwrap();
+        let bbox = self.bounding_box();
+        let (lo, hi) = ([bbox.min().x, bbox.min().y, bbox.min().z], [bbox.max().x, bbox.max().y, bbox.max().z]);
+        let _g = self.lock.lock().unwrap();
+        let (handle, _, _, offset) = self.run_batch(&shapes, &cells, &intervals);
+        let mut t: *mut pcv_terrain = std::ptr::null_mut();
+        let mut rc = unsafe { pcv_terrain_begin(self.ctx.0, params, lo.as_ptr(), hi.as_ptr(), &mut t) };
+        if rc == 0 {
+            rc = unsafe { pcv_terrain_add_query_batch(t, handle, 0, offset.len() as u64 - 1) };
+        }
+        if rc == 0 {
+            rc = unsafe { pcv_terrain_finish(t) };
+        }
+        if rc == 0 {
+            rc = unsafe { pcv_terrain_write_dir(t, dir.as_ptr()) };
+        }
+        let msg = if rc != 0 { unsafe { CStr::from_ptr(pcv_last_error(self.ctx.0)) }.to_string_lossy().into_owned() } else { String::new() };
+        unsafe {
+            pcv_terrain_free(t);
+            pcv_query_batch_free(handle);
+        }
+        if rc != 0 {
+            return Err(ErrorKind::InvalidInput(format!("terrain failed ({}): {}", rc, msg)).into());
+        }
+        Ok(())
     }
 }
 
