@@ -87,6 +87,10 @@ PCV_SA(sizeof(pcv_terrain_info) == 72 && offsetof(pcv_terrain_info, points_added
            offsetof(pcv_terrain_info, pool_bytes) == 40 && offsetof(pcv_terrain_info, vertex_min) == 48 &&
            offsetof(pcv_terrain_info, vertex_max) == 56 && offsetof(pcv_terrain_info, finished) == 64,
        "pcv_terrain_info");
+PCV_SA(sizeof(pcv_render_terrain_layers) == 24 && offsetof(pcv_render_terrain_layers, num_layers) == 0 &&
+           offsetof(pcv_render_terrain_layers, window) == 4 && offsetof(pcv_render_terrain_layers, layers) == 8 &&
+           offsetof(pcv_render_terrain_layers, camera_positions) == 16,
+       "pcv_render_terrain_layers");
 PCV_SA(sizeof(pcv_s2_filter) == 32 && offsetof(pcv_s2_filter, location) == 0 && offsetof(pcv_s2_filter, reserved) == 4 &&
            offsetof(pcv_s2_filter, attribute) == 8 && offsetof(pcv_s2_filter, lo) == 16 && offsetof(pcv_s2_filter, hi) == 24,
        "pcv_s2_filter");

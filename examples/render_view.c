@@ -3,13 +3,18 @@
  *
  *   render_view <octree dir> --matrix <16 doubles> --size WxH [--point-size s] [--gamma g] [--max-nodes n]
  *               [--show-octree-nodes] -o out.png
- *   render_view <octree dir> --look-at <eye xyz> <target xyz> <fovy radians> --size WxH [...] -o out.png
+ *   render_view <octree dir> --look-at <eye xyz> <target xyz> <fovy radians> --size WxH [...]
+ *               [--terrain <terrain dir>]... [--terrain-window N] -o out.png
  *
  * --matrix: world_to_gl, column-major, as the viewer uploads it. --look-at: a right-handed look-at view with +z up (+y when
  * looking along z) under Perspective3::new(W / H, fovy, near, far), far = the distance to the farthest corner of the octree's
  * bounding box, near = far / 10 000. --show-octree-nodes: the viewer's `O` key, the yellow wireframe of every drawn node's cube
  * (pcv_render_views_ex with PCV_RENDER_OUTLINE_NODES). Prints "<nodes visible> <nodes drawn> <points submitted> <points drawn>
  * <pixels covered>", and with outlines " <segments submitted> <segments drawn> <outline pixels>" after them.
+ * --terrain (repeatable, with --look-at: the eye is the camera position): a terrain directory as sdl_viewer --terrain takes
+ * it, drawn after the nodes as the viewer's wireframe layer in a window of --terrain-window vertices (even, 2 ..= 1024, default
+ * 1024) around the camera (pcv_terrain_open_dir, pcv_render_views_terrain); per layer " <edges submitted> <edges drawn>
+ * <pixels won>" is printed after the rest.
  */
 #include <math.h>
 #include <stdio.h>
@@ -53,7 +58,11 @@ static void look_at(const double eye[3], const double target[3], double fovy, do
 int main(int argc, char** argv) {
   const char* usage =
       "usage: render_view <octree dir> --matrix <16 doubles> | --look-at <eye xyz> <target xyz> <fovy> --size WxH "
-      "[--point-size s] [--gamma g] [--max-nodes n] [--show-octree-nodes] -o out.png\n";
+      "[--point-size s] [--gamma g] [--max-nodes n] [--show-octree-nodes] [--terrain <dir>]... [--terrain-window N] -o out.png\n";
+  enum { kMaxTerrain = 16 };
+  const char* terrain_dirs[kMaxTerrain];
+  pcv_terrain* terrains[kMaxTerrain] = {NULL};
+  pcv_render_terrain_layers layers = {0, PCV_RENDER_TERRAIN_WINDOW, terrains, NULL};
   double matrix[16], eye[3] = {0, 0, 0}, target[3] = {0, 0, 0}, fovy = 0.0;
   int have_matrix = 0, have_look = 0;
   pcv_render_params params;
@@ -85,6 +94,10 @@ int main(int argc, char** argv) {
       params.max_nodes = (uint32_t)strtoul(argv[++i], NULL, 10);
     } else if (strcmp(argv[i], "--show-octree-nodes") == 0) {
       overlay.flags |= PCV_RENDER_OUTLINE_NODES;
+    } else if (strcmp(argv[i], "--terrain") == 0 && i + 1 < argc && layers.num_layers < kMaxTerrain) {
+      terrain_dirs[layers.num_layers++] = argv[++i];
+    } else if (strcmp(argv[i], "--terrain-window") == 0 && i + 1 < argc) {
+      layers.window = (uint32_t)strtoul(argv[++i], NULL, 10);
     } else if (strcmp(argv[i], "-o") == 0 && i + 1 < argc) {
       out = argv[++i];
     } else {
@@ -95,6 +108,20 @@ int main(int argc, char** argv) {
   if (have_matrix == have_look || !out || pcv_render_check_params(&params) != PCV_OK) {
     fputs(usage, stderr);
     return 2;
+  }
+  {  /* the window is checked before any device work, layers or not; the layers themselves are opened below */
+    char why[128];
+    pcv_render_terrain_layers probe = layers;
+    probe.camera_positions = eye;
+    probe.num_layers = layers.num_layers ? layers.num_layers : 1;
+    for (uint32_t k = 0; k < probe.num_layers; ++k) terrains[k] = (pcv_terrain*)terrain_dirs;  /* not null; never read by the check */
+    const int bad = pcv_render_check_terrain_host(&probe, why, sizeof(why));
+    for (uint32_t k = 0; k < probe.num_layers; ++k) terrains[k] = NULL;
+    if (bad != PCV_OK || (layers.num_layers && !have_look)) {
+      fprintf(stderr, "render_view: %s\n", bad != PCV_OK ? why : "--terrain needs --look-at: the eye is the camera position");
+      fputs(usage, stderr);
+      return 2;
+    }
   }
   pcv_ctx* ctx = NULL;
   pcv_octree* tree = NULL;
@@ -117,7 +144,9 @@ int main(int argc, char** argv) {
     memcpy(shape.params, matrix, sizeof(matrix));
     rc = pcv_shapes_create(ctx, &shape, 1, &frusta);
   }
-  if (rc == PCV_OK) rc = pcv_render_views_ex(ctx, frusta, tree, &params, &overlay, &frame);
+  for (uint32_t k = 0; k < layers.num_layers && rc == PCV_OK; ++k) rc = pcv_terrain_open_dir(ctx, terrain_dirs[k], &terrains[k]);
+  layers.camera_positions = eye;
+  if (rc == PCV_OK) rc = pcv_render_views_terrain(ctx, frusta, tree, &params, &overlay, &layers, &frame);
   int32_t status = 0;
   uint32_t visible = 0, drawn_nodes = 0;
   uint64_t submitted = 0, drawn = 0, covered = 0, need = 0, seg_submitted = 0, seg_drawn = 0, outline_pixels = 0;
@@ -142,12 +171,19 @@ int main(int argc, char** argv) {
     printf("%u %u %llu %llu %llu", visible, drawn_nodes, (unsigned long long)submitted, (unsigned long long)drawn, (unsigned long long)covered);
     if (overlay.flags & PCV_RENDER_OUTLINE_NODES)
       printf(" %llu %llu %llu", (unsigned long long)seg_submitted, (unsigned long long)seg_drawn, (unsigned long long)outline_pixels);
+    for (uint32_t k = 0; k < layers.num_layers && rc == PCV_OK; ++k) {
+      uint64_t edges_submitted = 0, edges_drawn = 0, pixels_won = 0;
+      rc = pcv_render_terrain_info(frame, 0, k, NULL, &edges_submitted, &edges_drawn, &pixels_won);
+      printf(" %llu %llu %llu", (unsigned long long)edges_submitted, (unsigned long long)edges_drawn, (unsigned long long)pixels_won);
+    }
     printf("\n");
-  } else
+  }
+  if (rc != PCV_OK)
     fprintf(stderr, "render_view: %s (%d)\n", ctx && rc != PCV_E_IO ? pcv_last_error(ctx) : "cannot write the PNG", rc);
   free(png);
   free(rgba);
   pcv_render_free(frame);
+  for (uint32_t k = 0; k < layers.num_layers; ++k) pcv_terrain_free(terrains[k]);
   pcv_shapes_free(frusta);
   if (tree) pcv_octree_free(tree);
   if (ctx) pcv_ctx_destroy(ctx);

@@ -1735,6 +1735,70 @@ int pcv_terrain_tile_name_host(int32_t x, int32_t y, char* buf, uint64_t cap);
  * back to the same double, integral values with ".0". *len its length, the first min(cap, *len) bytes into buf. */
 int pcv_terrain_meta_json_host(const pcv_terrain_params* params, uint64_t num_tiles, const int32_t* positions, char* buf, uint64_t cap,
                                uint64_t* len);
+/* The reader of that schema (terrain_drawer/read_write.rs, serde_json): `len` bytes of meta.json, the five keys in any order,
+ * world_from_terrain as {"rotation":[i,j,k,w],"translation":[x,y,z]} (its two keys in any order), unknown keys skipped.
+ * Fills tile_size, resolution_m, origin and world_from_terrain of *params; statistic, min_points (1) and the limits are set
+ * to their defaults, and the result goes through pcv_terrain_check_params_host. *num_tiles the tiles listed, the first
+ * min(capacity, *num_tiles) positions into `positions` (nullable). PCV_E_INVALID names the key that is missing, of the
+ * wrong type or cut off (pcv_host_last_error). */
+int pcv_terrain_meta_read_host(const char* json, uint64_t len, pcv_terrain_params* params, uint64_t capacity, int32_t* positions,
+                               uint64_t* num_tiles);
+/* A finished terrain from tiles that were not built in this process: num_tiles positions (2 x i32 each, host), heights
+ * (tiles x T x T x 2 f32) and colors (tiles x T x T x 4 u8) in the layout of pcv_terrain_heights / pcv_terrain_colors, in memory
+ * that lives where `mem` says. The tiles are stored ascending by (x, y), whatever order they come in. It serves
+ * pcv_terrain_tiles, _heights, _colors, _info_get (tiles and finished; the counts of a build are zero) and _write_dir, and is a
+ * layer of pcv_render_views_terrain; pcv_terrain_counts and every pcv_terrain_add_* on it are PCV_E_INVALID with a message.
+ * PCV_E_INVALID: what pcv_terrain_check_params_host refuses (a tile_size outside 1 ..= 4096 among it), a tile position given
+ * twice, null arrays with num_tiles > 0, more than 2^22 tiles. */
+int pcv_terrain_from_tiles(pcv_ctx* ctx, const pcv_terrain_params* params, uint64_t num_tiles, const int32_t* positions,
+                           const float* heights, const uint8_t* colors, int mem, pcv_terrain** out);
+/* pcv_terrain_from_tiles over a directory as pcv_terrain_write_dir leaves it: meta.json through the reader above, then
+ * x{:08}_y{:08}.height / .color per listed tile. A file that is missing or unreadable is PCV_E_IO, one whose length is not
+ * T T 8 / T T 4 bytes PCV_E_INVALID; both name the file. */
+int pcv_terrain_open_dir(pcv_ctx* ctx, const char* directory, pcv_terrain** out);
+
+/* ---- terrain layers in the viewer's frame (sdl_viewer --terrain) ---------------------------------
+ * The viewer draws its terrain layers right after the points, under the same depth test, as a wireframe
+ * (sdl_viewer/src/lib.rs:602-606, terrain_drawer/mod.rs:152-187, shaders/terrain.vs, terrain.gs, terrain.fs). The restatement:
+ *  - window: l = M (c - t) for the view's camera position c (world frame) with pcv_terrain_frame_host's doubles; gx =
+ *    floor((l_x - o_x) / res), gy likewise; pos = (gx, gy) - (window / 2, window / 2) (layer.rs:222-235);
+ *  - vertices: window vertex (ax, ay) is global vertex pos + (ax, ay); height, mask and colour through the tile table, zeros
+ *    where the tile is missing; loc = (o_x + res ((double)ax + (double)pos_x), .. , o_z + (double)height); world = M^T loc + t
+ *    in f64, unfused; clip as a point's position (f64 dot, one rounding to f32); the mask is the stored f32 truncated to u32
+ *    (negative, non-finite or >= 2^32 reads as 0);
+ *  - triangles T1 = (ax,ay) (ax+1,ay) (ax,ay+1) and T2 = (ax+1,ay) (ax,ay+1) (ax+1,ay+1) of quad (ax, ay) are rendered iff the
+ *    AND of their three masks is non-zero; every edge H (ax,ay)->(ax+1,ay), V (ax,ay)->(ax,ay+1), D (ax+1,ay)->(ax,ay+1) is
+ *    drawn once iff a triangle that owns it is rendered; its index is 3 (ay window + ax) + kind (H 0, V 1, D 2);
+ *  - clip, window transform and width-1 raster as a node outline's segment; colour per channel (float)c0 + s ((float)c1 -
+ *    (float)c0) with s = t_in + t (t_out - t_in), clamped to [0, 255], plus 0.5, truncated; alpha 255; no gamma;
+ *  - layers are drawn after all nodes (and outlines), in the order given; layer k of a view owns 3 window^2 consecutive draw
+ *    ranks, a fragment's rank is its edge's index: at equal depth terrain loses to every point, outline and earlier layer.
+ *    The limit of 2^32 - 1 ranks per view includes them. A view whose status is 1 or 2 draws no terrain. */
+typedef struct pcv_render_terrain_layers {
+  uint32_t num_layers;
+  uint32_t window;                 /* the window's edge in vertices: even, 2 ..= 1024; the viewer's is 1024 */
+  pcv_terrain* const* layers;      /* num_layers finished terrains of the context; a terrain may be given more than once */
+  const double* camera_positions;  /* views x 3, host: the camera of every frustum, world frame */
+} pcv_render_terrain_layers;
+#define PCV_RENDER_TERRAIN_WINDOW 1024
+/* Host only, no context: PCV_E_INVALID with the reason in `message` (NUL-terminated, cut to `capacity`; nullable) for a window
+ * that is odd, 0 or above 1024, a null layer array or entry, null camera positions. A null `terrain` and num_layers == 0 are
+ * valid: nothing is drawn. */
+int pcv_render_check_terrain_host(const pcv_render_terrain_layers* terrain, char* message, uint64_t capacity);
+/* Host only, no context: the window position of one camera over one layer's grid, pos = 2 x i64. PCV_E_INVALID "Terrain
+ * location not representable." (layer.rs:176-183, 226-233) when gx or gy is not finite or |gx|, |gy| >= 2^53. */
+int pcv_render_terrain_window_host(const pcv_terrain_params* params, const double camera_position[3], uint32_t window, int64_t pos[2]);
+/* pcv_render_views_ex with terrain layers. A null `terrain` or num_layers == 0 is pcv_render_views_ex itself: the same
+ * launches, the same bytes. The window vertices (24 bytes each, per view and layer) count against max_workspace_bytes beside
+ * the key planes when views are grouped; a single view over the limit is PCV_E_OOM before anything is allocated. PCV_E_INVALID:
+ * what pcv_render_check_terrain_host refuses, a layer that is not finished or of another context, a window position that is
+ * not representable, 2^32 - 1 draw ranks or more in a view. The layers may be freed after the call. */
+int pcv_render_views_terrain(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree, const pcv_render_params* params,
+                             const pcv_render_overlay* overlay, const pcv_render_terrain_layers* terrain, pcv_render** out);
+/* Per view and layer (each output nullable): the window position, the edges step 15 draws, those that survived the clip, the
+ * pixels of the final image the layer won. Counters are zero for a view whose status is not 0. PCV_E_INVALID past the end. */
+int pcv_render_terrain_info(pcv_render* r, uint32_t view, uint32_t layer, int64_t pos[2], uint64_t* edges_submitted,
+                            uint64_t* edges_drawn, uint64_t* pixels_won);
 
 /* Host only: which arm PointCloudClientBuilder::build (point_cloud_client/src/lib.rs:107-132) would take for this
  * directory's meta.pb: `version <= 11 || has_octree()` is PCV_CLOUD_OCTREE, anything else PCV_CLOUD_S2. The reference

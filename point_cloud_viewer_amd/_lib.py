@@ -84,6 +84,11 @@ class RenderOverlay(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("outline_rgba", C.c_uint8 * 4)]
 
 
+class RenderTerrainLayers(C.Structure):  # pcv_render_terrain_layers
+    _fields_ = [("num_layers", C.c_uint32), ("window", C.c_uint32), ("layers", C.POINTER(C.c_void_p)), ("camera_positions", C.c_void_p)]
+
+
+RENDER_TERRAIN_WINDOW = 1024  # PCV_RENDER_TERRAIN_WINDOW: the viewer's window edge in vertices
 RENDER_MAX_POINT_SIZE = 64  # PCV_RENDER_MAX_POINT_SIZE
 RENDER_OUTLINE_NODES = 1  # PCV_RENDER_OUTLINE_NODES
 RENDER_OUTLINE_YELLOW = (255, 255, 0, 255)  # PCV_RENDER_OUTLINE_YELLOW: the viewer's YELLOW
@@ -458,6 +463,14 @@ _SIGNATURES = {
     "pcv_ply_header_host": (C.c_int, [C.POINTER(C.c_char_p), _vp, C.c_uint32, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pcv_ply_append_check_host": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), _vp, C.c_uint32, C.POINTER(C.c_uint64)]),
     "pcv_ctx_pool_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
+    "pcv_render_check_terrain_host": (C.c_int, [C.POINTER(RenderTerrainLayers), C.c_char_p, C.c_uint64]),
+    "pcv_render_terrain_window_host": (C.c_int, [C.POINTER(TerrainParams), _vp, C.c_uint32, _vp]),
+    "pcv_render_views_terrain": (C.c_int, [_vp, _vp, _vp, C.POINTER(RenderParams), C.POINTER(RenderOverlay), C.POINTER(RenderTerrainLayers),
+                                           C.POINTER(_vp)]),
+    "pcv_render_terrain_info": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "pcv_terrain_meta_read_host": (C.c_int, [C.c_char_p, C.c_uint64, C.POINTER(TerrainParams), C.c_uint64, _vp, C.POINTER(C.c_uint64)]),
+    "pcv_terrain_from_tiles": (C.c_int, [_vp, C.POINTER(TerrainParams), C.c_uint64, _vp, _vp, _vp, C.c_int, C.POINTER(_vp)]),
+    "pcv_terrain_open_dir": (C.c_int, [_vp, C.c_char_p, C.POINTER(_vp)]),
     "pcv_terrain_begin": (C.c_int, [_vp, C.POINTER(TerrainParams), _vp, _vp, C.POINTER(_vp)]),
     "pcv_terrain_add_points": (C.c_int, [_vp, C.c_uint64, _vp, _vp, _vp, _vp, C.c_int]),
     "pcv_terrain_add_query_batch": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),

@@ -128,6 +128,8 @@ enum PcvKernelId {
   PCV_K_TERRAIN_COUNT,        // pcv_terrain.hip: set vertices per touched tile
   PCV_K_TERRAIN_RESOLVE,      // pcv_terrain.hip: accumulators -> height, colour, count of the kept tiles
   PCV_K_TERRAIN_MASK,         // pcv_terrain.hip: quad masks from the set flags of each vertex's neighbourhood, across tile seams
+  PCV_K_RENDER_TERRAIN_GATHER,  // pcv_render_views_terrain: the window vertices of every (view, layer): tile lookup, f64 chain, clip point
+  PCV_K_RENDER_TERRAIN_EDGES,   // pcv_render_views_terrain: patches of window vertices in LDS, the drawn edges clipped and rasterised
   PCV_K_COUNT
 };
 

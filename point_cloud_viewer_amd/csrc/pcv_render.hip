@@ -19,6 +19,16 @@
 //                         Liang-Barsky against the seven half-spaces in f32, window transform, width-1 raster along the
 //                         major axis, one atomicMin of (bits(zw) << 32 | outline rank) per fragment
 //
+// With terrain layers (pcv_render_views_terrain; sdl_viewer --terrain, lib.rs:602-606, terrain_drawer/, shaders/terrain.*) two
+// more run after the group's points and outlines, and the resolve runs as render_resolve_terrain:
+//
+//   K_tg  render_terrain_gather  a thread per window vertex of every (view, layer): the vertex's tile through the layer's sorted
+//                                tile keys, the f64 chain of terrain.vs once per vertex, the f32 clip point, mask and colour
+//                                stored (24 bytes): the window loader
+//   K_te  render_terrain_edges   a workgroup per patch of 14 x 14 edge origins, its 16 x 16 vertices staged in LDS: the mask
+//                                test of terrain.gs per triangle, every edge of a rendered triangle once, clipped and rasterised
+//                                by the outline's own segment walk (draw_segment), one atomicMin per fragment with the edge's rank
+//
 // An integer minimum does not depend on the order the atomics arrive in, so a frame's bytes do not depend on scheduling.
 // Every f32 step is a single correctly rounded operation (-ffp-contract=off, correctly rounded f32 division, denormals
 // kept); no libm call is made on the device: the gamma table comes from the host.
@@ -31,6 +41,8 @@
 #include <vector>
 
 #include "pcv_query_dev.h"
+#include "pcv_terrain_files.h"
+#include "pcv_terrain_obj.h"
 
 namespace {
 
@@ -213,6 +225,73 @@ __device__ __forceinline__ bool clip_plane(float d0, float d1, bool strict, floa
   return in0 || in1;
 }
 
+// Steps 10 and 11 of a segment between two f32 clip points, the one text for the node outlines and the terrain edges, and
+// for the terrain's resolve, which walks the same steps again for one pixel (SINGLE: only the fragment of major-axis pixel
+// single_x / single_y). survived() is called once for a segment that passes the clip, begin() once before its first
+// fragment (what it returns goes to every emit), emit(state, gx, gy, zw, t, t_in, t_out) per fragment inside the image: gx, gy
+// count from the lower left, t is the raster parameter between the clipped ends, t_in and t_out those ends on the segment.
+template <bool SINGLE, typename Survived, typename Begin, typename Emit>
+__device__ __forceinline__ void draw_segment(const float (&p)[4], const float (&q)[4], float half_w, float half_h, uint32_t W, uint32_t H,
+                                             int32_t single_x, int32_t single_y, Survived survived, Begin begin, Emit emit) {
+  bool alive = true;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) alive = alive && f32_finite(p[r]) && f32_finite(q[r]);
+  if (!alive) return;
+  // w > 0, then w + x, w - x, w + y, w - y, w + z, w - z >= 0: every distance one f32 operation on the unclipped endpoints
+  float t_in = 0.0f, t_out = 1.0f;
+  alive = clip_plane(p[3], q[3], true, t_in, t_out);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    alive = clip_plane(p[3] + p[r], q[3] + q[r], false, t_in, t_out) && alive;
+    alive = clip_plane(p[3] - p[r], q[3] - q[r], false, t_in, t_out) && alive;
+  }
+  if (!alive || t_in > t_out) return;
+  float c0[4], c1[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float d = q[r] - p[r];
+    c0[r] = t_in > 0.0f ? p[r] + t_in * d : p[r];
+    c1[r] = t_out < 1.0f ? p[r] + t_out * d : q[r];
+  }
+  if (!(c0[3] > 0.0f && c0[3] <= kF32Max && c1[3] > 0.0f && c1[3] <= kF32Max)) return;
+  const float x0 = (c0[0] / c0[3] + 1.0f) * half_w, y0 = (c0[1] / c0[3] + 1.0f) * half_h, z0 = (c0[2] / c0[3]) * 0.5f + 0.5f;
+  const float x1 = (c1[0] / c1[3] + 1.0f) * half_w, y1 = (c1[1] / c1[3] + 1.0f) * half_h, z1 = (c1[2] / c1[3]) * 0.5f + 0.5f;
+  if (!(f32_finite(x0) && f32_finite(y0) && f32_finite(z0) && f32_finite(x1) && f32_finite(y1) && f32_finite(z1))) return;
+  survived();
+  // width 1: the pixel centres of the major axis inside [min, max), one fragment each
+  const bool x_major = __builtin_fabsf(x1 - x0) >= __builtin_fabsf(y1 - y0);
+  const float m0 = x_major ? x0 : y0, m1 = x_major ? x1 : y1, n0 = x_major ? y0 : x0, n1 = x_major ? y1 : x1;
+  const uint32_t size_m = x_major ? W : H, size_n = x_major ? H : W;
+  const float lo = m0 < m1 ? m0 : m1, hi = m0 < m1 ? m1 : m0;
+  if (!(lo < hi)) return;
+  // both ends are brought into [-1, size + 1] before the conversion, then found by testing the predicate itself
+  const float top = (float)size_m + 1.0f;
+  int32_t i0 = (int32_t)(lo < -1.0f ? -1.0f : lo > top ? top : lo) - 1, i1 = (int32_t)(hi < -1.0f ? -1.0f : hi > top ? top : hi) + 1;
+  if (i0 < 0) i0 = 0;
+  if (i1 > (int32_t)size_m - 1) i1 = (int32_t)size_m - 1;
+  if constexpr (SINGLE) {  // the predicate on the one pixel
+    const int32_t i = x_major ? single_x : single_y;
+    if (i < i0 || i > i1 || !(lo <= (float)i + 0.5f) || !((float)i + 0.5f < hi)) return;
+    i0 = i1 = i;
+  } else {
+    while (i0 <= i1 && !(lo <= (float)i0 + 0.5f)) ++i0;
+    while (i1 >= i0 && !((float)i1 + 0.5f < hi)) --i1;
+  }
+  auto state = begin();
+  const float dm = m1 - m0, dn = n1 - n0, dz = z1 - z0, limit = (float)size_n;
+  for (int32_t i = i0; i <= i1; ++i) {
+    const float t = (((float)i + 0.5f) - m0) / dm;
+    const float n = n0 + t * dn;
+    if (!(n >= 0.0f && n < limit)) continue;  // outside the image (or NaN); inside, the conversion below is floorf
+    const uint32_t j = (uint32_t)(int32_t)n;
+    float zw = z0 + t * dz;
+    if (!(zw > 0.0f)) zw = 0.0f;  // (a NaN and -0.0f too: the key orders by the bit pattern)
+    if (zw > 1.0f) zw = 1.0f;
+    const uint32_t gx = x_major ? (uint32_t)i : j, gy = x_major ? j : (uint32_t)i;
+    emit(state, gx, gy, zw, t, t_in, t_out);
+  }
+}
+
 // K_ro: item = segment * 12 + edge over the group's segments; the grid strides over the items
 __global__ __launch_bounds__(256) void render_outline_kernel(RenderOutlineArgs a) {
   const uint64_t items = (a.s1 - a.s0) * 12, plane = (uint64_t)a.W * a.H;
@@ -224,60 +303,179 @@ __global__ __launch_bounds__(256) void render_outline_kernel(RenderOutlineArgs a
     float p[4], q[4];
     outline_corner(nd, mm, (kCornerPick >> (4u * (uint32_t)((kEdgeFrom >> (4u * e)) & 15u))) & 7u, p);
     outline_corner(nd, mm, (kCornerPick >> (4u * (uint32_t)((kEdgeTo >> (4u * e)) & 15u))) & 7u, q);
-    bool alive = true;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) alive = alive && f32_finite(p[r]) && f32_finite(q[r]);
-    if (!alive) continue;
-    // w > 0, then w + x, w - x, w + y, w - y, w + z, w - z >= 0: every distance one f32 operation on the unclipped endpoints
-    float t_in = 0.0f, t_out = 1.0f;
-    alive = clip_plane(p[3], q[3], true, t_in, t_out);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      alive = clip_plane(p[3] + p[r], q[3] + q[r], false, t_in, t_out) && alive;
-      alive = clip_plane(p[3] - p[r], q[3] - q[r], false, t_in, t_out) && alive;
-    }
-    if (!alive || t_in > t_out) continue;
-    float c0[4], c1[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float d = q[r] - p[r];
-      c0[r] = t_in > 0.0f ? p[r] + t_in * d : p[r];
-      c1[r] = t_out < 1.0f ? p[r] + t_out * d : q[r];
-    }
-    if (!(c0[3] > 0.0f && c0[3] <= kF32Max && c1[3] > 0.0f && c1[3] <= kF32Max)) continue;
-    const float x0 = (c0[0] / c0[3] + 1.0f) * a.half_w, y0 = (c0[1] / c0[3] + 1.0f) * a.half_h, z0 = (c0[2] / c0[3]) * 0.5f + 0.5f;
-    const float x1 = (c1[0] / c1[3] + 1.0f) * a.half_w, y1 = (c1[1] / c1[3] + 1.0f) * a.half_h, z1 = (c1[2] / c1[3]) * 0.5f + 0.5f;
-    if (!(f32_finite(x0) && f32_finite(y0) && f32_finite(z0) && f32_finite(x1) && f32_finite(y1) && f32_finite(z1))) continue;
-    atomicAdd(a.seg_drawn + view, 1ull);
-    // width 1: the pixel centres of the major axis inside [min, max), one fragment each
-    const bool x_major = __builtin_fabsf(x1 - x0) >= __builtin_fabsf(y1 - y0);
-    const float m0 = x_major ? x0 : y0, m1 = x_major ? x1 : y1, n0 = x_major ? y0 : x0, n1 = x_major ? y1 : x1;
-    const uint32_t size_m = x_major ? a.W : a.H, size_n = x_major ? a.H : a.W;
-    const float lo = m0 < m1 ? m0 : m1, hi = m0 < m1 ? m1 : m0;
-    if (!(lo < hi)) continue;
-    // both ends are brought into [-1, size + 1] before the conversion, then found by testing the predicate itself
-    const float top = (float)size_m + 1.0f;
-    int32_t i0 = (int32_t)(lo < -1.0f ? -1.0f : lo > top ? top : lo) - 1, i1 = (int32_t)(hi < -1.0f ? -1.0f : hi > top ? top : hi) + 1;
-    if (i0 < 0) i0 = 0;
-    if (i1 > (int32_t)size_m - 1) i1 = (int32_t)size_m - 1;
-    while (i0 <= i1 && !(lo <= (float)i0 + 0.5f)) ++i0;
-    while (i1 >= i0 && !((float)i1 + 0.5f < hi)) --i1;
-    // the outline's rank is the last of its node's n + 1
-    const unsigned long long rank = (unsigned long long)(uint32_t)(a.seg_rank[s + 1] - 1 - a.seg_rank[a.view_seg[view]]);
-    unsigned long long* keys = a.keys + (uint64_t)(view - a.view0) * plane;
-    const float dm = m1 - m0, dn = n1 - n0, dz = z1 - z0, limit = (float)size_n;
-    for (int32_t i = i0; i <= i1; ++i) {
-      const float t = (((float)i + 0.5f) - m0) / dm;
-      const float n = n0 + t * dn;
-      if (!(n >= 0.0f && n < limit)) continue;  // outside the image (or NaN); inside, the conversion below is floorf
-      const uint32_t j = (uint32_t)(int32_t)n;
-      float zw = z0 + t * dz;
-      if (!(zw > 0.0f)) zw = 0.0f;  // (a NaN and -0.0f too: the key orders by the bit pattern)
-      if (zw > 1.0f) zw = 1.0f;
-      const uint32_t gx = x_major ? (uint32_t)i : j, gy = x_major ? j : (uint32_t)i;
-      atomicMin(keys + (uint64_t)(a.H - 1u - gy) * a.W + gx, ((unsigned long long)__float_as_uint(zw) << 32) | rank);
-    }
+    unsigned long long* keys = nullptr;
+    draw_segment<false>(
+        p, q, a.half_w, a.half_h, a.W, a.H, 0, 0, [&]() { atomicAdd(a.seg_drawn + view, 1ull); },
+        [&]() {
+          keys = a.keys + (uint64_t)(view - a.view0) * plane;
+          // the outline's rank is the last of its node's n + 1
+          return (unsigned long long)(uint32_t)(a.seg_rank[s + 1] - 1 - a.seg_rank[a.view_seg[view]]);
+        },
+        [&](unsigned long long rank, uint32_t gx, uint32_t gy, float zw, float, float, float) {
+          atomicMin(keys + (uint64_t)(a.H - 1u - gy) * a.W + gx, ((unsigned long long)__float_as_uint(zw) << 32) | rank);
+        });
   }
+}
+
+// ---- terrain layers -------------------------------------------------------------------------------
+// one layer as the kernels read it
+struct TerrainLayerDev {
+  PcvTerrainGrid grid;
+  uint64_t ntiles;
+  const int64_t* tile_keys;  // ascending (pcv_terrain_tile_key)
+  const float* heights;      // ntiles x T x T x (height, mask)
+  const uint8_t* colors;     // ntiles x T x T x 4
+  uint32_t T, pad;
+};
+
+struct RenderTerrainArgs {
+  const TerrainLayerDev* layers;
+  const int64_t* pos;              // per (view of the call, layer): the window position
+  const uint32_t* view_status;     // per view of the call: 0 draws
+  const PcvShapeDev* shapes;
+  const uint64_t* view_seg;        // V + 1
+  const uint64_t* seg_rank;        // nseg + 1: the ranks of the nodes (and outlines); a view's terrain ranks follow them
+  float4* clip;                    // the group's windows, (view - view0) * L + layer, Wn x Wn each: f32 clip points,
+  uint32_t* mask;                  //   masks,
+  uint32_t* color;                 //   colours as stored (r | g << 8 | b << 16 | a << 24)
+  unsigned long long* keys;        // the group's key planes
+  unsigned long long* counters;    // per (view of the call, layer): edges submitted, edges drawn, pixels won
+  uint32_t L, Wn;
+  uint32_t view0, nv;
+  uint32_t W, H;
+  float half_w, half_h;
+};
+
+// K_tg: a thread per window vertex of every (view, layer) of the group, the grid strides over them: the tile of the vertex by
+// binary search in the layer's sorted tile keys, then step 14. This is the window loader: 24 bytes out per vertex.
+__global__ __launch_bounds__(256) void render_terrain_gather_kernel(RenderTerrainArgs a) {
+  const uint64_t per = (uint64_t)a.Wn * a.Wn, items = per * a.L * a.nv;
+  for (uint64_t it = (uint64_t)blockIdx.x * 256 + threadIdx.x; it < items; it += (uint64_t)gridDim.x * 256) {
+    const uint32_t vl = (uint32_t)(it / per), cell = (uint32_t)(it % per);
+    const uint32_t view = a.view0 + vl / a.L, layer = vl % a.L;
+    if (a.view_status[view] != 0) continue;  // a cleared view: its windows are never read
+    const uint32_t ax = cell % a.Wn, ay = cell / a.Wn;
+    const TerrainLayerDev& ly = a.layers[layer];
+    const int64_t px = a.pos[2 * ((uint64_t)view * a.L + layer)], py = a.pos[2 * ((uint64_t)view * a.L + layer) + 1];
+    const int64_t gi = px + (int64_t)ax, gj = py + (int64_t)ay;  // |pos| < 2^53 + 512
+    const int64_t T = (int64_t)ly.T;
+    const int64_t tx = pcv_terrain_floor_div(gi, T), ty = pcv_terrain_floor_div(gj, T);
+    float height = 0.0f, maskf = 0.0f;
+    uint32_t color = 0;
+    if (tx >= INT32_MIN && tx <= INT32_MAX && ty >= INT32_MIN && ty <= INT32_MAX && ly.ntiles) {
+      const int64_t key = pcv_terrain_tile_key((int32_t)tx, (int32_t)ty);
+      uint64_t lo = 0, hi = ly.ntiles;  // the last tile whose key is <= key
+      while (hi - lo > 1) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (ly.tile_keys[mid] <= key) lo = mid;
+        else hi = mid;
+      }
+      if (ly.tile_keys[lo] == key) {
+        const uint64_t o = lo * (uint64_t)(T * T) + (uint64_t)pcv_terrain_floor_mod(gj, T) * ly.T + (uint64_t)pcv_terrain_floor_mod(gi, T);
+        height = ly.heights[2 * o];
+        maskf = ly.heights[2 * o + 1];
+        color = reinterpret_cast<const uint32_t*>(ly.colors)[o];
+      }
+    }
+    const PcvTerrainGrid& g = ly.grid;
+    const double lx = g.o[0] + g.res * ((double)ax + (double)px);
+    const double lyy = g.o[1] + g.res * ((double)ay + (double)py);
+    const double lz = g.o[2] + (double)height;
+    // world = M^T loc + t: column r of M against loc
+    const double wx = ((g.m[0] * lx + g.m[3] * lyy) + g.m[6] * lz) + g.t[0];
+    const double wy = ((g.m[1] * lx + g.m[4] * lyy) + g.m[7] * lz) + g.t[1];
+    const double wz = ((g.m[2] * lx + g.m[5] * lyy) + g.m[8] * lz) + g.t[2];
+    const double* mm = a.shapes[view].clip_from_query;
+    float4 c;
+    c.x = (float)(((mm[0] * wx + mm[4] * wy) + mm[8] * wz) + mm[12]);
+    c.y = (float)(((mm[1] * wx + mm[5] * wy) + mm[9] * wz) + mm[13]);
+    c.z = (float)(((mm[2] * wx + mm[6] * wy) + mm[10] * wz) + mm[14]);
+    c.w = (float)(((mm[3] * wx + mm[7] * wy) + mm[11] * wz) + mm[15]);
+    a.clip[it] = c;
+    a.mask[it] = (maskf >= 0.0f && maskf < 4294967296.0f) ? (uint32_t)maskf : 0u;  // (a NaN fails both)
+    a.color[it] = color;
+  }
+}
+
+// the ranks a view's nodes (and outlines) take: its first terrain rank
+__device__ __forceinline__ uint64_t terrain_rank0(const uint64_t* view_seg, const uint64_t* seg_rank, uint32_t view) {
+  return seg_rank[view_seg[view + 1]] - seg_rank[view_seg[view]];
+}
+
+constexpr uint32_t kTerrainPatch = 14;  // edge origins per patch side: 16 x 16 vertices in LDS, a rim of one vertex around them
+
+// K_te: a workgroup per patch of 14 x 14 edge origins of one (view, layer), the grid strides over the patches. The patch's
+// 16 x 16 vertices (one beyond it on every side; outside the window: mask 0) are staged in LDS, so the three edges of an
+// origin and the four triangle tests that own them read LDS only. Then steps 15-16 and one atomicMin per fragment.
+__global__ __launch_bounds__(256) void render_terrain_edges_kernel(RenderTerrainArgs a) {
+  __shared__ float4 s_clip[256];
+  __shared__ uint32_t s_mask[256];
+  __shared__ uint32_t s_count[2];
+  const uint32_t tid = threadIdx.x, lx = tid & 15u, lyy = tid >> 4;
+  const uint32_t side = (a.Wn + kTerrainPatch - 1) / kTerrainPatch;
+  const uint64_t per_vl = (uint64_t)side * side, patches = per_vl * a.L * a.nv, per = (uint64_t)a.Wn * a.Wn, plane = (uint64_t)a.W * a.H;
+  for (uint64_t patch = blockIdx.x; patch < patches; patch += gridDim.x) {
+    const uint32_t vl = (uint32_t)(patch / per_vl), pr = (uint32_t)(patch % per_vl);
+    const uint32_t view = a.view0 + vl / a.L, layer = vl % a.L;
+    if (a.view_status[view] != 0) continue;  // (the whole workgroup)
+    const int32_t ax = (int32_t)((pr % side) * kTerrainPatch + lx) - 1, ay = (int32_t)((pr / side) * kTerrainPatch + lyy) - 1;
+    const bool inside = ax >= 0 && ay >= 0 && ax < (int32_t)a.Wn && ay < (int32_t)a.Wn;
+    const uint64_t at = (uint64_t)vl * per + (uint64_t)(inside ? ay : 0) * a.Wn + (uint64_t)(inside ? ax : 0);
+    s_clip[tid] = inside ? a.clip[at] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    s_mask[tid] = inside ? a.mask[at] : 0u;
+    if (tid < 2) s_count[tid] = 0;
+    __syncthreads();
+    uint32_t submitted = 0, drawn = 0;
+    if (inside && lx >= 1 && lx <= kTerrainPatch && lyy >= 1 && lyy <= kTerrainPatch) {
+      const uint32_t m00 = s_mask[tid], m10 = s_mask[tid + 1], m01 = s_mask[tid + 16], m11 = s_mask[tid + 17];
+      const bool t1 = (m00 & m10 & m01) != 0, t2 = (m10 & m01 & m11) != 0;
+      const bool t2_below = (s_mask[tid - 15] & m00 & m10) != 0;  // T2 of quad (ax, ay - 1): (ax + 1, ay - 1) (ax, ay) (ax + 1, ay)
+      const bool t2_left = (m00 & s_mask[tid + 15] & m01) != 0;   // T2 of quad (ax - 1, ay): (ax, ay) (ax - 1, ay + 1) (ax, ay + 1)
+      const uint64_t first = terrain_rank0(a.view_seg, a.seg_rank, view) + (uint64_t)layer * 3 * per + 3 * ((uint64_t)ay * a.Wn + (uint64_t)ax);
+      unsigned long long* keys = a.keys + (uint64_t)(view - a.view0) * plane;
+      for (uint32_t kind = 0; kind < 3; ++kind) {  // H, V, D
+        if (!(kind == 0 ? (t1 || t2_below) : kind == 1 ? (t1 || t2_left) : (t1 || t2))) continue;
+        ++submitted;
+        const float4 cp = s_clip[kind == 2 ? tid + 1 : tid], cq = s_clip[kind == 0 ? tid + 1 : tid + 16];
+        const float p[4] = {cp.x, cp.y, cp.z, cp.w}, q[4] = {cq.x, cq.y, cq.z, cq.w};
+        draw_segment<false>(
+            p, q, a.half_w, a.half_h, a.W, a.H, 0, 0, [&]() { ++drawn; }, [&]() { return (unsigned long long)(uint32_t)(first + kind); },
+            [&](unsigned long long rank, uint32_t gx, uint32_t gy, float zw, float, float, float) {
+              atomicMin(keys + (uint64_t)(a.H - 1u - gy) * a.W + gx, ((unsigned long long)__float_as_uint(zw) << 32) | rank);
+            });
+      }
+    }
+    if (submitted) atomicAdd(&s_count[0], submitted);
+    if (drawn) atomicAdd(&s_count[1], drawn);
+    __syncthreads();  // (and the patch's vertices have been read for the last time)
+    if (tid < 2 && s_count[tid]) atomicAdd(a.counters + 3 * ((uint64_t)view * a.L + layer) + tid, (unsigned long long)s_count[tid]);
+    __syncthreads();  // the counts are read before the next patch clears them
+  }
+}
+
+// Steps 16-17 again for the pixel (gx, gy from the lower left) that edge `e` of a window won: the colour of its fragment.
+__device__ __forceinline__ uint32_t terrain_fragment_color(const RenderTerrainArgs& a, uint64_t window, uint32_t e, uint32_t gx, uint32_t gy) {
+  const uint32_t kind = e % 3u, cell = e / 3u;
+  const uint64_t v00 = window * ((uint64_t)a.Wn * a.Wn) + cell;
+  const uint64_t from = kind == 2 ? v00 + 1 : v00, to = kind == 0 ? v00 + 1 : v00 + a.Wn;
+  const float4 cp = a.clip[from], cq = a.clip[to];
+  const float p[4] = {cp.x, cp.y, cp.z, cp.w}, q[4] = {cq.x, cq.y, cq.z, cq.w};
+  const uint32_t c0 = a.color[from], c1 = a.color[to];
+  uint32_t px = 0xff000000u;  // (kept only if the edge left no fragment here: never)
+  draw_segment<true>(
+      p, q, a.half_w, a.half_h, a.W, a.H, (int32_t)gx, (int32_t)gy, []() {}, []() { return 0; },
+      [&](int, uint32_t, uint32_t, float, float t, float t_in, float t_out) {
+        const float s = t_in + t * (t_out - t_in);
+#pragma unroll
+        for (uint32_t ch = 0; ch < 3; ++ch) {
+          const float f0 = (float)((c0 >> (8u * ch)) & 255u), f1 = (float)((c1 >> (8u * ch)) & 255u);
+          float v = f0 + s * (f1 - f0);
+          if (!(v > 0.0f)) v = 0.0f;  // (a NaN too)
+          if (v > 255.0f) v = 255.0f;
+          px |= (uint32_t)(v + 0.5f) << (8u * ch);  // v + 0.5 >= 0: the conversion is floorf
+        }
+      });
+  return px;
 }
 
 struct RenderResolveArgs {
@@ -297,33 +495,45 @@ struct RenderResolveArgs {
   uint32_t outline_px;             // OUTLINE: outline_rgba as the image stores it
 };
 
-// K_rr: a thread per pixel of the group. OUTLINE: the rank after a node's points is its outline's, in outline_px as given
-template <bool OUTLINE>
-__global__ __launch_bounds__(256) void render_resolve_kernel(RenderResolveArgs a) {
+// K_rr: a thread per pixel of the group. OUTLINE: the rank after a node's points is its outline's, in outline_px as given.
+// TERRAIN: the ranks after the view's nodes are its layers' edges, 3 Wn^2 per layer; the colour is the fragment's, found by
+// walking the edge again from the stored window vertices (no side buffer that fragments would race for)
+template <bool OUTLINE, bool TERRAIN>
+__device__ __forceinline__ void render_resolve_pixels(const RenderResolveArgs& a, const RenderTerrainArgs& terrain) {
   const uint32_t lane = threadIdx.x & 63;
   for (uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x; p < a.npix; p += (uint64_t)gridDim.x * 256) {
     const uint32_t view = a.view0 + (uint32_t)(p / a.plane);
     const unsigned long long key = a.keys[p];
     const bool cov = key != kEmptyKey;
-    bool box = false;
+    bool box = false, ground = false;
     uint32_t px = 0xff000000u;  // (0, 0, 0, 255)
+    uint32_t layer = 0;         // TERRAIN: of a pixel a layer won
     float zw = 1.0f;
     if (cov) {
       const uint64_t s0 = a.view_seg[view], s1 = a.view_seg[view + 1];
-      const uint64_t g = a.seg_pts[s0] + (uint32_t)key;  // the point's place among the points of all views
-      uint64_t lo = s0, hi = s1;
-      while (hi - lo > 1) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (a.seg_pts[mid] <= g) lo = mid;
-        else hi = mid;
-      }
-      const BatchNode* nd = a.nodes + a.seg_node[lo];
-      if constexpr (OUTLINE) box = g - a.seg_pts[lo] == nd->n;
-      if (box) {
-        px = a.outline_px;
+      if constexpr (TERRAIN) ground = (uint64_t)(uint32_t)key >= a.seg_pts[s1] - a.seg_pts[s0];
+      if (ground) {
+        const uint64_t per = 3ull * terrain.Wn * terrain.Wn, r = (uint64_t)(uint32_t)key - (a.seg_pts[s1] - a.seg_pts[s0]);
+        const uint32_t q = (uint32_t)((p % a.plane) / terrain.W);
+        layer = (uint32_t)(r / per);
+        px = terrain_fragment_color(terrain, (uint64_t)(view - a.view0) * terrain.L + layer, (uint32_t)(r % per), (uint32_t)((p % a.plane) % terrain.W),
+                                    terrain.H - 1u - q);
       } else {
-        const uint8_t* c = a.rgb + 3 * (nd->point_off + (g - a.seg_pts[lo]));
-        px = (uint32_t)a.lut[c[0]] | (uint32_t)a.lut[c[1]] << 8 | (uint32_t)a.lut[c[2]] << 16 | 0xff000000u;
+        const uint64_t g = a.seg_pts[s0] + (uint32_t)key;  // the point's place among the points of all views
+        uint64_t lo = s0, hi = s1;
+        while (hi - lo > 1) {
+          const uint64_t mid = (lo + hi) >> 1;
+          if (a.seg_pts[mid] <= g) lo = mid;
+          else hi = mid;
+        }
+        const BatchNode* nd = a.nodes + a.seg_node[lo];
+        if constexpr (OUTLINE) box = g - a.seg_pts[lo] == nd->n;
+        if (box) {
+          px = a.outline_px;
+        } else {
+          const uint8_t* c = a.rgb + 3 * (nd->point_off + (g - a.seg_pts[lo]));
+          px = (uint32_t)a.lut[c[0]] | (uint32_t)a.lut[c[1]] << 8 | (uint32_t)a.lut[c[2]] << 16 | 0xff000000u;
+        }
       }
       zw = __uint_as_float((uint32_t)(key >> 32));
     }
@@ -339,6 +549,16 @@ __global__ __launch_bounds__(256) void render_resolve_kernel(RenderResolveArgs a
     } else if (cov) {
       atomicAdd(a.covered + view, 1ull);
     }
+    if constexpr (TERRAIN) {  // the pixels each layer won: one add per wave for the layer of the wave's first such pixel
+      const unsigned long long gm = __ballot(ground);
+      if (gm) {
+        const uint32_t slot = view * terrain.L + layer, first = (uint32_t)(__ffsll(gm) - 1);
+        const uint32_t slot0 = (uint32_t)__shfl((int)slot, (int)first);
+        const unsigned long long same = __ballot(ground && slot == slot0);
+        if (ground && slot != slot0) atomicAdd(terrain.counters + 3 * (uint64_t)slot + 2, 1ull);
+        else if (lane == first) atomicAdd(terrain.counters + 3 * (uint64_t)slot0 + 2, (unsigned long long)__popcll(same));
+      }
+    }
     if constexpr (OUTLINE) {  // the pixels an outline won, counted the same way
       const unsigned long long bx = __ballot(box);
       if (one_view) {
@@ -350,12 +570,30 @@ __global__ __launch_bounds__(256) void render_resolve_kernel(RenderResolveArgs a
   }
 }
 
+template <bool OUTLINE>
+__global__ __launch_bounds__(256) void render_resolve_kernel(RenderResolveArgs a) {
+  render_resolve_pixels<OUTLINE, false>(a, RenderTerrainArgs{});
+}
+
+// K_rr over a frame with terrain layers: `t` holds the group's windows and the per-layer counters
+template <bool OUTLINE>
+__global__ __launch_bounds__(256) void render_resolve_terrain_kernel(RenderResolveArgs a, RenderTerrainArgs t) {
+  render_resolve_pixels<OUTLINE, true>(a, t);
+}
+
 struct ViewInfo {
   int32_t status = 0;
   uint32_t nodes_visible = 0, nodes_drawn = 0;
   uint64_t points_submitted = 0, points_drawn = 0, pixels_covered = 0;
   uint64_t segments_submitted = 0, segments_drawn = 0, outline_pixels = 0;  // show_octree_nodes
 };
+
+struct TerrainViewInfo {  // per (view, layer)
+  int64_t pos[2] = {0, 0};
+  uint64_t edges_submitted = 0, edges_drawn = 0, pixels_won = 0;
+};
+
+constexpr uint64_t kTerrainVertexBytes = 24;  // a window vertex: f32 clip point, mask, colour
 
 int resident_grid(pcv_ctx* ctx, const void* kernel, int* grid) {
   int cus = 0, per_cu = 0;
@@ -373,6 +611,8 @@ struct pcv_render {
   uint32_t* d_images = nullptr;
   float* d_depth = nullptr;
   std::vector<ViewInfo> info;
+  uint32_t L = 0;  // terrain layers
+  std::vector<TerrainViewInfo> terrain_info;  // V x L
 };
 
 extern "C" int pcv_render_check_params(const pcv_render_params* p) {
@@ -398,20 +638,39 @@ extern "C" void pcv_render_free(pcv_render* r) {
 }
 
 static int render_views(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree, const pcv_render_params* p,
-                        const pcv_render_overlay* overlay, pcv_render* r) {
+                        const pcv_render_overlay* overlay, const pcv_render_terrain_layers* terrain, pcv_render* r) {
   const bool outline = overlay && (overlay->flags & PCV_RENDER_OUTLINE_NODES);
   const uint32_t V = frusta->count, W = p->width, H = p->height;
-  const uint64_t plane = (uint64_t)W * H;
+  const uint32_t L = terrain ? terrain->num_layers : 0, Wn = L ? terrain->window : 0;
+  const uint64_t plane = (uint64_t)W * H, window_vertices = (uint64_t)Wn * Wn;
   r->V = V;
   r->W = W;
   r->H = H;
+  r->L = L;
   r->info.assign(V, ViewInfo());
+  r->terrain_info.assign((size_t)V * L, TerrainViewInfo());
   if (V == 0) return PCV_OK;
-  // the key planes of one group of views are the workspace; a single view over the limit is refused before anything is
-  // allocated
+  // the key planes of one group of views, and with terrain the group's window vertices, are the workspace; a single view
+  // over the limit is refused before anything is allocated
   const uint64_t workspace = p->max_workspace_bytes ? p->max_workspace_bytes : kDefaultWorkspace;
-  const uint64_t group_views = std::min<uint64_t>(V, workspace / (8 * plane));
-  if (group_views == 0) return ctx->fail(PCV_E_OOM, "render: the key plane of one view exceeds max_workspace_bytes");
+  const uint64_t view_bytes = 8 * plane + (uint64_t)L * window_vertices * kTerrainVertexBytes;  // < 2^32 L
+  const uint64_t group_views = std::min<uint64_t>(V, workspace / view_bytes);
+  if (group_views == 0)
+    return ctx->fail(PCV_E_OOM, L ? "render: the key plane and the terrain windows of one view exceed max_workspace_bytes"
+                                  : "render: the key plane of one view exceeds max_workspace_bytes");
+  if (3 * window_vertices * L >= 0xffffffffull) return ctx->fail(PCV_E_INVALID, "render: a view's terrain edges take 2^32 - 1 draw ranks or more");
+  // step 13: every view's window over every layer
+  std::vector<PcvTerrainLayerView> layer_view(L);
+  std::vector<int64_t> window_pos((size_t)V * L * 2, 0);
+  for (uint32_t k = 0; k < L; ++k) {
+    if (int lrc = pcv_terrain_layer_view(terrain->layers[k], ctx, &layer_view[k])) return lrc;
+    for (uint32_t v = 0; v < V; ++v) {
+      int64_t* pos = &window_pos[2 * ((size_t)v * L + k)];
+      if (!pcv_terrain_window_pos(layer_view[k].grid, terrain->camera_positions + 3 * (size_t)v, Wn, pos))
+        return ctx->fail(PCV_E_INVALID, "Terrain location not representable.");
+      r->terrain_info[(size_t)v * L + k].pos[0] = pos[0], r->terrain_info[(size_t)v * L + k].pos[1] = pos[1];
+    }
+  }
   if (!tree->d_xyz && !tree->nodes.empty()) {  // an octree opened from a directory: node files are uploaded on first use
     int lrc = pcv_octree_load_device(tree);
     if (lrc) return lrc;
@@ -451,6 +710,8 @@ static int render_views(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree
       if (vi.points_submitted >= 0xffffffffull) return ctx->fail(PCV_E_INVALID, "render: a view draws 2^32 - 1 points or more");
       if (vi.points_submitted + vi.segments_submitted / 12 >= 0xffffffffull)
         return ctx->fail(PCV_E_INVALID, "render: a view's points and node outlines take 2^32 - 1 draw ranks or more");
+      if (vi.points_submitted + vi.segments_submitted / 12 + 3 * window_vertices * L >= 0xffffffffull)
+        return ctx->fail(PCV_E_INVALID, "render: a view's points, node outlines and terrain edges take 2^32 - 1 draw ranks or more");
     }
     view_seg[v + 1] = seg_node.size();
     view_chunk[v + 1] = seg_chunk.back();
@@ -470,6 +731,53 @@ static int render_views(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree
       (rc = sc.get(&d_seg_chunk, nseg + 1)) || (rc = sc.get(&d_seg_pts, nseg + 1)) || (rc = sc.get(&d_view_seg, (size_t)V + 1)) ||
       (rc = sc.get(&d_desc, std::max<uint64_t>(nchunks, 1))))
     return rc;
+  RenderTerrainArgs ta{};
+  if (L) {
+    TerrainLayerDev* d_layers;
+    int64_t* d_pos;
+    uint32_t* d_status;
+    float4* d_clip;
+    uint32_t *d_mask, *d_color;
+    unsigned long long* d_tcounters;
+    const uint64_t nvert = group_views * L * window_vertices;
+    if ((rc = sc.get(&d_layers, L)) || (rc = sc.get(&d_pos, window_pos.size())) || (rc = sc.get(&d_status, V)) || (rc = sc.get(&d_clip, nvert)) ||
+        (rc = sc.get(&d_mask, nvert)) || (rc = sc.get(&d_color, nvert)) || (rc = sc.get(&d_tcounters, 3 * (size_t)V * L)))
+      return rc;
+    std::vector<TerrainLayerDev> layers(L);
+    for (uint32_t k = 0; k < L; ++k) {
+      layers[k].grid = layer_view[k].grid;
+      layers[k].ntiles = layer_view[k].ntiles;
+      layers[k].tile_keys = layer_view[k].d_tile_keys;
+      layers[k].heights = layer_view[k].d_heights;
+      layers[k].colors = layer_view[k].d_colors;
+      layers[k].T = layer_view[k].T;
+      layers[k].pad = 0;
+    }
+    std::vector<uint32_t> view_status(V);
+    for (uint32_t v = 0; v < V; ++v) view_status[v] = (uint32_t)status[v];
+    // pageable sources: the copies have left the vectors when the calls return
+    PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_layers, layers.data(), sizeof(TerrainLayerDev) * L, hipMemcpyHostToDevice, ctx->stream));
+    PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_pos, window_pos.data(), 8 * window_pos.size(), hipMemcpyHostToDevice, ctx->stream));
+    PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_status, view_status.data(), 4 * (size_t)V, hipMemcpyHostToDevice, ctx->stream));
+    PCV_HIP_CHECK(ctx, hipMemsetAsync(d_tcounters, 0, 8 * 3 * (size_t)V * L, ctx->stream));
+    ta.layers = d_layers;
+    ta.pos = d_pos;
+    ta.view_status = d_status;
+    ta.shapes = frusta->dev;
+    ta.view_seg = d_view_seg;
+    ta.seg_rank = d_seg_pts;
+    ta.clip = d_clip;
+    ta.mask = d_mask;
+    ta.color = d_color;
+    ta.keys = d_keys;
+    ta.counters = d_tcounters;
+    ta.L = L;
+    ta.Wn = Wn;
+    ta.W = W;
+    ta.H = H;
+    ta.half_w = 0.5f * (float)W;
+    ta.half_h = 0.5f * (float)H;
+  }
   uint8_t lut[256];
   if ((rc = pcv_render_gamma_lut(p->gamma, lut))) return ctx->fail(rc, "render: gamma");
   PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_lut, lut, 256, hipMemcpyHostToDevice, ctx->stream));
@@ -483,11 +791,14 @@ static int render_views(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree
   PCV_HIP_CHECK(ctx, hipMemcpyAsync(d_view_seg, view_seg.data(), 8 * ((size_t)V + 1), hipMemcpyHostToDevice, ctx->stream));
   const BatchNode* d_nodes = pcv_octree_query_nodes(tree);
   // grids of resident size that stride over chunks / pixels: no dispatch grows with V or with the node count
-  int splat_grid = 1, resolve_grid = 1, chunks_grid = 1, outline_grid = 1;
-  const void* resolve = outline ? (const void*)render_resolve_kernel<true> : (const void*)render_resolve_kernel<false>;
+  int splat_grid = 1, resolve_grid = 1, chunks_grid = 1, outline_grid = 1, gather_grid = 1, edges_grid = 1;
+  const void* resolve = L ? (outline ? (const void*)render_resolve_terrain_kernel<true> : (const void*)render_resolve_terrain_kernel<false>)
+                          : (outline ? (const void*)render_resolve_kernel<true> : (const void*)render_resolve_kernel<false>);
   if ((rc = resident_grid(ctx, (const void*)render_splat_kernel, &splat_grid)) || (rc = resident_grid(ctx, resolve, &resolve_grid)) ||
       (rc = resident_grid(ctx, (const void*)render_chunks_kernel, &chunks_grid)) ||
-      (outline && (rc = resident_grid(ctx, (const void*)render_outline_kernel, &outline_grid))))
+      (outline && (rc = resident_grid(ctx, (const void*)render_outline_kernel, &outline_grid))) ||
+      (L && ((rc = resident_grid(ctx, (const void*)render_terrain_gather_kernel, &gather_grid)) ||
+             (rc = resident_grid(ctx, (const void*)render_terrain_edges_kernel, &edges_grid)))))
     return rc;
   if (nchunks) {
     PcvProf prof(ctx, PCV_K_RENDER_CHUNKS);
@@ -557,19 +868,45 @@ static int render_views(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree
                          dim3(256), 0, ctx->stream, oa);
       PCV_HIP_CHECK(ctx, hipGetLastError());
     }
+    if (L) {  // after the group's points and outlines: the windows, then their edges
+      ta.view0 = v0;
+      ta.nv = nv;
+      const uint64_t side = (Wn + kTerrainPatch - 1) / kTerrainPatch;
+      {
+        PcvProf prof(ctx, PCV_K_RENDER_TERRAIN_GATHER);
+        hipLaunchKernelGGL(render_terrain_gather_kernel, dim3((uint32_t)std::min<uint64_t>((window_vertices * L * nv + 255) / 256, (uint64_t)gather_grid)),
+                           dim3(256), 0, ctx->stream, ta);
+        PCV_HIP_CHECK(ctx, hipGetLastError());
+      }
+      {
+        PcvProf prof(ctx, PCV_K_RENDER_TERRAIN_EDGES);
+        hipLaunchKernelGGL(render_terrain_edges_kernel, dim3((uint32_t)std::min<uint64_t>(side * side * L * nv, (uint64_t)edges_grid)), dim3(256), 0,
+                           ctx->stream, ta);
+        PCV_HIP_CHECK(ctx, hipGetLastError());
+      }
+    }
     ra.npix = plane * nv;
     ra.view0 = v0;
     {
       PcvProf prof(ctx, PCV_K_RENDER_RESOLVE);
       const dim3 grid((uint32_t)std::min<uint64_t>((ra.npix + 255) / 256, (uint64_t)resolve_grid));
-      if (outline) hipLaunchKernelGGL(render_resolve_kernel<true>, grid, dim3(256), 0, ctx->stream, ra);
+      if (L && outline) hipLaunchKernelGGL(render_resolve_terrain_kernel<true>, grid, dim3(256), 0, ctx->stream, ra, ta);
+      else if (L) hipLaunchKernelGGL(render_resolve_terrain_kernel<false>, grid, dim3(256), 0, ctx->stream, ra, ta);
+      else if (outline) hipLaunchKernelGGL(render_resolve_kernel<true>, grid, dim3(256), 0, ctx->stream, ra);
       else hipLaunchKernelGGL(render_resolve_kernel<false>, grid, dim3(256), 0, ctx->stream, ra);
       PCV_HIP_CHECK(ctx, hipGetLastError());
     }
   }
   std::vector<unsigned long long> h_counters(ncounters * (size_t)V);
   PCV_HIP_CHECK(ctx, hipMemcpyAsync(h_counters.data(), d_counters, 8 * ncounters * (size_t)V, hipMemcpyDeviceToHost, ctx->stream));
+  std::vector<unsigned long long> h_tcounters(3 * (size_t)V * L);
+  if (L) PCV_HIP_CHECK(ctx, hipMemcpyAsync(h_tcounters.data(), ta.counters, 8 * h_tcounters.size(), hipMemcpyDeviceToHost, ctx->stream));
   PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // the scratch is released on return
+  for (size_t k = 0; k < (size_t)V * L; ++k) {
+    r->terrain_info[k].edges_submitted = h_tcounters[3 * k];
+    r->terrain_info[k].edges_drawn = h_tcounters[3 * k + 1];
+    r->terrain_info[k].pixels_won = h_tcounters[3 * k + 2];
+  }
   for (uint32_t v = 0; v < V; ++v) {
     r->info[v].points_drawn = h_counters[v];
     r->info[v].pixels_covered = h_counters[(size_t)V + v];
@@ -598,10 +935,32 @@ extern "C" int pcv_render_views(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octr
 
 extern "C" int pcv_render_views_ex(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree, const pcv_render_params* params,
                                    const pcv_render_overlay* overlay, pcv_render** out) {
+  return pcv_render_views_terrain(ctx, frusta, tree, params, overlay, nullptr, out);
+}
+
+static const char* terrain_error(const pcv_render_terrain_layers* t) {
+  if (!t || t->num_layers == 0) return nullptr;
+  if (t->window < 2 || t->window > PCV_RENDER_TERRAIN_WINDOW || (t->window & 1u)) return "render: the terrain window must be even and in 2 ..= 1024";
+  if (!t->layers) return "render: null terrain layer array";
+  for (uint32_t k = 0; k < t->num_layers; ++k)
+    if (!t->layers[k]) return "render: a terrain layer is null";
+  if (!t->camera_positions) return "render: terrain layers need the camera positions of the views";
+  return nullptr;
+}
+
+extern "C" int pcv_render_check_terrain_host(const pcv_render_terrain_layers* terrain, char* message, uint64_t capacity) {
+  const char* why = terrain_error(terrain);
+  if (message && capacity) snprintf(message, (size_t)capacity, "%s", why ? why : "");
+  return why ? PCV_E_INVALID : PCV_OK;
+}
+
+extern "C" int pcv_render_views_terrain(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_octree* tree, const pcv_render_params* params,
+                                        const pcv_render_overlay* overlay, const pcv_render_terrain_layers* terrain, pcv_render** out) {
   if (!ctx) return PCV_E_INVALID;
   if (!frusta || !tree || !params || !out) return ctx->fail(PCV_E_INVALID, "null argument");
   *out = nullptr;
   if (const char* why = overlay_error(overlay)) return ctx->fail(PCV_E_INVALID, why);
+  if (const char* why = terrain_error(terrain)) return ctx->fail(PCV_E_INVALID, why);
   if (pcv_render_check_params(params) != PCV_OK)
     return ctx->fail(PCV_E_INVALID, "render: width and height in 1 ..= 16384, point_size in 1 ..= 64, gamma finite and > 0");
   if (frusta->ctx != ctx || tree->ctx != ctx) return ctx->fail(PCV_E_INVALID, "render: shapes and octree must belong to the context");
@@ -610,7 +969,7 @@ extern "C" int pcv_render_views_ex(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_o
     if (kind != PCV_SHAPE_FRUSTUM && kind != PCV_SHAPE_FRUSTUM_WITH_INVERSE) return ctx->fail(PCV_E_INVALID, "render: every shape must be a frustum");
   pcv_render* r = new pcv_render();
   r->ctx = ctx;
-  const int rc = render_views(ctx, frusta, tree, params, overlay, r);
+  const int rc = render_views(ctx, frusta, tree, params, overlay, terrain && terrain->num_layers ? terrain : nullptr, r);
   if (rc != PCV_OK) {
     (void)hipStreamSynchronize(ctx->stream);  // nothing queued may still write into what is freed here
     (void)hipGetLastError();
@@ -644,6 +1003,18 @@ extern "C" int pcv_render_outline_info(pcv_render* r, uint32_t view, uint64_t* s
   if (segments_submitted) *segments_submitted = vi.segments_submitted;
   if (segments_drawn) *segments_drawn = vi.segments_drawn;
   if (outline_pixels) *outline_pixels = vi.outline_pixels;
+  return PCV_OK;
+}
+
+extern "C" int pcv_render_terrain_info(pcv_render* r, uint32_t view, uint32_t layer, int64_t pos[2], uint64_t* edges_submitted,
+                                       uint64_t* edges_drawn, uint64_t* pixels_won) {
+  if (!r) return PCV_E_INVALID;
+  if (view >= r->V || layer >= r->L) return r->ctx->fail(PCV_E_INVALID, "render: view or terrain layer past the end");
+  const TerrainViewInfo& ti = r->terrain_info[(size_t)view * r->L + layer];
+  if (pos) pos[0] = ti.pos[0], pos[1] = ti.pos[1];
+  if (edges_submitted) *edges_submitted = ti.edges_submitted;
+  if (edges_drawn) *edges_drawn = ti.edges_drawn;
+  if (pixels_won) *pixels_won = ti.pixels_won;
   return PCV_OK;
 }
 

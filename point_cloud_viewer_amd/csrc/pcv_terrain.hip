@@ -10,12 +10,16 @@
 //   finish    terrain_count_kernel (set vertices per slot), the tiles with a set vertex sorted by (x, y) on the host,
 //             terrain_resolve_kernel (accumulators -> height, colour, count in the output layout), terrain_mask_kernel (the
 //             set flags of a vertex's 3 x 3 neighbourhood through the tile table -> the quad mask), accumulators released
+//   from_tiles / open_dir   a finished terrain from tiles made elsewhere (a directory written earlier): the tiles sorted by
+//             (x, y) and copied to the device; no accumulators, no counts. pcv_terrain_layer_view hands the renderer
+//             (pcv_render.hip) the tiles and a sorted key per tile, made on first use
 // Every result is an exact function of the multiset of points: integer sums and a total-order maximum.
 #include <sys/stat.h>
 
 #include <algorithm>
 #include <cerrno>
 #include <cstring>
+#include <new>
 
 #include "pcv_internal.h"
 #include "pcv_query_dev.h"
@@ -23,6 +27,7 @@
 #include "pcv_s2_query_dev.h"
 #include "pcv_terrain_dev.h"
 #include "pcv_terrain_files.h"
+#include "pcv_terrain_obj.h"
 
 namespace {
 
@@ -236,7 +241,9 @@ struct pcv_terrain {
   std::vector<int32_t> positions;  // 2 per kept tile
   float* d_heights = nullptr;
   uint8_t* d_colors = nullptr;
-  uint32_t* d_counts = nullptr;
+  uint32_t* d_counts = nullptr;    // null for a terrain made from tiles
+  int64_t* d_tile_keys = nullptr;  // the renderer's tile table (pcv_terrain_layer_view), made on first use
+  bool from_tiles = false;
 
   void free_pool() {
     for (void* p : chunks) ctx->dev_free(p);
@@ -255,10 +262,11 @@ struct pcv_terrain {
     (void)hipStreamSynchronize(ctx->stream);
     free_pool();
     free_staging();
-    for (void* p : {(void*)dev.table, (void*)dev.slot_tile, (void*)dev.slot_base, (void*)dev.ctr, (void*)d_heights, (void*)d_colors, (void*)d_counts})
+    for (void* p : {(void*)dev.table, (void*)dev.slot_tile, (void*)dev.slot_base, (void*)dev.ctr, (void*)d_heights, (void*)d_colors, (void*)d_counts,
+                    (void*)d_tile_keys})
       if (p) ctx->dev_free(p);
     dev.table = dev.slot_tile = nullptr, dev.slot_base = dev.ctr = nullptr;
-    d_heights = nullptr, d_colors = nullptr, d_counts = nullptr;
+    d_heights = nullptr, d_colors = nullptr, d_counts = nullptr, d_tile_keys = nullptr;
   }
   int die(int code, const std::string& msg) {
     release_all();
@@ -272,7 +280,9 @@ namespace {
 int usable(pcv_terrain* t, bool want_finished) {
   if (t->dead) return t->ctx->fail(PCV_E_INVALID, "the terrain failed earlier and can only be freed");
   if (t->finished != want_finished)
-    return t->ctx->fail(PCV_E_INVALID, want_finished ? "the terrain is not finished" : "the terrain is finished: no more points");
+    return t->ctx->fail(PCV_E_INVALID, want_finished       ? "the terrain is not finished"
+                                       : t->from_tiles ? "the terrain was made from tiles: it takes no points"
+                                                       : "the terrain is finished: no more points");
   return PCV_OK;
 }
 
@@ -665,7 +675,9 @@ extern "C" int pcv_terrain_colors(pcv_terrain* t, uint64_t first_tile, uint64_t 
 extern "C" int pcv_terrain_counts(pcv_terrain* t, uint64_t first_tile, uint64_t num_tiles, int mem, uint32_t* out) {
   if (!t) return PCV_E_INVALID;
   int rc;
-  if ((rc = usable(t, true)) || (rc = check_range_output(t, first_tile, num_tiles, mem, out))) return rc;
+  if ((rc = usable(t, true))) return rc;
+  if (t->from_tiles) return t->ctx->fail(PCV_E_INVALID, "the terrain was made from tiles: it has no point counts");
+  if ((rc = check_range_output(t, first_tile, num_tiles, mem, out))) return rc;
   const uint64_t per = t->dev.cells;
   return copy_out(t, t->d_counts + first_tile * per, num_tiles * per * sizeof(uint32_t), mem, out);
 }
@@ -711,6 +723,114 @@ extern "C" int pcv_terrain_write_dir(pcv_terrain* t, const char* directory) {
   const std::string json = pcv_terrain_meta_json(t->params, nk, t->positions.data());
   std::string why;
   if (int r = pcv_terrain_write_file(dir + "/meta.json", json.data(), json.size(), &why)) return ctx->fail(r, why);
+  return PCV_OK;
+}
+
+extern "C" int pcv_terrain_from_tiles(pcv_ctx* ctx, const pcv_terrain_params* params, uint64_t num_tiles, const int32_t* positions, const float* heights,
+                                      const uint8_t* colors, int mem, pcv_terrain** out) {
+  if (!ctx) return PCV_E_INVALID;
+  if (!out) return ctx->fail(PCV_E_INVALID, "null argument");
+  *out = nullptr;
+  std::string why;
+  if (pcv_terrain_check_params(params, &why)) return ctx->fail(PCV_E_INVALID, why);
+  if (mem != PCV_MEM_HOST && mem != PCV_MEM_DEVICE) return ctx->fail(PCV_E_INVALID, "bad mem");
+  if (num_tiles > kMaxTiles) return ctx->fail(PCV_E_INVALID, "terrain: more than 2^22 tiles");
+  if (num_tiles && (!positions || !heights || !colors)) return ctx->fail(PCV_E_INVALID, "null tile arrays");
+  // ascending by (x, y), as finish leaves them
+  std::vector<uint64_t> order(num_tiles);
+  for (uint64_t k = 0; k < num_tiles; ++k) order[k] = k;
+  auto key = [&](uint64_t k) { return pcv_terrain_tile_key(positions[2 * k], positions[2 * k + 1]); };
+  std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return key(a) < key(b); });
+  for (uint64_t k = 1; k < num_tiles; ++k)
+    if (key(order[k]) == key(order[k - 1]))
+      return ctx->fail(PCV_E_INVALID, "terrain: tile (" + std::to_string(positions[2 * order[k]]) + ", " + std::to_string(positions[2 * order[k] + 1]) +
+                                          ") is given twice");
+  PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  pcv_terrain* t = new (std::nothrow) pcv_terrain;
+  if (!t) return ctx->fail(PCV_E_OOM, "out of host memory");
+  t->ctx = ctx, t->params = *params;
+  t->dev.grid = pcv_terrain_grid(*params);
+  t->dev.T = params->tile_size, t->dev.statistic = params->statistic, t->dev.min_points = params->min_points;
+  t->dev.cells = (uint64_t)t->dev.T * t->dev.T;
+  t->from_tiles = true, t->finished = true;
+  t->positions.resize(2 * num_tiles);
+  for (uint64_t k = 0; k < num_tiles; ++k) t->positions[2 * k] = positions[2 * order[k]], t->positions[2 * k + 1] = positions[2 * order[k] + 1];
+  int rc = PCV_OK;
+  if (num_tiles) {
+    const uint64_t hper = t->dev.cells * 2, cper = t->dev.cells * 4;
+    if ((rc = alloc(t, &t->d_heights, num_tiles * hper)) || (rc = alloc(t, &t->d_colors, num_tiles * cper))) {
+      t->release_all();
+      delete t;
+      return rc;
+    }
+    const hipMemcpyKind kind = mem == PCV_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    // runs of tiles that are already in order go in one copy each
+    for (uint64_t k = 0; k < num_tiles && rc == PCV_OK;) {
+      uint64_t n = 1;
+      while (k + n < num_tiles && order[k + n] == order[k] + n) ++n;
+      if (hipMemcpyAsync(t->d_heights + k * hper, heights + order[k] * hper, n * hper * sizeof(float), kind, ctx->stream) != hipSuccess ||
+          hipMemcpyAsync(t->d_colors + k * cper, colors + order[k] * cper, n * cper, kind, ctx->stream) != hipSuccess)
+        rc = ctx->fail(PCV_E_HIP, "terrain: copying tiles to the device failed");
+      k += n;
+    }
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == PCV_OK) rc = ctx->fail(PCV_E_HIP, "terrain: copying tiles to the device failed");
+    if (rc) {
+      t->release_all();
+      delete t;
+      return rc;
+    }
+  }
+  *out = t;
+  return PCV_OK;
+}
+
+extern "C" int pcv_terrain_open_dir(pcv_ctx* ctx, const char* directory, pcv_terrain** out) {
+  if (!ctx) return PCV_E_INVALID;
+  if (!directory || !out) return ctx->fail(PCV_E_INVALID, "null argument");
+  *out = nullptr;
+  const std::string dir = directory;
+  std::string text, why;
+  if (int rc = pcv_terrain_read_text(dir + "/meta.json", &text, &why)) return ctx->fail(rc, why);
+  pcv_terrain_params params;
+  std::vector<int32_t> positions;
+  if (int rc = pcv_terrain_meta_read(text.data(), text.size(), &params, &positions, &why)) return ctx->fail(rc, dir + "/" + why);
+  const uint64_t n = positions.size() / 2, cells = (uint64_t)params.tile_size * params.tile_size;
+  if (n > kMaxTiles) return ctx->fail(PCV_E_INVALID, "terrain: more than 2^22 tiles");
+  std::vector<float> heights;
+  std::vector<uint8_t> colors;
+  try {
+    heights.resize(n * cells * 2);
+    colors.resize(n * cells * 4);
+  } catch (const std::bad_alloc&) {
+    return ctx->fail(PCV_E_OOM, "out of host memory");
+  }
+  if (int rc = ctx->ring_ensure()) return rc;  // starts the host threads
+  std::vector<int> frc(2 * n, PCV_OK);
+  std::vector<std::string> fwhy(2 * n);
+  ctx->host_pool.run((size_t)(2 * n), [&](size_t f) {
+    const uint64_t k = f / 2;
+    const std::string name = dir + "/" + pcv_terrain_tile_name(positions[2 * k], positions[2 * k + 1]);
+    frc[f] = (f & 1) ? pcv_terrain_read_file(name + ".color", colors.data() + k * cells * 4, cells * 4, &fwhy[f])
+                     : pcv_terrain_read_file(name + ".height", heights.data() + k * cells * 2, cells * 8, &fwhy[f]);
+  });
+  for (size_t f = 0; f < frc.size(); ++f)
+    if (frc[f]) return ctx->fail(frc[f], fwhy[f]);
+  return pcv_terrain_from_tiles(ctx, &params, n, positions.data(), heights.data(), colors.data(), PCV_MEM_HOST, out);
+}
+
+int pcv_terrain_layer_view(pcv_terrain* t, pcv_ctx* ctx, PcvTerrainLayerView* out) {
+  if (!t || t->ctx != ctx) return ctx->fail(PCV_E_INVALID, "render: a terrain layer is null or of another context");
+  if (int rc = usable(t, true)) return rc;
+  const uint64_t n = t->positions.size() / 2;
+  if (n && !t->d_tile_keys) {
+    std::vector<int64_t> keys(n);
+    for (uint64_t k = 0; k < n; ++k) keys[k] = pcv_terrain_tile_key(t->positions[2 * k], t->positions[2 * k + 1]);
+    if (int rc = alloc(t, &t->d_tile_keys, n)) return rc;
+    PCV_HIP_CHECK(ctx, hipMemcpyAsync(t->d_tile_keys, keys.data(), n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // the vector goes away
+  }
+  out->grid = t->dev.grid, out->T = t->dev.T, out->ntiles = n;
+  out->d_tile_keys = t->d_tile_keys, out->d_heights = t->d_heights, out->d_colors = t->d_colors;
   return PCV_OK;
 }
 
@@ -763,6 +883,26 @@ extern "C" int pcv_terrain_tile_name_host(int32_t x, int32_t y, char* buf, uint6
   const std::string s = pcv_terrain_tile_name(x, y);
   if (!buf || cap < s.size() + 1) return pcv_host_fail(PCV_E_INVALID, "buffer too small for a tile name");
   std::memcpy(buf, s.c_str(), s.size() + 1);
+  return PCV_OK;
+}
+
+extern "C" int pcv_terrain_meta_read_host(const char* json, uint64_t len, pcv_terrain_params* params, uint64_t capacity, int32_t* positions,
+                                          uint64_t* num_tiles) {
+  if (!json || !params) return pcv_host_fail(PCV_E_INVALID, "null argument");
+  std::vector<int32_t> pos;
+  std::string why;
+  if (int rc = pcv_terrain_meta_read(json, (size_t)len, params, &pos, &why)) return pcv_host_fail(rc, why);
+  const uint64_t n = pos.size() / 2;
+  if (num_tiles) *num_tiles = n;
+  if (positions && std::min(n, capacity)) std::memcpy(positions, pos.data(), std::min(n, capacity) * 2 * sizeof(int32_t));
+  return PCV_OK;
+}
+
+extern "C" int pcv_render_terrain_window_host(const pcv_terrain_params* params, const double camera_position[3], uint32_t window, int64_t pos[2]) {
+  if (int rc = pcv_terrain_check_params_host(params)) return rc;
+  if (!camera_position || !pos) return pcv_host_fail(PCV_E_INVALID, "null argument");
+  if (window < 2 || window > 1024 || (window & 1)) return pcv_host_fail(PCV_E_INVALID, "render: the terrain window must be even and in 2 ..= 1024");
+  if (!pcv_terrain_window_pos(pcv_terrain_grid(*params), camera_position, window, pos)) return pcv_host_fail(PCV_E_INVALID, "Terrain location not representable.");
   return PCV_OK;
 }
 

@@ -233,6 +233,40 @@ class Context:
         self._check(self.lib.pcv_terrain_begin(self.handle, C.byref(pr), lo, hi, C.byref(h)))
         return Terrain(self, h, pr)
 
+    def terrain_open(self, directory):
+        """The finished Terrain of a terrain directory (pcv_terrain_open_dir): what Terrain.write leaves, or any directory
+        sdl_viewer --terrain reads. It serves tiles, heights, colors, info, write and OctreeResult.render(terrain=...)."""
+        import json
+        h = C.c_void_p()
+        self._check(self.lib.pcv_terrain_open_dir(self.handle, os.fsencode(str(directory)), C.byref(h)))
+        with open(os.path.join(str(directory), "meta.json")) as f:
+            meta = json.load(f)
+        iso = meta["world_from_terrain"]
+        pr = terrain_params(tile_size=meta["tile_size"], resolution_m=meta["resolution_m"], origin=meta["origin"],
+                            world_from_terrain=list(iso["translation"]) + list(iso["rotation"]))
+        return Terrain(self, h, pr)
+
+    def terrain_from_tiles(self, tile_size, world_from_terrain, origin, resolution_m, tiles, heights, colors):
+        """A finished Terrain from tiles made elsewhere (pcv_terrain_from_tiles); the arguments are read_terrain's keys:
+        tiles int32 [n, 2], heights float32 [n, T, T, 2], colors uint8 [n, T, T, 4], numpy arrays or torch device tensors.
+        The tiles are stored ascending by (x, y)."""
+        pr = terrain_params(tile_size=tile_size, resolution_m=resolution_m, origin=origin, world_from_terrain=world_from_terrain)
+        terrain_check_params(pr)
+        pos = np.ascontiguousarray(np.asarray(tiles, dtype=np.int32).reshape(-1, 2))
+        n, T = pos.shape[0], int(tile_size)
+        bh, bc = _Buf(heights, np.float32, "heights"), _Buf(colors, np.uint8, "colors")
+        if bh.size != n * T * T * 2 or bc.size != n * T * T * 4:
+            raise L.PcvError(L.PCV_E_INVALID, f"{n} tiles of {T} x {T} vertices take {n * T * T * 2} heights and {n * T * T * 4} colour bytes, "
+                                              f"got {bh.size} and {bc.size}")
+        if bh.device != bc.device:
+            raise ValueError("heights and colors must live in the same memory space")
+        if bh.device:
+            self.wait_torch()
+        h = C.c_void_p()
+        self._check(self.lib.pcv_terrain_from_tiles(self.handle, C.byref(pr), n, pos.ctypes.data, bh.ptr, bc.ptr,
+                                                    L.MEM_DEVICE if bh.device else L.MEM_HOST, C.byref(h)))
+        return Terrain(self, h, pr)
+
     def _points(self, x, y, z, color=None, intensity=None):
         bx, by, bz = _Buf(x, np.float64, "x"), _Buf(y, np.float64, "y"), _Buf(z, np.float64, "z")
         bc = _Buf(color, np.uint8, "color")
@@ -1250,21 +1284,53 @@ class OctreeResult:
         return xt
 
     def render(self, frusta, width, height, point_size=1.0, gamma=1.0, max_nodes=0, depth=False, max_workspace_bytes=None,
-               show_octree_nodes=False, outline_color=L.RENDER_OUTLINE_YELLOW):
+               show_octree_nodes=False, outline_color=L.RENDER_OUTLINE_YELLOW, terrain=None, camera_positions=None,
+               terrain_window=L.RENDER_TERRAIN_WINDOW):
         """The viewer's frame for every frustum of `frusta` (a Shapes of "frustum" / "frustum2" entries), rasterised on the
         device (pcv_render_views; sdl_viewer/src/lib.rs:158-209): get_visible_nodes, its first max_nodes entries (0: all)
         drawn as points of `point_size` pixels under a depth test, colours through `gamma`, over black. depth=True fetches
         the window-depth planes with the call (they are kept on the device either way). show_octree_nodes (the viewer's `O`
         key, lib.rs:202-208) draws the wireframe of every drawn node's cube right after the node's points, under the same
-        depth test, in `outline_color` (r, g, b, a) as given (pcv_render_views_ex). Returns a RenderedViews."""
+        depth test, in `outline_color` (r, g, b, a) as given (pcv_render_views_ex). `terrain`: a list of finished Terrains
+        or terrain directories, drawn after the nodes as the viewer's wireframe layers (sdl_viewer --terrain; DESIGN §9b
+        steps 13-18, pcv_render_views_terrain) in a window of `terrain_window` vertices around each view's camera, whose
+        world positions are `camera_positions` [V, 3]. Returns a RenderedViews."""
         p = render_params(width, height, point_size, gamma, max_nodes, max_workspace_bytes)
         h = C.c_void_p()
+        if terrain is not None and len(terrain):
+            return self._render_terrain(frusta, p, render_overlay(show_octree_nodes, outline_color), list(terrain), camera_positions,
+                                        terrain_window, depth)
         if show_octree_nodes:
             o = render_overlay(True, outline_color)
             self.ctx._check(self.lib.pcv_render_views_ex(self.ctx.handle, frusta.handle, self.handle, C.byref(p), C.byref(o), C.byref(h)))
         else:
             self.ctx._check(self.lib.pcv_render_views(self.ctx.handle, frusta.handle, self.handle, C.byref(p), C.byref(h)))
         return RenderedViews(self.ctx, h, frusta.count, int(width), int(height), bool(depth))
+
+    def _render_terrain(self, frusta, p, overlay, terrain, camera_positions, window, depth):
+        if camera_positions is None:
+            raise L.PcvError(L.PCV_E_INVALID, "render: terrain layers need camera_positions [V, 3]")
+        cams = np.ascontiguousarray(camera_positions, dtype=np.float64)
+        if cams.shape != (frusta.count, 3):
+            raise L.PcvError(L.PCV_E_INVALID, f"camera_positions: expected shape ({frusta.count}, 3), got {cams.shape}")
+        opened = []
+        try:
+            layers = []
+            for t in terrain:
+                if not isinstance(t, Terrain):
+                    t = self.ctx.terrain_open(t)
+                    opened.append(t)
+                t._live()
+                layers.append(t)
+            arr = (C.c_void_p * len(layers))(*[t.handle.value if isinstance(t.handle, C.c_void_p) else t.handle for t in layers])
+            tl = L.RenderTerrainLayers(len(layers), int(window), arr, cams.ctypes.data)
+            h = C.c_void_p()
+            self.ctx._check(self.lib.pcv_render_views_terrain(self.ctx.handle, frusta.handle, self.handle, C.byref(p), C.byref(overlay),
+                                                              C.byref(tl), C.byref(h)))
+        finally:
+            for t in opened:
+                t.free()
+        return RenderedViews(self.ctx, h, frusta.count, int(p.width), int(p.height), bool(depth), len(layers))
 
     def nodes_blob(self, node_indices):
         """octree_web_viewer's /nodes_data reply body for the given nodes."""
@@ -2011,6 +2077,44 @@ def render_check_overlay(overlay):
         raise L.PcvError(rc, msg.value.decode())
 
 
+def render_check_terrain(num_layers, window, layers=True, camera_positions=True):
+    """pcv_render_check_terrain_host (host only) over a pcv_render_terrain_layers with `num_layers` entries: `layers` True
+    (placeholders that are never read), None (a null array) or a list with None for a null entry; `camera_positions` True or
+    None. Raises PcvError with the library's message."""
+    n = int(num_layers)
+    arr = None
+    if layers is not None:
+        entries = [1] * n if layers is True else [None if e is None else 1 for e in layers]
+        arr = (C.c_void_p * max(len(entries), 1))(*entries)
+    cams = (C.c_double * 3)() if camera_positions is not None else None
+    tl = L.RenderTerrainLayers(n, int(window), arr, C.cast(cams, C.c_void_p) if cams is not None else None)
+    msg = C.create_string_buffer(256)
+    rc = L.load_library().pcv_render_check_terrain_host(C.byref(tl), msg, 256)
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, msg.value.decode())
+
+
+def render_terrain_window(params, camera_pos, window=L.RENDER_TERRAIN_WINDOW):
+    """The window position (two ints) of a camera at `camera_pos` (world frame) over the grid of `params` (terrain_params or
+    its arguments) for a window of `window` vertices (pcv_render_terrain_window_host)."""
+    cam = (C.c_double * 3)(*[float(v) for v in camera_pos])
+    pos = (C.c_int64 * 2)()
+    _host_check(L.load_library().pcv_render_terrain_window_host(C.byref(_terrain_pr(params)), cam, int(window), pos), "pcv_render_terrain_window_host")
+    return int(pos[0]), int(pos[1])
+
+
+def terrain_meta_read(text):
+    """meta.json's text through the library's reader (pcv_terrain_meta_read_host): dict(tile_size, world_from_terrain [7],
+    origin [3], resolution_m, tiles int32 [n, 2]). Raises PcvError naming the key that is missing or cut off."""
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    lib, pr, n = L.load_library(), L.TerrainParams(), C.c_uint64()
+    _host_check(lib.pcv_terrain_meta_read_host(raw, len(raw), C.byref(pr), 0, None, C.byref(n)), "pcv_terrain_meta_read_host")
+    pos = np.zeros((n.value, 2), dtype=np.int32)
+    _host_check(lib.pcv_terrain_meta_read_host(raw, len(raw), C.byref(pr), n.value, pos.ctypes.data, C.byref(n)), "pcv_terrain_meta_read_host")
+    return dict(tile_size=int(pr.tile_size), world_from_terrain=np.array(list(pr.world_from_terrain)), origin=np.array(list(pr.origin)),
+                resolution_m=float(pr.resolution_m), tiles=pos)
+
+
 def render_gamma_lut(gamma):
     """pcv_render_gamma_lut (host only): the 256-entry colour table of the frame for `gamma`."""
     lut = np.zeros(256, dtype=np.uint8)
@@ -2023,9 +2127,9 @@ def render_gamma_lut(gamma):
 class RenderedViews:
     """The result of OctreeResult.render: one RGBA8 frame and one window-depth plane per view, on the device."""
 
-    def __init__(self, ctx, handle, num_views, width, height, depth):
+    def __init__(self, ctx, handle, num_views, width, height, depth, num_terrain_layers=0):
         self.ctx, self.lib, self.handle = ctx, ctx.lib, handle
-        self.num_views, self.width, self.height = num_views, width, height
+        self.num_views, self.width, self.height, self.num_terrain_layers = num_views, width, height, num_terrain_layers
         ctx._children.add(self)
         self._depth = None
         if depth:
@@ -2072,6 +2176,14 @@ class RenderedViews:
         ss, sd, op = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self.ctx._check(self.lib.pcv_render_outline_info(self.handle, int(view), C.byref(ss), C.byref(sd), C.byref(op)))
         return dict(segments_submitted=ss.value, segments_drawn=sd.value, outline_pixels=op.value)
+
+    def terrain_info(self, view, layer):
+        """dict(pos, edges_submitted, edges_drawn, pixels_won) of one terrain layer in one view: the window position (two
+        ints), the edges the mask test draws, those that survived the clip, the pixels of the image the layer won."""
+        self._alive()
+        pos, es, ed, pw = (C.c_int64 * 2)(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self.ctx._check(self.lib.pcv_render_terrain_info(self.handle, int(view), int(layer), pos, C.byref(es), C.byref(ed), C.byref(pw)))
+        return dict(pos=(int(pos[0]), int(pos[1])), edges_submitted=es.value, edges_drawn=ed.value, pixels_won=pw.value)
 
     def write_png(self, directory):
         """One view_<index>.png per view (pcv_xray_png_encode's stored-deflate PNG); returns the paths."""

@@ -100,6 +100,16 @@ pub struct PcvRenderOverlay {
     pub outline_rgba: [u8; 4],
 }
 
+/// include/pcv_hip.h pcv_render_terrain_layers: the terrain layers pcv_render_views_terrain draws after the nodes
+/// (sdl_viewer --terrain). `camera_positions`: views x 3 doubles, world frame.
+#[repr(C)]
+pub struct PcvRenderTerrainLayers {
+    pub num_layers: u32,
+    pub window: u32,
+    pub layers: *const *mut pcv_terrain,
+    pub camera_positions: *const c_double,
+}
+
 /// include/pcv_hip.h pcv_ooc_stats: what an out-of-core build did (points, nodes, partitions, host spill, link traffic, phase times).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -182,6 +192,8 @@ extern "C" {
     fn pcv_s2_free(c: *mut pcv_s2_cloud);
     fn pcv_render_views(ctx: *mut pcv_ctx, frusta: *const pcv_shapes, t: *mut pcv_octree, params: *const PcvRenderParams, out: *mut *mut pcv_render) -> c_int;
     fn pcv_render_views_ex(ctx: *mut pcv_ctx, frusta: *const pcv_shapes, t: *mut pcv_octree, params: *const PcvRenderParams, overlay: *const PcvRenderOverlay, out: *mut *mut pcv_render) -> c_int;
+    fn pcv_render_views_terrain(ctx: *mut pcv_ctx, frusta: *const pcv_shapes, t: *mut pcv_octree, params: *const PcvRenderParams, overlay: *const PcvRenderOverlay, terrain: *const PcvRenderTerrainLayers, out: *mut *mut pcv_render) -> c_int;
+    fn pcv_terrain_open_dir(ctx: *mut pcv_ctx, directory: *const std::os::raw::c_char, out: *mut *mut pcv_terrain) -> c_int;
     fn pcv_render_images(r: *mut pcv_render, first: u32, count: u32, rgba: *mut c_void, mem: c_int) -> c_int;
     fn pcv_render_free(r: *mut pcv_render);
 }
@@ -900,6 +912,47 @@ impl HipOctree {
             self.ctx.check(rc);
             rgba
         })
+    }
+
+    /// `render` with the terrain layers of `sdl_viewer --terrain <dir>...` (src/lib.rs:602-606, terrain_drawer/mod.rs:152-187):
+    /// every directory is opened on the device and drawn after the nodes as the viewer's wireframe, in a window of
+    /// `terrain_window` vertices (the viewer's is 1024) around `camera_position`, the camera's place in the world frame
+    /// (the translation of the viewer's `local_from_global` inverse, which `TerrainDrawer::camera_changed` takes).
+    pub fn render_with_terrain(&self, world_to_gl: &Matrix4<f64>, camera_position: &[f64; 3], terrain_directories: &[std::path::PathBuf],
+                               terrain_window: u32, width: u32, height: u32, point_size: f32, gamma: f32, max_nodes_to_display: usize,
+                               show_octree_nodes: bool) -> Vec<u8> {
+        use std::os::unix::ffi::OsStrExt;
+        let mut shape = PcvShape { kind: 2, reserved: 0, params: [0.0; 32] };
+        shape.params[..16].copy_from_slice(world_to_gl.as_slice());
+        let params = PcvRenderParams { width, height, point_size, gamma, max_nodes: max_nodes_to_display.min(u32::MAX as usize) as u32, max_workspace_bytes: 0 };
+        let _g = self.lock.lock().unwrap();
+        let mut layers: Vec<*mut pcv_terrain> = Vec::new();
+        for dir in terrain_directories {
+            let path = std::ffi::CString::new(dir.as_os_str().as_bytes()).expect("a path without NUL");
+            let mut t = std::ptr::null_mut();
+            let rc = unsafe { pcv_terrain_open_dir(self.ctx.0, path.as_ptr(), &mut t) };
+            if rc != 0 {
+                layers.iter().for_each(|&l| unsafe { pcv_terrain_free(l) });
+                self.ctx.check(rc);
+            }
+            layers.push(t);
+        }
+        let rgba = self.with_shape(&shape, &[], |shapes| {
+            let mut frame = std::ptr::null_mut();
+            let overlay = PcvRenderOverlay { flags: show_octree_nodes as u32, outline_rgba: [255, 255, 0, 255] };
+            let terrain = PcvRenderTerrainLayers { num_layers: layers.len() as u32, window: terrain_window, layers: layers.as_ptr(),
+                                                   camera_positions: camera_position.as_ptr() };
+            let mut rc = unsafe { pcv_render_views_terrain(self.ctx.0, shapes, self.tree, &params, &overlay, &terrain, &mut frame) };
+            let mut rgba = vec![0u8; 4 * width as usize * height as usize];
+            if rc == 0 {
+                rc = unsafe { pcv_render_images(frame, 0, 1, rgba.as_mut_ptr() as *mut c_void, 0) };
+                unsafe { pcv_render_free(frame) };
+            }
+            (rc, rgba)
+        });
+        layers.iter().for_each(|&l| unsafe { pcv_terrain_free(l) });
+        self.ctx.check(rgba.0);
+        rgba.1
     }
 }
 

@@ -18,8 +18,15 @@ outlines-off wall time is also measured next to the parent's: fresh processes, o
 times (the way tools/ab_libs.sh alternates variants), each building the cloud itself. The off path launches the instances
 the parent launches, so a difference beyond the spread of those runs is a finding, recorded with the figures.
 
+--terrain: the same case without and with one terrain layer built from the same tree (resolution_m 0.1, tile size 256; the
+viewer's window of 1024 vertices around each eye), alternating in one process (profiles/render_terrain_bench.json): per
+point size and setting the wall time, the per-kernel times (render_terrain_gather_kernel and render_terrain_edges_kernel
+among them), the edges and the pixels the layer won, and view 0 against tests/render_terrain_oracle.py when the layer has
+at most 256 tiles (the oracle holds them on the host).
+
 usage: python tools/render_bench.py [--points N] [--views V] [--size WxH] [--steps K] [--out FILE]
-       python tools/render_bench.py --outlines [--parent-library FILE] [--ab-reps R] [...]"""
+       python tools/render_bench.py --outlines [--parent-library FILE] [--ab-reps R] [...]
+       python tools/render_bench.py --terrain [--terrain-resolution R] [--terrain-window N] [...]"""
 import argparse
 import hashlib
 import json
@@ -39,11 +46,13 @@ import oracle_lib as O  # noqa: E402
 import point_cloud_viewer_amd as pcv  # noqa: E402
 import render_oracle as R  # noqa: E402
 import render_outline_oracle as RO  # noqa: E402
+import render_terrain_oracle as RT  # noqa: E402
 from bench import build_hash, make_cloud  # noqa: E402
 
 HBM_PEAK = 8.0e12
 ATOMIC_PEAK_BYTES = 1.3e12  # chip-wide no-return global atomics, operand bytes per second
-KERNELS = ("visible_nodes_kernel", "render_chunks_kernel", "render_splat_kernel", "render_outline_kernel", "render_resolve_kernel")
+KERNELS = ("visible_nodes_kernel", "render_chunks_kernel", "render_splat_kernel", "render_outline_kernel", "render_terrain_gather_kernel",
+           "render_terrain_edges_kernel", "render_resolve_kernel")
 
 
 def oracle_view(tree, matrix, W, H, point_size, gamma, outlines=False):
@@ -61,7 +70,7 @@ def oracle_view(tree, matrix, W, H, point_size, gamma, outlines=False):
 
 
 def setup(args):
-    """The config-2 tree and the config-4 frusta of the case: (ctx, tree, mats, shapes)."""
+    """The config-2 tree and the config-4 frusta of the case: (ctx, tree, mats, shapes); the eyes are left in args.eyes."""
     dev = torch.device("cuda", 0)
     x, y, z, rgb = make_cloud(torch, args.points, seed=1, device=dev)
     ctx = pcv.Context(0)
@@ -72,9 +81,10 @@ def setup(args):
     bmin, bmax = meta["bbox_min"], meta["bbox_max"]
     rng = np.random.default_rng(3)  # config-4 frusta exactly as bench.py's query leg draws them
     persp = O.perspective3_new(1.0, 1.2, 0.1, 100.0)
-    mats = []
+    mats, args.eyes = [], []
     for _ in range(args.views):
         eye = rng.uniform(bmin, bmax)
+        args.eyes.append(eye)
         q = rng.normal(size=4)
         q = q / math.sqrt(float(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]))
         mats.append(O.frustum_new(eye, q, persp)[0])
@@ -184,6 +194,57 @@ def outlines(args, W, H):
     return 0 if ok else 1
 
 
+def terrain(args, W, H):
+    """--terrain: no layer and one layer of the same tree, alternating in one process."""
+    ctx, tree, mats, shapes = setup(args)
+    eyes = np.array(args.eyes)
+    t0 = time.perf_counter()
+    layer = tree.terrain(resolution_m=args.terrain_resolution, tile_size=256)
+    build_ms = (time.perf_counter() - t0) * 1e3
+    info = layer.info()
+    small = info["tiles"] <= 256
+    layer_dict = None
+    if small:
+        layer_dict = dict(tile_size=256, resolution_m=args.terrain_resolution, origin=np.zeros(3), world_from_terrain=np.array([0.0, 0, 0, 0, 0, 0, 1]),
+                          tiles=layer.tiles(), heights=layer.heights(), colors=layer.colors())
+    ctx.set_profiling(True)
+    runs, ok = [], True
+    for point_size in (1.0, 3.0):
+        for on in (False, True, False, True):
+            kw = dict(terrain=[layer], camera_positions=eyes, terrain_window=args.terrain_window) if on else {}
+            walls, split, infos, _, img0 = measure(ctx, tree, shapes, W, H, args.steps, point_size, **kw)
+            rec = dict(point_size=point_size, terrain=on, wall_ms_median=round(float(np.median(walls)), 3), wall_ms=[round(w, 3) for w in walls],
+                       kernel_ms=split, points_submitted=sum(i["points_submitted"] for i in infos), pixels_covered=sum(i["pixels_covered"] for i in infos))
+            if on:
+                rv = tree.render(shapes, W, H, point_size=point_size, **kw)
+                tinfo = [rv.terrain_info(v, 0) for v in range(shapes.count)]
+                rv.close()
+                rec.update(edges_submitted=sum(t["edges_submitted"] for t in tinfo), edges_drawn=sum(t["edges_drawn"] for t in tinfo),
+                           pixels_won=sum(t["pixels_won"] for t in tinfo))
+            if small or not on:
+                want = oracle_view(tree, mats[0], W, H, point_size, 1.0)
+                if on:
+                    want.update(status=0)
+                    RT.add_layers(want, want["points_submitted"], [layer_dict], eyes[0], mats[0], W, H, args.terrain_window)
+                digest, want_digest = hashlib.sha256(img0.tobytes()).hexdigest(), hashlib.sha256(want["image"].tobytes()).hexdigest()
+                ok = ok and digest == want_digest
+                rec.update(view0_digest=digest, view0_oracle_digest=want_digest, view0_equals_oracle=digest == want_digest)
+            runs.append(rec)
+    out = {"tool": "tools/render_bench.py --terrain", "build_hash": build_hash(), "device": torch.cuda.get_device_name(0),
+           "cloud": f"config 2: {args.points} Gaussian-cluster points (bench.make_cloud, seed 1), resolution {args.resolution}",
+           "nodes": tree.num_nodes, "views": args.views, "size": [W, H], "steps": args.steps,
+           "terrain": dict(resolution_m=args.terrain_resolution, tile_size=256, window=args.terrain_window, tiles=info["tiles"],
+                           set_vertices=info["set_vertices"], rendered_quads=info["rendered_quads"], build_ms=round(build_ms, 1)), "runs": runs}
+    print(json.dumps(out))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(json.dumps(out, indent=1) + "\n")
+    layer.free()
+    tree.free()
+    ctx.close()
+    return 0 if ok else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=100_000_000)
@@ -193,17 +254,23 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--outlines", action="store_true")
+    ap.add_argument("--terrain", action="store_true")
+    ap.add_argument("--terrain-resolution", type=float, default=0.1)
+    ap.add_argument("--terrain-window", type=int, default=1024)
     ap.add_argument("--parent-library", default=None)
     ap.add_argument("--ab-reps", type=int, default=2)
     ap.add_argument("--wall-only", action="store_true", help="one process of the parent comparison (used by --outlines)")
     args = ap.parse_args()
     W, H = (int(v) for v in args.size.split("x"))
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "render_outline_bench.json" if args.outlines else "render_bench.json")
+        args.out = os.path.join(ROOT, "profiles", "render_outline_bench.json" if args.outlines else
+                                "render_terrain_bench.json" if args.terrain else "render_bench.json")
     if args.wall_only:
         return wall_only(args, W, H)
     if args.outlines:
         return outlines(args, W, H)
+    if args.terrain:
+        return terrain(args, W, H)
 
     ctx, tree, mats, shapes = setup(args)
     stride = {1: 3, 2: 6, 3: 12, 4: 24}
