@@ -1,12 +1,13 @@
 /* query_to_ply.c — "the points under these map tiles, as a PLY", in plain C11 on top of the C ABI: what the reference does with
  * a PointQuery, stream_points_for_query and a PlyNodeWriter (src/read_write/ply.rs:559-732), over an octree directory or an S2
  * cell cloud directory (pcv_cloud_kind decides). The call sequence of a non-Python host:
- *   pcv_cloud_kind -> pcv_octree_open_dir | pcv_s2_open_dir -> pcv_shapes_create[_ex] -> pcv_query_batch_run |
+ *   pcv_cloud_kind -> pcv_octree_open_dir | pcv_s2_open_dir -> pcv_shapes_create[_ex | _ex2] -> pcv_query_batch_run |
  *   pcv_s2_query_run_ex -> pcv_query_batch_write_ply | pcv_s2_query_write_ply
  * The rows are packed on the device and reach the file in pieces: no point array is held on the host.
  *
  *   query_to_ply <cloud dir> (--aabb x0,y0,z0,x1,y1,z1 | --cells tok,.. | --map-tiles z | --all) [--filter NAME:LO:HI]
  *                [--attributes a,b] --output out.ply [--append] [--per-location out_%u.ply]
+ *   query_to_ply <cloud dir> --polygon FILE [--polygon-frame xy|web-mercator] [--z LO,HI] [the options above]
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -17,10 +18,16 @@
 static const char kUsage[] =
     "usage: query_to_ply <cloud dir> (--aabb x0,y0,z0,x1,y1,z1 | --cells tok,.. | --map-tiles z | --all) [--filter NAME:LO:HI]\n"
     "                    [--attributes a,b] --output out.ply [--append] [--per-location out_%u.ply]\n"
+    "       query_to_ply <cloud dir> --polygon FILE [--polygon-frame xy|web-mercator] [--z LO,HI] [the options above]\n"
     "  <cloud dir>       an octree directory or an S2 cell cloud directory (meta.pb decides)\n"
     "  --aabb            one location: an axis-aligned box in the cloud's coordinates\n"
     "  --cells           one location: the union of these S2 cells (tokens, ascending by id), over ECEF points\n"
     "  --map-tiles z     one location per web-mercator tile of zoom z (0 ..= 23) that the bounding box touches, over ECEF points\n"
+    "  --polygon FILE    one location: the polygon (even-odd) whose rings FILE holds, one `x y` pair per line, a blank line\n"
+    "                    between rings; the per-node counts are printed\n"
+    "  --polygon-frame   xy (default): the pairs are in the cloud's own x and y; web-mercator: they are `lat lng` in degrees,\n"
+    "                    over ECEF points\n"
+    "  --z LO,HI         the polygon's closed height range in the xy frame (default: unbounded)\n"
     "  --all             one location: every point\n"
     "  --filter          keep the points whose scalar attribute NAME lies in [LO, HI]; an octree knows `intensity` only\n"
     "  --attributes      the columns of a row behind x y z (default: every attribute of the cloud; an empty list: positions only)\n"
@@ -84,10 +91,43 @@ static int split_commas(char* arg, const char** fields, int cap) {
 #define MAX_CELLS 4096
 #define MAX_TILES 4096
 
-enum { LOC_NONE, LOC_AABB, LOC_CELLS, LOC_TILES, LOC_ALL };
+#define MAX_RINGS 4096
+#define MAX_VERTICES 65535
+
+enum { LOC_NONE, LOC_AABB, LOC_CELLS, LOC_TILES, LOC_ALL, LOC_POLYGON };
+
+/* one `x y` pair per line, a blank line between rings: ring_first (num_rings + 1 offsets) and the pairs */
+static int read_rings(const char* path, uint32_t* ring_first, uint32_t* num_rings, double* vertices, uint32_t* num_vertices) {
+  FILE* f = fopen(path, "r");
+  if (!f) return 0;
+  char line[256];
+  uint32_t nr = 0, nv = 0;
+  int open = 0, ok = 1;
+  ring_first[0] = 0;
+  while (ok && fgets(line, sizeof(line), f)) {
+    double a, b;
+    if (sscanf(line, "%lf %lf", &a, &b) == 2) {
+      if (nv == MAX_VERTICES) ok = 0;
+      else vertices[2 * nv] = a, vertices[2 * nv + 1] = b, ++nv, open = 1;
+    } else if (line[strspn(line, " \t\r\n")] == '\0') { /* a blank line closes the ring */
+      if (open && nr < MAX_RINGS) ring_first[++nr] = nv;
+      else if (open) ok = 0;
+      open = 0;
+    } else {
+      ok = 0;
+    }
+  }
+  if (ok && open && nr < MAX_RINGS) ring_first[++nr] = nv;
+  else if (open) ok = 0;
+  fclose(f);
+  *num_rings = nr, *num_vertices = nv;
+  return ok;
+}
 
 int main(int argc, char** argv) {
-  const char *dir = NULL, *output = NULL, *pattern = NULL;
+  const char *dir = NULL, *output = NULL, *pattern = NULL, *polygon_file = NULL;
+  int web_mercator = 0;
+  double z_range[2] = {-1.0 / 0.0, 1.0 / 0.0};
   int location = LOC_NONE, append = 0, have_attrs = 0, num_attrs = 0, num_filters = 0;
   double box[6] = {0};
   long zoom = -1;
@@ -127,6 +167,21 @@ int main(int argc, char** argv) {
       zoom = strtol(argv[++i], &end, 10);
       if (end == argv[i] || *end || zoom < 0 || zoom > 23) return usage();
       location = LOC_TILES;
+    } else if (strcmp(a, "--polygon") == 0 && more && location == LOC_NONE) {
+      polygon_file = argv[++i];
+      location = LOC_POLYGON;
+    } else if (strcmp(a, "--polygon-frame") == 0 && more) {
+      ++i;
+      if (strcmp(argv[i], "xy") != 0 && strcmp(argv[i], "web-mercator") != 0) return usage();
+      web_mercator = strcmp(argv[i], "web-mercator") == 0;
+    } else if (strcmp(a, "--z") == 0 && more) {
+      const char* f[2];
+      if (split_commas(argv[++i], f, 2) != 2) return usage();
+      for (int k = 0; k < 2; ++k) {
+        char* end;
+        z_range[k] = strtod(f[k], &end);
+        if (end == f[k] || *end) return usage();
+      }
     } else if (strcmp(a, "--all") == 0 && location == LOC_NONE) {
       location = LOC_ALL;
     } else if (strcmp(a, "--filter") == 0 && more && num_filters < MAX_FILTERS) {
@@ -170,6 +225,9 @@ int main(int argc, char** argv) {
   double *intervals = NULL, lo[3], hi[3];
   pcv_s2_filter* filters = NULL;
   uint64_t *first = NULL, *offset = NULL;
+  static uint32_t ring_first[MAX_RINGS + 1];
+  static double vertices[2 * MAX_VERTICES];
+  uint32_t num_rings = 0, num_vertices = 0;
   const char* what = "open";
   rc = kind == PCV_CLOUD_S2 ? pcv_s2_open_dir(ctx, dir, &cloud) : pcv_octree_open_dir(ctx, dir, &tree);
   if (rc != PCV_OK) goto done;
@@ -210,6 +268,27 @@ int main(int argc, char** argv) {
       fprintf(stderr, "no web-mercator tiles for this bounding box (%d): %s\n", rc, pcv_host_last_error());
       goto cleanup;
     }
+  } else if (location == LOC_POLYGON) {
+    if (!read_rings(polygon_file, ring_first, &num_rings, vertices, &num_vertices)) {
+      fprintf(stderr, "%s: one `x y` pair per line, a blank line between rings (at most %d rings, %d vertices)\n", polygon_file, MAX_RINGS,
+              MAX_VERTICES);
+      rc = PCV_E_INVALID;
+      goto cleanup;
+    }
+    if (web_mercator) { /* `lat lng` in degrees -> normalized web-mercator x y */
+      static double lat[MAX_VERTICES], lng[MAX_VERTICES], u[MAX_VERTICES], v[MAX_VERTICES];
+      for (uint32_t k = 0; k < num_vertices; ++k) lat[k] = vertices[2 * k] * (3.141592653589793 / 180.0), lng[k] = vertices[2 * k + 1] * (3.141592653589793 / 180.0);
+      if ((rc = pcv_wmr_from_lat_lng(num_vertices, lat, lng, u, v)) != PCV_OK) goto done;
+      for (uint32_t k = 0; k < num_vertices; ++k) vertices[2 * k] = u[k], vertices[2 * k + 1] = v[k];
+    }
+    num_shapes = 1;
+    if (!(specs = (pcv_shape*)calloc(1, sizeof(pcv_shape)))) rc = PCV_E_OOM;
+    if (rc == PCV_OK) {
+      specs[0].kind = PCV_SHAPE_POLYGON; /* .reserved = 0: the first (and only) polygon */
+      specs[0].params[0] = web_mercator ? -1.0 / 0.0 : z_range[0];
+      specs[0].params[1] = web_mercator ? 1.0 / 0.0 : z_range[1];
+      specs[0].params[2] = web_mercator ? 1.0 : 0.0;
+    }
   } else if (location == LOC_CELLS && cloud) {
     num_unions = 1; /* an S2 cloud takes unions beside the shape table */
   } else {
@@ -222,8 +301,10 @@ int main(int argc, char** argv) {
   }
   if (rc != PCV_OK) goto done;
   if (num_shapes) {
-    rc = location == LOC_CELLS ? pcv_shapes_create_ex(ctx, specs, num_shapes, 1, union_first, cells, &shapes)
-                               : pcv_shapes_create(ctx, specs, num_shapes, &shapes);
+    const uint32_t one_polygon[2] = {0, num_rings};
+    rc = location == LOC_POLYGON ? pcv_shapes_create_ex2(ctx, specs, num_shapes, 0, NULL, NULL, 1, one_polygon, ring_first, vertices, &shapes)
+         : location == LOC_CELLS ? pcv_shapes_create_ex(ctx, specs, num_shapes, 1, union_first, cells, &shapes)
+                                 : pcv_shapes_create(ctx, specs, num_shapes, &shapes);
     if (rc != PCV_OK) goto done;
   }
   const uint32_t locations = num_shapes + num_unions;
@@ -268,6 +349,18 @@ int main(int argc, char** argv) {
   if (rc != PCV_OK) goto done;
   printf("%s: %u locations, %llu segments, %llu points %s %s\n", dir, locations, (unsigned long long)num_segments, (unsigned long long)written,
          append ? "appended to" : "written to", written ? output : "no file (a PLY without points is not written)");
+  if (location == LOC_POLYGON && num_segments) { /* the per-node (per-cell) counts */
+    uint32_t* node = (uint32_t*)calloc((size_t)num_segments, sizeof(uint32_t));
+    uint64_t* at = (uint64_t*)calloc((size_t)num_segments + 1, sizeof(uint64_t));
+    uint64_t shape_first[2];
+    if (!node || !at) rc = PCV_E_OOM;
+    if (rc == PCV_OK) rc = cloud ? pcv_s2_query_segments(query, shape_first, node, at) : pcv_query_batch_segments(batch, shape_first, node, at);
+    for (uint64_t k = 0; rc == PCV_OK && k < num_segments; ++k)
+      printf("  %s %u: %llu points\n", cloud ? "cell" : "node", node[k], (unsigned long long)(at[k + 1] - at[k]));
+    free(node);
+    free(at);
+    if (rc != PCV_OK) goto done;
+  }
   if (pattern) {
     first = (uint64_t*)calloc((size_t)locations + 1, sizeof(uint64_t));
     offset = (uint64_t*)calloc((size_t)num_segments + 1, sizeof(uint64_t));

@@ -622,7 +622,16 @@ int pcv_octree_open_dir(pcv_ctx* ctx, const char* directory, pcv_octree** out);
  *                                   constructor's checks (NaN or inverted bounds give a shape that contains nothing).
  *   PCV_SHAPE_S2_CELL_UNION         -  (no params)                             PointLocation::S2Cells(CellUnion): `reserved`
  *                                   is the index of the shape's union among the unions handed to pcv_shapes_create_ex. The
- *                                   query space is ECEF. Every other kind ignores `reserved`. */
+ *                                   query space is ECEF.
+ *   PCV_SHAPE_POLYGON               z_min, z_max, frame                        a polygon with holes, or several polygons, under
+ *                                   the even-odd rule: `reserved` is the index of the shape's polygon among those handed to
+ *                                   pcv_shapes_create_ex2, given as rings of (x, y) vertices, each ring implicitly closed.
+ *                                   frame 0 (xy): the vertices are in the cloud's own x and y and the location is the prism
+ *                                   polygon x [z_min, z_max], closed; either bound may be -inf / +inf, and z_min > z_max or a
+ *                                   NaN bound contains nothing. frame 1 (web-mercator): the vertices are normalized
+ *                                   web-mercator coordinates in [0, 1) as PCV_SHAPE_WEB_MERCATOR_RECT's, the query space is
+ *                                   ECEF, z_min and z_max must be -inf and +inf, and nothing wraps across x = 0.
+ *                                   Every other kind ignores `reserved`. */
 #define PCV_SHAPE_ALL 0
 #define PCV_SHAPE_AABB 1
 #define PCV_SHAPE_FRUSTUM 2
@@ -630,9 +639,11 @@ int pcv_octree_open_dir(pcv_ctx* ctx, const char* directory, pcv_octree** out);
 #define PCV_SHAPE_FRUSTUM_WITH_INVERSE 4
 #define PCV_SHAPE_WEB_MERCATOR_RECT 5
 #define PCV_SHAPE_S2_CELL_UNION 6
+#define PCV_SHAPE_POLYGON 7
 typedef struct pcv_shape {
   int32_t kind;
-  int32_t reserved; /* PCV_SHAPE_S2_CELL_UNION: index of the shape's union (pcv_shapes_create_ex); otherwise unused */
+  int32_t reserved; /* PCV_SHAPE_S2_CELL_UNION: index of the shape's union (pcv_shapes_create_ex); PCV_SHAPE_POLYGON: index of
+                     * the shape's polygon (pcv_shapes_create_ex2); otherwise unused */
   double params[32];
 } pcv_shape;
 typedef struct pcv_shapes pcv_shapes;
@@ -665,11 +676,53 @@ int pcv_shapes_create_ex(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t count, 
 /* The cells of shape i, a PCV_SHAPE_S2_CELL_UNION: *num_cells is the union's length, of which the first
  * min(length, capacity) are written to `cells` (nullable with capacity 0). PCV_E_INVALID for any other kind. */
 int pcv_shapes_union(pcv_shapes* shapes, uint32_t i, uint64_t capacity, uint64_t* cells, uint32_t* num_cells);
+/* The same with polygons as locations (PCV_SHAPE_POLYGON). The unions are taken as pcv_shapes_create_ex takes them. The
+ * polygons are host memory: polygon p's rings are polygon_first[p] .. polygon_first[p + 1], ring r's vertices
+ * ring_first[r] .. ring_first[r + 1], `vertices` holds x, y pairs; polygon_first[0] == ring_first[0] == 0. Polygons mix with the
+ * other six kinds in any order; a polygon may be named by several shapes or by none. pcv_shapes_create and
+ * pcv_shapes_create_ex refuse the kind. PCV_E_INVALID with a message for: a polygon without a ring, a ring with fewer than 3
+ * vertices, a vertex that is not finite, more than 65 535 vertices in one polygon, "polygon index out of range", a frame other
+ * than 0 or 1, and in frame 1 a vertex outside [0, 1) or a z range other than -inf, +inf.
+ *
+ * The point rule. Per polygon an edge table is built once: horizontal edges are dropped; every other edge is stored from its
+ * lower endpoint (lx, ly) to its upper (ux, uy), ly < uy, with slope = (ux - lx) / (uy - ly), one rounded f64 division.
+ * inside(px, py) is the parity of the number of edges with ly <= py && py < uy && px < lx + (py - ly) * slope (product and
+ * sum rounded separately). Two polygons that share an edge evaluate it identically whatever their orientation, so polygons
+ * that tile a region keep every point in exactly one of them. A point is kept iff inside(x, y) && z_min <= z && z <= z_max of
+ * its decoded f64 position (frame 0), or inside of its normalized projection, the chain pcv_wmr_project runs (frame 1); then
+ * the interval.
+ * The node rule, frame 0. For a node cube (min, edge) with hi = min + edge per axis: listed and descended into iff
+ * z_min <= hi.z && z_max >= min.z, and inside(min.x, min.y) or some edge (horizontal ones included) hits the square
+ * [min.x, hi.x] x [min.y, hi.y]: the edge's bounding interval overlaps the square's in x and in y, and the four corners'
+ * side = (bx - ax) * (cy - ay) - (by - ay) * (cx - ax) are neither all > 0 nor all < 0. A polygon has no Relation.
+ * The node and cell rule, frame 1: the node list over an octree and the cell list over an S2 cell cloud are those of the
+ * PCV_SHAPE_WEB_MERCATOR_RECT (min x, min y), (max x, max y) over the polygon's vertices.
+ * pcv_nodes_in_location, pcv_cull_points, pcv_cull_node_points, pcv_query_points, pcv_query_node_points and
+ * pcv_query_batch_run (and what reads its batches: PLY output, terrain layers) take such shapes; pcv_s2_cells_in_location and
+ * pcv_s2_query_run[_ex] take frame 1 and refuse frame 0 ("a polygon in the xy frame has no meaning over an ECEF cell cloud");
+ * pcv_cull_nodes, pcv_cull_nodes_sparse and pcv_visible_nodes refuse a table that holds one, naming the first. */
+int pcv_shapes_create_ex2(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t count, uint32_t num_unions, const uint32_t* union_first,
+                          const uint64_t* union_cells, uint32_t num_polygons, const uint32_t* polygon_first, const uint32_t* ring_first,
+                          const double* vertices, pcv_shapes** out);
+/* The rings of shape i, a PCV_SHAPE_POLYGON: *num_rings and *num_vertices are its counts; when ring_capacity >= *num_rings
+ * and vertex_capacity >= *num_vertices (and ring_capacity > 0), ring_first receives *num_rings + 1 offsets from 0 and
+ * `vertices` the x, y pairs, as given. PCV_E_INVALID for any other kind. */
+int pcv_shapes_polygon(pcv_shapes* shapes, uint32_t i, uint32_t ring_capacity, uint32_t* ring_first, uint32_t* num_rings,
+                       uint32_t vertex_capacity, double* vertices, uint32_t* num_vertices);
+/* Host twins of the polygon rules (no device, no context; messages through pcv_host_last_error): one polygon as num_rings rings,
+ * ring_first[0] == 0. _check_host: the validation above. _contains_host: the keep flag of n points in either frame, bit for
+ * bit the device's. _intersects_cubes_host: the node rule of frame 0 for m cubes (m x 4: min xyz, edge). */
+int pcv_polygon_check_host(uint32_t num_rings, const uint32_t* ring_first, const double* vertices, int32_t frame, double z_min, double z_max);
+int pcv_polygon_contains_host(uint32_t num_rings, const uint32_t* ring_first, const double* vertices, int32_t frame, double z_min,
+                              double z_max, uint64_t n, const double* x, const double* y, const double* z, uint8_t* keep);
+int pcv_polygon_intersects_cubes_host(uint32_t num_rings, const uint32_t* ring_first, const double* vertices, double z_min, double z_max,
+                                      uint64_t m, const double* cubes, uint8_t* intersects);
 void pcv_shapes_free(pcv_shapes* shapes);
 uint32_t pcv_shapes_count(const pcv_shapes* shapes);
 /* Inspect one prepared shape (tests): 8 corners, up to 26 axes. valid == 0: the matrix is not invertible. PCV_E_INVALID for
  * a shape with more than 26 axes (a web-mercator rectangle may have up to 45): use pcv_shapes_get_ex. Both calls are
- * PCV_E_INVALID for a cell union, which has neither corners nor axes: pcv_shapes_union gives its cells. */
+ * PCV_E_INVALID for a cell union, which has neither corners nor axes: pcv_shapes_union gives its cells; and for a polygon:
+ * pcv_shapes_polygon gives its rings. */
 int pcv_shapes_get(pcv_shapes* shapes, uint32_t i, double corners[24], double axes[78], uint32_t* num_axes, int* valid);
 /* The same for any shape: `axes` holds 3 * axes_capacity doubles (PCV_MAX_SHAPE_AXES always suffices); *num_axes is the
  * shape's count, of which the first min(count, axes_capacity) are written. */

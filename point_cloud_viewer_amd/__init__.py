@@ -16,6 +16,7 @@ from .octree import (Aabb, Context, OctreeResult, QueryBatch, RenderedViews, S2C
                      terrain_quad_masks, terrain_tile_name, terrain_vertex, terrain_meta_read,
                      render_check_overlay, render_check_params, render_gamma_lut, render_overlay, render_params,
                      render_check_terrain, render_terrain_window,
+                     polygon_check, polygon_contains, polygon_from_lat_lng, polygon_intersects_cubes,
                      web_mercator_rect_from_zoomed, wmr_contains, wmr_corners, wmr_from_lat_lng, wmr_math, wmr_project, wmr_to_lat_lng,
                      inpaint_xray_quadtree, merge_xray_quadtrees, png_decode, xray_check_params, xray_coloring, xray_finalize, xray_lanczos_taps, xray_leaf_tiles,
                      xray_bins, xray_check_attrs, xray_filters, xray_inpaint_check, xray_inpaint_plan, xray_merge_check, xray_open_host, xray_params, xray_png_encode, xray_png_encode_tiles)

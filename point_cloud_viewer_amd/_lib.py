@@ -59,6 +59,7 @@ class Shape(C.Structure):
 
 SHAPE_ALL, SHAPE_AABB, SHAPE_FRUSTUM, SHAPE_OBB, SHAPE_FRUSTUM_WITH_INVERSE, SHAPE_WEB_MERCATOR_RECT = 0, 1, 2, 3, 4, 5
 SHAPE_S2_CELL_UNION = 6  # PCV_SHAPE_S2_CELL_UNION: Shape.reserved is the union's index (pcv_shapes_create_ex)
+SHAPE_POLYGON = 7  # PCV_SHAPE_POLYGON: Shape.reserved is the polygon's index (pcv_shapes_create_ex2); params z_min, z_max, frame
 MAX_SHAPE_AXES = 45  # PCV_MAX_SHAPE_AXES
 WMR_FN_ATAN2, WMR_FN_SINCOS, WMR_FN_LN = 0, 1, 2
 
@@ -319,6 +320,11 @@ _SIGNATURES = {
     "pcv_shapes_create": (C.c_int, [_vp, C.POINTER(Shape), C.c_uint32, C.POINTER(_vp)]),
     "pcv_shapes_create_ex": (C.c_int, [_vp, C.POINTER(Shape), C.c_uint32, C.c_uint32, _vp, _vp, C.POINTER(_vp)]),
     "pcv_shapes_union": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _vp, C.POINTER(C.c_uint32)]),
+    "pcv_shapes_create_ex2": (C.c_int, [_vp, C.POINTER(Shape), C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "pcv_shapes_polygon": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.POINTER(C.c_uint32), C.c_uint32, _vp, C.POINTER(C.c_uint32)]),
+    "pcv_polygon_check_host": (C.c_int, [C.c_uint32, _vp, _vp, C.c_int32, C.c_double, C.c_double]),
+    "pcv_polygon_contains_host": (C.c_int, [C.c_uint32, _vp, _vp, C.c_int32, C.c_double, C.c_double, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "pcv_polygon_intersects_cubes_host": (C.c_int, [C.c_uint32, _vp, _vp, C.c_double, C.c_double, C.c_uint64, _vp, _vp]),
     "pcv_shapes_free": (None, [_vp]),
     "pcv_shapes_count": (C.c_uint32, [_vp]),
     "pcv_shapes_get": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double),

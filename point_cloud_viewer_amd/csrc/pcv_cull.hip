@@ -657,6 +657,7 @@ extern "C" int pcv_cull_nodes(pcv_ctx* ctx, const pcv_shapes* shapes, pcv_octree
   if (!shapes || !tree || !relation) return ctx->fail(PCV_E_INVALID, "null argument");
   int rc = pcv_refuse_unions(ctx, shapes, "pcv_cull_nodes");
   if (rc) return rc;
+  if ((rc = pcv_refuse_polygons(ctx, shapes, "pcv_cull_nodes"))) return rc;
   rc = pcv_octree_prepare_query(tree);
   if (rc) return rc;
   const uint32_t m = tree->query->m, f = shapes->count;
@@ -687,7 +688,7 @@ extern "C" int pcv_cull_nodes(pcv_ctx* ctx, const pcv_shapes* shapes, pcv_octree
 
 int pcv_launch_relation_row(pcv_ctx* ctx, const pcv_shapes* shapes, uint32_t shape_index, const pcv_octree* tree, uint8_t* d_rel) {
   const uint32_t m = tree->query->m;
-  const auto kernel = shapes->kinds[shape_index] == PCV_SHAPE_WEB_MERCATOR_RECT ? cull_nodes_kernel<true> : cull_nodes_kernel<false>;
+  const auto kernel = shapes->wide_shape(shape_index) ? cull_nodes_kernel<true> : cull_nodes_kernel<false>;
   {
     PcvProf prof(ctx, PCV_K_CULL_NODES);
     hipLaunchKernelGGL(kernel, dim3((m + 255) / 256, 1), dim3(256), 0, ctx->stream, shapes->dev + shape_index, m, tree->query->fb_cubes,
@@ -703,6 +704,7 @@ extern "C" int pcv_cull_nodes_sparse(pcv_ctx* ctx, const pcv_shapes* shapes, pcv
   if (!shapes || !tree || !counts || (capacity && (!node_indices || !relation))) return ctx->fail(PCV_E_INVALID, "null argument");
   int rc = pcv_refuse_unions(ctx, shapes, "pcv_cull_nodes_sparse");
   if (rc) return rc;
+  if ((rc = pcv_refuse_polygons(ctx, shapes, "pcv_cull_nodes_sparse"))) return rc;
   rc = pcv_octree_prepare_query(tree);
   if (rc) return rc;
   const PcvOctreeQuery* q = tree->query;
@@ -758,7 +760,8 @@ size_t pcv_node_lists_scratch(uint32_t f, uint32_t m) { return f + queue_bytes(m
 // one-lane-per-shape walk took 3.1 ms for 10 000 frusta; it stays for the shapes the wave walk hands back (a frontier that
 // outgrows the wave's queue, AllPoints), batch by batch, and its WIDE instance, behind it in every batch, writes the
 // web-mercator rectangles' lists and counts over what the launches before it wrote for them. Cell unions have a walk of their
-// own behind all of these (pcv_union.hip), a wave per location, which reuses the queues.
+// own behind all of these (pcv_union.hip), a wave per location, which reuses the queues; so have the xy-frame polygons
+// (pcv_polygon.hip). A web-mercator polygon is a web-mercator rectangle here.
 int pcv_launch_node_lists(pcv_ctx* ctx, int label, bool walk_bracket, const pcv_shapes* shapes, const pcv_octree* tree,
                           uint32_t capacity, uint32_t* counts, uint32_t* out, uint32_t* scratch, const uint64_t* rows) {
   const PcvOctreeQuery* q = tree->query;
@@ -787,8 +790,10 @@ int pcv_launch_node_lists(pcv_ctx* ctx, int label, bool walk_bracket, const pcv_
                          q->fb_cubes, queues, capacity, counts, out, (const uint32_t*)nullptr, rows);
   }
   PCV_HIP_CHECK(ctx, hipGetLastError());
-  // the cell unions' counts and lists, over the zeroes the launches above wrote for them (to those a union is not valid)
-  return pcv_launch_union_lists(ctx, label, shapes, tree, capacity, counts, out, queues, batch, rows);
+  // the cell unions' and the xy-frame polygons' counts and lists, over the zeroes the launches above wrote for them (to those
+  // neither is valid)
+  const int rc = pcv_launch_union_lists(ctx, label, shapes, tree, capacity, counts, out, queues, batch, rows);
+  return rc ? rc : pcv_launch_polygon_lists(ctx, label, shapes, tree, capacity, counts, out, queues, batch, rows);
 }
 
 // What the two traversals share. Before their launches: the arguments, the tree's tables, counts and lists on the device
@@ -823,6 +828,7 @@ extern "C" int pcv_visible_nodes(pcv_ctx* ctx, const pcv_shapes* frusta, pcv_oct
   uint32_t f, *d_counts, *d_out;
   int rc = frusta ? pcv_refuse_unions(ctx, frusta, "pcv_visible_nodes") : PCV_OK;
   if (rc) return rc;
+  if (frusta && (rc = pcv_refuse_polygons(ctx, frusta, "pcv_visible_nodes"))) return rc;
   rc = traversal_begin(ctx, frusta, tree, capacity, counts, node_indices, sc, &f, &d_counts, &d_out);
   if (rc || f == 0) return rc;
   const PcvOctreeQuery* q = tree->query;

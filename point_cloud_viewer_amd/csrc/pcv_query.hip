@@ -19,6 +19,7 @@
 #include "pcv_query_dev.h"
 #include "pcv_wmr_dev.h"
 #include "pcv_contain_dev.h"
+#include "pcv_polygon_dev.h"
 #include "pcv_s2_dev.h"
 
 namespace {
@@ -242,6 +243,68 @@ __device__ __forceinline__ uint32_t staged_keep_union(const uint64_t* __restrict
   }
   return tot;
 }
+// The same for a polygon (PCV_SHAPE_POLYGON): the point rule of pcv_polygon_dev.h on the decoded position (xy frame,
+// with the closed z range) or on its web-mercator projection (the chain of pcv_wmr_dev.h, once per point). What the test needs of
+// the shape is wave-uniform; the edge loop runs outside every divergent branch, so its trip count and its addresses are uniform
+// too and the table is read with scalar loads. Like the chains above it exists once, in kernels of its own.
+struct PolygonParams {
+  const double* edges;
+  uint32_t nedges;
+  int32_t frame;
+  double z_min, z_max;
+};
+__device__ __forceinline__ PolygonParams load_polygon(const PcvShapeDev* __restrict__ sh) {
+  return PolygonParams{sh->polygon.edges, sh->polygon.nedges, sh->polygon.frame, sh->polygon.z_min, sh->polygon.z_max};
+}
+// `live`: the lane holds a point (p is anything otherwise)
+__device__ __forceinline__ bool polygon_keep(const PolygonParams& pg, bool live, V3d p) {
+  double px = p.x, py = p.y;
+  bool k = live;
+  if (pg.frame) {  // wave-uniform
+    if (live) wmr::project(p.x, p.y, p.z, &px, &py);
+  } else {
+    k = k && (pg.z_min <= p.z && p.z <= pg.z_max);
+  }
+  return poly::inside(pg.edges, pg.nedges, px, py) && k;
+}
+__device__ __forceinline__ uint32_t staged_keep_polygon(const PolygonParams& pg, const uint4* stage, uint32_t skew, uint32_t enc,
+                                                        const double* cube_min, double cube_edge, uint32_t cnt,
+                                                        const float* __restrict__ attr, double lo, double hi, uint32_t lane,
+                                                        uint8_t* __restrict__ keep) {
+  const uint8_t* bytes = reinterpret_cast<const uint8_t*>(stage) + skew;
+  uint32_t tot = 0;
+  for (uint32_t g0 = 0; g0 < cnt; g0 += kGroup) {
+    unsigned long long b[4] = {0, 0, 0, 0};
+#pragma unroll 1
+    for (uint32_t r = 0; r < 4; ++r) {
+      const uint32_t q = g0 + r * 64 + lane;
+      const bool live = q < cnt;
+      V3d p = {0.0, 0.0, 0.0};
+      bool in_interval = true;
+      if (live) {
+        switch (enc) {  // wave-uniform
+          case PCV_ENC_UINT8: p = staged_point<PCV_ENC_UINT8>(bytes + q * 3u, cube_min, cube_edge); break;
+          case PCV_ENC_UINT16: p = staged_point<PCV_ENC_UINT16>(bytes + q * 6u, cube_min, cube_edge); break;
+          case PCV_ENC_FLOAT32: p = staged_point<PCV_ENC_FLOAT32>(bytes + q * 12u, cube_min, cube_edge); break;
+          default: p = staged_point<PCV_ENC_FLOAT64>(bytes + q * 24u, cube_min, cube_edge); break;
+        }
+        if (attr) {  // iterator.rs:82-91 + math/mod.rs:86-88
+          const double a = (double)attr[q];
+          in_interval = lo <= a && a <= hi;
+        }
+      }
+      const bool k = polygon_keep(pg, live, p) && in_interval;
+      const unsigned long long bal = __ballot(k);
+      b[0] = r == 0 ? bal : b[0];
+      b[1] = r == 1 ? bal : b[1];
+      b[2] = r == 2 ? bal : b[2];
+      b[3] = r == 3 ? bal : b[3];
+    }
+    store_keep(keep + g0, cnt - g0, b, lane);
+    tot += (uint32_t)(__popcll(b[0]) + __popcll(b[1]) + __popcll(b[2]) + __popcll(b[3]));
+  }
+  return tot;
+}
 template <int KIND>
 __device__ __forceinline__ uint32_t staged_keep(const ContainParams<KIND>& shape, const uint4* stage, uint32_t skew,
                                                 uint32_t enc, const double* cube_min, double cube_edge, uint32_t cnt,
@@ -361,6 +424,59 @@ __global__ __launch_bounds__(256) void cull_points_union_kernel(const PcvShapeDe
   }
 }
 
+// K8 for a polygon: cull_points_kernel's frame around the polygon's own test
+__global__ __launch_bounds__(256) void cull_points_polygon_kernel(const PcvShapeDev* __restrict__ shape_dev, PointsView v, uint32_t chunk,
+                                                                   uint8_t* __restrict__ keep, unsigned long long* __restrict__ kept) {
+  __shared__ uint4 stage[4][kStageSlots];
+  __shared__ uint32_t wave_cnt[4];
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  const uint64_t base = ((uint64_t)blockIdx.x * 4 + wave) * chunk;
+  uint32_t tot = 0;
+  if (base < v.n) {
+    const PolygonParams pg = load_polygon(shape_dev);
+    const uint32_t cnt = (uint32_t)(v.n - base < chunk ? v.n - base : chunk);
+    if (v.encoded) {
+      const StageRegs sr = stage_issue(v.encoded, base * enc_stride(v.enc), cnt * enc_stride(v.enc), lane);
+      stage_commit(sr, stage[wave], lane);
+      tot = staged_keep_polygon(pg, stage[wave], sr.skew, v.enc, v.cube_min, v.cube_edge, cnt, v.has_interval ? v.attr + base : nullptr, v.lo,
+                                v.hi, lane, keep + base);
+    } else {
+      for (uint32_t g0 = 0; g0 < cnt; g0 += kGroup) {
+        unsigned long long b[4] = {0, 0, 0, 0};
+#pragma unroll 1
+        for (uint32_t r = 0; r < 4; ++r) {
+          const uint32_t q = g0 + r * 64 + lane;
+          const bool live = q < cnt;
+          V3d p = {0.0, 0.0, 0.0};
+          bool in_interval = true;
+          if (live) {
+            const uint64_t i = base + q;
+            p = V3d{v.x[i], v.y[i], v.z[i]};
+            if (v.has_interval) {
+              const double a = (double)v.attr[i];
+              in_interval = v.lo <= a && a <= v.hi;
+            }
+          }
+          const bool k = polygon_keep(pg, live, p) && in_interval;
+          const unsigned long long bal = __ballot(k);
+          b[0] = r == 0 ? bal : b[0];
+          b[1] = r == 1 ? bal : b[1];
+          b[2] = r == 2 ? bal : b[2];
+          b[3] = r == 3 ? bal : b[3];
+        }
+        store_keep(keep + base + g0, cnt - g0, b, lane);
+        tot += (uint32_t)(__popcll(b[0]) + __popcll(b[1]) + __popcll(b[2]) + __popcll(b[3]));
+      }
+    }
+  }
+  if (lane == 0) wave_cnt[wave] = tot;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t t = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    if (t) atomicAdd(kept, (unsigned long long)t);
+  }
+}
+
 // K9
 __global__ __launch_bounds__(256) void transform_points_kernel(uint64_t n, const double* __restrict__ x,
                                                                 const double* __restrict__ y, const double* __restrict__ z,
@@ -435,7 +551,7 @@ __global__ __launch_bounds__(256) void query_chunks_kernel(const uint64_t* __res
       else b = mid;
     }
     const BatchNode nd = nodes[seg_node[lo]];
-    desc[c] = make_chunk_desc(nd, seg_chunk[lo], seg_flags[lo], a, shapes[a].kind, c, shift);
+    desc[c] = make_chunk_desc(nd, seg_chunk[lo], seg_flags[lo], a, shapes[a].point_kind, c, shift);
   }
 }
 
@@ -552,6 +668,33 @@ __global__ __launch_bounds__(256) void query_flags_union_kernel(const PcvShapeDe
     stage_commit(sr, stage, lane);
     const uint32_t tot = staged_keep_union(sh->cell_union.cells, sh->cell_union.count, stage, sr.skew, d.enc & 15u, d.cube_min, d.cube_edge,
                                            d.cnt, iv.used ? inten_blob + d.attr_index : nullptr, iv.lo, iv.hi, lane, keep + d.keep_off);
+    if (lane == 0) chunk_counts[c] = tot;
+    // the LDS slice is rewritten by the next commit: every lane must be done reading it
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// The polygon chunks, of a mixed batch (behind query_flags_kernel<-1>, to which they were AllPoints chunks) or of one location
+// (every chunk: shape 0 of `shapes`): a wave per chunk, grid-stride, the other kinds' chunks skipped; 64 points per step in the
+// lanes, the edge loop wave-uniform.
+__global__ __launch_bounds__(256) void query_flags_polygon_kernel(const PcvShapeDev* __restrict__ shapes, const BatchIval* __restrict__ ivals,
+                                                                   const ChunkDesc* __restrict__ desc, uint32_t nchunks,
+                                                                   const uint8_t* __restrict__ xyz_blob, const float* __restrict__ inten_blob,
+                                                                   uint8_t* __restrict__ keep, uint32_t* __restrict__ chunk_counts) {
+  __shared__ uint4 stage_all[4][kStageSlots];
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  uint4* stage = stage_all[wave];
+  const uint32_t nwaves = gridDim.x * 4;
+  for (uint32_t c = blockIdx.x * 4 + wave; c < nchunks; c += nwaves) {
+    const ChunkDesc d = desc[c];  // wave-uniform: scalar loads
+    if (((d.enc >> 4) & 15u) != (uint32_t)PCV_SHAPE_POLYGON) continue;
+    const PolygonParams pg = load_polygon(shapes + (d.enc >> 8));
+    const BatchIval iv = ivals[d.enc >> 8];
+    const StageRegs sr = stage_issue(xyz_blob, d.src, d.cnt * enc_stride(d.enc & 15u), lane);
+    stage_commit(sr, stage, lane);
+    const uint32_t tot = staged_keep_polygon(pg, stage, sr.skew, d.enc & 15u, d.cube_min, d.cube_edge, d.cnt,
+                                             iv.used ? inten_blob + d.attr_index : nullptr, iv.lo, iv.hi, lane, keep + d.keep_off);
     if (lane == 0) chunk_counts[c] = tot;
     // the LDS slice is rewritten by the next commit: every lane must be done reading it
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -699,6 +842,7 @@ int launch_flags(pcv_ctx* ctx, decltype(&query_flags_wmr_kernel) kernel, const P
 int launch_query_flags(pcv_ctx* ctx, int32_t kind, const PcvShapeDev* shapes, const BatchIval* ivals, const ChunkDesc* desc,
                        uint32_t nchunks, const pcv_octree* tree, uint8_t* keep, uint32_t* chunk_counts) {
   if (kind == PCV_SHAPE_S2_CELL_UNION) return launch_flags(ctx, query_flags_union_kernel, shapes, ivals, desc, nchunks, tree, keep, chunk_counts);
+  if (kind == PCV_SHAPE_POLYGON) return launch_flags(ctx, query_flags_polygon_kernel, shapes, ivals, desc, nchunks, tree, keep, chunk_counts);
   auto kernel = query_flags_kernel<-1>;
 #define PCV_CALL(K) kernel = query_flags_kernel<K>
   if (kind >= 0) {
@@ -792,6 +936,8 @@ static int launch_cull_points(pcv_ctx* ctx, PcvScratch& sc, const pcv_shapes* sh
 #define PCV_CALL(K) hipLaunchKernelGGL(cull_points_kernel<K>, grid, dim3(256), 0, ctx->stream, shapes->dev + shape_index, v, chunk, d_keep, d_cnt)
     if (shapes->kinds[shape_index] == PCV_SHAPE_S2_CELL_UNION) {
       hipLaunchKernelGGL(cull_points_union_kernel, grid, dim3(256), 0, ctx->stream, shapes->dev + shape_index, v, chunk, d_keep, d_cnt);
+    } else if (shapes->kinds[shape_index] == PCV_SHAPE_POLYGON) {
+      hipLaunchKernelGGL(cull_points_polygon_kernel, grid, dim3(256), 0, ctx->stream, shapes->dev + shape_index, v, chunk, d_keep, d_cnt);
     } else {
       PCV_DISPATCH_KIND(shapes->kinds[shape_index], PCV_CALL)
     }
@@ -926,6 +1072,9 @@ static int query_points_impl(pcv_ctx* ctx, const pcv_shapes* shapes, uint32_t sh
   } else if (shapes->kinds[shape_index] == PCV_SHAPE_S2_CELL_UNION) {
     // 1. a cell union has no Relation: its own walk gives the list (pcv_union.hip)
     if ((rc = pcv_union_node_list(ctx, shapes, shape_index, tree, &nodes))) return rc;
+  } else if (shapes->polygon_frame_of(shape_index) == 0) {
+    // 1. nor has a polygon in the xy frame (pcv_polygon.hip); a web-mercator one is its bounding rectangle below
+    if ((rc = pcv_polygon_node_list(ctx, shapes, shape_index, tree, &nodes))) return rc;
   } else {
     // 1. PointCloud::nodes_in_location for this one shape: the Relation of every node cube in one dense launch
     //    (same sat() as the traversal kernel), then the breadth-first walk of NodeIdsIterator on the host.
@@ -1209,6 +1358,9 @@ static int query_batch_run(pcv_ctx* ctx, const pcv_shapes* shapes, pcv_octree* t
       return rc;
     if (!shapes->union_shapes.empty() &&
         (rc = launch_flags(ctx, query_flags_union_kernel, shapes->dev, d_iv, desc, (uint32_t)nchunks, tree, b->d_keep, d_cc)))
+      return rc;
+    if (!shapes->polygon_shapes.empty() &&
+        (rc = launch_flags(ctx, query_flags_polygon_kernel, shapes->dev, d_iv, desc, (uint32_t)nchunks, tree, b->d_keep, d_cc)))
       return rc;
   }
   // 4. kept points per chunk -> u64 offsets; segment offsets from the first chunk of each segment

@@ -4,8 +4,10 @@
 // No kernel is shared across translation units: the point query reaches node culling through the two host functions at the
 // end.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "pcv_chain_dev.h"
@@ -96,7 +98,7 @@ struct PcvShapeDev {
   int32_t kind;   // PCV_SHAPE_*
   int32_t valid;  // 0: matrix not invertible (Frustum::from_matrix4 -> None)
   int32_t naxes;  // 0 for a web-mercator rectangle: its axes live in its PcvShapeWide
-  int32_t pad;
+  int32_t point_kind;  // the kind of the per-point test (ChunkDesc::enc): `kind`, but PCV_SHAPE_POLYGON for a web-mercator polygon
   double clip_from_query[16];
   union {
     double query_from_clip[16];
@@ -107,6 +109,14 @@ struct PcvShapeDev {
       uint32_t count, first;    // this union's cells are columns first .. first + count of the planes
       uint32_t stride, pad;
     } cell_union;
+    struct {                      // polygon (no matrices): its tables beside the table (pcv_polygon.hip). In the web-mercator
+      struct PcvShapeWide* wide;  // frame `kind` is PCV_SHAPE_WEB_MERCATOR_RECT and this is the bounding rectangle's record
+      const double* edges;        // the point rule's table: 4 doubles per non-horizontal edge (pcv_polygon_dev.h)
+      const double* segs;         // every edge a -> b as given, 4 doubles each: the node rule's
+      uint32_t nedges, nsegs;
+      double z_min, z_max;
+      int32_t frame, pad;
+    } polygon;
   };
   double iso[7];   // obb_from_query (translation xyz, quaternion ijkw) for contains()
   double half[3];
@@ -148,6 +158,25 @@ struct pcv_shapes {
   std::vector<uint32_t> union_of;      // per union shape (same order): its union
   void* d_union = nullptr;             // one block: the cells, their geometry planes, union_shapes
   const uint32_t* d_union_shapes = nullptr;
+  // polygons (pcv_shapes_create_ex2). An xy-frame polygon is, like a union, `valid == 0` with no axes on the device; a
+  // web-mercator one is its bounding web-mercator rectangle to every node and cell traversal (device kind, corners, axes) and a
+  // polygon to the point kernels (point_kind).
+  std::vector<uint32_t> polygon_first;   // host copies, as given: P + 1 offsets in rings, R + 1 in vertices, x y pairs
+  std::vector<uint32_t> ring_first;
+  std::vector<double> vertices;
+  std::vector<uint32_t> polygon_shapes;  // the shapes of kind PCV_SHAPE_POLYGON, ascending
+  std::vector<uint32_t> polygon_of;      // per polygon shape (same order): its polygon
+  std::vector<int32_t> polygon_frame;    // per polygon shape: 0 xy, 1 web-mercator
+  std::vector<uint32_t> xy_polygons;     // positions in polygon_shapes of the xy-frame ones (the walk's locations)
+  void* d_polygon = nullptr;             // one block: edge tables, raw edges, the xy-frame polygon shapes' indices
+  const uint32_t* d_xy_polygon_shapes = nullptr;
+  // -1: shape i is no polygon; otherwise its frame
+  int polygon_frame_of(uint32_t i) const {
+    const auto it = std::lower_bound(polygon_shapes.begin(), polygon_shapes.end(), i);
+    return it == polygon_shapes.end() || *it != i ? -1 : polygon_frame[it - polygon_shapes.begin()];
+  }
+  // the traversals see shape i as a web-mercator rectangle (its own axes in a PcvShapeWide)
+  bool wide_shape(uint32_t i) const { return kinds[i] == PCV_SHAPE_WEB_MERCATOR_RECT || polygon_frame_of(i) == 1; }
 };
 
 // Device-resident query view of an octree, built lazily (pcv_octree::query, pcv_octree_prepare_query in pcv_cull.hip): one
@@ -211,6 +240,25 @@ int pcv_launch_union_lists(pcv_ctx* ctx, int label, const pcv_shapes* shapes, co
                            uint32_t* counts, uint32_t* out, uint32_t* queues, uint32_t batch, const uint64_t* rows);
 // the same for one union shape into `nodes` (host), for the single-location point query
 int pcv_union_node_list(pcv_ctx* ctx, const pcv_shapes* shapes, uint32_t shape_index, const pcv_octree* tree, std::vector<uint32_t>* nodes);
+
+// ---- polygons (pcv_polygon.hip) ---------------------------------------------------------------------------------------
+// `what` refused because the table holds a polygon (no Relation, no clip matrix): PCV_E_INVALID naming the first one
+int pcv_refuse_polygons(pcv_ctx* ctx, const pcv_shapes* shapes, const char* what);
+// pcv_polygon_check_host's checks for polygons given as pcv_shapes_create_ex2 takes them; the message in *why
+int pcv_polygon_check_table(uint32_t num_polygons, const uint32_t* polygon_first, const uint32_t* ring_first, const double* vertices,
+                            std::string* why);
+// what a shape adds to its polygon's checks: the frame (params[2]) and what the web-mercator frame asks of vertices and z range
+int pcv_polygon_check_shape(double frame, double z_min, double z_max, uint32_t num_rings, const uint32_t* ring_first, const double* vertices,
+                            std::string* why);
+// The block behind pcv_shapes::d_polygon (edge tables of every polygon that a shape names) and the polygon members of `h`
+// pointed at it; a web-mercator member also gets its bounding rectangle's parameters and corners.
+int pcv_polygon_prepare_shapes(pcv_ctx* ctx, pcv_shapes* r, PcvShapeDev* h);
+// The node lists of the table's xy-frame polygons, behind pcv_launch_node_lists' other launches and with its arguments, as
+// pcv_launch_union_lists.
+int pcv_launch_polygon_lists(pcv_ctx* ctx, int label, const pcv_shapes* shapes, const pcv_octree* tree, uint32_t capacity,
+                             uint32_t* counts, uint32_t* out, uint32_t* queues, uint32_t batch, const uint64_t* rows);
+// the same for one xy-frame polygon shape into `nodes` (host), for the single-location point query
+int pcv_polygon_node_list(pcv_ctx* ctx, const pcv_shapes* shapes, uint32_t shape_index, const pcv_octree* tree, std::vector<uint32_t>* nodes);
 
 // out[0 .. n] = exclusive u64 scan of in[0 .. n), out[n] the total (asynchronous on ctx->stream)
 int pcv_batch_scan(pcv_ctx* ctx, PcvScratch& sc, const uint32_t* in, uint64_t n, uint64_t* out);

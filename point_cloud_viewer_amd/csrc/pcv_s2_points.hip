@@ -15,6 +15,7 @@
 
 #include "pcv_internal.h"
 #include "pcv_contain_dev.h"
+#include "pcv_polygon_dev.h"
 #include "pcv_s2_obj.h"
 #include "pcv_s2_dev.h"
 #include "pcv_s2_query_dev.h"
@@ -24,6 +25,7 @@ namespace {
 using Chunk = PcvS2Chunk;
 constexpr uint32_t kChunkPoints = kS2ChunkPoints;
 constexpr int kKindUnion = 100;  // a cell union: not a PCV_SHAPE_*
+constexpr int kKindPolygon = 101;  // a web-mercator polygon (the point kind of its shape; its device kind is the bounding rectangle's)
 
 struct Ival {  // ClosedInterval of one location on intensity
   double lo, hi;
@@ -41,16 +43,26 @@ __global__ __launch_bounds__(256) void s2_flags_kernel(const Chunk* __restrict__
                                                         const float* __restrict__ inten, uint32_t* __restrict__ flags) {
   const Chunk c = chunks[which[blockIdx.x]];
   const Ival iv = ivals[c.location];
-  ContainParams<KIND == kKindUnion ? PCV_SHAPE_ALL : KIND> shape;
+  ContainParams<KIND == kKindUnion || KIND == kKindPolygon ? PCV_SHAPE_ALL : KIND> shape;
   UnionRef u{0, 0};
+  const double* edges = nullptr;  // the polygon's point rule table (workgroup-uniform)
+  uint32_t nedges = 0;
   if constexpr (KIND == kKindUnion) u = unions[c.location - num_shapes];
+  else if constexpr (KIND == kKindPolygon) edges = shapes[c.location].polygon.edges, nedges = shapes[c.location].polygon.nedges;
   else shape = load_contain<KIND>(shapes + c.location);
   for (uint32_t q = threadIdx.x; q < c.count; q += 256u) {
     const uint64_t i = c.src + q;
     const double px = xyz[3 * i], py = xyz[3 * i + 1], pz = xyz[3 * i + 2];
     bool k;
-    if constexpr (KIND == kKindUnion) k = s2::union_contains(union_cells + u.first, u.count, s2::leaf_from_point(px, py, pz));
-    else k = shape_contains<KIND>(shape, V3d{px, py, pz});
+    if constexpr (KIND == kKindUnion) {
+      k = s2::union_contains(union_cells + u.first, u.count, s2::leaf_from_point(px, py, pz));
+    } else if constexpr (KIND == kKindPolygon) {  // the projection once per point, then the edges
+      double wu, wv;
+      wmr::project(px, py, pz, &wu, &wv);
+      k = poly::inside(edges, nedges, wu, wv);
+    } else {
+      k = shape_contains<KIND>(shape, V3d{px, py, pz});
+    }
     if (iv.used) {  // iterator.rs:82-91 + math/mod.rs:86-88
       const double a = (double)inten[i];
       k = k && (iv.lo <= a && a <= iv.hi);
@@ -97,6 +109,7 @@ int kind_of(const pcv_shapes* shapes, uint32_t num_shapes, uint32_t location) {
     case PCV_SHAPE_OBB: return PCV_SHAPE_OBB;
     case PCV_SHAPE_WEB_MERCATOR_RECT: return PCV_SHAPE_WEB_MERCATOR_RECT;
     case PCV_SHAPE_S2_CELL_UNION: return kKindUnion;  // a union member of the table: the union location it is
+    case PCV_SHAPE_POLYGON: return kKindPolygon;      // (web-mercator: pcv_s2_cells_in_location refuses the xy frame)
     default: return PCV_SHAPE_ALL;
   }
 }
@@ -134,7 +147,7 @@ int run_impl(pcv_s2_cloud* c, const pcv_shapes* shapes, uint32_t num_unions, con
   if ((rc = pcv_s2_make_resident(c))) return rc;
   std::vector<Chunk> chunks;
   std::vector<uint64_t> seg_candidate(1, 0);
-  std::vector<std::vector<uint32_t>> by_kind(kKindUnion + 1);
+  std::vector<std::vector<uint32_t>> by_kind(kKindPolygon + 1);
   for (uint64_t l = 0; l < locations; ++l) {
     const int kind = kind_of(shapes, num_shapes, (uint32_t)l);
     for (uint32_t k = 0; k < counts[l]; ++k) {
@@ -202,7 +215,7 @@ int run_impl(pcv_s2_cloud* c, const pcv_shapes* shapes, uint32_t num_unions, con
   }
     // (the order of by_kind: ascending kind, as `which` was filled)
     LAUNCH(PCV_SHAPE_ALL) LAUNCH(PCV_SHAPE_AABB) LAUNCH(PCV_SHAPE_FRUSTUM) LAUNCH(PCV_SHAPE_OBB) LAUNCH(PCV_SHAPE_WEB_MERCATOR_RECT)
-    LAUNCH(kKindUnion)
+    LAUNCH(kKindUnion) LAUNCH(kKindPolygon)
 #undef LAUNCH
   }
   PCV_HIP_CHECK(ctx, hipGetLastError());

@@ -273,6 +273,9 @@ extern "C" int pcv_s2_cells_in_location(pcv_s2_cloud* c, const pcv_shapes* shape
   const uint32_t n = (uint32_t)c->ids.size();
   bool geometric = false;  // (a cell union in the table asks for ids only, like the call's own unions)
   for (uint32_t f = 0; f < num_shapes; ++f)
+    if (shapes->polygon_frame_of(f) == 0)
+      return ctx->fail(PCV_E_INVALID, "shape " + std::to_string(f) + ": a polygon in the xy frame has no meaning over an ECEF cell cloud");
+  for (uint32_t f = 0; f < num_shapes; ++f)
     geometric = geometric || (shapes->kinds[f] != PCV_SHAPE_ALL && shapes->kinds[f] != PCV_SHAPE_S2_CELL_UNION);
   std::string why;
   if (check_cloud_cells(c->ids.size(), c->ids.data(), geometric, &why) || check_unions(num_unions, union_first, union_cells, &why))

@@ -1,5 +1,5 @@
 // pcv_shapes.hip — prepared query shapes for gfx950: pcv_shapes_create / _create_ex / _free / _count / _get /
-// _get_ex / _union.
+// _get_ex / _union / _create_ex2 / _polygon.
 //
 //   K7a shape_setup      Frustum::from_matrix4 / intersector / cache_separating_axes_for_aabb
 //                        (reference src/geometry/frustum.rs:111-166, src/math/sat.rs:111-143), Obb (obb.rs:48-80),
@@ -196,9 +196,10 @@ __global__ __launch_bounds__(64) void shape_setup_kernel(PcvShapeDev* shapes, ui
     for (int a = 0; a < w->naxes; ++a)
       project8(s->corners, V3d{w->axes[3 * a], w->axes[3 * a + 1], w->axes[3 * a + 2]}, &w->amin[a], &w->amax[a]);
     s->naxes = 0;
-  } else if (s->kind == PCV_SHAPE_S2_CELL_UNION) {
+  } else if (s->kind == PCV_SHAPE_S2_CELL_UNION || s->kind == PCV_SHAPE_POLYGON) {
     // no corners, no axes. Not valid to the traversals of the other kinds, which then report nothing for it; its own walk and
-    // point instances (pcv_union.hip, pcv_query.hip) read s->cell_union and do not look at this flag.
+    // point instances (pcv_union.hip / pcv_polygon.hip, pcv_query.hip) read s->cell_union / s->polygon and do not look at this
+    // flag. (A web-mercator polygon arrives here as the web-mercator rectangle over its vertices.)
     s->valid = 0;
     s->naxes = 0;
   } else {
@@ -212,17 +213,24 @@ __global__ __launch_bounds__(64) void shape_setup_kernel(PcvShapeDev* shapes, ui
 
 static void release_shapes(pcv_shapes* s) {
   if (s->d_union) s->ctx->dev_free(s->d_union);
+  if (s->d_polygon) s->ctx->dev_free(s->d_polygon);
   if (s->wide) s->ctx->dev_free(s->wide);
   if (s->dev) s->ctx->dev_free(s->dev);
   delete s;
 }
 
 static int shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t count, bool with_unions, uint32_t num_unions,
-                         const uint32_t* union_first, const uint64_t* union_cells, pcv_shapes** out) {
+                         const uint32_t* union_first, const uint64_t* union_cells, bool with_polygons, uint32_t num_polygons,
+                         const uint32_t* polygon_first, const uint32_t* ring_first, const double* vertices, pcv_shapes** out) {
   if (!ctx) return PCV_E_INVALID;
   if (!out || (count && !shapes)) return ctx->fail(PCV_E_INVALID, "null argument");
   *out = nullptr;
-  std::vector<uint32_t> union_shapes, union_of;
+  std::vector<uint32_t> union_shapes, union_of, polygon_shapes, polygon_of;
+  std::vector<int32_t> polygon_frame;
+  if (with_polygons) {
+    std::string why;
+    if (pcv_polygon_check_table(num_polygons, polygon_first, ring_first, vertices, &why)) return ctx->fail(PCV_E_INVALID, why);
+  }
   if (with_unions) {
     std::string why;
     if (pcv_s2_check_unions(num_unions, union_first, union_cells, &why)) return ctx->fail(PCV_E_INVALID, why);
@@ -236,7 +244,7 @@ static int shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t count, 
     const pcv_shape& s = shapes[i];
     PcvShapeDev& d = h[i];
     std::memset(&d, 0, sizeof(d));
-    d.kind = s.kind;
+    d.kind = d.point_kind = s.kind;
     switch (s.kind) {
       case PCV_SHAPE_ALL: break;
       case PCV_SHAPE_AABB:
@@ -272,6 +280,22 @@ static int shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t count, 
         union_shapes.push_back(i);
         union_of.push_back((uint32_t)s.reserved);
         break;
+      case PCV_SHAPE_POLYGON: {
+        if (!with_polygons) return ctx->fail(PCV_E_INVALID, "a polygon needs its rings: pcv_shapes_create_ex2");
+        if (s.reserved < 0 || (uint32_t)s.reserved >= num_polygons) return ctx->fail(PCV_E_INVALID, "polygon index out of range");
+        std::string why;
+        const uint32_t p = (uint32_t)s.reserved;
+        if (pcv_polygon_check_shape(s.params[2], s.params[0], s.params[1], polygon_first[p + 1] - polygon_first[p], ring_first + polygon_first[p],
+                                    vertices, &why))
+          return ctx->fail(PCV_E_INVALID, "shape " + std::to_string(i) + ": " + why);
+        d.polygon.z_min = s.params[0];
+        d.polygon.z_max = s.params[1];
+        polygon_shapes.push_back(i);
+        polygon_of.push_back(p);
+        polygon_frame.push_back(s.params[2] == 1.0 ? 1 : 0);
+        if (s.params[2] == 1.0) wide_of.push_back(i);  // the rectangle over its vertices (pcv_polygon_prepare_shapes)
+        break;
+      }
       default: return ctx->fail(PCV_E_INVALID, "unknown shape kind");
     }
   }
@@ -294,6 +318,19 @@ static int shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t count, 
     r->union_shapes = union_shapes;
     r->union_of = union_of;
     if ((rc = pcv_union_prepare_shapes(ctx, r, h.data()))) {
+      release_shapes(r);
+      return rc;
+    }
+  }
+  if (!polygon_shapes.empty()) {
+    const uint32_t nrings = polygon_first[num_polygons];
+    r->polygon_first.assign(polygon_first, polygon_first + num_polygons + 1);
+    r->ring_first.assign(ring_first, ring_first + nrings + 1);
+    r->vertices.assign(vertices, vertices + 2 * (size_t)ring_first[nrings]);
+    r->polygon_shapes = polygon_shapes;
+    r->polygon_of = polygon_of;
+    r->polygon_frame = polygon_frame;
+    if ((rc = pcv_polygon_prepare_shapes(ctx, r, h.data()))) {
       release_shapes(r);
       return rc;
     }
@@ -324,12 +361,19 @@ static int shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t count, 
 }
 
 extern "C" int pcv_shapes_create(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t count, pcv_shapes** out) {
-  return shapes_create(ctx, shapes, count, false, 0, nullptr, nullptr, out);
+  return shapes_create(ctx, shapes, count, false, 0, nullptr, nullptr, false, 0, nullptr, nullptr, nullptr, out);
 }
 
 extern "C" int pcv_shapes_create_ex(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t count, uint32_t num_unions, const uint32_t* union_first,
                                     const uint64_t* union_cells, pcv_shapes** out) {
-  return shapes_create(ctx, shapes, count, true, num_unions, union_first, union_cells, out);
+  return shapes_create(ctx, shapes, count, true, num_unions, union_first, union_cells, false, 0, nullptr, nullptr, nullptr, out);
+}
+
+extern "C" int pcv_shapes_create_ex2(pcv_ctx* ctx, const pcv_shape* shapes, uint32_t count, uint32_t num_unions, const uint32_t* union_first,
+                                     const uint64_t* union_cells, uint32_t num_polygons, const uint32_t* polygon_first,
+                                     const uint32_t* ring_first, const double* vertices, pcv_shapes** out) {
+  return shapes_create(ctx, shapes, count, true, num_unions, union_first, union_cells, true, num_polygons, polygon_first, ring_first, vertices,
+                       out);
 }
 
 extern "C" void pcv_shapes_free(pcv_shapes* s) {
@@ -349,12 +393,30 @@ extern "C" int pcv_shapes_union(pcv_shapes* s, uint32_t i, uint64_t capacity, ui
   return PCV_OK;
 }
 
+extern "C" int pcv_shapes_polygon(pcv_shapes* s, uint32_t i, uint32_t ring_capacity, uint32_t* ring_first, uint32_t* num_rings,
+                                  uint32_t vertex_capacity, double* vertices, uint32_t* num_vertices) {
+  if (!s || i >= s->count) return PCV_E_INVALID;
+  const auto it = std::lower_bound(s->polygon_shapes.begin(), s->polygon_shapes.end(), i);
+  if (it == s->polygon_shapes.end() || *it != i) return s->ctx->fail(PCV_E_INVALID, "shape " + std::to_string(i) + " is not a polygon");
+  if (!num_rings || !num_vertices || (ring_capacity && !ring_first) || (vertex_capacity && !vertices)) return s->ctx->fail(PCV_E_INVALID, "null argument");
+  const uint32_t p = s->polygon_of[it - s->polygon_shapes.begin()];
+  const uint32_t r0 = s->polygon_first[p], nr = s->polygon_first[p + 1] - r0, v0 = s->ring_first[r0], nv = s->ring_first[r0 + nr] - v0;
+  *num_rings = nr;
+  *num_vertices = nv;
+  if (ring_capacity >= nr && vertex_capacity >= nv && ring_capacity) {
+    for (uint32_t k = 0; k <= nr; ++k) ring_first[k] = s->ring_first[r0 + k] - v0;
+    std::memcpy(vertices, s->vertices.data() + 2 * (size_t)v0, 16 * (size_t)nv);
+  }
+  return PCV_OK;
+}
+
 extern "C" uint32_t pcv_shapes_count(const pcv_shapes* s) { return s ? s->count : 0; }
 
 extern "C" int pcv_shapes_get(pcv_shapes* s, uint32_t i, double corners[24], double axes[78], uint32_t* num_axes,
                               int* valid) {
   if (!s || i >= s->count) return PCV_E_INVALID;
   if (s->kinds[i] == PCV_SHAPE_S2_CELL_UNION) return s->ctx->fail(PCV_E_INVALID, "a cell union has no corners or axes: pcv_shapes_union gives its cells");
+  if (s->kinds[i] == PCV_SHAPE_POLYGON) return s->ctx->fail(PCV_E_INVALID, "a polygon has no corners or axes: pcv_shapes_polygon gives its rings");
   if (s->kinds[i] != PCV_SHAPE_WEB_MERCATOR_RECT) {  // (all 78 doubles, as ever)
     pcv_ctx* ctx = s->ctx;
     PcvShapeDev h;
@@ -380,6 +442,7 @@ extern "C" int pcv_shapes_get_ex(pcv_shapes* s, uint32_t i, double corners[24], 
   if (!s || i >= s->count) return PCV_E_INVALID;
   pcv_ctx* ctx = s->ctx;
   if (s->kinds[i] == PCV_SHAPE_S2_CELL_UNION) return ctx->fail(PCV_E_INVALID, "a cell union has no corners or axes: pcv_shapes_union gives its cells");
+  if (s->kinds[i] == PCV_SHAPE_POLYGON) return ctx->fail(PCV_E_INVALID, "a polygon has no corners or axes: pcv_shapes_polygon gives its rings");
   PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   PcvShapeDev h;
   PCV_HIP_CHECK(ctx, hipMemcpy(&h, s->dev + i, sizeof(h), hipMemcpyDeviceToHost));

@@ -473,23 +473,40 @@ class Context:
         ("frustum2", clip_from_query16, query_from_clip16), ("obb", translation3, quat_ijkw4, half_extent3),
         ("web_mercator_rect", north_west2, south_east2) — normalised map coordinates, as web_mercator_rect_from_zoomed
         returns them; the query space is ECEF; ("s2_cells", cell_ids) — PointLocation::S2Cells over an octree: S2 cell ids,
-        ascending, of level 1 or finer, taken as given (not normalized); the query space is ECEF (pcv_shapes_create_ex)."""
+        ascending, of level 1 or finer, taken as given (not normalized); the query space is ECEF (pcv_shapes_create_ex);
+        ("polygon", rings, z_min, z_max) — a polygon with holes, or several, under the even-odd rule in the cloud's own x and y,
+        times the closed height range (either bound may be infinite; both default to it): `rings` is one (k, 2) array or a list
+        of them, each ring implicitly closed; ("polygon_web_mercator", rings) — the same with normalized web-mercator vertices in
+        [0, 1) over an ECEF cloud, as polygon_from_lat_lng returns them (pcv_shapes_create_ex2)."""
         arr = (L.Shape * max(1, len(shapes)))()
-        unions = []
+        unions, polygons = [], []
         for i, sh in enumerate(shapes):
             kind = {"all": L.SHAPE_ALL, "aabb": L.SHAPE_AABB, "frustum": L.SHAPE_FRUSTUM, "obb": L.SHAPE_OBB,
                     "frustum2": L.SHAPE_FRUSTUM_WITH_INVERSE, "web_mercator_rect": L.SHAPE_WEB_MERCATOR_RECT,
-                    "s2_cells": L.SHAPE_S2_CELL_UNION}[sh[0]]
+                    "s2_cells": L.SHAPE_S2_CELL_UNION, "polygon": L.SHAPE_POLYGON, "polygon_web_mercator": L.SHAPE_POLYGON}[sh[0]]
             arr[i].kind = kind
             if kind == L.SHAPE_S2_CELL_UNION:
                 arr[i].reserved = len(unions)
                 unions.append(sh[1])
                 continue
+            if kind == L.SHAPE_POLYGON:
+                arr[i].reserved = len(polygons)
+                polygons.append(sh[1])
+                web = sh[0] == "polygon_web_mercator"
+                arr[i].params[0] = float(sh[2]) if not web and len(sh) > 2 else -np.inf
+                arr[i].params[1] = float(sh[3]) if not web and len(sh) > 3 else np.inf
+                arr[i].params[2] = 1.0 if web else 0.0
+                continue
             flat = [float(v) for part in sh[1:] for v in np.asarray(part, dtype=np.float64).ravel()]
             for j, v in enumerate(flat):
                 arr[i].params[j] = v
         h = C.c_void_p()
-        if unions:
+        if polygons:
+            first, flat = _s2_unions(unions)
+            pfirst, rfirst, verts = _polygon_table(polygons)
+            self._check(self.lib.pcv_shapes_create_ex2(self.handle, arr, len(shapes), len(unions), first.ctypes.data, flat.ctypes.data,
+                                                       len(polygons), pfirst.ctypes.data, rfirst.ctypes.data, verts.ctypes.data, C.byref(h)))
+        elif unions:
             first, flat = _s2_unions(unions)
             self._check(self.lib.pcv_shapes_create_ex(self.handle, arr, len(shapes), len(unions), first.ctypes.data, flat.ctypes.data,
                                                       C.byref(h)))
@@ -1065,6 +1082,16 @@ class Shapes:
         cells = np.zeros(n.value, dtype=np.uint64)
         self.ctx._check(self.ctx.lib.pcv_shapes_union(self.handle, i, cells.size, cells.ctypes.data, C.byref(n)))
         return cells
+
+    def polygon(self, i):
+        """The rings of shape i, a ("polygon", ...) or ("polygon_web_mercator", ...) entry, as given: a list of (k, 2) arrays
+        (pcv_shapes_polygon)."""
+        nr, nv = C.c_uint32(), C.c_uint32()
+        self.ctx._check(self.ctx.lib.pcv_shapes_polygon(self.handle, i, 0, None, C.byref(nr), 0, None, C.byref(nv)))
+        first, verts = np.zeros(nr.value + 1, dtype=np.uint32), np.zeros((nv.value, 2))
+        self.ctx._check(self.ctx.lib.pcv_shapes_polygon(self.handle, i, nr.value, first.ctypes.data, C.byref(nr), nv.value, verts.ctypes.data,
+                                                        C.byref(nv)))
+        return [verts[first[r]:first[r + 1]].copy() for r in range(nr.value)]
 
     def free(self):
         if self.handle and self.ctx.handle:
@@ -2946,6 +2973,74 @@ def _s2_unions(unions):
     first[1:] = np.cumsum([u.size for u in unions], dtype=np.uint64)
     flat = np.ascontiguousarray(np.concatenate(unions) if unions else np.zeros(0), dtype=np.uint64)
     return first, flat
+
+
+def _polygon_rings(rings):
+    """(ring_first uint32[R + 1], vertices float64 (V, 2)) of one (k, 2) array or a sequence of them."""
+    if isinstance(rings, np.ndarray) and rings.ndim == 2:
+        rings = [rings]
+    rings = [np.ascontiguousarray(r, dtype=np.float64).reshape(-1, 2) for r in rings]
+    first = np.zeros(len(rings) + 1, dtype=np.uint32)
+    first[1:] = np.cumsum([r.shape[0] for r in rings], dtype=np.uint64)
+    verts = np.ascontiguousarray(np.concatenate(rings) if rings else np.zeros((0, 2)), dtype=np.float64)
+    return first, verts
+
+
+def _polygon_table(polygons):
+    """(polygon_first, ring_first, vertices) of a sequence of polygons, as pcv_shapes_create_ex2 takes them."""
+    parts = [_polygon_rings(p) for p in polygons]
+    pfirst = np.zeros(len(parts) + 1, dtype=np.uint32)
+    pfirst[1:] = np.cumsum([f.size - 1 for f, _ in parts], dtype=np.uint64)
+    rfirst, at = [np.zeros(1, dtype=np.uint32)], 0
+    for f, v in parts:
+        rfirst.append((f[1:].astype(np.uint64) + at).astype(np.uint32))
+        at += v.shape[0]
+    verts = np.ascontiguousarray(np.concatenate([v for _, v in parts]) if parts else np.zeros((0, 2)), dtype=np.float64)
+    return pfirst, np.ascontiguousarray(np.concatenate(rfirst), dtype=np.uint32), verts
+
+
+def polygon_check(rings, frame=0, z_min=-np.inf, z_max=np.inf):
+    """pcv_polygon_check_host: what Context.shapes checks of a polygon; raises PcvError with the message."""
+    first, verts = _polygon_rings(rings)
+    _host_check(L.load_library().pcv_polygon_check_host(first.size - 1, first.ctypes.data, verts.ctypes.data, int(frame), float(z_min),
+                                                        float(z_max)), "pcv_polygon_check_host")
+
+
+def polygon_contains(rings, x, y, z, frame=0, z_min=-np.inf, z_max=np.inf):
+    """pcv_polygon_contains_host: the keep flag of every point, as uint8 — frame 0: the point rule on (x, y) and the closed
+    height range on z; frame 1: the rule on the web-mercator projection of the ECEF point. Bit for bit the device's."""
+    first, verts = _polygon_rings(rings)
+    x, y, z = _wmr_xyz(x, y, z)
+    keep = np.zeros(x.size, dtype=np.uint8)
+    _host_check(L.load_library().pcv_polygon_contains_host(first.size - 1, first.ctypes.data, verts.ctypes.data, int(frame), float(z_min),
+                                                           float(z_max), x.size, x.ctypes.data, y.ctypes.data, z.ctypes.data,
+                                                           keep.ctypes.data), "pcv_polygon_contains_host")
+    return keep
+
+
+def polygon_intersects_cubes(rings, cubes, z_min=-np.inf, z_max=np.inf):
+    """pcv_polygon_intersects_cubes_host: the node rule of an xy-frame polygon per cube (n x 4: min xyz, edge), as uint8 flags —
+    the predicate its node list over an octree is the breadth-first walk of."""
+    first, verts = _polygon_rings(rings)
+    cubes = np.ascontiguousarray(cubes, dtype=np.float64).reshape(-1, 4)
+    out = np.zeros(cubes.shape[0], dtype=np.uint8)
+    _host_check(L.load_library().pcv_polygon_intersects_cubes_host(first.size - 1, first.ctypes.data, verts.ctypes.data, float(z_min),
+                                                                   float(z_max), cubes.shape[0], cubes.ctypes.data, out.ctypes.data),
+                "pcv_polygon_intersects_cubes_host")
+    return out
+
+
+def polygon_from_lat_lng(rings_deg):
+    """Rings of (latitude, longitude) in degrees as rings of normalized web-mercator (x, y), for ("polygon_web_mercator", rings):
+    wmr_from_lat_lng per vertex."""
+    if isinstance(rings_deg, np.ndarray) and rings_deg.ndim == 2:
+        rings_deg = [rings_deg]
+    out = []
+    for r in rings_deg:
+        r = np.asarray(r, dtype=np.float64).reshape(-1, 2)
+        u, v = wmr_from_lat_lng(np.radians(r[:, 0]), np.radians(r[:, 1]))
+        out.append(np.stack([u, v], axis=1))
+    return out
 
 
 def s2_cell_geometry(cell_id):

@@ -158,6 +158,8 @@ extern "C" {
     fn pcv_shapes_create(ctx: *mut pcv_ctx, shapes: *const PcvShape, count: u32, out: *mut *mut pcv_shapes) -> c_int;
     fn pcv_shapes_create_ex(ctx: *mut pcv_ctx, shapes: *const PcvShape, count: u32, num_unions: u32, union_first: *const u32, union_cells: *const u64,
                             out: *mut *mut pcv_shapes) -> c_int;
+    fn pcv_shapes_create_ex2(ctx: *mut pcv_ctx, shapes: *const PcvShape, count: u32, num_unions: u32, union_first: *const u32, union_cells: *const u64,
+                             num_polygons: u32, polygon_first: *const u32, ring_first: *const u32, vertices: *const f64, out: *mut *mut pcv_shapes) -> c_int;
     fn pcv_shapes_free(s: *mut pcv_shapes);
     fn pcv_visible_nodes(ctx: *mut pcv_ctx, frusta: *const pcv_shapes, t: *mut pcv_octree, capacity: u32, counts: *mut u32, node_indices: *mut u32, status: *mut i32) -> c_int;
     // per frustum the nodes whose Relation is not Out, with relation and relative_size_on_screen (octree/mod.rs:119-139, 261-272)
@@ -440,6 +442,13 @@ pub struct HipOctree {
 unsafe impl Send for HipOctree {}
 unsafe impl Sync for HipOctree {}
 
+/// Locations the library offers beyond the reference's `PointLocation` (which has no polygon variant): rings of (x, y) vertices
+/// under the even-odd rule, each ring implicitly closed — in the cloud's own x and y with a closed height range, or, with
+/// `web_mercator`, as normalized web-mercator coordinates over an ECEF cloud (z_min / z_max then -inf / +inf).
+pub enum HipLocation {
+    Polygon { rings: Vec<Vec<nalgebra::Point2<f64>>>, z_min: f64, z_max: f64, web_mercator: bool },
+}
+
 impl HipOctree {
     pub fn from_directory(directory: impl AsRef<Path>) -> Result<Self> {
         let ctx = HipContext::new(0).map_err(|e| ErrorKind::InvalidInput(e))?;
@@ -538,6 +547,31 @@ impl HipOctree {
             } else {
                 pcv_shapes_create_ex(self.ctx.0, table.as_ptr(), table.len() as u32, (first.len() - 1) as u32, first.as_ptr(), flat.as_ptr(), &mut out)
             }
+        });
+        out
+    }
+
+    /// One prepared table of polygon locations (PCV_SHAPE_POLYGON): shape i is `locations[i]`, each with a polygon
+    /// of its own, named by `reserved`.
+    pub fn create_polygon_shapes(&self, locations: &[HipLocation]) -> *mut pcv_shapes {
+        let (mut table, mut polygon_first, mut ring_first, mut vertices) = (Vec::new(), vec![0u32], vec![0u32], Vec::<f64>::new());
+        for location in locations {
+            let HipLocation::Polygon { rings, z_min, z_max, web_mercator } = location;
+            let mut s = PcvShape { kind: 7, reserved: (polygon_first.len() - 1) as i32, params: [0.0; 32] };
+            s.params[..3].copy_from_slice(&[*z_min, *z_max, if *web_mercator { 1.0 } else { 0.0 }]);
+            table.push(s);
+            for ring in rings {
+                for v in ring {
+                    vertices.extend_from_slice(&[v.x, v.y]);
+                }
+                ring_first.push((vertices.len() / 2) as u32);
+            }
+            polygon_first.push((ring_first.len() - 1) as u32);
+        }
+        let mut out = std::ptr::null_mut();
+        self.ctx.check(unsafe {
+            pcv_shapes_create_ex2(self.ctx.0, table.as_ptr(), table.len() as u32, 0, std::ptr::null(), std::ptr::null(), (polygon_first.len() - 1) as u32,
+                                  polygon_first.as_ptr(), ring_first.as_ptr(), vertices.as_ptr(), &mut out)
         });
         out
     }
