@@ -359,6 +359,10 @@ uint64_t pcv_octree_settled_in_sort(const pcv_octree* t);
 /* Bytes of one record of the last build's record sort (rank + leaf codes + colour): 20, or 12 when the single-chain
  * build packed the record (16-bit codes; the points of Float32-coded levels travel as the index of their pool entry). */
 int pcv_octree_record_bytes(const pcv_octree* t);
+/* How the chain pass handed its records to the record sort: 0 = records with their colour; 1 = packed 8-byte records and a
+ * plane of 16-bit ranks, loaded as they are by the sort's first pass, which joins the colour; 2 = packed, but unpacked in place
+ * in front of a sort that cannot take them. */
+int pcv_octree_packed_handover(const pcv_octree* t);
 
 /* ---- stage-level entry points (unit parity against the oracle) ------------------------------ */
 /* K1: find_bounding_box (generation.rs:256-270; Aabb::grow aabb.rs:41-44). n == 0 -> Aabb::zero(). */
@@ -506,6 +510,12 @@ int pcv_sort_pairs32(pcv_ctx* ctx, uint32_t* keys, uint32_t* values, uint64_t n,
  *     only receives the sorted plane.
  *   color_in (rows, or null): the keys arrive as rank << 8 and the upper half of the payload's second word empty; the first
  *     pass reads red, green, blue of record i at color_in + i * color_stride (3 or 4; n * color_stride bytes in all).
+ *   flags & PCV_SORT_RECORDS_PACKED (vec_bytes 8, no plane, map of <= 65 536 entries, rows, color_in): the records arrive as
+ *     the chain pass of the build hands them over — `vec` holds 8 bytes per record, first word as above, second word = third
+ *     code | predicted rank << 16 — and there are no keys to read: `keys` only receives the sorted keys. On input its first
+ *     2 n bytes hold the predicted ranks once more as half words, which PCV_SORT_ROWS_DEVICE counts (nothing else reads them).
+ *     The first pass loads 8 bytes per record, joins the colour and writes the 12-byte records every later stage reads. The
+ *     map stays in LDS up to 15 824 / 11 216 entries (digits of <= 7 / 8 bits; 11 728 / 7 120 at color_stride 4).
  *   hold_second: the sort gets a place to hold its second pass back in (the two-pass rows form does), and the entry then runs
  *     that pass in its plain form, as pcv_build_finish does for leaves the pass does not settle itself.
  *   flags & PCV_SORT_RECORDS_CHECK_KEYS: every predicted rank is compared with map_entries first (a pass of its own; a
@@ -516,6 +526,7 @@ int pcv_sort_pairs32(pcv_ctx* ctx, uint32_t* keys, uint32_t* values, uint64_t n,
 #define PCV_SORT_ROWS_GIVEN 1
 #define PCV_SORT_ROWS_DEVICE 2
 #define PCV_SORT_RECORDS_CHECK_KEYS 1u
+#define PCV_SORT_RECORDS_PACKED 2u
 typedef struct pcv_sort_records_args {
   uint64_t n;
   uint32_t* keys;

@@ -149,6 +149,7 @@ class NodeInfo(C.Structure):
 
 SORT_ROWS_NONE, SORT_ROWS_GIVEN, SORT_ROWS_DEVICE = 0, 1, 2  # PCV_SORT_ROWS_*
 SORT_RECORDS_CHECK_KEYS = 1  # PCV_SORT_RECORDS_CHECK_KEYS
+SORT_RECORDS_PACKED = 2  # PCV_SORT_RECORDS_PACKED
 
 
 class SortRecordsArgs(C.Structure):
@@ -275,6 +276,7 @@ _SIGNATURES = {
     "pcv_octree_build_info": (None, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pcv_octree_spec_stats": (None, [_vp, C.POINTER(C.c_uint64)]),
     "pcv_octree_record_bytes": (C.c_int, [_vp]),
+    "pcv_octree_packed_handover": (C.c_int, [_vp]),
     "pcv_octree_spec_continued": (C.c_uint64, [_vp]),
     "pcv_octree_wide_pool_entries": (C.c_uint64, [_vp]),
     "pcv_octree_settled_in_sort": (C.c_uint64, [_vp]),

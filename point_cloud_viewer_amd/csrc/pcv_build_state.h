@@ -53,7 +53,10 @@ struct PcvBuild {
   std::vector<uint32_t> resolve_host_map;
   std::vector<uint8_t> resolve_host_inner;  // T'' node is an inner node: its map entry is never read (the device leaves it unwritten)
   PcvSortPayload pl;
-  bool color_late = false;  // single-chain build: the chain pass wrote its 12-byte records without the colour
+  bool color_late = false;  // single-chain build: the chain pass wrote its records without the colour
+  // ... and as packed 8-byte records with the ranks as a plane of half words in keys_a (pcv_packed_handover: the pass was
+  // launched in that form and the predicted tree is small enough)
+  bool pack_tried = false, packed = false;
   explicit PcvBuild(pcv_ctx* c) : ctx(c), sc(c) {}
   // A build dropped between begin and finish (an error in finish before the held-back pass was queued, a tree freed without
   // finish): the pass's layout kernels on the side stream write into `sc`'s sort scratch; the main stream must be ordered behind

@@ -303,20 +303,26 @@ __device__ __forceinline__ uint32_t cp_walk_at(const uint32_t* __restrict__ walk
     CP_LOOP(true, lv.nlevels, , pcv_chain_apply_bits<true>(lv.enc[U + 1], b, ec, ic, px, py, pz, mx, my, mz, vx, vy, vz)) \
   }
 
-// DIAG (libpcv_hip_exp.so only). Bit 1 (PCV_COLOR_LATE=1, a correct build): the 12-byte records leave WITHOUT their colour — the
+// DIAG 1 (libpcv_hip_exp.so only, PCV_COLOR_LATE=1, a correct build): the 12-byte records leave WITHOUT their colour — the
 // record sort's first pass reads it from the caller's array as it loads the records (PcvSortPayload::color_in): no colour loads
-// behind the walks (1.86 -> 1.73 ms for the pass at 100 M points; the sort pass loses more than that: not shipped).
+// behind the walks (1.86 -> 1.73 ms for the pass at 100 M points).
+// DIAG 2 (ships): the PACKED hand-over. Where the predicted tree has at most 65 536 nodes (tree_info[0], which the device knows
+// when the pass starts and the host learns from its mirror: pcv_packed_handover) no colour is loaded and a record is 8 bytes —
+// lo = code x | code y << 16 (or the `wide` pool entry), hi = code z | predicted rank << 16 — in `payload`, and the ranks leave
+// once more as a dense plane of half words in `rank` for the count: 10 bytes per point written instead of 12, and the sort's
+// first pass loads 8 bytes per record, not 12. Bigger trees: the 12-byte records WITH their colour, as DIAG 0.
 template <bool KEEP, bool RAW, int BLOCK, int TOP = 0 /* walk records mirrored in LDS (a multiple of 4 x BLOCK, or 0) */, int DIAG = 0>
 __global__ __launch_bounds__(BLOCK, 8) void chain_pass_kernel(
     PcvLevels lv, const uint32_t* __restrict__ walk, uint64_t n, const double* __restrict__ x, const double* __restrict__ y,
     const double* __restrict__ z, PcvRouted routed, const uint8_t* __restrict__ color, uint32_t color_stride,
     const float* __restrict__ intensity, uint32_t* __restrict__ rank, uint4* __restrict__ payload, uint32_t* __restrict__ inten_bits,
     const uint8_t* __restrict__ depth_grid /* null: no deal by depth (small builds) */, float cells_per_unit /* 128 / root edge */,
-    uint4* __restrict__ wide /* set: 12-byte records */, uint32_t* __restrict__ pool_ctr, uint32_t pool_cap) {
+    uint4* __restrict__ wide /* set: 12-byte records */, uint32_t* __restrict__ pool_ctr, uint32_t pool_cap,
+    const uint32_t* __restrict__ tree_info = nullptr /* DIAG 2: [0] = number of T'' nodes */) {
   constexpr int TILE = 2 * BLOCK, kGroups = TILE / 64;
   static_assert(TILE <= 1024, "a tile must not span two pool regions, and its slot numbers share 16 bits with the wild flag");
   constexpr uint32_t kWild = 0x8000u;
-  __shared__ double sxyz[3 * TILE];  // slot s: half s / BLOCK, {x, y, z}[s % BLOCK]
+  __shared__ alignas(DIAG == 2 ? 16 : 8) double sxyz[3 * TILE];  // slot s: half s / BLOCK, {x, y, z}[s % BLOCK] (DIAG 2: 16-byte LDS reads)
   __shared__ uint16_t sidx[TILE];
   __shared__ uint32_t kcnt[32];  // points of the tile per depth class
   __shared__ uint32_t swalk[TOP ? TOP : 4];
@@ -491,7 +497,28 @@ __global__ __launch_bounds__(BLOCK, 8) void chain_pass_kernel(
   }
   // closing phase, input order again: full lines; the colour and the intensity bits join here
   tid = wave * 64 + (int)pcv_lane_again();
-  if (stage) {
+  if (DIAG == 2 && stage && pcv_packed_handover(tree_info[0])) {  // (scalar)
+    // two adjacent points per lane: one 16-byte store of records and one dword of ranks (the tile starts at a multiple of 1 024
+    // points and the arrays come from the pool: aligned); streaming stores as below
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    __syncthreads();
+    const uint32_t t = 2u * (uint32_t)tid;
+    if (t < here) {
+      const uint2 k2 = *reinterpret_cast<const uint2*>(okey + t);
+      const uint4 q2 = *reinterpret_cast<const uint4*>(opay + t);
+      const uint32_t r0 = k2.x >> 8, r1 = k2.y >> 8;
+      uint64_t* const rec = reinterpret_cast<uint64_t*>(payload) + base + t;
+      uint16_t* const r16 = reinterpret_cast<uint16_t*>(rank) + base + t;
+      if (t + 1 < here) {
+        const u32x4 v = {q2.x, q2.y | (r0 << 16), q2.z, q2.w | (r1 << 16)};
+        __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(rec));
+        __builtin_nontemporal_store(r0 | (r1 << 16), reinterpret_cast<uint32_t*>(r16));
+      } else {  // the cloud's last point, at an even position
+        __builtin_nontemporal_store(((uint64_t)(q2.y | (r0 << 16)) << 32) | q2.x, rec);
+        __builtin_nontemporal_store((uint16_t)r0, r16);
+      }
+    }
+  } else if (stage) {
     uint32_t rgb[2];
     // (round 6, measured: requesting the colour in the front phase and parking it in LDS, or fetching it as aligned dwords + two
     // ds_bpermute per lane, changes nothing — 1.85 ms either way against 1.72 without any colour (a timing-only variant): what the
@@ -500,7 +527,7 @@ __global__ __launch_bounds__(BLOCK, 8) void chain_pass_kernel(
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const uint32_t t = (uint32_t)(h * BLOCK + tid);
-      rgb[h] = (!(DIAG & 1) && t < here) ? pcv_load_rgb(color + (base + t) * color_stride, base + t + 1 < n) : 0u;
+      rgb[h] = (DIAG != 1 && t < here) ? pcv_load_rgb(color + (base + t) * color_stride, base + t + 1 < n) : 0u;
     }
     __syncthreads();
 #pragma unroll
@@ -536,6 +563,7 @@ __global__ __launch_bounds__(BLOCK, 8) void chain_pass_kernel(
 // [bin_base, bin_base + nbins), nbins <= kHistBins; one flush of the non-zero bins per workgroup.
 constexpr int kHistBins = 16384;      // 64 KiB of LDS: the plain count (512 workgroups, two to a CU)
 constexpr int kHistBinsRows = 32768;  // 128 KiB: the count over the record sort's workgroups with the rows kept (one to a CU)
+template <bool H16 = false /* `rank` is a dense plane of 16-bit ranks (shift unused) */>
 __global__ __launch_bounds__(1024) void rank_hist_kernel(const uint32_t* __restrict__ rank, uint64_t n, uint64_t chunk,
                                                           uint32_t bin_base, uint32_t nbins, uint32_t* __restrict__ counts,
                                                           int shift /* 8: 12-byte records, the rank sits above the blue byte */,
@@ -548,6 +576,28 @@ __global__ __launch_bounds__(1024) void rank_hist_kernel(const uint32_t* __restr
   const uint64_t begin = (uint64_t)blockIdx.x * chunk;
   uint64_t end = begin + chunk;
   if (end > n) end = n;
+  if (H16) {
+    // the packed hand-over's plane of 16-bit ranks: 16-byte loads of eight ranks each over the chunk's whole groups of eight.
+    // Every chunk BEGINS at a multiple of 8 — both launchers below cut chunks of whole tiles of 4 096 or 8 192 ranks, and the
+    // array comes from the pool (256-byte aligned) — so there is no head; the last chunk ends with n: what lies behind its last
+    // whole group is counted rank by rank
+    const uint16_t* const r16 = reinterpret_cast<const uint16_t*>(rank);
+    const auto count = [&](uint32_t v) {
+      const uint32_t r = v - bin_base;
+      if (r < nbins) atomicAdd(&hist[r], 1u);
+    };
+    const uint64_t body_end = begin + ((end - begin) & ~(uint64_t)7);
+    for (uint64_t i = begin + (uint64_t)threadIdx.x * 8; i < body_end; i += 8192) {
+      const uint4 v = *reinterpret_cast<const uint4*>(r16 + i);
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        count(w[k] & 0xffffu);
+        count(w[k] >> 16);
+      }
+    }
+    for (uint64_t j = body_end + threadIdx.x; j < end; j += 1024) count(r16[j]);
+  } else
   // chunk is a multiple of 4 and the array comes from the pool (256-byte aligned): 16-byte loads
   for (uint64_t i = begin + (uint64_t)threadIdx.x * 4; i < end; i += 4096) {
     if (i + 4 <= end) {
@@ -975,10 +1025,9 @@ void pcv_launch_spec_encode(pcv_ctx* ctx, const PcvLevels& lv, const uint32_t* w
                             uint32_t* inten_bits, uint8_t* depth_grid /* pcv_spec_depth_grid_bytes() of scratch, or null */,
                             void* wide, uint32_t* pool_ctr /* kPcvPoolRegions zeroed counters: entries of `wide` handed out per region */,
                             const uint32_t* tree_info /* device: [0] = number of T'' nodes (spec_tree_scan_kernel's info block) */,
-                            bool color_late, uint32_t* zero, size_t zero_words) {
+                            bool color_late, uint32_t* zero, size_t zero_words, bool packed) {
   if (n == 0) return;
   PcvProf prof(ctx, PCV_K_SPEC_ENCODE);
-  (void)tree_info;
   constexpr int kBlock = 512;  // tiles of 1 024 points: one pool region, 26 KB of LDS, four workgroups per CU
   const dim3 grid((unsigned)((n + 2 * kBlock - 1) / (2 * kBlock)));
   const float cells = lv.edge[0] > 0.0 ? (float)((double)(1 << kGridBits) / lv.edge[0]) : 0.f;
@@ -994,6 +1043,11 @@ void pcv_launch_spec_encode(pcv_ctx* ctx, const PcvLevels& lv, const uint32_t* w
 #define PCV_CHAIN_TOP_LAUNCH(RAWIN, T)                                                                                                  \
   hipLaunchKernelGGL((chain_pass_kernel<true, RAWIN, kBlock, T>), grid, dim3(kBlock), 0, ctx->stream, lv, walk, n, x, y, z, routed, color, \
                      color_stride, intensity, rank, (uint4*)payload, inten_bits, depth_grid, cells, (uint4*)wide, pool_ctr, pool_cap)
+  if (packed && wide && !routed.oct) {  // the packed hand-over (raw input, 12-byte records): 8-byte records without colour where the tree allows
+    hipLaunchKernelGGL((chain_pass_kernel<true, true, kBlock, kTop, 2>), grid, dim3(kBlock), 0, ctx->stream, lv, walk, n, x, y, z, routed, color,
+                       color_stride, intensity, rank, (uint4*)payload, inten_bits, depth_grid, cells, (uint4*)wide, pool_ctr, pool_cap, tree_info);
+    return;
+  }
 #ifdef PCV_EXPERIMENTS  // (PCV_COLOR_LATE=1: measured, slower overall, not instantiated in libpcv_hip.so)
 #define PCV_CHAIN_LATE_LAUNCH(RAWIN)                                                                                                     \
   hipLaunchKernelGGL((chain_pass_kernel<true, RAWIN, kBlock, kTop, 1>), grid, dim3(kBlock), 0, ctx->stream, lv, walk, n, x, y, z, routed, color, \
@@ -1027,7 +1081,24 @@ void pcv_launch_join_color(pcv_ctx* ctx, uint64_t n, const uint8_t* color, uint3
                      (uint2*)payload_uint2);
 }
 
-void pcv_launch_rank_hist(pcv_ctx* ctx, const uint32_t* rank, uint64_t n, uint32_t num_bins, uint32_t* counts, int shift) {
+// packed records -> 12-byte records with their colour, in place: record i reads and writes its own payload slot and writes its
+// own key (the plane of 16-bit ranks that `keys` held is not read: the rank comes out of the record)
+__global__ __launch_bounds__(256) void unpack_records_kernel(uint64_t n, const uint8_t* __restrict__ color, uint32_t color_stride,
+                                                              uint32_t* __restrict__ keys, uint2* __restrict__ payload) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint2 q = payload[i];
+  const uint32_t rgb = pcv_load_rgb(color + i * color_stride, i + 1 < n);
+  keys[i] = ((q.y >> 16) << 8) | (rgb >> 16);
+  payload[i] = make_uint2(q.x, (q.y & 0xffffu) | ((rgb & 0xffffu) << 16));
+}
+void pcv_launch_unpack_records(pcv_ctx* ctx, uint64_t n, const uint8_t* color, uint32_t color_stride, uint32_t* keys, void* payload_uint2) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(unpack_records_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, color, color_stride, keys,
+                     (uint2*)payload_uint2);
+}
+
+void pcv_launch_rank_hist(pcv_ctx* ctx, const uint32_t* rank, uint64_t n, uint32_t num_bins, uint32_t* counts, int shift, bool ranks16) {
   if (n == 0 || num_bins == 0) return;
   // one workgroup per CU-ish: 512 workgroups of 1024 lanes; the chunk is a multiple of 4096 keys
   uint64_t chunk = (n + 511) / 512;
@@ -1036,8 +1107,8 @@ void pcv_launch_rank_hist(pcv_ctx* ctx, const uint32_t* rank, uint64_t n, uint32
   for (uint32_t base = 0; base < num_bins; base += kHistBins) {
     const uint32_t nb = num_bins - base < (uint32_t)kHistBins ? num_bins - base : (uint32_t)kHistBins;
     PcvProf prof(ctx, PCV_K_RANK_HIST);
-    hipLaunchKernelGGL(rank_hist_kernel, dim3(groups), dim3(1024), (size_t)nb * 4, ctx->stream, rank, n, chunk, base, nb, counts, shift,
-                       (uint32_t*)nullptr, 0u);
+    hipLaunchKernelGGL(ranks16 ? rank_hist_kernel<true> : rank_hist_kernel<false>, dim3(groups), dim3(1024), (size_t)nb * 4, ctx->stream, rank,
+                       n, chunk, base, nb, counts, shift, (uint32_t*)nullptr, 0u);
   }
 }
 
@@ -1047,16 +1118,18 @@ void pcv_launch_rank_hist(pcv_ctx* ctx, const uint32_t* rank, uint64_t n, uint32
 // bigger trees (1 B points: ~50 000 predicted nodes) take one launch per 32 768 bins. num_bins <= pcv_rank_hist_max_bins().
 uint32_t pcv_rank_hist_max_bins() { return 1u << 18; }
 void pcv_launch_rank_hist_rows(pcv_ctx* ctx, const uint32_t* rank, uint64_t n, uint32_t num_bins, uint32_t* counts, int shift,
-                               int groups, uint64_t chunk, uint32_t* rows) {
+                               int groups, uint64_t chunk, uint32_t* rows, bool ranks16) {
   if (n == 0 || num_bins == 0) return;
-  static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&rank_hist_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+  static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&rank_hist_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             kHistBinsRows * 4) == hipSuccess &&
+                         hipFuncSetAttribute(reinterpret_cast<const void*>(&rank_hist_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                              kHistBinsRows * 4) == hipSuccess;
   (void)ok;
   for (uint32_t base = 0; base < num_bins; base += kHistBinsRows) {
     const uint32_t nb = num_bins - base < (uint32_t)kHistBinsRows ? num_bins - base : (uint32_t)kHistBinsRows;
     PcvProf prof(ctx, PCV_K_RANK_HIST);
-    hipLaunchKernelGGL(rank_hist_kernel, dim3(groups), dim3(1024), (size_t)nb * 4, ctx->stream, rank, n, chunk, base, nb, counts, shift, rows,
-                       num_bins);
+    hipLaunchKernelGGL(ranks16 ? rank_hist_kernel<true> : rank_hist_kernel<false>, dim3(groups), dim3(1024), (size_t)nb * 4, ctx->stream, rank,
+                       n, chunk, base, nb, counts, shift, rows, num_bins);
   }
 }
 

@@ -352,6 +352,10 @@ struct PcvSortPayload {
   // it loads the record; what it writes is the record with colour (blue in the key's low byte, red / green in payload .y)
   const uint8_t* color_in = nullptr;
   uint32_t color_stride = 3;
+  // set: vec_in holds the chain pass's PACKED records — 8 bytes {codes x | y << 16 or the pool entry, code z | predicted rank
+  // << 16} — and there are no keys yet (keys_a is free: its first 2 n bytes hold the ranks once more, as a plane for the count);
+  // color_in is set. The first pass of the rows form without a plane only (pcv_sort_plan refuses anything else).
+  bool packed = false;
 };
 size_t pcv_sort_scratch_bytes(uint64_t n);  // PcvSortScratch::end + slack
 // Sorts keys_in -> ... ping-pong between (keys_a, payload.in) and (keys_b, payload.out). Returns in
@@ -430,6 +434,7 @@ inline PcvSortFacts pcv_sort_facts(uint64_t n, int key_bytes, int begin_bit, int
   PcvSortFacts f;
   f.n = n, f.key_bytes = key_bytes, f.begin_bit = begin_bit, f.end_bit = end_bit;
   if (pl) f.vec_in = pl->vec_in != nullptr, f.vec_bytes = pl->vec_bytes, f.nwords = pl->nwords, f.color_in = pl->color_in != nullptr;
+  if (pl) f.color_stride = (int)pl->color_stride, f.packed = pl->packed;
   f.sort_rows2 = pcv_switches().sort_rows2, f.sort_msd = pcv_switches().sort_msd, f.rows_true_bins = pcv_switches().rows_true_bins;
   return f;
 }
@@ -438,6 +443,8 @@ inline PcvSortFacts pcv_sort_facts(uint64_t n, int key_bytes, int begin_bit, int
 struct PcvSortRec12Args {
   int R = 128, MAP = 0;
   bool PL = false, WC = false;
+  bool PK = false;       // first pass: packed 8-byte records in vec_in (src unused)
+  size_t color_lds = 0;  // ... bytes of the staged colours' buffer, launched on top of dyn_lds
   const PcvSortFuse* fuse = nullptr;
   int grid = 0;  // workgroups: the sort's groups (chunks), or the pieces of a second pass
   size_t dyn_lds = 0;
@@ -556,7 +563,11 @@ void pcv_launch_spec_encode(pcv_ctx* ctx, const PcvLevels& lv, const uint32_t* w
                             uint32_t* inten_bits, uint8_t* depth_grid, void* wide, uint32_t* pool_ctr, const uint32_t* tree_info,
                             bool color_late = false /* 12-byte records leave without their colour (PcvSortPayload::color_in) */,
                             uint32_t* zero = nullptr /* with depth_grid: zero_words words (16-byte aligned, a multiple of 4) cleared before the pass */,
-                            size_t zero_words = 0);
+                            size_t zero_words = 0,
+                            bool packed = false /* raw input, 12-byte records: the packed hand-over (chain_pass_kernel, DIAG 2) */);
+// Packed records (and the colour) back into the 12-byte form, in place: for the sorts that cannot take them (the rank-count rows
+// did not fit). keys[i] = rank << 8 | blue, payload[i] = {lo, code z | red << 16 | green << 24}.
+void pcv_launch_unpack_records(pcv_ctx* ctx, uint64_t n, const uint8_t* color, uint32_t color_stride, uint32_t* keys, void* payload_uint2);
 // The colour joined into records that left the chain pass without it, in place (the record sort's first pass does this on the
 // fly; this pass exists for the sorts that cannot: the rank-count rows did not fit, experiments).
 void pcv_launch_join_color(pcv_ctx* ctx, uint64_t n, const uint8_t* color, uint32_t color_stride, uint32_t* keys, void* payload_uint2);
@@ -565,10 +576,10 @@ constexpr uint32_t kPcvPoolRegions = 1024;
 inline uint64_t pcv_pool_region_entries(uint64_t n) { return (((n + 1023) / 1024 + kPcvPoolRegions - 1) / kPcvPoolRegions) * 1024; }
 size_t pcv_spec_depth_grid_bytes();  // scratch for the depth-prediction grid of the binned pass
 void pcv_launch_rank_hist(pcv_ctx* ctx, const uint32_t* rank, uint64_t n, uint32_t num_bins, uint32_t* counts /* zeroed */,
-                          int shift = 0);
+                          int shift = 0, bool ranks16 = false /* `rank` is the packed hand-over's plane of 16-bit ranks */);
 uint32_t pcv_rank_hist_max_bins();
 void pcv_launch_rank_hist_rows(pcv_ctx* ctx, const uint32_t* rank, uint64_t n, uint32_t num_bins, uint32_t* counts /* zeroed */,
-                               int shift, int groups, uint64_t chunk, uint32_t* rows /* groups x num_bins */);
+                               int shift, int groups, uint64_t chunk, uint32_t* rows /* groups x num_bins */, bool ranks16 = false);
 // workgroups and keys per workgroup of the 12-byte record sort (tiles of 8 192)
 void pcv_sort_rec12_geometry(uint64_t n, int* groups, uint64_t* chunk);
 // Chain continuation of the true leaves below a split first candidate (pcv_spec.h): `ranges` = device array of
@@ -638,6 +649,7 @@ struct pcv_octree {
   int key_levels = 0;    // digit levels the key sort covered (depth speculation)
   int key_attempts = 0;  // 0 = single-chain build, 1 = depth speculation held (or was off), 2+ = redone
   int record_bytes = 0;  // bytes per record in the record sort (20, or 12 packed)
+  int packed_handover = 0;  // pcv_octree_packed_handover
   uint64_t spec_stats[4] = {};  // single-chain build: nodes / leaves of the predicted tree, points in an unsplit first
                                 // candidate (their kept codes are their leaf codes), points that replayed the chain
   uint64_t wide_pool_entries = 0;  // single-chain build, 12-byte records: entries of the Float32-code pool the chain pass used

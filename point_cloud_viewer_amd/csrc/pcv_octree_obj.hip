@@ -53,6 +53,7 @@ extern "C" void pcv_octree_spec_stats(const pcv_octree* t, uint64_t stats[4]) {
   for (int k = 0; k < 4; ++k) stats[k] = t->spec_stats[k];
 }
 extern "C" int pcv_octree_record_bytes(const pcv_octree* t) { return t ? t->record_bytes : 0; }
+extern "C" int pcv_octree_packed_handover(const pcv_octree* t) { return t ? t->packed_handover : 0; }
 extern "C" uint64_t pcv_octree_spec_continued(const pcv_octree* t) { return t ? t->spec_continued : 0; }
 extern "C" uint64_t pcv_octree_wide_pool_entries(const pcv_octree* t) { return t ? t->wide_pool_entries : 0; }
 extern "C" uint64_t pcv_octree_settled_in_sort(const pcv_octree* t) { return t ? t->settled_in_sort : 0; }

@@ -42,6 +42,7 @@ int pcv_queue_record_sort(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, const PcvWa
   pl.vec_out = pay_b;
   pl.vec_bytes = compact ? 8 : 16;
   t->record_bytes = compact ? 12 : 20;
+  t->packed_handover = 0;
   pl.nwords = (t->has_intensity ? 1 : 0) + (wide ? 3 : 0);
   for (int w = 0; w < pl.nwords; ++w) {
     if (w == 0) {  // first plane fits in the second half of the key buffers
@@ -72,6 +73,11 @@ int pcv_queue_record_sort(pcv_ctx* ctx, PcvBuild* bs, pcv_octree* t, const PcvWa
     if (first_pass_joins) {
       pl.color_in = d.color;
       pl.color_stride = d.color_stride;
+      pl.packed = bs->packed;  // (no plane: the packed hand-over is not tried with an intensity)
+      t->packed_handover = bs->packed ? 1 : 0;
+    } else if (bs->packed) {
+      pcv_launch_unpack_records(ctx, n, d.color, d.color_stride, rank_a, pay_a);
+      t->packed_handover = 2;
     } else {
       pcv_launch_join_color(ctx, n, d.color, d.color_stride, rank_a, pay_a);
     }
@@ -373,6 +379,17 @@ static int sample_round(SingleChain& s, SampleRound* out) {
   // sort's first pass loses 0.31 (0.59 -> 0.90): eight more (unaligned) loads per lane on top of its sixteen — that pass is
   // bound by the issue of its vector-memory instructions, not by bytes. Same octree either way.
   bs->color_late = pcv_switches().color_late && s.compact;
+  // The packed hand-over (ships; packed_handover off: the 12-byte records with their colour): single-chain build with 12-byte
+  // records, raw input, no intensity plane. Where T'' has at most 65 536 nodes — which the device knows now and the host once it
+  // has mirrored the tree (count_and_queue_sort) — the pass leaves the colour to the sort's first pass and writes 8-byte
+  // records and the ranks as a plane of half words; a bigger tree gets today's 12-byte records with their colour. Whether the
+  // sort can take packed records is settled when it is queued (pcv_queue_record_sort): the rows form's first pass loads them
+  // as they are, any other sort gets them unpacked first. (rec_wc bit 0, experiments: the write-combining first pass takes
+  // 12-byte records with their colour: the old hand-over.)
+  bs->pack_tried = pcv_packed_handover_tried(pcv_switches().packed_handover && !bs->color_late && !(pcv_switches().rec_wc & 1), s.compact,
+                                             d.routed.oct != nullptr,
+                                             d.intensity != nullptr || s.t->has_intensity);
+  bs->packed = false;
   // the exact counters (d_counts) are cleared by the depth-grid kernel in front of the pass where there is one; small builds
   // clear them with a fill on `stream`
   const size_t counts_words = (tcap + 3) & ~(size_t)3;
@@ -383,7 +400,7 @@ static int sample_round(SingleChain& s, SampleRound* out) {
   uint32_t* inten_bits = nullptr;
   pcv_launch_spec_encode(ctx, lv, s.d_walk, n, d.x, d.y, d.z, d.routed, d.color, d.color_stride, d.intensity, s.rank, s.payload,
                          inten_bits, s.depth_grid, s.wide, s.d_pool_ctr /* zeroed by the spec_tree kernels */, s.d_info, bs->color_late,
-                         zero_in_grid ? s.d_counts : nullptr, zero_in_grid ? counts_words : 0);
+                         zero_in_grid ? s.d_counts : nullptr, zero_in_grid ? counts_words : 0, bs->pack_tried);
   ctx->stage_end(PCV_STAGE_LEAF_ENCODE);
 
   PCV_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->side, ctx->side_fork, 0));
@@ -415,6 +432,10 @@ static int count_and_queue_sort(SingleChain& s) {
   // pass derives its digit histogram (the keys are then read by its downsweep only, which applies the map itself).
   // sort_rows off (libpcv_hip_exp.so): the first pass counts (and maps) the keys in a pass of its own.
   bs->spec_rows = nullptr;
+  // (a predicted leaf is named by its node index: tree.num_leaves is the number of T'' nodes the chain pass decided by)
+  bs->packed = bs->pack_tried && pcv_packed_handover(tree.num_leaves);
+  if (bs->packed) bs->color_late = true;  // (packed records come without their colour)
+  const int rank_shift = bs->packed ? 0 : s.compact ? 8 : 0;
   if (pcv_switches().sort_rows && s.compact && tree.num_leaves <= pcv_rank_hist_max_bins()) {
     int sgroups;
     uint64_t schunk;
@@ -423,11 +444,11 @@ static int count_and_queue_sort(SingleChain& s) {
     // the rows are an optimisation (up to ~1 GB beside the records for the biggest trees): a failed allocation falls
     // back to the plain count, whose sort takes a counting pass instead
     if (sc.get(&rows, (size_t)sgroups * tree.num_leaves) == PCV_OK) {
-      pcv_launch_rank_hist_rows(ctx, s.rank, n, tree.num_leaves, s.d_counts, 8, sgroups, schunk, rows);
+      pcv_launch_rank_hist_rows(ctx, s.rank, n, tree.num_leaves, s.d_counts, rank_shift, sgroups, schunk, rows, bs->packed);
       bs->spec_rows = rows;
     }
   }
-  if (!bs->spec_rows) pcv_launch_rank_hist(ctx, s.rank, n, tree.num_leaves, s.d_counts, s.compact ? 8 : 0);
+  if (!bs->spec_rows) pcv_launch_rank_hist(ctx, s.rank, n, tree.num_leaves, s.d_counts, rank_shift, bs->packed);
   PCV_HIP_CHECK(ctx, hipGetLastError());
   if ((rc = ctx->pinned_spec_reserve((size_t)tree.num_leaves * 8 + 512 + kPcvPoolRegions * 4))) return rc;
   uint8_t* hp = (uint8_t*)ctx->pinned_spec;

@@ -59,11 +59,15 @@ void plan_rows_form(const PcvSortFacts& f, int width, PcvSortPlan* plan) {
   plan->msd = f.sort_msd && plan->two_pass;  // upper digit first, the second pass sorts inside every bucket
   const int p1_shift = plan->msd ? shift + width : shift, p1_bits = plan->msd ? nbits2 : nbits;
   // the map's place is judged by the LOWER digit's width, msd or not: never the more generous of the two kernel forms
-  const bool map_in_lds = f.map_entries <= pcv_sort_map_lds(plan->with_plane, digit_values(nbits)).max_entries;
+  const uint32_t lds_entries = f.packed ? pcv_sort_map_lds_staged(digit_values(nbits), f.color_stride)
+                                        : pcv_sort_map_lds(plan->with_plane, digit_values(nbits)).max_entries;
+  const bool map_in_lds = f.map_entries <= lds_entries;
   PcvSortPass& first = plan->pass[plan->npasses++];
   first = rec12_pass(p1_shift, p1_bits, plan->two_pass ? PCV_HIST_ROWS_TRUE : PCV_HIST_ROWS, PCV_DOWN_REC12_CHUNKS, plan->with_plane);
   first.MAP = map_in_lds ? 1 : 2;
   first.dyn_lds = map_in_lds ? (((size_t)f.map_entries * 2 + 15) & ~(size_t)15) : 0;
+  first.packed = f.packed;
+  first.color_lds = f.packed ? pcv_sort_color_buffer(f.color_stride) : 0;
   if (!plan->two_pass) return;
   // second pass: pieces of whole first-pass runs
   const int D1 = 1 << p1_bits;
@@ -99,6 +103,8 @@ const char* pcv_sort_plan(const PcvSortFacts& f, PcvSortPlan* plan) {
   const int passes = (total_bits + 7) / 8;
   const int width = plan->records ? (total_bits + passes - 1) / passes : 8;
   int shift = f.begin_bit;
+  if (f.packed && !(f.map && f.rows && plan->rec12 && !plan->with_plane && f.color_in && f.map_entries <= kPcvPackedRanks))
+    return "record sort: packed records need the rows form without a plane, color_in and a map of <= 65 536 entries";
   if (f.map && f.rows && plan->rec12) {
     plan_rows_form(f, width, plan);
     shift = plan->two_pass ? f.end_bit : f.begin_bit + width;

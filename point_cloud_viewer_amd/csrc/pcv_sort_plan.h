@@ -7,6 +7,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "pcv_color_stage.h"
+
 constexpr int kPcvSortRadix = 256;       // digit values of a pass (8-bit digits)
 constexpr int kPcvSortMaxGroups = 1024;  // sort workgroups (and pieces of a second pass) at most: one scan workgroup covers them
 constexpr int kPcvSortTileUnit = 4096;   // chunk granularity of the 256-lane kernels: 256 lanes x 16 keys
@@ -46,6 +48,40 @@ struct PcvSortMapLds {
 constexpr PcvSortMapLds pcv_sort_map_lds(bool plane, int R) {
   return !plane ? PcvSortMapLds{16384u, 32768u} : R == 128 ? PcvSortMapLds{10000u, 20480u} : PcvSortMapLds{5000u, 10240u};
 }
+
+// The staged colours of that pass (pcv_color_stage.h): where the records arrive without their colour, the workgroup fetches a
+// tile's colour bytes as aligned 16-byte pieces into a buffer in the same dynamic LDS, behind the map. ONE rule says what fits:
+//   static LDS of the form + the map's half words (rounded up to 16 bytes) + the buffer <= 163 840 bytes.
+// (pcv_sort_rec12.hip asserts that the static part is what pcv_sort_rec12_static_lds says.)
+// The packed hand-over (PcvSortFacts::packed) needs the buffer, so the map gives way: it stays in LDS up to
+// pcv_sort_map_lds_staged(R, stride) entries — 15 824 / 11 216 entries at stride 3 for 128 / 256 digit values, 11 728 / 7 120 at
+// stride 4 — and is gathered from global memory above that. 12-byte records with color_in (the stage entry, PCV_COLOR_LATE) keep
+// their plan — a map of up to 16 384 entries in LDS, which leaves no room for the buffer — and their colour loads per lane.
+constexpr uint32_t kPcvSortLdsBytes = 163840;
+constexpr uint32_t pcv_sort_rec12_static_lds(bool plane, int R) {
+  return (uint32_t)kPcvSortRec12Tile * (plane ? 16u : 12u) + (uint32_t)R * 4u * (16u + 2u) + 64u;
+}
+constexpr uint32_t pcv_sort_color_buffer(int stride) { return pcv_color_stage_bytes(kPcvSortRec12Tile, (uint32_t)stride); }
+constexpr uint32_t pcv_sort_map_lds_staged(int R, int stride) {
+  return ((kPcvSortLdsBytes - pcv_sort_rec12_static_lds(false, R) - pcv_sort_color_buffer(stride)) / 16u) * 8u < pcv_sort_map_lds(false, R).max_entries
+             ? ((kPcvSortLdsBytes - pcv_sort_rec12_static_lds(false, R) - pcv_sort_color_buffer(stride)) / 16u) * 8u
+             : pcv_sort_map_lds(false, R).max_entries;
+}
+static_assert(pcv_sort_rec12_static_lds(false, 256) + 2 * (size_t)pcv_sort_map_lds_staged(256, 4) + pcv_sort_color_buffer(4) <= kPcvSortLdsBytes &&
+                  pcv_sort_rec12_static_lds(false, 128) + 2 * (size_t)pcv_sort_map_lds_staged(128, 3) + pcv_sort_color_buffer(3) <= kPcvSortLdsBytes,
+              "the lowered limits fit");
+// what the packed instantiations may ask for: everything the static part leaves (pcv_sort_rec12.hip asserts the static part)
+constexpr uint32_t pcv_sort_rec12_dyn_attr(int R) { return kPcvSortLdsBytes - pcv_sort_rec12_static_lds(false, R); }
+// The packed hand-over of the single-chain build (chain_pass_kernel DIAG 2 -> the first pass above), stated once.
+// Tried — the chain pass runs in the form that can pack — for 12-byte records of raw (not routed) input without an intensity plane.
+constexpr bool pcv_packed_handover_tried(bool switched_on, bool compact, bool routed, bool intensity) {
+  return switched_on && compact && !routed && !intensity;
+}
+// ... and the records are the 8-byte ones where the predicted tree T'' has at most 65 536 nodes: a predicted leaf is named by its
+// node index, which then fits the record's 16 bits. The chain pass asks the device's count of the nodes, the host its mirror of
+// the same tree; the sort's map has one entry per node. (constexpr: callable from kernels.)
+constexpr uint32_t kPcvPackedRanks = 65536;
+constexpr bool pcv_packed_handover(uint32_t tree_nodes) { return tree_nodes <= kPcvPackedRanks; }
 
 // upsweep_map_kernel<kMapLds = true> holds the map as words: 60 000 bytes next to its 4 KB of counters, inside the 64 KB a kernel
 // gets without opting in
@@ -90,6 +126,10 @@ struct PcvSortPass {
   bool PL;
   int MAP;
   size_t dyn_lds;
+  // first pass of the rows form: the records are the chain pass's packed 8-byte ones, and the bytes of the staged colours' buffer
+  // behind the map's dyn_lds (0 for every other form)
+  bool packed;
+  size_t color_lds;
 };
 
 struct PcvSortFacts {
@@ -101,6 +141,10 @@ struct PcvSortFacts {
   int vec_bytes = 16;
   int nwords = 0;
   bool color_in = false;  // (changes no pass: the first pass of the rows form reads the colour where it is set)
+  int color_stride = 3;
+  // the chain pass's packed hand-over: 8-byte records {codes / pool entry, code z | predicted rank << 16}, no key array, the
+  // colour in the caller's array (color_in). Rows form without a plane and map_entries <= kPcvPackedRanks only.
+  bool packed = false;
   // single-chain build: the rank map, the rank-count rows, a PcvSortSecond to hold the second pass back in
   bool map = false;
   uint32_t map_entries = 0;

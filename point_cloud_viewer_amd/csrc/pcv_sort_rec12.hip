@@ -7,6 +7,7 @@
 
 #include "pcv_sort_dev.h"
 // (after pcv_internal.h)
+#include "pcv_color_stage.h"
 #include "pcv_settle_dev.h"
 
 #ifndef PCV_FUSE_DIAG
@@ -56,7 +57,15 @@ constexpr uint32_t kFuseSettles = 1u, kFuseU8 = 2u;
 // digit each: a digit's run inside a tile is then ONE leaf's records at consecutive sorted slots. Waves take whole runs: the leaf's
 // record comes through the scalar cache, and the run's records leave as final bytes / climber records (flagged leaves) or as
 // 12-byte records like in the plain pass (the others: `settle` finishes those).
-template <int BLOCK, int KPT, int R, int WPE, bool NT, int MAP, bool PL, bool WC, bool FUSE>
+// PK (first pass of the rows form, no plane): the records are the chain pass's PACKED 8-byte ones — {codes x | y << 16 or the
+// pool entry, code z | predicted rank << 16}, no key array — and the colour joins here.
+// Its colours are staged: a tile's colours are contiguous bytes of the caller's array, fetched by the whole workgroup as aligned
+// 16-byte pieces in front of the NEXT tile's records (pcv_color_stage.h: at most two pieces per lane instead of eight unaligned
+// dwords), parked in dynamic LDS behind the map at the end of the iteration, and merged into the records after the ranking's
+// barriers, at the LDS scatter.
+// !PK: every other form compiles exactly as before the packed form existed (12-byte records with color_in keep their colour loads
+// per lane: with the plan they have, a map of 16 384 entries in LDS leaves no room for the colours' buffer).
+template <int BLOCK, int KPT, int R, int WPE, bool NT, int MAP, bool PL, bool WC, bool FUSE, bool PK = false>
 __device__ __forceinline__ void downsweep_rec12_body(const uint32_t* __restrict__ keys_in, uint32_t* __restrict__ keys_out, uint64_t n,
                                                      uint64_t chunk, int groups, int shift, int nbits, const uint32_t* __restrict__ offsets,
                                                      const uint32_t* __restrict__ totals, const uint2* __restrict__ vec_in,
@@ -67,6 +76,15 @@ __device__ __forceinline__ void downsweep_rec12_body(const uint32_t* __restrict_
                                                      uint32_t color_stride = 3) {
   constexpr int NW = BLOCK / 64, kTile = BLOCK * KPT, RW = R / 64;
   static_assert(!FUSE || (!WC && MAP == 0), "the settling pass: second pass of 12-byte records (+ the intensity plane)");
+  constexpr bool kStage = PK, staged = PK;
+  static_assert(!kStage || (MAP != 0 && !PL && !WC && !FUSE), "staged colours: first pass of the rows form, no plane");
+  // two pieces per lane cover a tile; the one piece more that a full stride-4 tile behind a skewed start needs (the 2 049th)
+  // is fetched as sixteen single bytes by sixteen lanes when the pieces are parked: no third piece's four registers
+  constexpr int kColRounds = kStage ? 2 : 1;
+  static_assert(!kStage || pcv_color_stage_pieces(kTile, 4) <= (uint32_t)(kColRounds * BLOCK + 1), "one piece beyond the rounds at most");
+  // the LDS rule of pcv_sort_plan.h rests on this static part
+  static_assert(!kStage || sizeof(uint32_t) * kTile + sizeof(uint2) * kTile + sizeof(DigitStateN<NW, R>) == pcv_sort_rec12_static_lds(false, R),
+                "pcv_sort_rec12_static_lds");
   __shared__ FuseLeaf sleaf[FUSE ? R : 1];  // FUSE: the leaf of digit value d in this piece: rank = d << low_bits | the piece's lower digit
   const uint32_t piece = order ? order[blockIdx.x] : blockIdx.x;
   static_assert(BLOCK >= R && R % 64 == 0 && KPT % 8 == 0, "geometry");
@@ -79,7 +97,10 @@ __device__ __forceinline__ void downsweep_rec12_body(const uint32_t* __restrict_
   __shared__ uint32_t wc_count[WC ? R : 1], wc_W[WC ? R : 1], wc_gb[WC ? R : 1], wc_A[WC ? R : 1], wc_ts[WC ? R : 1], wc_cnt[WC ? R : 1];
   __shared__ uint32_t wc_seg[WC ? R + 1 : 1];  // exclusive prefix of the digits' block counts of this tile; [R] = their sum
   __shared__ DigitStateN<NW, R> S;
-  extern __shared__ uint16_t smap_dyn[];  // MAP: map_entries half words: true rank (< 2^15) | replay mark << 15
+  extern __shared__ __attribute__((aligned(16))) uint16_t smap_dyn[];  // MAP: map_entries half words: true rank (< 2^15) | replay mark << 15
+  // the staged colours' buffer behind the map (MAP == 2: there is no map in LDS)
+  uint32_t* const scol = reinterpret_cast<uint32_t*>(smap_dyn) + (MAP == 1 ? ((map_entries * 2u + 15u) & ~15u) / 4u : 0u);
+  const uint32_t color_low4 = (uint32_t)reinterpret_cast<uintptr_t>(color_in) & 15u;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const uint32_t mask = (1u << nbits) - 1u;
   if (FUSE && t < R) {  // visible after the first barrier below
@@ -131,14 +152,39 @@ __device__ __forceinline__ void downsweep_rec12_body(const uint32_t* __restrict_
   uint32_t key[KPT];
   uint2 vec[KPT];
   uint32_t pln[PL ? KPT : 1];
+  uint4 col[kColRounds];  // staged colours: piece k x BLOCK + t of the tile in flight
   auto load_tile = [&](uint64_t base, uint32_t tile_n) {
-    const uint32_t* __restrict__ kp = keys_in + base + wbase;
+    if (kStage && staged) {  // the tile's colour bytes first (they are parked in LDS while the records are still on their way), 16 at a
+      // time; only bytes inside the caller's array are touched
+      const PcvColorTile ct = pcv_color_tile(color_low4, color_stride, base, tile_n);
+#pragma unroll
+      for (int k = 0; k < kColRounds; ++k) {
+        const uint32_t piece = (uint32_t)(k * BLOCK + t);
+        col[k] = make_uint4(0u, 0u, 0u, 0u);
+        if (piece < ct.npieces) {
+          const PcvColorSpan sp = pcv_color_piece(ct, piece, n, color_stride);
+          if (sp.lo == 0u && sp.hi == kPcvColorPiece) {
+            col[k] = *reinterpret_cast<const uint4*>(color_in + sp.at);
+          } else {  // the array's first / last bytes: one by one
+            uint64_t lo8 = 0, hi8 = 0;  // (a short loop, not unrolled: one lane of the grid's first and last tile runs it)
+#pragma unroll 1
+            for (uint32_t b = sp.lo; b < sp.hi; ++b) {
+              const uint64_t v = (uint64_t)color_in[sp.at + (int64_t)b] << (8u * (b & 7u));
+              if (b < 8u) lo8 |= v;
+              else hi8 |= v;
+            }
+            col[k] = make_uint4((uint32_t)lo8, (uint32_t)(lo8 >> 32), (uint32_t)hi8, (uint32_t)(hi8 >> 32));
+          }
+        }
+      }
+    }
+    const uint32_t* __restrict__ kp = PK ? nullptr : keys_in + base + wbase;
     const uint2* __restrict__ vp = vec_in + base + wbase;
     const uint32_t* __restrict__ pp = PL ? plane_in + base + wbase : nullptr;
     if (tile_n == (uint32_t)kTile) {  // full tile: straight-line loads off one base address each
 #pragma unroll
       for (int i = 0; i < KPT; ++i) {
-        key[i] = kp[i * 64];
+        if (!PK) key[i] = kp[i * 64];
         vec[i] = vp[i * 64];
         if (PL) pln[i] = pp[i * 64];
       }
@@ -146,12 +192,30 @@ __device__ __forceinline__ void downsweep_rec12_body(const uint32_t* __restrict_
 #pragma unroll
       for (int i = 0; i < KPT; ++i) {
         const bool valid = wbase + i * 64 < tile_n;
-        key[i] = valid ? kp[i * 64] : 0u;
+        if (!PK) key[i] = valid ? kp[i * 64] : 0u;
         vec[i] = valid ? vp[i * 64] : make_uint2(0u, 0u);
         if (PL) pln[i] = valid ? pp[i * 64] : 0u;
       }
     }
-    if (MAP != 0 && color_in) {  // (wave-uniform) the first pass of records that left the chain pass without their colour
+    if constexpr (PK) {
+      // packed records keep their rank where it is, in the upper half of vec.y — the true rank once it has been through the map
+      // (< 2^16: the map has at most 65 536 entries) — until the LDS scatter, where the key is made and the red and green bytes
+      // take its place: eight registers less across the ranking than a key array
+      uint32_t m[KPT];
+#pragma unroll
+      for (int i = 0; i < KPT; ++i) {
+        const uint32_t pr = vec[i].y >> 16;
+        m[i] = MAP == 1 ? (uint32_t)smap_dyn[pr < map_entries ? pr : 0u] : gmap[pr < map_entries ? pr : 0u];
+      }
+#pragma unroll
+      for (int i = 0; i < KPT; ++i) {
+        const bool replay = MAP == 1 ? (m[i] & 0x8000u) != 0u : (m[i] & (1u << 30)) != 0u;
+        if (__builtin_expect(replay, 0)) vec[i].x = (uint32_t)(base + wbase + i * 64);  // replay: the input index
+        vec[i].y = (vec[i].y & 0xffffu) | ((MAP == 1 ? (m[i] & 0x7fffu) : (m[i] & PCV_SPEC_INDEX_MASK)) << 16);
+      }
+      return;
+    }
+    if (MAP != 0 && color_in && !staged) {  // (wave-uniform) the first pass of records that left the chain pass without their colour
 #pragma unroll
       for (int i = 0; i < KPT; ++i) {
         const uint64_t idx = base + wbase + (uint32_t)(i * 64);
@@ -192,11 +256,37 @@ __device__ __forceinline__ void downsweep_rec12_body(const uint32_t* __restrict_
       }
     }
   };
+  // Staged colours: the pieces in `col` go to the LDS buffer. The first tile's before its ranking; the next tile's at the end of
+  // the iteration that requested them, behind that iteration's output phase — the records that read the buffer did so before the
+  // LDS scatter, a barrier ago, and the next readers come behind the ranking's barriers: no barrier of their own, and the
+  // pieces' registers are free while the ranking needs them.
+  auto park_colors = [&](uint64_t base, uint32_t tile_n) {
+    const PcvColorTile ct = pcv_color_tile(color_low4, color_stride, base, tile_n);
+#pragma unroll
+    for (int k = 0; k < kColRounds; ++k) {
+      const uint32_t piece = (uint32_t)(k * BLOCK + t);
+      if (piece < ct.npieces) reinterpret_cast<uint4*>(scol)[piece] = col[k];
+    }
+    // (that one piece more: loaded here, where it is parked — sixteen lanes of one wave wait for a byte each, and only for
+    // 4-byte colours in an array that is not 16-byte aligned)
+    if ((uint32_t)(kColRounds * BLOCK) < ct.npieces && t < (int)kPcvColorPiece) {
+      const PcvColorSpan sp = pcv_color_piece(ct, (uint32_t)(kColRounds * BLOCK), n, color_stride);
+      const uint32_t b = ((uint32_t)t >= sp.lo && (uint32_t)t < sp.hi) ? (uint32_t)color_in[sp.at + (int64_t)t] : 0u;
+      reinterpret_cast<uint8_t*>(scol)[(uint32_t)(kColRounds * BLOCK) * kPcvColorPiece + (uint32_t)t] = (uint8_t)b;
+    }
+  };
+  // the record's digit (PK: out of the rank in the upper half of vec.y; the first pass's shift counts from the key's bit 0)
+  auto digit_of = [&](int i) -> uint32_t { return PK ? ((vec[i].y >> 16) >> (shift - 8)) & mask : (key[i] >> shift) & mask; };
   // (MAP: the copy of the map above is complete: the digit-base prologue ended with a barrier)
-  if (begin < end) load_tile(begin, (uint32_t)((end - begin) < (uint64_t)kTile ? (end - begin) : (uint64_t)kTile));
+  if (begin < end) {
+    const uint32_t first_n = (uint32_t)((end - begin) < (uint64_t)kTile ? (end - begin) : (uint64_t)kTile);
+    load_tile(begin, first_n);
+    if (kStage && staged) park_colors(begin, first_n);
+  }
   for (uint64_t base = begin; base < end; base += kTile) {
     const uint32_t tile_n = (uint32_t)((end - base) < (uint64_t)kTile ? (end - base) : (uint64_t)kTile);
     const bool full = tile_n == (uint32_t)kTile;
+    const uint32_t col_skew = (kStage && staged) ? pcv_color_tile(color_low4, color_stride, base, tile_n).skew : 0u;
     // rank of every record among the earlier records of the same digit inside the wave's slice (see wave_rank_all)
     uint16_t lpos[KPT];
 #pragma unroll
@@ -206,7 +296,7 @@ __device__ __forceinline__ void downsweep_rec12_body(const uint32_t* __restrict_
       for (int j = 0; j < 8; ++j) {
         const int i = i0 + j;
         const bool valid = full || wbase + i * 64 < tile_n;
-        const uint32_t d = (key[i] >> shift) & mask;
+        const uint32_t d = digit_of(i);
         uint32_t plo = 0xffffffffu, phi = 0xffffffffu;
         if (!full) {
           const uint64_t vm = __ballot(valid);
@@ -278,13 +368,25 @@ __device__ __forceinline__ void downsweep_rec12_body(const uint32_t* __restrict_
       }
       __syncthreads();
     }
+    // red, green, blue of a record out of the parked bytes: the two aligned words around them
+    auto staged_rgb = [&](int i) -> uint32_t {
+      const uint32_t at = col_skew + (wbase + (uint32_t)(i * 64)) * color_stride;  // pcv_color_record_at
+      const uint32_t w0 = scol[at >> 2], w1 = scol[(at >> 2) + 1u];
+      return __builtin_amdgcn_alignbyte(w1, w0, at & 3u) & 0xffffffu;  // r | g << 8 | b << 16
+    };
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
       if (full || wbase + i * 64 < tile_n) {
-        const uint32_t d = (key[i] >> shift) & mask;
+        const uint32_t d = digit_of(i);
         const uint32_t p = S.whist[wave][d] + lpos[i];
-        skeys[p] = key[i];
-        svec[p] = vec[i];
+        if constexpr (PK) {
+          const uint32_t rgb = staged_rgb(i);
+          skeys[p] = ((vec[i].y >> 16) << 8) | (rgb >> 16);
+          svec[p] = make_uint2(vec[i].x, (vec[i].y & 0xffffu) | ((rgb & 0xffffu) << 16));
+        } else {
+          skeys[p] = key[i];
+          svec[p] = vec[i];
+        }
         if (PL) splane[p] = pln[i];
       }
     }
@@ -449,6 +551,10 @@ __device__ __forceinline__ void downsweep_rec12_body(const uint32_t* __restrict_
       __builtin_amdgcn_sched_barrier(0);
     }
     }
+    if (kStage && staged) {
+      const uint64_t nbase = base + kTile;
+      if (nbase < end) park_colors(nbase, (uint32_t)((end - nbase) < (uint64_t)kTile ? (end - nbase) : (uint64_t)kTile));
+    }
     for (int k = t; k < NW * R; k += BLOCK) (&S.whist[0][0])[k] = 0;  // last read before the barrier above
     __syncthreads();
   }
@@ -468,7 +574,7 @@ __device__ __forceinline__ void downsweep_rec12_body(const uint32_t* __restrict_
 
 
 template <int BLOCK, int KPT, int R, int WPE, bool NT, int MAP = 0 /* 1: the map in LDS (half words), 2: in global memory */, bool PL = false,
-          bool WC = false>
+          bool WC = false, bool PK = false /* packed 8-byte records in vec_in, keys_in unused; the colours staged through LDS */>
 __global__ __launch_bounds__(BLOCK, WPE) void downsweep_rec12_kernel(const uint32_t* __restrict__ keys_in,
                                                                      uint32_t* __restrict__ keys_out, uint64_t n, uint64_t chunk,
                                                                      int groups, int shift, int nbits,
@@ -485,9 +591,9 @@ __global__ __launch_bounds__(BLOCK, WPE) void downsweep_rec12_kernel(const uint3
                                                                      const uint8_t* __restrict__ color_in = nullptr /* MAP != 0: the
                                                                      records come without colour, record i's is here */,
                                                                      uint32_t color_stride = 3) {
-  downsweep_rec12_body<BLOCK, KPT, R, WPE, NT, MAP, PL, WC, false>(keys_in, keys_out, n, chunk, groups, shift, nbits, offsets, totals, vec_in,
-                                                                  vec_out, gmap, map_entries, ranges, order, plane_in, plane_out, PcvSortFuse(),
-                                                                  color_in, color_stride);
+  downsweep_rec12_body<BLOCK, KPT, R, WPE, NT, MAP, PL, WC, false, PK>(keys_in, keys_out, n, chunk, groups, shift, nbits, offsets, totals,
+                                                                       vec_in, vec_out, gmap, map_entries, ranges, order, plane_in, plane_out,
+                                                                       PcvSortFuse(), color_in, color_stride);
 }
 // the settling form of the second pass (FUSE above): a kernel of its own name for the profiles
 // (R = 128 digit values: the second digit of a rank of <= 15 bits has <= 7 bits; 256 for ranks of 16 bits)
@@ -648,17 +754,18 @@ __global__ __launch_bounds__(256) void msd_offsets_kernel(uint32_t* __restrict__
 //   tiles of 8 192: 1 024 x 8 1.20 ms (ships), 512 x 16 1.25; non-temporal stores +35 %
 //   tiles of 16 384 by staging keys and payloads one after the other through the same LDS: 1.27-1.29 against 1.01-1.11
 //   (two more barriers per tile, one workgroup per CU) — dropped
-template <int R, int MAP, bool PL, bool WC = false>
+template <int R, int MAP, bool PL, bool WC = false, bool PK = false>
 void launch_rec12(pcv_ctx* ctx, const PcvSortRec12Args& a) {
-  const auto kernel = downsweep_rec12_kernel<1024, 8, R, 4, false, MAP, PL, WC>;
-  if constexpr (MAP == 1) {  // the map in dynamic LDS: once per instantiation, the size from the table its entry limit comes from
+  const auto kernel = downsweep_rec12_kernel<1024, 8, R, 4, false, MAP, PL, WC, PK>;
+  // dynamic LDS (the map, the staged colours): once per instantiation, the size from the tables the plan's limits come from
+  if constexpr (MAP == 1 || PK) {
     static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)pcv_sort_map_lds(PL, R).attr_bytes) == hipSuccess;
+                                               (int)(PK ? pcv_sort_rec12_dyn_attr(R) : pcv_sort_map_lds(PL, R).attr_bytes)) == hipSuccess;
     (void)ok;
   }
-  hipLaunchKernelGGL(kernel, dim3(a.grid), dim3(1024), a.dyn_lds, ctx->stream, a.src, a.dst, a.n, a.chunk, a.grid, a.shift, a.nbits, a.hist,
-                     a.totals, (const uint2*)a.vec_in, (uint2*)a.vec_out, a.map, a.map_entries, (const uint2*)a.ranges, a.order, a.plane_in,
-                     a.plane_out, a.color_in, a.color_stride);
+  hipLaunchKernelGGL(kernel, dim3(a.grid), dim3(1024), a.dyn_lds + a.color_lds, ctx->stream, a.src, a.dst, a.n, a.chunk, a.grid, a.shift,
+                     a.nbits, a.hist, a.totals, (const uint2*)a.vec_in, (uint2*)a.vec_out, a.map, a.map_entries, (const uint2*)a.ranges, a.order,
+                     a.plane_in, a.plane_out, a.color_in, a.color_stride);
 }
 template <bool PL, int BLOCK, int R>
 void launch_settle(pcv_ctx* ctx, const PcvSortRec12Args& a) {
@@ -671,6 +778,7 @@ PcvSortRec12Args rec12_args(const PcvSortPlan& plan, const PcvSortPass& p, const
                             const uint32_t* totals) {
   PcvSortRec12Args r;
   r.R = p.R, r.MAP = p.MAP, r.PL = p.PL, r.dyn_lds = p.dyn_lds;
+  r.PK = p.packed, r.color_lds = p.color_lds;
   r.grid = p.down == PCV_DOWN_REC12_PIECES ? plan.pieces : plan.geom.groups;
   r.src = (const uint32_t*)s.src, r.dst = (uint32_t*)s.dst, r.n = plan.geom.n, r.chunk = plan.geom.chunk;
   r.shift = p.shift, r.nbits = p.nbits, r.hist = hist, r.totals = totals;
@@ -757,7 +865,7 @@ void rows_form(pcv_ctx* ctx, const PcvSortPlan& plan, uint32_t* a, uint32_t* b, 
   // rec_wc (bit 0: first pass, bit 1: second pass): the write-combining form of the downsweep measured slower than the kernel
   // that ships (profiles/r05_sort_same_box.json): not instantiated in libpcv_hip.so
   r.WC = (pcv_switches().rec_wc & 1) && !plan.with_plane && p1.nbits <= 7 && !payload->color_in;
-  if (r.WC) r.MAP = 2, r.dyn_lds = 0;  // (that form gathers the map from global memory)
+  if (r.WC) r.MAP = 2, r.dyn_lds = 0, r.color_lds = 0;  // (that form gathers the map from global memory)
 #endif
   pcv_sort_launch_rec12(ctx, r);
   if (plan.two_pass) rows_second_pass(ctx, plan, a, b, payload, scratch, lay, side_layout, second);
@@ -780,6 +888,10 @@ void pcv_sort_launch_rec12(pcv_ctx* ctx, const PcvSortRec12Args& a) {
 #ifdef PCV_EXPERIMENTS
   if (a.WC) return a.MAP ? launch_rec12<128, 2, false, true>(ctx, a) : launch_rec12<128, 0, false, true>(ctx, a);
 #endif
+  if (a.PK) {  // the chain pass's packed records (planned for the rows form without a plane only)
+    if (a.MAP == 1) return a.R == 256 ? launch_rec12<256, 1, false, false, true>(ctx, a) : launch_rec12<128, 1, false, false, true>(ctx, a);
+    return a.R == 256 ? launch_rec12<256, 2, false, false, true>(ctx, a) : launch_rec12<128, 2, false, false, true>(ctx, a);
+  }
   switch ((a.MAP << 2) | (a.R == 256 ? 2 : 0) | (a.PL ? 1 : 0)) {
     case 0: return launch_rec12<128, 0, false>(ctx, a);
     case 1: return launch_rec12<128, 0, true>(ctx, a);

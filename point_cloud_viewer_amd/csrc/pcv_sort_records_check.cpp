@@ -22,6 +22,9 @@ const char* pcv_sort_records_check(const pcv_sort_records_args* a, const PcvSort
   if (rows && a->map_entries > (1u << 18)) return "pcv_sort_records: rows of more than 2^18 ranks";
   if (a->color_in && !rows) return "pcv_sort_records: color_in is read by the first pass of the rows form only";
   if (a->plane0_in && a->nwords == 0) return "pcv_sort_records: plane0_in without a plane";
+  const bool packed = (a->flags & PCV_SORT_RECORDS_PACKED) != 0;
+  if (packed && !(rows && compact && a->nwords == 0 && a->color_in && a->map_entries <= kPcvPackedRanks))
+    return "pcv_sort_records: packed records need vec_bytes 8, no plane, rows, color_in and a map of <= 65 536 entries";
   if (a->n != 0) {
     if (!a->keys) return "pcv_sort_records: keys is null";
     if (a->vec_bytes != 0 && !a->vec) return "pcv_sort_records: vec is null";
@@ -33,6 +36,7 @@ const char* pcv_sort_records_check(const pcv_sort_records_args* a, const PcvSort
   const int base = compact ? 8 : 0;
   f.n = a->n, f.key_bytes = 4, f.begin_bit = base, f.end_bit = base + a->key_bits;
   f.vec_in = a->vec_bytes != 0, f.vec_bytes = a->vec_bytes ? a->vec_bytes : 16, f.nwords = a->nwords, f.color_in = a->color_in != nullptr;
+  f.color_stride = (int)a->color_stride, f.packed = packed;
   f.map = a->map != nullptr, f.map_entries = a->map ? a->map_entries : 0, f.rows = rows, f.second = a->map && a->hold_second;
   f.sort_rows2 = sw.sort_rows2, f.sort_msd = sw.sort_msd, f.rows_true_bins = sw.rows_true_bins;
   if (const char* why = pcv_sort_plan(f, plan)) return why;
@@ -40,6 +44,12 @@ const char* pcv_sort_records_check(const pcv_sort_records_args* a, const PcvSort
   if (plan->npasses && plan->pass[0].MAP == 1 && a->key_bits > 15)
     return "pcv_sort_records: a map of so few entries travels as half words: key_bits must be <= 15";
   *facts = f;
+  return nullptr;
+}
+
+const char* pcv_sort_records_check_packed(const uint32_t* vec, uint64_t n, uint32_t map_entries) {
+  for (uint64_t i = 0; i < n; ++i)
+    if ((vec[2 * i + 1] >> 16) >= map_entries) return "pcv_sort_records: a record's predicted rank lies outside the map";
   return nullptr;
 }
 

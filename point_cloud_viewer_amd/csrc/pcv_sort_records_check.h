@@ -16,4 +16,6 @@ const char* pcv_sort_records_check(const pcv_sort_records_args* a, const PcvSort
                                    PcvSortPlan* plan);
 // PCV_SORT_RECORDS_CHECK_KEYS: every predicted rank of `keys` (host memory) lies inside the map. Null, or the reason.
 const char* pcv_sort_records_check_keys(const uint32_t* keys, uint64_t n, int vec_bytes, uint32_t map_entries);
+// ... of packed records (PCV_SORT_RECORDS_PACKED: the rank sits in the upper half of a record's second word)
+const char* pcv_sort_records_check_packed(const uint32_t* vec, uint64_t n, uint32_t map_entries);
 void pcv_sort_records_plan_info(const PcvSortPlan& plan, pcv_sort_plan_info* out);

@@ -110,16 +110,19 @@ extern "C" int pcv_sort_records(pcv_ctx* ctx, const pcv_sort_records_args* args,
   const pcv_sort_records_args& a = *args;
   const uint64_t n = a.n;
   const bool host = a.mem == PCV_MEM_HOST;
+  const bool packed = (a.flags & PCV_SORT_RECORDS_PACKED) != 0;
   if (n && a.map && (a.flags & PCV_SORT_RECORDS_CHECK_KEYS)) {
     std::vector<uint32_t> copy;
-    const uint32_t* hk = a.keys;
+    const uint32_t* hk = packed ? (const uint32_t*)a.vec : a.keys;  // (packed: the ranks are in the records)
+    const size_t words = packed ? 2 * n : n;
     if (!host) {
-      copy.resize(n);
+      copy.resize(words);
       PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-      PCV_HIP_CHECK(ctx, hipMemcpy(copy.data(), a.keys, n * 4, hipMemcpyDeviceToHost));
+      PCV_HIP_CHECK(ctx, hipMemcpy(copy.data(), hk, words * 4, hipMemcpyDeviceToHost));
       hk = copy.data();
     }
-    if (const char* why = pcv_sort_records_check_keys(hk, n, a.vec_bytes, a.map_entries)) return ctx->fail(PCV_E_INVALID, why);
+    if (const char* why = packed ? pcv_sort_records_check_packed(hk, n, a.map_entries) : pcv_sort_records_check_keys(hk, n, a.vec_bytes, a.map_entries))
+      return ctx->fail(PCV_E_INVALID, why);
   }
   if (plan_out) pcv_sort_records_plan_info(plan, plan_out);
   if (n == 0) return PCV_OK;
@@ -161,6 +164,7 @@ extern "C" int pcv_sort_records(pcv_ctx* ctx, const pcv_sort_records_args* args,
   pl.first_in0 = (const uint32_t*)dev;
   if ((rc = staged(a.color_in, n * a.color_stride, &dev))) return rc;
   pl.color_in = (const uint8_t*)dev, pl.color_stride = a.color_in ? a.color_stride : 3;
+  pl.packed = packed;
   if ((rc = staged(a.map, (size_t)a.map_entries * 4, &dev))) return rc;
   const uint32_t* map = (const uint32_t*)dev;
   const uint32_t* rows = nullptr;
@@ -175,7 +179,7 @@ extern "C" int pcv_sort_records(pcv_ctx* ctx, const pcv_sort_records_args* args,
     uint32_t *counted, *counts;
     if ((rc = sc.get(&counted, rows_words)) || (rc = sc.get(&counts, a.map_entries))) return rc;
     PCV_HIP_CHECK(ctx, hipMemsetAsync(counts, 0, (size_t)a.map_entries * 4, st));
-    pcv_launch_rank_hist_rows(ctx, ka, n, a.map_entries, counts, 8, sgroups, schunk, counted);
+    pcv_launch_rank_hist_rows(ctx, ka, n, a.map_entries, counts, packed ? 0 : 8, sgroups, schunk, counted, packed);
     PCV_HIP_CHECK(ctx, hipGetLastError());
     if (a.rows) PCV_HIP_CHECK(ctx, hipMemcpyAsync(a.rows, counted, rows_words * 4, outk, st));
     rows = counted;

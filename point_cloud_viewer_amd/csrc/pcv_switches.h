@@ -11,6 +11,7 @@ struct PcvSwitches {
   bool code_steps = true;          // 0: every Float32 level step of the chain in full (test_gpu_single_chain)
   bool color_late = false;         // 1: the record sort's first pass fetches the colour, not the chain pass (test_gpu_single_chain)
   bool compact_records = true;     // 0: 20-byte records in the single-chain build (test_gpu_single_chain)
+  bool packed_handover = true;     // 0: the chain pass hands the sort 12-byte records with their colour (test_gpu_packed_handover)
   int rec_wc = 0;                  // bit 0 / 1: write-combining downsweep in the record sort's first / second pass (test_gpu_single_chain)
   uint32_t rows_true_bins = 0;     // 32768 / 65536: the 15- / 16-bit rank geometry on a cloud of any size (test_gpu_single_chain)
   bool sample_counts = false;      // 1: the sample tree by counting the keys instead of sorting them (test_gpu_single_chain)
@@ -42,6 +43,7 @@ inline const PcvSwitches& pcv_switches() {
     flag("PCV_CODE_STEPS", &s.code_steps);
     flag("PCV_COLOR_LATE", &s.color_late);
     flag("PCV_COMPACT_RECORDS", &s.compact_records);
+    flag("PCV_PACKED_HANDOVER", &s.packed_handover);
     if (const char* e = getenv("PCV_REC_WC")) s.rec_wc = atoi(e);
     if (const char* e = getenv("PCV_ROWS_TRUE_BINS")) s.rows_true_bins = (uint32_t)atoi(e);
     flag("PCV_SAMPLE_COUNTS", &s.sample_counts);

@@ -782,11 +782,13 @@ class Context:
         return k.keep, v.keep
 
     def sort_records(self, keys, key_bits, vec=None, planes=(), plane0_in=None, color_in=None, color_stride=3, map=None, rows=None,
-                     hold_second=False, check_keys=True):
+                     hold_second=False, check_keys=True, packed=False):
         """The build's stable record sort on its own (pcv_sort_records), in place: u32 keys, a payload `vec` of shape (n, 2) (12-byte
         records: the rank sits above a colour byte) or (n, 4) words or none, and up to 8 planes of words; all numpy arrays or all
         device tensors. plane0_in: plane 0 is read from this array, which is left as it is (planes[0] receives the sorted plane).
         rows: None, "device" (counted on the device and returned) or the rank counts per sort workgroup, shape (groups, len(map)).
+        packed: `vec` holds the chain pass's 8-byte records (second word: third code | predicted rank << 16) and `keys` only
+        receives the sorted keys; on input its first 2 n bytes hold the ranks as half words, which rows="device" counts.
         Returns (keys, vec, planes, rows, plan): the sorted arrays, the rows the device counted (or None) and the plan the sort
         ran as a dict (the fields of pcv_sort_plan_info)."""
         k = _Buf(keys, np.uint32, "keys")
@@ -828,7 +830,7 @@ class Context:
         a.rows_mode = L.SORT_ROWS_NONE if rows is None else L.SORT_ROWS_DEVICE if counted else L.SORT_ROWS_GIVEN
         a.hold_second = 1 if hold_second else 0
         a.mem = L.MEM_DEVICE if k.device else L.MEM_HOST
-        a.flags = L.SORT_RECORDS_CHECK_KEYS if check_keys else 0
+        a.flags = (L.SORT_RECORDS_CHECK_KEYS if check_keys else 0) | (L.SORT_RECORDS_PACKED if packed else 0)
         info = L.SortPlanInfo()
         self._check(self.lib.pcv_sort_records(self.handle, C.byref(a), C.byref(info)))
         plan = {f: getattr(info, f) for f, _ in L.SortPlanInfo._fields_ if f != "passes"}
@@ -1176,6 +1178,12 @@ class OctreeResult:
                     continued_points=int(self.lib.pcv_octree_spec_continued(self.handle)),
                     wide_pool_entries=int(self.lib.pcv_octree_wide_pool_entries(self.handle)),
                     settled_in_sort=int(self.lib.pcv_octree_settled_in_sort(self.handle)))
+
+    def packed_handover(self):
+        """How the chain pass handed its records to the record sort (pcv_octree_packed_handover): 1 = 8-byte records and a plane of
+        16-bit ranks, loaded as they are by the sort's first pass; 2 = those, unpacked for a sort that cannot take them; 0 = records
+        with their colour (the exact pipeline, an intensity plane, routed input, a predicted tree of more than 65 536 nodes)."""
+        return int(self.lib.pcv_octree_packed_handover(self.handle))
 
     def write_dir(self, directory):
         self.ctx._check(self.lib.pcv_octree_write_dir(self.handle, str(directory).encode()))
