@@ -87,6 +87,14 @@ PCV_SA(sizeof(pcv_terrain_info) == 72 && offsetof(pcv_terrain_info, points_added
            offsetof(pcv_terrain_info, pool_bytes) == 40 && offsetof(pcv_terrain_info, vertex_min) == 48 &&
            offsetof(pcv_terrain_info, vertex_max) == 56 && offsetof(pcv_terrain_info, finished) == 64,
        "pcv_terrain_info");
+PCV_SA(sizeof(pcv_maptiles_params) == 32 && offsetof(pcv_maptiles_params, zoom) == 0 && offsetof(pcv_maptiles_params, background) == 4 &&
+           offsetof(pcv_maptiles_params, max_tiles) == 8 && offsetof(pcv_maptiles_params, max_pool_bytes) == 16 &&
+           offsetof(pcv_maptiles_params, staging_points) == 24,
+       "pcv_maptiles_params");
+PCV_SA(sizeof(pcv_maptiles_info) == 240 && offsetof(pcv_maptiles_info, points_added) == 0 && offsetof(pcv_maptiles_info, dropped) == 8 &&
+           offsetof(pcv_maptiles_info, drawn) == 16 && offsetof(pcv_maptiles_info, pool_bytes) == 24 && offsetof(pcv_maptiles_info, zoom) == 32 &&
+           offsetof(pcv_maptiles_info, min_zoom) == 36 && offsetof(pcv_maptiles_info, finished) == 40 && offsetof(pcv_maptiles_info, tiles) == 48,
+       "pcv_maptiles_info");
 PCV_SA(sizeof(pcv_render_terrain_layers) == 24 && offsetof(pcv_render_terrain_layers, num_layers) == 0 &&
            offsetof(pcv_render_terrain_layers, window) == 4 && offsetof(pcv_render_terrain_layers, layers) == 8 &&
            offsetof(pcv_render_terrain_layers, camera_positions) == 16,

@@ -1872,6 +1872,93 @@ int pcv_render_terrain_info(pcv_render* r, uint32_t view, uint32_t layer, int64_
 #define PCV_CLOUD_S2 1
 int pcv_cloud_kind(const char* directory, int* kind);
 
+/* ---- map tiles ---------------------------------------------------------------------------- */
+/* z/x/y PNG pyramids of Earth-fixed (ECEF) clouds, the tiles of a slippy web map. The reference has the coordinates
+ * (src/math/web_mercator.rs: TILE_SIZE = 256 and MAX_ZOOM = 23 at :18-23, WebMercatorCoord::to_zoomed_coordinate at :70-77,
+ * from_zoomed_coordinate at :84-93) and WebMercatorRect::from_zoomed_coordinates; it ships no generator. The product is this
+ * library's and is stated here.
+ *   pixel   (u, v) = the chain of pcv_wmr_project; S = 256 * 2^zoom; gx = floor(u S), gy = floor(v S) (exact: S is a power
+ *           of two) = floor(to_zoomed_coordinate(zoom)). The point is DRAWN iff x, y, z, u S and v S are finite and u S, v S
+ *           are >= 0 and < S, else it is DROPPED and counted (NaN or infinite coordinates, also where the chain's atan2
+ *           would give them a finite (u, v); lng = pi; a clamped latitude whose v rounds outside). Its
+ *           tile is (gx >> 8, gy >> 8), its pixel in the tile (gx & 255, gy & 255); row 0 is north. Tile membership equals
+ *           what pcv_wmr_from_zoomed((256 x, 256 y), (256 (x + 1), 256 (y + 1)), zoom) keeps in a point query, bit for bit.
+ *   value   per pixel the exact integer sums of r, g, b and the count n of its drawn points; the image is xray's `colored`
+ *           (PCV_XRAY_FN_COLORED) of them, a pixel without a point is transparent, and pixels with alpha < 128 take
+ *           `background`. The bytes depend on the multiset of points only. A pixel with more than 2^24 points fails finish.
+ *   parents tile (x, y) of zoom k has the children (2x + dx, 2y + dy) of zoom k + 1; the 2:1 Lanczos3 resize of
+ *           pcv_xray_build_parents over the quadtree index of pcv_maptiles_quad_index_host; a missing child is background.
+ *   files   <dir>/<z>/<x>/<y>.png and <dir>/tiles.json (pcv_maptiles_json_host). */
+#define PCV_MAPTILES_MAX_ZOOM 23
+#define PCV_MAPTILES_TILE_PX 256
+typedef struct pcv_maptiles_params {
+  uint32_t zoom;            /* 0 ..= 23: the zoom the points are drawn at */
+  uint32_t background;      /* packed RGBA8, r | g << 8 | b << 16 | a << 24; 0: transparent black */
+  uint64_t max_tiles;       /* 1 ..= 2^22: tiles the points may touch (the tile table holds twice as many keys) */
+  uint64_t max_pool_bytes;  /* cap on the accumulators of the touched tiles (1 MiB each); 0: 2 GiB */
+  uint64_t staging_points;  /* points per piece (16 bytes of keys and staging each); 0: 2^22 */
+} pcv_maptiles_params;
+typedef struct pcv_maptiles_info {
+  uint64_t points_added;    /* every point handed in, dropped ones included */
+  uint64_t dropped;         /* after finish */
+  uint64_t drawn;           /* after finish: points_added - dropped */
+  uint64_t pool_bytes;      /* accumulators held for the touched tiles (none after finish) */
+  uint32_t zoom, min_zoom;  /* min_zoom < zoom once pcv_maptiles_build_parents has run */
+  uint32_t finished, reserved;
+  uint64_t tiles[24];       /* per zoom; at `zoom` before finish: tiles touched so far */
+} pcv_maptiles_info;
+typedef struct pcv_maptiles pcv_maptiles;
+/* PCV_E_INVALID: what pcv_maptiles_check_params_host refuses. No tile range is declared: tiles are found by a mark pass
+ * into a device hash table keyed by (x, y), and accumulators are allocated for the tiles a point touches only. */
+int pcv_maptiles_begin(pcv_ctx* ctx, const pcv_maptiles_params* params, pcv_maptiles** out);
+/* n ECEF points: f64 planes and 3-byte colours that live where `mem` says, taken in pieces of staging_points. More than
+ * 2^32 - 1 points in total is PCV_E_INVALID (nothing of the call is added). More than max_tiles touched tiles, or
+ * accumulators past max_pool_bytes, is PCV_E_OOM: everything held on the device is released and the handle can only be freed. */
+int pcv_maptiles_add_points(pcv_maptiles* m, uint64_t n, const double* x, const double* y, const double* z, const uint8_t* rgb, int mem);
+/* The points of segments [first_segment, first_segment + num_segments) of a query result, pulled through a staging buffer
+ * of staging_points rows filled by the PLY output's packer, as pcv_terrain_add_query_batch; pieces are cut at any row. */
+int pcv_maptiles_add_query_batch(pcv_maptiles* m, pcv_query_batch* batch, uint64_t first_segment, uint64_t num_segments);
+int pcv_maptiles_add_s2_query(pcv_maptiles* m, pcv_s2_query* query, uint64_t first_segment, uint64_t num_segments);
+/* Accumulators -> RGBA8 images and u32 count planes of the touched tiles, ascending by (x, y). No points after it.
+ * PCV_E_INVALID "choose a larger zoom": a pixel holds more than 2^24 points. A finish that fails releases everything held on
+ * the device, and the handle can only be freed. */
+int pcv_maptiles_finish(pcv_maptiles* m);
+/* After finish: the levels zoom - 1 down to min_zoom (<= zoom; == zoom builds nothing). Calling it again with the same
+ * min_zoom is PCV_OK; with another one PCV_E_INVALID. */
+int pcv_maptiles_build_parents(pcv_maptiles* m, uint32_t min_zoom);
+/* After finish. The tiles of `zoom` (min_zoom ..= zoom), 2 x u32 (x, y) each, ascending by (x, y), into host memory. */
+int pcv_maptiles_tiles(const pcv_maptiles* m, uint32_t zoom, uint64_t capacity, uint32_t* xy, uint64_t* num_tiles);
+/* Tiles [first, first + count) of that list: count x 256 x 256 x 4 bytes (row 0 north), into memory that lives where `mem`
+ * says. pcv_maptiles_counts: count x 256 x 256 u32 points per pixel, of the tiles of the maximum zoom. */
+int pcv_maptiles_images(pcv_maptiles* m, uint32_t zoom, uint64_t first, uint64_t count, int mem, uint8_t* rgba);
+int pcv_maptiles_counts(pcv_maptiles* m, uint64_t first, uint64_t count, int mem, uint32_t* out);
+/* Complete PNG files of tiles [first, first + count) of `zoom`, back to back in `out` (host; NULL: the offsets alone), file i
+ * at offsets[i] .. offsets[i + 1] (count + 1 offsets), as pcv_xray_node_pngs; mode: PCV_XRAY_PNG_STORED or _DEFLATE. */
+int pcv_maptiles_tile_pngs(pcv_maptiles* m, uint32_t zoom, uint64_t first, uint64_t count, int mode, uint64_t capacity, uint8_t* out,
+                           uint64_t* offsets);
+/* <directory>/<z>/<x>/<y>.png for every tile of every built zoom, encoded as pcv_maptiles_tile_pngs and written by the host
+ * threads of the xray quadtree's writer (pcv_xray_write_dir_ex), then <directory>/tiles.json. PCV_E_IO names the file. */
+int pcv_maptiles_write_dir(pcv_maptiles* m, const char* directory, int png_mode);
+int pcv_maptiles_info_get(const pcv_maptiles* m, pcv_maptiles_info* out);
+void pcv_maptiles_free(pcv_maptiles* m);
+/* Host only, no context (messages: pcv_host_last_error). PCV_E_INVALID: zoom above 23, max_tiles 0 or above 2^22. min_zoom is
+ * checked against zoom as pcv_maptiles_build_parents does; pass zoom itself where no parents are wanted. */
+int pcv_maptiles_check_params_host(const pcv_maptiles_params* params, uint32_t min_zoom);
+/* The pixel rule on the host, the kernels' twin (web_mercator.rs:70-77): gx, gy (u32, 0 where dropped) and ok (1 drawn,
+ * 0 dropped) of n points; each output nullable. */
+int pcv_maptiles_pixels_host(uint32_t zoom, uint64_t n, const double* x, const double* y, const double* z, uint32_t* gx, uint32_t* gy,
+                             uint8_t* ok);
+/* The xray quadtree index (pcv_xray_nodes' index at level `zoom`) of slippy tile (x, y), and back: digit 2 xbit + (1 - ybit)
+ * per level from the most significant bit. PCV_E_INVALID: zoom above 23, x or y >= 2^zoom, index >= 4^zoom. */
+int pcv_maptiles_quad_index_host(uint32_t zoom, uint32_t x, uint32_t y, uint64_t* index);
+int pcv_maptiles_quad_tile_host(uint32_t zoom, uint64_t index, uint32_t* x, uint32_t* y);
+/* tiles.json: {"scheme":"xyz","format":"png","tile_size":256,"minzoom":a,"maxzoom":z,"bounds":[west,south,east,north],
+ * "tiles":{"<a>":[[x,y],...],...,"<z>":[...]}}. counts: tiles per zoom, a ..= z; xy: their (x, y), zoom after zoom. bounds in
+ * degrees: the hull of the corners of the tiles of zoom z through pcv_wmr_to_lat_lng (from_zoomed_coordinate :84-93, then
+ * to_lat_lng), zeros without a tile; doubles as in the terrain's meta.json. *len: the length; buf takes min(cap, *len) bytes. */
+int pcv_maptiles_json_host(uint32_t min_zoom, uint32_t max_zoom, const uint64_t* counts, const uint32_t* xy, char* buf, uint64_t cap,
+                           uint64_t* len);
+
 #ifdef __cplusplus
 }
 #endif

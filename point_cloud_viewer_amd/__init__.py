@@ -14,6 +14,8 @@ from .octree import (Aabb, Context, OctreeResult, QueryBatch, RenderedViews, S2C
                      ply_append_check, ply_header, ply_layout,
                      Terrain, build_terrain, read_terrain, terrain_check_params, terrain_frame, terrain_meta_json, terrain_params,
                      terrain_quad_masks, terrain_tile_name, terrain_vertex, terrain_meta_read,
+                     MapTiles, build_map_tiles, map_tile_from_quad_index, map_tile_pixels, map_tile_quad_index, map_tiles_check_params,
+                     map_tiles_json, map_tiles_params, read_map_tiles,
                      render_check_overlay, render_check_params, render_gamma_lut, render_overlay, render_params,
                      render_check_terrain, render_terrain_window,
                      polygon_check, polygon_contains, polygon_from_lat_lng, polygon_intersects_cubes,

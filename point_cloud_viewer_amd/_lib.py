@@ -224,6 +224,16 @@ class TerrainInfo(C.Structure):  # pcv_terrain_info
                 ("finished", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class MapTilesParams(C.Structure):  # pcv_maptiles_params
+    _fields_ = [("zoom", C.c_uint32), ("background", C.c_uint32), ("max_tiles", C.c_uint64), ("max_pool_bytes", C.c_uint64),
+                ("staging_points", C.c_uint64)]
+
+
+class MapTilesInfo(C.Structure):  # pcv_maptiles_info
+    _fields_ = [("points_added", C.c_uint64), ("dropped", C.c_uint64), ("drawn", C.c_uint64), ("pool_bytes", C.c_uint64),
+                ("zoom", C.c_uint32), ("min_zoom", C.c_uint32), ("finished", C.c_uint32), ("reserved", C.c_uint32), ("tiles", C.c_uint64 * 24)]
+
+
 class OocStats(C.Structure):
     _fields_ = [("points", C.c_uint64), ("nodes", C.c_uint64), ("partitions", C.c_uint64), ("largest_bucket", C.c_uint64),
                 ("spill_bytes", C.c_uint64), ("h2d_bytes", C.c_uint64), ("d2h_bytes", C.c_uint64), ("h2d_ms", C.c_double),
@@ -497,6 +507,24 @@ _SIGNATURES = {
     "pcv_terrain_quad_masks_host": (C.c_int, [C.c_int64, C.c_int64, C.c_uint32, C.c_uint32, _vp, _vp]),
     "pcv_terrain_tile_name_host": (C.c_int, [C.c_int32, C.c_int32, C.c_char_p, C.c_uint64]),
     "pcv_terrain_meta_json_host": (C.c_int, [C.POINTER(TerrainParams), C.c_uint64, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "pcv_maptiles_begin": (C.c_int, [_vp, C.POINTER(MapTilesParams), C.POINTER(_vp)]),
+    "pcv_maptiles_add_points": (C.c_int, [_vp, C.c_uint64, _vp, _vp, _vp, _vp, C.c_int]),
+    "pcv_maptiles_add_query_batch": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
+    "pcv_maptiles_add_s2_query": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64]),
+    "pcv_maptiles_finish": (C.c_int, [_vp]),
+    "pcv_maptiles_build_parents": (C.c_int, [_vp, C.c_uint32]),
+    "pcv_maptiles_tiles": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _vp, C.POINTER(C.c_uint64)]),
+    "pcv_maptiles_images": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, _vp]),
+    "pcv_maptiles_counts": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_int, _vp]),
+    "pcv_maptiles_tile_pngs": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, _vp, _vp]),
+    "pcv_maptiles_write_dir": (C.c_int, [_vp, C.c_char_p, C.c_int]),
+    "pcv_maptiles_info_get": (C.c_int, [_vp, C.POINTER(MapTilesInfo)]),
+    "pcv_maptiles_free": (None, [_vp]),
+    "pcv_maptiles_check_params_host": (C.c_int, [C.POINTER(MapTilesParams), C.c_uint32]),
+    "pcv_maptiles_pixels_host": (C.c_int, [C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pcv_maptiles_quad_index_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "pcv_maptiles_quad_tile_host": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "pcv_maptiles_json_host": (C.c_int, [C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

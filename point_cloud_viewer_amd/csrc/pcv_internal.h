@@ -130,6 +130,12 @@ enum PcvKernelId {
   PCV_K_TERRAIN_MASK,         // pcv_terrain.hip: quad masks from the set flags of each vertex's neighbourhood, across tile seams
   PCV_K_RENDER_TERRAIN_GATHER,  // pcv_render_views_terrain: the window vertices of every (view, layer): tile lookup, f64 chain, clip point
   PCV_K_RENDER_TERRAIN_EDGES,   // pcv_render_views_terrain: patches of window vertices in LDS, the drawn edges clipped and rasterised
+  PCV_K_MAPTILES_PROJECT,     // pcv_maptiles.hip: one thread per point, the web-mercator chain, an 8-byte (gx, gy) key per point
+  PCV_K_MAPTILES_MARK,        // pcv_maptiles.hip: keys -> the hash table of touched tiles, a slot per new tile
+  PCV_K_MAPTILES_ACCUM,       // pcv_maptiles.hip: keys and colours -> two 64-bit atomic adds per drawn point
+  PCV_K_MAPTILES_UNPACK,      // pcv_maptiles.hip: packed x y z r g b rows of a query result's piece into the staging planes
+  PCV_K_MAPTILES_RESOLVE,     // pcv_maptiles.hip: accumulators -> RGBA8 images and count planes, the 2^24 check
+  PCV_K_MAPTILES_PARENT,      // pcv_maptiles_build_parents: xray_parent_kernel over the zooms below the maximum
   PCV_K_COUNT
 };
 

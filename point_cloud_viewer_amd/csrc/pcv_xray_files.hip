@@ -28,10 +28,6 @@
 
 namespace {
 
-// takes the finished file of a node; false: it could not be kept (PCV_E_IO). May be called from several threads at once
-// where xray_node_files is asked to work in parallel
-using XrayFileSink = std::function<bool(uint64_t node, const uint8_t* file, uint64_t len)>;
-
 bool write_at(int dirfd, const std::string& name, const uint8_t* data, uint64_t len) {
   const int fd = openat(dirfd, name.c_str(), O_CREAT | O_WRONLY | O_TRUNC | O_CLOEXEC, 0666);
   if (fd < 0) return false;
@@ -385,21 +381,19 @@ int xray_deflate_chunks(pcv_ctx* ctx, uint32_t W, uint64_t count, uint64_t per_c
   return rc;
 }
 
-// nodes [first, first + count) whose images are on x's device, encoded in `mode`, each file to the sink
-int xray_device_node_files(pcv_xray* x, uint64_t first, uint64_t count, int mode, bool parallel, const XrayFileSink& sink) {
-  pcv_ctx* ctx = x->ctx;
-  const uint32_t W = x->W;
+}  // namespace
+
+int xray_tile_files(pcv_ctx* ctx, uint32_t W, uint64_t count, int mode, bool parallel, const XrayTileSrc& src, const XrayFileSink& sink) {
   const uint64_t tile_bytes = 4ull * W * W;
   const uint64_t per_chunk = ctx->xray_chunk_bytes / tile_bytes;
   std::atomic<int> failed{0};
-  auto src = [&](uint64_t f, uint64_t c, const uint8_t** a, uint64_t* na, const uint8_t** b) { xray_device_tiles(x, first + f, c, a, na, b); };
   if (mode == PCV_XRAY_PNG_DEFLATE)
     return xray_deflate_chunks(ctx, W, count, per_chunk, src, [&](uint64_t f, uint64_t c, const uint8_t* streams, const uint64_t* offs) {
       xray_parallel_for(c, parallel, [&](uint64_t i, std::vector<uint8_t>& png) {
         if (failed.load()) return;
         png.resize(kPcvPngWrap + offs[i + 1] - offs[i]);
         pcv_png_wrap(W, W, streams + offs[i], offs[i + 1] - offs[i], png.data());
-        if (!sink(first + f + i, png.data(), png.size())) failed.store(1);
+        if (!sink(f + i, png.data(), png.size())) failed.store(1);
       });
       return failed.load() ? PCV_E_IO : PCV_OK;
     });
@@ -408,10 +402,20 @@ int xray_device_node_files(pcv_xray* x, uint64_t first, uint64_t count, int mode
       if (failed.load()) return;
       png.resize(pcv_png_stored_size(W, W));
       pcv_png_stored_encode(images + i * tile_bytes, W, W, png.data());
-      if (!sink(first + f + i, png.data(), png.size())) failed.store(1);
+      if (!sink(f + i, png.data(), png.size())) failed.store(1);
     });
     return failed.load() ? PCV_E_IO : PCV_OK;
   });
+}
+
+namespace {
+
+// nodes [first, first + count) whose images are on x's device, encoded in `mode`, each file to the sink
+int xray_device_node_files(pcv_xray* x, uint64_t first, uint64_t count, int mode, bool parallel, const XrayFileSink& sink) {
+  return xray_tile_files(
+      x->ctx, x->W, count, mode, parallel,
+      [&](uint64_t f, uint64_t c, const uint8_t** a, uint64_t* na, const uint8_t** b) { xray_device_tiles(x, first + f, c, a, na, b); },
+      [&](uint64_t i, const uint8_t* file, uint64_t len) { return sink(first + i, file, len); });
 }
 
 // the files of nodes [first, first + count) of any kind of quadtree: opened nodes as their files are, the others encoded

@@ -3,6 +3,7 @@
 // files of any kind of quadtree).
 #pragma once
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -124,3 +125,14 @@ PCV_XRAY_LOCAL int queue_node_images(pcv_xray* x, uint64_t first, uint64_t count
 PCV_XRAY_LOCAL int opened_node_to_host(const pcv_xray* x, uint64_t node, uint8_t* dst);
 // node images of any kind of quadtree into checked arguments; returns after the copies have completed
 PCV_XRAY_LOCAL int xray_node_images(pcv_xray* x, uint64_t first, uint64_t count, int mem, uint8_t* rgba);
+
+// pcv_xray_files.hip, the writer of device tiles as the map tiles use it too (pcv_maptiles.hip)
+// takes the finished file of tile i; false: it could not be kept (PCV_E_IO). May be called from several threads at once where
+// xray_tile_files is asked to work in parallel
+using XrayFileSink = std::function<bool(uint64_t i, const uint8_t* file, uint64_t len)>;
+// names the device tiles [f, f + c): tile i of them is a + i * 4 W W for i < na and b + (i - na) * 4 W W after that
+using XrayTileSrc = std::function<void(uint64_t f, uint64_t c, const uint8_t** a, uint64_t* na, const uint8_t** b)>;
+// `count` W x W device tiles encoded in `mode` (PCV_XRAY_PNG_STORED / _DEFLATE), a chunk of pcv_ctx_set_xray_chunk_bytes at a
+// time through two pinned buffers; while chunk k + 1 is on its way, up to 8 host threads (`parallel`; else the caller, in
+// order) wrap chunk k and hand each file to the sink
+PCV_XRAY_LOCAL int xray_tile_files(pcv_ctx* ctx, uint32_t W, uint64_t count, int mode, bool parallel, const XrayTileSrc& src, const XrayFileSink& sink);

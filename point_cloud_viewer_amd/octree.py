@@ -233,6 +233,13 @@ class Context:
         self._check(self.lib.pcv_terrain_begin(self.handle, C.byref(pr), lo, hi, C.byref(h)))
         return Terrain(self, h, pr)
 
+    def map_tiles_begin(self, zoom, **params):
+        """An empty MapTiles layer at `zoom` (pcv_maptiles_begin); params: map_tiles_params' arguments."""
+        pr = map_tiles_params(zoom, **params)
+        h = C.c_void_p()
+        self._check(self.lib.pcv_maptiles_begin(self.handle, C.byref(pr), C.byref(h)))
+        return MapTiles(self, h, pr)
+
     def terrain_open(self, directory):
         """The finished Terrain of a terrain directory (pcv_terrain_open_dir): what Terrain.write leaves, or any directory
         sdl_viewer --terrain reads. It serves tiles, heights, colors, info, write and OctreeResult.render(terrain=...)."""
@@ -1284,6 +1291,11 @@ class OctreeResult:
         streamed into the grid on the device. params: terrain_params' arguments."""
         return _cloud_terrain(self, shapes, params)
 
+    def map_tiles(self, zoom, min_zoom=None, shapes=None, **params):
+        """A finished MapTiles layer of the points `shapes` select (None: all points) of this ECEF octree at
+        `zoom`, with the parent levels down to `min_zoom` (None: none); params: map_tiles_params' arguments."""
+        return _cloud_map_tiles(self, shapes, zoom, min_zoom, params)
+
     def xray_tiles(self, tile_size_px=256, pixel_size_m=None, strategy="xray", query_from_global=None, intensity_interval=None,
                    background="white", root_node_id="r", max_workspace_bytes=None, min_intensity=0.0, max_intensity=1.0,
                    binning=None):
@@ -1597,6 +1609,19 @@ class QueryBatch:
             return t.finish()
         except Exception:
             t.free()
+            raise
+
+    def map_tiles(self, zoom, min_zoom=None, shape=None, **params):
+        """A finished MapTiles layer of this result's points (of shape `shape`, or of all of them) at `zoom`, with the
+        parent levels down to `min_zoom` (None: none); params: map_tiles_params' arguments."""
+        self._live()
+        m = self.ctx.map_tiles_begin(zoom, **params)
+        try:
+            m.add_query_batch(self, shape=shape)
+            m.finish()
+            return m if min_zoom is None else m.build_parents(min_zoom)
+        except Exception:
+            m.free()
             raise
 
     def free(self):
@@ -2728,6 +2753,11 @@ class S2Cloud:
         self._alive()
         return _cloud_terrain(self, shapes, params)
 
+    def map_tiles(self, zoom, min_zoom=None, shapes=None, **params):
+        """A finished MapTiles layer of the points `shapes` select (None: all points), as OctreeResult.map_tiles."""
+        self._alive()
+        return _cloud_map_tiles(self, shapes, zoom, min_zoom, params)
+
     def query_batch(self, shapes=None, unions=None, intervals=None, filters=None):
         """The points of every location of one call (pcv_s2_query_run): the prepared `shapes`, then `unions`; intervals: None,
         or one entry per location, None or (lo, hi) on intensity. filters (pcv_s2_query_run_ex): None, or one entry per
@@ -3410,6 +3440,284 @@ def build_terrain(ctx, point_cloud_locations, output_directory, **params):
     except Exception:
         if t is not None:
             t.free()
+        raise
+    finally:
+        for c in clouds:
+            c.free()
+
+
+# ---- map tiles (pcv_maptiles_*) ----
+def map_tiles_params(zoom, background=(0, 0, 0, 0), max_tiles=1 << 20, max_pool_bytes=0, staging_points=0):
+    """pcv_maptiles_params. background: (r, g, b, a) or the packed RGBA8 integer, transparent black by default."""
+    pr = L.MapTilesParams()
+    pr.zoom = int(zoom)
+    if isinstance(background, (int, np.integer)):
+        pr.background = int(background)
+    else:
+        r, g, b, a = (int(v) & 255 for v in background)
+        pr.background = r | g << 8 | b << 16 | a << 24
+    pr.max_tiles, pr.max_pool_bytes, pr.staging_points = int(max_tiles), int(max_pool_bytes), int(staging_points)
+    return pr
+
+
+def map_tiles_check_params(zoom, min_zoom=None, **params):
+    """pcv_maptiles_check_params_host: raises PcvError with the rule that is broken."""
+    pr = map_tiles_params(zoom, **params)
+    _host_check(L.load_library().pcv_maptiles_check_params_host(C.byref(pr), int(zoom if min_zoom is None else min_zoom)),
+                "pcv_maptiles_check_params_host")
+
+
+def map_tile_pixels(zoom, x, y, z):
+    """The pixel rule on the host (pcv_maptiles_pixels_host), the kernels' twin: (gx, gy as uint32 global pixels at `zoom`,
+    ok as bool: False where the point is dropped). The tile is (gx >> 8, gy >> 8), the pixel in it (gx & 255, gy & 255)."""
+    x, y, z = (np.ascontiguousarray(v, dtype=np.float64).ravel() for v in (x, y, z))
+    n = x.size
+    if y.size != n or z.size != n:
+        raise ValueError("x, y, z of n points")
+    gx, gy, ok = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint8)
+    _host_check(L.load_library().pcv_maptiles_pixels_host(int(zoom), n, x.ctypes.data, y.ctypes.data, z.ctypes.data, gx.ctypes.data,
+                                                          gy.ctypes.data, ok.ctypes.data), "pcv_maptiles_pixels_host")
+    return gx, gy, ok.astype(bool)
+
+
+def map_tile_quad_index(zoom, x, y):
+    """The xray quadtree index of slippy tile (x, y) at `zoom` (pcv_maptiles_quad_index_host)."""
+    out = C.c_uint64()
+    _host_check(L.load_library().pcv_maptiles_quad_index_host(int(zoom), int(x), int(y), C.byref(out)), "pcv_maptiles_quad_index_host")
+    return out.value
+
+
+def map_tile_from_quad_index(zoom, index):
+    """The slippy tile (x, y) of an xray quadtree index at `zoom` (pcv_maptiles_quad_tile_host)."""
+    x, y = C.c_uint32(), C.c_uint32()
+    _host_check(L.load_library().pcv_maptiles_quad_tile_host(int(zoom), int(index), C.byref(x), C.byref(y)), "pcv_maptiles_quad_tile_host")
+    return x.value, y.value
+
+
+def map_tiles_json(tiles):
+    """The text of tiles.json (pcv_maptiles_json_host) for {zoom: [[x, y], ...]} over a contiguous range of zooms."""
+    zooms = sorted(int(z) for z in tiles)
+    if not zooms or zooms != list(range(zooms[0], zooms[-1] + 1)):
+        raise ValueError("tiles: a dict over a contiguous, non-empty range of zooms")
+    lists = [np.asarray(tiles[z], dtype=np.uint32).reshape(-1, 2) for z in zooms]
+    counts = np.array([len(t) for t in lists], dtype=np.uint64)
+    xy = np.ascontiguousarray(np.concatenate(lists, axis=0))
+    lib, n = L.load_library(), C.c_uint64()
+    _host_check(lib.pcv_maptiles_json_host(zooms[0], zooms[-1], counts.ctypes.data, xy.ctypes.data, None, 0, C.byref(n)), "pcv_maptiles_json_host")
+    buf = C.create_string_buffer(n.value + 1)
+    _host_check(lib.pcv_maptiles_json_host(zooms[0], zooms[-1], counts.ctypes.data, xy.ctypes.data, buf, n.value, C.byref(n)), "pcv_maptiles_json_host")
+    return buf.raw[:n.value].decode()
+
+
+def read_map_tiles(directory):
+    """A map-tile directory in pure Python plus the library's PNG reader: dict(scheme, format, tile_size, minzoom, maxzoom,
+    bounds [west, south, east, north] in degrees, tiles {zoom: uint32 [n, 2]}, images {zoom: uint8 [n, 256, 256, 4]})."""
+    import json
+    directory = str(directory)
+    with open(os.path.join(directory, "tiles.json")) as f:
+        meta = json.load(f)
+    T = int(meta["tile_size"])
+    tiles, images = {}, {}
+    for key, lst in meta["tiles"].items():
+        z = int(key)
+        tiles[z] = np.asarray(lst, dtype=np.uint32).reshape(-1, 2)
+        images[z] = np.zeros((len(lst), T, T, 4), dtype=np.uint8)
+        for k, (x, y) in enumerate(lst):
+            with open(os.path.join(directory, str(z), str(x), f"{y}.png"), "rb") as f:
+                images[z][k] = png_decode(f.read())
+    return dict(scheme=meta["scheme"], format=meta["format"], tile_size=T, minzoom=int(meta["minzoom"]), maxzoom=int(meta["maxzoom"]),
+                bounds=[float(v) for v in meta["bounds"]], tiles=tiles, images=images)
+
+
+class MapTiles:
+    """One pcv_maptiles: ECEF points in (add_points / add_query_batch), finish, optionally build_parents, then the tiles of
+    every built zoom — ascending by (x, y) — as arrays, as PNG files in memory or as a z/x/y directory."""
+
+    def __init__(self, ctx, handle, params):
+        self.ctx, self.lib, self.handle, self.params = ctx, ctx.lib, handle, params
+        self.zoom, self.tile_size = int(params.zoom), 256
+        ctx._children.add(self)
+
+    def _live(self):
+        if not self.handle or not self.ctx.handle:
+            raise L.PcvError(L.PCV_E_INVALID, "the map-tile layer was freed")
+
+    def add_points(self, x, y, z, rgb):
+        """f64 ECEF planes and 3-byte colours, numpy arrays or torch device tensors (pcv_maptiles_add_points)."""
+        self._live()
+        bufs = [_Buf(x, np.float64, "x"), _Buf(y, np.float64, "y"), _Buf(z, np.float64, "z"), _Buf(rgb, np.uint8, "rgb")]
+        n = bufs[0].size
+        if bufs[1].size != n or bufs[2].size != n or bufs[3].size != 3 * n:
+            raise ValueError("x, y, z of n points and rgb of 3 n bytes")
+        if len({b.device for b in bufs}) != 1:
+            raise ValueError("all point arrays must live in the same memory space")
+        if bufs[0].device:
+            self.ctx.wait_torch()
+        self.ctx._check(self.lib.pcv_maptiles_add_points(self.handle, n, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr,
+                                                         L.MEM_DEVICE if bufs[0].device else L.MEM_HOST))
+        return self
+
+    def add_query_batch(self, batch, shape=None, first_segment=0, num_segments=None):
+        """The points of a QueryBatch or S2QueryBatch: of shape `shape`, or of a segment range (default: all), pulled through
+        a bounded staging buffer on the device (pcv_maptiles_add_query_batch / pcv_maptiles_add_s2_query)."""
+        self._live()
+        batch._live()
+        first, num = batch._ply_range(shape, first_segment, num_segments)
+        fn = self.lib.pcv_maptiles_add_s2_query if isinstance(batch, S2QueryBatch) else self.lib.pcv_maptiles_add_query_batch
+        self.ctx._check(fn(self.handle, batch.handle, first, num))
+        return self
+
+    def finish(self):
+        self._live()
+        self.ctx._check(self.lib.pcv_maptiles_finish(self.handle))
+        return self
+
+    def build_parents(self, min_zoom):
+        """The levels zoom - 1 down to min_zoom (pcv_maptiles_build_parents)."""
+        self._live()
+        self.ctx._check(self.lib.pcv_maptiles_build_parents(self.handle, int(min_zoom)))
+        return self
+
+    def info(self):
+        self._live()
+        inf = L.MapTilesInfo()
+        self.ctx._check(self.lib.pcv_maptiles_info_get(self.handle, C.byref(inf)))
+        lo = inf.min_zoom if inf.finished else inf.zoom
+        return dict(points_added=inf.points_added, dropped=inf.dropped, drawn=inf.drawn, pool_bytes=inf.pool_bytes, zoom=inf.zoom,
+                    min_zoom=inf.min_zoom, finished=bool(inf.finished), tiles={z: int(inf.tiles[z]) for z in range(lo, inf.zoom + 1)})
+
+    def _zoom(self, zoom):
+        return self.zoom if zoom is None else int(zoom)
+
+    def _count(self, zoom):
+        n = C.c_uint64()
+        self.ctx._check(self.lib.pcv_maptiles_tiles(self.handle, zoom, 0, None, C.byref(n)))
+        return n.value
+
+    def tiles(self, zoom=None):
+        """Tile positions (x, y) of `zoom` (default: the maximum), uint32 [n, 2], ascending by (x, y)."""
+        self._live()
+        zoom = self._zoom(zoom)
+        n = self._count(zoom)
+        out = np.zeros((n, 2), dtype=np.uint32)
+        self.ctx._check(self.lib.pcv_maptiles_tiles(self.handle, zoom, n, out.ctypes.data, None))
+        return out
+
+    def _range(self, zoom, first, count):
+        n = self._count(zoom)
+        first = int(first)
+        num = max(n - first, 0) if count is None else int(count)
+        if not (0 <= first <= n and 0 <= num <= n - first):
+            raise L.PcvError(L.PCV_E_INVALID, f"tile range past the end: tiles [{first}, {first + num}) of {n}")
+        return first, num
+
+    def _plane(self, call, first, num, tail, dtype, device):
+        if device:
+            import torch
+            out = torch.empty((num, 256, 256) + tail, dtype=getattr(torch, np.dtype(dtype).name), device=f"cuda:{self.ctx.device}")
+            self.ctx.wait_torch()
+            ptr, mem = out.data_ptr(), L.MEM_DEVICE
+        else:
+            out = np.zeros((num, 256, 256) + tail, dtype=dtype)
+            ptr, mem = out.ctypes.data, L.MEM_HOST
+        if num:
+            self.ctx._check(call(first, num, mem, ptr))
+        return out
+
+    def images(self, zoom=None, first=0, count=None, device=False):
+        """uint8 [n, 256, 256, 4]: the RGBA images of tiles [first, first + count) of `zoom`; row 0 is north."""
+        self._live()
+        zoom = self._zoom(zoom)
+        first, num = self._range(zoom, first, count)
+        return self._plane(lambda f, c, mem, ptr: self.lib.pcv_maptiles_images(self.handle, zoom, f, c, mem, ptr), first, num, (4,), np.uint8, device)
+
+    def counts(self, first=0, count=None, device=False):
+        """[n, 256, 256] points per pixel of the tiles of the maximum zoom (uint32; int32 bits on the device)."""
+        self._live()
+        first, num = self._range(self.zoom, first, count)
+        return self._plane(lambda f, c, mem, ptr: self.lib.pcv_maptiles_counts(self.handle, f, c, mem, ptr), first, num, (),
+                           np.int32 if device else np.uint32, device)
+
+    def tile_pngs(self, zoom=None, first=0, count=None, png="stored"):
+        """The complete PNG files of tiles [first, first + count) of `zoom` as a list of bytes (pcv_maptiles_tile_pngs)."""
+        self._live()
+        zoom, mode = self._zoom(zoom), _png_mode(png)
+        first, num = self._range(zoom, first, count)
+        offsets = np.zeros(num + 1, dtype=np.uint64)
+        cap = num * int(self.lib.pcv_xray_png_bound(256, 256, mode))
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        self.ctx._check(self.lib.pcv_maptiles_tile_pngs(self.handle, zoom, first, num, mode, cap, out.ctypes.data, offsets.ctypes.data))
+        return _split_files(out, offsets)
+
+    def write(self, directory, png="stored"):
+        """<directory>/<z>/<x>/<y>.png of every built zoom and <directory>/tiles.json (pcv_maptiles_write_dir)."""
+        self._live()
+        self.ctx._check(self.lib.pcv_maptiles_write_dir(self.handle, os.fsencode(str(directory)), _png_mode(png)))
+
+    def free(self):
+        if self.handle and self.ctx.handle:
+            self.lib.pcv_maptiles_free(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _cloud_map_tiles(cloud, shapes, zoom, min_zoom, params, into=None):
+    """The points `shapes` select from an octree or an S2 cloud (None: all) into `into`, or into a new finished MapTiles."""
+    ctx = cloud.ctx
+    own = shapes is None
+    if own:
+        shapes = ctx.shapes([("all",)])
+    batch = m = None
+    try:
+        batch = cloud.query_batch(shapes)
+        m = into if into is not None else ctx.map_tiles_begin(zoom, **params)
+        m.add_query_batch(batch)
+        if into is not None:
+            return m
+        m.finish()
+        return m if min_zoom is None else m.build_parents(min_zoom)
+    except Exception:
+        if m is not None and into is None:
+            m.free()
+        raise
+    finally:
+        if batch is not None:
+            batch.free()
+        if own:
+            shapes.free()
+
+
+def build_map_tiles(cloud_dir, out_dir, zoom, min_zoom=None, png="stored", ctx=None, **params):
+    """A z/x/y map-tile directory from an ECEF cloud directory, or from a list of them: the kind of the first one (cloud_kind)
+    decides, every directory is opened as that kind, all their points go into one layer at `zoom`, the parents are built down
+    to `min_zoom` (None: none) and the pyramid is written to out_dir. ctx: None = the default context; params:
+    map_tiles_params' arguments. Returns the finished MapTiles."""
+    ctx = ctx if ctx is not None else default_context()
+    locations = [cloud_dir] if isinstance(cloud_dir, (str, os.PathLike)) else list(cloud_dir)
+    if not locations:
+        raise ValueError("No locations specified for point cloud client.")
+    map_tiles_check_params(zoom, min_zoom, **params)
+    _png_mode(png)  # an unknown mode is refused before any work
+    opener = ctx.s2_open if cloud_kind(locations[0]) == "s2" else ctx.open_dir
+    clouds = [opener(d) for d in locations]
+    m = None
+    try:
+        m = ctx.map_tiles_begin(zoom, **params)
+        for c in clouds:
+            _cloud_map_tiles(c, None, zoom, None, params, into=m)
+        m.finish()
+        if min_zoom is not None:
+            m.build_parents(min_zoom)
+        m.write(out_dir, png=png)
+        return m
+    except Exception:
+        if m is not None:
+            m.free()
         raise
     finally:
         for c in clouds:

@@ -77,6 +77,8 @@ type pcv_query_batch = c_void;
 #[allow(non_camel_case_types)]
 type pcv_terrain = c_void;
 #[allow(non_camel_case_types)]
+type pcv_maptiles = c_void;
+#[allow(non_camel_case_types)]
 type pcv_render = c_void;
 
 /// include/pcv_hip.h pcv_render_params: one frame of the viewer (sdl_viewer/src/lib.rs:158-209).
@@ -181,6 +183,13 @@ extern "C" {
     fn pcv_terrain_finish(t: *mut pcv_terrain) -> c_int;
     fn pcv_terrain_write_dir(t: *mut pcv_terrain, directory: *const c_char) -> c_int;
     fn pcv_terrain_free(t: *mut pcv_terrain);
+    // map tiles: a query's result drawn into z/x/y PNG tiles on the device
+    fn pcv_maptiles_begin(ctx: *mut pcv_ctx, params: *const PcvMapTilesParams, out: *mut *mut pcv_maptiles) -> c_int;
+    fn pcv_maptiles_add_query_batch(m: *mut pcv_maptiles, b: *mut pcv_query_batch, first_segment: u64, num_segments: u64) -> c_int;
+    fn pcv_maptiles_finish(m: *mut pcv_maptiles) -> c_int;
+    fn pcv_maptiles_build_parents(m: *mut pcv_maptiles, min_zoom: u32) -> c_int;
+    fn pcv_maptiles_write_dir(m: *mut pcv_maptiles, directory: *const c_char, png_mode: c_int) -> c_int;
+    fn pcv_maptiles_free(m: *mut pcv_maptiles);
     // the viewer's frame: get_visible_nodes + GL_POINTS under a depth test, rasterised on the device
     fn pcv_s2_open_dir(ctx: *mut pcv_ctx, directory: *const c_char, out: *mut *mut pcv_s2_cloud) -> c_int;
     fn pcv_s2_info(c: *const pcv_s2_cloud, num_cells: *mut u64, num_points: *mut u64, bbox_min: *mut c_double, bbox_max: *mut c_double, has_intensity: *mut c_int, level: *mut u32) -> c_int;
@@ -209,6 +218,16 @@ pub struct PcvPlyWriteParams {
     pub num_attributes: u32,
     pub reserved: u32,
     pub chunk_points: u64,
+}
+
+/// pcv_maptiles_params (include/pcv_hip.h); background: packed RGBA8, r in the low byte
+#[repr(C)]
+pub struct PcvMapTilesParams {
+    pub zoom: u32,
+    pub background: u32,
+    pub max_tiles: u64,
+    pub max_pool_bytes: u64,
+    pub staging_points: u64,
 }
 
 /// pcv_terrain_params (include/pcv_hip.h); statistic: 0 max, 1 min, 2 mean
@@ -784,6 +803,45 @@ impl HipOctree {
 }
 
 impl HipOctree {
+    /// The z/x/y map-tile pyramid (`<dir>/<z>/<x>/<y>.png`, `tiles.json`) of the points `queries` select from this ECEF octree,
+    /// drawn at `params.zoom` with the parent levels down to `min_zoom`; png_mode: 0 stored, 1 deflate. Every query must be
+    /// one the library serves (as in query_many).
+    pub fn map_tiles(&self, queries: &[PointQuery], params: &PcvMapTilesParams, min_zoom: u32, png_mode: i32, output_directory: impl AsRef<Path>) -> Result<()> {
+        let served: Vec<Option<(PcvShape, Option<[f64; 2]>, Vec<u64>)>> = queries.iter().map(library_query).collect();
+        if queries.is_empty() || served.iter().any(|s| s.is_none()) {
+            return Err(ErrorKind::InvalidInput("map_tiles: every query must be one the library serves".to_string()).into());
+        }
+        let shapes: Vec<PcvShape> = served.iter().flatten().map(|(s, _, _)| *s).collect();
+        let intervals: Vec<Option<[f64; 2]>> = served.iter().flatten().map(|(_, iv, _)| *iv).collect();
+        let cells: Vec<Vec<u64>> = served.iter().flatten().map(|(_, _, c)| c.clone()).collect();
+        let dir = CString::new(output_directory.as_ref().to_str().unwrap()).unwrap();
+        let _g = self.lock.lock().unwrap();
+        let (handle, _, _, offset) = self.run_batch(&shapes, &cells, &intervals);
+        let mut m: *mut pcv_maptiles = std::ptr::null_mut();
+        let mut rc = unsafe { pcv_maptiles_begin(self.ctx.0, params, &mut m) };
+        if rc == 0 {
+            rc = unsafe { pcv_maptiles_add_query_batch(m, handle, 0, offset.len() as u64 - 1) };
+        }
+        if rc == 0 {
+            rc = unsafe { pcv_maptiles_finish(m) };
+        }
+        if rc == 0 {
+            rc = unsafe { pcv_maptiles_build_parents(m, min_zoom) };
+        }
+        if rc == 0 {
+            rc = unsafe { pcv_maptiles_write_dir(m, dir.as_ptr(), png_mode) };
+        }
+        let msg = if rc != 0 { unsafe { CStr::from_ptr(pcv_last_error(self.ctx.0)) }.to_string_lossy().into_owned() } else { String::new() };
+        unsafe {
+            pcv_maptiles_free(m);
+            pcv_query_batch_free(handle);
+        }
+        if rc != 0 {
+            return Err(ErrorKind::InvalidInput(format!("map_tiles failed ({}): {}", rc, msg)).into());
+        }
+        Ok(())
+    }
+
     /// The terrain layer `sdl_viewer --terrain <dir>` reads, of the points `queries` select, over this octree's bounding box:
     /// the queries' segments go into the grid on the device, one after the other (a point that two queries select counts
     /// twice). Every query must be one the library serves (as in query_many).
