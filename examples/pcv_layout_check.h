@@ -95,6 +95,24 @@ PCV_SA(sizeof(pcv_maptiles_info) == 240 && offsetof(pcv_maptiles_info, points_ad
            offsetof(pcv_maptiles_info, drawn) == 16 && offsetof(pcv_maptiles_info, pool_bytes) == 24 && offsetof(pcv_maptiles_info, zoom) == 32 &&
            offsetof(pcv_maptiles_info, min_zoom) == 36 && offsetof(pcv_maptiles_info, finished) == 40 && offsetof(pcv_maptiles_info, tiles) == 48,
        "pcv_maptiles_info");
+PCV_SA(sizeof(pcv_las_header) == 72 && offsetof(pcv_las_header, point_format) == 2 && offsetof(pcv_las_header, header_size) == 4 &&
+           offsetof(pcv_las_header, record_length) == 6 && offsetof(pcv_las_header, offset_to_points) == 8 &&
+           offsetof(pcv_las_header, num_points) == 16 && offsetof(pcv_las_header, scale) == 24 && offsetof(pcv_las_header, offset) == 48,
+       "pcv_las_header");
+PCV_SA(sizeof(pcv_las_params) == 208 && offsetof(pcv_las_params, constant_color) == 4 && offsetof(pcv_las_params, drop_withheld) == 7 &&
+           offsetof(pcv_las_params, keep_intensity) == 8 && offsetof(pcv_las_params, piece_points) == 12 &&
+           offsetof(pcv_las_params, use_transform) == 16 && offsetof(pcv_las_params, num_extras) == 20 &&
+           offsetof(pcv_las_params, class_mask) == 24 && offsetof(pcv_las_params, global_from_local) == 56 &&
+           offsetof(pcv_las_params, extras) == 112,
+       "pcv_las_params");
+PCV_SA(sizeof(pcv_las_info) == 2256 && offsetof(pcv_las_info, num_kept) == 8 && offsetof(pcv_las_info, dropped_class) == 16 &&
+           offsetof(pcv_las_info, dropped_withheld) == 24 && offsetof(pcv_las_info, max_color) == 32 &&
+           offsetof(pcv_las_info, max_intensity) == 36 && offsetof(pcv_las_info, color_rule) == 40 && offsetof(pcv_las_info, num_pieces) == 44 &&
+           offsetof(pcv_las_info, class_hist) == 48 && offsetof(pcv_las_info, return_hist) == 2096 && offsetof(pcv_las_info, flag_counts) == 2224,
+       "pcv_las_info");
+PCV_SA(sizeof(pcv_las_columns) == 136 && offsetof(pcv_las_columns, color) == 24 && offsetof(pcv_las_columns, intensity) == 32 &&
+           offsetof(pcv_las_columns, extras) == 40,
+       "pcv_las_columns");
 PCV_SA(sizeof(pcv_render_terrain_layers) == 24 && offsetof(pcv_render_terrain_layers, num_layers) == 0 &&
            offsetof(pcv_render_terrain_layers, window) == 4 && offsetof(pcv_render_terrain_layers, layers) == 8 &&
            offsetof(pcv_render_terrain_layers, camera_positions) == 16,

@@ -1959,6 +1959,117 @@ int pcv_maptiles_quad_tile_host(uint32_t zoom, uint64_t index, uint32_t* x, uint
 int pcv_maptiles_json_host(uint32_t min_zoom, uint32_t max_zoom, const uint64_t* counts, const uint32_t* xy, char* buf, uint64_t cap,
                            uint64_t* len);
 
+/* ---- LAS point clouds as input ---------------------------------------------------------- */
+/* ASPRS LAS 1.0 - 1.4, point data record formats 0 - 10, little endian, read at the fixed offsets of the public header block;
+ * VLRs and EVLRs are skipped, a record longer than its format's minimum is read by stride. The records are decoded and filtered
+ * on the device; the host parses the header and moves bytes. Not read: LAZ, extra-bytes descriptors, waveform data, CRS VLRs. */
+typedef struct pcv_las_header {
+  uint8_t version_major, version_minor;
+  uint8_t point_format; /* 0 ..= 10 */
+  uint8_t reserved0;
+  uint16_t header_size;
+  uint16_t record_length;
+  uint32_t offset_to_points;
+  uint32_t reserved1;
+  uint64_t num_points; /* 1.4: the 64-bit field; earlier versions: the legacy field */
+  double scale[3];
+  double offset[3];
+} pcv_las_header;
+
+#define PCV_LAS_COLOR_AUTO 0      /* RGB16 / RGB8 by the largest channel value of the file; INTENSITY for a format without RGB */
+#define PCV_LAS_COLOR_RGB16 1     /* c >> 8 */
+#define PCV_LAS_COLOR_RGB8 2      /* min(c, 255) */
+#define PCV_LAS_COLOR_INTENSITY 3 /* r = g = b = Imax == 0 ? 0 : (uint32)I * 255 / Imax */
+#define PCV_LAS_COLOR_CONSTANT 4  /* constant_color */
+#define PCV_LAS_MAX_EXTRAS 12
+/* The device holds at most this many raw pieces of piece_points records next to the outputs (and, for the AUTO and INTENSITY
+ * rules, 6 or 2 bytes of parked 16-bit values per record until the file's maxima are known). */
+#define PCV_LAS_RAW_PIECES 2
+typedef struct pcv_las_params {
+  uint32_t color_mode; /* PCV_LAS_COLOR_* */
+  uint8_t constant_color[3];
+  uint8_t drop_withheld;    /* 1: records with the withheld flag are dropped */
+  uint32_t keep_intensity;  /* 1: the intensity column (float)I is kept */
+  uint32_t piece_points;    /* records per piece; 0 = as many as one 32 MiB staging chunk holds, which is also the most */
+  uint32_t use_transform;   /* 1: global_from_local is applied (the arithmetic of pcv_transform_points) */
+  uint32_t num_extras;
+  uint64_t class_mask[4];   /* bit c of the 256 keeps class c; all zero keeps every class */
+  double global_from_local[7]; /* translation xyz, unit quaternion i j k w */
+  const char* extras[PCV_LAS_MAX_EXTRAS]; /* names of the table below, each at most once */
+} pcv_las_params;
+/* Extras (name, PCV_ATTR_* type): classification U8, classification_flags U8 (bit 0 synthetic, 1 key-point, 2 withheld,
+ * 3 overlap), return_number U8, number_of_returns U8, scan_direction_flag U8, edge_of_flight_line U8, scanner_channel U8
+ * (formats 6-10), scan_angle F32 (degrees), user_data U8, point_source_id U16, gps_time F64 (formats 1, 3-10; the eight bytes as
+ * they are), nir U16 (formats 8, 10). A name the format lacks is PCV_E_INVALID naming it. */
+
+typedef struct pcv_las_info {
+  uint64_t num_records, num_kept;
+  uint64_t dropped_class;    /* records whose class the mask does not keep */
+  uint64_t dropped_withheld; /* records the mask keeps and drop_withheld drops */
+  uint32_t max_color;        /* largest R, G or B over ALL records (0 for a format without RGB) */
+  uint32_t max_intensity;    /* largest intensity over ALL records */
+  uint32_t color_rule;       /* the PCV_LAS_COLOR_* that was applied (never AUTO) */
+  uint32_t num_pieces;
+  uint64_t class_hist[256];  /* over all records */
+  uint64_t return_hist[16];  /* return number, over all records */
+  uint64_t flag_counts[4];   /* synthetic, key-point, withheld, overlap, over all records */
+} pcv_las_info;
+
+/* Output columns of the stage entries: capacity n each (3 n bytes of colour); intensity when keep_intensity; extras[k] the
+ * column of params->extras[k] in its type. The first num_kept elements are written. */
+typedef struct pcv_las_columns {
+  double* x;
+  double* y;
+  double* z;
+  uint8_t* color;
+  float* intensity;
+  void* extras[PCV_LAS_MAX_EXTRAS];
+} pcv_las_columns;
+
+/* Host only, no context (messages: pcv_host_last_error). */
+/* PCV_E_INVALID naming the field: a wrong signature, a major version other than 1 or a minor version above 4, a header size
+ * below the version's (227, 227, 227, 235, 375), an offset to point data below the header size, a format above 10, a record
+ * length below the format's minimum (20, 28, 26, 34, 57, 63, 30, 36, 38, 59, 67), one of the top two bits of the format byte set
+ * (a LAZ file), a non-finite scale or offset, a 1.4 file whose non-zero legacy count differs from the 64-bit count, 2^32 - 1 or
+ * more records. PCV_E_IO: the file cannot be read, ends inside the header, or is shorter than header plus records. */
+int pcv_las_header_host(const char* path, pcv_las_header* out);
+/* PCV_E_INVALID: an unknown colour mode, RGB16 / RGB8 on a format without colour, an extra the format lacks or that is named
+ * twice or unknown, more than PCV_LAS_MAX_EXTRAS, a non-finite transform. */
+int pcv_las_check_params_host(const pcv_las_header* header, const pcv_las_params* params);
+/* The extras a format has, in the table's order: names[k] are static strings, types[k] PCV_ATTR_*; each nullable. */
+int pcv_las_extras_host(uint32_t point_format, const char** names, int32_t* types, uint32_t* count);
+/* The decode on the host, the device's twin bit for bit: n raw records of header->record_length bytes -> columns and info. */
+int pcv_las_decode_host(const pcv_las_header* header, const pcv_las_params* params, const void* raw, uint64_t n, pcv_las_columns* out,
+                        pcv_las_info* info);
+/* The one-pass host reader, shaped like pcv_ply_read_ex: host columns owned by the handle. */
+typedef struct pcv_las pcv_las;
+int pcv_las_read(const char* path, const pcv_las_params* params, pcv_las** out);
+uint64_t pcv_las_num_points(const pcv_las* las);
+int pcv_las_points(const pcv_las* las, pcv_points* out);
+int pcv_las_attributes(const pcv_las* las, uint32_t* count, struct pcv_attribute* out /* nullable; PCV_LAS_MAX_EXTRAS entries */);
+int pcv_las_info_get(const pcv_las* las, pcv_las_info* out);
+void pcv_las_free(pcv_las* las);
+
+/* The device path. The file goes up in pieces of piece_points records, pread by the context's host threads into the pinned
+ * ring; piece k is decoded on the context's stream while piece k + 1 is copied on its side stream. PCV_E_IO (a truncated
+ * file) leaves the context usable. */
+typedef struct pcv_las_cloud pcv_las_cloud;
+int pcv_las_load(pcv_ctx* ctx, const char* path, const pcv_las_params* params, pcv_las_cloud** out);
+int pcv_las_cloud_info(const pcv_las_cloud* c, pcv_las_info* out);
+/* PCV_MEM_DEVICE planes owned by the cloud (intensity NULL unless kept): as pcv_build_octree (with PCV_BUILD_COMPUTE_BBOX),
+ * pcv_s2_split_ex, pcv_s2_stream_append_ex, pcv_terrain_add_points and pcv_maptiles_add_points take them. */
+int pcv_las_cloud_points(const pcv_las_cloud* c, pcv_points* out);
+int pcv_las_cloud_attributes(const pcv_las_cloud* c, uint32_t* count, struct pcv_attribute* out /* nullable; PCV_LAS_MAX_EXTRAS entries */);
+/* One column into host memory: "x", "y", "z", "color", "intensity" or an extra's name; capacity_bytes must hold it. */
+int pcv_las_cloud_read(const pcv_las_cloud* c, const char* name, void* out, uint64_t capacity_bytes);
+void pcv_las_cloud_free(pcv_las_cloud* c);
+/* The stage entry: n raw records where `mem` says -> columns where `mem` says; the outputs of pcv_las_decode_host. */
+int pcv_las_decode(pcv_ctx* ctx, const pcv_las_header* header, const pcv_las_params* params, const void* raw, uint64_t n, int mem,
+                   pcv_las_columns* out, pcv_las_info* info);
+/* pcv_las_load + pcv_build_octree with PCV_BUILD_COMPUTE_BBOX; the octree carries intensity when keep_intensity. */
+int pcv_build_octree_from_las(pcv_ctx* ctx, const pcv_build_params* params, const char* path, const pcv_las_params* las_params,
+                              pcv_octree** out);
+
 #ifdef __cplusplus
 }
 #endif

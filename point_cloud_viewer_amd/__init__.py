@@ -11,6 +11,7 @@ from .octree import (Aabb, Context, OctreeResult, QueryBatch, RenderedViews, S2C
                      s2_cell_geometry, s2_cell_rect, s2_cells_in_location, s2_corners_rect, s2_rect_intersects_cell, s2_union_intersects, s2_union_intersects_cubes,
                      s2_open_host, s2_union_normalize, S2Stream, s2_merge_plan, s2_filter_keep, s2_check_attributes,
                      level_shortcuts, level_table, node_name, quadtree_node_id, quadtree_node_name, read_ply,
+                     DeviceColumn, LasCloud, las_decode_host, las_extras, las_params, read_las, read_las_header,
                      ply_append_check, ply_header, ply_layout,
                      Terrain, build_terrain, read_terrain, terrain_check_params, terrain_frame, terrain_meta_json, terrain_params,
                      terrain_quad_masks, terrain_tile_name, terrain_vertex, terrain_meta_read,

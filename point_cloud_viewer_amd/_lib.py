@@ -234,6 +234,35 @@ class MapTilesInfo(C.Structure):  # pcv_maptiles_info
                 ("zoom", C.c_uint32), ("min_zoom", C.c_uint32), ("finished", C.c_uint32), ("reserved", C.c_uint32), ("tiles", C.c_uint64 * 24)]
 
 
+LAS_COLOR_AUTO, LAS_COLOR_RGB16, LAS_COLOR_RGB8, LAS_COLOR_INTENSITY, LAS_COLOR_CONSTANT = range(5)
+LAS_COLOR_NAMES = ["auto", "rgb16", "rgb8", "intensity", "constant"]
+LAS_MAX_EXTRAS = 12
+LAS_RAW_PIECES = 2  # PCV_LAS_RAW_PIECES: the raw pieces a load holds on the device
+
+
+class LasHeader(C.Structure):  # pcv_las_header
+    _fields_ = [("version_major", C.c_uint8), ("version_minor", C.c_uint8), ("point_format", C.c_uint8), ("reserved0", C.c_uint8),
+                ("header_size", C.c_uint16), ("record_length", C.c_uint16), ("offset_to_points", C.c_uint32), ("reserved1", C.c_uint32),
+                ("num_points", C.c_uint64), ("scale", C.c_double * 3), ("offset", C.c_double * 3)]
+
+
+class LasParams(C.Structure):  # pcv_las_params
+    _fields_ = [("color_mode", C.c_uint32), ("constant_color", C.c_uint8 * 3), ("drop_withheld", C.c_uint8), ("keep_intensity", C.c_uint32),
+                ("piece_points", C.c_uint32), ("use_transform", C.c_uint32), ("num_extras", C.c_uint32), ("class_mask", C.c_uint64 * 4),
+                ("global_from_local", C.c_double * 7), ("extras", C.c_char_p * LAS_MAX_EXTRAS)]
+
+
+class LasInfo(C.Structure):  # pcv_las_info
+    _fields_ = [("num_records", C.c_uint64), ("num_kept", C.c_uint64), ("dropped_class", C.c_uint64), ("dropped_withheld", C.c_uint64),
+                ("max_color", C.c_uint32), ("max_intensity", C.c_uint32), ("color_rule", C.c_uint32), ("num_pieces", C.c_uint32),
+                ("class_hist", C.c_uint64 * 256), ("return_hist", C.c_uint64 * 16), ("flag_counts", C.c_uint64 * 4)]
+
+
+class LasColumns(C.Structure):  # pcv_las_columns
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("z", C.c_void_p), ("color", C.c_void_p), ("intensity", C.c_void_p),
+                ("extras", C.c_void_p * LAS_MAX_EXTRAS)]
+
+
 class OocStats(C.Structure):
     _fields_ = [("points", C.c_uint64), ("nodes", C.c_uint64), ("partitions", C.c_uint64), ("largest_bucket", C.c_uint64),
                 ("spill_bytes", C.c_uint64), ("h2d_bytes", C.c_uint64), ("d2h_bytes", C.c_uint64), ("h2d_ms", C.c_double),
@@ -525,6 +554,25 @@ _SIGNATURES = {
     "pcv_maptiles_quad_index_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "pcv_maptiles_quad_tile_host": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "pcv_maptiles_json_host": (C.c_int, [C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "pcv_las_header_host": (C.c_int, [C.c_char_p, C.POINTER(LasHeader)]),
+    "pcv_las_check_params_host": (C.c_int, [C.POINTER(LasHeader), C.POINTER(LasParams)]),
+    "pcv_las_extras_host": (C.c_int, [C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]),
+    "pcv_las_decode_host": (C.c_int, [C.POINTER(LasHeader), C.POINTER(LasParams), _vp, C.c_uint64, C.POINTER(LasColumns), C.POINTER(LasInfo)]),
+    "pcv_las_read": (C.c_int, [C.c_char_p, C.POINTER(LasParams), C.POINTER(_vp)]),
+    "pcv_las_num_points": (C.c_uint64, [_vp]),
+    "pcv_las_points": (C.c_int, [_vp, C.POINTER(Points)]),
+    "pcv_las_attributes": (C.c_int, [_vp, C.POINTER(C.c_uint32), _vp]),
+    "pcv_las_info_get": (C.c_int, [_vp, C.POINTER(LasInfo)]),
+    "pcv_las_free": (None, [_vp]),
+    "pcv_las_load": (C.c_int, [_vp, C.c_char_p, C.POINTER(LasParams), C.POINTER(_vp)]),
+    "pcv_las_cloud_info": (C.c_int, [_vp, C.POINTER(LasInfo)]),
+    "pcv_las_cloud_points": (C.c_int, [_vp, C.POINTER(Points)]),
+    "pcv_las_cloud_attributes": (C.c_int, [_vp, C.POINTER(C.c_uint32), _vp]),
+    "pcv_las_cloud_read": (C.c_int, [_vp, C.c_char_p, _vp, C.c_uint64]),
+    "pcv_las_cloud_free": (None, [_vp]),
+    "pcv_las_decode": (C.c_int, [_vp, C.POINTER(LasHeader), C.POINTER(LasParams), _vp, C.c_uint64, C.c_int, C.POINTER(LasColumns),
+                                 C.POINTER(LasInfo)]),
+    "pcv_build_octree_from_las": (C.c_int, [_vp, C.POINTER(BuildParams), C.c_char_p, C.POINTER(LasParams), C.POINTER(_vp)]),
 }
 
 _lib = None

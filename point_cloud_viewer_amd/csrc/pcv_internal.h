@@ -136,6 +136,10 @@ enum PcvKernelId {
   PCV_K_MAPTILES_UNPACK,      // pcv_maptiles.hip: packed x y z r g b rows of a query result's piece into the staging planes
   PCV_K_MAPTILES_RESOLVE,     // pcv_maptiles.hip: accumulators -> RGBA8 images and count planes, the 2^24 check
   PCV_K_MAPTILES_PARENT,      // pcv_maptiles_build_parents: xray_parent_kernel over the zooms below the maximum
+  PCV_K_LAS_COUNT,            // pcv_las.hip: kept records per tile of a piece, from the class and flag bytes (only with a filter)
+  PCV_K_LAS_SCAN,             // pcv_las.hip: tile offsets of a piece on top of the running base
+  PCV_K_LAS_DECODE,           // pcv_las.hip: a tile of records staged in LDS, picked, counted, compacted and stored as planes
+  PCV_K_LAS_COLOR,            // pcv_las.hip: the parked 16-bit colours or intensities narrowed once the file's maxima are known
   PCV_K_COUNT
 };
 

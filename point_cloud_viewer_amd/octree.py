@@ -35,6 +35,21 @@ class Aabb:
         self.max = np.maximum(a, b)
 
 
+class DeviceColumn:
+    """A column on the device that another object owns (a LasCloud): pointer, elements and dtype. It goes wherever a torch
+    device tensor goes (build, s2_split, Terrain.add_points, ...) for as long as its owner lives; numpy() downloads it."""
+
+    def __init__(self, owner, name, ptr, size, dtype):
+        self.owner, self.name, self.ptr, self.size, self.dtype = owner, name, ptr, int(size), np.dtype(dtype)
+
+    @property
+    def shape(self):
+        return (self.size // 3, 3) if self.name == "color" else (self.size,)
+
+    def numpy(self):
+        return self.owner.read(self.name)
+
+
 class _Buf:
     """Pointer + keep-alive for one input array."""
 
@@ -42,6 +57,12 @@ class _Buf:
         self.keep = arr
         if arr is None:
             self.ptr, self.device, self.size = None, None, 0
+            return
+        if isinstance(arr, DeviceColumn):
+            if arr.dtype != np.dtype(dtype):
+                raise TypeError(f"{what}: expected {np.dtype(dtype)}, got {arr.dtype}")
+            arr.owner._alive()
+            self.ptr, self.device, self.size = arr.ptr, True, arr.size
             return
         if _is_torch(arr):
             import torch
@@ -98,6 +119,14 @@ def _attributes(attrs, n, device):
         typ = None
         if isinstance(col, tuple):
             col, typ = col
+        if isinstance(col, DeviceColumn):
+            col.owner._alive()
+            if not device and n > 0:
+                raise ValueError("all point arrays must live in the same memory space")
+            name_b = os.fsencode(name) if isinstance(name, str) else bytes(name)
+            keep.extend((col, name_b))
+            out[k].name, out[k].data_type, out[k].reserved, out[k].data = name_b, L.ATTR_TYPES[_attr_type_of(np.zeros(0, col.dtype))][0], 0, col.ptr
+            continue
         if not _is_torch(col):
             col = np.asarray(col)
         typ = _attr_type_of(col) if typ is None else str(typ).lower()
@@ -391,6 +420,75 @@ class Context:
         self._check(self.lib.pcv_build_octree_from_ply(self.handle, C.byref(pr), str(filename).encode(), 1 if with_intensity else 0,
                                                        C.byref(h)))
         return OctreeResult(self, h)
+
+    def build_from_las(self, resolution, filename, max_points_per_node=0, **las):
+        """pcv_build_octree_from_las: las_load and the build with the bounding box computed on the device; **las are
+        las_params' keywords (keep_intensity=True gives the octree its intensity)."""
+        hdr = read_las_header(filename)
+        pr = self._params(resolution, None, None, max_points_per_node, L.BUILD_COMPUTE_BBOX)
+        lp, keep = las_params(hdr, **las)
+        h = C.c_void_p()
+        self._check(self.lib.pcv_build_octree_from_las(self.handle, C.byref(pr), os.fsencode(str(filename)), C.byref(lp), C.byref(h)))
+        del keep
+        return OctreeResult(self, h)
+
+    def las_load(self, path, **las):
+        """A LAS file decoded and filtered on the device (pcv_las_load) -> LasCloud. **las: las_params' keywords."""
+        hdr = read_las_header(path)
+        lp, keep = las_params(hdr, **las)
+        h = C.c_void_p()
+        self._check(self.lib.pcv_las_load(self.handle, os.fsencode(str(path)), C.byref(lp), C.byref(h)))
+        del keep
+        return LasCloud(self, h)
+
+    def las_decode(self, header, raw, n=None, **las):
+        """The stage entry (pcv_las_decode): n raw records (numpy uint8, or a torch device tensor of bytes) under `header` (a
+        LasHeader or read_las_header's dict) -> read_las's dict, as numpy arrays; the kernels run in either case."""
+        hdr = _las_header(header)
+        lp, keep = las_params(hdr, **las)
+        device = _is_torch(raw)
+        b = _Buf(raw, np.uint8, "raw")
+        if device and not b.device:
+            raise ValueError("raw: a torch tensor must live on the device")
+        n = b.size // max(1, hdr.record_length) if n is None else int(n)
+        if n * hdr.record_length > b.size:
+            raise ValueError(f"raw holds {b.size} bytes, {n} records of {hdr.record_length} take more")
+        if device:
+            self.wait_torch()
+        ids = [e.decode() for e in lp.extras[:lp.num_extras]]
+        cols, out, bufs = L.LasColumns(), {}, {}
+
+        def column(name, count, dtype):
+            if device:
+                import torch
+                t = torch.empty(max(1, count * np.dtype(dtype).itemsize), dtype=torch.uint8, device=raw.device)
+                bufs[name] = (t, count, dtype)
+                return t.data_ptr()
+            bufs[name] = np.zeros(max(1, count), dtype=dtype)
+            return bufs[name].ctypes.data
+
+        cols.x, cols.y, cols.z = column("x", n, np.float64), column("y", n, np.float64), column("z", n, np.float64)
+        cols.color = column("color", 3 * n, np.uint8)
+        if lp.keep_intensity:
+            cols.intensity = column("intensity", n, np.float32)
+        for k, name in enumerate(ids):
+            cols.extras[k] = column("@" + name, n, _LAS_EXTRA_DTYPES[name])
+        info = L.LasInfo()
+        self._check(self.lib.pcv_las_decode(self.handle, C.byref(hdr), C.byref(lp), b.ptr, n, L.MEM_DEVICE if device else L.MEM_HOST,
+                                            C.byref(cols), C.byref(info)))
+        del keep
+        m = int(info.num_kept)
+
+        def fetch(name, count):
+            if device:
+                t, _, dtype = bufs[name]
+                return t.cpu().numpy().view(dtype)[:count].copy()
+            return bufs[name][:count]
+
+        out = dict(x=fetch("x", m), y=fetch("y", m), z=fetch("z", m), color=fetch("color", 3 * m).reshape(-1, 3),
+                   intensity=fetch("intensity", m) if lp.keep_intensity else None,
+                   attributes={name: fetch("@" + name, m) for name in ids}, info=_las_info(info))
+        return out
 
     # ---- loading + queries -----------------------------------------------------------------------
     def open_dir(self, directory):
@@ -2521,6 +2619,207 @@ def ply_append_check(path, attributes):
     return old.value
 
 
+_LAS_EXTRA_DTYPES = {"classification": "u1", "classification_flags": "u1", "return_number": "u1", "number_of_returns": "u1",
+                     "scan_direction_flag": "u1", "edge_of_flight_line": "u1", "scanner_channel": "u1", "scan_angle": "<f4",
+                     "user_data": "u1", "point_source_id": "<u2", "gps_time": "<f8", "nir": "<u2"}
+
+
+def _las_check(rc):
+    if rc != L.PCV_OK:
+        raise L.PcvError(rc, L.load_library().pcv_host_last_error().decode())
+
+
+def _las_header(header):
+    if isinstance(header, L.LasHeader):
+        return header
+    h = L.LasHeader()
+    h.version_major, h.version_minor = header["version"]
+    h.point_format, h.header_size, h.record_length = header["point_format"], header["header_size"], header["record_length"]
+    h.offset_to_points, h.num_points = header["offset_to_points"], header["num_points"]
+    for a in range(3):
+        h.scale[a], h.offset[a] = header["scale"][a], header["offset"][a]
+    return h
+
+
+def _las_info(info):
+    return dict(num_records=int(info.num_records), num_kept=int(info.num_kept), dropped_class=int(info.dropped_class),
+                dropped_withheld=int(info.dropped_withheld), max_color=int(info.max_color), max_intensity=int(info.max_intensity),
+                color_rule=L.LAS_COLOR_NAMES[info.color_rule], num_pieces=int(info.num_pieces),
+                class_hist=np.array(info.class_hist, dtype=np.uint64), return_hist=np.array(info.return_hist, dtype=np.uint64),
+                flag_counts=dict(zip(("synthetic", "key_point", "withheld", "overlap"), (int(v) for v in info.flag_counts))))
+
+
+def read_las_header(path, as_dict=False):
+    """The public header block of a LAS 1.0 - 1.4 file (pcv_las_header_host) -> LasHeader, or a dict of its fields."""
+    h = L.LasHeader()
+    _las_check(L.load_library().pcv_las_header_host(os.fsencode(str(path)), C.byref(h)))
+    if not as_dict:
+        return h
+    return dict(version=(h.version_major, h.version_minor), point_format=h.point_format, header_size=h.header_size,
+                record_length=h.record_length, offset_to_points=h.offset_to_points, num_points=int(h.num_points),
+                scale=tuple(h.scale), offset=tuple(h.offset))
+
+
+def las_extras(point_format):
+    """The names of the extras a point data record format has, in the order of DESIGN §9j's table."""
+    names, count = (C.c_char_p * L.LAS_MAX_EXTRAS)(), C.c_uint32()
+    _las_check(L.load_library().pcv_las_extras_host(int(point_format), names, None, C.byref(count)))
+    return [names[k].decode() for k in range(count.value)]
+
+
+def las_params(header, color="auto", classes=None, drop_withheld=False, keep_intensity=False, extras=(), global_from_local=None,
+               piece_points=0, check=True):
+    """pcv_las_params for a file with `header` -> (LasParams, keep-alive). color: "auto" | "rgb16" | "rgb8" | "intensity" | an
+    (r, g, b); classes: the classes to keep (None: all); extras: names, or "all" for every extra the format has;
+    global_from_local: translation xyz + unit quaternion ijkw."""
+    hdr = _las_header(header)
+    p = L.LasParams()
+    if isinstance(color, str):
+        if color not in L.LAS_COLOR_NAMES[:4]:
+            raise ValueError('color is "auto", "rgb16", "rgb8", "intensity" or an (r, g, b)')
+        p.color_mode = L.LAS_COLOR_NAMES.index(color)
+    else:
+        p.color_mode = L.LAS_COLOR_CONSTANT
+        for k in range(3):
+            p.constant_color[k] = int(color[k])
+    for c in (classes if classes is not None else ()):
+        if not 0 <= int(c) <= 255:
+            raise ValueError("a class is 0 ..= 255")
+        p.class_mask[int(c) >> 6] |= 1 << (int(c) & 63)
+    if classes is not None and len(list(classes)) == 0:
+        raise ValueError("classes: an empty list keeps nothing; pass None to keep every class")
+    p.drop_withheld, p.keep_intensity, p.piece_points = int(bool(drop_withheld)), int(bool(keep_intensity)), int(piece_points)
+    if global_from_local is not None:
+        p.use_transform = 1
+        for k in range(7):
+            p.global_from_local[k] = float(global_from_local[k])
+    names = las_extras(hdr.point_format) if isinstance(extras, str) and extras == "all" else list(extras or ())
+    if len(names) > L.LAS_MAX_EXTRAS:
+        raise L.PcvError(L.PCV_E_INVALID, f"LAS: more than {L.LAS_MAX_EXTRAS} extras")
+    keep = [os.fsencode(n) for n in names]
+    for k, b in enumerate(keep):
+        p.extras[k] = b
+    p.num_extras = len(keep)
+    if check:
+        _las_check(L.load_library().pcv_las_check_params_host(C.byref(hdr), C.byref(p)))
+    return p, keep
+
+
+def las_decode_host(header, raw, n=None, **las):
+    """The host twin of the device decode (pcv_las_decode_host): raw records (bytes or a uint8 array) -> read_las's dict."""
+    hdr = _las_header(header)
+    lp, keep = las_params(hdr, **las)
+    raw = np.frombuffer(raw, dtype=np.uint8) if isinstance(raw, (bytes, bytearray, memoryview)) else np.ascontiguousarray(raw, dtype=np.uint8)
+    n = raw.size // max(1, hdr.record_length) if n is None else int(n)
+    if n * hdr.record_length > raw.size:
+        raise ValueError(f"raw holds {raw.size} bytes, {n} records of {hdr.record_length} take more")
+    ids = [e.decode() for e in lp.extras[:lp.num_extras]]
+    cols = L.LasColumns()
+    arrays = dict(x=np.zeros(max(1, n)), y=np.zeros(max(1, n)), z=np.zeros(max(1, n)), color=np.zeros(max(1, 3 * n), np.uint8),
+                  intensity=np.zeros(max(1, n), np.float32))
+    ex = {name: np.zeros(max(1, n), _LAS_EXTRA_DTYPES[name]) for name in ids}
+    cols.x, cols.y, cols.z = arrays["x"].ctypes.data, arrays["y"].ctypes.data, arrays["z"].ctypes.data
+    cols.color, cols.intensity = arrays["color"].ctypes.data, arrays["intensity"].ctypes.data
+    for k, name in enumerate(ids):
+        cols.extras[k] = ex[name].ctypes.data
+    info = L.LasInfo()
+    _las_check(L.load_library().pcv_las_decode_host(C.byref(hdr), C.byref(lp), raw.ctypes.data if raw.size else None, n, C.byref(cols),
+                                                     C.byref(info)))
+    del keep
+    m = int(info.num_kept)
+    return dict(x=arrays["x"][:m], y=arrays["y"][:m], z=arrays["z"][:m], color=arrays["color"][:3 * m].reshape(-1, 3),
+                intensity=arrays["intensity"][:m] if lp.keep_intensity else None, attributes={k: v[:m] for k, v in ex.items()},
+                info=_las_info(info))
+
+
+def read_las(path, extras=(), **las):
+    """The one-pass host reader (pcv_las_read): the dict read_ply(extras=True) returns — x, y, z float64, color (n, 3) uint8,
+    intensity float32 or None, attributes {name: array} — plus info. **las: las_params' keywords."""
+    lib = L.load_library()
+    lp, keep = las_params(read_las_header(path), extras=extras, **las)
+    h = C.c_void_p()
+    _las_check(lib.pcv_las_read(os.fsencode(str(path)), C.byref(lp), C.byref(h)))
+    try:
+        p = L.Points()
+        lib.pcv_las_points(h, C.byref(p))
+        n = int(p.n)
+
+        def arr(ptr, dtype, count):
+            a = np.zeros(count, dtype=dtype)
+            if count:
+                C.memmove(a.ctypes.data, ptr, a.nbytes)
+            return a
+
+        out = dict(x=arr(p.x, np.float64, n), y=arr(p.y, np.float64, n), z=arr(p.z, np.float64, n),
+                   color=arr(p.color, np.uint8, 3 * n).reshape(-1, 3), intensity=arr(p.intensity, np.float32, n) if lp.keep_intensity else None)
+        count, attrs = C.c_uint32(), (L.Attribute * L.LAS_MAX_EXTRAS)()
+        lib.pcv_las_attributes(h, C.byref(count), attrs)
+        out["attributes"] = {os.fsdecode(attrs[k].name): arr(attrs[k].data, _LAS_EXTRA_DTYPES[os.fsdecode(attrs[k].name)], n)
+                             for k in range(count.value)}
+        info = L.LasInfo()
+        lib.pcv_las_info_get(h, C.byref(info))
+        out["info"] = _las_info(info)
+        return out
+    finally:
+        lib.pcv_las_free(h)
+
+
+class LasCloud:
+    """A LAS file on the device (Context.las_load): .points is the dict Context.s2_split and build_octree's device path take
+    (x, y, z, color[, intensity], attributes) of DeviceColumns; .attributes the extras alone; .info the counts of the load."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.lib, self.handle = ctx, ctx.lib, handle
+        ctx._children.add(self)
+        p, info = L.Points(), L.LasInfo()
+        self.lib.pcv_las_cloud_points(handle, C.byref(p))
+        self.lib.pcv_las_cloud_info(handle, C.byref(info))
+        self.info, self.num_points = _las_info(info), int(p.n)
+        n = self.num_points
+        count, attrs = C.c_uint32(), (L.Attribute * L.LAS_MAX_EXTRAS)()
+        self.lib.pcv_las_cloud_attributes(handle, C.byref(count), attrs)
+        self.attributes = {}
+        for k in range(count.value):
+            name = os.fsdecode(attrs[k].name)
+            self.attributes[name] = DeviceColumn(self, name, attrs[k].data, n, _LAS_EXTRA_DTYPES[name])
+        self.points = dict(x=DeviceColumn(self, "x", p.x, n, np.float64), y=DeviceColumn(self, "y", p.y, n, np.float64),
+                           z=DeviceColumn(self, "z", p.z, n, np.float64), color=DeviceColumn(self, "color", p.color, 3 * n, np.uint8))
+        if p.intensity:
+            self.points["intensity"] = DeviceColumn(self, "intensity", p.intensity, n, np.float32)
+        self.points["attributes"] = self.attributes
+
+    def _alive(self):
+        if not self.handle:
+            raise L.PcvError(L.PCV_E_INVALID, "the LasCloud has been freed")
+
+    def read(self, name):
+        """One column as a numpy array (pcv_las_cloud_read): "x", "y", "z", "color" (n, 3), "intensity" or an extra's name."""
+        self._alive()
+        n = self.num_points
+        dtype, count = {"x": ("<f8", n), "y": ("<f8", n), "z": ("<f8", n), "color": ("u1", 3 * n), "intensity": ("<f4", n)}.get(
+            name, (_LAS_EXTRA_DTYPES.get(name, "u1"), n))
+        a = np.zeros(count, dtype=dtype)
+        self.ctx._check(self.lib.pcv_las_cloud_read(self.handle, os.fsencode(name), a.ctypes.data, a.nbytes))
+        return a.reshape(-1, 3) if name == "color" else a
+
+    def to_host(self):
+        """read_las's dict from the device columns."""
+        return dict(x=self.read("x"), y=self.read("y"), z=self.read("z"), color=self.read("color"),
+                    intensity=self.read("intensity") if "intensity" in self.points else None,
+                    attributes={k: self.read(k) for k in self.attributes}, info=self.info)
+
+    def free(self):
+        if getattr(self, "handle", None):
+            self.lib.pcv_las_cloud_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 def read_ply(path, extras=False):
     """PlyIterator in one pass (src/read_write/ply.rs): dict(x, y, z float64; color (n,3) uint8 or None; intensity or None).
     extras=True (pcv_ply_read_ex): also attributes = {name: array} of every other scalar vertex property in its own type, in the
@@ -2563,13 +2862,40 @@ def read_ply(path, extras=False):
         lib.pcv_ply_free(h)
 
 
+def _is_las(filename):
+    try:
+        with open(filename, "rb") as f:
+            return f.read(4) == b"LASF"
+    except OSError:
+        return False
+
+
 def build_octree_from_file(output_directory, resolution, filename, attributes=("color", "intensity"), ctx=None,
-                           host_decode=False):
+                           host_decode=False, **las):
     """Drop-in for reference `build_octree_from_file` (generation.rs:272-287): the vertex records of the file go to the
     device as they are and are decoded there (host_decode=True: the one-pass host parser instead), bounding box on the
     device, build, directory write. Like the reference binary (src/bin/build_octree.rs:47-52) the default attribute
     list asks for intensity; a PLY without it raises (the reference panics)."""
     attributes = tuple(attributes)
+    if _is_las(filename):  # LAS: every file has an intensity field; **las are las_params' keywords (DESIGN §9j)
+        if "color" not in attributes:
+            raise ValueError("the octree format requires the 'color' attribute (on_disk.rs:20-22)")
+        for a in attributes:
+            if a not in ("color", "intensity"):
+                raise ValueError(f"unsupported attribute {a!r} (octree/mod.rs:62-74 implies color and intensity)")
+        las.setdefault("keep_intensity", "intensity" in attributes)
+        ctx = ctx or default_context()
+        if host_decode:
+            pts = read_las(filename, **las)
+            cloud = {k: pts[k] for k in ("x", "y", "z", "color")}
+            if pts["intensity"] is not None:
+                cloud["intensity"] = pts["intensity"]
+            return build_octree(output_directory, resolution, None, cloud, ("color", "intensity") if pts["intensity"] is not None else ("color",), ctx)
+        tree = ctx.build_from_las(resolution, filename, **las)
+        tree.write_dir(output_directory)
+        return tree
+    if las:
+        raise TypeError(f"{sorted(las)} are keywords for LAS files; {filename!r} is none")
     if not host_decode:
         if "color" not in attributes:
             raise ValueError("the octree format requires the 'color' attribute (on_disk.rs:20-22)")

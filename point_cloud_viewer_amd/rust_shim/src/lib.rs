@@ -152,6 +152,8 @@ extern "C" {
     fn pcv_ooc_finish(ooc: *mut pcv_ooc, directory: *const c_char, stats: *mut PcvOocStats) -> c_int;
     fn pcv_ooc_abort(ooc: *mut pcv_ooc);
     fn pcv_build_octree_from_ply(ctx: *mut pcv_ctx, params: *const PcvBuildParams, path: *const c_char, with_intensity: c_int, out: *mut *mut pcv_octree) -> c_int;
+    // a LAS 1.0 - 1.4 file decoded and filtered on the device, then the build with the box computed there
+    fn pcv_build_octree_from_las(ctx: *mut pcv_ctx, params: *const PcvBuildParams, path: *const c_char, las_params: *const PcvLasParams, out: *mut *mut pcv_octree) -> c_int;
     fn pcv_octree_write_dir(t: *mut pcv_octree, directory: *const c_char) -> c_int;
     fn pcv_octree_open_dir(ctx: *mut pcv_ctx, directory: *const c_char, out: *mut *mut pcv_octree) -> c_int;
     fn pcv_octree_num_nodes(t: *const pcv_octree) -> u64;
@@ -228,6 +230,29 @@ pub struct PcvMapTilesParams {
     pub max_tiles: u64,
     pub max_pool_bytes: u64,
     pub staging_points: u64,
+}
+
+/// pcv_las_params (include/pcv_hip.h); color_mode: 0 auto, 1 rgb16, 2 rgb8, 3 intensity, 4 constant
+#[repr(C)]
+pub struct PcvLasParams {
+    pub color_mode: u32,
+    pub constant_color: [u8; 3],
+    pub drop_withheld: u8,
+    pub keep_intensity: u32,
+    pub piece_points: u32,
+    pub use_transform: u32,
+    pub num_extras: u32,
+    pub class_mask: [u64; 4],
+    pub global_from_local: [f64; 7],
+    pub extras: [*const c_char; 12],
+}
+
+impl Default for PcvLasParams {
+    /// Every class, colour by AUTO, intensity kept (the octree's second attribute), no extras, no transform.
+    fn default() -> Self {
+        PcvLasParams { color_mode: 0, constant_color: [0; 3], drop_withheld: 0, keep_intensity: 1, piece_points: 0, use_transform: 0, num_extras: 0,
+                       class_mask: [0; 4], global_from_local: [0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0], extras: [std::ptr::null(); 12] }
+    }
 }
 
 /// pcv_terrain_params (include/pcv_hip.h); statistic: 0 max, 1 min, 2 mean
@@ -803,6 +828,28 @@ impl HipOctree {
 }
 
 impl HipOctree {
+    /// A LAS file as an octree: `pcv_build_octree_from_las` (records decoded and filtered on the device, bounding box computed
+    /// there), the directory written, and the directory opened as `from_directory` does. The reference has no LAS reader; the
+    /// contract is DESIGN §9j. Uncompiled, like the rest of this veneer.
+    pub fn from_las(output_directory: impl AsRef<Path>, resolution: f64, filename: impl AsRef<Path>, las: &PcvLasParams) -> Result<Self> {
+        let ctx = HipContext::new(0).map_err(|e| ErrorKind::InvalidInput(e))?;
+        let params = PcvBuildParams { resolution, bbox_min: [0.0; 3], bbox_max: [0.0; 3], max_points_per_node: 0, flags: 0 };
+        let file = CString::new(filename.as_ref().to_str().unwrap()).unwrap();
+        let dir = CString::new(output_directory.as_ref().to_str().unwrap()).unwrap();
+        let mut tree = std::ptr::null_mut();
+        let mut rc = unsafe { pcv_build_octree_from_las(ctx.0, &params, file.as_ptr(), las, &mut tree) };
+        if rc == 0 {
+            rc = unsafe { pcv_octree_write_dir(tree, dir.as_ptr()) };
+        }
+        let msg = if rc != 0 { unsafe { CStr::from_ptr(pcv_last_error(ctx.0)) }.to_string_lossy().into_owned() } else { String::new() };
+        unsafe { pcv_octree_free(tree) };
+        if rc != 0 {
+            return Err(ErrorKind::InvalidInput(format!("from_las failed ({}): {}", rc, msg)).into());
+        }
+        drop(ctx);
+        HipOctree::from_directory(output_directory)
+    }
+
     /// The z/x/y map-tile pyramid (`<dir>/<z>/<x>/<y>.png`, `tiles.json`) of the points `queries` select from this ECEF octree,
     /// drawn at `params.zoom` with the parent levels down to `min_zoom`; png_mode: 0 stored, 1 deflate. Every query must be
     /// one the library serves (as in query_many).
