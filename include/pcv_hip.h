@@ -1700,6 +1700,32 @@ int pcv_ply_append_check_host(const char* path, const char* const* names, const 
 /* The device pool of a context: the bytes handed out now and the most since the last reset (reset_peak != 0 sets the mark to the
  * current figure after reading it). Either output may be NULL. */
 int pcv_ctx_pool_stats(pcv_ctx* ctx, uint64_t* live_bytes, uint64_t* peak_bytes, int reset_peak);
+/* The pool's contract: a block comes with arbitrary contents, and a request owns exactly the bytes it asked for. The guard is
+ * the test hook that holds every kernel to it (DESIGN "The pool's contract"); off unless set, no environment variable sets it.
+ *   mode 0  off.
+ *   mode 1  fill: every device block handed out, fresh or recycled, holds `fill` (0..255) over the requested bytes before the
+ *           request returns (set on the context's stream, and waited for); pinned result blocks likewise, by the host. The
+ *           staging blocks that callers keep across calls are left alone; the node-table block of the build is filled.
+ *   mode 2  fill and fence: also 256 canary bytes in front of the pointer handed out, and canary bytes from pointer + requested
+ *           to the end of the block, at least 256 past the rounded request. pcv_ctx_pool_stats counts the fences.
+ * Legal only while no block of the pool is live (PCV_E_INVALID otherwise); trims the cache, and resets the serial numbers and
+ * the report. With mode 2 the fences of a block are copied back and scanned when it is released (after a wait for the
+ * context's streams), at pcv_ctx_destroy for blocks still live, and for all live blocks by pcv_ctx_pool_guard_check. A damaged
+ * fence is counted, never an error. */
+int pcv_ctx_set_pool_guard(pcv_ctx* ctx, int mode, int fill);
+int pcv_ctx_pool_guard_check(pcv_ctx* ctx);
+/* *checked blocks whose fences were scanned, *damaged those with a byte that is not the canary (a live block scanned twice
+ * counts twice); of the first damaged one: the bytes it asked for, its serial number (the first request after
+ * pcv_ctx_set_pool_guard is 1), and the first damaged byte relative to the pointer handed out (negative: the front fence,
+ * which is scanned first). Any output may be NULL. */
+int pcv_ctx_pool_guard_report(pcv_ctx* ctx, uint64_t* checked, uint64_t* damaged, uint64_t* first_bytes, uint64_t* first_serial,
+                              int64_t* first_offset);
+/* Mode 2 only; host code and memsets, no kernel. Requests `bytes`, copies the block back and requires `fill` in every byte,
+ * writes another pattern over it and releases it; requests `bytes` again, which must return the cached block, filled again;
+ * sets the byte at pointer + offset (inside the block: [-256, block - 256)) and releases the block. Serial numbers 1 and 2 when
+ * called right after pcv_ctx_set_pool_guard; the report then names the second. PCV_E_INVALID with a message for a step that
+ * fails. */
+int pcv_ctx_pool_guard_selftest(pcv_ctx* ctx, uint64_t bytes, int64_t offset);
 
 /* ---- terrain layers -------------------------------------------------------------------- */
 /* The directory `sdl_viewer --terrain <dir>` draws (sdl_viewer/src/terrain_drawer/{read_write,layer,mod}.rs,

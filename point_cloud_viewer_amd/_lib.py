@@ -510,6 +510,11 @@ _SIGNATURES = {
     "pcv_ply_header_host": (C.c_int, [C.POINTER(C.c_char_p), _vp, C.c_uint32, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pcv_ply_append_check_host": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), _vp, C.c_uint32, C.POINTER(C.c_uint64)]),
     "pcv_ctx_pool_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]),
+    "pcv_ctx_set_pool_guard": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "pcv_ctx_pool_guard_check": (C.c_int, [_vp]),
+    "pcv_ctx_pool_guard_report": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_int64)]),
+    "pcv_ctx_pool_guard_selftest": (C.c_int, [_vp, C.c_uint64, C.c_int64]),
     "pcv_render_check_terrain_host": (C.c_int, [C.POINTER(RenderTerrainLayers), C.c_char_p, C.c_uint64]),
     "pcv_render_terrain_window_host": (C.c_int, [C.POINTER(TerrainParams), _vp, C.c_uint32, _vp]),
     "pcv_render_views_terrain": (C.c_int, [_vp, _vp, _vp, C.POINTER(RenderParams), C.POINTER(RenderOverlay), C.POINTER(RenderTerrainLayers),

@@ -1,6 +1,7 @@
-// pcv_ctx.hip — the context behind every entry point of the C ABI (include/pcv_hip.h): the caching device pool, the pinned
-// blocks, the host-thread pool and the host-to-device staging ring, the per-launch profile and its name table, and
-// pcv_ctx_create / destroy / synchronize / wait_stream / signal_stream / trim. Host code only.
+// pcv_ctx.hip — the context behind every entry point of the C ABI (include/pcv_hip.h): the caching device pool and its guard
+// mode (pcv_ctx_set_pool_guard, a test hook), the pinned blocks, the host-thread pool and the host-to-device staging ring, the
+// per-launch profile and its name table, and pcv_ctx_create / destroy / synchronize / wait_stream / signal_stream / trim.
+// Host code only.
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -52,24 +53,181 @@ void PcvPool::trim() {
 }
 
 int pcv_ctx::dev_alloc(void** p, size_t bytes) {
+  if (guard.mode) return guard_alloc(p, bytes);
   hipError_t e;
   *p = pool.alloc(bytes, &e);
   if (!*p) return fail(e == hipErrorOutOfMemory ? PCV_E_OOM : PCV_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
   return PCV_OK;
 }
-void pcv_ctx::dev_free(void* p) { pool.release(p); }
+void pcv_ctx::dev_free(void* p) {
+  if (guard.mode == 2) {
+    auto it = guard.blocks.find(p);
+    if (it == guard.blocks.end()) return;
+    guard_sync();  // whatever still writes the block, on either stream, has to land before its fences are read
+    guard_check(p, it->second);
+    p = it->second.base;
+    guard.blocks.erase(it);
+  }
+  pool.release(p);
+}
+
+// ---- guard mode (pcv_ctx_set_pool_guard): a test hook, DESIGN "The pool's contract" ----
+// The block is painted on the context's stream and the call waits for it: a block may be used first on the side stream, and a
+// poison that lands late would overwrite real data.
+int pcv_ctx::guard_alloc(void** p, size_t bytes) {
+  hipError_t e;
+  *p = nullptr;
+  uint8_t* base = (uint8_t*)pool.alloc(guard.mode == 2 ? pcv_guard_block_request(bytes) : bytes, &e);
+  if (!base) return fail(e == hipErrorOutOfMemory ? PCV_E_OOM : PCV_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+  ++guard.serial;
+  uint8_t* user = base;
+  hipError_t m = hipSuccess;
+  if (guard.mode == 2) {
+    PcvGuardLayout lay;
+    if (!pcv_guard_layout(bytes, pool.live[base], &lay)) {
+      pool.release(base);
+      return fail(PCV_E_INVALID, "pool guard: the block is smaller than its layout");
+    }
+    user = base + lay.user_off;
+    m = hipMemsetAsync(base, guard.canary, lay.user_off, stream);
+    if (m == hipSuccess) m = hipMemsetAsync(base + lay.back_off, guard.canary, lay.back_bytes, stream);
+    guard.blocks[user] = {base, bytes, guard.serial};
+  }
+  if (m == hipSuccess && bytes) m = hipMemsetAsync(user, guard.fill, bytes, stream);
+  if (m == hipSuccess) m = hipStreamSynchronize(stream);
+  if (m != hipSuccess) {
+    guard.blocks.erase(user);
+    pool.release(base);
+    return fail(PCV_E_HIP, std::string("pool guard, painting a block: ") + hipGetErrorString(m));
+  }
+  *p = user;
+  return PCV_OK;
+}
+void pcv_ctx::guard_sync() {
+  (void)hipStreamSynchronize(stream);
+  if (side) (void)hipStreamSynchronize(side);
+}
+// A damaged fence is counted, never an error of the call that found it.
+void pcv_ctx::guard_check(void* user, const PcvPoolGuard::Block& b) {
+  auto it = pool.live.find(b.base);
+  PcvGuardLayout lay;
+  if (it == pool.live.end() || !pcv_guard_layout(b.requested, it->second, &lay)) return;
+  guard.host.resize(lay.user_off + lay.back_bytes);
+  if (hipMemcpy(guard.host.data(), b.base, lay.user_off, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(guard.host.data() + lay.user_off, (const uint8_t*)b.base + lay.back_off, lay.back_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+    return;
+  ++guard.checked;
+  int64_t off = 0;
+  if (!pcv_guard_first_damage(guard.host.data(), guard.host.data() + lay.user_off, lay, guard.canary, &off)) return;
+  if (guard.damaged++ == 0) {
+    guard.first_bytes = b.requested;
+    guard.first_serial = b.serial;
+    guard.first_offset = off;
+  }
+}
+
+extern "C" int pcv_ctx_set_pool_guard(pcv_ctx* ctx, int mode, int fill) {
+  if (!ctx) return PCV_E_INVALID;
+  if (mode < 0 || mode > 2 || fill < 0 || fill > 255) return ctx->fail(PCV_E_INVALID, "pool guard: mode is 0, 1 or 2 and fill a byte");
+  if (!ctx->pool.live.empty())
+    return ctx->fail(PCV_E_INVALID, "pool guard: " + std::to_string(ctx->pool.live.size()) +
+                                        " block(s) of the pool are live; set the guard before anything is built on the context");
+  (void)hipSetDevice(ctx->device);
+  ctx->guard_sync();
+  ctx->pool.trim();  // no unfenced block survives into guard mode, no fenced one out of it
+  ctx->guard = PcvPoolGuard();
+  ctx->guard.mode = mode;
+  ctx->guard.fill = (uint8_t)fill;
+  ctx->guard.canary = pcv_guard_canary((uint8_t)fill);
+  return PCV_OK;
+}
+
+extern "C" int pcv_ctx_pool_guard_check(pcv_ctx* ctx) {
+  if (!ctx) return PCV_E_INVALID;
+  if (ctx->guard.mode != 2) return ctx->fail(PCV_E_INVALID, "pool guard: no fences to check (mode 2 is not set)");
+  (void)hipSetDevice(ctx->device);
+  ctx->guard_sync();
+  for (auto& kv : ctx->guard.blocks) ctx->guard_check(kv.first, kv.second);
+  return PCV_OK;
+}
+
+extern "C" int pcv_ctx_pool_guard_report(pcv_ctx* ctx, uint64_t* checked, uint64_t* damaged, uint64_t* first_bytes,
+                                         uint64_t* first_serial, int64_t* first_offset) {
+  if (!ctx) return PCV_E_INVALID;
+  if (checked) *checked = ctx->guard.checked;
+  if (damaged) *damaged = ctx->guard.damaged;
+  if (first_bytes) *first_bytes = ctx->guard.first_bytes;
+  if (first_serial) *first_serial = ctx->guard.first_serial;
+  if (first_offset) *first_offset = ctx->guard.first_offset;
+  return PCV_OK;
+}
+
+// Host code and hipMemset / hipMemcpy only: the guard shown to work on a block of the caller's size, and one byte planted
+// at user + offset for the report to find. The steps are those of the header's comment.
+extern "C" int pcv_ctx_pool_guard_selftest(pcv_ctx* ctx, uint64_t bytes, int64_t offset) {
+  if (!ctx) return PCV_E_INVALID;
+  if (ctx->guard.mode != 2) return ctx->fail(PCV_E_INVALID, "pool guard selftest: mode 2 is not set");
+  (void)hipSetDevice(ctx->device);
+  std::vector<uint8_t> back(bytes);
+  void *first = nullptr, *p = nullptr;
+  void* first_base = nullptr;
+  for (int round = 0; round < 2; ++round) {
+    if (int rc = ctx->dev_alloc(&p, bytes)) return rc;
+    const PcvPoolGuard::Block blk = ctx->guard.blocks[p];
+    if (round == 0) {
+      first = p;
+      first_base = blk.base;
+    } else if (p != first || blk.base != first_base) {
+      ctx->dev_free(p);
+      return ctx->fail(PCV_E_INVALID, "pool guard selftest: the second request was not served from the cache");
+    }
+    if (bytes && hipMemcpy(back.data(), p, bytes, hipMemcpyDeviceToHost) != hipSuccess) {
+      ctx->dev_free(p);
+      return ctx->fail(PCV_E_HIP, "pool guard selftest: copying the block back failed");
+    }
+    const int64_t bad = pcv_guard_first_unfilled(back.data(), bytes, ctx->guard.fill);
+    if (bad >= 0) {
+      ctx->dev_free(p);
+      return ctx->fail(PCV_E_INVALID, std::string("pool guard selftest: byte ") + std::to_string(bad) + " of a " +
+                                          (round ? "recycled" : "fresh") + " block is not the fill");
+    }
+    if (round == 0) {  // a pattern that is neither fill nor canary, for the second round to find if the fill is missing
+      const uint8_t inverse = (uint8_t)~ctx->guard.fill, pattern = inverse == ctx->guard.canary ? (uint8_t)0x33 : inverse;
+      hipError_t e = bytes ? hipMemsetAsync(p, pattern, bytes, ctx->stream) : hipSuccess;
+      ctx->dev_free(p);  // (waits for the stream)
+      if (e != hipSuccess) return ctx->fail(PCV_E_HIP, "pool guard selftest: hipMemset");
+      continue;
+    }
+    // the planted byte must lie in memory the block owns
+    const size_t block_bytes = ctx->pool.live[blk.base];
+    const int64_t lo = -(int64_t)kPcvGuardFront, hi = (int64_t)(block_bytes - kPcvGuardFront);
+    if (offset < lo || offset >= hi) {
+      ctx->dev_free(p);
+      return ctx->fail(PCV_E_INVALID, "pool guard selftest: offset " + std::to_string(offset) + " is outside the block [" +
+                                          std::to_string(lo) + ", " + std::to_string(hi) + ")");
+    }
+    hipError_t e = hipMemsetAsync((uint8_t*)p + offset, (uint8_t)(ctx->guard.canary ^ 0x80), 1, ctx->stream);
+    ctx->dev_free(p);  // (waits for the stream, then reads the fences)
+    if (e != hipSuccess) return ctx->fail(PCV_E_HIP, "pool guard selftest: hipMemset");
+  }
+  return PCV_OK;
+}
+
 int pcv_ctx::host_alloc(void** p, size_t bytes) {
+  const size_t asked = bytes;
   if (bytes == 0) bytes = 256;
   auto it = host_free.lower_bound(bytes);
   if (it != host_free.end() && it->first <= bytes * 2 + (1u << 20)) {
     *p = it->second;
     host_live[*p] = it->first;
     host_free.erase(it);
+    if (guard.mode) std::memset(*p, guard.fill, asked);
     return PCV_OK;
   }
   hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault);
   if (e != hipSuccess) return fail(PCV_E_OOM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
   host_live[*p] = bytes;
+  if (guard.mode) std::memset(*p, guard.fill, asked);
   return PCV_OK;
 }
 void pcv_ctx::host_release(void* p) {
@@ -91,6 +249,13 @@ int pcv_ctx::pinned_reserve(size_t bytes) {
 }
 
 int pcv_ctx::table_dev_reserve(size_t bytes) {
+  // guard mode: the block has one user, the node tables of pcv_build.hip, and every reserve there starts a new set of tables
+  // that the build writes before it reads them, so the block is filled like a pool block. No fence: it is no pool block.
+  if (guard.mode && bytes <= table_dev_bytes) {
+    guard_sync();
+    if (hipMemsetAsync(table_dev, guard.fill, table_dev_bytes, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
+      return fail(PCV_E_HIP, "pool guard, painting the node tables");
+  }
   if (bytes <= table_dev_bytes) return PCV_OK;
   // the old block may still be read by work in flight: drain both streams before it goes away
   if (table_dev) {
@@ -103,6 +268,11 @@ int pcv_ctx::table_dev_reserve(size_t bytes) {
   const size_t want = (bytes + (bytes >> 1) + 4095) & ~(size_t)4095;
   if (hipMalloc(&table_dev, want) != hipSuccess) return fail(PCV_E_OOM, "out of device memory (node tables)");
   table_dev_bytes = want;
+  if (guard.mode) {
+    guard_sync();
+    if (hipMemsetAsync(table_dev, guard.fill, table_dev_bytes, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
+      return fail(PCV_E_HIP, "pool guard, painting the node tables");
+  }
   return PCV_OK;
 }
 
@@ -366,8 +536,12 @@ extern "C" void pcv_ctx_destroy(pcv_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
   ctx->pool.trim();
+  if (ctx->guard.mode == 2) {  // blocks still live: their fences are read like those of a freed block
+    ctx->guard_sync();
+    for (auto& kv : ctx->guard.blocks) ctx->guard_check(kv.first, kv.second);
+  }
   {
-    for (auto& kv : ctx->pool.live) (void)hipFree(kv.first);
+    for (auto& kv : ctx->pool.live) (void)hipFree(kv.first);  // (base addresses, with the guard on as well)
   }
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);
   if (ctx->pinned_spec) (void)hipHostFree(ctx->pinned_spec);

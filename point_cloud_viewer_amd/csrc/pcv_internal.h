@@ -13,6 +13,7 @@
 
 #include "../../include/pcv_hip.h"
 #include "pcv_levels.h"
+#include "pcv_pool_guard.h"
 #include "pcv_sort_plan.h"
 #include "pcv_spec.h"
 
@@ -45,6 +46,24 @@ struct PcvPool {
   void* alloc(size_t bytes, hipError_t* err);
   void release(void* p);
   void trim();
+};
+
+// Guard mode of the pool (pcv_ctx_set_pool_guard; layout in pcv_pool_guard.h): a test hook, off unless set. The pool's own
+// maps keep holding base addresses and whole block sizes; `blocks` maps the user pointers of mode 2 to them.
+struct PcvPoolGuard {
+  int mode = 0;  // 0 off, 1 fill, 2 fill and fence
+  uint8_t fill = 0, canary = 0;
+  struct Block {
+    void* base;
+    size_t requested;
+    uint64_t serial;
+  };
+  std::map<void*, Block> blocks;  // mode 2: user pointer -> its block
+  uint64_t serial = 0;            // allocations since the guard was set (the first one is 1)
+  uint64_t checked = 0, damaged = 0;
+  uint64_t first_bytes = 0, first_serial = 0;  // the first damaged block
+  int64_t first_offset = 0;
+  std::vector<uint8_t> host;  // the fences of one block, copied back
 };
 
 // Kernel ids for the optional per-launch HIP-event profile (pcv_ctx_set_profiling).
@@ -251,6 +270,10 @@ struct pcv_ctx {
   int dev_alloc(void** p, size_t bytes);
   void dev_free(void* p);
   int pinned_reserve(size_t bytes);
+  PcvPoolGuard guard;
+  int guard_alloc(void** p, size_t bytes);
+  void guard_sync();                                      // every stream the context owns or was given
+  void guard_check(void* user, const PcvPoolGuard::Block& b);  // after guard_sync: the fences of one block, counted
 };
 
 // Kernels whose launches touch every point of the cloud (profiling level 2 brackets only these).

@@ -188,6 +188,26 @@ class Context:
         self._check(self.lib.pcv_ctx_pool_stats(self.handle, C.byref(live), C.byref(peak), 1 if reset_peak else 0))
         return live.value, peak.value
 
+    def set_pool_guard(self, mode, fill=0):
+        """Test hook (pcv_ctx_set_pool_guard): 0 off; 1 every block of the device pool is handed out holding the byte `fill`;
+        2 fenced with canary bytes on both sides as well. Only while nothing built on the context is alive; resets the report."""
+        self._check(self.lib.pcv_ctx_set_pool_guard(self.handle, int(mode), int(fill)))
+
+    def pool_guard_check(self):
+        """Scan the fences of every live block (pcv_ctx_pool_guard_check); blocks are scanned on release anyway."""
+        self._check(self.lib.pcv_ctx_pool_guard_check(self.handle))
+
+    def pool_guard_report(self):
+        """{"checked", "damaged", and of the first damaged block "bytes", "serial", "offset"} (pcv_ctx_pool_guard_report)."""
+        v = [C.c_uint64() for _ in range(4)]
+        off = C.c_int64()
+        self._check(self.lib.pcv_ctx_pool_guard_report(self.handle, *[C.byref(x) for x in v], C.byref(off)))
+        return {"checked": v[0].value, "damaged": v[1].value, "bytes": v[2].value, "serial": v[3].value, "offset": off.value}
+
+    def pool_guard_selftest(self, nbytes, offset):
+        """The guard shown to work on one block of nbytes, and one byte planted at pointer + offset (pcv_ctx_pool_guard_selftest)."""
+        self._check(self.lib.pcv_ctx_pool_guard_selftest(self.handle, int(nbytes), int(offset)))
+
     def close(self):
         # query batches first: freeing an S2 batch reads its cloud (pcv_s2_query_free), so the cloud must still be there
         for child in sorted(getattr(self, "_children", []), key=lambda c: 0 if isinstance(c, QueryBatch) else 1):

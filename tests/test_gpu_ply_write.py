@@ -86,8 +86,7 @@ def octree_big(ctx):
     return octree_scene(ctx, True, 5000)
 
 
-@pytest.fixture(scope="module")
-def s2_scene(ctx):
+def make_s2_scene(ctx):
     x, y, z, rgb = (a[:N_S2] for a in T.uniform_cloud())
     rng = np.random.Generator(np.random.PCG64(11))
     attrs = {name: random_column(typ, N_S2, rng) for name, typ in EXTRAS.items()}
@@ -101,9 +100,15 @@ def s2_scene(ctx):
     batch = cloud.query_batch(shapes)
     columns = {name: batch.attribute(name) for name in EXTRAS}
     have = {"color": "u8vec3", "intensity": "f32", **EXTRAS}
-    yield dict(cloud=cloud, batch=batch, have=have, points=batch.points(), columns=columns, input=points)
-    batch.free()  # before its cloud: pcv_s2_query_free reads the cloud
-    cloud.free()
+    return dict(cloud=cloud, batch=batch, have=have, points=batch.points(), columns=columns, input=points)
+
+
+@pytest.fixture(scope="module")
+def s2_scene(ctx):
+    sc = make_s2_scene(ctx)
+    yield sc
+    sc["batch"].free()  # before its cloud: pcv_s2_query_free reads the cloud
+    sc["cloud"].free()
 
 
 def pick(sc, names):

@@ -67,8 +67,7 @@ def polygon_specs(s):
     return specs
 
 
-@pytest.fixture(scope="module")
-def scene(ctx):
+def make_scene(ctx):
     """About 20 000 uniform points in [0, 100]^2 x [0, 20] with an intensity, max_points_per_node = 300: four levels."""
     x, y, z, rgb, bmin, bmax = local_cloud()
     inten = _intensity(x.size)
@@ -79,9 +78,15 @@ def scene(ctx):
     s["specs"] = polygon_specs(s)
     s["names"] = list(s["specs"])
     s["shapes"] = ctx.shapes([s["specs"][k] for k in s["names"]])
+    return s
+
+
+@pytest.fixture(scope="module")
+def scene(ctx):
+    s = make_scene(ctx)
     yield s
     s["shapes"].free()
-    tree.free()
+    s["tree"].free()
 
 
 def want_list(s, spec):

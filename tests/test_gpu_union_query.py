@@ -39,8 +39,7 @@ def _wide_enough(tree):
     return tree.num_nodes >= 150 and levels.max() > 64
 
 
-@pytest.fixture(scope="module")
-def scene(ctx):
+def make_scene(ctx):
     """The 20 000-point scene with an intensity, max_points_per_node = 300 (lowered until the tree has 150 nodes and a level
     wider than a queue chunk of 64), and the mixed table: the scene's unions and a level-8 cell among two boxes, a map tile and
     AllPoints."""
@@ -63,9 +62,15 @@ def scene(ctx):
     cubes, first_child, child_mask = U.tree_tables(tree)
     s = dict(tree=tree, table=table, shapes=ctx.shapes(table), cubes=cubes, first_child=first_child, child_mask=child_mask,
              x=x, y=y, z=z, rgb=rgb, inten=inten, bmin=bmin, bmax=bmax, cap=cap)
+    return s
+
+
+@pytest.fixture(scope="module")
+def scene(ctx):
+    s = make_scene(ctx)
     yield s
     s["shapes"].free()
-    tree.free()
+    s["tree"].free()
 
 
 def index_colors_are_indices(rgb):

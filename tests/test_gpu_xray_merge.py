@@ -27,8 +27,7 @@ def cell_name(cx, cy, level):
     return "r" + "".join(str((((cx >> l) & 1) << 1) | ((cy >> l) & 1)) for l in range(level - 1, -1, -1))
 
 
-@pytest.fixture(scope="module")
-def cloud(ctx):  # noqa: F811
+def make_cloud(ctx):  # noqa: F811
     rng = np.random.default_rng(42)
     n = 20_000
     which = rng.integers(0, len(PATCHES), n)
@@ -43,7 +42,12 @@ def cloud(ctx):  # noqa: F811
     # occupancy on the CPU: level-2 cells that hold a point strictly inside (the corners sit on cell borders)
     inner = (x > 0) & (x < 64)
     occupied = {cell_name(int(cx), int(cy), 2) for cx, cy in zip(x[inner] // 16, y[inner] // 16)}
-    return dict(tree=tree, occupied=occupied)
+    return dict(tree=tree, occupied=occupied, points=(x, y, z, rgb, bmin, bmax))
+
+
+@pytest.fixture(scope="module")
+def cloud(ctx):  # noqa: F811
+    return make_cloud(ctx)
 
 
 def build(cloud, strategy, background, root="r", tile=W, px=PX):
