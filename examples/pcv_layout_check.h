@@ -123,5 +123,18 @@ PCV_SA(sizeof(pcv_s2_filter) == 32 && offsetof(pcv_s2_filter, location) == 0 && 
 PCV_SA(sizeof(pcv_xray_filter) == 24 && offsetof(pcv_xray_filter, attribute) == 0 && offsetof(pcv_xray_filter, lo) == 8 &&
            offsetof(pcv_xray_filter, hi) == 16,
        "pcv_xray_filter");
+PCV_SA(sizeof(pcv_tiles3d_params) == 152 && offsetof(pcv_tiles3d_params, error_factor) == 0 && offsetof(pcv_tiles3d_params, transform) == 8 &&
+           offsetof(pcv_tiles3d_params, flags) == 136 && offsetof(pcv_tiles3d_params, position_mode) == 140 &&
+           offsetof(pcv_tiles3d_params, chunk_bytes) == 144,
+       "pcv_tiles3d_params");
+PCV_SA(sizeof(pcv_tiles3d_info) == 40 && offsetof(pcv_tiles3d_info, tiles) == 0 && offsetof(pcv_tiles3d_info, content_tiles) == 8 &&
+           offsetof(pcv_tiles3d_info, points) == 16 && offsetof(pcv_tiles3d_info, total_file_bytes) == 24 &&
+           offsetof(pcv_tiles3d_info, chunk_points) == 32,
+       "pcv_tiles3d_info");
+PCV_SA(sizeof(pcv_tiles3d_tile) == 64 && offsetof(pcv_tiles3d_tile, node) == 0 && offsetof(pcv_tiles3d_tile, num_points) == 8 &&
+           offsetof(pcv_tiles3d_tile, mode) == 16 && offsetof(pcv_tiles3d_tile, file_bytes) == 24 &&
+           offsetof(pcv_tiles3d_tile, feature_json_offset) == 32 && offsetof(pcv_tiles3d_tile, feature_binary_offset) == 40 &&
+           offsetof(pcv_tiles3d_tile, batch_json_offset) == 48 && offsetof(pcv_tiles3d_tile, batch_binary_offset) == 56,
+       "pcv_tiles3d_tile");
 
 #endif

@@ -2096,6 +2096,109 @@ int pcv_las_decode(pcv_ctx* ctx, const pcv_las_header* header, const pcv_las_par
 int pcv_build_octree_from_las(pcv_ctx* ctx, const pcv_build_params* params, const char* path, const pcv_las_params* las_params,
                               pcv_octree** out);
 
+/* ---- 3D Tiles export --------------------------------------------------------------------- */
+/* An octree as an OGC 3D Tiles 1.0 tileset: <dir>/tileset.json and one Point Cloud file <dir>/<NodeId>.pnts per node that
+ * holds points. The reference has no such writer; the product is this library's and is stated here. Every point of the octree
+ * is in exactly one node and a parent holds a sample of its subtree, which is "refine":"ADD"; a node's cube is the tile's box.
+ *   tiles    a node with num_points > 0 is a tile with content "<NodeId>.pnts"; a node with 0 points and a non-empty
+ *            descendant is a tile without content; a node whose whole subtree holds 0 points is left out. Children ascend
+ *            by child index.
+ *   json     {"asset":{"version":"1.0"},"geometricError":G,"root":T}, no whitespace, with
+ *            T = {"boundingVolume":{"box":[cx,cy,cz,h,0.0,0.0,0.0,h,0.0,0.0,0.0,h]},"geometricError":g,"refine":"ADD"
+ *                 [,"transform":[16 doubles, column-major]][,"content":{"uri":"<id>.pnts"}][,"children":[T,...]]}
+ *            c = cube_min + cube_edge / 2, h = cube_edge / 2; refine and transform on the root only; g = cube_edge *
+ *            error_factor for a tile with child tiles and 0.0 for one without; G = the root's edge. Doubles as in the
+ *            terrain's meta.json: the shortest of %.15g .. %.17g that round-trips, ".0" after an integral value.
+ *   .pnts    little endian. 28-byte header: "pnts", u32 version 1, u32 byteLength, u32 lengths of the feature table JSON, the
+ *            feature table binary, the batch table JSON, the batch table binary; then those four sections. A JSON is padded
+ *            with 0x20 and a binary with 0x00 so that each section and the file end on a multiple of 8 from the file's start;
+ *            the lengths include the padding.
+ *            feature JSON, quantized: {"POINTS_LENGTH":n,"RTC_CENTER":[a,b,c],"QUANTIZED_VOLUME_OFFSET":[a,b,c],
+ *              "QUANTIZED_VOLUME_SCALE":[e,e,e],"POSITION_QUANTIZED":{"byteOffset":0},"RGB":{"byteOffset":6n}}
+ *            feature JSON, float: {"POINTS_LENGTH":n,"RTC_CENTER":[a,b,c],"POSITION":{"byteOffset":0},"RGB":{"byteOffset":12n}}
+ *            feature binary: n x 3 u16 or n x 3 f32, then the node's .rgb bytes without a gap.
+ *            With PCV_TILES3D_INTENSITY the batch JSON is {"INTENSITY":{"byteOffset":0,"componentType":"FLOAT","type":"SCALAR"}}
+ *            and the batch binary the node's .intensity bytes; without it both lengths are 0.
+ *   centre   RTC_CENTER[a] = rc[a] = (double)(float)(cube_min[a] + cube_edge / 2): a reader may round these globals to
+ *            float32, and a centre that is a float32 value already loses nothing. QUANTIZED_VOLUME_OFFSET[a] = cube_min[a] -
+ *            rc[a] (exact in f64), QUANTIZED_VOLUME_SCALE = cube_edge. A reader's position is rc + offset + q * scale / 65535,
+ *            or rc + (double)f.
+ *   chain    quantized: a u8 code c -> c * 257; a u16 code verbatim; an f32 / f64 unit value t -> (uint16)trunc(65535.0 * t).
+ *            float: (float)(fma(u, cube_edge, cube_min) - rc) with u = c / 255.0, c / 65535.0 or t.
+ *            PCV_TILES3D_POS_AUTO: quantized for PCV_ENC_UINT8 / UINT16 nodes (every bit of the codes is kept), float for
+ *            PCV_ENC_FLOAT32 / FLOAT64 nodes; _QUANTIZED and _FLOAT force one form for every tile. */
+#define PCV_TILES3D_INTENSITY 1u /* flags: the INTENSITY batch table; the octree must carry intensity */
+#define PCV_TILES3D_POS_AUTO 0
+#define PCV_TILES3D_POS_QUANTIZED 1
+#define PCV_TILES3D_POS_FLOAT 2
+#define PCV_TILES3D_DEFAULT_ERROR_FACTOR 0.0625 /* a node refines when its edge covers about 256 px at a 16 px screen-space error */
+#define PCV_TILES3D_MIN_CHUNK_BYTES (4ull << 20)
+#define PCV_TILES3D_DEFAULT_CHUNK_BYTES (256ull << 20)
+typedef struct pcv_tiles3d_params {
+  double error_factor;    /* geometricError of a tile with children = cube_edge * error_factor; finite, >= 0 */
+  double transform[16];   /* the root's "transform", column-major; all zero: none */
+  uint32_t flags;         /* PCV_TILES3D_INTENSITY */
+  uint32_t position_mode; /* PCV_TILES3D_POS_* */
+  uint64_t chunk_bytes;   /* whole files per piece of pcv_tiles3d_write_dir; 0: 256 MiB, else at least 4 MiB */
+} pcv_tiles3d_params;
+typedef struct pcv_tiles3d_info {
+  uint64_t tiles;            /* tiles of tileset.json, those without content among them */
+  uint64_t content_tiles;    /* .pnts files */
+  uint64_t points;
+  uint64_t total_file_bytes; /* of the .pnts files */
+  uint32_t chunk_points;     /* points per work item of the packer (one workgroup each) */
+  uint32_t reserved;
+} pcv_tiles3d_info;
+typedef struct pcv_tiles3d_tile {
+  uint64_t node;          /* index into the octree's node table (pcv_octree_node) */
+  uint64_t num_points;
+  uint32_t mode;          /* PCV_TILES3D_POS_QUANTIZED or _FLOAT */
+  uint32_t reserved;
+  uint64_t file_bytes;
+  uint64_t feature_json_offset, feature_binary_offset, batch_json_offset, batch_binary_offset; /* from the file's start */
+} pcv_tiles3d_tile;
+
+/* Host only, no context (messages: pcv_host_last_error). */
+/* PCV_E_INVALID: a NULL argument, a non-finite or negative error_factor, a non-finite transform, an unknown flag or position
+ * mode, a chunk_bytes that is set and below PCV_TILES3D_MIN_CHUNK_BYTES. */
+int pcv_tiles3d_check_params_host(const pcv_tiles3d_params* params);
+/* rc[3] of a node (only cube_min and cube_edge are read). */
+int pcv_tiles3d_rtc_host(const pcv_node_info* node, double rc[3]);
+/* One complete .pnts file from a node's record and its host bytes (xyz: the .xyz content, rgb: 3 n bytes, intensity: n f32,
+ * NULL without PCV_TILES3D_INTENSITY), the device's twin bit for bit. *len: the file's length; out (nullable) takes
+ * min(capacity, *len) bytes; tile (nullable): the plan of the file, its `node` 0. PCV_E_INVALID: what check_params refuses,
+ * 0 points, the flag without intensity, a file of 4 GiB or more. */
+int pcv_tiles3d_tile_host(const pcv_node_info* node, const pcv_tiles3d_params* params, const uint8_t* xyz, const uint8_t* rgb,
+                          const float* intensity, uint8_t* out, uint64_t capacity, uint64_t* len, pcv_tiles3d_tile* tile);
+/* tileset.json of a node table: `count` nodes ascending by (level, index), the root first, every other node's parent among
+ * them (anything else is PCV_E_INVALID, as is a table without a point). id_high, id_low, num_points, level, cube_min and
+ * cube_edge are read. *len: the length; buf (nullable) takes min(cap, *len) bytes. */
+int pcv_tiles3d_tileset_json_host(const pcv_node_info* nodes, uint64_t count, const pcv_tiles3d_params* params, char* buf, uint64_t cap,
+                                  uint64_t* len);
+
+/* The plan of a tileset over a built octree or one from pcv_octree_open_dir (whose node files are read and uploaded once): which
+ * nodes are tiles, every file's size and section offsets. The octree must outlive the plan. PCV_E_INVALID: what
+ * check_params refuses, PCV_TILES3D_INTENSITY on an octree without intensity, an octree without a point, a single file larger
+ * than chunk_bytes (the message names the node). A failed call leaves nothing allocated. */
+typedef struct pcv_tiles3d pcv_tiles3d;
+int pcv_tiles3d_plan(pcv_octree* tree, const pcv_tiles3d_params* params, pcv_tiles3d** out);
+int pcv_tiles3d_info_get(const pcv_tiles3d* t, pcv_tiles3d_info* out);
+/* The content tiles in node-table order into host memory: *num_tiles (nullable) their number, the first `capacity` are written. */
+int pcv_tiles3d_tiles(const pcv_tiles3d* t, uint64_t capacity, pcv_tiles3d_tile* out, uint64_t* num_tiles);
+/* Complete .pnts files of content tiles [first, first + count), back to back in `out`, which lives where `mem` says (NULL: the
+ * offsets alone), file i at offsets[i] .. offsets[i + 1] (count + 1 offsets, host), as pcv_maptiles_tile_pngs. Packed by one
+ * launch of tiles3d_pack_kernel from the node blobs on the device. PCV_E_INVALID: a range past the end, a capacity below
+ * offsets[count]. A copy to device memory is complete on return as well. */
+int pcv_tiles3d_tile_files(pcv_tiles3d* t, uint64_t first, uint64_t count, int mem, uint64_t capacity, uint8_t* out, uint64_t* offsets);
+/* tileset.json of the plan's octree, as pcv_tiles3d_tileset_json_host. */
+int pcv_tiles3d_tileset_json(const pcv_tiles3d* t, char* buf, uint64_t cap, uint64_t* len);
+/* <directory>/<NodeId>.pnts for every content tile, then <directory>/tileset.json. Whole files are grouped into pieces of at
+ * most chunk_bytes; piece k + 1 is packed (one launch) while piece k crosses to the host and is written by the context's host
+ * threads. Two device buffers and two pinned blocks of the largest piece are held whatever the octree's size. PCV_E_IO names the
+ * file. */
+int pcv_tiles3d_write_dir(pcv_tiles3d* t, const char* directory);
+void pcv_tiles3d_free(pcv_tiles3d* t);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,8 @@ from .octree import (Aabb, Context, OctreeResult, QueryBatch, RenderedViews, S2C
                      terrain_quad_masks, terrain_tile_name, terrain_vertex, terrain_meta_read,
                      MapTiles, build_map_tiles, map_tile_from_quad_index, map_tile_pixels, map_tile_quad_index, map_tiles_check_params,
                      map_tiles_json, map_tiles_params, read_map_tiles,
+                     Tiles3D, build_3d_tiles, read_3d_tiles, tiles3d_check_params, tiles3d_params, tiles3d_rtc, tiles3d_tile_host,
+                     tiles3d_tileset_json,
                      render_check_overlay, render_check_params, render_gamma_lut, render_overlay, render_params,
                      render_check_terrain, render_terrain_window,
                      polygon_check, polygon_contains, polygon_from_lat_lng, polygon_intersects_cubes,

@@ -263,6 +263,29 @@ class LasColumns(C.Structure):  # pcv_las_columns
                 ("extras", C.c_void_p * LAS_MAX_EXTRAS)]
 
 
+TILES3D_INTENSITY = 1
+TILES3D_POS_AUTO, TILES3D_POS_QUANTIZED, TILES3D_POS_FLOAT = range(3)
+TILES3D_POS_NAMES = ["auto", "quantized", "float"]
+TILES3D_DEFAULT_ERROR_FACTOR = 0.0625
+TILES3D_MIN_CHUNK_BYTES = 4 << 20
+
+
+class Tiles3dParams(C.Structure):  # pcv_tiles3d_params
+    _fields_ = [("error_factor", C.c_double), ("transform", C.c_double * 16), ("flags", C.c_uint32), ("position_mode", C.c_uint32),
+                ("chunk_bytes", C.c_uint64)]
+
+
+class Tiles3dInfo(C.Structure):  # pcv_tiles3d_info
+    _fields_ = [("tiles", C.c_uint64), ("content_tiles", C.c_uint64), ("points", C.c_uint64), ("total_file_bytes", C.c_uint64),
+                ("chunk_points", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Tiles3dTile(C.Structure):  # pcv_tiles3d_tile
+    _fields_ = [("node", C.c_uint64), ("num_points", C.c_uint64), ("mode", C.c_uint32), ("reserved", C.c_uint32), ("file_bytes", C.c_uint64),
+                ("feature_json_offset", C.c_uint64), ("feature_binary_offset", C.c_uint64), ("batch_json_offset", C.c_uint64),
+                ("batch_binary_offset", C.c_uint64)]
+
+
 class OocStats(C.Structure):
     _fields_ = [("points", C.c_uint64), ("nodes", C.c_uint64), ("partitions", C.c_uint64), ("largest_bucket", C.c_uint64),
                 ("spill_bytes", C.c_uint64), ("h2d_bytes", C.c_uint64), ("d2h_bytes", C.c_uint64), ("h2d_ms", C.c_double),
@@ -578,6 +601,18 @@ _SIGNATURES = {
     "pcv_las_decode": (C.c_int, [_vp, C.POINTER(LasHeader), C.POINTER(LasParams), _vp, C.c_uint64, C.c_int, C.POINTER(LasColumns),
                                  C.POINTER(LasInfo)]),
     "pcv_build_octree_from_las": (C.c_int, [_vp, C.POINTER(BuildParams), C.c_char_p, C.POINTER(LasParams), C.POINTER(_vp)]),
+    "pcv_tiles3d_check_params_host": (C.c_int, [C.POINTER(Tiles3dParams)]),
+    "pcv_tiles3d_rtc_host": (C.c_int, [C.POINTER(NodeInfo), C.POINTER(C.c_double * 3)]),
+    "pcv_tiles3d_tile_host": (C.c_int, [C.POINTER(NodeInfo), C.POINTER(Tiles3dParams), _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64),
+                                        C.POINTER(Tiles3dTile)]),
+    "pcv_tiles3d_tileset_json_host": (C.c_int, [_vp, C.c_uint64, C.POINTER(Tiles3dParams), _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "pcv_tiles3d_plan": (C.c_int, [_vp, C.POINTER(Tiles3dParams), C.POINTER(_vp)]),
+    "pcv_tiles3d_info_get": (C.c_int, [_vp, C.POINTER(Tiles3dInfo)]),
+    "pcv_tiles3d_tiles": (C.c_int, [_vp, C.c_uint64, _vp, C.POINTER(C.c_uint64)]),
+    "pcv_tiles3d_tile_files": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, _vp, _vp]),
+    "pcv_tiles3d_tileset_json": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "pcv_tiles3d_write_dir": (C.c_int, [_vp, C.c_char_p]),
+    "pcv_tiles3d_free": (None, [_vp]),
 }
 
 _lib = None

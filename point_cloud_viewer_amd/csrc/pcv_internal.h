@@ -159,6 +159,7 @@ enum PcvKernelId {
   PCV_K_LAS_SCAN,             // pcv_las.hip: tile offsets of a piece on top of the running base
   PCV_K_LAS_DECODE,           // pcv_las.hip: a tile of records staged in LDS, picked, counted, compacted and stored as planes
   PCV_K_LAS_COLOR,            // pcv_las.hip: the parked 16-bit colours or intensities narrowed once the file's maxima are known
+  PCV_K_TILES3D_PACK,         // pcv_tiles3d.hip: one workgroup per (file, 1 024 points) of a piece: positions converted, colour and intensity re-aligned
   PCV_K_COUNT
 };
 

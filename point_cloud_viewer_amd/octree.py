@@ -1507,6 +1507,14 @@ class OctreeResult:
         self.ctx._check(self.lib.pcv_octree_nodes_blob(self.handle, ip, idx.size, buf.ctypes.data, buf.size, C.byref(need)))
         return buf.tobytes()
 
+    def tiles3d(self, error_factor=None, transform=None, intensity=False, position_mode="auto", chunk_bytes=None):
+        """The plan of this octree as an OGC 3D Tiles 1.0 tileset (pcv_tiles3d_plan): a Tiles3D, whose files are
+        packed on the device when they are asked for. The octree must outlive it. Arguments: tiles3d_params'."""
+        pr = tiles3d_params(error_factor, transform, intensity, position_mode, chunk_bytes)
+        h = C.c_void_p()
+        self.ctx._check(self.lib.pcv_tiles3d_plan(self.handle, C.byref(pr), C.byref(h)))
+        return Tiles3D(self, h, pr)
+
     def write_nodes(self, directory, min_level=0):
         """Node files of the nodes at level >= min_level, without meta.pb (multi-GPU output)."""
         self.ctx._check(self.lib.pcv_octree_write_nodes(self.handle, str(directory).encode(), int(min_level)))
@@ -4068,6 +4076,243 @@ def build_map_tiles(cloud_dir, out_dir, zoom, min_zoom=None, png="stored", ctx=N
     finally:
         for c in clouds:
             c.free()
+
+
+def tiles3d_params(error_factor=None, transform=None, intensity=False, position_mode="auto", chunk_bytes=None):
+    """pcv_tiles3d_params. error_factor: None = 0.0625; transform: 16 doubles, column-major (or a 4 x 4 array, whose transpose's
+    rows they are), None = none; position_mode: "auto", "quantized", "float" or the PCV_TILES3D_POS_* number; chunk_bytes: None or
+    0 = 256 MiB."""
+    pr = L.Tiles3dParams()
+    pr.error_factor = L.TILES3D_DEFAULT_ERROR_FACTOR if error_factor is None else float(error_factor)
+    if transform is not None:
+        m = np.asarray(transform, dtype=np.float64)
+        m = m.T.ravel() if m.shape == (4, 4) else m.ravel()
+        if m.size != 16:
+            raise ValueError("transform: 16 doubles, column-major, or a 4 x 4 array")
+        pr.transform[:] = [float(v) for v in m]
+    pr.flags = L.TILES3D_INTENSITY if intensity else 0
+    if isinstance(position_mode, str):
+        if position_mode not in L.TILES3D_POS_NAMES:
+            raise ValueError(f"position_mode: one of {L.TILES3D_POS_NAMES}")
+        position_mode = L.TILES3D_POS_NAMES.index(position_mode)
+    pr.position_mode = int(position_mode)
+    pr.chunk_bytes = int(chunk_bytes or 0)
+    return pr
+
+
+def tiles3d_check_params(**params):
+    """pcv_tiles3d_check_params_host: raises PcvError with the rule that is broken. params: tiles3d_params' arguments, or
+    params=a Tiles3dParams."""
+    pr = params["params"] if "params" in params else tiles3d_params(**params)
+    _host_check(L.load_library().pcv_tiles3d_check_params_host(C.byref(pr)), "pcv_tiles3d_check_params_host")
+
+
+def _node_info(node):
+    """A NodeInfo from a NodeInfo or a dict(id=(high, low) | id_high, id_low, num_points, level, encoding, cube_min, cube_edge)."""
+    if isinstance(node, L.NodeInfo):
+        return node
+    nd = L.NodeInfo()
+    hi, lo = node["id"] if "id" in node else (node["id_high"], node["id_low"])
+    nd.id_high, nd.id_low, nd.num_points = int(hi), int(lo), int(node["num_points"])
+    nd.level = int(node["level"]) if "level" in node else int(hi) >> 56
+    nd.encoding = int(node.get("encoding", L.ENC_FLOAT32))
+    nd.cube_min[:] = [float(v) for v in node["cube_min"]]
+    nd.cube_edge = float(node["cube_edge"])
+    return nd
+
+
+def tiles3d_rtc(node):
+    """RTC_CENTER of a node's tile (pcv_tiles3d_rtc_host): (double)(float)(cube_min + cube_edge / 2) per axis."""
+    out = (C.c_double * 3)()
+    _host_check(L.load_library().pcv_tiles3d_rtc_host(C.byref(_node_info(node)), C.byref(out)), "pcv_tiles3d_rtc_host")
+    return np.array(out[:])
+
+
+def tiles3d_tile_host(node, xyz, rgb, intensity=None, with_plan=False, **params):
+    """One complete .pnts file from a node's record and its bytes on the host (pcv_tiles3d_tile_host), the device's twin.
+    intensity: the node's .intensity bytes (or float32 array); params: tiles3d_params' arguments, where intensity=True is implied
+    by passing the bytes. with_plan: also the file's plan as a dict."""
+    nd = _node_info(node)
+    if intensity is not None:
+        params = dict(params, intensity=params.get("intensity", True))
+    pr = params["params"] if "params" in params else tiles3d_params(**params)
+    bufs = [np.frombuffer(bytes(b), dtype=np.uint8) if isinstance(b, (bytes, bytearray, memoryview)) else np.ascontiguousarray(b).view(np.uint8).ravel()
+            for b in (xyz, rgb)]
+    ib = None
+    if intensity is not None:
+        ib = (np.frombuffer(bytes(intensity), dtype=np.uint8) if isinstance(intensity, (bytes, bytearray, memoryview))
+              else np.ascontiguousarray(intensity, dtype=np.float32).view(np.uint8).ravel())
+    n = int(nd.num_points)
+    bpc = {L.ENC_UINT8: 1, L.ENC_UINT16: 2, L.ENC_FLOAT32: 4, L.ENC_FLOAT64: 8}.get(int(nd.encoding), 0)
+    if bufs[0].size != 3 * n * bpc or bufs[1].size != 3 * n or (ib is not None and ib.size != 4 * n):
+        raise ValueError("the node's bytes do not match its num_points and encoding")
+    lib, ln, tile = L.load_library(), C.c_uint64(), L.Tiles3dTile()
+    ip = ib.ctypes.data if ib is not None else None
+    _host_check(lib.pcv_tiles3d_tile_host(C.byref(nd), C.byref(pr), bufs[0].ctypes.data, bufs[1].ctypes.data, ip, None, 0, C.byref(ln), C.byref(tile)),
+                "pcv_tiles3d_tile_host")
+    out = np.zeros(ln.value, dtype=np.uint8)
+    _host_check(lib.pcv_tiles3d_tile_host(C.byref(nd), C.byref(pr), bufs[0].ctypes.data, bufs[1].ctypes.data, ip, out.ctypes.data, out.size, C.byref(ln),
+                                          None), "pcv_tiles3d_tile_host")
+    return (out.tobytes(), _tiles3d_tile(tile)) if with_plan else out.tobytes()
+
+
+def tiles3d_tileset_json(nodes, **params):
+    """The text of tileset.json for a node table (pcv_tiles3d_tileset_json_host): NodeInfo records or the dicts of _node_info,
+    ascending by (level, index). params: tiles3d_params' arguments."""
+    pr = params["params"] if "params" in params else tiles3d_params(**params)
+    arr = (L.NodeInfo * max(1, len(nodes)))()
+    for k, node in enumerate(nodes):
+        arr[k] = _node_info(node)
+    lib, n = L.load_library(), C.c_uint64()
+    _host_check(lib.pcv_tiles3d_tileset_json_host(arr, len(nodes), C.byref(pr), None, 0, C.byref(n)), "pcv_tiles3d_tileset_json_host")
+    buf = C.create_string_buffer(n.value + 1)
+    _host_check(lib.pcv_tiles3d_tileset_json_host(arr, len(nodes), C.byref(pr), buf, n.value, C.byref(n)), "pcv_tiles3d_tileset_json_host")
+    return buf.raw[:n.value].decode()
+
+
+def _tiles3d_tile(t):
+    return dict(node=int(t.node), num_points=int(t.num_points), mode=L.TILES3D_POS_NAMES[t.mode], file_bytes=int(t.file_bytes),
+                feature_json_offset=int(t.feature_json_offset), feature_binary_offset=int(t.feature_binary_offset),
+                batch_json_offset=int(t.batch_json_offset), batch_binary_offset=int(t.batch_binary_offset))
+
+
+class Tiles3D:
+    """One pcv_tiles3d: the plan of an octree as a 3D Tiles 1.0 tileset. The .pnts files are packed on the device from the
+    node blobs the octree holds there, into memory (tile_files) or into a directory (write)."""
+
+    def __init__(self, tree, handle, params):
+        self.tree, self.ctx, self.lib, self.handle, self.params = tree, tree.ctx, tree.lib, handle, params
+        self.ctx._children.add(self)
+
+    def _live(self):
+        if not self.handle or not self.ctx.handle or not self.tree.handle:
+            raise L.PcvError(L.PCV_E_INVALID, "the tileset plan or its octree was freed")
+
+    @property
+    def info(self):
+        self._live()
+        inf = L.Tiles3dInfo()
+        self.ctx._check(self.lib.pcv_tiles3d_info_get(self.handle, C.byref(inf)))
+        return dict(tiles=int(inf.tiles), content_tiles=int(inf.content_tiles), points=int(inf.points),
+                    total_file_bytes=int(inf.total_file_bytes), chunk_points=int(inf.chunk_points))
+
+    def tiles(self):
+        """The content tiles in node-table order: dicts of node (index into the octree's node table), num_points, mode
+        ("quantized" / "float"), file_bytes and the four section offsets."""
+        self._live()
+        n = C.c_uint64()
+        self.ctx._check(self.lib.pcv_tiles3d_tiles(self.handle, 0, None, C.byref(n)))
+        arr = (L.Tiles3dTile * max(1, n.value))()
+        self.ctx._check(self.lib.pcv_tiles3d_tiles(self.handle, n.value, arr, None))
+        return [_tiles3d_tile(arr[k]) for k in range(n.value)]
+
+    def tile_files(self, first=0, count=None, device=False):
+        """The complete .pnts files of content tiles [first, first + count) (pcv_tiles3d_tile_files): a list of bytes, or with
+        device=True (a uint8 torch tensor on the device holding them back to back, uint64 offsets [count + 1])."""
+        self._live()
+        total = self.info["content_tiles"]
+        first = int(first)
+        num = max(total - first, 0) if count is None else int(count)
+        if not (0 <= first <= total and 0 <= num <= total - first):
+            raise L.PcvError(L.PCV_E_INVALID, f"tile range past the end: tiles [{first}, {first + num}) of {total}")
+        offsets = np.zeros(num + 1, dtype=np.uint64)
+        self.ctx._check(self.lib.pcv_tiles3d_tile_files(self.handle, first, num, L.MEM_HOST, 0, None, offsets.ctypes.data))
+        cap = int(offsets[-1])
+        if device:
+            import torch
+            out = torch.empty(max(cap, 1), dtype=torch.uint8, device=f"cuda:{self.ctx.device}")
+            self.ctx.wait_torch()
+            self.ctx._check(self.lib.pcv_tiles3d_tile_files(self.handle, first, num, L.MEM_DEVICE, cap, out.data_ptr(), offsets.ctypes.data))
+            return out[:cap], offsets
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        self.ctx._check(self.lib.pcv_tiles3d_tile_files(self.handle, first, num, L.MEM_HOST, cap, out.ctypes.data, offsets.ctypes.data))
+        return _split_files(out, offsets)
+
+    def tileset_json(self):
+        self._live()
+        n = C.c_uint64()
+        self.ctx._check(self.lib.pcv_tiles3d_tileset_json(self.handle, None, 0, C.byref(n)))
+        buf = C.create_string_buffer(n.value + 1)
+        self.ctx._check(self.lib.pcv_tiles3d_tileset_json(self.handle, buf, n.value, C.byref(n)))
+        return buf.raw[:n.value].decode()
+
+    def write(self, directory):
+        """<directory>/<NodeId>.pnts of every content tile, then <directory>/tileset.json (pcv_tiles3d_write_dir)."""
+        self._live()
+        self.ctx._check(self.lib.pcv_tiles3d_write_dir(self.handle, os.fsencode(str(directory))))
+
+    def free(self):
+        if self.handle and self.ctx.handle:
+            self.lib.pcv_tiles3d_free(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def build_3d_tiles(octree_dir, out_dir, ctx=None, **params):
+    """A 3D Tiles directory (tileset.json and one .pnts per node that holds points) from an octree directory. ctx: None = the
+    default context; params: tiles3d_params' arguments. Returns the tileset's info."""
+    ctx = ctx if ctx is not None else default_context()
+    tiles3d_check_params(**params)
+    tree = ctx.open_dir(octree_dir)
+    t = None
+    try:
+        t = tree.tiles3d(**params)
+        t.write(out_dir)
+        return t.info
+    finally:
+        if t is not None:
+            t.free()
+        tree.free()
+
+
+def read_3d_tiles(directory):
+    """A 3D Tiles directory as this library writes it, in pure Python: walks tileset.json and returns one dict per tile in
+    document order: uri (None without content), box (12 doubles), geometric_error, depth, parent (index into the list, -1 for
+    the root), and for a content tile positions (float64 [n, 3]: rc + offset + q * scale / 65535, or rc + (double)f), rgb
+    (uint8 [n, 3]), intensity (float32 [n] or None), quantized (bool)."""
+    import json
+    import struct
+    directory = str(directory)
+    with open(os.path.join(directory, "tileset.json")) as f:
+        doc = json.load(f)
+    out = []
+
+    def walk(t, parent, depth):
+        rec = dict(uri=None, box=[float(v) for v in t["boundingVolume"]["box"]], geometric_error=float(t["geometricError"]), depth=depth,
+                   parent=parent, positions=None, rgb=None, intensity=None, quantized=None)
+        me = len(out)
+        out.append(rec)
+        if "content" in t:
+            rec["uri"] = t["content"]["uri"]
+            with open(os.path.join(directory, rec["uri"]), "rb") as f:
+                data = f.read()
+            magic, version, total, fj, fb, bj, bb = struct.unpack_from("<4sIIIIII", data, 0)
+            if magic != b"pnts" or version != 1 or total != len(data) or 28 + fj + fb + bj + bb != total:
+                raise ValueError(f"{rec['uri']}: not a .pnts file of version 1")
+            ft = json.loads(data[28:28 + fj].decode())
+            n, fbin = int(ft["POINTS_LENGTH"]), 28 + fj
+            rc = np.array(ft["RTC_CENTER"], dtype=np.float64)
+            if "POSITION_QUANTIZED" in ft:
+                q = np.frombuffer(data, dtype="<u2", count=3 * n, offset=fbin + ft["POSITION_QUANTIZED"]["byteOffset"]).reshape(n, 3)
+                off, scale = np.array(ft["QUANTIZED_VOLUME_OFFSET"], dtype=np.float64), np.array(ft["QUANTIZED_VOLUME_SCALE"], dtype=np.float64)
+                rec["positions"], rec["quantized"] = rc + off + q.astype(np.float64) * scale / 65535.0, True
+            else:
+                p = np.frombuffer(data, dtype="<f4", count=3 * n, offset=fbin + ft["POSITION"]["byteOffset"]).reshape(n, 3)
+                rec["positions"], rec["quantized"] = rc + p.astype(np.float64), False
+            rec["rgb"] = np.frombuffer(data, dtype=np.uint8, count=3 * n, offset=fbin + ft["RGB"]["byteOffset"]).reshape(n, 3).copy()
+            if bj:
+                bt = json.loads(data[fbin + fb:fbin + fb + bj].decode())
+                rec["intensity"] = np.frombuffer(data, dtype="<f4", count=n, offset=fbin + fb + bj + bt["INTENSITY"]["byteOffset"]).copy()
+        for c in t.get("children", []):
+            walk(c, me, depth + 1)
+
+    walk(doc["root"], -1, 0)
+    return out
 
 
 def cloud_kind(directory):

@@ -80,6 +80,8 @@ type pcv_terrain = c_void;
 type pcv_maptiles = c_void;
 #[allow(non_camel_case_types)]
 type pcv_render = c_void;
+#[allow(non_camel_case_types)]
+type pcv_tiles3d = c_void;
 
 /// include/pcv_hip.h pcv_render_params: one frame of the viewer (sdl_viewer/src/lib.rs:158-209).
 #[repr(C)]
@@ -192,6 +194,11 @@ extern "C" {
     fn pcv_maptiles_build_parents(m: *mut pcv_maptiles, min_zoom: u32) -> c_int;
     fn pcv_maptiles_write_dir(m: *mut pcv_maptiles, directory: *const c_char, png_mode: c_int) -> c_int;
     fn pcv_maptiles_free(m: *mut pcv_maptiles);
+    // 3D Tiles: the octree's node blobs packed into .pnts files on the device
+    fn pcv_tiles3d_plan(tree: *mut pcv_octree, params: *const PcvTiles3dParams, out: *mut *mut pcv_tiles3d) -> c_int;
+    fn pcv_tiles3d_info_get(t: *const pcv_tiles3d, out: *mut PcvTiles3dInfo) -> c_int;
+    fn pcv_tiles3d_write_dir(t: *mut pcv_tiles3d, directory: *const c_char) -> c_int;
+    fn pcv_tiles3d_free(t: *mut pcv_tiles3d);
     // the viewer's frame: get_visible_nodes + GL_POINTS under a depth test, rasterised on the device
     fn pcv_s2_open_dir(ctx: *mut pcv_ctx, directory: *const c_char, out: *mut *mut pcv_s2_cloud) -> c_int;
     fn pcv_s2_info(c: *const pcv_s2_cloud, num_cells: *mut u64, num_points: *mut u64, bbox_min: *mut c_double, bbox_max: *mut c_double, has_intensity: *mut c_int, level: *mut u32) -> c_int;
@@ -230,6 +237,35 @@ pub struct PcvMapTilesParams {
     pub max_tiles: u64,
     pub max_pool_bytes: u64,
     pub staging_points: u64,
+}
+
+/// pcv_tiles3d_params (include/pcv_hip.h); transform: column-major, all zero = none; flags: 1 = the INTENSITY
+/// batch table; position_mode: 0 auto, 1 quantized, 2 float; chunk_bytes: 0 = 256 MiB
+#[repr(C)]
+pub struct PcvTiles3dParams {
+    pub error_factor: f64,
+    pub transform: [f64; 16],
+    pub flags: u32,
+    pub position_mode: u32,
+    pub chunk_bytes: u64,
+}
+
+impl Default for PcvTiles3dParams {
+    fn default() -> Self {
+        PcvTiles3dParams { error_factor: 0.0625, transform: [0.0; 16], flags: 0, position_mode: 0, chunk_bytes: 0 }
+    }
+}
+
+/// pcv_tiles3d_info (include/pcv_hip.h)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct PcvTiles3dInfo {
+    pub tiles: u64,
+    pub content_tiles: u64,
+    pub points: u64,
+    pub total_file_bytes: u64,
+    pub chunk_points: u32,
+    pub reserved: u32,
 }
 
 /// pcv_las_params (include/pcv_hip.h); color_mode: 0 auto, 1 rgb16, 2 rgb8, 3 intensity, 4 constant
@@ -848,6 +884,28 @@ impl HipOctree {
         }
         drop(ctx);
         HipOctree::from_directory(output_directory)
+    }
+
+    /// This octree as an OGC 3D Tiles 1.0 tileset: `<dir>/tileset.json` and one `<NodeId>.pnts` per node that holds points,
+    /// packed on the device (`pcv_tiles3d_plan` + `pcv_tiles3d_write_dir`). Returns what was written.
+    pub fn tiles3d(&self, params: &PcvTiles3dParams, output_directory: impl AsRef<Path>) -> Result<PcvTiles3dInfo> {
+        let dir = CString::new(output_directory.as_ref().to_str().unwrap()).unwrap();
+        let _g = self.lock.lock().unwrap();
+        let mut t: *mut pcv_tiles3d = std::ptr::null_mut();
+        let mut info = PcvTiles3dInfo::default();
+        let mut rc = unsafe { pcv_tiles3d_plan(self.tree, params, &mut t) };
+        if rc == 0 {
+            rc = unsafe { pcv_tiles3d_write_dir(t, dir.as_ptr()) };
+        }
+        if rc == 0 {
+            rc = unsafe { pcv_tiles3d_info_get(t, &mut info) };
+        }
+        let msg = if rc != 0 { unsafe { CStr::from_ptr(pcv_last_error(self.ctx.0)) }.to_string_lossy().into_owned() } else { String::new() };
+        unsafe { pcv_tiles3d_free(t) };
+        if rc != 0 {
+            return Err(ErrorKind::InvalidInput(format!("tiles3d failed ({}): {}", rc, msg)).into());
+        }
+        Ok(info)
     }
 
     /// The z/x/y map-tile pyramid (`<dir>/<z>/<x>/<y>.png`, `tiles.json`) of the points `queries` select from this ECEF octree,
