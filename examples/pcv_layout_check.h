@@ -113,6 +113,22 @@ PCV_SA(sizeof(pcv_las_info) == 2256 && offsetof(pcv_las_info, num_kept) == 8 && 
 PCV_SA(sizeof(pcv_las_columns) == 136 && offsetof(pcv_las_columns, color) == 24 && offsetof(pcv_las_columns, intensity) == 32 &&
            offsetof(pcv_las_columns, extras) == 40,
        "pcv_las_columns");
+PCV_SA(sizeof(pcv_las_write_params) == 168 && offsetof(pcv_las_write_params, open_mode) == 4 && offsetof(pcv_las_write_params, point_format) == 8 &&
+           offsetof(pcv_las_write_params, version_minor) == 12 && offsetof(pcv_las_write_params, scale) == 16 &&
+           offsetof(pcv_las_write_params, offset) == 40 && offsetof(pcv_las_write_params, auto_offset) == 64 &&
+           offsetof(pcv_las_write_params, color_rule) == 68 && offsetof(pcv_las_write_params, intensity_scale) == 72 &&
+           offsetof(pcv_las_write_params, num_fields) == 76 && offsetof(pcv_las_write_params, fields) == 80 &&
+           offsetof(pcv_las_write_params, chunk_points) == 88 && offsetof(pcv_las_write_params, file_source_id) == 96 &&
+           offsetof(pcv_las_write_params, year) == 102 && offsetof(pcv_las_write_params, system_identifier) == 104 &&
+           offsetof(pcv_las_write_params, generating_software) == 136,
+       "pcv_las_write_params");
+PCV_SA(sizeof(pcv_las_write_info) == 296 && offsetof(pcv_las_write_info, header_size) == 12 && offsetof(pcv_las_write_info, scale) == 16 &&
+           offsetof(pcv_las_write_info, offset) == 40 && offsetof(pcv_las_write_info, min_xyz) == 64 && offsetof(pcv_las_write_info, max_xyz) == 76 &&
+           offsetof(pcv_las_write_info, bounds) == 88 && offsetof(pcv_las_write_info, num_records) == 136 &&
+           offsetof(pcv_las_write_info, by_return) == 144 && offsetof(pcv_las_write_info, out_of_range) == 264 &&
+           offsetof(pcv_las_write_info, clamped_intensity) == 272 && offsetof(pcv_las_write_info, masked_values) == 280 &&
+           offsetof(pcv_las_write_info, skipped_extras) == 288,
+       "pcv_las_write_info");
 PCV_SA(sizeof(pcv_render_terrain_layers) == 24 && offsetof(pcv_render_terrain_layers, num_layers) == 0 &&
            offsetof(pcv_render_terrain_layers, window) == 4 && offsetof(pcv_render_terrain_layers, layers) == 8 &&
            offsetof(pcv_render_terrain_layers, camera_positions) == 16,

@@ -13,6 +13,7 @@ from .octree import (Aabb, Context, OctreeResult, QueryBatch, RenderedViews, S2C
                      level_shortcuts, level_table, node_name, quadtree_node_id, quadtree_node_name, read_ply,
                      DeviceColumn, LasCloud, las_decode_host, las_extras, las_params, read_las, read_las_header,
                      ply_append_check, ply_header, ply_layout,
+                     las_append_check, las_encode_host, las_write_check_params, las_write_header, las_write_params,
                      Terrain, build_terrain, read_terrain, terrain_check_params, terrain_frame, terrain_meta_json, terrain_params,
                      terrain_quad_masks, terrain_tile_name, terrain_vertex, terrain_meta_read,
                      MapTiles, build_map_tiles, map_tile_from_quad_index, map_tile_pixels, map_tile_quad_index, map_tiles_check_params,

@@ -263,6 +263,26 @@ class LasColumns(C.Structure):  # pcv_las_columns
                 ("extras", C.c_void_p * LAS_MAX_EXTRAS)]
 
 
+LAS_FORMAT_AUTO = 255  # PCV_LAS_FORMAT_AUTO
+LAS_WRITE_COLOR_NAMES = ["x257", "shift8", "rgb8"]  # PCV_LAS_WRITE_COLOR_*
+LAS_TRUNCATE, LAS_APPEND = 0, 1
+
+
+class LasWriteParams(C.Structure):  # pcv_las_write_params
+    _fields_ = [("struct_size", C.c_uint32), ("open_mode", C.c_int32), ("point_format", C.c_uint32), ("version_minor", C.c_uint32),
+                ("scale", C.c_double * 3), ("offset", C.c_double * 3), ("auto_offset", C.c_uint32), ("color_rule", C.c_uint32),
+                ("intensity_scale", C.c_float), ("num_fields", C.c_uint32), ("fields", C.POINTER(C.c_char_p)), ("chunk_points", C.c_uint64),
+                ("file_source_id", C.c_uint16), ("global_encoding", C.c_uint16), ("day", C.c_uint16), ("year", C.c_uint16),
+                ("system_identifier", C.c_char * 32), ("generating_software", C.c_char * 32)]
+
+
+class LasWriteInfo(C.Structure):  # pcv_las_write_info
+    _fields_ = [("point_format", C.c_uint32), ("version_minor", C.c_uint32), ("record_length", C.c_uint32), ("header_size", C.c_uint32),
+                ("scale", C.c_double * 3), ("offset", C.c_double * 3), ("min_xyz", C.c_int32 * 3), ("max_xyz", C.c_int32 * 3),
+                ("bounds", C.c_double * 6), ("num_records", C.c_uint64), ("by_return", C.c_uint64 * 15), ("out_of_range", C.c_uint64),
+                ("clamped_intensity", C.c_uint64), ("masked_values", C.c_uint64), ("skipped_extras", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 TILES3D_INTENSITY = 1
 TILES3D_POS_AUTO, TILES3D_POS_QUANTIZED, TILES3D_POS_FLOAT = range(3)
 TILES3D_POS_NAMES = ["auto", "quantized", "float"]
@@ -600,6 +620,18 @@ _SIGNATURES = {
     "pcv_las_cloud_free": (None, [_vp]),
     "pcv_las_decode": (C.c_int, [_vp, C.POINTER(LasHeader), C.POINTER(LasParams), _vp, C.c_uint64, C.c_int, C.POINTER(LasColumns),
                                  C.POINTER(LasInfo)]),
+    "pcv_query_batch_las_records": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.POINTER(LasWriteParams), C.c_uint64, C.c_int, _vp,
+                                              C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(LasWriteInfo)]),
+    "pcv_s2_query_las_records": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.POINTER(LasWriteParams), C.c_uint64, C.c_int, _vp,
+                                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(LasWriteInfo)]),
+    "pcv_query_batch_write_las": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_char_p, C.POINTER(LasWriteParams), C.POINTER(LasWriteInfo)]),
+    "pcv_s2_query_write_las": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_char_p, C.POINTER(LasWriteParams), C.POINTER(LasWriteInfo)]),
+    "pcv_las_write_check_params_host": (C.c_int, [C.POINTER(LasWriteParams), C.c_int, C.POINTER(C.c_char_p), _vp, C.c_uint32,
+                                                  C.POINTER(LasWriteInfo)]),
+    "pcv_las_encode_host": (C.c_int, [C.POINTER(LasWriteParams), C.c_uint64, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_char_p), _vp,
+                                      C.POINTER(_vp), C.c_uint32, _vp, C.c_uint64, C.POINTER(LasWriteInfo)]),
+    "pcv_las_write_header_host": (C.c_int, [C.POINTER(LasWriteParams), C.POINTER(LasWriteInfo), _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "pcv_las_append_check_host": (C.c_int, [C.c_char_p, C.POINTER(LasWriteParams), C.POINTER(LasWriteInfo), C.POINTER(C.c_uint64)]),
     "pcv_build_octree_from_las": (C.c_int, [_vp, C.POINTER(BuildParams), C.c_char_p, C.POINTER(LasParams), C.POINTER(_vp)]),
     "pcv_tiles3d_check_params_host": (C.c_int, [C.POINTER(Tiles3dParams)]),
     "pcv_tiles3d_rtc_host": (C.c_int, [C.POINTER(NodeInfo), C.POINTER(C.c_double * 3)]),

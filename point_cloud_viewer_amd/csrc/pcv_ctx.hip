@@ -440,7 +440,8 @@ static const char* kKernelNames[PCV_K_COUNT] = {
     "s2_attr_gather_points_kernel", "ply_rows_kernel", "terrain_mark_kernel", "terrain_accum_kernel", "terrain_unpack_kernel", "terrain_count_kernel",
     "terrain_resolve_kernel", "terrain_mask_kernel", "render_terrain_gather_kernel", "render_terrain_edges_kernel",
     "maptiles_project_kernel", "maptiles_mark_kernel", "maptiles_accum_kernel", "maptiles_unpack_kernel", "maptiles_resolve_kernel",
-    "maptiles_parent_kernel", "las_tile_count_kernel", "las_tile_scan_kernel", "las_decode_kernel", "las_color_kernel", "tiles3d_pack_kernel"};
+    "maptiles_parent_kernel", "las_tile_count_kernel", "las_tile_scan_kernel", "las_decode_kernel", "las_color_kernel", "tiles3d_pack_kernel",
+    "las_records_kernel", "las_min_kernel"};
 static_assert(sizeof(kKernelNames) / sizeof(kKernelNames[0]) == PCV_K_COUNT, "kernel name table out of sync");
 
 extern "C" int pcv_ctx_set_profiling(pcv_ctx* ctx, int enabled) {

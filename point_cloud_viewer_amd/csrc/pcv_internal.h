@@ -160,6 +160,8 @@ enum PcvKernelId {
   PCV_K_LAS_DECODE,           // pcv_las.hip: a tile of records staged in LDS, picked, counted, compacted and stored as planes
   PCV_K_LAS_COLOR,            // pcv_las.hip: the parked 16-bit colours or intensities narrowed once the file's maxima are known
   PCV_K_TILES3D_PACK,         // pcv_tiles3d.hip: one workgroup per (file, 1 024 points) of a piece: positions converted, colour and intensity re-aligned
+  PCV_K_LAS_WRITE_RECORDS,    // pcv_las_write.hip: the kept points of a record range quantised and packed as LAS records (octree batch or S2 query)
+  PCV_K_LAS_WRITE_MIN,        // pcv_las_write.hip: the minima of the kept points' positions (auto_offset only)
   PCV_K_COUNT
 };
 

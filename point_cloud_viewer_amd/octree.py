@@ -1723,6 +1723,53 @@ class QueryBatch:
                 out[i] = n
         return out
 
+    # ---- LAS output (pcv_*_las_records, pcv_*_write_las) ----
+    def las_records(self, shape=None, first_segment=0, num_segments=None, device=False, **las):
+        """The points of a segment range (or of shape `shape`) as LAS point data records, quantised and packed on the device
+        (pcv_query_batch_las_records / pcv_s2_query_las_records) -> (uint8 array [records, record_length], info dict).
+        device=True: a torch tensor on the context's device. **las: las_write_params' keywords."""
+        self._live()
+        first, num = self._ply_range(shape, first_segment, num_segments)
+        pr, _keep = las_write_params(**las)
+        length, count, info = C.c_uint32(), C.c_uint64(), L.LasWriteInfo()
+        fn = self._fn("las_records")
+        rc = fn(self.handle, first, num, C.byref(pr), 0, L.MEM_HOST, None, C.byref(length), C.byref(count), C.byref(info))
+        if rc != L.PCV_OK and (length.value == 0 or count.value == 0):  # anything but "capacity too small"
+            self.ctx._check(rc)
+        n, s = count.value, length.value
+        if device:
+            import torch
+            out = torch.empty((n, s), dtype=torch.uint8, device=f"cuda:{self.ctx.device}")
+            self.ctx.wait_torch()
+            ptr, mem = out.data_ptr(), L.MEM_DEVICE
+        else:
+            out = np.zeros((n, s), dtype=np.uint8)
+            ptr, mem = out.ctypes.data, L.MEM_HOST
+        if n:
+            self.ctx._check(fn(self.handle, first, num, C.byref(pr), n * s, mem, ptr, C.byref(length), C.byref(count), C.byref(info)))
+        return out, _las_write_info(info)
+
+    def write_las(self, path, shape=None, first_segment=0, num_segments=None, **las):
+        """A LAS 1.2 / 1.4 file of a segment range (or shape `shape`), the records packed on the device
+        (pcv_query_batch_write_las / pcv_s2_query_write_las). **las: las_write_params' keywords, open_mode "truncate" | "append"
+        and chunk_points among them. Returns the info dict of the records written; a range without points writes no file."""
+        self._live()
+        first, num = self._ply_range(shape, first_segment, num_segments)
+        pr, _keep = las_write_params(**las)
+        info = L.LasWriteInfo()
+        self.ctx._check(self._fn("write_las")(self.handle, first, num, os.fsencode(str(path)), C.byref(pr), C.byref(info)))
+        return _las_write_info(info)
+
+    def write_las_per_location(self, pattern, **las):
+        """One file per shape (location): pattern.format(i) holds shape i's points; shapes without points get no file.
+        Returns {i: info} for the files that exist afterwards because of this call."""
+        out = {}
+        for i in range(self.num_shapes):
+            info = self.write_las(pattern.format(i), shape=i, **las)
+            if info["num_records"]:
+                out[i] = info
+        return out
+
     def terrain(self, shape=None, bbox_min=None, bbox_max=None, **params):
         """A finished Terrain of this result's points (of shape `shape`, or of all of them): terrain_params' arguments; the
         box defaults to the cloud's."""
@@ -2790,6 +2837,139 @@ def read_las(path, extras=(), **las):
         return out
     finally:
         lib.pcv_las_free(h)
+
+
+def las_write_params(point_format="auto", version_minor=0, scale=0.001, offset=None, color="x257", intensity_scale=1.0, fields=None,
+                     open_mode="truncate", chunk_points=0, file_source_id=0, global_encoding=0, day=0, year=0, system_identifier="",
+                     generating_software=""):
+    """pcv_las_write_params -> (LasWriteParams, keep-alive). point_format: 0 - 3, 6 - 8 or "auto"; scale, offset: a
+    number or three; offset None: floor(min) per axis of the points written (auto_offset; in append mode the file's offset);
+    color: "x257" | "shift8" | "rgb8"; fields: None (every field the source has and the format holds) or names among "color",
+    "intensity" and las_extras' names."""
+    if open_mode not in ("truncate", "append"):
+        raise ValueError("open_mode: 'truncate' or 'append'")
+    if color not in L.LAS_WRITE_COLOR_NAMES:
+        raise ValueError('color is "x257", "shift8" or "rgb8"')
+    p = L.LasWriteParams()
+    p.struct_size = C.sizeof(L.LasWriteParams)
+    p.open_mode = L.LAS_APPEND if open_mode == "append" else L.LAS_TRUNCATE
+    p.point_format = L.LAS_FORMAT_AUTO if isinstance(point_format, str) and point_format == "auto" else int(point_format)
+    p.version_minor = int(version_minor)
+    three = lambda v: [float(v)] * 3 if np.isscalar(v) else [float(a) for a in v]
+    for a, v in enumerate(three(scale)):
+        p.scale[a] = v
+    p.auto_offset = 1 if offset is None else 0
+    if offset is not None:
+        for a, v in enumerate(three(offset)):
+            p.offset[a] = v
+    p.color_rule, p.intensity_scale, p.chunk_points = L.LAS_WRITE_COLOR_NAMES.index(color), float(intensity_scale), int(chunk_points)
+    keep = None
+    if fields is not None:
+        keep = [os.fsencode(str(f)) for f in fields]
+        arr = (C.c_char_p * max(1, len(keep)))(*keep)
+        p.fields, p.num_fields = arr, len(keep)
+        keep = (keep, arr)
+    p.file_source_id, p.global_encoding, p.day, p.year = int(file_source_id), int(global_encoding), int(day), int(year)
+    for name, value in (("system_identifier", system_identifier), ("generating_software", generating_software)):
+        b = os.fsencode(value)
+        if len(b) > 32:
+            raise ValueError(f"{name}: at most 32 bytes")
+        setattr(p, name, b)
+    return p, keep
+
+
+def _las_write_info(info):
+    return dict(point_format=int(info.point_format), version_minor=int(info.version_minor), record_length=int(info.record_length),
+                header_size=int(info.header_size), scale=tuple(info.scale), offset=tuple(info.offset), min_xyz=tuple(info.min_xyz),
+                max_xyz=tuple(info.max_xyz), bounds=tuple(info.bounds), num_records=int(info.num_records),
+                by_return=np.array(info.by_return, dtype=np.uint64), out_of_range=int(info.out_of_range),
+                clamped_intensity=int(info.clamped_intensity), masked_values=int(info.masked_values), skipped_extras=int(info.skipped_extras))
+
+
+def _las_write_info_struct(info):
+    if isinstance(info, L.LasWriteInfo):
+        return info
+    s = L.LasWriteInfo()
+    s.point_format, s.version_minor = int(info["point_format"]), int(info["version_minor"])
+    s.record_length, s.header_size = int(info.get("record_length", 0)), int(info.get("header_size", 0))
+    s.num_records = int(info.get("num_records", 0))
+    for a in range(3):
+        s.scale[a], s.offset[a] = info["scale"][a], info["offset"][a]
+        s.min_xyz[a], s.max_xyz[a] = info.get("min_xyz", (0, 0, 0))[a], info.get("max_xyz", (0, 0, 0))[a]
+    for k in range(6):
+        s.bounds[k] = info.get("bounds", (0.0,) * 6)[k]
+    for k in range(15):
+        s.by_return[k] = int(info.get("by_return", [0] * 15)[k])
+    return s
+
+
+def _las_extra_arrays(attributes):
+    """{name: type string | array} -> (names char**, types int32[], n, keep-alive)."""
+    items = list((attributes or {}).items())
+    names = [os.fsencode(str(n)) for n, _ in items]
+    codes = []
+    for _, v in items:
+        if isinstance(v, str):
+            codes.append(L.ATTR_TYPES[v.lower()][0])
+        else:
+            a = np.asarray(v)
+            match = [t for t, (_, dt, comps) in L.ATTR_TYPES.items() if np.dtype(dt) == a.dtype and comps == (a.shape[1] if a.ndim == 2 else 1)]
+            codes.append(L.ATTR_TYPES[match[0]][0] if match else 0)
+    types = np.array(codes, dtype=np.int32)
+    return (C.c_char_p * max(1, len(names)))(*names), types, len(names), (names, types)
+
+
+def las_write_check_params(has_intensity=False, attributes=None, **las):
+    """What write_las checks of its params against a source with these extras ({name: type string}) before it runs
+    (pcv_las_write_check_params_host) -> info dict with the format, version, record length, header size and skipped_extras."""
+    pr, _keep = las_write_params(**las)
+    names, types, n, _k2 = _las_extra_arrays(attributes)
+    info = L.LasWriteInfo()
+    _las_check(L.load_library().pcv_las_write_check_params_host(C.byref(pr), int(bool(has_intensity)), names, types.ctypes.data, n, C.byref(info)))
+    return _las_write_info(info)
+
+
+def las_encode_host(points, **las):
+    """The host twin of the device packer (pcv_las_encode_host): points as read_las returns them (x, y, z, color or None,
+    intensity or None, attributes {name: array}) -> (uint8 array [n, record_length], info dict). **las: las_write_params' keywords."""
+    pr, _keep = las_write_params(**las)
+    x, y, z = (np.ascontiguousarray(points[k], dtype=np.float64) for k in "xyz")
+    n = len(x)
+    color = points.get("color")
+    color = None if color is None else np.ascontiguousarray(color, dtype=np.uint8)
+    inten = points.get("intensity")
+    inten = None if inten is None else np.ascontiguousarray(inten, dtype=np.float32)
+    attrs = {k: np.ascontiguousarray(v) for k, v in (points.get("attributes") or {}).items()}
+    names, types, ne, _k2 = _las_extra_arrays(attrs)
+    cols = (C.c_void_p * max(1, ne))(*[a.ctypes.data for a in attrs.values()])
+    ptr = lambda a: None if a is None else a.ctypes.data
+    lib = L.load_library()
+    info = L.LasWriteInfo()
+    args = (C.byref(pr), n, ptr(x), ptr(y), ptr(z), ptr(color), ptr(inten), names, types.ctypes.data, cols, ne)
+    _las_check(lib.pcv_las_write_check_params_host(C.byref(pr), int(inten is not None), names, types.ctypes.data, ne, C.byref(info)))
+    out = np.zeros((n, int(info.record_length)), dtype=np.uint8)
+    _las_check(lib.pcv_las_encode_host(*args, out.ctypes.data, out.nbytes, C.byref(info)))
+    return out, _las_write_info(info)
+
+
+def las_write_header(info, **las):
+    """The header write_las writes for records that `info` describes (an info dict, or its fields point_format, version_minor,
+    scale, offset, num_records, by_return, bounds), as bytes (pcv_las_write_header_host). **las: las_write_params' keywords."""
+    pr, _keep = las_write_params(**las)
+    s = _las_write_info_struct(info)
+    buf, need = C.create_string_buffer(375), C.c_uint64()
+    _las_check(L.load_library().pcv_las_write_header_host(C.byref(pr), C.byref(s), buf, 375, C.byref(need)))
+    return buf.raw[:need.value]
+
+
+def las_append_check(path, info, **las):
+    """What write_las(open_mode="append") checks before it touches `path` (pcv_las_append_check_host) for a file of `info`'s
+    format and version and, unless offset is None, these scale and offset: the file's record count (0: no file)."""
+    pr, _keep = las_write_params(**las)
+    s = _las_write_info_struct(info)
+    old = C.c_uint64()
+    _las_check(L.load_library().pcv_las_append_check_host(os.fsencode(str(path)), C.byref(pr), C.byref(s), C.byref(old)))
+    return old.value
 
 
 class LasCloud:

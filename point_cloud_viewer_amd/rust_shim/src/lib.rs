@@ -181,6 +181,8 @@ extern "C" {
     fn pcv_query_batch_free(b: *mut pcv_query_batch);
     // PlyNodeWriter over a query's result (ply.rs:559-732): the rows packed on the device, the file written in pieces
     fn pcv_query_batch_write_ply(b: *mut pcv_query_batch, first_segment: u64, num_segments: u64, path: *const c_char, params: *const PcvPlyWriteParams, written: *mut u64) -> c_int;
+    // the same result as an ASPRS LAS file: the records quantised and packed on the device
+    fn pcv_query_batch_write_las(b: *mut pcv_query_batch, first_segment: u64, num_segments: u64, path: *const c_char, params: *const PcvLasWriteParams, info: *mut PcvLasWriteInfo) -> c_int;
     // terrain layers: a query's result reduced to grid vertices on the device, the directory sdl_viewer --terrain reads
     fn pcv_terrain_begin(ctx: *mut pcv_ctx, params: *const PcvTerrainParams, bbox_min: *const c_double, bbox_max: *const c_double, out: *mut *mut pcv_terrain) -> c_int;
     fn pcv_terrain_add_query_batch(t: *mut pcv_terrain, b: *mut pcv_query_batch, first_segment: u64, num_segments: u64) -> c_int;
@@ -216,6 +218,51 @@ extern "C" {
     fn pcv_terrain_open_dir(ctx: *mut pcv_ctx, directory: *const std::os::raw::c_char, out: *mut *mut pcv_terrain) -> c_int;
     fn pcv_render_images(r: *mut pcv_render, first: u32, count: u32, rgba: *mut c_void, mem: c_int) -> c_int;
     fn pcv_render_free(r: *mut pcv_render);
+}
+
+/// pcv_las_write_params (include/pcv_hip.h)
+#[repr(C)]
+pub struct PcvLasWriteParams {
+    pub struct_size: u32,
+    pub open_mode: i32,
+    pub point_format: u32,
+    pub version_minor: u32,
+    pub scale: [f64; 3],
+    pub offset: [f64; 3],
+    pub auto_offset: u32,
+    pub color_rule: u32,
+    pub intensity_scale: f32,
+    pub num_fields: u32,
+    pub fields: *const *const c_char,
+    pub chunk_points: u64,
+    pub file_source_id: u16,
+    pub global_encoding: u16,
+    pub day: u16,
+    pub year: u16,
+    pub system_identifier: [c_char; 32],
+    pub generating_software: [c_char; 32],
+}
+
+/// pcv_las_write_info (include/pcv_hip.h)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct PcvLasWriteInfo {
+    pub point_format: u32,
+    pub version_minor: u32,
+    pub record_length: u32,
+    pub header_size: u32,
+    pub scale: [f64; 3],
+    pub offset: [f64; 3],
+    pub min_xyz: [i32; 3],
+    pub max_xyz: [i32; 3],
+    pub bounds: [f64; 6],
+    pub num_records: u64,
+    pub by_return: [u64; 15],
+    pub out_of_range: u64,
+    pub clamped_intensity: u64,
+    pub masked_values: u64,
+    pub skipped_extras: u32,
+    pub reserved: u32,
 }
 
 /// pcv_ply_write_params (include/pcv_hip.h)
@@ -860,6 +907,40 @@ impl HipOctree {
             return Err(ErrorKind::InvalidInput(format!("write_ply failed ({}): {}", rc, msg)).into());
         }
         Ok(written)
+    }
+
+    /// The points of `queries`, one after another, as an ASPRS LAS file: format 2 in LAS 1.2 (colour; intensity if
+    /// the octree carries it), coordinates quantised at `scale` around floor(min) per axis, the records packed on the device and
+    /// written in pieces. OpenMode::Append adds to a file of the same format, whose scale and offset are used. Queries without
+    /// points leave no file. Returns what the library reports about the records written.
+    pub fn write_las(&self, queries: &[PointQuery], path: impl AsRef<Path>, scale: f64, open_mode: OpenMode) -> Result<PcvLasWriteInfo> {
+        let served: Vec<Option<(PcvShape, Option<[f64; 2]>, Vec<u64>)>> = queries.iter().map(library_query).collect();
+        if queries.is_empty() || served.iter().any(|s| s.is_none()) {
+            return Err(ErrorKind::InvalidInput("write_las: every query must be one the library serves".to_string()).into());
+        }
+        let shapes: Vec<PcvShape> = served.iter().flatten().map(|(s, _, _)| *s).collect();
+        let intervals: Vec<Option<[f64; 2]>> = served.iter().flatten().map(|(_, iv, _)| *iv).collect();
+        let cells: Vec<Vec<u64>> = served.iter().flatten().map(|(_, _, c)| c.clone()).collect();
+        let file = CString::new(path.as_ref().to_str().unwrap()).unwrap();
+        let mut params: PcvLasWriteParams = unsafe { std::mem::zeroed() };
+        params.struct_size = std::mem::size_of::<PcvLasWriteParams>() as u32;
+        params.open_mode = match open_mode {
+            OpenMode::Truncate => 0,
+            OpenMode::Append => 1,
+        };
+        params.point_format = 255; // PCV_LAS_FORMAT_AUTO
+        params.scale = [scale; 3];
+        params.auto_offset = 1;
+        let _g = self.lock.lock().unwrap();
+        let (handle, _, _, offset) = self.run_batch(&shapes, &cells, &intervals);
+        let mut info: PcvLasWriteInfo = unsafe { std::mem::zeroed() };
+        let rc = unsafe { pcv_query_batch_write_las(handle, 0, offset.len() as u64 - 1, file.as_ptr(), &params, &mut info) };
+        let msg = if rc != 0 { unsafe { CStr::from_ptr(pcv_last_error(self.ctx.0)) }.to_string_lossy().into_owned() } else { String::new() };
+        unsafe { pcv_query_batch_free(handle) };
+        if rc != 0 {
+            return Err(ErrorKind::InvalidInput(format!("write_las failed ({}): {}", rc, msg)).into());
+        }
+        Ok(info)
     }
 }
 
