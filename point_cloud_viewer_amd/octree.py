@@ -3148,6 +3148,16 @@ class S2QueryBatch(QueryBatch):
         self._has_int = cloud.has_intensity
         self._segments = None
         self.ctx._children.add(self)
+        cloud._batch_handles[id(self)] = handle
+
+    def free(self):
+        # pcv_s2_query_free reads the batch's cloud: a batch that outlives its cloud (both dropped in one garbage collection,
+        # finalized in any order; a cloud freed by hand first) was released by S2Cloud.free and must not be freed again
+        cloud = self.tree
+        if self.handle and self.ctx.handle and cloud.handle:
+            self.lib.pcv_s2_query_free(self.handle)
+            cloud._batch_handles.pop(id(self), None)
+        self.handle = None
 
     def _ply_available(self):
         have = QueryBatch._ply_available(self)
@@ -3191,6 +3201,7 @@ class S2Cloud:
         self.bbox_min, self.bbox_max = np.array(bmin[:]), np.array(bmax[:])
         self._cells = None
         self._attributes = None
+        self._batch_handles = {}  # id(S2QueryBatch) -> its handle, of the batches not yet freed: they go before the cloud does
 
     def _check(self, rc):
         if self.ctx is not None:
@@ -3360,6 +3371,9 @@ class S2Cloud:
 
     def free(self):
         if self.handle and (self.ctx is None or self.ctx.handle):
+            for h in self._batch_handles.values():  # plain handles: weak references are gone by the time a collection finalizes
+                self.lib.pcv_s2_query_free(h)
+            self._batch_handles.clear()
             self.lib.pcv_s2_free(self.handle)
         self.handle = None
 

@@ -3,7 +3,8 @@ unit quaternions, half extents from a millimetre to larger than the cloud, one o
 whose faces lie ON node cube planes (the octree's cubes are min + k * edge / 2^L: `contains` / SAT ties, aabb.rs:46-48,
 sat.rs:55-101) or one ulp beside them, empty and inverted boxes, and frusta with narrow / wide fields of view and near
 planes from 1e-3 to 10. Relation for Relation like the fixed-seed tests of test_gpu_query.py, and the per-point keep
-masks of a few of each kind."""
+masks of a few of each kind. The ties here are the axis-aligned boxes'; oriented boxes and frusta AT their faces (planted
+points, shapes through node cube corners and stored points, exact scenes) are tests/test_gpu_contain_faces.py."""
 import math
 
 import numpy as np

@@ -349,3 +349,27 @@ def test_the_reference_integration_test_restated(ctx):
         assert sorted(ib.tolist()) == passing.tolist(), spec[0]
     for o in (octree, s2, cloud, tree, shapes):
         o.free()
+
+
+def test_a_batch_that_outlives_its_cloud_goes_with_it(ctx):
+    """pcv_s2_query_free reads the batch's cloud. A cloud freed before its batches — by hand, or by a garbage collection that
+    finalizes a cloud and its batch in the order it likes (an exception's traceback holds both) — releases them itself; the
+    batch is dead from then on, freeing it again does nothing, and the pool gets every byte back."""
+    shapes = ctx.shapes([("all",)])
+    live = ctx.pool_stats()[0]
+    cloud = _split(ctx, 20)
+    a, b = cloud.query_batch(shapes), cloud.query_batch(shapes)
+    assert a.num_points == b.num_points == cloud.num_points > 0
+    a.free()
+    cloud.free()
+    with pytest.raises(pcv.PcvError):
+        b.points()
+    b.free()
+    b.free()
+    assert ctx.pool_stats()[0] == live
+    cloud = _split(ctx, 20)
+    b = cloud.query_batch(shapes)
+    cloud.__del__()  # the collector's other order
+    b.__del__()
+    assert ctx.pool_stats()[0] == live and b.handle is None and cloud.handle is None
+    shapes.free()
