@@ -703,12 +703,6 @@ int pcv_octree_load_device(pcv_octree* t);  // directory octrees: read + upload 
 int pcv_octree_read_node_file(pcv_octree* t, uint64_t i, int which, const uint8_t** data, uint64_t* len);
 // (pcv_make_levels and pcv_bytes_per_coordinate: pcv_levels.h)
 
-// pcv_ply_rows.hip — a row range of a query result (an octree batch or an S2 query, the other null) packed as rows of x y z
-// (doubles) and r g b on the context's stream: the packer of the PLY output, for callers that stream a result piece by piece
-constexpr uint32_t kPcvXyzRgbRowBytes = 27;
-int pcv_ply_pack_xyz_rgb(pcv_query_batch* b, pcv_s2_query* q, uint64_t first_segment, uint64_t num_segments, uint64_t row0, uint64_t nrows,
-                         uint8_t* d_out);
-
 // A failure of a call that has no context to keep the message (pcv_png.cpp): kept per thread for pcv_host_last_error.
 int pcv_host_fail(int code, const std::string& msg);
 

@@ -3,16 +3,12 @@
 // into a file through two device buffers and two pinned blocks (pcv_query_batch_write_las, pcv_s2_query_write_las). The format
 // itself — fields, rules, header, append — is pcv_las_write.h / .cpp; its host-only entry points are at the end of this file.
 //
-// The tile form of pcv_ply_rows.hip, whose alignment properties its tests have pinned: one workgroup of 256 packs one TILE of
-// 32 KiB / record_length consecutive records. It finds the chunk that holds the tile's first record by bisection over the
-// scanned chunk offsets, its waves walk the chunks from there (ranks by ballot over the keep bytes for the octree batch, the
-// per-candidate offsets for an S2 query), every lane decodes its point with the query's own decode, quantises it and lays the
-// 20 - 38-byte record into an LDS image of the tile whose byte 0 stands at the alignment (mod 16) the tile has in the output; the
-// image leaves as aligned 16-byte vectors with a bytewise head and tail. New here are the header's reductions: every lane
-// keeps the extremes of X, Y, Z and the three counters of its points in registers, a wave counts the returns by ballot, the
-// waves meet in LDS behind the image, and the workgroup adds its 24 values to one zeroed block with one vector atomic each
-// (a sum of 0 is skipped).
-// All byte offsets into the output are u64.
+// Tiles of 32 KiB / record_length records, walks and the store are those of pcv_rows_dev.h, the source, the piece pipeline and
+// the slice writer those of pcv_result_rows.h. What is this file's: every lane decodes its point with the query's own decode,
+// quantises it and lays the 20 - 38-byte record into the tile's image; and the header's reductions: every lane keeps the
+// extremes of X, Y, Z and the three counters of its points in registers, a wave counts the returns by ballot, the waves meet in
+// LDS behind the image, and the workgroup adds its 24 values to one zeroed block with one vector atomic each (a sum of 0 is
+// skipped). The min pass of auto_offset walks whole chunks, not tiles.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -21,9 +17,8 @@
 
 #include "pcv_internal.h"
 #include "pcv_las_write.h"
-#include "pcv_query_dev.h"
-#include "pcv_s2_obj.h"
-#include "pcv_s2_query_dev.h"
+#include "pcv_result_rows.h"
+#include "pcv_rows_dev.h"
 
 namespace {
 
@@ -35,29 +30,6 @@ constexpr uint32_t kAccWords = 27;  // 15 returns, 3 counters, 3 hi keys, 3 lo k
 inline uint32_t las_image_bytes(uint32_t tile, uint32_t stride) { return (tile * stride + 16 + 15) & ~15u; }
 
 extern __shared__ __attribute__((aligned(16))) uint8_t las_image[];  // the only LDS of these kernels: its base stays 16-byte aligned
-
-// pcv_ply_rows.hip's store: the image of `bytes` bytes, whose byte 0 stands at las_image[phase] with phase = (address of dst) % 16
-__device__ __forceinline__ void las_store_image(uint8_t* __restrict__ dst, uint32_t phase, uint32_t bytes) {
-  const uint32_t head = min(bytes, (16u - phase) & 15u);
-  for (uint32_t j = threadIdx.x; j < head; j += 256u) dst[j] = las_image[phase + j];
-  const uint32_t nvec = (bytes - head) >> 4;
-  uint4* __restrict__ gv = reinterpret_cast<uint4*>(dst + head);
-  const uint4* lv = reinterpret_cast<const uint4*>(las_image + phase + head);  // phase + head is 0 or 16
-  for (uint32_t v = threadIdx.x; v < nvec; v += 256u) gv[v] = lv[v];
-  const uint32_t done = head + (nvec << 4);
-  for (uint32_t j = done + threadIdx.x; j < bytes; j += 256u) dst[j] = las_image[phase + j];
-}
-
-template <typename Start>
-__device__ __forceinline__ uint64_t las_chunk_of_row(uint64_t c0, uint64_t c1, uint64_t g, Start start) {
-  uint64_t lo = c0, hi = c1;  // start(lo) <= g, start(hi) > g (or hi == c1)
-  while (hi - lo > 1) {
-    const uint64_t mid = lo + ((hi - lo) >> 1);
-    if (start(mid) <= g) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
 
 // What a lane (counters, extremes) and a wave (returns; uniform) have seen of the header's reductions.
 struct LasLaneAcc {
@@ -122,79 +94,36 @@ __global__ __launch_bounds__(256) void las_records_octree_kernel(const ChunkDesc
                                                                  const uint64_t* __restrict__ chunk_off, PcvLasWritePlan pl, uint64_t row0,
                                                                  uint64_t nrows, uint32_t tile, uint32_t part_at, uint8_t* __restrict__ out,
                                                                  PcvLasWriteAcc* __restrict__ acc) {
-  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-  const uint64_t t0 = (uint64_t)blockIdx.x * tile;
-  const uint32_t rows = (uint32_t)min((uint64_t)tile, nrows - t0);
-  const uint64_t g0 = row0 + t0, g1 = g0 + rows;
-  uint8_t* dst = out + t0 * pl.stride;
-  const uint32_t phase = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u);
+  const PcvRowsTile t = pcv_rows_tile(row0, nrows, tile, pl.stride, out);
   LasLaneAcc a;
-  const uint64_t first = las_chunk_of_row(c0, c1, g0, [&](uint64_t c) { return chunk_off[c]; });
-  for (uint64_t ci = first + wave; ci < c1; ci += 4) {
-    uint64_t pos0 = chunk_off[ci];
-    if (pos0 >= g1) break;                  // (uniform) offsets only grow
-    if (chunk_off[ci + 1] <= g0) continue;  // nothing of this chunk in the tile
-    const ChunkDesc& d = desc[ci];
-    PointsView v{};
-    v.encoded = xyz_blob + d.src;
-    v.enc = d.enc & 15u;
-    v.cube_min[0] = d.cube_min[0];
-    v.cube_min[1] = d.cube_min[1];
-    v.cube_min[2] = d.cube_min[2];
-    v.cube_edge = d.cube_edge;
-    const uint8_t* kp = keep + d.keep_off;
-    for (uint32_t q0 = 0; q0 < d.cnt && pos0 < g1; q0 += 64) {
-      const uint32_t q = q0 + lane;
-      const unsigned long long b = __ballot(q < d.cnt && kp[q]);
-      const uint64_t pos = pos0 + (uint64_t)__popcll(b & ((1ull << lane) - 1ull));
-      const bool mine = ((b >> lane) & 1ull) && pos >= g0 && pos < g1;  // then (pos - g0) < rows: inside the image
-      V3d p{0.0, 0.0, 0.0};
-      if (mine) p = load_point(v, q);  // the decode of query_compact_kernel: the same bits as pcv_query_batch_points
-      las_take(pl, mine, d.attr_index + q, p.x, p.y, p.z, las_image + phase + (mine ? (uint32_t)(pos - g0) * pl.stride : 0u), a);
-      pos0 += (uint64_t)__popcll(b);
-    }
-  }
+  pcv_walk_octree_rows(desc, c0, c1, xyz_blob, keep, chunk_off, t.g0, t.g1,
+                       [&](bool mine, const PointsView& v, uint32_t q, uint64_t attr_index, uint32_t row_in_tile) {
+                         V3d p{0.0, 0.0, 0.0};
+                         if (mine) p = load_point(v, q);
+                         las_take(pl, mine, attr_index, p.x, p.y, p.z, las_image + t.phase + (mine ? row_in_tile * pl.stride : 0u), a);
+                       });
   las_flush(a, reinterpret_cast<uint32_t*>(las_image + part_at), acc);  // (its barrier is the one the image needs)
-  las_store_image(dst, phase, rows * pl.stride);
+  pcv_store_image(las_image, t.dst, t.phase, t.rows * pl.stride);
 }
 
-// The same over an S2 query: u32 flags and a scanned offset per candidate, positions read as the doubles they are.
+// The same over an S2 query: positions read as the doubles they are.
 __global__ __launch_bounds__(256) void las_records_s2_kernel(const PcvS2Chunk* __restrict__ chunks, uint64_t c0, uint64_t c1,
                                                              const uint8_t* __restrict__ xyz, const uint32_t* __restrict__ flags,
                                                              const uint64_t* __restrict__ offsets, PcvLasWritePlan pl, uint64_t row0, uint64_t nrows,
                                                              uint32_t tile, uint32_t part_at, uint8_t* __restrict__ out,
                                                              PcvLasWriteAcc* __restrict__ acc) {
-  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-  const uint64_t t0 = (uint64_t)blockIdx.x * tile;
-  const uint32_t rows = (uint32_t)min((uint64_t)tile, nrows - t0);
-  const uint64_t g0 = row0 + t0, g1 = g0 + rows;
-  uint8_t* dst = out + t0 * pl.stride;
-  const uint32_t phase = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u);
+  const PcvRowsTile t = pcv_rows_tile(row0, nrows, tile, pl.stride, out);
   LasLaneAcc a;
-  const uint64_t first = las_chunk_of_row(c0, c1, g0, [&](uint64_t c) { return offsets[chunks[c].first]; });
-  for (uint64_t ci = first + wave; ci < c1; ci += 4) {
-    const PcvS2Chunk c = chunks[ci];
-    if (offsets[c.first] >= g1) break;
-    if (offsets[c.first + c.count] <= g0) continue;
-    for (uint32_t q0 = 0; q0 < c.count; q0 += 64) {  // (uniform trip count: every lane reaches the ballots of las_take)
-      const uint32_t q = q0 + lane;
-      bool mine = q < c.count && flags[c.first + q] != 0;
-      uint64_t pos = 0;
-      if (mine) {
-        pos = offsets[c.first + q];
-        mine = pos >= g0 && pos < g1;
-      }
-      const uint64_t i = c.src + q;
-      double x = 0.0, y = 0.0, z = 0.0;
-      if (mine) {
-        const double* p = reinterpret_cast<const double*>(xyz) + 3 * i;
-        x = p[0], y = p[1], z = p[2];
-      }
-      las_take(pl, mine, i, x, y, z, las_image + phase + (mine ? (uint32_t)(pos - g0) * pl.stride : 0u), a);
+  pcv_walk_s2_rows(chunks, c0, c1, flags, offsets, t.g0, t.g1, [&](bool mine, uint64_t i, uint32_t row_in_tile) {
+    double x = 0.0, y = 0.0, z = 0.0;
+    if (mine) {
+      const double* p = reinterpret_cast<const double*>(xyz) + 3 * i;
+      x = p[0], y = p[1], z = p[2];
     }
-  }
+    las_take(pl, mine, i, x, y, z, las_image + t.phase + (mine ? row_in_tile * pl.stride : 0u), a);
+  });
   las_flush(a, reinterpret_cast<uint32_t*>(las_image + part_at), acc);
-  las_store_image(dst, phase, rows * pl.stride);
+  pcv_store_image(las_image, t.dst, t.phase, t.rows * pl.stride);
 }
 
 // The min pass of auto_offset: one wave per chunk of the range, the kept points' decoded positions as total-order keys under
@@ -217,13 +146,7 @@ __global__ __launch_bounds__(256) void las_min_octree_kernel(const ChunkDesc* __
   unsigned long long k[3] = {0, 0, 0};
   if (ci < c1) {
     const ChunkDesc& d = desc[ci];
-    PointsView v{};
-    v.encoded = xyz_blob + d.src;
-    v.enc = d.enc & 15u;
-    v.cube_min[0] = d.cube_min[0];
-    v.cube_min[1] = d.cube_min[1];
-    v.cube_min[2] = d.cube_min[2];
-    v.cube_edge = d.cube_edge;
+    const PointsView v = points_view_of(d, xyz_blob);
     const uint8_t* kp = keep + d.keep_off;
     for (uint32_t q = lane; q < d.cnt; q += 64) {
       if (!kp[q]) continue;
@@ -253,31 +176,8 @@ __global__ __launch_bounds__(256) void las_min_s2_kernel(const PcvS2Chunk* __res
 }
 
 // ---- what the two kinds of result share on the host -------------------------------------------------------------------------
-struct LasSource {
-  pcv_ctx* ctx = nullptr;
-  pcv_query_batch* octree = nullptr;
-  pcv_s2_query* s2 = nullptr;
-  uint64_t nseg = 0;
-  const uint64_t *seg_off = nullptr, *seg_chunk = nullptr;  // nseg + 1 each
-};
-LasSource source_of(pcv_query_batch* b) {
-  LasSource s;
-  s.ctx = b->ctx, s.octree = b, s.nseg = b->nseg, s.seg_off = b->seg_off.data(), s.seg_chunk = b->seg_chunk.data();
-  return s;
-}
-LasSource source_of(pcv_s2_query* q) {
-  LasSource s;
-  s.ctx = q->cloud->ctx, s.s2 = q, s.nseg = q->nseg, s.seg_off = q->seg_offset.data(), s.seg_chunk = q->seg_first_chunk.data();
-  return s;
-}
-
-int check_range(const LasSource& s, uint64_t first_segment, uint64_t num_segments) {
-  if (first_segment > s.nseg || num_segments > s.nseg - first_segment) return s.ctx->fail(PCV_E_INVALID, "segment range past the end");
-  return PCV_OK;
-}
-
 // The plan with its columns on the device. Loads the used extras of a cloud opened from a directory, and only those.
-int resolve_plan(const LasSource& s, const pcv_las_write_params* params, PcvLasWritePlan* plan, pcv_las_write_info* info) {
+int resolve_plan(const PcvResultSource& s, const pcv_las_write_params* params, PcvLasWritePlan* plan, pcv_las_write_info* info) {
   pcv_ctx* ctx = s.ctx;
   PcvLasSource src;
   src.has_intensity = s.octree ? s.octree->has_intensity : s.s2->cloud->has_intensity;
@@ -298,7 +198,7 @@ int resolve_plan(const LasSource& s, const pcv_las_write_params* params, PcvLasW
 }
 
 // auto_offset: floor(min) per axis over the rows of chunks [c0, c1) into plan->offset; a launch of its own and a wait
-int resolve_auto_offset(const LasSource& s, uint64_t c0, uint64_t c1, uint64_t np, PcvLasWritePlan* plan) {
+int resolve_auto_offset(const PcvResultSource& s, uint64_t c0, uint64_t c1, uint64_t np, PcvLasWritePlan* plan) {
   pcv_ctx* ctx = s.ctx;
   for (int a = 0; a < 3; ++a) plan->offset[a] = 0.0;
   if (np == 0 || c1 == c0) return PCV_OK;
@@ -334,7 +234,7 @@ int resolve_auto_offset(const LasSource& s, uint64_t c0, uint64_t c1, uint64_t n
 }
 
 // records [row0, row0 + nrows) of the result, found among the chunks [c0, c1), into d_out (device) on ctx->stream; d_acc accumulates
-int launch_records(const LasSource& s, const PcvLasWritePlan& plan, uint64_t c0, uint64_t c1, uint64_t row0, uint64_t nrows, uint8_t* d_out,
+int launch_records(const PcvResultSource& s, const PcvLasWritePlan& plan, uint64_t c0, uint64_t c1, uint64_t row0, uint64_t nrows, uint8_t* d_out,
                    PcvLasWriteAcc* d_acc) {
   pcv_ctx* ctx = s.ctx;
   const uint32_t tile = las_tile_records(plan.stride);
@@ -357,7 +257,7 @@ int launch_records(const LasSource& s, const PcvLasWritePlan& plan, uint64_t c0,
   return PCV_OK;
 }
 
-int las_records(const LasSource& s, uint64_t first_segment, uint64_t num_segments, const pcv_las_write_params* params, uint64_t capacity_bytes,
+int las_records(const PcvResultSource& s, uint64_t first_segment, uint64_t num_segments, const pcv_las_write_params* params, uint64_t capacity_bytes,
                 int mem, void* out, uint32_t* record_length, uint64_t* num_records, pcv_las_write_info* info) {
   pcv_ctx* ctx = s.ctx;
   if (record_length) *record_length = 0;
@@ -365,14 +265,13 @@ int las_records(const LasSource& s, uint64_t first_segment, uint64_t num_segment
   if (info) *info = pcv_las_write_info{};
   if (!params) return ctx->fail(PCV_E_INVALID, "null argument");
   int rc;
-  if ((rc = check_range(s, first_segment, num_segments))) return rc;
+  if ((rc = s.check_range(first_segment, num_segments))) return rc;
   if (mem != PCV_MEM_HOST && mem != PCV_MEM_DEVICE) return ctx->fail(PCV_E_INVALID, "bad mem");
   PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   PcvLasWritePlan plan{};
   pcv_las_write_info in{};
   if ((rc = resolve_plan(s, params, &plan, &in))) return rc;
-  const uint64_t p0 = s.seg_off[first_segment], np = s.seg_off[first_segment + num_segments] - p0;
-  const uint64_t c0 = s.seg_chunk[first_segment], c1 = s.seg_chunk[first_segment + num_segments];
+  const auto [p0, np, c0, c1] = s.rows_of_segments(first_segment, num_segments);
   if (np >= 0xffffffffull) return ctx->fail(PCV_E_INVALID, "LAS: number of point records " + std::to_string(np) + " is 2^32 - 1 or more");
   if (record_length) *record_length = plan.stride;
   if (num_records) *num_records = np;
@@ -402,39 +301,19 @@ int las_records(const LasSource& s, uint64_t first_segment, uint64_t num_segment
   return PCV_OK;
 }
 
-// The pipeline of pcv_ply_rows.hip's write_ply over LAS records; the accumulator block lives across the pieces.
-struct LasPipe {
-  pcv_ctx* ctx;
-  hipEvent_t packed[2] = {}, copied[2] = {};
-  explicit LasPipe(pcv_ctx* c) : ctx(c) {}
-  int make() {
-    for (int k = 0; k < 2; ++k) {
-      PCV_HIP_CHECK(ctx, hipEventCreateWithFlags(&packed[k], hipEventDisableTiming));
-      PCV_HIP_CHECK(ctx, hipEventCreateWithFlags(&copied[k], hipEventDisableTiming));
-    }
-    return PCV_OK;
-  }
-  ~LasPipe() {
-    for (int k = 0; k < 2; ++k) {
-      if (packed[k]) (void)hipEventDestroy(packed[k]);
-      if (copied[k]) (void)hipEventDestroy(copied[k]);
-    }
-  }
-};
-
-int write_las(const LasSource& s, uint64_t first_segment, uint64_t num_segments, const char* path, const pcv_las_write_params* params,
+int write_las(const PcvResultSource& s, uint64_t first_segment, uint64_t num_segments, const char* path, const pcv_las_write_params* params,
               pcv_las_write_info* info) {
   pcv_ctx* ctx = s.ctx;
   if (info) *info = pcv_las_write_info{};
   if (!path || !params) return ctx->fail(PCV_E_INVALID, "null argument");
   int rc;
-  if ((rc = check_range(s, first_segment, num_segments))) return rc;
+  if ((rc = s.check_range(first_segment, num_segments))) return rc;
   PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   PcvLasWritePlan plan{};
   pcv_las_write_info in{};
   if ((rc = resolve_plan(s, params, &plan, &in))) return rc;
-  const uint64_t p0 = s.seg_off[first_segment], np = s.seg_off[first_segment + num_segments] - p0;
-  const uint64_t c0 = s.seg_chunk[first_segment], c1 = s.seg_chunk[first_segment + num_segments];
+  const PcvResultSource::Rows r = s.rows_of_segments(first_segment, num_segments);
+  const uint64_t np = r.np;
   std::string why;
   bool exists = false;
   PcvLasTotals old;
@@ -446,7 +325,7 @@ int write_las(const LasSource& s, uint64_t first_segment, uint64_t num_segments,
     if (exists)
       for (int a = 0; a < 3; ++a) plan.scale[a] = fs[a], plan.offset[a] = fo[a];  // (auto_offset is satisfied by the file's)
   }
-  if (params->auto_offset && !exists && (rc = resolve_auto_offset(s, c0, c1, np, &plan))) return rc;
+  if (params->auto_offset && !exists && (rc = resolve_auto_offset(s, r.c0, r.c1, np, &plan))) return rc;
   if ((rc = pcv_las_write_check_offset(plan, &why))) return ctx->fail(rc, why);
   if (np + old.count >= 0xffffffffull)
     return ctx->fail(PCV_E_INVALID, "LAS: number of point records " + std::to_string(np + old.count) + " is 2^32 - 1 or more");
@@ -464,48 +343,16 @@ int write_las(const LasSource& s, uint64_t first_segment, uint64_t num_segments,
   PcvScratch sc(ctx);
   uint8_t* d_buf[2];
   PcvLasWriteAcc* d_acc = nullptr;
-  LasPipe pipe(ctx);
+  PcvPiecePipe pipe;  // the accumulator block lives across the pieces
   if ((rc = sc.get(&d_buf[0], piece_bytes)) || (rc = sc.get(&d_buf[1], piece_bytes)) || (rc = sc.get(&d_acc, 1)) ||
-      (rc = ctx->pinned_reserve(2 * piece_bytes)) || (rc = pipe.make()))
+      (rc = ctx->pinned_reserve(2 * piece_bytes)) || (rc = pipe.make(ctx)))
     return rc;
   PCV_HIP_CHECK(ctx, hipMemsetAsync(d_acc, 0, sizeof(PcvLasWriteAcc), ctx->stream));
   uint8_t* h_buf[2] = {(uint8_t*)ctx->pinned, (uint8_t*)ctx->pinned + piece_bytes};
   if ((rc = file.open_for_rows(&why))) return ctx->fail(rc, why);
-  const uint64_t npieces = (np + piece - 1) / piece;
   auto rows_of = [&](uint64_t k) { return std::min(piece, np - k * piece); };
-  // the host's part for piece k: wait for its copy, then pwrite it in slices, one per host thread
-  auto write_piece = [&](uint64_t k) -> int {
-    const int b = (int)(k & 1);
-    if (hipEventSynchronize(pipe.copied[b]) != hipSuccess) return ctx->fail(PCV_E_HIP, "copying LAS records to the host failed");
-    const uint64_t bytes = rows_of(k) * stride, at = k * piece * stride;
-    const size_t workers = ctx->host_pool.threads.size() + 1;
-    const uint64_t slice = std::max<uint64_t>(4u << 20, (bytes + workers - 1) / workers);
-    const size_t parts = (size_t)((bytes + slice - 1) / slice);
-    std::vector<int> part_rc(parts, PCV_OK);
-    std::vector<std::string> part_why(parts);
-    auto one = [&](size_t p) {
-      const uint64_t lo = p * slice, len = std::min(slice, bytes - lo);
-      part_rc[p] = file.write_at(at + lo, h_buf[b] + lo, len, &part_why[p]);
-    };
-    if (parts == 1) one(0);
-    else ctx->host_pool.run(parts, one);
-    for (size_t p = 0; p < parts; ++p)
-      if (part_rc[p]) return ctx->fail(part_rc[p], part_why[p]);
-    return PCV_OK;
-  };
-  auto run = [&]() -> int {
-    for (uint64_t k = 0; k < npieces; ++k) {
-      const int b = (int)(k & 1);
-      // d_buf[b] was last read by the copy of piece k - 2, which write_piece(k - 2) has waited for; h_buf[b] likewise
-      if (int r = launch_records(s, plan, c0, c1, p0 + k * piece, rows_of(k), d_buf[b], d_acc)) return r;
-      PCV_HIP_CHECK(ctx, hipEventRecord(pipe.packed[b], ctx->stream));
-      PCV_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->side, pipe.packed[b], 0));
-      PCV_HIP_CHECK(ctx, hipMemcpyAsync(h_buf[b], d_buf[b], rows_of(k) * stride, hipMemcpyDeviceToHost, ctx->side));
-      PCV_HIP_CHECK(ctx, hipEventRecord(pipe.copied[b], ctx->side));
-      if (k > 0)
-        if (int r = write_piece(k - 1)) return r;
-    }
-    if (int r = write_piece(npieces - 1)) return r;
+  // the header's reductions once the last piece is written; a point out of range refuses the file
+  auto totals = [&]() -> int {
     PCV_HIP_CHECK(ctx, hipMemcpyAsync(&acc, d_acc, sizeof(acc), hipMemcpyDeviceToHost, ctx->stream));
     PCV_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     pcv_las_write_fill_info(plan, acc, np, &in);
@@ -519,11 +366,18 @@ int write_las(const LasSource& s, uint64_t first_segment, uint64_t num_segments,
     }
     return PCV_OK;
   };
-  rc = run();
+  rc = pcv_run_pieces(
+      ctx, pipe, (np + piece - 1) / piece,
+      [&](uint64_t k, int b) { return launch_records(s, plan, r.c0, r.c1, r.p0 + k * piece, rows_of(k), d_buf[b], d_acc); },
+      [&](uint64_t k) { return rows_of(k) * stride; }, d_buf, h_buf,
+      [&](uint64_t k, int b) -> int {
+        if (hipEventSynchronize(pipe.copied[b]) != hipSuccess) return ctx->fail(PCV_E_HIP, "copying LAS records to the host failed");
+        const uint64_t at = k * piece * stride;
+        return pcv_write_slices(ctx, rows_of(k) * stride,
+                                [&](uint64_t lo, uint64_t len, std::string* w) { return file.write_at(at + lo, h_buf[b] + lo, len, w); });
+      });
+  if (rc == PCV_OK && (rc = totals()) != PCV_OK) pcv_drain_pieces(ctx);
   if (rc != PCV_OK) {
-    (void)hipStreamSynchronize(ctx->stream);  // nothing queued may still write into what is freed here
-    (void)hipStreamSynchronize(ctx->side);
-    (void)hipGetLastError();
     file.abandon();
     if (info) *info = in;
     return rc;

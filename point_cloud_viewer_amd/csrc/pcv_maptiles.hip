@@ -27,6 +27,7 @@
 #include "pcv_internal.h"
 #include "pcv_maptiles_dev.h"
 #include "pcv_query_dev.h"
+#include "pcv_result_rows.h"
 #include "pcv_s2_obj.h"
 #include "pcv_s2_query_dev.h"
 #include "pcv_terrain_files.h"
@@ -585,7 +586,7 @@ extern "C" int pcv_maptiles_add_query_batch(pcv_maptiles* m, pcv_query_batch* b,
   if (int rc = usable(m, false)) return rc;
   if (!b || b->ctx != m->ctx) return m->ctx->fail(PCV_E_INVALID, "map tiles: the query batch is null or of another context");
   return add_segments(m, b->seg_off.data(), b->nseg, first_segment, num_segments, [&](uint64_t row0, uint64_t rows, uint8_t* out) {
-    return pcv_ply_pack_xyz_rgb(b, nullptr, first_segment, num_segments, row0, rows, out);
+    return pcv_ply_pack_xyz_rgb(source_of(b), first_segment, num_segments, row0, rows, out);
   });
 }
 
@@ -594,7 +595,7 @@ extern "C" int pcv_maptiles_add_s2_query(pcv_maptiles* m, pcv_s2_query* q, uint6
   if (int rc = usable(m, false)) return rc;
   if (!q || !q->cloud || q->cloud->ctx != m->ctx) return m->ctx->fail(PCV_E_INVALID, "map tiles: the S2 query is null or of another context");
   return add_segments(m, q->seg_offset.data(), q->nseg, first_segment, num_segments, [&](uint64_t row0, uint64_t rows, uint8_t* out) {
-    return pcv_ply_pack_xyz_rgb(nullptr, q, first_segment, num_segments, row0, rows, out);
+    return pcv_ply_pack_xyz_rgb(source_of(q), first_segment, num_segments, row0, rows, out);
   });
 }
 

@@ -4,12 +4,9 @@
 // columns, header, append — is host code in pcv_ply_write.cpp; its three host-only entry points are at the end of this file.
 //
 // A row is the transpose of what the device holds: position as three doubles, then the attribute columns ascending by name,
-// packed without padding, so a stride is 24 + anything and a workgroup's byte range starts at any alignment. One workgroup
-// packs one TILE of `tile_rows` consecutive rows: it finds the chunk that holds the tile's first row by bisection over the
-// scanned chunk offsets, its waves walk the chunks from there (ranks by ballot over the keep bytes for the octree batch, as
-// query_compact_kernel counts them; the per-candidate offsets for an S2 query), every lane writes its point's row into an LDS
-// image of the tile whose byte 0 stands at the alignment (mod 16) the tile has in the output, and the image leaves as aligned
-// 16-byte vectors with a bytewise head and tail. All byte offsets into the output are u64.
+// packed without padding, so a stride is 24 + anything and a workgroup's byte range starts at any alignment. Tiles, walks and
+// the store are those of pcv_rows_dev.h, the source, the piece pipeline and the slice writer those of pcv_result_rows.h; what is
+// this file's is the row itself (put64, put_columns), which columns a result has, and the PLY file around the rows.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -17,9 +14,8 @@
 
 #include "pcv_internal.h"
 #include "pcv_ply_write.h"
-#include "pcv_query_dev.h"
-#include "pcv_s2_obj.h"
-#include "pcv_s2_query_dev.h"
+#include "pcv_result_rows.h"
+#include "pcv_rows_dev.h"
 
 namespace {
 
@@ -85,31 +81,6 @@ __device__ __forceinline__ void put_columns(uint8_t* row, const PlyCols& cols, u
   }
 }
 
-// The image of `bytes` bytes, whose byte 0 stands at ply_image[phase] with phase = (address of dst) % 16, to dst: the interior
-// as aligned 16-byte vectors, its unaligned head and tail bytewise.
-__device__ __forceinline__ void store_image(uint8_t* __restrict__ dst, uint32_t phase, uint32_t bytes) {
-  const uint32_t head = min(bytes, (16u - phase) & 15u);
-  for (uint32_t j = threadIdx.x; j < head; j += 256u) dst[j] = ply_image[phase + j];
-  const uint32_t nvec = (bytes - head) >> 4;
-  uint4* __restrict__ gv = reinterpret_cast<uint4*>(dst + head);
-  const uint4* lv = reinterpret_cast<const uint4*>(ply_image + phase + head);  // phase + head is 0 or 16
-  for (uint32_t v = threadIdx.x; v < nvec; v += 256u) gv[v] = lv[v];
-  const uint32_t done = head + (nvec << 4);
-  for (uint32_t j = done + threadIdx.x; j < bytes; j += 256u) dst[j] = ply_image[phase + j];
-}
-
-// the last chunk c of [c0, c1) whose first row start(c) is <= g; start(c0) <= g by the caller's choice of c0
-template <typename Start>
-__device__ __forceinline__ uint64_t chunk_of_row(uint64_t c0, uint64_t c1, uint64_t g, Start start) {
-  uint64_t lo = c0, hi = c1;  // start(lo) <= g, start(hi) > g (or hi == c1)
-  while (hi - lo > 1) {
-    const uint64_t mid = lo + ((hi - lo) >> 1);
-    if (start(mid) <= g) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
 // Rows [row0 + blockIdx.x * tile_rows, ...) of the octree batch, `nrows` from row0 on, to out + (row - row0) * stride. The chunks
 // [c0, c1) are those of the caller's segment range; chunk_off their scanned kept counts (the row of a chunk's first kept point).
 template <bool WORDS>
@@ -117,69 +88,43 @@ __global__ __launch_bounds__(256) void ply_rows_octree_kernel(const ChunkDesc* _
                                                                const uint8_t* __restrict__ xyz_blob, const uint8_t* __restrict__ keep,
                                                                const uint64_t* __restrict__ chunk_off, PlyCols cols, uint64_t row0,
                                                                uint64_t nrows, uint32_t tile_rows, uint8_t* __restrict__ out) {
-  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-  const uint64_t t0 = (uint64_t)blockIdx.x * tile_rows;
-  const uint32_t rows = (uint32_t)min((uint64_t)tile_rows, nrows - t0);
-  const uint64_t g0 = row0 + t0, g1 = g0 + rows;
-  uint8_t* dst = out + t0 * cols.stride;
-  const uint32_t phase = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u);
-  const uint64_t first = chunk_of_row(c0, c1, g0, [&](uint64_t c) { return chunk_off[c]; });
-  for (uint64_t ci = first + wave; ci < c1; ci += 4) {
-    uint64_t pos0 = chunk_off[ci];
-    if (pos0 >= g1) break;                   // (uniform) offsets only grow
-    if (chunk_off[ci + 1] <= g0) continue;   // nothing of this chunk in the tile (an empty chunk among them)
-    const ChunkDesc& d = desc[ci];
-    PointsView v{};
-    v.encoded = xyz_blob + d.src;
-    v.enc = d.enc & 15u;
-    v.cube_min[0] = d.cube_min[0];
-    v.cube_min[1] = d.cube_min[1];
-    v.cube_min[2] = d.cube_min[2];
-    v.cube_edge = d.cube_edge;
-    const uint8_t* kp = keep + d.keep_off;
-    for (uint32_t q0 = 0; q0 < d.cnt && pos0 < g1; q0 += 64) {
-      const uint32_t q = q0 + lane;
-      const unsigned long long b = __ballot(q < d.cnt && kp[q]);
-      const uint64_t pos = pos0 + (uint64_t)__popcll(b & ((1ull << lane) - 1ull));
-      if (((b >> lane) & 1ull) && pos >= g0 && pos < g1) {
-        const V3d p = load_point(v, q);  // the decode of query_compact_kernel: the same bits as pcv_query_batch_points
-        uint8_t* row = ply_image + phase + (uint32_t)(pos - g0) * cols.stride;
-        put64<WORDS>(row, 0, (uint64_t)__double_as_longlong(p.x));
-        put64<WORDS>(row, 8, (uint64_t)__double_as_longlong(p.y));
-        put64<WORDS>(row, 16, (uint64_t)__double_as_longlong(p.z));
-        put_columns<WORDS>(row, cols, d.attr_index + q);
-      }
-      pos0 += (uint64_t)__popcll(b);
-    }
-  }
+  const PcvRowsTile t = pcv_rows_tile(row0, nrows, tile_rows, cols.stride, out);
+  pcv_walk_octree_rows(desc, c0, c1, xyz_blob, keep, chunk_off, t.g0, t.g1,
+                       [&](bool mine, const PointsView& v, uint32_t q, uint64_t attr_index, uint32_t row_in_tile) {
+                         if (!mine) return;
+                         const V3d p = load_point(v, q);
+                         uint8_t* row = ply_image + t.phase + row_in_tile * cols.stride;
+                         put64<WORDS>(row, 0, (uint64_t)__double_as_longlong(p.x));
+                         put64<WORDS>(row, 8, (uint64_t)__double_as_longlong(p.y));
+                         put64<WORDS>(row, 16, (uint64_t)__double_as_longlong(p.z));
+                         put_columns<WORDS>(row, cols, attr_index);
+                       });
   __syncthreads();
-  store_image(dst, phase, rows * cols.stride);
+  pcv_store_image(ply_image, t.dst, t.phase, t.rows * cols.stride);
 }
 
-// The same over an S2 query: u32 flags and a scanned offset per candidate, positions copied as the 24 bytes they are.
+// The same over an S2 query: u32 flags and a scanned offset per candidate, positions copied as the 24 bytes they are. The walk
+// is this kernel's own lane-strided loop, not pcv_walk_s2_rows: nothing here needs every lane in every step, and in that form
+// the kernel measured 0.4 % slower over rows with three extras (profiles/result_rows_refactor.md).
 template <bool WORDS>
 __global__ __launch_bounds__(256) void ply_rows_s2_kernel(const PcvS2Chunk* __restrict__ chunks, uint64_t c0, uint64_t c1,
                                                            const uint8_t* __restrict__ xyz, const uint32_t* __restrict__ flags,
                                                            const uint64_t* __restrict__ offsets, PlyCols cols, uint64_t row0, uint64_t nrows,
                                                            uint32_t tile_rows, uint8_t* __restrict__ out) {
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-  const uint64_t t0 = (uint64_t)blockIdx.x * tile_rows;
-  const uint32_t rows = (uint32_t)min((uint64_t)tile_rows, nrows - t0);
-  const uint64_t g0 = row0 + t0, g1 = g0 + rows;
-  uint8_t* dst = out + t0 * cols.stride;
-  const uint32_t phase = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u);
-  const uint64_t first = chunk_of_row(c0, c1, g0, [&](uint64_t c) { return offsets[chunks[c].first]; });
+  const PcvRowsTile t = pcv_rows_tile(row0, nrows, tile_rows, cols.stride, out);
+  const uint64_t first = pcv_chunk_of_row(c0, c1, t.g0, [&](uint64_t c) { return offsets[chunks[c].first]; });
   for (uint64_t ci = first + wave; ci < c1; ci += 4) {
     const PcvS2Chunk c = chunks[ci];
-    if (offsets[c.first] >= g1) break;
-    if (offsets[c.first + c.count] <= g0) continue;
+    if (offsets[c.first] >= t.g1) break;
+    if (offsets[c.first + c.count] <= t.g0) continue;
     for (uint32_t q = lane; q < c.count; q += 64) {
       if (!flags[c.first + q]) continue;
       const uint64_t pos = offsets[c.first + q];
-      if (pos < g0 || pos >= g1) continue;
+      if (pos < t.g0 || pos >= t.g1) continue;
       const uint64_t i = c.src + q;
       const uint64_t* p = reinterpret_cast<const uint64_t*>(xyz) + 3 * i;
-      uint8_t* row = ply_image + phase + (uint32_t)(pos - g0) * cols.stride;
+      uint8_t* row = ply_image + t.phase + (uint32_t)(pos - t.g0) * cols.stride;
       put64<WORDS>(row, 0, p[0]);
       put64<WORDS>(row, 8, p[1]);
       put64<WORDS>(row, 16, p[2]);
@@ -187,33 +132,13 @@ __global__ __launch_bounds__(256) void ply_rows_s2_kernel(const PcvS2Chunk* __re
     }
   }
   __syncthreads();
-  store_image(dst, phase, rows * cols.stride);
+  pcv_store_image(ply_image, t.dst, t.phase, t.rows * cols.stride);
 }
 
 // ---- what the two kinds of result share on the host -------------------------------------------------------------------------
-// A result as the packer sees it: the columns it can name, its segment tables, and the launch of its kernel.
-struct PlySource {
-  pcv_ctx* ctx = nullptr;
-  pcv_query_batch* octree = nullptr;
-  pcv_s2_query* s2 = nullptr;
-  uint64_t nseg = 0;
-  const uint64_t *seg_off = nullptr, *seg_chunk = nullptr;  // nseg + 1 each
-};
-
-PlySource source_of(pcv_query_batch* b) {
-  PlySource s;
-  s.ctx = b->ctx, s.octree = b, s.nseg = b->nseg, s.seg_off = b->seg_off.data(), s.seg_chunk = b->seg_chunk.data();
-  return s;
-}
-PlySource source_of(pcv_s2_query* q) {
-  PlySource s;
-  s.ctx = q->cloud->ctx, s.s2 = q, s.nseg = q->nseg, s.seg_off = q->seg_offset.data(), s.seg_chunk = q->seg_first_chunk.data();
-  return s;
-}
-
 // `attributes` (NULL: every attribute the cloud has) as the sorted columns of a row and their device sources. Loads the named
 // extras of a cloud opened from a directory, and only those.
-int resolve_columns(const PlySource& s, const char* const* attributes, uint32_t num_attributes, std::vector<PcvPlyColumn>* cols, uint32_t* stride,
+int resolve_columns(const PcvResultSource& s, const char* const* attributes, uint32_t num_attributes, std::vector<PcvPlyColumn>* cols, uint32_t* stride,
                     PlyCols* dev) {
   pcv_ctx* ctx = s.ctx;
   std::vector<std::string> have_names;
@@ -255,7 +180,7 @@ int resolve_columns(const PlySource& s, const char* const* attributes, uint32_t 
 }
 
 // rows [row0, row0 + nrows) of the result, found among the chunks [c0, c1), into d_out (device) on ctx->stream
-int launch_rows(const PlySource& s, const PlyCols& cols, uint64_t c0, uint64_t c1, uint64_t row0, uint64_t nrows, uint8_t* d_out) {
+int launch_rows(const PcvResultSource& s, const PlyCols& cols, uint64_t c0, uint64_t c1, uint64_t row0, uint64_t nrows, uint8_t* d_out) {
   pcv_ctx* ctx = s.ctx;
   const uint32_t tile = ply_tile_rows(cols.stride);
   const uint64_t blocks = (nrows + tile - 1) / tile;
@@ -280,25 +205,20 @@ int launch_rows(const PlySource& s, const PlyCols& cols, uint64_t c0, uint64_t c
   return PCV_OK;
 }
 
-int check_range(const PlySource& s, uint64_t first_segment, uint64_t num_segments) {
-  if (first_segment > s.nseg || num_segments > s.nseg - first_segment) return s.ctx->fail(PCV_E_INVALID, "segment range past the end");
-  return PCV_OK;
-}
-
-int ply_rows(const PlySource& s, uint64_t first_segment, uint64_t num_segments, const char* const* attributes, uint32_t num_attributes,
+int ply_rows(const PcvResultSource& s, uint64_t first_segment, uint64_t num_segments, const char* const* attributes, uint32_t num_attributes,
              uint64_t capacity_bytes, int mem, void* out, uint32_t* stride_out, uint64_t* num_rows) {
   pcv_ctx* ctx = s.ctx;
   if (stride_out) *stride_out = 0;
   if (num_rows) *num_rows = 0;
   int rc;
-  if ((rc = check_range(s, first_segment, num_segments))) return rc;
+  if ((rc = s.check_range(first_segment, num_segments))) return rc;
   if (mem != PCV_MEM_HOST && mem != PCV_MEM_DEVICE) return ctx->fail(PCV_E_INVALID, "bad mem");
   PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   std::vector<PcvPlyColumn> cols;
   uint32_t stride = 0;
   PlyCols dev{};
   if ((rc = resolve_columns(s, attributes, num_attributes, &cols, &stride, &dev))) return rc;
-  const uint64_t p0 = s.seg_off[first_segment], np = s.seg_off[first_segment + num_segments] - p0;
+  const auto [p0, np, c0, c1] = s.rows_of_segments(first_segment, num_segments);
   if (stride_out) *stride_out = stride;
   if (num_rows) *num_rows = np;
   if (np > capacity_bytes / stride)
@@ -306,7 +226,6 @@ int ply_rows(const PlySource& s, uint64_t first_segment, uint64_t num_segments, 
                                         std::to_string(capacity_bytes) + " bytes");
   if (np == 0) return PCV_OK;
   if (!out) return ctx->fail(PCV_E_INVALID, "null output");
-  const uint64_t c0 = s.seg_chunk[first_segment], c1 = s.seg_chunk[first_segment + num_segments];
   PcvScratch sc(ctx);
   uint8_t* d_out = (uint8_t*)out;
   if (mem == PCV_MEM_HOST && (rc = sc.get(&d_out, np * stride))) return rc;
@@ -317,32 +236,9 @@ int ply_rows(const PlySource& s, uint64_t first_segment, uint64_t num_segments, 
   return PCV_OK;
 }
 
-// The pipeline of pcv_*_write_ply: the rows in pieces of at most `chunk_points`, cut at any row (the packer finds a piece's
-// first chunk itself, so neither a segment of millions of points nor a chunk sets a piece's size); piece k + 1 is packed on
-// the context's stream while piece k crosses to its pinned block on the side stream and piece k - 1 is written by the host
-// threads. Device and pinned memory: two buffers of chunk_points * stride bytes each, whatever the result's size.
-struct PlyPipe {
-  pcv_ctx* ctx;
-  hipEvent_t packed[2] = {}, copied[2] = {};
-  bool made = false;
-  explicit PlyPipe(pcv_ctx* c) : ctx(c) {}
-  int make() {
-    for (int k = 0; k < 2; ++k) {
-      PCV_HIP_CHECK(ctx, hipEventCreateWithFlags(&packed[k], hipEventDisableTiming));
-      PCV_HIP_CHECK(ctx, hipEventCreateWithFlags(&copied[k], hipEventDisableTiming));
-    }
-    made = true;
-    return PCV_OK;
-  }
-  ~PlyPipe() {
-    for (int k = 0; k < 2; ++k) {
-      if (packed[k]) (void)hipEventDestroy(packed[k]);
-      if (copied[k]) (void)hipEventDestroy(copied[k]);
-    }
-  }
-};
-
-int write_ply(const PlySource& s, uint64_t first_segment, uint64_t num_segments, const char* path, const pcv_ply_write_params* params,
+// pcv_*_write_ply: the rows through the piece pipeline in pieces of at most `chunk_points`, cut at any row (the packer finds a
+// piece's first chunk itself, so neither a segment of millions of points nor a chunk sets a piece's size).
+int write_ply(const PcvResultSource& s, uint64_t first_segment, uint64_t num_segments, const char* path, const pcv_ply_write_params* params,
               uint64_t* written) {
   pcv_ctx* ctx = s.ctx;
   if (written) *written = 0;
@@ -350,68 +246,39 @@ int write_ply(const PlySource& s, uint64_t first_segment, uint64_t num_segments,
   if (params->struct_size < sizeof(pcv_ply_write_params)) return ctx->fail(PCV_E_INVALID, "pcv_ply_write_params.struct_size is too small");
   if (params->open_mode != PCV_PLY_TRUNCATE && params->open_mode != PCV_PLY_APPEND) return ctx->fail(PCV_E_INVALID, "bad open_mode");
   int rc;
-  if ((rc = check_range(s, first_segment, num_segments))) return rc;
+  if ((rc = s.check_range(first_segment, num_segments))) return rc;
   PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   std::vector<PcvPlyColumn> cols;
   uint32_t stride = 0;
   PlyCols dev{};
   if ((rc = resolve_columns(s, params->attributes, params->num_attributes, &cols, &stride, &dev))) return rc;
-  const uint64_t p0 = s.seg_off[first_segment], np = s.seg_off[first_segment + num_segments] - p0;
+  const PcvResultSource::Rows r = s.rows_of_segments(first_segment, num_segments);
+  const uint64_t np = r.np;
   PcvPlyFile file;
   std::string why;
   if ((rc = file.begin(path, params->open_mode == PCV_PLY_APPEND, cols, &why))) return ctx->fail(rc, why);
   if (np == 0) return PCV_OK;  // nothing written, no file (node_writer.rs:78-84); an appended file stays as it is
-  const uint64_t c0 = s.seg_chunk[first_segment], c1 = s.seg_chunk[first_segment + num_segments];
   const uint64_t piece = std::min<uint64_t>(np, params->chunk_points ? params->chunk_points : kPlyDefaultChunkPoints);
   const uint64_t piece_bytes = ((piece * stride + 255) / 256) * 256;
   PcvScratch sc(ctx);
   uint8_t* d_buf[2];
-  PlyPipe pipe(ctx);
-  if ((rc = sc.get(&d_buf[0], piece_bytes)) || (rc = sc.get(&d_buf[1], piece_bytes)) || (rc = ctx->pinned_reserve(2 * piece_bytes)) || (rc = pipe.make()))
+  PcvPiecePipe pipe;
+  if ((rc = sc.get(&d_buf[0], piece_bytes)) || (rc = sc.get(&d_buf[1], piece_bytes)) || (rc = ctx->pinned_reserve(2 * piece_bytes)) ||
+      (rc = pipe.make(ctx)))
     return rc;
   uint8_t* h_buf[2] = {(uint8_t*)ctx->pinned, (uint8_t*)ctx->pinned + piece_bytes};
   if ((rc = file.open_for_rows(&why))) return ctx->fail(rc, why);
-  const uint64_t npieces = (np + piece - 1) / piece;
   auto rows_of = [&](uint64_t k) { return std::min(piece, np - k * piece); };
-  // the host's part for piece k: wait for its copy, then pwrite it in slices, one per host thread
-  auto write_piece = [&](uint64_t k) -> int {
-    const int b = (int)(k & 1);
-    if (hipEventSynchronize(pipe.copied[b]) != hipSuccess) return ctx->fail(PCV_E_HIP, "copying PLY rows to the host failed");
-    const uint64_t bytes = rows_of(k) * stride, at = k * piece * stride;
-    const size_t workers = ctx->host_pool.threads.size() + 1;
-    const uint64_t slice = std::max<uint64_t>(4u << 20, (bytes + workers - 1) / workers);
-    const size_t parts = (size_t)((bytes + slice - 1) / slice);
-    std::vector<int> part_rc(parts, PCV_OK);
-    std::vector<std::string> part_why(parts);
-    auto one = [&](size_t p) {
-      const uint64_t lo = p * slice, len = std::min(slice, bytes - lo);
-      part_rc[p] = file.write_at(at + lo, h_buf[b] + lo, len, &part_why[p]);
-    };
-    if (parts == 1) one(0);
-    else ctx->host_pool.run(parts, one);
-    for (size_t p = 0; p < parts; ++p)
-      if (part_rc[p]) return ctx->fail(part_rc[p], part_why[p]);
-    return PCV_OK;
-  };
-  auto run = [&]() -> int {
-    for (uint64_t k = 0; k < npieces; ++k) {
-      const int b = (int)(k & 1);
-      // d_buf[b] was last read by the copy of piece k - 2, which write_piece(k - 2) has waited for; h_buf[b] likewise
-      if (int r = launch_rows(s, dev, c0, c1, p0 + k * piece, rows_of(k), d_buf[b])) return r;
-      PCV_HIP_CHECK(ctx, hipEventRecord(pipe.packed[b], ctx->stream));
-      PCV_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->side, pipe.packed[b], 0));
-      PCV_HIP_CHECK(ctx, hipMemcpyAsync(h_buf[b], d_buf[b], rows_of(k) * stride, hipMemcpyDeviceToHost, ctx->side));
-      PCV_HIP_CHECK(ctx, hipEventRecord(pipe.copied[b], ctx->side));
-      if (k > 0)
-        if (int r = write_piece(k - 1)) return r;
-    }
-    return write_piece(npieces - 1);
-  };
-  rc = run();
+  rc = pcv_run_pieces(
+      ctx, pipe, (np + piece - 1) / piece, [&](uint64_t k, int b) { return launch_rows(s, dev, r.c0, r.c1, r.p0 + k * piece, rows_of(k), d_buf[b]); },
+      [&](uint64_t k) { return rows_of(k) * stride; }, d_buf, h_buf,
+      [&](uint64_t k, int b) -> int {
+        if (hipEventSynchronize(pipe.copied[b]) != hipSuccess) return ctx->fail(PCV_E_HIP, "copying PLY rows to the host failed");
+        const uint64_t at = k * piece * stride;
+        return pcv_write_slices(ctx, rows_of(k) * stride,
+                                [&](uint64_t lo, uint64_t len, std::string* w) { return file.write_at(at + lo, h_buf[b] + lo, len, w); });
+      });
   if (rc != PCV_OK) {
-    (void)hipStreamSynchronize(ctx->stream);  // nothing queued may still write into what is freed here
-    (void)hipStreamSynchronize(ctx->side);
-    (void)hipGetLastError();
     file.abandon();
     return rc;
   }
@@ -424,16 +291,12 @@ int write_ply(const PlySource& s, uint64_t first_segment, uint64_t num_segments,
 
 }  // namespace
 
-// pcv_internal.h: rows [row0, row0 + nrows) of the result's segments [first_segment, first_segment + num_segments) as 27-byte rows
-// (x y z as doubles, then r g b) into d_out on the context's stream, nothing waited for — any row range, for callers that
-// stream a result through a bounded buffer (pcv_terrain.hip). Exactly one of b / q is set.
-int pcv_ply_pack_xyz_rgb(pcv_query_batch* b, pcv_s2_query* q, uint64_t first_segment, uint64_t num_segments, uint64_t row0, uint64_t nrows,
-                         uint8_t* d_out) {
-  const PlySource s = b ? source_of(b) : source_of(q);
+// pcv_result_rows.h
+int pcv_ply_pack_xyz_rgb(const PcvResultSource& s, uint64_t first_segment, uint64_t num_segments, uint64_t row0, uint64_t nrows, uint8_t* d_out) {
   int rc;
-  if ((rc = check_range(s, first_segment, num_segments))) return rc;
-  const uint64_t p0 = s.seg_off[first_segment], p1 = s.seg_off[first_segment + num_segments];
-  if (row0 < p0 || row0 > p1 || nrows > p1 - row0) return s.ctx->fail(PCV_E_INVALID, "row range outside the segments");
+  if ((rc = s.check_range(first_segment, num_segments))) return rc;
+  const auto [p0, np, c0, c1] = s.rows_of_segments(first_segment, num_segments);
+  if (row0 < p0 || row0 > p0 + np || nrows > p0 + np - row0) return s.ctx->fail(PCV_E_INVALID, "row range outside the segments");
   if (nrows == 0) return PCV_OK;
   static const char* const kColor[] = {"color"};
   std::vector<PcvPlyColumn> cols;
@@ -441,7 +304,7 @@ int pcv_ply_pack_xyz_rgb(pcv_query_batch* b, pcv_s2_query* q, uint64_t first_seg
   PlyCols dev{};
   if ((rc = resolve_columns(s, kColor, 1, &cols, &stride, &dev))) return rc;
   if (stride != kPcvXyzRgbRowBytes) return s.ctx->fail(PCV_E_INVALID, "unexpected row layout");
-  return launch_rows(s, dev, s.seg_chunk[first_segment], s.seg_chunk[first_segment + num_segments], row0, nrows, d_out);
+  return launch_rows(s, dev, c0, c1, row0, nrows, d_out);
 }
 
 extern "C" int pcv_query_batch_ply_rows(pcv_query_batch* b, uint64_t first_segment, uint64_t num_segments, const char* const* attributes,

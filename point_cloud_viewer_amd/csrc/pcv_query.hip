@@ -792,13 +792,7 @@ __global__ __launch_bounds__(256) void query_compact_kernel(const ChunkDesc* __r
     uint64_t pos0 = chunk_off[ci] - base;
     if (pos0 >= limit) break;  // (uniform) this chunk and the wave's later ones are past the caller's buffers: offsets only grow
     const ChunkDesc& d = desc[ci];
-    PointsView v{};
-    v.encoded = xyz_blob + d.src;
-    v.enc = d.enc & 15u;
-    v.cube_min[0] = d.cube_min[0];
-    v.cube_min[1] = d.cube_min[1];
-    v.cube_min[2] = d.cube_min[2];
-    v.cube_edge = d.cube_edge;
+    const PointsView v = points_view_of(d, xyz_blob);
     const uint8_t* kp = keep + d.keep_off;
     for (uint32_t q0 = 0; q0 < d.cnt; q0 += 64) {
       const uint32_t q = q0 + lane;

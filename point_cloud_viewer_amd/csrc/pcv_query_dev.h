@@ -211,6 +211,17 @@ struct ChunkDesc {
 };
 static_assert(sizeof(ChunkDesc) == 64, "one descriptor per s_load_dwordx16");
 constexpr uint32_t kBatchShapeBits = 24;  // ChunkDesc::enc = encoding | kind << 4 | shape << 8
+// the chunk's encoded points as load_point takes them
+__device__ __forceinline__ PointsView points_view_of(const ChunkDesc& d, const uint8_t* xyz_blob) {
+  PointsView v{};
+  v.encoded = xyz_blob + d.src;
+  v.enc = d.enc & 15u;
+  v.cube_min[0] = d.cube_min[0];
+  v.cube_min[1] = d.cube_min[1];
+  v.cube_min[2] = d.cube_min[2];
+  v.cube_edge = d.cube_edge;
+  return v;
+}
 
 struct pcv_query_batch {
   pcv_ctx* ctx = nullptr;

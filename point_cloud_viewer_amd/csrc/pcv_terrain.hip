@@ -23,6 +23,7 @@
 
 #include "pcv_internal.h"
 #include "pcv_query_dev.h"
+#include "pcv_result_rows.h"
 #include "pcv_s2_obj.h"
 #include "pcv_s2_query_dev.h"
 #include "pcv_terrain_dev.h"
@@ -523,7 +524,7 @@ extern "C" int pcv_terrain_add_query_batch(pcv_terrain* t, pcv_query_batch* b, u
   if (int rc = usable(t, false)) return rc;
   if (!b || b->ctx != t->ctx) return t->ctx->fail(PCV_E_INVALID, "terrain: the query batch is null or of another context");
   return add_segments(t, b->seg_off.data(), b->nseg, first_segment, num_segments, [&](uint64_t row0, uint64_t rows, uint8_t* out) {
-    return pcv_ply_pack_xyz_rgb(b, nullptr, first_segment, num_segments, row0, rows, out);
+    return pcv_ply_pack_xyz_rgb(source_of(b), first_segment, num_segments, row0, rows, out);
   });
 }
 
@@ -532,7 +533,7 @@ extern "C" int pcv_terrain_add_s2_query(pcv_terrain* t, pcv_s2_query* q, uint64_
   if (int rc = usable(t, false)) return rc;
   if (!q || !q->cloud || q->cloud->ctx != t->ctx) return t->ctx->fail(PCV_E_INVALID, "terrain: the S2 query is null or of another context");
   return add_segments(t, q->seg_offset.data(), q->nseg, first_segment, num_segments, [&](uint64_t row0, uint64_t rows, uint8_t* out) {
-    return pcv_ply_pack_xyz_rgb(nullptr, q, first_segment, num_segments, row0, rows, out);
+    return pcv_ply_pack_xyz_rgb(source_of(q), first_segment, num_segments, row0, rows, out);
   });
 }
 

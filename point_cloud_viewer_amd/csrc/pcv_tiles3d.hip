@@ -12,6 +12,8 @@
 // the alignment (mod 16) the destination has, and the image leaves as aligned 16-byte vectors with a bytewise head and tail.
 // Colour and intensity are the same re-alignment without arithmetic. The workgroup of a file's first item also places the
 // header and JSON bytes and writes every padding byte: nothing of a file is left unwritten. All blob offsets are u64.
+// The store of an image is pcv_rows_dev.h's, the piece pipeline pcv_result_rows.h's; the staging, the conversion
+// and what a piece of whole files needs — an upload table per buffer, one host job per file — are this file's.
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -23,6 +25,8 @@
 #include <vector>
 
 #include "pcv_internal.h"
+#include "pcv_result_rows.h"
+#include "pcv_rows_dev.h"
 #include "pcv_tiles3d_dev.h"
 #include "pcv_tiles3d_files.h"
 
@@ -77,32 +81,19 @@ __device__ __forceinline__ uint32_t stage(const uint8_t* __restrict__ blob, uint
   return phase;
 }
 
-// `bytes` bytes whose byte 0 stands at img[phase], phase = (address of dst) % 16 and img 16-byte aligned, to dst: the interior
-// as aligned 16-byte vectors, its unaligned head and tail bytewise (store_image of pcv_ply_rows.hip, over a region of its own).
-__device__ __forceinline__ void store_image(const uint8_t* img, uint8_t* __restrict__ dst, uint32_t phase, uint32_t bytes) {
-  const uint32_t head = min(bytes, (16u - phase) & 15u);
-  for (uint32_t j = threadIdx.x; j < head; j += 256u) dst[j] = img[phase + j];
-  const uint32_t nvec = (bytes - head) >> 4;
-  uint4* __restrict__ gv = reinterpret_cast<uint4*>(dst + head);
-  const uint4* lv = reinterpret_cast<const uint4*>(img + phase + head);  // phase + head is 0 or 16
-  for (uint32_t v = threadIdx.x; v < nvec; v += 256u) gv[v] = lv[v];
-  const uint32_t done = head + (nvec << 4);
-  for (uint32_t j = done + threadIdx.x; j < bytes; j += 256u) dst[j] = img[phase + j];
-}
-
 // `bytes` bytes of a blob to dst as they are: staged, moved to the destination's phase, stored. Ends with a barrier.
 __device__ __forceinline__ void realign(const uint8_t* __restrict__ blob, uint64_t blob_bytes, uint64_t off, uint32_t bytes, uint8_t* __restrict__ dst) {
   const uint32_t sphase = stage(blob, blob_bytes, off, bytes);
   const uint32_t dphase = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u);
   __syncthreads();
   if (sphase == dphase) {  // (uniform) the staged bytes are the image
-    store_image(t3d_lds, dst, dphase, bytes);
+    pcv_store_image(t3d_lds, dst, dphase, bytes);
   } else {
     const uint8_t* s = t3d_lds + sphase;
     uint8_t* img = t3d_lds + kT3dSrcBytes;
     for (uint32_t j = threadIdx.x; j < bytes; j += 256u) img[dphase + j] = s[j];
     __syncthreads();
-    store_image(img, dst, dphase, bytes);
+    pcv_store_image(img, dst, dphase, bytes);
   }
   __syncthreads();
 }
@@ -189,7 +180,7 @@ __global__ __launch_bounds__(256) void tiles3d_pack_kernel(const T3dFile* __rest
     default: convert<PCV_ENC_FLOAT64>(f, sphase, dphase, m); break;
   }
   __syncthreads();
-  store_image(t3d_lds + kT3dSrcBytes, pos, dphase, m * dstride);
+  pcv_store_image(t3d_lds + kT3dSrcBytes, pos, dphase, m * dstride);
   __syncthreads();
   // colours, after the file's last position without a gap; intensity
   realign(blobs.rgb, blobs.rgb_bytes, (f.src_pt + p0) * 3u, m * 3u, file + f.fbin_off + (uint64_t)f.n * dstride + (uint64_t)p0 * 3u);
@@ -299,22 +290,10 @@ bool write_file_at(int dirfd, const std::string& name, const uint8_t* data, uint
   return ::close(fd) == 0 && ok;
 }
 
-struct T3dPipe {
-  hipEvent_t packed[2] = {}, copied[2] = {};
-  int dirfd = -1;
-  int make(pcv_ctx* ctx) {
-    for (int k = 0; k < 2; ++k) {
-      PCV_HIP_CHECK(ctx, hipEventCreateWithFlags(&packed[k], hipEventDisableTiming));
-      PCV_HIP_CHECK(ctx, hipEventCreateWithFlags(&copied[k], hipEventDisableTiming));
-    }
-    return PCV_OK;
-  }
-  ~T3dPipe() {
-    for (int k = 0; k < 2; ++k) {
-      if (packed[k]) (void)hipEventDestroy(packed[k]);
-      if (copied[k]) (void)hipEventDestroy(copied[k]);
-    }
-    if (dirfd >= 0) ::close(dirfd);
+struct T3dDir {  // the output directory, open while its files are written
+  int fd = -1;
+  ~T3dDir() {
+    if (fd >= 0) ::close(fd);
   }
 };
 
@@ -408,9 +387,8 @@ extern "C" int pcv_tiles3d_tileset_json(const pcv_tiles3d* t, char* buf, uint64_
   return PCV_OK;
 }
 
-// The pipeline of pcv_tiles3d_write_dir, the one of pcv_*_write_ply over whole files: piece k + 1 is packed on the context's
-// stream while piece k crosses to its pinned block on the side stream and piece k - 1 is written by the host threads, one file
-// per job. Device and pinned memory: two buffers of the largest piece, two upload blocks of the largest table.
+// pcv_tiles3d_write_dir: whole files through the piece pipeline, one host job per file. Device and pinned memory: two buffers
+// of the largest piece, two upload blocks of the largest table.
 extern "C" int pcv_tiles3d_write_dir(pcv_tiles3d* t, const char* directory) {
   if (!t) return PCV_E_INVALID;
   pcv_ctx* ctx = t->ctx;
@@ -421,9 +399,9 @@ extern "C" int pcv_tiles3d_write_dir(pcv_tiles3d* t, const char* directory) {
   ::mkdir(dir.c_str(), 0777);  // it may be there already
   struct stat st;
   if (stat(dir.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) return ctx->fail(PCV_E_IO, "cannot create directory " + dir);
-  T3dPipe pipe;
-  pipe.dirfd = open(dir.c_str(), O_RDONLY | O_DIRECTORY | O_CLOEXEC);
-  if (pipe.dirfd < 0) return ctx->fail(PCV_E_IO, "cannot open directory " + dir);
+  T3dDir d;
+  d.fd = open(dir.c_str(), O_RDONLY | O_DIRECTORY | O_CLOEXEC);
+  if (d.fd < 0) return ctx->fail(PCV_E_IO, "cannot open directory " + dir);
   PCV_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const uint64_t chunk = t->params.chunk_bytes ? t->params.chunk_bytes : PCV_TILES3D_DEFAULT_CHUNK_BYTES;
   const std::vector<uint64_t> first = pcv_tiles3d_pieces(t->file_bytes, chunk);
@@ -439,53 +417,38 @@ extern "C" int pcv_tiles3d_write_dir(pcv_tiles3d* t, const char* directory) {
   const uint64_t buf_bytes = (most + 255) & ~255ull;
   PcvScratch sc(ctx);
   uint8_t *d_buf[2], *d_up[2];
+  PcvPiecePipe pipe;
   if ((rc = sc.get(&d_buf[0], buf_bytes)) || (rc = sc.get(&d_buf[1], buf_bytes)) || (rc = sc.get(&d_up[0], most_up)) || (rc = sc.get(&d_up[1], most_up)) ||
       (rc = ctx->pinned_reserve(2 * buf_bytes)) || (rc = pipe.make(ctx)) || (rc = ctx->ring_ensure()))  // the ring's host threads write the files
     return rc;
   uint8_t* h_buf[2] = {(uint8_t*)ctx->pinned, (uint8_t*)ctx->pinned + buf_bytes};
-  T3dUpload up[2];
-  // the host's part for piece k: wait for its copy, then one job per file
-  auto write_piece = [&](uint64_t k) -> int {
-    const int b = (int)(k & 1);
-    if (hipEventSynchronize(pipe.copied[b]) != hipSuccess) return ctx->fail(PCV_E_HIP, "copying tile files to the host failed");
-    const uint64_t f0 = first[k], nf = first[k + 1] - f0;
-    std::vector<uint64_t> at(nf + 1, 0);
-    for (uint64_t i = 0; i < nf; ++i) at[i + 1] = at[i] + t->file_bytes[f0 + i];
-    std::vector<uint8_t> bad(nf, 0);
-    ctx->host_pool.run((size_t)nf, [&](size_t i) {
-      const std::string name = pcv_tiles3d_node_name(t->tree->nodes[t->node_of[f0 + i]]) + ".pnts";
-      if (!write_file_at(pipe.dirfd, name, h_buf[b] + at[i], t->file_bytes[f0 + i])) bad[i] = 1;
-    });
-    for (uint64_t i = 0; i < nf; ++i)
-      if (bad[i]) return ctx->fail(PCV_E_IO, "cannot write " + dir + "/" + pcv_tiles3d_node_name(t->tree->nodes[t->node_of[f0 + i]]) + ".pnts");
-    return PCV_OK;
-  };
-  auto run = [&]() -> int {
-    for (uint64_t k = 0; k < npieces; ++k) {
-      const int b = (int)(k & 1);
-      // d_buf[b], d_up[b] and up[b] were last used by piece k - 2, whose copy write_piece(k - 2) has waited for
-      if (int r = make_upload(t, first[k], first[k + 1] - first[k], &up[b])) return r;
-      if (int r = launch_piece(t, up[b], d_up[b], d_buf[b])) return r;
-      PCV_HIP_CHECK(ctx, hipEventRecord(pipe.packed[b], ctx->stream));
-      PCV_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->side, pipe.packed[b], 0));
-      PCV_HIP_CHECK(ctx, hipMemcpyAsync(h_buf[b], d_buf[b], up[b].piece_bytes, hipMemcpyDeviceToHost, ctx->side));
-      PCV_HIP_CHECK(ctx, hipEventRecord(pipe.copied[b], ctx->side));
-      if (k > 0)
-        if (int r = write_piece(k - 1)) return r;
-    }
-    return write_piece(npieces - 1);
-  };
-  rc = run();
-  const bool drained = hipStreamSynchronize(ctx->stream) == hipSuccess && hipStreamSynchronize(ctx->side) == hipSuccess;  // nothing queued may
-  if (rc) {                                                                                                              // still use what is freed
-    (void)hipGetLastError();
-    return rc;
-  }
-  if (!drained) return ctx->fail(PCV_E_HIP, "packing the tile files failed");
+  T3dUpload up[2];  // with d_up: one per buffer, free again when the buffer is
+  rc = pcv_run_pieces(
+      ctx, pipe, npieces,
+      [&](uint64_t k, int b) -> int {
+        if (int r = make_upload(t, first[k], first[k + 1] - first[k], &up[b])) return r;
+        return launch_piece(t, up[b], d_up[b], d_buf[b]);
+      },
+      [&](uint64_t k) { return up[k & 1].piece_bytes; }, d_buf, h_buf,
+      [&](uint64_t k, int b) -> int {
+        if (hipEventSynchronize(pipe.copied[b]) != hipSuccess) return ctx->fail(PCV_E_HIP, "copying tile files to the host failed");
+        const uint64_t f0 = first[k], nf = first[k + 1] - f0;
+        std::vector<uint64_t> at(nf + 1, 0);
+        for (uint64_t i = 0; i < nf; ++i) at[i + 1] = at[i] + t->file_bytes[f0 + i];
+        std::vector<uint8_t> bad(nf, 0);
+        ctx->host_pool.run((size_t)nf, [&](size_t i) {
+          const std::string name = pcv_tiles3d_node_name(t->tree->nodes[t->node_of[f0 + i]]) + ".pnts";
+          if (!write_file_at(d.fd, name, h_buf[b] + at[i], t->file_bytes[f0 + i])) bad[i] = 1;
+        });
+        for (uint64_t i = 0; i < nf; ++i)
+          if (bad[i]) return ctx->fail(PCV_E_IO, "cannot write " + dir + "/" + pcv_tiles3d_node_name(t->tree->nodes[t->node_of[f0 + i]]) + ".pnts");
+        return PCV_OK;
+      });
+  if (rc) return rc;
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->side) != hipSuccess) return ctx->fail(PCV_E_HIP, "packing the tile files failed");
   ctx->prof_resolve();
   // tileset.json last: a directory that has it is complete
-  if (!write_file_at(pipe.dirfd, "tileset.json", (const uint8_t*)t->json.data(), t->json.size()))
-    return ctx->fail(PCV_E_IO, "cannot write " + dir + "/tileset.json");
+  if (!write_file_at(d.fd, "tileset.json", (const uint8_t*)t->json.data(), t->json.size())) return ctx->fail(PCV_E_IO, "cannot write " + dir + "/tileset.json");
   return PCV_OK;
 }
 

@@ -383,13 +383,7 @@ __global__ __launch_bounds__(256) void xray_bin_kernel(XrayBinArgs a, uint32_t* 
       if (created < 0) continue;  // wave-uniform: no octree's query kept anything for this tile
       const XrayTileDev t = a.tiles[created];
       const uint32_t bbase = ((uint32_t)created - a.created0) * a.nblocks;
-      PointsView v{};
-      v.encoded = (const uint8_t*)(tr.xyz + d.src);
-      v.enc = d.enc & 15u;
-      v.cube_min[0] = d.cube_min[0];
-      v.cube_min[1] = d.cube_min[1];
-      v.cube_min[2] = d.cube_min[2];
-      v.cube_edge = d.cube_edge;
+      const PointsView v = points_view_of(d, (const uint8_t*)tr.xyz);
       const XrayNodeSource src{(const uint8_t*)tr.rgb, (const float*)tr.inten, d, v, tr.keep + d.keep_off};
       xray_bin_chunk<SCATTER>(a, src, d.cnt, created, t, bbase, lane, counts, offsets, rec, recz, recb);
     }
