@@ -88,9 +88,11 @@ def top_layout(l1, l2, split_mask):
 
 def top_nodes(layout, encodings, has_intensity):
     """Finished root + level-1 nodes described by a layout: [(name, level, digit, num_points, encoding, xyz_off, rgb_off,
-    int_off)] and the total byte size of the buffer that holds their xyz | rgb | intensity bytes."""
+    int_off)] and the total byte size of the buffer that holds their xyz | rgb | intensity bytes. A cloud without points has no
+    node at all, the root included (like the one-GPU build of an empty cloud): gather() is empty and write_dir writes meta.pb
+    alone."""
     bpc = {1: 1, 2: 2, 3: 4, 4: 8}
-    specs = [("r", 0, 0, layout["root_points"])]
+    specs = [("r", 0, 0, layout["root_points"])] if layout["root_points"] > 0 else []
     for c in range(8):
         s = layout["l1_stream"][c]
         if s > 0:

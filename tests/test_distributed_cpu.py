@@ -12,6 +12,8 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+from host_backend import HostBackend, _HostPending, _HostTree  # noqa: F401 - shared with tests/test_sharded_fuzz_cpu.py
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -21,103 +23,6 @@ def _free_port():
     p = s.getsockname()[1]
     s.close()
     return p
-
-
-class _Node:
-    def __init__(self, level, id_high, id_low, num_points=0, encoding=1):
-        self.level, self.id_high, self.id_low, self.num_points, self.encoding = level, id_high, id_low, num_points, encoding
-
-
-class _HostTree:
-    """Stand-in for OctreeResult on top of an oracle tree (nodes in breadth-first order like the library's)."""
-
-    def __init__(self, oct_):
-        self.oct = oct_
-        self.names = sorted(oct_.nodes, key=lambda k: (oct_.nodes[k]["level"], oct_.nodes[k]["id"]))
-        self.num_nodes = len(self.names)
-
-    def node(self, i):
-        nd = self.oct.nodes[self.names[i]]
-        return _Node(nd["level"], nd["id"][0], nd["id"][1], nd["num_points"], nd["encoding"])
-
-    def copy_node_into(self, i, which, dst):
-        data = self.oct.nodes[self.names[i]][("xyz", "rgb", "intensity")[which]]
-        dst.copy_(torch.frombuffer(bytearray(data), dtype=torch.uint8))
-
-    def to_dict(self):
-        return {k: dict(num_points=v["num_points"], encoding=v["encoding"], xyz=v["xyz"], rgb=v["rgb"],
-                        intensity=v["intensity"], id=v["id"], level=v["level"]) for k, v in self.oct.nodes.items()}
-
-    def stage_ms(self):
-        return {}
-
-
-class _HostPending:
-    def __init__(self, O, cap, args, force_mask, routed=None):
-        self.O, self.cap, self.args, self.force_mask, self.routed = O, cap, args, force_mask, routed
-
-    def _run(self, layout):
-        resolution, bbox, x, y, z, rgb, intensity = self.args
-        with self.O.max_points_per_node(self.cap):
-            if self.routed is not None:
-                packed = self.routed["oct_rgb"].numpy().view(np.uint32)
-                ro = [(packed & 7).astype(np.uint8)] + [self.routed[k].numpy().view(np.uint32) for k in ("cx", "cy", "cz")]
-                rgb = np.stack([(packed >> 8) & 255, (packed >> 16) & 255, packed >> 24], axis=1).astype(np.uint8)
-                return self.O.build_closed_shard(resolution, bbox.min, bbox.max, None, None, None, rgb,
-                                                 None if intensity is None else intensity.numpy(),
-                                                 force_mask=self.force_mask, layout=layout, routed=ro)
-            return self.O.build_closed_shard(resolution, bbox.min, bbox.max, x.numpy(), y.numpy(), z.numpy(), rgb.numpy(),
-                                             None if intensity is None else intensity.numpy(),
-                                             force_mask=self.force_mask, layout=layout)
-
-    def top_streams(self):
-        _, s = self._run(None)
-        return s[:8].astype(np.int64), s[8:72].astype(np.int64), int(s[72])
-
-    def finish(self, layout):
-        flat = [layout["root_points"]] + list(layout["l1_stream"]) + list(layout["l1_offset"]) + list(layout["l2_offset"])
-        t, _ = self._run(np.array(flat, dtype=np.uint64))
-        return _HostTree(t)
-
-
-class HostBackend:
-    def __init__(self, O, cap):
-        self.O, self.cap = O, cap
-
-    def aabb(self, x, y, z):
-        return self.O.aabb(x.numpy(), y.numpy(), z.numpy())
-
-    def level_table(self, resolution, bbox):
-        return self.O.level_table(bbox.min, bbox.max, resolution)
-
-    def buckets(self, resolution, bbox, x, y, z, rgb=None, with_state=False):
-        keys = self.O.chain_keys64(bbox.min, bbox.max, resolution, 2, x.numpy(), y.numpy(), z.numpy())
-        bucket = torch.from_numpy((keys >> np.uint64(57)).astype(np.int64) & 63)
-        counts = np.bincount(bucket.numpy(), minlength=64).astype(np.int64)
-        if not with_state:
-            return bucket, counts
-        o, cx, cy, cz = self.O.chain_state1(bbox.min, bbox.max, resolution, x.numpy(), y.numpy(), z.numpy())
-        c = rgb.numpy().astype(np.uint32)
-        packed = o.astype(np.uint32) | (c[:, 0] << 8) | (c[:, 1] << 16) | (c[:, 2] << 24)
-        state = dict(cx=torch.from_numpy(cx.view(np.int32)), cy=torch.from_numpy(cy.view(np.int32)),
-                     cz=torch.from_numpy(cz.view(np.int32)), oct_rgb=torch.from_numpy(packed.view(np.int32)))
-        return bucket, counts, state
-
-    def partition(self, bucket, rank_of_bucket, planes, dsts):
-        owner = torch.from_numpy(np.asarray(rank_of_bucket, dtype=np.int64))[bucket]
-        for k, row in enumerate(dsts):
-            sel = owner == k  # boolean-mask selection keeps input order
-            for src, dst in zip(planes, row):
-                dst.copy_(src[sel])
-
-    def build_begin(self, resolution, bbox, x, y, z, rgb, intensity, max_points_per_node, force_split_level1):
-        assert max_points_per_node == self.cap
-        return _HostPending(self.O, self.cap, (resolution, bbox, x, y, z, rgb, intensity), force_split_level1)
-
-    def build_begin_routed(self, resolution, bbox, state, intensity, max_points_per_node, force_split_level1):
-        assert max_points_per_node == self.cap
-        return _HostPending(self.O, self.cap, (resolution, bbox, None, None, None, None, intensity), force_split_level1,
-                            routed=state)
 
 
 def _worker(rank, world, port, n, cap, with_intensity, out_path, compress=True, shard_mode="buckets"):
